@@ -14,9 +14,10 @@ OUT=gpurun_out
 export TMPDIR=/tmp
 STEPS=50
 case $CFG in cfg3|cfg4|cfg5) STEPS=20;; esac
-# (--b2b-seconds 0: the untimed back-to-back pass stays at its minimum of 200 launches — the profiler's per-kernel AVERAGE must describe the
-#  timed region's launches, which start from an idle GPU block by block and run ~7 % longer than launches that keep the queue busy)
-BENCH="python3 bench.py --config $CFG --steps $STEPS --warmup 5 --blocks 3 --b2b-seconds 0 --no-cpu-baseline --no-extras $EXTRA"
+# (--b2b-seconds 0: the untimed back-to-back pass stays at its minimum of 200 launches, and --settle-seconds 0: no untimed settle pass — the
+#  profiler's per-kernel AVERAGE must describe the timed region's launches, which start from an idle GPU block by block and run ~7 % longer
+#  than launches that keep the queue busy)
+BENCH="python3 bench.py --full --config $CFG --steps $STEPS --warmup 5 --blocks 3 --b2b-seconds 0 --settle-seconds 0 --no-cpu-baseline --no-extras $EXTRA"
 mkdir -p $OUT
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o $TAG -- $BENCH > $OUT/${TAG}_stats.log 2>&1
 if [ "$MODE" != "stats" ]; then

@@ -611,7 +611,7 @@ def test_multi_device_group_shards_a_batch_through_the_c_abi(n_engines, B):
 
 
 @pytest.mark.parametrize("config,batch", [("headline", 512), ("cfg4", 1024)])
-def test_bench_two_ranks_on_one_gpu(config, batch):
+def test_bench_two_ranks_on_one_gpu(config, batch, tmp_path):
     """The N > 1 path of bench.py on the 1-GPU box: `python bench.py --gpus 2` starts its two rank processes itself
     (fresh children of a child that never touches the GPU; FPE_BENCH_SHARE_GPU=1 puts both on cuda:0 with gloo
     collectives — RCCL refuses two ranks on one device).  The JSON must name the 2-rank exchange, carry the exchange
@@ -626,7 +626,8 @@ def test_bench_two_ranks_on_one_gpu(config, batch):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", config, "--batch", str(batch),
-                        "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-cpu-baseline", "--gather-every", "2"],
+                        "--steps", "3", "--warmup", "1", "--blocks", "2", "--full", "--no-cpu-baseline", "--gather-every", "2",
+                        "--dump-outputs", str(tmp_path)],
                        env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -640,6 +641,61 @@ def test_bench_two_ranks_on_one_gpu(config, batch):
     assert line["config"]["exchange_alt"]["gather_every"] == 1
     assert line["config"]["step_bound_at_this_n"]["by_direct_links"] in ("plan", "exchange")
     assert line["value"] > 0 and "roofline" in line
+    # rank 0 dumps its own shard and the records the all-gather delivered to it: every rank's, its own among them
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    n = line["config"]["n_cycles"]
+    assert got["gathered_selected_row"].shape == (2, batch, n, 4) and got["nominal_row"].shape == (batch, n, 4)
+    for f in ("row", "col", "z", "valid", "source", "foot_id", "gait_cycle_id"):
+        assert np.array_equal(got[f"gathered_selected_{f}"][0], got[f"nominal_{f}"], equal_nan=True), f
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_the_last_step_computed(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline line only (K timed steps, `ms_per_step`; no side measurement,
+    no oracle check), and --dump-outputs DIR writes the last timed step's products as float32 / float64 arrays (<= 64 MB) that,
+    read back into the engine's records, equal the oracle's plan of the same seeded poses."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "FPE_BENCH_SHARE_GPU", "FPE_BENCH_FORCE_NCCL"):
+        env.pop(k, None)
+    B = 512
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "headline", "--batch", str(B),
+                        "--steps", "9", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 9 and line["warmup"] == 2 and line["unit"] == "footholds/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(line["config"]["footholds_per_step"] / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["config"]["verified"] is None
+    for k in ("roofline", "cpu_baseline", "ms_per_step_blocks", "value_incl_d2h", "service_latency_us", "opt_track"):
+        assert k not in line, k
+    files = list(tmp_path.iterdir())
+    assert sum(p.stat().st_size for p in files) <= 64 * 10**6
+    got = {p.stem: np.load(p) for p in files}
+    assert "pose_index" not in got and all(a.dtype in (np.float32, np.float64) for a in got.values())
+
+    def records(name, dtype):
+        rec = np.zeros(got[f"{name}_row"].shape, dtype)
+        for f in dtype.names:
+            if f != "pad":
+                rec[f] = got[f"{name}_{f}"]
+        return rec
+
+    eng = {"nominal": records("nominal", _capi.FOOTHOLD_DTYPE), "centroid": records("centroid", _capi.CENTROID_DTYPE),
+           "selected": records("selected", _capi.SELECTED_DTYPE), "default": got["default"], "cycle_ok": got["cycle_ok"].astype(np.uint8),
+           "stance": got["stance"], "pose_status": got["pose_status"].astype(np.uint8)}
+    trav, elev, res, poses, n_cycles, _ = synth.make_config("headline", B=B)
+    assert eng["nominal"].shape == (B, n_cycles, 4)
+    omap = fpo.OracleMap(trav, elev, res)
+    op, opo = util.to_oracle_params(_capi.params_yaml()), util.to_oracle_poses(poses)
+    ora = omap.plan(op, opo, n_cycles, threads=4)
+    ora["pose_status"] = omap.pose_status(op, opo)
+    util.assert_plan_equal(eng, ora)
 
 
 @pytest.mark.parametrize("record", ["packed", "selected"])
@@ -658,14 +714,15 @@ def test_bench_runs_its_exchange_through_rccl_in_a_one_rank_group(record):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "FPE_BENCH_SHARE_GPU"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "headline", "--batch", "1024",
-                        "--steps", "7", "--warmup", "2", "--blocks", "1", "--no-cpu-baseline", "--no-extras", "--gather-every", "3", "--exchange-record", record],
+                        "--steps", "7", "--warmup", "2", "--blocks", "1", "--full", "--no-cpu-baseline", "--no-extras", "--gather-every", "3",
+                        "--exchange-record", record],
                        env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
     ex = line["config"]["exchange"]
     assert "backend nccl, 1 rank in the process group" in ex and "collective forced" in ex
     assert ("fpe_selected_packed" in ex) == (record == "packed")
-    assert "one collective per 3 steps" in ex and " 4 collectives issued" in ex  # warm-up (2 steps: 1 flush) + 7 timed steps: 3
+    assert "one collective per 3 steps" in ex and " 4 collectives issued" in ex  # warm-up (2 steps: 1 flush) + the 7 headline steps: 3
     assert line["config"]["verified"] is True and line["n_gpus"] == 1
 
 
