@@ -512,6 +512,33 @@ int fpe_multi_plan_device(fpe_multi_handle h, const fpe_params* params, const fp
 void* fpe_multi_stream(fpe_multi_handle h, int32_t k); /* the group's own stream of device k (a hipStream_t) */
 int fpe_multi_synchronize(fpe_multi_handle h);          /* waits for the group's own streams */
 
+/* ---- dense foothold map: the reference's foot-disc functions at EVERY cell centre of a region -----------------
+ * For cell (i, j) of the current snapshot (canonical indices: row-major, start index (0,0), rows span x) with centre
+ * p = getPosition(i, j) and disc CircleIterator(map, p, footRadius) — clipped at the map edge, f64 membership test:
+ *   FPE_FMAP_DEFAULT_OK   checkDefaultFoothold(p) (cpp:2039-2082, defaultFootholdThreshold): the disc is non-empty and no
+ *                         FINITE cell of it is below the threshold (non-finite cells pass);
+ *   FPE_FMAP_CANDIDATE_OK checkCirclePolygonFoothold(p) (cpp:2117-2163, candidateFootholdThreshold) with a polygon that
+ *                         holds every cell: the spiral candidate test of fpe_search_legs / fpe_plan;
+ *   FPE_FMAP_UNKNOWN      build-defined: some in-map cell of the disc has non-finite traversability;
+ *   height                getFootholdMeanHeight(p, footRadius, h) (cpp:2520-2554), bit for bit.
+ * Discs use the host-proved offset table where it holds and the literal walk elsewhere, as the plan kernels do
+ * (fpe_set_tuning "literal_discs" 1 forces the walk).  FPE_E_UNSUPPORTED when the literal walk is needed and
+ * ceil(footRadius / resolution) > 32.  Snapshot semantics of fpe_plan; the threshold pair's bit planes are shared with
+ * the plan calls.  The host form is synchronous (pinned destinations are written by DMA); the device form is
+ * asynchronous on `stream` and waits GPU-side for the snapshot's upload. */
+#define FPE_FMAP_DEFAULT_OK 1u
+#define FPE_FMAP_CANDIDATE_OK 2u
+#define FPE_FMAP_UNKNOWN 4u
+typedef struct fpe_foothold_map_out {
+    uint8_t* flags; /* [n_rows * n_cols] FPE_FMAP_* bits, or NULL */
+    float* height;  /* [n_rows * n_cols] foot-disc mean height, or NULL */
+} fpe_foothold_map_out;
+/* roi = {row0, col0, n_rows, n_cols} in canonical indices, inside the map; NULL = the whole map.
+ * Output element (r, c) = cell (row0 + r, col0 + c), row-major. */
+int fpe_foothold_map(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_foothold_map_out* out);
+int fpe_foothold_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4],
+                            const fpe_foothold_map_out* d_out, void* stream);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

@@ -177,6 +177,14 @@ class FilterParams(C.Structure):
     ]
 
 
+FMAP_DEFAULT_OK, FMAP_CANDIDATE_OK, FMAP_UNKNOWN = 1, 2, 4  # FPE_FMAP_* bits of fpe_foothold_map_out.flags
+
+
+class FootholdMapOut(C.Structure):
+    """fpe_foothold_map_out: products of a dense foothold-map call (either pointer may be NULL)."""
+    _fields_ = [("flags", C.c_void_p), ("height", C.c_void_p)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the ctypes structures below mirror that layout
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -225,6 +233,8 @@ EXPORTED_SYMBOLS = [
     "fpe_multi_plan_device",
     "fpe_multi_stream",
     "fpe_multi_synchronize",
+    "fpe_foothold_map",
+    "fpe_foothold_map_device",
     "fpe_spiral_offsets",
     "fpe_tile_halfwidth",
     "fpe_algorithmic_bytes_per_foothold",
@@ -307,6 +317,8 @@ def lib():
     L.fpe_multi_stream.restype = vp
     L.fpe_multi_stream.argtypes = [vp, i32]
     L.fpe_multi_synchronize.argtypes = [vp]
+    L.fpe_foothold_map.argtypes = [vp, vp, vp, C.POINTER(FootholdMapOut)]
+    L.fpe_foothold_map_device.argtypes = [vp, vp, vp, C.POINTER(FootholdMapOut), vp]
     L.fpe_spiral_offsets.argtypes = [i32, vp, i32]
     L.fpe_tile_halfwidth.argtypes = [f32, f32, f64]
     L.fpe_algorithmic_bytes_per_foothold.restype = f64

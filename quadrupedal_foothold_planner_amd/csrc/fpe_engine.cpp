@@ -48,6 +48,13 @@ hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts&
 // opt track (fpe_opt.hpp part of fpe_kernels.hip)
 hipError_t launch_opt_track(const DevMap& m, const PlanConsts& pc, const OptConsts& oc, const fpe_pose* d_poses, int B, int nCycles,
                             const uint8_t* d_cycleOk, const fpe_opt_out& d_out, hipStream_t stream, uint32_t* doneFlag = nullptr, uint32_t doneValue = 0);
+// dense foothold map (fpe_footmap.hpp part of fpe_kernels.hip)
+struct FootmapRoi {
+    int row0, col0, nr, nc;
+};
+int foothold_map_supported(const PlanConsts& pc, const MapGeom& g);
+hipError_t launch_foothold_map(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const FootmapRoi& roi, uint8_t* d_flags,
+                               float* d_height, hipStream_t stream);
 }  // namespace fpe
 
 namespace {
@@ -491,6 +498,37 @@ int build_mask(MapSnapshot& snap, float thrD, float thrC, hipStream_t stream, bo
     return FPE_OK;
 }
 
+// The snapshot's bit planes for a threshold pair into cp.mask / cp.bits, `stream` ordered after their build.  A pair this snapshot
+// has not been planned with (the upload pre-builds the pairs of the previous snapshot) is built here on `stream`, into fresh memory
+// when no clean pooled buffer is free (a call never synchronises the device for a recycled buffer); a fifth pair evicts the least
+// recently used set (calls in flight keep theirs alive).
+int acquire_mask(MapSnapshot& snap, float thrD, float thrC, hipStream_t stream, CallPlan& cp) {
+    std::lock_guard<std::mutex> lk(snap.mu);
+    std::shared_ptr<MaskSet> found;
+    for (auto& ms : snap.masks)
+        if (std::memcmp(&ms->thrD, &thrD, 4) == 0 && std::memcmp(&ms->thrC, &thrC, 4) == 0) found = ms;
+    if (!found) {
+        const int rc = build_mask(snap, thrD, thrC, stream, true, found);
+        if (rc != FPE_OK) return rc;
+        if (snap.masks.size() >= 4) {
+            size_t lru = 0;
+            for (size_t k = 1; k < snap.masks.size(); ++k)
+                if (snap.masks[k]->lastUse.load() < snap.masks[lru]->lastUse.load()) lru = k;
+            if (snap.asyncUsed.load(std::memory_order_acquire)) snap.masks[lru]->asyncUsed.store(true);
+            snap.masks.erase(snap.masks.begin() + static_cast<long>(lru));
+        }
+        snap.masks.push_back(found);
+    }
+    found->lastUse.store(++snap.useClock);
+    cp.mask = found;
+    cp.bits = fpe::BitMap{reinterpret_cast<const uint4*>(found->d_words), found->strideW, found->nw};
+    if (!found->readyDone.load(std::memory_order_acquire)) {
+        if (hipEventQuery(found->ready) == hipSuccess) found->readyDone.store(true, std::memory_order_release);
+        else FPE_HIP(hipStreamWaitEvent(stream, found->ready, 0));
+    }
+    return FPE_OK;
+}
+
 int prepare_call(fpe_engine* h, const fpe_params* params, float maxRadius, CallPlan& cp, hipStream_t stream, bool wantBits) {
     if (!h || !params) return fail(FPE_E_INVALID_ARG, "null handle or params");
     int rc = fpe::validate_params(*params);
@@ -517,37 +555,45 @@ int prepare_call(fpe_engine* h, const fpe_params* params, float maxRadius, CallP
     FPE_HIP(hipSetDevice(h->device));
     FPE_HIP(snap.wait_ready(stream));
     cp.useBits = wantBits && fpe::bits_supported(pc, snap.g);
-    if (cp.useBits) {
-        std::lock_guard<std::mutex> lk(snap.mu);
-        std::shared_ptr<MaskSet> found;
-        for (auto& ms : snap.masks)
-            if (std::memcmp(&ms->thrD, &pc.thrDefault, 4) == 0 && std::memcmp(&ms->thrC, &pc.thrCandidate, 4) == 0) found = ms;
-        if (!found) {
-            // a pair this snapshot has not been planned with (the upload pre-builds the pairs of the previous snapshot).
-            // cleanOnly: a plan never synchronises the device for a recycled buffer — it allocates instead.
-            rc = build_mask(snap, pc.thrDefault, pc.thrCandidate, stream, true, found);
-            if (rc != FPE_OK) return rc;
-            if (snap.masks.size() >= 4) {  // least recently used set out (calls in flight keep theirs alive)
-                size_t lru = 0;
-                for (size_t k = 1; k < snap.masks.size(); ++k)
-                    if (snap.masks[k]->lastUse.load() < snap.masks[lru]->lastUse.load()) lru = k;
-                if (snap.asyncUsed.load(std::memory_order_acquire)) snap.masks[lru]->asyncUsed.store(true);
-                snap.masks.erase(snap.masks.begin() + static_cast<long>(lru));
-            }
-            snap.masks.push_back(found);
-        }
-        found->lastUse.store(++snap.useClock);
-        cp.mask = found;
-        cp.bits = fpe::BitMap{reinterpret_cast<const uint4*>(found->d_words), found->strideW, found->nw};
-        if (!found->readyDone.load(std::memory_order_acquire)) {
-            if (hipEventQuery(found->ready) == hipSuccess) found->readyDone.store(true, std::memory_order_release);
-            else FPE_HIP(hipStreamWaitEvent(stream, found->ready, 0));
-        }
-    }
+    if (cp.useBits) return acquire_mask(snap, pc.thrDefault, pc.thrCandidate, stream, cp);
     return FPE_OK;
 }
 
 fpe::DevMap dev_map(const MapSnapshot& s) { return fpe::DevMap{s.g, s.d_trav, s.d_elev}; }
+
+// fpe_foothold_map*: the snapshot current at entry, the disc constants, the region; `stream` ordered after the snapshot's
+// upload and (bit-plane path) its planes' build.  prepare_call's search-radius and plan-LDS bounds do not apply here.
+int prepare_foothold_map(fpe_engine* h, const fpe_params* params, const int32_t roi[4], bool anyOut, CallPlan& cp,
+                         fpe::FootmapRoi& r, hipStream_t stream) {
+    if (!h || !params) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    if (!anyOut) return fail(FPE_E_INVALID_ARG, "no output requested");
+    int rc = fpe::validate_params(*params);
+    if (rc != FPE_OK) return fail(rc, "non-finite or negative parameter");
+    fpe::Tuning tuning;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        cp.snap = h->map;
+        tuning = h->tuning;
+    }
+    if (!cp.snap) return fail(FPE_E_NO_MAP, "no map uploaded");
+    MapSnapshot& snap = *cp.snap;
+    if (roi) {
+        if (roi[0] < 0 || roi[1] < 0 || roi[2] <= 0 || roi[3] <= 0 || static_cast<int64_t>(roi[0]) + roi[2] > snap.g.rows ||
+            static_cast<int64_t>(roi[1]) + roi[3] > snap.g.cols)
+            return fail(FPE_E_INVALID_ARG, "region outside the map or empty");
+        r = fpe::FootmapRoi{roi[0], roi[1], roi[2], roi[3]};
+    } else {
+        r = fpe::FootmapRoi{0, 0, snap.g.rows, snap.g.cols};
+    }
+    fpe::PlanConsts& pc = cp.pc;
+    fpe::derive_constants(*params, snap.g, params->searchRadius, tuning, pc);
+    if (fpe::foothold_map_supported(pc, snap.g) != FPE_OK)
+        return fail(FPE_E_UNSUPPORTED, "foot radius over 32 cells: the literal disc walk is bounded there");
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(snap.wait_ready(stream));
+    if (pc.footRobust && pc.nHW > 0) return acquire_mask(snap, pc.thrDefault, pc.thrCandidate, stream, cp);
+    return FPE_OK;
+}
 
 int check_desc(const fpe_map_desc* d) {
     if (!d) return fail(FPE_E_INVALID_ARG, "null map descriptor");
@@ -1502,6 +1548,52 @@ int fpe_search_legs(fpe_handle h, const fpe_params* params, const fpe_leg_query*
     FPE_HIP(hipStreamSynchronize(cx.stream));
     cx.inFlight = false;
     std::memcpy(out, cx.pinned + szQ, static_cast<size_t>(n) * sizeof(fpe_foothold));
+    return FPE_OK;
+}
+
+int fpe_foothold_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_foothold_map_out* d_out,
+                            void* stream) {
+    if (!d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    fpe::FootmapRoi r{};
+    int rc = prepare_foothold_map(h, params, roi, d_out->flags || d_out->height, cp, r, st);
+    if (rc != FPE_OK) return rc;
+    cp.snap->note_async_use();  // (before the launch: a concurrent upload that retires the snapshot hands its buffers back dirty)
+    FPE_HIP(fpe::launch_foothold_map(dev_map(*cp.snap), cp.bits, cp.pc, r, d_out->flags, d_out->height, st));
+    return FPE_OK;
+}
+
+int fpe_foothold_map(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_foothold_map_out* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    CallPlan cp;  // (before the lease, as in plan_host)
+    CtxLease lease(h->ctxPool);
+    CallCtx& cx = *lease.ctx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(0));  // the stream
+    fpe::FootmapRoi r{};
+    int rc = prepare_foothold_map(h, params, roi, out->flags || out->height, cp, r, cx.stream);
+    if (rc != FPE_OK) return rc;
+    const size_t n = static_cast<size_t>(r.nr) * r.nc;
+    // device products in the call's arena; a pinned destination is written by DMA, any other through the pinned arena
+    void* dst[2] = {out->flags, out->height};
+    const size_t len[2] = {out->flags ? n : 0, out->height ? n * sizeof(float) : 0};
+    const bool pinned[2] = {dst[0] && is_pinned_host(dst[0]), dst[1] && is_pinned_host(dst[1])};
+    const size_t off[2] = {0, align256(len[0])};
+    size_t stage = 0;
+    for (int k = 0; k < 2; ++k)
+        if (len[k] && !pinned[k]) stage = off[k] + len[k];
+    FPE_HIP(cx.reserve(std::max(off[1] + len[1], stage)));
+    cx.inFlight = true;
+    FPE_HIP(fpe::launch_foothold_map(dev_map(*cp.snap), cp.bits, cp.pc, r, out->flags ? cx.dev + off[0] : nullptr,
+                                     out->height ? reinterpret_cast<float*>(cx.dev + off[1]) : nullptr, cx.stream));
+    for (int k = 0; k < 2; ++k)
+        if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? dst[k] : cx.pinned + off[k], cx.dev + off[k], len[k], hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    for (int k = 0; k < 2; ++k)
+        if (len[k] && !pinned[k]) std::memcpy(dst[k], cx.pinned + off[k], len[k]);
     return FPE_OK;
 }
 

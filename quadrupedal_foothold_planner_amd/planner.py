@@ -15,8 +15,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import (CENTROID_DTYPE, FOOTHOLD_DTYPE, GLOBAL_FOOTHOLDS_DTYPE, OPT_CYCLE_DTYPE, OPT_FOOTHOLD_DTYPE, OPT_PARAMS_DTYPE,
-                    PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable, MapDesc,
-                    OptOut, PlanOut, ptr)
+                    PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
+                    FootholdMapOut, MapDesc, OptOut, PlanOut, ptr)
 
 # products of a chained plan in the order of fpe_plan_out's fields (= the order of the engine's device arena)
 PRODUCT_ORDER = ("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status", "selected_packed")
@@ -277,6 +277,40 @@ class FootholdPlanner:
     def search_legs_device(self, d_queries_ptr, n, d_out_ptr, stream=0):
         self._check(self._lib.fpe_search_legs_device(self._h, ptr(self.params), C.c_void_p(d_queries_ptr), int(n),
                                                      C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)))
+
+    # ---- dense foothold map: checkDefaultFoothold / checkCirclePolygonFoothold / getFootholdMeanHeight at every cell centre --
+    @staticmethod
+    def _roi(roi):
+        return None if roi is None else np.ascontiguousarray(roi, dtype=np.int32).reshape(4)
+
+    def foothold_map(self, roi=None, products=("flags", "height")):
+        """fpe_foothold_map on the current map: {"flags": uint8 [n_rows, n_cols] FPE_FMAP_* bits, "height": float32
+        [n_rows, n_cols]} for the requested products.  roi = (row0, col0, n_rows, n_cols) in canonical indices; None = the
+        whole map."""
+        unknown = set(products) - {"flags", "height"}
+        if unknown:
+            raise ValueError(f"unknown foothold-map products {sorted(unknown)}")
+        r = self._roi(roi)
+        if r is not None:
+            shape = (max(int(r[2]), 0), max(int(r[3]), 0))
+        else:
+            d = MapDesc()
+            self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
+            shape = (d.rows, d.cols)
+        out = {}
+        if "flags" in products:
+            out["flags"] = np.empty(shape, np.uint8)
+        if "height" in products:
+            out["height"] = np.empty(shape, np.float32)
+        mo = FootholdMapOut(ptr(out.get("flags")), ptr(out.get("height")))
+        self._check(self._lib.fpe_foothold_map(self._h, ptr(self.params), ptr(r), C.byref(mo)))
+        return out
+
+    def foothold_map_device(self, d_flags_ptr, d_height_ptr, roi=None, stream=0):
+        """Device form: DEVICE pointers (0 = product not wanted), asynchronous on `stream`."""
+        r = self._roi(roi)
+        mo = FootholdMapOut(C.c_void_p(d_flags_ptr or None), C.c_void_p(d_height_ptr or None))
+        self._check(self._lib.fpe_foothold_map_device(self._h, ptr(self.params), ptr(r), C.byref(mo), C.c_void_p(stream or 0)))
 
     # ---- the service (globalFootholdPlan, cpp:539-1602): response content for one pose ---------------------
     @staticmethod
