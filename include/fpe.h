@@ -539,6 +539,32 @@ int fpe_foothold_map(fpe_handle h, const fpe_params* params, const int32_t roi[4
 int fpe_foothold_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4],
                             const fpe_foothold_map_out* d_out, void* stream);
 
+/* ---- dense snap map: checkFoothold's landing cell for EVERY cell of a region -----------------------------------
+ * Output element (r, c) is exactly what fpe_search_legs returns for the query of cell (i, j) = (row0 + r, col0 + c) of the
+ * current snapshot (canonical indices, as fpe_foothold_map): centre = getPosition(i, j); search_radius (<= 0 means
+ * fpe_params.searchRadius); polygon = getSearchPolygon(centre, search_radius) (cpp:2496-2517: vertices LU, RU, RD, LD with
+ * r = double(float R) and 0.5 * r) for polygon_kind 0, or the plan kernels' hexagon of fpe_pose.leg_polygon_kind 1.  With
+ * that result f:
+ *   source  f.source: 0 default-disc hit, 1 spiral candidate, 2 none;
+ *   offset  (f.row - i, f.col - j) when source is 1, else (0, 0) (a default hit lands on getIndex(centre) = (i, j); a spiral
+ *           hit at ring 0, default failed and candidate passed, is source 1 with offset (0, 0));
+ *   z       f.z: getFootholdMeanHeight at the CELL centre (cpp:2029), 0 when source is 2.
+ * A radius that fpe_search_legs would report as source 3 (over the tile bound) fails with FPE_E_UNSUPPORTED and writes
+ * nothing; a polygon_kind other than 0 or 1 fails with FPE_E_INVALID_ARG.  Any NULL product is skipped (at least one must be
+ * given).  roi, snapshot semantics, pinned destinations, the literal_discs tuning and the shared bit planes behave as in
+ * fpe_foothold_map; z needs what fpe_foothold_map's height needs.  Where the host proves the rectangle and the spiral's ring
+ * filter translation-invariant for this map and radius, the search is a bitwise first-hit dilation of the bit planes; the
+ * hexagon and everything else run the per-cell search of fpe_search_legs (same results, per-query speed). */
+typedef struct fpe_foothold_snap_out {
+    int8_t* offset;  /* [n_rows * n_cols * 2] (di, dj): landing cell = (i + di, j + dj); (0, 0) unless source == 1 */
+    uint8_t* source; /* [n_rows * n_cols] fpe_foothold.source: 0 default-disc hit, 1 spiral candidate, 2 none */
+    float* z;        /* [n_rows * n_cols] fpe_foothold.z: getFootholdMeanHeight at the cell centre, 0 when source 2 */
+} fpe_foothold_snap_out;
+int fpe_foothold_snap(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius, int32_t polygon_kind,
+                      const fpe_foothold_snap_out* out);
+int fpe_foothold_snap_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius,
+                             int32_t polygon_kind, const fpe_foothold_snap_out* d_out, void* stream);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

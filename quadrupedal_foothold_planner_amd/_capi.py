@@ -185,6 +185,11 @@ class FootholdMapOut(C.Structure):
     _fields_ = [("flags", C.c_void_p), ("height", C.c_void_p)]
 
 
+class FootholdSnapOut(C.Structure):
+    """fpe_foothold_snap_out: products of a dense snap-map call (any pointer may be NULL)."""
+    _fields_ = [("offset", C.c_void_p), ("source", C.c_void_p), ("z", C.c_void_p)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the ctypes structures below mirror that layout
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -235,6 +240,8 @@ EXPORTED_SYMBOLS = [
     "fpe_multi_synchronize",
     "fpe_foothold_map",
     "fpe_foothold_map_device",
+    "fpe_foothold_snap",
+    "fpe_foothold_snap_device",
     "fpe_spiral_offsets",
     "fpe_tile_halfwidth",
     "fpe_algorithmic_bytes_per_foothold",
@@ -319,6 +326,8 @@ def lib():
     L.fpe_multi_synchronize.argtypes = [vp]
     L.fpe_foothold_map.argtypes = [vp, vp, vp, C.POINTER(FootholdMapOut)]
     L.fpe_foothold_map_device.argtypes = [vp, vp, vp, C.POINTER(FootholdMapOut), vp]
+    L.fpe_foothold_snap.argtypes = [vp, vp, vp, f32, i32, C.POINTER(FootholdSnapOut)]
+    L.fpe_foothold_snap_device.argtypes = [vp, vp, vp, f32, i32, C.POINTER(FootholdSnapOut), vp]
     L.fpe_spiral_offsets.argtypes = [i32, vp, i32]
     L.fpe_tile_halfwidth.argtypes = [f32, f32, f64]
     L.fpe_algorithmic_bytes_per_foothold.restype = f64

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <cmath>
 #include <condition_variable>
 #include <deque>
@@ -55,6 +56,21 @@ struct FootmapRoi {
 int foothold_map_supported(const PlanConsts& pc, const MapGeom& g);
 hipError_t launch_foothold_map(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const FootmapRoi& roi, uint8_t* d_flags,
                                float* d_height, hipStream_t stream);
+// dense snap map (fpe_footsnap.hpp part of fpe_kernels.hip)
+struct SnapConsts {
+    int32_t nRings, nCand;
+    int32_t ringT;
+    int32_t rectA, rectB;
+    float Rf;
+    int32_t polyKind;
+};
+bool foothold_snap_bits_ok(const PlanConsts& pc, const SnapConsts& sc, bool haveBits, bool rectProved);
+hipError_t launch_foothold_snap_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SnapConsts& sc, const SpiralLut& lut,
+                                     const FootmapRoi& roi, int8_t* d_offset, uint8_t* d_source, float* d_z, hipStream_t stream);
+size_t foothold_snap_literal_scratch_bytes();
+hipError_t launch_foothold_snap_literal(const DevMap& m, const PlanConsts& pc, const SnapConsts& sc, const SpiralLut& lut,
+                                        const FootmapRoi& roi, void* scratch, int8_t* d_offset, uint8_t* d_source, float* d_z,
+                                        hipStream_t stream);
 }  // namespace fpe
 
 namespace {
@@ -593,6 +609,83 @@ int prepare_foothold_map(fpe_engine* h, const fpe_params* params, const int32_t 
     FPE_HIP(snap.wait_ready(stream));
     if (pc.footRobust && pc.nHW > 0) return acquire_mask(snap, pc.thrDefault, pc.thrCandidate, stream, cp);
     return FPE_OK;
+}
+
+// The snap map's translation-invariance proof (fpe_footsnap.hpp): with p = getPosition(i, j) and a candidate (i + di, j + dj),
+// the kernels' f64 comparisons see -di * res, -dj * res and r = double(R) up to a few ulps of the map's coordinates.  Where
+// every compared quantity is farther than E from its threshold, the outcome is the same for every cell of the map:
+//   rectangle (PNPOLY of getSearchPolygon): inside iff |di| res < r and |dj| res < r / 2  ->  |di| <= rectA, |dj| <= rectB;
+//   ring filter of rings nRings - 1, nRings (isInside): (di^2 + dj^2) res^2 <= r^2        ->  di^2 + dj^2 <= ringT.
+// Returns false when some threshold lies within E of a lattice value (e.g. r / res whole with r and res exact binary fractions).
+bool snap_prove(const fpe::MapGeom& g, fpe::SnapConsts& sc) {
+    const double res = g.res, r = static_cast<double>(sc.Rf);
+    const double ext = std::max(std::max(std::fabs(g.baseX), std::fabs(fpe::cell_pos(g.baseX, res, g.rows - 1))),
+                                std::max(std::fabs(g.baseY), std::fabs(fpe::cell_pos(g.baseY, res, g.cols - 1)))) + r + res;
+    const double E = 64.0 * DBL_EPSILON * (1.0 + ext);
+    auto half = [&](double hr, int32_t& A) {
+        int a = static_cast<int>(std::floor(hr / res));
+        while (a >= 0 && a * res >= hr) --a;
+        while ((a + 1) * res < hr) ++a;
+        A = a;
+        return std::fabs(a * res - hr) > E && std::fabs((a + 1) * res - hr) > E;
+    };
+    bool ok = half(r, sc.rectA);
+    ok = half(0.5 * r, sc.rectB) && ok;
+    const double E2 = 2.0 * (r + 2.0 * res) * E + E * E;
+    sc.ringT = -1;
+    for (int n = 0; n <= 2 * (sc.nRings + 1) * (sc.nRings + 1); ++n) {
+        const double d2 = static_cast<double>(n) * res * res;
+        if (std::fabs(d2 - r * r) <= E2) ok = false;
+        if (d2 <= r * r) sc.ringT = n;
+    }
+    return ok;
+}
+
+// fpe_foothold_snap*: prepare_call for the search radius (the tile, the ring bound and the LDS bound of fpe_search_legs: what it
+// would report as source 3 is FPE_E_UNSUPPORTED here), the region, the snap constants and the path; `stream` ordered after the
+// snapshot's upload and (bit path) its planes' build.
+int prepare_foothold_snap(fpe_engine* h, const fpe_params* params, const int32_t roi[4], float searchRadius, int32_t polygonKind,
+                          bool anyOut, bool wantZ, CallPlan& cp, fpe::FootmapRoi& r, fpe::SnapConsts& sc, bool& bitPath,
+                          hipStream_t stream) {
+    if (!h || !params) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    if (!anyOut) return fail(FPE_E_INVALID_ARG, "no output requested");
+    if (polygonKind != 0 && polygonKind != 1) return fail(FPE_E_INVALID_ARG, "polygon_kind must be 0 (rectangle) or 1 (hexagon)");
+    if (!std::isfinite(searchRadius)) return fail(FPE_E_INVALID_ARG, "bad search radius");
+    const float R = searchRadius > 0.0f ? searchRadius : params->searchRadius;
+    int rc = prepare_call(h, params, R, cp, stream, false);
+    if (rc != FPE_OK) return rc;
+    const fpe::MapGeom& g = cp.snap->g;
+    if (roi) {
+        if (roi[0] < 0 || roi[1] < 0 || roi[2] <= 0 || roi[3] <= 0 || static_cast<int64_t>(roi[0]) + roi[2] > g.rows ||
+            static_cast<int64_t>(roi[1]) + roi[3] > g.cols)
+            return fail(FPE_E_INVALID_ARG, "region outside the map or empty");
+        r = fpe::FootmapRoi{roi[0], roi[1], roi[2], roi[3]};
+    } else {
+        r = fpe::FootmapRoi{0, 0, g.rows, g.cols};
+    }
+    const fpe::PlanConsts& pc = cp.pc;
+    if (wantZ && fpe::foothold_map_supported(pc, g) != FPE_OK)
+        return fail(FPE_E_UNSUPPORTED, "foot radius over 32 cells: the literal disc walk is bounded there");
+    sc.Rf = R;
+    sc.polyKind = polygonKind;
+    sc.nRings = fpe::spiral_rings(R, g.res);
+    sc.nCand = h->ringStart[static_cast<size_t>(std::min(sc.nRings, h->maxRing)) + 1];
+    const bool proved = snap_prove(g, sc);
+    bitPath = fpe::foothold_snap_bits_ok(pc, sc, true, proved);
+    if (bitPath) return acquire_mask(*cp.snap, pc.thrDefault, pc.thrCandidate, stream, cp);
+    return FPE_OK;
+}
+
+// Queue the products of a prepared snap call on `stream` (the literal path's scratch is stream-ordered).
+hipError_t run_foothold_snap(fpe_engine* h, const CallPlan& cp, const fpe::FootmapRoi& r, const fpe::SnapConsts& sc, bool bitPath,
+                             int8_t* d_offset, uint8_t* d_source, float* d_z, hipStream_t stream) {
+    if (bitPath) return fpe::launch_foothold_snap_bits(dev_map(*cp.snap), cp.bits, cp.pc, sc, h->lut(), r, d_offset, d_source, d_z, stream);
+    void* scratch = nullptr;
+    hipError_t e = hipMallocAsync(&scratch, fpe::foothold_snap_literal_scratch_bytes(), stream);
+    if (e != hipSuccess) return e;
+    e = fpe::launch_foothold_snap_literal(dev_map(*cp.snap), cp.pc, sc, h->lut(), r, scratch, d_offset, d_source, d_z, stream);
+    const hipError_t f = hipFreeAsync(scratch, stream);
+    return e != hipSuccess ? e : f;
 }
 
 int check_desc(const fpe_map_desc* d) {
@@ -1593,6 +1686,63 @@ int fpe_foothold_map(fpe_handle h, const fpe_params* params, const int32_t roi[4
     FPE_HIP(hipStreamSynchronize(cx.stream));
     cx.inFlight = false;
     for (int k = 0; k < 2; ++k)
+        if (len[k] && !pinned[k]) std::memcpy(dst[k], cx.pinned + off[k], len[k]);
+    return FPE_OK;
+}
+
+int fpe_foothold_snap_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius, int32_t polygon_kind,
+                             const fpe_foothold_snap_out* d_out, void* stream) {
+    if (!d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    fpe::FootmapRoi r{};
+    fpe::SnapConsts sc{};
+    bool bitPath = false;
+    int rc = prepare_foothold_snap(h, params, roi, search_radius, polygon_kind, d_out->offset || d_out->source || d_out->z, d_out->z != nullptr,
+                                   cp, r, sc, bitPath, st);
+    if (rc != FPE_OK) return rc;
+    cp.snap->note_async_use();  // (before the launch, as in fpe_foothold_map_device)
+    FPE_HIP(run_foothold_snap(h, cp, r, sc, bitPath, d_out->offset, d_out->source, d_out->z, st));
+    return FPE_OK;
+}
+
+int fpe_foothold_snap(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius, int32_t polygon_kind,
+                      const fpe_foothold_snap_out* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    CallPlan cp;  // (before the lease, as in plan_host)
+    CtxLease lease(h->ctxPool);
+    CallCtx& cx = *lease.ctx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(0));  // the stream
+    fpe::FootmapRoi r{};
+    fpe::SnapConsts sc{};
+    bool bitPath = false;
+    int rc = prepare_foothold_snap(h, params, roi, search_radius, polygon_kind, out->offset || out->source || out->z, out->z != nullptr,
+                                   cp, r, sc, bitPath, cx.stream);
+    if (rc != FPE_OK) return rc;
+    const size_t n = static_cast<size_t>(r.nr) * r.nc;
+    // device products in the call's arena; a pinned destination is written by DMA, any other through the pinned arena
+    void* dst[3] = {out->offset, out->source, out->z};
+    const size_t len[3] = {out->offset ? 2 * n : 0, out->source ? n : 0, out->z ? n * sizeof(float) : 0};
+    bool pinned[3];
+    size_t off[3], end = 0, stage = 0;
+    for (int k = 0; k < 3; ++k) {
+        pinned[k] = dst[k] && is_pinned_host(dst[k]);
+        off[k] = end;
+        end = align256(end + len[k]);
+        if (len[k] && !pinned[k]) stage = off[k] + len[k];
+    }
+    FPE_HIP(cx.reserve(std::max(end, stage)));
+    cx.inFlight = true;
+    FPE_HIP(run_foothold_snap(h, cp, r, sc, bitPath, out->offset ? reinterpret_cast<int8_t*>(cx.dev + off[0]) : nullptr,
+                              out->source ? cx.dev + off[1] : nullptr, out->z ? reinterpret_cast<float*>(cx.dev + off[2]) : nullptr,
+                              cx.stream));
+    for (int k = 0; k < 3; ++k)
+        if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? dst[k] : cx.pinned + off[k], cx.dev + off[k], len[k], hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    for (int k = 0; k < 3; ++k)
         if (len[k] && !pinned[k]) std::memcpy(dst[k], cx.pinned + off[k], len[k]);
     return FPE_OK;
 }

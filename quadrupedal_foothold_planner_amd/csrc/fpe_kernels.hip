@@ -2129,6 +2129,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_opt.hpp"
 // ---- part four: the dense foothold map (fpe_foothold_map*) ---------------------------------------------------
 #include "fpe_footmap.hpp"
+// ---- part five: the dense snap map (fpe_foothold_snap*) ------------------------------------------------------
+#include "fpe_footsnap.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<16>),

@@ -16,7 +16,7 @@ import numpy as np
 from . import _capi
 from ._capi import (CENTROID_DTYPE, FOOTHOLD_DTYPE, GLOBAL_FOOTHOLDS_DTYPE, OPT_CYCLE_DTYPE, OPT_FOOTHOLD_DTYPE, OPT_PARAMS_DTYPE,
                     PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
-                    FootholdMapOut, MapDesc, OptOut, PlanOut, ptr)
+                    FootholdMapOut, FootholdSnapOut, MapDesc, OptOut, PlanOut, ptr)
 
 # products of a chained plan in the order of fpe_plan_out's fields (= the order of the engine's device arena)
 PRODUCT_ORDER = ("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status", "selected_packed")
@@ -311,6 +311,51 @@ class FootholdPlanner:
         r = self._roi(roi)
         mo = FootholdMapOut(C.c_void_p(d_flags_ptr or None), C.c_void_p(d_height_ptr or None))
         self._check(self._lib.fpe_foothold_map_device(self._h, ptr(self.params), ptr(r), C.byref(mo), C.c_void_p(stream or 0)))
+
+    # ---- dense snap map: checkFoothold's landing cell for every cell centre -----------------------------------------------
+    _POLYGONS = {"rectangle": 0, "hexagon": 1}
+
+    @classmethod
+    def _polygon_kind(cls, polygon):
+        if isinstance(polygon, str):
+            if polygon not in cls._POLYGONS:
+                raise ValueError(f"unknown search polygon {polygon!r}")
+            return cls._POLYGONS[polygon]
+        return int(polygon)  # a raw polygon_kind: the engine checks it
+
+    def foothold_snap(self, roi=None, search_radius=None, polygon="rectangle", products=("offset", "source", "z")):
+        """fpe_foothold_snap on the current map: {"offset": int8 [n_rows, n_cols, 2] (di, dj) of the landing cell, "source":
+        uint8 [n_rows, n_cols] (0 default hit, 1 spiral candidate, 2 none), "z": float32 [n_rows, n_cols]} for the requested
+        products.  roi as in foothold_map; search_radius None = params.searchRadius; polygon "rectangle" | "hexagon"."""
+        unknown = set(products) - {"offset", "source", "z"}
+        if unknown:
+            raise ValueError(f"unknown foothold-snap products {sorted(unknown)}")
+        r = self._roi(roi)
+        if r is not None:
+            shape = (max(int(r[2]), 0), max(int(r[3]), 0))
+        else:
+            d = MapDesc()
+            self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
+            shape = (d.rows, d.cols)
+        out = {}
+        if "offset" in products:
+            out["offset"] = np.empty(shape + (2,), np.int8)
+        if "source" in products:
+            out["source"] = np.empty(shape, np.uint8)
+        if "z" in products:
+            out["z"] = np.empty(shape, np.float32)
+        so = FootholdSnapOut(ptr(out.get("offset")), ptr(out.get("source")), ptr(out.get("z")))
+        self._check(self._lib.fpe_foothold_snap(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0),
+                                                self._polygon_kind(polygon), C.byref(so)))
+        return out
+
+    def foothold_snap_device(self, d_offset_ptr, d_source_ptr, d_z_ptr, roi=None, search_radius=None, polygon="rectangle",
+                             stream=0):
+        """Device form: DEVICE pointers (0 = product not wanted), asynchronous on `stream`."""
+        r = self._roi(roi)
+        so = FootholdSnapOut(C.c_void_p(d_offset_ptr or None), C.c_void_p(d_source_ptr or None), C.c_void_p(d_z_ptr or None))
+        self._check(self._lib.fpe_foothold_snap_device(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0),
+                                                       self._polygon_kind(polygon), C.byref(so), C.c_void_p(stream or 0)))
 
     # ---- the service (globalFootholdPlan, cpp:539-1602): response content for one pose ---------------------
     @staticmethod
