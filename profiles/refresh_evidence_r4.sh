@@ -7,8 +7,6 @@ for c in headline cfg2 cfg3 cfg4 cfg5; do python3 profiles/summarise.py r4p_$c r
 cp gpurun_out/r4p_bench_full.json profiles/round4_bench_line_full.json
 cp gpurun_out/r4p_pytest.log profiles/round4_gpu_pytest_durations.log
 [ -f gpurun_out/r4p_batch_scaling.txt ] && cp gpurun_out/r4p_batch_scaling.txt profiles/round4_batch_scaling.txt
-[ -f gpurun_out/r4p_residency.txt ] && grep -v "Warn\|amdgpu.ids" gpurun_out/r4p_residency.txt > profiles/round4_residency.txt
-[ -f gpurun_out/r4p_stage_traces.txt ] && cp gpurun_out/r4p_stage_traces.txt profiles/round4_stage_traces.txt
 [ -f gpurun_out/r4p_service_latency.txt ] && grep -v "Warn\|amdgpu.ids" gpurun_out/r4p_service_latency.txt > profiles/round4_service_latency.txt
 [ -f gpurun_out/r4p_bench_2rank.json ] && cp gpurun_out/r4p_bench_2rank.json profiles/round4_bench_line_2rank_one_gpu.json
 [ -d gpurun_out/prof_filters ] && python3 profiles/summarise_filters.py > profiles/round4_filters.txt

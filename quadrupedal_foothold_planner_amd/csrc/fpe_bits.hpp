@@ -60,12 +60,8 @@ __global__ __launch_bounds__(256) void build_bitmap_kernel(const float* __restri
 // store of the wavefront: in the one-wavefront-per-pose kernels that serialised the leg's loads with its LDS hand-offs.)
 template <int G>
 __device__ __forceinline__ void bits_sync() {
-#ifdef FPE_BITS_BARRIER_SYNC
-    pose_sync<G>();
-#else
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-#endif
 }
 
 // 64-lane kernels: upper bound of a CircleIterator bounding box (cells): two rounds of 64 membership tests
@@ -88,24 +84,16 @@ struct LegBits {
     uint32_t* f;
     uint32_t* h0;  // array k of the eroded rows at h0 + k * hStride (a pointer array indexed at run time would live in scratch)
     int hStride;
-    float* hs;  // 96-bit-row kernels only: the visited elevations of a leg's three discs (in-chain heights, heights3_finish)
     int rows;
 };
-// words (4 bytes) of one leg's LDS: the row arrays, then hs for the 96-bit-row kernels
-// widest row (in 32-bit words) of the one-wavefront-per-pose kernels whose mean heights leave the chain (flush_seqrec2)
-// (2: the 96-bit-row kernels keep their in-chain sums — TermSum / heights3_finish — as they did until the flush read its
-// boxes without divisions and in two load groups per batch; measured then: cfg-5 0.402 ms in-chain, 0.379 ms deferred)
-#ifndef FPE_SEQ_DEFER_KW
-#define FPE_SEQ_DEFER_KW 3
-#endif
-constexpr int kSeqDeferMaxKW = FPE_SEQ_DEFER_KW;
-__host__ __device__ __forceinline__ int legbits_words(int rows, int kw, int nHW, bool wide) {
+// words (4 bytes) of one leg's LDS: the row arrays
+__host__ __device__ __forceinline__ int legbits_words(int rows, int kw, int nHW) {
     // (multi-word rows use three of the arrays only since the nested erosion; the others stay: shrinking the allocation
     // to three arrays was measured 1.5 % SLOWER on cfg-3, neutral on cfg-5 — kept as measured)
     const int arrays = 2 + (nHW > 0 ? nHW : 1);
-    return ((arrays * rows * kw + 3) & ~3) + ((wide && kw > kSeqDeferMaxKW) ? 3 * kBitsMaxBoxCells : 0);
+    return (arrays * rows * kw + 3) & ~3;
 }
-__device__ __forceinline__ LegBits make_legbits(unsigned char* base, int rows, int kw, int nHW, bool wide) {
+__device__ __forceinline__ LegBits make_legbits(unsigned char* base, int rows, int kw) {
     LegBits lb;
     uint32_t* p = reinterpret_cast<uint32_t*>(base);
     const int n = rows * kw;
@@ -114,9 +102,6 @@ __device__ __forceinline__ LegBits make_legbits(unsigned char* base, int rows, i
     lb.f = p + n;
     lb.h0 = p + 2 * n;
     lb.hStride = n;
-    const int arrays = 2 + (nHW > 0 ? nHW : 1);
-    lb.hs = reinterpret_cast<float*>(p + ((arrays * n + 3) & ~3));
-    (void)wide;
     return lb;
 }
 
@@ -146,18 +131,11 @@ __device__ __forceinline__ double swizzle_f64(double v) {
     return __builtin_bit_cast(double, (static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
 }
 
-// Value of lane L (compile-time) of every 8-lane group: a ds_swizzle in bit mode.  (-DFPE_BCAST8_DPP: two DPP moves instead —
-// a quad broadcast, every quad gets ITS lane L & 3, then the half-row mirror hands the owner quad's value to the group's
-// other quad; VALU latency instead of an LDS round trip, two VALU instructions instead of one LDS instruction.  Measured on
-// the headline, round 4: 27.5 us either way — the exchange is not on the critical path; the swizzle stays.)
+// Value of lane L (compile-time) of every 8-lane group: a ds_swizzle in bit mode.  (Two DPP moves instead — a quad broadcast,
+// then the half-row mirror — were measured on the headline, round 4: 27.5 us either way; the exchange is not on the critical path.)
 template <int L>
 __device__ __forceinline__ int bcast8_dpp(int x) {
-#ifndef FPE_BCAST8_DPP
     return __builtin_amdgcn_ds_swizzle(x, 0x18 | (L << 5));
-#else
-    const int q = __builtin_amdgcn_update_dpp(0, x, (L & 3) * 0x55, 0xF, 0xF, true);
-    return __builtin_amdgcn_update_dpp(q, q, 0x141, 0xF, (L < 4) ? 0xA : 0x5, false);
-#endif
 }
 template <int L>
 __device__ __forceinline__ double bcast8_dpp_f64(double v) {
@@ -204,7 +182,6 @@ __device__ __forceinline__ void win_issue(const BitMap& bm, const MapGeom& mg, c
     for (int k = 0; k < NRL; ++k) {
         int i = iw0 + g.sub + G * k;
         i = max(-1, min(i, mg.rows));
-#if FPE_BITS_TILED
         // tile (row group, word) = one 128-byte line holding 8 consecutive rows: the lanes that own rows of one row
         // group read different 16-byte pieces of the SAME line (8-lane kernels: one or two lines per load instruction
         // instead of eight; one-wavefront-per-pose kernels: eight or nine instead of 64)
@@ -212,11 +189,6 @@ __device__ __forceinline__ void win_issue(const BitMap& bm, const MapGeom& mg, c
         const unsigned first = ((__umul24(r1 >> 3, static_cast<unsigned>(bm.strideW)) + static_cast<unsigned>(w0 + kBitPadW)) << 3) + (r1 & 7u);
 #pragma unroll
         for (int q = 0; q <= KW; ++q) grp[k][q] = load_group(bm.words, first + 8u * static_cast<unsigned>(q));
-#else
-        const unsigned first = __umul24(static_cast<unsigned>(i + 1), static_cast<unsigned>(bm.strideW)) + static_cast<unsigned>(w0 + kBitPadW);
-#pragma unroll
-        for (int q = 0; q <= KW; ++q) grp[k][q] = load_group(bm.words, first + static_cast<unsigned>(q));
-#endif
     }
 }
 template <int NRL, int KW>
@@ -422,7 +394,7 @@ __device__ __forceinline__ void centroid_begin_bits_impl(const DevMap& m, const 
     o.row = s.i0 + newRow;
     o.col = s.j0 + newCol;
     if constexpr (!kLoad) {
-        // (the caller defers the result's height: flush_seqrec walks the offset table itself)
+        // (the caller defers the result's height: flush_seqrec2 walks the offset table itself)
     } else if constexpr (kOneCell) {
         cp.e0 = m.elev[static_cast<size_t>(o.row) * m.g.cols + o.col];  // a cell of the submap: inside the map
     } else {
@@ -492,77 +464,6 @@ __device__ __forceinline__ float centroid_height_bits(const PlanConsts& pc, cons
         }
         return finish_mean(sum, last, cnt, pc.h);
     }
-}
-
-// 64-lane kernels: the three mean heights of a leg (centre disc, default-track disc, centroid result; cpp:2520-2554)
-// in ONE pass over three LDS arrays of terms in CircleIterator order; the f32 division runs once.
-// Ordered f32 sum of a disc's visited elevations (getFootholdMeanHeight, cpp:2520-2554) prepared for a serial pass of
-// PURE additions: what the reference decides per element is decided here while the elements still sit on different
-// lanes — the element's term (the value, or -0.0f when >= 10, cpp:2539: s + (-0.0f) == s for every s) is what gets
-// compacted into LDS, the count of summed elements is a ballot popcount, and `last` (the mean's fallback when nothing
-// was summed, cpp:2547-2551) is the value of the highest visited lane of the last non-empty round.
-struct TermSum {
-    float* terms;  // >= (cells of the disc bounding box) floats, 16-byte aligned
-    int n;         // elements visited
-    int cnt;       // elements < 10
-    float last;
-};
-template <int G>
-__device__ __forceinline__ void term_push(const Grp<G>& g, TermSum& ts, bool vis, float v) {
-    const unsigned long long mask = g.ballot(vis);
-    const int rank = __builtin_popcountll(mask & ((1ull << g.sub) - 1ull));
-    const bool inc = v < 10;
-    if (vis) ts.terms[ts.n + rank] = inc ? v : -0.0f;
-    ts.n += __builtin_popcountll(mask);
-    ts.cnt += __builtin_popcountll(g.ballot(vis && inc));
-    if (mask) ts.last = g.bcast(v, 63 - __builtin_clzll(mask));
-}
-template <int G>
-__device__ __forceinline__ void push_disc(const Grp<G>& g, TermSum& ts, const DiscLoads& d) {
-#pragma unroll
-    for (int r = 0; r < disc_rounds<G>(); ++r) {
-        const float v = __builtin_isfinite(d.e[r]) ? d.e[r] : 0.0f;  // cpp:2532-2537
-        term_push(g, ts, d.vis[r] != 0, v);
-    }
-}
-// The three sums of a leg side by side: lanes 0-15 walk the first array, 16-31 the second, 32-63 the third — the same
-// instruction stream for all three.  Eight terms per pass (two 16-byte LDS reads, eight dependent additions); the arrays
-// are padded with -0.0f to the common length first (they hold kBitsMaxBoxCells, a multiple of 8, floats each).
-template <int G>
-__device__ __forceinline__ void heights3_finish(const Grp<G>& g, float* hs, const TermSum& A, const TermSum& B, const TermSum& C, double h,
-                                                float& zA, float& zB, float& zC) {
-    static_assert(kBitsMaxBoxCells % 8 == 0, "heights3_finish reads whole groups of eight");
-    const int nMax = max(A.n, max(B.n, C.n));
-    const int padEnd = (nMax + 7) & ~7;
-    {
-        const int kA = A.n + g.sub, kB = B.n + g.sub, kC = C.n + g.sub;
-        if (kA < padEnd) hs[kA] = -0.0f;
-        if (kB < padEnd) hs[kBitsMaxBoxCells + kB] = -0.0f;
-        if (kC < padEnd) hs[2 * kBitsMaxBoxCells + kC] = -0.0f;
-    }
-    bits_sync<G>();
-    const int d = min(g.sub >> 4, 2);
-    const float* p = hs + d * kBitsMaxBoxCells;
-    float sum = 0.0f;
-    for (int t0 = 0; t0 < padEnd; t0 += 8) {
-        const float4 q0 = *reinterpret_cast<const float4*>(p + t0), q1 = *reinterpret_cast<const float4*>(p + t0 + 4);
-        sum = sum + q0.x;
-        sum = sum + q0.y;
-        sum = sum + q0.z;
-        sum = sum + q0.w;
-        sum = sum + q1.x;
-        sum = sum + q1.y;
-        sum = sum + q1.z;
-        sum = sum + q1.w;
-    }
-    const int cntBC = d == 1 ? B.cnt : C.cnt;
-    const int cnt = d == 0 ? A.cnt : cntBC;
-    const float lastBC = d == 1 ? B.last : C.last;
-    const float last = d == 0 ? A.last : lastBC;
-    const float z = finish_mean(sum, last, cnt, h);
-    zA = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, z), 0));
-    zB = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, z), 16));
-    zC = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, z), 32));
 }
 
 // The reference rectangle in index space.  Cell centres x_i = base + res * (-i) are non-increasing in i, so
@@ -736,8 +637,6 @@ __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralL
     // candidate; without this test such a leg scans every round with in_range false, in every phase of every remaining
     // cycle (cfg-3: 122 of a pose's 128 searches, 1.3 of its 2.5 M clocks, and the kernel waits for its slowest pose).
     if (c.ici + c.nRings < 0 || c.ici - c.nRings >= m.g.rows || c.icj + c.nRings < 0 || c.icj - c.nRings >= m.g.cols) return false;
-    if (G == 8) stamp_any(pc, c.cyc, 11);
-    if (G == 64) stamp_any(pc, 0, 14);  // (profiling builds: the LAST search of the pose wins; see scratch/trace_seq.py)
     // generic 8-lane kernels: the first round's table entries are requested here, ahead of the P rows and the erosion
     uint4 tabFirst = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (G == 8 && KW == 1 && !kOneCellFoot) tabFirst = reinterpret_cast<const uint4*>(lut.packed)[g.sub];
@@ -845,8 +744,6 @@ __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralL
         }
     }
     bits_sync<G>();
-    if (G == 8) stamp_any(pc, c.cyc, 12);
-    if (G == 64) stamp_any(pc, 0, 15);
     // (2) erosion with the foot-disc offset table: E bit (row, col) = AND_k P(row + da_k, col + db_k)
     const uint32_t* E = lb.a;
     if (!kOneCellFoot && pc.nFoot > 1 && pc.nHW > 0) {
@@ -967,20 +864,12 @@ __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralL
         bits_sync<G>();
         E = lb.h0;
     }
-    if (G == 8) stamp_any(pc, c.cyc, 13);
-    if (G == 64) stamp_any(pc, 2, 14);
     // Forms of the candidate scan, chosen per kernel shape by measurement (A/B on the BASELINE configurations): the
     // one-wavefront-per-pose kernels (64- and 96-bit rows) take straight-line rounds of 64 candidates with the ring skip
     // (cfg-5: 0.98 -> 0.76 ms in round 2); the generic 8-lane kernels four packed table entries per lane and round (below); the
     // 3x3-only 8-lane kernels, which come here only for ranks beyond their own first sixteen, the straight-line rounds
-    // without the skip.  (The branchy rounds at the end of this function are the round-1 form, kept for A/B builds.)
-#ifdef FPE_SKIP_ALL
-    constexpr bool kFlatRounds = true;
-    constexpr bool kRingSkip = true;
-#else
-    constexpr bool kFlatRounds = true;
+    // without the skip.
     constexpr bool kRingSkip = KW >= 2;
-#endif
     if constexpr (G == 8 && KW == 1 && !kOneCellFoot) {
         // (3) generic 8-lane kernels (the 3x3-only ones evaluate ranks 0-15 in leg_fast8m and come here for the rest; the
         // scan below cost them registers: measured +3 % on the headline): FOUR candidates per lane and round (rank k = 32 * round + 4 * lane + u, one uint4 of packed
@@ -1055,7 +944,7 @@ __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralL
                 return true;
             }
         }
-    } else if constexpr (kFlatRounds) {
+    } else {
         // (3) candidates in rank order, lane = rank; lowest set ballot bit = argmin of rank.  Straight-line per round
         // (per-lane `if` chains are compiled into exec-mask branches): lanes beyond the table and cells outside the map carry
         // ok = false through unconditional, clamped evaluations; the disc filter of the outer rings and the per-candidate
@@ -1112,8 +1001,6 @@ __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralL
             }
         }
         int round = startBase / G;
-        if (G == 64) stamp_any(pc, 2, 15);
-        if (G == 64) stamp_value(pc, 4, 14, round);
         int nDi = 0, nDj = 0, nR = c.nRings;
         if (__ballot(round >= kLutHeadRounds) != 0ull) {  // uniform: a late start reads its first round's entries here
             const int kn = min(startBase + g.sub, M - 1);
@@ -1171,67 +1058,6 @@ __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralL
                 const int l = __builtin_ctzll(mask);
                 wi = g.bcast(i, l);
                 wj = g.bcast(j, l);
-                if (G == 64) stamp_any(pc, 3, 14);
-                if (G == 64) stamp_value(pc, 4, 15, round);
-                return true;
-            }
-        }
-    } else {
-        // (3) candidates in rank order, lane = rank; lowest set ballot bit = argmin of rank
-        const int M = c.nCand;
-        int round = 0;
-        int nDi = 0, nDj = 0, nR = c.nRings;
-        for (int base = 0; base < M; base += G, ++round) {
-            const int k = base + g.sub;
-            bool ok = false;
-            int i = 0, j = 0;
-            int di = 0, dj = 0, r = c.nRings;
-            if (round < kLutHeadRounds) {
-                if (k < M) {
-                    const int e = round == 0 ? head.dij[0] : head.dij[1];
-                    di = static_cast<int16_t>(e & 0xFFFF);
-                    dj = e >> 16;
-                    r = round == 0 ? head.ring[0] : head.ring[1];
-                }
-            } else {
-                di = nDi;
-                dj = nDj;
-                r = nR;
-            }
-            if (round + 1 >= kLutHeadRounds) {
-                const int kn = k + G;
-                nR = c.nRings;
-                if (kn < M) {
-                    nDi = lut.di[kn];
-                    nDj = lut.dj[kn];
-                    nR = lut.ring[kn];
-                }
-            }
-            if (k < M) {
-                i = c.ici + di;
-                j = c.icj + dj;
-                ok = in_range(i, j, m.g.rows, m.g.cols);
-                // SpiralIterator::generateRing filters rings nRings-1 and nRings by isInside; the centre cell (ring 0)
-                // is pushed unfiltered by the constructor
-                if (ok && r >= 1 && (r == c.nRings || r + 1 == c.nRings)) ok = cell_in_disc(m.g, i, j, c.cx, c.cy, c.R2);
-                if (ok) ok = win_bit<KW>(E, NR, i - iw0, j - jw0) != 0u;
-                if (ok && !polyFolded) {
-                    // arbitrary polygon not folded into P: every FINITE cell of the foot disc must lie inside it (cpp:2138)
-                    for (int f = 0; f < pc.nFoot; ++f) {
-                        const int qi = i + c.footDa[f], qj = j + c.footDb[f];
-                        if (win_bit<KW>(lb.f, NR, qi - iw0, qj - jw0) == 0u) continue;
-                        if (!polygon_inside_fast(c.vx, c.vy, c.nv, cell_pos(m.g.baseX, m.g.res, qi), cell_pos(m.g.baseY, m.g.res, qj))) {
-                            ok = false;
-                            break;
-                        }
-                    }
-                }
-            }
-            const unsigned long long mask = g.ballot(ok);
-            if (mask) {
-                const int l = __builtin_ctzll(mask);
-                wi = g.bcast(i, l);
-                wj = g.bcast(j, l);
                 return true;
             }
         }
@@ -1244,7 +1070,7 @@ __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralL
 // single-lane store instructions per leg — and, since round 3, the MEAN HEIGHTS leave the chain as well.  Nothing a later
 // phase reads depends on a height (the feet-polygon centre uses x and y, cpp:2421-2463; records are write-only), so the
 // chain only deposits which cells of each CircleIterator bounding box were visited (two 64-bit ballots per disc) and
-// where the box lies; flush_seqrec reads those elevations itself and runs the reference's ordered f32 sums
+// where the box lies; flush_seqrec2 reads those elevations itself and runs the reference's ordered f32 sums
 // (cpp:2520-2554), up to 32 units side by side instead of one leg at a time (compaction into LDS, three serial sums,
 // three divisions per leg-phase: 15-19 % of a leg's clocks on cfg-3 / cfg-5).
 struct SeqRecBase {
@@ -1253,16 +1079,14 @@ struct SeqRecBase {
     int32_t nomRow, nomCol, cenRow, cenCol;
     uint32_t flags;  // nominal valid | source << 8 | centroid code << 16 | kSeqDefer* << 24
 };
-struct SeqRec : SeqRecBase {  // kernels that defer the heights (64-bit rows)
+struct SeqRec : SeqRecBase {
     int32_t aI0, aJ0, aNj;  // centre disc: bounding box origin and width (cells in row-major order t = a * nj + b)
     int32_t bI0, bJ0, bNj;  // default-track disc
     uint32_t pad[2];
     unsigned long long visA[2], visB[2];  // bit t of word t / 64: cell t of the box is a member inside the map
 };
 static_assert(sizeof(SeqRecBase) == 80 && sizeof(SeqRec) == 144 && sizeof(SeqRec) % 16 == 0, "SeqRec layout");
-template <int KW>
-using SeqRecOf = typename std::conditional<(KW <= kSeqDeferMaxKW), SeqRec, SeqRecBase>::type;
-constexpr uint32_t kSeqDeferA = 1u << 24;  // zA = mean height of the centre disc, to be computed by flush_seqrec
+constexpr uint32_t kSeqDeferA = 1u << 24;  // zA = mean height of the centre disc, to be computed by flush_seqrec2
 constexpr uint32_t kSeqDeferB = 1u << 25;  // zB (default track)
 constexpr uint32_t kSeqDeferC = 1u << 26;  // zC = mean height of the cell-centred disc of (cenRow, cenCol) (offset table)
 constexpr uint32_t kSeqCIsA = 1u << 27;    // zC = zA (whole region valid: the height at the centre, cpp:1687)
@@ -1275,7 +1099,7 @@ template <int G, int NRL, int KW, bool kMid, bool kDirect>
 __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut,
                                                const LutHead& head, PoseShared& sh, const LegBits& lb, const Grp<G>& g, int leg,
                                                const LegStatic& ls, double y0, double adjY, double advance, int cyc, int nCycles,
-                                               int b, bool live, const fpe_plan_out& out, LegCommit* lc, SeqRecOf<KW>* recs = nullptr,
+                                               int b, bool live, const fpe_plan_out& out, LegCommit* lc, SeqRec* recs = nullptr,
                                                int* validOut = nullptr) {
     const float Rf = ls.Rf;
     const int polyKind = ls.polyKind;
@@ -1330,11 +1154,8 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
     float zDefault = static_cast<float>(static_cast<double>(0.0f) + pc.h);  // value when no cell is visited
     float* scratch = reinterpret_cast<float*>(lb.a);
     const bool wantDefault = out.default_next != nullptr;
-    // one wavefront per pose: the mean heights are deferred to flush_seqrec (SeqRec); what the chain deposits for them
-    // (64-bit-row kernels: 1 cm maps, boxes of <= 25 cells, layers that stay in the L2s.  The 96-bit-row kernels keep the
-    // heights in the chain: their boxes hold up to 81 cells of a layer that does not fit the L2s, and a flush that waits for
-    // eleven dependent load batches per disc costs more than the chain's overlapped loads — measured on cfg-5: +8 %)
-    constexpr bool kDeferH = (G == 64) && !kDirect && KW <= kSeqDeferMaxKW;
+    // one wavefront per pose: the mean heights are deferred to flush_seqrec2 (SeqRec)
+    constexpr bool kDeferH = (G == 64) && !kDirect;
     uint32_t deferFlags = 0u;
     unsigned long long visA0 = 0ull, visA1 = 0ull, visB0 = 0ull, visB1 = 0ull;
     int aI0 = 0, aJ0 = 0, aNj = 1, bI0 = 0, bJ0 = 0, bNj = 1;
@@ -1360,7 +1181,6 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
         c.icj = cs.template get<13>(g);
         const Submap sm = submap_from_corners(m.g, rbox, cs.box_within(1), c.cx, c.cy);
         const int iw0 = c.ici - pc.winH, jw0 = c.icj - pc.winH;
-        stamp(pc, cyc, 2);
         // one memory round trip: the window's bit rows and the elevation of the two discs around known centres
         uint4 grp[NRL][KW + 1];
         win_issue<G, NRL, KW>(bm, m.g, g, iw0, jw0, grp);
@@ -1368,7 +1188,6 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
         disc_issue<G, false, kMid, !kDeferH>(m, pc, c.cx, c.cy, bb, g, dc);
         const bool dfltUsable = wantDefault && centre_usable(nx0, ny);
         if (dfltUsable) disc_issue<G, false, kMid, !kDeferH>(m, pc, nx0, ny, dbox, g, dd);
-        stamp(pc, cyc, 3);
         WinRows<NRL, KW> w;
         win_finish<NRL, KW>(jw0, grp, w);
 #pragma unroll
@@ -1378,12 +1197,10 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
                 if (g.sub + G * k < lb.rows) lb.a[(g.sub + G * k) * KW + q] = w.Df[k][q];
         const CentroidScan sc = rows_from_bits<G, NRL, KW>(sm, w, g, iw0, jw0);
         bits_sync<G>();
-        stamp(pc, cyc, 4);
         const bool defaultOk = default_ok_bits<G, KW, kMid>(m, pc, c.cx, c.cy, bb, dc, lb.a, lb.rows, iw0, jw0, g);  // cpp:2012
         bits_sync<G>();  // lb doubles as scratch below
         bool unused;
         float zCentre = 0.0f;
-        TermSum osA{nullptr, 0, 0, 0.0f}, osB{nullptr, 0, 0, 0.0f}, osC{nullptr, 0, 0, 0.0f};
         if constexpr (kDeferH) {
             // membership of the two discs around known centres as ballots over the bounding boxes' cells (t = round * 64 +
             // lane, row-major: CircleIterator order); a box beyond the two rounds (never with bits_supported's bound on
@@ -1406,26 +1223,15 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
                     zDefault = disc_pass_direct<G, false>(m, pc, nx0, ny, dbox, g, unused, scratch);
                 }
             }
-        } else if constexpr (G == 64) {
-            // the three ordered height sums run side by side at the end of the leg (heights3_finish): here the visited
-            // elevations of the two discs around known centres are only compacted into LDS
-            osA.terms = lb.hs;
-            osB.terms = lb.hs + kBitsMaxBoxCells;
-            osC.terms = lb.hs + 2 * kBitsMaxBoxCells;
-            push_disc(g, osA, dc);
-            if (dfltUsable) push_disc(g, osB, dd);
         } else {
             zCentre = disc_consume<G, false, kMid>(m, pc, c.cx, c.cy, bb, g, dc, unused, scratch);  // cpp:2029
         }
-        stamp(pc, cyc, 5);
         constexpr bool kOneCell = kMid;  // the 3x3-only variants are launched for one-cell foot discs
         CentroidPendingBits cp;
         centroid_begin_bits<G, kOneCell, !kDeferH>(m, pc, c, sm, sc, zCentre, g, cp);                        // cpp:818-821
-        stamp(pc, cyc, 6);
         if constexpr (G != 64) {
             if (dfltUsable) zDefault = disc_consume<G, false, kMid>(m, pc, nx0, ny, dbox, g, dd, unused, scratch);  // cpp:2289-2301
         }
-        stamp(pc, cyc, 7);
         if (defaultOk) {
             no.valid = 1;
             no.source = 0;
@@ -1437,17 +1243,7 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
             nominal_invalid(no, c.cx, c.cy, 2);
             int wi = 0, wj = 0;
             bits_sync<G>();
-#ifdef FPE_TRACE
-            const long long tSp0 = __builtin_readcyclecounter();
-#endif
             const bool spFound = spiral_bits<G, NRL, KW>(m, pc, lut, head, c, w, lb, g, iw0, jw0, wi, wj);
-#ifdef FPE_TRACE
-            if (g.sub == 0 && G == 64) {
-                sh.pad[0] += static_cast<int>((__builtin_readcyclecounter() - tSp0) >> 4);
-                sh.pad[1] += 1;
-                sh.pad[2] += spFound ? 0 : 1;
-            }
-#endif
             if (spFound) {  // cpp:2022
                 no.valid = 1;
                 no.source = 1;
@@ -1458,27 +1254,12 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
             }
             bits_sync<G>();
         }
-        stamp(pc, cyc, 8);
         if constexpr (kDeferH) {
             if (cp.needDisc != 0) deferFlags |= kSeqDeferC;          // the result's own cell-centred disc (offset table)
             else if (cp.o.code == 0) {                               // whole region valid: the height at the centre (cpp:1687)
                 if (deferFlags & kSeqDeferA) deferFlags |= kSeqCIsA;
                 else cp.o.z = zCentre;
             }
-            stamp(pc, cyc, 11);
-            stamp(pc, cyc, 12);
-        } else if constexpr (G == 64) {
-            if (cp.needDisc != 0) {
-                const float v = __builtin_isfinite(cp.e[0]) ? cp.e[0] : 0.0f;
-                term_push(g, osC, cp.vis[0] != 0, v);
-            }
-            stamp(pc, cyc, 11);
-            float zB, zC;
-            heights3_finish(g, lb.hs, osA, osB, osC, pc.h, zCentre, zB, zC);
-            stamp(pc, cyc, 12);
-            if (dfltUsable) zDefault = zB;
-            if (cp.needDisc != 0) cp.o.z = zC;
-            else if (cp.o.code == 0) cp.o.z = zCentre;  // whole region valid: the height at the centre (cpp:1687)
         } else {
             if (cp.needDisc != 0) cp.o.z = centroid_height_bits<G, kOneCell>(pc, g, cp, scratch);
         }
@@ -1501,9 +1282,8 @@ __device__ __forceinline__ void leg_phase_bits(const DevMap& m, const BitMap& bm
                 sh.nxt[2][leg][0] = no.x;  sh.nxt[2][leg][1] = no.y;  sh.nxt[2][leg][2] = static_cast<double>(no.z);
             }
         }
-        stamp(pc, cyc, 13);
-        if (live && recs) {  // staged: flush_seqrec writes the records of a few cycles at a time
-            SeqRecOf<KW> r;
+        if (live && recs) {  // staged: flush_seqrec2 writes the records of a few cycles at a time
+            SeqRec r;
             r.nomX = no.x; r.nomY = no.y; r.cenX = co.x; r.cenY = co.y; r.defX = nx0; r.defY = ny;
             r.nomZ = no.z; r.cenZ = co.z; r.defZ = zDefault;
             r.nomRow = no.row; r.nomCol = no.col; r.cenRow = co.row; r.cenCol = co.col;
@@ -1581,14 +1361,8 @@ __device__ __forceinline__ void mean_acc(MeanAcc& a, bool vis, float e) {
     a.cnt += inc ? 1 : 0;
     a.sum = a.sum + (inc ? v : -0.0f);  // s + (-0.0f) == s for every s
 }
-#ifndef FPE_FLUSH_NA
-#define FPE_FLUSH_NA 8
-#endif
-#ifndef FPE_FLUSH_NC
-#define FPE_FLUSH_NC 8
-#endif
 // NA box cells and NC table entries per batch (one dependent round trip per batch)
-template <int NA = FPE_FLUSH_NA, int NC = FPE_FLUSH_NC>
+template <int NA, int NC>
 __device__ __forceinline__ void seq_mean2(const float* __restrict__ elev, int rows, int cols, int i0, int j0, int nj, unsigned long long v0,
                                           unsigned long long v1, bool wantC, int cRow, int cCol, const int8_t* da, const int8_t* db, int nFoot,
                                           double h, float& zBox, float& zC) {
@@ -1681,42 +1455,7 @@ __device__ __forceinline__ void seq_mean2_visited(const float* __restrict__ elev
     zC = finish_mean(C.sum, C.last, C.cnt, h);
 }
 
-template <class Rec>
-__device__ __forceinline__ void flush_seqrec(const DevMap& m, const PlanConsts& pc, const int8_t* footDa, const int8_t* footDb, const Rec& rLds,
-                                             int b, int cyc, int leg, int nCycles, const fpe_plan_out& out) {
-    Rec r;
-    __builtin_memcpy(&r, &rLds, sizeof(Rec));
-    const size_t o = (static_cast<size_t>(b) * nCycles + cyc) * 4 + leg;
-    const uint8_t valid = static_cast<uint8_t>(r.flags & 0xFFu), source = static_cast<uint8_t>((r.flags >> 8) & 0xFFu);
-    // (records whose heights are deferred go through flush_seqrec2; the ones that arrive here — -DFPE_SEQ_DEFER_KW=2 builds of
-    // the 96-bit-row kernel — carry final values)
-    const float zN = r.nomZ, zB = r.defZ, zC = r.cenZ;
-    (void)footDa;
-    (void)footDb;
-    (void)m;
-    (void)pc;
-    if (out.nominal) {
-        fpe_foothold f;
-        f.row = r.nomRow; f.col = r.nomCol; f.x = r.nomX; f.y = r.nomY; f.z = zN;
-        f.valid = valid; f.source = source;
-        f.foot_id = static_cast<uint8_t>(leg); f.gait_cycle_id = static_cast<uint8_t>(cyc);
-        store_record<true>(out.nominal + o, f);
-    }
-    store_selected<true>(out, o, r.nomRow, r.nomCol, zN, valid, source, leg, cyc);
-    if (out.centroid) {
-        fpe_centroid_foothold cf;
-        cf.x = r.cenX; cf.y = r.cenY; cf.z = zC; cf.row = r.cenRow; cf.col = r.cenCol;
-        cf.code = static_cast<uint8_t>((r.flags >> 16) & 0xFFu); cf.pad[0] = cf.pad[1] = cf.pad[2] = 0;
-        store_record<true>(out.centroid + o, cf);
-    }
-    if (out.default_next) {
-        store_record<true>(out.default_next + o * 3 + 0, r.defX);
-        store_record<true>(out.default_next + o * 3 + 1, r.defY);
-        store_record<true>(out.default_next + o * 3 + 2, static_cast<double>(zB));
-    }
-}
-
-// The same with two lanes per unit (64-bit-row kernels, deferred heights): lane half 0 takes the centre disc and the
+// The staged records of one (cycle, leg) unit, two lanes per unit: lane half 0 takes the centre disc and the
 // centroid result's disc and writes the nominal / selected / centroid records, half 1 the default-track disc and the
 // default_next record.  One instruction stream for both halves (the arguments differ per lane, not the code).
 __device__ __forceinline__ void flush_seqrec2(const DevMap& m, const PlanConsts& pc, const int8_t* footDa, const int8_t* footDb, const SeqRec& rLds,
@@ -1728,10 +1467,8 @@ __device__ __forceinline__ void flush_seqrec2(const DevMap& m, const PlanConsts&
     const bool defer = (r.flags & (h1 ? kSeqDeferB : kSeqDeferA)) != 0u && (h1 ? out.default_next != nullptr : true);
     const bool wantC = !h1 && (r.flags & kSeqDeferC) != 0u && out.centroid != nullptr;
     float sBox, sC;
-#ifndef FPE_FLUSH_NA_SEQ
-#define FPE_FLUSH_NA_SEQ 12  // box cells per batch here (measured: 8 -> 12: cfg-3 -1.3 %, cfg-5 -1.5 %; 13, 14 the same; 16 worse on cfg-3)
-#endif
-    seq_mean2<FPE_FLUSH_NA_SEQ, 8>(m.elev, m.g.rows, m.g.cols, h1 ? r.bI0 : r.aI0, h1 ? r.bJ0 : r.aJ0, max(h1 ? r.bNj : r.aNj, 1), defer ? (h1 ? r.visB[0] : r.visA[0]) : 0ull,
+    constexpr int kBoxCellsPerBatch = 12;  // measured: 8 -> 12: cfg-3 -1.3 %, cfg-5 -1.5 %; 13, 14 the same; 16 worse on cfg-3
+    seq_mean2<kBoxCellsPerBatch, 8>(m.elev, m.g.rows, m.g.cols, h1 ? r.bI0 : r.aI0, h1 ? r.bJ0 : r.aJ0, max(h1 ? r.bNj : r.aNj, 1), defer ? (h1 ? r.visB[0] : r.visA[0]) : 0ull,
               defer ? (h1 ? r.visB[1] : r.visA[1]) : 0ull, wantC, r.cenRow, r.cenCol, footDa, footDb, pc.nFoot, pc.h, sBox, sC);
     if (h1) {
         if (out.default_next) {
@@ -1951,13 +1688,8 @@ __device__ __forceinline__ void flush_unit_g(const DevMap& m, const PlanConsts& 
     const bool wantC = !h1 && (u.flags & kUgCTable) != 0u && out.centroid != nullptr;
     const int nj = max(static_cast<int>(h1 ? (u.flags >> 24) : ((u.flags >> 16) & 0xFFu)), 1);
     float sBox, sC;
-#ifdef FPE_FLUSH_BOX_ORDER
-    seq_mean2(m.elev, mg.rows, mg.cols, h1 ? u.bI0 : u.aI0, h1 ? u.bJ0 : u.aJ0, nj, wantBox ? static_cast<unsigned long long>(visW) : 0ull, 0ull,
-              wantC, u.cenRow, u.cenCol, footDa, footDb, pc.nFoot, pc.h, sBox, sC);
-#else
     seq_mean2_visited(m.elev, mg.rows, mg.cols, h1 ? u.bI0 : u.aI0, h1 ? u.bJ0 : u.aJ0, nj, wantBox ? visW : 0u, wantC, u.cenRow, u.cenCol, footDa,
                       footDb, pc.nFoot, pc.h, sBox, sC);
-#endif
     const float zBox = pre ? __uint_as_float(visW) : sBox;
     const size_t o = (static_cast<size_t>(b) * nCycles + cyc) * 4 + leg;
     if (h1) {
@@ -2223,7 +1955,6 @@ __device__ __forceinline__ void leg_phase_bits8(const DevMap& m, const BitMap& b
             sm.baseY = sm.ok ? ye.sbaseY : 0.0;
         }
         const int iw0 = c.ici - pc.winH, jw0 = c.icj - pc.winH;
-        stamp(pc, cyc, 2);
         // one memory round trip: the window's bit rows and the elevation of the two discs around known centres
         uint4 grp[NRL][KW + 1];
         win_issue<G, NRL, KW>(bm, m.g, g, iw0, jw0, grp);
@@ -2243,14 +1974,12 @@ __device__ __forceinline__ void leg_phase_bits8(const DevMap& m, const BitMap& b
             rowsB = __ballot(!fitB) == 0ull;
             if (rowsA || rowsB) disc_rows8(m.g, pc.rf2, c.cx, nx0, c.cy, bb, dbox, g, rowA, rowB);
         }
-        stamp(pc, cyc, 3);
         WinRows<NRL, KW> w;
         win_finish<NRL, KW>(jw0, grp, w);
 #pragma unroll
         for (int k = 0; k < NRL; ++k) lb.a[g.sub + G * k] = w.Df[k][0];
         const CentroidScan sc = rows_from_bits<G, NRL, KW>(sm, w, g, iw0, jw0);
         bits_sync<G>();
-        stamp(pc, cyc, 4);
         bool defaultOk;
         if constexpr (kMid) {
             defaultOk = default_ok_bits<G, KW, kMid>(m, pc, c.cx, c.cy, bb, dc, lb.a, lb.rows, iw0, jw0, g);  // cpp:2012
@@ -2292,12 +2021,9 @@ __device__ __forceinline__ void leg_phase_bits8(const DevMap& m, const BitMap& b
             }
         }
         (void)unused;
-        stamp(pc, cyc, 5);
         constexpr bool kOneCell = kMid;  // the 3x3-only variants are launched for one-cell foot discs
         CentroidPendingBits cp;
         centroid_begin_bits<G, kOneCell, kMid>(m, pc, c, sm, sc, zCentre, g, cp, ye.yA, ye.yB);          // cpp:818-821
-        stamp(pc, cyc, 6);
-        stamp(pc, cyc, 7);
         if (defaultOk) {
             no.valid = 1;
             no.source = 0;
@@ -2321,7 +2047,6 @@ __device__ __forceinline__ void leg_phase_bits8(const DevMap& m, const BitMap& b
             }
             bits_sync<G>();
         }
-        stamp(pc, cyc, 8);
         if constexpr (kMid) {
             if (g.sub == 0) unit->eC = cp.e0;
             cp.o.z = 0.0f;
@@ -2528,7 +2253,6 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
         sm.baseX = subPosX + (subOrgX - 0.5 * m.g.res);
         sm.baseY = ye.sbaseY;
     }
-    stamp(pc, cyc, 2);
     // ---- same round trip: the elevation of both discs (lane = cell t of the 3x3 boxes) ----
     const int t = g.sub + (g.sub >= 4 ? 1 : 0);
     const int a = t >= 6 ? 2 : (t >= 3 ? 1 : 0);
@@ -2577,11 +2301,9 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
         iA = (pb & 1u) ? eH : iA1;
         iB = (pb & 4u) ? eL + 1 : iB1;
     }
-    stamp(pc, cyc, 3);
     WinRows<NRL, KW> w;
     win_finish<NRL, KW>(jw0, grp, w);
     const CentroidScan sc = rows_from_bits<G, NRL, KW>(sm, w, g, iw0, jw0, &ye.rmask);
-    stamp(pc, cyc, 4);
     // ---- checkDefaultFoothold: the lanes owning the box's three window rows test their Df bits under the members ----
     const unsigned mA = static_cast<unsigned>(g.ballot(visA)), mB = kNoDefault ? 0u : static_cast<unsigned>(g.ballot(visB));
     // the nine membership bits in CircleIterator order (the middle cell is always a member)
@@ -2605,7 +2327,6 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
         unit->eB[t] = eB;
         unit->eB[4] = eMidB;
     }
-    stamp(pc, cyc, 5);
     // ---- centroid method (cpp:1684-1952) as selects ----
     const int bottomRow = sm.ni - 1, rightCol = sm.nj - 1;
     const int minRow = sc.minRow, maxRow = sc.maxRow;
@@ -2636,7 +2357,6 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
     co.y = whole ? ny : yCell;
     co.row = whole ? ici : rowCell;
     co.col = whole ? icj : colCell;
-    stamp(pc, cyc, 7);
     // ---- nominal result: the default foothold, else the spiral search (cpp:2012-2029) ----
     NominalOut no;
     no.valid = 1;
@@ -2656,35 +2376,6 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
         // evaluation as spiral_bits: x interval as in rectangle_index_bounds, columns from the y entry, pass rows
         // P = ~F | (~C & inside) in the leg's LDS, lowest set ballot bit = first valid cell in spiral order.
         if (fastSpiral) {
-#ifdef FPE_FAST16_LDS
-            const int NR = lb.rows;
-#pragma unroll
-            for (int k = 0; k < NRL; ++k) {
-                const int ri = g.sub + G * k;
-                const int i = iw0 + ri;
-                const unsigned inside = (i >= iA && i <= iB) ? ye.pmask : 0u;
-                if (ri < NR) lb.a[ri] = ~w.F[k][0] | (~w.C[k][0] & inside);
-            }
-            bits_sync<G>();
-            const int rowW = ici - iw0, colW = icj - jw0;  // the centre inside the window (winH, winH)
-            static_assert(kLutHeadRounds == 2, "both register rounds are evaluated side by side");
-            // both rounds' pass bits in flight together, one broadcast of the winning entry
-            const int e0 = head.dij[0], e1 = head.dij[1];
-            const int di0 = static_cast<int16_t>(e0 & 0xFFFF), dj0 = e0 >> 16, di1 = static_cast<int16_t>(e1 & 0xFFFF), dj1 = e1 >> 16;
-            const unsigned bit0 = win_bit<KW>(lb.a, NR, rowW + di0, colW + dj0), bit1 = win_bit<KW>(lb.a, NR, rowW + di1, colW + dj1);
-            const bool ok0 = in_range(ici + di0, icj + dj0, m.g.rows, m.g.cols) & (bit0 != 0u);
-            const bool ok1 = in_range(ici + di1, icj + dj1, m.g.rows, m.g.cols) & (bit1 != 0u);
-            const unsigned m0 = static_cast<unsigned>(g.ballot(ok0)), m1 = static_cast<unsigned>(g.ballot(ok1));
-            const bool first = m0 != 0u;
-            const unsigned mSel = first ? m0 : m1;
-            const int eMine = first ? e0 : e1;
-            const int eWin = g.bcast(eMine, __builtin_ctz(mSel | 0x100u) & 7);
-            found = (m0 | m1) != 0u;
-            wi = ici + static_cast<int16_t>(eWin & 0xFFFF);
-            wj = icj + (eWin >> 16);
-            searched = lk.nCand <= G * kLutHeadRounds;  // nothing beyond the two rounds
-            bits_sync<G>();
-#else
             // this lane's row of the five around the centre (FastRanks): pass bits P = ~F | (~C & inside) (cpp:2132-2138)
             unsigned Fs = w.F[0][0], Cs = w.C[0][0];
 #pragma unroll
@@ -2711,7 +2402,6 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
             wi = ici + static_cast<int>((fk.di >> rank4) & 7ull) - 2;
             wj = icj + static_cast<int>((fk.dj >> rank4) & 7ull) - 2;
             searched = lk.nCand <= 16;  // nothing beyond the sixteen
-#endif
         }
         if (!found && !searched) {  // other polygons, larger foot discs, small search radii, or no hit in the first two rounds
             LegCtx c;
@@ -2761,7 +2451,6 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
             no.y = cell_pos(m.g.baseY, m.g.res, wj);
         }
     }
-    stamp(pc, cyc, 8);
     if (g.sub == 0) {  // what flush_unit needs to rebuild this leg's four records
         unit->visA = visA9;
         unit->visB = visB9;
@@ -2815,13 +2504,11 @@ __host__ inline int product_shape(const fpe_plan_out& o) {
 }
 
 // ---- chained plan on the bit window: 8 lanes per leg, two poses per wavefront ------------------------------------
-#ifndef FPE_BITS_GENERIC_WAVES
-#define FPE_BITS_GENERIC_WAVES 3  // measured on cfg-4: 2 -> 1.36 ms, 3 -> 1.25 ms (27 spilled VGPRs), 4 -> 1.46 ms (69 spilled)
-#endif
+constexpr int kBitsGenericWaves = 3;  // measured on cfg-4: 2 -> 1.36 ms, 3 -> 1.25 ms (27 spilled VGPRs), 4 -> 1.46 ms (69 spilled)
 template <int NRL, bool kMid, int kProd>
 // (the pose pointer and the counts lead the argument list: scalar arguments at the head of the kernarg segment are
 // preloaded into SGPRs at wave launch, -amdgpu-kernarg-preload-count, so the pose loads can be issued at once)
-__global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bits_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles,
+__global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles,
                                                           DevMap mArg, BitMap bm, PlanConsts pc, SpiralLut lut, fpe_plan_out outArg) {
     constexpr int G = 8;
     const fpe_plan_out out = specialise_products<kProd>(outArg);
@@ -2841,8 +2528,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
     const float rOverride = pp->leg_search_radius[leg];
     const int polyKindIn = pp->leg_polygon_kind[leg];
     __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
-    stamp(pc, 1, 11);
-    stamp(pc, 6, 14);  // (-DFPE_TRACE_ALL_BLOCKS builds: start / end / hardware id of every workgroup, with the stamp after the cycle loop)
     // the map geometry doubles are operands of vector f64 arithmetic only: parked in VGPRs (see plan_chained_kernel) — in
     // the 3x3-only variants; the generic ones run at their register cap (168 VGPRs at three wavefronts per SIMD), where the
     // twenty registers cost more in spills than the scalar operands do in moves (measured: cfg-4 0.713 -> 0.664 ms without)
@@ -2867,24 +2552,18 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
     hc.drift = kMid ? in_vgpr(pc.drift) : pc.drift;  // (the generic variants run at their register cap: nothing extra parked)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const Grp<G> g(tid);
-    const size_t legBytes = 4 * static_cast<size_t>(legbits_words(NR, 1, pc.nHW, false));
+    const size_t legBytes = 4 * static_cast<size_t>(legbits_words(NR, 1, pc.nHW));
     // cycles between two flushes (units and y entries staged in LDS): eight for the 3x3-only kernels, four for the generic ones
     constexpr int kBatch = kMid ? 8 : 4;
     using UnitT = typename std::conditional<kMid, Unit, UnitG>::type;
     const size_t poseBytes = sizeof(PoseShared) + 4 * legBytes + (sizeof(YEntry) + sizeof(UnitT)) * 4 * kBatch;
     unsigned char* base = smem + static_cast<size_t>(slot) * poseBytes;
     PoseShared& sh = *reinterpret_cast<PoseShared*>(base);
-    const LegBits lb = make_legbits(base + sizeof(PoseShared) + static_cast<size_t>(leg) * legBytes, NR, 1, pc.nHW, false);
+    const LegBits lb = make_legbits(base + sizeof(PoseShared) + static_cast<size_t>(leg) * legBytes, NR, 1);
     YEntry* ytab = reinterpret_cast<YEntry*>(base + sizeof(PoseShared) + 4 * legBytes) + leg * kBatch;  // [cycle % kBatch] of this leg
     UnitT* units = reinterpret_cast<UnitT*>(base + sizeof(PoseShared) + 4 * legBytes + sizeof(YEntry) * 4 * kBatch) + leg * kBatch;
 
     const LutHead head = load_lut_head(lut, g);
-#ifdef FPE_TRACE
-    asm volatile("" ::"v"(x0), "v"(gait));
-    stamp(pc, 3, 11);  // pose arrived
-    asm volatile("" ::"v"(head.dij[0]), "v"(head.ring[1]));
-    stamp(pc, 3, 12);  // rank-table head arrived
-#endif
     LegStatic ls;
     {
         if (__ballot(rOverride > 0.0f) != 0ull) {  // some leg of the wavefront overrides the search radius (build-defined)
@@ -2914,7 +2593,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
         ls.biasX = in_vgpr(ls.biasX);
         ls.biasY = in_vgpr(ls.biasY);
     }
-    stamp(pc, 3, 13);  // per-leg constants
     if constexpr (kMid) {  // launched for one-cell foot discs only: the table is the single offset (0, 0)
         if (tid % kPoseThreads == 0) {
             sh.footDa[0] = 0;
@@ -2928,7 +2606,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
             sh.footOff[k] = 0;
         }
     }
-    stamp(pc, 3, 14);  // offset table copied
     // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699)
     if (g.sub == 0) {
         double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
@@ -2950,7 +2627,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
         }
     }
     bits_sync<G>();
-    stamp(pc, 1, 12);
     if (out.pose_status) {
         // getGaitCycleSearchGridMap's getSubmap in the first cycle (opt_gate_cycle0), its four corners on four lanes
         const double gx = polygon_center_x(sh.cur[0]) + pc.step, gy = y0 + 0.0;  // cpp:2327-2329
@@ -2986,7 +2662,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
         if (live && leg == 0 && g.sub == 0)
             out.pose_status[b] = (centre_usable(gx, gy) && gs.ok) ? 0 : static_cast<uint8_t>(FPE_POSE_OPT_SUBMAP_FAILED);
     }
-    stamp(pc, 1, 13);
 
     double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (gait == 1) ? 4 : 1;
@@ -3016,13 +2691,9 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwSlot));
         hwSlot &= 15u;
     }
-#ifndef FPE_PRIO_SWAP_EIGHTHS
-#define FPE_PRIO_SWAP_EIGHTHS 3
-#endif
+    constexpr int kPrioSwapEighths = 3;
     for (int cyc = 0; cyc < nCycles; ++cyc) {
-#ifndef FPE_NO_PRIO_SWAP
-        if (kMid && cyc == (nCycles * FPE_PRIO_SWAP_EIGHTHS) / 8 && (hwSlot & 1u)) __builtin_amdgcn_s_setprio(2);
-#endif
+        if (kMid && cyc == (nCycles * kPrioSwapEighths) / 8 && (hwSlot & 1u)) __builtin_amdgcn_s_setprio(2);
         if ((cyc & (kBatch - 1)) == 0) {
             // y side of the next kBatch cycles: lane (leg, s) fills the entry of cycle cyc + s.  ajustedPose_[1] is the
             // reference's running sum (cpp:1578): cycle cyc + s has seen s more additions of the drift
@@ -3034,18 +2705,15 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
             }
             if (kBatch == 8 || g.sub < kBatch) fill_yentry(m.g, pc, ls, (y0 + mine) + ls.biasY, ytab[g.sub]);  // cpp:2201, 2414
             bits_sync<G>();
-            stamp(pc, 1, 14);
         }
         const YEntry& ye = ytab[cyc & (kBatch - 1)];
         bool cycleOk = true;
         for (int ph = 0; ph < nPhases; ++ph) {
             const unsigned mask = (gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
             const bool active = (mask >> leg) & 1u;
-            stamp(pc, cyc, 0);
             // feet-polygon centres (getPolygonCenter, cpp:2191, 2265): every lane computes ONE track's centre from the
             // committed feet in LDS; the values reach the group's other lanes by swizzle (no LDS hand-off, no barrier)
             const double myCtr = polygon_center_x(sh.cur[myTrack]);
-            stamp(pc, cyc, 1);
             // footholdValidation_ (cpp:1323) is a ballot over the pose's lanes; the committed positions go from
             // registers straight to PoseShared::cur (cpp:1332-1576)
             LegCommit lc;
@@ -3062,7 +2730,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
                                                 out, &lc, units + (cyc & (kBatch - 1)));
                 }
             }
-            stamp(pc, cyc, 9);
             const bool phaseOk = (__ballot(lc.valid == 0) & poseMask) == 0ull;
             if (phaseOk && active && g.sub == 0) {
 #pragma unroll
@@ -3073,7 +2740,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
             }
             bits_sync<G>();
             cycleOk = cycleOk && phaseOk;
-            stamp(pc, cyc, 10);
         }
         adjY += hc.drift;  // cpp:1578
         okBits |= (cycleOk ? 1u : 0u) << (cyc & 7);
@@ -3081,7 +2747,6 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
             // heights, output records and cycle validity of the last (up to) kBatch cycles: lane (leg, s) takes the
             // unit of cycle base + s
             const int c0 = cyc & ~(kBatch - 1);
-            stamp(pc, 2, 11);
             if constexpr (kMid) {
                 if (live && c0 + g.sub <= cyc) flush_unit(m, pc, units[g.sub], ytab[g.sub], b, c0 + g.sub, leg, nCycles, okBits, out);
             } else {
@@ -3091,22 +2756,18 @@ __global__ __launch_bounds__(64, kMid ? 2 : FPE_BITS_GENERIC_WAVES) void plan_bi
             }
             okBits = 0u;
             bits_sync<G>();  // the units and the y entries are rewritten next
-            stamp(pc, 2, 12);
         }
     }
-    stamp(pc, 6, 15);
 }
 
 // ---- chained plan on the bit window, sequential-legs form (large windows): one wavefront per pose, lane = window
 // row, KW words per row; the swing legs of a phase are searched one after the other (see plan_sequential_kernel) ----
-#ifndef FPE_SEQ_WAVES  // wavefronts per SIMD the register allocation aims at (measurement builds: 3 / 5)
-#define FPE_SEQ_WAVES 4
-#endif
+constexpr int kSeqWaves = 4;  // wavefronts per SIMD the register allocation aims at
 // The kernel's argument list as a struct: HIP lays a kernel's arguments out one after the other, each at its natural alignment —
 // a C struct of the same members in the same order — so this is a VIEW of plan_bits_seq_kernel's argument segment, through which a
-// leg search can read its constants again (FPE_SEQ_RELOAD_ARGS, below) instead of keeping them in scalar registers across the
-// whole chain.  (The kernel keeps its separate arguments: taking this struct as its one argument cost <1, 2> 0.6 %.)  Any change
-// of the kernel's signature must be mirrored here; every parity test of cfg-5's kernel fails loudly otherwise.
+// leg search can read its constants again (kSeqReloadArgs, below) instead of keeping them in scalar registers across the
+// whole chain.  (The kernel keeps its separate arguments: taking this struct as its one argument cost <1, 2> 0.6 %.)  A static_assert
+// behind the kernel checks the mirror against its signature.
 struct SeqKernArgs {
     DevMap m;
     BitMap bm;
@@ -3117,15 +2778,11 @@ struct SeqKernArgs {
     fpe_plan_out out;
     int recSlots;
 };
-// FPE_SEQ_RELOAD_ARGS: 0 never, 1 always, 2 (default) the 96-bit-row instantiations only — measured, round 6, A/B in one call, twice:
+// The argument reload pays on the 96-bit-row instantiations only — measured, round 6, A/B in one call, twice:
 // cfg-5 (<2, 3>) 0.3060 -> 0.3017 ms and its 32 B of vector scratch gone; cfg-3 (<1, 2>) 0.6075 -> 0.6211 ms although three quarters of
 // its leg search's spill reads disappear with it (see the leg loop): the lane reads were never what bound that kernel.
-#ifndef FPE_SEQ_RELOAD_ARGS
-#define FPE_SEQ_RELOAD_ARGS 2
-#endif
-#ifndef FPE_SEQ_GROUP16  // 0: always one pose per workgroup (measurement builds)
-#define FPE_SEQ_GROUP16 1
-#endif
+template <int KW>
+constexpr bool kSeqReloadArgs = KW >= 3;
 // One pose's chain, from its stance to its last gait cycle: a FUNCTION the kernel calls once per wavefront, not inlined.  Round 6:
 // as a callee the body reads everything uniform from the kernel's ARGUMENT SEGMENT (scalar loads through `kaIn`) instead of holding the
 // arguments in scalar registers the allocator spills to vector lanes (no spilled scalars in the kernel, 60-150 before: cfg-3 0.6046 ->
@@ -3157,20 +2814,17 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
     unsigned char* const smem = smemAll + slotOff;
     const Grp<G> g(tid);
     PoseShared& sh = *reinterpret_cast<PoseShared*>(smem);
-#ifdef FPE_TRACE
-    if (tid < 4) sh.pad[tid] = 0;
-#endif
     // per-leg constants of the pose, computed once (lane = leg) instead of once per leg and phase: a division and a
     // dependent rank-table load each
     LegStatic* lsTab = reinterpret_cast<LegStatic*>(smem + sizeof(PoseShared));
     constexpr size_t kLsBytes = (4 * sizeof(LegStatic) + 15) & ~static_cast<size_t>(15);
     // rows actually allocated: the window's 2 winH + 1 (not 64 * NRL) — LDS bounds the occupancy of these kernels
-    const LegBits lb = make_legbits(smem + sizeof(PoseShared) + kLsBytes, min(2 * pc.winH + 1, NR), KW, pc.nHW, true);
+    const LegBits lb = make_legbits(smem + sizeof(PoseShared) + kLsBytes, min(2 * pc.winH + 1, NR), KW);
     // staged output records: recSlots (a power of two, sized by the launch to keep the LDS within the occupancy budget)
     // cycles of four legs behind the row arrays
-    using Rec = SeqRecOf<KW>;
+    using Rec = SeqRec;
     Rec* recBase = reinterpret_cast<Rec*>(
-        smem + ((sizeof(PoseShared) + kLsBytes + 4 * static_cast<size_t>(legbits_words(min(2 * pc.winH + 1, NR), KW, pc.nHW, true)) + 15) & ~static_cast<size_t>(15)));
+        smem + ((sizeof(PoseShared) + kLsBytes + 4 * static_cast<size_t>(legbits_words(min(2 * pc.winH + 1, NR), KW, pc.nHW)) + 15) & ~static_cast<size_t>(15)));
     const bool live = true;
 
     const fpe_pose* pp = poses + b;
@@ -3212,10 +2866,6 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
     const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
 
     const int cycLag = (static_cast<int>(hwid & 3u) * nCycles) / 16;  // launch order of this wavefront on its SIMD (HW_ID.WAVE_ID: 0 oldest .. 3) x a sixteenth of the cycles
-#ifdef FPE_TRACE
-    long long flushClocks = 0, nFlushes = 0, legClocks = 0, nLegs = 0;
-    stamp(pc, 5, 14);  // end of the prologue
-#endif
     for (int cyc = 0; cyc < nCycles; ++cyc) {
         {
             // Issue priority by PROGRESS (s_setprio, four levels): the SIMD's arbiter serves the oldest wavefront first, so the
@@ -3244,7 +2894,6 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
         bool cycleOk = true;
         for (int ph = 0; ph < nPhases; ++ph) {
             const unsigned mask = (gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
-            stamp(pc, cyc, 0);
             // feet-polygon centres: lane t computes track t (getPolygonCenter, cpp:2191, 2265)
             if (tid < 3) sh.ctr[tid] = polygon_center_x(sh.cur[tid]);
             pose_sync<16>();
@@ -3252,12 +2901,8 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
             for (int leg = 0; leg < 4; ++leg) {
                 if (!((mask >> leg) & 1u)) continue;
                 const LegStatic ls = lsTab[leg];
-                stamp(pc, cyc, 1);
-#ifdef FPE_TRACE
-                const long long tLeg0 = static_cast<long long>(__builtin_readcyclecounter());
-#endif
                 int legValid = 1;
-                constexpr bool kReload = FPE_SEQ_RELOAD_ARGS == 1 || (FPE_SEQ_RELOAD_ARGS == 2 && KW >= 3);
+                constexpr bool kReload = kSeqReloadArgs<KW>;
                 if constexpr (kReload) {
                 // Round 6: the leg search reads the map's geometry, the plan constants, the table and output pointers from the
                 // ARGUMENT SEGMENT again (scalar loads through a pointer the optimiser cannot see through: nothing is hoisted out
@@ -3275,9 +2920,9 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
                 const fpe_plan_out outL = specialise_products<kProd>(ka->out);
                 // (the LDS carve-up likewise: a few scalar operations on two of the constants instead of six held registers)
                 const int rowsL = min(2 * ka->pc.winH + 1, NR);
-                const LegBits lbL = make_legbits(smem + sizeof(PoseShared) + kLsBytes, rowsL, KW, ka->pc.nHW, true);
+                const LegBits lbL = make_legbits(smem + sizeof(PoseShared) + kLsBytes, rowsL, KW);
                 Rec* const recL = reinterpret_cast<Rec*>(
-                    smem + ((sizeof(PoseShared) + kLsBytes + 4 * static_cast<size_t>(legbits_words(rowsL, KW, ka->pc.nHW, true)) + 15) & ~static_cast<size_t>(15)));
+                    smem + ((sizeof(PoseShared) + kLsBytes + 4 * static_cast<size_t>(legbits_words(rowsL, KW, ka->pc.nHW)) + 15) & ~static_cast<size_t>(15)));
                 leg_phase_bits<G, NRL, KW, false, false>(ka->m, ka->bm, ka->pc, ka->lut, head, sh, lbL, g, leg, ls, y0, adjY, advance, cyc, ka->nCycles, b, live, outL,
                                                          nullptr, recL + 4 * (cyc & (ka->recSlots - 1)), &legValid);
                 } else {
@@ -3285,11 +2930,6 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
                                                          recBase + 4 * (cyc & (recSlots - 1)), &legValid);
                 }
                 allValid &= legValid;
-                stamp(pc, cyc, 9);
-#ifdef FPE_TRACE
-                legClocks += static_cast<long long>(__builtin_readcyclecounter()) - tLeg0;
-                ++nLegs;
-#endif
             }
             pose_sync<16>();
             // footholdValidation_ = AND of the swing legs' flags (cpp:1323); commit or skip (cpp:1332-1576)
@@ -3305,19 +2945,15 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
             }
             pose_sync<16>();
             cycleOk = cycleOk && phaseOk;
-            stamp(pc, cyc, 10);
         }
         if (tid == 0 && out.cycle_ok) out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
         adjY += pc.drift;  // cpp:1578
         {   // the staged records of the last recSlots cycles: lane = (cycle slot, leg)
             const int slot = cyc & (recSlots - 1);
             if (slot == recSlots - 1 || cyc == nCycles - 1) {
-#ifdef FPE_TRACE
-                const long long tFlush0 = static_cast<long long>(__builtin_readcyclecounter());
-#endif
                 pose_sync<16>();
                 // (the flush reads its constants and pointers from the argument segment as well where the leg loop does)
-                constexpr bool kReloadF = FPE_SEQ_RELOAD_ARGS == 1 || (FPE_SEQ_RELOAD_ARGS == 2 && KW >= 3);
+                constexpr bool kReloadF = kSeqReloadArgs<KW>;
                 typedef const SeqKernArgs __attribute__((address_space(4))) * KernArgPtr;
                 KernArgPtr kf4 = (KernArgPtr)kaArg;
                 if constexpr (kReloadF) asm volatile("" : "+s"(kf4));
@@ -3327,44 +2963,25 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
                 const fpe_plan_out outF = kReloadF ? specialise_products<kProd>(kf->out) : out;
                 const int nCycF = kReloadF ? kf->nCycles : nCycles, slotsF = kReloadF ? kf->recSlots : recSlots;
                 Rec* const recF = kReloadF ? reinterpret_cast<Rec*>(smem + ((sizeof(PoseShared) + kLsBytes +
-                                                                            4 * static_cast<size_t>(legbits_words(min(2 * pcF.winH + 1, NR), KW, pcF.nHW, true)) + 15) &
+                                                                            4 * static_cast<size_t>(legbits_words(min(2 * pcF.winH + 1, NR), KW, pcF.nHW)) + 15) &
                                                                            ~static_cast<size_t>(15)))
                                            : recBase;
-                if constexpr (KW <= kSeqDeferMaxKW) {  // deferred heights: two lanes per (cycle, leg) unit
+                {  // deferred heights: two lanes per (cycle, leg) unit
                     const int un = tid >> 1, c = (cyc - slot) + (un >> 2);
                     if (un < 4 * slotsF && c <= cyc) flush_seqrec2(mF, pcF, sh.footDa, sh.footDb, recF[un], b, c, un & 3, tid & 1, nCycF, outF);
-                } else {
-                    const int s = tid >> 2, c = (cyc - slot) + s;
-                    if (tid < 4 * slotsF && c <= cyc) flush_seqrec(mF, pcF, sh.footDa, sh.footDb, recF[tid], b, c, tid & 3, nCycF, outF);
                 }
                 pose_sync<16>();  // the slots are rewritten next
-#ifdef FPE_TRACE
-                __builtin_amdgcn_s_waitcnt(0);
-                flushClocks += static_cast<long long>(__builtin_readcyclecounter()) - tFlush0;
-                ++nFlushes;
-#endif
             }
         }
     }
-    stamp(pc, 6, 15);
-#ifdef FPE_TRACE
-    stamp_value(pc, 7, 14, flushClocks);  // clocks inside the flushes (records + deferred heights) and their number
-    stamp_value(pc, 7, 15, nFlushes);
-    stamp_value(pc, 5, 15, legClocks);    // clocks inside the leg searches of ALL cycles, and their number
-    stamp_value(pc, 1, 14, nLegs);
-    stamp_value(pc, 6, 13, static_cast<long long>(sh.pad[0]) << 4);  // clocks inside the spiral search,
-    stamp_value(pc, 6, 12, sh.pad[1]);                               // searches, and searches without a hit
-    stamp_value(pc, 6, 11, sh.pad[2]);
-#endif
 }
 
 // The kernel: kGroup wavefronts — poses — per workgroup, each runs seq_run_pose on its own slot of the workgroup's LDS.  kGroup 16 (one
 // workgroup of 1 024 threads per CU; the launch's choice for batches of at least 64 poses on the 96-bit-row windows) or 1.
 template <int NRL, int KW, int kProd, int kGroup>
-__global__ __launch_bounds__(64 * kGroup, kGroup == 1 ? FPE_SEQ_WAVES : 1) void plan_bits_seq_kernel(DevMap m, BitMap bm, PlanConsts pc, SpiralLut lut,
+__global__ __launch_bounds__(64 * kGroup, kGroup == 1 ? kSeqWaves : 1) void plan_bits_seq_kernel(DevMap m, BitMap bm, PlanConsts pc, SpiralLut lut,
                                                                                                 const fpe_pose* __restrict__ poses, int B, int nCycles, fpe_plan_out outArg,
                                                                                                 int recSlots, int slotBytes) {
-    stamp(pc, 6, 14);  // (profiling builds: lifetime of the wavefront, with the stamp after the cycle loop)
     const int tid = static_cast<int>(threadIdx.x) & 63, wv = static_cast<int>(threadIdx.x) >> 6;
     const int b = static_cast<int>(blockIdx.x) * kGroup + wv;
     if (b >= B) return;
@@ -3376,16 +2993,18 @@ __global__ __launch_bounds__(64 * kGroup, kGroup == 1 ? FPE_SEQ_WAVES : 1) void 
     typedef const SeqKernArgs __attribute__((address_space(4))) * KernArgPtr0;
     seq_run_pose<NRL, KW, kProd>((KernArgPtr0)__builtin_amdgcn_kernarg_segment_ptr(), wv * slotBytes, b, tid, hwid, head);
 }
+static_assert(kernargs_mirror<decltype(plan_bits_seq_kernel<1, 2, 0, 1>)>(
+                  {offsetof(SeqKernArgs, m), offsetof(SeqKernArgs, bm), offsetof(SeqKernArgs, pc), offsetof(SeqKernArgs, lut),
+                   offsetof(SeqKernArgs, poses), offsetof(SeqKernArgs, B), offsetof(SeqKernArgs, nCycles), offsetof(SeqKernArgs, out),
+                   offsetof(SeqKernArgs, recSlots)},
+                  offsetof(SeqKernArgs, recSlots) + sizeof(SeqKernArgs::recSlots)),
+              "SeqKernArgs must mirror plan_bits_seq_kernel's parameters");
 
 // ---- host side of the bit-window path --------------------------------------------------------------------------
 size_t bitmap_words(int rows, int cols, int* strideW, int* nw) {
     *nw = (cols + 31) / 32;
     *strideW = *nw + 2 * kBitPadW;
-#if FPE_BITS_TILED
     return static_cast<size_t>(bit_row_groups(rows)) * 8 * (*strideW) * 4;  // 4-byte units (4 planes per word group, 8 rows per tile)
-#else
-    return static_cast<size_t>(rows + 2) * (*strideW) * 4;  // 4-byte units (4 planes per word group)
-#endif
 }
 
 hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float thrDefault, float thrCandidate, uint32_t* d_words,
@@ -3431,7 +3050,7 @@ bool bits_supported(const PlanConsts& pc, const MapGeom& g) {
     // bounding box of up to (2 ceil(rf / res) + 2)^2 cells
     const double side = 2.0 * ceil(pc.rf / g.res) + 2.0;
     if (sp.lanes == 64) return side * side <= kBitsMaxBoxCells;  // 64-lane kernels: membership in two rounds of 64 cells (SeqRec::visA / visB)
-    return side * side <= legbits_words(8 * sp.nrl, 1, pc.nHW, false);
+    return side * side <= legbits_words(8 * sp.nrl, 1, pc.nHW);
 }
 
 // Which kernel a chained plan with these constants launches (evidence for bench.py / profiles).
@@ -3460,7 +3079,7 @@ hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts&
     const int prod = product_shape(d_out);
 #define FPE_LAUNCH_BITS_P(NRL, MID, PROD)                                                                                    \
     hipLaunchKernelGGL((plan_bits_kernel<NRL, MID, PROD>), dim3((B + 1) / 2), block,                                        \
-                       2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW, false) +                                      \
+                       2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW) +                                      \
                             (MID ? (sizeof(YEntry) + sizeof(Unit)) * 32 : (sizeof(YEntry) + sizeof(UnitG)) * 16)), stream, d_poses, B,  \
                        nCycles, m, bm, pc, lut, d_out)
 #define FPE_LAUNCH_BITS(NRL, MID)                                  \
@@ -3487,15 +3106,15 @@ hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts&
 #define FPE_LAUNCH_BITS_SEQ(NRL, KW)                                                                                         \
     do {                                                                                                                     \
         const size_t base = (sizeof(PoseShared) + ((4 * sizeof(LegStatic) + 15) & ~static_cast<size_t>(15)) +                            \
-                             4 * legbits_words(2 * pc.winH + 1 < 64 * NRL ? 2 * pc.winH + 1 : 64 * NRL, KW, pc.nHW, true) + 15) &        \
+                             4 * legbits_words(2 * pc.winH + 1 < 64 * NRL ? 2 * pc.winH + 1 : 64 * NRL, KW, pc.nHW) + 15) &        \
                             ~static_cast<size_t>(15);                                                                                 \
         int recSlots = 8; /* cycles of staged records: as many as keep sixteen poses per CU (10 KiB each) */                       \
-        while (recSlots > 1 && base + recSlots * 4 * sizeof(SeqRecOf<KW>) > 10240) recSlots >>= 1;                                   \
-        const size_t slot = (base + recSlots * 4 * sizeof(SeqRecOf<KW>) + 15) & ~static_cast<size_t>(15);                            \
+        while (recSlots > 1 && base + recSlots * 4 * sizeof(SeqRec) > 10240) recSlots >>= 1;                                   \
+        const size_t slot = (base + recSlots * 4 * sizeof(SeqRec) + 15) & ~static_cast<size_t>(15);                            \
         /* (the all-seven shape takes the generic instantiation here: compiled on its own it spills more — cfg-5 +2 %, cfg-3 0) */     \
         /* sixteen poses per workgroup — one workgroup per CU — where it was measured to pay: the 96-bit-row windows (cfg-5 -2 %; the    \
            64-bit-row kernel of cfg-3 +2 %), batches that fill at least four CUs, slots that fit sixteen times into the LDS */            \
-        if (FPE_SEQ_GROUP16 && KW >= 3 && B >= 64 && 16 * slot <= 160 * 1024)                                                            \
+        if (KW >= 3 && B >= 64 && 16 * slot <= 160 * 1024)                                                            \
             FPE_LAUNCH_BITS_SEQ_G(NRL, KW, 16, (B + 15) / 16, 16 * slot, slot);                                                          \
         else                                                                                                                             \
             FPE_LAUNCH_BITS_SEQ_G(NRL, KW, 1, B, slot, slot);                                                                            \

@@ -1,6 +1,8 @@
 // fpe_device.hpp — plain-data types shared by the host side of the engine and the gfx950 kernels.
 #pragma once
+#include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 
 #include <hip/hip_runtime.h>
 
@@ -78,7 +80,7 @@ struct PlanConsts {
     // a spiral candidate), valid only when footRobust != 0: the host proved that no lattice offset
     // lies within rounding distance of the radius, so the f64 per-candidate bounding-box walk
     // visits exactly {candidate + offset} ∩ map (fpe_host.cpp::derive_foot_offsets).
-    unsigned long long* trace;  // profiling-only (-DFPE_TRACE builds): per-phase s_memtime stamps; null in production
+    uint64_t reserved;  // zero; keeps the byte layout of this by-value kernel argument where a profiling pointer was
     int32_t nFoot;
     int32_t footRobust;
     int32_t footReach;     // cells a foot disc can reach from its centre cell (max |offset|, or ceil(rf/res)+1)
@@ -104,13 +106,10 @@ constexpr int kMaxHW = 4;
 // Bit planes of one map snapshot for one (defaultFootholdThreshold, candidateFootholdThreshold) pair
 // (fpe_bits.hpp).  One uint4 per 32 columns of a row: x = D  (trav < thrDefault, raw compare: NaN 0, -inf 1),
 // y = Df (finite && trav < thrDefault), z = C (finite && trav < thrCandidate), w = F (finite); bit b of a word =
-// column 32 * word + b.  TILED: the groups of 8 consecutive rows x one word are one 128-byte line (a search window
+// column 32 * word + b.  Tiled: the groups of 8 consecutive rows x one word are one 128-byte line (a search window
 // is a few dozen rows of one or two words: row-major planes spend a line per window row, 32-64 bytes of it used);
 // tiles in row-major tile order.  Rows -1 and `rows`, kBitPadW word groups left of column 0 and everything right of
 // the last column are zero ("not in the map"), so a window hanging over the map edge reads zeros without a bounds test.
-#ifndef FPE_BITS_TILED
-#define FPE_BITS_TILED 1  // 0: row-major planes (round-2 layout, kept for A/B measurements)
-#endif
 constexpr int kBitPadW = 4;
 struct BitMap {
     const uint4* words;  // group of (row i, word w) at bit_group_index(i, w, strideW)
@@ -120,12 +119,8 @@ struct BitMap {
 // row groups (tiles of 8 rows) covering the rows -1 .. rows
 __host__ __device__ constexpr int bit_row_groups(int rows) { return ((rows + 1) >> 3) + 1; }
 __host__ __device__ __forceinline__ size_t bit_group_index(int i, int w, int strideW) {
-#if FPE_BITS_TILED
     const int r1 = i + 1;
     return ((static_cast<size_t>(r1 >> 3) * strideW + static_cast<size_t>(w + kBitPadW)) << 3) + static_cast<size_t>(r1 & 7);
-#else
-    return static_cast<size_t>(i + 1) * strideW + static_cast<size_t>(w + kBitPadW);
-#endif
 }
 
 // Producer filters (fpe_filters.hpp): parameters of the published default chain and the eight
@@ -154,6 +149,30 @@ struct OptConsts {
     int32_t pad;
 };
 constexpr long long kMaxLatticePoints = 1ll << 24;  // row points the build-defined optimiser enumerates (oracle: same)
+
+// A kernel's argument segment: HIP lays the parameters of a kernel of type void(A...) out in order, each at its natural
+// alignment.  A struct that views the segment (SeqKernArgs, OptKernArgs, FusedKernArgs) lists its members' offsets and the
+// end of its last member; kernargs_mirror says whether they are those of the kernel's first parameters.
+template <class F>
+struct KernArgs;
+template <class... A>
+struct KernArgs<void(A...)> {
+    static constexpr bool mirror(std::initializer_list<size_t> offsets, size_t end) {
+        constexpr size_t sizes[] = {sizeof(A)...}, aligns[] = {alignof(A)...};
+        size_t o = 0, k = 0;
+        for (const size_t want : offsets) {
+            if (k == sizeof...(A)) return false;
+            o = (o + aligns[k] - 1) / aligns[k] * aligns[k];
+            if (o != want) return false;
+            o += sizes[k++];
+        }
+        return o == end;
+    }
+};
+template <class F>
+constexpr bool kernargs_mirror(std::initializer_list<size_t> offsets, size_t end) {
+    return KernArgs<F>::mirror(offsets, end);
+}
 
 // Tile flag bits (one byte per cell in LDS).
 enum : uint8_t {

@@ -1190,22 +1190,6 @@ int prepare_opt(const fpe_params* params, const fpe_opt_params* opt, const CallP
 // The host-buffer form of the plan and / or the opt track: one device arena, the launches back to back on one
 // stream, the results copied out.  `out` NULL: no plan products are returned (the plan still runs when the opt track
 // needs its cycle flags and the caller gave none).
-#ifdef FPE_HOST_TIMING  // measurement builds only: where a small host-buffer call spends its time on the HOST (profiles/probe_host_timing.py)
-static double g_hostT[16];
-static long g_hostN = 0;
-struct HostTimer {
-    std::chrono::steady_clock::time_point t[16];
-    int last = -1;
-    void mark(int k) { t[k] = std::chrono::steady_clock::now(); last = k; }
-    void commit() {
-        for (int k = 1; k <= last; ++k) g_hostT[k] += std::chrono::duration<double, std::micro>(t[k] - t[k - 1]).count();
-        ++g_hostN;
-    }
-};
-#define FPE_HT_MARK(k) ht.mark(k)
-#else
-#define FPE_HT_MARK(k) do { } while (0)
-#endif
 struct GateGeom {  // what the service call's host-side (lateral) gate needs from the call's snapshot and constants
     fpe::MapGeom g;
     double isosLen, isosWid, drift;
@@ -1213,10 +1197,6 @@ struct GateGeom {  // what the service call's host-side (lateral) gate needs fro
 int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B, int32_t n_cycles,
               const fpe_plan_out* out, const uint8_t* cycleOkIn, const fpe_opt_out* oout, GateGeom* gateGeom = nullptr,
               bool* optDropped = nullptr) {
-#ifdef FPE_HOST_TIMING
-    HostTimer ht;
-#endif
-    FPE_HT_MARK(0);
     if (!poses || (!out && !oout)) return fail(FPE_E_INVALID_ARG, "null argument");
     if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
     float maxRadius = 0.0f;
@@ -1269,10 +1249,8 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
     FPE_HIP(hipSetDevice(h->device));
     FPE_HIP(cx.reserve(total));
     cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
-    FPE_HT_MARK(1);
     int rc = prepare_call(h, params, maxRadius, cp, cx.stream, runPlan);
     if (rc != FPE_OK) return rc;
-    FPE_HT_MARK(2);
     if (gateGeom) *gateGeom = GateGeom{cp.snap->g, cp.pc.isosLen, cp.pc.isosWid, cp.pc.drift};
     fpe::OptConsts oc;
     if (oout) {
@@ -1320,15 +1298,11 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
         FPE_HIP(hipHostGetDevicePointer(&arena, hp, 0));
         dp = static_cast<unsigned char*>(arena);
     } else {
-#ifndef FPE_POSES_BY_DMA
         // the poses are read by the kernels straight from the pinned arena (device-mapped): 64 bytes per pose, once, at the start
         // of its workgroup — a DMA transfer ahead of the launch costs its fixed fifteen microseconds before anything runs
         void* mapped = nullptr;
         FPE_HIP(hipHostGetDevicePointer(&mapped, hp, 0));
         dPoses = static_cast<const fpe_pose*>(mapped);
-#else
-        FPE_HIP(hipMemcpyAsync(dp, hp, static_cast<size_t>(B) * sizeof(fpe_pose), hipMemcpyHostToDevice, cx.stream));
-#endif
         if (oout && cycleOkIn) FPE_HIP(hipMemcpyAsync(dp + oOk, hp + oOk, nCyc, hipMemcpyHostToDevice, cx.stream));
     }
     fpe_opt_out od;
@@ -1360,9 +1334,7 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
             // the chain reads both layers: the side stream waits for an asynchronous upload (fpe_upload_map_device) exactly as
             // prepare_call made cx.stream wait (the speculative chain used to start while the canonicalise / copy
             // kernels of the snapshot were still writing d_trav / d_elev)
-#ifndef FPE_TEST_NO_SIDE_WAIT  // (test builds only: the suite checks that its upload-race test FAILS without this wait)
             FPE_HIP(cp.snap->wait_ready(os));
-#endif
             okDev = dp + oSpec;
         }
         FPE_HIP(fpe::launch_opt_track(dev_map(*cp.snap), cp.pc, oc, dPoses ? dPoses : reinterpret_cast<const fpe_pose*>(dp), B, n_cycles, okDev, od, os, doneDev, doneValue));
@@ -1370,7 +1342,6 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
     };
     // (the overlapped form queues the LONGER kernel first — the chain is the call's critical path; the plan kernel's launch then costs
     // it nothing)
-    FPE_HT_MARK(3);
     if (speculate) {
         rc = queue_opt();
         if (rc != FPE_OK) return rc;
@@ -1379,7 +1350,6 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
         // profiles/round6_service_latency.txt).  One non-blocking query per stream, right behind its launch.
         if (pollDone && hipStreamQuery(cx.side) != hipSuccess) (void)hipGetLastError();
     }
-    FPE_HT_MARK(4);
     if (runPlan) {
         fpe_plan_out d;
         std::memset(&d, 0, sizeof(d));
@@ -1401,7 +1371,6 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
         if (rc != FPE_OK) return rc;
     }
     if (pollDone && hipStreamQuery(cx.stream) != hipSuccess) (void)hipGetLastError();  // (see the side stream's query above)
-    FPE_HT_MARK(5);
     // ---- results to the caller ----
     struct Seg {
         size_t off, len;
@@ -1444,13 +1413,11 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
             (void)hipGetLastError();
             FPE_HIP(hipStreamSynchronize(cx.stream));
         }
-        FPE_HT_MARK(6);
         if (oout && speculate) {
             // polled: every product of the chain is in the arena (its stores precede the word); the stream's own completion is
             // looked at without waiting — the context's next call queues behind it in stream order
             if (!polled) FPE_HIP(hipStreamSynchronize(cx.side));
             else if (hipStreamQuery(cx.side) != hipSuccess) (void)hipGetLastError();
-            FPE_HT_MARK(7);
             bool allCommitted = true;
             for (size_t c = 0; c < nCyc; ++c) allCommitted = allCommitted && hp[oOk + c] != 0;
             if (!allCommitted) {  // a nominal search failed in some cycle: the chain again, on the flags as they are
@@ -1461,11 +1428,6 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
         }
         cx.inFlight = false;
         for (int k = 0; k < nSeg; ++k) std::memcpy(segs[k].dst, hp + segs[k].off, segs[k].len);
-#ifdef FPE_HOST_TIMING
-        if (ht.last < 7) ht.mark(7);
-        ht.mark(8);
-        ht.commit();
-#endif
         return FPE_OK;
     }
     // Only what the caller asked for crosses PCIe.  A product whose destination is pinned / registered host memory
@@ -1948,18 +1910,3 @@ int fpe_plan_service_opt(fpe_handle h, const fpe_params* params, const fpe_opt_p
 }
 
 }  // extern "C"
-
-#ifdef FPE_HOST_TIMING
-// mean microseconds per zero-copy plan_host call between its marks: [1] lease + reserve, [2] prepare_call, [3] opt constants + pose
-// copy + device pointers, [4] chain queued (overlapped form), [5] plan kernel queued, [6] main stream synchronised, [7] side stream
-// synchronised, [8] results copied out; out[0] = calls
-extern "C" int fpe_debug_host_timing(double* out, int reset) {
-    out[0] = static_cast<double>(g_hostN);
-    for (int k = 1; k < 16; ++k) out[k] = g_hostN ? g_hostT[k] / static_cast<double>(g_hostN) : 0.0;
-    if (reset) {
-        for (double& v : g_hostT) v = 0.0;
-        g_hostN = 0;
-    }
-    return 0;
-}
-#endif

@@ -21,18 +21,6 @@
 
 namespace {
 
-#ifndef FPE_FUSED_WAVES
-#define FPE_FUSED_WAVES 6
-#endif
-#ifndef FPE_FUSED_WAVES_2CM  // the published chain at 2 cm: four workgroups per CU (64 registers, 21 dwords of scratch in the walk phase): 0.056 -> 0.053 ms; at 1 cm the same trade loses (0.274 -> 0.278)
-#define FPE_FUSED_WAVES_2CM 8
-#endif
-#ifdef FPE_FUSED_TIMELINE  // measurement builds only (scratch/): per-workgroup clock marks of the fused kernel
-__device__ unsigned long long g_fusedTimeline[8192][16];
-#define FPE_TL_MARK(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_fusedTimeline[blockIdx.x][k] = wall_clock64(); } while (0)
-#else
-#define FPE_TL_MARK(k) do { } while (0)
-#endif
 constexpr int kFT = 16;        // tile edge of the disc stencils
 constexpr int kFilterMaxH = 24;  // largest halo the tables are sized for (e.g. r 0.115 m at 0.5 cm)
 
@@ -111,9 +99,7 @@ __device__ __forceinline__ void disc_tables(const DiscLds& d, const MapGeom& g, 
 // kTables false: the tile and the bounding boxes only (the step filter's row runs need no per-axis distance tables).
 // tilesOnly (run time, wave-uniform): the tile alone — the caller knows that nothing on its hot path reads a table (the moment
 // phase of a disc without an offset on the circle) and builds them later if a cell has to walk (disc_tables, walk_phase).
-// kCoherent: the source was written by OTHER workgroups of this launch (filter_chain_kernel): device-scope loads, which do not hit
-// a stale line of this XCD's caches.
-template <bool kTables = true, int TR = kFT, int TC = kFT, int HS = 0, bool kCoherent = false>
+template <bool kTables = true, int TR = kFT, int TC = kFT, int HS = 0>
 __device__ __forceinline__ void disc_setup(const DiscLds& d, const MapGeom& g, const float* __restrict__ src, int ti0, int tj0, double r, bool tileOnly = false) {
     // HS > 0: the halo is a compile-time constant (every loop bound, the divisions by 2 H + 1 and the number of tile rows a
     // lane requests are then constants); 0: run time
@@ -137,8 +123,7 @@ __device__ __forceinline__ void disc_setup(const DiscLds& d, const MapGeom& g, c
             const int row = base + firstRow + rowStep * q, ti = ti0 - H + row;
             v[q] = __builtin_nanf("");
             if (row < WR && colOk && ti >= 0 && ti < g.rows) {
-                if constexpr (kCoherent) v[q] = __hip_atomic_load(&src[static_cast<size_t>(ti) * g.cols + tj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else v[q] = src[static_cast<size_t>(ti) * g.cols + tj];
+                v[q] = src[static_cast<size_t>(ti) * g.cols + tj];
             }
         }
     };
@@ -271,9 +256,6 @@ __device__ __forceinline__ void normal_from_scatter(double a00, double a01, doub
 // bit in every cell that converges within the iteration cap (scratch/eig_proto.py: 99.9-100 % of the cells; mean 3.9
 // iterations per cell, 4.1 per wavefront); a cell that does not — eigenvalues within a few per cent of each other — reports
 // false and takes the sweeps.  wS / wL as normal_from_scatter, wL being the trace (>= the largest eigenvalue, <= 3 x).
-#ifndef FPE_NEWTON_CAP
-#define FPE_NEWTON_CAP 32
-#endif
 __device__ __forceinline__ double rcp_refined(double x) {
     double r = __builtin_amdgcn_rcp(x);
     r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
@@ -302,7 +284,8 @@ __device__ __forceinline__ bool normal_newton(double a00, double a01, double a02
     // at 1 cm — and the iteration halves its error step by step until it is inside their gap: 13-20 steps.  At a cap of 16 such
     // cells fell to the sweeps and, their gap being below 1e-3, to the literal walks: 196 cells of the 1 cm probe map, each holding
     // its workgroup for 20-40 us.  The loop leaves when the wavefront's last lane is done.)
-    for (int it = 0; it < FPE_NEWTON_CAP; ++it) {
+    constexpr int kNewtonCap = 32;
+    for (int it = 0; it < kNewtonCap; ++it) {
         const double f = __builtin_fma(__builtin_fma(lam - c2, lam, c1), lam, -c0);
         const double fp = __builtin_fma(__builtin_fma(3.0, lam, -2.0 * c2), lam, c1);
         const double dl = f * rcp_refined(fp);
@@ -317,13 +300,9 @@ __device__ __forceinline__ bool normal_newton(double a00, double a01, double a02
     // loop — with them the 2 cm instantiation (64 registers, eight wavefronts per SIMD) spilled four doubles of the caller's matrix
     // in EVERY cell, 32 B of scratch stores per thread and launch (47 MB written per 1000 x 1000 launch for 4 MB of
     // layers).  Same operands, same operation: the same values bit for bit.
-#ifndef FPE_NEWTON_KEEP_SCALED
     double inv2 = inv;
     asm volatile("" : "+v"(inv2));
     const double d00 = a00 * inv2, d01 = a01 * inv2, d02 = a02 * inv2, d11 = a11 * inv2, d12 = a12 * inv2, d22 = a22 * inv2;
-#else
-    const double d00 = b00, d01 = b01, d02 = b02, d11 = b11, d12 = b12, d22 = b22;
-#endif
     const double m00 = d00 - lam, m11 = d11 - lam, m22 = d22 - lam;
     // cross products of the rows of A - lambda I: where the lattice's x and y spread dominate the matrix (terrain below ~45
     // degrees on a disc that is not cut down to a sliver: entries d00, d11 of order 1 after the scaling) rows 0 and 1 give the
@@ -626,7 +605,7 @@ __device__ __forceinline__ float min3_skip_nan(float a, float b, float c) {
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-template <bool kSecond, int TR, int TC, int HS, bool kCoherent = false>
+template <bool kSecond, int TR, int TC, int HS>
 __device__ __forceinline__ void step_runs_phase(char* ldsRaw, const MapGeom& g, const float* __restrict__ src, double r, int Hrt, const StepShape& sp,
                                                 float critDown, int ti0, int tj0, bool live, float& hiOut, float& loOut, int& cntOut, float& centreOut) {
     const int H = HS > 0 ? HS : Hrt;
@@ -643,8 +622,7 @@ __device__ __forceinline__ void step_runs_phase(char* ldsRaw, const MapGeom& g, 
     const unsigned storeMask = sp.storeMask;
     // (with the per-axis distance tables: the on-circle offsets' tests below read them instead of recomputing two cell
     // positions per offset and cell)
-    disc_setup<true, TR, TC, HS, kCoherent>(d, g, src, ti0, tj0, r);
-    if (kSecond) FPE_TL_MARK(8);
+    disc_setup<true, TR, TC, HS>(d, g, src, ti0, tj0, r);
     const float ninf = -__builtin_huge_valf(), pinf = __builtin_huge_valf();
     for (int e = threadIdx.x; e < WR * TC; e += TR * TC) {  // 1. one run per (tile row, interior column)
         const int row = e / TC, c = e - row * TC;
@@ -676,7 +654,6 @@ __device__ __forceinline__ void step_runs_phase(char* ldsRaw, const MapGeom& g, 
         }
     }
     __syncthreads();
-    if (kSecond) FPE_TL_MARK(9);
     const int li = threadIdx.x / TC, lj = threadIdx.x % TC;
     const int i = ti0 + li, j = tj0 + lj;
     const float centre = d.tile[(li + H) * WC + lj + H];
@@ -705,7 +682,6 @@ __device__ __forceinline__ void step_runs_phase(char* ldsRaw, const MapGeom& g, 
                 if (w >= 0) fold(o, w);
             }
         }
-        if (kSecond) FPE_TL_MARK(10);
         // 3. the offsets on the circle, by the iterator's own tests: bounding box, and the squared axis distances of
         // disc_setup's tables (the difference of two cell positions, squared — CircleIterator::isInside's operands)
         const double r2 = r * r;
@@ -795,9 +771,8 @@ __global__ __launch_bounds__(TR * TC) void filter_step_runs_kernel(MapGeom g, co
 // layer and nothing else.
 // (512-thread workgroups: three of them per CU — six wavefronts per SIMD, 80 registers; without the hint the allocator takes 88
 // and a third of the CU's wavefronts with them: 0.283 -> 0.341 ms at 1 cm)
-// One tile of the fused launch: the second step window, the moment phase, the stores, the walking phase.  kChain: the tile's
-// coordinates come from the caller (filter_chain_kernel) instead of the workgroup number.
-template <int H, int TR, int TC, int HS, bool kChain>
+// One tile of the fused launch: the second step window, the moment phase, the stores, the walking phase.
+template <int H, int TR, int TC, int HS>
 __device__ __forceinline__ void fused_tile(char* ldsRaw, const MapGeom& g, const float* __restrict__ elev, const FilterLayers& L, double rN, double slopeCritical, double roughCritical,
                                            double invSlopeCritical, double invRoughCritical, const StepShape& sN, double r2nd, int h2nd, const StepShape& s2, double stepCritical,
                                            float critDown, int nCritical, int kStepFlags, int travOnly, int ty, int tx) {
@@ -805,13 +780,6 @@ __device__ __forceinline__ void fused_tile(char* ldsRaw, const MapGeom& g, const
     const int i = ti0 + static_cast<int>(threadIdx.x) / TC, j = tj0 + static_cast<int>(threadIdx.x) % TC;
     const bool live = i < g.rows && j < g.cols;
     float stepOut = 0.0f;
-    FPE_TL_MARK(0);
-#ifdef FPE_FUSED_TIMELINE
-    if (threadIdx.x == 0 && blockIdx.x < 8192) {
-        g_fusedTimeline[blockIdx.x][6] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-        g_fusedTimeline[blockIdx.x][7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-    }
-#endif
     // kStepFlags: bit 0 = the second step window rides in this launch, bit 1 = the first step window is at least as wide as the
     // normals' disc (a step height of exactly 0 then certifies a disc of equal elevations: normals_from_moments, `flat`)
     const int kStep = kStepFlags & 1;
@@ -819,14 +787,13 @@ __device__ __forceinline__ void fused_tile(char* ldsRaw, const MapGeom& g, const
     if (kStep) {
         float hi, lo;
         int cnt;
-        step_runs_phase<true, TR, TC, HS, kChain>(ldsRaw, g, L.stepHeight, r2nd, h2nd, s2, critDown, ti0, tj0, live, hi, lo, cnt, stepHeightHere);
+        step_runs_phase<true, TR, TC, HS>(ldsRaw, g, L.stepHeight, r2nd, h2nd, s2, critDown, ti0, tj0, live, hi, lo, cnt, stepHeightHere);
         stepOut = step_value(hi, cnt, stepCritical, nCritical);
         __syncthreads();  // the moment phase reuses the LDS
     } else if (live && (kStepFlags & 2)) {
         stepHeightHere = L.stepHeight[static_cast<size_t>(i) * g.cols + j];
     }
     const bool flat = (kStepFlags & 2) != 0 && stepHeightHere == 0.0f;
-    FPE_TL_MARK(1);
     float ox, oy, oz, os, orough;
     const bool needWalk = moments_phase<H, TR, TC>(ldsRaw, g, elev, ti0, tj0, rN, travOnly == 0, flat, sN, slopeCritical, roughCritical, invSlopeCritical, invRoughCritical, live, ox,
                                                    oy, oz, os, orough);
@@ -845,80 +812,32 @@ __device__ __forceinline__ void fused_tile(char* ldsRaw, const MapGeom& g, const
         }
     }
     if (live && kStep && !travOnly) L.step[static_cast<size_t>(i) * g.cols + j] = stepOut;
-    FPE_TL_MARK(2);
     // the cells that take the literal walks (rank-deficient scatter, components at rounding level): a phase of their own
-    walk_phase<H, TR, TC, kChain>(ldsRaw, needWalk, stepOut, ty, tx);
-    FPE_TL_MARK(3);
+    walk_phase<H, TR, TC>(ldsRaw, needWalk, stepOut);
 }
 
+constexpr int kFusedWaves = 6;
+// the published chain at 2 cm: four workgroups per CU (64 registers, 21 dwords of scratch in the walk phase): 0.056 -> 0.053 ms; at 1 cm
+// the same trade loses (0.274 -> 0.278)
+constexpr int kFusedWaves2cm = 8;
 template <int H, int TR, int TC, int HS>
-__global__ __launch_bounds__(TR * TC) __attribute__((amdgpu_waves_per_eu(TR * TC == 512 ? ((H == 3 && HS == 5) ? FPE_FUSED_WAVES_2CM : FPE_FUSED_WAVES) : 4))) void filter_fused_kernel(MapGeom g, const float* __restrict__ elev, FilterLayers L, double rN, double slopeCritical,
+__global__ __launch_bounds__(TR * TC) __attribute__((amdgpu_waves_per_eu(TR * TC == 512 ? ((H == 3 && HS == 5) ? kFusedWaves2cm : kFusedWaves) : 4))) void filter_fused_kernel(MapGeom g, const float* __restrict__ elev, FilterLayers L, double rN, double slopeCritical,
                                                             double roughCritical, double invSlopeCritical, double invRoughCritical, StepShape sN, double r2nd, int h2nd, StepShape s2, double stepCritical,
                                                             float critDown, int nCritical, int kStepFlags, int travOnly, int tilesX, int nTiles) {
     extern __shared__ __attribute__((aligned(16))) char ldsRaw[];
     int ty, tx;
     xcd_tile(tilesX, nTiles, ty, tx);
-    fused_tile<H, TR, TC, HS, false>(ldsRaw, g, elev, L, rN, slopeCritical, roughCritical, invSlopeCritical, invRoughCritical, sN, r2nd, h2nd, s2, stepCritical, critDown, nCritical,
-                                     kStepFlags, travOnly, ty, tx);
+    fused_tile<H, TR, TC, HS>(ldsRaw, g, elev, L, rN, slopeCritical, roughCritical, invSlopeCritical, invRoughCritical, sN, r2nd, h2nd, s2, stepCritical, critDown, nCritical,
+                              kStepFlags, travOnly, ty, tx);
 }
-
-// ---- the chain as ONE launch (round 6) --------------------------------------------------------------------------------------
-// Every workgroup first computes the step heights of one tile (the first window: step_runs_phase<false>), publishes them (release
-// at device scope, one flag per tile), then runs the fused tile `lag` positions BEHIND in its XCD's order, after the flags of that
-// tile and its eight neighbours.  Order: XCD x = workgroup % 8 owns the strip of `cw` tile columns [x cw, (x + 1) cw), row-major
-// inside the strip (position k = workgroup / 8: tile row k / cw, column x cw + k % cw).  A neighbour of position k - lag lies at
-// most at position k - lag + 2 cw - 1 of its own strip, so with lag = 2 cw every flag a workgroup waits for is set by a
-// workgroup with a SMALLER number, which the dispatcher has started before it (workgroups are dispatched in the order of their
-// numbers) and which waits for nobody before it sets its flag: no cycle.  A wait that never ends (the assumption broken) traps
-// after ~1 s of polling instead of hanging the device.  Flags hold the launch's epoch: nobody clears them.
-template <int H, int TR, int TC, int HS>
-__global__ __launch_bounds__(TR * TC) __attribute__((amdgpu_waves_per_eu(TR * TC == 512 ? ((H == 3 && HS == 5) ? FPE_FUSED_WAVES_2CM : FPE_FUSED_WAVES) : 4))) void filter_chain_kernel(MapGeom g, const float* __restrict__ elev, FilterLayers L, double rN, double slopeCritical,
-                                                            double roughCritical, double invSlopeCritical, double invRoughCritical, StepShape sN, double r2nd, int h2nd, StepShape s2, double stepCritical,
-                                                            float critDown, int nCritical, int kStepFlags, int travOnly, int tilesX, int nTiles, StepShape s1, double r1st,
-                                                            unsigned* flags, unsigned epoch, int cw, int nK, int lag) {
-    extern __shared__ __attribute__((aligned(16))) char ldsRaw[];
-    const int x = static_cast<int>(blockIdx.x & 7u), k = static_cast<int>(blockIdx.x >> 3);
-    const int tilesY = nTiles / tilesX;
-    if (k < nK) {
-        const int ty = k / cw, tx = x * cw + (k - ty * cw);
-        if (tx < tilesX) {  // (wave-uniform)
-            const int ti0 = ty * TR, tj0 = tx * TC;
-            const int i = ti0 + static_cast<int>(threadIdx.x) / TC, j = tj0 + static_cast<int>(threadIdx.x) % TC;
-            const bool live = i < g.rows && j < g.cols;
-            float hi, lo, centre;
-            int cnt;
-            step_runs_phase<false, TR, TC, HS>(ldsRaw, g, elev, r1st, HS, s1, 0.0f, ti0, tj0, live, hi, lo, cnt, centre);
-            // device-scope stores (written through to where every XCD reads them) and device-scope loads on the other side: a release /
-            // acquire pair of FENCES at device scope writes back and invalidates the XCD's whole L2 per workgroup — measured: the
-            // chain at 0.475 ms instead of 0.054
-            if (live)
-                __hip_atomic_store(&L.stepHeight[static_cast<size_t>(i) * g.cols + j],
-                                   isfinite(centre) ? static_cast<float>(static_cast<double>(hi) - static_cast<double>(lo)) : __builtin_nanf(""), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wavefront's stores are acknowledged ...
-            __syncthreads();                                   // ... before the one flag says so (and the next phase reuses the LDS)
-            if (threadIdx.x == 0) __hip_atomic_store(&flags[ty * tilesX + tx], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    const int k2 = k - lag;
-    if (k2 < 0) return;
-    const int ty = k2 / cw, tx = x * cw + (k2 - ty * cw);
-    if (tx >= tilesX) return;
-    if (threadIdx.x < 9) {
-        const int ny = ty + static_cast<int>(threadIdx.x) / 3 - 1, nx = tx + static_cast<int>(threadIdx.x) % 3 - 1;
-        if (ny >= 0 && ny < tilesY && nx >= 0 && nx < tilesX) {
-            const unsigned* f = &flags[ny * tilesX + nx];
-            unsigned polls = 0;
-            while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-                __builtin_amdgcn_s_sleep(8);
-                if (++polls > (1u << 22)) __builtin_trap();
-            }
-        }
-    }
-    __syncthreads();
-    fused_tile<H, TR, TC, HS, true>(ldsRaw, g, elev, L, rN, slopeCritical, roughCritical, invSlopeCritical, invRoughCritical, sN, r2nd, h2nd, s2, stepCritical, critDown, nCritical,
-                                    kStepFlags, travOnly, ty, tx);
-}
+static_assert(kernargs_mirror<decltype(filter_fused_kernel<3, 32, 16, 5>)>(
+                  {offsetof(FusedKernArgs, g), offsetof(FusedKernArgs, elev), offsetof(FusedKernArgs, L), offsetof(FusedKernArgs, rN),
+                   offsetof(FusedKernArgs, slopeCritical), offsetof(FusedKernArgs, roughCritical), offsetof(FusedKernArgs, invSlopeCritical),
+                   offsetof(FusedKernArgs, invRoughCritical), offsetof(FusedKernArgs, sN), offsetof(FusedKernArgs, r2nd), offsetof(FusedKernArgs, h2nd),
+                   offsetof(FusedKernArgs, s2), offsetof(FusedKernArgs, stepCritical), offsetof(FusedKernArgs, critDown), offsetof(FusedKernArgs, nCritical),
+                   offsetof(FusedKernArgs, kStepFlags), offsetof(FusedKernArgs, travOnly), offsetof(FusedKernArgs, tilesX), offsetof(FusedKernArgs, nTiles)},
+                  offsetof(FusedKernArgs, nTiles) + sizeof(FusedKernArgs::nTiles)),
+              "FusedKernArgs must mirror filter_fused_kernel's parameters");
 
 __host__ inline int filter_halo(double r, double res) { return static_cast<int>(r / res) + 1; }
 
@@ -954,26 +873,6 @@ hipError_t launch_fused_one(const MapGeom& g, const FilterConsts& fc, const floa
                        rt.stepFused | (fc.normalRadius <= fc.stepFirstRadius ? 2 : 0), travOnly, tilesX, nTiles);
     return hipGetLastError();
 }
-// The chain as one launch (filter_chain_kernel): flags = one word per tile, holding the epoch of the last launch that wrote the tile.
-template <int H, int TR, int TC, int HS>
-hipError_t launch_chain_one(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, const FilterRoute& rt, float critDown, int travOnly,
-                            unsigned* flags, unsigned epoch, hipStream_t stream) {
-    const void* fn = reinterpret_cast<const void*>(filter_chain_kernel<H, TR, TC, HS>);
-    size_t bytes = rt.fusedBytes;
-    const size_t first = step_lds_bytes(rt.h1, rt.s1.nClasses, TR, TC);
-    if (first > bytes) bytes = first;
-    if (bytes > 150 * 1024) return hipErrorInvalidValue;
-    if (bytes > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-        if (e != hipSuccess) return e;
-    }
-    const int tilesX = (g.cols + TC - 1) / TC, tilesY = (g.rows + TR - 1) / TR, nTiles = tilesX * tilesY;
-    const int cw = (tilesX + 7) / 8, nK = cw * tilesY, lag = 2 * cw;
-    hipLaunchKernelGGL((filter_chain_kernel<H, TR, TC, HS>), dim3(8 * (nK + lag)), dim3(TR * TC), bytes, stream, g, d_elev, L, fc.normalRadius, fc.slopeCritical,
-                       fc.roughnessCritical, 1.0 / fc.slopeCritical, 1.0 / fc.roughnessCritical, rt.sN, fc.stepSecondRadius, rt.h2, rt.s2, fc.stepCritical, critDown, fc.stepCriticalCells,
-                       rt.stepFused | (fc.normalRadius <= fc.stepFirstRadius ? 2 : 0), travOnly, tilesX, nTiles, rt.s1, fc.stepFirstRadius, flags, epoch, cw, nK, lag);
-    return hipGetLastError();
-}
 // The fused kernel's tile: 32 rows x 16 columns (512 threads) for halos up to eight cells, 32 x 32 beyond.  Rows amortise: the
 // row runs of the step window are one per (tile row with halo, interior column), the prefix scans one lane per tile row.
 constexpr int kFusedRows = 32;
@@ -987,8 +886,6 @@ FilterRoute filter_route(const FilterConsts& fc, const MapGeom& g) {
     rt.h1 = filter_halo(fc.stepFirstRadius, g.res);
     rt.h2 = filter_halo(fc.stepSecondRadius, g.res);
     const double reach = std::fmax(std::fabs(g.posX) + g.orgX, std::fabs(g.posY) + g.orgY) + g.res;
-    static const int forcedTile = std::getenv("FPE_FILTER_TILE") ? std::atoi(std::getenv("FPE_FILTER_TILE")) : 0;
-#ifndef FPE_FILTERS_WALK_ONLY
     rt.sN = step_shape(fc.normalRadius, g.res, rt.hN, reach);
     rt.s1 = step_shape(fc.stepFirstRadius, g.res, rt.h1, reach);
     rt.s2 = step_shape(fc.stepSecondRadius, g.res, rt.h2, reach);
@@ -999,22 +896,18 @@ FilterRoute filter_route(const FilterConsts& fc, const MapGeom& g) {
     const bool latticeExact = reach / g.res < 2.0e5;
     const bool sameDisc = fc.roughnessRadius == fc.normalRadius;  // the published default chain: both 0.05 m
     if (sameDisc && rt.hN >= 1 && rt.hN <= kMomentMaxH && rt.sN.rowsOk && latticeExact) rt.tF = fused_tile(rt.hN);
-#endif
     // Tile edge of the row-run launches: 32 (1024 threads) when a tile row with its halo is still one wavefront load and the
-    // arrays fit the LDS, else 16.  FPE_FILTER_TILE=16 (environment: a measurement switch) keeps the small tile.
+    // arrays fit the LDS, else 16.
     // (32 x 16 where a 32-column tile row with its halo is more than one wavefront load or the runs outgrow the LDS: windows of
     // 15-24 cells — 0.08 m at 0.5 cm: against 16 x 16 the runs per cell drop from 3.1 to 2.1 and the CU holds eight wavefronts
     // instead of four)
     const auto tile_of = [&](int H, int nClasses) {
-        if (forcedTile == 16 || g.rows < 64 || g.cols < 64) return 16;
+        if (g.rows < 64 || g.cols < 64) return 16;
         if (32 + 2 * H <= 64 && step_lds_bytes(H, nClasses, 32, 32) <= 150 * 1024) return 32;
         if (16 + 2 * H <= 64 && step_lds_bytes(H, nClasses, 32, 16) <= 150 * 1024) return 24;
         return 16;
     };
     rt.t1 = tile_of(rt.h1, rt.s1.nClasses);
-#ifdef FPE_FILTER_T1_ENV  // (measurement builds: the first window's tile from the environment)
-    if (std::getenv("FPE_FILTER_T1")) rt.t1 = std::atoi(std::getenv("FPE_FILTER_T1"));
-#endif
     rt.t2 = tile_of(rt.h2, rt.s2.nClasses);
     if (rt.tF) {
         rt.fusedBytes = fused_moment_bytes(rt.hN, kFusedRows, rt.tF);
@@ -1069,27 +962,12 @@ hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float*
             FPE_RUNS(32, 32, 0);
         }
         if (tcode == 24) {
-#ifdef FPE_FILTER_T1_ENV
-            if (!kSecond && H == 5) FPE_RUNS(32, 16, 5);
-            if (!kSecond && H == 9) FPE_RUNS(32, 16, 9);
-#endif
             if (H == 17) FPE_RUNS(32, 16, 17);  // the published windows (0.08 m) at 0.5 cm
             FPE_RUNS(32, 16, 0);
         }
         FPE_RUNS(16, 16, 0);
 #undef FPE_RUNS
     };
-#ifdef FPE_FILTER_CHAIN_EXPERIMENT  // (measurement build: the flags from a process-wide buffer — one chain at a time)
-    if (rt.tF == 16 && rt.stepFused && rt.h1 == rt.h2 && rt.s1.ok && std::getenv("FPE_FILTER_CHAIN")) {
-        static unsigned* gFlags = nullptr;
-        static unsigned gEpoch = 0;
-        if (!gFlags) {
-            if (hipMalloc(&gFlags, 4u << 20) != hipSuccess || hipMemset(gFlags, 0, 4u << 20) != hipSuccess) return hipErrorOutOfMemory;
-        }
-        if (rt.hN == 3 && rt.h2 == 5) return launch_chain_one<3, kFusedRows, 16, 5>(g, fc, d_elev, L, rt, critDown, travOnly ? 1 : 0, gFlags, ++gEpoch, stream);
-        if (rt.hN == 6 && rt.h2 == 9) return launch_chain_one<6, kFusedRows, 16, 9>(g, fc, d_elev, L, rt, critDown, travOnly ? 1 : 0, gFlags, ++gEpoch, stream);
-    }
-#endif
     // 1. step heights (first window)
     if (!launch_runs(std::false_type{}, rt.t1, rt.h1, rt.s1, d_elev, fc.stepFirstRadius))  // (the walking kernel writes L.stepHeight only: fine for travOnly too)
         hipLaunchKernelGGL(filter_step1_kernel, grid, block, disc_lds_bytes(rt.h1), stream, g, d_elev, L, fc.stepFirstRadius, rt.h1);

@@ -95,16 +95,8 @@ __device__ __forceinline__ double acos_unit(double x) {
 // float layers' rounding (tests/test_gpu_filters.py: one float ulp, >= 99.99 % of the cells bit-identical to the oracle).
 // Returns true when the cell has to take the literal walks instead (the outputs are then not set): the caller queues it for
 // the workgroup's walking phase (walk_phase below).
-#ifndef FPE_NORMAL_MIN_GAP
-#define FPE_NORMAL_MIN_GAP 3e-4
-#endif
-#ifndef FPE_NORMAL_MIN_COMPONENT_GAP
-#define FPE_NORMAL_MIN_COMPONENT_GAP 1e-7
-#endif
-#ifdef FPE_DBG_COUNT_WALKS
-__device__ unsigned g_walkWhy[4];
-__device__ double g_walkDbg[64][8];
-#endif
+constexpr double kNormalMinGap = 3e-4;
+constexpr double kNormalMinComponentGap = 1e-7;
 template <bool kSweeps>
 __device__ __forceinline__ bool normals_from_moments(const MapGeom& g, double slopeCritical, double roughCritical, double invSlopeCritical,
                                                      double invRoughCritical, int N, int Sc, int Scc, int Sv, int Svv, int Svc, double Sz, double Szz, double Scz,
@@ -169,23 +161,14 @@ __device__ __forceinline__ bool normals_from_moments(const MapGeom& g, double sl
     // 2 cm, 32 of 300 at 1 cm, all of it the tail of the few workgroups that hold such a cell) stay on the moment path.  A gap
     // below 1e-4 is a genuine degeneracy (members on a line): the oracle's normal is then decided by its own rounding — walk.
     const double cMin = fmin(fmin(fabs(ex), fabs(ey)), fabs(ez));
-#ifdef FPE_DBG_COUNT_WALKS
-    if (walk) {
-        const unsigned k = atomicAdd(&g_walkWhy[0], 1u);
-        if (k < 64) { g_walkDbg[k][0] = static_cast<double>(N); g_walkDbg[k][1] = a00; g_walkDbg[k][2] = a11; g_walkDbg[k][3] = a22; g_walkDbg[k][4] = a01; g_walkDbg[k][5] = a02; g_walkDbg[k][6] = a12; g_walkDbg[k][7] = gapRel; }
-    }
-    else if (!(eigS > 1e-10 * eigL)) atomicAdd(&g_walkWhy[1], 1u);
-    else if (normalsStored ? !(cMin * fmin(gapRel, 0.3) > FPE_NORMAL_MIN_COMPONENT_GAP) : !(gapRel > 1e-4)) atomicAdd(&g_walkWhy[2], 1u);
-    else if (normalsStored && !(gapRel > FPE_NORMAL_MIN_GAP)) atomicAdd(&g_walkWhy[3], 1u);
-#endif
     if (walk || !(eigS > 1e-10 * eigL)) return true;
-    if (normalsStored ? !(cMin * fmin(gapRel, 0.3) > FPE_NORMAL_MIN_COMPONENT_GAP) : !(gapRel > 1e-4)) return true;
+    if (normalsStored ? !(cMin * fmin(gapRel, 0.3) > kNormalMinComponentGap) : !(gapRel > 1e-4)) return true;
     // The stored normal of a cell whose two SMALL eigenvalues nearly coincide (a steep smooth face under a symmetric disc: both are
     // the lattice's own second moment) turns within their plane by dA / gap, and dA — prefix differences over a tile row — is ~3e-14
     // of the scale, not 1e-15: at a gap of 3.6e-5 every component is within 1e-9 of where the oracle puts it and rounds the other
     // way in 3 % of the cases (campaign seed 10090970, round 6: five such cells on one 56 x 63 map, over the cap of the tests'
     // `loose` class; mpmath says the oracle's rounding is the right one in all five).  Below 3e-4 the cell walks.
-    if (normalsStored && !(gapRel > FPE_NORMAL_MIN_GAP)) return true;
+    if (normalsStored && !(gapRel > kNormalMinGap)) return true;
     {
         // (Measured and not built, round 6: sending a cell to the walks when a component lies within 2e-15 .. 3e-14 / gap of the
         // midpoint between two floats — the `loose` class of the tests at its source.  One walk holds a 512-cell workgroup: +10 %
@@ -229,7 +212,6 @@ __device__ __forceinline__ bool moments_phase(char* ldsRaw, const MapGeom& g, co
     // scalars of the shape: the tile alone, and walk_phase builds the tables for the workgroups that walk (round 6: the tables were
     // ~150 vector instructions of the first wavefront and ~40 of five more, in every workgroup).
     disc_setup<true, TR, TC, H>(d, g, elev, ti0, tj0, r, sp.edgeRows == 0ull);
-    FPE_TL_MARK(11);
     // z0, the elevation the prefix sums are taken about: a VALID cell near the tile's centre (the sums' cancellation grows with the
     // square of the largest |z - z0| in the tile: the centre halves it against a corner, and a hole at one fixed cell must not
     // leave z0 = 0 — a map at an altitude of 100 m would then sum squares of 10^4).  Every wavefront looks at the same 64 cells —
@@ -282,7 +264,6 @@ __device__ __forceinline__ bool moments_phase(char* ldsRaw, const MapGeom& g, co
         }
     }
     __syncthreads();
-    FPE_TL_MARK(12);
     const int li = threadIdx.x / TC, lj = threadIdx.x % TC;
     const int i = ti0 + li, j = tj0 + lj;
     const float nanf = __builtin_nanf("");
@@ -343,7 +324,6 @@ __device__ __forceinline__ bool moments_phase(char* ldsRaw, const MapGeom& g, co
         Scz += cz;
         Svz += static_cast<double>(o) * z;
     }
-    FPE_TL_MARK(13);
     const int N = static_cast<int>(AnC & 0xFFFFu), SC = static_cast<int>(AnC >> 16);
     const int Sc = SC - cc * N;
     const int Scc = static_cast<int>(ACC) - 2 * cc * SC + cc * cc * N;
@@ -372,9 +352,7 @@ __device__ __forceinline__ void disc_walk_rows(const DiscLds& d, const int8_t* r
     const double* const yRow = d.yP + lj + H;
     // (not unrolled: the walks are the kernel's cold path — one cell in 10^4 — and three unrolled copies of the visitor per row
     // were what pushed the 2 cm instantiation past its 64 registers)
-#ifndef FPE_WALK_UNROLL
 #pragma unroll 1
-#endif
     for (int oo = 0; oo < D; ++oo) {
         const int o = oo - H;
         const int w0 = rowW[oo];
@@ -496,12 +474,9 @@ struct FusedKernArgs {
     float critDown;
     int nCritical, kStepFlags, travOnly, tilesX, nTiles;
 };
-template <int H, int TR, int TC, bool kChain = false>
-__device__ __forceinline__ void walk_phase(char* ldsRaw, bool needWalk, float stepOut, int tyIn = 0, int txIn = 0) {
+template <int H, int TR, int TC>
+__device__ __forceinline__ void walk_phase(char* ldsRaw, bool needWalk, float stepOut) {
     using Lay = FusedLayout<H, TR, TC>;
-#ifdef FPE_NO_WALK  // (measurement builds only: what the kernel costs without its walking phase)
-    return;
-#endif
     if (!__syncthreads_or(needWalk ? 1 : 0)) return;  // (also: every thread is done with the prefix records)
     typedef const FusedKernArgs __attribute__((address_space(4))) * FusedArgPtr;
     FusedArgPtr ka4 = (FusedArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -512,8 +487,8 @@ __device__ __forceinline__ void walk_phase(char* ldsRaw, bool needWalk, float st
     const StepShape& sp = ka->sN;
     const double r = ka->rN, slopeCritical = ka->slopeCritical, roughCritical = ka->roughCritical;
     const int kStep = ka->kStepFlags & 1, travOnly = ka->travOnly;
-    int tyW = tyIn, txW = txIn;  // (filter_chain_kernel: the tile is not a function of the workgroup number alone)
-    if constexpr (!kChain) xcd_tile(ka->tilesX, ka->nTiles, tyW, txW);
+    int tyW, txW;
+    xcd_tile(ka->tilesX, ka->nTiles, tyW, txW);
     const int ti0 = tyW * TR, tj0 = txW * TC;
     const DiscLds d = disc_carve(ldsRaw, H, TR, TC);
     int* const count = reinterpret_cast<int*>(ldsRaw + Lay::discBytes);

@@ -255,10 +255,7 @@ void derive_constants(const fpe_params& p, const MapGeom& geom, float maxSearchR
     c.groupOverride = tuning.planGroup;
     c.noMidVariant = tuning.noMidVariant;
     c.noBits = tuning.noBits;
-    c.trace = nullptr;
-#ifdef FPE_TRACE  // profiling builds only (scratch/trace.py); the shipped library never reads the environment per call
-    if (const char* tr = std::getenv("FPE_TRACE_PTR")) c.trace = reinterpret_cast<unsigned long long*>(std::strtoull(tr, nullptr, 0));
-#endif
+    c.reserved = 0;
     // isos_ (cpp:384-394): longEdge = lengthBase + skew*2 in f32 (hpp:666, 683), promoted on assignment to the
     // double member (hpp:679); footSearchRect_.length = searchRadius_*2 and .width = searchRadius_ are f32 values
     // stored in doubles (hpp:700-701); the sums are f64

@@ -28,57 +28,6 @@ namespace fpe {
 
 namespace {
 
-// profiling-only timeline stamps (pc.trace != null): slot = ((block * 8 + cycle) * 16 + point)
-// compiled in only with -DFPE_TRACE (scratch/trace.py); a no-op in the shipped library
-__device__ __forceinline__ void stamp(const PlanConsts& pc, int cyc, int point) {
-#ifdef FPE_TRACE
-    if (pc.trace && blockIdx.x < 256 && cyc < 8 && threadIdx.x == 0)
-        pc.trace[(static_cast<size_t>(blockIdx.x) * 8 + cyc) * 16 + point] = __builtin_readcyclecounter();
-#ifdef FPE_TRACE_ALL_BLOCKS  // (start, end, hardware id) of EVERY block behind the 256 x 8 x 16 stage table: residency studies
-    if (pc.trace && cyc == 6 && point >= 14 && threadIdx.x == 0 && blockIdx.x < 65536) {
-        pc.trace[256 * 8 * 16 + static_cast<size_t>(blockIdx.x) * 4 + (point - 14)] = __builtin_readcyclecounter();
-        if (point == 14) {
-            unsigned hw;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            unsigned xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            pc.trace[256 * 8 * 16 + static_cast<size_t>(blockIdx.x) * 4 + 2] = hw;
-            pc.trace[256 * 8 * 16 + static_cast<size_t>(blockIdx.x) * 4 + 3] = xcc;
-        }
-    }
-#endif
-#else
-    (void)pc;
-    (void)cyc;
-    (void)point;
-#endif
-}
-
-// the same from whichever lane is the first active one (inside lane-divergent regions)
-__device__ __forceinline__ void stamp_any(const PlanConsts& pc, int cyc, int point) {
-#ifdef FPE_TRACE
-    const int first = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x));
-    if (pc.trace && blockIdx.x < 256 && cyc < 8 && static_cast<int>(threadIdx.x) == first)
-        pc.trace[(static_cast<size_t>(blockIdx.x) * 8 + cyc) * 16 + point] = __builtin_readcyclecounter();
-#else
-    (void)pc;
-    (void)cyc;
-    (void)point;
-#endif
-}
-
-__device__ __forceinline__ void stamp_value(const PlanConsts& pc, int cyc, int point, long long v) {
-#ifdef FPE_TRACE
-    if (pc.trace && blockIdx.x < 256 && cyc < 8 && threadIdx.x == 0)
-        pc.trace[(static_cast<size_t>(blockIdx.x) * 8 + cyc) * 16 + point] = v;
-#else
-    (void)pc;
-    (void)cyc;
-    (void)point;
-    (void)v;
-#endif
-}
-
 // Keep a (wave-uniform) value in a vector register: the empty asm hides its uniformity from the compiler.
 __device__ __forceinline__ double in_vgpr(double x) {
     asm volatile("" : "+v"(x));
@@ -648,9 +597,6 @@ __device__ bool candidate_search_grp(const DevMap& m, const PlanConsts& pc, cons
     // rank-table entries of the NEXT round are loaded while the current round is evaluated (from the
     // last register-held round on; searches that end earlier never touch the table)
     int nDi = 0, nDj = 0, nR = c.nRings;
-#ifdef FPE_TRACE
-    long long traceStage = 0;
-#endif
     for (int base = 0; base < M; base += G, ++round) {
         const int k = base + g.sub;
         bool ok = false;
@@ -685,9 +631,6 @@ __device__ bool candidate_search_grp(const DevMap& m, const PlanConsts& pc, cons
             int need = g.bcast(r, G - 1) + pc.footReach;
             if (need > staged && staged >= 0) need = max(need, min(pc.tileH, staged + max(2, staged / 2)));
             if (need > staged) {
-#ifdef FPE_TRACE
-                const long long t0 = __builtin_readcyclecounter();
-#endif
                 if (staged < 0 && !c.rect) {  // the rectangle's own test is six compares: nothing to precompute
                     useColX = column_crossings(m, pc, c, g, reinterpret_cast<double*>(tile + tile_flag_bytes(pc)));
                     // the crossings are read by other lanes of the group (a group never spans wavefronts, and the
@@ -697,9 +640,6 @@ __device__ bool candidate_search_grp(const DevMap& m, const PlanConsts& pc, cons
                 }
                 stage_annulus(m, pc, c, tile, g, staged, need, useColX);
                 staged = need;
-#ifdef FPE_TRACE
-                traceStage += __builtin_readcyclecounter() - t0;
-#endif
             }
         }
         if (k < M) {
@@ -716,17 +656,9 @@ __device__ bool candidate_search_grp(const DevMap& m, const PlanConsts& pc, cons
             const int l = __builtin_ctzll(mask);
             wi = g.bcast(i, l);
             wj = g.bcast(j, l);
-#ifdef FPE_TRACE
-            stamp_value(pc, c.cyc, 11, traceStage);
-            stamp_value(pc, c.cyc, 12, round + 1);
-#endif
             return true;
         }
     }
-#ifdef FPE_TRACE
-    stamp_value(pc, c.cyc, 11, traceStage);
-    stamp_value(pc, c.cyc, 12, round);
-#endif
     return false;
 }
 
@@ -1258,22 +1190,17 @@ __device__ void search_leg(const DevMap& m, const PlanConsts& pc, const SpiralLu
     disc_issue<G, true, kMid>(m, pc, c.cx, c.cy, bb, g, dc);
     DiscLoads dd;
     if (dflt.want != 0) disc_issue<G, false, kMid>(m, pc, dflt.x, dflt.y, dflt.bb, g, dd);
-    stamp(pc, c.cyc, 3);
     CentroidScan sc;
     if (kCentroid) sc = rows_finish(m, pc, s, g, rl);
-    stamp(pc, c.cyc, 4);
     bool defaultOk = true;
     float* scratch = reinterpret_cast<float*>(tile);  // the tile is idle outside the spiral search
     const float zCentre = disc_consume<G, true, kMid>(m, pc, c.cx, c.cy, bb, g, dc, defaultOk, scratch);  // cpp:2012 + cpp:2029
-    stamp(pc, c.cyc, 5);
     CentroidPending cp;
     if (kCentroid) centroid_begin<G, kMid>(m, pc, c, s, sc, zCentre, g, cp);                          // cpp:818-821
-    stamp(pc, c.cyc, 6);
     if (dflt.want != 0) {
         bool unused;
         dflt.z = disc_consume<G, false, kMid>(m, pc, dflt.x, dflt.y, dflt.bb, g, dd, unused, scratch);  // cpp:2289-2301
     }
-    stamp(pc, c.cyc, 7);
     if (defaultOk) {
         no.valid = 1;
         no.source = 0;
@@ -1325,9 +1252,6 @@ typedef unsigned int fpe_v2u __attribute__((ext_vector_type(2)));
 template <bool kStream, class T>
 __device__ __forceinline__ void store_record(T* dst, const T& v) {
     static_assert(sizeof(T) % 8 == 0, "records are stored in 8- or 16-byte pieces");
-#ifdef FPE_DBG_NOSTORE  // measurement only: the store stays in the code (and everything it depends on) but never executes
-    if (reinterpret_cast<uintptr_t>(dst) != 1) return;
-#endif
     if constexpr (!kStream) {
         *dst = v;
     } else if constexpr (sizeof(T) % 16 == 0) {
@@ -1551,7 +1475,6 @@ __device__ __forceinline__ void leg_phase(const DevMap& m, const PlanConsts& pc,
             c.icj = cs.template get<13>(g);
             const bool rectWithin = cs.box_within(1);
             const Submap sm = submap_from_corners(m.g, rbox, rectWithin, c.cx, c.cy);
-            stamp(pc, cyc, 2);
             DefaultDisc dflt;
             dflt.want = (out.default_next != nullptr && centre_usable(nx0, ny)) ? 1 : 0;
             dflt.x = nx0;
@@ -1561,7 +1484,6 @@ __device__ __forceinline__ void leg_phase(const DevMap& m, const PlanConsts& pc,
             search_leg<G, true, kMid>(m, pc, lut, head, c, lk, tile, g, bb, sm, dflt, no, co);
             zDefault = dflt.z;
             haveDbox = true;
-            stamp(pc, cyc, 8);
         }
         if (out.default_next && !haveDbox) {  // cpp:2289-2301 (leg search skipped: radius / centre unusable)
             if (!centre_usable(nx0, ny)) {
@@ -1609,11 +1531,9 @@ __device__ __forceinline__ void leg_phase(const DevMap& m, const PlanConsts& pc,
 // ---- chained plan kernel ------------------------------------------------------------------------------
 // G lanes per leg; a pose owns 4*G consecutive threads; block = max(64, 4*G) threads holds
 // PPB = blockDim / (4*G) poses.  Dynamic LDS per pose = sizeof(PoseShared) + 4 * tileBytes.
-#ifndef FPE_MINWAVES
-#define FPE_MINWAVES 4
-#endif
+constexpr int kMinWavesG16 = 4;  // occupancy the G = 16 register allocation aims at
 template <int G, bool kMid = false>
-__global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? FPE_MINWAVES : 2)) void plan_chained_kernel(DevMap mArg, PlanConsts pc, SpiralLut lut,
+__global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWavesG16 : 2)) void plan_chained_kernel(DevMap mArg, PlanConsts pc, SpiralLut lut,
                                                                            const fpe_pose* __restrict__ poses, int B,
                                                                            int nCycles, fpe_plan_out out) {
     // The map geometry is wave-uniform and would live in 20 scalar registers; this kernel needs more uniform
@@ -1697,13 +1617,11 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? FPE_MI
             const unsigned mask = (gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
             const bool active = (mask >> leg) & 1u;
 
-            stamp(pc, cyc, 0);
             // feet-polygon centres: group t computes track t (getPolygonCenter, cpp:2191, 2265)
             if (leg < 3 && g.sub == 0) {
                 sh.ctr[leg] = polygon_center_x(sh.cur[leg]);
             }
             pose_sync<G>();
-            stamp(pc, cyc, 1);
 
             bool phaseOk;
             if constexpr (G <= 16) {
@@ -1714,7 +1632,6 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? FPE_MI
                 if (active) {
                     leg_phase<G, kMid, true>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out, &lc);
                 }
-                stamp(pc, cyc, 9);
                 constexpr int kPoseLanes = 4 * G;
                 const unsigned long long poseMask = (kPoseLanes == 64) ? ~0ull : (((1ull << (kPoseLanes & 63)) - 1ull) << (slot * kPoseLanes));
                 phaseOk = (__ballot(lc.valid == 0) & poseMask) == 0ull;
@@ -1731,7 +1648,6 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? FPE_MI
                     sh.valid[leg] = 1;  // non-swing legs do not vote
                 }
                 pose_sync<G>();
-                stamp(pc, cyc, 9);
                 // footholdValidation_ = AND of the swing legs' flags (cpp:1323); commit or skip (cpp:1332-1576)
                 phaseOk = (sh.valid[0] & sh.valid[1] & sh.valid[2] & sh.valid[3]) != 0;
                 if (phaseOk && active) {
@@ -1743,7 +1659,6 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? FPE_MI
             }
             pose_sync<G>();
             cycleOk = cycleOk && phaseOk;
-            stamp(pc, cyc, 10);
         }
         if (leg == 0 && g.sub == 0 && live && out.cycle_ok)
             out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
@@ -1811,23 +1726,18 @@ __global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanCo
         bool cycleOk = true;
         for (int ph = 0; ph < nPhases; ++ph) {
             const unsigned mask = (gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
-            stamp(pc, cyc, 0);
             // feet-polygon centres: lane t computes track t (getPolygonCenter, cpp:2191, 2265)
             if (tid < 3) {
                 sh.ctr[tid] = polygon_center_x(sh.cur[tid]);
             }
             if (tid < 4) sh.valid[tid] = 1;  // non-swing legs do not vote
             pose_sync<16>();
-            stamp(pc, cyc, 1);
             for (int leg = 0; leg < 4; ++leg) {
                 if (!((mask >> leg) & 1u)) continue;
                 const LegStatic ls = make_leg_static(pc, pp, leg, m.g.res, lut);
-                stamp(pc, cyc, 13);
                 leg_phase<G>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out);
-                stamp(pc, cyc, 14);
             }
             pose_sync<16>();
-            stamp(pc, cyc, 9);
             // footholdValidation_ = AND of the swing legs' flags (cpp:1323); commit or skip (cpp:1332-1576)
             const bool phaseOk = (sh.valid[0] & sh.valid[1] & sh.valid[2] & sh.valid[3]) != 0;
             if (phaseOk && tid < 36) {
@@ -1839,7 +1749,6 @@ __global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanCo
             }
             pose_sync<16>();
             cycleOk = cycleOk && phaseOk;
-            stamp(pc, cyc, 10);
         }
         if (tid == 0 && out.cycle_ok) out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
         adjY += pc.drift;  // cpp:1578
@@ -2009,7 +1918,6 @@ __global__ __launch_bounds__(256) void canonicalise_layer_kernel(const float* __
             }
         }
     }
-#ifndef FPE_CANON_SCALAR_STORE
     if ((cols & 3) == 0) {  // rows of the destination start 16-byte aligned: four columns per thread, one 16-byte store
         constexpr int kGroups = T / 4, kRowsPerPass = 256 / kGroups;
         const int g4 = threadIdx.x % kGroups, r0 = threadIdx.x / kGroups;
@@ -2024,7 +1932,6 @@ __global__ __launch_bounds__(256) void canonicalise_layer_kernel(const float* __
         }
         return;
     }
-#endif
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
         const int i = iBase + ty + kStep * q, j = jBase + tx;
@@ -2103,12 +2010,9 @@ size_t bitmap_words(int rows, int cols, int* strideW, int* nw);  // fpe_bits.hpp
 // (padding rows / word groups; recycled buffers are dirty) — or null.
 hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int cols, int si, int sj, int srcRowMajor,
                                hipStream_t stream, uint32_t* d_planeWords, float thrDefault, float thrCandidate) {
-#ifndef FPE_CANON_TILE
-#define FPE_CANON_TILE 64
-#endif
+    constexpr int kTile = 64;  // the bit planes are built only by the 64-wide tile
     CanonPlanes pl{nullptr, 0, 0, 0.0f, 0.0f};
     if (d_planeWords) {
-        if (FPE_CANON_TILE != 64) return hipErrorInvalidValue;
         const size_t units = bitmap_words(rows, cols, &pl.strideW, &pl.nw);
         const hipError_t e = hipMemsetAsync(d_planeWords, 0, units * 4, stream);
         if (e != hipSuccess) return e;
@@ -2116,8 +2020,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
         pl.thrD = thrDefault;
         pl.thrC = thrCandidate;
     }
-    dim3 grid((cols + FPE_CANON_TILE - 1) / FPE_CANON_TILE, (rows + FPE_CANON_TILE - 1) / FPE_CANON_TILE);
-    hipLaunchKernelGGL(canonicalise_layer_kernel<FPE_CANON_TILE>, grid, dim3(256), 0, stream, d_src, d_dst, rows, cols, si, sj, srcRowMajor, pl);
+    dim3 grid((cols + kTile - 1) / kTile, (rows + kTile - 1) / kTile);
+    hipLaunchKernelGGL(canonicalise_layer_kernel<kTile>, grid, dim3(256), 0, stream, d_src, d_dst, rows, cols, si, sj, srcRowMajor, pl);
     return hipGetLastError();
 }
 
@@ -2162,23 +2066,3 @@ hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
 }
 
 }  // namespace fpe
-
-#ifdef FPE_FUSED_TIMELINE
-extern "C" int fpe_debug_timeline(void* out, size_t bytes) {
-    return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(fpe::g_fusedTimeline), bytes));
-}
-#endif
-#ifdef FPE_OPT_TRACE
-extern "C" int fpe_debug_opt_trace(void* out, size_t bytes) {
-    return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(fpe::g_optTrace), bytes));
-}
-#endif
-#ifdef FPE_DBG_COUNT_WALKS
-extern "C" int fpe_debug_walk_dbg(double* out) { return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(fpe::g_walkDbg), 64 * 8 * 8)); }
-extern "C" int fpe_debug_walk_counts(unsigned* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(fpe::g_walkWhy), 16);
-    if (reset) { unsigned z[4] = {0, 0, 0, 0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(fpe::g_walkWhy), z, 16); }
-    return static_cast<int>(e);
-}
-#endif
-

@@ -155,7 +155,6 @@ __device__ __forceinline__ double opt_violation(const double (&x)[8], const OptC
 // row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3): six VALU operations and a v_readlane where the butterfly of
 // ds_bpermute exchanges takes six dependent LDS-crossbar round trips (~0.2 us each way on a lone wavefront — the opt track's
 // chain is ONE wavefront's latency, stage after stage).  Lanes without a source keep the operation's identity.
-#ifndef FPE_OPT_NO_DPP
 #define FPE_DPP_STEP(op, ident, v, ctrl, rmask) v = op(v, static_cast<unsigned>(__builtin_amdgcn_update_dpp(static_cast<int>(ident), static_cast<int>(v), ctrl, rmask, 0xF, false)))
 __device__ __forceinline__ unsigned dpp_min_op(unsigned a, unsigned b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned dpp_or_op(unsigned a, unsigned b) { return a | b; }
@@ -189,27 +188,6 @@ __device__ __forceinline__ int wave_inclusive_sum(int x) {  // every lane: the s
     return static_cast<int>(v);
 }
 #undef FPE_DPP_STEP
-#else  // the same by ds_bpermute exchanges (measurement builds)
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned wave_or_u32(unsigned v) {
-    for (int off = 32; off >= 1; off >>= 1) v |= __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ int wave_inclusive_sum(int x) {
-    const int lane = static_cast<int>(threadIdx.x) & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(x, off);
-        if (lane >= off) x += o;
-    }
-    return x;
-}
-#endif
 // wave-wide minimum of a NON-NEGATIVE double (violations, objectives: sums of absolute values; +inf allowed): such doubles order
 // like their bit patterns — the high words' minimum, then the low words' among the lanes that hold it
 __device__ __forceinline__ double wave_min_nonneg(double v) {
@@ -306,12 +284,6 @@ __device__ void opt_solve_columns(const OptConsts& oc, const int (&nIdx)[8], con
 
 __device__ OptBest opt_solve_rows_plain(const OptConsts& oc, const int (&nIdx)[8], const int (&cIdx)[8], const int (&lo)[8], const int (&up)[8],
                                         double lfRow, double rhRow, int lane, int slice, int nSearch, const double (&x)[8]);
-#ifdef FPE_OPT_TRACE  // measurement builds only (profiles/collect_opt_trace.sh): wall-clock stamps of workgroup 0's stages, per gait cycle
-__device__ unsigned long long g_optTrace[256][16];
-#define FPE_OPT_STAMP(k) do { if (blockIdx.x == 0 && lane == 0 && cyc < 256) g_optTrace[cyc][k] = wall_clock64(); } while (0)
-#else
-#define FPE_OPT_STAMP(k) do { } while (0)
-#endif
 constexpr int kOptListCap = 1024;  // surviving points a wavefront lists (LDS, 4 bytes each); more: every point is searched
 // LDS of the listed search: the lists (one per searching wavefront) and, for W > 1, what the wavefronts tell each other about
 // their share of the Dab values (per lane and (c, d) slot: smallest violation, mask of the values that attain it)
@@ -445,7 +417,6 @@ __device__ __forceinline__ void opt_rows_prepare(const OptConsts& oc, const int 
             }
         }
     }
-    if (slice == 0 && nSearch > 1) FPE_OPT_STAMP(14);
     if constexpr (W > 1) {
         if (nSearch > 1) {
 #pragma unroll
@@ -475,7 +446,6 @@ __device__ __forceinline__ void opt_rows_prepare(const OptConsts& oc, const int 
 #pragma unroll
     for (int s = 0; s < kSlots; ++s)
         if (!(myMin[s] == minKey)) good[s] = 0ull;
-    if (slice == 0 && nSearch > 1) FPE_OPT_STAMP(15);
     // list the surviving points in enumeration order: entry = ab | cd << 16.
     // Whether (ab, cd) survives depends on ab only through its Dab value k: the (c, d) pairs of value k are two 64-bit masks
     // (the ballots of bit k of the lanes' `good`), kept by lane k.  A lane then takes an (a, b) pair of the wavefront's share,
@@ -689,9 +659,6 @@ struct OptKernArgs {  // opt_track_kernel's argument list as a struct (the argum
     uint32_t* doneFlag;
     uint32_t doneValue;
 };
-#ifndef FPE_OPT_RELOAD_ARGS
-#define FPE_OPT_RELOAD_ARGS 1
-#endif
 template <int W>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) void opt_track_kernel(DevMap m, PlanConsts pc, OptConsts oc, const fpe_pose* __restrict__ poses, int B,
                                                            int nCycles, const uint8_t* __restrict__ cycleOk, fpe_opt_out out, uint32_t* doneFlag, uint32_t doneValue) {
@@ -720,15 +687,12 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
         if (threadIdx.x < 4) sync[threadIdx.x] = 0;
         __syncthreads();
         if (wave > 0) {  // helper wavefronts: the row search only
-#ifndef FPE_OPT_NO_PRIO
             // wavefront 4 shares its SIMD with wavefront 0, whose column searches are done long before anybody needs them: the helpers
             // go first (they sleep in their polls while wavefront 0 has the critical path), or the seven wait for the one at their exchange
             __builtin_amdgcn_s_setprio(3);
-#endif
             int meets = 0;
             for (int cyc = 0; cyc < nCycles; ++cyc) {
                 opt_wait_ge(&sync[0], cyc + 1);  // the cycle's problem is published
-                if (wave == 1) FPE_OPT_STAMP(10);
                 const OptProblem& prob = probs[cyc & 1];
                 const int run = runOf[cyc & 255];
                 if (run < 0) return;
@@ -744,16 +708,13 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
                 const double lfRowP = prob.lfRow, rhRowP = prob.rhRow;
                 OptRowsState st;
                 opt_rows_prepare<W>(oc, nIdx, cIdx, lo, up, lfRowP, rhRowP, lane, wave - 1, W - 1, &optLists, &sync[2], meets, st, cyc);  // while wavefront 0 decides the columns
-                if (wave == 1) FPE_OPT_STAMP(11);
                 opt_wait_ge(&sync[1], cyc + 1);  // the columns are decided
-                if (wave == 1) FPE_OPT_STAMP(12);
                 double x[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) x[k] = prob.x[k];
                 const OptBest mine = opt_rows_finish<W>(oc, nIdx, cIdx, lo, up, lfRowP, rhRowP, lane, wave - 1, W - 1, x, &optLists, st);
                 if (lane == 0) slots[wave] = mine;
                 opt_arrive(&sync[3], lane);
-                if (wave == 1) FPE_OPT_STAMP(13);
             }
             return;
         }
@@ -801,7 +762,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
         // Round 6, the one-pose form (W > 1): the cycle reads the map's geometry and the constants from the ARGUMENT SEGMENT again
         // (scalar loads through a laundered pointer) instead of holding them — spilled to vector lanes — across the chain, as the
         // one-wavefront-per-pose plan kernels do: the service call 108.3 -> 106.9 us (A/B in one call, three repetitions).
-        constexpr bool kReloadO = FPE_OPT_RELOAD_ARGS != 0 && W > 1;
+        constexpr bool kReloadO = W > 1;
         typedef const OptKernArgs __attribute__((address_space(4))) * OptArgPtr;
         OptArgPtr ka4 = (OptArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         if constexpr (kReloadO) asm volatile("" : "+s"(ka4));
@@ -822,7 +783,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
         SubGeom gm;
         gm.ok = false;
         double nextX = 0.0, nextY = 0.0;
-        FPE_OPT_STAMP(0);
         if (!stopped) {
             // ---- STEP(1) getGaitCycleSearchGridMap, cpp:2307-2408 ----
             nextX = polygon_center_x(sh.cur) + pc.step;  // cpp:2322-2327
@@ -852,7 +812,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
             // (getMapIndex, cpp:965-976)
             const double nx = nextX + biasX, ny = nextY + biasY;
             const int nomI = index_of(nx, gm.g.orgX, gm.g.posX, gm.g.res), nomJ = index_of(ny, gm.g.orgY, gm.g.posY, gm.g.res);
-            FPE_OPT_STAMP(1);
             // ---- STEP(3) checkFootholdUseCentroidMethod(gaitMap_, next, result, beginRow, endRow), cpp:1010-1013 ----
             int code = 6, beginRow = 0, endRow = 0;
             double cenX = 0.0, cenY = 0.0;
@@ -883,7 +842,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
                     if (r0 < 64) blkLo |= mk << r0;
                     else if (r0 < 128) blkHi |= mk << (r0 - 64);
                 }
-                FPE_OPT_STAMP(2);
                 const bool whole = ni * nj > 0 && !g.any(anyBelow);
                 const int minRow = blkLo ? __builtin_ctzll(blkLo) : (blkHi ? 64 + __builtin_ctzll(blkHi) : 0);
                 const int maxRow = blkHi ? 127 - __builtin_clzll(blkHi) : (blkLo ? 63 - __builtin_clzll(blkLo) : 0);
@@ -988,7 +946,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
                 }
                 opt_publish(&sync[0], cyc + 1, lane);
             }
-            FPE_OPT_STAMP(3);
             if (status != 1) opt_solve_columns(oc, nIdx, cIdx, lo, up, lfRow, rhRow, lane, x);
             if (status == 3) minf = opt_objective(x, oc, nIdx, cIdx, lfRow, rhRow);
             if (status < 0) {
@@ -1000,10 +957,8 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
                         for (int k = 0; k < 8; ++k) prob.x[k] = x[k];
                     }
                     opt_publish(&sync[1], cyc + 1, lane);
-                    FPE_OPT_STAMP(4);
                     ++nRuns;
                     opt_wait_ge(&sync[3], (W - 1) * nRuns);  // every helper's best is in place
-                    FPE_OPT_STAMP(5);
                     OptBest o{__builtin_huge_val(), __builtin_huge_val(), 0xFFFFFFFFu, 0u};
                     if (lane < W - 1) o = slots[1 + lane];
                     opt_wave_min(o.key, o.f, o.t);
@@ -1016,7 +971,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
                 }
                 status = opt_solve_end(best, lo, up, x, minf);
             }
-            FPE_OPT_STAMP(6);
             rec.solver_status = static_cast<uint8_t>(status);
             rec.minf = minf;
 #pragma unroll
@@ -1047,7 +1001,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
                     myJ = j;
                 }
             }
-            FPE_OPT_STAMP(7);
             const bool commit = ((okMask[(cyc >> 6) & 3] >> (cyc & 63)) & 1ull) != 0ull;  // footholdValidation_ of the NOMINAL track (cpp:1323-1332)
             // (heights feed the footholds' z and nothing the chain reads later — getPolygonCenter's x uses x and y only: a caller
             // that asked for no footholds, the service's gate-only call, skips the elevation round trip; uniform over the workgroup)
@@ -1076,7 +1029,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
             }
             pose_sync<16>();
             adjY += pc.drift;  // cpp:1578
-            FPE_OPT_STAMP(8);
         }
         if (lane == 0 && out.cycles) out.cycles[oCyc] = rec;
         if (g.sub == 0 && out.footholds) out.footholds[oCyc * 4 + leg] = fh;
@@ -1092,14 +1044,18 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
     // relaxed store behind s_waitcnt 0, end at the same time — the ordering is not what the word costs.)
     if (doneFlag && lane == 0) __hip_atomic_store(doneFlag, doneValue, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+static_assert(kernargs_mirror<decltype(opt_track_kernel<1>)>(
+                  {offsetof(OptKernArgs, m), offsetof(OptKernArgs, pc), offsetof(OptKernArgs, oc), offsetof(OptKernArgs, poses),
+                   offsetof(OptKernArgs, B), offsetof(OptKernArgs, nCycles), offsetof(OptKernArgs, cycleOk), offsetof(OptKernArgs, out),
+                   offsetof(OptKernArgs, doneFlag), offsetof(OptKernArgs, doneValue)},
+                  offsetof(OptKernArgs, doneValue) + sizeof(OptKernArgs::doneValue)),
+              "OptKernArgs must mirror opt_track_kernel's parameters");
 
 hipError_t launch_opt_track(const DevMap& m, const PlanConsts& pc, const OptConsts& oc, const fpe_pose* d_poses, int B, int nCycles,
                             const uint8_t* d_cycleOk, const fpe_opt_out& d_out, hipStream_t stream, uint32_t* doneFlag, uint32_t doneValue) {
     if (B != 1) doneFlag = nullptr;  // (one workgroup per pose: a single word can only speak for one of them)
-#ifndef FPE_OPT_W_SMALL
-#define FPE_OPT_W_SMALL 8
-#endif
-    if (B <= 64) hipLaunchKernelGGL(opt_track_kernel<FPE_OPT_W_SMALL>, dim3(B), dim3(64 * FPE_OPT_W_SMALL), 0, stream, m, pc, oc, d_poses, B, nCycles, d_cycleOk, d_out, doneFlag, doneValue);
+    constexpr int kWSmall = 8;  // wavefronts per pose of small batches
+    if (B <= 64) hipLaunchKernelGGL(opt_track_kernel<kWSmall>, dim3(B), dim3(64 * kWSmall), 0, stream, m, pc, oc, d_poses, B, nCycles, d_cycleOk, d_out, doneFlag, doneValue);
     else hipLaunchKernelGGL(opt_track_kernel<1>, dim3(B), dim3(64), 0, stream, m, pc, oc, d_poses, B, nCycles, d_cycleOk, d_out, doneFlag, doneValue);
     return hipGetLastError();
 }
