@@ -565,6 +565,46 @@ int fpe_foothold_snap(fpe_handle h, const fpe_params* params, const int32_t roi[
 int fpe_foothold_snap_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius,
                              int32_t polygon_kind, const fpe_foothold_snap_out* d_out, void* stream);
 
+/* ---- open-loop centroid method: checkFootholdUseCentroidMethod (cpp:1605-1997) one call per query ------------------
+ * Each query returns exactly the record the plan kernels write to fpe_plan_out.centroid for a leg centred on (cx, cy) with
+ * that search radius: the rectangle {2R, R} around the centre (cpp:1616-1617), the scan of its rows, then the case and the
+ * mean foot height of the result.  A centre outside the map or not finite gives code 6 (getSubmap fails).  The host form
+ * refuses a non-finite search_radius with FPE_E_INVALID_ARG; the device form gives such a query code 6.  The radius has no
+ * upper bound here (the row scan loops).  The device form is asynchronous on `stream` and sees the snapshot current at the
+ * call. */
+typedef struct fpe_centroid_query {
+    double cx, cy;       /* the foothold the method starts from (defaultFoothold, cpp:1605) */
+    float search_radius; /* searchRadius_ of the rectangle {2R, R} (cpp:1616-1617); <= 0: fpe_params.searchRadius */
+    int32_t pad;
+} fpe_centroid_query;    /* 24 bytes */
+int fpe_centroid_legs(fpe_handle h, const fpe_params* params, const fpe_centroid_query* queries, int32_t n,
+                      fpe_centroid_foothold* out);
+int fpe_centroid_legs_device(fpe_handle h, const fpe_params* params, const fpe_centroid_query* d_queries, int32_t n,
+                             fpe_centroid_foothold* d_out, void* stream);
+
+/* ---- dense centroid map: the centroid method at EVERY cell centre of a region ------------------------------------------
+ * Output element (r, c) is exactly the record the open-loop centroid query returns for the centre getPosition(i, j) of cell
+ * (i, j) = (row0 + r, col0 + c) of the current snapshot (canonical indices, as fpe_foothold_map) and search_radius (<= 0
+ * means fpe_params.searchRadius), written as:
+ *   code    the record's code (0..6);
+ *   offset  (row - i, col - j) of the record: the landing cell.  (0, 0) for codes 0, 5 and 6.  The record's exact x / y are
+ *           the SUBMAP's getPosition of the result (cpp:1816) and can differ from getPosition(row, col) in the last bits:
+ *           callers who need them exactly use the open-loop query;
+ *   z       the record's z: the mean foot height at the centre (code 0) or at the result's position (codes 1-4), 0 for 5, 6.
+ * A radius whose rectangle reaches more than 100 rows or columns from its cell (ceil(R / res) + 2 > 100) fails with
+ * FPE_E_UNSUPPORTED and writes nothing.  Any NULL product is skipped (at least one must be given).  roi, snapshot semantics
+ * and pinned destinations behave as in fpe_foothold_map: the host form is synchronous, the device form asynchronous on
+ * `stream`.  literal_discs changes nothing: z always comes from the per-query disc functions. */
+typedef struct fpe_centroid_map_out {
+    uint8_t* code;  /* [n_rows * n_cols] fpe_centroid_foothold.code (0..6) */
+    int8_t* offset; /* [n_rows * n_cols * 2] (row - i, col - j) of the result; (0, 0) for codes 0, 5, 6 */
+    float* z;       /* [n_rows * n_cols] fpe_centroid_foothold.z; 0 for codes 5, 6 */
+} fpe_centroid_map_out;
+int fpe_centroid_map(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius,
+                     const fpe_centroid_map_out* out);
+int fpe_centroid_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius,
+                            const fpe_centroid_map_out* d_out, void* stream);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

@@ -80,6 +80,8 @@ QUERY_DTYPE = np.dtype(
      ("vx", "<f8", (MAX_POLYGON_VERTICES,)), ("vy", "<f8", (MAX_POLYGON_VERTICES,))],
     align=True,
 )
+# fpe_centroid_query: one open-loop centroid-method query (24 bytes)
+CENTROID_QUERY_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("search_radius", "<f4"), ("pad", "<i4")], align=True)
 MSG_FOOTHOLD_DTYPE = np.dtype(
     [("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("foot_id", "u1"), ("gait_cycle_id", "u1"), ("pad", "u1", (6,))],
     align=True,
@@ -190,6 +192,16 @@ class FootholdSnapOut(C.Structure):
     _fields_ = [("offset", C.c_void_p), ("source", C.c_void_p), ("z", C.c_void_p)]
 
 
+class CentroidQuery(C.Structure):
+    """fpe_centroid_query: the foothold the centroid method starts from and its search radius (<= 0: params.searchRadius)."""
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("search_radius", C.c_float), ("pad", C.c_int32)]
+
+
+class CentroidMapOut(C.Structure):
+    """fpe_centroid_map_out: products of a dense centroid-map call (any pointer may be NULL)."""
+    _fields_ = [("code", C.c_void_p), ("offset", C.c_void_p), ("z", C.c_void_p)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the ctypes structures below mirror that layout
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -242,6 +254,10 @@ EXPORTED_SYMBOLS = [
     "fpe_foothold_map_device",
     "fpe_foothold_snap",
     "fpe_foothold_snap_device",
+    "fpe_centroid_legs",
+    "fpe_centroid_legs_device",
+    "fpe_centroid_map",
+    "fpe_centroid_map_device",
     "fpe_spiral_offsets",
     "fpe_tile_halfwidth",
     "fpe_algorithmic_bytes_per_foothold",
@@ -328,6 +344,10 @@ def lib():
     L.fpe_foothold_map_device.argtypes = [vp, vp, vp, C.POINTER(FootholdMapOut), vp]
     L.fpe_foothold_snap.argtypes = [vp, vp, vp, f32, i32, C.POINTER(FootholdSnapOut)]
     L.fpe_foothold_snap_device.argtypes = [vp, vp, vp, f32, i32, C.POINTER(FootholdSnapOut), vp]
+    L.fpe_centroid_legs.argtypes = [vp, vp, vp, i32, vp]
+    L.fpe_centroid_legs_device.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.fpe_centroid_map.argtypes = [vp, vp, vp, f32, C.POINTER(CentroidMapOut)]
+    L.fpe_centroid_map_device.argtypes = [vp, vp, vp, f32, C.POINTER(CentroidMapOut), vp]
     L.fpe_spiral_offsets.argtypes = [i32, vp, i32]
     L.fpe_tile_halfwidth.argtypes = [f32, f32, f64]
     L.fpe_algorithmic_bytes_per_foothold.restype = f64

@@ -71,6 +71,19 @@ size_t foothold_snap_literal_scratch_bytes();
 hipError_t launch_foothold_snap_literal(const DevMap& m, const PlanConsts& pc, const SnapConsts& sc, const SpiralLut& lut,
                                         const FootmapRoi& roi, void* scratch, int8_t* d_offset, uint8_t* d_source, float* d_z,
                                         hipStream_t stream);
+// open-loop centroid method (fpe_kernels.hip) and the dense centroid map (fpe_centroidmap.hpp part of it)
+hipError_t launch_centroid_legs(const DevMap& m, const PlanConsts& pc, float defaultR, const fpe_centroid_query* d_q, int n,
+                                fpe_centroid_foothold* d_out, hipStream_t stream);
+struct CmapConsts {
+    float Rf;
+    int32_t H;
+    int32_t rb, re;
+    int32_t nwr;
+};
+bool centroid_map_consts(const MapGeom& g, const FootmapRoi& roi, float R, CmapConsts& cc);
+size_t centroid_map_scratch_bytes(const FootmapRoi& roi, const CmapConsts& cc);
+hipError_t launch_centroid_map(const DevMap& m, const PlanConsts& pc, const CmapConsts& cc, const FootmapRoi& roi, void* scratch,
+                               uint8_t* d_code, int8_t* d_offset, float* d_z, hipStream_t stream);
 }  // namespace fpe
 
 namespace {
@@ -684,6 +697,41 @@ hipError_t run_foothold_snap(fpe_engine* h, const CallPlan& cp, const fpe::Footm
     hipError_t e = hipMallocAsync(&scratch, fpe::foothold_snap_literal_scratch_bytes(), stream);
     if (e != hipSuccess) return e;
     e = fpe::launch_foothold_snap_literal(dev_map(*cp.snap), cp.pc, sc, h->lut(), r, scratch, d_offset, d_source, d_z, stream);
+    const hipError_t f = hipFreeAsync(scratch, stream);
+    return e != hipSuccess ? e : f;
+}
+
+// fpe_centroid_map*: prepare_call (the plan constants of the disc functions), the region and the dense constants; `stream`
+// ordered after the snapshot's upload.  A rectangle over the dense kernels' reach is FPE_E_UNSUPPORTED.
+int prepare_centroid_map(fpe_engine* h, const fpe_params* params, const int32_t roi[4], float searchRadius, bool anyOut, CallPlan& cp,
+                         fpe::FootmapRoi& r, fpe::CmapConsts& cc, hipStream_t stream) {
+    if (!h || !params) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    if (!anyOut) return fail(FPE_E_INVALID_ARG, "no output requested");
+    if (!std::isfinite(searchRadius)) return fail(FPE_E_INVALID_ARG, "bad search radius");
+    int rc = prepare_call(h, params, 0.0f, cp, stream, false);
+    if (rc != FPE_OK) return rc;
+    const fpe::MapGeom& g = cp.snap->g;
+    if (roi) {
+        if (roi[0] < 0 || roi[1] < 0 || roi[2] <= 0 || roi[3] <= 0 || static_cast<int64_t>(roi[0]) + roi[2] > g.rows ||
+            static_cast<int64_t>(roi[1]) + roi[3] > g.cols)
+            return fail(FPE_E_INVALID_ARG, "region outside the map or empty");
+        r = fpe::FootmapRoi{roi[0], roi[1], roi[2], roi[3]};
+    } else {
+        r = fpe::FootmapRoi{0, 0, g.rows, g.cols};
+    }
+    const float R = searchRadius > 0.0f ? searchRadius : params->searchRadius;
+    if (!fpe::centroid_map_consts(g, r, R, cc))
+        return fail(FPE_E_UNSUPPORTED, "search radius over the dense centroid map's reach (ceil(R / res) + 2 > 100 cells)");
+    return FPE_OK;
+}
+
+// Queue the products of a prepared dense centroid call on `stream` (its scratch is stream-ordered)
+hipError_t run_centroid_map(const CallPlan& cp, const fpe::FootmapRoi& r, const fpe::CmapConsts& cc, uint8_t* d_code, int8_t* d_offset,
+                            float* d_z, hipStream_t stream) {
+    void* scratch = nullptr;
+    hipError_t e = hipMallocAsync(&scratch, fpe::centroid_map_scratch_bytes(r, cc), stream);
+    if (e != hipSuccess) return e;
+    e = fpe::launch_centroid_map(dev_map(*cp.snap), cp.pc, cc, r, scratch, d_code, d_offset, d_z, stream);
     const hipError_t f = hipFreeAsync(scratch, stream);
     return e != hipSuccess ? e : f;
 }
@@ -1700,6 +1748,99 @@ int fpe_foothold_snap(fpe_handle h, const fpe_params* params, const int32_t roi[
     FPE_HIP(run_foothold_snap(h, cp, r, sc, bitPath, out->offset ? reinterpret_cast<int8_t*>(cx.dev + off[0]) : nullptr,
                               out->source ? cx.dev + off[1] : nullptr, out->z ? reinterpret_cast<float*>(cx.dev + off[2]) : nullptr,
                               cx.stream));
+    for (int k = 0; k < 3; ++k)
+        if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? dst[k] : cx.pinned + off[k], cx.dev + off[k], len[k], hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    for (int k = 0; k < 3; ++k)
+        if (len[k] && !pinned[k]) std::memcpy(dst[k], cx.pinned + off[k], len[k]);
+    return FPE_OK;
+}
+
+int fpe_centroid_legs_device(fpe_handle h, const fpe_params* params, const fpe_centroid_query* d_queries, int32_t n,
+                             fpe_centroid_foothold* d_out, void* stream) {
+    if (!d_queries || !d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    int rc = prepare_call(h, params, 0.0f, cp, st, false);
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(fpe::launch_centroid_legs(dev_map(*cp.snap), cp.pc, params->searchRadius, d_queries, n, d_out, st));
+    cp.snap->note_async_use();
+    return FPE_OK;
+}
+
+int fpe_centroid_legs(fpe_handle h, const fpe_params* params, const fpe_centroid_query* queries, int32_t n, fpe_centroid_foothold* out) {
+    if (!queries || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    for (int k = 0; k < n; ++k)  // any centre is a query (code 6 off the map); a radius must be a number
+        if (!std::isfinite(queries[k].search_radius)) return fail(FPE_E_INVALID_ARG, "bad search radius");
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    const size_t szQ = align256(static_cast<size_t>(n) * sizeof(fpe_centroid_query));
+    const size_t szO = align256(static_cast<size_t>(n) * sizeof(fpe_centroid_foothold));
+    CallPlan cp;  // (before the lease, as in plan_host)
+    CtxLease lease(h->ctxPool);
+    CallCtx& cx = *lease.ctx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(szQ + szO));
+    cx.inFlight = true;
+    int rc = prepare_call(h, params, 0.0f, cp, cx.stream, false);
+    if (rc != FPE_OK) return rc;
+    std::memcpy(cx.pinned, queries, static_cast<size_t>(n) * sizeof(fpe_centroid_query));
+    FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, static_cast<size_t>(n) * sizeof(fpe_centroid_query), hipMemcpyHostToDevice, cx.stream));
+    FPE_HIP(fpe::launch_centroid_legs(dev_map(*cp.snap), cp.pc, params->searchRadius, reinterpret_cast<const fpe_centroid_query*>(cx.dev),
+                                      n, reinterpret_cast<fpe_centroid_foothold*>(cx.dev + szQ), cx.stream));
+    FPE_HIP(hipMemcpyAsync(cx.pinned + szQ, cx.dev + szQ, static_cast<size_t>(n) * sizeof(fpe_centroid_foothold), hipMemcpyDeviceToHost,
+                           cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    std::memcpy(out, cx.pinned + szQ, static_cast<size_t>(n) * sizeof(fpe_centroid_foothold));
+    return FPE_OK;
+}
+
+int fpe_centroid_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius,
+                            const fpe_centroid_map_out* d_out, void* stream) {
+    if (!d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    fpe::FootmapRoi r{};
+    fpe::CmapConsts cc{};
+    int rc = prepare_centroid_map(h, params, roi, search_radius, d_out->code || d_out->offset || d_out->z, cp, r, cc, st);
+    if (rc != FPE_OK) return rc;
+    cp.snap->note_async_use();  // (before the launch, as in fpe_foothold_map_device)
+    FPE_HIP(run_centroid_map(cp, r, cc, d_out->code, d_out->offset, d_out->z, st));
+    return FPE_OK;
+}
+
+int fpe_centroid_map(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius, const fpe_centroid_map_out* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    CallPlan cp;  // (before the lease, as in plan_host)
+    CtxLease lease(h->ctxPool);
+    CallCtx& cx = *lease.ctx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(0));  // the stream
+    fpe::FootmapRoi r{};
+    fpe::CmapConsts cc{};
+    int rc = prepare_centroid_map(h, params, roi, search_radius, out->code || out->offset || out->z, cp, r, cc, cx.stream);
+    if (rc != FPE_OK) return rc;
+    const size_t n = static_cast<size_t>(r.nr) * r.nc;
+    // device products in the call's arena; a pinned destination is written by DMA, any other through the pinned arena
+    void* dst[3] = {out->code, out->offset, out->z};
+    const size_t len[3] = {out->code ? n : 0, out->offset ? 2 * n : 0, out->z ? n * sizeof(float) : 0};
+    bool pinned[3];
+    size_t off[3], end = 0, stage = 0;
+    for (int k = 0; k < 3; ++k) {
+        pinned[k] = dst[k] && is_pinned_host(dst[k]);
+        off[k] = end;
+        end = align256(end + len[k]);
+        if (len[k] && !pinned[k]) stage = off[k] + len[k];
+    }
+    FPE_HIP(cx.reserve(std::max(end, stage)));
+    cx.inFlight = true;
+    FPE_HIP(run_centroid_map(cp, r, cc, out->code ? cx.dev + off[0] : nullptr,
+                             out->offset ? reinterpret_cast<int8_t*>(cx.dev + off[1]) : nullptr,
+                             out->z ? reinterpret_cast<float*>(cx.dev + off[2]) : nullptr, cx.stream));
     for (int k = 0; k < 3; ++k)
         if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? dst[k] : cx.pinned + off[k], cx.dev + off[k], len[k], hipMemcpyDeviceToHost, cx.stream));
     FPE_HIP(hipStreamSynchronize(cx.stream));

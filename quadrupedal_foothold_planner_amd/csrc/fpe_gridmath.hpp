@@ -176,6 +176,40 @@ FPE_HD Submap submap_info(const MapGeom& g, double px, double py, double lx, dou
     return s;
 }
 
+// One axis of submap_info: x (org, pos, len, base of the map's x side, n = rows, p = px, l = lx) or y (the y side, n = cols,
+// p = py, l = ly).  Every quantity of submap_info's x side depends on px alone and every one of its y side on py alone, and
+// its ok is the AND of the per-axis tests, so for s = submap_info(g, px, py, lx, ly): s.ok == (x.ok && y.ok) and, when it
+// holds, (s.i0, s.ni, s.baseX) == (x.i0, x.ni, x.base) and likewise for y.  Same expressions in the same order.
+struct SubmapAxis {
+    double base;  // submap position + (0.5*sublen - 0.5*res) on this axis
+    int32_t i0, ni;
+    int32_t ok, pad;
+};
+FPE_HD SubmapAxis submap_axis(double org, double pos, double len, double base, double res, double rinv, int n, double p, double l) {
+    SubmapAxis a;
+    a.ok = 0;
+    a.pad = 0;
+    a.i0 = a.ni = 0;
+    a.base = 0.0;
+    const double tl = bound_axis(p - (-0.5 * l), org, pos, len);
+    a.i0 = index_of_fast(tl, org, pos, res, rinv);
+    if (!within_axis(tl, org, pos, len)) return a;
+    const double br = bound_axis(p + (-0.5 * l), org, pos, len);
+    const int i1 = index_of_fast(br, org, pos, res, rinv);
+    if (!within_axis(br, org, pos, len)) return a;
+    if (!(a.i0 >= 0 && a.i0 < n)) return a;  // getPositionFromIndex(topLeft) range check
+    if (i1 >= n) return a;                    // getBufferRegionsForSubmap
+    const double corner = cell_pos(base, res, a.i0) - (-(0.5 * res));
+    a.ni = i1 - a.i0 + 1;
+    const double subLen = static_cast<double>(a.ni) * res;
+    const double subOrg = 0.5 * subLen;
+    const double subPos = corner - subOrg;
+    if (!within_axis(p, subOrg, subPos, subLen)) return a;
+    a.base = subPos + (subOrg - 0.5 * res);
+    a.ok = 1;
+    return a;
+}
+
 // Polygon::isInside (PNPOLY), vertices in arrays.  cpp:2138.
 FPE_HD bool polygon_inside(const double* vx, const double* vy, int n, double px, double py) {
     int cross = 0;

@@ -1830,6 +1830,63 @@ __global__ __launch_bounds__(256) void search_legs_kernel(DevMap m, PlanConsts p
     if (g.sub == 0) store_foothold(out + q, no, 0, 0);
 }
 
+__device__ __forceinline__ void store_centroid(fpe_centroid_foothold* dst, const CentroidOut& co) {
+    fpe_centroid_foothold cf;
+    cf.x = co.x; cf.y = co.y; cf.z = co.z; cf.row = co.row; cf.col = co.col;
+    cf.code = static_cast<uint8_t>(co.code); cf.pad[0] = cf.pad[1] = cf.pad[2] = 0;
+    store_record<false>(dst, cf);
+}
+
+// Open-loop checkFootholdUseCentroidMethod (cpp:1605-1997), fpe_centroid_legs*: the lane-group layout of search_legs_kernel
+// (G lanes per query, the group's LDS tile as the ordered-sum scratch), the plan kernels' functions in their order: the
+// rectangle's submap, the row scan, the centre disc's mean height (code 0 only), then the case and its result disc.
+// defaultR: the radius of a query whose search_radius is <= 0.  A centre off the usable range or a non-finite radius: code 6.
+template <int G, bool kMid = false>
+__global__ __launch_bounds__(256) void centroid_legs_kernel(DevMap m, PlanConsts pc, float defaultR,
+                                                             const fpe_centroid_query* __restrict__ queries, int n,
+                                                             fpe_centroid_foothold* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = static_cast<int>(threadIdx.x);
+    const int w = tid / G;
+    const Grp<G> g(tid);
+    const int q = blockIdx.x * (256 / G) + w;
+    float* scratch = reinterpret_cast<float*>(smem + static_cast<size_t>(w) * tile_total_bytes(pc));
+    if (q >= n) return;
+    const fpe_centroid_query qr = queries[q];
+    const float Rf = qr.search_radius > 0.0f ? qr.search_radius : defaultR;
+    CentroidOut co;
+    co.x = co.y = 0.0;
+    co.z = 0.0f;
+    co.row = co.col = -1;
+    co.code = 6;
+    if (centre_usable(qr.cx, qr.cy) && __builtin_isfinite(Rf)) {
+        LegCtx c;
+        c.cx = qr.cx;
+        c.cy = qr.cy;
+        c.ici = c.icj = -1;
+        const Submap s = submap_info(m.g, c.cx, c.cy, static_cast<double>(Rf * 2), static_cast<double>(Rf));  // cpp:1615-1627
+        const CentroidScan sc = centroid_scan(m, pc, s, g);
+        float zCentre = 0.0f;
+        if (sc.whole) {  // the whole-region-valid result: getIndex and mean height of the centre (cpp:1684-1689)
+            const Box b0{c.cx, c.cy, pc.rf, pc.rf};
+            Corners<G, 8> cs;
+            cs.eval(m.g, g, b0, b0, b0, b0, 0x2u);  // quantities 4,5 = getIndex(centre)
+            const BBox bb = cs.template bbox<0>(g);
+            c.ici = cs.template get<4>(g);
+            c.icj = cs.template get<5>(g);
+            DiscLoads dc;
+            disc_issue<G, true, kMid>(m, pc, c.cx, c.cy, bb, g, dc);
+            bool unused;
+            zCentre = disc_consume<G, true, kMid>(m, pc, c.cx, c.cy, bb, g, dc, unused, scratch);
+        }
+        CentroidPending cp;
+        centroid_begin<G, kMid>(m, pc, c, s, sc, zCentre, g, cp);
+        centroid_end<G, kMid>(m, pc, g, cp, scratch);
+        co = cp.o;
+    }
+    if (g.sub == 0) store_centroid(out + q, co);
+}
+
 // ---- map ingest: grid_map_msgs layout -> canonical row-major start-index-0 layer --------------------
 // src is column-major with circular-buffer start index (si, sj): unwrapped (i, j) lives at buffer
 // index ((i + si) % rows, (j + sj) % cols) (grid_map getBufferIndexFromIndex).  64 x 64 tiles through
@@ -2005,6 +2062,20 @@ hipError_t launch_search_legs(const DevMap& m, const PlanConsts& pc, const Spira
     return hipGetLastError();
 }
 
+// The group size and variant of launch_search_legs (the same disc functions, hence the same heights); LDS = the groups' tiles.
+size_t centroid_lds_bytes(const PlanConsts& pc) { return static_cast<size_t>(256 / search_group_size(pc)) * tile_bytes(pc); }
+hipError_t launch_centroid_legs(const DevMap& m, const PlanConsts& pc, float defaultR, const fpe_centroid_query* d_q, int n,
+                                fpe_centroid_foothold* d_out, hipStream_t stream) {
+    const size_t lds = centroid_lds_bytes(pc);
+    if (search_group_size(pc) == 8 && mid_variant(pc, m.g.res))
+        hipLaunchKernelGGL((centroid_legs_kernel<8, true>), dim3((n + 31) / 32), dim3(256), lds, stream, m, pc, defaultR, d_q, n, d_out);
+    else if (search_group_size(pc) == 8)
+        hipLaunchKernelGGL(centroid_legs_kernel<8>, dim3((n + 31) / 32), dim3(256), lds, stream, m, pc, defaultR, d_q, n, d_out);
+    else
+        hipLaunchKernelGGL(centroid_legs_kernel<64>, dim3((n + 3) / 4), dim3(256), lds, stream, m, pc, defaultR, d_q, n, d_out);
+    return hipGetLastError();
+}
+
 size_t bitmap_words(int rows, int cols, int* strideW, int* nw);  // fpe_bits.hpp (part two of this translation unit)
 // d_planeWords: also build the bit planes of the destination layer for (thrDefault, thrCandidate) — the buffer zeroed here first
 // (padding rows / word groups; recycled buffers are dirty) — or null.
@@ -2035,6 +2106,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_footmap.hpp"
 // ---- part five: the dense snap map (fpe_foothold_snap*) ------------------------------------------------------
 #include "fpe_footsnap.hpp"
+// ---- part six: the dense centroid map (fpe_centroid_map*) ----------------------------------------------------
+#include "fpe_centroidmap.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<16>),
@@ -2061,8 +2134,19 @@ hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_legs_kernel<8, true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(search_legs_kernel<64>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_legs_kernel<64>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(centroid_legs_kernel<8>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(centroid_legs_kernel<8, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(centroid_legs_kernel<64>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
+    if (e != hipSuccess) return e;
+    return set_max_lds_centroid_map(searchBytes);
 }
 
 }  // namespace fpe

@@ -14,9 +14,9 @@ import threading
 import numpy as np
 
 from . import _capi
-from ._capi import (CENTROID_DTYPE, FOOTHOLD_DTYPE, GLOBAL_FOOTHOLDS_DTYPE, OPT_CYCLE_DTYPE, OPT_FOOTHOLD_DTYPE, OPT_PARAMS_DTYPE,
+from ._capi import (CENTROID_DTYPE, CENTROID_QUERY_DTYPE, FOOTHOLD_DTYPE, GLOBAL_FOOTHOLDS_DTYPE, OPT_CYCLE_DTYPE, OPT_FOOTHOLD_DTYPE, OPT_PARAMS_DTYPE,
                     PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
-                    FootholdMapOut, FootholdSnapOut, MapDesc, OptOut, PlanOut, ptr)
+                    CentroidMapOut, FootholdMapOut, FootholdSnapOut, MapDesc, OptOut, PlanOut, ptr)
 
 # products of a chained plan in the order of fpe_plan_out's fields (= the order of the engine's device arena)
 PRODUCT_ORDER = ("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status", "selected_packed")
@@ -356,6 +356,52 @@ class FootholdPlanner:
         so = FootholdSnapOut(C.c_void_p(d_offset_ptr or None), C.c_void_p(d_source_ptr or None), C.c_void_p(d_z_ptr or None))
         self._check(self._lib.fpe_foothold_snap_device(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0),
                                                        self._polygon_kind(polygon), C.byref(so), C.c_void_p(stream or 0)))
+
+    # ---- open-loop centroid method and the dense centroid map (checkFootholdUseCentroidMethod, cpp:1605-1997) ---------------
+    def centroid_legs(self, queries):
+        """fpe_centroid_legs: one CENTROID_DTYPE record per CENTROID_QUERY_DTYPE query (cx, cy, search_radius <= 0 =
+        params.searchRadius)."""
+        queries = np.ascontiguousarray(queries, dtype=CENTROID_QUERY_DTYPE).reshape(-1)
+        out = np.zeros(queries.shape[0], dtype=CENTROID_DTYPE)
+        self._check(self._lib.fpe_centroid_legs(self._h, ptr(self.params), ptr(queries), queries.shape[0], ptr(out)))
+        return out
+
+    def centroid_legs_device(self, d_queries_ptr, n, d_out_ptr, stream=0):
+        """Device form: DEVICE pointers to n queries and n records, asynchronous on `stream`."""
+        self._check(self._lib.fpe_centroid_legs_device(self._h, ptr(self.params), C.c_void_p(d_queries_ptr), int(n),
+                                                       C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)))
+
+    def centroid_map(self, roi=None, search_radius=None, products=("code", "offset", "z")):
+        """fpe_centroid_map on the current map: {"code": uint8 [n_rows, n_cols] (0..6), "offset": int8 [n_rows, n_cols, 2]
+        (row - i, col - j) of the landing cell, "z": float32 [n_rows, n_cols]} for the requested products.  roi as in
+        foothold_map; search_radius None = params.searchRadius."""
+        unknown = set(products) - {"code", "offset", "z"}
+        if unknown:
+            raise ValueError(f"unknown centroid-map products {sorted(unknown)}")
+        r = self._roi(roi)
+        if r is not None:
+            shape = (max(int(r[2]), 0), max(int(r[3]), 0))
+        else:
+            d = MapDesc()
+            self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
+            shape = (d.rows, d.cols)
+        out = {}
+        if "code" in products:
+            out["code"] = np.empty(shape, np.uint8)
+        if "offset" in products:
+            out["offset"] = np.empty(shape + (2,), np.int8)
+        if "z" in products:
+            out["z"] = np.empty(shape, np.float32)
+        co = CentroidMapOut(ptr(out.get("code")), ptr(out.get("offset")), ptr(out.get("z")))
+        self._check(self._lib.fpe_centroid_map(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0), C.byref(co)))
+        return out
+
+    def centroid_map_device(self, d_code_ptr, d_offset_ptr, d_z_ptr, roi=None, search_radius=None, stream=0):
+        """Device form: DEVICE pointers (0 = product not wanted), asynchronous on `stream`."""
+        r = self._roi(roi)
+        co = CentroidMapOut(C.c_void_p(d_code_ptr or None), C.c_void_p(d_offset_ptr or None), C.c_void_p(d_z_ptr or None))
+        self._check(self._lib.fpe_centroid_map_device(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0), C.byref(co),
+                                                      C.c_void_p(stream or 0)))
 
     # ---- the service (globalFootholdPlan, cpp:539-1602): response content for one pose ---------------------
     @staticmethod
