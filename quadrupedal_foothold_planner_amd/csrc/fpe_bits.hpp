@@ -2274,33 +2274,18 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
         eB = load_cell(m.elev, boxB + laneCell);
         eMidB = load_cell(m.elev, boxB + colsU + 1u);
     }
-    // In the shadow of that round trip: the rows of the search rectangle, which only a spiral search uses — but most
-    // wavefronts have one leg in eight that needs it (88 % of the headline's cycles), and these forty instructions
-    // would otherwise sit on the dependent chain behind the default check.  (Moving the candidates' window addresses
-    // and the chain-independent unit fields up here as well changed nothing.)
+    // In the shadow of that round trip: whether this lane's row of the five around the centre (FastRanks) lies in the search
+    // rectangle, which only a spiral search uses — but most wavefronts have one leg in eight that needs it (88 % of the
+    // headline's cycles), and otherwise this would sit on the dependent chain behind the default check.  The rectangle's rows are
+    // [min{i : x_i < xhi}, max{i : x_i >= xlo}] (rectangle_index_bounds) and cell centres x_i are non-increasing in i, so row i
+    // is one of them iff xlo <= x_i < xhi: the lane tests ITS row's centre, nobody derives the interval's ends (a floor, a
+    // clamp and a conversion per end, four corrected estimates over a ballot: fifty instructions a cycle).
     const bool fastSpiral = __ballot(ls.polyKind != 0 || lk.nRings < 4 || lk.nCand < 16) == 0ull && pc.nFoot <= 1;  // uniform
-    int iA = 0, iB = -1;
-    if (fastSpiral) {
-        const double r = static_cast<double>(ls.Rf);
-        const double xhi = nx2 + r, xlo = nx2 - r;  // getSearchPolygon around the NOMINAL track (cpp:2496-2517)
-        double qh = floor((m.g.baseX - xhi) * m.g.rinv), ql = floor((m.g.baseX - xlo) * m.g.rinv);
-        qh = fmin(fmax(qh, -1.0e9), 1.0e9);
-        ql = fmin(fmax(ql, -1.0e9), 1.0e9);
-        const int eH = static_cast<int>(qh), eL = static_cast<int>(ql);
-        // lane q & 3: 0 P(eH), 1 P(eH + 1) with P(i) = x_i < xhi;  2 Q(eL + 1), 3 Q(eL) with Q(i) = x_i >= xlo
-        const bool isLo = (g.sub & 2) != 0;
-        const int odd = g.sub & 1;
-        const int tLo = eL + 1 - odd, tHi = eH + odd;
-        const int tq = isLo ? tLo : tHi;
-        const double lim = isLo ? xlo : xhi;
-        const double xt = cell_pos(m.g.baseX, m.g.res, tq);
-        const bool predLo = xt >= lim, predHi = xt < lim;
-        const bool pred = isLo ? predLo : predHi;
-        const unsigned pb = static_cast<unsigned>(g.ballot(pred));
-        const int iA1 = (pb & 2u) ? eH + 1 : eH + 2, iB1 = (pb & 8u) ? eL : eL - 1;
-        iA = (pb & 1u) ? eH : iA1;
-        iB = (pb & 4u) ? eL + 1 : iB1;
-    }
+    const int iFast = iw0 + g.sub + G * fk.slot;
+    const double rS = static_cast<double>(ls.Rf);
+    const double xFast = cell_pos(m.g.baseX, m.g.res, iFast);
+    // getSearchPolygon around the NOMINAL track (cpp:2496-2517)
+    const bool rowInside = (xFast < nx2 + rS) & (xFast >= nx2 - rS);
     WinRows<NRL, KW> w;
     win_finish<NRL, KW>(jw0, grp, w);
     const CentroidScan sc = rows_from_bits<G, NRL, KW>(sm, w, g, iw0, jw0, &ye.rmask);
@@ -2383,8 +2368,8 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
                 Fs = fk.slot == k ? w.F[k][0] : Fs;
                 Cs = fk.slot == k ? w.C[k][0] : Cs;
             }
-            const int i = iw0 + g.sub + G * fk.slot;
-            const unsigned inside = (i >= iA && i <= iB) ? ye.pmask : 0u;
+            const int i = iFast;
+            const unsigned inside = rowInside ? ye.pmask : 0u;
             unsigned P = ~Fs | (~Cs & inside);
             // cells outside the map pass every test (their F bit is 0) but are no candidates: windows over the map's edge only
             const bool border = (iw0 < 0) | (jw0 < 0) | (iw0 + G * NRL > m.g.rows) | (jw0 + 32 > m.g.cols);
