@@ -84,6 +84,87 @@ def assert_plan_equal(eng, ora, swing_only_mask=None):
 
 
 ALL_PRODUCTS = ("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status", "selected_packed")
+DEFAULT_PRODUCTS = ALL_PRODUCTS[:7]  # what planner.plan() asks for when `products` is left out
+
+
+def product_shape(products):
+    """The product shape the engine compiles kernels for (csrc/fpe_bits.hpp::product_shape): 2 = all seven base products,
+    1 = nominal track only (none of centroid / default / stance / pose_status), 0 = any other combination (generic)."""
+    s = set(products)
+    if s.issuperset(DEFAULT_PRODUCTS):
+        return 2
+    if not s & {"centroid", "default", "stance", "pose_status"}:
+        return 1
+    return 0
+
+
+def _assert_exchange_equal(rec, ora_nominal, what):
+    """rec: SELECTED_DTYPE records (the 16-byte record, or the unpacked 8-byte one) against the ORACLE's nominal record."""
+    assert rec.shape == ora_nominal.shape
+    for f in ("valid", "source", "row", "col"):
+        bad = np.nonzero(rec[f] != ora_nominal[f])
+        assert bad[0].size == 0, f"{what}.{f}: {bad[0].size} mismatches, first at {tuple(b[0] for b in bad)}: " \
+                                 f"engine {rec[f][bad][0]} oracle {ora_nominal[f][bad][0]}"
+    n_cycles = rec.shape[-2]
+    assert np.array_equal(rec["foot_id"], np.broadcast_to(np.arange(4, dtype=np.uint8), rec.shape)), f"{what}.foot_id"
+    assert np.array_equal(rec["gait_cycle_id"], np.broadcast_to(np.arange(n_cycles, dtype=np.uint8)[:, None], rec.shape)), \
+        f"{what}.gait_cycle_id"
+    dz = np.abs(rec["z"].astype(np.float64) - ora_nominal["z"].astype(np.float64))
+    assert np.all(dz <= Z_TOL), f"{what}.z: max |dz| = {dz.max()}"
+
+
+def assert_products_equal(eng, ora, products):
+    """The bars of assert_plan_equal for exactly the products asked for (any subset of ALL_PRODUCTS): indices, flags, x and
+    y bit-exact, |dz| <= Z_TOL.  The exchange records are compared with the oracle's nominal record, not the engine's own
+    (a subset need not hold `nominal`).  The engine must return what was asked for and nothing else."""
+    products = tuple(products)
+    assert len(products) > 0 and set(products) <= set(ALL_PRODUCTS), products
+    assert set(eng) == set(products), f"asked for {sorted(products)}, engine returned {sorted(eng)}"
+    for k in products:
+        if k == "nominal":
+            assert_nominal_equal(eng["nominal"], ora["nominal"])
+            n_cycles = eng["nominal"].shape[-2]
+            assert np.array_equal(eng["nominal"]["foot_id"], np.broadcast_to(np.arange(4, dtype=np.uint8), eng["nominal"].shape))
+            assert np.array_equal(eng["nominal"]["gait_cycle_id"],
+                                  np.broadcast_to(np.arange(n_cycles, dtype=np.uint8)[:, None], eng["nominal"].shape))
+        elif k == "centroid":
+            assert_centroid_equal(eng["centroid"], ora["centroid"])
+        elif k == "cycle_ok":
+            assert eng["cycle_ok"].shape == ora["cycle_ok"].shape and np.array_equal(eng["cycle_ok"], ora["cycle_ok"]), "cycle_ok differs"
+        elif k == "stance":
+            assert eng["stance"].shape == ora["stance"].shape and np.array_equal(eng["stance"], ora["stance"]), "stance differs"
+        elif k == "pose_status":
+            assert eng["pose_status"].shape == ora["pose_status"].shape and np.array_equal(eng["pose_status"], ora["pose_status"]), \
+                "pose_status (opt-track gate of cycle 0) differs"
+        elif k == "default":
+            d_e, d_o = eng["default"], ora["default"]
+            assert d_e.shape == d_o.shape
+            assert not _neq(d_e[..., :2], d_o[..., :2]).any(), "default track x/y differ"
+            assert np.all(np.abs(d_e[..., 2] - d_o[..., 2]) <= Z_TOL), "default track z differs"
+        elif k == "selected":
+            _assert_exchange_equal(eng["selected"], ora["nominal"], "selected")
+        elif k == "selected_packed":
+            _assert_exchange_equal(_capi.unpack_selected(eng["selected_packed"]), ora["nominal"], "selected_packed")
+
+
+def run_oracle(planner, trav, elev, res, poses, n_cycles, position=(0.0, 0.0), threads=4):
+    """The oracle's plan (pose_status included) for the planner's current parameters."""
+    omap = fpo.OracleMap(trav, elev, res, position)
+    ora = omap.plan(to_oracle_params(planner.params), to_oracle_poses(poses), n_cycles, threads=threads)
+    ora["pose_status"] = omap.pose_status(to_oracle_params(planner.params), to_oracle_poses(poses))
+    return ora
+
+
+def slice_plan(plan, B):
+    """The first B poses of an oracle plan (poses are planned independently of each other)."""
+    return {k: v[:B] for k, v in plan.items() if isinstance(v, np.ndarray)}
+
+
+def run_both_products(planner, trav, elev, res, poses, n_cycles, products, position=(0.0, 0.0), threads=4):
+    """run_both for a subset of the products: (engine's dict of exactly `products`, the oracle's full plan)."""
+    planner.gridmapCallback(trav, elev, res, position)
+    eng = planner.plan(poses, n_cycles, products=tuple(products))
+    return eng, run_oracle(planner, trav, elev, res, poses, n_cycles, position, threads)
 
 
 def run_both(planner, trav, elev, res, poses, n_cycles, position=(0.0, 0.0), threads=4, products=None):
