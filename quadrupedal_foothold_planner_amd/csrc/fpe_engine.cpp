@@ -590,6 +590,19 @@ int prepare_call(fpe_engine* h, const fpe_params* params, float maxRadius, CallP
 
 fpe::DevMap dev_map(const MapSnapshot& s) { return fpe::DevMap{s.g, s.d_trav, s.d_elev}; }
 
+// The region of a dense call: the caller's (row0, col0, n_rows, n_cols), or the whole map for a null `roi`.
+int resolve_roi(const int32_t roi[4], const fpe::MapGeom& g, fpe::FootmapRoi& r) {
+    if (!roi) {
+        r = fpe::FootmapRoi{0, 0, g.rows, g.cols};
+        return FPE_OK;
+    }
+    if (roi[0] < 0 || roi[1] < 0 || roi[2] <= 0 || roi[3] <= 0 || static_cast<int64_t>(roi[0]) + roi[2] > g.rows ||
+        static_cast<int64_t>(roi[1]) + roi[3] > g.cols)
+        return fail(FPE_E_INVALID_ARG, "region outside the map or empty");
+    r = fpe::FootmapRoi{roi[0], roi[1], roi[2], roi[3]};
+    return FPE_OK;
+}
+
 // fpe_foothold_map*: the snapshot current at entry, the disc constants, the region; `stream` ordered after the snapshot's
 // upload and (bit-plane path) its planes' build.  prepare_call's search-radius and plan-LDS bounds do not apply here.
 int prepare_foothold_map(fpe_engine* h, const fpe_params* params, const int32_t roi[4], bool anyOut, CallPlan& cp,
@@ -606,14 +619,8 @@ int prepare_foothold_map(fpe_engine* h, const fpe_params* params, const int32_t 
     }
     if (!cp.snap) return fail(FPE_E_NO_MAP, "no map uploaded");
     MapSnapshot& snap = *cp.snap;
-    if (roi) {
-        if (roi[0] < 0 || roi[1] < 0 || roi[2] <= 0 || roi[3] <= 0 || static_cast<int64_t>(roi[0]) + roi[2] > snap.g.rows ||
-            static_cast<int64_t>(roi[1]) + roi[3] > snap.g.cols)
-            return fail(FPE_E_INVALID_ARG, "region outside the map or empty");
-        r = fpe::FootmapRoi{roi[0], roi[1], roi[2], roi[3]};
-    } else {
-        r = fpe::FootmapRoi{0, 0, snap.g.rows, snap.g.cols};
-    }
+    rc = resolve_roi(roi, snap.g, r);
+    if (rc != FPE_OK) return rc;
     fpe::PlanConsts& pc = cp.pc;
     fpe::derive_constants(*params, snap.g, params->searchRadius, tuning, pc);
     if (fpe::foothold_map_supported(pc, snap.g) != FPE_OK)
@@ -668,14 +675,8 @@ int prepare_foothold_snap(fpe_engine* h, const fpe_params* params, const int32_t
     int rc = prepare_call(h, params, R, cp, stream, false);
     if (rc != FPE_OK) return rc;
     const fpe::MapGeom& g = cp.snap->g;
-    if (roi) {
-        if (roi[0] < 0 || roi[1] < 0 || roi[2] <= 0 || roi[3] <= 0 || static_cast<int64_t>(roi[0]) + roi[2] > g.rows ||
-            static_cast<int64_t>(roi[1]) + roi[3] > g.cols)
-            return fail(FPE_E_INVALID_ARG, "region outside the map or empty");
-        r = fpe::FootmapRoi{roi[0], roi[1], roi[2], roi[3]};
-    } else {
-        r = fpe::FootmapRoi{0, 0, g.rows, g.cols};
-    }
+    rc = resolve_roi(roi, g, r);
+    if (rc != FPE_OK) return rc;
     const fpe::PlanConsts& pc = cp.pc;
     if (wantZ && fpe::foothold_map_supported(pc, g) != FPE_OK)
         return fail(FPE_E_UNSUPPORTED, "foot radius over 32 cells: the literal disc walk is bounded there");
@@ -711,14 +712,8 @@ int prepare_centroid_map(fpe_engine* h, const fpe_params* params, const int32_t 
     int rc = prepare_call(h, params, 0.0f, cp, stream, false);
     if (rc != FPE_OK) return rc;
     const fpe::MapGeom& g = cp.snap->g;
-    if (roi) {
-        if (roi[0] < 0 || roi[1] < 0 || roi[2] <= 0 || roi[3] <= 0 || static_cast<int64_t>(roi[0]) + roi[2] > g.rows ||
-            static_cast<int64_t>(roi[1]) + roi[3] > g.cols)
-            return fail(FPE_E_INVALID_ARG, "region outside the map or empty");
-        r = fpe::FootmapRoi{roi[0], roi[1], roi[2], roi[3]};
-    } else {
-        r = fpe::FootmapRoi{0, 0, g.rows, g.cols};
-    }
+    rc = resolve_roi(roi, g, r);
+    if (rc != FPE_OK) return rc;
     const float R = searchRadius > 0.0f ? searchRadius : params->searchRadius;
     if (!fpe::centroid_map_consts(g, r, R, cc))
         return fail(FPE_E_UNSUPPORTED, "search radius over the dense centroid map's reach (ceil(R / res) + 2 > 100 cells)");
@@ -734,6 +729,82 @@ hipError_t run_centroid_map(const CallPlan& cp, const fpe::FootmapRoi& r, const 
     e = fpe::launch_centroid_map(dev_map(*cp.snap), cp.pc, cc, r, scratch, d_code, d_offset, d_z, stream);
     const hipError_t f = hipFreeAsync(scratch, stream);
     return e != hipSuccess ? e : f;
+}
+
+// Every *_device entry point calls this after a successful prepare and BEFORE its launch.  The launch is asynchronous: the host never
+// waits for it, so the snapshot's layers and the bit planes the call launches with may be recycled only behind a device
+// synchronisation (BufferPool; the planes directly, not by way of the snapshot's mark — a set evicted by a fifth threshold pair no
+// longer hears of that one).  Before the launch, so that no way out of the entry point leaves work queued on buffers that count as
+// clean; a launch that then fails leaves them dirty too: one synchronisation on a 10-20 Hz path, never on a plan.
+void mark_async_launch(const CallPlan& cp) {
+    cp.snap->note_async_use();
+    if (cp.mask) cp.mask->asyncUsed.store(true, std::memory_order_release);
+}
+
+// What a host-buffer call holds while it runs.  The member order is the point: the lease goes first, so on an early exit it waits
+// for the stream BEFORE the snapshot / bit planes are released (plan_host declares its CallPlan before its CtxLease for this).
+struct HostCall {
+    CallPlan cp;
+    CtxLease lease;
+    CallCtx& cx;
+    explicit HostCall(fpe_engine* h) : lease(h->ctxPool), cx(*lease.ctx) {}
+};
+
+// One product of a dense host-form call: the caller's array and its length in bytes (null or 0: not requested).
+struct HostProduct {
+    void* dst;
+    size_t len;
+};
+
+// The host form of a dense call behind its prepare: the requested products side by side in the context's device arena (256-byte
+// steps), `launch(d, stream)` queues the kernels (d[k]: where product k goes, null when not requested), one DMA transfer per product
+// — straight into a pinned destination, into the pinned arena for any other — one synchronisation, the staged products copied out.
+template <int N, class Launch>
+int stage_products(CallCtx& cx, const HostProduct (&prod)[N], Launch launch) {
+    size_t len[N], off[N], end = 0;
+    bool pinned[N];
+    for (int k = 0; k < N; ++k) {
+        len[k] = prod[k].dst ? prod[k].len : 0;
+        pinned[k] = len[k] && is_pinned_host(prod[k].dst);
+        off[k] = end;
+        end = align256(end + len[k]);
+    }
+    FPE_HIP(cx.reserve(end));
+    unsigned char* d[N];
+    for (int k = 0; k < N; ++k) d[k] = len[k] ? cx.dev + off[k] : nullptr;
+    cx.inFlight = true;
+    FPE_HIP(launch(d, cx.stream));
+    for (int k = 0; k < N; ++k)
+        if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? prod[k].dst : cx.pinned + off[k], d[k], len[k], hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    for (int k = 0; k < N; ++k)
+        if (len[k] && !pinned[k]) std::memcpy(prod[k].dst, cx.pinned + off[k], len[k]);
+    return FPE_OK;
+}
+
+// The host form of an open-loop query call behind its per-query checks: n queries up, `launch(cp, d_queries, d_out, stream)`,
+// n records back, both through the context's arenas.
+template <class Query, class Record, class Launch>
+int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, const Query* queries, int32_t n, Record* out, Launch launch) {
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    const size_t nQ = static_cast<size_t>(n) * sizeof(Query), nO = static_cast<size_t>(n) * sizeof(Record);
+    const size_t szQ = align256(nQ);
+    HostCall hc(h);
+    CallCtx& cx = hc.cx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(szQ + align256(nO)));
+    cx.inFlight = true;
+    int rc = prepare_call(h, params, maxRadius, hc.cp, cx.stream, false);
+    if (rc != FPE_OK) return rc;
+    std::memcpy(cx.pinned, queries, nQ);
+    FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, nQ, hipMemcpyHostToDevice, cx.stream));
+    FPE_HIP(launch(hc.cp, reinterpret_cast<const Query*>(cx.dev), reinterpret_cast<Record*>(cx.dev + szQ), cx.stream));
+    FPE_HIP(hipMemcpyAsync(cx.pinned + szQ, cx.dev + szQ, nO, hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    std::memcpy(out, cx.pinned + szQ, nO);
+    return FPE_OK;
 }
 
 int check_desc(const fpe_map_desc* d) {
@@ -1212,11 +1283,8 @@ int fpe_plan_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_po
     CallPlan cp;
     int rc = prepare_call(h, params, 0.0f, cp, st, true);
     if (rc != FPE_OK) return rc;
-    rc = launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st);
-    if (rc != FPE_OK) return rc;
-    cp.snap->note_async_use();  // asynchronous launch: the snapshot's buffers are recycled only behind a device sync
-    if (cp.mask) cp.mask->asyncUsed.store(true, std::memory_order_release);
-    return FPE_OK;
+    mark_async_launch(cp);
+    return launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st);
 }
 
 namespace {
@@ -1600,8 +1668,8 @@ int fpe_plan_opt_device(fpe_handle h, const fpe_params* params, const fpe_opt_pa
     fpe::OptConsts oc;
     rc = prepare_opt(params, opt, cp, std::max(params->searchRadius, cp.pc.maxSearchRadius), oc);
     if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
     FPE_HIP(fpe::launch_opt_track(dev_map(*cp.snap), cp.pc, oc, d_poses, B, n_cycles, d_cycle_ok, *d_out, st));
-    cp.snap->note_async_use();
     return FPE_OK;
 }
 
@@ -1613,8 +1681,8 @@ int fpe_search_legs_device(fpe_handle h, const fpe_params* params, const fpe_leg
     CallPlan cp;
     int rc = prepare_call(h, params, 0.0f, cp, st, false);
     if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
     FPE_HIP(fpe::launch_search_legs(dev_map(*cp.snap), cp.pc, h->lut(), d_queries, n, d_out, st));
-    cp.snap->note_async_use();
     return FPE_OK;
 }
 
@@ -1632,26 +1700,10 @@ int fpe_search_legs(fpe_handle h, const fpe_params* params, const fpe_leg_query*
             return fail(FPE_E_INVALID_ARG, "too many polygon vertices");
         maxRadius = std::max(maxRadius, queries[k].search_radius);
     }
-    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
-    const size_t szQ = align256(static_cast<size_t>(n) * sizeof(fpe_leg_query));
-    const size_t szO = align256(static_cast<size_t>(n) * sizeof(fpe_foothold));
-    CallPlan cp;  // (before the lease, as in plan_host)
-    CtxLease lease(h->ctxPool);
-    CallCtx& cx = *lease.ctx;
-    FPE_HIP(hipSetDevice(h->device));
-    FPE_HIP(cx.reserve(szQ + szO));
-    cx.inFlight = true;
-    int rc = prepare_call(h, params, maxRadius, cp, cx.stream, false);
-    if (rc != FPE_OK) return rc;
-    std::memcpy(cx.pinned, queries, static_cast<size_t>(n) * sizeof(fpe_leg_query));
-    FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, static_cast<size_t>(n) * sizeof(fpe_leg_query), hipMemcpyHostToDevice, cx.stream));
-    FPE_HIP(fpe::launch_search_legs(dev_map(*cp.snap), cp.pc, h->lut(), reinterpret_cast<const fpe_leg_query*>(cx.dev), n,
-                                    reinterpret_cast<fpe_foothold*>(cx.dev + szQ), cx.stream));
-    FPE_HIP(hipMemcpyAsync(cx.pinned + szQ, cx.dev + szQ, static_cast<size_t>(n) * sizeof(fpe_foothold), hipMemcpyDeviceToHost, cx.stream));
-    FPE_HIP(hipStreamSynchronize(cx.stream));
-    cx.inFlight = false;
-    std::memcpy(out, cx.pinned + szQ, static_cast<size_t>(n) * sizeof(fpe_foothold));
-    return FPE_OK;
+    return query_round_trip(h, params, maxRadius, queries, n, out,
+                            [&](const CallPlan& cp, const fpe_leg_query* d_q, fpe_foothold* d_out, hipStream_t s) {
+                                return fpe::launch_search_legs(dev_map(*cp.snap), cp.pc, h->lut(), d_q, n, d_out, s);
+                            });
 }
 
 int fpe_foothold_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_foothold_map_out* d_out,
@@ -1662,7 +1714,7 @@ int fpe_foothold_map_device(fpe_handle h, const fpe_params* params, const int32_
     fpe::FootmapRoi r{};
     int rc = prepare_foothold_map(h, params, roi, d_out->flags || d_out->height, cp, r, st);
     if (rc != FPE_OK) return rc;
-    cp.snap->note_async_use();  // (before the launch: a concurrent upload that retires the snapshot hands its buffers back dirty)
+    mark_async_launch(cp);
     FPE_HIP(fpe::launch_foothold_map(dev_map(*cp.snap), cp.bits, cp.pc, r, d_out->flags, d_out->height, st));
     return FPE_OK;
 }
@@ -1670,34 +1722,19 @@ int fpe_foothold_map_device(fpe_handle h, const fpe_params* params, const int32_
 int fpe_foothold_map(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_foothold_map_out* out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
-    CallPlan cp;  // (before the lease, as in plan_host)
-    CtxLease lease(h->ctxPool);
-    CallCtx& cx = *lease.ctx;
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
     FPE_HIP(hipSetDevice(h->device));
     FPE_HIP(cx.reserve(0));  // the stream
     fpe::FootmapRoi r{};
     int rc = prepare_foothold_map(h, params, roi, out->flags || out->height, cp, r, cx.stream);
     if (rc != FPE_OK) return rc;
     const size_t n = static_cast<size_t>(r.nr) * r.nc;
-    // device products in the call's arena; a pinned destination is written by DMA, any other through the pinned arena
-    void* dst[2] = {out->flags, out->height};
-    const size_t len[2] = {out->flags ? n : 0, out->height ? n * sizeof(float) : 0};
-    const bool pinned[2] = {dst[0] && is_pinned_host(dst[0]), dst[1] && is_pinned_host(dst[1])};
-    const size_t off[2] = {0, align256(len[0])};
-    size_t stage = 0;
-    for (int k = 0; k < 2; ++k)
-        if (len[k] && !pinned[k]) stage = off[k] + len[k];
-    FPE_HIP(cx.reserve(std::max(off[1] + len[1], stage)));
-    cx.inFlight = true;
-    FPE_HIP(fpe::launch_foothold_map(dev_map(*cp.snap), cp.bits, cp.pc, r, out->flags ? cx.dev + off[0] : nullptr,
-                                     out->height ? reinterpret_cast<float*>(cx.dev + off[1]) : nullptr, cx.stream));
-    for (int k = 0; k < 2; ++k)
-        if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? dst[k] : cx.pinned + off[k], cx.dev + off[k], len[k], hipMemcpyDeviceToHost, cx.stream));
-    FPE_HIP(hipStreamSynchronize(cx.stream));
-    cx.inFlight = false;
-    for (int k = 0; k < 2; ++k)
-        if (len[k] && !pinned[k]) std::memcpy(dst[k], cx.pinned + off[k], len[k]);
-    return FPE_OK;
+    const HostProduct prod[2] = {{out->flags, n}, {out->height, n * sizeof(float)}};
+    return stage_products(cx, prod, [&](unsigned char* const* d, hipStream_t s) {
+        return fpe::launch_foothold_map(dev_map(*cp.snap), cp.bits, cp.pc, r, d[0], reinterpret_cast<float*>(d[1]), s);
+    });
 }
 
 int fpe_foothold_snap_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius, int32_t polygon_kind,
@@ -1711,7 +1748,7 @@ int fpe_foothold_snap_device(fpe_handle h, const fpe_params* params, const int32
     int rc = prepare_foothold_snap(h, params, roi, search_radius, polygon_kind, d_out->offset || d_out->source || d_out->z, d_out->z != nullptr,
                                    cp, r, sc, bitPath, st);
     if (rc != FPE_OK) return rc;
-    cp.snap->note_async_use();  // (before the launch, as in fpe_foothold_map_device)
+    mark_async_launch(cp);
     FPE_HIP(run_foothold_snap(h, cp, r, sc, bitPath, d_out->offset, d_out->source, d_out->z, st));
     return FPE_OK;
 }
@@ -1720,9 +1757,9 @@ int fpe_foothold_snap(fpe_handle h, const fpe_params* params, const int32_t roi[
                       const fpe_foothold_snap_out* out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
-    CallPlan cp;  // (before the lease, as in plan_host)
-    CtxLease lease(h->ctxPool);
-    CallCtx& cx = *lease.ctx;
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
     FPE_HIP(hipSetDevice(h->device));
     FPE_HIP(cx.reserve(0));  // the stream
     fpe::FootmapRoi r{};
@@ -1732,29 +1769,10 @@ int fpe_foothold_snap(fpe_handle h, const fpe_params* params, const int32_t roi[
                                    cp, r, sc, bitPath, cx.stream);
     if (rc != FPE_OK) return rc;
     const size_t n = static_cast<size_t>(r.nr) * r.nc;
-    // device products in the call's arena; a pinned destination is written by DMA, any other through the pinned arena
-    void* dst[3] = {out->offset, out->source, out->z};
-    const size_t len[3] = {out->offset ? 2 * n : 0, out->source ? n : 0, out->z ? n * sizeof(float) : 0};
-    bool pinned[3];
-    size_t off[3], end = 0, stage = 0;
-    for (int k = 0; k < 3; ++k) {
-        pinned[k] = dst[k] && is_pinned_host(dst[k]);
-        off[k] = end;
-        end = align256(end + len[k]);
-        if (len[k] && !pinned[k]) stage = off[k] + len[k];
-    }
-    FPE_HIP(cx.reserve(std::max(end, stage)));
-    cx.inFlight = true;
-    FPE_HIP(run_foothold_snap(h, cp, r, sc, bitPath, out->offset ? reinterpret_cast<int8_t*>(cx.dev + off[0]) : nullptr,
-                              out->source ? cx.dev + off[1] : nullptr, out->z ? reinterpret_cast<float*>(cx.dev + off[2]) : nullptr,
-                              cx.stream));
-    for (int k = 0; k < 3; ++k)
-        if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? dst[k] : cx.pinned + off[k], cx.dev + off[k], len[k], hipMemcpyDeviceToHost, cx.stream));
-    FPE_HIP(hipStreamSynchronize(cx.stream));
-    cx.inFlight = false;
-    for (int k = 0; k < 3; ++k)
-        if (len[k] && !pinned[k]) std::memcpy(dst[k], cx.pinned + off[k], len[k]);
-    return FPE_OK;
+    const HostProduct prod[3] = {{out->offset, 2 * n}, {out->source, n}, {out->z, n * sizeof(float)}};
+    return stage_products(cx, prod, [&](unsigned char* const* d, hipStream_t s) {
+        return run_foothold_snap(h, cp, r, sc, bitPath, reinterpret_cast<int8_t*>(d[0]), d[1], reinterpret_cast<float*>(d[2]), s);
+    });
 }
 
 int fpe_centroid_legs_device(fpe_handle h, const fpe_params* params, const fpe_centroid_query* d_queries, int32_t n,
@@ -1765,8 +1783,8 @@ int fpe_centroid_legs_device(fpe_handle h, const fpe_params* params, const fpe_c
     CallPlan cp;
     int rc = prepare_call(h, params, 0.0f, cp, st, false);
     if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
     FPE_HIP(fpe::launch_centroid_legs(dev_map(*cp.snap), cp.pc, params->searchRadius, d_queries, n, d_out, st));
-    cp.snap->note_async_use();
     return FPE_OK;
 }
 
@@ -1775,27 +1793,10 @@ int fpe_centroid_legs(fpe_handle h, const fpe_params* params, const fpe_centroid
     if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
     for (int k = 0; k < n; ++k)  // any centre is a query (code 6 off the map); a radius must be a number
         if (!std::isfinite(queries[k].search_radius)) return fail(FPE_E_INVALID_ARG, "bad search radius");
-    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
-    const size_t szQ = align256(static_cast<size_t>(n) * sizeof(fpe_centroid_query));
-    const size_t szO = align256(static_cast<size_t>(n) * sizeof(fpe_centroid_foothold));
-    CallPlan cp;  // (before the lease, as in plan_host)
-    CtxLease lease(h->ctxPool);
-    CallCtx& cx = *lease.ctx;
-    FPE_HIP(hipSetDevice(h->device));
-    FPE_HIP(cx.reserve(szQ + szO));
-    cx.inFlight = true;
-    int rc = prepare_call(h, params, 0.0f, cp, cx.stream, false);
-    if (rc != FPE_OK) return rc;
-    std::memcpy(cx.pinned, queries, static_cast<size_t>(n) * sizeof(fpe_centroid_query));
-    FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, static_cast<size_t>(n) * sizeof(fpe_centroid_query), hipMemcpyHostToDevice, cx.stream));
-    FPE_HIP(fpe::launch_centroid_legs(dev_map(*cp.snap), cp.pc, params->searchRadius, reinterpret_cast<const fpe_centroid_query*>(cx.dev),
-                                      n, reinterpret_cast<fpe_centroid_foothold*>(cx.dev + szQ), cx.stream));
-    FPE_HIP(hipMemcpyAsync(cx.pinned + szQ, cx.dev + szQ, static_cast<size_t>(n) * sizeof(fpe_centroid_foothold), hipMemcpyDeviceToHost,
-                           cx.stream));
-    FPE_HIP(hipStreamSynchronize(cx.stream));
-    cx.inFlight = false;
-    std::memcpy(out, cx.pinned + szQ, static_cast<size_t>(n) * sizeof(fpe_centroid_foothold));
-    return FPE_OK;
+    return query_round_trip(h, params, 0.0f, queries, n, out,
+                            [&](const CallPlan& cp, const fpe_centroid_query* d_q, fpe_centroid_foothold* d_out, hipStream_t s) {
+                                return fpe::launch_centroid_legs(dev_map(*cp.snap), cp.pc, params->searchRadius, d_q, n, d_out, s);
+                            });
 }
 
 int fpe_centroid_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius,
@@ -1807,7 +1808,7 @@ int fpe_centroid_map_device(fpe_handle h, const fpe_params* params, const int32_
     fpe::CmapConsts cc{};
     int rc = prepare_centroid_map(h, params, roi, search_radius, d_out->code || d_out->offset || d_out->z, cp, r, cc, st);
     if (rc != FPE_OK) return rc;
-    cp.snap->note_async_use();  // (before the launch, as in fpe_foothold_map_device)
+    mark_async_launch(cp);
     FPE_HIP(run_centroid_map(cp, r, cc, d_out->code, d_out->offset, d_out->z, st));
     return FPE_OK;
 }
@@ -1815,9 +1816,9 @@ int fpe_centroid_map_device(fpe_handle h, const fpe_params* params, const int32_
 int fpe_centroid_map(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius, const fpe_centroid_map_out* out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
-    CallPlan cp;  // (before the lease, as in plan_host)
-    CtxLease lease(h->ctxPool);
-    CallCtx& cx = *lease.ctx;
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
     FPE_HIP(hipSetDevice(h->device));
     FPE_HIP(cx.reserve(0));  // the stream
     fpe::FootmapRoi r{};
@@ -1825,29 +1826,10 @@ int fpe_centroid_map(fpe_handle h, const fpe_params* params, const int32_t roi[4
     int rc = prepare_centroid_map(h, params, roi, search_radius, out->code || out->offset || out->z, cp, r, cc, cx.stream);
     if (rc != FPE_OK) return rc;
     const size_t n = static_cast<size_t>(r.nr) * r.nc;
-    // device products in the call's arena; a pinned destination is written by DMA, any other through the pinned arena
-    void* dst[3] = {out->code, out->offset, out->z};
-    const size_t len[3] = {out->code ? n : 0, out->offset ? 2 * n : 0, out->z ? n * sizeof(float) : 0};
-    bool pinned[3];
-    size_t off[3], end = 0, stage = 0;
-    for (int k = 0; k < 3; ++k) {
-        pinned[k] = dst[k] && is_pinned_host(dst[k]);
-        off[k] = end;
-        end = align256(end + len[k]);
-        if (len[k] && !pinned[k]) stage = off[k] + len[k];
-    }
-    FPE_HIP(cx.reserve(std::max(end, stage)));
-    cx.inFlight = true;
-    FPE_HIP(run_centroid_map(cp, r, cc, out->code ? cx.dev + off[0] : nullptr,
-                             out->offset ? reinterpret_cast<int8_t*>(cx.dev + off[1]) : nullptr,
-                             out->z ? reinterpret_cast<float*>(cx.dev + off[2]) : nullptr, cx.stream));
-    for (int k = 0; k < 3; ++k)
-        if (len[k]) FPE_HIP(hipMemcpyAsync(pinned[k] ? dst[k] : cx.pinned + off[k], cx.dev + off[k], len[k], hipMemcpyDeviceToHost, cx.stream));
-    FPE_HIP(hipStreamSynchronize(cx.stream));
-    cx.inFlight = false;
-    for (int k = 0; k < 3; ++k)
-        if (len[k] && !pinned[k]) std::memcpy(dst[k], cx.pinned + off[k], len[k]);
-    return FPE_OK;
+    const HostProduct prod[3] = {{out->code, n}, {out->offset, 2 * n}, {out->z, n * sizeof(float)}};
+    return stage_products(cx, prod, [&](unsigned char* const* d, hipStream_t s) {
+        return run_centroid_map(cp, r, cc, d[0], reinterpret_cast<int8_t*>(d[1]), reinterpret_cast<float*>(d[2]), s);
+    });
 }
 
 int fpe_last_service_gate(fpe_handle h, fpe_service_gate* out) {

@@ -283,13 +283,12 @@ class FootholdPlanner:
     def _roi(roi):
         return None if roi is None else np.ascontiguousarray(roi, dtype=np.int32).reshape(4)
 
-    def foothold_map(self, roi=None, products=("flags", "height")):
-        """fpe_foothold_map on the current map: {"flags": uint8 [n_rows, n_cols] FPE_FMAP_* bits, "height": float32
-        [n_rows, n_cols]} for the requested products.  roi = (row0, col0, n_rows, n_cols) in canonical indices; None = the
-        whole map."""
-        unknown = set(products) - {"flags", "height"}
+    def _dense_outputs(self, what, roi, products, table):
+        """The region as the C ABI takes it (None = the whole map) and one uninitialised array per requested product of a
+        dense map: `table` maps a product name to (dtype, trailing shape) behind [n_rows, n_cols]."""
+        unknown = set(products) - set(table)
         if unknown:
-            raise ValueError(f"unknown foothold-map products {sorted(unknown)}")
+            raise ValueError(f"unknown {what} products {sorted(unknown)}")
         r = self._roi(roi)
         if r is not None:
             shape = (max(int(r[2]), 0), max(int(r[3]), 0))
@@ -297,11 +296,13 @@ class FootholdPlanner:
             d = MapDesc()
             self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
             shape = (d.rows, d.cols)
-        out = {}
-        if "flags" in products:
-            out["flags"] = np.empty(shape, np.uint8)
-        if "height" in products:
-            out["height"] = np.empty(shape, np.float32)
+        return r, {k: np.empty(shape + tail, dtype) for k, (dtype, tail) in table.items() if k in products}
+
+    def foothold_map(self, roi=None, products=("flags", "height")):
+        """fpe_foothold_map on the current map: {"flags": uint8 [n_rows, n_cols] FPE_FMAP_* bits, "height": float32
+        [n_rows, n_cols]} for the requested products.  roi = (row0, col0, n_rows, n_cols) in canonical indices; None = the
+        whole map."""
+        r, out = self._dense_outputs("foothold-map", roi, products, {"flags": (np.uint8, ()), "height": (np.float32, ())})
         mo = FootholdMapOut(ptr(out.get("flags")), ptr(out.get("height")))
         self._check(self._lib.fpe_foothold_map(self._h, ptr(self.params), ptr(r), C.byref(mo)))
         return out
@@ -327,23 +328,8 @@ class FootholdPlanner:
         """fpe_foothold_snap on the current map: {"offset": int8 [n_rows, n_cols, 2] (di, dj) of the landing cell, "source":
         uint8 [n_rows, n_cols] (0 default hit, 1 spiral candidate, 2 none), "z": float32 [n_rows, n_cols]} for the requested
         products.  roi as in foothold_map; search_radius None = params.searchRadius; polygon "rectangle" | "hexagon"."""
-        unknown = set(products) - {"offset", "source", "z"}
-        if unknown:
-            raise ValueError(f"unknown foothold-snap products {sorted(unknown)}")
-        r = self._roi(roi)
-        if r is not None:
-            shape = (max(int(r[2]), 0), max(int(r[3]), 0))
-        else:
-            d = MapDesc()
-            self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
-            shape = (d.rows, d.cols)
-        out = {}
-        if "offset" in products:
-            out["offset"] = np.empty(shape + (2,), np.int8)
-        if "source" in products:
-            out["source"] = np.empty(shape, np.uint8)
-        if "z" in products:
-            out["z"] = np.empty(shape, np.float32)
+        r, out = self._dense_outputs("foothold-snap", roi, products,
+                                     {"offset": (np.int8, (2,)), "source": (np.uint8, ()), "z": (np.float32, ())})
         so = FootholdSnapOut(ptr(out.get("offset")), ptr(out.get("source")), ptr(out.get("z")))
         self._check(self._lib.fpe_foothold_snap(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0),
                                                 self._polygon_kind(polygon), C.byref(so)))
@@ -375,23 +361,8 @@ class FootholdPlanner:
         """fpe_centroid_map on the current map: {"code": uint8 [n_rows, n_cols] (0..6), "offset": int8 [n_rows, n_cols, 2]
         (row - i, col - j) of the landing cell, "z": float32 [n_rows, n_cols]} for the requested products.  roi as in
         foothold_map; search_radius None = params.searchRadius."""
-        unknown = set(products) - {"code", "offset", "z"}
-        if unknown:
-            raise ValueError(f"unknown centroid-map products {sorted(unknown)}")
-        r = self._roi(roi)
-        if r is not None:
-            shape = (max(int(r[2]), 0), max(int(r[3]), 0))
-        else:
-            d = MapDesc()
-            self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
-            shape = (d.rows, d.cols)
-        out = {}
-        if "code" in products:
-            out["code"] = np.empty(shape, np.uint8)
-        if "offset" in products:
-            out["offset"] = np.empty(shape + (2,), np.int8)
-        if "z" in products:
-            out["z"] = np.empty(shape, np.float32)
+        r, out = self._dense_outputs("centroid-map", roi, products,
+                                     {"code": (np.uint8, ()), "offset": (np.int8, (2,)), "z": (np.float32, ())})
         co = CentroidMapOut(ptr(out.get("code")), ptr(out.get("offset")), ptr(out.get("z")))
         self._check(self._lib.fpe_centroid_map(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0), C.byref(co)))
         return out
