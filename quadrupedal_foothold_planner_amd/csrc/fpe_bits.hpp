@@ -23,6 +23,37 @@
 // (row, col) for the centroid result.  When a proof fails the engine launches the direct kernels instead.
 #pragma once
 
+// ---- products as a compile-time mask --------------------------------------------------------------------------------
+// Which of fpe_plan_out's products a launch writes is a run-time null test per product in the generic instantiation
+// (kProd = 0: any combination).  The two shapes that matter are compiled on their own: kProd = 2, ALL seven base products
+// (bench.py's headline step, fpe_plan with every array: the tests fold away) and kProd = 1, the NOMINAL track only —
+// {nominal, selected, selected_packed, cycle_ok}: the service's response (cpp:1588) and the multi-GPU exchange record —
+// where the default-track disc (its loads, membership, deposits and height sums), the centroid result's height and record,
+// the stance and the first-cycle gate are not compiled at all.  The engine picks the instantiation from the pointers.
+template <int kProd>
+__device__ __forceinline__ fpe_plan_out specialise_products(fpe_plan_out out) {
+    if constexpr (kProd == 1) {
+        out.centroid = nullptr;
+        out.default_next = nullptr;
+        out.stance = nullptr;
+        out.pose_status = nullptr;
+    } else if constexpr (kProd == 2) {
+        __builtin_assume(out.nominal != nullptr);
+        __builtin_assume(out.centroid != nullptr);
+        __builtin_assume(out.default_next != nullptr);
+        __builtin_assume(out.cycle_ok != nullptr);
+        __builtin_assume(out.stance != nullptr);
+        __builtin_assume(out.selected != nullptr);
+        __builtin_assume(out.pose_status != nullptr);
+    }
+    return out;
+}
+__host__ inline int product_shape(const fpe_plan_out& o) {
+    if (o.nominal && o.centroid && o.default_next && o.cycle_ok && o.stance && o.selected && o.pose_status) return 2;
+    if (!o.centroid && !o.default_next && !o.stance && !o.pose_status) return 1;
+    return 0;
+}
+
 namespace {
 
 // ---- bit-plane build: one wavefront ballots 64 columns of a row ---------------------------------------------
@@ -1532,7 +1563,7 @@ __device__ __forceinline__ float unit_mean9(const float* e, uint32_t vis, double
     return finish_mean(sum, last, cnt, h);
 }
 // One (leg, cycle) unit per lane: heights and the four output records of that unit.
-__device__ __forceinline__ void flush_unit(const DevMap& m, const PlanConsts& pc, const Unit& uLds, const YEntry& yeLds, int b, int cyc,
+__device__ __forceinline__ void flush_unit(const DevMap& m, double h, const Unit& uLds, const YEntry& yeLds, int b, int cyc,
                                            int leg, int nCycles, uint32_t okBits, const fpe_plan_out& out) {
     const MapGeom& mg = m.g;
     // the unit and its y entry in registers by one batch of 16-byte LDS reads (read field by field the reads are
@@ -1546,14 +1577,14 @@ __device__ __forceinline__ void flush_unit(const DevMap& m, const PlanConsts& pc
     float eC = u.eC;
     if (out.centroid && (u.cenCode & 0x200u)) eC = m.elev[static_cast<size_t>(u.cenRow) * mg.cols + u.cenCol];
     if (leg == 0 && out.cycle_ok) out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = static_cast<uint8_t>((okBits >> (cyc & 7)) & 1u);
-    const float zA = unit_mean9(u.eA, u.visA, pc.h);
-    const float zB = out.default_next ? unit_mean9(u.eB, u.visB, pc.h) : 0.0f;
+    const float zA = unit_mean9(u.eA, u.visA, h);
+    const float zB = out.default_next ? unit_mean9(u.eB, u.visB, h) : 0.0f;
     const int code = static_cast<int>(u.cenCode & 0xFFu);
     float zC = 0.0f;
     if (u.cenCode & 0x300u) {
         const float v = __builtin_isfinite(eC) ? eC : 0.0f;
         const bool inc = v < 10;
-        zC = finish_mean(inc ? 0.0f + v : 0.0f, v, inc ? 1 : 0, pc.h);
+        zC = finish_mean(inc ? 0.0f + v : 0.0f, v, inc ? 1 : 0, h);
     } else if (code == 0) {
         zC = zA;  // whole region valid: the height at the centre (cpp:1687)
     }
@@ -1730,7 +1761,13 @@ __device__ __forceinline__ void flush_unit_g(const DevMap& m, const PlanConsts& 
     }
 }
 
-__device__ __forceinline__ void fill_yentry(const MapGeom& mg, const PlanConsts& pc, const LegStatic& ls, double ny, YEntry& e) {
+// PC: the plan constants of the caller (rf, cornerEps, winH: PlanConsts, or YFillConsts of the 3x3-only kernels)
+struct YFillConsts {
+    double rf, cornerEps;
+    int winH;
+};
+template <class PC>
+__device__ __forceinline__ void fill_yentry(const MapGeom& mg, const PC& pc, const LegStatic& ls, double ny, YEntry& e) {
     const double ly = ls.lk.ly;  // centroid rectangle width (cpp:1617)
     const double r = static_cast<double>(ls.Rf);
     int flags = fabs(ny) <= 1e6 ? 2 : 0;
@@ -2178,12 +2215,57 @@ __device__ __forceinline__ FastRanks load_fast_ranks(const SpiralLut& lut, const
     return fr;
 }
 
-template <int NRL, bool kNoDefault>
-__device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const HotConsts& hc, const LaneRole& role,
+// The argument segment of plan_bits_kernel<NRL, true, kProd> as a struct (see SeqKernArgs below; a static_assert behind the
+// kernel checks the mirror).  What the cycle loop reads in every cycle — the layer and plane pointers, the map's size, winH —
+// the kernel takes from its parameters: scalar registers for the whole chain.  What it reads once per eight cycles (the
+// flush: h, the seven product pointers) or in a rare branch (the general leg search: the rank tables, every plan constant) it
+// loads through mid_cold_args() where it uses it: held across the chain these were scalar registers the allocator parked in
+// lanes of two vector registers and read back, sixteen lane reads per flush and per rare branch for the product pointers alone.
+struct MidKernArgs {
+    const fpe_pose* poses;
+    int B, nCycles;
+    DevMap m;
+    BitMap bm;
+    PlanMidConsts pc;
+    SpiralLut lut;
+    fpe_plan_out out;
+};
+// the argument segment through a pointer the optimiser cannot see through: the loads stay where they are written
+__device__ __forceinline__ const MidKernArgs* mid_cold_args() {
+    typedef const MidKernArgs __attribute__((address_space(4))) * KernArgPtr;
+    KernArgPtr ka4 = (KernArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka4));
+    return (const MidKernArgs*)ka4;
+}
+// The PlanConsts view of the block for the general leg search (leg_phase_bits8<NRL, true>, spiral_bits<8, NRL, 1, true> and what
+// they call: disc_issue / disc_pass_direct without the threshold check, default_ok_bits, unit_put_disc, centroid_begin_bits
+// with a one-cell disc), which the generic kernels share.  Those read rf, rf2, h, winH, cornerEps, nFoot and midCellInside.
+// Everything else stays ZERO and must not be read on this path:
+//   footReach            0 is also its value for the one-cell disc these kernels are launched for (launch_plan_bits: nFoot == 1,
+//                        offset (0, 0)); read by spiral_bits under G == 64 or KW > 1 only
+//   nHW, hwList, hwIdx, footDa, footDb   the erosion is compiled out (kOneCellFoot); the offset table is PoseShared's
+//   thrDefault, thrCandidate, footRobust, tile*   direct kernels only (every call here has kCheck == false)
+//   searchRadius .. defNCand, the stance and step constants   prologue only (the kernel reads them from PlanMidConsts itself)
+// A new read of one of these in the shared functions has to add the field to PlanMidConsts and to this view.
+__device__ __forceinline__ PlanConsts plan_consts_of(const PlanMidConsts& k) {
+    PlanConsts pc{};
+    pc.rf = k.rf;
+    pc.rf2 = k.rf2;
+    pc.h = k.h;
+    pc.winH = k.winH;
+    pc.cornerEps = k.cornerEps;
+    pc.nFoot = 1;
+    pc.footReach = 0;
+    pc.midCellInside = k.midCellInside;
+    return pc;
+}
+
+template <int NRL, bool kNoDefault, int kProd>
+__device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, int winH, bool wantDefaultArg, const HotConsts& hc, const LaneRole& role,
                                            const FastRanks& fk,
-                                           const SpiralLut& lut, const LutHead& head, PoseShared& sh, const LegBits& lb, const Grp<8>& g,
+                                           const LutHead& head, PoseShared& sh, const LegBits& lb, const Grp<8>& g,
                                            int leg, const LegStatic& ls, const YEntry& yeIn, double myCtr, double advance, int cyc,
-                                           int nCycles, int b, bool live, const fpe_plan_out& out, LegCommit* lc, Unit* unit) {
+                                           int nCycles, int b, bool live, LegCommit* lc, Unit* unit) {
     constexpr int G = 8, KW = 1;
     const LegConst& lk = ls.lk;
     // the entry's scalar fields in ONE batch of LDS reads (scattered reads would each wait for their own round trip);
@@ -2199,7 +2281,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
     const double ny = ye.ny;
     // (kNoDefault: the launch writes no default-track product — compile-time, see specialise_products: the default-track disc is
     // neither loaded nor tested; its lanes of the x pass still run, in the same instructions as the others)
-    const bool wantDefault = kNoDefault ? false : out.default_next != nullptr;
+    const bool wantDefault = kNoDefault ? false : wantDefaultArg;
     const double xq = nxq + role.hqS;  // a - h == a + (-h)
     const double qf = ((xq - m.g.orgX) - m.g.posX) * m.g.rinv;
     const double kq = trunc(qf);
@@ -2220,7 +2302,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
     const int j0d = ye.j0d, icj = ye.jc;
     // the window rows are requested before anything else looks at the indices (win_issue clamps whatever it is given;
     // the rare path below discards them): the round trip runs under the box tests, the ballot and the submap arithmetic
-    const int iw0 = ici - pc.winH, jw0 = icj - pc.winH;
+    const int iw0 = ici - winH, jw0 = icj - winH;
     uint4 grp[NRL][KW + 1];
     win_issue<G, NRL, KW>(bm, m.g, g, iw0, jw0, grp);
     // both foot-disc boxes: 3x3 and clear of the map's outermost rows / columns (not clamped, inside the map)
@@ -2235,7 +2317,11 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
     if (__ballot(rare) != 0ull) {  // wave-uniform
         const double ctr0 = swizzle_f64<kKeep | (5 << 5)>(myCtr), ctr1 = swizzle_f64<kKeep | (0 << 5)>(myCtr),
                      ctr2 = swizzle_f64<kKeep | (7 << 5)>(myCtr);
-        leg_phase_bits8<NRL, true>(m, bm, pc, lut, head, sh, lb, g, leg, ls, yeIn, ctr0, ctr1, ctr2, advance, cyc, nCycles, b, live, out, lc, unit);
+        // (rare: the plan constants, the rank tables and the product pointers from the argument segment, here)
+        const MidKernArgs* ka = mid_cold_args();
+        const PlanConsts pcR = plan_consts_of(ka->pc);
+        const fpe_plan_out outR = specialise_products<kProd>(ka->out);
+        leg_phase_bits8<NRL, true>(m, bm, pcR, ka->lut, head, sh, lb, g, leg, ls, yeIn, ctr0, ctr1, ctr2, advance, cyc, nCycles, b, live, outR, lc, unit);
         return;
     }
     // getSubmapInformation's tail, x part (corners strictly inside the map: within); y part from the entry
@@ -2280,7 +2366,8 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
     // [min{i : x_i < xhi}, max{i : x_i >= xlo}] (rectangle_index_bounds) and cell centres x_i are non-increasing in i, so row i
     // is one of them iff xlo <= x_i < xhi: the lane tests ITS row's centre, nobody derives the interval's ends (a floor, a
     // clamp and a conversion per end, four corrected estimates over a ballot: fifty instructions a cycle).
-    const bool fastSpiral = __ballot(ls.polyKind != 0 || lk.nRings < 4 || lk.nCand < 16) == 0ull && pc.nFoot <= 1;  // uniform
+    // (one-cell foot disc: what these kernels are launched for, launch_plan_bits)
+    const bool fastSpiral = __ballot(ls.polyKind != 0 || lk.nRings < 4 || lk.nCand < 16) == 0ull;  // uniform
     const int iFast = iw0 + g.sub + G * fk.slot;
     const double rS = static_cast<double>(ls.Rf);
     const double xFast = cell_pos(m.g.baseX, m.g.res, iFast);
@@ -2377,7 +2464,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
                 const unsigned colIn = range_word(-jw0, m.g.cols - 1 - jw0, 0);
                 P = static_cast<unsigned>(i) < static_cast<unsigned>(m.g.rows) ? (P & colIn) : 0u;
             }
-            const unsigned b5 = P >> static_cast<unsigned>(pc.winH - 2);  // bit c = column offset c - 2 from the centre column (winH)
+            const unsigned b5 = P >> static_cast<unsigned>(winH - 2);  // bit c = column offset c - 2 from the centre column (winH)
             unsigned m16 = 0u;
 #pragma unroll
             for (int c = 0; c < 5; ++c) m16 |= ((b5 >> c) & 1u) << ((fk.rowTab >> (5 * c)) & 31u);  // (rank 31: not a candidate)
@@ -2424,7 +2511,9 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
                 }
                 bits_sync<G>();
             }
-            found = spiral_bits<G, NRL, KW, true>(m, pc, lut, head, c, w, lb, g, iw0, jw0, wi, wj, &yeIn);  // cpp:2022
+            const MidKernArgs* ka = mid_cold_args();  // (rare: see above)
+            const PlanConsts pcR = plan_consts_of(ka->pc);
+            found = spiral_bits<G, NRL, KW, true>(m, pcR, ka->lut, head, c, w, lb, g, iw0, jw0, wi, wj, &yeIn);  // cpp:2022
             bits_sync<G>();
         }
         if (found) {
@@ -2457,44 +2546,14 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, co
 
 }  // namespace
 
-// ---- products as a compile-time mask --------------------------------------------------------------------------------
-// Which of fpe_plan_out's products a launch writes is a run-time null test per product in the generic instantiation
-// (kProd = 0: any combination).  The two shapes that matter are compiled on their own: kProd = 2, ALL seven base products
-// (bench.py's headline step, fpe_plan with every array: the tests fold away) and kProd = 1, the NOMINAL track only —
-// {nominal, selected, selected_packed, cycle_ok}: the service's response (cpp:1588) and the multi-GPU exchange record —
-// where the default-track disc (its loads, membership, deposits and height sums), the centroid result's height and record,
-// the stance and the first-cycle gate are not compiled at all.  The engine picks the instantiation from the pointers.
-template <int kProd>
-__device__ __forceinline__ fpe_plan_out specialise_products(fpe_plan_out out) {
-    if constexpr (kProd == 1) {
-        out.centroid = nullptr;
-        out.default_next = nullptr;
-        out.stance = nullptr;
-        out.pose_status = nullptr;
-    } else if constexpr (kProd == 2) {
-        __builtin_assume(out.nominal != nullptr);
-        __builtin_assume(out.centroid != nullptr);
-        __builtin_assume(out.default_next != nullptr);
-        __builtin_assume(out.cycle_ok != nullptr);
-        __builtin_assume(out.stance != nullptr);
-        __builtin_assume(out.selected != nullptr);
-        __builtin_assume(out.pose_status != nullptr);
-    }
-    return out;
-}
-__host__ inline int product_shape(const fpe_plan_out& o) {
-    if (o.nominal && o.centroid && o.default_next && o.cycle_ok && o.stance && o.selected && o.pose_status) return 2;
-    if (!o.centroid && !o.default_next && !o.stance && !o.pose_status) return 1;
-    return 0;
-}
-
 // ---- chained plan on the bit window: 8 lanes per leg, two poses per wavefront ------------------------------------
 constexpr int kBitsGenericWaves = 3;  // measured on cfg-4: 2 -> 1.36 ms, 3 -> 1.25 ms (27 spilled VGPRs), 4 -> 1.46 ms (69 spilled)
 template <int NRL, bool kMid, int kProd>
 // (the pose pointer and the counts lead the argument list: scalar arguments at the head of the kernarg segment are
 // preloaded into SGPRs at wave launch, -amdgpu-kernarg-preload-count, so the pose loads can be issued at once)
 __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles,
-                                                          DevMap mArg, BitMap bm, PlanConsts pc, SpiralLut lut, fpe_plan_out outArg) {
+                                                          DevMap mArg, BitMap bm, typename std::conditional<kMid, PlanMidConsts, PlanConsts>::type pc,
+                                                          SpiralLut lut, fpe_plan_out outArg) {
     constexpr int G = 8;
     const fpe_plan_out out = specialise_products<kProd>(outArg);
     constexpr bool kNoDefault = kProd == 1;
@@ -2662,6 +2721,7 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
     if constexpr (kMid) role = make_lane_role(g.sub, pc.rf, ls.lk.lx, pc.cornerEps, static_cast<double>(mArg.g.rows));
     FastRanks fr{};
     if constexpr (kMid) fr = load_fast_ranks<NRL>(lut, g, pc.winH);
+    const bool wantDefault = out.default_next != nullptr;  // (3x3-only kernels: the one product test of the fast leg search)
     uint32_t okBits = 0u;  // cycleOk of the cycles since the last flush (3x3-only kernels: stored by flush_unit)
 
     // Issue priority, 3x3-only kernels (two wavefronts per SIMD at the headline's batch): the SIMD's arbiter serves the OLDER of
@@ -2688,7 +2748,12 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
                 a += hc.drift;
                 if (g.sub == k) mine = a;
             }
-            if (kBatch == 8 || g.sub < kBatch) fill_yentry(m.g, pc, ls, (y0 + mine) + ls.biasY, ytab[g.sub]);  // cpp:2201, 2414
+            if constexpr (kMid) {  // (its constants from the vector registers they are parked in)
+                const YFillConsts yc{hc.rf, hc.cornerEps, pc.winH};
+                fill_yentry(m.g, yc, ls, (y0 + mine) + ls.biasY, ytab[g.sub]);  // cpp:2201, 2414
+            } else if (g.sub < kBatch) {
+                fill_yentry(m.g, pc, ls, (y0 + mine) + ls.biasY, ytab[g.sub]);
+            }
             bits_sync<G>();
         }
         const YEntry& ye = ytab[cyc & (kBatch - 1)];
@@ -2705,8 +2770,8 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
             lc.valid = 1;  // non-swing legs do not vote
             if (active) {
                 if constexpr (kMid) {
-                    leg_fast8m<NRL, kNoDefault>(m, bm, pc, hc, role, fr, lut, head, sh, lb, g, leg, ls, ye, myCtr, advance, cyc, nCycles, b, live, out, &lc,
-                                                units + (cyc & (kBatch - 1)));
+                    leg_fast8m<NRL, kNoDefault, kProd>(m, bm, pc.winH, wantDefault, hc, role, fr, head, sh, lb, g, leg, ls, ye, myCtr, advance, cyc, nCycles, b,
+                                                       live, &lc, units + (cyc & (kBatch - 1)));
                 } else {
                     constexpr int kKeep = (~(G - 1)) & 0x1F;
                     const double ctr0 = swizzle_f64<kKeep | (0 << 5)>(myCtr), ctr1 = swizzle_f64<kKeep | (1 << 5)>(myCtr),
@@ -2733,7 +2798,11 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
             // unit of cycle base + s
             const int c0 = cyc & ~(kBatch - 1);
             if constexpr (kMid) {
-                if (live && c0 + g.sub <= cyc) flush_unit(m, pc, units[g.sub], ytab[g.sub], b, c0 + g.sub, leg, nCycles, okBits, out);
+                // (once per eight cycles: h and the product pointers from the argument segment, see MidKernArgs)
+                const MidKernArgs* ka = mid_cold_args();
+                const double hF = ka->pc.h;
+                const fpe_plan_out outF = specialise_products<kProd>(ka->out);
+                if (live && c0 + g.sub <= cyc) flush_unit(m, hF, units[g.sub], ytab[g.sub], b, c0 + g.sub, leg, nCycles, okBits, outF);
             } else {
                 const int us = g.sub >> 1;  // two lanes per unit (kBatch * 2 == G)
                 if (live && c0 + us <= cyc)
@@ -2744,6 +2813,12 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
         }
     }
 }
+
+static_assert(kernargs_mirror<decltype(plan_bits_kernel<2, true, 2>)>(
+                  {offsetof(MidKernArgs, poses), offsetof(MidKernArgs, B), offsetof(MidKernArgs, nCycles), offsetof(MidKernArgs, m),
+                   offsetof(MidKernArgs, bm), offsetof(MidKernArgs, pc), offsetof(MidKernArgs, lut), offsetof(MidKernArgs, out)},
+                  offsetof(MidKernArgs, out) + sizeof(MidKernArgs::out)),
+              "MidKernArgs must mirror the parameters of plan_bits_kernel<NRL, true, kProd>");
 
 // ---- chained plan on the bit window, sequential-legs form (large windows): one wavefront per pose, lane = window
 // row, KW words per row; the swing legs of a phase are searched one after the other (see plan_sequential_kernel) ----
@@ -3056,6 +3131,13 @@ void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, siz
     else snprintf(buf, n, "plan_chained_kernel<%d, %s> (direct)", G, (G == 8 && mid_variant(pc, g.res)) ? "true" : "false");
 }
 
+// the plan constants as plan_bits_kernel<NRL, kMid, kProd> takes them: the 3x3-only kernels' own block, filled from this call's constants
+template <bool kMid>
+static auto bits_kernel_consts(const PlanConsts& pc) {
+    if constexpr (kMid) return plan_mid_consts(pc);
+    else return pc;
+}
+
 hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
                             int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream) {
     const BitsShape sp = bits_shape(pc.winH);
@@ -3066,7 +3148,7 @@ hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts&
     hipLaunchKernelGGL((plan_bits_kernel<NRL, MID, PROD>), dim3((B + 1) / 2), block,                                        \
                        2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW) +                                      \
                             (MID ? (sizeof(YEntry) + sizeof(Unit)) * 32 : (sizeof(YEntry) + sizeof(UnitG)) * 16)), stream, d_poses, B,  \
-                       nCycles, m, bm, pc, lut, d_out)
+                       nCycles, m, bm, bits_kernel_consts<MID>(pc), lut, d_out)
 #define FPE_LAUNCH_BITS(NRL, MID)                                  \
     do {                                                           \
         if (prod == 2) FPE_LAUNCH_BITS_P(NRL, MID, 2);             \

@@ -103,6 +103,59 @@ struct PlanConsts {
 };
 constexpr int kMaxHW = 4;
 
+// The plan constants of the 3x3-only 8-lane bit-window kernels (plan_bits_kernel<NRL, true, kProd>) — what their prologue, the
+// y-entry fill, the fast leg search, the flush and the rare branches read, and nothing else: those kernels are launched for
+// one-cell foot discs only (nFoot == 1: no offset table, no row-interval erosion) and never stage an LDS tile.  Filled per
+// launch from the call's PlanConsts (plan_mid_consts).  How the kernels read it (fpe_bits.hpp):
+//   winH                  every gait cycle, from the by-value parameter: a scalar register for the whole chain
+//   rf, rf2, cornerEps, drift   operands of vector f64 arithmetic: parked in vector registers once per wavefront
+//   h                     the flush, every eighth cycle: loaded from the argument segment there (mid_cold_args)
+//   rf .. h, winH, midCellInside   again in the rare general leg search, loaded from the argument segment there (plan_consts_of)
+//   everything else       the prologue only (LDS carve-up, LegStatic, stance, first-cycle gate, step and swing order), through
+//                         the by-value parameter: read once per wavefront, not held across the cycle loop
+struct PlanMidConsts {
+    int32_t winH;
+    int32_t nHW;  // LDS carve-up (legbits_words), prologue only
+    double rf, rf2, cornerEps, drift;
+    double h;
+    float searchRadius, maxSearchRadius;
+    int32_t defNRings, defNCand;
+    int32_t RF_FIRST, midCellInside;
+    double LbHalf, WbHalfNeg, WbHalfPos;
+    double biasX[4], biasY[4];
+    double stepHalf, step, stepQuarter;
+    double isosLen, isosWid;
+};
+inline PlanMidConsts plan_mid_consts(const PlanConsts& pc) {
+    PlanMidConsts k;
+    k.winH = pc.winH;
+    k.nHW = pc.nHW;
+    k.rf = pc.rf;
+    k.rf2 = pc.rf2;
+    k.cornerEps = pc.cornerEps;
+    k.drift = pc.drift;
+    k.h = pc.h;
+    k.searchRadius = pc.searchRadius;
+    k.maxSearchRadius = pc.maxSearchRadius;
+    k.defNRings = pc.defNRings;
+    k.defNCand = pc.defNCand;
+    k.RF_FIRST = pc.RF_FIRST;
+    k.midCellInside = pc.midCellInside;
+    k.LbHalf = pc.LbHalf;
+    k.WbHalfNeg = pc.WbHalfNeg;
+    k.WbHalfPos = pc.WbHalfPos;
+    for (int l = 0; l < 4; ++l) {
+        k.biasX[l] = pc.biasX[l];
+        k.biasY[l] = pc.biasY[l];
+    }
+    k.stepHalf = pc.stepHalf;
+    k.step = pc.step;
+    k.stepQuarter = pc.stepQuarter;
+    k.isosLen = pc.isosLen;
+    k.isosWid = pc.isosWid;
+    return k;
+}
+
 // Bit planes of one map snapshot for one (defaultFootholdThreshold, candidateFootholdThreshold) pair
 // (fpe_bits.hpp).  One uint4 per 32 columns of a row: x = D  (trav < thrDefault, raw compare: NaN 0, -inf 1),
 // y = Df (finite && trav < thrDefault), z = C (finite && trav < thrCandidate), w = F (finite); bit b of a word =

@@ -1370,7 +1370,8 @@ struct LegStatic {
     LegConst lk;
     double biasX, biasY;  // defaultBias of the leg (cpp:403-421)
 };
-__device__ __forceinline__ LegStatic make_leg_static(const PlanConsts& pc, const fpe_pose* pp, int leg, double res,
+template <class PC>  // PlanConsts, or the 3x3-only bit-window kernels' PlanMidConsts
+__device__ __forceinline__ LegStatic make_leg_static(const PC& pc, const fpe_pose* pp, int leg, double res,
                                                      const SpiralLut& lut) {
     LegStatic ls;
     ls.Rf = pp->leg_search_radius[leg];
