@@ -605,6 +605,70 @@ int fpe_centroid_map(fpe_handle h, const fpe_params* params, const int32_t roi[4
 int fpe_centroid_map_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], float search_radius,
                             const fpe_centroid_map_out* d_out, void* stream);
 
+/* ---- rank a pose batch on the device: per-pose summaries, the best K poses and their products, compacted ----------------
+ * BUILD-DEFINED (the reference plans one pose per service call and ranks nothing).  One call plans the batch as fpe_plan does,
+ * reduces every pose's plan to a 64-byte summary, scores the poses, and returns the K best pose indices with only those
+ * poses' products.  What a summary holds is the reference's own bookkeeping and KPIs, per pose:
+ *   success, gait_cycles_succeed   the GlobalFootholds bookkeeping of the nominal message (cpp:1379-1380, 1574), exactly as
+ *                         fpe_plan_service derives it from cycle_ok;
+ *   cog_speed_*, feet_distance_*   footholdsKPI_ of the nominal track (getHipDistance cpp:2571-2584, getCogSpeed cpp:2587-2623):
+ *                         the entries of fpe_track_report of the nominal track — the current feet start at stance - double(stepLength / 2),
+ *                         two entries of each per committed cycle, RF_FIRST honoured.  min / max by `v < min` / `v > max` from the
+ *                         first entry on; the sum sequential in report order.  Trot only: walk-gait poses have all five 0;
+ *   deviation_sq_sum      over every cycle g with cycle_ok, ascending, legs RF, RH, LH, LF: acc = acc + (dx*dx + dy*dy) with
+ *                         dx = nominal.x - default_next.x, dy alike (f64, no contraction).
+ * score = w_fail*(n_cycles - committed) + w_spiral*n_source[1] + w_none*(n_source[2] + n_source[3]) + w_deviation*deviation_sq_sum
+ *         + w_speed_spread*(cog_speed_max - cog_speed_min): each product first, the five terms added left to right in f64, -0.0
+ * stored as +0.0.  Order: (class, score, pose index) ascending — class 2 = non-finite score (ordered by index alone), class 1 =
+ * gait_cycles_succeed < min_cycles, class 0 = the rest; equal scores (IEEE ==) fall to the index.  The result is a function
+ * of the inputs alone: nothing depends on workgroup scheduling. */
+typedef struct fpe_pose_summary {          /* 64 bytes */
+    uint8_t  success;              /* nominal message: validity of the LAST cycle (cpp:1380, 1574) */
+    uint8_t  gait_cycles_succeed;  /* index + 1 of the last valid cycle (cpp:1379); 0 = none */
+    uint8_t  committed;            /* number of valid cycles */
+    uint8_t  first_failed;         /* first cycle with cycle_ok 0; 255 = none */
+    uint8_t  pose_status;          /* FPE_POSE_* bits */
+    uint8_t  pad[3];
+    uint16_t n_source[4];          /* legs of ALL planned cycles by fpe_foothold.source 0..3; sums to 4 * n_cycles */
+    double   cog_speed_sum;        /* sum of the nominal track's cog_speed entries, report order, starting from +0.0 */
+    double   cog_speed_min, cog_speed_max;         /* over the same entries; 0 when there are none */
+    double   feet_distance_min, feet_distance_max; /* over the nominal feet_distance entries; 0 when none */
+    double   deviation_sq_sum;     /* see above */
+} fpe_pose_summary;
+
+typedef struct fpe_rank_params {
+    double  w_fail, w_spiral, w_none, w_deviation, w_speed_spread;  /* all finite, else FPE_E_INVALID_ARG */
+    int32_t min_cycles;   /* poses with gait_cycles_succeed < min_cycles are class 1; 0..255 */
+    int32_t reserved;
+} fpe_rank_params;
+/* build-defined defaults: w_fail 100, w_spiral 1, w_none 0, w_deviation 10, w_speed_spread 0, min_cycles 0 */
+int fpe_rank_params_defaults(fpe_rank_params* out);
+
+typedef struct fpe_rank_out {
+    fpe_pose_summary* summary;   /* [B] or NULL */
+    double*  score;              /* [B] or NULL */
+    int32_t* best;               /* [K] pose indices, best first — required */
+    int32_t* n_class0;           /* [1] number of class-0 poses in the whole batch, or NULL */
+    fpe_plan_out best_products;  /* products of pose best[k] in slot k: shapes of fpe_plan_out with B replaced by K;
+                                    any pointer may be NULL.  gait_cycle_id / foot_id inside the records stay as planned */
+} fpe_rank_out;
+
+/* Replaces, for a node that samples B candidate start poses, B plan_global_footholds calls (cpp:539-1602) and the comparison of
+ * their responses on the host: fpe_plan's seam (cpp:762-1579) for the batch, then the pick.  Host arrays; synchronous; only the
+ * K-sized and B-sized outputs cross the link (pinned destinations, fpe_host_alloc, are written without a staging copy where the
+ * output is large).  rank NULL = fpe_rank_params_defaults.  1 <= K <= min(B, 1024) and 1 <= n_cycles <= 255, else
+ * FPE_E_INVALID_ARG; a refused call writes nothing.  The map-size bound of selected_packed (FPE_PACKED_MAX_CELLS) applies only
+ * when that product is requested. */
+int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses,
+                  int32_t B, int32_t n_cycles, int32_t K, const fpe_rank_out* out);
+/* Device-resident form of the same seam: d_poses and every non-NULL pointer of d_full / d_out are DEVICE pointers; asynchronous
+ * on `stream`, snapshot semantics of fpe_plan_device.  d_full (may be NULL) receives the un-compacted products of all B poses
+ * exactly as fpe_plan_device writes them, and the ranking reads them there; products the ranking needs that the caller did
+ * not ask for live in stream-ordered scratch. */
+int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses,
+                         int32_t B, int32_t n_cycles, int32_t K, const fpe_plan_out* d_full /* may be NULL */,
+                         const fpe_rank_out* d_out, void* stream);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

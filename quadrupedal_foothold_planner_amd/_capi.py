@@ -202,6 +202,41 @@ class CentroidMapOut(C.Structure):
     _fields_ = [("code", C.c_void_p), ("offset", C.c_void_p), ("z", C.c_void_p)]
 
 
+# fpe_pose_summary: what fpe_plan_rank* reduces one pose's plan to (64 bytes)
+POSE_SUMMARY_DTYPE = np.dtype(
+    [("success", "u1"), ("gait_cycles_succeed", "u1"), ("committed", "u1"), ("first_failed", "u1"), ("pose_status", "u1"),
+     ("pad", "u1", (3,)), ("n_source", "<u2", (4,)), ("cog_speed_sum", "<f8"), ("cog_speed_min", "<f8"), ("cog_speed_max", "<f8"),
+     ("feet_distance_min", "<f8"), ("feet_distance_max", "<f8"), ("deviation_sq_sum", "<f8")],
+    align=True,
+)
+RANK_PARAMS_DTYPE = np.dtype(
+    [("w_fail", "<f8"), ("w_spiral", "<f8"), ("w_none", "<f8"), ("w_deviation", "<f8"), ("w_speed_spread", "<f8"),
+     ("min_cycles", "<i4"), ("reserved", "<i4")],
+    align=True,
+)
+assert POSE_SUMMARY_DTYPE.itemsize == 64 and RANK_PARAMS_DTYPE.itemsize == 48
+
+
+class PoseSummary(C.Structure):
+    """fpe_pose_summary (include/fpe.h)."""
+    _fields_ = [("success", C.c_uint8), ("gait_cycles_succeed", C.c_uint8), ("committed", C.c_uint8), ("first_failed", C.c_uint8),
+                ("pose_status", C.c_uint8), ("pad", C.c_uint8 * 3), ("n_source", C.c_uint16 * 4), ("cog_speed_sum", C.c_double),
+                ("cog_speed_min", C.c_double), ("cog_speed_max", C.c_double), ("feet_distance_min", C.c_double),
+                ("feet_distance_max", C.c_double), ("deviation_sq_sum", C.c_double)]
+
+
+class RankParams(C.Structure):
+    """fpe_rank_params: the score's weights and the class-1 threshold."""
+    _fields_ = [("w_fail", C.c_double), ("w_spiral", C.c_double), ("w_none", C.c_double), ("w_deviation", C.c_double),
+                ("w_speed_spread", C.c_double), ("min_cycles", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RankOut(C.Structure):
+    """fpe_rank_out: outputs of a ranking call (`best` is required; anything else may be NULL)."""
+    _fields_ = [("summary", C.c_void_p), ("score", C.c_void_p), ("best", C.c_void_p), ("n_class0", C.c_void_p),
+                ("best_products", PlanOut)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the ctypes structures below mirror that layout
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -258,6 +293,9 @@ EXPORTED_SYMBOLS = [
     "fpe_centroid_legs_device",
     "fpe_centroid_map",
     "fpe_centroid_map_device",
+    "fpe_rank_params_defaults",
+    "fpe_plan_rank",
+    "fpe_plan_rank_device",
     "fpe_spiral_offsets",
     "fpe_tile_halfwidth",
     "fpe_algorithmic_bytes_per_foothold",
@@ -348,6 +386,9 @@ def lib():
     L.fpe_centroid_legs_device.argtypes = [vp, vp, vp, i32, vp, vp]
     L.fpe_centroid_map.argtypes = [vp, vp, vp, f32, C.POINTER(CentroidMapOut)]
     L.fpe_centroid_map_device.argtypes = [vp, vp, vp, f32, C.POINTER(CentroidMapOut), vp]
+    L.fpe_rank_params_defaults.argtypes = [C.POINTER(RankParams)]
+    L.fpe_plan_rank.argtypes = [vp, vp, C.POINTER(RankParams), vp, i32, i32, i32, C.POINTER(RankOut)]
+    L.fpe_plan_rank_device.argtypes = [vp, vp, C.POINTER(RankParams), vp, i32, i32, i32, C.POINTER(PlanOut), C.POINTER(RankOut), vp]
     L.fpe_spiral_offsets.argtypes = [i32, vp, i32]
     L.fpe_tile_halfwidth.argtypes = [f32, f32, f64]
     L.fpe_algorithmic_bytes_per_foothold.restype = f64
@@ -382,6 +423,17 @@ def opt_params_code_defaults():
     p = np.zeros(1, dtype=OPT_PARAMS_DTYPE)
     assert lib().fpe_opt_params_code_defaults(ptr(p)) == FPE_OK
     return p
+
+
+def rank_params_defaults(**overrides):
+    """fpe_rank_params_defaults, with any field replaced by a keyword."""
+    rp = RankParams()
+    assert lib().fpe_rank_params_defaults(C.byref(rp)) == FPE_OK
+    for k, v in overrides.items():
+        if k not in dict(RankParams._fields_):
+            raise ValueError(f"unknown rank parameter {k!r}")
+        setattr(rp, k, v)
+    return rp
 
 
 def spiral_offsets(n_rings):

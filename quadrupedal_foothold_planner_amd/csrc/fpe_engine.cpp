@@ -84,6 +84,18 @@ bool centroid_map_consts(const MapGeom& g, const FootmapRoi& roi, float R, CmapC
 size_t centroid_map_scratch_bytes(const FootmapRoi& roi, const CmapConsts& cc);
 hipError_t launch_centroid_map(const DevMap& m, const PlanConsts& pc, const CmapConsts& cc, const FootmapRoi& roi, void* scratch,
                                uint8_t* d_code, int8_t* d_offset, float* d_z, hipStream_t stream);
+// ranking of a planned batch (fpe_rank.hpp part of fpe_kernels.hip)
+struct RankConsts {
+    double wFail, wSpiral, wNone, wDeviation, wSpeedSpread;
+    double stepHalf;
+    int32_t minCycles;
+    int32_t rfFirst;
+};
+size_t rank_scratch_bytes(int B, int K);
+hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
+                       fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
+                       const fpe_plan_out& bestProducts, hipStream_t stream);
+hipError_t set_max_lds_rank();
 }  // namespace fpe
 
 namespace {
@@ -1020,6 +1032,7 @@ int fpe_create(int device_id, fpe_handle* out) {
     // every kernel may use the whole 160 KiB of LDS: set once per process and device, never lowered again (a
     // second engine on the same device sets the same value)
     FPE_HIP_C(fpe::set_max_lds(kMaxLdsBytes, kMaxLdsBytes));
+    FPE_HIP_C(fpe::set_max_lds_rank());
 #undef FPE_HIP_C
     *out = h;
     return FPE_OK;
@@ -1306,16 +1319,9 @@ int prepare_opt(const fpe_params* params, const fpe_opt_params* opt, const CallP
 // The host-buffer form of the plan and / or the opt track: one device arena, the launches back to back on one
 // stream, the results copied out.  `out` NULL: no plan products are returned (the plan still runs when the opt track
 // needs its cycle flags and the caller gave none).
-struct GateGeom {  // what the service call's host-side (lateral) gate needs from the call's snapshot and constants
-    fpe::MapGeom g;
-    double isosLen, isosWid, drift;
-};
-int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B, int32_t n_cycles,
-              const fpe_plan_out* out, const uint8_t* cycleOkIn, const fpe_opt_out* oout, GateGeom* gateGeom = nullptr,
-              bool* optDropped = nullptr) {
-    if (!poses || (!out && !oout)) return fail(FPE_E_INVALID_ARG, "null argument");
-    if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
-    float maxRadius = 0.0f;
+// The poses of a host-buffer call, checked; maxRadius: the largest per-leg search radius among them.
+int check_host_poses(const fpe_pose* poses, int32_t B, float& maxRadius) {
+    maxRadius = 0.0f;
     for (int b = 0; b < B; ++b) {
         for (int k = 0; k < 3; ++k)
             if (!std::isfinite(poses[b].position[k]) || std::fabs(poses[b].position[k]) > 1e6)
@@ -1327,6 +1333,21 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
                 return fail(FPE_E_INVALID_ARG, "unknown polygon kind");
         }
     }
+    return FPE_OK;
+}
+
+struct GateGeom {  // what the service call's host-side (lateral) gate needs from the call's snapshot and constants
+    fpe::MapGeom g;
+    double isosLen, isosWid, drift;
+};
+int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B, int32_t n_cycles,
+              const fpe_plan_out* out, const uint8_t* cycleOkIn, const fpe_opt_out* oout, GateGeom* gateGeom = nullptr,
+              bool* optDropped = nullptr) {
+    if (!poses || (!out && !oout)) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
+    float maxRadius = 0.0f;
+    int rcPoses = check_host_poses(poses, B, maxRadius);
+    if (rcPoses != FPE_OK) return rcPoses;
     fpe_plan_out none;
     std::memset(&none, 0, sizeof(none));
     const fpe_plan_out& po = out ? *out : none;
@@ -1830,6 +1851,188 @@ int fpe_centroid_map(fpe_handle h, const fpe_params* params, const int32_t roi[4
     return stage_products(cx, prod, [&](unsigned char* const* d, hipStream_t s) {
         return run_centroid_map(cp, r, cc, d[0], reinterpret_cast<int8_t*>(d[1]), reinterpret_cast<float*>(d[2]), s);
     });
+}
+
+int fpe_rank_params_defaults(fpe_rank_params* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->w_fail = 100.0;
+    out->w_spiral = 1.0;
+    out->w_none = 0.0;
+    out->w_deviation = 10.0;
+    out->w_speed_spread = 0.0;
+    out->min_cycles = 0;
+    return FPE_OK;
+}
+
+namespace {
+// Arguments of fpe_plan_rank* that need no map; rc: the ranking's constants (rank NULL: the defaults).
+int check_rank_args(const fpe_params* params, const fpe_rank_params* rank, int32_t B, int32_t n_cycles, int32_t K, const fpe_rank_out* out,
+                    fpe::RankConsts& rc) {
+    if (!params || !out || !out->best) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
+    if (K < 1 || K > B || K > 1024) return fail(FPE_E_INVALID_ARG, "K must be in [1, min(B, 1024)]");
+    fpe_rank_params def;
+    if (!rank) {
+        fpe_rank_params_defaults(&def);
+        rank = &def;
+    }
+    const double w[5] = {rank->w_fail, rank->w_spiral, rank->w_none, rank->w_deviation, rank->w_speed_spread};
+    for (double v : w)
+        if (!std::isfinite(v)) return fail(FPE_E_INVALID_ARG, "rank weights must be finite");
+    if (rank->min_cycles < 0 || rank->min_cycles > 255) return fail(FPE_E_INVALID_ARG, "min_cycles must be in [0, 255]");
+    rc = fpe::RankConsts{w[0], w[1], w[2], w[3], w[4], static_cast<double>(params->stepLength / 2), rank->min_cycles, params->RF_FIRST};
+    return FPE_OK;
+}
+
+// Where everything a ranking call touches on the device lives.  `full`: the un-compacted products — the caller's (d_full) where given,
+// scratch for what the ranking reads or the compaction copies from, null for the rest.  The B-sized and K-sized outputs the caller
+// did not place (null in `placed`) go to the output block when `outputs` says so (the host form: every requested one), and summary /
+// score to scratch otherwise.  lay(base, outBase) fills the pointers; both bases null: sizes only.
+struct RankLayout {
+    int32_t B, n, K;
+    fpe_plan_out full, best;
+    fpe_pose_summary* summary;
+    double* score;
+    int32_t* bestIdx;
+    int32_t* nClass0;
+    void* keys;
+    size_t scratchBytes, outBytes;
+    size_t outOff[12], outLen[12];  // summary, score, best, n_class0, the eight products: the host form's transfers
+};
+void rank_layout(RankLayout& L, const fpe_plan_out* dFull, const fpe_rank_out& want, bool hostForm, unsigned char* base, unsigned char* outBase) {
+    const size_t nRec = static_cast<size_t>(L.n) * 4;
+    const size_t perPose[8] = {nRec * sizeof(fpe_foothold), nRec * sizeof(fpe_centroid_foothold), nRec * 3 * sizeof(double), static_cast<size_t>(L.n),
+                               12 * sizeof(double), nRec * sizeof(fpe_selected_foothold), 1, nRec * sizeof(fpe_selected_packed)};
+    const bool reads[8] = {true, false, true, true, true, false, true, false};  // rank_summary_kernel's inputs
+    size_t off = 0, oo = 0;
+    const auto take = [&](size_t bytes) {
+        unsigned char* p = base + off;
+        off += align256(bytes);
+        return static_cast<void*>(p);
+    };
+    const auto takeOut = [&](int k, size_t bytes) {
+        L.outOff[k] = oo;
+        L.outLen[k] = bytes;
+        oo += align256(bytes);
+        return static_cast<void*>(outBase + L.outOff[k]);
+    };
+    for (int k = 0; k < 12; ++k) L.outOff[k] = L.outLen[k] = 0;
+    void* const* given = reinterpret_cast<void* const*>(dFull);  // fpe_plan_out is eight pointers
+    void* const* wanted = reinterpret_cast<void* const*>(&want.best_products);
+    void** full = reinterpret_cast<void**>(&L.full);
+    void** best = reinterpret_cast<void**>(&L.best);
+    for (int k = 0; k < 8; ++k) {
+        full[k] = (given && given[k]) ? given[k] : ((reads[k] || wanted[k]) ? take(static_cast<size_t>(L.B) * perPose[k]) : nullptr);
+        best[k] = !wanted[k] ? nullptr : (hostForm ? takeOut(4 + k, static_cast<size_t>(L.K) * perPose[k]) : wanted[k]);
+    }
+    const size_t szSum = static_cast<size_t>(L.B) * sizeof(fpe_pose_summary), szScore = static_cast<size_t>(L.B) * sizeof(double);
+    L.summary = static_cast<fpe_pose_summary*>(!want.summary ? take(szSum) : (hostForm ? takeOut(0, szSum) : want.summary));
+    L.score = static_cast<double*>(!want.score ? take(szScore) : (hostForm ? takeOut(1, szScore) : want.score));
+    L.bestIdx = static_cast<int32_t*>(hostForm ? takeOut(2, static_cast<size_t>(L.K) * sizeof(int32_t)) : want.best);
+    L.nClass0 = static_cast<int32_t*>(!want.n_class0 ? nullptr : (hostForm ? takeOut(3, sizeof(int32_t)) : want.n_class0));
+    L.keys = take(fpe::rank_scratch_bytes(L.B, L.K));
+    L.scratchBytes = off;
+    L.outBytes = oo;
+}
+
+// The launches of a prepared ranking call on `stream`: the plan through launch_plan, then summary, select, gather.
+int run_rank(fpe_engine* h, const CallPlan& cp, const fpe::RankConsts& rc, const fpe_pose* d_poses, const RankLayout& L, hipStream_t stream) {
+    int rc0 = launch_plan(h, cp, d_poses, L.B, L.n, L.full, stream);
+    if (rc0 != FPE_OK) return rc0;
+    FPE_HIP(fpe::launch_rank(rc, d_poses, L.B, L.n, L.K, L.full, L.summary, L.score, L.keys, L.bestIdx, L.nClass0, L.best, stream));
+    return FPE_OK;
+}
+}  // namespace
+
+int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses, int32_t B,
+                         int32_t n_cycles, int32_t K, const fpe_plan_out* d_full, const fpe_rank_out* d_out, void* stream) {
+    fpe::RankConsts rc;
+    int rc0 = check_rank_args(params, rank, B, n_cycles, K, d_out, rc);
+    if (rc0 != FPE_OK) return rc0;
+    if (!d_poses) return fail(FPE_E_INVALID_ARG, "null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    rc0 = prepare_call(h, params, 0.0f, cp, st, true);
+    if (rc0 != FPE_OK) return rc0;
+    RankLayout L{};
+    L.B = B, L.n = n_cycles, L.K = K;
+    rank_layout(L, d_full, *d_out, false, nullptr, nullptr);
+    if (((d_full && d_full->selected_packed) || d_out->best_products.selected_packed) && (cp.snap->g.rows > FPE_PACKED_MAX_CELLS || cp.snap->g.cols > FPE_PACKED_MAX_CELLS))
+        return fail(FPE_E_UNSUPPORTED, "selected_packed holds biased 14-bit grid indices: the map has more than 15871 rows or columns");
+    mark_async_launch(cp);
+    void* scratch = nullptr;
+    FPE_HIP(hipMallocAsync(&scratch, L.scratchBytes, st));
+    rank_layout(L, d_full, *d_out, false, static_cast<unsigned char*>(scratch), nullptr);
+    rc0 = run_rank(h, cp, rc, d_poses, L, st);
+    const hipError_t f = hipFreeAsync(scratch, st);
+    if (rc0 != FPE_OK) return rc0;
+    FPE_HIP(f);
+    return FPE_OK;
+}
+
+int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses, int32_t B, int32_t n_cycles,
+                  int32_t K, const fpe_rank_out* out) {
+    fpe::RankConsts rc;
+    int rc0 = check_rank_args(params, rank, B, n_cycles, K, out, rc);
+    if (rc0 != FPE_OK) return rc0;
+    if (!h || !poses) return fail(FPE_E_INVALID_ARG, "null argument");
+    float maxRadius = 0.0f;
+    rc0 = check_host_poses(poses, B, maxRadius);
+    if (rc0 != FPE_OK) return rc0;
+    RankLayout L{};
+    L.B = B, L.n = n_cycles, L.K = K;
+    rank_layout(L, nullptr, *out, true, nullptr, nullptr);
+    // both arenas: [poses | outputs | scratch].  The poses are read from the pinned arena (device-mapped), as in fpe_plan; outputs of up
+    // to kZeroCopyBytes are WRITTEN there by the kernels too (no transfer at all: a DMA costs some ten microseconds, whatever its size)
+    const size_t szPose = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    const bool zeroCopy = L.outBytes <= kZeroCopyBytes;
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(szPose + L.outBytes + L.scratchBytes));
+    cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
+    rc0 = prepare_call(h, params, maxRadius, cp, cx.stream, true);
+    if (rc0 != FPE_OK) return rc0;
+    if (out->best_products.selected_packed && (cp.snap->g.rows > FPE_PACKED_MAX_CELLS || cp.snap->g.cols > FPE_PACKED_MAX_CELLS))
+        return fail(FPE_E_UNSUPPORTED, "selected_packed holds biased 14-bit grid indices: the map has more than 15871 rows or columns");
+    std::memcpy(cx.pinned, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
+    void* mapped = nullptr;
+    FPE_HIP(hipHostGetDevicePointer(&mapped, cx.pinned, 0));
+    unsigned char* const hostOut = cx.pinned + szPose;
+    unsigned char* const devOut = zeroCopy ? static_cast<unsigned char*>(mapped) + szPose : cx.dev + szPose;
+    rank_layout(L, nullptr, *out, true, cx.dev + szPose + L.outBytes, devOut);
+    rc0 = run_rank(h, cp, rc, static_cast<const fpe_pose*>(mapped), L, cx.stream);
+    if (rc0 != FPE_OK) return rc0;
+    void* const dst[12] = {out->summary, out->score, out->best, out->n_class0, out->best_products.nominal, out->best_products.centroid,
+                           out->best_products.default_next, out->best_products.cycle_ok, out->best_products.stance, out->best_products.selected,
+                           out->best_products.pose_status, out->best_products.selected_packed};
+    bool direct[12] = {false};
+    if (!zeroCopy) {
+        // stage_products' pattern: a pinned destination is written by DMA, any other through the pinned arena — neighbours there in one transfer
+        for (int k = 0; k < 12; ++k) direct[k] = L.outLen[k] && is_pinned_host(dst[k]);
+        for (int k = 0; k < 12; ++k) {
+            if (!L.outLen[k]) continue;
+            if (direct[k]) {
+                FPE_HIP(hipMemcpyAsync(dst[k], devOut + L.outOff[k], L.outLen[k], hipMemcpyDeviceToHost, cx.stream));
+                continue;
+            }
+            size_t begin = L.outOff[k], end = begin + L.outLen[k];
+            int last = k;
+            while (last + 1 < 12 && (!L.outLen[last + 1] || (!is_pinned_host(dst[last + 1]) && L.outOff[last + 1] == align256(end)))) {
+                ++last;
+                if (L.outLen[last]) end = L.outOff[last] + L.outLen[last];
+            }
+            FPE_HIP(hipMemcpyAsync(hostOut + begin, devOut + begin, end - begin, hipMemcpyDeviceToHost, cx.stream));
+            k = last;
+        }
+    }
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    for (int k = 0; k < 12; ++k)
+        if (L.outLen[k] && !direct[k]) std::memcpy(dst[k], hostOut + L.outOff[k], L.outLen[k]);
+    return FPE_OK;
 }
 
 int fpe_last_service_gate(fpe_handle h, fpe_service_gate* out) {

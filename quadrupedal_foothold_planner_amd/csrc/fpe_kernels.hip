@@ -2109,6 +2109,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_footsnap.hpp"
 // ---- part six: the dense centroid map (fpe_centroid_map*) ----------------------------------------------------
 #include "fpe_centroidmap.hpp"
+// ---- part seven: ranking a planned batch (fpe_plan_rank*) ------------------------------------------------------
+#include "fpe_rank.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<16>),

@@ -1,0 +1,340 @@
+// fpe_rank.hpp — part seven of fpe_kernels.hip: rank a planned pose batch on the device (fpe_plan_rank*, include/fpe.h).
+// Three kernels behind the plan kernel, on what it wrote: a per-pose summary with its score and sort key, the K smallest keys
+// (sorted), and the copy of the chosen poses' products into K slots.  No atomics anywhere: every output is a function of the
+// inputs alone.
+#pragma once
+
+struct RankConsts {
+    double wFail, wSpiral, wNone, wDeviation, wSpeedSpread;
+    double stepHalf;  // double(stepLength / 2): the current feet start at stance - stepHalf (setFirstGait, cpp:2679-2699)
+    int32_t minCycles;
+    int32_t rfFirst;
+};
+
+// Sort key of one pose, ascending = better: hi = class << 32 | image >> 32, lo = image << 32 | pose index, with `image` the
+// order-preserving 64-bit image of the score (0 for class 2: those fall to the index alone).  All ones = no pose.
+struct alignas(16) RankKey {
+    unsigned long long hi, lo;
+};
+
+constexpr int kRankTile = 8192;  // keys one workgroup sorts in LDS: 128 KiB of the CU's 160
+constexpr int kRankMaxK = 1024;
+constexpr int kRankProducts = 8;
+
+// One product of the gather: `unit`-byte words (16, 4 or 1: what both pointers and the per-pose size are multiples of)
+struct RankCopy {
+    const unsigned char* src;
+    unsigned char* dst;
+    uint32_t words;  // per pose
+    uint32_t unit;
+};
+struct RankCopies {
+    RankCopy c[kRankProducts];
+    int32_t n;
+};
+
+namespace {
+
+__device__ __forceinline__ bool rank_key_less(const RankKey& a, const RankKey& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+
+// One pose per group of four lanes, lane = leg: each lane loads its leg's records, the four values of a cycle meet by shuffle
+// and every lane of the group runs the same f64 chain on them in the stated order (lane 0 writes).
+__global__ __launch_bounds__(256) void rank_summary_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, RankConsts rc,
+                                                           const fpe_foothold* __restrict__ nominal, const double* __restrict__ defaultNext,
+                                                           const uint8_t* __restrict__ cycleOk, const double* __restrict__ stance,
+                                                           const uint8_t* __restrict__ poseStatus, fpe_pose_summary* __restrict__ summary,
+                                                           double* __restrict__ score, RankKey* __restrict__ keys) {
+    const int t = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int b = t >> 2, leg = t & 3;
+    const int bb = b < B ? b : B - 1;  // (lanes past the batch run pose B - 1 again and write nothing: the shuffles stay whole)
+    int gait = leg == 0 ? poses[bb].gait : 0;
+    gait = __shfl(gait, 0, 4);
+    const bool trot = gait == 0;
+    const double cx = stance[static_cast<size_t>(bb) * 12 + leg * 3] - rc.stepHalf;
+    enum { RF = 0, RH = 1, LH = 2, LF = 3 };
+    double cur[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) cur[l] = __shfl(cx, l, 4);
+    uint32_t cnt01 = 0, cnt23 = 0;  // this leg's records by source, 16 bits each
+    int committed = 0, succeed = 0, firstFailed = 255, lastOk = 0, nKpi = 0;
+    double dev = 0.0, spSum = 0.0, spMin = 0.0, spMax = 0.0, fdMin = 0.0, fdMax = 0.0;
+    const size_t rec0 = static_cast<size_t>(bb) * nCycles * 4 + leg;
+    for (int g = 0; g < nCycles; ++g) {
+        const size_t q = rec0 + static_cast<size_t>(g) * 4;
+        const fpe_foothold& f = nominal[q];
+        const double x = f.x, y = f.y;
+        const uint32_t src = f.source & 3u;
+        const double dx = x - defaultNext[q * 3], dy = y - defaultNext[q * 3 + 1];
+        const double term = dx * dx + dy * dy;
+        const int ok = cycleOk[static_cast<size_t>(bb) * nCycles + g] != 0;
+        if (src < 2) cnt01 += 1u << (16 * src);
+        else cnt23 += 1u << (16 * (src - 2));
+        double r[4], d[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            r[l] = __shfl(x, l, 4);
+            d[l] = __shfl(term, l, 4);
+        }
+        lastOk = ok;
+        if (!ok && firstFailed == 255) firstFailed = g;
+        if (!ok) continue;  // (uniform within the pose's four lanes; the shuffles above ran with every lane)
+        ++committed;
+        succeed = g + 1;
+        dev = dev + d[RF];
+        dev = dev + d[RH];
+        dev = dev + d[LH];
+        dev = dev + d[LF];
+        if (trot) {  // assemble_track_report (fpe_host.cpp), nominal track
+            const double fd0 = r[RF] - r[LH], fd1 = r[LF] - r[RH];
+            double c1, c2, c3;
+            if (rc.rfFirst) {
+                c1 = (cur[RF] + cur[LH]) / 2;
+                c2 = (r[LF] + r[RH]) / 2;
+                c3 = (r[RF] + r[LH]) / 2;
+            } else {
+                c1 = (cur[LF] + cur[RH]) / 2;
+                c2 = (r[RF] + r[LH]) / 2;
+                c3 = (r[LF] + r[RH]) / 2;
+            }
+            const double s0 = (c2 - c1) / 0.5, s1 = (c3 - c2) / 0.5;
+            if (nKpi == 0) {
+                spMin = spMax = s0;
+                fdMin = fdMax = fd0;
+            }
+            if (s0 < spMin) spMin = s0;
+            if (s0 > spMax) spMax = s0;
+            if (s1 < spMin) spMin = s1;
+            if (s1 > spMax) spMax = s1;
+            if (fd0 < fdMin) fdMin = fd0;
+            if (fd0 > fdMax) fdMax = fd0;
+            if (fd1 < fdMin) fdMin = fd1;
+            if (fd1 > fdMax) fdMax = fd1;
+            spSum = spSum + s0;
+            spSum = spSum + s1;
+            nKpi += 2;
+#pragma unroll
+            for (int l = 0; l < 4; ++l) cur[l] = r[l];
+        }
+    }
+    cnt01 += __shfl_xor(cnt01, 1, 4);
+    cnt01 += __shfl_xor(cnt01, 2, 4);
+    cnt23 += __shfl_xor(cnt23, 1, 4);
+    cnt23 += __shfl_xor(cnt23, 2, 4);
+    if (leg != 0 || b >= B) return;
+    const uint32_t n0 = cnt01 & 0xFFFFu, n1 = cnt01 >> 16, n2 = cnt23 & 0xFFFFu, n3 = cnt23 >> 16;
+    fpe_pose_summary s;
+    s.success = static_cast<uint8_t>(lastOk);
+    s.gait_cycles_succeed = static_cast<uint8_t>(succeed);
+    s.committed = static_cast<uint8_t>(committed);
+    s.first_failed = static_cast<uint8_t>(firstFailed);
+    s.pose_status = poseStatus[b];
+    s.pad[0] = s.pad[1] = s.pad[2] = 0;
+    s.n_source[0] = static_cast<uint16_t>(n0);
+    s.n_source[1] = static_cast<uint16_t>(n1);
+    s.n_source[2] = static_cast<uint16_t>(n2);
+    s.n_source[3] = static_cast<uint16_t>(n3);
+    s.cog_speed_sum = spSum;
+    s.cog_speed_min = spMin;
+    s.cog_speed_max = spMax;
+    s.feet_distance_min = fdMin;
+    s.feet_distance_max = fdMax;
+    s.deviation_sq_sum = dev;
+    summary[b] = s;
+    const double t0 = rc.wFail * static_cast<double>(nCycles - committed);
+    const double t1 = rc.wSpiral * static_cast<double>(n1);
+    const double t2 = rc.wNone * static_cast<double>(n2 + n3);
+    const double t3 = rc.wDeviation * dev;
+    const double t4 = rc.wSpeedSpread * (spMax - spMin);
+    double sc = t0 + t1;
+    sc = sc + t2;
+    sc = sc + t3;
+    sc = sc + t4;
+    if (sc == 0.0) sc = 0.0;  // -0.0 -> +0.0
+    score[b] = sc;
+    const bool finite = __builtin_isfinite(sc);
+    const unsigned long long cls = !finite ? 2ull : (succeed < rc.minCycles ? 1ull : 0ull);
+    unsigned long long img = 0ull;
+    if (finite) {
+        const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(sc));
+        img = (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
+    }
+    RankKey k;
+    k.hi = (cls << 32) | (img >> 32);
+    k.lo = (img << 32) | static_cast<unsigned long long>(static_cast<uint32_t>(b));
+    keys[b] = k;
+}
+
+// Workgroup blockIdx.x sorts keys [blockIdx.x * kRankTile, + kRankTile) of `in` (n keys in all) in LDS — a bitonic network over
+// the next power of two, padded with "no pose" keys — and keeps the first K.  Tile stage (tileOut given): K keys per tile to
+// tileOut, and (countsOut given) the tile's number of class-0 keys.  Final stage (one workgroup, n <= kRankTile): best[K], and
+// n_class0 = the sum of `tileCounts` when a tile stage counted, else this workgroup's own count.
+__global__ __launch_bounds__(1024) void rank_select_kernel(const RankKey* __restrict__ in, int n, int K, RankKey* __restrict__ tileOut,
+                                                           int32_t* __restrict__ countsOut, int32_t* __restrict__ best,
+                                                           int32_t* __restrict__ nClass0, const int32_t* __restrict__ tileCounts,
+                                                           int nTileCounts) {
+    extern __shared__ RankKey rankLds[];
+    __shared__ int32_t waveCount[16];
+    RankKey* s = rankLds;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int base = static_cast<int>(blockIdx.x) * kRankTile;
+    const int cnt = n - base < kRankTile ? n - base : kRankTile;
+    int N = 64;
+    while (N < cnt) N <<= 1;
+    const RankKey none{~0ull, ~0ull};
+    int c0 = 0;
+    for (int i = tid; i < N; i += 1024) {
+        RankKey k = none;
+        if (i < cnt) {
+            k = in[base + i];
+            c0 += (k.hi >> 32) == 0ull;
+        }
+        s[i] = k;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c0 += __shfl_xor(c0, o, 64);
+    if ((tid & 63) == 0) waveCount[tid >> 6] = c0;
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < (N >> 1); i += 1024) {
+                const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1)), c = a | j;
+                const RankKey ka = s[a], kc = s[c];
+                const bool up = (a & k) == 0;
+                if (rank_key_less(kc, ka) == up) {
+                    s[a] = kc;
+                    s[c] = ka;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tileOut) {
+        for (int i = tid; i < K; i += 1024) tileOut[static_cast<size_t>(blockIdx.x) * K + i] = i < N ? s[i] : none;
+    } else {
+        for (int i = tid; i < K; i += 1024) best[i] = static_cast<int32_t>(static_cast<uint32_t>(s[i].lo));
+    }
+    if (tid == 0) {
+        int total = 0;
+        for (int w = 0; w < 16; ++w) total += waveCount[w];
+        if (countsOut) countsOut[blockIdx.x] = total;
+        if (nClass0) {
+            if (tileCounts) {
+                total = 0;
+                for (int q = 0; q < nTileCounts; ++q) total += tileCounts[q];
+            }
+            *nClass0 = total;
+        }
+    }
+}
+
+// Slot blockIdx.x takes pose best[blockIdx.x]: every requested product's block of that pose, word by word.
+template <class Word>
+__device__ __forceinline__ void rank_copy_words(const RankCopy& c, size_t pose, size_t slot) {
+    const Word* src = reinterpret_cast<const Word*>(c.src) + pose * c.words;
+    Word* dst = reinterpret_cast<Word*>(c.dst) + slot * c.words;
+    for (uint32_t i = threadIdx.x; i < c.words; i += 256) dst[i] = src[i];
+}
+__global__ __launch_bounds__(256) void rank_gather_kernel(const int32_t* __restrict__ best, RankCopies cp) {
+    const size_t slot = blockIdx.x;
+    const size_t pose = static_cast<size_t>(best[slot]);
+    for (int p = 0; p < cp.n; ++p) {
+        const RankCopy& c = cp.c[p];
+        if (c.unit == 16) rank_copy_words<uint4>(c, pose, slot);
+        else if (c.unit == 4) rank_copy_words<uint32_t>(c, pose, slot);
+        else rank_copy_words<unsigned char>(c, pose, slot);
+    }
+}
+
+inline size_t rank_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
+inline int rank_tiles(int n) { return (n + kRankTile - 1) / kRankTile; }
+
+}  // namespace
+
+// Scratch of the ranking of B poses for the best K: the keys, then (B over one tile) the tile stages' two key buffers and the
+// first stage's counts
+size_t rank_scratch_bytes(int B, int K) {
+    size_t total = rank_align256(static_cast<size_t>(B) * sizeof(RankKey));
+    if (B > kRankTile) {
+        const int t1 = rank_tiles(B);
+        total += rank_align256(static_cast<size_t>(t1) * K * sizeof(RankKey));
+        const long long n2 = static_cast<long long>(t1) * K;
+        if (n2 > kRankTile) total += rank_align256(static_cast<size_t>(rank_tiles(static_cast<int>(n2))) * K * sizeof(RankKey));
+        total += rank_align256(static_cast<size_t>(t1) * sizeof(int32_t));
+    }
+    return total;
+}
+
+// Summary, select and gather on `stream`, behind the plan kernel that wrote `full` (nominal, default_next, cycle_ok, stance and
+// pose_status are read; a product of `bestProducts` is copied from the same product of `full`).  d_summary and d_score are
+// required here (the engine hands scratch for what the caller did not ask for).
+hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
+                       fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
+                       const fpe_plan_out& bestProducts, hipStream_t stream) {
+    unsigned char* sp = static_cast<unsigned char*>(scratch);
+    RankKey* keys = reinterpret_cast<RankKey*>(sp);
+    sp += rank_align256(static_cast<size_t>(B) * sizeof(RankKey));
+    hipLaunchKernelGGL(rank_summary_kernel, dim3(static_cast<unsigned>((static_cast<long long>(B) * 4 + 255) / 256)), dim3(256), 0, stream,
+                       d_poses, B, nCycles, rc, full.nominal, full.default_next, full.cycle_ok, full.stance, full.pose_status, d_summary,
+                       d_score, keys);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const RankKey* cur = keys;
+    int n = B;
+    const int32_t* counts = nullptr;
+    int nCounts = 0;
+    if (B > kRankTile) {
+        const int t1 = rank_tiles(B);
+        RankKey* bufA = reinterpret_cast<RankKey*>(sp);
+        sp += rank_align256(static_cast<size_t>(t1) * K * sizeof(RankKey));
+        RankKey* bufB = reinterpret_cast<RankKey*>(sp);
+        if (static_cast<long long>(t1) * K > kRankTile) sp += rank_align256(static_cast<size_t>(rank_tiles(t1 * K)) * K * sizeof(RankKey));
+        int32_t* countsBuf = reinterpret_cast<int32_t*>(sp);
+        RankKey* out = bufA;
+        while (n > kRankTile) {  // every stage keeps K of each 8192 keys: at least four times fewer
+            const int tiles = rank_tiles(n);
+            hipLaunchKernelGGL(rank_select_kernel, dim3(tiles), dim3(1024), kRankTile * sizeof(RankKey), stream, cur, n, K, out,
+                               counts ? nullptr : countsBuf, nullptr, nullptr, nullptr, 0);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            if (!counts) {
+                counts = countsBuf;
+                nCounts = tiles;
+            }
+            cur = out;
+            n = tiles * K;
+            out = out == bufA ? bufB : bufA;
+        }
+    }
+    int N = 64;
+    while (N < n) N <<= 1;
+    hipLaunchKernelGGL(rank_select_kernel, dim3(1), dim3(1024), N * sizeof(RankKey), stream, cur, n, K, nullptr, nullptr, d_best, d_nClass0,
+                       counts, nCounts);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    RankCopies cp;
+    cp.n = 0;
+    const auto add = [&](const void* src, void* dst, size_t bytesPerPose) {
+        if (!dst) return;
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | bytesPerPose;
+        const uint32_t unit = (bits & 15) == 0 ? 16u : ((bits & 3) == 0 ? 4u : 1u);
+        cp.c[cp.n++] = RankCopy{static_cast<const unsigned char*>(src), static_cast<unsigned char*>(dst),
+                                static_cast<uint32_t>(bytesPerPose / unit), unit};
+    };
+    const size_t nRec = static_cast<size_t>(nCycles) * 4;
+    add(full.nominal, bestProducts.nominal, nRec * sizeof(fpe_foothold));
+    add(full.centroid, bestProducts.centroid, nRec * sizeof(fpe_centroid_foothold));
+    add(full.default_next, bestProducts.default_next, nRec * 3 * sizeof(double));
+    add(full.cycle_ok, bestProducts.cycle_ok, static_cast<size_t>(nCycles));
+    add(full.stance, bestProducts.stance, 12 * sizeof(double));
+    add(full.selected, bestProducts.selected, nRec * sizeof(fpe_selected_foothold));
+    add(full.pose_status, bestProducts.pose_status, 1);
+    add(full.selected_packed, bestProducts.selected_packed, nRec * sizeof(fpe_selected_packed));
+    if (cp.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rank_gather_kernel, dim3(K), dim3(256), 0, stream, d_best, cp);
+    return hipGetLastError();
+}
+
+hipError_t set_max_lds_rank() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(rank_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(kRankTile * sizeof(RankKey)));
+}

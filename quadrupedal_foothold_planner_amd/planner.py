@@ -16,7 +16,7 @@ import numpy as np
 from . import _capi
 from ._capi import (CENTROID_DTYPE, CENTROID_QUERY_DTYPE, FOOTHOLD_DTYPE, GLOBAL_FOOTHOLDS_DTYPE, OPT_CYCLE_DTYPE, OPT_FOOTHOLD_DTYPE, OPT_PARAMS_DTYPE,
                     PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
-                    CentroidMapOut, FootholdMapOut, FootholdSnapOut, MapDesc, OptOut, PlanOut, ptr)
+                    CentroidMapOut, FootholdMapOut, FootholdSnapOut, MapDesc, OptOut, PlanOut, RankOut, ptr)
 
 # products of a chained plan in the order of fpe_plan_out's fields (= the order of the engine's device arena)
 PRODUCT_ORDER = ("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status", "selected_packed")
@@ -247,6 +247,57 @@ class FootholdPlanner:
                      d_stance_ptr or None, d_selected_ptr or None, d_pose_status_ptr or None, d_selected_packed_ptr or None)
         self._check(self._lib.fpe_plan_device(self._h, ptr(self.params), C.c_void_p(d_poses_ptr), int(B), int(n_cycles),
                                               C.byref(po), C.c_void_p(stream or 0)))
+
+    # ---- plan a batch and rank it on the device (build-defined: fpe_plan_rank*) ---------------------------------------------
+    @staticmethod
+    def _rank_params(rank):
+        """None (the defaults), a _capi.RankParams, or a dict of its fields to replace."""
+        if rank is None or isinstance(rank, _capi.RankParams):
+            return rank
+        return _capi.rank_params_defaults(**dict(rank))
+
+    def plan_rank(self, poses, n_cycles, K, rank=None, products=("nominal", "cycle_ok", "stance"), summary=True):
+        """fpe_plan_rank with host buffers: plans the batch, scores every pose on the device and returns {"best": int32 [K] pose
+        indices, best first, "n_class0": int, "summary": POSE_SUMMARY_DTYPE [B] and "score": float64 [B] (with summary=True),
+        and each requested product of the K chosen poses, slot k = pose best[k]} — shapes of plan() with B replaced by K."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        B, K = poses.shape[0], int(K)
+        unknown = set(products) - set(PRODUCT_ORDER)
+        if unknown:
+            raise ValueError(f"unknown plan products {sorted(unknown)}")
+        shapes = product_shapes(max(K, 0), n_cycles)
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in PRODUCT_ORDER if k in products}
+        best = np.zeros(max(K, 0), np.int32)
+        n0 = np.zeros(1, np.int32)
+        ro = RankOut(None, None, ptr(best), ptr(n0))
+        if summary:
+            out["summary"] = np.zeros(B, _capi.POSE_SUMMARY_DTYPE)
+            out["score"] = np.zeros(B, np.float64)
+            ro.summary, ro.score = ptr(out["summary"]), ptr(out["score"])
+        for k in products:
+            setattr(ro.best_products, PRODUCT_FIELDS[k], ptr(out[k]))
+        rp = self._rank_params(rank)
+        self._check(self._lib.fpe_plan_rank(self._h, ptr(self.params), C.byref(rp) if rp is not None else None, ptr(poses), B,
+                                            int(n_cycles), K, C.byref(ro)))
+        out["best"], out["n_class0"] = best, int(n0[0])
+        return out
+
+    def plan_rank_device(self, d_poses_ptr, B, n_cycles, K, d_best_ptr, rank=None, d_summary_ptr=0, d_score_ptr=0, d_n_class0_ptr=0,
+                         best_products=None, full=None, stream=0):
+        """Device form: DEVICE pointers (0 / missing = not wanted), asynchronous on `stream`.  best_products / full: dicts
+        {product name: device pointer} of the K-slot compacted products and of the un-compacted products of all B poses."""
+        ro = RankOut(d_summary_ptr or None, d_score_ptr or None, d_best_ptr or None, d_n_class0_ptr or None)
+        for k, p in (best_products or {}).items():
+            setattr(ro.best_products, PRODUCT_FIELDS[k], p or None)
+        fo = None
+        if full is not None:
+            fo = PlanOut()
+            for k, p in full.items():
+                setattr(fo, PRODUCT_FIELDS[k], p or None)
+        rp = self._rank_params(rank)
+        self._check(self._lib.fpe_plan_rank_device(self._h, ptr(self.params), C.byref(rp) if rp is not None else None,
+                                                   C.c_void_p(d_poses_ptr), int(B), int(n_cycles), int(K),
+                                                   C.byref(fo) if fo is not None else None, C.byref(ro), C.c_void_p(stream or 0)))
 
     # ---- the opt track of a batch (cpp:913-1319, 1485-1568; build-defined optimiser) ---------------------------
     def plan_opt(self, poses, n_cycles, cycle_ok=None):
