@@ -26,13 +26,6 @@
 // larger radii are FPE_E_UNSUPPORTED (centroid_legs_kernel has no such bound).
 #pragma once
 
-// Host-derived constants of a dense centroid call (centroid_map_consts)
-struct CmapConsts {
-    float Rf;         // the search radius: the rectangle is {2 Rf, Rf} (cpp:1616-1617)
-    int32_t H;        // reach of the rectangle from its cell, rows or columns: ceil(Rf / res) + 2
-    int32_t rb, re;   // map rows [rb, re) of the planes: the region's rows +- H, clipped to the map
-    int32_t nwr;      // words per plane column: ceil((re - rb) / 32)
-};
 constexpr int kCmapMaxReach = 100;  // |landing - cell| <= H <= 100 fits the int8 offsets
 
 namespace {

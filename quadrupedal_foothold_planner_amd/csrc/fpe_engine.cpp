@@ -22,81 +22,7 @@
 #include <vector>
 
 #include "fpe_host.hpp"
-
-namespace fpe {
-// fpe_kernels.hip
-hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream);
-hipError_t launch_search_legs(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_leg_query* d_q,
-                              int n, fpe_foothold* d_out, hipStream_t stream);
-hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int cols, int si, int sj, int srcRowMajor, hipStream_t stream,
-                               uint32_t* d_planeWords = nullptr, float thrDefault = 0.0f, float thrCandidate = 0.0f);
-hipError_t set_max_lds(size_t planBytes, size_t searchBytes);
-size_t plan_lds_bytes(const PlanConsts& pc);
-size_t search_lds_bytes(const PlanConsts& pc);
-// bit-window path (fpe_bits.hip part of fpe_kernels.hip)
-size_t bitmap_words(int rows, int cols, int* strideW, int* nw);
-hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float thrDefault, float thrCandidate,
-                               uint32_t* d_words, hipStream_t stream);
-bool bits_supported(const PlanConsts& pc, const MapGeom& g);
-void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n);
-// producer filters (fpe_filters.hpp part of fpe_kernels.hip)
-bool filters_supported(const FilterConsts& fc, const MapGeom& g);
-bool filters_trav_only_ok(const FilterConsts& fc, const MapGeom& g);
-hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, bool travOnly, hipStream_t stream);
-hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut,
-                            const fpe_pose* d_poses, int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream);
-// opt track (fpe_opt.hpp part of fpe_kernels.hip)
-hipError_t launch_opt_track(const DevMap& m, const PlanConsts& pc, const OptConsts& oc, const fpe_pose* d_poses, int B, int nCycles,
-                            const uint8_t* d_cycleOk, const fpe_opt_out& d_out, hipStream_t stream, uint32_t* doneFlag = nullptr, uint32_t doneValue = 0);
-// dense foothold map (fpe_footmap.hpp part of fpe_kernels.hip)
-struct FootmapRoi {
-    int row0, col0, nr, nc;
-};
-int foothold_map_supported(const PlanConsts& pc, const MapGeom& g);
-hipError_t launch_foothold_map(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const FootmapRoi& roi, uint8_t* d_flags,
-                               float* d_height, hipStream_t stream);
-// dense snap map (fpe_footsnap.hpp part of fpe_kernels.hip)
-struct SnapConsts {
-    int32_t nRings, nCand;
-    int32_t ringT;
-    int32_t rectA, rectB;
-    float Rf;
-    int32_t polyKind;
-};
-bool foothold_snap_bits_ok(const PlanConsts& pc, const SnapConsts& sc, bool haveBits, bool rectProved);
-hipError_t launch_foothold_snap_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SnapConsts& sc, const SpiralLut& lut,
-                                     const FootmapRoi& roi, int8_t* d_offset, uint8_t* d_source, float* d_z, hipStream_t stream);
-size_t foothold_snap_literal_scratch_bytes();
-hipError_t launch_foothold_snap_literal(const DevMap& m, const PlanConsts& pc, const SnapConsts& sc, const SpiralLut& lut,
-                                        const FootmapRoi& roi, void* scratch, int8_t* d_offset, uint8_t* d_source, float* d_z,
-                                        hipStream_t stream);
-// open-loop centroid method (fpe_kernels.hip) and the dense centroid map (fpe_centroidmap.hpp part of it)
-hipError_t launch_centroid_legs(const DevMap& m, const PlanConsts& pc, float defaultR, const fpe_centroid_query* d_q, int n,
-                                fpe_centroid_foothold* d_out, hipStream_t stream);
-struct CmapConsts {
-    float Rf;
-    int32_t H;
-    int32_t rb, re;
-    int32_t nwr;
-};
-bool centroid_map_consts(const MapGeom& g, const FootmapRoi& roi, float R, CmapConsts& cc);
-size_t centroid_map_scratch_bytes(const FootmapRoi& roi, const CmapConsts& cc);
-hipError_t launch_centroid_map(const DevMap& m, const PlanConsts& pc, const CmapConsts& cc, const FootmapRoi& roi, void* scratch,
-                               uint8_t* d_code, int8_t* d_offset, float* d_z, hipStream_t stream);
-// ranking of a planned batch (fpe_rank.hpp part of fpe_kernels.hip)
-struct RankConsts {
-    double wFail, wSpiral, wNone, wDeviation, wSpeedSpread;
-    double stepHalf;
-    int32_t minCycles;
-    int32_t rfFirst;
-};
-size_t rank_scratch_bytes(int B, int K);
-hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
-                       fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
-                       const fpe_plan_out& bestProducts, hipStream_t stream);
-hipError_t set_max_lds_rank();
-}  // namespace fpe
+#include "fpe_launch.hpp"
 
 namespace {
 
@@ -754,7 +680,7 @@ void mark_async_launch(const CallPlan& cp) {
 }
 
 // What a host-buffer call holds while it runs.  The member order is the point: the lease goes first, so on an early exit it waits
-// for the stream BEFORE the snapshot / bit planes are released (plan_host declares its CallPlan before its CtxLease for this).
+// for the stream BEFORE the snapshot / bit planes are released (every host-buffer entry point, plan_host included, holds both here).
 struct HostCall {
     CallPlan cp;
     CtxLease lease;
@@ -816,6 +742,157 @@ int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, c
     FPE_HIP(hipStreamSynchronize(cx.stream));
     cx.inFlight = false;
     std::memcpy(out, cx.pinned + szQ, nO);
+    return FPE_OK;
+}
+
+// The products of a plan call, described ONCE: the eight of fpe_plan_out, then the four of fpe_opt_out, in field order — which
+// is also the order of the arenas that FootholdPlanner.plan_outputs(pinned=True) relies on (its one pinned block then leaves in one
+// transfer, copy_out).  plan_host's sizes, offsets, device-side structs and copy segments and the ranking's layout all follow
+// this table: a new product is a line here beside its field in include/fpe.h.
+enum ProductScale { kPerLeg, kPerCycle, kPerPose };  // elements: pose x cycle x leg, pose x cycle, pose
+struct Product {
+    size_t elemBytes;
+    ProductScale scale;
+};
+constexpr int kPlanProducts = 8, kOptProducts = 4, kProducts = kPlanProducts + kOptProducts;
+constexpr Product kProductTable[kProducts] = {
+    {sizeof(fpe_foothold), kPerLeg},            // fpe_plan_out: nominal
+    {sizeof(fpe_centroid_foothold), kPerLeg},   //   centroid
+    {3 * sizeof(double), kPerLeg},              //   default_next
+    {1, kPerCycle},                             //   cycle_ok
+    {12 * sizeof(double), kPerPose},            //   stance
+    {sizeof(fpe_selected_foothold), kPerLeg},   //   selected
+    {1, kPerPose},                              //   pose_status
+    {sizeof(fpe_selected_packed), kPerLeg},     //   selected_packed
+    {sizeof(fpe_opt_foothold), kPerLeg},        // fpe_opt_out: footholds
+    {sizeof(fpe_opt_cycle), kPerCycle},         //   cycles
+    {1, kPerPose},                              //   gate_fail_cycle
+    {2 * sizeof(double), kPerPose},             //   rows_after
+};
+constexpr int kCycleOk = 3;  // the one product the engine itself reads (the opt track's input, the speculative call's check)
+constexpr size_t product_bytes(int k, size_t B, size_t nCycles) {
+    return kProductTable[k].elemBytes * B *
+           (kProductTable[k].scale == kPerPose ? 1 : (kProductTable[k].scale == kPerCycle ? nCycles : nCycles * 4));
+}
+// The one place that views the two structs as arrays of pointers: slot k of fpe_plan_out = product k of the table, slot k of
+// fpe_opt_out = product kPlanProducts + k.
+static_assert(sizeof(fpe_plan_out) == kPlanProducts * sizeof(void*), "fpe_plan_out: one pointer per product of the table");
+static_assert(sizeof(fpe_opt_out) == kOptProducts * sizeof(void*), "fpe_opt_out: one pointer per product of the table");
+static_assert(offsetof(fpe_plan_out, cycle_ok) == kCycleOk * sizeof(void*), "kCycleOk names fpe_plan_out::cycle_ok");
+inline void** slots(fpe_plan_out& o) { return reinterpret_cast<void**>(&o); }
+inline void* const* slots(const fpe_plan_out& o) { return reinterpret_cast<void* const*>(&o); }
+inline void** slots(fpe_opt_out& o) { return reinterpret_cast<void**>(&o); }
+inline void* const* slots(const fpe_opt_out& o) { return reinterpret_cast<void* const*>(&o); }
+
+// selected_packed holds biased 14-bit grid indices: wherever the product is asked for, a larger map is refused.
+int check_packed_fits(const CallPlan& cp, bool wanted) {
+    if (wanted && (cp.snap->g.rows > FPE_PACKED_MAX_CELLS || cp.snap->g.cols > FPE_PACKED_MAX_CELLS))
+        return fail(FPE_E_UNSUPPORTED, "selected_packed holds biased 14-bit grid indices: the map has more than 15871 rows or columns");
+    return FPE_OK;
+}
+
+// One result of a host-form plan / ranking call: `len` bytes at offset `off` of the call's arenas (device and pinned: the same
+// offsets in both), wanted at `dst`.  A list holds them in arena order.
+struct Seg {
+    size_t off, len;
+    void* dst;
+};
+struct SegList {
+    Seg s[kProducts];  // (a ranking call: its eight products and four outputs of its own)
+    int n = 0;
+    void add(size_t off, size_t len, void* dst) {
+        if (dst && len) s[n++] = Seg{off, len, dst};
+    }
+};
+// Every result is in the pinned arena (the kernels of a zero-copy call wrote it there themselves): out to the caller.
+void copy_from_pinned(const SegList& segs, const unsigned char* pinned) {
+    for (int k = 0; k < segs.n; ++k) std::memcpy(segs.s[k].dst, pinned + segs.s[k].off, segs.s[k].len);
+}
+
+// The results of a host-form call from the device arena `dev` to the caller, behind the kernels queued on cx.stream; `pinned`: the
+// pinned arena (the staging area).  Ends synchronised.  The list comes by value: a segment that has left directly loses its `dst`.
+// Only what the caller asked for crosses PCIe.  A product whose destination is pinned / registered host memory
+// (fpe_host_alloc) is written by DMA directly; the others go through the pinned arena in chunks, and the copy of a
+// chunk into the caller's array runs on the copy pool while the next chunks are still in flight.
+// Pinned destinations that lie behind one another exactly as the products do in the device arena (no padding in between:
+// FootholdPlanner.plan_outputs(pinned=True) carves them out of ONE fpe_host_alloc block in this order) leave in ONE copy:
+// a DMA transfer has a fixed cost of some ten microseconds, and seven of them in a row are a third of a 4 096-pose call.
+int copy_out(fpe_engine* h, CallCtx& cx, SegList list, const unsigned char* dev, unsigned char* pinned) {
+    Seg* const segs = list.s;
+    const int nSeg = list.n;
+    size_t staged = 0;
+    bool pinnedSeg[kProducts];
+    for (int k = 0; k < nSeg; ++k) pinnedSeg[k] = is_pinned_host(segs[k].dst);
+    for (int k = 0; k < nSeg; ++k) {
+        if (!pinnedSeg[k]) {
+            staged += segs[k].len;
+            continue;
+        }
+        size_t len = segs[k].len;
+        int last = k;
+        while (last + 1 < nSeg && pinnedSeg[last + 1] && segs[last + 1].off == segs[last].off + segs[last].len &&
+               static_cast<unsigned char*>(segs[last + 1].dst) == static_cast<unsigned char*>(segs[last].dst) + segs[last].len) {
+            ++last;
+            len += segs[last].len;
+        }
+        FPE_HIP(hipMemcpyAsync(segs[k].dst, dev + segs[k].off, len, hipMemcpyDeviceToHost, cx.stream));
+        for (int q = k; q <= last; ++q) segs[q].dst = nullptr;
+        k = last;
+    }
+    // A DMA transfer has a fixed cost of some ten microseconds: few, large pieces (a quarter of what is staged, at least
+    // 1 MB), and the copy of a piece into the caller's array split over the pool's threads so that the last piece's copy — the
+    // only one that is not hidden behind a later transfer — is short.
+    constexpr size_t kTargetChunks = 4;
+    const size_t chunk = std::max<size_t>(1u << 20, (staged / kTargetChunks + 4095) & ~static_cast<size_t>(4095));
+    // DMA pieces are cut from RUNS of staged products that are neighbours in the arena (alignment padding rides along: both
+    // arenas are the engine's own), not from single products: four transfers for seven products, not nine.
+    struct Piece {
+        size_t off, len;
+    };
+    std::vector<Piece> pieces;
+    for (int k = 0; k < nSeg; ++k) {
+        if (!segs[k].dst) continue;
+        int last = k;
+        while (last + 1 < nSeg && segs[last + 1].dst && segs[last + 1].off == align256(segs[last].off + segs[last].len)) ++last;
+        const size_t end = segs[last].off + segs[last].len;
+        for (size_t c = segs[k].off; c < end; c += chunk) pieces.push_back(Piece{c, std::min(chunk, end - c)});
+        k = last;
+    }
+    for (size_t k = 0; k < pieces.size(); ++k) {
+        hipEvent_t ev;
+        FPE_HIP(cx.event(k, &ev));
+        FPE_HIP(hipMemcpyAsync(pinned + pieces[k].off, dev + pieces[k].off, pieces[k].len, hipMemcpyDeviceToHost, cx.stream));
+        FPE_HIP(hipEventRecord(ev, cx.stream));
+    }
+    CopyPool::Batch batch;
+    hipError_t evErr = hipSuccess;
+    for (size_t k = 0; k < pieces.size(); ++k) {
+        const hipError_t e = hipEventSynchronize(cx.events[k]);
+        if (e != hipSuccess) {
+            evErr = e;
+            break;
+        }
+        // what the piece holds of each staged product, into the caller's array
+        const size_t p0 = pieces[k].off, p1 = p0 + pieces[k].len;
+        for (int q = 0; q < nSeg; ++q) {
+            if (!segs[q].dst) continue;
+            const size_t a0 = std::max(p0, segs[q].off), a1 = std::min(p1, segs[q].off + segs[q].len);
+            if (a0 >= a1) continue;
+            unsigned char* dst = static_cast<unsigned char*>(segs[q].dst) + (a0 - segs[q].off);
+            const size_t len = a1 - a0;
+            if (len >= (256u << 10)) {
+                const size_t parts = std::min<size_t>(h->copyPool.width(), (len + (256u << 10) - 1) / (256u << 10));
+                const size_t step = ((len + parts - 1) / parts + 63) & ~static_cast<size_t>(63);
+                for (size_t c = 0; c < len; c += step) h->copyPool.submit(batch, dst + c, pinned + a0 + c, std::min(step, len - c));
+            } else {
+                std::memcpy(dst, pinned + a0, len);
+            }
+        }
+    }
+    CopyPool::wait(batch);
+    if (evErr != hipSuccess) return fail_hip(evErr, "result copy");  // (the lease waits for the stream)
+    FPE_HIP(hipStreamSynchronize(cx.stream));  // the direct (pinned-destination) copies
+    cx.inFlight = false;
     return FPE_OK;
 }
 
@@ -1279,8 +1356,8 @@ int fpe_map_info(fpe_handle h, fpe_map_desc* out) {
 // One chained-plan launch on `stream`: the bit-window kernels when the snapshot's bit planes apply, else the direct ones.
 static int launch_plan(fpe_engine* h, const CallPlan& cp, const fpe_pose* d_poses, int32_t B, int32_t n_cycles,
                        const fpe_plan_out& d_out, hipStream_t stream) {
-    if (d_out.selected_packed && (cp.snap->g.rows > FPE_PACKED_MAX_CELLS || cp.snap->g.cols > FPE_PACKED_MAX_CELLS))
-        return fail(FPE_E_UNSUPPORTED, "selected_packed holds biased 14-bit grid indices: the map has more than 15871 rows or columns");
+    const int rc = check_packed_fits(cp, d_out.selected_packed != nullptr);
+    if (rc != FPE_OK) return rc;
     if (cp.useBits)
         FPE_HIP(fpe::launch_plan_bits(dev_map(*cp.snap), cp.bits, cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream));
     else
@@ -1316,9 +1393,6 @@ int prepare_opt(const fpe_params* params, const fpe_opt_params* opt, const CallP
     return FPE_OK;
 }
 
-// The host-buffer form of the plan and / or the opt track: one device arena, the launches back to back on one
-// stream, the results copied out.  `out` NULL: no plan products are returned (the plan still runs when the opt track
-// needs its cycle flags and the caller gave none).
 // The poses of a host-buffer call, checked; maxRadius: the largest per-leg search radius among them.
 int check_host_poses(const fpe_pose* poses, int32_t B, float& maxRadius) {
     maxRadius = 0.0f;
@@ -1340,6 +1414,170 @@ struct GateGeom {  // what the service call's host-side (lateral) gate needs fro
     fpe::MapGeom g;
     double isosLen, isosWid, drift;
 };
+
+// Where a host-form plan call keeps everything in its two arenas, one device and one pinned, at the same offsets, from the product
+// table: [poses | nominal | centroid | default | cycle_ok | stance | selected | status | packed | opt footholds | opt cycles | gate
+// | rows | speculative flags | completion word], in 256-byte steps; a product that is not part of the call takes no room.
+struct PlanLayout {
+    size_t off[kProducts], len[kProducts];  // len 0: not in the arenas
+    size_t oSpec, oDone, total;
+};
+PlanLayout plan_layout(int32_t B, int32_t nCycles, const bool (&inArena)[kProducts], bool specWanted) {
+    PlanLayout L;
+    size_t off = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    for (int k = 0; k < kProducts; ++k) {
+        L.off[k] = off;
+        L.len[k] = inArena[k] ? product_bytes(k, static_cast<size_t>(B), static_cast<size_t>(nCycles)) : 0;
+        off += align256(L.len[k]);
+    }
+    // the flags of 1 the speculative chain runs on, and the chain's completion word (one-pose calls: polled by the host): plan_launches
+    L.oSpec = off;
+    off += specWanted ? align256(static_cast<size_t>(B) * nCycles) : 0;
+    L.oDone = off;
+    off += specWanted ? 256 : 0;
+    L.total = off;
+    return L;
+}
+
+// One host-form plan call between plan_host and its parts.
+struct PlanRun {
+    // set by plan_host, read by plan_launches and plan_wait_zero_copy
+    int32_t B = 0, nCycles = 0;
+    bool runPlan = false, runOpt = false, specWanted = false;
+    // set by plan_launches: what it decided, for the wait and the copy-out
+    bool zeroCopy = false, speculate = false, pollDone = false;
+    uint32_t doneValue = 0;
+    unsigned char* dp = nullptr;       // the arena the kernels write, as the device sees it: cx.dev, or the pinned arena itself (zeroCopy)
+    const fpe_pose* dPoses = nullptr;  // where the kernels read the poses
+    fpe_opt_out od;                    // the opt products in that arena
+};
+
+// The launches of a host-form plan call: the plan kernel and / or the opt track's chain on cx.stream — or, speculatively, the chain
+// beside the plan kernel on the side stream.
+int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayout& L, const fpe::OptConsts& oc, const fpe_pose* poses,
+                  const uint8_t* cycleOkIn, PlanRun& r) {
+    unsigned char* const hp = cx.pinned;
+    const int32_t B = r.B, n_cycles = r.nCycles;
+    const size_t nCyc = static_cast<size_t>(B) * n_cycles;
+    const size_t oOk = L.off[kCycleOk];
+    std::memcpy(hp, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
+    if (r.runOpt && cycleOkIn) std::memcpy(hp + oOk, cycleOkIn, nCyc);
+    // Small calls (the plan_global_footholds service: one pose) skip both DMA copies: the kernels read the
+    // poses from, and write their few KB of results straight into, the pinned (coherent, device-mapped) host
+    // arena — two copy-engine round trips (~10 us each) less on a call whose kernel runs ~25 us.
+    r.zeroCopy = L.total <= kZeroCopyBytes;
+    // A small call that runs the plan AND the opt track (the service: one pose) launches the two kernels side by side: the opt
+    // track's chain needs the nominal track's cycle flags only to decide whether a cycle's result is committed, and the flags are
+    // all 1 unless a nominal search fails — the chain runs on a second stream on flags of 1 (L.oSpec) while the plan kernel produces
+    // the real ones, and runs again, after it, in the rare call whose flags turn out otherwise (round 5: the plan kernel's ~18 us
+    // off the service's latency).
+    // One-pose overlapped calls (the service): the chain's last instruction writes a completion word into the pinned arena and the
+    // host POLLS it (tuning key service_poll, default 1) instead of waiting for the side stream's completion signal.
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        r.speculate = r.specWanted && r.zeroCopy && r.runOpt && h->tuning.serviceOverlap;
+        r.pollDone = r.speculate && B == 1 && h->tuning.servicePoll != 0;
+    }
+    // the poses are read by the kernels straight from the pinned arena (device-mapped): 64 bytes per pose, once, at the start
+    // of its workgroup — a DMA transfer ahead of the launch costs its fixed fifteen microseconds before anything runs
+    void* mapped = nullptr;
+    FPE_HIP(hipHostGetDevicePointer(&mapped, hp, 0));
+    r.dPoses = static_cast<const fpe_pose*>(mapped);
+    r.dp = r.zeroCopy ? static_cast<unsigned char*>(mapped) : cx.dev;
+    unsigned char* const dp = r.dp;
+    if (!r.zeroCopy && r.runOpt && cycleOkIn) FPE_HIP(hipMemcpyAsync(dp + oOk, hp + oOk, nCyc, hipMemcpyHostToDevice, cx.stream));
+    std::memset(&r.od, 0, sizeof(r.od));
+    const auto queue_opt = [&]() -> int {
+        if (!r.runOpt) return FPE_OK;
+        for (int k = 0; k < kOptProducts; ++k) slots(r.od)[k] = L.len[kPlanProducts + k] ? dp + L.off[kPlanProducts + k] : nullptr;
+        hipStream_t os = cx.stream;
+        const unsigned char* okDev = dp + oOk;
+        uint32_t* doneDev = nullptr;
+        if (r.speculate && r.pollDone) {
+            r.doneValue = ++cx.doneSeq ? cx.doneSeq : ++cx.doneSeq;  // (never 0, never the value the word holds from the last call)
+            doneDev = reinterpret_cast<uint32_t*>(dp + L.oDone);
+        }
+        if (r.speculate) {
+            std::memset(hp + L.oSpec, 1, nCyc);
+            FPE_HIP(cx.side_stream(&os));
+            // the chain reads both layers: the side stream waits for an asynchronous upload (fpe_upload_map_device) exactly as
+            // prepare_call made cx.stream wait (ADVICE r5: the speculative chain used to start while the canonicalise / copy
+            // kernels of the snapshot were still writing d_trav / d_elev)
+            FPE_HIP(cp.snap->wait_ready(os));
+            okDev = dp + L.oSpec;
+        }
+        FPE_HIP(fpe::launch_opt_track(dev_map(*cp.snap), cp.pc, oc, r.dPoses, B, n_cycles, okDev, r.od, os, doneDev, r.doneValue));
+        return FPE_OK;
+    };
+    // (the overlapped form queues the LONGER kernel first — the chain is the call's critical path; the plan kernel's launch then costs
+    // it nothing)
+    if (r.speculate) {
+        const int rc = queue_opt();
+        if (rc != FPE_OK) return rc;
+        // A polled call never enters a stream wait, and it is a stream wait (or query) that makes the runtime hand queued work to
+        // the hardware at once: without it the chain was seen to END 12 us later than under hipStreamSynchronize (measured, round 6:
+        // profiles/round6_service_latency.txt).  One non-blocking query per stream, right behind its launch.
+        if (r.pollDone && hipStreamQuery(cx.side) != hipSuccess) (void)hipGetLastError();
+    }
+    if (r.runPlan) {
+        fpe_plan_out d;
+        for (int k = 0; k < kPlanProducts; ++k) slots(d)[k] = L.len[k] ? dp + L.off[k] : nullptr;
+        // every (pose, cycle, leg) record is written by the kernel (trot: all legs each cycle; walk: each
+        // leg in its phase), so the buffers need no clearing
+        const int rc = launch_plan(h, cp, r.dPoses, B, n_cycles, d, cx.stream);
+        if (rc != FPE_OK) return rc;
+    }
+    if (!r.speculate) {
+        const int rc = queue_opt();
+        if (rc != FPE_OK) return rc;
+    }
+    if (r.pollDone && hipStreamQuery(cx.stream) != hipSuccess) (void)hipGetLastError();  // (see the side stream's query above)
+    return FPE_OK;
+}
+
+// The wait of a zero-copy call (the kernels wrote into the pinned arena itself): polled or synchronised, and the speculative
+// chain again where the real flags differ from the ones it ran on.
+int plan_wait_zero_copy(const CallPlan& cp, CallCtx& cx, const PlanLayout& L, const fpe::OptConsts& oc, const PlanRun& r) {
+    unsigned char* const hp = cx.pinned;
+    bool polled = false;
+    if (r.pollDone && r.doneValue != 0) {
+        // The chain is the call's critical path (~90 us against the plan kernel's ~20): wait for ITS word first.  Bounded: after
+        // 5 ms the ordinary synchronisation below takes over (a word that never arrives must not hang the caller).
+        volatile uint32_t* word = reinterpret_cast<volatile uint32_t*>(hp + L.oDone);
+        const auto t0 = std::chrono::steady_clock::now();
+        int spins = 0;
+        while (*word != r.doneValue) {
+            __builtin_ia32_pause();
+            if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+        }
+        polled = *word == r.doneValue;
+        std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    // (the plan kernel ended long before the chain; when the runtime has not yet seen that, wait for it the ordinary way)
+    if (!(polled && hipStreamQuery(cx.stream) == hipSuccess)) {
+        (void)hipGetLastError();
+        FPE_HIP(hipStreamSynchronize(cx.stream));
+    }
+    if (r.runOpt && r.speculate) {
+        // polled: every product of the chain is in the arena (its stores precede the word); the stream's own completion is
+        // looked at without waiting — the context's next call queues behind it in stream order
+        if (!polled) FPE_HIP(hipStreamSynchronize(cx.side));
+        else if (hipStreamQuery(cx.side) != hipSuccess) (void)hipGetLastError();
+        const size_t nCyc = static_cast<size_t>(r.B) * r.nCycles, oOk = L.off[kCycleOk];
+        bool allCommitted = true;
+        for (size_t c = 0; c < nCyc; ++c) allCommitted = allCommitted && hp[oOk + c] != 0;
+        if (!allCommitted) {  // a nominal search failed in some cycle: the chain again, on the flags as they are
+            FPE_HIP(fpe::launch_opt_track(dev_map(*cp.snap), cp.pc, oc, r.dPoses, r.B, r.nCycles, r.dp + oOk, r.od, cx.stream));
+            FPE_HIP(hipStreamSynchronize(cx.stream));
+        }
+    }
+    cx.inFlight = false;
+    return FPE_OK;
+}
+
+// The host-buffer form of the plan and / or the opt track: one device arena (plan_layout), the launches back to back on one
+// stream or side by side on two (plan_launches), the results copied out (copy_out).  `out` NULL: no plan products are returned (the
+// plan still runs when the opt track needs its cycle flags and the caller gave none).
 int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B, int32_t n_cycles,
               const fpe_plan_out* out, const uint8_t* cycleOkIn, const fpe_opt_out* oout, GateGeom* gateGeom = nullptr,
               bool* optDropped = nullptr) {
@@ -1348,304 +1586,51 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
     float maxRadius = 0.0f;
     int rcPoses = check_host_poses(poses, B, maxRadius);
     if (rcPoses != FPE_OK) return rcPoses;
-    fpe_plan_out none;
-    std::memset(&none, 0, sizeof(none));
-    const fpe_plan_out& po = out ? *out : none;
-    const bool runPlan = out != nullptr || (oout && !cycleOkIn);
-    const bool needOkDev = po.cycle_ok != nullptr || oout != nullptr;  // device copy of the cycle flags
-    // one device arena + one pinned arena:
-    // [poses | nominal | centroid | default | cycle_ok | stance | selected | status | packed | opt footholds | opt cycles | gate]
-    const size_t nRec = static_cast<size_t>(B) * n_cycles * 4;
-    const size_t nCyc = static_cast<size_t>(B) * n_cycles;
-    const size_t szPose = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
-    const size_t szNom = po.nominal ? align256(nRec * sizeof(fpe_foothold)) : 0;
-    const size_t szCen = po.centroid ? align256(nRec * sizeof(fpe_centroid_foothold)) : 0;
-    const size_t szDef = po.default_next ? align256(nRec * 3 * sizeof(double)) : 0;
-    const size_t szOk = needOkDev ? align256(nCyc) : 0;
-    const size_t szSt = po.stance ? align256(static_cast<size_t>(B) * 12 * sizeof(double)) : 0;
-    const size_t szSel = po.selected ? align256(nRec * sizeof(fpe_selected_foothold)) : 0;
-    const size_t szPs = po.pose_status ? align256(static_cast<size_t>(B)) : 0;
-    const size_t szPk = po.selected_packed ? align256(nRec * sizeof(fpe_selected_packed)) : 0;
-    const size_t szOf = (oout && oout->footholds) ? align256(nRec * sizeof(fpe_opt_foothold)) : 0;
-    const size_t szOc = (oout && oout->cycles) ? align256(nCyc * sizeof(fpe_opt_cycle)) : 0;
-    const size_t szOg = (oout && oout->gate_fail_cycle) ? align256(static_cast<size_t>(B)) : 0;
-    const size_t szOr = (oout && oout->rows_after) ? align256(static_cast<size_t>(B) * 2 * sizeof(double)) : 0;
-    // A small call that runs the plan AND the opt track (the service: one pose) launches the two kernels side by side: the opt
-    // track's chain needs the nominal track's cycle flags only to decide whether a cycle's result is committed, and the flags are
-    // all 1 unless a nominal search fails — the chain runs on a second stream on flags of 1 (szSpec) while the plan kernel produces
-    // the real ones, and runs again, after it, in the rare call whose flags turn out otherwise (round 5: the plan kernel's ~18 us
-    // off the service's latency).
-    const bool specWanted = runPlan && oout != nullptr && !cycleOkIn && B <= 4;
-    const size_t szSpec = specWanted ? align256(nCyc) : 0;
-    const size_t szDone = specWanted ? 256 : 0;  // the chain's completion word (one-pose calls: polled by the host, below)
-    const size_t total = szPose + szNom + szCen + szDef + szOk + szSt + szSel + szPs + szPk + szOf + szOc + szOg + szOr + szSpec + szDone;
+    void* want[kProducts] = {nullptr};  // the caller's arrays, by product
+    if (out) std::copy(slots(*out), slots(*out) + kPlanProducts, want);
+    if (oout) std::copy(slots(*oout), slots(*oout) + kOptProducts, want + kPlanProducts);
+    bool inArena[kProducts];
+    for (int k = 0; k < kProducts; ++k) inArena[k] = want[k] != nullptr;
+    inArena[kCycleOk] = inArena[kCycleOk] || oout != nullptr;  // the opt track reads the device copy of the cycle flags
+    PlanRun run;
+    run.B = B;
+    run.nCycles = n_cycles;
+    run.runPlan = out != nullptr || (oout && !cycleOkIn);
+    run.specWanted = run.runPlan && oout != nullptr && !cycleOkIn && B <= 4;
+    const PlanLayout L = plan_layout(B, n_cycles, inArena, run.specWanted);
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
-    CallPlan cp;  // declared before the lease: on an early exit the lease waits for the stream BEFORE the snapshot / bit planes are released
-    CtxLease lease(h->ctxPool);
-    CallCtx& cx = *lease.ctx;
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
     FPE_HIP(hipSetDevice(h->device));
-    FPE_HIP(cx.reserve(total));
+    FPE_HIP(cx.reserve(L.total));
     cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
-    int rc = prepare_call(h, params, maxRadius, cp, cx.stream, runPlan);
+    int rc = prepare_call(h, params, maxRadius, cp, cx.stream, run.runPlan);
     if (rc != FPE_OK) return rc;
     if (gateGeom) *gateGeom = GateGeom{cp.snap->g, cp.pc.isosLen, cp.pc.isosWid, cp.pc.drift};
     fpe::OptConsts oc;
+    run.runOpt = oout != nullptr;
     if (oout) {
         rc = prepare_opt(params, opt, cp, maxRadius, oc);
         // optOptional: the opt track was asked for its gate verdict only (fpe_plan_service* under service_opt_gate 1 / 2) and
         // is not supported for this geometry: the plan's own products must not fail with it
-        if (rc == FPE_E_UNSUPPORTED && optDropped && runPlan) {
+        if (rc == FPE_E_UNSUPPORTED && optDropped && run.runPlan) {
             *optDropped = true;
-            oout = nullptr;
+            run.runOpt = false;
+            std::fill(want + kPlanProducts, want + kProducts, nullptr);
         } else if (rc != FPE_OK) {
             return rc;
         }
     }
-    unsigned char* dp = cx.dev;
-    unsigned char* hp = cx.pinned;
-    size_t off = szPose;
-    const size_t oNom = off; off += szNom;
-    const size_t oCen = off; off += szCen;
-    const size_t oDef = off; off += szDef;
-    const size_t oOk = off; off += szOk;
-    const size_t oSt = off; off += szSt;
-    const size_t oSel = off; off += szSel;
-    const size_t oPs = off; off += szPs;
-    const size_t oPk = off; off += szPk;
-    const size_t oOf = off; off += szOf;
-    const size_t oOc = off; off += szOc;
-    const size_t oOg = off; off += szOg;
-    const size_t oOr = off; off += szOr;
-    const size_t oSpec = off; off += szSpec;
-    const size_t oDone = off;
-    std::memcpy(hp, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
-    if (oout && cycleOkIn) std::memcpy(hp + oOk, cycleOkIn, nCyc);
-    // Small calls (the plan_global_footholds service: one pose) skip both DMA copies: the kernels read the
-    // poses from, and write their few KB of results straight into, the pinned (coherent, device-mapped) host
-    // arena — two copy-engine round trips (~10 us each) less on a call whose kernel runs ~25 us.
-    const bool zeroCopy = total <= kZeroCopyBytes;
-    bool speculate = specWanted && zeroCopy && oout != nullptr;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->tuning.serviceOverlap) speculate = false;
-    }
-    const fpe_pose* dPoses = nullptr;  // where the kernels read the poses (null: the head of the device arena)
-    if (zeroCopy) {
-        void* arena = nullptr;
-        FPE_HIP(hipHostGetDevicePointer(&arena, hp, 0));
-        dp = static_cast<unsigned char*>(arena);
-    } else {
-        // the poses are read by the kernels straight from the pinned arena (device-mapped): 64 bytes per pose, once, at the start
-        // of its workgroup — a DMA transfer ahead of the launch costs its fixed fifteen microseconds before anything runs
-        void* mapped = nullptr;
-        FPE_HIP(hipHostGetDevicePointer(&mapped, hp, 0));
-        dPoses = static_cast<const fpe_pose*>(mapped);
-        if (oout && cycleOkIn) FPE_HIP(hipMemcpyAsync(dp + oOk, hp + oOk, nCyc, hipMemcpyHostToDevice, cx.stream));
-    }
-    fpe_opt_out od;
-    std::memset(&od, 0, sizeof(od));
-    // One-pose overlapped calls (the service): the chain's last instruction writes a completion word into the pinned arena and the
-    // host POLLS it (tuning key service_poll, default 1) instead of waiting for the side stream's completion signal.
-    bool pollDone = false;
-    uint32_t doneValue = 0;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        pollDone = speculate && B == 1 && h->tuning.servicePoll != 0;
-    }
-    const auto queue_opt = [&]() -> int {
-        if (!oout) return FPE_OK;
-        if (oout->footholds) od.footholds = reinterpret_cast<fpe_opt_foothold*>(dp + oOf);
-        if (oout->cycles) od.cycles = reinterpret_cast<fpe_opt_cycle*>(dp + oOc);
-        if (oout->gate_fail_cycle) od.gate_fail_cycle = dp + oOg;
-        if (oout->rows_after) od.rows_after = reinterpret_cast<double*>(dp + oOr);
-        hipStream_t os = cx.stream;
-        const unsigned char* okDev = dp + oOk;
-        uint32_t* doneDev = nullptr;
-        if (speculate && pollDone) {
-            doneValue = ++cx.doneSeq ? cx.doneSeq : ++cx.doneSeq;  // (never 0, never the value the word holds from the last call)
-            doneDev = reinterpret_cast<uint32_t*>(dp + oDone);
-        }
-        if (speculate) {
-            std::memset(hp + oSpec, 1, nCyc);
-            FPE_HIP(cx.side_stream(&os));
-            // the chain reads both layers: the side stream waits for an asynchronous upload (fpe_upload_map_device) exactly as
-            // prepare_call made cx.stream wait (ADVICE r5: the speculative chain used to start while the canonicalise / copy
-            // kernels of the snapshot were still writing d_trav / d_elev)
-            FPE_HIP(cp.snap->wait_ready(os));
-            okDev = dp + oSpec;
-        }
-        FPE_HIP(fpe::launch_opt_track(dev_map(*cp.snap), cp.pc, oc, dPoses ? dPoses : reinterpret_cast<const fpe_pose*>(dp), B, n_cycles, okDev, od, os, doneDev, doneValue));
-        return FPE_OK;
-    };
-    // (the overlapped form queues the LONGER kernel first — the chain is the call's critical path; the plan kernel's launch then costs
-    // it nothing)
-    if (speculate) {
-        rc = queue_opt();
-        if (rc != FPE_OK) return rc;
-        // A polled call never enters a stream wait, and it is a stream wait (or query) that makes the runtime hand queued work to
-        // the hardware at once: without it the chain was seen to END 12 us later than under hipStreamSynchronize (measured, round 6:
-        // profiles/round6_service_latency.txt).  One non-blocking query per stream, right behind its launch.
-        if (pollDone && hipStreamQuery(cx.side) != hipSuccess) (void)hipGetLastError();
-    }
-    if (runPlan) {
-        fpe_plan_out d;
-        std::memset(&d, 0, sizeof(d));
-        if (po.nominal) d.nominal = reinterpret_cast<fpe_foothold*>(dp + oNom);
-        if (po.centroid) d.centroid = reinterpret_cast<fpe_centroid_foothold*>(dp + oCen);
-        if (po.default_next) d.default_next = reinterpret_cast<double*>(dp + oDef);
-        if (needOkDev) d.cycle_ok = dp + oOk;
-        if (po.stance) d.stance = reinterpret_cast<double*>(dp + oSt);
-        if (po.selected) d.selected = reinterpret_cast<fpe_selected_foothold*>(dp + oSel);
-        if (po.pose_status) d.pose_status = dp + oPs;
-        if (po.selected_packed) d.selected_packed = reinterpret_cast<fpe_selected_packed*>(dp + oPk);
-        // every (pose, cycle, leg) record is written by the kernel (trot: all legs each cycle; walk: each
-        // leg in its phase), so the buffers need no clearing
-        rc = launch_plan(h, cp, dPoses ? dPoses : reinterpret_cast<const fpe_pose*>(dp), B, n_cycles, d, cx.stream);
-        if (rc != FPE_OK) return rc;
-    }
-    if (!speculate) {
-        rc = queue_opt();
-        if (rc != FPE_OK) return rc;
-    }
-    if (pollDone && hipStreamQuery(cx.stream) != hipSuccess) (void)hipGetLastError();  // (see the side stream's query above)
+    rc = plan_launches(h, cp, cx, L, oc, poses, cycleOkIn, run);
+    if (rc != FPE_OK) return rc;
     // ---- results to the caller ----
-    struct Seg {
-        size_t off, len;
-        void* dst;
-    };
-    Seg segs[13];
-    int nSeg = 0;
-    auto add = [&](size_t o, size_t len, void* dst) {
-        if (dst && len) segs[nSeg++] = Seg{o, len, dst};
-    };
-    add(oNom, nRec * sizeof(fpe_foothold), po.nominal);
-    add(oCen, nRec * sizeof(fpe_centroid_foothold), po.centroid);
-    add(oDef, nRec * 3 * sizeof(double), po.default_next);
-    add(oOk, nCyc, po.cycle_ok);
-    add(oSt, static_cast<size_t>(B) * 12 * sizeof(double), po.stance);
-    add(oSel, nRec * sizeof(fpe_selected_foothold), po.selected);
-    add(oPs, static_cast<size_t>(B), po.pose_status);
-    add(oPk, nRec * sizeof(fpe_selected_packed), po.selected_packed);
-    if (oout && szOf) add(oOf, nRec * sizeof(fpe_opt_foothold), oout->footholds);
-    if (oout && szOc) add(oOc, nCyc * sizeof(fpe_opt_cycle), oout->cycles);
-    if (oout && szOg) add(oOg, static_cast<size_t>(B), oout->gate_fail_cycle);
-    if (oout && szOr) add(oOr, static_cast<size_t>(B) * 2 * sizeof(double), oout->rows_after);
-    if (zeroCopy) {  // the kernels wrote into the pinned arena itself
-        bool polled = false;
-        if (pollDone && doneValue != 0) {
-            // The chain is the call's critical path (~90 us against the plan kernel's ~20): wait for ITS word first.  Bounded: after
-            // 5 ms the ordinary synchronisation below takes over (a word that never arrives must not hang the caller).
-            volatile uint32_t* word = reinterpret_cast<volatile uint32_t*>(hp + oDone);
-            const auto t0 = std::chrono::steady_clock::now();
-            int spins = 0;
-            while (*word != doneValue) {
-                __builtin_ia32_pause();
-                if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
-            }
-            polled = *word == doneValue;
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        // (the plan kernel ended long before the chain; when the runtime has not yet seen that, wait for it the ordinary way)
-        if (!(polled && hipStreamQuery(cx.stream) == hipSuccess)) {
-            (void)hipGetLastError();
-            FPE_HIP(hipStreamSynchronize(cx.stream));
-        }
-        if (oout && speculate) {
-            // polled: every product of the chain is in the arena (its stores precede the word); the stream's own completion is
-            // looked at without waiting — the context's next call queues behind it in stream order
-            if (!polled) FPE_HIP(hipStreamSynchronize(cx.side));
-            else if (hipStreamQuery(cx.side) != hipSuccess) (void)hipGetLastError();
-            bool allCommitted = true;
-            for (size_t c = 0; c < nCyc; ++c) allCommitted = allCommitted && hp[oOk + c] != 0;
-            if (!allCommitted) {  // a nominal search failed in some cycle: the chain again, on the flags as they are
-                FPE_HIP(fpe::launch_opt_track(dev_map(*cp.snap), cp.pc, oc, dPoses ? dPoses : reinterpret_cast<const fpe_pose*>(dp), B, n_cycles, dp + oOk, od,
-                                              cx.stream));
-                FPE_HIP(hipStreamSynchronize(cx.stream));
-            }
-        }
-        cx.inFlight = false;
-        for (int k = 0; k < nSeg; ++k) std::memcpy(segs[k].dst, hp + segs[k].off, segs[k].len);
-        return FPE_OK;
-    }
-    // Only what the caller asked for crosses PCIe.  A product whose destination is pinned / registered host memory
-    // (fpe_host_alloc) is written by DMA directly; the others go through the pinned arena in chunks, and the copy of a
-    // chunk into the caller's array runs on the copy pool while the next chunks are still in flight.
-    // Pinned destinations that lie behind one another exactly as the products do in the device arena (no padding in between:
-    // FootholdPlanner.plan_outputs(pinned=True) carves them out of ONE fpe_host_alloc block in this order) leave in ONE copy:
-    // a DMA transfer has a fixed cost of some ten microseconds, and seven of them in a row are a third of a 4 096-pose call.
-    size_t staged = 0;
-    bool pinnedSeg[13];
-    for (int k = 0; k < nSeg; ++k) pinnedSeg[k] = is_pinned_host(segs[k].dst);
-    for (int k = 0; k < nSeg; ++k) {
-        if (!pinnedSeg[k]) {
-            staged += segs[k].len;
-            continue;
-        }
-        size_t len = segs[k].len;
-        int last = k;
-        while (last + 1 < nSeg && pinnedSeg[last + 1] && segs[last + 1].off == segs[last].off + segs[last].len &&
-               static_cast<unsigned char*>(segs[last + 1].dst) == static_cast<unsigned char*>(segs[last].dst) + segs[last].len) {
-            ++last;
-            len += segs[last].len;
-        }
-        FPE_HIP(hipMemcpyAsync(segs[k].dst, dp + segs[k].off, len, hipMemcpyDeviceToHost, cx.stream));
-        for (int q = k; q <= last; ++q) segs[q].dst = nullptr;
-        k = last;
-    }
-    // A DMA transfer has a fixed cost of some ten microseconds: few, large pieces (a quarter of what is staged, at least
-    // 1 MB), and the copy of a piece into the caller's array split over the pool's threads so that the last piece's copy — the
-    // only one that is not hidden behind a later transfer — is short.
-    constexpr size_t kTargetChunks = 4;
-    const size_t chunk = std::max<size_t>(1u << 20, (staged / kTargetChunks + 4095) & ~static_cast<size_t>(4095));
-    // DMA pieces are cut from RUNS of staged products that are neighbours in the arena (alignment padding rides along: both
-    // arenas are the engine's own), not from single products: four transfers for seven products, not nine.
-    struct Piece {
-        size_t off, len;
-    };
-    std::vector<Piece> pieces;
-    for (int k = 0; k < nSeg; ++k) {
-        if (!segs[k].dst) continue;
-        int last = k;
-        while (last + 1 < nSeg && segs[last + 1].dst && segs[last + 1].off == align256(segs[last].off + segs[last].len)) ++last;
-        const size_t end = segs[last].off + segs[last].len;
-        for (size_t c = segs[k].off; c < end; c += chunk) pieces.push_back(Piece{c, std::min(chunk, end - c)});
-        k = last;
-    }
-    for (size_t k = 0; k < pieces.size(); ++k) {
-        hipEvent_t ev;
-        FPE_HIP(cx.event(k, &ev));
-        FPE_HIP(hipMemcpyAsync(hp + pieces[k].off, dp + pieces[k].off, pieces[k].len, hipMemcpyDeviceToHost, cx.stream));
-        FPE_HIP(hipEventRecord(ev, cx.stream));
-    }
-    CopyPool::Batch batch;
-    hipError_t evErr = hipSuccess;
-    for (size_t k = 0; k < pieces.size(); ++k) {
-        const hipError_t e = hipEventSynchronize(cx.events[k]);
-        if (e != hipSuccess) {
-            evErr = e;
-            break;
-        }
-        // what the piece holds of each staged product, into the caller's array
-        const size_t p0 = pieces[k].off, p1 = p0 + pieces[k].len;
-        for (int q = 0; q < nSeg; ++q) {
-            if (!segs[q].dst) continue;
-            const size_t a0 = std::max(p0, segs[q].off), a1 = std::min(p1, segs[q].off + segs[q].len);
-            if (a0 >= a1) continue;
-            unsigned char* dst = static_cast<unsigned char*>(segs[q].dst) + (a0 - segs[q].off);
-            const size_t len = a1 - a0;
-            if (len >= (256u << 10)) {
-                const size_t parts = std::min<size_t>(h->copyPool.width(), (len + (256u << 10) - 1) / (256u << 10));
-                const size_t step = ((len + parts - 1) / parts + 63) & ~static_cast<size_t>(63);
-                for (size_t c = 0; c < len; c += step) h->copyPool.submit(batch, dst + c, hp + a0 + c, std::min(step, len - c));
-            } else {
-                std::memcpy(dst, hp + a0, len);
-            }
-        }
-    }
-    CopyPool::wait(batch);
-    if (evErr != hipSuccess) return fail_hip(evErr, "result copy");  // (the lease waits for the stream)
-    FPE_HIP(hipStreamSynchronize(cx.stream));  // the direct (pinned-destination) copies
-    cx.inFlight = false;
+    SegList segs;
+    for (int k = 0; k < kProducts; ++k) segs.add(L.off[k], L.len[k], want[k]);
+    if (!run.zeroCopy) return copy_out(h, cx, segs, run.dp, cx.pinned);
+    rc = plan_wait_zero_copy(cp, cx, L, oc, run);
+    if (rc != FPE_OK) return rc;
+    copy_from_pinned(segs, cx.pinned);
     return FPE_OK;
 }
 }  // namespace
@@ -1898,13 +1883,13 @@ struct RankLayout {
     int32_t* nClass0;
     void* keys;
     size_t scratchBytes, outBytes;
-    size_t outOff[12], outLen[12];  // summary, score, best, n_class0, the eight products: the host form's transfers
+    // the host form's transfers, in the output block's order: the eight products, then summary, score, best, n_class0
+    size_t outOff[kPlanProducts + 4], outLen[kPlanProducts + 4];
 };
+static_assert(kPlanProducts + 4 <= kProducts, "SegList holds a ranking call's outputs");
 void rank_layout(RankLayout& L, const fpe_plan_out* dFull, const fpe_rank_out& want, bool hostForm, unsigned char* base, unsigned char* outBase) {
-    const size_t nRec = static_cast<size_t>(L.n) * 4;
-    const size_t perPose[8] = {nRec * sizeof(fpe_foothold), nRec * sizeof(fpe_centroid_foothold), nRec * 3 * sizeof(double), static_cast<size_t>(L.n),
-                               12 * sizeof(double), nRec * sizeof(fpe_selected_foothold), 1, nRec * sizeof(fpe_selected_packed)};
-    const bool reads[8] = {true, false, true, true, true, false, true, false};  // rank_summary_kernel's inputs
+    const bool reads[kPlanProducts] = {true, false, true, true, true, false, true, false};  // rank_summary_kernel's inputs
+    const size_t B = static_cast<size_t>(L.B), K = static_cast<size_t>(L.K), n = static_cast<size_t>(L.n);
     size_t off = 0, oo = 0;
     const auto take = [&](size_t bytes) {
         unsigned char* p = base + off;
@@ -1917,20 +1902,18 @@ void rank_layout(RankLayout& L, const fpe_plan_out* dFull, const fpe_rank_out& w
         oo += align256(bytes);
         return static_cast<void*>(outBase + L.outOff[k]);
     };
-    for (int k = 0; k < 12; ++k) L.outOff[k] = L.outLen[k] = 0;
-    void* const* given = reinterpret_cast<void* const*>(dFull);  // fpe_plan_out is eight pointers
-    void* const* wanted = reinterpret_cast<void* const*>(&want.best_products);
-    void** full = reinterpret_cast<void**>(&L.full);
-    void** best = reinterpret_cast<void**>(&L.best);
-    for (int k = 0; k < 8; ++k) {
-        full[k] = (given && given[k]) ? given[k] : ((reads[k] || wanted[k]) ? take(static_cast<size_t>(L.B) * perPose[k]) : nullptr);
-        best[k] = !wanted[k] ? nullptr : (hostForm ? takeOut(4 + k, static_cast<size_t>(L.K) * perPose[k]) : wanted[k]);
+    for (int k = 0; k < kPlanProducts + 4; ++k) L.outOff[k] = L.outLen[k] = 0;
+    void* const* given = dFull ? slots(*dFull) : nullptr;
+    void* const* wanted = slots(want.best_products);
+    for (int k = 0; k < kPlanProducts; ++k) {
+        slots(L.full)[k] = (given && given[k]) ? given[k] : ((reads[k] || wanted[k]) ? take(product_bytes(k, B, n)) : nullptr);
+        slots(L.best)[k] = !wanted[k] ? nullptr : (hostForm ? takeOut(k, product_bytes(k, K, n)) : wanted[k]);
     }
-    const size_t szSum = static_cast<size_t>(L.B) * sizeof(fpe_pose_summary), szScore = static_cast<size_t>(L.B) * sizeof(double);
-    L.summary = static_cast<fpe_pose_summary*>(!want.summary ? take(szSum) : (hostForm ? takeOut(0, szSum) : want.summary));
-    L.score = static_cast<double*>(!want.score ? take(szScore) : (hostForm ? takeOut(1, szScore) : want.score));
-    L.bestIdx = static_cast<int32_t*>(hostForm ? takeOut(2, static_cast<size_t>(L.K) * sizeof(int32_t)) : want.best);
-    L.nClass0 = static_cast<int32_t*>(!want.n_class0 ? nullptr : (hostForm ? takeOut(3, sizeof(int32_t)) : want.n_class0));
+    const size_t szSum = B * sizeof(fpe_pose_summary), szScore = B * sizeof(double);
+    L.summary = static_cast<fpe_pose_summary*>(!want.summary ? take(szSum) : (hostForm ? takeOut(kPlanProducts, szSum) : want.summary));
+    L.score = static_cast<double*>(!want.score ? take(szScore) : (hostForm ? takeOut(kPlanProducts + 1, szScore) : want.score));
+    L.bestIdx = static_cast<int32_t*>(hostForm ? takeOut(kPlanProducts + 2, K * sizeof(int32_t)) : want.best);
+    L.nClass0 = static_cast<int32_t*>(!want.n_class0 ? nullptr : (hostForm ? takeOut(kPlanProducts + 3, sizeof(int32_t)) : want.n_class0));
     L.keys = take(fpe::rank_scratch_bytes(L.B, L.K));
     L.scratchBytes = off;
     L.outBytes = oo;
@@ -1958,8 +1941,8 @@ int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_
     RankLayout L{};
     L.B = B, L.n = n_cycles, L.K = K;
     rank_layout(L, d_full, *d_out, false, nullptr, nullptr);
-    if (((d_full && d_full->selected_packed) || d_out->best_products.selected_packed) && (cp.snap->g.rows > FPE_PACKED_MAX_CELLS || cp.snap->g.cols > FPE_PACKED_MAX_CELLS))
-        return fail(FPE_E_UNSUPPORTED, "selected_packed holds biased 14-bit grid indices: the map has more than 15871 rows or columns");
+    rc0 = check_packed_fits(cp, (d_full && d_full->selected_packed) || d_out->best_products.selected_packed);
+    if (rc0 != FPE_OK) return rc0;
     mark_async_launch(cp);
     void* scratch = nullptr;
     FPE_HIP(hipMallocAsync(&scratch, L.scratchBytes, st));
@@ -1995,43 +1978,24 @@ int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params*
     cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
     rc0 = prepare_call(h, params, maxRadius, cp, cx.stream, true);
     if (rc0 != FPE_OK) return rc0;
-    if (out->best_products.selected_packed && (cp.snap->g.rows > FPE_PACKED_MAX_CELLS || cp.snap->g.cols > FPE_PACKED_MAX_CELLS))
-        return fail(FPE_E_UNSUPPORTED, "selected_packed holds biased 14-bit grid indices: the map has more than 15871 rows or columns");
+    rc0 = check_packed_fits(cp, out->best_products.selected_packed != nullptr);
+    if (rc0 != FPE_OK) return rc0;
     std::memcpy(cx.pinned, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
     void* mapped = nullptr;
     FPE_HIP(hipHostGetDevicePointer(&mapped, cx.pinned, 0));
-    unsigned char* const hostOut = cx.pinned + szPose;
-    unsigned char* const devOut = zeroCopy ? static_cast<unsigned char*>(mapped) + szPose : cx.dev + szPose;
-    rank_layout(L, nullptr, *out, true, cx.dev + szPose + L.outBytes, devOut);
+    unsigned char* const devArena = zeroCopy ? static_cast<unsigned char*>(mapped) : cx.dev;
+    rank_layout(L, nullptr, *out, true, cx.dev + szPose + L.outBytes, devArena + szPose);
     rc0 = run_rank(h, cp, rc, static_cast<const fpe_pose*>(mapped), L, cx.stream);
     if (rc0 != FPE_OK) return rc0;
-    void* const dst[12] = {out->summary, out->score, out->best, out->n_class0, out->best_products.nominal, out->best_products.centroid,
-                           out->best_products.default_next, out->best_products.cycle_ok, out->best_products.stance, out->best_products.selected,
-                           out->best_products.pose_status, out->best_products.selected_packed};
-    bool direct[12] = {false};
-    if (!zeroCopy) {
-        // stage_products' pattern: a pinned destination is written by DMA, any other through the pinned arena — neighbours there in one transfer
-        for (int k = 0; k < 12; ++k) direct[k] = L.outLen[k] && is_pinned_host(dst[k]);
-        for (int k = 0; k < 12; ++k) {
-            if (!L.outLen[k]) continue;
-            if (direct[k]) {
-                FPE_HIP(hipMemcpyAsync(dst[k], devOut + L.outOff[k], L.outLen[k], hipMemcpyDeviceToHost, cx.stream));
-                continue;
-            }
-            size_t begin = L.outOff[k], end = begin + L.outLen[k];
-            int last = k;
-            while (last + 1 < 12 && (!L.outLen[last + 1] || (!is_pinned_host(dst[last + 1]) && L.outOff[last + 1] == align256(end)))) {
-                ++last;
-                if (L.outLen[last]) end = L.outOff[last] + L.outLen[last];
-            }
-            FPE_HIP(hipMemcpyAsync(hostOut + begin, devOut + begin, end - begin, hipMemcpyDeviceToHost, cx.stream));
-            k = last;
-        }
-    }
+    void* dst[kPlanProducts + 4];
+    std::copy(slots(out->best_products), slots(out->best_products) + kPlanProducts, dst);
+    dst[kPlanProducts] = out->summary, dst[kPlanProducts + 1] = out->score, dst[kPlanProducts + 2] = out->best, dst[kPlanProducts + 3] = out->n_class0;
+    SegList segs;
+    for (int k = 0; k < kPlanProducts + 4; ++k) segs.add(szPose + L.outOff[k], L.outLen[k], dst[k]);
+    if (!zeroCopy) return copy_out(h, cx, segs, cx.dev, cx.pinned);
     FPE_HIP(hipStreamSynchronize(cx.stream));
     cx.inFlight = false;
-    for (int k = 0; k < 12; ++k)
-        if (L.outLen[k] && !direct[k]) std::memcpy(dst[k], hostOut + L.outOff[k], L.outLen[k]);
+    copy_from_pinned(segs, cx.pinned);
     return FPE_OK;
 }
 

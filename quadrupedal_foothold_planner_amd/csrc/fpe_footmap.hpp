@@ -22,10 +22,6 @@
 //                              without a row-interval form, the flags over the offset table.
 #pragma once
 
-// Region of a foothold-map call in canonical indices (fpe_foothold_map's roi)
-struct FootmapRoi {
-    int row0, col0, nr, nc;
-};
 // The literal walk visits a (2 ceil(rf / res) + 2)^2 box per cell: bounded so that one call stays a short kernel
 constexpr int kFmapMaxLiteralReach = 32;
 

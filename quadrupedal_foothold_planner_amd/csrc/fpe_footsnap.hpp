@@ -22,14 +22,6 @@
 //                          are built on the device in chunks and run through search_legs_kernel itself, then converted.
 #pragma once
 
-// Host-proved constants of a snap call (snap_prove in fpe_engine.cpp)
-struct SnapConsts {
-    int32_t nRings, nCand;  // SpiralIterator rings of R and rank-table entries of rings 0..nRings
-    int32_t ringT;          // the outer two rings' isInside test: di^2 + dj^2 <= ringT
-    int32_t rectA, rectB;   // rectangle: |di| <= rectA and |dj| <= rectB inside (cell-centre offsets)
-    float Rf;               // the search radius
-    int32_t polyKind;       // 0 rectangle, 1 hexagon (query construction of the literal path)
-};
 // The bit path holds P for a halo of nRings rows and one word per side: rings up to 32
 constexpr int kSnapMaxRings = 32;
 // Cells per literal-path chunk (queries + records of a chunk live in stream-ordered scratch)

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "fpe_device.hpp"
+#include "fpe_launch.hpp"
 
 namespace fpe {
 
@@ -2077,7 +2078,6 @@ hipError_t launch_centroid_legs(const DevMap& m, const PlanConsts& pc, float def
     return hipGetLastError();
 }
 
-size_t bitmap_words(int rows, int cols, int* strideW, int* nw);  // fpe_bits.hpp (part two of this translation unit)
 // d_planeWords: also build the bit planes of the destination layer for (thrDefault, thrCandidate) — the buffer zeroed here first
 // (padding rows / word groups; recycled buffers are dirty) — or null.
 hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int cols, int si, int sj, int srcRowMajor,

@@ -1,0 +1,96 @@
+// fpe_launch.hpp — the boundary between the host side of the engine (fpe_engine.cpp) and the kernel translation unit
+// (fpe_kernels.hip and the family headers it includes): the ONE declaration of every fpe:: function the engine calls and the
+// kernel side defines, the argument structs of the newer kernel families, and the only place for default arguments.
+// fpe_kernels.hip includes this ahead of its own definitions, so a definition that drifts from its declaration — a changed
+// parameter list, a struct field added on one side — no longer compiles or links; it cannot run with two layouts.
+// (DevMap, PlanConsts, BitMap, FilterConsts, OptConsts: fpe_device.hpp.)
+#pragma once
+#include "fpe_device.hpp"
+
+namespace fpe {
+
+// ---- direct kernels (fpe_kernels.hip) ------------------------------------------------------------------------
+hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
+                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream);
+hipError_t launch_search_legs(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_leg_query* d_q,
+                              int n, fpe_foothold* d_out, hipStream_t stream);
+// open-loop centroid method
+hipError_t launch_centroid_legs(const DevMap& m, const PlanConsts& pc, float defaultR, const fpe_centroid_query* d_q, int n,
+                                fpe_centroid_foothold* d_out, hipStream_t stream);
+hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int cols, int si, int sj, int srcRowMajor, hipStream_t stream,
+                               uint32_t* d_planeWords = nullptr, float thrDefault = 0.0f, float thrCandidate = 0.0f);
+hipError_t set_max_lds(size_t planBytes, size_t searchBytes);
+size_t plan_lds_bytes(const PlanConsts& pc);
+size_t search_lds_bytes(const PlanConsts& pc);
+
+// ---- bit-window path (fpe_bits.hpp) --------------------------------------------------------------------------
+size_t bitmap_words(int rows, int cols, int* strideW, int* nw);
+hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float thrDefault, float thrCandidate,
+                               uint32_t* d_words, hipStream_t stream);
+bool bits_supported(const PlanConsts& pc, const MapGeom& g);
+void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n);
+hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut,
+                            const fpe_pose* d_poses, int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream);
+
+// ---- producer filters (fpe_filters.hpp) ----------------------------------------------------------------------
+bool filters_supported(const FilterConsts& fc, const MapGeom& g);
+bool filters_trav_only_ok(const FilterConsts& fc, const MapGeom& g);
+hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, bool travOnly, hipStream_t stream);
+
+// ---- opt track (fpe_opt.hpp) ---------------------------------------------------------------------------------
+hipError_t launch_opt_track(const DevMap& m, const PlanConsts& pc, const OptConsts& oc, const fpe_pose* d_poses, int B, int nCycles,
+                            const uint8_t* d_cycleOk, const fpe_opt_out& d_out, hipStream_t stream, uint32_t* doneFlag = nullptr, uint32_t doneValue = 0);
+
+// ---- dense foothold map (fpe_footmap.hpp) --------------------------------------------------------------------
+// Region of a foothold-map call in canonical indices (fpe_foothold_map's roi)
+struct FootmapRoi {
+    int row0, col0, nr, nc;
+};
+int foothold_map_supported(const PlanConsts& pc, const MapGeom& g);
+hipError_t launch_foothold_map(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const FootmapRoi& roi, uint8_t* d_flags,
+                               float* d_height, hipStream_t stream);
+
+// ---- dense snap map (fpe_footsnap.hpp) -----------------------------------------------------------------------
+// Host-proved constants of a snap call (snap_prove in fpe_engine.cpp)
+struct SnapConsts {
+    int32_t nRings, nCand;  // SpiralIterator rings of R and rank-table entries of rings 0..nRings
+    int32_t ringT;          // the outer two rings' isInside test: di^2 + dj^2 <= ringT
+    int32_t rectA, rectB;   // rectangle: |di| <= rectA and |dj| <= rectB inside (cell-centre offsets)
+    float Rf;               // the search radius
+    int32_t polyKind;       // 0 rectangle, 1 hexagon (query construction of the literal path)
+};
+bool foothold_snap_bits_ok(const PlanConsts& pc, const SnapConsts& sc, bool haveBits, bool rectProved);
+hipError_t launch_foothold_snap_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SnapConsts& sc, const SpiralLut& lut,
+                                     const FootmapRoi& roi, int8_t* d_offset, uint8_t* d_source, float* d_z, hipStream_t stream);
+size_t foothold_snap_literal_scratch_bytes();
+hipError_t launch_foothold_snap_literal(const DevMap& m, const PlanConsts& pc, const SnapConsts& sc, const SpiralLut& lut,
+                                        const FootmapRoi& roi, void* scratch, int8_t* d_offset, uint8_t* d_source, float* d_z,
+                                        hipStream_t stream);
+
+// ---- dense centroid map (fpe_centroidmap.hpp) ----------------------------------------------------------------
+// Host-derived constants of a dense centroid call (centroid_map_consts)
+struct CmapConsts {
+    float Rf;         // the search radius: the rectangle is {2 Rf, Rf} (cpp:1616-1617)
+    int32_t H;        // reach of the rectangle from its cell, rows or columns: ceil(Rf / res) + 2
+    int32_t rb, re;   // map rows [rb, re) of the planes: the region's rows +- H, clipped to the map
+    int32_t nwr;      // words per plane column: ceil((re - rb) / 32)
+};
+bool centroid_map_consts(const MapGeom& g, const FootmapRoi& roi, float R, CmapConsts& cc);
+size_t centroid_map_scratch_bytes(const FootmapRoi& roi, const CmapConsts& cc);
+hipError_t launch_centroid_map(const DevMap& m, const PlanConsts& pc, const CmapConsts& cc, const FootmapRoi& roi, void* scratch,
+                               uint8_t* d_code, int8_t* d_offset, float* d_z, hipStream_t stream);
+
+// ---- ranking of a planned batch (fpe_rank.hpp) ---------------------------------------------------------------
+struct RankConsts {
+    double wFail, wSpiral, wNone, wDeviation, wSpeedSpread;
+    double stepHalf;  // double(stepLength / 2): the current feet start at stance - stepHalf (setFirstGait, cpp:2679-2699)
+    int32_t minCycles;
+    int32_t rfFirst;
+};
+size_t rank_scratch_bytes(int B, int K);
+hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
+                       fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
+                       const fpe_plan_out& bestProducts, hipStream_t stream);
+hipError_t set_max_lds_rank();
+
+}  // namespace fpe

@@ -4,13 +4,6 @@
 // inputs alone.
 #pragma once
 
-struct RankConsts {
-    double wFail, wSpiral, wNone, wDeviation, wSpeedSpread;
-    double stepHalf;  // double(stepLength / 2): the current feet start at stance - stepHalf (setFirstGait, cpp:2679-2699)
-    int32_t minCycles;
-    int32_t rfFirst;
-};
-
 // Sort key of one pose, ascending = better: hi = class << 32 | image >> 32, lo = image << 32 | pose index, with `image` the
 // order-preserving 64-bit image of the score (0 for class 2: those fall to the index alone).  All ones = no pose.
 struct alignas(16) RankKey {

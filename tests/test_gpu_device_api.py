@@ -752,3 +752,176 @@ def test_host_plan_into_pinned_arrays_equals_the_pageable_path(planner, B):
     out3 = planner.plan(poses, n, out=mixed)
     for k in ref:
         assert out3[k].tobytes() == ref[k].tobytes(), k
+
+
+# ---- the host forms' layout and copy-out (one product table, one copy-out routine in the engine) -----------------------------
+ALL_PRODUCTS = ("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status", "selected_packed")
+ZERO_COPY_BYTES = 64 * 1024  # arenas up to this size are written by the kernels themselves, larger ones cross by DMA
+GUARD, FILL = 64, 0xA5
+
+
+def _align256(n):
+    return (n + 255) & ~255
+
+
+def _product_bytes(B, n):
+    from quadrupedal_foothold_planner_amd.planner import product_shapes
+
+    return {k: int(np.prod(shape)) * np.dtype(dtype).itemsize for k, (shape, dtype) in product_shapes(B, n).items()}
+
+
+def _plan_arena_bytes(B, n, products=ALL_PRODUCTS):
+    """What fpe_plan keeps in its arena: the poses, then each requested product, in 256-byte steps."""
+    sizes = _product_bytes(B, n)
+    return _align256(B * _capi.POSE_DTYPE.itemsize) + sum(_align256(sizes[k]) for k in products)
+
+
+def _rough_300(planner, B, seed=77):
+    planner.params = _capi.params_yaml()
+    trav, elev = synth.rough_map(300, 300, 0.02, seed=seed)
+    rng = np.random.default_rng(B)
+    poses = make_poses(np.column_stack([rng.uniform(-2.0, 0.5, B), rng.uniform(-2.0, 2.0, B), np.zeros(B)]))
+    poses["gait"] = rng.integers(0, 2, B)
+    planner.gridmapCallback(trav, elev, 0.02)
+    return poses
+
+
+def _plan_device_all(planner, poses, n):
+    """fpe_plan_device on the current map, every product, then an explicit copy: {product: array}."""
+    import torch
+    from quadrupedal_foothold_planner_amd.planner import product_shapes
+
+    B = poses.shape[0]
+    shapes, sizes = product_shapes(B, n), _product_bytes(B, n)
+    d_poses = torch.from_numpy(poses.view(np.uint8).reshape(-1).copy()).cuda()
+    d = {k: torch.zeros(sizes[k], dtype=torch.uint8, device="cuda") for k in ALL_PRODUCTS}
+    torch.cuda.synchronize()
+    planner.plan_device(d_poses.data_ptr(), B, n, d["nominal"].data_ptr(), d["centroid"].data_ptr(), d["default"].data_ptr(),
+                        d["cycle_ok"].data_ptr(), d["stance"].data_ptr(), d_selected_ptr=d["selected"].data_ptr(),
+                        d_pose_status_ptr=d["pose_status"].data_ptr(), d_selected_packed_ptr=d["selected_packed"].data_ptr())
+    torch.cuda.synchronize()
+    return {k: d[k].cpu().numpy().view(shapes[k][1]).reshape(shapes[k][0]) for k in ALL_PRODUCTS}
+
+
+def _guarded(shape, dtype):
+    """(buffer, view): `view` sits between GUARD bytes of FILL on both sides of `buffer`."""
+    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    buf = np.full(nbytes + 2 * GUARD, FILL, np.uint8)
+    return buf, buf[GUARD:GUARD + nbytes].view(dtype).reshape(shape)
+
+
+def _guards_untouched(buf):
+    return bool(np.all(buf[:GUARD] == FILL) and np.all(buf[-GUARD:] == FILL))
+
+
+def test_host_plan_on_either_side_of_the_zero_copy_bound_equals_the_device_form(planner):
+    """fpe_plan with every product at n = 5 for the largest batch whose arena still fits the zero-copy bound and for one pose
+    more (the first that goes through DMA transfers): both byte-equal to fpe_plan_device plus an explicit copy."""
+    n = 5
+    under = max(B for B in range(1, 200) if _plan_arena_bytes(B, n) <= ZERO_COPY_BYTES)
+    over = under + 1
+    assert _plan_arena_bytes(under, n) <= ZERO_COPY_BYTES < _plan_arena_bytes(over, n)
+    for B in (under, over):
+        poses = _rough_300(planner, B)
+        host = planner.plan(poses, n, products=ALL_PRODUCTS)
+        dev = _plan_device_all(planner, poses, n)
+        for k in ALL_PRODUCTS:
+            assert host[k].tobytes() == dev[k].tobytes(), (B, k)
+
+
+def test_host_plan_opt_with_given_flags_on_the_dma_path_equals_the_device_form(planner):
+    """fpe_plan_opt with the caller's cycle_ok (some cycles failed), B = 64, n = 5: an arena over the zero-copy bound, pinned
+    and pageable destinations mixed.  Byte-equal to fpe_plan_opt_device on the same poses and flags."""
+    import ctypes as C
+
+    import torch
+
+    planner.params = _capi.params_yaml()
+    planner.opt_params = _capi.opt_params_yaml()
+    B, n = 64, 5
+    trav, elev = synth.rough_map(300, 300, 0.02, seed=41, bad_frac=0.35)  # bad terrain: many failed cycles
+    poses = synth.poses_in_map(B, 6.0, 6.0, n, 0.18, seed=42, margin=0.7)
+    planner.gridmapCallback(trav, elev, 0.02)
+    ok = planner.plan(poses, n, products=("cycle_ok",))["cycle_ok"]
+    assert ok.any() and not ok.all(), "both committed and failed cycles expected"
+    shapes = {"footholds": ((B, n, 4), _capi.OPT_FOOTHOLD_DTYPE), "cycles": ((B, n), _capi.OPT_CYCLE_DTYPE),
+              "gate_fail_cycle": ((B,), np.uint8), "rows_after": ((B, 2), np.float64)}
+    sizes = {k: int(np.prod(s)) * np.dtype(t).itemsize for k, (s, t) in shapes.items()}
+    arena = _align256(B * _capi.POSE_DTYPE.itemsize) + _align256(B * n) + sum(_align256(v) for v in sizes.values())
+    assert arena > ZERO_COPY_BYTES
+    host = {k: (planner.host_array(*shapes[k]) if k in ("footholds", "gate_fail_cycle") else np.zeros(*shapes[k])) for k in shapes}
+    oo = _capi.OptOut(*[_capi.ptr(host[k]) for k in shapes])
+    planner._check(planner._lib.fpe_plan_opt(planner._h, _capi.ptr(planner.params), _capi.ptr(planner.opt_params), _capi.ptr(poses), B, n,
+                                             _capi.ptr(ok), C.byref(oo)))
+    d_poses = torch.from_numpy(poses.view(np.uint8).reshape(-1).copy()).cuda()
+    d_ok = torch.from_numpy(ok.reshape(-1).copy()).cuda()
+    d = {k: torch.zeros(sizes[k], dtype=torch.uint8, device="cuda") for k in shapes}
+    do = _capi.OptOut(*[C.c_void_p(d[k].data_ptr()) for k in shapes])
+    torch.cuda.synchronize()
+    planner._check(planner._lib.fpe_plan_opt_device(planner._h, _capi.ptr(planner.params), _capi.ptr(planner.opt_params),
+                                                    C.c_void_p(d_poses.data_ptr()), B, n, C.c_void_p(d_ok.data_ptr()), C.byref(do),
+                                                    C.c_void_p(0)))
+    torch.cuda.synchronize()
+    for k in shapes:
+        assert host[k].tobytes() == d[k].cpu().numpy().tobytes(), k
+
+
+def test_host_plan_product_subsets_equal_the_full_call_and_leave_their_guards(planner):
+    """Every single product of fpe_plan_out alone, and the complement of each, through the host form at B = 37, n = 3 (no
+    product size is a multiple of 256: padding sits between the products in the arena).  That arena is under the zero-copy
+    bound, so those calls check the layout and the copy out of the pinned arena; the complements again at B = 75, n = 3
+    (padding again, every arena over the bound) cross by DMA in merged runs.  Byte-equal to the full call's product, the
+    guard bytes around every array untouched."""
+    from quadrupedal_foothold_planner_amd.planner import product_shapes
+
+    n = 3
+    singles = [(k,) for k in ALL_PRODUCTS]
+    complements = [tuple(q for q in ALL_PRODUCTS if q != k) for k in ALL_PRODUCTS]
+    assert _plan_arena_bytes(37, n) <= ZERO_COPY_BYTES
+    assert all(_plan_arena_bytes(75, n, c) > ZERO_COPY_BYTES for c in complements)
+    assert all(v % 256 for B in (37, 75) for v in _product_bytes(B, n).values())
+    for B, subsets in ((37, singles + complements), (75, complements)):
+        poses = _rough_300(planner, B)
+        full = planner.plan(poses, n, products=ALL_PRODUCTS)
+        shapes = product_shapes(B, n)
+        for products in subsets:
+            bufs, out = {}, {}
+            for k in products:
+                bufs[k], out[k] = _guarded(*shapes[k])
+            got = planner.plan(poses, n, out=out)
+            assert set(got) == set(products)
+            for k in products:
+                assert got[k].tobytes() == full[k].tobytes(), (B, products, k)
+                assert _guards_untouched(bufs[k]), (B, products, k)
+
+
+@pytest.mark.parametrize("where", ["pinned", "pageable", "mixed"])
+def test_host_plan_rank_into_pinned_pageable_and_mixed_arrays_equals_the_device_form(planner, where):
+    """fpe_plan_rank's host form, B = 300, K = 40, n = 4, every output: over the zero-copy bound, so every output crosses by
+    DMA — straight into pinned destinations, through the staging arena into pageable ones.  Byte-equal to the device form."""
+    import ctypes as C
+
+    import torch
+    from quadrupedal_foothold_planner_amd.planner import PRODUCT_FIELDS, product_shapes
+
+    B, K, n = 300, 40, 4
+    poses = _rough_300(planner, B)
+    shapes = dict(product_shapes(K, n))
+    shapes.update(summary=((B,), _capi.POSE_SUMMARY_DTYPE), score=((B,), np.float64), best=((K,), np.int32), n_class0=((1,), np.int32))
+    sizes = {k: int(np.prod(s)) * np.dtype(t).itemsize for k, (s, t) in shapes.items()}
+    assert sum(_align256(v) for v in sizes.values()) > ZERO_COPY_BYTES
+    pinned = {"pinned": set(shapes), "pageable": set(), "mixed": set(list(shapes)[::2])}[where]
+    host = {k: (planner.host_array(*shapes[k]) if k in pinned else np.zeros(*shapes[k])) for k in shapes}
+    ro = _capi.RankOut(_capi.ptr(host["summary"]), _capi.ptr(host["score"]), _capi.ptr(host["best"]), _capi.ptr(host["n_class0"]))
+    for k in ALL_PRODUCTS:
+        setattr(ro.best_products, PRODUCT_FIELDS[k], _capi.ptr(host[k]))
+    planner._check(planner._lib.fpe_plan_rank(planner._h, _capi.ptr(planner.params), None, _capi.ptr(poses), B, n, K, C.byref(ro)))
+    d_poses = torch.from_numpy(poses.view(np.uint8).reshape(-1).copy()).cuda()
+    d = {k: torch.zeros(sizes[k], dtype=torch.uint8, device="cuda") for k in shapes}
+    torch.cuda.synchronize()
+    planner.plan_rank_device(d_poses.data_ptr(), B, n, K, d["best"].data_ptr(), d_summary_ptr=d["summary"].data_ptr(),
+                             d_score_ptr=d["score"].data_ptr(), d_n_class0_ptr=d["n_class0"].data_ptr(),
+                             best_products={k: d[k].data_ptr() for k in ALL_PRODUCTS})
+    torch.cuda.synchronize()
+    for k in shapes:
+        assert host[k].tobytes() == d[k].cpu().numpy().tobytes(), k
