@@ -669,6 +669,53 @@ int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_
                          int32_t B, int32_t n_cycles, int32_t K, const fpe_plan_out* d_full /* may be NULL */,
                          const fpe_rank_out* d_out, void* stream);
 
+/* ---- the dense maps as grid_map message layers: the inverse of fpe_upload_map's ingest ----------------------------------
+ * BUILD-DEFINED (the reference publishes none of these layers).  One call runs the dense families whose layers are requested —
+ * fpe_foothold_map, fpe_foothold_snap, fpe_centroid_map with the same params, roi, radius and polygon; only the products
+ * those layers need — and writes every requested layer as rows * cols floats of the WHOLE map in the layout of the message
+ * being filled: canonical cell (i, j) goes to buffer cell bi = (i + start_index[0]) mod rows, bj = (j + start_index[1]) mod
+ * cols, which is element bi + bj * rows of a column-major buffer (storage_order 0) and bi * cols + bj of a row-major one
+ * (fpe_map_desc's mapping, inverted).  Inside roi the value is the layer's float of the table below, computed from exactly
+ * what the dense call returns; outside roi it is the quiet NaN 0x7FC00000 (grid_map's "no data").  Every call writes every
+ * cell of every requested destination; a refused call writes nothing.  Refusals: FPE_E_INVALID_ARG for a null handle, params
+ * or request, n_layers out of range, an unknown or duplicated id, a null dst, a start index outside the map, a storage order
+ * other than 0 or 1, a bad roi; FPE_E_NO_MAP; and every refusal of the dense calls of the families requested (a bad polygon
+ * kind is refused only when a snap layer is requested).  Snapshot semantics, literal_discs and pinned destinations behave as in
+ * fpe_foothold_map: the host form is synchronous, the device form asynchronous on `stream`. */
+/* layer ids; the float a layer holds for canonical cell (i, j) inside the region */
+#define FPE_LAYER_FOOTHOLD_FLAGS  0  /* (float) fpe_foothold_map flags byte, 0..7            */
+#define FPE_LAYER_FOOTHOLD_HEIGHT 1  /* fpe_foothold_map height, bit for bit                 */
+#define FPE_LAYER_SNAP_DI         2  /* (float) fpe_foothold_snap offset[0]                  */
+#define FPE_LAYER_SNAP_DJ         3  /* (float) offset[1]                                    */
+#define FPE_LAYER_SNAP_SOURCE     4  /* (float) source                                       */
+#define FPE_LAYER_SNAP_Z          5  /* z, bit for bit                                       */
+#define FPE_LAYER_CENTROID_CODE   6  /* (float) fpe_centroid_map code                        */
+#define FPE_LAYER_CENTROID_DI     7  /* (float) fpe_centroid_map offset[0]                   */
+#define FPE_LAYER_CENTROID_DJ     8  /* (float) offset[1]                                    */
+#define FPE_LAYER_CENTROID_Z      9  /* z, bit for bit                                       */
+#define FPE_LAYER_COUNT          10
+
+typedef struct fpe_layer_layout {      /* the DESTINATION buffers' layout: that of the message being filled */
+    int32_t start_index[2];            /* 0 <= start_index[k] < size[k] */
+    int32_t storage_order;             /* 0 column-major (grid_map_msgs), 1 row-major — as fpe_map_desc */
+    int32_t reserved;                  /* 0 */
+} fpe_layer_layout;                    /* NULL layout = canonical: start (0,0), row-major */
+
+typedef struct fpe_layer_request {
+    int32_t n_layers;                  /* 1..FPE_LAYER_COUNT */
+    int32_t layer[FPE_LAYER_COUNT];    /* FPE_LAYER_* ids, no duplicates */
+    float*  dst[FPE_LAYER_COUNT];      /* dst[k]: rows*cols floats of the WHOLE map for layer[k]; non-NULL */
+    float   snap_search_radius;        /* as fpe_foothold_snap (<= 0: params->searchRadius) */
+    int32_t snap_polygon_kind;         /* as fpe_foothold_snap */
+    float   centroid_search_radius;    /* as fpe_centroid_map */
+    int32_t reserved;
+} fpe_layer_request;
+
+int fpe_export_layers(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_layer_layout* layout,
+                      const fpe_layer_request* request);
+int fpe_export_layers_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_layer_layout* layout,
+                             const fpe_layer_request* d_request /* dst = DEVICE pointers */, void* stream);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

@@ -202,6 +202,24 @@ class CentroidMapOut(C.Structure):
     _fields_ = [("code", C.c_void_p), ("offset", C.c_void_p), ("z", C.c_void_p)]
 
 
+# FPE_LAYER_* ids of include/fpe.h by name, in id order: the message layers fpe_export_layers* writes
+LAYER_NAMES = ("foothold_flags", "foothold_height", "snap_di", "snap_dj", "snap_source", "snap_z", "centroid_code", "centroid_di",
+               "centroid_dj", "centroid_z")
+LAYER_COUNT = len(LAYER_NAMES)
+
+
+class LayerLayout(C.Structure):
+    """fpe_layer_layout: start index and storage order (0 column-major, 1 row-major) of the destination buffers."""
+    _fields_ = [("start_index", C.c_int32 * 2), ("storage_order", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LayerRequest(C.Structure):
+    """fpe_layer_request: the layers of one fpe_export_layers* call and where each goes (rows * cols floats of the whole map)."""
+    _fields_ = [("n_layers", C.c_int32), ("layer", C.c_int32 * LAYER_COUNT), ("dst", C.c_void_p * LAYER_COUNT),
+                ("snap_search_radius", C.c_float), ("snap_polygon_kind", C.c_int32), ("centroid_search_radius", C.c_float),
+                ("reserved", C.c_int32)]
+
+
 # fpe_pose_summary: what fpe_plan_rank* reduces one pose's plan to (64 bytes)
 POSE_SUMMARY_DTYPE = np.dtype(
     [("success", "u1"), ("gait_cycles_succeed", "u1"), ("committed", "u1"), ("first_failed", "u1"), ("pose_status", "u1"),
@@ -296,6 +314,8 @@ EXPORTED_SYMBOLS = [
     "fpe_rank_params_defaults",
     "fpe_plan_rank",
     "fpe_plan_rank_device",
+    "fpe_export_layers",
+    "fpe_export_layers_device",
     "fpe_spiral_offsets",
     "fpe_tile_halfwidth",
     "fpe_algorithmic_bytes_per_foothold",
@@ -389,6 +409,8 @@ def lib():
     L.fpe_rank_params_defaults.argtypes = [C.POINTER(RankParams)]
     L.fpe_plan_rank.argtypes = [vp, vp, C.POINTER(RankParams), vp, i32, i32, i32, C.POINTER(RankOut)]
     L.fpe_plan_rank_device.argtypes = [vp, vp, C.POINTER(RankParams), vp, i32, i32, i32, C.POINTER(PlanOut), C.POINTER(RankOut), vp]
+    L.fpe_export_layers.argtypes = [vp, vp, vp, C.POINTER(LayerLayout), C.POINTER(LayerRequest)]
+    L.fpe_export_layers_device.argtypes = [vp, vp, vp, C.POINTER(LayerLayout), C.POINTER(LayerRequest), vp]
     L.fpe_spiral_offsets.argtypes = [i32, vp, i32]
     L.fpe_tile_halfwidth.argtypes = [f32, f32, f64]
     L.fpe_algorithmic_bytes_per_foothold.restype = f64

@@ -503,7 +503,7 @@ int prepare_call(fpe_engine* h, const fpe_params* params, float maxRadius, CallP
     fpe::Tuning tuning;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        cp.snap = h->map;
+        if (!cp.snap) cp.snap = h->map;  // (a snapshot set by the caller stays: prepare_export_layers runs its families on one)
         maxRadius = std::max(maxRadius, std::max(params->searchRadius, h->maxLegSearchRadius));
         tuning = h->tuning;
     }
@@ -552,7 +552,7 @@ int prepare_foothold_map(fpe_engine* h, const fpe_params* params, const int32_t 
     fpe::Tuning tuning;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        cp.snap = h->map;
+        if (!cp.snap) cp.snap = h->map;  // (as prepare_call)
         tuning = h->tuning;
     }
     if (!cp.snap) return fail(FPE_E_NO_MAP, "no map uploaded");
@@ -719,6 +719,139 @@ int stage_products(CallCtx& cx, const HostProduct (&prod)[N], Launch launch) {
     for (int k = 0; k < N; ++k)
         if (len[k] && !pinned[k]) std::memcpy(prod[k].dst, cx.pinned + off[k], len[k]);
     return FPE_OK;
+}
+
+// fpe_export_layers*: what a layer id reads — its dense family, that family's canonical product and how layers_export_kernel
+// reads it (fpe_launch.hpp).  One line per FPE_LAYER_* id of include/fpe.h, in id order.
+enum ExportFamily { kFamFootmap, kFamSnap, kFamCentroid, kExportFamilies };
+enum ExportProduct { kXpFlags, kXpHeight, kXpSnapOffset, kXpSnapSource, kXpSnapZ, kXpCenCode, kXpCenOffset, kXpCenZ, kExportProducts };
+struct ExportLayerDef {
+    int family, product, kind;
+};
+constexpr ExportLayerDef kExportLayers[FPE_LAYER_COUNT] = {
+    {kFamFootmap, kXpFlags, fpe::kLayerSrcU8},             // FPE_LAYER_FOOTHOLD_FLAGS
+    {kFamFootmap, kXpHeight, fpe::kLayerSrcF32},           // FPE_LAYER_FOOTHOLD_HEIGHT
+    {kFamSnap, kXpSnapOffset, fpe::kLayerSrcI8Pair0},      // FPE_LAYER_SNAP_DI
+    {kFamSnap, kXpSnapOffset, fpe::kLayerSrcI8Pair1},      // FPE_LAYER_SNAP_DJ
+    {kFamSnap, kXpSnapSource, fpe::kLayerSrcU8},           // FPE_LAYER_SNAP_SOURCE
+    {kFamSnap, kXpSnapZ, fpe::kLayerSrcF32},               // FPE_LAYER_SNAP_Z
+    {kFamCentroid, kXpCenCode, fpe::kLayerSrcU8},          // FPE_LAYER_CENTROID_CODE
+    {kFamCentroid, kXpCenOffset, fpe::kLayerSrcI8Pair0},   // FPE_LAYER_CENTROID_DI
+    {kFamCentroid, kXpCenOffset, fpe::kLayerSrcI8Pair1},   // FPE_LAYER_CENTROID_DJ
+    {kFamCentroid, kXpCenZ, fpe::kLayerSrcF32},            // FPE_LAYER_CENTROID_Z
+};
+constexpr size_t kExportProductBytes[kExportProducts] = {1, 4, 2, 1, 4, 1, 2, 4};  // per cell of the region
+
+// A prepared export call.  One snapshot; a CallPlan per family, because the families derive different plan constants from the
+// same parameters (the snap map sizes its tile for its own radius, the centroid map for the engine's leg bound, the foothold map
+// for params->searchRadius) and every product has to be exactly its own dense call's.  The foothold map and the snap map ask for the
+// same threshold pair: the second acquire_mask finds the first one's planes.
+struct ExportPlan {
+    CallPlan cp[kExportFamilies];
+    bool prepared[kExportFamilies] = {};  // the family is requested and its prepare succeeded
+    bool want[kExportProducts] = {};
+    fpe::FootmapRoi r{};
+    fpe::SnapConsts sc{};
+    bool bitPath = false;
+    fpe::CmapConsts cc{};
+    fpe::LayersArgs args{};  // everything but the slots' pointers
+};
+
+// Every check of an export call, then the prepares of the families requested on ONE snapshot; `stream` ordered as they order it.
+// The centroid map (no bit planes) goes first and the foothold map last, so that as few refusals as possible come behind a queued
+// build of the planes; xp.prepared tells the device form which plans a refusal leaves to mark.
+int prepare_export_layers(fpe_engine* h, const fpe_params* params, const int32_t roi[4], const fpe_layer_layout* layout,
+                          const fpe_layer_request* req, ExportPlan& xp, hipStream_t stream) {
+    if (!h || !params || !req) return fail(FPE_E_INVALID_ARG, "null handle, params or request");
+    if (req->n_layers < 1 || req->n_layers > FPE_LAYER_COUNT) return fail(FPE_E_INVALID_ARG, "n_layers must be 1..FPE_LAYER_COUNT");
+    bool need[kExportFamilies] = {};
+    uint32_t seen = 0;
+    for (int k = 0; k < req->n_layers; ++k) {
+        const int32_t id = req->layer[k];
+        if (id < 0 || id >= FPE_LAYER_COUNT) return fail(FPE_E_INVALID_ARG, "unknown layer id");
+        if ((seen >> id) & 1u) return fail(FPE_E_INVALID_ARG, "layer requested twice");
+        seen |= 1u << id;
+        if (!req->dst[k]) return fail(FPE_E_INVALID_ARG, "null layer destination");
+        need[kExportLayers[id].family] = true;
+        xp.want[kExportLayers[id].product] = true;
+    }
+    const int32_t si = layout ? layout->start_index[0] : 0, sj = layout ? layout->start_index[1] : 0;
+    const int32_t order = layout ? layout->storage_order : 1;
+    if (order != 0 && order != 1) return fail(FPE_E_INVALID_ARG, "storage_order must be 0 (column-major) or 1 (row-major)");
+    std::shared_ptr<MapSnapshot> snap;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        snap = h->map;
+    }
+    if (!snap) return fail(FPE_E_NO_MAP, "no map uploaded");
+    const fpe::MapGeom& g = snap->g;
+    if (si < 0 || si >= g.rows || sj < 0 || sj >= g.cols) return fail(FPE_E_INVALID_ARG, "start index outside the map");
+    int rc = resolve_roi(roi, g, xp.r);
+    if (rc != FPE_OK) return rc;
+    if (need[kFamCentroid]) {
+        xp.cp[kFamCentroid].snap = snap;
+        rc = prepare_centroid_map(h, params, roi, req->centroid_search_radius, true, xp.cp[kFamCentroid], xp.r, xp.cc, stream);
+        if (rc != FPE_OK) return rc;
+        xp.prepared[kFamCentroid] = true;
+    }
+    if (need[kFamSnap]) {
+        xp.cp[kFamSnap].snap = snap;
+        rc = prepare_foothold_snap(h, params, roi, req->snap_search_radius, req->snap_polygon_kind, true, xp.want[kXpSnapZ], xp.cp[kFamSnap],
+                                   xp.r, xp.sc, xp.bitPath, stream);
+        if (rc != FPE_OK) return rc;
+        xp.prepared[kFamSnap] = true;
+    }
+    if (need[kFamFootmap]) {
+        xp.cp[kFamFootmap].snap = snap;
+        rc = prepare_foothold_map(h, params, roi, true, xp.cp[kFamFootmap], xp.r, stream);
+        if (rc != FPE_OK) return rc;
+        xp.prepared[kFamFootmap] = true;
+    }
+    fpe::LayersArgs& a = xp.args;
+    a.rows = g.rows;
+    a.cols = g.cols;
+    a.si = si;
+    a.sj = sj;
+    a.dstRowMajor = order;
+    a.nLayers = req->n_layers;
+    a.roi = xp.r;
+    return FPE_OK;
+}
+
+// Queue a prepared export call on `stream`: the canonical products the layers need in one stream-ordered block, the dense
+// families' own launches into it, then ONE launch of layers_export_kernel into d_dst[k] (device; layer req.layer[k]).
+hipError_t run_export_layers(fpe_engine* h, const ExportPlan& xp, const fpe_layer_request& req, float* const* d_dst, hipStream_t stream) {
+    const size_t n = static_cast<size_t>(xp.r.nr) * xp.r.nc;
+    size_t off[kExportProducts], end = 0;
+    for (int p = 0; p < kExportProducts; ++p) {
+        off[p] = end;
+        if (xp.want[p]) end = align256(end + n * kExportProductBytes[p]);
+    }
+    void* block = nullptr;
+    hipError_t e = hipMallocAsync(&block, end, stream);
+    if (e != hipSuccess) return e;
+    unsigned char* base = static_cast<unsigned char*>(block);
+    auto at = [&](int p) { return xp.want[p] ? base + off[p] : nullptr; };
+    if (xp.prepared[kFamFootmap]) {
+        const CallPlan& cp = xp.cp[kFamFootmap];
+        e = fpe::launch_foothold_map(dev_map(*cp.snap), cp.bits, cp.pc, xp.r, at(kXpFlags), reinterpret_cast<float*>(at(kXpHeight)), stream);
+    }
+    if (e == hipSuccess && xp.prepared[kFamSnap])
+        e = run_foothold_snap(h, xp.cp[kFamSnap], xp.r, xp.sc, xp.bitPath, reinterpret_cast<int8_t*>(at(kXpSnapOffset)), at(kXpSnapSource),
+                              reinterpret_cast<float*>(at(kXpSnapZ)), stream);
+    if (e == hipSuccess && xp.prepared[kFamCentroid])
+        e = run_centroid_map(xp.cp[kFamCentroid], xp.r, xp.cc, at(kXpCenCode), reinterpret_cast<int8_t*>(at(kXpCenOffset)),
+                             reinterpret_cast<float*>(at(kXpCenZ)), stream);
+    if (e == hipSuccess) {
+        fpe::LayersArgs a = xp.args;
+        for (int k = 0; k < a.nLayers; ++k) {
+            const ExportLayerDef& d = kExportLayers[req.layer[k]];
+            a.slot[k] = fpe::LayerSlot{at(d.product), d_dst[k], d.kind, 0};
+        }
+        e = fpe::launch_layers_export(a, stream);
+    }
+    const hipError_t f = hipFreeAsync(block, stream);
+    return e != hipSuccess ? e : f;
 }
 
 // The host form of an open-loop query call behind its per-query checks: n queries up, `launch(cp, d_queries, d_out, stream)`,
@@ -1835,6 +1968,39 @@ int fpe_centroid_map(fpe_handle h, const fpe_params* params, const int32_t roi[4
     const HostProduct prod[3] = {{out->code, n}, {out->offset, 2 * n}, {out->z, n * sizeof(float)}};
     return stage_products(cx, prod, [&](unsigned char* const* d, hipStream_t s) {
         return run_centroid_map(cp, r, cc, d[0], reinterpret_cast<int8_t*>(d[1]), reinterpret_cast<float*>(d[2]), s);
+    });
+}
+
+int fpe_export_layers_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_layer_layout* layout,
+                             const fpe_layer_request* d_request, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ExportPlan xp;
+    const int rc = prepare_export_layers(h, params, roi, layout, d_request, xp, st);
+    // (also behind a refusal that follows a family's prepare: that prepare may have queued the planes' build on `stream`)
+    for (int f = 0; f < kExportFamilies; ++f)
+        if (xp.prepared[f]) mark_async_launch(xp.cp[f]);
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(run_export_layers(h, xp, *d_request, d_request->dst, st));
+    return FPE_OK;
+}
+
+int fpe_export_layers(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_layer_layout* layout,
+                      const fpe_layer_request* request) {
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle, params or request");
+    ExportPlan xp;  // ahead of the lease: the stream is waited for before the snapshot and the planes are released (HostCall)
+    HostCall hc(h);
+    CallCtx& cx = hc.cx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(0));  // the stream
+    const int rc = prepare_export_layers(h, params, roi, layout, request, xp, cx.stream);
+    if (rc != FPE_OK) return rc;
+    const size_t bytes = static_cast<size_t>(xp.args.rows) * xp.args.cols * sizeof(float);
+    HostProduct prod[FPE_LAYER_COUNT] = {};
+    for (int k = 0; k < request->n_layers; ++k) prod[k] = HostProduct{request->dst[k], bytes};
+    return stage_products(cx, prod, [&](unsigned char* const* d, hipStream_t s) {
+        float* d_dst[FPE_LAYER_COUNT];
+        for (int k = 0; k < FPE_LAYER_COUNT; ++k) d_dst[k] = reinterpret_cast<float*>(d[k]);
+        return run_export_layers(h, xp, *request, d_dst, s);
     });
 }
 

@@ -2111,6 +2111,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_centroidmap.hpp"
 // ---- part seven: ranking a planned batch (fpe_plan_rank*) ------------------------------------------------------
 #include "fpe_rank.hpp"
+// ---- part eight: the dense maps as grid_map message layers (fpe_export_layers*) --------------------------------
+#include "fpe_layers.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<16>),

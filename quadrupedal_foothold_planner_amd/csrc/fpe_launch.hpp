@@ -93,4 +93,27 @@ hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int
                        const fpe_plan_out& bestProducts, hipStream_t stream);
 hipError_t set_max_lds_rank();
 
+// ---- the dense maps as message layers (fpe_layers.hpp) -------------------------------------------------------
+// What a layer reads: a canonical product of the region, element (r, c) at r * nc + c (times 2, plus the component, for the
+// interleaved int8 offset pairs)
+enum LayerSrcKind : int32_t { kLayerSrcU8 = 0, kLayerSrcI8Pair0 = 1, kLayerSrcI8Pair1 = 2, kLayerSrcF32 = 3 };
+struct LayerSlot {
+    const void* src;  // the canonical product (device)
+    float* dst;       // rows * cols floats of the whole map (device)
+    int32_t kind;     // LayerSrcKind
+    int32_t pad;
+};
+// The argument block of layers_export_kernel: the whole map, the destination layout, the region, one slot per layer
+struct LayersArgs {
+    int32_t rows, cols;    // the whole map
+    int32_t si, sj;        // start index of the destination buffers: 0 <= si < rows, 0 <= sj < cols
+    int32_t dstRowMajor;   // 1 row-major, 0 column-major destinations
+    int32_t nLayers;       // slots used
+    int32_t vec16;         // set by launch_layers_export: the 16-byte store path holds for every destination
+    int32_t pad;
+    FootmapRoi roi;
+    LayerSlot slot[FPE_LAYER_COUNT];
+};
+hipError_t launch_layers_export(const LayersArgs& a, hipStream_t stream);
+
 }  // namespace fpe

@@ -149,6 +149,35 @@ public:
         return true;
     }
 
+    // The dense maps (fpe_foothold_map / fpe_foothold_snap / fpe_centroid_map) republished as layers of a grid_map laid out like
+    // `like` — the map that was uploaded, or any map of its size: its getStartIndex() and Eigen's column-major storage — computed
+    // and laid out on the device: NaN outside `roi` (canonical {row0, col0, n_rows, n_cols}; nullptr = the whole map).  The node
+    // add()s one layer per id to its outgoing map and passes map[name].data(): dst[k] receives layer layerIds[k] (FPE_LAYER_*),
+    // getSize()(0) * getSize()(1) floats.  false when `like` is not of the engine's map size (the destinations are sized by it) or
+    // the engine refuses the call (lastError()).
+    bool exportLayers(const grid_map::GridMap& like, const fpe_params& params, const std::vector<int32_t>& layerIds,
+                      const std::vector<float*>& dst, const int32_t* roi = nullptr, float snapSearchRadius = 0.0f,
+                      int32_t snapPolygonKind = 0, float centroidSearchRadius = 0.0f) {
+        if (layerIds.empty() || layerIds.size() > FPE_LAYER_COUNT || dst.size() != layerIds.size()) return false;
+        fpe_map_desc cur;
+        if (fpe_map_info(h_, &cur) != FPE_OK || cur.rows != like.getSize()(0) || cur.cols != like.getSize()(1)) return false;
+        fpe_layer_layout layout;
+        layout.start_index[0] = like.getStartIndex()(0);
+        layout.start_index[1] = like.getStartIndex()(1);
+        layout.storage_order = 0;  // Eigen column-major
+        layout.reserved = 0;
+        fpe_layer_request req = {};
+        req.n_layers = static_cast<int32_t>(layerIds.size());
+        for (size_t k = 0; k < layerIds.size(); ++k) {
+            req.layer[k] = layerIds[k];
+            req.dst[k] = dst[k];
+        }
+        req.snap_search_radius = snapSearchRadius;
+        req.snap_polygon_kind = snapPolygonKind;
+        req.centroid_search_radius = centroidSearchRadius;
+        return fpe_export_layers(h_, &params, roi, &layout, &req) == FPE_OK;
+    }
+
     // The handler's gate failed in a way the call did not refuse by itself: under fpe_set_tuning("service_opt_gate", 0 | 1) the
     // engine answers FPE_OK although the opt track's chain stopped at its gate (kind FPE_GATE_BUILD_DEFINED, opt products
     // empty).  The reference's handler returns false at that gate (cpp:931-934): so does this adapter, whatever the mode.

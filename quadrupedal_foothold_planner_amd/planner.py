@@ -425,6 +425,65 @@ class FootholdPlanner:
         self._check(self._lib.fpe_centroid_map_device(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0), C.byref(co),
                                                       C.c_void_p(stream or 0)))
 
+    # ---- the dense maps as grid_map message layers (fpe_export_layers*) ----------------------------------------------------
+    def _layer_request(self, names, dsts, snap_search_radius, snap_polygon, centroid_search_radius):
+        """fpe_layer_request for layer names and their destinations (addresses); unknown names raise before the library is called."""
+        names = list(names)
+        unknown = [n for n in names if n not in _capi.LAYER_NAMES]
+        if unknown:
+            raise ValueError(f"unknown layers {sorted(unknown)}")
+        if len(names) > _capi.LAYER_COUNT:
+            raise ValueError(f"at most {_capi.LAYER_COUNT} layers, each once")
+        rq = _capi.LayerRequest()
+        rq.n_layers = len(names)
+        for k, (n, d) in enumerate(zip(names, dsts)):
+            rq.layer[k] = _capi.LAYER_NAMES.index(n)
+            rq.dst[k] = d
+        rq.snap_search_radius = float(snap_search_radius or 0.0)
+        rq.snap_polygon_kind = self._polygon_kind(snap_polygon)
+        rq.centroid_search_radius = float(centroid_search_radius or 0.0)
+        return rq
+
+    @staticmethod
+    def _layer_layout(start_index, storage_order):
+        if storage_order not in ("col", "row"):
+            raise ValueError(f"unknown storage order {storage_order!r}")
+        return _capi.LayerLayout((C.c_int32 * 2)(*map(int, start_index)), 1 if storage_order == "row" else 0, 0)
+
+    def export_layers(self, layers=_capi.LAYER_NAMES, roi=None, start_index=(0, 0), storage_order="col", snap_search_radius=None,
+                      snap_polygon="rectangle", centroid_search_radius=None, pinned=False, out=None):
+        """fpe_export_layers on the current map: {name: float32 array of the WHOLE map} for the requested layers
+        (_capi.LAYER_NAMES), in the layout of the message being filled — shape (cols, rows) for storage_order "col" (the
+        grid_map_msgs column-major buffer), (rows, cols) for "row", rotated by `start_index`, NaN outside `roi` — which is what
+        gridmapCallback accepts with the same start_index and storage_order.  pinned: the arrays come from host_array (written by
+        DMA, alive until close()); out: {name: C-contiguous float32 array of that shape} to fill instead of fresh arrays."""
+        layers = list(layers)
+        unknown = [n for n in layers if n not in _capi.LAYER_NAMES]
+        if unknown:
+            raise ValueError(f"unknown layers {sorted(unknown)}")
+        lay = self._layer_layout(start_index, storage_order)
+        d = MapDesc()
+        self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
+        shape = (d.rows, d.cols) if storage_order == "row" else (d.cols, d.rows)
+        if out is None:
+            out = {n: (self.host_array(shape, np.float32) if pinned else np.empty(shape, np.float32)) for n in layers}
+        for n in layers:
+            a = out[n]
+            if a.dtype != np.float32 or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError(f"layer {n!r}: the destination must be a C-contiguous float32 array of shape {shape}")
+        rq = self._layer_request(layers, [out[n].ctypes.data for n in layers], snap_search_radius, snap_polygon, centroid_search_radius)
+        self._check(self._lib.fpe_export_layers(self._h, ptr(self.params), ptr(self._roi(roi)), C.byref(lay), C.byref(rq)))
+        return {n: out[n] for n in layers}
+
+    def export_layers_device(self, d_layer_ptrs, roi=None, start_index=(0, 0), storage_order="col", snap_search_radius=None,
+                             snap_polygon="rectangle", centroid_search_radius=None, stream=0):
+        """Device form: d_layer_ptrs = {name: DEVICE pointer to rows * cols floats}, asynchronous on `stream`."""
+        names = list(d_layer_ptrs)
+        rq = self._layer_request(names, [int(d_layer_ptrs[n]) for n in names], snap_search_radius, snap_polygon, centroid_search_radius)
+        lay = self._layer_layout(start_index, storage_order)
+        self._check(self._lib.fpe_export_layers_device(self._h, ptr(self.params), ptr(self._roi(roi)), C.byref(lay), C.byref(rq),
+                                                       C.c_void_p(stream or 0)))
+
     # ---- the service (globalFootholdPlan, cpp:539-1602): response content for one pose ---------------------
     @staticmethod
     def _msg(m):
