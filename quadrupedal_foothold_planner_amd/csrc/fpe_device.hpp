@@ -31,7 +31,7 @@ struct SpiralLut {
     // plus one more group of 32: the 8-lane bit-window kernels read four consecutive entries per lane and round (uint4)
     const uint32_t* packed;
     // The first sixteen ranks (ring 0, ring 1, seven cells of ring 2: all within two rows / columns of the centre) by ROW, for
-    // the 3x3-only kernels' LDS-free first rounds (fpe_bits.hpp::leg_fast8m): words 0-4 = row offsets di = -2..2, five 5-bit
+    // the 3x3-only kernels' LDS-free first rounds (fpe_bits_lane8.hpp::leg_fast8m): words 0-4 = row offsets di = -2..2, five 5-bit
     // fields each (column offset dj = -2..2 -> the rank of (di, dj), 31 = not among the first sixteen); words 6-7 / 8-9 = di + 2
     // / dj + 2 of rank q in the 4-bit field q of a 64-bit word.  Built by fpe_create from the same table.
     const uint32_t* fast16;
@@ -106,7 +106,7 @@ constexpr int kMaxHW = 4;
 // The plan constants of the 3x3-only 8-lane bit-window kernels (plan_bits_kernel<NRL, true, kProd>) — what their prologue, the
 // y-entry fill, the fast leg search, the flush and the rare branches read, and nothing else: those kernels are launched for
 // one-cell foot discs only (nFoot == 1: no offset table, no row-interval erosion) and never stage an LDS tile.  Filled per
-// launch from the call's PlanConsts (plan_mid_consts).  How the kernels read it (fpe_bits.hpp):
+// launch from the call's PlanConsts (plan_mid_consts).  How the kernels read it (fpe_bits_lane8.hpp):
 //   winH                  every gait cycle, from the by-value parameter: a scalar register for the whole chain
 //   rf, rf2, cornerEps, drift   operands of vector f64 arithmetic: parked in vector registers once per wavefront
 //   h                     the flush, every eighth cycle: loaded from the argument segment there (mid_cold_args)
@@ -157,7 +157,7 @@ inline PlanMidConsts plan_mid_consts(const PlanConsts& pc) {
 }
 
 // Bit planes of one map snapshot for one (defaultFootholdThreshold, candidateFootholdThreshold) pair
-// (fpe_bits.hpp).  One uint4 per 32 columns of a row: x = D  (trav < thrDefault, raw compare: NaN 0, -inf 1),
+// (fpe_bits_window.hpp).  One uint4 per 32 columns of a row: x = D  (trav < thrDefault, raw compare: NaN 0, -inf 1),
 // y = Df (finite && trav < thrDefault), z = C (finite && trav < thrCandidate), w = F (finite); bit b of a word =
 // column 32 * word + b.  Tiled: the groups of 8 consecutive rows x one word are one 128-byte line (a search window
 // is a few dozen rows of one or two words: row-major planes spend a line per window row, 32-64 bytes of it used);

@@ -10,8 +10,9 @@
 //   G = 4 / 16 and the four-wavefronts-per-pose form of G = 64 exist for measurement (fpe_set_tuning "plan_group").
 // Direct kernels (this file's first part) read the f32 layers themselves: the default disc and the centroid
 // rectangle straight through L1/L2, the spiral window of large foot discs staged into LDS as flag bytes.
-// Bit-window kernels (second part, fpe_bits.hpp) read per-snapshot bit planes instead — one 32/64/96-bit row mask
-// per window row and lane — and touch the f32 elevation layer only for the mean heights.
+// Bit-window kernels (second part: fpe_bits.hpp and the fpe_bits_*.hpp it includes) read per-snapshot bit planes
+// instead — one 32/64/96-bit row mask per window row and lane — and touch the f32 elevation layer only for the mean
+// heights.
 // Spiral candidates: lane = SpiralIterator rank, lowest set ballot bit = argmin of rank.
 // No MFMA: nothing here is a contraction.
 //
@@ -730,9 +731,9 @@ struct DiscLoads {
 // hot region: with both forms present the compiler's s_waitcnt insertion has to assume those loads pending at the
 // join and stalls the 3x3 form on the row loads issued just before it (measured: 56.2 -> 53.7 us per launch).
 // dy2tab (optional, 3x3 form only): (cell_pos(baseY, res, bb.j0 + k) - cy)^2 for k = 0..2, precomputed by the caller —
-// the y side of a leg's geometry does not depend on the chain (fpe_bits.hpp, YEntry).
+// the y side of a leg's geometry does not depend on the chain (fpe_bits_window.hpp, YEntry).
 // kLoad = false: membership only (DiscLoads::vis / pipelined) — the caller defers the heights and reads the elevations
-// itself later (one-wavefront-per-pose bit-window kernels, fpe_bits.hpp::flush_seqrec).
+// itself later (one-wavefront-per-pose bit-window kernels, fpe_bits_seq.hpp::flush_seqrec2).
 template <int G, bool kCheck, bool kMid = false, bool kLoad = true>
 __device__ __forceinline__ void disc_issue(const DevMap& m, const PlanConsts& pc, double cx, double cy, const BBox& bb,
                                            const Grp<G>& g, DiscLoads& d, const double* dy2tab = nullptr) {
@@ -1895,7 +1896,7 @@ __global__ __launch_bounds__(256) void centroid_legs_kernel(DevMap m, PlanConsts
 // LDS so that both the column-major reads and the row-major writes are coalesced (round 4: 32 x 32 tiles moved 128 bytes
 // per wavefront instruction and 3.95 TB/s on two 4000 x 4000 layers; 64 x 64 with sixteen loads in flight per thread 4.6,
 // 16-byte stores where the destination's rows allow them 4.7 — the plain wrapped copy of a row-major source runs at 4.5).
-// Bit planes of the canonical layer while it passes through (round 5; SURVEY 8(f) N1 + the planes of fpe_bits.hpp): with
+// Bit planes of the canonical layer while it passes through (round 5; SURVEY 8(f) N1 + the planes of fpe_bits_window.hpp): with
 // `planes.words` set, every wavefront ballots the 64 columns of a destination row it holds anyway — lane = column — and lanes 0 / 1
 // store the row's two word groups {D, Df, C, F}: the separate pass of build_bitmap_kernel over the traversability layer (13 us for
 // 4000 x 4000) is gone.  Same predicates, same layout (bit_group_index) as build_bitmap_kernel; the buffer's padding is zeroed by the
@@ -2097,7 +2098,7 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
     return hipGetLastError();
 }
 
-// ---- part two of this translation unit: the bit-window kernels ---------------------------------------------
+// ---- part two of this translation unit: the bit-window kernels (fpe_bits_window / _lane8 / _seq.hpp through it) ----
 #include "fpe_bits.hpp"
 // ---- part three: the producer's filters (elevation -> traversability) ----------------------------------------
 #include "fpe_filters.hpp"
@@ -2115,42 +2116,27 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_layers.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(planBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<8>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(planBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<8, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(planBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(planBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_chained_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(planBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_sequential_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(planBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_legs_kernel<8>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_legs_kernel<8, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_legs_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(centroid_legs_kernel<8>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(centroid_legs_kernel<8, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(centroid_legs_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(searchBytes));
-    if (e != hipSuccess) return e;
+    const struct {
+        const void* kernel;
+        size_t bytes;
+    } limits[] = {
+        {reinterpret_cast<const void*>(plan_chained_kernel<16>), planBytes},
+        {reinterpret_cast<const void*>(plan_chained_kernel<8>), planBytes},
+        {reinterpret_cast<const void*>(plan_chained_kernel<8, true>), planBytes},
+        {reinterpret_cast<const void*>(plan_chained_kernel<4>), planBytes},
+        {reinterpret_cast<const void*>(plan_chained_kernel<64>), planBytes},
+        {reinterpret_cast<const void*>(plan_sequential_kernel), planBytes},
+        {reinterpret_cast<const void*>(search_legs_kernel<8>), searchBytes},
+        {reinterpret_cast<const void*>(search_legs_kernel<8, true>), searchBytes},
+        {reinterpret_cast<const void*>(search_legs_kernel<64>), searchBytes},
+        {reinterpret_cast<const void*>(centroid_legs_kernel<8>), searchBytes},
+        {reinterpret_cast<const void*>(centroid_legs_kernel<8, true>), searchBytes},
+        {reinterpret_cast<const void*>(centroid_legs_kernel<64>), searchBytes},
+    };
+    for (const auto& l : limits) {
+        const hipError_t e = hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(l.bytes));
+        if (e != hipSuccess) return e;
+    }
     return set_max_lds_centroid_map(searchBytes);
 }
 

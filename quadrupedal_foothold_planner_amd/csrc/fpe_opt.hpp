@@ -16,7 +16,7 @@
 //   * positions and mean heights taken from gaitMap_ (its own geometry: a CircleIterator on a submap is clamped to the
 //     submap and measures distances to the SUBMAP's cell centres), the commit with the nominal track's validity.
 // Everything is the reference's f64 expression order (-ffp-contract=off); this is a secondary product, written for
-// exactness first: the hot path is fpe_bits.hpp.
+// exactness first: the hot path is fpe_bits.hpp and its pieces.
 #pragma once
 
 namespace {

@@ -1,4 +1,4 @@
-"""The argument block of the 3x3-only 8-lane kernels (plan_bits_kernel<NRL, true, kProd>, csrc/fpe_bits.hpp): those kernels
+"""The argument block of the 3x3-only 8-lane kernels (plan_bits_kernel<NRL, true, kProd>, csrc/fpe_bits_lane8.hpp): those kernels
 take PlanMidConsts, a cut of the call's PlanConsts, and read part of it again from the argument segment inside the cycle loop
 (the flush every eighth cycle, the general leg search).  A field that is dropped, mis-copied or read at a wrong offset shows
 where it is used, so the cases go there: batch edges of the two-pose wavefront, cycle counts around the eight-cycle flush,
