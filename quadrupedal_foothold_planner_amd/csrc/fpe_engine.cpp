@@ -1627,8 +1627,15 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
         const unsigned char* okDev = dp + oOk;
         uint32_t* doneDev = nullptr;
         if (r.speculate && r.pollDone) {
-            r.doneValue = ++cx.doneSeq ? cx.doneSeq : ++cx.doneSeq;  // (never 0, never the value the word holds from the last call)
+            r.doneValue = ++cx.doneSeq ? cx.doneSeq : ++cx.doneSeq;  // (never 0)
             doneDev = reinterpret_cast<uint32_t*>(dp + L.oDone);
+            // The counter alone says nothing about what the word holds NOW: L.oDone moves with n_cycles and the product set, and
+            // the same arena takes the poses, queries and staged products of every other host-form call, and is fresh,
+            // uninitialised memory after cx.reserve grew it.  Cleared here, before the chain is queued, the word can turn into
+            // doneValue by the chain's own store only (nothing is in flight on this context: the last call synchronised, or its
+            // chain's word was seen, before it returned).
+            *reinterpret_cast<volatile uint32_t*>(hp + L.oDone) = 0;
+            std::atomic_thread_fence(std::memory_order_release);
         }
         if (r.speculate) {
             std::memset(hp + L.oSpec, 1, nCyc);

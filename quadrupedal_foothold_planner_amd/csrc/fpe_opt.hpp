@@ -1039,10 +1039,16 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(2))) voi
         out.rows_after[2 * static_cast<size_t>(b) + 1] = rhRow;
     }
     // One-pose service call (round 6): wavefront 0 — the only one that stores products — says so in the caller's host-mapped arena
-    // with a system-scope RELEASE store behind its product stores; the host polls that word instead of waiting for the stream's
-    // completion signal (fpe_engine.cpp, plan_host: -4 us of a ~100 us call).  (Measured: an additional __threadfence_system, or a
-    // relaxed store behind s_waitcnt 0, end at the same time — the ordering is not what the word costs.)
-    if (doneFlag && lane == 0) __hip_atomic_store(doneFlag, doneValue, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    // behind its product stores; the host polls that word instead of waiting for the stream's completion signal (fpe_engine.cpp,
+    // plan_host: -4 us of a ~100 us call).  The products are stored by several lanes (the footholds by lanes 0 / 16 / 32 / 48), and
+    // a release by lane 0 orders lane 0's stores only: EVERY lane executes a system-scope release fence, then lane 0 stores the
+    // word, relaxed — behind the fence in program order, and the lanes of a wavefront run in lockstep, so behind every lane's
+    // fence.  (Measured, round 6: the fence, or a relaxed store behind s_waitcnt 0, end at the same time as a release store by
+    // lane 0 alone — the ordering is not what the word costs.)
+    if (doneFlag) {  // (uniform: a kernel argument)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+        if (lane == 0) __hip_atomic_store(doneFlag, doneValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 static_assert(kernargs_mirror<decltype(opt_track_kernel<1>)>(
                   {offsetof(OptKernArgs, m), offsetof(OptKernArgs, pc), offsetof(OptKernArgs, oc), offsetof(OptKernArgs, poses),

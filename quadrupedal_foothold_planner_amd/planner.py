@@ -526,7 +526,7 @@ class FootholdPlanner:
                 m, q = np.zeros(1, dtype=GLOBAL_FOOTHOLDS_DTYPE), np.zeros(3, dtype=np.float64)
                 sv = tls.sv = (m, q, ptr(m), ptr(q), self.params, ptr(self.params),
                                m["success"], m["gait_cycles"], m["gait_cycles_succeed"], m["n_footholds"], m["footholds"][0])  # field views, made once
-            sv[1][:] = initial_position
+            sv[1][:] = np.asarray(initial_position, np.float64).reshape(3)  # (as the all_tracks path: three values or a ValueError, never a broadcast)
             rc = self._lib.fpe_plan_service(self._h, sv[5], sv[3], int(gait_cycles) & 0xFF, sv[2])
             if rc == _capi.FPE_E_SERVICE_FALSE:
                 return False  # the reference's handler returns false here (cpp:931-934): the ROS call fails
