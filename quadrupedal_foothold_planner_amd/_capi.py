@@ -1,5 +1,7 @@
-"""ctypes binding of libfpe.so (include/fpe.h).  Record layouts are numpy structured dtypes that
-mirror the C structs byte for byte; `check_layout()` asserts the sizes against the library."""
+"""ctypes binding of libfpe.so (include/fpe.h).  Every struct of the header has ONE written-out mirror here — a numpy structured
+dtype for the records that live in arrays, a ctypes.Structure for what is passed by reference, the second form derived from the
+first where both are needed — and STRUCTS names them all; PROTOTYPES holds every entry point's restype and argtypes.
+tests/test_cpu_abi.py compares size, every field's offset and size, and the field tiling of each mirror with the C compiler's."""
 import ctypes as C
 import os
 
@@ -80,8 +82,6 @@ QUERY_DTYPE = np.dtype(
      ("vx", "<f8", (MAX_POLYGON_VERTICES,)), ("vy", "<f8", (MAX_POLYGON_VERTICES,))],
     align=True,
 )
-# fpe_centroid_query: one open-loop centroid-method query (24 bytes)
-CENTROID_QUERY_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("search_radius", "<f4"), ("pad", "<i4")], align=True)
 MSG_FOOTHOLD_DTYPE = np.dtype(
     [("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("foot_id", "u1"), ("gait_cycle_id", "u1"), ("pad", "u1", (6,))],
     align=True,
@@ -197,6 +197,9 @@ class CentroidQuery(C.Structure):
     _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("search_radius", C.c_float), ("pad", C.c_int32)]
 
 
+CENTROID_QUERY_DTYPE = np.dtype(CentroidQuery)  # the array form of the same 24 bytes
+
+
 class CentroidMapOut(C.Structure):
     """fpe_centroid_map_out: products of a dense centroid-map call (any pointer may be NULL)."""
     _fields_ = [("code", C.c_void_p), ("offset", C.c_void_p), ("z", C.c_void_p)]
@@ -220,23 +223,8 @@ class LayerRequest(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-# fpe_pose_summary: what fpe_plan_rank* reduces one pose's plan to (64 bytes)
-POSE_SUMMARY_DTYPE = np.dtype(
-    [("success", "u1"), ("gait_cycles_succeed", "u1"), ("committed", "u1"), ("first_failed", "u1"), ("pose_status", "u1"),
-     ("pad", "u1", (3,)), ("n_source", "<u2", (4,)), ("cog_speed_sum", "<f8"), ("cog_speed_min", "<f8"), ("cog_speed_max", "<f8"),
-     ("feet_distance_min", "<f8"), ("feet_distance_max", "<f8"), ("deviation_sq_sum", "<f8")],
-    align=True,
-)
-RANK_PARAMS_DTYPE = np.dtype(
-    [("w_fail", "<f8"), ("w_spiral", "<f8"), ("w_none", "<f8"), ("w_deviation", "<f8"), ("w_speed_spread", "<f8"),
-     ("min_cycles", "<i4"), ("reserved", "<i4")],
-    align=True,
-)
-assert POSE_SUMMARY_DTYPE.itemsize == 64 and RANK_PARAMS_DTYPE.itemsize == 48
-
-
 class PoseSummary(C.Structure):
-    """fpe_pose_summary (include/fpe.h)."""
+    """fpe_pose_summary: what fpe_plan_rank* reduces one pose's plan to (64 bytes)."""
     _fields_ = [("success", C.c_uint8), ("gait_cycles_succeed", C.c_uint8), ("committed", C.c_uint8), ("first_failed", C.c_uint8),
                 ("pose_status", C.c_uint8), ("pad", C.c_uint8 * 3), ("n_source", C.c_uint16 * 4), ("cog_speed_sum", C.c_double),
                 ("cog_speed_min", C.c_double), ("cog_speed_max", C.c_double), ("feet_distance_min", C.c_double),
@@ -249,77 +237,95 @@ class RankParams(C.Structure):
                 ("w_speed_spread", C.c_double), ("min_cycles", C.c_int32), ("reserved", C.c_int32)]
 
 
+POSE_SUMMARY_DTYPE, RANK_PARAMS_DTYPE = np.dtype(PoseSummary), np.dtype(RankParams)  # the array forms
+
+
 class RankOut(C.Structure):
     """fpe_rank_out: outputs of a ranking call (`best` is required; anything else may be NULL)."""
     _fields_ = [("summary", C.c_void_p), ("score", C.c_void_p), ("best", C.c_void_p), ("n_class0", C.c_void_p),
                 ("best_products", PlanOut)]
 
 
-ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the ctypes structures below mirror that layout
+ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
+# every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
+STRUCTS = {
+    "fpe_params": PARAMS_DTYPE, "fpe_pose": POSE_DTYPE, "fpe_map_desc": MapDesc, "fpe_foothold": FOOTHOLD_DTYPE,
+    "fpe_centroid_foothold": CENTROID_DTYPE, "fpe_selected_foothold": SELECTED_DTYPE, "fpe_selected_packed": PACKED_DTYPE,
+    "fpe_plan_out": PlanOut, "fpe_opt_params": OPT_PARAMS_DTYPE, "fpe_opt_foothold": OPT_FOOTHOLD_DTYPE,
+    "fpe_opt_cycle": OPT_CYCLE_DTYPE, "fpe_opt_out": OptOut, "fpe_leg_query": QUERY_DTYPE, "fpe_msg_foothold": MSG_FOOTHOLD_DTYPE,
+    "fpe_global_footholds": GLOBAL_FOOTHOLDS_DTYPE, "fpe_filter_params": FilterParams, "fpe_service_gate": ServiceGate,
+    "fpe_track_report": TRACK_REPORT_DTYPE, "fpe_multi_device_io": MultiDeviceIO, "fpe_foothold_map_out": FootholdMapOut,
+    "fpe_foothold_snap_out": FootholdSnapOut, "fpe_centroid_query": CentroidQuery, "fpe_centroid_map_out": CentroidMapOut,
+    "fpe_pose_summary": PoseSummary, "fpe_rank_params": RankParams, "fpe_rank_out": RankOut, "fpe_layer_layout": LayerLayout,
+    "fpe_layer_request": LayerRequest,
+}
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
-# every symbol include/fpe.h declares (tests check the library exports each of them)
-EXPORTED_SYMBOLS = [
-    "fpe_params_yaml",
-    "fpe_params_code_defaults",
-    "fpe_create",
-    "fpe_destroy",
-    "fpe_last_error",
-    "fpe_version",
-    "fpe_abi_version",
-    "fpe_upload_map",
-    "fpe_upload_map_device",
-    "fpe_map_info",
-    "fpe_filter_params_defaults",
-    "fpe_traversability",
-    "fpe_traversability_device",
-    "fpe_set_max_leg_search_radius",
-    "fpe_set_tuning",
-    "fpe_describe_plan",
-    "fpe_host_alloc",
-    "fpe_host_free",
-    "fpe_plan",
-    "fpe_plan_device",
-    "fpe_search_legs",
-    "fpe_search_legs_device",
-    "fpe_plan_service",
-    "fpe_plan_service_ex",
-    "fpe_plan_service_report",
-    "fpe_plan_service_opt",
-    "fpe_last_service_gate",
-    "fpe_opt_params_yaml",
-    "fpe_opt_params_code_defaults",
-    "fpe_plan_opt",
-    "fpe_plan_opt_device",
-    "fpe_multi_create",
-    "fpe_multi_destroy",
-    "fpe_multi_device_count",
-    "fpe_multi_engine",
-    "fpe_multi_last_error",
-    "fpe_multi_upload_map",
-    "fpe_multi_set_tuning",
-    "fpe_multi_plan",
-    "fpe_multi_shard_range",
-    "fpe_multi_plan_device",
-    "fpe_multi_stream",
-    "fpe_multi_synchronize",
-    "fpe_foothold_map",
-    "fpe_foothold_map_device",
-    "fpe_foothold_snap",
-    "fpe_foothold_snap_device",
-    "fpe_centroid_legs",
-    "fpe_centroid_legs_device",
-    "fpe_centroid_map",
-    "fpe_centroid_map_device",
-    "fpe_rank_params_defaults",
-    "fpe_plan_rank",
-    "fpe_plan_rank_device",
-    "fpe_export_layers",
-    "fpe_export_layers_device",
-    "fpe_spiral_offsets",
-    "fpe_tile_halfwidth",
-    "fpe_algorithmic_bytes_per_foothold",
-]
+# every entry point include/fpe.h declares -> (restype, argtypes); lib() applies the table, tests check it names exactly the
+# header's functions and that the library exports each of them
+vp, cint, i32, u8, f32, f64, cstr, P = C.c_void_p, C.c_int, C.c_int32, C.c_uint8, C.c_float, C.c_double, C.c_char_p, C.POINTER
+PROTOTYPES = {
+    "fpe_params_yaml": (cint, [vp]),
+    "fpe_params_code_defaults": (cint, [vp]),
+    "fpe_create": (cint, [cint, P(vp)]),
+    "fpe_destroy": (cint, [vp]),
+    "fpe_last_error": (cstr, [vp]),
+    "fpe_version": (cstr, []),
+    "fpe_abi_version": (cint, []),
+    "fpe_upload_map": (cint, [vp, P(MapDesc), vp, vp]),
+    "fpe_upload_map_device": (cint, [vp, P(MapDesc), vp, vp, vp]),
+    "fpe_map_info": (cint, [vp, P(MapDesc)]),
+    "fpe_filter_params_defaults": (cint, [P(FilterParams)]),
+    "fpe_traversability": (cint, [vp, P(MapDesc), P(FilterParams), vp, vp, vp]),
+    "fpe_traversability_device": (cint, [vp, P(MapDesc), P(FilterParams), vp, vp, vp, vp]),
+    "fpe_set_max_leg_search_radius": (cint, [vp, f32]),
+    "fpe_set_tuning": (cint, [vp, cstr, i32]),
+    "fpe_describe_plan": (cint, [vp, vp, cstr, i32]),
+    "fpe_host_alloc": (cint, [vp, C.c_size_t, P(vp)]),
+    "fpe_host_free": (cint, [vp, vp]),
+    "fpe_plan": (cint, [vp, vp, vp, i32, i32, P(PlanOut)]),
+    "fpe_plan_device": (cint, [vp, vp, vp, i32, i32, P(PlanOut), vp]),
+    "fpe_search_legs": (cint, [vp, vp, vp, i32, vp]),
+    "fpe_search_legs_device": (cint, [vp, vp, vp, i32, vp, vp]),
+    "fpe_plan_service": (cint, [vp, vp, vp, u8, vp]),
+    "fpe_plan_service_ex": (cint, [vp, vp, vp, u8, vp, vp, vp, vp]),
+    "fpe_plan_service_report": (cint, [vp, vp, vp, u8, vp, vp, vp, vp, vp, vp]),
+    "fpe_plan_service_opt": (cint, [vp, vp, vp, vp, u8] + [vp] * 9),
+    "fpe_last_service_gate": (cint, [vp, P(ServiceGate)]),
+    "fpe_opt_params_yaml": (cint, [vp]),
+    "fpe_opt_params_code_defaults": (cint, [vp]),
+    "fpe_plan_opt": (cint, [vp, vp, vp, vp, i32, i32, vp, P(OptOut)]),
+    "fpe_plan_opt_device": (cint, [vp, vp, vp, vp, i32, i32, vp, P(OptOut), vp]),
+    "fpe_multi_create": (cint, [vp, i32, P(vp)]),
+    "fpe_multi_destroy": (cint, [vp]),
+    "fpe_multi_device_count": (cint, [vp]),
+    "fpe_multi_engine": (vp, [vp, i32]),
+    "fpe_multi_last_error": (cstr, [vp]),
+    "fpe_multi_upload_map": (cint, [vp, P(MapDesc), vp, vp]),
+    "fpe_multi_set_tuning": (cint, [vp, cstr, i32]),
+    "fpe_multi_plan": (cint, [vp, vp, vp, i32, i32, P(PlanOut)]),
+    "fpe_multi_shard_range": (cint, [i32, i32, i32, P(i32), P(i32)]),
+    "fpe_multi_plan_device": (cint, [vp, vp, P(MultiDeviceIO), i32, i32, i32]),
+    "fpe_multi_stream": (vp, [vp, i32]),
+    "fpe_multi_synchronize": (cint, [vp]),
+    "fpe_foothold_map": (cint, [vp, vp, vp, P(FootholdMapOut)]),
+    "fpe_foothold_map_device": (cint, [vp, vp, vp, P(FootholdMapOut), vp]),
+    "fpe_foothold_snap": (cint, [vp, vp, vp, f32, i32, P(FootholdSnapOut)]),
+    "fpe_foothold_snap_device": (cint, [vp, vp, vp, f32, i32, P(FootholdSnapOut), vp]),
+    "fpe_centroid_legs": (cint, [vp, vp, vp, i32, vp]),
+    "fpe_centroid_legs_device": (cint, [vp, vp, vp, i32, vp, vp]),
+    "fpe_centroid_map": (cint, [vp, vp, vp, f32, P(CentroidMapOut)]),
+    "fpe_centroid_map_device": (cint, [vp, vp, vp, f32, P(CentroidMapOut), vp]),
+    "fpe_rank_params_defaults": (cint, [P(RankParams)]),
+    "fpe_plan_rank": (cint, [vp, vp, P(RankParams), vp, i32, i32, i32, P(RankOut)]),
+    "fpe_plan_rank_device": (cint, [vp, vp, P(RankParams), vp, i32, i32, i32, P(PlanOut), P(RankOut), vp]),
+    "fpe_export_layers": (cint, [vp, vp, vp, P(LayerLayout), P(LayerRequest)]),
+    "fpe_export_layers_device": (cint, [vp, vp, vp, P(LayerLayout), P(LayerRequest), vp]),
+    "fpe_spiral_offsets": (cint, [i32, vp, i32]),
+    "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
+    "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),
+}
+EXPORTED_SYMBOLS = list(PROTOTYPES)
 
 _lib = None
 
@@ -342,79 +348,17 @@ def lib():
         L = C.CDLL(path)
     except OSError as e:
         raise EngineUnavailable(f"cannot load {path}: {e}") from e
-    vp, i32, f32, f64 = C.c_void_p, C.c_int32, C.c_float, C.c_double
     # a library that predates a symbol of include/fpe.h (FPE_LIB pointing at an old scratch build) is "unavailable", not an
     # AttributeError out of ctypes that callers catching EngineUnavailable would not see
     missing = [name for name in EXPORTED_SYMBOLS if not hasattr(L, name)]
     if missing:
         raise EngineUnavailable(f"{path} predates include/fpe.h (ABI version {ABI_VERSION}): it does not export {', '.join(missing[:4])}"
                                 + (" ..." if len(missing) > 4 else ""))
-    L.fpe_version.restype = C.c_char_p
-    L.fpe_abi_version.restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     if L.fpe_abi_version() != ABI_VERSION:
         raise EngineUnavailable(f"libfpe.so has struct layout version {L.fpe_abi_version()}, this binding mirrors version {ABI_VERSION} of include/fpe.h")
-    L.fpe_last_error.restype = C.c_char_p
-    L.fpe_last_error.argtypes = [vp]
-    L.fpe_params_yaml.argtypes = [vp]
-    L.fpe_params_code_defaults.argtypes = [vp]
-    L.fpe_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.fpe_destroy.argtypes = [vp]
-    L.fpe_upload_map.argtypes = [vp, C.POINTER(MapDesc), vp, vp]
-    L.fpe_upload_map_device.argtypes = [vp, C.POINTER(MapDesc), vp, vp, vp]
-    L.fpe_filter_params_defaults.argtypes = [C.POINTER(FilterParams)]
-    L.fpe_traversability.argtypes = [vp, C.POINTER(MapDesc), C.POINTER(FilterParams), vp, vp, vp]
-    L.fpe_traversability_device.argtypes = [vp, C.POINTER(MapDesc), C.POINTER(FilterParams), vp, vp, vp, vp]
-    L.fpe_map_info.argtypes = [vp, C.POINTER(MapDesc)]
-    L.fpe_set_max_leg_search_radius.argtypes = [vp, f32]
-    L.fpe_set_tuning.argtypes = [vp, C.c_char_p, i32]
-    L.fpe_describe_plan.argtypes = [vp, vp, C.c_char_p, i32]
-    L.fpe_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
-    L.fpe_host_free.argtypes = [vp, vp]
-    L.fpe_plan.argtypes = [vp, vp, vp, i32, i32, C.POINTER(PlanOut)]
-    L.fpe_plan_device.argtypes = [vp, vp, vp, i32, i32, C.POINTER(PlanOut), vp]
-    L.fpe_search_legs.argtypes = [vp, vp, vp, i32, vp]
-    L.fpe_search_legs_device.argtypes = [vp, vp, vp, i32, vp, vp]
-    L.fpe_plan_service.argtypes = [vp, vp, vp, C.c_uint8, vp]
-    L.fpe_plan_service_ex.argtypes = [vp, vp, vp, C.c_uint8, vp, vp, vp, vp]
-    L.fpe_plan_service_report.argtypes = [vp, vp, vp, C.c_uint8, vp, vp, vp, vp, vp, vp]
-    L.fpe_plan_service_opt.argtypes = [vp, vp, vp, vp, C.c_uint8] + [vp] * 9
-    L.fpe_last_service_gate.argtypes = [vp, C.POINTER(ServiceGate)]
-    L.fpe_opt_params_yaml.argtypes = [vp]
-    L.fpe_opt_params_code_defaults.argtypes = [vp]
-    L.fpe_plan_opt.argtypes = [vp, vp, vp, vp, i32, i32, vp, C.POINTER(OptOut)]
-    L.fpe_plan_opt_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, C.POINTER(OptOut), vp]
-    L.fpe_multi_create.argtypes = [vp, i32, C.POINTER(vp)]
-    L.fpe_multi_destroy.argtypes = [vp]
-    L.fpe_multi_device_count.argtypes = [vp]
-    L.fpe_multi_engine.restype = vp
-    L.fpe_multi_engine.argtypes = [vp, i32]
-    L.fpe_multi_last_error.restype = C.c_char_p
-    L.fpe_multi_last_error.argtypes = [vp]
-    L.fpe_multi_upload_map.argtypes = [vp, C.POINTER(MapDesc), vp, vp]
-    L.fpe_multi_set_tuning.argtypes = [vp, C.c_char_p, i32]
-    L.fpe_multi_plan.argtypes = [vp, vp, vp, i32, i32, C.POINTER(PlanOut)]
-    L.fpe_multi_shard_range.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
-    L.fpe_multi_plan_device.argtypes = [vp, vp, C.POINTER(MultiDeviceIO), i32, i32, i32]
-    L.fpe_multi_stream.restype = vp
-    L.fpe_multi_stream.argtypes = [vp, i32]
-    L.fpe_multi_synchronize.argtypes = [vp]
-    L.fpe_foothold_map.argtypes = [vp, vp, vp, C.POINTER(FootholdMapOut)]
-    L.fpe_foothold_map_device.argtypes = [vp, vp, vp, C.POINTER(FootholdMapOut), vp]
-    L.fpe_foothold_snap.argtypes = [vp, vp, vp, f32, i32, C.POINTER(FootholdSnapOut)]
-    L.fpe_foothold_snap_device.argtypes = [vp, vp, vp, f32, i32, C.POINTER(FootholdSnapOut), vp]
-    L.fpe_centroid_legs.argtypes = [vp, vp, vp, i32, vp]
-    L.fpe_centroid_legs_device.argtypes = [vp, vp, vp, i32, vp, vp]
-    L.fpe_centroid_map.argtypes = [vp, vp, vp, f32, C.POINTER(CentroidMapOut)]
-    L.fpe_centroid_map_device.argtypes = [vp, vp, vp, f32, C.POINTER(CentroidMapOut), vp]
-    L.fpe_rank_params_defaults.argtypes = [C.POINTER(RankParams)]
-    L.fpe_plan_rank.argtypes = [vp, vp, C.POINTER(RankParams), vp, i32, i32, i32, C.POINTER(RankOut)]
-    L.fpe_plan_rank_device.argtypes = [vp, vp, C.POINTER(RankParams), vp, i32, i32, i32, C.POINTER(PlanOut), C.POINTER(RankOut), vp]
-    L.fpe_export_layers.argtypes = [vp, vp, vp, C.POINTER(LayerLayout), C.POINTER(LayerRequest)]
-    L.fpe_export_layers_device.argtypes = [vp, vp, vp, C.POINTER(LayerLayout), C.POINTER(LayerRequest), vp]
-    L.fpe_spiral_offsets.argtypes = [i32, vp, i32]
-    L.fpe_tile_halfwidth.argtypes = [f32, f32, f64]
-    L.fpe_algorithmic_bytes_per_foothold.restype = f64
-    L.fpe_algorithmic_bytes_per_foothold.argtypes = [f32, f32, f64]
     _lib = L
     return L
 

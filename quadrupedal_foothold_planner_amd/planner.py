@@ -20,8 +20,8 @@ from ._capi import (CENTROID_DTYPE, CENTROID_QUERY_DTYPE, FOOTHOLD_DTYPE, GLOBAL
 
 # products of a chained plan in the order of fpe_plan_out's fields (= the order of the engine's device arena)
 PRODUCT_ORDER = ("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status", "selected_packed")
-PRODUCT_FIELDS = {"nominal": "nominal", "centroid": "centroid", "default": "default_next", "cycle_ok": "cycle_ok", "stance": "stance",
-                  "selected": "selected", "pose_status": "pose_status", "selected_packed": "selected_packed"}
+PRODUCT_FIELDS = dict(zip(PRODUCT_ORDER, (name for name, _ in PlanOut._fields_)))  # ("default" is fpe_plan_out.default_next)
+DEFAULT_PRODUCTS = PRODUCT_ORDER[:7]  # what a plan returns when `products` is left out: everything but the 8-byte exchange record
 
 
 def product_shapes(B, n_cycles):
@@ -56,30 +56,31 @@ def make_poses(xyz, gait=0, leg_search_radius=None, leg_polygon_kind=None):
 TUNING_DEFAULTS = {"service_opt_gate": 2, "service_overlap": 1, "service_poll": 1}
 
 
-class FootholdPlanner:
-    """One engine per process per GPU."""
+def _map_desc(rows, cols, resolution, position=(0.0, 0.0), start_index=(0, 0), storage_order="row"):
+    return MapDesc(rows, cols, float(resolution), (C.c_double * 2)(*map(float, position)),
+                   (C.c_int32 * 2)(*map(int, start_index)), 1 if storage_order == "row" else 0)
 
-    def __init__(self, device_id=0, params=None):
+
+class _Handle:
+    """What an engine and a group of engines share: the handle's creation, close / __del__, and the status check.  A subclass names
+    its three entry points."""
+    _CREATE = _DESTROY = _LAST_ERROR = None
+
+    def _create(self, *args, params=None):
         self._lib = _capi.lib()
         self._h = C.c_void_p()
-        rc = self._lib.fpe_create(int(device_id), C.byref(self._h))
+        rc = getattr(self._lib, self._CREATE)(*args, C.byref(self._h))
         if rc != _capi.FPE_OK:
-            msg = self._lib.fpe_last_error(None).decode()
+            msg = getattr(self._lib, self._LAST_ERROR)(None).decode()
             self._h = None
             if rc == _capi.FPE_E_NO_DEVICE:
-                raise EngineUnavailable(f"fpe_create failed: {msg} (the engine has no CPU fallback)")
+                raise EngineUnavailable(f"{self._CREATE} failed: {msg} (the engine has no CPU fallback)")
             raise FpeError(rc, msg)
         self.params = _capi.params_yaml() if params is None else np.array(params, dtype=PARAMS_DTYPE).reshape(1)
-        self.opt_params = _capi.opt_params_yaml()  # nlopt/* of the yaml (SURVEY §8(f) N4)
-        self.device_id = int(device_id)
-        self._tuning = {}  # last value set per knob (tuning() restores these, not zeros)
 
     def close(self):
         if getattr(self, "_h", None):
-            for p in getattr(self, "_pinned", []):  # arrays from host_array() must not be used after close()
-                self._lib.fpe_host_free(self._h, p)
-            self._pinned = []
-            self._lib.fpe_destroy(self._h)
+            getattr(self._lib, self._DESTROY)(self._h)
             self._h = None
 
     def __del__(self):
@@ -90,7 +91,25 @@ class FootholdPlanner:
 
     def _check(self, rc):
         if rc != _capi.FPE_OK:
-            raise FpeError(rc, self._lib.fpe_last_error(self._h).decode())
+            raise FpeError(rc, getattr(self._lib, self._LAST_ERROR)(self._h).decode())
+
+
+class FootholdPlanner(_Handle):
+    """One engine per process per GPU."""
+    _CREATE, _DESTROY, _LAST_ERROR = "fpe_create", "fpe_destroy", "fpe_last_error"
+
+    def __init__(self, device_id=0, params=None):
+        self._create(int(device_id), params=params)
+        self.opt_params = _capi.opt_params_yaml()  # nlopt/* of the yaml (SURVEY §8(f) N4)
+        self.device_id = int(device_id)
+        self._tuning = {}  # last value set per knob (tuning() restores these, not zeros)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for p in getattr(self, "_pinned", []):  # arrays from host_array() must not be used after close()
+                self._lib.fpe_host_free(self._h, p)
+            self._pinned = []
+        super().close()
 
     # ---- map ingest (gridmapCallback, cpp:504-536) -------------------------------------------------
     def gridmapCallback(self, traversability, elevation, resolution, position=(0.0, 0.0), start_index=(0, 0),
@@ -103,15 +122,13 @@ class FootholdPlanner:
             rows, cols = trav.shape
         else:
             cols, rows = trav.shape
-        d = MapDesc(rows, cols, float(resolution), (C.c_double * 2)(*map(float, position)),
-                    (C.c_int32 * 2)(*map(int, start_index)), 1 if storage_order == "row" else 0)
+        d = _map_desc(rows, cols, resolution, position, start_index, storage_order)
         self._check(self._lib.fpe_upload_map(self._h, C.byref(d), ptr(trav), ptr(elev)))
         self.rows, self.cols, self.resolution = rows, cols, float(resolution)
 
     def upload_map_device(self, d_trav_ptr, d_elev_ptr, rows, cols, resolution, position=(0.0, 0.0), start_index=(0, 0),
                           storage_order="row", stream=None):
-        d = MapDesc(rows, cols, float(resolution), (C.c_double * 2)(*map(float, position)),
-                    (C.c_int32 * 2)(*map(int, start_index)), 1 if storage_order == "row" else 0)
+        d = _map_desc(rows, cols, resolution, position, start_index, storage_order)
         self._check(self._lib.fpe_upload_map_device(self._h, C.byref(d), C.c_void_p(d_trav_ptr), C.c_void_p(d_elev_ptr),
                                                     C.c_void_p(stream or 0)))
         self.rows, self.cols, self.resolution = rows, cols, float(resolution)
@@ -130,8 +147,7 @@ class FootholdPlanner:
         the device filters; with want_layers also the dict of all FPE_FILTER_LAYERS layers."""
         elev = np.ascontiguousarray(elevation, dtype=np.float32)
         rows, cols = elev.shape if storage_order == "row" else elev.shape[::-1]
-        d = MapDesc(rows, cols, float(resolution), (C.c_double * 2)(*map(float, position)),
-                    (C.c_int32 * 2)(*map(int, start_index)), 1 if storage_order == "row" else 0)
+        d = _map_desc(rows, cols, resolution, position, start_index, storage_order)
         fp = params if params is not None else self.filter_params()
         trav = np.empty((rows, cols), np.float32)
         layers = np.empty((len(_capi.FILTER_LAYERS), rows, cols), np.float32) if want_layers else None
@@ -144,7 +160,7 @@ class FootholdPlanner:
     def traversability_device(self, d_elev_ptr, d_trav_ptr, rows, cols, resolution, position=(0.0, 0.0), params=None,
                               d_layers_ptr=0, stream=None):
         """Device-resident form (canonical row-major layers), asynchronous on `stream`."""
-        d = MapDesc(rows, cols, float(resolution), (C.c_double * 2)(*map(float, position)), (C.c_int32 * 2)(0, 0), 1)
+        d = _map_desc(rows, cols, resolution, position)
         fp = params if params is not None else self.filter_params()
         self._check(self._lib.fpe_traversability_device(self._h, C.byref(d), C.byref(fp), C.c_void_p(d_elev_ptr),
                                                         C.c_void_p(d_trav_ptr), C.c_void_p(d_layers_ptr or 0), C.c_void_p(stream or 0)))
@@ -195,8 +211,7 @@ class FootholdPlanner:
         a[...] = np.zeros((), dtype)
         return a
 
-    def plan_outputs(self, B, n_cycles, products=("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status"),
-                     pinned=False):
+    def plan_outputs(self, B, n_cycles, products=DEFAULT_PRODUCTS, pinned=False):
         shapes = product_shapes(B, n_cycles)
         if not pinned:
             return {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in products}
@@ -212,8 +227,7 @@ class FootholdPlanner:
         return {k: arena[o:o + n].view(shapes[k][1]).reshape(shapes[k][0]) for k, o, n in zip(order, offs, sizes)}
 
     # ---- chained plan, host buffers ------------------------------------------------------------------
-    def plan(self, poses, n_cycles, products=("nominal", "centroid", "default", "cycle_ok", "stance", "selected", "pose_status"),
-             out=None):
+    def plan(self, poses, n_cycles, products=DEFAULT_PRODUCTS, out=None):
         """fpe_plan with host buffers.  `out`: a dict returned by an earlier call with the same shapes (timing loops
         reuse the arrays instead of allocating ~100 B per foothold per call)."""
         poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
@@ -334,9 +348,22 @@ class FootholdPlanner:
     def _roi(roi):
         return None if roi is None else np.ascontiguousarray(roi, dtype=np.int32).reshape(4)
 
-    def _dense_outputs(self, what, roi, products, table):
-        """The region as the C ABI takes it (None = the whole map) and one uninitialised array per requested product of a
-        dense map: `table` maps a product name to (dtype, trailing shape) behind [n_rows, n_cols]."""
+    # the dense maps: out struct of the C ABI (its field names are the product names) and per product (dtype, trailing shape)
+    # behind [n_rows, n_cols]
+    _DENSE = {"foothold-map": (FootholdMapOut, {"flags": (np.uint8, ()), "height": (np.float32, ())}),
+              "foothold-snap": (FootholdSnapOut, {"offset": (np.int8, (2,)), "source": (np.uint8, ()), "z": (np.float32, ())}),
+              "centroid-map": (CentroidMapOut, {"code": (np.uint8, ()), "offset": (np.int8, (2,)), "z": (np.float32, ())})}
+
+    @classmethod
+    def _dense_out(cls, what, **addresses):
+        """The out struct of a dense map from {product: address} (host or device; 0 / None / missing = product not wanted)."""
+        struct = cls._DENSE[what][0]
+        return struct(*(addresses.get(name) or None for name, _ in struct._fields_))
+
+    def _dense_outputs(self, what, roi, products):
+        """The region as the C ABI takes it (None = the whole map), one uninitialised array per requested product of a dense
+        map, and the out struct that points at them."""
+        table = self._DENSE[what][1]
         unknown = set(products) - set(table)
         if unknown:
             raise ValueError(f"unknown {what} products {sorted(unknown)}")
@@ -344,24 +371,23 @@ class FootholdPlanner:
         if r is not None:
             shape = (max(int(r[2]), 0), max(int(r[3]), 0))
         else:
-            d = MapDesc()
-            self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
-            shape = (d.rows, d.cols)
-        return r, {k: np.empty(shape + tail, dtype) for k, (dtype, tail) in table.items() if k in products}
+            info = self.map_info()
+            shape = (info["rows"], info["cols"])
+        out = {k: np.empty(shape + tail, dtype) for k, (dtype, tail) in table.items() if k in products}
+        return r, out, self._dense_out(what, **{k: a.ctypes.data for k, a in out.items()})
 
     def foothold_map(self, roi=None, products=("flags", "height")):
         """fpe_foothold_map on the current map: {"flags": uint8 [n_rows, n_cols] FPE_FMAP_* bits, "height": float32
         [n_rows, n_cols]} for the requested products.  roi = (row0, col0, n_rows, n_cols) in canonical indices; None = the
         whole map."""
-        r, out = self._dense_outputs("foothold-map", roi, products, {"flags": (np.uint8, ()), "height": (np.float32, ())})
-        mo = FootholdMapOut(ptr(out.get("flags")), ptr(out.get("height")))
+        r, out, mo = self._dense_outputs("foothold-map", roi, products)
         self._check(self._lib.fpe_foothold_map(self._h, ptr(self.params), ptr(r), C.byref(mo)))
         return out
 
     def foothold_map_device(self, d_flags_ptr, d_height_ptr, roi=None, stream=0):
         """Device form: DEVICE pointers (0 = product not wanted), asynchronous on `stream`."""
         r = self._roi(roi)
-        mo = FootholdMapOut(C.c_void_p(d_flags_ptr or None), C.c_void_p(d_height_ptr or None))
+        mo = self._dense_out("foothold-map", flags=d_flags_ptr, height=d_height_ptr)
         self._check(self._lib.fpe_foothold_map_device(self._h, ptr(self.params), ptr(r), C.byref(mo), C.c_void_p(stream or 0)))
 
     # ---- dense snap map: checkFoothold's landing cell for every cell centre -----------------------------------------------
@@ -379,9 +405,7 @@ class FootholdPlanner:
         """fpe_foothold_snap on the current map: {"offset": int8 [n_rows, n_cols, 2] (di, dj) of the landing cell, "source":
         uint8 [n_rows, n_cols] (0 default hit, 1 spiral candidate, 2 none), "z": float32 [n_rows, n_cols]} for the requested
         products.  roi as in foothold_map; search_radius None = params.searchRadius; polygon "rectangle" | "hexagon"."""
-        r, out = self._dense_outputs("foothold-snap", roi, products,
-                                     {"offset": (np.int8, (2,)), "source": (np.uint8, ()), "z": (np.float32, ())})
-        so = FootholdSnapOut(ptr(out.get("offset")), ptr(out.get("source")), ptr(out.get("z")))
+        r, out, so = self._dense_outputs("foothold-snap", roi, products)
         self._check(self._lib.fpe_foothold_snap(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0),
                                                 self._polygon_kind(polygon), C.byref(so)))
         return out
@@ -390,7 +414,7 @@ class FootholdPlanner:
                              stream=0):
         """Device form: DEVICE pointers (0 = product not wanted), asynchronous on `stream`."""
         r = self._roi(roi)
-        so = FootholdSnapOut(C.c_void_p(d_offset_ptr or None), C.c_void_p(d_source_ptr or None), C.c_void_p(d_z_ptr or None))
+        so = self._dense_out("foothold-snap", offset=d_offset_ptr, source=d_source_ptr, z=d_z_ptr)
         self._check(self._lib.fpe_foothold_snap_device(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0),
                                                        self._polygon_kind(polygon), C.byref(so), C.c_void_p(stream or 0)))
 
@@ -412,16 +436,14 @@ class FootholdPlanner:
         """fpe_centroid_map on the current map: {"code": uint8 [n_rows, n_cols] (0..6), "offset": int8 [n_rows, n_cols, 2]
         (row - i, col - j) of the landing cell, "z": float32 [n_rows, n_cols]} for the requested products.  roi as in
         foothold_map; search_radius None = params.searchRadius."""
-        r, out = self._dense_outputs("centroid-map", roi, products,
-                                     {"code": (np.uint8, ()), "offset": (np.int8, (2,)), "z": (np.float32, ())})
-        co = CentroidMapOut(ptr(out.get("code")), ptr(out.get("offset")), ptr(out.get("z")))
+        r, out, co = self._dense_outputs("centroid-map", roi, products)
         self._check(self._lib.fpe_centroid_map(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0), C.byref(co)))
         return out
 
     def centroid_map_device(self, d_code_ptr, d_offset_ptr, d_z_ptr, roi=None, search_radius=None, stream=0):
         """Device form: DEVICE pointers (0 = product not wanted), asynchronous on `stream`."""
         r = self._roi(roi)
-        co = CentroidMapOut(C.c_void_p(d_code_ptr or None), C.c_void_p(d_offset_ptr or None), C.c_void_p(d_z_ptr or None))
+        co = self._dense_out("centroid-map", code=d_code_ptr, offset=d_offset_ptr, z=d_z_ptr)
         self._check(self._lib.fpe_centroid_map_device(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0), C.byref(co),
                                                       C.c_void_p(stream or 0)))
 
@@ -462,9 +484,8 @@ class FootholdPlanner:
         if unknown:
             raise ValueError(f"unknown layers {sorted(unknown)}")
         lay = self._layer_layout(start_index, storage_order)
-        d = MapDesc()
-        self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
-        shape = (d.rows, d.cols) if storage_order == "row" else (d.cols, d.rows)
+        info = self.map_info()
+        shape = (info["rows"], info["cols"]) if storage_order == "row" else (info["cols"], info["rows"])
         if out is None:
             out = {n: (self.host_array(shape, np.float32) if pinned else np.empty(shape, np.float32)) for n in layers}
         for n in layers:
@@ -559,37 +580,14 @@ class FootholdPlanner:
         return out
 
 
-class MultiFootholdPlanner:
+class MultiFootholdPlanner(_Handle):
     """Several GPUs in ONE process behind the C ABI (fpe_multi_*): the map is replicated on every device and a pose
     batch is split into contiguous blocks, one host thread per device (include/fpe.h, "several GPUs")."""
+    _CREATE, _DESTROY, _LAST_ERROR = "fpe_multi_create", "fpe_multi_destroy", "fpe_multi_last_error"
 
     def __init__(self, device_ids, params=None):
-        self._lib = _capi.lib()
         ids = np.ascontiguousarray(device_ids, dtype=np.int32)
-        self._h = C.c_void_p()
-        rc = self._lib.fpe_multi_create(ptr(ids), ids.size, C.byref(self._h))
-        if rc != _capi.FPE_OK:
-            msg = self._lib.fpe_multi_last_error(None).decode()
-            self._h = None
-            if rc == _capi.FPE_E_NO_DEVICE:
-                raise EngineUnavailable(f"fpe_multi_create failed: {msg} (the engine has no CPU fallback)")
-            raise FpeError(rc, msg)
-        self.params = _capi.params_yaml() if params is None else np.array(params, dtype=PARAMS_DTYPE).reshape(1)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fpe_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != _capi.FPE_OK:
-            raise FpeError(rc, self._lib.fpe_multi_last_error(self._h).decode())
+        self._create(ptr(ids), ids.size, params=params)
 
     @property
     def device_count(self):
@@ -603,7 +601,7 @@ class MultiFootholdPlanner:
         trav = np.ascontiguousarray(traversability, dtype=np.float32)
         elev = np.ascontiguousarray(elevation, dtype=np.float32)
         rows, cols = trav.shape
-        d = MapDesc(rows, cols, float(resolution), (C.c_double * 2)(*map(float, position)), (C.c_int32 * 2)(0, 0), 1)
+        d = _map_desc(rows, cols, resolution, position)
         self._check(self._lib.fpe_multi_upload_map(self._h, C.byref(d), ptr(trav), ptr(elev)))
 
     def engine(self, k):
@@ -638,13 +636,8 @@ class MultiFootholdPlanner:
     def plan(self, poses, n_cycles):
         poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
         B = poses.shape[0]
-        out = {
-            "nominal": np.zeros((B, n_cycles, 4), dtype=FOOTHOLD_DTYPE), "centroid": np.zeros((B, n_cycles, 4), dtype=CENTROID_DTYPE),
-            "default": np.zeros((B, n_cycles, 4, 3), dtype=np.float64), "cycle_ok": np.zeros((B, n_cycles), dtype=np.uint8),
-            "stance": np.zeros((B, 4, 3), dtype=np.float64), "selected": np.zeros((B, n_cycles, 4), dtype=SELECTED_DTYPE),
-            "pose_status": np.zeros(B, dtype=np.uint8),
-        }
-        po = PlanOut(ptr(out["nominal"]), ptr(out["centroid"]), ptr(out["default"]), ptr(out["cycle_ok"]), ptr(out["stance"]),
-                     ptr(out["selected"]), ptr(out["pose_status"]))
+        shapes = product_shapes(B, n_cycles)
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in DEFAULT_PRODUCTS}
+        po = PlanOut(*(ptr(out[k]) for k in DEFAULT_PRODUCTS))  # (DEFAULT_PRODUCTS are the struct's leading fields, in its order)
         self._check(self._lib.fpe_multi_plan(self._h, ptr(self.params), ptr(poses), B, int(n_cycles), C.byref(po)))
         return out

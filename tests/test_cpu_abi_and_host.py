@@ -10,6 +10,7 @@ import pytest
 
 from oracle import fpo
 from quadrupedal_foothold_planner_amd import _capi, synth
+from tests import abi_c
 from tests.conftest import yaml_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +20,8 @@ def test_library_loads_and_exports_every_declared_symbol():
     L = _capi.lib()
     hdr = open(os.path.join(ROOT, "include", "fpe.h")).read()
     declared = set(re.findall(r"\b(fpe_[a-z_0-9]+)\s*\(", hdr))
-    assert declared == set(_capi.EXPORTED_SYMBOLS), declared ^ set(_capi.EXPORTED_SYMBOLS)
+    assert declared == set(_capi.PROTOTYPES), declared ^ set(_capi.PROTOTYPES)  # every declared symbol has its restype and argtypes
+    assert _capi.EXPORTED_SYMBOLS == list(_capi.PROTOTYPES)
     for name in declared:
         assert hasattr(L, name), name
     assert b"gfx950" in L.fpe_version()
@@ -230,8 +232,7 @@ def test_the_header_is_plain_c(tmp_path):
     src.write_text('#include "fpe.h"\n#include <stdio.h>\nint main(void) { fpe_params p; fpe_opt_params o; fpe_filter_params f;\n'
                    '  if (fpe_params_yaml(&p) || fpe_opt_params_yaml(&o) || fpe_filter_params_defaults(&f)) return 1;\n'
                    '  printf("%s %.3f %.3f\\n", fpe_version(), (double)p.searchRadius, f.normal_radius); return 0; }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)],
-                       capture_output=True, text=True)
+    r = subprocess.run(abi_c.STRICT + [str(src)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     lib = fbuild.build_engine()
     exe = tmp_path / "hdr"

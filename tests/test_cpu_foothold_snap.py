@@ -1,55 +1,6 @@
-"""CPU-only checks of the dense snap map's C ABI (fpe_foothold_snap*, include/fpe.h): the header additions compile as plain C,
-the ctypes mirror of fpe_foothold_snap_out has the C layout, and the library exports both entry points."""
-import ctypes as C
-import os
-import subprocess
-
+"""CPU-only check of the dense snap map's entry points (fpe_foothold_snap*, include/fpe.h): the binding names them and the library
+exports them.  (Layouts and prototypes: tests/test_cpu_abi.py.)"""
 from quadrupedal_foothold_planner_amd import _capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _compile_and_run(tmp_path, body, decls=""):
-    """C99 with warnings as errors over the whole program (`decls` is checked for syntax only: it may name the library's
-    functions), then the program without `decls` built and run (no library, no GPU)."""
-    inc = "-I" + os.path.join(ROOT, "include")
-    head = '#include "fpe.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(void) {\n'
-    full = tmp_path / "fsnap_decls.c"
-    full.write_text(head + decls + body + "\n  return 0;\n}\n")
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", inc, str(full)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    src = tmp_path / "fsnap.c"
-    src.write_text(head + body + "\n  return 0;\n}\n")
-    exe = tmp_path / "fsnap"
-    r = subprocess.run(["gcc", "-std=c99", inc, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return r.stdout
-
-
-def test_foothold_snap_declarations_are_plain_c(tmp_path):
-    """The struct and both prototypes compile as C99 with warnings as errors; the ABI version is unchanged."""
-    decls = ("  int (*f)(fpe_handle, const fpe_params*, const int32_t*, float, int32_t, const fpe_foothold_snap_out*) = "
-             "fpe_foothold_snap;\n"
-             "  int (*g)(fpe_handle, const fpe_params*, const int32_t*, float, int32_t, const fpe_foothold_snap_out*, void*) = "
-             "fpe_foothold_snap_device;\n"
-             "  (void)f; (void)g;\n")
-    out = _compile_and_run(tmp_path, "  fpe_foothold_snap_out o = {0, 0, 0};\n  (void)o;\n"
-                                     '  printf("%d\\n", FPE_ABI_VERSION);', decls)
-    assert out.split() == ["5"]
-    assert _capi.ABI_VERSION == 5
-
-
-def test_foothold_snap_out_layout_matches_the_ctypes_mirror(tmp_path):
-    out = _compile_and_run(tmp_path, '  printf("%zu %zu %zu %zu\\n", sizeof(fpe_foothold_snap_out), '
-                                     "offsetof(fpe_foothold_snap_out, offset), offsetof(fpe_foothold_snap_out, source), "
-                                     "offsetof(fpe_foothold_snap_out, z));")
-    size, o_off, o_src, o_z = map(int, out.split())
-    M = _capi.FootholdSnapOut
-    assert [name for name, _ in M._fields_] == ["offset", "source", "z"]  # the header's field order
-    assert (C.sizeof(M), M.offset.offset, M.source.offset, M.z.offset) == (size, o_off, o_src, o_z)
 
 
 def test_foothold_snap_symbols_are_exported():

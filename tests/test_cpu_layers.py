@@ -1,79 +1,22 @@
-"""CPU-only checks of the message-layer export's C ABI (fpe_export_layers*, include/fpe.h): the header additions compile as plain
-C, the ABI version is unchanged, the ctypes mirrors have the C layout, the layer names follow the header's ids, and the library
-exports both entry points."""
+"""CPU-only checks of the message-layer export (fpe_export_layers*, include/fpe.h): the layer names follow the header's ids, the
+library exports both entry points, and the binding refuses unknown names itself.  (Layouts and prototypes: tests/test_cpu_abi.py.)"""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 from quadrupedal_foothold_planner_amd import _capi
+from tests import abi_c
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("fpe_export_layers", "fpe_export_layers_device")
 IDS = ("FOOTHOLD_FLAGS", "FOOTHOLD_HEIGHT", "SNAP_DI", "SNAP_DJ", "SNAP_SOURCE", "SNAP_Z", "CENTROID_CODE", "CENTROID_DI",
        "CENTROID_DJ", "CENTROID_Z")
 
 
-def _compile_and_run(tmp_path, body, decls=""):
-    """C99 with warnings as errors over the whole program (`decls` is checked for syntax only: it may name the library's
-    functions), then the program without `decls` built and run (no library, no GPU)."""
-    inc = "-I" + os.path.join(ROOT, "include")
-    head = '#include "fpe.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(void) {\n'
-    full = tmp_path / "layers_decls.c"
-    full.write_text(head + decls + body + "\n  return 0;\n}\n")
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", inc, str(full)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    src = tmp_path / "layers.c"
-    src.write_text(head + body + "\n  return 0;\n}\n")
-    exe = tmp_path / "layers"
-    r = subprocess.run(["gcc", "-std=c99", inc, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return r.stdout
-
-
-def test_layer_declarations_are_plain_c(tmp_path):
-    """Both structs and both prototypes compile as C99 with warnings as errors; the ABI version is unchanged."""
-    decls = ("  int (*f)(fpe_handle, const fpe_params*, const int32_t*, const fpe_layer_layout*, const fpe_layer_request*) = "
-             "fpe_export_layers;\n"
-             "  int (*g)(fpe_handle, const fpe_params*, const int32_t*, const fpe_layer_layout*, const fpe_layer_request*, void*) = "
-             "fpe_export_layers_device;\n"
-             "  (void)f; (void)g;\n")
-    out = _compile_and_run(tmp_path, "  fpe_layer_layout l = {{0, 0}, 0, 0};\n  fpe_layer_request q;\n  q.n_layers = 1;\n"
-                                     "  q.layer[0] = FPE_LAYER_SNAP_SOURCE;\n  q.dst[0] = 0;\n  (void)l; (void)q;\n"
-                                     '  printf("%d\\n", FPE_ABI_VERSION);', decls)
-    assert out.split() == ["5"]
-    assert _capi.ABI_VERSION == 5
-
-
 def test_layer_ids_follow_the_header(tmp_path):
-    out = _compile_and_run(tmp_path, '  printf("' + " ".join(["%d"] * (len(IDS) + 1)) + '\\n", '
-                           + ", ".join("FPE_LAYER_" + n for n in IDS) + ", FPE_LAYER_COUNT);")
+    out = abi_c.compile_and_run(tmp_path, '  printf("' + " ".join(["%d"] * (len(IDS) + 1)) + '\\n", '
+                                + ", ".join("FPE_LAYER_" + n for n in IDS) + ", FPE_LAYER_COUNT);")
     assert list(map(int, out.split())) == list(range(len(IDS))) + [len(IDS)]
     assert _capi.LAYER_NAMES == tuple(n.lower() for n in IDS) and _capi.LAYER_COUNT == len(IDS)
-
-
-def test_layer_struct_layouts_match_the_ctypes_mirrors(tmp_path):
-    out = _compile_and_run(
-        tmp_path,
-        '  printf("%zu %zu %zu %zu\\n", sizeof(fpe_layer_layout), offsetof(fpe_layer_layout, start_index), '
-        "offsetof(fpe_layer_layout, storage_order), offsetof(fpe_layer_layout, reserved));\n"
-        '  printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(fpe_layer_request), offsetof(fpe_layer_request, n_layers), '
-        "offsetof(fpe_layer_request, layer), offsetof(fpe_layer_request, dst), offsetof(fpe_layer_request, snap_search_radius), "
-        "offsetof(fpe_layer_request, snap_polygon_kind), offsetof(fpe_layer_request, centroid_search_radius), "
-        "offsetof(fpe_layer_request, reserved));")
-    lay, req = (list(map(int, ln.split())) for ln in out.strip().split("\n"))
-    M = _capi.LayerLayout
-    assert [name for name, _ in M._fields_] == ["start_index", "storage_order", "reserved"]
-    assert [C.sizeof(M), M.start_index.offset, M.storage_order.offset, M.reserved.offset] == lay and lay[0] == 16
-    R = _capi.LayerRequest
-    assert [name for name, _ in R._fields_] == ["n_layers", "layer", "dst", "snap_search_radius", "snap_polygon_kind",
-                                                 "centroid_search_radius", "reserved"]
-    assert [C.sizeof(R), R.n_layers.offset, R.layer.offset, R.dst.offset, R.snap_search_radius.offset, R.snap_polygon_kind.offset,
-            R.centroid_search_radius.offset, R.reserved.offset] == req
 
 
 def test_build_produces_a_library_that_exports_both_symbols():

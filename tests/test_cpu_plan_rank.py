@@ -1,10 +1,8 @@
-"""CPU-only checks of the batch ranking's C ABI (fpe_plan_rank*, include/fpe.h) and of its numpy reference (tests/rank_reference.py):
-the header additions compile as plain C, the ctypes and numpy mirrors have the C layout, the library exports the entry points,
-the defaults are the documented ones, the reference reproduces the closed form of the oracle's flat world, and the inputs of the
-GPU parity test keep the ranking from being trivial."""
+"""CPU-only checks of the batch ranking (fpe_plan_rank*, include/fpe.h) and of its numpy reference (tests/rank_reference.py):
+the library exports the entry points, the defaults are the documented ones, the reference reproduces the closed form of the
+oracle's flat world, and the inputs of the GPU parity test keep the ranking from being trivial.  (Layouts and prototypes:
+tests/test_cpu_abi.py.)"""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -14,77 +12,8 @@ from tests import rank_reference as ref
 from tests import util
 from tests.conftest import oracle_poses, yaml_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("fpe_rank_params_defaults", "fpe_plan_rank", "fpe_plan_rank_device")
-
-
-def _compile_and_run(tmp_path, body, decls=""):
-    """C99 with warnings as errors over the whole program (`decls` is checked for syntax only: it may name the library's
-    functions), then the program without `decls` built and run (no library, no GPU)."""
-    inc = "-I" + os.path.join(ROOT, "include")
-    head = '#include "fpe.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(void) {\n'
-    full = tmp_path / "rank_decls.c"
-    full.write_text(head + decls + body + "\n  return 0;\n}\n")
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", inc, str(full)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    src = tmp_path / "rank.c"
-    src.write_text(head + body + "\n  return 0;\n}\n")
-    exe = tmp_path / "rank"
-    r = subprocess.run(["gcc", "-std=c99", inc, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return r.stdout
-
-
-def test_rank_declarations_are_plain_c_and_the_abi_version_stays(tmp_path):
-    decls = ("  int (*d)(fpe_rank_params*) = fpe_rank_params_defaults;\n"
-             "  int (*f)(fpe_handle, const fpe_params*, const fpe_rank_params*, const fpe_pose*, int32_t, int32_t, int32_t, "
-             "const fpe_rank_out*) = fpe_plan_rank;\n"
-             "  int (*g)(fpe_handle, const fpe_params*, const fpe_rank_params*, const fpe_pose*, int32_t, int32_t, int32_t, "
-             "const fpe_plan_out*, const fpe_rank_out*, void*) = fpe_plan_rank_device;\n"
-             "  (void)d; (void)f; (void)g;\n")
-    out = _compile_and_run(tmp_path, "  fpe_rank_out o;\n  fpe_rank_params r;\n  fpe_pose_summary s;\n  o.best = 0; r.min_cycles = 0; s.success = 0;\n"
-                                     "  (void)o; (void)r; (void)s;\n"
-                                     '  printf("%d %zu\\n", FPE_ABI_VERSION, sizeof(fpe_pose_summary));', decls)
-    assert out.split() == ["5", "64"]
-    assert _capi.ABI_VERSION == 5
-
-
-SUMMARY_FIELDS = ("success", "gait_cycles_succeed", "committed", "first_failed", "pose_status", "pad", "n_source", "cog_speed_sum",
-                  "cog_speed_min", "cog_speed_max", "feet_distance_min", "feet_distance_max", "deviation_sq_sum")
 PARAM_FIELDS = ("w_fail", "w_spiral", "w_none", "w_deviation", "w_speed_spread", "min_cycles", "reserved")
-OUT_FIELDS = ("summary", "score", "best", "n_class0", "best_products")
-
-
-def _c_layout(tmp_path, struct, fields):
-    fmt = " ".join(["%zu"] * (len(fields) + 1))
-    args = ", ".join([f"sizeof({struct})"] + [f"offsetof({struct}, {f})" for f in fields])
-    vals = list(map(int, _compile_and_run(tmp_path, f'  printf("{fmt}\\n", {args});').split()))
-    return vals[0], vals[1:]
-
-
-def test_every_offset_of_the_three_structs_equals_the_mirrors(tmp_path):
-    size, offs = _c_layout(tmp_path, "fpe_pose_summary", SUMMARY_FIELDS)
-    assert size == 64
-    M, D = _capi.PoseSummary, _capi.POSE_SUMMARY_DTYPE
-    assert tuple(name for name, _ in M._fields_) == SUMMARY_FIELDS == D.names
-    assert (C.sizeof(M), [getattr(M, f).offset for f in SUMMARY_FIELDS]) == (size, offs)
-    assert (D.itemsize, [D.fields[f][1] for f in SUMMARY_FIELDS]) == (size, offs)
-    assert D.fields["n_source"][0] == np.dtype(("<u2", (4,))) and D.fields["deviation_sq_sum"][0] == np.dtype("<f8")
-
-    size, offs = _c_layout(tmp_path, "fpe_rank_params", PARAM_FIELDS)
-    M, D = _capi.RankParams, _capi.RANK_PARAMS_DTYPE
-    assert tuple(name for name, _ in M._fields_) == PARAM_FIELDS == D.names
-    assert (C.sizeof(M), [getattr(M, f).offset for f in PARAM_FIELDS]) == (size, offs)
-    assert (D.itemsize, [D.fields[f][1] for f in PARAM_FIELDS]) == (size, offs)
-
-    size, offs = _c_layout(tmp_path, "fpe_rank_out", OUT_FIELDS)
-    M = _capi.RankOut
-    assert tuple(name for name, _ in M._fields_) == OUT_FIELDS
-    assert (C.sizeof(M), [getattr(M, f).offset for f in OUT_FIELDS]) == (size, offs)
-    assert C.sizeof(_capi.PlanOut) == size - offs[-1]
 
 
 def test_rank_symbols_are_exported():
