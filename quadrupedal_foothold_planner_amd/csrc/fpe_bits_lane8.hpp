@@ -746,7 +746,9 @@ __device__ __forceinline__ PlanConsts plan_consts_of(const PlanMidConsts& k) {
     return pc;
 }
 
-template <int NRL, bool kNoDefault, int kProd>
+// kPlain: the wavefront's poses are plain (plan_bits_kernel: trot, no radius override, rectangle polygons): ls.Rf and lk.* are the
+// uniform plan constants (scalar values: no ballot over them), radiusOk and the rectangle are compile-time facts.
+template <int NRL, bool kNoDefault, int kProd, bool kPlain>
 __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, int winH, bool wantDefaultArg, const HotConsts& hc, const LaneRole& role,
                                            const FastRanks& fk,
                                            const LutHead& head, PoseShared& sh, const LegBits& lb, const Grp<8>& g,
@@ -799,7 +801,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
     // (kNoDefault: lanes 5-6 evaluate default-track corners nobody reads: their `safe` / magnitude tests do not count)
     const bool dfltLane = (g.sub == 5) | (g.sub == 6);
     const bool laneOk = kNoDefault ? (dfltLane | (safe & (fabs(nxq) <= 1e6))) : (safe & (fabs(nxq) <= 1e6));
-    const bool rare = !ls.radiusOk | ((ye.flags & 2) == 0) | !laneOk | (!kNoDefault & !wantDefault) | !boxes;
+    const bool rare = (!kPlain & !ls.radiusOk) | ((ye.flags & 2) == 0) | !laneOk | (!kNoDefault & !wantDefault) | !boxes;
     if (__ballot(rare) != 0ull) {  // wave-uniform
         const double ctr0 = swizzle_f64<kKeep | (5 << 5)>(myCtr), ctr1 = swizzle_f64<kKeep | (0 << 5)>(myCtr),
                      ctr2 = swizzle_f64<kKeep | (7 << 5)>(myCtr);
@@ -853,7 +855,9 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
     // is one of them iff xlo <= x_i < xhi: the lane tests ITS row's centre, nobody derives the interval's ends (a floor, a
     // clamp and a conversion per end, four corrected estimates over a ballot: fifty instructions a cycle).
     // (one-cell foot disc: what these kernels are launched for, launch_plan_bits)
-    const bool fastSpiral = __ballot(ls.polyKind != 0 || lk.nRings < 4 || lk.nCand < 16) == 0ull;  // uniform
+    bool fastSpiral;  // uniform
+    if constexpr (kPlain) fastSpiral = lk.nRings >= 4 && lk.nCand >= 16;  // (the plan's defNRings / defNCand: a scalar test)
+    else fastSpiral = __ballot(ls.polyKind != 0 || lk.nRings < 4 || lk.nCand < 16) == 0ull;
     const int iFast = iw0 + g.sub + G * fk.slot;
     const double rS = static_cast<double>(ls.Rf);
     const double xFast = cell_pos(m.g.baseX, m.g.res, iFast);
@@ -966,8 +970,8 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
             c.cyc = cyc;
             c.cx = cx;
             c.cy = ny;
-            c.nv = ls.polyKind == 0 ? 4 : 6;
-            c.rect = ls.polyKind == 0;
+            c.nv = (kPlain || ls.polyKind == 0) ? 4 : 6;
+            c.rect = kPlain || ls.polyKind == 0;
             c.xhi = nx2 + r;
             c.xlo = nx2 - r;
             c.yhi = ny + 0.5 * r;
@@ -983,7 +987,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
             c.ti0 = c.tj0 = 0;
             c.ici = ici;
             c.icj = icj;
-            if (!c.rect) {  // hexagon vertices from the NOMINAL track's position (build-defined, App. E)
+            if (!kPlain && !c.rect) {  // hexagon vertices from the NOMINAL track's position (build-defined, App. E)
                 if (g.sub == 0) {
                     double* vx = sh.polyX[leg];
                     double* vy = sh.polyY[leg];
@@ -1034,52 +1038,23 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
 
 // ---- chained plan on the bit window: 8 lanes per leg, two poses per wavefront ------------------------------------
 constexpr int kBitsGenericWaves = 3;  // measured on cfg-4: 2 -> 1.36 ms, 3 -> 1.25 ms (27 spilled VGPRs), 4 -> 1.46 ms (69 spilled)
-template <int NRL, bool kMid, int kProd>
-// (the pose pointer and the counts lead the argument list: scalar arguments at the head of the kernarg segment are
-// preloaded into SGPRs at wave launch, -amdgpu-kernarg-preload-count, so the pose loads can be issued at once)
-__global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles,
-                                                          DevMap mArg, BitMap bm, typename std::conditional<kMid, PlanMidConsts, PlanConsts>::type pc,
-                                                          SpiralLut lut, fpe_plan_out outArg) {
+// Everything of plan_bits_kernel behind the pose loads and the parked constants: the LDS views, the legs' constants, the stance,
+// the gate of the first cycle, the cycle loop with its flushes.  kPlain (3x3-only kernels, decided per wavefront by the kernel):
+// both poses trot, no leg overrides the search radius, every search polygon is the rectangle — one phase a cycle with all four
+// legs swinging (no phase loop, no swing mask), advance = step, and the legs' search constants are the plan's own (uniform).
+// kPlain = false is the general code.  Always inlined into the kernel.
+// (The LDS views and the rank table's head are set up HERE, once per copy, not in the kernel ahead of the verdict: a value both
+// copies read has to be computed in front of the branch and stays in its register through either copy, where one copy's own
+// value is computed next to its use — with them in the kernel the <4, true, *> instances spilled four vector registers.)
+template <int NRL, bool kMid, int kProd, bool kPlain, class PC>
+__device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool live, double x0, double y0, double z0, int gait, float rOverride,
+                                               int polyKindIn, int nCycles, const DevMap& m, const DevMap& mArg, const BitMap& bm, const PC& pc,
+                                               const SpiralLut& lut, const fpe_plan_out& out, const HotConsts& hc, int tid, int slot, int leg) {
+    static_assert(kMid || !kPlain, "the generic kernels have no plain instance");
     constexpr int G = 8;
-    const fpe_plan_out out = specialise_products<kProd>(outArg);
     constexpr bool kNoDefault = kProd == 1;
-    constexpr int NR = G * NRL;
     constexpr int kPoseThreads = 4 * G;
-    const int tid = static_cast<int>(threadIdx.x);
-    const int slot = tid / kPoseThreads;
-    const int leg = (tid / G) & 3;
-    // the pose first: its address needs nothing but the preloaded arguments, and everything else waits for it
-    int b = blockIdx.x * 2 + slot;
-    const bool live = b < B;  // the padding pose of the last block runs the chain on pose B-1, stores nothing
-    if (!live) b = B - 1;
-    const fpe_pose* pp = poses + b;
-    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
-    const int gait = pp->gait;
-    const float rOverride = pp->leg_search_radius[leg];
-    const int polyKindIn = pp->leg_polygon_kind[leg];
-    __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
-    // the map geometry doubles are operands of vector f64 arithmetic only: parked in VGPRs (see plan_chained_kernel) — in
-    // the 3x3-only variants; the generic ones run at their register cap (168 VGPRs at three wavefronts per SIMD), where the
-    // twenty registers cost more in spills than the scalar operands do in moves (measured: cfg-4 0.713 -> 0.664 ms without)
-    DevMap m = mArg;
-    if constexpr (kMid) {
-        m.g.res = in_vgpr(m.g.res);
-        m.g.rinv = in_vgpr(m.g.rinv);
-        m.g.lenX = in_vgpr(m.g.lenX);
-        m.g.lenY = in_vgpr(m.g.lenY);
-        m.g.posX = in_vgpr(m.g.posX);
-        m.g.posY = in_vgpr(m.g.posY);
-        m.g.orgX = in_vgpr(m.g.orgX);
-        m.g.orgY = in_vgpr(m.g.orgY);
-        m.g.baseX = in_vgpr(m.g.baseX);
-        m.g.baseY = in_vgpr(m.g.baseY);
-    }
-    HotConsts hc;
-    hc.rf = in_vgpr(pc.rf);
-    hc.rf2 = in_vgpr(pc.rf2);
-    hc.cornerEps = in_vgpr(pc.cornerEps);
-    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
-    hc.drift = kMid ? in_vgpr(pc.drift) : pc.drift;  // (the generic variants run at their register cap: nothing extra parked)
+    constexpr int NR = G * NRL;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const Grp<G> g(tid);
     const size_t legBytes = 4 * static_cast<size_t>(legbits_words(NR, 1, pc.nHW));
@@ -1096,11 +1071,11 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
     const LutHead head = load_lut_head(lut, g);
     LegStatic ls;
     {
-        if (__ballot(rOverride > 0.0f) != 0ull) {  // some leg of the wavefront overrides the search radius (build-defined)
+        if (!kPlain && __ballot(rOverride > 0.0f) != 0ull) {  // some leg of the wavefront overrides the search radius (build-defined)
             ls = make_leg_static(pc, pp, leg, m.g.res, lut);
         } else {  // the reference's single searchRadius_: constants precomputed on the host
             ls.Rf = pc.searchRadius;
-            ls.polyKind = polyKindIn;
+            ls.polyKind = kPlain ? 0 : polyKindIn;
             ls.radiusOk = true;
             const double R = static_cast<double>(pc.searchRadius);
             ls.lk.Rf = pc.searchRadius;
@@ -1194,8 +1169,8 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
     }
 
     double adjY = 0.0;  // ajustedPose_[1], cpp:759
-    const int nPhases = (gait == 1) ? 4 : 1;
-    const double advance = (gait == 1) ? pc.stepQuarter : pc.step;
+    const int nPhases = (!kPlain && gait == 1) ? 4 : 1;
+    const double advance = (!kPlain && gait == 1) ? pc.stepQuarter : pc.step;
     // swing order LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
     const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
     constexpr int kPoseLanes = 4 * G;
@@ -1245,8 +1220,8 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
         const YEntry& ye = ytab[cyc & (kBatch - 1)];
         bool cycleOk = true;
         for (int ph = 0; ph < nPhases; ++ph) {
-            const unsigned mask = (gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
-            const bool active = (mask >> leg) & 1u;
+            const unsigned mask = (!kPlain && gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
+            const bool active = kPlain || ((mask >> leg) & 1u) != 0u;  // (plain: every leg swings in the one phase)
             // feet-polygon centres (getPolygonCenter, cpp:2191, 2265): every lane computes ONE track's centre from the
             // committed feet in LDS; the values reach the group's other lanes by swizzle (no LDS hand-off, no barrier)
             const double myCtr = polygon_center_x(sh.cur[myTrack]);
@@ -1256,7 +1231,7 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
             lc.valid = 1;  // non-swing legs do not vote
             if (active) {
                 if constexpr (kMid) {
-                    leg_fast8m<NRL, kNoDefault, kProd>(m, bm, pc.winH, wantDefault, hc, role, fr, head, sh, lb, g, leg, ls, ye, myCtr, advance, cyc, &lc,
+                    leg_fast8m<NRL, kNoDefault, kProd, kPlain>(m, bm, pc.winH, wantDefault, hc, role, fr, head, sh, lb, g, leg, ls, ye, myCtr, advance, cyc, &lc,
                                                        units + (cyc & (kBatch - 1)));
                 } else {
                     constexpr int kKeep = (~(G - 1)) & 0x1F;
@@ -1298,6 +1273,64 @@ __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_ke
             bits_sync<G>();  // the units and the y entries are rewritten next
         }
     }
+}
+
+template <int NRL, bool kMid, int kProd>
+// (the pose pointer and the counts lead the argument list: scalar arguments at the head of the kernarg segment are
+// preloaded into SGPRs at wave launch, -amdgpu-kernarg-preload-count, so the pose loads can be issued at once)
+__global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles,
+                                                          DevMap mArg, BitMap bm, typename std::conditional<kMid, PlanMidConsts, PlanConsts>::type pc,
+                                                          SpiralLut lut, fpe_plan_out outArg) {
+    constexpr int G = 8;
+    const fpe_plan_out out = specialise_products<kProd>(outArg);
+    constexpr int kPoseThreads = 4 * G;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int slot = tid / kPoseThreads;
+    const int leg = (tid / G) & 3;
+    // the pose first: its address needs nothing but the preloaded arguments, and everything else waits for it
+    int b = blockIdx.x * 2 + slot;
+    const bool live = b < B;  // the padding pose of the last block runs the chain on pose B-1, stores nothing
+    if (!live) b = B - 1;
+    const fpe_pose* pp = poses + b;
+    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
+    const int gait = pp->gait;
+    const float rOverride = pp->leg_search_radius[leg];
+    const int polyKindIn = pp->leg_polygon_kind[leg];
+    __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
+    // the map geometry doubles are operands of vector f64 arithmetic only: parked in VGPRs (see plan_chained_kernel) — in
+    // the 3x3-only variants; the generic ones run at their register cap (168 VGPRs at three wavefronts per SIMD), where the
+    // twenty registers cost more in spills than the scalar operands do in moves (measured: cfg-4 0.713 -> 0.664 ms without)
+    DevMap m = mArg;
+    if constexpr (kMid) {
+        m.g.res = in_vgpr(m.g.res);
+        m.g.rinv = in_vgpr(m.g.rinv);
+        m.g.lenX = in_vgpr(m.g.lenX);
+        m.g.lenY = in_vgpr(m.g.lenY);
+        m.g.posX = in_vgpr(m.g.posX);
+        m.g.posY = in_vgpr(m.g.posY);
+        m.g.orgX = in_vgpr(m.g.orgX);
+        m.g.orgY = in_vgpr(m.g.orgY);
+        m.g.baseX = in_vgpr(m.g.baseX);
+        m.g.baseY = in_vgpr(m.g.baseY);
+    }
+    HotConsts hc;
+    hc.rf = in_vgpr(pc.rf);
+    hc.rf2 = in_vgpr(pc.rf2);
+    hc.cornerEps = in_vgpr(pc.cornerEps);
+    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
+    hc.drift = kMid ? in_vgpr(pc.drift) : pc.drift;  // (the generic variants run at their register cap: nothing extra parked)
+    // 3x3-only kernels: one verdict per wavefront.  PLAIN = both pose slots trot, no leg overrides its search radius, every
+    // search polygon is the rectangle: the reference planner's only case (one gait, one searchRadius_, getSearchPolygon).  The
+    // padding slot of an odd batch runs pose B-1 again and votes as that pose does.  Each verdict has its own copy of the rest
+    // of the kernel, inlined (as a callee the chain ran at 33.7 us instead of 24.7); the kernel's name and arguments stay.
+    if constexpr (kMid) {
+        if (__ballot(gait == 1 || rOverride > 0.0f || polyKindIn != 0) == 0ull) {
+            plan_bits_body<NRL, kMid, kProd, true>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, m, mArg, bm, pc, lut, out, hc, tid, slot,
+                                                   leg);
+            return;
+        }
+    }
+    plan_bits_body<NRL, kMid, kProd, false>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, m, mArg, bm, pc, lut, out, hc, tid, slot, leg);
 }
 
 static_assert(kernargs_mirror<decltype(plan_bits_kernel<2, true, 2>)>(
