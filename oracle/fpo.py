@@ -1,4 +1,6 @@
-"""ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see oracle/fpo_gridmap.hpp).
+"""ORACLE — TEST INFRASTRUCTURE ONLY.  Parity with the reference: pinned for the logic of FootholdPlanner.cpp by
+tests/golden/ref/ (the reference's own planner built on shims, oracle/ref_shim/); grid_map_core's semantics stay unpinned
+(see oracle/fpo_gridmap.hpp).
 
 ctypes loader for the CPU restatement (oracle/_build/libfpo.so).  Only tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the engine
@@ -114,7 +116,14 @@ class _Map(C.Structure):
 
 
 def build(force=False):
-    """Compile the oracle with the committed Makefile (g++, -ffp-contract=off)."""
+    """Compile the oracle with the committed Makefile (g++, -ffp-contract=off) and, where the reference tree is present,
+    the reference driver (build_reference_driver)."""
+    _build_lib(force)
+    build_reference_driver()
+    return _LIB_PATH
+
+
+def _build_lib(force=False):
     if force or not os.path.exists(_LIB_PATH) or any(
         os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(_LIB_PATH)
         for f in ("fpo_gridmap.hpp", "fpo_planner.hpp", "fpo_planner.cpp", "fpo_opt.cpp", "fpo_capi.cpp", "fpo_filters.cpp", "Makefile")
@@ -123,13 +132,33 @@ def build(force=False):
     return _LIB_PATH
 
 
+REF = os.environ.get("REF", "/root/reference")
+REF_DRIVER = os.path.join(_HERE, "_ref", "ref_driver")
+REF_DRIVER_STATUS = ""
+
+
+def build_reference_driver():
+    """oracle/_ref/ref_driver: the REFERENCE's own FootholdPlanner.cpp compiled verbatim, in place, against the shim headers
+    of oracle/ref_shim/ (Makefile target _ref/ref_driver; make rebuilds it when a shim, the driver or the reference is
+    newer).  Only where the reference tree is present; says in one line what it did."""
+    global REF_DRIVER_STATUS
+    src = os.path.join(REF, "foothold_planner", "src", "FootholdPlanner.cpp")
+    if not os.path.exists(src):
+        REF_DRIVER_STATUS = f"oracle/_ref/ref_driver skipped: no reference tree at {REF}"
+    else:
+        subprocess.check_call(["make", "-s", "-C", _HERE, "_ref/ref_driver", "REF=" + REF])
+        REF_DRIVER_STATUS = f"oracle/_ref/ref_driver built from the reference in place ({src})"
+    print("build:", REF_DRIVER_STATUS)
+    return REF_DRIVER_STATUS
+
+
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        build()
+        _build_lib()
         L = C.CDLL(_LIB_PATH)
         L.fpo_map_create.restype = C.c_void_p
         L.fpo_map_create.argtypes = [C.POINTER(_Map)]
@@ -157,6 +186,7 @@ def lib():
         L.fpo_solve_lattice.argtypes = [C.c_void_p] * 5 + [C.c_double] * 5 + [C.c_void_p] * 2
         L.fpo_plan_opt_forced.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.fpo_centroid_on_submap.argtypes = [C.c_void_p, C.c_void_p] + [C.c_double] * 6 + [C.c_float, C.c_void_p, C.c_void_p]
+        L.fpo_centroid_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_void_p]
         L.fpo_filter_defaults.argtypes = [C.c_void_p]
         L.fpo_filters.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         assert L.fpo_sizeof(0) == PARAMS_DTYPE.itemsize
@@ -323,6 +353,14 @@ class OracleMap:
         out = np.zeros(1, dtype=CENTROID_DTYPE)
         lib().fpo_centroid_method(self._h, _ptr(params), x, y, search_radius, _ptr(out))
         return out[0]
+
+    def centroid_rows(self, params, x, y, search_radius):
+        """checkFootholdUseCentroidMethod on this map with the band's rows: (record, code, begin_row, end_row)."""
+        params = np.ascontiguousarray(params, dtype=PARAMS_DTYPE).reshape(1)
+        out = np.zeros(1, dtype=CENTROID_DTYPE)
+        o3 = np.zeros(3, dtype=np.int32)
+        lib().fpo_centroid_rows(self._h, _ptr(params), x, y, search_radius, _ptr(out), _ptr(o3))
+        return out[0], int(o3[0]), int(o3[1]), int(o3[2])
 
     def mean_height(self, x, y, radius, h=0.01):
         return float(lib().fpo_mean_height(self._h, x, y, np.float32(radius), h))

@@ -1,4 +1,4 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see fpo_planner.hpp / fpo_gridmap.hpp).
+// ORACLE — TEST INFRASTRUCTURE ONLY.  Parity status: see fpo_planner.hpp (planner logic pinned) / fpo_gridmap.hpp (unpinned).
 // Plain C entry points so tests/, smoke() and bench.py's cpu_baseline leg can drive the CPU
 // restatement through ctypes.  Record layouts are documented in oracle/fpo.py (numpy dtypes).
 #include <algorithm>
@@ -460,6 +460,20 @@ int fpo_centroid_on_submap(const void* mapHandle, const Params* params, double s
     out->x = r.x; out->y = r.y; out->z = r.z; out->row = r.row; out->col = r.col; out->code = r.code;
     out6[0] = r.code; out6[1] = b; out6[2] = e; out6[3] = r.row; out6[4] = r.col; out6[5] = 1;
     return 1;
+}
+
+// checkFootholdUseCentroidMethod on the map itself with the caller's traversableBeginRow / traversableEndRow (cpp:1608-1609):
+// out3 = {code, beginRow, endRow}; the rows are 0 where the reference leaves them untouched (codes 5 and 6).
+int fpo_centroid_rows(const void* mapHandle, const Params* params, double x, double y, float searchRadius, fpo_centroid* out,
+                      int32_t* out3) {
+    const GridMap& map = *static_cast<const GridMap*>(mapHandle);
+    CentroidResult r;
+    int b = 0, e = 0;
+    checkFootholdUseCentroidMethod(map, {x, y}, searchRadius, *params, r, &map, &b, &e);
+    std::memset(out, 0, sizeof(*out));
+    out->x = r.x; out->y = r.y; out->z = r.z; out->row = r.row; out->col = r.col; out->code = r.code;
+    out3[0] = r.code; out3[1] = b; out3[2] = e;
+    return 0;
 }
 
 int fpo_sizeof(int which) {

@@ -1,8 +1,12 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY.  Nothing under oracle/ is part of the shipped engine; only
 // tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may build, load or call it.
 //
-// PARITY UNPINNED: the reference has no tests/golden vectors for this path and grid_map_core is not
-// vendored under /root/reference nor installed in this image.  This file is the
+// THIS FILE STAYS UNPINNED, and here is why: grid_map_core is not vendored under /root/reference nor installed in this
+// image, so the reference's planner can only be built against shim headers (oracle/ref_shim/) — and
+// the shim's grid_map CALLS THIS FILE for every piece of index / position arithmetic and every iterator order, so that
+// the project has one statement of those semantics and not a second recollection.  tests/golden/ref/ therefore pins the
+// logic of FootholdPlanner.cpp ON TOP of this file (fpo_planner.hpp lists what), never this file itself;
+// tests/probe/upstream_check.cpp is the one-command pin against the real library.  This file is the
 // ONE place that freezes the *assumed upstream semantics* of ANYbotics/grid_map 1.6.x
 // (grid_map_core/src/GridMapMath.cpp, GridMap.cpp, Polygon.cpp, iterators/*.cpp), restated
 // literally (iterator objects, vectors, operation order of every f64 expression) so that it can be
@@ -14,6 +18,7 @@
 // circular-buffer start index, so parity is only defined for canonical maps).
 #pragma once
 #include <cmath>
+#include <cstdlib>
 #include <cfloat>
 #include <cstdint>
 #include <limits>
@@ -353,6 +358,68 @@ private:
     double radius_, radiusSquare_;
     unsigned int nRings_, distance_;
     std::vector<Idx2> pointsRing_;
+};
+
+// ---- iterators/LineIterator.cpp (index form).  cpp:1733 -------------------------------------------
+// Bresenham walk from `start` to `end`, BOTH INCLUDED (nCells = max(|dx|, |dy|) + 1); the index form applies no range
+// check, so an end index outside the map is visited like any other (the reference passes (row, size(1)), cpp:1720).
+// Used by the reference shim only (oracle/ref_shim/); the restatement scans the in-range columns directly.
+class LineIterator {
+public:
+    LineIterator(const Idx2& start, const Idx2& end) : index_(start) {
+        const int dx = std::abs(end.i - start.i), dy = std::abs(end.j - start.j);
+        const int sx = end.i >= start.i ? 1 : -1, sy = end.j >= start.j ? 1 : -1;
+        inc1_ = {sx, sy};
+        inc2_ = {sx, sy};
+        if (dx >= dy) {
+            inc1_.i = 0;
+            inc2_.j = 0;
+            denominator_ = dx;
+            numerator_ = dx / 2;
+            numeratorAdd_ = dy;
+            nCells_ = dx + 1;
+        } else {
+            inc2_.i = 0;
+            inc1_.j = 0;
+            denominator_ = dy;
+            numerator_ = dy / 2;
+            numeratorAdd_ = dx;
+            nCells_ = dy + 1;
+        }
+    }
+    bool isPastEnd() const { return iCell_ >= nCells_; }
+    Idx2 operator*() const { return index_; }
+    LineIterator& operator++() {
+        numerator_ += numeratorAdd_;
+        if (numerator_ >= denominator_) {
+            numerator_ -= denominator_;
+            index_.i += inc1_.i;
+            index_.j += inc1_.j;
+        }
+        index_.i += inc2_.i;
+        index_.j += inc2_.j;
+        ++iCell_;
+        return *this;
+    }
+
+private:
+    Idx2 index_, inc1_, inc2_;
+    int denominator_ = 0, numerator_ = 0, numeratorAdd_ = 0, nCells_ = 0, iCell_ = 0;
+};
+
+// ---- iterators/GridMapIterator.cpp.  cpp:1651 -------------------------------------------------------
+// Linear index 0 .. rows*cols-1 over the column-major storage (start index 0): (i, j) = (k % rows, k / rows).
+class GridMapIterator {
+public:
+    explicit GridMapIterator(const Idx2& size) : size_(size), n_((size_t)size.i * (size_t)size.j) {}
+    bool isPastEnd() const { return k_ >= n_; }
+    size_t linearIndex() const { return k_; }
+    Idx2 operator*() const { return {(int)(k_ % (size_t)size_.i), (int)(k_ / (size_t)size_.i)}; }
+    GridMapIterator& operator++() { ++k_; return *this; }
+
+private:
+    Idx2 size_;
+    size_t n_, k_ = 0;
 };
 
 }  // namespace fpo

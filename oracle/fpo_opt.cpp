@@ -1,4 +1,11 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see fpo_planner.hpp / fpo_gridmap.hpp).
+// ORACLE — TEST INFRASTRUCTURE ONLY.
+// PARITY: the logic of FootholdPlanner.cpp is PINNED by tests/golden/ref/ (the reference's own planner compiled verbatim against
+// oracle/ref_shim/; tests/test_ref_golden.py requires this restatement to reproduce it bit for bit, z included): checkFoothold,
+// checkFootholdUseCentroidMethod, getFootholdMeanHeight, getDefaultFootholdNext, setFirstGait, getGaitCycleSearchGridMap, getMapIndex,
+// the per-cycle driver of globalFootholdPlan for all three tracks, the commit rule, the service's return value, the opt track's
+// objective and eight constraints.  STILL UNPINNED: grid_map_core's semantics (fpo_gridmap.hpp — the shim calls it too), NLopt's
+// COBYLA (the shim's optimiser is the build-defined lattice rule), the traversability filter package, everything build-defined
+// (walk gait, hexagon polygons, per-leg radii).
 // The "opt" track of globalFootholdPlan: /root/reference/foothold_planner/src/FootholdPlanner.cpp
 //   cpp:28-51    file-scope NLopt globals            cpp:54-88    nloptFunc (objective)
 //   cpp:92-148   nloptConstraint1..8                 cpp:913-1319 the per-cycle driver

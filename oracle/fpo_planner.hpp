@@ -1,5 +1,12 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY (see fpo_gridmap.hpp header).  PARITY UNPINNED: the
-// reference has no tests / golden vectors for this path; fidelity is argued by citation.
+// ORACLE — TEST INFRASTRUCTURE ONLY (see fpo_gridmap.hpp header).
+// PARITY: the logic of FootholdPlanner.cpp is PINNED by tests/golden/ref/ (the reference's own planner compiled verbatim against
+// oracle/ref_shim/; tests/test_ref_golden.py requires this restatement to reproduce it bit for bit, z included): checkFoothold,
+// checkFootholdUseCentroidMethod, getFootholdMeanHeight, getDefaultFootholdNext, setFirstGait, getGaitCycleSearchGridMap, getMapIndex,
+// the per-cycle driver of globalFootholdPlan for all three tracks, the commit rule, the service's return value, the opt track's
+// objective and eight constraints.  STILL UNPINNED: grid_map_core's semantics (fpo_gridmap.hpp — the shim calls it too), NLopt's
+// COBYLA (the shim's optimiser is the build-defined lattice rule), the traversability filter package, everything build-defined
+// (walk gait, hexagon polygons, per-leg radii).  The centroid method's codes 1-5 are pinned to the reference WITH ITS READ ONE
+// COLUMN PAST THE LAYER RETURNING NaN (cpp:1719-1736; the shim defines that read): the real library reads foreign memory there.
 //
 // CPU restatement of the reference's foothold-search hot path
 // (/root/reference/foothold_planner/src/FootholdPlanner.cpp, "cpp:" below; header "hpp:").

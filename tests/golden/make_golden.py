@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Generate the committed golden vectors (tests/golden/*.npz).
 
-PROVENANCE: the reference (lukechencqu/quadrupedal_foothold_planner) has no tests, no golden
-vectors and cannot be built in this image (needs ROS1, grid_map_core, Eigen, NLopt), so these
-vectors are produced by THIS repo's oracle (oracle/, the CPU restatement of the reference's
-algorithm) — "parity unpinned" beyond the analytic KATs in tests/test_oracle_kat.py.  They freeze
+PROVENANCE: these vectors are produced by THIS repo's oracle (oracle/, the CPU restatement of the
+reference's algorithm).  The four trot vectors and their opt variants are cross-checked against the
+reference's own planner built on shims (tests/golden/make_ref_golden.py, tests/test_ref_golden.py),
+which pins the logic of FootholdPlanner.cpp (checkFoothold, checkFootholdUseCentroidMethod,
+getFootholdMeanHeight, getDefaultFootholdNext, setFirstGait, getGaitCycleSearchGridMap, getMapIndex,
+the per-cycle driver of globalFootholdPlan for all three tracks, the commit rule, the service's return
+value, the opt track's objective and eight constraints); grid_map_core's semantics, NLopt's COBYLA, the
+traversability filter package and everything build-defined (the walk gait, hexagon polygons, per-leg
+radii: walk_hex_2cm) stay unpinned.  They freeze
 the oracle's behaviour so that later edits to either the oracle or the engine are caught.
 
 Inputs are tiny seeded maps (<= 96x96 cells) with steps, holes, NaN and +-inf; outputs are the full
