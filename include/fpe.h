@@ -288,7 +288,9 @@ const char* fpe_version(void);
 /* Layout version of the structs this header passes by pointer (fpe_plan_out, fpe_opt_out, fpe_params, ... have no size
  * field: fields are only ever APPENDED, and every append bumps this number).  A host compiled against this header checks
  * fpe_abi_version() == FPE_ABI_VERSION once after loading the library — a library that reads a longer struct than the host
- * passes would take whatever lies behind it for a device pointer (csrc/ros_adapter/fpe_ros_adapter.hpp and _capi.py do). */
+ * passes would take whatever lies behind it for a device pointer (csrc/ros_adapter/fpe_ros_adapter.hpp and _capi.py do).
+ * A NEW struct with new entry points (fpe_stride and the fpe_*_strides* calls) is not an append to an existing struct: it leaves
+ * every layout a version-5 host passes as it was, so the number stays 5. */
 #define FPE_ABI_VERSION 5
 int fpe_abi_version(void);
 
@@ -668,6 +670,49 @@ int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params*
 int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses,
                          int32_t B, int32_t n_cycles, int32_t K, const fpe_plan_out* d_full /* may be NULL */,
                          const fpe_rank_out* d_out, void* stream);
+
+/* ---- per-pose stride: step length and lateral drift as a parallel array ---------------------------------------------------------
+ * BUILD-DEFINED (the reference has one stepLength_ and one hard-coded drift).  strides[b] belongs to poses[b]: pose b's products are
+ * exactly what fpe_plan returns for that pose ALONE with params->stepLength = strides[b].step_length and params->lateralDrift =
+ * strides[b].lateral_drift, every other parameter shared by the batch; its summary, score and rank are likewise what fpe_plan_rank
+ * computes for it with those two values.  The constants follow the reference's typing (derive_constants): step = double(s),
+ * stepHalf = double(s / 2) and stepQuarter = double(s / 4) with the divisions in float, drift = d — so this covers pose_status
+ * (the first cycle's gate adds `step`), the walk gait (stepQuarter) and the ranking's cog_speed_* (their first current feet are
+ * stance - stepHalf).  Nothing the host proves about windows, discs, rings or rectangles depends on either value.
+ * strides == NULL is fpe_plan / fpe_plan_rank itself: the same checks, the same kernel as today.
+ * Kernels: every plan kernel family has a stride instantiation (fpe_describe_plan_strides names the one a stride call launches,
+ * "... stride (...)").  There is no stride form of the 3x3-only 8-lane variants: a stride call on such a configuration runs the
+ * generic variant, which computes the same products (what "no_mid_variant" 1 runs), more slowly.  The direct kernels have stride
+ * forms at the automatic group sizes (8 lanes per leg, one wavefront per pose = "plan_group" 65); a stride call under a forced
+ * "plan_group" of 4, 16 or 64 returns FPE_E_UNSUPPORTED.
+ * Refusals, host forms: a non-finite step_length or lateral_drift, or reserved != 0, in ANY element returns FPE_E_INVALID_ARG and
+ * writes nothing; any finite value is taken, zero and negative included (what validate_params takes for the two parameters).
+ * Device forms cannot look at the values.  A non-finite stride takes the path a non-finite pose position takes today — every leg
+ * centre derived from it fails centre_usable ahead of any index: a non-finite step_length gives, in every cycle, nominal records
+ * with valid 0, source 2, row = col = -1 and the non-finite centre as x / y, centroid records of code 6 (zeros, row = col = -1),
+ * default_next holding the non-finite positions with z = h, cycle_ok 0, and pose_status FPE_POSE_OPT_SUBMAP_FAILED; a non-finite
+ * lateral_drift leaves cycle 0 (which has seen no drift yet) and pose_status as planned and gives every later cycle those records.
+ * reserved is not read by the kernels.
+ * Out of scope, unchanged: the opt track (fpe_plan_opt*), the service calls (fpe_plan_service*), fpe_multi_* (and dist.py) — all of
+ * them keep the one stride of fpe_params — and stride forms of the 3x3-only ("MID") kernels (above). */
+typedef struct fpe_stride {   /* 16 bytes; element b belongs to poses[b] */
+    float   step_length;      /* replaces fpe_params.stepLength for this pose */
+    int32_t reserved;         /* 0 */
+    double  lateral_drift;    /* replaces fpe_params.lateralDrift for this pose */
+} fpe_stride;
+/* fpe_plan / fpe_plan_device with one stride per pose (host array / device array of B elements, or NULL). */
+int fpe_plan_strides(fpe_handle h, const fpe_params* params, const fpe_pose* poses, const fpe_stride* strides, int32_t B,
+                     int32_t n_cycles, const fpe_plan_out* out);
+int fpe_plan_strides_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_poses, const fpe_stride* d_strides, int32_t B,
+                            int32_t n_cycles, const fpe_plan_out* d_out, void* stream);
+/* fpe_plan_rank / fpe_plan_rank_device with one stride per pose: the candidates of ONE ranking may differ in stride. */
+int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses,
+                          const fpe_stride* strides, int32_t B, int32_t n_cycles, int32_t K, const fpe_rank_out* out);
+int fpe_plan_rank_strides_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses,
+                                 const fpe_stride* d_strides, int32_t B, int32_t n_cycles, int32_t K,
+                                 const fpe_plan_out* d_full /* may be NULL */, const fpe_rank_out* d_out, void* stream);
+/* fpe_describe_plan for the kernel a stride call (strides != NULL) launches on the current map. */
+int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf, int32_t n);
 
 /* ---- the dense maps as grid_map message layers: the inverse of fpe_upload_map's ingest ----------------------------------
  * BUILD-DEFINED (the reference publishes none of these layers).  One call runs the dense families whose layers are requested —

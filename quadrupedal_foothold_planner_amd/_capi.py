@@ -51,6 +51,8 @@ CENTROID_DTYPE = np.dtype(
     [("x", "<f8"), ("y", "<f8"), ("z", "<f4"), ("row", "<i4"), ("col", "<i4"), ("code", "u1"), ("pad", "u1", (3,))],
     align=True,
 )
+# fpe_stride: step length and lateral drift of ONE pose (fpe_plan_strides*, fpe_plan_rank_strides*); element b belongs to poses[b]
+STRIDE_DTYPE = np.dtype([("step_length", "<f4"), ("reserved", "<i4"), ("lateral_drift", "<f8")], align=True)
 # fpe_selected_foothold: the 16-byte multi-GPU exchange record
 SELECTED_DTYPE = np.dtype(
     [("row", "<i4"), ("col", "<i4"), ("z", "<f4"), ("valid", "u1"), ("source", "u1"), ("foot_id", "u1"), ("gait_cycle_id", "u1")],
@@ -257,7 +259,7 @@ STRUCTS = {
     "fpe_track_report": TRACK_REPORT_DTYPE, "fpe_multi_device_io": MultiDeviceIO, "fpe_foothold_map_out": FootholdMapOut,
     "fpe_foothold_snap_out": FootholdSnapOut, "fpe_centroid_query": CentroidQuery, "fpe_centroid_map_out": CentroidMapOut,
     "fpe_pose_summary": PoseSummary, "fpe_rank_params": RankParams, "fpe_rank_out": RankOut, "fpe_layer_layout": LayerLayout,
-    "fpe_layer_request": LayerRequest,
+    "fpe_layer_request": LayerRequest, "fpe_stride": STRIDE_DTYPE,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -321,6 +323,11 @@ PROTOTYPES = {
     "fpe_plan_rank_device": (cint, [vp, vp, P(RankParams), vp, i32, i32, i32, P(PlanOut), P(RankOut), vp]),
     "fpe_export_layers": (cint, [vp, vp, vp, P(LayerLayout), P(LayerRequest)]),
     "fpe_export_layers_device": (cint, [vp, vp, vp, P(LayerLayout), P(LayerRequest), vp]),
+    "fpe_plan_strides": (cint, [vp, vp, vp, vp, i32, i32, P(PlanOut)]),
+    "fpe_plan_strides_device": (cint, [vp, vp, vp, vp, i32, i32, P(PlanOut), vp]),
+    "fpe_plan_rank_strides": (cint, [vp, vp, P(RankParams), vp, vp, i32, i32, i32, P(RankOut)]),
+    "fpe_plan_rank_strides_device": (cint, [vp, vp, P(RankParams), vp, vp, i32, i32, i32, P(PlanOut), P(RankOut), vp]),
+    "fpe_describe_plan_strides": (cint, [vp, vp, cstr, i32]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

@@ -116,7 +116,24 @@ bool bits_supported(const PlanConsts& pc, const MapGeom& g) {
 }
 
 // Which kernel a chained plan with these constants launches (evidence for bench.py / profiles).
-void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n) {
+// strides: the kernel a stride call (fpe_plan_strides*) launches — "<kernel> stride (...)"; the 3x3-only variants have no stride form.
+void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, bool strides) {
+    if (strides) {
+        if (bits_supported(pc, g)) {
+            const BitsShape sp = bits_shape(pc.winH);
+            if (sp.lanes == 8)
+                snprintf(buf, n, "plan_bits_kernel<%d, false> stride (8 lanes per leg, %d x %d bit window)", sp.nrl, 2 * pc.winH + 1, 2 * pc.winH + 1);
+            else
+                snprintf(buf, n, "plan_bits_seq_kernel<%d, %d> stride (one wavefront per pose, %d x %d bit window, %d-bit rows)", sp.nrl, sp.kw,
+                         2 * pc.winH + 1, 2 * pc.winH + 1, 32 * sp.kw);
+            return;
+        }
+        const int G = plan_group_size(pc);
+        if (G == 65) snprintf(buf, n, "plan_sequential_kernel stride (direct, one wavefront per pose)");
+        else if (G == 8) snprintf(buf, n, "plan_chained_kernel<8, false> stride (direct)");
+        else snprintf(buf, n, "no stride kernel for plan_group %d", G);
+        return;
+    }
     if (bits_supported(pc, g)) {
         const BitsShape sp = bits_shape(pc.winH);
         const bool mid = mid_variant(pc, g.res) && pc.nFoot == 1;
@@ -140,8 +157,53 @@ static auto bits_kernel_consts(const PlanConsts& pc) {
     else return pc;
 }
 
+// The stride form of launch_plan_bits (fpe_plan_strides*): the same shapes, grids and LDS; one instantiation per family member —
+// the any-combination product mask (kProd 0), the generic 8-lane variants, and the group sizes the launch below can reach.
+static hipError_t launch_plan_bits_strides(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
+                                           int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides) {
+    const BitsShape sp = bits_shape(pc.winH);
+    const dim3 block(64);
+#define FPE_LAUNCH_BITS_STRIDE(NRL)                                                                                                   \
+    hipLaunchKernelGGL((plan_bits_stride_kernel<NRL, 0>), dim3((B + 1) / 2), block,                                                  \
+                       2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW) + (sizeof(YEntry) + sizeof(UnitG)) * 16), stream, \
+                       d_poses, B, nCycles, m, bm, pc, lut, d_out, d_strides)
+#define FPE_LAUNCH_BITS_SEQ_STRIDE_G(NRL, KW, GRP, GRID, LDS, SLOT)                                                                     \
+    do {                                                                                                                              \
+        if ((LDS) > 64 * 1024) {                                                                                                      \
+            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>),   \
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(LDS));             \
+            if (ea != hipSuccess) return ea;                                                                                          \
+        }                                                                                                                             \
+        hipLaunchKernelGGL((plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B, \
+                           nCycles, d_out, recSlots, static_cast<int>(SLOT), d_strides);                                              \
+    } while (0)
+    if (sp.lanes == 8) {
+        if (sp.nrl == 2) FPE_LAUNCH_BITS_STRIDE(2);
+        else if (sp.nrl == 3) FPE_LAUNCH_BITS_STRIDE(3);
+        else FPE_LAUNCH_BITS_STRIDE(4);
+    } else if (sp.lanes == 64) {
+        // (slot size, staged cycles and the sixteen-pose workgroups exactly as launch_plan_bits has them)
+        const int nrl = sp.nrl, kw = sp.kw;
+        const size_t base = (sizeof(PoseShared) + ((4 * sizeof(LegStatic) + 15) & ~static_cast<size_t>(15)) +
+                             4 * legbits_words(2 * pc.winH + 1 < 64 * nrl ? 2 * pc.winH + 1 : 64 * nrl, kw, pc.nHW) + 15) &
+                            ~static_cast<size_t>(15);
+        int recSlots = 8;
+        while (recSlots > 1 && base + recSlots * 4 * sizeof(SeqRec) > 10240) recSlots >>= 1;
+        const size_t slot = (base + recSlots * 4 * sizeof(SeqRec) + 15) & ~static_cast<size_t>(15);
+        if (kw == 2) FPE_LAUNCH_BITS_SEQ_STRIDE_G(1, 2, 1, B, slot, slot);
+        else if (B >= 64 && 16 * slot <= 160 * 1024) FPE_LAUNCH_BITS_SEQ_STRIDE_G(2, 3, 16, (B + 15) / 16, 16 * slot, slot);
+        else FPE_LAUNCH_BITS_SEQ_STRIDE_G(2, 3, 1, B, slot, slot);
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef FPE_LAUNCH_BITS_STRIDE
+#undef FPE_LAUNCH_BITS_SEQ_STRIDE_G
+    return hipGetLastError();
+}
+
 hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                            int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream) {
+                            int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides) {
+    if (d_strides) return launch_plan_bits_strides(m, bm, pc, lut, d_poses, B, nCycles, d_out, stream, d_strides);
     const BitsShape sp = bits_shape(pc.winH);
     const bool mid = mid_variant(pc, m.g.res) && pc.nFoot == 1;  // rf < res: the candidate disc is the candidate's own cell
     const dim3 block(64);

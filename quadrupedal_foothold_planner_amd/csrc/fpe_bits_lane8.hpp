@@ -1042,15 +1042,18 @@ constexpr int kBitsGenericWaves = 3;  // measured on cfg-4: 2 -> 1.36 ms, 3 -> 1
 // the gate of the first cycle, the cycle loop with its flushes.  kPlain (3x3-only kernels, decided per wavefront by the kernel):
 // both poses trot, no leg overrides the search radius, every search polygon is the rectangle — one phase a cycle with all four
 // legs swinging (no phase loop, no swing mask), advance = step, and the legs' search constants are the plan's own (uniform).
-// kPlain = false is the general code.  Always inlined into the kernel.
+// kPlain = false is the general code.  Always inlined into the kernel.  kStride (plan_bits_stride_kernel): step and drift are the
+// pose's own (sv, and hc.drift filled from it by the kernel) instead of the plan's.
 // (The LDS views and the rank table's head are set up HERE, once per copy, not in the kernel ahead of the verdict: a value both
 // copies read has to be computed in front of the branch and stays in its register through either copy, where one copy's own
 // value is computed next to its use — with them in the kernel the <4, true, *> instances spilled four vector registers.)
-template <int NRL, bool kMid, int kProd, bool kPlain, class PC>
+template <int NRL, bool kMid, int kProd, bool kPlain, bool kStride = false, class PC>
 __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool live, double x0, double y0, double z0, int gait, float rOverride,
                                                int polyKindIn, int nCycles, const DevMap& m, const DevMap& mArg, const BitMap& bm, const PC& pc,
-                                               const SpiralLut& lut, const fpe_plan_out& out, const HotConsts& hc, int tid, int slot, int leg) {
+                                               const SpiralLut& lut, const fpe_plan_out& out, const HotConsts& hc, int tid, int slot, int leg,
+                                               const StrideVals& sv = StrideVals{}) {
     static_assert(kMid || !kPlain, "the generic kernels have no plain instance");
+    static_assert(!kMid || !kStride, "the 3x3-only kernels have no stride instance");
     constexpr int G = 8;
     constexpr bool kNoDefault = kProd == 1;
     constexpr int kPoseThreads = 4 * G;
@@ -1126,7 +1129,7 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             st[2] = sz;
         }
         for (int t = 0; t < 3; ++t) {
-            sh.cur[t][leg][0] = sx - pc.stepHalf;
+            sh.cur[t][leg][0] = sx - (kStride ? sv.stepHalf : pc.stepHalf);
             sh.cur[t][leg][1] = sy;
             sh.cur[t][leg][2] = sz;
         }
@@ -1134,7 +1137,7 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
     bits_sync<G>();
     if (out.pose_status) {
         // getGaitCycleSearchGridMap's getSubmap in the first cycle (opt_gate_cycle0), its four corners on four lanes
-        const double gx = polygon_center_x(sh.cur[0]) + pc.step, gy = y0 + 0.0;  // cpp:2327-2329
+        const double gx = polygon_center_x(sh.cur[0]) + (kStride ? sv.step : pc.step), gy = y0 + 0.0;  // cpp:2327-2329
         Submap gs;
         {
             // lane q & 3: 0 top-left x, 1 top-left y, 2 bottom-right x, 3 bottom-right y — predicted as in the x pass
@@ -1170,7 +1173,7 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
 
     double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (!kPlain && gait == 1) ? 4 : 1;
-    const double advance = (!kPlain && gait == 1) ? pc.stepQuarter : pc.step;
+    const double advance = (!kPlain && gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
     // swing order LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
     const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
     constexpr int kPoseLanes = 4 * G;
@@ -1338,3 +1341,37 @@ static_assert(kernargs_mirror<decltype(plan_bits_kernel<2, true, 2>)>(
                    offsetof(MidKernArgs, bm), offsetof(MidKernArgs, pc), offsetof(MidKernArgs, lut), offsetof(MidKernArgs, out)},
                   offsetof(MidKernArgs, out) + sizeof(MidKernArgs::out)),
               "MidKernArgs must mirror the parameters of plan_bits_kernel<NRL, true, kProd>");
+
+// The stride form of the generic 8-lane kernel (fpe_plan_strides*): the same body, with the step and the drift of each pose slot read
+// from strides[b] — one 16-byte record per pose, loaded next to the pose — and `strides` as the one TRAILING argument behind
+// plan_bits_kernel's own list.  Generic variants only: a stride call on a 3x3-only configuration runs this kernel (the two are
+// pinned equivalent under no_mid_variant).
+template <int NRL, int kProd>
+__global__ __launch_bounds__(64, kBitsGenericWaves) void plan_bits_stride_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, DevMap mArg, BitMap bm,
+                                                                                PlanConsts pc, SpiralLut lut, fpe_plan_out outArg,
+                                                                                const fpe_stride* __restrict__ strides) {
+    constexpr int G = 8;
+    const fpe_plan_out out = specialise_products<kProd>(outArg);
+    constexpr int kPoseThreads = 4 * G;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int slot = tid / kPoseThreads;
+    const int leg = (tid / G) & 3;
+    int b = blockIdx.x * 2 + slot;
+    const bool live = b < B;  // the padding pose of the last block runs the chain on pose B-1 (with ITS stride), stores nothing
+    if (!live) b = B - 1;
+    const fpe_pose* pp = poses + b;
+    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
+    const int gait = pp->gait;
+    const float rOverride = pp->leg_search_radius[leg];
+    const int polyKindIn = pp->leg_polygon_kind[leg];
+    const StrideVals sv = load_stride(strides, b);
+    __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
+    HotConsts hc;
+    hc.rf = in_vgpr(pc.rf);
+    hc.rf2 = in_vgpr(pc.rf2);
+    hc.cornerEps = in_vgpr(pc.cornerEps);
+    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
+    hc.drift = sv.drift;  // per pose slot: the y-table fill and the per-cycle sum add the pose's own drift
+    plan_bits_body<NRL, false, kProd, false, true>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, mArg, mArg, bm, pc, lut, out, hc, tid, slot, leg,
+                                                   sv);
+}

@@ -299,6 +299,8 @@ struct SeqKernArgs {
     int B, nCycles;
     fpe_plan_out out;
     int recSlots;
+    int slotBytes;
+    const fpe_stride* strides;  // the one trailing argument of the kernel's stride form (not in the segment otherwise: never read there)
 };
 // The argument reload pays on the 96-bit-row instantiations only — measured, round 6, A/B in one call, twice:
 // cfg-5 (<2, 3>) 0.3060 -> 0.3017 ms and its 32 B of vector scratch gone; cfg-3 (<1, 2>) 0.6075 -> 0.6211 ms although three quarters of
@@ -310,7 +312,9 @@ constexpr bool kSeqReloadArgs = KW >= 3;
 // arguments in scalar registers the allocator spills to vector lanes (no spilled scalars in the kernel, 60-150 before: cfg-3 0.6046 ->
 // 0.5959 ms), and the kernel can put SIXTEEN poses in one workgroup (one workgroup per CU instead of sixteen: cfg-5 0.3023 -> 0.2959 ms;
 // plan_bits_seq_kernel below).  A/B in one call, three repetitions: profiles/round6_seq_floor.txt.
-template <int NRL, int KW, int kProd>
+// kStride (the kernel's stride form): the step and the drift are the pose's own, scalar loads of strides[b] through the argument
+// segment's trailing pointer.
+template <int NRL, int KW, int kProd, bool kStride = false>
 __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attribute__((address_space(4))) * kaIn, int slotOffIn, int bInV, int tid, unsigned hwidIn,
                                                        const LutHead& head) {
     constexpr int G = 64;
@@ -351,6 +355,8 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
     const fpe_pose* pp = poses + b;
     const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
     const int gait = pp->gait;
+    StrideVals sv{};
+    if constexpr (kStride) sv = load_stride(kaG->strides, b);
     for (int k = tid; k < pc.nFoot; k += G) {
         sh.footDa[k] = pc.footDa[k];
         sh.footDb[k] = pc.footDb[k];
@@ -373,17 +379,17 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
             st[2] = sz;
         }
         for (int t = 0; t < 3; ++t) {
-            sh.cur[t][leg][0] = sx - pc.stepHalf;
+            sh.cur[t][leg][0] = sx - (kStride ? sv.stepHalf : pc.stepHalf);
             sh.cur[t][leg][1] = sy;
             sh.cur[t][leg][2] = sz;
         }
     }
     pose_sync<16>();
-    if (out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0(m.g, pc, polygon_center_x(sh.cur[0]), y0);
+    if (out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
 
     double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (gait == 1) ? 4 : 1;
-    const double advance = (gait == 1) ? pc.stepQuarter : pc.step;
+    const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
     const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
 
     const int cycLag = (static_cast<int>(hwid & 3u) * nCycles) / 16;  // launch order of this wavefront on its SIMD (HW_ID.WAVE_ID: 0 oldest .. 3) x a sixteenth of the cycles
@@ -468,7 +474,7 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
             cycleOk = cycleOk && phaseOk;
         }
         if (tid == 0 && out.cycle_ok) out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
-        adjY += pc.drift;  // cpp:1578
+        adjY += kStride ? sv.drift : pc.drift;  // cpp:1578
         {   // the staged records of the last recSlots cycles: lane = (cycle slot, leg)
             const int slot = cyc & (recSlots - 1);
             if (slot == recSlots - 1 || cyc == nCycles - 1) {
@@ -499,10 +505,13 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
 
 // The kernel: kGroup wavefronts — poses — per workgroup, each runs seq_run_pose on its own slot of the workgroup's LDS.  kGroup 16 (one
 // workgroup of 1 024 threads per CU; the launch's choice for batches of at least 64 poses on the 96-bit-row windows) or 1.
-template <int NRL, int KW, int kProd, int kGroup>
+// Stride form (fpe_plan_strides*): S = {const fpe_stride*}, ONE trailing argument behind slotBytes, which the callee reads through
+// SeqKernArgs::strides.  S empty (the default): the kernel and its argument segment as they always were.
+template <int NRL, int KW, int kProd, int kGroup, class... S>
 __global__ __launch_bounds__(64 * kGroup, kGroup == 1 ? kSeqWaves : 1) void plan_bits_seq_kernel(DevMap m, BitMap bm, PlanConsts pc, SpiralLut lut,
                                                                                                 const fpe_pose* __restrict__ poses, int B, int nCycles, fpe_plan_out outArg,
-                                                                                                int recSlots, int slotBytes) {
+                                                                                                int recSlots, int slotBytes, S... strideArg) {
+    static_assert(sizeof...(S) <= 1, "one optional trailing argument: the strides");
     const int tid = static_cast<int>(threadIdx.x) & 63, wv = static_cast<int>(threadIdx.x) >> 6;
     const int b = static_cast<int>(blockIdx.x) * kGroup + wv;
     if (b >= B) return;
@@ -511,8 +520,9 @@ __global__ __launch_bounds__(64 * kGroup, kGroup == 1 ? kSeqWaves : 1) void plan
     unsigned hwid;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
     (void)m; (void)bm; (void)poses; (void)nCycles; (void)outArg; (void)recSlots;
+    ((void)strideArg, ...);
     typedef const SeqKernArgs __attribute__((address_space(4))) * KernArgPtr0;
-    seq_run_pose<NRL, KW, kProd>((KernArgPtr0)__builtin_amdgcn_kernarg_segment_ptr(), wv * slotBytes, b, tid, hwid, head);
+    seq_run_pose<NRL, KW, kProd, sizeof...(S) != 0>((KernArgPtr0)__builtin_amdgcn_kernarg_segment_ptr(), wv * slotBytes, b, tid, hwid, head);
 }
 static_assert(kernargs_mirror<decltype(plan_bits_seq_kernel<1, 2, 0, 1>)>(
                   {offsetof(SeqKernArgs, m), offsetof(SeqKernArgs, bm), offsetof(SeqKernArgs, pc), offsetof(SeqKernArgs, lut),
@@ -520,3 +530,9 @@ static_assert(kernargs_mirror<decltype(plan_bits_seq_kernel<1, 2, 0, 1>)>(
                    offsetof(SeqKernArgs, recSlots)},
                   offsetof(SeqKernArgs, recSlots) + sizeof(SeqKernArgs::recSlots)),
               "SeqKernArgs must mirror plan_bits_seq_kernel's parameters");
+static_assert(kernargs_mirror<decltype(plan_bits_seq_kernel<1, 2, 0, 1, const fpe_stride*>)>(
+                  {offsetof(SeqKernArgs, m), offsetof(SeqKernArgs, bm), offsetof(SeqKernArgs, pc), offsetof(SeqKernArgs, lut),
+                   offsetof(SeqKernArgs, poses), offsetof(SeqKernArgs, B), offsetof(SeqKernArgs, nCycles), offsetof(SeqKernArgs, out),
+                   offsetof(SeqKernArgs, recSlots), offsetof(SeqKernArgs, slotBytes), offsetof(SeqKernArgs, strides)},
+                  offsetof(SeqKernArgs, strides) + sizeof(SeqKernArgs::strides)),
+              "SeqKernArgs must mirror the parameters of plan_bits_seq_kernel's stride form");

@@ -1285,7 +1285,7 @@ int fpe_set_tuning(fpe_handle h, const char* key, int32_t value) {
     return FPE_OK;
 }
 
-int fpe_describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n) {
+static int describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n, bool strides) {
     if (!h || !params || !buf || n <= 0) return fail(FPE_E_INVALID_ARG, "null argument");
     std::shared_ptr<MapSnapshot> snap;
     fpe::Tuning tuning;
@@ -1299,9 +1299,11 @@ int fpe_describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t
     if (!snap) return fail(FPE_E_NO_MAP, "no map uploaded");
     fpe::PlanConsts pc;
     fpe::derive_constants(*params, snap->g, maxRadius, tuning, pc);
-    fpe::describe_plan_kernel(pc, snap->g, buf, static_cast<size_t>(n));
+    fpe::describe_plan_kernel(pc, snap->g, buf, static_cast<size_t>(n), strides);
     return FPE_OK;
 }
+int fpe_describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, false); }
+int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, true); }
 
 int fpe_set_max_leg_search_radius(fpe_handle h, float radius) {
     if (!h || !(radius >= 0.0f) || !std::isfinite(radius)) return fail(FPE_E_INVALID_ARG, "bad radius");
@@ -1487,27 +1489,42 @@ int fpe_map_info(fpe_handle h, fpe_map_desc* out) {
 }
 
 // One chained-plan launch on `stream`: the bit-window kernels when the snapshot's bit planes apply, else the direct ones.
+// d_strides (null: none): the stride form, fpe_plan_strides* / fpe_plan_rank_strides*.
+static int check_strides_launchable(const CallPlan& cp, const fpe_stride* d_strides) {
+    if (d_strides && !cp.useBits && !fpe::plan_chained_strides_supported(cp.pc))
+        return fail(FPE_E_UNSUPPORTED, "per-pose strides: no stride kernel for a forced plan_group of 4, 16 or 64");
+    return FPE_OK;
+}
 static int launch_plan(fpe_engine* h, const CallPlan& cp, const fpe_pose* d_poses, int32_t B, int32_t n_cycles,
-                       const fpe_plan_out& d_out, hipStream_t stream) {
-    const int rc = check_packed_fits(cp, d_out.selected_packed != nullptr);
+                       const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr) {
+    int rc = check_packed_fits(cp, d_out.selected_packed != nullptr);
+    if (rc != FPE_OK) return rc;
+    rc = check_strides_launchable(cp, d_strides);
     if (rc != FPE_OK) return rc;
     if (cp.useBits)
-        FPE_HIP(fpe::launch_plan_bits(dev_map(*cp.snap), cp.bits, cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream));
+        FPE_HIP(fpe::launch_plan_bits(dev_map(*cp.snap), cp.bits, cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides));
     else
-        FPE_HIP(fpe::launch_plan_chained(dev_map(*cp.snap), cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream));
+        FPE_HIP(fpe::launch_plan_chained(dev_map(*cp.snap), cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides));
     return FPE_OK;
 }
 
 int fpe_plan_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_poses, int32_t B, int32_t n_cycles,
                     const fpe_plan_out* d_out, void* stream) {
+    return fpe_plan_strides_device(h, params, d_poses, nullptr, B, n_cycles, d_out, stream);
+}
+
+int fpe_plan_strides_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_poses, const fpe_stride* d_strides, int32_t B,
+                            int32_t n_cycles, const fpe_plan_out* d_out, void* stream) {
     if (!d_poses || !d_out) return fail(FPE_E_INVALID_ARG, "null argument");
     if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
     hipStream_t st = static_cast<hipStream_t>(stream);
     CallPlan cp;
     int rc = prepare_call(h, params, 0.0f, cp, st, true);
     if (rc != FPE_OK) return rc;
+    rc = check_strides_launchable(cp, d_strides);  // (a refusal queues nothing: ahead of the async mark)
+    if (rc != FPE_OK) return rc;
     mark_async_launch(cp);
-    return launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st);
+    return launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st, d_strides);
 }
 
 namespace {
@@ -1543,21 +1560,34 @@ int check_host_poses(const fpe_pose* poses, int32_t B, float& maxRadius) {
     return FPE_OK;
 }
 
+// The strides of a host-buffer call (null: none), checked: finite values, reserved 0.
+int check_host_strides(const fpe_stride* strides, int32_t B) {
+    if (!strides) return FPE_OK;
+    for (int b = 0; b < B; ++b) {
+        if (!std::isfinite(strides[b].step_length) || !std::isfinite(strides[b].lateral_drift))
+            return fail(FPE_E_INVALID_ARG, "non-finite stride");
+        if (strides[b].reserved != 0) return fail(FPE_E_INVALID_ARG, "fpe_stride.reserved must be 0");
+    }
+    return FPE_OK;
+}
+
 struct GateGeom {  // what the service call's host-side (lateral) gate needs from the call's snapshot and constants
     fpe::MapGeom g;
     double isosLen, isosWid, drift;
 };
 
 // Where a host-form plan call keeps everything in its two arenas, one device and one pinned, at the same offsets, from the product
-// table: [poses | nominal | centroid | default | cycle_ok | stance | selected | status | packed | opt footholds | opt cycles | gate
-// | rows | speculative flags | completion word], in 256-byte steps; a product that is not part of the call takes no room.
+// table: [poses | strides | nominal | centroid | default | cycle_ok | stance | selected | status | packed | opt footholds | opt cycles
+// | gate | rows | speculative flags | completion word], in 256-byte steps; the strides (fpe_plan_strides) next to the poses; a product that is not part of the call takes no room.
 struct PlanLayout {
     size_t off[kProducts], len[kProducts];  // len 0: not in the arenas
-    size_t oSpec, oDone, total;
+    size_t oStrides, oSpec, oDone, total;
 };
-PlanLayout plan_layout(int32_t B, int32_t nCycles, const bool (&inArena)[kProducts], bool specWanted) {
+PlanLayout plan_layout(int32_t B, int32_t nCycles, const bool (&inArena)[kProducts], bool specWanted, bool stridesGiven) {
     PlanLayout L;
     size_t off = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    L.oStrides = off;
+    off += stridesGiven ? align256(static_cast<size_t>(B) * sizeof(fpe_stride)) : 0;
     for (int k = 0; k < kProducts; ++k) {
         L.off[k] = off;
         L.len[k] = inArena[k] ? product_bytes(k, static_cast<size_t>(B), static_cast<size_t>(nCycles)) : 0;
@@ -1582,8 +1612,17 @@ struct PlanRun {
     uint32_t doneValue = 0;
     unsigned char* dp = nullptr;       // the arena the kernels write, as the device sees it: cx.dev, or the pinned arena itself (zeroCopy)
     const fpe_pose* dPoses = nullptr;  // where the kernels read the poses
+    const fpe_stride* strides = nullptr;   // set by plan_host: the caller's strides (fpe_plan_strides), or null
+    const fpe_stride* dStrides = nullptr;  // where the kernels read them
     fpe_opt_out od;                    // the opt products in that arena
 };
+
+// The per-pose inputs of a host-form batch call (fpe_plan*, fpe_plan_rank*) into its pinned arena, which the kernels read
+// device-mapped: the poses at its start, the strides (null: none) at oStrides behind them.
+void stage_batch_inputs(unsigned char* pinned, size_t oStrides, const fpe_pose* poses, const fpe_stride* strides, int32_t B) {
+    std::memcpy(pinned, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
+    if (strides) std::memcpy(pinned + oStrides, strides, static_cast<size_t>(B) * sizeof(fpe_stride));
+}
 
 // The launches of a host-form plan call: the plan kernel and / or the opt track's chain on cx.stream — or, speculatively, the chain
 // beside the plan kernel on the side stream.
@@ -1593,7 +1632,7 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
     const int32_t B = r.B, n_cycles = r.nCycles;
     const size_t nCyc = static_cast<size_t>(B) * n_cycles;
     const size_t oOk = L.off[kCycleOk];
-    std::memcpy(hp, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
+    stage_batch_inputs(hp, L.oStrides, poses, r.strides, B);
     if (r.runOpt && cycleOkIn) std::memcpy(hp + oOk, cycleOkIn, nCyc);
     // Small calls (the plan_global_footholds service: one pose) skip both DMA copies: the kernels read the
     // poses from, and write their few KB of results straight into, the pinned (coherent, device-mapped) host
@@ -1616,6 +1655,7 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
     void* mapped = nullptr;
     FPE_HIP(hipHostGetDevicePointer(&mapped, hp, 0));
     r.dPoses = static_cast<const fpe_pose*>(mapped);
+    r.dStrides = r.strides ? reinterpret_cast<const fpe_stride*>(static_cast<unsigned char*>(mapped) + L.oStrides) : nullptr;
     r.dp = r.zeroCopy ? static_cast<unsigned char*>(mapped) : cx.dev;
     unsigned char* const dp = r.dp;
     if (!r.zeroCopy && r.runOpt && cycleOkIn) FPE_HIP(hipMemcpyAsync(dp + oOk, hp + oOk, nCyc, hipMemcpyHostToDevice, cx.stream));
@@ -1664,7 +1704,7 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
         for (int k = 0; k < kPlanProducts; ++k) slots(d)[k] = L.len[k] ? dp + L.off[k] : nullptr;
         // every (pose, cycle, leg) record is written by the kernel (trot: all legs each cycle; walk: each
         // leg in its phase), so the buffers need no clearing
-        const int rc = launch_plan(h, cp, r.dPoses, B, n_cycles, d, cx.stream);
+        const int rc = launch_plan(h, cp, r.dPoses, B, n_cycles, d, cx.stream, r.dStrides);
         if (rc != FPE_OK) return rc;
     }
     if (!r.speculate) {
@@ -1720,11 +1760,13 @@ int plan_wait_zero_copy(const CallPlan& cp, CallCtx& cx, const PlanLayout& L, co
 // plan still runs when the opt track needs its cycle flags and the caller gave none).
 int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B, int32_t n_cycles,
               const fpe_plan_out* out, const uint8_t* cycleOkIn, const fpe_opt_out* oout, GateGeom* gateGeom = nullptr,
-              bool* optDropped = nullptr) {
+              bool* optDropped = nullptr, const fpe_stride* strides = nullptr) {
     if (!poses || (!out && !oout)) return fail(FPE_E_INVALID_ARG, "null argument");
     if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
     float maxRadius = 0.0f;
     int rcPoses = check_host_poses(poses, B, maxRadius);
+    if (rcPoses != FPE_OK) return rcPoses;
+    rcPoses = check_host_strides(strides, B);
     if (rcPoses != FPE_OK) return rcPoses;
     void* want[kProducts] = {nullptr};  // the caller's arrays, by product
     if (out) std::copy(slots(*out), slots(*out) + kPlanProducts, want);
@@ -1737,7 +1779,8 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
     run.nCycles = n_cycles;
     run.runPlan = out != nullptr || (oout && !cycleOkIn);
     run.specWanted = run.runPlan && oout != nullptr && !cycleOkIn && B <= 4;
-    const PlanLayout L = plan_layout(B, n_cycles, inArena, run.specWanted);
+    run.strides = strides;
+    const PlanLayout L = plan_layout(B, n_cycles, inArena, run.specWanted, strides != nullptr);
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
     HostCall hc(h);
     CallPlan& cp = hc.cp;
@@ -1793,8 +1836,13 @@ int fpe_host_free(fpe_handle h, void* p) {
 
 int fpe_plan(fpe_handle h, const fpe_params* params, const fpe_pose* poses, int32_t B, int32_t n_cycles,
              const fpe_plan_out* out) {
+    return fpe_plan_strides(h, params, poses, nullptr, B, n_cycles, out);
+}
+
+int fpe_plan_strides(fpe_handle h, const fpe_params* params, const fpe_pose* poses, const fpe_stride* strides, int32_t B, int32_t n_cycles,
+                     const fpe_plan_out* out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
-    return plan_host(h, params, nullptr, poses, B, n_cycles, out, nullptr, nullptr);
+    return plan_host(h, params, nullptr, poses, B, n_cycles, out, nullptr, nullptr, nullptr, nullptr, strides);
 }
 
 int fpe_plan_opt(fpe_handle h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B,
@@ -2093,16 +2141,23 @@ void rank_layout(RankLayout& L, const fpe_plan_out* dFull, const fpe_rank_out& w
 }
 
 // The launches of a prepared ranking call on `stream`: the plan through launch_plan, then summary, select, gather.
-int run_rank(fpe_engine* h, const CallPlan& cp, const fpe::RankConsts& rc, const fpe_pose* d_poses, const RankLayout& L, hipStream_t stream) {
-    int rc0 = launch_plan(h, cp, d_poses, L.B, L.n, L.full, stream);
+int run_rank(fpe_engine* h, const CallPlan& cp, const fpe::RankConsts& rc, const fpe_pose* d_poses, const fpe_stride* d_strides, const RankLayout& L,
+             hipStream_t stream) {
+    int rc0 = launch_plan(h, cp, d_poses, L.B, L.n, L.full, stream, d_strides);
     if (rc0 != FPE_OK) return rc0;
-    FPE_HIP(fpe::launch_rank(rc, d_poses, L.B, L.n, L.K, L.full, L.summary, L.score, L.keys, L.bestIdx, L.nClass0, L.best, stream));
+    FPE_HIP(fpe::launch_rank(rc, d_poses, L.B, L.n, L.K, L.full, L.summary, L.score, L.keys, L.bestIdx, L.nClass0, L.best, stream, d_strides));
     return FPE_OK;
 }
 }  // namespace
 
 int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses, int32_t B,
                          int32_t n_cycles, int32_t K, const fpe_plan_out* d_full, const fpe_rank_out* d_out, void* stream) {
+    return fpe_plan_rank_strides_device(h, params, rank, d_poses, nullptr, B, n_cycles, K, d_full, d_out, stream);
+}
+
+int fpe_plan_rank_strides_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses,
+                                 const fpe_stride* d_strides, int32_t B, int32_t n_cycles, int32_t K, const fpe_plan_out* d_full,
+                                 const fpe_rank_out* d_out, void* stream) {
     fpe::RankConsts rc;
     int rc0 = check_rank_args(params, rank, B, n_cycles, K, d_out, rc);
     if (rc0 != FPE_OK) return rc0;
@@ -2116,11 +2171,13 @@ int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_
     rank_layout(L, d_full, *d_out, false, nullptr, nullptr);
     rc0 = check_packed_fits(cp, (d_full && d_full->selected_packed) || d_out->best_products.selected_packed);
     if (rc0 != FPE_OK) return rc0;
+    rc0 = check_strides_launchable(cp, d_strides);
+    if (rc0 != FPE_OK) return rc0;
     mark_async_launch(cp);
     void* scratch = nullptr;
     FPE_HIP(hipMallocAsync(&scratch, L.scratchBytes, st));
     rank_layout(L, d_full, *d_out, false, static_cast<unsigned char*>(scratch), nullptr);
-    rc0 = run_rank(h, cp, rc, d_poses, L, st);
+    rc0 = run_rank(h, cp, rc, d_poses, d_strides, L, st);
     const hipError_t f = hipFreeAsync(scratch, st);
     if (rc0 != FPE_OK) return rc0;
     FPE_HIP(f);
@@ -2129,6 +2186,11 @@ int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_
 
 int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses, int32_t B, int32_t n_cycles,
                   int32_t K, const fpe_rank_out* out) {
+    return fpe_plan_rank_strides(h, params, rank, poses, nullptr, B, n_cycles, K, out);
+}
+
+int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses, const fpe_stride* strides,
+                          int32_t B, int32_t n_cycles, int32_t K, const fpe_rank_out* out) {
     fpe::RankConsts rc;
     int rc0 = check_rank_args(params, rank, B, n_cycles, K, out, rc);
     if (rc0 != FPE_OK) return rc0;
@@ -2136,12 +2198,15 @@ int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params*
     float maxRadius = 0.0f;
     rc0 = check_host_poses(poses, B, maxRadius);
     if (rc0 != FPE_OK) return rc0;
+    rc0 = check_host_strides(strides, B);
+    if (rc0 != FPE_OK) return rc0;
     RankLayout L{};
     L.B = B, L.n = n_cycles, L.K = K;
     rank_layout(L, nullptr, *out, true, nullptr, nullptr);
-    // both arenas: [poses | outputs | scratch].  The poses are read from the pinned arena (device-mapped), as in fpe_plan; outputs of up
+    // both arenas: [poses (| strides) | outputs | scratch].  The poses are read from the pinned arena (device-mapped), as in fpe_plan; outputs of up
     // to kZeroCopyBytes are WRITTEN there by the kernels too (no transfer at all: a DMA costs some ten microseconds, whatever its size)
-    const size_t szPose = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    const size_t oStrides = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    const size_t szPose = oStrides + (strides ? align256(static_cast<size_t>(B) * sizeof(fpe_stride)) : 0);  // (the per-pose inputs)
     const bool zeroCopy = L.outBytes <= kZeroCopyBytes;
     HostCall hc(h);
     CallPlan& cp = hc.cp;
@@ -2153,12 +2218,13 @@ int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params*
     if (rc0 != FPE_OK) return rc0;
     rc0 = check_packed_fits(cp, out->best_products.selected_packed != nullptr);
     if (rc0 != FPE_OK) return rc0;
-    std::memcpy(cx.pinned, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
+    stage_batch_inputs(cx.pinned, oStrides, poses, strides, B);
     void* mapped = nullptr;
     FPE_HIP(hipHostGetDevicePointer(&mapped, cx.pinned, 0));
     unsigned char* const devArena = zeroCopy ? static_cast<unsigned char*>(mapped) : cx.dev;
     rank_layout(L, nullptr, *out, true, cx.dev + szPose + L.outBytes, devArena + szPose);
-    rc0 = run_rank(h, cp, rc, static_cast<const fpe_pose*>(mapped), L, cx.stream);
+    const fpe_stride* dStrides = strides ? reinterpret_cast<const fpe_stride*>(static_cast<unsigned char*>(mapped) + oStrides) : nullptr;
+    rc0 = run_rank(h, cp, rc, static_cast<const fpe_pose*>(mapped), dStrides, L, cx.stream);
     if (rc0 != FPE_OK) return rc0;
     void* dst[kPlanProducts + 4];
     std::copy(slots(out->best_products), slots(out->best_products) + kPlanProducts, dst);

@@ -1343,8 +1343,28 @@ __device__ __forceinline__ double polygon_center_x(const double (*feet)[3]) {
 // stance like every other track's (setFirstGait, cpp:582-588), so the next feet centre is (centre.x + stepLength_,
 // initialPose_[1] + 0) and the gate is getSubmap(centre, isos_.length x isos_.width) succeeding (cpp:2345-2349).
 // Later cycles depend on the NLopt results and are not evaluated.
-__device__ __forceinline__ uint8_t opt_gate_cycle0(const MapGeom& g, const PlanConsts& pc, double ctrX, double y0) {
-    const double px = ctrX + pc.step;  // cpp:2327
+// The stride constants of ONE pose (fpe_stride, include/fpe.h) with derive_constants' typing: what the stride instantiations of the
+// plan kernels read where the others read PlanConsts::stepHalf / step / stepQuarter / drift.
+struct StrideVals {
+    double stepHalf, step, stepQuarter, drift;
+};
+__device__ __forceinline__ StrideVals load_stride(const fpe_stride* __restrict__ strides, int b) {
+    const float s = strides[b].step_length;
+    StrideVals v;
+    v.stepHalf = static_cast<double>(s / 2);
+    v.step = static_cast<double>(s);
+    v.stepQuarter = static_cast<double>(s / 4);
+    v.drift = strides[b].lateral_drift;
+    return v;
+}
+
+// the optional trailing argument of a kernel that has a stride form (plan_chained_kernel, plan_bits_seq_kernel)
+__device__ __forceinline__ const fpe_stride* stride_arg() { return nullptr; }
+__device__ __forceinline__ const fpe_stride* stride_arg(const fpe_stride* p) { return p; }
+// kStride (the stride kernels): the step is the pose's own, sv.step.
+template <bool kStride = false>
+__device__ __forceinline__ uint8_t opt_gate_cycle0(const MapGeom& g, const PlanConsts& pc, double ctrX, double y0, const StrideVals& sv = StrideVals{}) {
+    const double px = ctrX + (kStride ? sv.step : pc.step);  // cpp:2327
     const double py = y0 + 0.0;        // cpp:2329 with ajustedPose_[1] = 0 (cpp:759)
     const bool ok = centre_usable(px, py) && submap_info(g, px, py, pc.isosLen, pc.isosWid).ok;
     return ok ? 0 : static_cast<uint8_t>(FPE_POSE_OPT_SUBMAP_FAILED);
@@ -1535,10 +1555,14 @@ __device__ __forceinline__ void leg_phase(const DevMap& m, const PlanConsts& pc,
 // G lanes per leg; a pose owns 4*G consecutive threads; block = max(64, 4*G) threads holds
 // PPB = blockDim / (4*G) poses.  Dynamic LDS per pose = sizeof(PoseShared) + 4 * tileBytes.
 constexpr int kMinWavesG16 = 4;  // occupancy the G = 16 register allocation aims at
-template <int G, bool kMid = false>
+// Stride form (fpe_plan_strides*): S = {const fpe_stride*}, ONE trailing argument behind the list below — step and drift are then
+// the pose's own, strides[b].  S empty (the default): the kernel and its argument segment as they always were.
+template <int G, bool kMid = false, class... S>
 __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWavesG16 : 2)) void plan_chained_kernel(DevMap mArg, PlanConsts pc, SpiralLut lut,
                                                                            const fpe_pose* __restrict__ poses, int B,
-                                                                           int nCycles, fpe_plan_out out) {
+                                                                           int nCycles, fpe_plan_out out, S... strideArg) {
+    constexpr bool kStride = sizeof...(S) != 0;
+    static_assert(sizeof...(S) <= 1 && !(kStride && kMid), "one optional trailing argument: the strides; generic variant only");
     // The map geometry is wave-uniform and would live in 20 scalar registers; this kernel needs more uniform
     // state than the 102 SGPRs hold, and every spilled SGPR costs a v_readlane (+ wait states) per use.  The
     // doubles are only ever operands of vector f64 arithmetic, so they are parked in VGPRs instead.
@@ -1576,6 +1600,8 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
     const fpe_pose* pp = poses + b;
     const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
     const int gait = pp->gait;
+    StrideVals sv{};
+    if constexpr (kStride) sv = load_stride(stride_arg(strideArg...), b);
     const LegStatic ls = make_leg_static(pc, pp, leg, m.g.res, lut);
     const LutHead head = load_lut_head(lut, g);
 
@@ -1599,18 +1625,18 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
             st[2] = sz;
         }
         for (int t = 0; t < 3; ++t) {
-            sh.cur[t][leg][0] = sx - pc.stepHalf;
+            sh.cur[t][leg][0] = sx - (kStride ? sv.stepHalf : pc.stepHalf);
             sh.cur[t][leg][1] = sy;
             sh.cur[t][leg][2] = sz;
         }
     }
     pose_sync<G>();
     if (out.pose_status && live && leg == 0 && g.sub == 0)
-        out.pose_status[b] = opt_gate_cycle0(m.g, pc, polygon_center_x(sh.cur[0]), y0);
+        out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
 
     double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (gait == 1) ? 4 : 1;
-    const double advance = (gait == 1) ? pc.stepQuarter : pc.step;
+    const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
     // swing order LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
     const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
 
@@ -1665,7 +1691,7 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
         }
         if (leg == 0 && g.sub == 0 && live && out.cycle_ok)
             out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
-        adjY += pc.drift;  // cpp:1578
+        adjY += kStride ? sv.drift : pc.drift;  // cpp:1578
     }
 }
 
@@ -1674,89 +1700,12 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
 // 64 lanes.  For large spiral windows (1 cm / 0.5 cm maps) a leg has enough cells and candidates to
 // fill a wavefront, the per-leg geometry becomes truly wave-uniform, there are no workgroup barriers
 // and — for the 4-phase walk gait, where only one leg swings per phase — no idle wavefronts.
-__global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanConsts pc, SpiralLut lut,
-                                                                const fpe_pose* __restrict__ poses, int B, int nCycles,
-                                                                fpe_plan_out out) {
-    constexpr int G = 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = static_cast<int>(threadIdx.x);
-    const Grp<G> g(tid);
-    PoseShared& sh = *reinterpret_cast<PoseShared*>(smem);
-    uint8_t* tile = smem + sizeof(PoseShared);
-    const int b = blockIdx.x;
-    if (b >= B) return;
-    const bool live = true;
-
-    const fpe_pose* pp = poses + b;
-    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
-    const int gait = pp->gait;
-    const LutHead head = load_lut_head(lut, g);
-    for (int k = tid; k < pc.nFoot; k += G) {
-        sh.footDa[k] = pc.footDa[k];
-        sh.footDb[k] = pc.footDb[k];
-        sh.footOff[k] = static_cast<int16_t>(pc.footDa[k] * pc.tileW + pc.footDb[k]);
-    }
-    // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699): lane = leg
-    if (tid < 4) {
-        const int leg = tid;
-        double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
-        double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
-        double sz = 0;
-        sx += x0;
-        sy += y0;
-        sz += z0;
-        if (out.stance) {
-            double* st = out.stance + (static_cast<size_t>(b) * 4 + leg) * 3;
-            st[0] = sx;
-            st[1] = sy;
-            st[2] = sz;
-        }
-        for (int t = 0; t < 3; ++t) {
-            sh.cur[t][leg][0] = sx - pc.stepHalf;
-            sh.cur[t][leg][1] = sy;
-            sh.cur[t][leg][2] = sz;
-        }
-    }
-    pose_sync<16>();
-    if (out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0(m.g, pc, polygon_center_x(sh.cur[0]), y0);
-
-    double adjY = 0.0;  // ajustedPose_[1], cpp:759
-    const int nPhases = (gait == 1) ? 4 : 1;
-    const double advance = (gait == 1) ? pc.stepQuarter : pc.step;
-    const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
-
-    for (int cyc = 0; cyc < nCycles; ++cyc) {
-        bool cycleOk = true;
-        for (int ph = 0; ph < nPhases; ++ph) {
-            const unsigned mask = (gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
-            // feet-polygon centres: lane t computes track t (getPolygonCenter, cpp:2191, 2265)
-            if (tid < 3) {
-                sh.ctr[tid] = polygon_center_x(sh.cur[tid]);
-            }
-            if (tid < 4) sh.valid[tid] = 1;  // non-swing legs do not vote
-            pose_sync<16>();
-            for (int leg = 0; leg < 4; ++leg) {
-                if (!((mask >> leg) & 1u)) continue;
-                const LegStatic ls = make_leg_static(pc, pp, leg, m.g.res, lut);
-                leg_phase<G>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out);
-            }
-            pose_sync<16>();
-            // footholdValidation_ = AND of the swing legs' flags (cpp:1323); commit or skip (cpp:1332-1576)
-            const bool phaseOk = (sh.valid[0] & sh.valid[1] & sh.valid[2] & sh.valid[3]) != 0;
-            if (phaseOk && tid < 36) {
-                const int leg = tid / 9, e = tid - leg * 9;
-                if ((mask >> leg) & 1u) {
-                    const int t = e / 3, k = e - t * 3;
-                    sh.cur[t][leg][k] = sh.nxt[t][leg][k];
-                }
-            }
-            pose_sync<16>();
-            cycleOk = cycleOk && phaseOk;
-        }
-        if (tid == 0 && out.cycle_ok) out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
-        adjY += pc.drift;  // cpp:1578
-    }
-}
+#define FPE_SEQUENTIAL_STRIDE 0
+#include "fpe_plan_sequential_body.hpp"  // plan_sequential_kernel
+#undef FPE_SEQUENTIAL_STRIDE
+#define FPE_SEQUENTIAL_STRIDE 1
+#include "fpe_plan_sequential_body.hpp"  // plan_sequential_stride_kernel: `strides` as the one trailing argument
+#undef FPE_SEQUENTIAL_STRIDE
 
 // ---- open-loop per-leg search: one wavefront per checkFoothold call (hpp:94-100) ----------------------
 constexpr int kMaxQueriesPerBlock = 32;  // 256 threads / 8 lanes per query
@@ -2033,11 +1982,23 @@ static bool mid_variant(const PlanConsts& pc, double res) {
            pc.noMidVariant == 0;
 }
 
+// d_strides (fpe_plan_strides*; null: none): the stride kernels, which exist at the automatic group sizes only (8, 65)
+bool plan_chained_strides_supported(const PlanConsts& pc) {
+    const int G = plan_group_size(pc);
+    return G == 8 || G == 65;
+}
 hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream) {
+                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides) {
     const size_t lds = plan_lds_bytes(pc);
     const int G = plan_group_size(pc);
-    if (G == 65) {
+    if (d_strides) {
+        if (G == 65)
+            hipLaunchKernelGGL(plan_sequential_stride_kernel, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides);
+        else if (G == 8)
+            hipLaunchKernelGGL((plan_chained_kernel<8, false, const fpe_stride*>), dim3((B + 1) / 2), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides);
+        else
+            return hipErrorNotSupported;
+    } else if (G == 65) {
         hipLaunchKernelGGL(plan_sequential_kernel, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
     } else if (G == 4) {
         hipLaunchKernelGGL(plan_chained_kernel<4>, dim3((B + 3) / 4), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
@@ -2126,6 +2087,8 @@ hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
         {reinterpret_cast<const void*>(plan_chained_kernel<4>), planBytes},
         {reinterpret_cast<const void*>(plan_chained_kernel<64>), planBytes},
         {reinterpret_cast<const void*>(plan_sequential_kernel), planBytes},
+        {reinterpret_cast<const void*>(plan_chained_kernel<8, false, const fpe_stride*>), planBytes},
+        {reinterpret_cast<const void*>(plan_sequential_stride_kernel), planBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<8>), searchBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<8, true>), searchBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<64>), searchBytes},

@@ -10,8 +10,11 @@
 namespace fpe {
 
 // ---- direct kernels (fpe_kernels.hip) ------------------------------------------------------------------------
+// d_strides (here and in launch_plan_bits / launch_rank): one fpe_stride per pose, the stride form of the call (fpe_plan_strides*,
+// fpe_plan_rank_strides*) — the kernels' stride instantiations; null: the kernels as they were
 hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream);
+                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr);
+bool plan_chained_strides_supported(const PlanConsts& pc);  // the direct stride kernels exist at the automatic group sizes only
 hipError_t launch_search_legs(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_leg_query* d_q,
                               int n, fpe_foothold* d_out, hipStream_t stream);
 // open-loop centroid method
@@ -28,9 +31,10 @@ size_t bitmap_words(int rows, int cols, int* strideW, int* nw);
 hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float thrDefault, float thrCandidate,
                                uint32_t* d_words, hipStream_t stream);
 bool bits_supported(const PlanConsts& pc, const MapGeom& g);
-void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n);
+void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, bool strides = false);
 hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut,
-                            const fpe_pose* d_poses, int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream);
+                            const fpe_pose* d_poses, int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream,
+                            const fpe_stride* d_strides = nullptr);
 
 // ---- producer filters (fpe_filters.hpp) ----------------------------------------------------------------------
 bool filters_supported(const FilterConsts& fc, const MapGeom& g);
@@ -90,7 +94,7 @@ struct RankConsts {
 size_t rank_scratch_bytes(int B, int K);
 hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
                        fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
-                       const fpe_plan_out& bestProducts, hipStream_t stream);
+                       const fpe_plan_out& bestProducts, hipStream_t stream, const fpe_stride* d_strides = nullptr);
 hipError_t set_max_lds_rank();
 
 // ---- the dense maps as message layers (fpe_layers.hpp) -------------------------------------------------------

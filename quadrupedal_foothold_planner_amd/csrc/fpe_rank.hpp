@@ -32,18 +32,22 @@ __device__ __forceinline__ bool rank_key_less(const RankKey& a, const RankKey& b
 
 // One pose per group of four lanes, lane = leg: each lane loads its leg's records, the four values of a cycle meet by shuffle
 // and every lane of the group runs the same f64 chain on them in the stated order (lane 0 writes).
-__global__ __launch_bounds__(256) void rank_summary_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, RankConsts rc,
-                                                           const fpe_foothold* __restrict__ nominal, const double* __restrict__ defaultNext,
-                                                           const uint8_t* __restrict__ cycleOk, const double* __restrict__ stance,
-                                                           const uint8_t* __restrict__ poseStatus, fpe_pose_summary* __restrict__ summary,
-                                                           double* __restrict__ score, RankKey* __restrict__ keys) {
+// (the body of rank_summary_kernel and of its stride form — kStride: stepHalf is the pose's own, double(strides[b].step_length / 2))
+template <bool kStride>
+__device__ __forceinline__ void rank_summary_body(const fpe_pose* __restrict__ poses, int B, int nCycles, const RankConsts& rc,
+                                                  const fpe_foothold* __restrict__ nominal, const double* __restrict__ defaultNext,
+                                                  const uint8_t* __restrict__ cycleOk, const double* __restrict__ stance,
+                                                  const uint8_t* __restrict__ poseStatus, fpe_pose_summary* __restrict__ summary,
+                                                  double* __restrict__ score, RankKey* __restrict__ keys, const fpe_stride* __restrict__ strides) {
     const int t = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
     const int b = t >> 2, leg = t & 3;
     const int bb = b < B ? b : B - 1;  // (lanes past the batch run pose B - 1 again and write nothing: the shuffles stay whole)
     int gait = leg == 0 ? poses[bb].gait : 0;
     gait = __shfl(gait, 0, 4);
     const bool trot = gait == 0;
-    const double cx = stance[static_cast<size_t>(bb) * 12 + leg * 3] - rc.stepHalf;
+    double stepHalf = rc.stepHalf;
+    if constexpr (kStride) stepHalf = static_cast<double>(strides[bb].step_length / 2);
+    const double cx = stance[static_cast<size_t>(bb) * 12 + leg * 3] - stepHalf;
     enum { RF = 0, RH = 1, LH = 2, LF = 3 };
     double cur[4];
 #pragma unroll
@@ -156,6 +160,21 @@ __global__ __launch_bounds__(256) void rank_summary_kernel(const fpe_pose* __res
     k.lo = (img << 32) | static_cast<unsigned long long>(static_cast<uint32_t>(b));
     keys[b] = k;
 }
+__global__ __launch_bounds__(256) void rank_summary_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, RankConsts rc,
+                                                           const fpe_foothold* __restrict__ nominal, const double* __restrict__ defaultNext,
+                                                           const uint8_t* __restrict__ cycleOk, const double* __restrict__ stance,
+                                                           const uint8_t* __restrict__ poseStatus, fpe_pose_summary* __restrict__ summary,
+                                                           double* __restrict__ score, RankKey* __restrict__ keys) {
+    rank_summary_body<false>(poses, B, nCycles, rc, nominal, defaultNext, cycleOk, stance, poseStatus, summary, score, keys, nullptr);
+}
+__global__ __launch_bounds__(256) void rank_summary_stride_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, RankConsts rc,
+                                                                  const fpe_foothold* __restrict__ nominal, const double* __restrict__ defaultNext,
+                                                                  const uint8_t* __restrict__ cycleOk, const double* __restrict__ stance,
+                                                                  const uint8_t* __restrict__ poseStatus, fpe_pose_summary* __restrict__ summary,
+                                                                  double* __restrict__ score, RankKey* __restrict__ keys,
+                                                                  const fpe_stride* __restrict__ strides) {
+    rank_summary_body<true>(poses, B, nCycles, rc, nominal, defaultNext, cycleOk, stance, poseStatus, summary, score, keys, strides);
+}
 
 // Workgroup blockIdx.x sorts keys [blockIdx.x * kRankTile, + kRankTile) of `in` (n keys in all) in LDS — a bitonic network over
 // the next power of two, padded with "no pose" keys — and keeps the first K.  Tile stage (tileOut given): K keys per tile to
@@ -262,11 +281,16 @@ size_t rank_scratch_bytes(int B, int K) {
 // required here (the engine hands scratch for what the caller did not ask for).
 hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
                        fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
-                       const fpe_plan_out& bestProducts, hipStream_t stream) {
+                       const fpe_plan_out& bestProducts, hipStream_t stream, const fpe_stride* d_strides) {
     unsigned char* sp = static_cast<unsigned char*>(scratch);
     RankKey* keys = reinterpret_cast<RankKey*>(sp);
     sp += rank_align256(static_cast<size_t>(B) * sizeof(RankKey));
-    hipLaunchKernelGGL(rank_summary_kernel, dim3(static_cast<unsigned>((static_cast<long long>(B) * 4 + 255) / 256)), dim3(256), 0, stream,
+    const dim3 summaryGrid(static_cast<unsigned>((static_cast<long long>(B) * 4 + 255) / 256));
+    if (d_strides)
+        hipLaunchKernelGGL(rank_summary_stride_kernel, summaryGrid, dim3(256), 0, stream, d_poses, B, nCycles, rc, full.nominal, full.default_next,
+                           full.cycle_ok, full.stance, full.pose_status, d_summary, d_score, keys, d_strides);
+    else
+        hipLaunchKernelGGL(rank_summary_kernel, summaryGrid, dim3(256), 0, stream,
                        d_poses, B, nCycles, rc, full.nominal, full.default_next, full.cycle_ok, full.stance, full.pose_status, d_summary,
                        d_score, keys);
     hipError_t e = hipGetLastError();

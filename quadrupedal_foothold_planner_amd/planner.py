@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (CENTROID_DTYPE, CENTROID_QUERY_DTYPE, FOOTHOLD_DTYPE, GLOBAL_FOOTHOLDS_DTYPE, OPT_CYCLE_DTYPE, OPT_FOOTHOLD_DTYPE, OPT_PARAMS_DTYPE,
-                    PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
+                    PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, STRIDE_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
                     CentroidMapOut, FootholdMapOut, FootholdSnapOut, MapDesc, OptOut, PlanOut, RankOut, ptr)
 
 # products of a chained plan in the order of fpe_plan_out's fields (= the order of the engine's device arena)
@@ -50,6 +50,23 @@ def make_poses(xyz, gait=0, leg_search_radius=None, leg_polygon_kind=None):
     if leg_polygon_kind is not None:
         poses["leg_polygon_kind"] = leg_polygon_kind
     return poses
+
+
+def make_strides(step_length, lateral_drift):
+    """Build an fpe_stride array (one element per pose of a batch: plan(strides=...), plan_rank(strides=...)) from per-pose step
+    lengths (kept as float32, the type of fpe_params.stepLength) and lateral drifts (float64); scalars broadcast."""
+    step, drift = np.broadcast_arrays(np.asarray(step_length, dtype=np.float32), np.asarray(lateral_drift, dtype=np.float64))
+    strides = np.zeros(step.size, dtype=STRIDE_DTYPE)
+    strides["step_length"] = step.reshape(-1)
+    strides["lateral_drift"] = drift.reshape(-1)
+    return strides
+
+
+def _strides_for(strides, B):
+    strides = np.ascontiguousarray(strides, dtype=STRIDE_DTYPE)
+    if strides.shape != (B,):
+        raise ValueError(f"strides must hold one element per pose: shape {strides.shape}, {B} poses")
+    return strides
 
 
 # fpe_set_tuning's knobs whose engine default is not 0 (tuning() restores these after a with-block)
@@ -173,10 +190,12 @@ class FootholdPlanner(_Handle):
     def set_max_leg_search_radius(self, r):
         self._check(self._lib.fpe_set_max_leg_search_radius(self._h, np.float32(r)))
 
-    def describe_plan(self):
-        """Name and shape of the kernel a chained plan launches with the current parameters and map."""
+    def describe_plan(self, strides=False):
+        """Name and shape of the kernel a chained plan launches with the current parameters and map; strides=True: the kernel
+        a plan with per-pose strides launches (fpe_describe_plan_strides)."""
         buf = C.create_string_buffer(256)
-        self._check(self._lib.fpe_describe_plan(self._h, ptr(self.params), buf, 256))
+        describe = self._lib.fpe_describe_plan_strides if strides else self._lib.fpe_describe_plan
+        self._check(describe(self._h, ptr(self.params), buf, 256))
         return buf.value.decode()
 
     def set_tuning(self, **kw):
@@ -227,9 +246,10 @@ class FootholdPlanner(_Handle):
         return {k: arena[o:o + n].view(shapes[k][1]).reshape(shapes[k][0]) for k, o, n in zip(order, offs, sizes)}
 
     # ---- chained plan, host buffers ------------------------------------------------------------------
-    def plan(self, poses, n_cycles, products=DEFAULT_PRODUCTS, out=None):
+    def plan(self, poses, n_cycles, products=DEFAULT_PRODUCTS, out=None, strides=None):
         """fpe_plan with host buffers.  `out`: a dict returned by an earlier call with the same shapes (timing loops
-        reuse the arrays instead of allocating ~100 B per foothold per call)."""
+        reuse the arrays instead of allocating ~100 B per foothold per call).  `strides`: an fpe_stride array (make_strides),
+        one element per pose — pose b is planned with ITS step length and lateral drift (fpe_plan_strides)."""
         poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
         B = poses.shape[0]
         shapes = product_shapes(B, n_cycles)
@@ -251,16 +271,26 @@ class FootholdPlanner(_Handle):
                 assert out[k].shape == shapes[k][0] and out[k].dtype == shapes[k][1]
                 setattr(po, fields[k], ptr(out[k]))
             self._plan_out_cache = (key, po, out)
-        self._check(self._lib.fpe_plan(self._h, ptr(self.params), ptr(poses), B, int(n_cycles), C.byref(po)))
+        if strides is None:
+            self._check(self._lib.fpe_plan(self._h, ptr(self.params), ptr(poses), B, int(n_cycles), C.byref(po)))
+        else:
+            self._check(self._lib.fpe_plan_strides(self._h, ptr(self.params), ptr(poses), ptr(_strides_for(strides, B)), B, int(n_cycles),
+                                                   C.byref(po)))
         return out
 
     # ---- chained plan, device-resident (torch tensors / raw pointers) ----------------------------------
     def plan_device(self, d_poses_ptr, B, n_cycles, d_nominal_ptr=0, d_centroid_ptr=0, d_default_ptr=0,
-                    d_cycle_ok_ptr=0, d_stance_ptr=0, stream=0, d_selected_ptr=0, d_pose_status_ptr=0, d_selected_packed_ptr=0):
+                    d_cycle_ok_ptr=0, d_stance_ptr=0, stream=0, d_selected_ptr=0, d_pose_status_ptr=0, d_selected_packed_ptr=0,
+                    d_strides_ptr=0):
+        """d_strides_ptr: device array of B fpe_stride elements (fpe_plan_strides_device), or 0 for fpe_plan_device."""
         po = PlanOut(d_nominal_ptr or None, d_centroid_ptr or None, d_default_ptr or None, d_cycle_ok_ptr or None,
                      d_stance_ptr or None, d_selected_ptr or None, d_pose_status_ptr or None, d_selected_packed_ptr or None)
-        self._check(self._lib.fpe_plan_device(self._h, ptr(self.params), C.c_void_p(d_poses_ptr), int(B), int(n_cycles),
-                                              C.byref(po), C.c_void_p(stream or 0)))
+        if not d_strides_ptr:
+            self._check(self._lib.fpe_plan_device(self._h, ptr(self.params), C.c_void_p(d_poses_ptr), int(B), int(n_cycles),
+                                                  C.byref(po), C.c_void_p(stream or 0)))
+        else:
+            self._check(self._lib.fpe_plan_strides_device(self._h, ptr(self.params), C.c_void_p(d_poses_ptr), C.c_void_p(d_strides_ptr),
+                                                          int(B), int(n_cycles), C.byref(po), C.c_void_p(stream or 0)))
 
     # ---- plan a batch and rank it on the device (build-defined: fpe_plan_rank*) ---------------------------------------------
     @staticmethod
@@ -270,10 +300,11 @@ class FootholdPlanner(_Handle):
             return rank
         return _capi.rank_params_defaults(**dict(rank))
 
-    def plan_rank(self, poses, n_cycles, K, rank=None, products=("nominal", "cycle_ok", "stance"), summary=True):
+    def plan_rank(self, poses, n_cycles, K, rank=None, products=("nominal", "cycle_ok", "stance"), summary=True, strides=None):
         """fpe_plan_rank with host buffers: plans the batch, scores every pose on the device and returns {"best": int32 [K] pose
         indices, best first, "n_class0": int, "summary": POSE_SUMMARY_DTYPE [B] and "score": float64 [B] (with summary=True),
-        and each requested product of the K chosen poses, slot k = pose best[k]} — shapes of plan() with B replaced by K."""
+        and each requested product of the K chosen poses, slot k = pose best[k]} — shapes of plan() with B replaced by K.
+        `strides`: as in plan() (fpe_plan_rank_strides) — the candidates of one ranking may differ in stride."""
         poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
         B, K = poses.shape[0], int(K)
         unknown = set(products) - set(PRODUCT_ORDER)
@@ -291,13 +322,17 @@ class FootholdPlanner(_Handle):
         for k in products:
             setattr(ro.best_products, PRODUCT_FIELDS[k], ptr(out[k]))
         rp = self._rank_params(rank)
-        self._check(self._lib.fpe_plan_rank(self._h, ptr(self.params), C.byref(rp) if rp is not None else None, ptr(poses), B,
-                                            int(n_cycles), K, C.byref(ro)))
+        if strides is None:
+            self._check(self._lib.fpe_plan_rank(self._h, ptr(self.params), C.byref(rp) if rp is not None else None, ptr(poses), B,
+                                                int(n_cycles), K, C.byref(ro)))
+        else:
+            self._check(self._lib.fpe_plan_rank_strides(self._h, ptr(self.params), C.byref(rp) if rp is not None else None, ptr(poses),
+                                                        ptr(_strides_for(strides, B)), B, int(n_cycles), K, C.byref(ro)))
         out["best"], out["n_class0"] = best, int(n0[0])
         return out
 
     def plan_rank_device(self, d_poses_ptr, B, n_cycles, K, d_best_ptr, rank=None, d_summary_ptr=0, d_score_ptr=0, d_n_class0_ptr=0,
-                         best_products=None, full=None, stream=0):
+                         best_products=None, full=None, stream=0, d_strides_ptr=0):
         """Device form: DEVICE pointers (0 / missing = not wanted), asynchronous on `stream`.  best_products / full: dicts
         {product name: device pointer} of the K-slot compacted products and of the un-compacted products of all B poses."""
         ro = RankOut(d_summary_ptr or None, d_score_ptr or None, d_best_ptr or None, d_n_class0_ptr or None)
@@ -309,9 +344,10 @@ class FootholdPlanner(_Handle):
             for k, p in full.items():
                 setattr(fo, PRODUCT_FIELDS[k], p or None)
         rp = self._rank_params(rank)
-        self._check(self._lib.fpe_plan_rank_device(self._h, ptr(self.params), C.byref(rp) if rp is not None else None,
-                                                   C.c_void_p(d_poses_ptr), int(B), int(n_cycles), int(K),
-                                                   C.byref(fo) if fo is not None else None, C.byref(ro), C.c_void_p(stream or 0)))
+        self._check(self._lib.fpe_plan_rank_strides_device(self._h, ptr(self.params), C.byref(rp) if rp is not None else None,
+                                                           C.c_void_p(d_poses_ptr), C.c_void_p(d_strides_ptr or 0), int(B), int(n_cycles),
+                                                           int(K), C.byref(fo) if fo is not None else None, C.byref(ro),
+                                                           C.c_void_p(stream or 0)))
 
     # ---- the opt track of a batch (cpp:913-1319, 1485-1568; build-defined optimiser) ---------------------------
     def plan_opt(self, poses, n_cycles, cycle_ok=None):
