@@ -268,6 +268,7 @@ __device__ __forceinline__ void flush_unit_g(const DevMap& m, const PlanConsts& 
     }
 }
 
+constexpr int kYCentreMid = 4;  // YEntry::flags, 3x3-only kernels: jc == j0d + 1
 // PC: the plan constants of the caller (rf, cornerEps, winH: PlanConsts, or YFillConsts of the 3x3-only kernels)
 struct YFillConsts {
     double rf, cornerEps;
@@ -328,6 +329,8 @@ __device__ __forceinline__ void fill_yentry(const MapGeom& mg, const PC& pc, con
     e.yA = cell_pos(e.sbaseY, mg.res, (rightCol + 1) >> 1);
     e.yB = cell_pos(e.sbaseY, mg.res, rightCol >> 1);
     if (okY) flags |= 1;
+    // 3x3-only kernels (leg_fast8m): getIndex(centre) is the column behind the disc box's first one — with a three-column box, its middle
+    if constexpr (std::is_same<PC, YFillConsts>::value) flags |= (idx[2] == idx[0] + 1) ? kYCentreMid : 0;
     e.flags = flags;
     // reference rectangle polygon (getSearchPolygon, cpp:2496-2517): y limits centre -+ 0.5 * r
     {
@@ -801,7 +804,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
     // (kNoDefault: lanes 5-6 evaluate default-track corners nobody reads: their `safe` / magnitude tests do not count)
     const bool dfltLane = (g.sub == 5) | (g.sub == 6);
     const bool laneOk = kNoDefault ? (dfltLane | (safe & (fabs(nxq) <= 1e6))) : (safe & (fabs(nxq) <= 1e6));
-    const bool rare = (!kPlain & !ls.radiusOk) | ((ye.flags & 2) == 0) | !laneOk | (!kNoDefault & !wantDefault) | !boxes;
+    const bool rare = (!kPlain & !ls.radiusOk) | ((ye.flags & (2 | kYCentreMid)) != (2 | kYCentreMid)) | !laneOk | (!kNoDefault & !wantDefault) | !boxes;
     if (__ballot(rare) != 0ull) {  // wave-uniform
         const double ctr0 = swizzle_f64<kKeep | (5 << 5)>(myCtr), ctr1 = swizzle_f64<kKeep | (0 << 5)>(myCtr),
                      ctr2 = swizzle_f64<kKeep | (7 << 5)>(myCtr);
@@ -945,15 +948,14 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
                 Fs = fk.slot == k ? w.F[k][0] : Fs;
                 Cs = fk.slot == k ? w.C[k][0] : Cs;
             }
-            const int i = iFast;
             const unsigned inside = rowInside ? ye.pmask : 0u;
-            unsigned P = ~Fs | (~Cs & inside);
-            // cells outside the map pass every test (their F bit is 0) but are no candidates: windows over the map's edge only
-            const bool border = (iw0 < 0) | (jw0 < 0) | (iw0 + G * NRL > m.g.rows) | (jw0 + 32 > m.g.cols);
-            if (__ballot(border) != 0ull) {  // wave-uniform, rare
-                const unsigned colIn = range_word(-jw0, m.g.cols - 1 - jw0, 0);
-                P = static_cast<unsigned>(i) < static_cast<unsigned>(m.g.rows) ? (P & colIn) : 0u;
-            }
+            // No cell outside the map among the sixteen: they lie within two rows and columns of the centre cell, and the centre cell
+            // is the middle one of the centre disc's 3x3 box — its row because the foot radius is at most one cell and the three
+            // corner quotients are clear of the cell boundaries (`safe`), its column by the y entry's flag (kYCentreMid: the y side
+            // may have been evaluated ON a cell boundary, by the reference's own expressions) — which `boxes` keeps clear of the
+            // map's outermost rows and columns.  So the window may reach over the map's edge here (cells outside pass every test:
+            // their F bit is 0) without such a cell being looked at; the general search below masks them itself.
+            const unsigned P = ~Fs | (~Cs & inside);
             const unsigned b5 = P >> static_cast<unsigned>(winH - 2);  // bit c = column offset c - 2 from the centre column (winH)
             unsigned m16 = 0u;
 #pragma unroll
@@ -1135,9 +1137,18 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
         }
     }
     bits_sync<G>();
+    // The shifted stance's feet-polygon centre, ONCE: the gate of the first cycle needs it, and so does the first phase of cycle 0 on
+    // every lane — sh.cur[0..2] were written identically just above, so whichever track a lane evaluates (myTrack) it would
+    // compute this value again, bit for bit.  The tracks diverge with the first commit: every later phase computes its own.
+    // Not where the value's two registers, held from here into the loop, do not fit: the <4, true, *> instances sit at the cap of
+    // 256 vector registers (three spilled with it, 16 bytes of scratch), the generic ones run at theirs with spills already
+    // (<4, false, 2 / 0>: 48 -> 64 / 72 bytes of scratch with it) — those compute the centre at both places, as before.
+    constexpr bool kStanceOnce = kMid && NRL < 4;
+    double stanceCtr = 0.0;
+    if constexpr (kStanceOnce) stanceCtr = polygon_center_x(sh.cur[0]);
     if (out.pose_status) {
         // getGaitCycleSearchGridMap's getSubmap in the first cycle (opt_gate_cycle0), its four corners on four lanes
-        const double gx = polygon_center_x(sh.cur[0]) + (kStride ? sv.step : pc.step), gy = y0 + 0.0;  // cpp:2327-2329
+        const double gx = (kStanceOnce ? stanceCtr : polygon_center_x(sh.cur[0])) + (kStride ? sv.step : pc.step), gy = y0 + 0.0;  // cpp:2327-2329
         Submap gs;
         {
             // lane q & 3: 0 top-left x, 1 top-left y, 2 bottom-right x, 3 bottom-right y — predicted as in the x pass
@@ -1227,7 +1238,8 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             const bool active = kPlain || ((mask >> leg) & 1u) != 0u;  // (plain: every leg swings in the one phase)
             // feet-polygon centres (getPolygonCenter, cpp:2191, 2265): every lane computes ONE track's centre from the
             // committed feet in LDS; the values reach the group's other lanes by swizzle (no LDS hand-off, no barrier)
-            const double myCtr = polygon_center_x(sh.cur[myTrack]);
+            double myCtr = stanceCtr;
+            if (!kStanceOnce || cyc != 0 || ph != 0) myCtr = polygon_center_x(sh.cur[myTrack]);  // (wave-uniform branch)
             // footholdValidation_ (cpp:1323) is a ballot over the pose's lanes; the committed positions go from
             // registers straight to PoseShared::cur (cpp:1332-1576)
             LegCommit lc;

@@ -93,7 +93,7 @@ struct YEntry {
     int j0d, njd;  // foot-disc box columns (centre disc and default-track disc: same y, same radius)
     int j0r, njr;  // centroid rectangle columns (getSubmap, cpp:1615-1627)
     int jA, jB;    // reference rectangle polygon: the columns j with ylo <= y_j < yhi (rectangle_index_bounds)
-    int flags;     // bit 0: y part of getSubmap's success; bit 1: |y| usable (centre_usable)
+    int flags;     // bit 0: y part of getSubmap's success; bit 1: |y| usable (centre_usable); bit 2 (3x3-only kernels): jc == j0d + 1
     double ny;
     double sbaseY;   // submap position.y + (0.5 * sublength.y - 0.5 * res)
     double yA, yB;   // cell_pos(sbaseY, res, (rightCol + 1) >> 1), cell_pos(sbaseY, res, rightCol >> 1)  (cpp:1816)
