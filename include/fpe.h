@@ -714,6 +714,65 @@ int fpe_plan_rank_strides_device(fpe_handle h, const fpe_params* params, const f
 /* fpe_describe_plan for the kernel a stride call (strides != NULL) launches on the current map. */
 int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf, int32_t n);
 
+/* ---- resumable plans: the chain's state across the call boundary, in both directions ---------------------------------------------
+ * BUILD-DEFINED (the reference's request carries the four *_current_foothold points, GlobalFootholdPlan.srv:1-4, and its handler
+ * never reads them: every plan starts from setFirstGait, cpp:2679-2699).  The state of a pose's chain BETWEEN two gait cycles is the
+ * committed feet x / y of the three tracks, the running ajustedPose_[1] and the cycle index — fpe_plan_state.  fpe_plan_resume*
+ * returns it behind the last cycle (state_out) and starts a plan from it (state_in) instead of from the nominal stance: replan the
+ * remaining cycles on a new map snapshot, branch a plan with several strides, plan a long horizon in segments.
+ * The contract:
+ *  - Concatenation.  For any pose, any n and any 0 < k < n: k cycles with state_out, then n - k cycles with that state as state_in,
+ *    give — concatenated per pose — nominal, centroid, default_next, cycle_ok, selected and selected_packed byte for byte as ONE call
+ *    of n cycles returns them, gait_cycle_id included (a resumed record carries state.cycle + g); the second call's state_out equals
+ *    the n-cycle call's state_out.
+ *  - Indexing.  Inside a call, record (b, g, leg) sits at ((b * n_cycles) + g) * 4 + leg with g LOCAL to the call.
+ *  - Start from the poses.  state_in == NULL: the call is fpe_plan_strides plus the state (all eight products).
+ *    fpe_plan_state_from_pose returns what such a call starts from: stance - double(step / 2) in all three tracks (the division in
+ *    float), adjusted_y 0, cycle 0.
+ *  - What a resumed call reads.  state_in != NULL: of poses[b] the kernels read only position[1] (N.y = initialPose_[1] +
+ *    ajustedPose_[1], cpp:2201), gait, the leg radii and the polygon kinds.  (The host forms still check every field of every pose.)
+ *  - Refused products.  stance and pose_status are products of a START, not of a continuation: a resumed call (state_in != NULL)
+ *    that asks for either returns FPE_E_INVALID_ARG and writes nothing.
+ *  - Failed cycles.  A cycle that fails commits nothing, the walk gait commits per phase — as in fpe_plan; adjusted_y and cycle
+ *    advance all the same.
+ *  - Strides.  strides == NULL: every pose uses the stride of `params`.  The stride may change from one segment to the next.
+ *  - Aliasing.  state_out may be the same array as state_in: a pose reads its element in its prologue and writes it behind its last
+ *    cycle.
+ *  - Refusals, host forms: a non-finite value, reserved != 0, cycle < 0 or cycle + n_cycles > 255 in ANY element, before anything is
+ *    queued; 1 <= n_cycles <= 255 (FPE_E_INVALID_ARG; nothing is written).
+ *  - Non-finite states, device forms (which cannot look at the values): a state with ANY non-finite foot coordinate or a non-finite
+ *    adjusted_y is treated as WHOLLY non-finite — the prologue replaces every feet[..][..][0] with NaN before the first cycle.  The
+ *    pose then takes the path a non-finite pose position takes: every leg centre fails centre_usable ahead of any index, and every
+ *    cycle holds the records listed above for a non-finite step_length; its state_out holds NaN x in every track.  (No half-finite
+ *    state reaches a kernel.)
+ *  - cycle past 255 in a device call wraps in the uint8 gait_cycle_id of the records; state_out.cycle itself does not wrap.
+ * Kernels: a resume instantiation beside every stride instantiation (fpe_describe_plan_resume: "... resume (...)"); as for strides
+ * there is no 3x3-only form, and a forced "plan_group" of 4, 16 or 64 returns FPE_E_UNSUPPORTED.  A call with neither state runs
+ * exactly what fpe_plan_strides runs.
+ * Out of scope: fpe_plan_rank* (the cog-speed KPI's first current feet are a separate question), the opt track, the service calls,
+ * fpe_multi_* / dist.py, and z in the state (getDefaultFootholdNext overwrites it with 0, and no track's recurrence reads it). */
+typedef struct fpe_plan_state {      /* 208 bytes; element b belongs to poses[b] */
+    double  feet[3][4][2];  /* [track: 0 default, 1 centroid, 2 nominal][leg: RF,RH,LH,LF][x, y]: the three tracks'
+                               *_currentPosition_ members between two gait cycles (cpp:562-588, 1338-1341, 1413-1416, 1480-1483) */
+    double  adjusted_y;     /* ajustedPose_[1] (cpp:759, 1578): the running sum, not cycle * drift */
+    int32_t cycle;          /* gait cycles planned so far = gait_cycle_id of the next one */
+    int32_t reserved;       /* 0 */
+} fpe_plan_state;
+/* Host arrays; synchronous.  strides, state_in and state_out may each be NULL. */
+int fpe_plan_resume(fpe_handle h, const fpe_params* params, const fpe_pose* poses, const fpe_stride* strides,
+                    const fpe_plan_state* state_in, int32_t B, int32_t n_cycles, const fpe_plan_out* out, fpe_plan_state* state_out);
+/* Device arrays; asynchronous on `stream`, snapshot semantics of fpe_plan_device. */
+int fpe_plan_resume_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_poses, const fpe_stride* d_strides,
+                           const fpe_plan_state* d_state_in, int32_t B, int32_t n_cycles, const fpe_plan_out* d_out,
+                           fpe_plan_state* d_state_out, void* stream);
+/* What a call with state_in == NULL starts pose `pose` from (stride NULL: the stride of params).  Host arithmetic only; no engine. */
+int fpe_plan_state_from_pose(const fpe_params* params, const fpe_pose* pose, const fpe_stride* stride, fpe_plan_state* out);
+/* A state whose three tracks all stand on the given feet ([leg: RF,RH,LH,LF][x, y]) — the seam for the request's four
+ * *_current_foothold points.  Finite values and 0 <= cycle <= 254, else FPE_E_INVALID_ARG.  Host arithmetic only; no engine. */
+int fpe_plan_state_from_feet(const double feet_xy[4][2], double adjusted_y, int32_t cycle, fpe_plan_state* out);
+/* fpe_describe_plan for the kernel a resume call (either state given) launches on the current map. */
+int fpe_describe_plan_resume(fpe_handle h, const fpe_params* params, char* buf, int32_t n);
+
 /* ---- the dense maps as grid_map message layers: the inverse of fpe_upload_map's ingest ----------------------------------
  * BUILD-DEFINED (the reference publishes none of these layers).  One call runs the dense families whose layers are requested —
  * fpe_foothold_map, fpe_foothold_snap, fpe_centroid_map with the same params, roi, radius and polygon; only the products

@@ -53,6 +53,9 @@ CENTROID_DTYPE = np.dtype(
 )
 # fpe_stride: step length and lateral drift of ONE pose (fpe_plan_strides*, fpe_plan_rank_strides*); element b belongs to poses[b]
 STRIDE_DTYPE = np.dtype([("step_length", "<f4"), ("reserved", "<i4"), ("lateral_drift", "<f8")], align=True)
+# fpe_plan_state: the state of ONE pose's chain between two gait cycles (fpe_plan_resume*): feet[track][leg][x, y], the running
+# lateral drift and the number of cycles planned so far
+PLAN_STATE_DTYPE = np.dtype([("feet", "<f8", (3, 4, 2)), ("adjusted_y", "<f8"), ("cycle", "<i4"), ("reserved", "<i4")], align=True)
 # fpe_selected_foothold: the 16-byte multi-GPU exchange record
 SELECTED_DTYPE = np.dtype(
     [("row", "<i4"), ("col", "<i4"), ("z", "<f4"), ("valid", "u1"), ("source", "u1"), ("foot_id", "u1"), ("gait_cycle_id", "u1")],
@@ -259,7 +262,7 @@ STRUCTS = {
     "fpe_track_report": TRACK_REPORT_DTYPE, "fpe_multi_device_io": MultiDeviceIO, "fpe_foothold_map_out": FootholdMapOut,
     "fpe_foothold_snap_out": FootholdSnapOut, "fpe_centroid_query": CentroidQuery, "fpe_centroid_map_out": CentroidMapOut,
     "fpe_pose_summary": PoseSummary, "fpe_rank_params": RankParams, "fpe_rank_out": RankOut, "fpe_layer_layout": LayerLayout,
-    "fpe_layer_request": LayerRequest, "fpe_stride": STRIDE_DTYPE,
+    "fpe_layer_request": LayerRequest, "fpe_stride": STRIDE_DTYPE, "fpe_plan_state": PLAN_STATE_DTYPE,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -328,6 +331,11 @@ PROTOTYPES = {
     "fpe_plan_rank_strides": (cint, [vp, vp, P(RankParams), vp, vp, i32, i32, i32, P(RankOut)]),
     "fpe_plan_rank_strides_device": (cint, [vp, vp, P(RankParams), vp, vp, i32, i32, i32, P(PlanOut), P(RankOut), vp]),
     "fpe_describe_plan_strides": (cint, [vp, vp, cstr, i32]),
+    "fpe_plan_resume": (cint, [vp, vp, vp, vp, vp, i32, i32, P(PlanOut), vp]),
+    "fpe_plan_resume_device": (cint, [vp, vp, vp, vp, vp, i32, i32, P(PlanOut), vp, vp]),
+    "fpe_plan_state_from_pose": (cint, [vp, vp, vp, vp]),
+    "fpe_plan_state_from_feet": (cint, [vp, f64, i32, vp]),
+    "fpe_describe_plan_resume": (cint, [vp, vp, cstr, i32]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

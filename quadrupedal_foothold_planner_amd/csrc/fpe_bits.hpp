@@ -116,22 +116,24 @@ bool bits_supported(const PlanConsts& pc, const MapGeom& g) {
 }
 
 // Which kernel a chained plan with these constants launches (evidence for bench.py / profiles).
-// strides: the kernel a stride call (fpe_plan_strides*) launches — "<kernel> stride (...)"; the 3x3-only variants have no stride form.
-void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, bool strides) {
-    if (strides) {
+// form 1: the kernel a stride call (fpe_plan_strides*) launches — "<kernel> stride (...)"; form 2: the one a resume call
+// (fpe_plan_resume* with either state) launches — "<kernel> resume (...)"; the 3x3-only variants have neither form.
+void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, int form) {
+    if (form != 0) {
+        const char* what = form == 2 ? "resume" : "stride";
         if (bits_supported(pc, g)) {
             const BitsShape sp = bits_shape(pc.winH);
             if (sp.lanes == 8)
-                snprintf(buf, n, "plan_bits_kernel<%d, false> stride (8 lanes per leg, %d x %d bit window)", sp.nrl, 2 * pc.winH + 1, 2 * pc.winH + 1);
+                snprintf(buf, n, "plan_bits_kernel<%d, false> %s (8 lanes per leg, %d x %d bit window)", sp.nrl, what, 2 * pc.winH + 1, 2 * pc.winH + 1);
             else
-                snprintf(buf, n, "plan_bits_seq_kernel<%d, %d> stride (one wavefront per pose, %d x %d bit window, %d-bit rows)", sp.nrl, sp.kw,
+                snprintf(buf, n, "plan_bits_seq_kernel<%d, %d> %s (one wavefront per pose, %d x %d bit window, %d-bit rows)", sp.nrl, sp.kw, what,
                          2 * pc.winH + 1, 2 * pc.winH + 1, 32 * sp.kw);
             return;
         }
         const int G = plan_group_size(pc);
-        if (G == 65) snprintf(buf, n, "plan_sequential_kernel stride (direct, one wavefront per pose)");
-        else if (G == 8) snprintf(buf, n, "plan_chained_kernel<8, false> stride (direct)");
-        else snprintf(buf, n, "no stride kernel for plan_group %d", G);
+        if (G == 65) snprintf(buf, n, "plan_sequential_kernel %s (direct, one wavefront per pose)", what);
+        else if (G == 8) snprintf(buf, n, "plan_chained_kernel<8, false> %s (direct)", what);
+        else snprintf(buf, n, "no %s kernel for plan_group %d", what, G);
         return;
     }
     if (bits_supported(pc, g)) {
@@ -159,23 +161,39 @@ static auto bits_kernel_consts(const PlanConsts& pc) {
 
 // The stride form of launch_plan_bits (fpe_plan_strides*): the same shapes, grids and LDS; one instantiation per family member —
 // the any-combination product mask (kProd 0), the generic 8-lane variants, and the group sizes the launch below can reach.
+// With either state (fpe_plan_resume*): the resume instantiations, {strides, state_in, state_out} as the trailing arguments, each of
+// which may be null.
 static hipError_t launch_plan_bits_strides(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                                           int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides) {
+                                           int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides,
+                                           const fpe_plan_state* d_stateIn, fpe_plan_state* d_stateOut) {
     const BitsShape sp = bits_shape(pc.winH);
     const dim3 block(64);
+    const bool resume = d_stateIn != nullptr || d_stateOut != nullptr;
 #define FPE_LAUNCH_BITS_STRIDE(NRL)                                                                                                   \
-    hipLaunchKernelGGL((plan_bits_stride_kernel<NRL, 0>), dim3((B + 1) / 2), block,                                                  \
-                       2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW) + (sizeof(YEntry) + sizeof(UnitG)) * 16), stream, \
-                       d_poses, B, nCycles, m, bm, pc, lut, d_out, d_strides)
+    do {                                                                                                                              \
+        const size_t ldsB = 2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW) + (sizeof(YEntry) + sizeof(UnitG)) * 16); \
+        if (resume)                                                                                                                   \
+            hipLaunchKernelGGL((plan_bits_resume_kernel<NRL, 0>), dim3((B + 1) / 2), block, ldsB, stream, d_poses, B, nCycles, m, bm, pc, lut, \
+                               d_out, d_strides, d_stateIn, d_stateOut);                                                              \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((plan_bits_stride_kernel<NRL, 0>), dim3((B + 1) / 2), block, ldsB, stream, d_poses, B, nCycles, m, bm, pc, lut, \
+                               d_out, d_strides);                                                                                     \
+    } while (0)
+#define FPE_SEQ_RESUME_KERNEL(NRL, KW, GRP) plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>
 #define FPE_LAUNCH_BITS_SEQ_STRIDE_G(NRL, KW, GRP, GRID, LDS, SLOT)                                                                     \
     do {                                                                                                                              \
         if ((LDS) > 64 * 1024) {                                                                                                      \
-            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>),   \
+            const hipError_t ea = hipFuncSetAttribute(resume ? reinterpret_cast<const void*>(FPE_SEQ_RESUME_KERNEL(NRL, KW, GRP))     \
+                                                             : reinterpret_cast<const void*>(plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>),   \
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(LDS));             \
             if (ea != hipSuccess) return ea;                                                                                          \
         }                                                                                                                             \
-        hipLaunchKernelGGL((plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B, \
-                           nCycles, d_out, recSlots, static_cast<int>(SLOT), d_strides);                                              \
+        if (resume)                                                                                                                   \
+            hipLaunchKernelGGL((FPE_SEQ_RESUME_KERNEL(NRL, KW, GRP)), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B, \
+                               nCycles, d_out, recSlots, static_cast<int>(SLOT), d_strides, d_stateIn, d_stateOut);                   \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B, \
+                               nCycles, d_out, recSlots, static_cast<int>(SLOT), d_strides);                                          \
     } while (0)
     if (sp.lanes == 8) {
         if (sp.nrl == 2) FPE_LAUNCH_BITS_STRIDE(2);
@@ -198,12 +216,15 @@ static hipError_t launch_plan_bits_strides(const DevMap& m, const BitMap& bm, co
     }
 #undef FPE_LAUNCH_BITS_STRIDE
 #undef FPE_LAUNCH_BITS_SEQ_STRIDE_G
+#undef FPE_SEQ_RESUME_KERNEL
     return hipGetLastError();
 }
 
 hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                            int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides) {
-    if (d_strides) return launch_plan_bits_strides(m, bm, pc, lut, d_poses, B, nCycles, d_out, stream, d_strides);
+                            int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides,
+                            const fpe_plan_state* d_stateIn, fpe_plan_state* d_stateOut) {
+    if (d_strides || d_stateIn || d_stateOut)
+        return launch_plan_bits_strides(m, bm, pc, lut, d_poses, B, nCycles, d_out, stream, d_strides, d_stateIn, d_stateOut);
     const BitsShape sp = bits_shape(pc.winH);
     const bool mid = mid_variant(pc, m.g.res) && pc.nFoot == 1;  // rf < res: the candidate disc is the candidate's own cell
     const dim3 block(64);

@@ -214,7 +214,8 @@ __device__ __forceinline__ void unitg_put_disc(const DevMap& m, const PlanConsts
 // validity.  One instruction stream for both (the arguments differ per lane, not the code).
 __device__ __forceinline__ void flush_unit_g(const DevMap& m, const PlanConsts& pc, const int8_t* footDa, const int8_t* footDb,
                                              const UnitG& uLds, const YEntry& yeLds, int b, int cyc, int leg, int half, int nCycles,
-                                             uint32_t okBits, const fpe_plan_out& out) {
+                                             uint32_t okBits, const fpe_plan_out& out, int cycBase = 0) {
+    // cycBase (the resume kernels: fpe_plan_state.cycle): added to the records' gait_cycle_id; every index stays the call's own `cyc`
     const MapGeom& mg = m.g;
     UnitG u;
     __builtin_memcpy(&u, &uLds, sizeof(UnitG));
@@ -254,10 +255,10 @@ __device__ __forceinline__ void flush_unit_g(const DevMap& m, const PlanConsts& 
         f.valid = static_cast<uint8_t>(valid);
         f.source = static_cast<uint8_t>(source);
         f.foot_id = static_cast<uint8_t>(leg);
-        f.gait_cycle_id = static_cast<uint8_t>(cyc);
+        f.gait_cycle_id = static_cast<uint8_t>(cycBase + cyc);
         store_record<true>(out.nominal + o, f);
     }
-    store_selected<true>(out, o, u.nomRow, u.nomCol, zN, valid, source, leg, cyc);
+    store_selected<true>(out, o, u.nomRow, u.nomCol, zN, valid, source, leg, cycBase + cyc);
     if (out.centroid) {
         fpe_centroid_foothold cf;
         cf.x = code == 0 ? u.cx : (code <= 4 ? u.cenX : 0.0);
@@ -1045,17 +1046,20 @@ constexpr int kBitsGenericWaves = 3;  // measured on cfg-4: 2 -> 1.36 ms, 3 -> 1
 // both poses trot, no leg overrides the search radius, every search polygon is the rectangle — one phase a cycle with all four
 // legs swinging (no phase loop, no swing mask), advance = step, and the legs' search constants are the plan's own (uniform).
 // kPlain = false is the general code.  Always inlined into the kernel.  kStride (plan_bits_stride_kernel): step and drift are the
-// pose's own (sv, and hc.drift filled from it by the kernel) instead of the plan's.
+// pose's own (sv, and hc.drift filled from it by the kernel) instead of the plan's.  kResume (plan_bits_resume_kernel, a stride form
+// too): with rs.in the prologue takes the pose's committed feet, running drift and cycle index from an earlier call's state instead
+// of the stance, and with rs.out the epilogue returns them behind the last flush (fpe_plan_resume*, include/fpe.h).
 // (The LDS views and the rank table's head are set up HERE, once per copy, not in the kernel ahead of the verdict: a value both
 // copies read has to be computed in front of the branch and stays in its register through either copy, where one copy's own
 // value is computed next to its use — with them in the kernel the <4, true, *> instances spilled four vector registers.)
-template <int NRL, bool kMid, int kProd, bool kPlain, bool kStride = false, class PC>
+template <int NRL, bool kMid, int kProd, bool kPlain, bool kStride = false, bool kResume = false, class PC>
 __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool live, double x0, double y0, double z0, int gait, float rOverride,
                                                int polyKindIn, int nCycles, const DevMap& m, const DevMap& mArg, const BitMap& bm, const PC& pc,
                                                const SpiralLut& lut, const fpe_plan_out& out, const HotConsts& hc, int tid, int slot, int leg,
-                                               const StrideVals& sv = StrideVals{}) {
+                                               const StrideVals& sv = StrideVals{}, const ResumeArgs& rs = ResumeArgs{}) {
     static_assert(kMid || !kPlain, "the generic kernels have no plain instance");
     static_assert(!kMid || !kStride, "the 3x3-only kernels have no stride instance");
+    static_assert(!kResume || kStride, "a resume instance is a stride instance");
     constexpr int G = 8;
     constexpr bool kNoDefault = kProd == 1;
     constexpr int kPoseThreads = 4 * G;
@@ -1116,8 +1120,28 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             sh.footOff[k] = 0;
         }
     }
+    double adjY = 0.0;  // ajustedPose_[1], cpp:759
+    int cycBase = 0;    // gait_cycle_id of the call's first cycle
+    bool started = true;
+    if constexpr (kResume) {
+        if (rs.in) {  // (uniform) the state of an earlier call instead of the stance; the padding slot of an odd batch reads pose B-1's
+            started = false;
+            const LegState st = load_leg_state(rs.in, b, leg);
+            const unsigned long long poseMaskR = ((1ull << kPoseThreads) - 1ull) << (slot * kPoseThreads);
+            const bool poseFinite = (__ballot(!st.finite) & poseMaskR) == 0ull;  // any non-finite value: the whole state is non-finite
+            adjY = st.adjY;
+            cycBase = st.cycle;
+            if (g.sub == 0) {
+                for (int t = 0; t < 3; ++t) {
+                    sh.cur[t][leg][0] = poseFinite ? st.x[t] : __builtin_nan("");
+                    sh.cur[t][leg][1] = st.y[t];
+                    sh.cur[t][leg][2] = 0.0;
+                }
+            }
+        }
+    }
     // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699)
-    if (g.sub == 0) {
+    if (started && g.sub == 0) {
         double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
         double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
         double sz = 0;
@@ -1146,7 +1170,7 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
     constexpr bool kStanceOnce = kMid && NRL < 4;
     double stanceCtr = 0.0;
     if constexpr (kStanceOnce) stanceCtr = polygon_center_x(sh.cur[0]);
-    if (out.pose_status) {
+    if (started && out.pose_status) {
         // getGaitCycleSearchGridMap's getSubmap in the first cycle (opt_gate_cycle0), its four corners on four lanes
         const double gx = (kStanceOnce ? stanceCtr : polygon_center_x(sh.cur[0])) + (kStride ? sv.step : pc.step), gy = y0 + 0.0;  // cpp:2327-2329
         Submap gs;
@@ -1182,7 +1206,6 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             out.pose_status[b] = (centre_usable(gx, gy) && gs.ok) ? 0 : static_cast<uint8_t>(FPE_POSE_OPT_SUBMAP_FAILED);
     }
 
-    double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (!kPlain && gait == 1) ? 4 : 1;
     const double advance = (!kPlain && gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
     // swing order LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
@@ -1282,11 +1305,14 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             } else {
                 const int us = g.sub >> 1;  // two lanes per unit (kBatch * 2 == G)
                 if (live && c0 + us <= cyc)
-                    flush_unit_g(m, pc, sh.footDa, sh.footDb, units[us], ytab[us], b, c0 + us, leg, g.sub & 1, nCycles, okBits, out);
+                    flush_unit_g(m, pc, sh.footDa, sh.footDb, units[us], ytab[us], b, c0 + us, leg, g.sub & 1, nCycles, okBits, out, cycBase);
             }
             okBits = 0u;
             bits_sync<G>();  // the units and the y entries are rewritten next
         }
+    }
+    if constexpr (kResume) {  // the state behind the last flush (the last phase's commit is behind its bits_sync)
+        if (rs.out && live && g.sub == 0) store_leg_state(rs.out, b, leg, sh.cur, adjY, cycBase + nCycles);
     }
 }
 
@@ -1386,4 +1412,39 @@ __global__ __launch_bounds__(64, kBitsGenericWaves) void plan_bits_stride_kernel
     hc.drift = sv.drift;  // per pose slot: the y-table fill and the per-cycle sum add the pose's own drift
     plan_bits_body<NRL, false, kProd, false, true>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, mArg, mArg, bm, pc, lut, out, hc, tid, slot, leg,
                                                    sv);
+}
+
+// The resume form of the generic 8-lane kernel (fpe_plan_resume*): the stride form's body with the chain's state across the call
+// boundary — {strides, state_in, state_out} as the TRAILING arguments, each of which may be null (strides: the plan's own step and
+// drift, one uniform branch; state_in: today's prologue; state_out: nothing returned).  A pose's 208-byte state is loaded beside its
+// pose and its stride, the padding slot of an odd batch reading pose B-1's like its pose.
+template <int NRL, int kProd>
+__global__ __launch_bounds__(64, kBitsGenericWaves) void plan_bits_resume_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, DevMap mArg, BitMap bm,
+                                                                                PlanConsts pc, SpiralLut lut, fpe_plan_out outArg,
+                                                                                const fpe_stride* __restrict__ strides, const fpe_plan_state* stateIn,
+                                                                                fpe_plan_state* stateOut) {
+    constexpr int G = 8;
+    const fpe_plan_out out = specialise_products<kProd>(outArg);
+    constexpr int kPoseThreads = 4 * G;
+    const int tid = static_cast<int>(threadIdx.x);
+    const int slot = tid / kPoseThreads;
+    const int leg = (tid / G) & 3;
+    int b = blockIdx.x * 2 + slot;
+    const bool live = b < B;  // the padding pose of the last block runs the chain on pose B-1 (its stride, its state), stores nothing
+    if (!live) b = B - 1;
+    const fpe_pose* pp = poses + b;
+    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
+    const int gait = pp->gait;
+    const float rOverride = pp->leg_search_radius[leg];
+    const int polyKindIn = pp->leg_polygon_kind[leg];
+    const StrideVals sv = load_stride_or_plan(strides, b, pc);
+    __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
+    HotConsts hc;
+    hc.rf = in_vgpr(pc.rf);
+    hc.rf2 = in_vgpr(pc.rf2);
+    hc.cornerEps = in_vgpr(pc.cornerEps);
+    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
+    hc.drift = sv.drift;  // per pose slot: the y-table fill and the per-cycle sum add the pose's own drift
+    plan_bits_body<NRL, false, kProd, false, true, true>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, mArg, mArg, bm, pc, lut, out, hc, tid, slot,
+                                                         leg, sv, ResumeArgs{stateIn, stateOut});
 }

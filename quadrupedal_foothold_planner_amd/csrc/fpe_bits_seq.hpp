@@ -241,7 +241,8 @@ __device__ __forceinline__ void seq_leg_phase(const DevMap& m, const BitMap& bm,
 // centroid result's disc and writes the nominal / selected / centroid records, half 1 the default-track disc and the
 // default_next record.  One instruction stream for both halves (the arguments differ per lane, not the code).
 __device__ __forceinline__ void flush_seqrec2(const DevMap& m, const PlanConsts& pc, const int8_t* footDa, const int8_t* footDb, const SeqRec& rLds,
-                                              int b, int cyc, int leg, int half, int nCycles, const fpe_plan_out& out) {
+                                              int b, int cyc, int leg, int half, int nCycles, const fpe_plan_out& out, int cycBase = 0) {
+    // cycBase (the resume form: fpe_plan_state.cycle): added to the records' gait_cycle_id; the index stays the call's own `cyc`
     SeqRec r;
     __builtin_memcpy(&r, &rLds, sizeof(SeqRec));
     const size_t o = (static_cast<size_t>(b) * nCycles + cyc) * 4 + leg;
@@ -268,10 +269,10 @@ __device__ __forceinline__ void flush_seqrec2(const DevMap& m, const PlanConsts&
         fpe_foothold f;
         f.row = r.nomRow; f.col = r.nomCol; f.x = r.nomX; f.y = r.nomY; f.z = zN;
         f.valid = valid; f.source = source;
-        f.foot_id = static_cast<uint8_t>(leg); f.gait_cycle_id = static_cast<uint8_t>(cyc);
+        f.foot_id = static_cast<uint8_t>(leg); f.gait_cycle_id = static_cast<uint8_t>(cycBase + cyc);
         store_record<true>(out.nominal + o, f);
     }
-    store_selected<true>(out, o, r.nomRow, r.nomCol, zN, valid, source, leg, cyc);
+    store_selected<true>(out, o, r.nomRow, r.nomCol, zN, valid, source, leg, cycBase + cyc);
     if (out.centroid) {
         fpe_centroid_foothold cf;
         cf.x = r.cenX; cf.y = r.cenY; cf.z = zC; cf.row = r.cenRow; cf.col = r.cenCol;
@@ -301,6 +302,8 @@ struct SeqKernArgs {
     int recSlots;
     int slotBytes;
     const fpe_stride* strides;  // the one trailing argument of the kernel's stride form (not in the segment otherwise: never read there)
+    const fpe_plan_state* stateIn;  // ... and, behind it, the two more of its resume form (likewise)
+    fpe_plan_state* stateOut;
 };
 // The argument reload pays on the 96-bit-row instantiations only — measured, round 6, A/B in one call, twice:
 // cfg-5 (<2, 3>) 0.3060 -> 0.3017 ms and its 32 B of vector scratch gone; cfg-3 (<1, 2>) 0.6075 -> 0.6211 ms although three quarters of
@@ -313,8 +316,9 @@ constexpr bool kSeqReloadArgs = KW >= 3;
 // 0.5959 ms), and the kernel can put SIXTEEN poses in one workgroup (one workgroup per CU instead of sixteen: cfg-5 0.3023 -> 0.2959 ms;
 // plan_bits_seq_kernel below).  A/B in one call, three repetitions: profiles/round6_seq_floor.txt.
 // kStride (the kernel's stride form): the step and the drift are the pose's own, scalar loads of strides[b] through the argument
-// segment's trailing pointer.
-template <int NRL, int KW, int kProd, bool kStride = false>
+// segment's trailing pointer.  kResume (the kernel's resume form, a stride form too): a null `strides` means the plan's own pair, and
+// the chain's state comes from stateIn (null: the stance prologue) and goes to stateOut (null: nowhere) — fpe_plan_resume*.
+template <int NRL, int KW, int kProd, bool kStride = false, bool kResume = false>
 __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attribute__((address_space(4))) * kaIn, int slotOffIn, int bInV, int tid, unsigned hwidIn,
                                                        const LutHead& head) {
     constexpr int G = 64;
@@ -355,15 +359,38 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
     const fpe_pose* pp = poses + b;
     const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
     const int gait = pp->gait;
+    static_assert(!kResume || kStride, "a resume instance is a stride instance");
     StrideVals sv{};
-    if constexpr (kStride) sv = load_stride(kaG->strides, b);
+    if constexpr (kResume) sv = load_stride_or_plan(kaG->strides, b, pc);
+    else if constexpr (kStride) sv = load_stride(kaG->strides, b);
+    double adjY = 0.0;  // ajustedPose_[1], cpp:759
+    int cycBase = 0;    // gait_cycle_id of the call's first cycle
+    bool started = true;
+    if constexpr (kResume) {
+        const fpe_plan_state* stateIn = kaG->stateIn;
+        if (stateIn) {  // (uniform) the committed feet, the running drift and the cycle index of an earlier call instead of the stance
+            started = false;
+            const LegState st = load_leg_state(stateIn, b, tid & 3);  // lane = leg (every lane loads: the verdict is a ballot)
+            const bool poseFinite = __ballot(!st.finite) == 0ull;
+            adjY = st.adjY;
+            cycBase = __builtin_amdgcn_readfirstlane(st.cycle);
+            if (tid < 4) {
+                lsTab[tid] = make_leg_static(pc, pp, tid, m.g.res, lut);
+                for (int t = 0; t < 3; ++t) {
+                    sh.cur[t][tid][0] = poseFinite ? st.x[t] : __builtin_nan("");
+                    sh.cur[t][tid][1] = st.y[t];
+                    sh.cur[t][tid][2] = 0.0;
+                }
+            }
+        }
+    }
     for (int k = tid; k < pc.nFoot; k += G) {
         sh.footDa[k] = pc.footDa[k];
         sh.footDb[k] = pc.footDb[k];
         sh.footOff[k] = 0;
     }
     // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699): lane = leg
-    if (tid < 4) {
+    if (started && tid < 4) {
         const int leg = tid;
         lsTab[leg] = make_leg_static(pc, pp, leg, m.g.res, lut);
         double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
@@ -385,9 +412,8 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
         }
     }
     pose_sync<16>();
-    if (out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
+    if (started && out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
 
-    double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (gait == 1) ? 4 : 1;
     const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
     const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
@@ -495,11 +521,15 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
                                            : recBase;
                 {  // deferred heights: two lanes per (cycle, leg) unit
                     const int un = tid >> 1, c = (cyc - slot) + (un >> 2);
-                    if (un < 4 * slotsF && c <= cyc) flush_seqrec2(mF, pcF, sh.footDa, sh.footDb, recF[un], b, c, un & 3, tid & 1, nCycF, outF);
+                    if (un < 4 * slotsF && c <= cyc) flush_seqrec2(mF, pcF, sh.footDa, sh.footDb, recF[un], b, c, un & 3, tid & 1, nCycF, outF, cycBase);
                 }
                 pose_sync<16>();  // the slots are rewritten next
             }
         }
+    }
+    if constexpr (kResume) {  // the state behind the last flush (the last phase's commit is behind its pose_sync)
+        fpe_plan_state* stateOut = kaG->stateOut;
+        if (stateOut && tid < 4) store_leg_state(stateOut, b, tid, sh.cur, adjY, cycBase + kaG->nCycles);
     }
 }
 
@@ -507,11 +537,12 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
 // workgroup of 1 024 threads per CU; the launch's choice for batches of at least 64 poses on the 96-bit-row windows) or 1.
 // Stride form (fpe_plan_strides*): S = {const fpe_stride*}, ONE trailing argument behind slotBytes, which the callee reads through
 // SeqKernArgs::strides.  S empty (the default): the kernel and its argument segment as they always were.
+// Resume form (fpe_plan_resume*): S = {const fpe_stride*, const fpe_plan_state*, fpe_plan_state*}, read through SeqKernArgs likewise.
 template <int NRL, int KW, int kProd, int kGroup, class... S>
 __global__ __launch_bounds__(64 * kGroup, kGroup == 1 ? kSeqWaves : 1) void plan_bits_seq_kernel(DevMap m, BitMap bm, PlanConsts pc, SpiralLut lut,
                                                                                                 const fpe_pose* __restrict__ poses, int B, int nCycles, fpe_plan_out outArg,
                                                                                                 int recSlots, int slotBytes, S... strideArg) {
-    static_assert(sizeof...(S) <= 1, "one optional trailing argument: the strides");
+    static_assert(sizeof...(S) <= 1 || sizeof...(S) == 3, "optional trailing arguments: the strides, or the strides and the two states");
     const int tid = static_cast<int>(threadIdx.x) & 63, wv = static_cast<int>(threadIdx.x) >> 6;
     const int b = static_cast<int>(blockIdx.x) * kGroup + wv;
     if (b >= B) return;
@@ -522,7 +553,7 @@ __global__ __launch_bounds__(64 * kGroup, kGroup == 1 ? kSeqWaves : 1) void plan
     (void)m; (void)bm; (void)poses; (void)nCycles; (void)outArg; (void)recSlots;
     ((void)strideArg, ...);
     typedef const SeqKernArgs __attribute__((address_space(4))) * KernArgPtr0;
-    seq_run_pose<NRL, KW, kProd, sizeof...(S) != 0>((KernArgPtr0)__builtin_amdgcn_kernarg_segment_ptr(), wv * slotBytes, b, tid, hwid, head);
+    seq_run_pose<NRL, KW, kProd, sizeof...(S) != 0, sizeof...(S) == 3>((KernArgPtr0)__builtin_amdgcn_kernarg_segment_ptr(), wv * slotBytes, b, tid, hwid, head);
 }
 static_assert(kernargs_mirror<decltype(plan_bits_seq_kernel<1, 2, 0, 1>)>(
                   {offsetof(SeqKernArgs, m), offsetof(SeqKernArgs, bm), offsetof(SeqKernArgs, pc), offsetof(SeqKernArgs, lut),
@@ -536,3 +567,10 @@ static_assert(kernargs_mirror<decltype(plan_bits_seq_kernel<1, 2, 0, 1, const fp
                    offsetof(SeqKernArgs, recSlots), offsetof(SeqKernArgs, slotBytes), offsetof(SeqKernArgs, strides)},
                   offsetof(SeqKernArgs, strides) + sizeof(SeqKernArgs::strides)),
               "SeqKernArgs must mirror the parameters of plan_bits_seq_kernel's stride form");
+static_assert(kernargs_mirror<decltype(plan_bits_seq_kernel<1, 2, 0, 1, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>)>(
+                  {offsetof(SeqKernArgs, m), offsetof(SeqKernArgs, bm), offsetof(SeqKernArgs, pc), offsetof(SeqKernArgs, lut),
+                   offsetof(SeqKernArgs, poses), offsetof(SeqKernArgs, B), offsetof(SeqKernArgs, nCycles), offsetof(SeqKernArgs, out),
+                   offsetof(SeqKernArgs, recSlots), offsetof(SeqKernArgs, slotBytes), offsetof(SeqKernArgs, strides),
+                   offsetof(SeqKernArgs, stateIn), offsetof(SeqKernArgs, stateOut)},
+                  offsetof(SeqKernArgs, stateOut) + sizeof(SeqKernArgs::stateOut)),
+              "SeqKernArgs must mirror the parameters of plan_bits_seq_kernel's resume form");

@@ -931,7 +931,7 @@ struct Seg {
     void* dst;
 };
 struct SegList {
-    Seg s[kProducts];  // (a ranking call: its eight products and four outputs of its own)
+    Seg s[kProducts + 1];  // (a ranking call: its eight products and four outputs of its own; a resume call: the state as well)
     int n = 0;
     void add(size_t off, size_t len, void* dst) {
         if (dst && len) s[n++] = Seg{off, len, dst};
@@ -954,7 +954,7 @@ int copy_out(fpe_engine* h, CallCtx& cx, SegList list, const unsigned char* dev,
     Seg* const segs = list.s;
     const int nSeg = list.n;
     size_t staged = 0;
-    bool pinnedSeg[kProducts];
+    bool pinnedSeg[kProducts + 1];
     for (int k = 0; k < nSeg; ++k) pinnedSeg[k] = is_pinned_host(segs[k].dst);
     for (int k = 0; k < nSeg; ++k) {
         if (!pinnedSeg[k]) {
@@ -1285,7 +1285,7 @@ int fpe_set_tuning(fpe_handle h, const char* key, int32_t value) {
     return FPE_OK;
 }
 
-static int describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n, bool strides) {
+static int describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n, int form) {
     if (!h || !params || !buf || n <= 0) return fail(FPE_E_INVALID_ARG, "null argument");
     std::shared_ptr<MapSnapshot> snap;
     fpe::Tuning tuning;
@@ -1299,11 +1299,12 @@ static int describe_plan(fpe_handle h, const fpe_params* params, char* buf, int3
     if (!snap) return fail(FPE_E_NO_MAP, "no map uploaded");
     fpe::PlanConsts pc;
     fpe::derive_constants(*params, snap->g, maxRadius, tuning, pc);
-    fpe::describe_plan_kernel(pc, snap->g, buf, static_cast<size_t>(n), strides);
+    fpe::describe_plan_kernel(pc, snap->g, buf, static_cast<size_t>(n), form);
     return FPE_OK;
 }
-int fpe_describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, false); }
-int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, true); }
+int fpe_describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, 0); }
+int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, 1); }
+int fpe_describe_plan_resume(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, 2); }
 
 int fpe_set_max_leg_search_radius(fpe_handle h, float radius) {
     if (!h || !(radius >= 0.0f) || !std::isfinite(radius)) return fail(FPE_E_INVALID_ARG, "bad radius");
@@ -1489,22 +1490,32 @@ int fpe_map_info(fpe_handle h, fpe_map_desc* out) {
 }
 
 // One chained-plan launch on `stream`: the bit-window kernels when the snapshot's bit planes apply, else the direct ones.
-// d_strides (null: none): the stride form, fpe_plan_strides* / fpe_plan_rank_strides*.
-static int check_strides_launchable(const CallPlan& cp, const fpe_stride* d_strides) {
-    if (d_strides && !cp.useBits && !fpe::plan_chained_strides_supported(cp.pc))
-        return fail(FPE_E_UNSUPPORTED, "per-pose strides: no stride kernel for a forced plan_group of 4, 16 or 64");
+// d_strides (null: none): the stride form, fpe_plan_strides* / fpe_plan_rank_strides*.  states (either one of fpe_plan_resume*'s
+// given): the resume form, which exists where the stride form does.
+static int check_strides_launchable(const CallPlan& cp, const fpe_stride* d_strides, bool states = false) {
+    if ((d_strides || states) && !cp.useBits && !fpe::plan_chained_strides_supported(cp.pc))
+        return fail(FPE_E_UNSUPPORTED, states ? "resumable plans: no resume kernel for a forced plan_group of 4, 16 or 64"
+                                              : "per-pose strides: no stride kernel for a forced plan_group of 4, 16 or 64");
+    return FPE_OK;
+}
+// stance and pose_status are products of a start, not of a continuation (include/fpe.h)
+static int check_resumed_products(const fpe_plan_state* stateIn, const fpe_plan_out& out) {
+    if (stateIn && (out.stance || out.pose_status))
+        return fail(FPE_E_INVALID_ARG, "a resumed plan (state_in given) has no stance and no pose_status");
     return FPE_OK;
 }
 static int launch_plan(fpe_engine* h, const CallPlan& cp, const fpe_pose* d_poses, int32_t B, int32_t n_cycles,
-                       const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr) {
+                       const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr,
+                       const fpe_plan_state* d_stateIn = nullptr, fpe_plan_state* d_stateOut = nullptr) {
     int rc = check_packed_fits(cp, d_out.selected_packed != nullptr);
     if (rc != FPE_OK) return rc;
-    rc = check_strides_launchable(cp, d_strides);
+    rc = check_strides_launchable(cp, d_strides, d_stateIn || d_stateOut);
     if (rc != FPE_OK) return rc;
     if (cp.useBits)
-        FPE_HIP(fpe::launch_plan_bits(dev_map(*cp.snap), cp.bits, cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides));
+        FPE_HIP(fpe::launch_plan_bits(dev_map(*cp.snap), cp.bits, cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides, d_stateIn,
+                                      d_stateOut));
     else
-        FPE_HIP(fpe::launch_plan_chained(dev_map(*cp.snap), cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides));
+        FPE_HIP(fpe::launch_plan_chained(dev_map(*cp.snap), cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides, d_stateIn, d_stateOut));
     return FPE_OK;
 }
 
@@ -1515,16 +1526,26 @@ int fpe_plan_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_po
 
 int fpe_plan_strides_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_poses, const fpe_stride* d_strides, int32_t B,
                             int32_t n_cycles, const fpe_plan_out* d_out, void* stream) {
+    return fpe_plan_resume_device(h, params, d_poses, d_strides, nullptr, B, n_cycles, d_out, nullptr, stream);
+}
+
+int fpe_plan_resume_device(fpe_handle h, const fpe_params* params, const fpe_pose* d_poses, const fpe_stride* d_strides,
+                           const fpe_plan_state* d_state_in, int32_t B, int32_t n_cycles, const fpe_plan_out* d_out,
+                           fpe_plan_state* d_state_out, void* stream) {
     if (!d_poses || !d_out) return fail(FPE_E_INVALID_ARG, "null argument");
     if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
+    int rc = check_resumed_products(d_state_in, *d_out);
+    if (rc != FPE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     CallPlan cp;
-    int rc = prepare_call(h, params, 0.0f, cp, st, true);
+    rc = prepare_call(h, params, 0.0f, cp, st, true);
     if (rc != FPE_OK) return rc;
-    rc = check_strides_launchable(cp, d_strides);  // (a refusal queues nothing: ahead of the async mark)
+    rc = check_strides_launchable(cp, d_strides, d_state_in || d_state_out);  // (a refusal queues nothing: ahead of the async mark)
+    if (rc != FPE_OK) return rc;
+    rc = check_packed_fits(cp, d_out->selected_packed != nullptr);
     if (rc != FPE_OK) return rc;
     mark_async_launch(cp);
-    return launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st, d_strides);
+    return launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st, d_strides, d_state_in, d_state_out);
 }
 
 namespace {
@@ -1571,23 +1592,40 @@ int check_host_strides(const fpe_stride* strides, int32_t B) {
     return FPE_OK;
 }
 
+// The states of a host-buffer resume call (null: none), checked: finite values, reserved 0, 0 <= cycle and cycle + n_cycles <= 255.
+int check_host_states(const fpe_plan_state* states, int32_t B, int32_t nCycles) {
+    if (!states) return FPE_OK;
+    for (int b = 0; b < B; ++b) {
+        const double* v = &states[b].feet[0][0][0];
+        for (int k = 0; k < 24; ++k)
+            if (!std::isfinite(v[k])) return fail(FPE_E_INVALID_ARG, "non-finite plan state");
+        if (!std::isfinite(states[b].adjusted_y)) return fail(FPE_E_INVALID_ARG, "non-finite plan state");
+        if (states[b].reserved != 0) return fail(FPE_E_INVALID_ARG, "fpe_plan_state.reserved must be 0");
+        if (states[b].cycle < 0 || states[b].cycle + nCycles > 255)
+            return fail(FPE_E_INVALID_ARG, "fpe_plan_state.cycle must be >= 0 and cycle + n_cycles <= 255");
+    }
+    return FPE_OK;
+}
+
 struct GateGeom {  // what the service call's host-side (lateral) gate needs from the call's snapshot and constants
     fpe::MapGeom g;
     double isosLen, isosWid, drift;
 };
 
 // Where a host-form plan call keeps everything in its two arenas, one device and one pinned, at the same offsets, from the product
-// table: [poses | strides | nominal | centroid | default | cycle_ok | stance | selected | status | packed | opt footholds | opt cycles
-// | gate | rows | speculative flags | completion word], in 256-byte steps; the strides (fpe_plan_strides) next to the poses; a product that is not part of the call takes no room.
+// table: [poses | strides | states | nominal | centroid | default | cycle_ok | stance | selected | status | packed | opt footholds | opt cycles
+// | gate | rows | speculative flags | completion word], in 256-byte steps; the strides (fpe_plan_strides) and the states (fpe_plan_resume: state_in staged there, state_out written there, in place in a zero-copy call) next to the poses; a product that is not part of the call takes no room.
 struct PlanLayout {
     size_t off[kProducts], len[kProducts];  // len 0: not in the arenas
-    size_t oStrides, oSpec, oDone, total;
+    size_t oStrides, oStates, oSpec, oDone, total;
 };
-PlanLayout plan_layout(int32_t B, int32_t nCycles, const bool (&inArena)[kProducts], bool specWanted, bool stridesGiven) {
+PlanLayout plan_layout(int32_t B, int32_t nCycles, const bool (&inArena)[kProducts], bool specWanted, bool stridesGiven, bool statesGiven = false) {
     PlanLayout L;
     size_t off = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
     L.oStrides = off;
     off += stridesGiven ? align256(static_cast<size_t>(B) * sizeof(fpe_stride)) : 0;
+    L.oStates = off;
+    off += statesGiven ? align256(static_cast<size_t>(B) * sizeof(fpe_plan_state)) : 0;
     for (int k = 0; k < kProducts; ++k) {
         L.off[k] = off;
         L.len[k] = inArena[k] ? product_bytes(k, static_cast<size_t>(B), static_cast<size_t>(nCycles)) : 0;
@@ -1614,14 +1652,21 @@ struct PlanRun {
     const fpe_pose* dPoses = nullptr;  // where the kernels read the poses
     const fpe_stride* strides = nullptr;   // set by plan_host: the caller's strides (fpe_plan_strides), or null
     const fpe_stride* dStrides = nullptr;  // where the kernels read them
+    const fpe_plan_state* stateIn = nullptr;   // set by plan_host: the caller's states (fpe_plan_resume), or null
+    bool stateOutWanted = false;
+    const fpe_plan_state* dStateIn = nullptr;  // where the kernels read them (the pinned arena, device-mapped) ...
+    fpe_plan_state* dStateOut = nullptr;       // ... and write them (the arena the products go to, at the same offset)
     fpe_opt_out od;                    // the opt products in that arena
 };
 
 // The per-pose inputs of a host-form batch call (fpe_plan*, fpe_plan_rank*) into its pinned arena, which the kernels read
-// device-mapped: the poses at its start, the strides (null: none) at oStrides behind them.
-void stage_batch_inputs(unsigned char* pinned, size_t oStrides, const fpe_pose* poses, const fpe_stride* strides, int32_t B) {
+// device-mapped: the poses at its start, the strides (null: none) at oStrides behind them, the states a resume call starts from
+// (null: none) at oStates behind those.
+void stage_batch_inputs(unsigned char* pinned, size_t oStrides, const fpe_pose* poses, const fpe_stride* strides, int32_t B,
+                        size_t oStates = 0, const fpe_plan_state* states = nullptr) {
     std::memcpy(pinned, poses, static_cast<size_t>(B) * sizeof(fpe_pose));
     if (strides) std::memcpy(pinned + oStrides, strides, static_cast<size_t>(B) * sizeof(fpe_stride));
+    if (states) std::memcpy(pinned + oStates, states, static_cast<size_t>(B) * sizeof(fpe_plan_state));
 }
 
 // The launches of a host-form plan call: the plan kernel and / or the opt track's chain on cx.stream — or, speculatively, the chain
@@ -1632,7 +1677,7 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
     const int32_t B = r.B, n_cycles = r.nCycles;
     const size_t nCyc = static_cast<size_t>(B) * n_cycles;
     const size_t oOk = L.off[kCycleOk];
-    stage_batch_inputs(hp, L.oStrides, poses, r.strides, B);
+    stage_batch_inputs(hp, L.oStrides, poses, r.strides, B, L.oStates, r.stateIn);
     if (r.runOpt && cycleOkIn) std::memcpy(hp + oOk, cycleOkIn, nCyc);
     // Small calls (the plan_global_footholds service: one pose) skip both DMA copies: the kernels read the
     // poses from, and write their few KB of results straight into, the pinned (coherent, device-mapped) host
@@ -1658,6 +1703,8 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
     r.dStrides = r.strides ? reinterpret_cast<const fpe_stride*>(static_cast<unsigned char*>(mapped) + L.oStrides) : nullptr;
     r.dp = r.zeroCopy ? static_cast<unsigned char*>(mapped) : cx.dev;
     unsigned char* const dp = r.dp;
+    r.dStateIn = r.stateIn ? reinterpret_cast<const fpe_plan_state*>(static_cast<unsigned char*>(mapped) + L.oStates) : nullptr;
+    r.dStateOut = r.stateOutWanted ? reinterpret_cast<fpe_plan_state*>(dp + L.oStates) : nullptr;
     if (!r.zeroCopy && r.runOpt && cycleOkIn) FPE_HIP(hipMemcpyAsync(dp + oOk, hp + oOk, nCyc, hipMemcpyHostToDevice, cx.stream));
     std::memset(&r.od, 0, sizeof(r.od));
     const auto queue_opt = [&]() -> int {
@@ -1704,7 +1751,7 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
         for (int k = 0; k < kPlanProducts; ++k) slots(d)[k] = L.len[k] ? dp + L.off[k] : nullptr;
         // every (pose, cycle, leg) record is written by the kernel (trot: all legs each cycle; walk: each
         // leg in its phase), so the buffers need no clearing
-        const int rc = launch_plan(h, cp, r.dPoses, B, n_cycles, d, cx.stream, r.dStrides);
+        const int rc = launch_plan(h, cp, r.dPoses, B, n_cycles, d, cx.stream, r.dStrides, r.dStateIn, r.dStateOut);
         if (rc != FPE_OK) return rc;
     }
     if (!r.speculate) {
@@ -1760,7 +1807,8 @@ int plan_wait_zero_copy(const CallPlan& cp, CallCtx& cx, const PlanLayout& L, co
 // plan still runs when the opt track needs its cycle flags and the caller gave none).
 int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B, int32_t n_cycles,
               const fpe_plan_out* out, const uint8_t* cycleOkIn, const fpe_opt_out* oout, GateGeom* gateGeom = nullptr,
-              bool* optDropped = nullptr, const fpe_stride* strides = nullptr) {
+              bool* optDropped = nullptr, const fpe_stride* strides = nullptr, const fpe_plan_state* stateIn = nullptr,
+              fpe_plan_state* stateOut = nullptr) {
     if (!poses || (!out && !oout)) return fail(FPE_E_INVALID_ARG, "null argument");
     if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
     float maxRadius = 0.0f;
@@ -1768,6 +1816,12 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
     if (rcPoses != FPE_OK) return rcPoses;
     rcPoses = check_host_strides(strides, B);
     if (rcPoses != FPE_OK) return rcPoses;
+    rcPoses = check_host_states(stateIn, B, n_cycles);
+    if (rcPoses != FPE_OK) return rcPoses;
+    if (out) {
+        rcPoses = check_resumed_products(stateIn, *out);
+        if (rcPoses != FPE_OK) return rcPoses;
+    }
     void* want[kProducts] = {nullptr};  // the caller's arrays, by product
     if (out) std::copy(slots(*out), slots(*out) + kPlanProducts, want);
     if (oout) std::copy(slots(*oout), slots(*oout) + kOptProducts, want + kPlanProducts);
@@ -1780,7 +1834,9 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
     run.runPlan = out != nullptr || (oout && !cycleOkIn);
     run.specWanted = run.runPlan && oout != nullptr && !cycleOkIn && B <= 4;
     run.strides = strides;
-    const PlanLayout L = plan_layout(B, n_cycles, inArena, run.specWanted, strides != nullptr);
+    run.stateIn = stateIn;
+    run.stateOutWanted = stateOut != nullptr;
+    const PlanLayout L = plan_layout(B, n_cycles, inArena, run.specWanted, strides != nullptr, stateIn != nullptr || stateOut != nullptr);
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
     HostCall hc(h);
     CallPlan& cp = hc.cp;
@@ -1809,6 +1865,7 @@ int plan_host(fpe_engine* h, const fpe_params* params, const fpe_opt_params* opt
     if (rc != FPE_OK) return rc;
     // ---- results to the caller ----
     SegList segs;
+    segs.add(L.oStates, static_cast<size_t>(B) * sizeof(fpe_plan_state), stateOut);  // (fpe_plan_resume: the state leaves with the products)
     for (int k = 0; k < kProducts; ++k) segs.add(L.off[k], L.len[k], want[k]);
     if (!run.zeroCopy) return copy_out(h, cx, segs, run.dp, cx.pinned);
     rc = plan_wait_zero_copy(cp, cx, L, oc, run);
@@ -1841,8 +1898,13 @@ int fpe_plan(fpe_handle h, const fpe_params* params, const fpe_pose* poses, int3
 
 int fpe_plan_strides(fpe_handle h, const fpe_params* params, const fpe_pose* poses, const fpe_stride* strides, int32_t B, int32_t n_cycles,
                      const fpe_plan_out* out) {
+    return fpe_plan_resume(h, params, poses, strides, nullptr, B, n_cycles, out, nullptr);
+}
+
+int fpe_plan_resume(fpe_handle h, const fpe_params* params, const fpe_pose* poses, const fpe_stride* strides, const fpe_plan_state* state_in,
+                    int32_t B, int32_t n_cycles, const fpe_plan_out* out, fpe_plan_state* state_out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
-    return plan_host(h, params, nullptr, poses, B, n_cycles, out, nullptr, nullptr, nullptr, nullptr, strides);
+    return plan_host(h, params, nullptr, poses, B, n_cycles, out, nullptr, nullptr, nullptr, nullptr, strides, state_in, state_out);
 }
 
 int fpe_plan_opt(fpe_handle h, const fpe_params* params, const fpe_opt_params* opt, const fpe_pose* poses, int32_t B,

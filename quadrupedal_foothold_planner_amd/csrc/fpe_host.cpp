@@ -586,4 +586,46 @@ double fpe_algorithmic_bytes_per_foothold(float search_radius, float foot_radius
     return 4.0 * W * W + 8.0 * nFoot + 16.0;
 }
 
+// The state a plan starts from when no state is given: the stance (cpp:350-378) shifted by setFirstGait (cpp:2679-2699) in all three
+// tracks, with derive_constants' typing — what the kernels' stance prologue writes to PoseShared::cur.
+int fpe_plan_state_from_pose(const fpe_params* params, const fpe_pose* pose, const fpe_stride* stride, fpe_plan_state* out) {
+    if (!params || !pose || !out) return FPE_E_INVALID_ARG;
+    const float step = stride ? stride->step_length : params->stepLength;
+    if (!std::isfinite(step) || (stride && stride->reserved != 0)) return FPE_E_INVALID_ARG;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(pose->position[k]) || std::fabs(pose->position[k]) > 1e6) return FPE_E_INVALID_ARG;
+    const float lengthBase = params->length;                    // cpp:340
+    const float widthBase = params->width + params->l1 * 2;     // cpp:341
+    const double LbHalf = lengthBase * 0.5, WbHalfNeg = -widthBase * 0.5, WbHalfPos = widthBase * 0.5;  // cpp:350, 351, 359
+    const double stepHalf = static_cast<double>(step / 2);      // cpp:2693 (float / int)
+    std::memset(out, 0, sizeof(*out));
+    for (int leg = 0; leg < 4; ++leg) {
+        double sx = (leg == 0 || leg == 3) ? LbHalf : -LbHalf;
+        double sy = (leg <= 1) ? WbHalfNeg : WbHalfPos;
+        sx += pose->position[0];
+        sy += pose->position[1];
+        for (int t = 0; t < 3; ++t) {
+            out->feet[t][leg][0] = sx - stepHalf;
+            out->feet[t][leg][1] = sy;
+        }
+    }
+    return FPE_OK;
+}
+
+int fpe_plan_state_from_feet(const double feet_xy[4][2], double adjusted_y, int32_t cycle, fpe_plan_state* out) {
+    if (!feet_xy || !out) return FPE_E_INVALID_ARG;
+    if (!std::isfinite(adjusted_y) || cycle < 0 || cycle > 254) return FPE_E_INVALID_ARG;
+    for (int leg = 0; leg < 4; ++leg)
+        if (!std::isfinite(feet_xy[leg][0]) || !std::isfinite(feet_xy[leg][1])) return FPE_E_INVALID_ARG;
+    std::memset(out, 0, sizeof(*out));
+    for (int t = 0; t < 3; ++t)
+        for (int leg = 0; leg < 4; ++leg) {
+            out->feet[t][leg][0] = feet_xy[leg][0];
+            out->feet[t][leg][1] = feet_xy[leg][1];
+        }
+    out->adjusted_y = adjusted_y;
+    out->cycle = cycle;
+    return FPE_OK;
+}
+
 }  // extern "C"

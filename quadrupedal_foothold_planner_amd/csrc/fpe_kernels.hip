@@ -1361,6 +1361,66 @@ __device__ __forceinline__ StrideVals load_stride(const fpe_stride* __restrict__
 // the optional trailing argument of a kernel that has a stride form (plan_chained_kernel, plan_bits_seq_kernel)
 __device__ __forceinline__ const fpe_stride* stride_arg() { return nullptr; }
 __device__ __forceinline__ const fpe_stride* stride_arg(const fpe_stride* p) { return p; }
+__device__ __forceinline__ const fpe_stride* stride_arg(const fpe_stride* p, const fpe_plan_state*, fpe_plan_state*) { return p; }
+
+// ---- resume forms (fpe_plan_resume*, include/fpe.h): the chain's state across the call boundary --------------------------------
+// The trailing pack of a kernel's resume form is {strides, state_in, state_out}, each of which may be null.
+struct ResumeArgs {
+    const fpe_plan_state* in = nullptr;  // null: the call starts from the poses (today's prologue)
+    fpe_plan_state* out = nullptr;       // null: the state is not returned
+};
+__device__ __forceinline__ ResumeArgs resume_args() { return ResumeArgs{}; }
+__device__ __forceinline__ ResumeArgs resume_args(const fpe_stride*) { return ResumeArgs{}; }
+__device__ __forceinline__ ResumeArgs resume_args(const fpe_stride*, const fpe_plan_state* in, fpe_plan_state* out) { return ResumeArgs{in, out}; }
+// The stride of a pose in a resume kernel: strides[b], or — a null array, one uniform branch — the plan's own constants.
+__device__ __forceinline__ StrideVals load_stride_or_plan(const fpe_stride* __restrict__ strides, int b, const PlanConsts& pc) {
+    if (strides) return load_stride(strides, b);
+    StrideVals v;
+    v.stepHalf = pc.stepHalf;
+    v.step = pc.step;
+    v.stepQuarter = pc.stepQuarter;
+    v.drift = pc.drift;
+    return v;
+}
+// One leg's share of a pose's state, as the prologue of a resume kernel loads it: x / y of the three tracks, and the pose's running
+// drift and cycle index (the same for its four legs).  `finite`: every value this lane looked at is finite — the caller ANDs the
+// four legs' verdicts, and a pose with any non-finite value starts with NaN x in every track (include/fpe.h).
+struct LegState {
+    double x[3], y[3];
+    double adjY;
+    int cycle;
+    bool finite;
+};
+__device__ __forceinline__ LegState load_leg_state(const fpe_plan_state* __restrict__ st, int b, int leg) {
+    const fpe_plan_state* s = st + b;
+    LegState r;
+    bool fin = true;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        r.x[t] = s->feet[t][leg][0];
+        r.y[t] = s->feet[t][leg][1];
+        fin = fin && __builtin_isfinite(r.x[t]) && __builtin_isfinite(r.y[t]);
+    }
+    r.adjY = s->adjusted_y;
+    r.cycle = s->cycle;
+    r.finite = fin && __builtin_isfinite(r.adjY);
+    return r;
+}
+// ... and what the epilogue writes behind the last cycle: the lane of `leg` stores its leg's committed x / y of the three tracks
+// (PoseShared::cur), the lane of leg 0 the running drift and the cycle index as well.
+__device__ __forceinline__ void store_leg_state(fpe_plan_state* __restrict__ st, int b, int leg, const double (*cur)[4][3], double adjY, int cycle) {
+    fpe_plan_state* s = st + b;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        s->feet[t][leg][0] = cur[t][leg][0];
+        s->feet[t][leg][1] = cur[t][leg][1];
+    }
+    if (leg == 0) {
+        s->adjusted_y = adjY;
+        s->cycle = cycle;
+        s->reserved = 0;
+    }
+}
 // kStride (the stride kernels): the step is the pose's own, sv.step.
 template <bool kStride = false>
 __device__ __forceinline__ uint8_t opt_gate_cycle0(const MapGeom& g, const PlanConsts& pc, double ctrX, double y0, const StrideVals& sv = StrideVals{}) {
@@ -1419,7 +1479,8 @@ template <int G, bool kMid = false, bool kDirect = false>
 __device__ __forceinline__ void leg_phase(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const LutHead& head,
                                           PoseShared& sh, uint8_t* tile, const Grp<G>& g, int leg, const LegStatic& ls,
                                           double y0, double adjY, double advance, int cyc, int nCycles, int b, bool live,
-                                          const fpe_plan_out& out, LegCommit* lc = nullptr) {
+                                          const fpe_plan_out& out, LegCommit* lc = nullptr, int cycBase = 0) {
+    // cycBase (the resume kernels: fpe_plan_state.cycle): added to the records' gait_cycle_id; the index stays the call's own `cyc`
     const float Rf = ls.Rf;
     const int polyKind = ls.polyKind;
     const bool radiusOk = ls.radiusOk;
@@ -1532,8 +1593,8 @@ __device__ __forceinline__ void leg_phase(const DevMap& m, const PlanConsts& pc,
             }
             if (live) {
                 const size_t o = (static_cast<size_t>(b) * nCycles + cyc) * 4 + leg;
-                if (out.nominal) store_foothold(out.nominal + o, no, leg, cyc);
-                store_selected<false>(out, o, no.row, no.col, no.z, no.valid, no.source, leg, cyc);
+                if (out.nominal) store_foothold(out.nominal + o, no, leg, cycBase + cyc);
+                store_selected<false>(out, o, no.row, no.col, no.z, no.valid, no.source, leg, cycBase + cyc);
                 if (out.centroid) {
                     fpe_centroid_foothold cf;
                     cf.x = co.x; cf.y = co.y; cf.z = co.z; cf.row = co.row; cf.col = co.col;
@@ -1557,12 +1618,16 @@ __device__ __forceinline__ void leg_phase(const DevMap& m, const PlanConsts& pc,
 constexpr int kMinWavesG16 = 4;  // occupancy the G = 16 register allocation aims at
 // Stride form (fpe_plan_strides*): S = {const fpe_stride*}, ONE trailing argument behind the list below — step and drift are then
 // the pose's own, strides[b].  S empty (the default): the kernel and its argument segment as they always were.
+// Resume form (fpe_plan_resume*): S = {const fpe_stride*, const fpe_plan_state*, fpe_plan_state*} — strides (null: the plan's own),
+// state_in (null: today's prologue) and state_out (null: not returned).
 template <int G, bool kMid = false, class... S>
 __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWavesG16 : 2)) void plan_chained_kernel(DevMap mArg, PlanConsts pc, SpiralLut lut,
                                                                            const fpe_pose* __restrict__ poses, int B,
                                                                            int nCycles, fpe_plan_out out, S... strideArg) {
     constexpr bool kStride = sizeof...(S) != 0;
-    static_assert(sizeof...(S) <= 1 && !(kStride && kMid), "one optional trailing argument: the strides; generic variant only");
+    constexpr bool kResume = sizeof...(S) == 3;
+    static_assert((sizeof...(S) <= 1 || kResume) && !(kStride && kMid), "optional trailing arguments: the strides, or strides and the two states; generic variant only");
+    static_assert(!kResume || G <= 16, "the resume form keeps a pose in one wavefront");
     // The map geometry is wave-uniform and would live in 20 scalar registers; this kernel needs more uniform
     // state than the 102 SGPRs hold, and every spilled SGPR costs a v_readlane (+ wait states) per use.  The
     // doubles are only ever operands of vector f64 arithmetic, so they are parked in VGPRs instead.
@@ -1601,7 +1666,9 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
     const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
     const int gait = pp->gait;
     StrideVals sv{};
-    if constexpr (kStride) sv = load_stride(stride_arg(strideArg...), b);
+    if constexpr (kResume) sv = load_stride_or_plan(stride_arg(strideArg...), b, pc);
+    else if constexpr (kStride) sv = load_stride(stride_arg(strideArg...), b);
+    const ResumeArgs rs = resume_args(strideArg...);
     const LegStatic ls = make_leg_static(pc, pp, leg, m.g.res, lut);
     const LutHead head = load_lut_head(lut, g);
 
@@ -1610,8 +1677,29 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
         sh.footDb[k] = pc.footDb[k];
         sh.footOff[k] = static_cast<int16_t>(pc.footDa[k] * pc.tileW + pc.footDb[k]);
     }
+    double adjY = 0.0;  // ajustedPose_[1], cpp:759
+    int cycBase = 0;    // gait_cycle_id of the call's first cycle
+    bool started = true;
+    if constexpr (kResume) {
+        if (rs.in) {  // (uniform) the committed feet, the running drift and the cycle index of an earlier call instead of the stance
+            started = false;
+            const LegState st = load_leg_state(rs.in, b, leg);
+            constexpr int kPoseLanesR = 4 * G;
+            const unsigned long long poseMaskR = (kPoseLanesR == 64) ? ~0ull : (((1ull << (kPoseLanesR & 63)) - 1ull) << (slot * kPoseLanesR));
+            const bool poseFinite = (__ballot(!st.finite) & poseMaskR) == 0ull;
+            adjY = st.adjY;
+            cycBase = st.cycle;
+            if (g.sub == 0) {
+                for (int t = 0; t < 3; ++t) {
+                    sh.cur[t][leg][0] = poseFinite ? st.x[t] : __builtin_nan("");
+                    sh.cur[t][leg][1] = st.y[t];
+                    sh.cur[t][leg][2] = 0.0;
+                }
+            }
+        }
+    }
     // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699)
-    if (g.sub == 0) {
+    if (started && g.sub == 0) {
         double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
         double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
         double sz = 0;
@@ -1631,10 +1719,9 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
         }
     }
     pose_sync<G>();
-    if (out.pose_status && live && leg == 0 && g.sub == 0)
+    if (started && out.pose_status && live && leg == 0 && g.sub == 0)
         out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
 
-    double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (gait == 1) ? 4 : 1;
     const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
     // swing order LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
@@ -1659,7 +1746,7 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
                 LegCommit lc;
                 lc.valid = 1;  // non-swing legs do not vote
                 if (active) {
-                    leg_phase<G, kMid, true>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out, &lc);
+                    leg_phase<G, kMid, true>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out, &lc, cycBase);
                 }
                 constexpr int kPoseLanes = 4 * G;
                 const unsigned long long poseMask = (kPoseLanes == 64) ? ~0ull : (((1ull << (kPoseLanes & 63)) - 1ull) << (slot * kPoseLanes));
@@ -1693,6 +1780,9 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
             out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
         adjY += kStride ? sv.drift : pc.drift;  // cpp:1578
     }
+    if constexpr (kResume) {  // the state behind the last cycle (the last phase's commit is behind its pose_sync)
+        if (rs.out && live && g.sub == 0) store_leg_state(rs.out, b, leg, sh.cur, adjY, cycBase + nCycles);
+    }
 }
 
 // ---- chained plan, sequential-legs form (large windows) ------------------------------------------------------
@@ -1705,6 +1795,9 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
 #undef FPE_SEQUENTIAL_STRIDE
 #define FPE_SEQUENTIAL_STRIDE 1
 #include "fpe_plan_sequential_body.hpp"  // plan_sequential_stride_kernel: `strides` as the one trailing argument
+#undef FPE_SEQUENTIAL_STRIDE
+#define FPE_SEQUENTIAL_STRIDE 2
+#include "fpe_plan_sequential_body.hpp"  // plan_sequential_resume_kernel: strides, state_in and state_out behind the list
 #undef FPE_SEQUENTIAL_STRIDE
 
 // ---- open-loop per-leg search: one wavefront per checkFoothold call (hpp:94-100) ----------------------
@@ -1988,10 +2081,20 @@ bool plan_chained_strides_supported(const PlanConsts& pc) {
     return G == 8 || G == 65;
 }
 hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides) {
+                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides,
+                               const fpe_plan_state* d_stateIn, fpe_plan_state* d_stateOut) {
     const size_t lds = plan_lds_bytes(pc);
     const int G = plan_group_size(pc);
-    if (d_strides) {
+    if (d_stateIn || d_stateOut) {  // the resume forms (fpe_plan_resume*), at the group sizes of the stride forms
+        if (G == 65)
+            hipLaunchKernelGGL(plan_sequential_resume_kernel, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides, d_stateIn,
+                               d_stateOut);
+        else if (G == 8)
+            hipLaunchKernelGGL((plan_chained_kernel<8, false, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>), dim3((B + 1) / 2), dim3(64), lds,
+                               stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides, d_stateIn, d_stateOut);
+        else
+            return hipErrorNotSupported;
+    } else if (d_strides) {
         if (G == 65)
             hipLaunchKernelGGL(plan_sequential_stride_kernel, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides);
         else if (G == 8)
@@ -2089,6 +2192,8 @@ hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
         {reinterpret_cast<const void*>(plan_sequential_kernel), planBytes},
         {reinterpret_cast<const void*>(plan_chained_kernel<8, false, const fpe_stride*>), planBytes},
         {reinterpret_cast<const void*>(plan_sequential_stride_kernel), planBytes},
+        {reinterpret_cast<const void*>(plan_chained_kernel<8, false, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>), planBytes},
+        {reinterpret_cast<const void*>(plan_sequential_resume_kernel), planBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<8>), searchBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<8, true>), searchBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<64>), searchBytes},

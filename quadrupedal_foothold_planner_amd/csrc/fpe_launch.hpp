@@ -12,8 +12,11 @@ namespace fpe {
 // ---- direct kernels (fpe_kernels.hip) ------------------------------------------------------------------------
 // d_strides (here and in launch_plan_bits / launch_rank): one fpe_stride per pose, the stride form of the call (fpe_plan_strides*,
 // fpe_plan_rank_strides*) — the kernels' stride instantiations; null: the kernels as they were
+// d_stateIn / d_stateOut (launch_plan_chained, launch_plan_bits): one fpe_plan_state per pose, the resume form of the call
+// (fpe_plan_resume*) — with either one the kernels' resume instantiations, which take a null d_strides as the plan's own stride
 hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr);
+                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr,
+                               const fpe_plan_state* d_stateIn = nullptr, fpe_plan_state* d_stateOut = nullptr);
 bool plan_chained_strides_supported(const PlanConsts& pc);  // the direct stride kernels exist at the automatic group sizes only
 hipError_t launch_search_legs(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_leg_query* d_q,
                               int n, fpe_foothold* d_out, hipStream_t stream);
@@ -31,10 +34,11 @@ size_t bitmap_words(int rows, int cols, int* strideW, int* nw);
 hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float thrDefault, float thrCandidate,
                                uint32_t* d_words, hipStream_t stream);
 bool bits_supported(const PlanConsts& pc, const MapGeom& g);
-void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, bool strides = false);
+void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, int form = 0);  // 0 plain, 1 stride, 2 resume
 hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut,
                             const fpe_pose* d_poses, int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream,
-                            const fpe_stride* d_strides = nullptr);
+                            const fpe_stride* d_strides = nullptr, const fpe_plan_state* d_stateIn = nullptr,
+                            fpe_plan_state* d_stateOut = nullptr);
 
 // ---- producer filters (fpe_filters.hpp) ----------------------------------------------------------------------
 bool filters_supported(const FilterConsts& fc, const MapGeom& g);

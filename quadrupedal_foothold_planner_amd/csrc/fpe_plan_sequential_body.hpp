@@ -1,10 +1,16 @@
 // fpe_plan_sequential_body.hpp — the text of plan_sequential_kernel, a piece of the kernel translation unit (inside namespace fpe,
 // not stand-alone) that fpe_kernels.hip includes TWICE: FPE_SEQUENTIAL_STRIDE 0 defines plan_sequential_kernel exactly as it always
 // was, 1 defines plan_sequential_stride_kernel (fpe_plan_strides*) — the same kernel with `strides` as its one trailing argument and
-// the step and the drift of the pose read from strides[b].  A kernel that is no template cannot take the flag as a parameter, and
+// the step and the drift of the pose read from strides[b]; 2 defines plan_sequential_resume_kernel (fpe_plan_resume*) — strides (null:
+// the plan's own), state_in (null: the stance prologue) and state_out (null: not returned) behind the list.  A kernel that is no template cannot take the flag as a parameter, and
 // a shared inlined body changed the register allocation of the existing kernel; the same text compiled twice does not.
 // (no include guard)
-#if FPE_SEQUENTIAL_STRIDE
+#if FPE_SEQUENTIAL_STRIDE == 2
+__global__ __launch_bounds__(64, 4) void plan_sequential_resume_kernel(DevMap m, PlanConsts pc, SpiralLut lut,
+                                                                       const fpe_pose* __restrict__ poses, int B, int nCycles,
+                                                                       fpe_plan_out out, const fpe_stride* __restrict__ strides,
+                                                                       const fpe_plan_state* stateIn, fpe_plan_state* stateOut) {
+#elif FPE_SEQUENTIAL_STRIDE
 __global__ __launch_bounds__(64, 4) void plan_sequential_stride_kernel(DevMap m, PlanConsts pc, SpiralLut lut,
                                                                        const fpe_pose* __restrict__ poses, int B, int nCycles,
                                                                        fpe_plan_out out, const fpe_stride* __restrict__ strides) {
@@ -26,7 +32,10 @@ __global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanCo
     const fpe_pose* pp = poses + b;
     const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
     const int gait = pp->gait;
-#if FPE_SEQUENTIAL_STRIDE
+#if FPE_SEQUENTIAL_STRIDE == 2
+    constexpr bool kStride = true;
+    const StrideVals sv = load_stride_or_plan(strides, b, pc);
+#elif FPE_SEQUENTIAL_STRIDE
     constexpr bool kStride = true;
     const StrideVals sv = load_stride(strides, b);
 #else
@@ -39,8 +48,29 @@ __global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanCo
         sh.footDb[k] = pc.footDb[k];
         sh.footOff[k] = static_cast<int16_t>(pc.footDa[k] * pc.tileW + pc.footDb[k]);
     }
+    double adjY = 0.0;  // ajustedPose_[1], cpp:759
+#if FPE_SEQUENTIAL_STRIDE == 2
+    int cycBase = 0;  // gait_cycle_id of the call's first cycle
+    const bool started = stateIn == nullptr;
+    if (!started) {  // (uniform) the committed feet, the running drift and the cycle index of an earlier call instead of the stance
+        const LegState st = load_leg_state(stateIn, b, tid & 3);  // lane = leg (every lane loads: the verdict is a ballot)
+        const bool poseFinite = __ballot(!st.finite) == 0ull;
+        adjY = st.adjY;
+        cycBase = st.cycle;
+        if (tid < 4) {
+            for (int t = 0; t < 3; ++t) {
+                sh.cur[t][tid][0] = poseFinite ? st.x[t] : __builtin_nan("");
+                sh.cur[t][tid][1] = st.y[t];
+                sh.cur[t][tid][2] = 0.0;
+            }
+        }
+    }
+#else
+    constexpr int cycBase = 0;
+    constexpr bool started = true;
+#endif
     // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699): lane = leg
-    if (tid < 4) {
+    if (started && tid < 4) {
         const int leg = tid;
         double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
         double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
@@ -61,9 +91,8 @@ __global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanCo
         }
     }
     pose_sync<16>();
-    if (out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
+    if (started && out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
 
-    double adjY = 0.0;  // ajustedPose_[1], cpp:759
     const int nPhases = (gait == 1) ? 4 : 1;
     const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
     const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
@@ -81,7 +110,7 @@ __global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanCo
             for (int leg = 0; leg < 4; ++leg) {
                 if (!((mask >> leg) & 1u)) continue;
                 const LegStatic ls = make_leg_static(pc, pp, leg, m.g.res, lut);
-                leg_phase<G>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out);
+                leg_phase<G>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out, nullptr, cycBase);
             }
             pose_sync<16>();
             // footholdValidation_ = AND of the swing legs' flags (cpp:1323); commit or skip (cpp:1332-1576)
@@ -99,5 +128,8 @@ __global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanCo
         if (tid == 0 && out.cycle_ok) out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
         adjY += kStride ? sv.drift : pc.drift;  // cpp:1578
     }
+#if FPE_SEQUENTIAL_STRIDE == 2
+    if (stateOut && tid < 4) store_leg_state(stateOut, b, tid, sh.cur, adjY, cycBase + nCycles);  // (behind the last commit's pose_sync)
+#endif
 }
 

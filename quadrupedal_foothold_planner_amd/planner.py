@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (CENTROID_DTYPE, CENTROID_QUERY_DTYPE, FOOTHOLD_DTYPE, GLOBAL_FOOTHOLDS_DTYPE, OPT_CYCLE_DTYPE, OPT_FOOTHOLD_DTYPE, OPT_PARAMS_DTYPE,
-                    PACKED_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, STRIDE_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
+                    PACKED_DTYPE, PLAN_STATE_DTYPE, POSE_DTYPE, PARAMS_DTYPE, QUERY_DTYPE, SELECTED_DTYPE, STRIDE_DTYPE, TRACK_REPORT_DTYPE, EngineUnavailable,
                     CentroidMapOut, FootholdMapOut, FootholdSnapOut, MapDesc, OptOut, PlanOut, RankOut, ptr)
 
 # products of a chained plan in the order of fpe_plan_out's fields (= the order of the engine's device arena)
@@ -67,6 +67,37 @@ def _strides_for(strides, B):
     if strides.shape != (B,):
         raise ValueError(f"strides must hold one element per pose: shape {strides.shape}, {B} poses")
     return strides
+
+
+def make_plan_states(params, poses=None, strides=None, feet=None, adjusted_y=0.0, cycle=0):
+    """Build an fpe_plan_state array (plan_resume(states=...)).  From `poses` (and optional per-pose `strides`): what a plan of
+    those poses starts from (fpe_plan_state_from_pose).  From `feet` ([B, 4, 2]: x / y of RF, RH, LH, LF — e.g. the request's four
+    *_current_foothold points): all three tracks stand on them, with the given running drift and cycle index, scalars broadcast
+    (fpe_plan_state_from_feet).  Pure host arithmetic: no engine, no GPU."""
+    L = _capi.lib()
+    if (poses is None) == (feet is None):
+        raise ValueError("give either poses or feet")
+    if feet is not None:
+        feet = np.ascontiguousarray(feet, dtype=np.float64).reshape(-1, 4, 2)
+        B = feet.shape[0]
+        adj, cyc = np.broadcast_to(np.asarray(adjusted_y, np.float64), (B,)), np.broadcast_to(np.asarray(cycle, np.int32), (B,))
+        states = np.zeros(B, dtype=PLAN_STATE_DTYPE)
+        for b in range(B):
+            rc = L.fpe_plan_state_from_feet(ptr(feet[b]), float(adj[b]), int(cyc[b]), ptr(states[b:b + 1]))
+            if rc != _capi.FPE_OK:
+                raise FpeError(rc, "fpe_plan_state_from_feet: non-finite value or cycle outside [0, 254]")
+        return states
+    params = np.ascontiguousarray(params, dtype=PARAMS_DTYPE).reshape(1)
+    poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+    B = poses.shape[0]
+    strides = _strides_for(strides, B) if strides is not None else None
+    states = np.zeros(B, dtype=PLAN_STATE_DTYPE)
+    for b in range(B):
+        rc = L.fpe_plan_state_from_pose(ptr(params), ptr(poses[b:b + 1]), ptr(strides[b:b + 1]) if strides is not None else None,
+                                        ptr(states[b:b + 1]))
+        if rc != _capi.FPE_OK:
+            raise FpeError(rc, "fpe_plan_state_from_pose: non-finite pose or stride")
+    return states
 
 
 # fpe_set_tuning's knobs whose engine default is not 0 (tuning() restores these after a with-block)
@@ -190,11 +221,12 @@ class FootholdPlanner(_Handle):
     def set_max_leg_search_radius(self, r):
         self._check(self._lib.fpe_set_max_leg_search_radius(self._h, np.float32(r)))
 
-    def describe_plan(self, strides=False):
+    def describe_plan(self, strides=False, resume=False):
         """Name and shape of the kernel a chained plan launches with the current parameters and map; strides=True: the kernel
-        a plan with per-pose strides launches (fpe_describe_plan_strides)."""
+        a plan with per-pose strides launches (fpe_describe_plan_strides); resume=True: the kernel a plan_resume call launches
+        (fpe_describe_plan_resume)."""
         buf = C.create_string_buffer(256)
-        describe = self._lib.fpe_describe_plan_strides if strides else self._lib.fpe_describe_plan
+        describe = self._lib.fpe_describe_plan_resume if resume else (self._lib.fpe_describe_plan_strides if strides else self._lib.fpe_describe_plan)
         self._check(describe(self._h, ptr(self.params), buf, 256))
         return buf.value.decode()
 
@@ -277,6 +309,46 @@ class FootholdPlanner(_Handle):
             self._check(self._lib.fpe_plan_strides(self._h, ptr(self.params), ptr(poses), ptr(_strides_for(strides, B)), B, int(n_cycles),
                                                    C.byref(po)))
         return out
+
+    # ---- resumable plans (build-defined: fpe_plan_resume*) ------------------------------------------------
+    RESUME_PRODUCTS = ("nominal", "centroid", "default", "cycle_ok", "selected")  # what a continuation can return by default
+
+    def plan_resume(self, poses, n_cycles, states=None, strides=None, products=None, want_state=True):
+        """fpe_plan_resume with host buffers: plan `n_cycles` more cycles of every pose from `states` (an fpe_plan_state array, one
+        element per pose: make_plan_states, or the states an earlier call returned; None: start from the poses as plan() does) and
+        return (products, states) — the state behind the last cycle, to resume from again (None with want_state=False).  Records
+        are indexed by the call's own cycle count and carry gait_cycle_id = state.cycle + g.  A resumed call has no stance and no
+        pose_status; `products` defaults to plan()'s set without them (with them when states is None)."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        B = poses.shape[0]
+        if products is None:
+            products = DEFAULT_PRODUCTS if states is None else self.RESUME_PRODUCTS
+        unknown = set(products) - set(PRODUCT_ORDER)
+        if unknown:
+            raise ValueError(f"unknown plan products {sorted(unknown)}")
+        if states is not None:
+            states = np.ascontiguousarray(states, dtype=PLAN_STATE_DTYPE)
+            if states.shape != (B,):
+                raise ValueError(f"states must hold one element per pose: shape {states.shape}, {B} poses")
+        shapes = product_shapes(B, n_cycles)
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in PRODUCT_ORDER if k in products}
+        po = PlanOut()
+        for k in out:
+            setattr(po, PRODUCT_FIELDS[k], ptr(out[k]))
+        state_out = np.zeros(B, dtype=PLAN_STATE_DTYPE) if want_state else None
+        self._check(self._lib.fpe_plan_resume(self._h, ptr(self.params), ptr(poses), ptr(_strides_for(strides, B)) if strides is not None else None,
+                                              ptr(states), B, int(n_cycles), C.byref(po), ptr(state_out)))
+        return out, state_out
+
+    def plan_resume_device(self, d_poses_ptr, B, n_cycles, d_out, d_state_in_ptr=0, d_state_out_ptr=0, d_strides_ptr=0, stream=0):
+        """fpe_plan_resume_device: `d_out` maps product names to device pointers; the state pointers are device arrays of B
+        fpe_plan_state elements (0: none; the two may be the same array).  Asynchronous on `stream`."""
+        po = PlanOut()
+        for k, p in d_out.items():
+            setattr(po, PRODUCT_FIELDS[k], C.c_void_p(p) if p else None)
+        self._check(self._lib.fpe_plan_resume_device(self._h, ptr(self.params), C.c_void_p(d_poses_ptr), C.c_void_p(d_strides_ptr or 0) if d_strides_ptr else None,
+                                                     C.c_void_p(d_state_in_ptr) if d_state_in_ptr else None, int(B), int(n_cycles), C.byref(po),
+                                                     C.c_void_p(d_state_out_ptr) if d_state_out_ptr else None, C.c_void_p(stream or 0)))
 
     # ---- chained plan, device-resident (torch tensors / raw pointers) ----------------------------------
     def plan_device(self, d_poses_ptr, B, n_cycles, d_nominal_ptr=0, d_centroid_ptr=0, d_default_ptr=0,
