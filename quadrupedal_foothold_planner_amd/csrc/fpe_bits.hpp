@@ -83,6 +83,7 @@ hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float th
 
 // Kernel shape for a window half-width: 8 lanes per leg with 2-4 rows per lane (windows of up to 32 rows / columns);
 // one wavefront per pose with 64-bit rows (up to 64 rows) or 96-bit rows (up to 96 columns, 2 rows per lane).
+// (Which instantiation a call launches, and the launch itself: select_plan_kernel / launch_plan, fpe_plan_launch.hpp.)
 struct BitsShape {
     int lanes;  // 8 or 64; 0 = no instantiation fits
     int nrl, kw;
@@ -113,180 +114,4 @@ bool bits_supported(const PlanConsts& pc, const MapGeom& g) {
     const double side = 2.0 * ceil(pc.rf / g.res) + 2.0;
     if (sp.lanes == 64) return side * side <= kBitsMaxBoxCells;  // 64-lane kernels: membership in two rounds of 64 cells (SeqRec::visA / visB)
     return side * side <= legbits_words(8 * sp.nrl, 1, pc.nHW);
-}
-
-// Which kernel a chained plan with these constants launches (evidence for bench.py / profiles).
-// form 1: the kernel a stride call (fpe_plan_strides*) launches — "<kernel> stride (...)"; form 2: the one a resume call
-// (fpe_plan_resume* with either state) launches — "<kernel> resume (...)"; the 3x3-only variants have neither form.
-void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, int form) {
-    if (form != 0) {
-        const char* what = form == 2 ? "resume" : "stride";
-        if (bits_supported(pc, g)) {
-            const BitsShape sp = bits_shape(pc.winH);
-            if (sp.lanes == 8)
-                snprintf(buf, n, "plan_bits_kernel<%d, false> %s (8 lanes per leg, %d x %d bit window)", sp.nrl, what, 2 * pc.winH + 1, 2 * pc.winH + 1);
-            else
-                snprintf(buf, n, "plan_bits_seq_kernel<%d, %d> %s (one wavefront per pose, %d x %d bit window, %d-bit rows)", sp.nrl, sp.kw, what,
-                         2 * pc.winH + 1, 2 * pc.winH + 1, 32 * sp.kw);
-            return;
-        }
-        const int G = plan_group_size(pc);
-        if (G == 65) snprintf(buf, n, "plan_sequential_kernel %s (direct, one wavefront per pose)", what);
-        else if (G == 8) snprintf(buf, n, "plan_chained_kernel<8, false> %s (direct)", what);
-        else snprintf(buf, n, "no %s kernel for plan_group %d", what, G);
-        return;
-    }
-    if (bits_supported(pc, g)) {
-        const BitsShape sp = bits_shape(pc.winH);
-        const bool mid = mid_variant(pc, g.res) && pc.nFoot == 1;
-        if (sp.lanes == 8)
-            snprintf(buf, n, "plan_bits_kernel<%d, %s> (8 lanes per leg, %d x %d bit window%s)", sp.nrl, mid ? "true" : "false",
-                     2 * pc.winH + 1, 2 * pc.winH + 1, mid ? ", 3x3-only fast path" : "");
-        else
-            snprintf(buf, n, "plan_bits_seq_kernel<%d, %d> (one wavefront per pose, %d x %d bit window, %d-bit rows)", sp.nrl, sp.kw,
-                     2 * pc.winH + 1, 2 * pc.winH + 1, 32 * sp.kw);
-        return;
-    }
-    const int G = plan_group_size(pc);
-    if (G == 65) snprintf(buf, n, "plan_sequential_kernel (direct, one wavefront per pose)");
-    else snprintf(buf, n, "plan_chained_kernel<%d, %s> (direct)", G, (G == 8 && mid_variant(pc, g.res)) ? "true" : "false");
-}
-
-// the plan constants as plan_bits_kernel<NRL, kMid, kProd> takes them: the 3x3-only kernels' own block, filled from this call's constants
-template <bool kMid>
-static auto bits_kernel_consts(const PlanConsts& pc) {
-    if constexpr (kMid) return plan_mid_consts(pc);
-    else return pc;
-}
-
-// The stride form of launch_plan_bits (fpe_plan_strides*): the same shapes, grids and LDS; one instantiation per family member —
-// the any-combination product mask (kProd 0), the generic 8-lane variants, and the group sizes the launch below can reach.
-// With either state (fpe_plan_resume*): the resume instantiations, {strides, state_in, state_out} as the trailing arguments, each of
-// which may be null.
-static hipError_t launch_plan_bits_strides(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                                           int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides,
-                                           const fpe_plan_state* d_stateIn, fpe_plan_state* d_stateOut) {
-    const BitsShape sp = bits_shape(pc.winH);
-    const dim3 block(64);
-    const bool resume = d_stateIn != nullptr || d_stateOut != nullptr;
-#define FPE_LAUNCH_BITS_STRIDE(NRL)                                                                                                   \
-    do {                                                                                                                              \
-        const size_t ldsB = 2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW) + (sizeof(YEntry) + sizeof(UnitG)) * 16); \
-        if (resume)                                                                                                                   \
-            hipLaunchKernelGGL((plan_bits_resume_kernel<NRL, 0>), dim3((B + 1) / 2), block, ldsB, stream, d_poses, B, nCycles, m, bm, pc, lut, \
-                               d_out, d_strides, d_stateIn, d_stateOut);                                                              \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((plan_bits_stride_kernel<NRL, 0>), dim3((B + 1) / 2), block, ldsB, stream, d_poses, B, nCycles, m, bm, pc, lut, \
-                               d_out, d_strides);                                                                                     \
-    } while (0)
-#define FPE_SEQ_RESUME_KERNEL(NRL, KW, GRP) plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>
-#define FPE_LAUNCH_BITS_SEQ_STRIDE_G(NRL, KW, GRP, GRID, LDS, SLOT)                                                                     \
-    do {                                                                                                                              \
-        if ((LDS) > 64 * 1024) {                                                                                                      \
-            const hipError_t ea = hipFuncSetAttribute(resume ? reinterpret_cast<const void*>(FPE_SEQ_RESUME_KERNEL(NRL, KW, GRP))     \
-                                                             : reinterpret_cast<const void*>(plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>),   \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(LDS));             \
-            if (ea != hipSuccess) return ea;                                                                                          \
-        }                                                                                                                             \
-        if (resume)                                                                                                                   \
-            hipLaunchKernelGGL((FPE_SEQ_RESUME_KERNEL(NRL, KW, GRP)), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B, \
-                               nCycles, d_out, recSlots, static_cast<int>(SLOT), d_strides, d_stateIn, d_stateOut);                   \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((plan_bits_seq_kernel<NRL, KW, 0, GRP, const fpe_stride*>), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B, \
-                               nCycles, d_out, recSlots, static_cast<int>(SLOT), d_strides);                                          \
-    } while (0)
-    if (sp.lanes == 8) {
-        if (sp.nrl == 2) FPE_LAUNCH_BITS_STRIDE(2);
-        else if (sp.nrl == 3) FPE_LAUNCH_BITS_STRIDE(3);
-        else FPE_LAUNCH_BITS_STRIDE(4);
-    } else if (sp.lanes == 64) {
-        // (slot size, staged cycles and the sixteen-pose workgroups exactly as launch_plan_bits has them)
-        const int nrl = sp.nrl, kw = sp.kw;
-        const size_t base = (sizeof(PoseShared) + ((4 * sizeof(LegStatic) + 15) & ~static_cast<size_t>(15)) +
-                             4 * legbits_words(2 * pc.winH + 1 < 64 * nrl ? 2 * pc.winH + 1 : 64 * nrl, kw, pc.nHW) + 15) &
-                            ~static_cast<size_t>(15);
-        int recSlots = 8;
-        while (recSlots > 1 && base + recSlots * 4 * sizeof(SeqRec) > 10240) recSlots >>= 1;
-        const size_t slot = (base + recSlots * 4 * sizeof(SeqRec) + 15) & ~static_cast<size_t>(15);
-        if (kw == 2) FPE_LAUNCH_BITS_SEQ_STRIDE_G(1, 2, 1, B, slot, slot);
-        else if (B >= 64 && 16 * slot <= 160 * 1024) FPE_LAUNCH_BITS_SEQ_STRIDE_G(2, 3, 16, (B + 15) / 16, 16 * slot, slot);
-        else FPE_LAUNCH_BITS_SEQ_STRIDE_G(2, 3, 1, B, slot, slot);
-    } else {
-        return hipErrorInvalidValue;
-    }
-#undef FPE_LAUNCH_BITS_STRIDE
-#undef FPE_LAUNCH_BITS_SEQ_STRIDE_G
-#undef FPE_SEQ_RESUME_KERNEL
-    return hipGetLastError();
-}
-
-hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                            int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides,
-                            const fpe_plan_state* d_stateIn, fpe_plan_state* d_stateOut) {
-    if (d_strides || d_stateIn || d_stateOut)
-        return launch_plan_bits_strides(m, bm, pc, lut, d_poses, B, nCycles, d_out, stream, d_strides, d_stateIn, d_stateOut);
-    const BitsShape sp = bits_shape(pc.winH);
-    const bool mid = mid_variant(pc, m.g.res) && pc.nFoot == 1;  // rf < res: the candidate disc is the candidate's own cell
-    const dim3 block(64);
-    const int prod = product_shape(d_out);
-#define FPE_LAUNCH_BITS_P(NRL, MID, PROD)                                                                                    \
-    hipLaunchKernelGGL((plan_bits_kernel<NRL, MID, PROD>), dim3((B + 1) / 2), block,                                        \
-                       2 * (sizeof(PoseShared) + 16 * legbits_words(8 * NRL, 1, pc.nHW) +                                      \
-                            (MID ? (sizeof(YEntry) + sizeof(Unit)) * 32 : (sizeof(YEntry) + sizeof(UnitG)) * 16)), stream, d_poses, B,  \
-                       nCycles, m, bm, bits_kernel_consts<MID>(pc), lut, d_out)
-#define FPE_LAUNCH_BITS(NRL, MID)                                  \
-    do {                                                           \
-        if (prod == 2) FPE_LAUNCH_BITS_P(NRL, MID, 2);             \
-        else if (prod == 1) FPE_LAUNCH_BITS_P(NRL, MID, 1);        \
-        else FPE_LAUNCH_BITS_P(NRL, MID, 0);                       \
-    } while (0)
-#define FPE_LAUNCH_BITS_SEQ_G(NRL, KW, GRP, GRID, LDS, SLOT)                                                                                      \
-    do {                                                                                                                                        \
-        if ((LDS) > 64 * 1024) {                                                                                                                \
-            const hipError_t ea = hipFuncSetAttribute(prod == 1 ? reinterpret_cast<const void*>(plan_bits_seq_kernel<NRL, KW, 1, GRP>)          \
-                                                                : reinterpret_cast<const void*>(plan_bits_seq_kernel<NRL, KW, 0, GRP>),        \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(LDS));                       \
-            if (ea != hipSuccess) return ea;                                                                                                    \
-        }                                                                                                                                       \
-        if (prod == 1)                                                                                                                          \
-            hipLaunchKernelGGL((plan_bits_seq_kernel<NRL, KW, 1, GRP>), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B,    \
-                               nCycles, d_out, recSlots, static_cast<int>(SLOT));                                                              \
-        else                                                                                                                                    \
-            hipLaunchKernelGGL((plan_bits_seq_kernel<NRL, KW, 0, GRP>), dim3(GRID), dim3(64 * GRP), LDS, stream, m, bm, pc, lut, d_poses, B,    \
-                               nCycles, d_out, recSlots, static_cast<int>(SLOT));                                                              \
-    } while (0)
-#define FPE_LAUNCH_BITS_SEQ(NRL, KW)                                                                                         \
-    do {                                                                                                                     \
-        const size_t base = (sizeof(PoseShared) + ((4 * sizeof(LegStatic) + 15) & ~static_cast<size_t>(15)) +                            \
-                             4 * legbits_words(2 * pc.winH + 1 < 64 * NRL ? 2 * pc.winH + 1 : 64 * NRL, KW, pc.nHW) + 15) &        \
-                            ~static_cast<size_t>(15);                                                                                 \
-        int recSlots = 8; /* cycles of staged records: as many as keep sixteen poses per CU (10 KiB each) */                       \
-        while (recSlots > 1 && base + recSlots * 4 * sizeof(SeqRec) > 10240) recSlots >>= 1;                                   \
-        const size_t slot = (base + recSlots * 4 * sizeof(SeqRec) + 15) & ~static_cast<size_t>(15);                            \
-        /* (the all-seven shape takes the generic instantiation here: compiled on its own it spills more — cfg-5 +2 %, cfg-3 0) */     \
-        /* sixteen poses per workgroup — one workgroup per CU — where it was measured to pay: the 96-bit-row windows (cfg-5 -2 %; the    \
-           64-bit-row kernel of cfg-3 +2 %), batches that fill at least four CUs, slots that fit sixteen times into the LDS */            \
-        if (KW >= 3 && B >= 64 && 16 * slot <= 160 * 1024)                                                            \
-            FPE_LAUNCH_BITS_SEQ_G(NRL, KW, 16, (B + 15) / 16, 16 * slot, slot);                                                          \
-        else                                                                                                                             \
-            FPE_LAUNCH_BITS_SEQ_G(NRL, KW, 1, B, slot, slot);                                                                            \
-    } while (0)
-    if (sp.lanes == 8) {
-        if (sp.nrl == 2 && mid) FPE_LAUNCH_BITS(2, true);
-        else if (sp.nrl == 2) FPE_LAUNCH_BITS(2, false);
-        else if (sp.nrl == 3 && mid) FPE_LAUNCH_BITS(3, true);
-        else if (sp.nrl == 3) FPE_LAUNCH_BITS(3, false);
-        else if (sp.nrl == 4 && mid) FPE_LAUNCH_BITS(4, true);
-        else FPE_LAUNCH_BITS(4, false);
-    } else if (sp.lanes == 64) {
-        if (sp.kw == 2) FPE_LAUNCH_BITS_SEQ(1, 2);
-        else FPE_LAUNCH_BITS_SEQ(2, 3);
-    } else {
-        return hipErrorInvalidValue;
-    }
-#undef FPE_LAUNCH_BITS
-#undef FPE_LAUNCH_BITS_P
-#undef FPE_LAUNCH_BITS_SEQ
-#undef FPE_LAUNCH_BITS_SEQ_G
-    return hipGetLastError();
 }

@@ -731,7 +731,7 @@ __device__ __forceinline__ const MidKernArgs* mid_cold_args() {
 // they call: disc_issue / disc_pass_direct without the threshold check, default_ok_bits, unit_put_disc, centroid_begin_bits
 // with a one-cell disc), which the generic kernels share.  Those read rf, rf2, h, winH, cornerEps, nFoot and midCellInside.
 // Everything else stays ZERO and must not be read on this path:
-//   footReach            0 is also its value for the one-cell disc these kernels are launched for (launch_plan_bits: nFoot == 1,
+//   footReach            0 is also its value for the one-cell disc these kernels are launched for (select_plan_kernel: nFoot == 1,
 //                        offset (0, 0)); read by spiral_bits under G == 64 or KW > 1 only
 //   nHW, hwList, hwIdx, footDa, footDb   the erosion is compiled out (kOneCellFoot); the offset table is PoseShared's
 //   thrDefault, thrCandidate, footRobust, tile*   direct kernels only (every call here has kCheck == false)
@@ -858,7 +858,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
     // [min{i : x_i < xhi}, max{i : x_i >= xlo}] (rectangle_index_bounds) and cell centres x_i are non-increasing in i, so row i
     // is one of them iff xlo <= x_i < xhi: the lane tests ITS row's centre, nobody derives the interval's ends (a floor, a
     // clamp and a conversion per end, four corrected estimates over a ballot: fifty instructions a cycle).
-    // (one-cell foot disc: what these kernels are launched for, launch_plan_bits)
+    // (one-cell foot disc: what these kernels are launched for, select_plan_kernel)
     bool fastSpiral;  // uniform
     if constexpr (kPlain) fastSpiral = lk.nRings >= 4 && lk.nCand >= 16;  // (the plan's defNRings / defNCand: a scalar test)
     else fastSpiral = __ballot(ls.polyKind != 0 || lk.nRings < 4 || lk.nCand < 16) == 0ull;

@@ -553,7 +553,7 @@ __device__ __forceinline__ void erode_h(unsigned (&A)[KW], int d) {
 }
 
 // checkCandidateFoothold (cpp:2085-2114) on the window's bit rows: first valid cell in SpiralIterator order.
-// kOneCellFoot: the caller is a 3x3-only kernel, launched for one-cell foot discs only (launch_plan_bits): the erosion
+// kOneCellFoot: the caller is a 3x3-only kernel, launched for one-cell foot discs only (select_plan_kernel): the erosion
 // is compiled out (its code and live scalars cost the chain of those kernels 1 us of register allocation otherwise).
 template <int G, int NRL, int KW, bool kOneCellFoot = false>
 __device__ bool spiral_bits(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const LutHead& head, const LegCtx& c,

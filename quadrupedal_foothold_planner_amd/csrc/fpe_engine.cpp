@@ -1285,7 +1285,7 @@ int fpe_set_tuning(fpe_handle h, const char* key, int32_t value) {
     return FPE_OK;
 }
 
-static int describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n, int form) {
+static int describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n, fpe::PlanForm form) {
     if (!h || !params || !buf || n <= 0) return fail(FPE_E_INVALID_ARG, "null argument");
     std::shared_ptr<MapSnapshot> snap;
     fpe::Tuning tuning;
@@ -1299,12 +1299,13 @@ static int describe_plan(fpe_handle h, const fpe_params* params, char* buf, int3
     if (!snap) return fail(FPE_E_NO_MAP, "no map uploaded");
     fpe::PlanConsts pc;
     fpe::derive_constants(*params, snap->g, maxRadius, tuning, pc);
-    fpe::describe_plan_kernel(pc, snap->g, buf, static_cast<size_t>(n), form);
+    // (the family-level part of the selection: no batch, no products)
+    fpe::describe_plan_kernel(fpe::select_plan_kernel(pc, snap->g, fpe::bits_supported(pc, snap->g), 0, 0, form), buf, static_cast<size_t>(n));
     return FPE_OK;
 }
-int fpe_describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, 0); }
-int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, 1); }
-int fpe_describe_plan_resume(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, 2); }
+int fpe_describe_plan(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, fpe::PlanForm::Plain); }
+int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, fpe::PlanForm::Stride); }
+int fpe_describe_plan_resume(fpe_handle h, const fpe_params* params, char* buf, int32_t n) { return describe_plan(h, params, buf, n, fpe::PlanForm::Resume); }
 
 int fpe_set_max_leg_search_radius(fpe_handle h, float radius) {
     if (!h || !(radius >= 0.0f) || !std::isfinite(radius)) return fail(FPE_E_INVALID_ARG, "bad radius");
@@ -1490,12 +1491,12 @@ int fpe_map_info(fpe_handle h, fpe_map_desc* out) {
 }
 
 // One chained-plan launch on `stream`: the bit-window kernels when the snapshot's bit planes apply, else the direct ones.
-// d_strides (null: none): the stride form, fpe_plan_strides* / fpe_plan_rank_strides*.  states (either one of fpe_plan_resume*'s
-// given): the resume form, which exists where the stride form does.
-static int check_strides_launchable(const CallPlan& cp, const fpe_stride* d_strides, bool states = false) {
-    if ((d_strides || states) && !cp.useBits && !fpe::plan_chained_strides_supported(cp.pc))
-        return fail(FPE_E_UNSUPPORTED, states ? "resumable plans: no resume kernel for a forced plan_group of 4, 16 or 64"
-                                              : "per-pose strides: no stride kernel for a forced plan_group of 4, 16 or 64");
+// chain: the optional arrays of fpe_plan_strides* / fpe_plan_rank_strides* (the stride form) and fpe_plan_resume* (the resume form,
+// which exists where the stride form does).
+static int check_strides_launchable(const CallPlan& cp, fpe::PlanForm form) {
+    if (form != fpe::PlanForm::Plain && fpe::select_plan_kernel(cp.pc, cp.snap->g, cp.useBits, 0, 0, form).family == fpe::PlanFamily::None)
+        return fail(FPE_E_UNSUPPORTED, form == fpe::PlanForm::Resume ? "resumable plans: no resume kernel for a forced plan_group of 4, 16 or 64"
+                                                                    : "per-pose strides: no stride kernel for a forced plan_group of 4, 16 or 64");
     return FPE_OK;
 }
 // stance and pose_status are products of a start, not of a continuation (include/fpe.h)
@@ -1505,17 +1506,12 @@ static int check_resumed_products(const fpe_plan_state* stateIn, const fpe_plan_
     return FPE_OK;
 }
 static int launch_plan(fpe_engine* h, const CallPlan& cp, const fpe_pose* d_poses, int32_t B, int32_t n_cycles,
-                       const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr,
-                       const fpe_plan_state* d_stateIn = nullptr, fpe_plan_state* d_stateOut = nullptr) {
+                       const fpe_plan_out& d_out, hipStream_t stream, const fpe::PlanChain& chain = {}) {
     int rc = check_packed_fits(cp, d_out.selected_packed != nullptr);
     if (rc != FPE_OK) return rc;
-    rc = check_strides_launchable(cp, d_strides, d_stateIn || d_stateOut);
+    rc = check_strides_launchable(cp, chain.form());
     if (rc != FPE_OK) return rc;
-    if (cp.useBits)
-        FPE_HIP(fpe::launch_plan_bits(dev_map(*cp.snap), cp.bits, cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides, d_stateIn,
-                                      d_stateOut));
-    else
-        FPE_HIP(fpe::launch_plan_chained(dev_map(*cp.snap), cp.pc, h->lut(), d_poses, B, n_cycles, d_out, stream, d_strides, d_stateIn, d_stateOut));
+    FPE_HIP(fpe::launch_plan(dev_map(*cp.snap), cp.useBits ? &cp.bits : nullptr, cp.pc, h->lut(), d_poses, B, n_cycles, d_out, chain, stream));
     return FPE_OK;
 }
 
@@ -1540,12 +1536,13 @@ int fpe_plan_resume_device(fpe_handle h, const fpe_params* params, const fpe_pos
     CallPlan cp;
     rc = prepare_call(h, params, 0.0f, cp, st, true);
     if (rc != FPE_OK) return rc;
-    rc = check_strides_launchable(cp, d_strides, d_state_in || d_state_out);  // (a refusal queues nothing: ahead of the async mark)
+    const fpe::PlanChain chain{d_strides, d_state_in, d_state_out};
+    rc = check_strides_launchable(cp, chain.form());  // (a refusal queues nothing: ahead of the async mark)
     if (rc != FPE_OK) return rc;
     rc = check_packed_fits(cp, d_out->selected_packed != nullptr);
     if (rc != FPE_OK) return rc;
     mark_async_launch(cp);
-    return launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st, d_strides, d_state_in, d_state_out);
+    return launch_plan(h, cp, d_poses, B, n_cycles, *d_out, st, chain);
 }
 
 namespace {
@@ -1751,7 +1748,7 @@ int plan_launches(fpe_engine* h, const CallPlan& cp, CallCtx& cx, const PlanLayo
         for (int k = 0; k < kPlanProducts; ++k) slots(d)[k] = L.len[k] ? dp + L.off[k] : nullptr;
         // every (pose, cycle, leg) record is written by the kernel (trot: all legs each cycle; walk: each
         // leg in its phase), so the buffers need no clearing
-        const int rc = launch_plan(h, cp, r.dPoses, B, n_cycles, d, cx.stream, r.dStrides, r.dStateIn, r.dStateOut);
+        const int rc = launch_plan(h, cp, r.dPoses, B, n_cycles, d, cx.stream, {r.dStrides, r.dStateIn, r.dStateOut});
         if (rc != FPE_OK) return rc;
     }
     if (!r.speculate) {
@@ -2205,7 +2202,7 @@ void rank_layout(RankLayout& L, const fpe_plan_out* dFull, const fpe_rank_out& w
 // The launches of a prepared ranking call on `stream`: the plan through launch_plan, then summary, select, gather.
 int run_rank(fpe_engine* h, const CallPlan& cp, const fpe::RankConsts& rc, const fpe_pose* d_poses, const fpe_stride* d_strides, const RankLayout& L,
              hipStream_t stream) {
-    int rc0 = launch_plan(h, cp, d_poses, L.B, L.n, L.full, stream, d_strides);
+    int rc0 = launch_plan(h, cp, d_poses, L.B, L.n, L.full, stream, {d_strides});
     if (rc0 != FPE_OK) return rc0;
     FPE_HIP(fpe::launch_rank(rc, d_poses, L.B, L.n, L.K, L.full, L.summary, L.score, L.keys, L.bestIdx, L.nClass0, L.best, stream, d_strides));
     return FPE_OK;
@@ -2233,7 +2230,7 @@ int fpe_plan_rank_strides_device(fpe_handle h, const fpe_params* params, const f
     rank_layout(L, d_full, *d_out, false, nullptr, nullptr);
     rc0 = check_packed_fits(cp, (d_full && d_full->selected_packed) || d_out->best_products.selected_packed);
     if (rc0 != FPE_OK) return rc0;
-    rc0 = check_strides_launchable(cp, d_strides);
+    rc0 = check_strides_launchable(cp, d_strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain);
     if (rc0 != FPE_OK) return rc0;
     mark_async_launch(cp);
     void* scratch = nullptr;

@@ -2075,47 +2075,11 @@ static bool mid_variant(const PlanConsts& pc, double res) {
            pc.noMidVariant == 0;
 }
 
-// d_strides (fpe_plan_strides*; null: none): the stride kernels, which exist at the automatic group sizes only (8, 65)
-bool plan_chained_strides_supported(const PlanConsts& pc) {
-    const int G = plan_group_size(pc);
-    return G == 8 || G == 65;
-}
-hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides,
-                               const fpe_plan_state* d_stateIn, fpe_plan_state* d_stateOut) {
-    const size_t lds = plan_lds_bytes(pc);
-    const int G = plan_group_size(pc);
-    if (d_stateIn || d_stateOut) {  // the resume forms (fpe_plan_resume*), at the group sizes of the stride forms
-        if (G == 65)
-            hipLaunchKernelGGL(plan_sequential_resume_kernel, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides, d_stateIn,
-                               d_stateOut);
-        else if (G == 8)
-            hipLaunchKernelGGL((plan_chained_kernel<8, false, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>), dim3((B + 1) / 2), dim3(64), lds,
-                               stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides, d_stateIn, d_stateOut);
-        else
-            return hipErrorNotSupported;
-    } else if (d_strides) {
-        if (G == 65)
-            hipLaunchKernelGGL(plan_sequential_stride_kernel, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides);
-        else if (G == 8)
-            hipLaunchKernelGGL((plan_chained_kernel<8, false, const fpe_stride*>), dim3((B + 1) / 2), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out, d_strides);
-        else
-            return hipErrorNotSupported;
-    } else if (G == 65) {
-        hipLaunchKernelGGL(plan_sequential_kernel, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
-    } else if (G == 4) {
-        hipLaunchKernelGGL(plan_chained_kernel<4>, dim3((B + 3) / 4), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
-    } else if (G == 8 && mid_variant(pc, m.g.res)) {
-        hipLaunchKernelGGL((plan_chained_kernel<8, true>), dim3((B + 1) / 2), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
-    } else if (G == 8) {
-        hipLaunchKernelGGL(plan_chained_kernel<8>, dim3((B + 1) / 2), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
-    } else if (G == 16) {
-        hipLaunchKernelGGL(plan_chained_kernel<16>, dim3(B), dim3(64), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
-    } else {
-        hipLaunchKernelGGL(plan_chained_kernel<64>, dim3(B), dim3(256), lds, stream, m, pc, lut, d_poses, B, nCycles, d_out);
-    }
-    return hipGetLastError();
-}
+// ---- part two of this translation unit: the bit-window kernels (fpe_bits_window / _lane8 / _seq.hpp through it) ----
+#include "fpe_bits.hpp"
+// ---- the host side of every chained-plan kernel, direct and bit-window: selection, instantiation lists, launch ----
+// (here, ahead of the other launch wrappers: the plan kernels are instantiated first, as they always were)
+#include "fpe_plan_launch.hpp"
 
 hipError_t launch_search_legs(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_leg_query* d_q,
                               int n, fpe_foothold* d_out, hipStream_t stream) {
@@ -2162,8 +2126,6 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
     return hipGetLastError();
 }
 
-// ---- part two of this translation unit: the bit-window kernels (fpe_bits_window / _lane8 / _seq.hpp through it) ----
-#include "fpe_bits.hpp"
 // ---- part three: the producer's filters (elevation -> traversability) ----------------------------------------
 #include "fpe_filters.hpp"
 
@@ -2180,20 +2142,12 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_layers.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
+    const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)
+    if (ep != hipSuccess) return ep;
     const struct {
         const void* kernel;
         size_t bytes;
     } limits[] = {
-        {reinterpret_cast<const void*>(plan_chained_kernel<16>), planBytes},
-        {reinterpret_cast<const void*>(plan_chained_kernel<8>), planBytes},
-        {reinterpret_cast<const void*>(plan_chained_kernel<8, true>), planBytes},
-        {reinterpret_cast<const void*>(plan_chained_kernel<4>), planBytes},
-        {reinterpret_cast<const void*>(plan_chained_kernel<64>), planBytes},
-        {reinterpret_cast<const void*>(plan_sequential_kernel), planBytes},
-        {reinterpret_cast<const void*>(plan_chained_kernel<8, false, const fpe_stride*>), planBytes},
-        {reinterpret_cast<const void*>(plan_sequential_stride_kernel), planBytes},
-        {reinterpret_cast<const void*>(plan_chained_kernel<8, false, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>), planBytes},
-        {reinterpret_cast<const void*>(plan_sequential_resume_kernel), planBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<8>), searchBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<8, true>), searchBytes},
         {reinterpret_cast<const void*>(search_legs_kernel<64>), searchBytes},

@@ -9,15 +9,39 @@
 
 namespace fpe {
 
+// ---- chained plans (fpe_plan_launch.hpp) ---------------------------------------------------------------------
+// The optional per-pose arrays of a chained plan, and the form of every plan kernel they select, decided once:
+//   strides            one fpe_stride per pose (fpe_plan_strides*, fpe_plan_rank_strides*): the kernels' stride instantiations;
+//   stateIn / stateOut one fpe_plan_state per pose (fpe_plan_resume*): with either one the resume instantiations, which take a
+//                      null strides as the plan's own stride;
+//   none               the kernels as they were.
+enum class PlanForm { Plain, Stride, Resume };
+struct PlanChain {
+    const fpe_stride* strides = nullptr;
+    const fpe_plan_state* stateIn = nullptr;
+    fpe_plan_state* stateOut = nullptr;
+    PlanForm form() const { return (stateIn || stateOut) ? PlanForm::Resume : strides ? PlanForm::Stride : PlanForm::Plain; }
+};
+// What a chained-plan call launches.  None: no kernel of this form for the forced plan_group (`group` says which).
+enum class PlanFamily { None, Lane8, Seq, Chained, Sequential };  // bit window: 8 lanes per leg | one wavefront per pose; direct: chained | sequential legs
+struct PlanKernel {
+    PlanFamily family;
+    PlanForm form;
+    int nrl, kw, winSide;  // bit-window families: rows per lane, words per row, window rows = columns
+    int group;             // G of the direct families (plan_group_size), poses per workgroup of Seq (1 or 16)
+    bool mid;              // the 3x3-only variant (Lane8, Chained<8>)
+    int prod;              // compiled product mask (product_shape; Seq: 0 or 1)
+    unsigned grid, block;
+    size_t ldsBytes;
+    int recSlots, slotBytes;  // Seq: cycles of staged records per pose, bytes of a pose's LDS slot
+};
+PlanKernel select_plan_kernel(const PlanConsts& pc, const MapGeom& g, bool bits, int B, int productShape, PlanForm form);
+void describe_plan_kernel(const PlanKernel& k, char* buf, size_t n);
+// bm: the snapshot's bit planes (the bit-window kernels), or null: the direct kernels
+hipError_t launch_plan(const DevMap& m, const BitMap* bm, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses, int B,
+                       int nCycles, const fpe_plan_out& d_out, const PlanChain& chain, hipStream_t stream);
+
 // ---- direct kernels (fpe_kernels.hip) ------------------------------------------------------------------------
-// d_strides (here and in launch_plan_bits / launch_rank): one fpe_stride per pose, the stride form of the call (fpe_plan_strides*,
-// fpe_plan_rank_strides*) — the kernels' stride instantiations; null: the kernels as they were
-// d_stateIn / d_stateOut (launch_plan_chained, launch_plan_bits): one fpe_plan_state per pose, the resume form of the call
-// (fpe_plan_resume*) — with either one the kernels' resume instantiations, which take a null d_strides as the plan's own stride
-hipError_t launch_plan_chained(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_pose* d_poses,
-                               int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream, const fpe_stride* d_strides = nullptr,
-                               const fpe_plan_state* d_stateIn = nullptr, fpe_plan_state* d_stateOut = nullptr);
-bool plan_chained_strides_supported(const PlanConsts& pc);  // the direct stride kernels exist at the automatic group sizes only
 hipError_t launch_search_legs(const DevMap& m, const PlanConsts& pc, const SpiralLut& lut, const fpe_leg_query* d_q,
                               int n, fpe_foothold* d_out, hipStream_t stream);
 // open-loop centroid method
@@ -34,11 +58,6 @@ size_t bitmap_words(int rows, int cols, int* strideW, int* nw);
 hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float thrDefault, float thrCandidate,
                                uint32_t* d_words, hipStream_t stream);
 bool bits_supported(const PlanConsts& pc, const MapGeom& g);
-void describe_plan_kernel(const PlanConsts& pc, const MapGeom& g, char* buf, size_t n, int form = 0);  // 0 plain, 1 stride, 2 resume
-hipError_t launch_plan_bits(const DevMap& m, const BitMap& bm, const PlanConsts& pc, const SpiralLut& lut,
-                            const fpe_pose* d_poses, int B, int nCycles, const fpe_plan_out& d_out, hipStream_t stream,
-                            const fpe_stride* d_strides = nullptr, const fpe_plan_state* d_stateIn = nullptr,
-                            fpe_plan_state* d_stateOut = nullptr);
 
 // ---- producer filters (fpe_filters.hpp) ----------------------------------------------------------------------
 bool filters_supported(const FilterConsts& fc, const MapGeom& g);
@@ -96,6 +115,7 @@ struct RankConsts {
     int32_t rfFirst;
 };
 size_t rank_scratch_bytes(int B, int K);
+// d_strides: one fpe_stride per pose, the stride form of the call (fpe_plan_rank_strides*); null: the kernels as they were
 hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
                        fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
                        const fpe_plan_out& bestProducts, hipStream_t stream, const fpe_stride* d_strides = nullptr);

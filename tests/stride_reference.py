@@ -71,11 +71,13 @@ def mixed_strides(params, B, seed):
 
 # ---- the inputs of tests/test_gpu_strides.py (checked on the oracle alone in tests/test_cpu_strides.py) --------------------------
 # rows of tests/test_gpu_plan_matrix.py's table with its map recipe; B = 37 (odd: the last workgroup of an 8-lane kernel holds one
-# pose), 70 (sixteen poses per workgroup, the last one partly empty), 19 elsewhere
-CASE_B = {"w7_mid": 37, "w7_gen": 37, "w12_gen": 37, "w16_seq": 19, "w47_seq": 70, "w48_direct": 19}
+# pose), 70 (sixteen poses per workgroup, the last one partly empty), 19 elsewhere (w32_seq: below 64, one pose per workgroup on
+# the 96-bit rows)
+CASE_B = {"w7_mid": 37, "w7_gen": 37, "w8_gen": 37, "w12_gen": 37, "w16_seq": 19, "w32_seq": 19, "w47_seq": 70, "w48_direct": 19}
 CYCLES = (5, 9)  # both sides of the 4-cycle y-table batch and of the 8-cycle flush
 STRIDE_KERNEL = {"w7_mid": "plan_bits_kernel<2, false> stride", "w7_gen": "plan_bits_kernel<2, false> stride",
-                 "w12_gen": "plan_bits_kernel<4, false> stride", "w16_seq": "plan_bits_seq_kernel<1, 2> stride",
+                 "w8_gen": "plan_bits_kernel<3, false> stride", "w12_gen": "plan_bits_kernel<4, false> stride",
+                 "w16_seq": "plan_bits_seq_kernel<1, 2> stride", "w32_seq": "plan_bits_seq_kernel<2, 3> stride",
                  "w47_seq": "plan_bits_seq_kernel<2, 3> stride", "w48_direct": "plan_sequential_kernel stride (direct"}
 
 

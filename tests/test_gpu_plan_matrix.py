@@ -1,4 +1,4 @@
-"""Every kernel that launch_plan_bits can launch, against the oracle: one table row on each side of every bits_shape switch
+"""Every bit-window kernel that launch_plan can launch, against the oracle: one table row on each side of every bits_shape switch
 (window sides 15|17, 23|25, 31|33, 63|65, 95|97), every product shape on each row, odd and even batches, cycle counts on
 both sides of the eight-cycle flush, the sixteen-poses-per-workgroup launch with a partly empty last workgroup, the refusal
 edges of bits_supported, and exact-tie geometry (tests/tie_fixtures.py).  Each case asserts which kernel ran
@@ -72,7 +72,7 @@ def kernel_name(planner):
 
 
 def note(planner, products, B):
-    """Record the instantiation launch_plan_bits picks for this call (csrc/fpe_bits.hpp)."""
+    """Record the instantiation select_plan_kernel picks for this call (csrc/fpe_plan_launch.hpp)."""
     name, shape = kernel_name(planner), util.product_shape(products)
     if name.startswith("plan_bits_kernel"):
         key = (name, ("prod", shape))
@@ -175,7 +175,7 @@ def test_sixteen_poses_per_workgroup_with_a_partly_empty_last_workgroup(planner,
 
 @pytest.mark.parametrize("row_id,B", [("w47_seq", 21), ("w47_seq", 66), ("w32_seq", 21), ("w16_seq", 21)])
 def test_staged_record_slots_at_seventeen_cycles(planner, row_id, B):
-    """recSlots, the cycles of staged records per pose (launch_plan_bits, FPE_LAUNCH_BITS_SEQ): 8, halved while
+    """recSlots, the cycles of staged records per pose (select_plan_kernel, csrc/fpe_plan_launch.hpp): 8, halved while
         base + recSlots * 4 * sizeof(SeqRec) > 10240,
         base = sizeof(PoseShared) + 4 * sizeof(LegStatic) + 4 * legbits_words(rows, KW, nHW)      (each term a multiple of 16)
              = 1664 + 288 + 4 * ((2 + max(nHW, 1)) * rows * KW rounded up to 4),    sizeof(SeqRec) = 144, rows = 2 winH + 1.
@@ -309,11 +309,11 @@ def test_exact_tie_geometry(planner, name):
 
 # ---- what ran -----------------------------------------------------------------------------------------------------
 def promised():
-    """Every instantiation launch_plan_bits can pick — 18 of plan_bits_kernel<NRL, MID, PROD>, 8 of
-    plan_bits_seq_kernel<NRL, KW, kProd, GRP> — and the direct kernels on the far side of the refusal edges."""
+    """Every plain-form instantiation visit_lane8 / visit_seq name (csrc/fpe_plan_launch.hpp) — 18 of plan_bits_kernel<NRL, MID, PROD>,
+    6 of plan_bits_seq_kernel<NRL, KW, kProd, GRP> — and the direct kernels on the far side of the refusal edges."""
     want = {(f"plan_bits_kernel<{nrl}, {mid}>", ("prod", s)) for nrl in (2, 3, 4) for mid in ("true", "false") for s in (0, 1, 2)}
     want |= {("plan_bits_seq_kernel<1, 2>", ("kProd", k, "GRP", 1)) for k in (0, 1)}  # GRP 16 is for KW >= 3 only:
-    want |= {("plan_bits_seq_kernel<2, 3>", ("kProd", k, "GRP", g)) for k in (0, 1) for g in (1, 16)}  # <1, 2, *, 16> is never launched
+    want |= {("plan_bits_seq_kernel<2, 3>", ("kProd", k, "GRP", g)) for k in (0, 1) for g in (1, 16)}  # <1, 2, *, 16> is not compiled
     want |= {("plan_sequential_kernel", ()), ("plan_chained_kernel<8, false>", ())}
     return want
 
