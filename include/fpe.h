@@ -749,7 +749,8 @@ int fpe_describe_plan_strides(fpe_handle h, const fpe_params* params, char* buf,
  * Kernels: a resume instantiation beside every stride instantiation (fpe_describe_plan_resume: "... resume (...)"); as for strides
  * there is no 3x3-only form, and a forced "plan_group" of 4, 16 or 64 returns FPE_E_UNSUPPORTED.  A call with neither state runs
  * exactly what fpe_plan_strides runs.
- * Out of scope: fpe_plan_rank* (the cog-speed KPI's first current feet are a separate question), the opt track, the service calls,
+ * Out of scope: fpe_plan_rank* (the cog-speed KPI's first current feet are a separate question; resumed segments are scored and
+ * pruned on the device by fpe_plan_beam*, below, whose score has no cog-speed term), the opt track, the service calls,
  * fpe_multi_* / dist.py, and z in the state (getDefaultFootholdNext overwrites it with 0, and no track's recurrence reads it). */
 typedef struct fpe_plan_state {      /* 208 bytes; element b belongs to poses[b] */
     double  feet[3][4][2];  /* [track: 0 default, 1 centroid, 2 nominal][leg: RF,RH,LH,LF][x, y]: the three tracks'
@@ -772,6 +773,75 @@ int fpe_plan_state_from_pose(const fpe_params* params, const fpe_pose* pose, con
 int fpe_plan_state_from_feet(const double feet_xy[4][2], double adjusted_y, int32_t cycle, fpe_plan_state* out);
 /* fpe_describe_plan for the kernel a resume call (either state given) launches on the current map. */
 int fpe_describe_plan_resume(fpe_handle h, const fpe_params* params, char* buf, int32_t n);
+
+/* ---- beam search over stride options on the device, on resumable plans ---------------------------------------------------------
+ * BUILD-DEFINED (the reference has one stride, and a failing cycle of it commits nothing: the next cycle retries from the same
+ * feet).  The planner chooses its strides: S segments of k gait cycles; in every segment each kept plan of a root pose is continued
+ * with each of the M stride options, the continuations are scored, and the best W per root are kept.  Expand, score, prune,
+ * remember and trace back run on the device, on one stream, with no host synchronisation between segments; the chain arithmetic is
+ * fpe_plan_resume's (one resume launch per segment, one map snapshot for the whole beam) and nothing here adds search arithmetic.
+ * Every root pose b has its own beam; roots never compete with one another.
+ *  - Parents of segment 0.  One per root: state_in[b], or "start from the pose" when state_in == NULL; penalty +0.0; n_{-1} = 1.
+ *  - Candidates of segment s.  Parent slot p < n_{s-1} and option m < M give candidate c = p * M + m: k cycles of fpe_plan_resume
+ *    for poses[b] with the stride options[m] from the parent's state.  In segment 0 with state_in == NULL it is exactly what
+ *    fpe_plan_strides computes for that pose and stride (the half-step shift of the start depends on the option).
+ *  - Segment penalty.  q = w_fail*(k - committed) + w_spiral*n_source[1] + w_none*(n_source[2] + n_source[3]) +
+ *    w_deviation*deviation_sq_sum, with committed, n_source and deviation_sq_sum as fpe_pose_summary defines them over the segment's
+ *    k cycles: each product first, the four terms added left to right in f64, no contraction.  P_c = P_parent + q.
+ *  - Progress.  cx = ((x_RF + x_RH) + (x_LH + x_LF)) * 0.25 over the NOMINAL track (feet[2]) of the candidate's state behind the
+ *    segment.  Candidates of one root are compared only among themselves, so the absolute cx needs no baseline.
+ *  - Score.  t = w_progress * cx, then score = P_c - t (two operations, no fused multiply-add); -0.0 is stored as +0.0.  There is no
+ *    cog-speed term (fpe_plan_rank's KPI assumes a start from the stance), so walk-gait roots are ordinary.
+ *  - Order and survivors.  (class, score, c) ascending; class 1 = non-finite score, ordered by c alone; equal scores (IEEE ==) fall
+ *    to c.  n_s = min(W, n_{s-1} * M), the same for every root; the survivors fill slots 0 .. n_s - 1 in order.
+ *  - Outputs for live slot (b, w), w < n_{S-1}, best first, at element b * W + w: score and penalty of the last segment; path[s],
+ *    the option taken in segment s along the slot's ancestry; state, behind the last cycle; products, the ancestry's segments
+ *    concatenated — record (g, leg) of the slot's S * k cycles sits where ONE fpe_plan_resume call of S * k cycles for B * W poses
+ *    would put it, gait_cycle_id = state.cycle + g.  n_live[b] = n_{S-1}.  Dead slots (w >= n_live) are NOT WRITTEN, in every output
+ *    array.  No atomics: every byte is a function of the inputs alone.
+ *  - Replay.  For any live slot, S successive fpe_plan_resume calls of k cycles for poses[b] with the stride options[path[s]] and
+ *    the state carried over give the slot's products (concatenated) and its state byte for byte.
+ *  - Refusals (FPE_E_INVALID_ARG; nothing written or queued): M outside 1..FPE_BEAM_MAX_OPTIONS, width outside
+ *    1..FPE_BEAM_MAX_WIDTH, segments or cycles_per_segment < 1, segments * cycles_per_segment > 255, B < 1, B * width * M >
+ *    FPE_BEAM_MAX_CHAINS, reserved != 0, a non-finite weight, path == NULL, stance or pose_status requested (products of a start,
+ *    as for a resumed plan).  The host form also refuses what fpe_plan_resume refuses for poses, options and states, with cycle +
+ *    segments * cycles_per_segment > 255 in place of its cycle bound.  A forced "plan_group" of 4, 16 or 64 returns
+ *    FPE_E_UNSUPPORTED (no resume kernel exists there); the map-size bound of selected_packed applies when that product is requested.
+ *  - Device form.  It cannot look at the values: a non-finite option or state takes the resume kernels' documented path.  A chain
+ *    that STARTS from a non-finite value — a non-finite state, or a non-finite step length from the poses (the start is stance -
+ *    step / 2) — has NaN x in every track, which gives a NaN cx: the candidate is class 1, and so is every descendant.  A non-finite
+ *    step length on a finite parent state fails every cycle and commits nothing: the candidate keeps its parent's feet, so it is
+ *    class 0 with k failed cycles in its penalty.
+ * Out of scope: a global beam across roots, deduplication of equal states, the opt track, the service calls, fpe_multi_* / dist.py. */
+#define FPE_BEAM_MAX_OPTIONS 16
+#define FPE_BEAM_MAX_WIDTH   64
+#define FPE_BEAM_MAX_CHAINS  (1 << 20)   /* B * width * n_options */
+typedef struct fpe_beam_params {          /* 56 bytes */
+    int32_t segments;            /* S >= 1 */
+    int32_t cycles_per_segment;  /* k >= 1; S * k <= 255 */
+    int32_t width;               /* W, 1..FPE_BEAM_MAX_WIDTH: beam entries kept PER ROOT pose */
+    int32_t reserved;            /* 0 */
+    double  w_fail, w_spiral, w_none, w_deviation, w_progress;   /* all finite */
+} fpe_beam_params;
+/* build-defined defaults: segments 4, cycles_per_segment 2, width 8; w_fail 100, w_spiral 1, w_none 0, w_deviation 10, w_progress 100 */
+int fpe_beam_params_defaults(fpe_beam_params* out);
+typedef struct fpe_beam_out {             /* 104 bytes */
+    int32_t* n_live;        /* [B] live entries of each root's final beam, or NULL */
+    double*  score;         /* [B * W] or NULL */
+    double*  penalty;       /* [B * W] or NULL */
+    uint8_t* path;          /* [B * W * S] option index taken in each segment — required */
+    fpe_plan_state* state;  /* [B * W] state behind the last cycle, or NULL */
+    fpe_plan_out products;  /* shapes of fpe_plan_out with B -> B * W and n_cycles -> S * k; any pointer may be NULL;
+                               stance and pose_status must be NULL (FPE_E_INVALID_ARG), as for a resumed plan */
+} fpe_beam_out;
+/* Host arrays; synchronous.  beam NULL = fpe_beam_params_defaults; state_in may be NULL; options: M elements. */
+int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_pose* poses,
+                  const fpe_plan_state* state_in, int32_t B, const fpe_stride* options, int32_t M, const fpe_beam_out* out);
+/* Device arrays (every non-NULL pointer of d_out too); asynchronous on `stream`, snapshot semantics of fpe_plan_device.  The
+ * candidates, keys and the history live in one stream-ordered scratch block. */
+int fpe_plan_beam_device(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_pose* d_poses,
+                         const fpe_plan_state* d_state_in, int32_t B, const fpe_stride* d_options, int32_t M,
+                         const fpe_beam_out* d_out, void* stream);
 
 /* ---- the dense maps as grid_map message layers: the inverse of fpe_upload_map's ingest ----------------------------------
  * BUILD-DEFINED (the reference publishes none of these layers).  One call runs the dense families whose layers are requested —

@@ -251,6 +251,22 @@ class RankOut(C.Structure):
                 ("best_products", PlanOut)]
 
 
+BEAM_MAX_OPTIONS, BEAM_MAX_WIDTH, BEAM_MAX_CHAINS = 16, 64, 1 << 20  # FPE_BEAM_MAX_*
+
+
+class BeamParams(C.Structure):
+    """fpe_beam_params: the shape of a beam search over stride options (segments x cycles, entries kept per root) and its weights."""
+    _fields_ = [("segments", C.c_int32), ("cycles_per_segment", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("w_fail", C.c_double), ("w_spiral", C.c_double), ("w_none", C.c_double), ("w_deviation", C.c_double),
+                ("w_progress", C.c_double)]
+
+
+class BeamOut(C.Structure):
+    """fpe_beam_out: outputs of a beam call (`path` is required; anything else may be NULL; no stance, no pose_status)."""
+    _fields_ = [("n_live", C.c_void_p), ("score", C.c_void_p), ("penalty", C.c_void_p), ("path", C.c_void_p), ("state", C.c_void_p),
+                ("products", PlanOut)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -263,6 +279,7 @@ STRUCTS = {
     "fpe_foothold_snap_out": FootholdSnapOut, "fpe_centroid_query": CentroidQuery, "fpe_centroid_map_out": CentroidMapOut,
     "fpe_pose_summary": PoseSummary, "fpe_rank_params": RankParams, "fpe_rank_out": RankOut, "fpe_layer_layout": LayerLayout,
     "fpe_layer_request": LayerRequest, "fpe_stride": STRIDE_DTYPE, "fpe_plan_state": PLAN_STATE_DTYPE,
+    "fpe_beam_params": BeamParams, "fpe_beam_out": BeamOut,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -336,6 +353,9 @@ PROTOTYPES = {
     "fpe_plan_state_from_pose": (cint, [vp, vp, vp, vp]),
     "fpe_plan_state_from_feet": (cint, [vp, f64, i32, vp]),
     "fpe_describe_plan_resume": (cint, [vp, vp, cstr, i32]),
+    "fpe_beam_params_defaults": (cint, [P(BeamParams)]),
+    "fpe_plan_beam": (cint, [vp, vp, P(BeamParams), vp, vp, i32, vp, i32, P(BeamOut)]),
+    "fpe_plan_beam_device": (cint, [vp, vp, P(BeamParams), vp, vp, i32, vp, i32, P(BeamOut), vp]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),
@@ -415,6 +435,17 @@ def rank_params_defaults(**overrides):
             raise ValueError(f"unknown rank parameter {k!r}")
         setattr(rp, k, v)
     return rp
+
+
+def beam_params_defaults(**overrides):
+    """fpe_beam_params_defaults, with any field replaced by a keyword."""
+    bp = BeamParams()
+    assert lib().fpe_beam_params_defaults(C.byref(bp)) == FPE_OK
+    for k, v in overrides.items():
+        if k not in dict(BeamParams._fields_):
+            raise ValueError(f"unknown beam parameter {k!r}")
+        setattr(bp, k, v)
+    return bp
 
 
 def spiral_offsets(n_rings):

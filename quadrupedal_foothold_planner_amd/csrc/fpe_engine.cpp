@@ -2297,6 +2297,221 @@ int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank
     return FPE_OK;
 }
 
+int fpe_beam_params_defaults(fpe_beam_params* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->segments = 4;
+    out->cycles_per_segment = 2;
+    out->width = 8;
+    out->w_fail = 100.0;
+    out->w_spiral = 1.0;
+    out->w_none = 0.0;
+    out->w_deviation = 10.0;
+    out->w_progress = 100.0;
+    return FPE_OK;
+}
+
+namespace {
+constexpr int kBeamOwn = 5;  // a beam call's outputs of its own, behind the products: n_live, score, penalty, path, state
+static_assert(kPlanProducts + kBeamOwn <= kProducts + 1, "SegList holds a beam call's outputs");
+
+// Arguments of fpe_plan_beam* that need no map; bc / sh: the beam's constants and shape (beam NULL: the defaults).
+int check_beam_args(const fpe_params* params, const fpe_beam_params* beam, int32_t B, int32_t M, const fpe_beam_out* out, fpe::BeamConsts& bc,
+                    fpe::BeamShape& sh) {
+    if (!params || !out || !out->path) return fail(FPE_E_INVALID_ARG, "null argument (path is required)");
+    fpe_beam_params def;
+    if (!beam) {
+        fpe_beam_params_defaults(&def);
+        beam = &def;
+    }
+    const int32_t S = beam->segments, k = beam->cycles_per_segment, W = beam->width;
+    if (B < 1 || M < 1 || M > FPE_BEAM_MAX_OPTIONS || W < 1 || W > FPE_BEAM_MAX_WIDTH)
+        return fail(FPE_E_INVALID_ARG, "beam: B >= 1, 1 <= M <= 16 and 1 <= width <= 64");
+    if (S < 1 || k < 1 || static_cast<long long>(S) * k > 255) return fail(FPE_E_INVALID_ARG, "beam: segments, cycles_per_segment >= 1 and their product <= 255");
+    if (static_cast<long long>(B) * W * M > FPE_BEAM_MAX_CHAINS) return fail(FPE_E_INVALID_ARG, "beam: B * width * M exceeds FPE_BEAM_MAX_CHAINS");
+    if (beam->reserved != 0) return fail(FPE_E_INVALID_ARG, "fpe_beam_params.reserved must be 0");
+    const double w[5] = {beam->w_fail, beam->w_spiral, beam->w_none, beam->w_deviation, beam->w_progress};
+    for (double v : w)
+        if (!std::isfinite(v)) return fail(FPE_E_INVALID_ARG, "beam weights must be finite");
+    if (out->products.stance || out->products.pose_status)
+        return fail(FPE_E_INVALID_ARG, "a beam's plans are continuations: no stance and no pose_status");
+    bc = fpe::BeamConsts{w[0], w[1], w[2], w[3], w[4]};
+    sh = fpe::BeamShape{B, M, W, S, k, 0, W};
+    sh.slotStride = fpe::beam_live(sh, S - 1);
+    return FPE_OK;
+}
+
+// Where everything a beam call touches on the device lives: the scratch (fpe::BeamScratch) and — the host form — the output block,
+// dense (outStride = n_{S-1} slots per root), in the order products, n_live, score, penalty, path, state.  outSlot[k]: bytes per
+// slot of output k (0: one element per root).  lay(base, outBase) fills the pointers; both bases null: sizes only.
+struct BeamLayout {
+    fpe::BeamShape sh;
+    fpe::BeamScratch sc;
+    fpe_beam_out out;
+    size_t scratchBytes, outBytes;
+    size_t outOff[kPlanProducts + kBeamOwn], outLen[kPlanProducts + kBeamOwn], outSlot[kPlanProducts + kBeamOwn];
+};
+void beam_layout(BeamLayout& L, const fpe_beam_out& want, bool hostForm, unsigned char* base, unsigned char* outBase) {
+    const bool reads[kPlanProducts] = {true, false, true, true, false, false, false, false};  // beam_score_kernel's inputs
+    const fpe::BeamShape& sh = L.sh;
+    const size_t S = static_cast<size_t>(sh.S), k = static_cast<size_t>(sh.k), slots_ = static_cast<size_t>(sh.B) * sh.slotStride;
+    const size_t chains = static_cast<size_t>(sh.B) * (sh.S > 1 ? fpe::beam_live(sh, sh.S - 2) : 1) * sh.M;
+    size_t off = 0, oo = 0;
+    const auto take = [&](size_t bytes) {
+        unsigned char* p = base + off;
+        off += align256(bytes);
+        return static_cast<void*>(p);
+    };
+    const auto takeOut = [&](int q, size_t bytesPerSlot, size_t n) {
+        L.outOff[q] = oo;
+        L.outLen[q] = bytesPerSlot * n;
+        oo += align256(L.outLen[q]);
+        return static_cast<void*>(outBase + L.outOff[q]);
+    };
+    for (int q = 0; q < kPlanProducts + kBeamOwn; ++q) L.outOff[q] = L.outLen[q] = L.outSlot[q] = 0;
+    L.sc.poses = static_cast<fpe_pose*>(take(chains * sizeof(fpe_pose)));
+    L.sc.strides = static_cast<fpe_stride*>(take(chains * sizeof(fpe_stride)));
+    L.sc.stateIn = static_cast<fpe_plan_state*>(take(chains * sizeof(fpe_plan_state)));
+    L.sc.stateOut = static_cast<fpe_plan_state*>(take(chains * sizeof(fpe_plan_state)));
+    L.sc.candPenalty = static_cast<double*>(take(chains * sizeof(double)));
+    L.sc.candScore = static_cast<double*>(take(chains * sizeof(double)));
+    L.sc.keys = take(chains * 16);
+    L.sc.surv = static_cast<fpe::BeamSurvivor*>(take(S * slots_ * sizeof(fpe::BeamSurvivor)));
+    L.sc.parents = static_cast<fpe_plan_state*>(take(slots_ * sizeof(fpe_plan_state)));
+    void* const* wanted = slots(want.products);
+    const size_t outSlots = static_cast<size_t>(sh.B) * sh.outStride;
+    for (int q = 0; q < kPlanProducts; ++q) {
+        slots(L.sc.cand)[q] = (reads[q] || wanted[q]) ? take(product_bytes(q, chains, k)) : nullptr;
+        slots(L.sc.hist)[q] = wanted[q] ? take(product_bytes(q, S * slots_, k)) : nullptr;
+        L.outSlot[q] = product_bytes(q, 1, S * k);
+        slots(L.out.products)[q] = !wanted[q] ? nullptr : (hostForm ? takeOut(q, L.outSlot[q], outSlots) : wanted[q]);
+    }
+    const int o = kPlanProducts;
+    L.outSlot[o + 1] = L.outSlot[o + 2] = sizeof(double), L.outSlot[o + 3] = S, L.outSlot[o + 4] = sizeof(fpe_plan_state);
+    L.out.n_live = !want.n_live ? nullptr : (hostForm ? static_cast<int32_t*>(takeOut(o, sizeof(int32_t), sh.B)) : want.n_live);
+    L.out.score = !want.score ? nullptr : (hostForm ? static_cast<double*>(takeOut(o + 1, L.outSlot[o + 1], outSlots)) : want.score);
+    L.out.penalty = !want.penalty ? nullptr : (hostForm ? static_cast<double*>(takeOut(o + 2, L.outSlot[o + 2], outSlots)) : want.penalty);
+    L.out.path = hostForm ? static_cast<uint8_t*>(takeOut(o + 3, L.outSlot[o + 3], outSlots)) : want.path;
+    L.out.state = !want.state ? nullptr : (hostForm ? static_cast<fpe_plan_state*>(takeOut(o + 4, L.outSlot[o + 4], outSlots)) : want.state);
+    L.scratchBytes = off;
+    L.outBytes = oo;
+}
+
+// The launches of a prepared beam call on `stream`: S x (expand, the resume kernels through launch_plan, score / select / keep),
+// then the trace.  Nothing synchronises the host.
+int run_beam(fpe_engine* h, const CallPlan& cp, const fpe::BeamConsts& bc, const fpe_pose* d_poses, const fpe_stride* d_options,
+             const fpe_plan_state* d_stateIn, const BeamLayout& L, hipStream_t stream) {
+    const fpe::BeamShape& sh = L.sh;
+    for (int s = 0; s < sh.S; ++s) {
+        FPE_HIP(fpe::launch_beam_expand(sh, s, d_poses, d_options, d_stateIn, L.sc, stream));
+        const int chains = sh.B * (s == 0 ? 1 : fpe::beam_live(sh, s - 1)) * sh.M;
+        const fpe::PlanChain chain{L.sc.strides, (s == 0 && !d_stateIn) ? nullptr : L.sc.stateIn, L.sc.stateOut};
+        const int rc = launch_plan(h, cp, L.sc.poses, chains, sh.k, L.sc.cand, stream, chain);
+        if (rc != FPE_OK) return rc;
+        FPE_HIP(fpe::launch_beam_prune(bc, sh, s, L.sc, stream));
+    }
+    FPE_HIP(fpe::launch_beam_trace(sh, L.sc, L.out, stream));
+    return FPE_OK;
+}
+}  // namespace
+
+int fpe_plan_beam_device(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_pose* d_poses,
+                         const fpe_plan_state* d_state_in, int32_t B, const fpe_stride* d_options, int32_t M, const fpe_beam_out* d_out,
+                         void* stream) {
+    BeamLayout L{};
+    fpe::BeamConsts bc;
+    int rc = check_beam_args(params, beam, B, M, d_out, bc, L.sh);
+    if (rc != FPE_OK) return rc;
+    if (!h || !d_poses || !d_options) return fail(FPE_E_INVALID_ARG, "null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    rc = prepare_call(h, params, 0.0f, cp, st, true);
+    if (rc != FPE_OK) return rc;
+    rc = check_strides_launchable(cp, fpe::PlanForm::Resume);  // (a refusal queues nothing: ahead of the async mark)
+    if (rc != FPE_OK) return rc;
+    rc = check_packed_fits(cp, d_out->products.selected_packed != nullptr);
+    if (rc != FPE_OK) return rc;
+    beam_layout(L, *d_out, false, nullptr, nullptr);
+    mark_async_launch(cp);
+    void* scratch = nullptr;
+    FPE_HIP(hipMallocAsync(&scratch, L.scratchBytes, st));
+    beam_layout(L, *d_out, false, static_cast<unsigned char*>(scratch), nullptr);
+    rc = run_beam(h, cp, bc, d_poses, d_options, d_state_in, L, st);
+    const hipError_t f = hipFreeAsync(scratch, st);
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(f);
+    return FPE_OK;
+}
+
+int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_pose* poses, const fpe_plan_state* state_in,
+                  int32_t B, const fpe_stride* options, int32_t M, const fpe_beam_out* out) {
+    BeamLayout L{};
+    fpe::BeamConsts bc;
+    int rc = check_beam_args(params, beam, B, M, out, bc, L.sh);
+    if (rc != FPE_OK) return rc;
+    if (!h || !poses || !options) return fail(FPE_E_INVALID_ARG, "null argument");
+    float maxRadius = 0.0f;
+    rc = check_host_poses(poses, B, maxRadius);
+    if (rc != FPE_OK) return rc;
+    rc = check_host_strides(options, M);
+    if (rc != FPE_OK) return rc;
+    rc = check_host_states(state_in, B, L.sh.S * L.sh.k);
+    if (rc != FPE_OK) return rc;
+    const fpe::BeamShape want = L.sh;  // (the caller's arrays: W slots per root)
+    L.sh.outStride = L.sh.slotStride;  // the arena's output block is dense: only live slots exist there
+    beam_layout(L, *out, true, nullptr, nullptr);
+    // both arenas: [poses | options | state_in | outputs | scratch (device arena only)]; the inputs are read from the pinned arena
+    const size_t oOptions = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    const size_t oStates = oOptions + align256(static_cast<size_t>(M) * sizeof(fpe_stride));
+    const size_t szIn = oStates + (state_in ? align256(static_cast<size_t>(B) * sizeof(fpe_plan_state)) : 0);
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(szIn + L.outBytes + L.scratchBytes));
+    cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
+    rc = prepare_call(h, params, maxRadius, cp, cx.stream, true);
+    if (rc != FPE_OK) return rc;
+    rc = check_strides_launchable(cp, fpe::PlanForm::Resume);
+    if (rc != FPE_OK) return rc;
+    rc = check_packed_fits(cp, out->products.selected_packed != nullptr);
+    if (rc != FPE_OK) return rc;
+    stage_batch_inputs(cx.pinned, 0, poses, nullptr, B, oStates, state_in);
+    std::memcpy(cx.pinned + oOptions, options, static_cast<size_t>(M) * sizeof(fpe_stride));
+    void* mapped = nullptr;
+    FPE_HIP(hipHostGetDevicePointer(&mapped, cx.pinned, 0));
+    unsigned char* const in = static_cast<unsigned char*>(mapped);
+    beam_layout(L, *out, true, cx.dev + szIn + L.outBytes, cx.dev + szIn);
+    rc = run_beam(h, cp, bc, reinterpret_cast<const fpe_pose*>(in), reinterpret_cast<const fpe_stride*>(in + oOptions),
+                  state_in ? reinterpret_cast<const fpe_plan_state*>(in + oStates) : nullptr, L, cx.stream);
+    if (rc != FPE_OK) return rc;
+    void* dst[kPlanProducts + kBeamOwn];
+    std::copy(slots(out->products), slots(out->products) + kPlanProducts, dst);
+    const int o = kPlanProducts;
+    dst[o] = out->n_live, dst[o + 1] = out->score, dst[o + 2] = out->penalty, dst[o + 3] = out->path, dst[o + 4] = out->state;
+    if (L.sh.outStride == want.outStride) {  // a full beam: the arena's arrays are the caller's
+        SegList segs;
+        for (int q = 0; q < kPlanProducts + kBeamOwn; ++q) segs.add(szIn + L.outOff[q], L.outLen[q], dst[q]);
+        return copy_out(h, cx, segs, cx.dev, cx.pinned);
+    }
+    // an underfilled beam (M^S < W: a few slots): one transfer, then every root's live slots to the head of its W slots — the dead
+    // ones are not written
+    FPE_HIP(hipMemcpyAsync(cx.pinned + szIn, cx.dev + szIn, L.outBytes, hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    for (int q = 0; q < kPlanProducts + kBeamOwn; ++q) {
+        if (!dst[q] || !L.outLen[q]) continue;
+        const unsigned char* src = cx.pinned + szIn + L.outOff[q];
+        if (!L.outSlot[q] || q == o) {
+            std::memcpy(dst[q], src, L.outLen[q]);
+            continue;
+        }
+        const size_t live = L.outSlot[q] * L.sh.outStride, all = L.outSlot[q] * want.outStride;
+        for (int b = 0; b < B; ++b) std::memcpy(static_cast<unsigned char*>(dst[q]) + b * all, src + b * live, live);
+    }
+    return FPE_OK;
+}
+
 int fpe_last_service_gate(fpe_handle h, fpe_service_gate* out) {
     if (!h || !out) return fail(FPE_E_INVALID_ARG, "null argument");
     if (g_gateEngine != h) return fail(FPE_E_INVALID_ARG, "no fpe_plan_service* call was made with this engine on this thread");

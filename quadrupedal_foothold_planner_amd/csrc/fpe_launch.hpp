@@ -144,4 +144,44 @@ struct LayersArgs {
 };
 hipError_t launch_layers_export(const LayersArgs& a, hipStream_t stream);
 
+// ---- beam search over stride options (fpe_beam.hpp) ----------------------------------------------------------
+struct BeamConsts {
+    double wFail, wSpiral, wNone, wDeviation, wProgress;
+};
+// B roots, M options, W entries kept per root, S segments of k cycles.  slotStride: slots per root of the survivor, parent and
+// history arrays (the final beam's live entries, n_{S-1}: no segment keeps more); outStride: slots per root of the outputs (W in the
+// caller's arrays; the host form's arena is dense, n_{S-1}).
+struct BeamShape {
+    int32_t B, M, W, S, k;
+    int32_t slotStride, outStride;
+};
+// One kept candidate of a segment: where it came from, its accumulated penalty and its score
+struct BeamSurvivor {
+    int32_t parent, option;
+    double penalty, score;
+};
+// The device scratch of a beam call (laid out by the engine).  chains: B * n_{S-2} * M, the most one segment plans.
+struct BeamScratch {
+    fpe_pose* poses;            // [chains] the candidates' poses, strides and states: what the segment's plan call reads ...
+    fpe_stride* strides;
+    fpe_plan_state* stateIn;
+    fpe_plan_state* stateOut;   // ... and writes, with
+    fpe_plan_out cand;          // its products: nominal, default_next and cycle_ok (scoring reads them) and every requested one
+    double* candPenalty;        // [chains]
+    double* candScore;          // [chains]
+    void* keys;                 // [chains] 16-byte sort keys
+    BeamSurvivor* surv;         // [S][B][slotStride]
+    fpe_plan_state* parents;    // [B][slotStride] the states behind the last segment's survivors
+    fpe_plan_out hist;          // [S][B][slotStride] blocks of k cycles: the requested products only
+};
+int beam_live(const BeamShape& sh, int s);  // n_s = min(W, M^(s+1)): entries every root keeps behind segment s
+// Segment s: the candidates' inputs from the survivors of segment s - 1 (s = 0: from d_stateIn, or — null — none: the chains start
+// from the poses) ...
+hipError_t launch_beam_expand(const BeamShape& sh, int s, const fpe_pose* d_poses, const fpe_stride* d_options,
+                              const fpe_plan_state* d_stateIn, const BeamScratch& sc, hipStream_t stream);
+// ... and, behind the segment's plan call, score, select and keep
+hipError_t launch_beam_prune(const BeamConsts& bc, const BeamShape& sh, int s, const BeamScratch& sc, hipStream_t stream);
+// Behind the last segment: every live slot's path, products, state, score and penalty, and n_live
+hipError_t launch_beam_trace(const BeamShape& sh, const BeamScratch& sc, const fpe_beam_out& d_out, hipStream_t stream);
+
 }  // namespace fpe

@@ -350,6 +350,61 @@ class FootholdPlanner(_Handle):
                                                      C.c_void_p(d_state_in_ptr) if d_state_in_ptr else None, int(B), int(n_cycles), C.byref(po),
                                                      C.c_void_p(d_state_out_ptr) if d_state_out_ptr else None, C.c_void_p(stream or 0)))
 
+    # ---- beam search over stride options on resumable plans (build-defined: fpe_plan_beam*) ---------------------------------
+    BEAM_PRODUCTS = ("nominal", "centroid", "default", "cycle_ok", "selected", "selected_packed")  # what a beam's plans can return
+
+    @staticmethod
+    def _beam_params(beam):
+        """None (the defaults), a _capi.BeamParams, or a dict of its fields to replace."""
+        if beam is None or isinstance(beam, _capi.BeamParams):
+            return beam
+        return _capi.beam_params_defaults(**dict(beam))
+
+    def plan_beam(self, poses, options, beam=None, states=None, products=("nominal", "cycle_ok")):
+        """fpe_plan_beam with host buffers: for every root pose a beam search over the stride `options` (an fpe_stride array,
+        make_strides) — S segments of k cycles, the W best continuations kept per root (`beam`: None for the defaults, a
+        _capi.BeamParams, or a dict of its fields) — from `states` (one fpe_plan_state per root) or from the poses.  Returns {"path":
+        uint8 [B, W, S] option indices, "score", "penalty": float64 [B, W], "n_live": int32 [B], "state": fpe_plan_state [B, W], and
+        each requested product with the shapes of plan() for B * W poses and S * k cycles, reshaped to [B, W, ...]}; slot (b, w) is
+        root b's w-th best plan, and slots w >= n_live[b] are left as allocated (zeros)."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        options = np.ascontiguousarray(options, dtype=STRIDE_DTYPE).reshape(-1)
+        B, M = poses.shape[0], options.shape[0]
+        unknown = set(products) - set(self.BEAM_PRODUCTS)
+        if unknown:
+            raise ValueError(f"a beam call has no products {sorted(unknown)}")
+        if states is not None:
+            states = np.ascontiguousarray(states, dtype=PLAN_STATE_DTYPE)
+            if states.shape != (B,):
+                raise ValueError(f"states must hold one element per pose: shape {states.shape}, {B} poses")
+        bp = self._beam_params(beam)
+        shape = bp if bp is not None else _capi.beam_params_defaults()
+        S, k, W = max(int(shape.segments), 1), max(int(shape.cycles_per_segment), 1), max(int(shape.width), 1)
+        shapes = product_shapes(B * W, S * k)
+        out = {q: np.zeros(shapes[q][0], dtype=shapes[q][1]) for q in PRODUCT_ORDER if q in products}
+        out.update(path=np.zeros((B, W, S), np.uint8), score=np.zeros((B, W)), penalty=np.zeros((B, W)), n_live=np.zeros(B, np.int32),
+                   state=np.zeros((B, W), PLAN_STATE_DTYPE))
+        bo = _capi.BeamOut(ptr(out["n_live"]), ptr(out["score"]), ptr(out["penalty"]), ptr(out["path"]), ptr(out["state"]))
+        for q in products:
+            setattr(bo.products, PRODUCT_FIELDS[q], ptr(out[q]))
+        self._check(self._lib.fpe_plan_beam(self._h, ptr(self.params), C.byref(bp) if bp is not None else None, ptr(poses), ptr(states), B,
+                                            ptr(options), M, C.byref(bo)))
+        for q in products:
+            out[q] = out[q].reshape((B, W) + out[q].shape[1:])
+        return out
+
+    def plan_beam_device(self, d_poses_ptr, B, d_options_ptr, M, d_path_ptr, beam=None, d_state_in_ptr=0, d_n_live_ptr=0, d_score_ptr=0,
+                         d_penalty_ptr=0, d_state_ptr=0, products=None, stream=0):
+        """fpe_plan_beam_device: DEVICE pointers (0 / missing = not wanted), asynchronous on `stream`.  products: {product name:
+        device pointer} with plan()'s shapes for B * W poses and S * k cycles."""
+        bo = _capi.BeamOut(d_n_live_ptr or None, d_score_ptr or None, d_penalty_ptr or None, d_path_ptr or None, d_state_ptr or None)
+        for q, p in (products or {}).items():
+            setattr(bo.products, PRODUCT_FIELDS[q], p or None)
+        bp = self._beam_params(beam)
+        self._check(self._lib.fpe_plan_beam_device(self._h, ptr(self.params), C.byref(bp) if bp is not None else None, C.c_void_p(d_poses_ptr),
+                                                   C.c_void_p(d_state_in_ptr) if d_state_in_ptr else None, int(B), C.c_void_p(d_options_ptr), int(M),
+                                                   C.byref(bo), C.c_void_p(stream or 0)))
+
     # ---- chained plan, device-resident (torch tensors / raw pointers) ----------------------------------
     def plan_device(self, d_poses_ptr, B, n_cycles, d_nominal_ptr=0, d_centroid_ptr=0, d_default_ptr=0,
                     d_cycle_ok_ptr=0, d_stance_ptr=0, stream=0, d_selected_ptr=0, d_pose_status_ptr=0, d_selected_packed_ptr=0,
