@@ -308,6 +308,60 @@ int fpe_upload_map_device(fpe_handle h, const fpe_map_desc* desc, const float* d
                           const float* d_elevation, void* stream);
 int fpe_map_info(fpe_handle h, fpe_map_desc* out); /* geometry of the current snapshot */
 
+/* ---- incremental map updates: the current snapshot shifted by whole cells, a few rectangles replaced ------------------------
+ * BUILD-DEFINED seam for a robot-centric map (elevation_mapping moves its map with grid_map::move: from one message to the next
+ * almost every cell keeps its value and only changes its index).  Instead of both full layers, the caller names the shift and hands
+ * over the rectangles whose values are new; one streaming pass on the device reads the old canonical layers and writes the new
+ * ones together with the bit planes.  Only the patches cross the host link.
+ *  - Content.  The base is the snapshot current at entry: rows, cols, resolution, canonical layers T0, E0.  The new snapshot has the
+ *    same size and resolution, position u->position, start index (0, 0), row-major.  For every cell (i, j), in this order:
+ *      1. if (i + sr, j + sc) lies inside the map, both layers take the base's value there, bit for bit;
+ *      2. otherwise both take the quiet NaN 0x7FC00000 (grid_map's cleared cell);
+ *      3. patches 0 .. n_patches - 1 are written over that in order: where two patches overlap, the later one wins.
+ *    |sr| >= rows or |sc| >= cols is valid: nothing is carried.
+ *  - Equivalence.  After the call every entry point behaves byte for byte as if fpe_upload_map had been called with those composed
+ *    canonical layers and {rows, cols, resolution, u->position, start (0,0), row-major} — fpe_map_info included.  The planes of
+ *    every threshold pair the base snapshot held are rebuilt for the new content in the same pass ("plans never pay for it" keeps
+ *    holding); a pair the base never saw is built lazily, as after an upload.  The engine derives nothing about the position from
+ *    shift and resolution: it takes the caller's doubles, so the geometry is rounded once, by the caller's grid_map.
+ *  - Where shift comes from.  It is the un-wrapped start-index difference of the circular buffer: canonical row i lives in buffer
+ *    row (i + s) mod rows, so a buffer whose start index goes from s_old to s_old + d, before wrapping, has shift = d — the index
+ *    shift grid_map::move computes (columns alike).  INTEGRATION.md shows the binding.
+ *  - Patch sources.  Element (r, c) of a rectangle lies at r * row_stride + c * col_stride, in floats, in one of two forms:
+ *    row-major with a pitch (col_stride == 1, row_stride >= n_cols), or column-major with a pitch (row_stride == 1, col_stride >=
+ *    n_rows) — a patch may point straight into a non-wrapping region of a column-major message buffer, which is what move's
+ *    newRegions are.  Anything else is refused.  Host sources may be freed on return, device sources once `stream` has passed
+ *    the call.
+ *  - Snapshot semantics: the upload's.  A plan that entered before the update keeps the base; the new snapshot becomes current
+ *    atomically; consumers on other streams wait GPU-side for its ready event; the update's own stream waits GPU-side for the base's
+ *    upload.  The device form reads the base asynchronously, so the base counts as read by an asynchronous launch (its buffers are
+ *    recycled only behind a device synchronisation of a later upload or update); no reference to the base outlives the call: there
+ *    is no chain of snapshots.  Updates of one engine serialise among themselves.  An update racing a full upload from another
+ *    thread: each is internally consistent, and the last to install wins.  The host form returns with the snapshot and its planes
+ *    complete, like fpe_upload_map.
+ *  - Refusals (nothing installed, queued or written).  FPE_E_NO_MAP before any upload.  FPE_E_INVALID_ARG for a null handle or
+ *    update, n_patches outside 0..FPE_UPDATE_MAX_PATCHES, reserved != 0, a non-finite position, an empty rectangle or one reaching
+ *    outside the map, a null layer pointer in a used patch, a stride pair of neither form.  fpe_map_update_validate is that same
+ *    routine without an engine: of `base` only rows and cols are read.
+ * Out of scope: a change of size or resolution (a full upload), the producer's filters on the dirty region only. */
+#define FPE_UPDATE_MAX_PATCHES 8
+typedef struct fpe_map_patch {        /* 48 bytes */
+    int32_t row0, col0, n_rows, n_cols;   /* rectangle in canonical indices of the NEW map; non-empty, inside it */
+    const float* traversability;          /* element (r, c) of the rectangle at r * row_stride + c * col_stride */
+    const float* elevation;               /* same strides */
+    int64_t row_stride, col_stride;       /* in floats; one of the two forms above */
+} fpe_map_patch;
+typedef struct fpe_map_update {       /* 416 bytes */
+    int32_t shift[2];      /* (sr, sc): new canonical cell (i, j) carries old canonical cell (i + sr, j + sc) */
+    double  position[2];   /* getPosition() of the new map */
+    int32_t n_patches;     /* 0..FPE_UPDATE_MAX_PATCHES */
+    int32_t reserved;      /* 0 */
+    fpe_map_patch patch[FPE_UPDATE_MAX_PATCHES];
+} fpe_map_update;
+int fpe_update_map(fpe_handle h, const fpe_map_update* u);                       /* patch pointers: HOST; synchronous */
+int fpe_update_map_device(fpe_handle h, const fpe_map_update* u, void* stream);  /* `u` on the host, patch pointers: DEVICE; asynchronous */
+int fpe_map_update_validate(const fpe_map_desc* base, const fpe_map_update* u);  /* host arithmetic only; no engine */
+
 /* ---- the producer of the map: elevation layer -> traversability layer -----------------
  * The reference starts leggedrobotics/traversability_estimation (launch/mapping.launch:12-13,
  * launch/all.launch:21-22, README.md:29) and subscribes to its output (cpp:188); package and filter
@@ -484,6 +538,8 @@ fpe_handle fpe_multi_engine(fpe_multi_handle h, int32_t k); /* engine of device 
 const char* fpe_multi_last_error(fpe_multi_handle h);
 int fpe_multi_upload_map(fpe_multi_handle h, const fpe_map_desc* desc, const float* traversability,
                          const float* elevation);
+/* fpe_update_map (the host form) on every engine of the group; every engine must hold a map of the same size */
+int fpe_multi_update_map(fpe_multi_handle h, const fpe_map_update* u);
 int fpe_multi_set_tuning(fpe_multi_handle h, const char* key, int32_t value);
 int fpe_multi_plan(fpe_multi_handle h, const fpe_params* params, const fpe_pose* poses, int32_t B, int32_t n_cycles,
                    const fpe_plan_out* out);

@@ -267,6 +267,21 @@ class BeamOut(C.Structure):
                 ("products", PlanOut)]
 
 
+UPDATE_MAX_PATCHES = 8  # FPE_UPDATE_MAX_PATCHES
+
+
+class MapPatch(C.Structure):
+    """fpe_map_patch: a rectangle of the NEW map and where its two layers lie (element (r, c) at r * row_stride + c * col_stride floats)."""
+    _fields_ = [("row0", C.c_int32), ("col0", C.c_int32), ("n_rows", C.c_int32), ("n_cols", C.c_int32), ("traversability", C.c_void_p),
+                ("elevation", C.c_void_p), ("row_stride", C.c_int64), ("col_stride", C.c_int64)]
+
+
+class MapUpdate(C.Structure):
+    """fpe_map_update: the current snapshot shifted by whole cells, with up to UPDATE_MAX_PATCHES rectangles replaced."""
+    _fields_ = [("shift", C.c_int32 * 2), ("position", C.c_double * 2), ("n_patches", C.c_int32), ("reserved", C.c_int32),
+                ("patch", MapPatch * UPDATE_MAX_PATCHES)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -279,7 +294,7 @@ STRUCTS = {
     "fpe_foothold_snap_out": FootholdSnapOut, "fpe_centroid_query": CentroidQuery, "fpe_centroid_map_out": CentroidMapOut,
     "fpe_pose_summary": PoseSummary, "fpe_rank_params": RankParams, "fpe_rank_out": RankOut, "fpe_layer_layout": LayerLayout,
     "fpe_layer_request": LayerRequest, "fpe_stride": STRIDE_DTYPE, "fpe_plan_state": PLAN_STATE_DTYPE,
-    "fpe_beam_params": BeamParams, "fpe_beam_out": BeamOut,
+    "fpe_beam_params": BeamParams, "fpe_beam_out": BeamOut, "fpe_map_patch": MapPatch, "fpe_map_update": MapUpdate,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -297,6 +312,9 @@ PROTOTYPES = {
     "fpe_upload_map": (cint, [vp, P(MapDesc), vp, vp]),
     "fpe_upload_map_device": (cint, [vp, P(MapDesc), vp, vp, vp]),
     "fpe_map_info": (cint, [vp, P(MapDesc)]),
+    "fpe_update_map": (cint, [vp, P(MapUpdate)]),
+    "fpe_update_map_device": (cint, [vp, P(MapUpdate), vp]),
+    "fpe_map_update_validate": (cint, [P(MapDesc), P(MapUpdate)]),
     "fpe_filter_params_defaults": (cint, [P(FilterParams)]),
     "fpe_traversability": (cint, [vp, P(MapDesc), P(FilterParams), vp, vp, vp]),
     "fpe_traversability_device": (cint, [vp, P(MapDesc), P(FilterParams), vp, vp, vp, vp]),
@@ -324,6 +342,7 @@ PROTOTYPES = {
     "fpe_multi_engine": (vp, [vp, i32]),
     "fpe_multi_last_error": (cstr, [vp]),
     "fpe_multi_upload_map": (cint, [vp, P(MapDesc), vp, vp]),
+    "fpe_multi_update_map": (cint, [vp, P(MapUpdate)]),
     "fpe_multi_set_tuning": (cint, [vp, cstr, i32]),
     "fpe_multi_plan": (cint, [vp, vp, vp, i32, i32, P(PlanOut)]),
     "fpe_multi_shard_range": (cint, [i32, i32, i32, P(i32), P(i32)]),

@@ -365,6 +365,7 @@ constexpr size_t kZeroCopyBytes = 64 * 1024;  // fpe_plan calls up to this size 
 struct fpe_engine {
     int device = 0;
     std::mutex mu;
+    std::mutex updateMu;  // fpe_update_map*: updates of one engine serialise among themselves (each takes the snapshot current at entry as its base)
     std::shared_ptr<MapSnapshot> map;
     std::shared_ptr<BufferPool> pool = std::make_shared<BufferPool>();
     CtxPool ctxPool;
@@ -1041,6 +1042,69 @@ int check_desc(const fpe_map_desc* d) {
     return FPE_OK;
 }
 
+// ---- what a full upload (upload_common) and an incremental update (update_common) share ----------------------------------------
+// A snapshot of this geometry with both layers from the pool, not yet filled.
+int new_snapshot(fpe_engine* h, int rows, int cols, double res, double posX, double posY, std::shared_ptr<MapSnapshot>& out) {
+    auto snap = std::make_shared<MapSnapshot>();
+    snap->g = fpe::make_geom(rows, cols, res, posX, posY);
+    snap->n = static_cast<size_t>(rows) * cols;
+    snap->pool = h->pool;
+    FPE_HIP(alloc_units(*h->pool, snap->n, &snap->d_trav, &snap->capTrav));
+    FPE_HIP(alloc_units(*h->pool, snap->n, &snap->d_elev, &snap->capElev));
+    out = std::move(snap);
+    return FPE_OK;
+}
+// Threshold pairs `cur` (the snapshot being replaced; may be null) was planned with: the new snapshot gets their planes at once.
+std::vector<std::pair<float, float>> carried_pairs(const std::shared_ptr<MapSnapshot>& cur) {
+    std::vector<std::pair<float, float>> pairs;
+    if (cur) {
+        std::lock_guard<std::mutex> lk(cur->mu);
+        for (auto& ms : cur->masks) pairs.emplace_back(ms->thrD, ms->thrC);
+    }
+    return pairs;
+}
+// The plane buffer of a pair whose planes are written by the kernel that moves the traversability layer.  That kernel writes the
+// buffer asynchronously: should any later step fail, the buffer goes back to the pool DIRTY (its next taker synchronises) — a dirty
+// return costs a synchronisation, a clean one of a buffer with work queued on it would be a race.  Cleared again by
+// folded_ready.
+int alloc_folded(MapSnapshot& snap, const std::pair<float, float>& pair, std::shared_ptr<MaskSet>& out) {
+    const int rc = alloc_mask(snap, pair.first, pair.second, false, out);
+    if (rc != FPE_OK) return rc;
+    out->asyncUsed.store(true, std::memory_order_release);
+    return FPE_OK;
+}
+// Behind the kernel that wrote `folded`: its event, and into the snapshot's sets.
+int folded_ready(MapSnapshot& snap, const std::shared_ptr<MaskSet>& folded, hipStream_t stream) {
+    const int rc = mask_ready(*folded, stream);
+    if (rc != FPE_OK) return rc;
+    // from here on ~MaskSet waits for `ready` (recorded behind the kernel that wrote the planes) before it gives the buffer back
+    folded->asyncUsed.store(false, std::memory_order_release);
+    folded->lastUse.store(++snap.useClock);
+    snap.masks.push_back(folded);
+    return FPE_OK;
+}
+// `snap`, filled on `stream` with its `ready` recorded, becomes the engine's current snapshot.
+int install_snapshot(fpe_engine* h, std::shared_ptr<MapSnapshot>& snap, bool hostForm, hipStream_t stream) {
+    // A host-buffer upload is synchronous already (the caller's arrays may be freed on return): it also waits for the planes it
+    // has just queued, so the snapshot it installs is COMPLETE and the first service call on the new map waits for nothing
+    // (bench.py service_latency_us: first_call_after_a_map was 16 us above steady_map — the plane build and its event on the
+    // call's critical path; the map stream is the 10-20 Hz path that can afford it).
+    if (hostForm && !snap->masks.empty()) {
+        FPE_HIP(hipStreamSynchronize(stream));
+        for (auto& ms : snap->masks) ms->readyDone.store(true, std::memory_order_release);
+    }
+    // (a host form has synchronised behind its copies and kernels: the snapshot is known complete — its first consumer need not ask the event)
+    if (hostForm) snap->readyDone.store(true, std::memory_order_release);
+    std::shared_ptr<MapSnapshot> old;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        old = std::move(h->map);
+        h->map = snap;  // readers holding the old snapshot keep it alive until they finish
+    }
+    old.reset();  // outside the engine lock: ~MapSnapshot may wait for the old snapshot's last asynchronous readers
+    return FPE_OK;
+}
+
 int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, const float* elev, bool srcOnDevice,
                   hipStream_t stream) {
     if (!h || !trav || !elev) return fail(FPE_E_INVALID_ARG, "null argument");
@@ -1048,12 +1112,9 @@ int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, co
     if (rc != FPE_OK) return rc;
     FPE_HIP(hipSetDevice(h->device));
     const size_t n = static_cast<size_t>(desc->rows) * desc->cols;
-    auto snap = std::make_shared<MapSnapshot>();
-    snap->g = fpe::make_geom(desc->rows, desc->cols, desc->resolution, desc->position[0], desc->position[1]);
-    snap->n = n;
-    snap->pool = h->pool;
-    FPE_HIP(alloc_units(*h->pool, n, &snap->d_trav, &snap->capTrav));
-    FPE_HIP(alloc_units(*h->pool, n, &snap->d_elev, &snap->capElev));
+    std::shared_ptr<MapSnapshot> snap;
+    rc = new_snapshot(h, desc->rows, desc->cols, desc->resolution, desc->position[0], desc->position[1], snap);
+    if (rc != FPE_OK) return rc;
     const bool canonical = desc->storage_order == 1 && desc->start_index[0] == 0 && desc->start_index[1] == 0;
     const float* src[2] = {trav, elev};
     float* dst[2] = {snap->d_trav, snap->d_elev};
@@ -1084,20 +1145,13 @@ int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, co
             std::lock_guard<std::mutex> lk(h->mu);
             cur = h->map;
         }
-        if (cur) {
-            std::lock_guard<std::mutex> lk(cur->mu);
-            for (auto& ms : cur->masks) pairs.emplace_back(ms->thrD, ms->thrC);
-        }
+        pairs = carried_pairs(cur);
     }
     std::shared_ptr<MaskSet> folded;
     const bool travThroughKernel = !canonical || srcOnDevice;
     if (!pairs.empty() && travThroughKernel && desc->rows < (1 << 24) - 2 && desc->cols < (1 << 24) - 64) {
-        rc = alloc_mask(*snap, pairs[0].first, pairs[0].second, false, folded);
+        rc = alloc_folded(*snap, pairs[0], folded);  // (the canonicalising kernel below writes it)
         if (rc != FPE_OK) return rc;
-        // the canonicalising kernel below writes this buffer asynchronously: should any later step of the upload fail, the buffer
-        // goes back to the pool DIRTY (its next taker synchronises) — a dirty return costs a synchronisation, a clean one of a
-        // buffer with work queued on it would be a race.  Cleared again once `ready` is recorded, below.
-        folded->asyncUsed.store(true, std::memory_order_release);
     }
     for (int l = 0; l < 2; ++l) {
         uint32_t* planeWords = (l == 0 && folded) ? folded->d_words : nullptr;
@@ -1121,12 +1175,8 @@ int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, co
     FPE_HIP(hipEventCreateWithFlags(&snap->ready, hipEventDisableTiming));
     FPE_HIP(hipEventRecord(snap->ready, stream));
     if (folded) {
-        rc = mask_ready(*folded, stream);
+        rc = folded_ready(*snap, folded, stream);
         if (rc != FPE_OK) return rc;
-        // from here on ~MaskSet waits for `ready` (recorded behind the kernel that wrote the planes) before it gives the buffer back
-        folded->asyncUsed.store(false, std::memory_order_release);
-        folded->lastUse.store(++snap->useClock);
-        snap->masks.push_back(folded);
     }
     for (size_t k = folded ? 1 : 0; k < pairs.size(); ++k) {
         std::shared_ptr<MaskSet> ms;
@@ -1135,24 +1185,104 @@ int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, co
         ms->lastUse.store(++snap->useClock);
         snap->masks.push_back(std::move(ms));
     }
-    // A host-buffer upload is synchronous already (the caller's arrays may be freed on return): it also waits for the planes it
-    // has just queued, so the snapshot it installs is COMPLETE and the first service call on the new map waits for nothing
-    // (bench.py service_latency_us: first_call_after_a_map was 16 us above steady_map — the plane build and its event on the
-    // call's critical path; the map stream is the 10-20 Hz path that can afford it).
-    if (!srcOnDevice && !snap->masks.empty()) {
-        FPE_HIP(hipStreamSynchronize(stream));
-        for (auto& ms : snap->masks) ms->readyDone.store(true, std::memory_order_release);
-    }
-    // (a host upload has synchronised behind each layer's copy: the snapshot is known complete — its first consumer need not ask the event)
-    if (!srcOnDevice) snap->readyDone.store(true, std::memory_order_release);
-    std::shared_ptr<MapSnapshot> old;
+    return install_snapshot(h, snap, !srcOnDevice, stream);
+}
+
+// fpe_update_map*: the snapshot current at entry shifted by whole cells, cleared where nothing is carried, the patches written over
+// that (include/fpe.h) — one launch of map_update_kernel, which also writes the planes of every pair the base was planned with.
+// Host form: the patches packed row-major into the call context's pinned arena (their strides resolved here), ONE host-to-device
+// copy, the kernel on the context's stream, one synchronisation.  Device form: the caller's patch arrays as they are, on `stream`.
+int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipStream_t stream) {
+    if (!h || !u) return fail(FPE_E_INVALID_ARG, "null handle or update");
+    std::lock_guard<std::mutex> serial(h->updateMu);
+    // (declared ahead of the lease: on an early exit the lease waits for its stream BEFORE the snapshots are released, as in HostCall)
+    CallPlan baseRef;
+    std::shared_ptr<MapSnapshot>& base = baseRef.snap;
+    std::shared_ptr<MapSnapshot> snap;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        old = std::move(h->map);
-        h->map = snap;  // readers holding the old snapshot keep it alive until they finish
+        base = h->map;
     }
-    old.reset();  // outside the engine lock: ~MapSnapshot may wait for the old snapshot's last asynchronous readers
-    return FPE_OK;
+    if (!base) return fail(FPE_E_NO_MAP, "no map uploaded");
+    const int rows = base->g.rows, cols = base->g.cols;
+    const char* why = "";
+    int rc = fpe::check_map_update(rows, cols, u, &why);
+    if (rc != FPE_OK) return fail(rc, why);
+    FPE_HIP(hipSetDevice(h->device));
+    rc = new_snapshot(h, rows, cols, base->g.res, u->position[0], u->position[1], snap);
+    if (rc != FPE_OK) return rc;
+
+    fpe::MapUpdateArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.baseTrav = reinterpret_cast<const uint32_t*>(base->d_trav);
+    a.baseElev = reinterpret_cast<const uint32_t*>(base->d_elev);
+    a.dstTrav = reinterpret_cast<uint32_t*>(snap->d_trav);
+    a.dstElev = reinterpret_cast<uint32_t*>(snap->d_elev);
+    a.rows = rows;
+    a.cols = cols;
+    a.sr = std::max(-rows, std::min(rows, u->shift[0]));  // beyond +-rows nothing is carried either way
+    a.sc = std::max(-cols, std::min(cols, u->shift[1]));
+    a.nPatches = u->n_patches;
+    std::unique_ptr<CtxLease> lease;
+    if (srcOnDevice) {
+        for (int k = 0; k < u->n_patches; ++k) {
+            const fpe_map_patch& p = u->patch[k];
+            a.patch[k] = fpe::MapUpdatePatch{p.row0, p.col0, p.n_rows, p.n_cols, reinterpret_cast<const uint32_t*>(p.traversability),
+                                             reinterpret_cast<const uint32_t*>(p.elevation), p.row_stride, p.col_stride};
+        }
+    } else {
+        lease.reset(new CtxLease(h->ctxPool));
+        CallCtx& cx = *lease->ctx;
+        size_t cells = 0;
+        for (int k = 0; k < u->n_patches; ++k) cells += static_cast<size_t>(u->patch[k].n_rows) * u->patch[k].n_cols;
+        const size_t bytes = 2 * cells * sizeof(float);
+        FPE_HIP(cx.reserve(bytes));
+        stream = cx.stream;
+        float* hp = reinterpret_cast<float*>(cx.pinned);
+        size_t off = 0;
+        for (int k = 0; k < u->n_patches; ++k) {
+            const fpe_map_patch& p = u->patch[k];
+            const size_t pn = static_cast<size_t>(p.n_rows) * p.n_cols;
+            const float* src[2] = {p.traversability, p.elevation};
+            for (int l = 0; l < 2; ++l)
+                for (int r = 0; r < p.n_rows; ++r) {
+                    float* row = hp + off + l * pn + static_cast<size_t>(r) * p.n_cols;
+                    if (p.col_stride == 1) std::memcpy(row, src[l] + r * p.row_stride, static_cast<size_t>(p.n_cols) * sizeof(float));
+                    else
+                        for (int c = 0; c < p.n_cols; ++c) row[c] = src[l][r * p.row_stride + c * p.col_stride];
+                }
+            const uint32_t* dp = reinterpret_cast<const uint32_t*>(cx.dev) + off;
+            a.patch[k] = fpe::MapUpdatePatch{p.row0, p.col0, p.n_rows, p.n_cols, dp, dp + pn, p.n_cols, 1};
+            off += 2 * pn;
+        }
+        cx.inFlight = true;
+        if (bytes) FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, bytes, hipMemcpyHostToDevice, stream));
+    }
+    FPE_HIP(base->wait_ready(stream));  // the update's stream behind the base's upload
+    // the device form reads the base asynchronously and keeps no reference past this call: the base counts as read by an
+    // asynchronous launch, so its buffers (and, through ~MapSnapshot, its planes) are recycled only behind a device synchronisation
+    if (srcOnDevice) mark_async_launch(baseRef);
+    const std::vector<std::pair<float, float>> pairs = carried_pairs(base);
+    std::vector<std::shared_ptr<MaskSet>> folded(pairs.size());
+    a.nPairs = static_cast<int32_t>(std::min<size_t>(pairs.size(), fpe::kUpdateMaxPairs));
+    for (int k = 0; k < a.nPairs; ++k) {
+        rc = alloc_folded(*snap, pairs[static_cast<size_t>(k)], folded[static_cast<size_t>(k)]);
+        if (rc != FPE_OK) return rc;
+        a.pair[k] = fpe::MapUpdatePair{reinterpret_cast<uint4*>(folded[static_cast<size_t>(k)]->d_words), pairs[static_cast<size_t>(k)].first,
+                                       pairs[static_cast<size_t>(k)].second};
+    }
+    FPE_HIP(fpe::launch_map_update(a, stream));
+    FPE_HIP(hipEventCreateWithFlags(&snap->ready, hipEventDisableTiming));
+    FPE_HIP(hipEventRecord(snap->ready, stream));
+    for (int k = 0; k < a.nPairs; ++k) {
+        rc = folded_ready(*snap, folded[static_cast<size_t>(k)], stream);
+        if (rc != FPE_OK) return rc;
+    }
+    if (!srcOnDevice) {  // host sources may be freed on return — and the arena goes back to the pool
+        FPE_HIP(hipStreamSynchronize(stream));
+        lease->ctx->inFlight = false;
+    }
+    return install_snapshot(h, snap, !srcOnDevice, stream);
 }
 
 }  // namespace
@@ -1321,6 +1451,12 @@ int fpe_upload_map(fpe_handle h, const fpe_map_desc* desc, const float* traversa
 int fpe_upload_map_device(fpe_handle h, const fpe_map_desc* desc, const float* d_traversability,
                           const float* d_elevation, void* stream) {
     return upload_common(h, desc, d_traversability, d_elevation, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_update_map(fpe_handle h, const fpe_map_update* u) { return update_common(h, u, false, nullptr); }
+
+int fpe_update_map_device(fpe_handle h, const fpe_map_update* u, void* stream) {
+    return update_common(h, u, true, static_cast<hipStream_t>(stream));
 }
 
 int fpe_filter_params_defaults(fpe_filter_params* out) {

@@ -628,4 +628,37 @@ int fpe_plan_state_from_feet(const double feet_xy[4][2], double adjusted_y, int3
     return FPE_OK;
 }
 
+int fpe_map_update_validate(const fpe_map_desc* base, const fpe_map_update* u) {
+    if (!base) return FPE_E_INVALID_ARG;
+    const char* why = nullptr;
+    return fpe::check_map_update(base->rows, base->cols, u, &why);
+}
+
 }  // extern "C"
+
+namespace fpe {
+
+int check_map_update(int rows, int cols, const fpe_map_update* u, const char** why) {
+    auto bad = [&](const char* msg) {
+        *why = msg;
+        return static_cast<int>(FPE_E_INVALID_ARG);
+    };
+    if (!u) return bad("null map update");
+    if (rows <= 0 || cols <= 0) return bad("map size out of range");
+    if (u->n_patches < 0 || u->n_patches > FPE_UPDATE_MAX_PATCHES) return bad("n_patches out of range");
+    if (u->reserved != 0) return bad("reserved must be 0");
+    if (!std::isfinite(u->position[0]) || !std::isfinite(u->position[1])) return bad("bad position");
+    for (int k = 0; k < u->n_patches; ++k) {
+        const fpe_map_patch& p = u->patch[k];
+        if (p.n_rows <= 0 || p.n_cols <= 0) return bad("empty patch rectangle");
+        if (p.row0 < 0 || p.col0 < 0 || static_cast<int64_t>(p.row0) + p.n_rows > rows || static_cast<int64_t>(p.col0) + p.n_cols > cols)
+            return bad("patch rectangle outside the map");
+        if (!p.traversability || !p.elevation) return bad("null patch layer");
+        const bool rowMajor = p.col_stride == 1 && p.row_stride >= p.n_cols;
+        const bool colMajor = p.row_stride == 1 && p.col_stride >= p.n_rows;
+        if (!rowMajor && !colMajor) return bad("patch strides are neither row-major nor column-major with a pitch");
+    }
+    return FPE_OK;
+}
+
+}  // namespace fpe

@@ -49,6 +49,34 @@ hipError_t launch_centroid_legs(const DevMap& m, const PlanConsts& pc, float def
                                 fpe_centroid_foothold* d_out, hipStream_t stream);
 hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int cols, int si, int sj, int srcRowMajor, hipStream_t stream,
                                uint32_t* d_planeWords = nullptr, float thrDefault = 0.0f, float thrCandidate = 0.0f);
+// ---- incremental map update (fpe_mapupdate.hpp) ----------------------------------------------------------------
+// The argument block of map_update_kernel: the base snapshot's canonical layers, the new snapshot's, the shift (clamped by the
+// engine to |sr| <= rows, |sc| <= cols: the same content, and i + sr cannot overflow), the patches in the order they are applied
+// (device pointers; element (r, c) at r * rowStride + c * colStride) and the plane buffers of the carried threshold pairs.
+// Layers travel as 32-bit patterns.
+constexpr int kUpdateMaxPairs = 4;  // the sets a snapshot keeps (acquire_mask)
+struct MapUpdatePatch {
+    int32_t row0, col0, nr, nc;
+    const uint32_t* trav;
+    const uint32_t* elev;
+    int64_t rowStride, colStride;
+};
+struct MapUpdatePair {
+    uint4* words;  // bitmap_words(rows, cols) units, padding zeroed by launch_map_update
+    float thrD, thrC;
+};
+struct MapUpdateArgs {
+    const uint32_t* baseTrav;
+    const uint32_t* baseElev;
+    uint32_t* dstTrav;
+    uint32_t* dstElev;
+    int32_t rows, cols, sr, sc;
+    int32_t nPatches, nPairs;
+    int32_t strideW, nw;  // set by launch_map_update
+    MapUpdatePair pair[kUpdateMaxPairs];
+    MapUpdatePatch patch[FPE_UPDATE_MAX_PATCHES];
+};
+hipError_t launch_map_update(const MapUpdateArgs& a, hipStream_t stream);
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes);
 size_t plan_lds_bytes(const PlanConsts& pc);
 size_t search_lds_bytes(const PlanConsts& pc);

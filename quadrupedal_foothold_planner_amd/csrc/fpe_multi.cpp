@@ -348,6 +348,11 @@ int fpe_multi_upload_map(fpe_multi_handle h, const fpe_map_desc* desc, const flo
     return for_each_device(h, [&](int k) { return fpe_upload_map(h->engines[static_cast<size_t>(k)], desc, traversability, elevation); });
 }
 
+int fpe_multi_update_map(fpe_multi_handle h, const fpe_map_update* u) {
+    if (!h) return mfail(nullptr, FPE_E_INVALID_ARG, "null handle");
+    return for_each_device(h, [&](int k) { return fpe_update_map(h->engines[static_cast<size_t>(k)], u); });
+}
+
 int fpe_multi_set_tuning(fpe_multi_handle h, const char* key, int32_t value) {
     if (!h) return mfail(nullptr, FPE_E_INVALID_ARG, "null handle");
     if (key && std::string(key) == "gather_padded") {  // the group's own knob (tests: the uneven batches' path on an even batch)

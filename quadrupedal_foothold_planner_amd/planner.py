@@ -109,6 +109,41 @@ def _map_desc(rows, cols, resolution, position=(0.0, 0.0), start_index=(0, 0), s
                    (C.c_int32 * 2)(*map(int, start_index)), 1 if storage_order == "row" else 0)
 
 
+def make_map_update(shift, position, patches):
+    """An fpe_map_update from raw patches (row0, col0, n_rows, n_cols, traversability address, elevation address, row_stride,
+    col_stride), strides in floats.  More than UPDATE_MAX_PATCHES patches cannot be expressed: ValueError."""
+    if len(patches) > _capi.UPDATE_MAX_PATCHES:
+        raise ValueError(f"an update takes at most {_capi.UPDATE_MAX_PATCHES} patches")
+    u = _capi.MapUpdate()
+    u.shift[0], u.shift[1] = int(shift[0]), int(shift[1])
+    u.position[0], u.position[1] = float(position[0]), float(position[1])
+    u.n_patches = len(patches)
+    for k, (row0, col0, n_rows, n_cols, t, e, rs, cs) in enumerate(patches):
+        u.patch[k] = _capi.MapPatch(int(row0), int(col0), int(n_rows), int(n_cols), t, e, int(rs), int(cs))
+    return u
+
+
+def _host_patches(patches):
+    """[(row0, col0, traversability, elevation), ...] with 2-D arrays or views of one shape (n_rows, n_cols) -> raw patches and the
+    arrays they point into.  The strides are the arrays' own where both layers share one of the two forms of fpe_map_patch (row-
+    or column-major with a pitch: a view into a message buffer goes as it is); anything else is copied to a packed array first."""
+    raw, keep = [], []
+    for row0, col0, trav, elev in patches:
+        t, e = np.asarray(trav), np.asarray(elev)
+        if t.ndim != 2 or t.shape != e.shape:
+            raise ValueError("a patch is two 2-D arrays of one shape")
+        n_rows, n_cols = t.shape
+        rs, cs = (t.strides[0] // 4, t.strides[1] // 4) if n_rows and n_cols else (0, 0)
+        direct = (t.dtype == np.float32 and e.dtype == np.float32 and t.strides == e.strides and t.strides[0] % 4 == 0 and t.strides[1] % 4 == 0
+                  and ((cs == 1 and rs >= n_cols) or (rs == 1 and cs >= n_rows)))
+        if not direct and n_rows and n_cols:
+            t, e = np.ascontiguousarray(t, dtype=np.float32), np.ascontiguousarray(e, dtype=np.float32)
+            rs, cs = n_cols, 1
+        keep += [t, e]
+        raw.append((row0, col0, n_rows, n_cols, t.ctypes.data, e.ctypes.data, rs, cs))
+    return raw, keep
+
+
 class _Handle:
     """What an engine and a group of engines share: the handle's creation, close / __del__, and the status check.  A subclass names
     its three entry points."""
@@ -180,6 +215,22 @@ class FootholdPlanner(_Handle):
         self._check(self._lib.fpe_upload_map_device(self._h, C.byref(d), C.c_void_p(d_trav_ptr), C.c_void_p(d_elev_ptr),
                                                     C.c_void_p(stream or 0)))
         self.rows, self.cols, self.resolution = rows, cols, float(resolution)
+
+    def update_map(self, shift, position, patches=()):
+        """fpe_update_map: the current snapshot shifted by `shift` = (sr, sc) whole cells (new cell (i, j) carries old cell
+        (i + sr, j + sc); cells without a source are cleared to NaN), then `patches` = [(row0, col0, traversability, elevation), ...]
+        written over it in order — host arrays or views of shape (n_rows, n_cols), read with their own strides.  `position`: the new
+        map's getPosition().  Synchronous."""
+        raw, keep = _host_patches(patches)
+        u = make_map_update(shift, position, raw)
+        self._check(self._lib.fpe_update_map(self._h, C.byref(u)))
+        del keep
+
+    def update_map_device(self, shift, position, patches=(), stream=None):
+        """fpe_update_map_device: `patches` = [(row0, col0, n_rows, n_cols, d_traversability_ptr, d_elevation_ptr, row_stride,
+        col_stride), ...] with DEVICE addresses and strides in floats; asynchronous on `stream`."""
+        u = make_map_update(shift, position, list(patches))
+        self._check(self._lib.fpe_update_map_device(self._h, C.byref(u), C.c_void_p(stream or 0)))
 
     # ---- the producer of the map (SURVEY §8(f) N3; launch/mapping.launch:12-13) ----------------------
     def filter_params(self, **overrides):
@@ -766,6 +817,13 @@ class MultiFootholdPlanner(_Handle):
         rows, cols = trav.shape
         d = _map_desc(rows, cols, resolution, position)
         self._check(self._lib.fpe_multi_upload_map(self._h, C.byref(d), ptr(trav), ptr(elev)))
+
+    def update_map(self, shift, position, patches=()):
+        """fpe_multi_update_map: FootholdPlanner.update_map on every engine of the group."""
+        raw, keep = _host_patches(patches)
+        u = make_map_update(shift, position, raw)
+        self._check(self._lib.fpe_multi_update_map(self._h, C.byref(u)))
+        del keep
 
     def engine(self, k):
         return self._lib.fpe_multi_engine(self._h, int(k))

@@ -1,0 +1,408 @@
+"""Incremental map updates (fpe_update_map*, map_update_kernel) against the oracle on the COMPOSED map of
+tests/map_update_reference.py: the base is one of ingest_reference's hostile maps, the patch values come from other hostile maps of
+the same shape (so every special value can arrive by patch), and every cell of every map (at most 16 384) is compared.
+
+The observers are the ingest suite's (tests/test_gpu_ingest.py), on the updated snapshot:
+  1. foothold_map() with the yaml footRadius reads the bit planes — written by the update kernel for every pair the base held;
+  2. foothold_map() with footRadius 0 reads the two float layers;
+  3. the 48 edge poses x 4 cycles on a plan_bits_* kernel;
+  4. observers 1 and 2 byte-identical to a fresh engine that received the composed map by fpe_upload_map.
+The conditions a case rests on (cells carried, cleared and patched; every patch changes a plane class and an elevation; overlapping
+patches differ) are asserted on the CPU while the case is built, so that a case cannot pass by showing nothing."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import fpo
+from quadrupedal_foothold_planner_amd import _capi
+from quadrupedal_foothold_planner_amd.planner import FootholdPlanner, FpeError, MultiFootholdPlanner, make_map_update
+from tests import ingest_reference as ir
+from tests import map_update_reference as mu
+from tests import util
+from tests.test_gpu_foothold_map import all_cells, oracle_cells
+from tests.test_gpu_ingest import (N_CYCLES, DeviceSide, assert_cells_equal, assert_same_bytes, check_observers, edge_poses, observe_host,
+                                   params_for)
+
+pytestmark = pytest.mark.gpu
+
+RES = ir.RES
+YAML = ir.YAML_PAIR
+PAIRS = ir.HISTORY_PAIRS[:3]  # the pair history of these tests; the hostile maps carry the categories of all three
+NEW_POS = (0.26, -0.14)      # getPosition() of every updated map (the bases lie at the origin)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+class MapRef:
+    """A canonical map at a position with the oracle's answers on it, each computed once (the interface check_observers reads)."""
+
+    def __init__(self, trav, elev, position, seed):
+        self.trav, self.elev, self.position = np.ascontiguousarray(trav), np.ascontiguousarray(elev), position
+        self.rows, self.cols = trav.shape
+        self.omap = fpo.OracleMap(self.trav, self.elev, RES, position=position)
+        self.poses = edge_poses(self.rows, self.cols, seed)
+        self.poses["position"][:, 0] += position[0]
+        self.poses["position"][:, 1] += position[1]
+        self._cells, self._plans, self._fresh = {}, {}, {}
+
+    def cells(self, pair, foot_radius=None):
+        key = (np.float32(pair[0]).tobytes(), np.float32(pair[1]).tobytes(), foot_radius)
+        if key not in self._cells:
+            f, h = oracle_cells(self.omap, params_for(pair, foot_radius), all_cells(self.rows, self.cols))
+            self._cells[key] = {"flags": f.reshape(self.rows, self.cols), "height": h.reshape(self.rows, self.cols)}
+        return self._cells[key]
+
+    def plan(self, pair, poses=None):
+        poses = self.poses if poses is None else poses
+        key = (pair, poses.tobytes())
+        if key not in self._plans:
+            op, opo = util.to_oracle_params(params_for(pair)), util.to_oracle_poses(poses)
+            ora = self.omap.plan(op, opo, N_CYCLES, threads=8)
+            ora["pose_status"] = self.omap.pose_status(op, opo)
+            self._plans[key] = ora
+        return self._plans[key]
+
+    def fresh(self, pair):
+        """Observers 1 and 2 of a fresh engine that received this map by fpe_upload_map (observer 4's other side)."""
+        if pair not in self._fresh:
+            planner = FootholdPlanner(0)
+            try:
+                planner.gridmapCallback(self.trav, self.elev, RES, position=self.position)
+                obs = observe_host(planner, pair)
+                check_observers(obs, self, pair, "fresh upload of the composed map")
+                self._fresh[pair] = obs
+            finally:
+                planner.close()
+        return self._fresh[pair]
+
+
+_BASES, _CASES = {}, {}
+
+
+def base(rows, cols):
+    """(the base map, the hostile maps the patch values are cut from) of a shape."""
+    if (rows, cols) not in _BASES:
+        starts = ir.start_indices(rows, cols)
+        maps = [ir.hostile_map(rows, cols, RES, rows * 1000 + cols + 50 + k, PAIRS, starts)[:2] for k in range(7)]
+        # (the last source is flat ground: the hostile maps all put NaN into the one corner cell of a single-row or single-column
+        # map, which is also what a cleared cell holds — a 1 x 1 patch there would show nothing)
+        flat = (np.full((rows, cols), 0.5, np.float32), np.full((rows, cols), 0.25, np.float32))
+        _BASES[(rows, cols)] = (MapRef(maps[0][0], maps[0][1], (0.0, 0.0), rows + cols), maps[1:] + [flat])
+    return _BASES[(rows, cols)]
+
+
+class Case:
+    """One update: the base, the shift, the patch values, the composed map, and the CPU-side conditions on them."""
+
+    def __init__(self, rows, cols, shift, rects, base_ref=None, sources=None, first_source=0):
+        b, srcs = base(rows, cols)
+        self.base = base_ref or b
+        srcs = sources or srcs
+        self.rows, self.cols, self.shift, self.rects = rows, cols, shift, rects
+        cur_t, cur_e = mu.compose(self.base.trav, self.base.elev, shift, [])
+        cur_t, cur_e = cur_t.copy(), cur_e.copy()
+        self.carried = mu.carried_mask(rows, cols, shift)
+        self.n_carried = int(self.carried.sum())
+        assert self.n_carried == max(0, rows - abs(shift[0])) * max(0, cols - abs(shift[1]))
+        assert int(((bits(cur_t) == mu.CLEARED) & ~self.carried).sum()) == rows * cols - self.n_carried  # every cell not carried is cleared
+        self.values = []
+        self.patched = np.zeros((rows, cols), bool)
+        for k, (r0, c0, nr, nc) in enumerate(rects):
+            sl = (slice(r0, r0 + nr), slice(c0, c0 + nc))
+            # the first source whose values change a plane class and an elevation in this rectangle, and differ from every
+            # earlier patch where they overlap
+            for q in range(len(srcs)):
+                st, se = srcs[(first_source + k + q) % len(srcs)]
+                vt, ve = st[sl].copy(), se[sl].copy()
+                ok = (mu.plane_class(vt, YAML) != mu.plane_class(cur_t[sl], YAML)).any() and (bits(ve) != bits(cur_e[sl])).any()
+                for (p0, q0, pr, pc), (pt, pe) in zip(rects[:k], self.values):
+                    i0, i1, j0, j1 = max(r0, p0), min(r0 + nr, p0 + pr), max(c0, q0), min(c0 + nc, q0 + pc)
+                    if i0 < i1 and j0 < j1:
+                        mine, theirs = vt[i0 - r0:i1 - r0, j0 - c0:j1 - c0], pt[i0 - p0:i1 - p0, j0 - q0:j1 - q0]
+                        ok = ok and (bits(mine) != bits(theirs)).any()
+                if ok:
+                    break
+            else:
+                raise AssertionError(f"no source makes patch {k} {rects[k]} visible")
+            cur_t[sl], cur_e[sl] = vt, ve
+            self.patched[sl] = True
+            self.values.append((vt, ve))
+        trav, elev = mu.compose(self.base.trav, self.base.elev, shift, [(r[0], r[1], v[0], v[1]) for r, v in zip(rects, self.values)])
+        assert np.array_equal(bits(trav), bits(cur_t)) and np.array_equal(bits(elev), bits(cur_e))
+        self.n_patched = int(self.patched.sum())
+        self.n_filled = int((~self.carried & ~self.patched).sum())
+        self.new = MapRef(trav, elev, NEW_POS, rows + cols + 1)
+
+    def patches(self, form="packed"):
+        return [(r[0], r[1], mu.patch_source(vt, form, self.rows, self.cols, r[0], r[1]), mu.patch_source(ve, form, self.rows, self.cols, r[0], r[1]))
+                for r, (vt, ve) in zip(self.rects, self.values)]
+
+
+def case(rows, cols, shift, set_name):
+    key = (rows, cols, shift, set_name)
+    if key not in _CASES:
+        c = Case(rows, cols, shift, mu.patch_set_rects(set_name, rows, cols, shift))
+        total = rows * cols
+        # the regions have the cell counts the set intends
+        if set_name == "none":
+            assert c.n_patched == 0 and c.n_filled == total - c.n_carried
+        elif set_name == "bands":
+            assert c.n_patched == total - c.n_carried and c.n_filled == 0 and not (c.patched & c.carried).any()
+            assert (c.n_patched > 0) == (shift != (0, 0))
+        elif set_name == "interior":
+            assert c.n_patched > 0 and not (c.patched & ~c.carried).any() and c.n_filled == total - c.n_carried > 0
+        elif set_name == "overlap":
+            (a0, a1, ar, ac), (b0, b1, br, bc) = c.rects
+            assert 0 < c.n_patched < ar * ac + br * bc
+        elif set_name == "corner":
+            assert c.n_patched == 1 and c.patched[-1, -1]
+        elif set_name == "lastword":
+            nw = (cols + 31) // 32
+            assert c.patched[((np.arange(rows) + 1) >> 3) == (rows >> 3)][:, 32 * (nw - 1):].all()
+            assert rows * cols > c.n_patched and (c.rects[0][0] == 0 or not c.patched[c.rects[0][0] - 1].any())
+        elif set_name == "whole":
+            assert c.n_patched == total and c.n_filled == 0
+        elif set_name == "eight":
+            assert len(c.rects) == _capi.UPDATE_MAX_PATCHES and 0 < c.n_patched < sum(r[2] * r[3] for r in c.rects)  # some of them overlap
+        _CASES[key] = c
+    return _CASES[key]
+
+
+def upload_base(planner, c, pairs=(YAML,)):
+    """The base by fpe_upload_map, then observer 1 for each pair: the base snapshot holds their planes, so the update rebuilds them."""
+    planner.gridmapCallback(c.base.trav, c.base.elev, RES)
+    for pair in pairs:
+        assert_cells_equal(observe_host(planner, pair, layers=False)["bits"], c.base.cells(pair), f"the base, pair {pair}")
+
+
+def check_updated(planner, c, pair, what, poses=True):
+    info = planner.map_info()
+    assert (info["rows"], info["cols"], info["resolution"], info["position"]) == (c.rows, c.cols, RES, NEW_POS)
+    obs = observe_host(planner, pair, c.new.poses if poses else None)
+    check_observers(obs, c.new, pair, what)
+    assert_same_bytes(obs, c.new.fresh(pair), what)
+    return obs
+
+
+def run_host(rows, cols, shift, set_name, form):
+    c = case(rows, cols, shift, set_name)
+    planner = FootholdPlanner(0)
+    try:
+        upload_base(planner, c)
+        planner.update_map(shift, NEW_POS, c.patches(form))
+        check_updated(planner, c, YAML, f"{rows} x {cols}, shift {shift}, patches {set_name} ({form})")
+    finally:
+        planner.close()
+
+
+# ---- A. every shift, with the uncovered bands as patches -----------------------------------------------------------------------------
+def _shift_cases():
+    for rows, cols in mu.FULL_SHAPES + mu.SMALL_SHAPES:
+        for shift in mu.shifts(rows, cols):
+            yield rows, cols, shift
+
+
+@pytest.mark.parametrize("rows,cols,shift", list(_shift_cases()), ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_shift_with_band_patches(rows, cols, shift):
+    run_host(rows, cols, shift, "bands", "packed")
+
+
+# ---- B. every patch set, once per source form ----------------------------------------------------------------------------------------
+def _patch_cases():
+    for rows, cols in mu.FULL_SHAPES:
+        for name in mu.PATCH_SETS:
+            for form in mu.FORMS if name != "none" else ("packed",):
+                yield rows, cols, mu.PATCH_SHIFT, name, form
+    for rows, cols in mu.SMALL_SHAPES:  # the degenerate paths: single rows and columns of patches, in every form
+        for name in ("none", "corner", "whole"):
+            for form in mu.FORMS if name != "none" else ("packed",):
+                yield rows, cols, (1 if rows > 1 else 0, -1 if cols > 1 else 0), name, form
+
+
+@pytest.mark.parametrize("rows,cols,shift,name,form", list(_patch_cases()), ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_patch_set_and_source_form(rows, cols, shift, name, form):
+    run_host(rows, cols, shift, name, form)
+
+
+# ---- C. pair history ---------------------------------------------------------------------------------------------------------------
+def test_pairs_of_the_base_are_rebuilt_by_the_update():
+    rows, cols = ir.HISTORY_SHAPE
+    c = case(rows, cols, mu.PATCH_SHIFT, "eight")
+    for a, b in zip(PAIRS, PAIRS[1:] + PAIRS[:1]):  # a stale or swapped set would show
+        assert (c.new.cells(a)["flags"] != c.new.cells(b)["flags"]).mean() >= 0.01, (a, b)
+        assert (c.new.cells(a)["flags"] != c.base.cells(a)["flags"]).mean() >= 0.01, a
+    planner = FootholdPlanner(0)
+    try:
+        upload_base(planner, c, PAIRS)
+        planner.update_map(c.shift, NEW_POS, c.patches("colmajor"))
+        for pair in PAIRS:
+            check_updated(planner, c, pair, f"three pairs carried through an update, pair {pair}")
+    finally:
+        planner.close()
+
+
+def test_update_at_once_after_an_upload_builds_the_planes_lazily():
+    c = case(*ir.HISTORY_SHAPE, mu.PATCH_SHIFT, "eight")
+    planner = FootholdPlanner(0)
+    try:
+        planner.gridmapCallback(c.base.trav, c.base.elev, RES)
+        planner.update_map(c.shift, NEW_POS, c.patches("pitched"))
+        check_updated(planner, c, YAML, "no pair in the base's history")
+    finally:
+        planner.close()
+
+
+# ---- D. a walk -----------------------------------------------------------------------------------------------------------------------
+def test_a_walk_of_five_updates():
+    rows, cols, step = 65, 63, (-2, 1)
+    b, srcs = base(rows, cols)
+    planner = FootholdPlanner(0)
+    try:
+        planner.gridmapCallback(b.trav, b.elev, RES)
+        observe_host(planner, YAML, layers=False)
+        cur = b
+        for k in range(5):
+            c = Case(rows, cols, step, mu.band_rects(rows, cols, step), base_ref=cur, first_source=k)
+            assert c.n_patched == rows * cols - c.n_carried > 0
+            planner.update_map(step, NEW_POS, c.patches(mu.FORMS[k % 3]))
+            cur = c.new
+        # what the first cell of the base has become: five steps further
+        assert bits(cur.trav)[10, 0] == bits(b.trav)[0, 5]
+        check_updated(planner, c, YAML, "five updates of (-2, 1)")
+    finally:
+        planner.close()
+
+
+# ---- E. device form --------------------------------------------------------------------------------------------------------------------
+def device_patches(dev, patches):
+    """The patch sources copied to the device with their layout (the whole buffer a view points into), as raw patches."""
+    torch, raw = dev.torch, []
+    for row0, col0, t, e in patches:
+        addr = []
+        for v in (t, e):
+            root = v
+            while root.base is not None:
+                root = root.base
+            d = torch.from_numpy(np.ascontiguousarray(root).reshape(-1)).cuda()
+            dev.keep.append(d)
+            addr.append(d.data_ptr() + (v.ctypes.data - root.ctypes.data))
+        raw.append((row0, col0, t.shape[0], t.shape[1], addr[0], addr[1], t.strides[0] // 4, t.strides[1] // 4))
+    torch.cuda.synchronize()  # the sources are in HBM; from here on the host waits for nothing
+    return raw
+
+
+def upload_base_device(dev, planner, c):
+    torch = dev.torch
+    d_t, d_e = torch.from_numpy(c.base.trav.reshape(-1)).cuda(), torch.from_numpy(c.base.elev.reshape(-1)).cuda()
+    torch.cuda.synchronize()
+    dev.keep += [d_t, d_e]
+    planner.upload_map_device(d_t.data_ptr(), d_e.data_ptr(), c.rows, c.cols, RES, stream=dev.up.cuda_stream)
+
+
+@pytest.mark.parametrize("rows,cols", mu.FULL_SHAPES, ids=lambda v: str(v))
+@pytest.mark.parametrize("name,form", [("bands", "packed"), ("eight", "colmajor"), ("overlap", "pitched"), ("none", "packed")])
+def test_device_form_with_no_host_wait(name, form, rows, cols):
+    """Upload and update on stream `up` with device patch arrays, the base's pair registered by a call on `side`; the observers on
+    `side`: nothing between the upload and the last observer waits for the GPU."""
+    c = case(rows, cols, mu.PATCH_SHIFT, name)
+    planner = FootholdPlanner(0)
+    try:
+        dev = DeviceSide()
+        d_poses = dev.poses(c.new.poses)
+        raw = device_patches(dev, c.patches(form))
+        upload_base_device(dev, planner, c)
+        before = dev.queue_map(planner, YAML, (rows, cols))  # the base snapshot now holds the pair
+        planner.update_map_device(c.shift, NEW_POS, raw, stream=dev.up.cuda_stream)
+        obs = dev.observe(planner, c.new, YAML, d_poses)
+        what = f"device form, {rows} x {cols}, patches {name} ({form})"
+        assert_cells_equal(dev.fetch_map(before, (rows, cols)), c.base.cells(YAML), what + ": the base")
+        check_observers(obs, c.new, YAML, what)
+        assert_same_bytes(obs, c.new.fresh(YAML), what)
+    finally:
+        planner.close()
+
+
+def test_a_plan_queued_before_the_update_keeps_the_base():
+    rows, cols = 127, 100
+    c = case(rows, cols, mu.PATCH_SHIFT, "bands")
+    poses = c.new.poses
+    want_base, want_new = c.base.plan(YAML, poses), c.new.plan(YAML, poses)
+    assert not np.array_equal(want_base["nominal"]["row"], want_new["nominal"]["row"]), "the two maps must plan differently"
+    planner = FootholdPlanner(0)
+    try:
+        dev = DeviceSide()
+        d_poses = dev.poses(poses)
+        raw = device_patches(dev, c.patches("packed"))
+        upload_base_device(dev, planner, c)
+        before = dev.queue_plan(planner, YAML, d_poses, poses.shape[0], N_CYCLES)
+        planner.update_map_device(c.shift, NEW_POS, raw, stream=dev.up.cuda_stream)
+        after = dev.queue_plan(planner, YAML, d_poses, poses.shape[0], N_CYCLES)
+        dev.side.synchronize()
+        dev.up.synchronize()
+        util.assert_plan_equal(dev.fetch_plan(before, poses.shape[0], N_CYCLES), want_base)
+        util.assert_plan_equal(dev.fetch_plan(after, poses.shape[0], N_CYCLES), want_new)
+    finally:
+        planner.close()
+
+
+# ---- F. refusals through the engine ------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_snapshot_as_it_was():
+    c = case(65, 63, mu.PATCH_SHIFT, "bands")
+    planner = FootholdPlanner(0)
+    try:
+        with pytest.raises(FpeError) as x:
+            planner.update_map((1, 0), NEW_POS, [])
+        assert x.value.code == _capi.FPE_E_NO_MAP
+        with pytest.raises(FpeError) as x:
+            planner.update_map_device((1, 0), NEW_POS, [])
+        assert x.value.code == _capi.FPE_E_NO_MAP
+        upload_base(planner, c)
+        before, info = observe_host(planner, YAML), planner.map_info()
+        good = c.patches("packed")
+        t, e = good[0][2], good[0][3]
+        nr, nc = t.shape
+        refused = [
+            make_map_update(c.shift, (float("nan"), 0.0), []),
+            make_map_update(c.shift, NEW_POS, [(c.rows - nr + 1, 0, nr, nc, t.ctypes.data, e.ctypes.data, nc, 1)]),
+            make_map_update(c.shift, NEW_POS, [(0, 0, nr, nc, t.ctypes.data, None, nc, 1)]),
+            make_map_update(c.shift, NEW_POS, [(0, 0, nr, nc, t.ctypes.data, e.ctypes.data, nc, 2)]),
+            make_map_update(c.shift, NEW_POS, [(0, 0, 0, nc, t.ctypes.data, e.ctypes.data, nc, 1)]),
+        ]
+        refused.append(make_map_update(c.shift, NEW_POS, []))
+        refused[-1].reserved = 1
+        refused.append(make_map_update(c.shift, NEW_POS, []))
+        refused[-1].n_patches = 9
+        for k, u in enumerate(refused):
+            assert planner._lib.fpe_update_map(planner._h, C.byref(u)) == _capi.FPE_E_INVALID_ARG, k
+            assert planner._lib.fpe_update_map_device(planner._h, C.byref(u), None) == _capi.FPE_E_INVALID_ARG, k
+        assert planner._lib.fpe_update_map(planner._h, None) == _capi.FPE_E_INVALID_ARG
+        assert planner.map_info() == info
+        assert_same_bytes(observe_host(planner, YAML), before, "after refused updates")
+        planner.update_map(c.shift, NEW_POS, good)  # and the engine still takes a good one
+        check_updated(planner, c, YAML, "a good update after refused ones", poses=False)
+    finally:
+        planner.close()
+
+
+# ---- G. the group of engines ---------------------------------------------------------------------------------------------------------
+def test_multi_update_then_multi_plan():
+    c = case(65, 63, mu.PATCH_SHIFT, "eight")
+    mp = MultiFootholdPlanner([0, 0])
+    single = FootholdPlanner(0)
+    try:
+        mp.params = params_for(YAML)
+        single.params = params_for(YAML)
+        mp.gridmapCallback(c.base.trav, c.base.elev, RES)
+        mp.update_map(c.shift, NEW_POS, c.patches("colmajor"))
+        got = mp.plan(c.new.poses, N_CYCLES)
+        single.gridmapCallback(c.new.trav, c.new.elev, RES, position=NEW_POS)
+        want = single.plan(c.new.poses, N_CYCLES)
+        for k in want:
+            assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k
+        util.assert_plan_equal(got, c.new.plan(YAML))
+    finally:
+        single.close()
+        mp.close()
