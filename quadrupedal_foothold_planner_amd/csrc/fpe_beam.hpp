@@ -40,9 +40,9 @@ __global__ __launch_bounds__(256) void beam_expand_kernel(const fpe_pose* __rest
     else beam_expand_lane<uint2>(poses + b, options + m, parent, cp + ch, cs + ch, cst + ch);
 }
 
-// One candidate per group of four lanes, lane = leg (rank_summary_body's shape): the segment's penalty from its k cycles, the
-// progress from the nominal track of its state_out, the score and the key.  Every lane of the group runs the same f64 chain in the
-// stated order; lane 0 writes.  prevSurv: the previous segment's survivors (their penalty is the parent's), null in segment 0.
+// One candidate per group of four lanes, lane = leg (rank_summary_body's shape): the segment's penalty from its k cycles (the
+// ranking's PenaltyAcc), the progress from the nominal track of its state_out, the score and the key.  Every lane of the group runs
+// the same f64 chain in the stated order; lane 0 writes.  prevSurv: the previous segment's survivors (their penalty is the parent's), null in segment 0.
 __global__ __launch_bounds__(256) void beam_score_kernel(int nChains, int nPrev, int M, int k, int slotStride, BeamConsts bc,
                                                          const fpe_foothold* __restrict__ nominal, const double* __restrict__ defaultNext,
                                                          const uint8_t* __restrict__ cycleOk, const fpe_plan_state* __restrict__ stateOut,
@@ -52,33 +52,13 @@ __global__ __launch_bounds__(256) void beam_score_kernel(int nChains, int nPrev,
     const int ch = t >> 2, leg = t & 3;
     const int cc = ch < nChains ? ch : nChains - 1;  // (lanes past the last chain run it again and write nothing: the shuffles stay whole)
     enum { RF = 0, RH = 1, LH = 2, LF = 3 };
-    uint32_t cnt01 = 0, cnt23 = 0;  // this leg's records by source, 16 bits each
-    int committed = 0;
-    double dev = 0.0;
+    PenaltyAcc acc;
     const size_t rec0 = static_cast<size_t>(cc) * k * 4 + leg;
     for (int g = 0; g < k; ++g) {
         const size_t q = rec0 + static_cast<size_t>(g) * 4;
-        const fpe_foothold& f = nominal[q];
-        const uint32_t src = f.source & 3u;
-        const double dx = f.x - defaultNext[q * 3], dy = f.y - defaultNext[q * 3 + 1];
-        const double term = dx * dx + dy * dy;
-        const int ok = cycleOk[static_cast<size_t>(cc) * k + g] != 0;
-        if (src < 2) cnt01 += 1u << (16 * src);
-        else cnt23 += 1u << (16 * (src - 2));
-        double d[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) d[l] = __shfl(term, l, 4);
-        if (!ok) continue;  // (uniform within the candidate's four lanes; the shuffles above ran with every lane)
-        ++committed;
-        dev = dev + d[RF];
-        dev = dev + d[RH];
-        dev = dev + d[LH];
-        dev = dev + d[LF];
+        acc.cycle(nominal[q], defaultNext + q * 3, cycleOk[static_cast<size_t>(cc) * k + g] != 0);
     }
-    cnt01 += __shfl_xor(cnt01, 1, 4);
-    cnt01 += __shfl_xor(cnt01, 2, 4);
-    cnt23 += __shfl_xor(cnt23, 1, 4);
-    cnt23 += __shfl_xor(cnt23, 2, 4);
+    const double q = acc.finish(bc.wFail, bc.wSpiral, bc.wNone, bc.wDeviation, k);
     const double fx = stateOut[cc].feet[2][leg][0];
     double x[4];
 #pragma unroll
@@ -87,14 +67,6 @@ __global__ __launch_bounds__(256) void beam_score_kernel(int nChains, int nPrev,
     const int nKeys = nPrev * M;
     const int c = ch % nKeys, b = ch / nKeys;
     const double parentPenalty = prevSurv ? prevSurv[static_cast<size_t>(b) * slotStride + c / M].penalty : 0.0;
-    const uint32_t n1 = cnt01 >> 16, n2 = cnt23 & 0xFFFFu, n3 = cnt23 >> 16;
-    const double t0 = bc.wFail * static_cast<double>(k - committed);
-    const double t1 = bc.wSpiral * static_cast<double>(n1);
-    const double t2 = bc.wNone * static_cast<double>(n2 + n3);
-    const double t3 = bc.wDeviation * dev;
-    double q = t0 + t1;
-    q = q + t2;
-    q = q + t3;
     const double penalty = parentPenalty + q;
     const double cx = ((x[RF] + x[RH]) + (x[LH] + x[LF])) * 0.25;
     const double prog = bc.wProgress * cx;
@@ -102,21 +74,12 @@ __global__ __launch_bounds__(256) void beam_score_kernel(int nChains, int nPrev,
     if (sc == 0.0) sc = 0.0;  // -0.0 -> +0.0
     candPenalty[ch] = penalty;
     candScore[ch] = sc;
-    const bool finite = __builtin_isfinite(sc);
-    unsigned long long img = 0ull;  // (class 1 falls to the candidate index alone)
-    if (finite) {
-        const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(sc));
-        img = (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
-    }
-    RankKey key;
-    key.hi = ((finite ? 0ull : 1ull) << 32) | (img >> 32);
-    key.lo = (img << 32) | static_cast<unsigned long long>(static_cast<uint32_t>(c));
-    keys[ch] = key;
+    keys[ch] = rank_key(sc, static_cast<uint32_t>(c), 0ull, 1ull);  // (class 1 falls to the candidate index alone)
 }
 
 constexpr int kBeamMaxKeys = FPE_BEAM_MAX_WIDTH * FPE_BEAM_MAX_OPTIONS;  // per root: 1024 keys, 16 KiB of LDS
 
-// Workgroup blockIdx.x sorts root blockIdx.x's nKeys keys in LDS — rank_select_kernel's bitonic network over the next power of two,
+// Workgroup blockIdx.x sorts root blockIdx.x's nKeys keys in LDS — the ranking's bitonic network (rank_sort_lds) over the next power of two,
 // padded with "no candidate" keys — and writes the first nKeep as the segment's survivors, best first.
 __global__ __launch_bounds__(256) void beam_select_kernel(const RankKey* __restrict__ keys, const double* __restrict__ candPenalty,
                                                           const double* __restrict__ candScore, int nKeys, int M, int nKeep, int slotStride,
@@ -129,20 +92,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const RankKey* __restr
     const RankKey none{~0ull, ~0ull};
     for (int i = tid; i < N; i += 256) s[i] = i < nKeys ? keys[base + i] : none;
     __syncthreads();
-    for (int kk = 2; kk <= N; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < (N >> 1); i += 256) {
-                const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1)), c = a | j;
-                const RankKey ka = s[a], kc = s[c];
-                const bool up = (a & kk) == 0;
-                if (rank_key_less(kc, ka) == up) {
-                    s[a] = kc;
-                    s[c] = ka;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    rank_sort_lds<256>(s, N, tid);
     for (int i = tid; i < nKeep; i += 256) {
         const int c = static_cast<int>(static_cast<uint32_t>(s[i].lo));
         BeamSurvivor v;
@@ -151,16 +101,6 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const RankKey* __restr
         v.penalty = candPenalty[base + c];
         v.score = candScore[base + c];
         surv[static_cast<size_t>(blockIdx.x) * slotStride + i] = v;
-    }
-}
-
-// Block `from` of every product to block `to` (RankCopy: words per block and the word size both pointers and the block size allow)
-__device__ __forceinline__ void beam_copy_blocks(const RankCopies& cp, size_t from, size_t to) {
-    for (int p = 0; p < cp.n; ++p) {
-        const RankCopy& c = cp.c[p];
-        if (c.unit == 16) rank_copy_words<uint4>(c, from, to);
-        else if (c.unit == 4) rank_copy_words<uint32_t>(c, from, to);
-        else rank_copy_words<unsigned char>(c, from, to);
     }
 }
 
@@ -173,7 +113,7 @@ __global__ __launch_bounds__(256) void beam_keep_kernel(const BeamSurvivor* __re
     const size_t slot = static_cast<size_t>(b) * slotStride + w;
     const BeamSurvivor v = surv[slot];
     const size_t ch = (static_cast<size_t>(b) * nPrev + v.parent) * M + v.option;
-    beam_copy_blocks(cp, ch, slot);
+    rank_copy_blocks(cp, ch, slot);
     constexpr int kWords = sizeof(fpe_plan_state) / sizeof(uint4);
     if (threadIdx.x < kWords)
         reinterpret_cast<uint4*>(parents + slot)[threadIdx.x] = reinterpret_cast<const uint4*>(stateOut + ch)[threadIdx.x];
@@ -195,7 +135,7 @@ __global__ __launch_bounds__(256) void beam_trace_kernel(const BeamSurvivor* __r
         const size_t h = (static_cast<size_t>(s) * B + b) * slotStride + slot;
         const BeamSurvivor v = surv[h];
         if (threadIdx.x == 0) path[out * S + s] = static_cast<uint8_t>(v.option);
-        beam_copy_blocks(cp, h, out * S + s);
+        rank_copy_blocks(cp, h, out * S + s);
         slot = v.parent;
     }
     constexpr int kWords = sizeof(fpe_plan_state) / sizeof(uint2);  // (the caller's array: 8-byte aligned by its type)
@@ -207,27 +147,6 @@ __global__ __launch_bounds__(256) void beam_trace_kernel(const BeamSurvivor* __r
         if (penalty) penalty[out] = v.penalty;
         if (nLiveOut && w == 0) nLiveOut[b] = nLive;
     }
-}
-
-// The copies of the products both structs hold: blocks of `cycles` gait cycles.  stance and pose_status never take part.
-inline RankCopies beam_copies(const fpe_plan_out& from, const fpe_plan_out& to, int cycles, size_t dstBlockOffset) {
-    RankCopies cp;
-    cp.n = 0;
-    const auto add = [&](const void* src, void* dst, size_t bytesPerBlock) {
-        if (!src || !dst) return;
-        const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | bytesPerBlock;
-        const uint32_t unit = (bits & 15) == 0 ? 16u : ((bits & 3) == 0 ? 4u : 1u);
-        cp.c[cp.n++] = RankCopy{static_cast<const unsigned char*>(src), static_cast<unsigned char*>(dst) + dstBlockOffset * bytesPerBlock,
-                                static_cast<uint32_t>(bytesPerBlock / unit), unit};
-    };
-    const size_t nRec = static_cast<size_t>(cycles) * 4;
-    add(from.nominal, to.nominal, nRec * sizeof(fpe_foothold));
-    add(from.centroid, to.centroid, nRec * sizeof(fpe_centroid_foothold));
-    add(from.default_next, to.default_next, nRec * 3 * sizeof(double));
-    add(from.cycle_ok, to.cycle_ok, static_cast<size_t>(cycles));
-    add(from.selected, to.selected, nRec * sizeof(fpe_selected_foothold));
-    add(from.selected_packed, to.selected_packed, nRec * sizeof(fpe_selected_packed));
-    return cp;
 }
 
 }  // namespace
@@ -264,14 +183,14 @@ hipError_t launch_beam_prune(const BeamConsts& bc, const BeamShape& sh, int s, c
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(beam_keep_kernel, dim3(sh.B * nKeep), dim3(256), 0, stream, surv, nPrev, sh.M, nKeep, sh.slotStride,
-                       beam_copies(sc.cand, sc.hist, sh.k, static_cast<size_t>(s) * segSlots), sc.stateOut, sc.parents);
+                       plan_copies(sc.cand, sc.hist, sh.k, static_cast<size_t>(s) * segSlots), sc.stateOut, sc.parents);
     return hipGetLastError();
 }
 
 hipError_t launch_beam_trace(const BeamShape& sh, const BeamScratch& sc, const fpe_beam_out& d_out, hipStream_t stream) {
     const int nLive = beam_live(sh, sh.S - 1);
     hipLaunchKernelGGL(beam_trace_kernel, dim3(sh.B * nLive), dim3(256), 0, stream, sc.surv, sh.B, sh.S, nLive, sh.slotStride, sh.outStride,
-                       beam_copies(sc.hist, d_out.products, sh.k, 0), sc.parents, d_out.n_live, d_out.score, d_out.penalty, d_out.path,
+                       plan_copies(sc.hist, d_out.products, sh.k, 0), sc.parents, d_out.n_live, d_out.score, d_out.penalty, d_out.path,
                        d_out.state);
     return hipGetLastError();
 }

@@ -879,44 +879,13 @@ int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, c
     return FPE_OK;
 }
 
-// The products of a plan call, described ONCE: the eight of fpe_plan_out, then the four of fpe_opt_out, in field order — which
-// is also the order of the arenas that FootholdPlanner.plan_outputs(pinned=True) relies on (its one pinned block then leaves in one
-// transfer, copy_out).  plan_host's sizes, offsets, device-side structs and copy segments and the ranking's layout all follow
-// this table: a new product is a line here beside its field in include/fpe.h.
-enum ProductScale { kPerLeg, kPerCycle, kPerPose };  // elements: pose x cycle x leg, pose x cycle, pose
-struct Product {
-    size_t elemBytes;
-    ProductScale scale;
-};
-constexpr int kPlanProducts = 8, kOptProducts = 4, kProducts = kPlanProducts + kOptProducts;
-constexpr Product kProductTable[kProducts] = {
-    {sizeof(fpe_foothold), kPerLeg},            // fpe_plan_out: nominal
-    {sizeof(fpe_centroid_foothold), kPerLeg},   //   centroid
-    {3 * sizeof(double), kPerLeg},              //   default_next
-    {1, kPerCycle},                             //   cycle_ok
-    {12 * sizeof(double), kPerPose},            //   stance
-    {sizeof(fpe_selected_foothold), kPerLeg},   //   selected
-    {1, kPerPose},                              //   pose_status
-    {sizeof(fpe_selected_packed), kPerLeg},     //   selected_packed
-    {sizeof(fpe_opt_foothold), kPerLeg},        // fpe_opt_out: footholds
-    {sizeof(fpe_opt_cycle), kPerCycle},         //   cycles
-    {1, kPerPose},                              //   gate_fail_cycle
-    {2 * sizeof(double), kPerPose},             //   rows_after
-};
-constexpr int kCycleOk = 3;  // the one product the engine itself reads (the opt track's input, the speculative call's check)
-constexpr size_t product_bytes(int k, size_t B, size_t nCycles) {
-    return kProductTable[k].elemBytes * B *
-           (kProductTable[k].scale == kPerPose ? 1 : (kProductTable[k].scale == kPerCycle ? nCycles : nCycles * 4));
-}
-// The one place that views the two structs as arrays of pointers: slot k of fpe_plan_out = product k of the table, slot k of
-// fpe_opt_out = product kPlanProducts + k.
-static_assert(sizeof(fpe_plan_out) == kPlanProducts * sizeof(void*), "fpe_plan_out: one pointer per product of the table");
-static_assert(sizeof(fpe_opt_out) == kOptProducts * sizeof(void*), "fpe_opt_out: one pointer per product of the table");
-static_assert(offsetof(fpe_plan_out, cycle_ok) == kCycleOk * sizeof(void*), "kCycleOk names fpe_plan_out::cycle_ok");
-inline void** slots(fpe_plan_out& o) { return reinterpret_cast<void**>(&o); }
-inline void* const* slots(const fpe_plan_out& o) { return reinterpret_cast<void* const*>(&o); }
-inline void** slots(fpe_opt_out& o) { return reinterpret_cast<void**>(&o); }
-inline void* const* slots(const fpe_opt_out& o) { return reinterpret_cast<void* const*>(&o); }
+// The products of a plan call and the slots() views of fpe_plan_out / fpe_opt_out: the product table of fpe_launch.hpp
+using fpe::kCycleOk;
+using fpe::kOptProducts;
+using fpe::kPlanProducts;
+using fpe::kProducts;
+using fpe::product_bytes;
+using fpe::slots;
 
 // selected_packed holds biased 14-bit grid indices: wherever the product is asked for, a larger map is refused.
 int check_packed_fits(const CallPlan& cp, bool wanted) {
@@ -941,6 +910,45 @@ struct SegList {
 // Every result is in the pinned arena (the kernels of a zero-copy call wrote it there themselves): out to the caller.
 void copy_from_pinned(const SegList& segs, const unsigned char* pinned) {
     for (int k = 0; k < segs.n; ++k) std::memcpy(segs.s[k].dst, pinned + segs.s[k].off, segs.s[k].len);
+}
+
+// The cursor of a ranking / beam call's layout over its two blocks, in offsets: the scratch (256-byte steps) and — the host form —
+// the output block, whose transfers to the caller it lists as it goes (outs: offsets in the call's arenas, the block at outOff0).
+// A layout runs twice: without bases for the sizes (null comes back, nothing is added to a null pointer), then on the bases.
+struct ArenaCursor {
+    unsigned char* base = nullptr;     // the scratch
+    unsigned char* outBase = nullptr;  // the output block, as the kernels see it
+    size_t outOff0 = 0;
+    size_t scratchBytes = 0, outBytes = 0;
+    SegList outs;
+    void* take(size_t bytes) {
+        const size_t off = scratchBytes;
+        scratchBytes += align256(bytes);
+        return base ? base + off : nullptr;
+    }
+    template <class T>
+    T* take_n(size_t n) {
+        return static_cast<T*>(take(n * sizeof(T)));
+    }
+    void* out(void* callerDst, size_t bytes) {
+        const size_t off = outBytes;
+        outBytes += align256(bytes);
+        outs.add(outOff0 + off, bytes, callerDst);
+        return outBase ? outBase + off : nullptr;
+    }
+};
+
+// The tail of a device-form call: `run(scratch)` queues its launches on `bytes` of stream-ordered scratch; its error goes ahead of
+// the free's.
+template <class Run>
+int with_stream_scratch(size_t bytes, hipStream_t stream, Run run) {
+    void* scratch = nullptr;
+    FPE_HIP(hipMallocAsync(&scratch, bytes, stream));
+    const int rc = run(static_cast<unsigned char*>(scratch));
+    const hipError_t f = hipFreeAsync(scratch, stream);
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(f);
+    return FPE_OK;
 }
 
 // The results of a host-form call from the device arena `dev` to the caller, behind the kernels queued on cx.stream; `pinned`: the
@@ -2286,10 +2294,31 @@ int check_rank_args(const fpe_params* params, const fpe_rank_params* rank, int32
     return FPE_OK;
 }
 
+// What the host forms of the ranking and beam calls open with, on the lease `hc` of the caller: the arenas, the prepare, the two
+// refusals that need the map, and the pinned arena as the device sees it (`mapped`: the kernels read the call's inputs there, as in
+// fpe_plan; the caller stages them).
+int open_batch_call(fpe_engine* h, HostCall& hc, const fpe_params* params, float maxRadius, size_t arenaBytes, bool packedWanted,
+                    fpe::PlanForm form, unsigned char*& mapped) {
+    CallCtx& cx = hc.cx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(arenaBytes));
+    cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
+    int rc = prepare_call(h, params, maxRadius, hc.cp, cx.stream, true);
+    if (rc != FPE_OK) return rc;
+    rc = check_packed_fits(hc.cp, packedWanted);
+    if (rc != FPE_OK) return rc;
+    rc = check_strides_launchable(hc.cp, form);
+    if (rc != FPE_OK) return rc;
+    void* p = nullptr;
+    FPE_HIP(hipHostGetDevicePointer(&p, cx.pinned, 0));
+    mapped = static_cast<unsigned char*>(p);
+    return FPE_OK;
+}
+
 // Where everything a ranking call touches on the device lives.  `full`: the un-compacted products — the caller's (d_full) where given,
-// scratch for what the ranking reads or the compaction copies from, null for the rest.  The B-sized and K-sized outputs the caller
-// did not place (null in `placed`) go to the output block when `outputs` says so (the host form: every requested one), and summary /
-// score to scratch otherwise.  lay(base, outBase) fills the pointers; both bases null: sizes only.
+// scratch for what the ranking reads or the compaction copies from, null for the rest.  The B-sized and K-sized outputs are the
+// caller's own arrays (the device form) or — the host form — lie in the output block in the order products, summary, score, best,
+// n_class0; summary and score go to scratch when the caller did not ask for them.
 struct RankLayout {
     int32_t B, n, K;
     fpe_plan_out full, best;
@@ -2298,41 +2327,24 @@ struct RankLayout {
     int32_t* bestIdx;
     int32_t* nClass0;
     void* keys;
-    size_t scratchBytes, outBytes;
-    // the host form's transfers, in the output block's order: the eight products, then summary, score, best, n_class0
-    size_t outOff[kPlanProducts + 4], outLen[kPlanProducts + 4];
 };
 static_assert(kPlanProducts + 4 <= kProducts, "SegList holds a ranking call's outputs");
-void rank_layout(RankLayout& L, const fpe_plan_out* dFull, const fpe_rank_out& want, bool hostForm, unsigned char* base, unsigned char* outBase) {
+void rank_layout(RankLayout& L, ArenaCursor& A, const fpe_plan_out* dFull, const fpe_rank_out& want, bool hostForm) {
     const bool reads[kPlanProducts] = {true, false, true, true, true, false, true, false};  // rank_summary_kernel's inputs
     const size_t B = static_cast<size_t>(L.B), K = static_cast<size_t>(L.K), n = static_cast<size_t>(L.n);
-    size_t off = 0, oo = 0;
-    const auto take = [&](size_t bytes) {
-        unsigned char* p = base + off;
-        off += align256(bytes);
-        return static_cast<void*>(p);
-    };
-    const auto takeOut = [&](int k, size_t bytes) {
-        L.outOff[k] = oo;
-        L.outLen[k] = bytes;
-        oo += align256(bytes);
-        return static_cast<void*>(outBase + L.outOff[k]);
-    };
-    for (int k = 0; k < kPlanProducts + 4; ++k) L.outOff[k] = L.outLen[k] = 0;
+    const auto out = [&](void* dst, size_t bytes) { return (dst && hostForm) ? A.out(dst, bytes) : dst; };
     void* const* given = dFull ? slots(*dFull) : nullptr;
     void* const* wanted = slots(want.best_products);
     for (int k = 0; k < kPlanProducts; ++k) {
-        slots(L.full)[k] = (given && given[k]) ? given[k] : ((reads[k] || wanted[k]) ? take(product_bytes(k, B, n)) : nullptr);
-        slots(L.best)[k] = !wanted[k] ? nullptr : (hostForm ? takeOut(k, product_bytes(k, K, n)) : wanted[k]);
+        slots(L.full)[k] = (given && given[k]) ? given[k] : ((reads[k] || wanted[k]) ? A.take(product_bytes(k, B, n)) : nullptr);
+        slots(L.best)[k] = out(wanted[k], product_bytes(k, K, n));
     }
     const size_t szSum = B * sizeof(fpe_pose_summary), szScore = B * sizeof(double);
-    L.summary = static_cast<fpe_pose_summary*>(!want.summary ? take(szSum) : (hostForm ? takeOut(kPlanProducts, szSum) : want.summary));
-    L.score = static_cast<double*>(!want.score ? take(szScore) : (hostForm ? takeOut(kPlanProducts + 1, szScore) : want.score));
-    L.bestIdx = static_cast<int32_t*>(hostForm ? takeOut(kPlanProducts + 2, K * sizeof(int32_t)) : want.best);
-    L.nClass0 = static_cast<int32_t*>(!want.n_class0 ? nullptr : (hostForm ? takeOut(kPlanProducts + 3, sizeof(int32_t)) : want.n_class0));
-    L.keys = take(fpe::rank_scratch_bytes(L.B, L.K));
-    L.scratchBytes = off;
-    L.outBytes = oo;
+    L.summary = static_cast<fpe_pose_summary*>(want.summary ? out(want.summary, szSum) : A.take(szSum));
+    L.score = static_cast<double*>(want.score ? out(want.score, szScore) : A.take(szScore));
+    L.bestIdx = static_cast<int32_t*>(out(want.best, K * sizeof(int32_t)));
+    L.nClass0 = static_cast<int32_t*>(out(want.n_class0, sizeof(int32_t)));
+    L.keys = A.take(fpe::rank_scratch_bytes(L.B, L.K));
 }
 
 // The launches of a prepared ranking call on `stream`: the plan through launch_plan, then summary, select, gather.
@@ -2363,20 +2375,18 @@ int fpe_plan_rank_strides_device(fpe_handle h, const fpe_params* params, const f
     if (rc0 != FPE_OK) return rc0;
     RankLayout L{};
     L.B = B, L.n = n_cycles, L.K = K;
-    rank_layout(L, d_full, *d_out, false, nullptr, nullptr);
+    ArenaCursor sizes;
+    rank_layout(L, sizes, d_full, *d_out, false);
     rc0 = check_packed_fits(cp, (d_full && d_full->selected_packed) || d_out->best_products.selected_packed);
     if (rc0 != FPE_OK) return rc0;
     rc0 = check_strides_launchable(cp, d_strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain);
     if (rc0 != FPE_OK) return rc0;
     mark_async_launch(cp);
-    void* scratch = nullptr;
-    FPE_HIP(hipMallocAsync(&scratch, L.scratchBytes, st));
-    rank_layout(L, d_full, *d_out, false, static_cast<unsigned char*>(scratch), nullptr);
-    rc0 = run_rank(h, cp, rc, d_poses, d_strides, L, st);
-    const hipError_t f = hipFreeAsync(scratch, st);
-    if (rc0 != FPE_OK) return rc0;
-    FPE_HIP(f);
-    return FPE_OK;
+    return with_stream_scratch(sizes.scratchBytes, st, [&](unsigned char* scratch) {
+        ArenaCursor A{scratch};
+        rank_layout(L, A, d_full, *d_out, false);
+        return run_rank(h, cp, rc, d_poses, d_strides, L, st);
+    });
 }
 
 int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses, int32_t B, int32_t n_cycles,
@@ -2397,39 +2407,29 @@ int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank
     if (rc0 != FPE_OK) return rc0;
     RankLayout L{};
     L.B = B, L.n = n_cycles, L.K = K;
-    rank_layout(L, nullptr, *out, true, nullptr, nullptr);
+    ArenaCursor sizes;
+    rank_layout(L, sizes, nullptr, *out, true);
     // both arenas: [poses (| strides) | outputs | scratch].  The poses are read from the pinned arena (device-mapped), as in fpe_plan; outputs of up
     // to kZeroCopyBytes are WRITTEN there by the kernels too (no transfer at all: a DMA costs some ten microseconds, whatever its size)
     const size_t oStrides = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
     const size_t szPose = oStrides + (strides ? align256(static_cast<size_t>(B) * sizeof(fpe_stride)) : 0);  // (the per-pose inputs)
-    const bool zeroCopy = L.outBytes <= kZeroCopyBytes;
+    const bool zeroCopy = sizes.outBytes <= kZeroCopyBytes;
     HostCall hc(h);
-    CallPlan& cp = hc.cp;
     CallCtx& cx = hc.cx;
-    FPE_HIP(hipSetDevice(h->device));
-    FPE_HIP(cx.reserve(szPose + L.outBytes + L.scratchBytes));
-    cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
-    rc0 = prepare_call(h, params, maxRadius, cp, cx.stream, true);
-    if (rc0 != FPE_OK) return rc0;
-    rc0 = check_packed_fits(cp, out->best_products.selected_packed != nullptr);
+    unsigned char* mapped = nullptr;
+    rc0 = open_batch_call(h, hc, params, maxRadius, szPose + sizes.outBytes + sizes.scratchBytes, out->best_products.selected_packed != nullptr,
+                          strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain, mapped);
     if (rc0 != FPE_OK) return rc0;
     stage_batch_inputs(cx.pinned, oStrides, poses, strides, B);
-    void* mapped = nullptr;
-    FPE_HIP(hipHostGetDevicePointer(&mapped, cx.pinned, 0));
-    unsigned char* const devArena = zeroCopy ? static_cast<unsigned char*>(mapped) : cx.dev;
-    rank_layout(L, nullptr, *out, true, cx.dev + szPose + L.outBytes, devArena + szPose);
-    const fpe_stride* dStrides = strides ? reinterpret_cast<const fpe_stride*>(static_cast<unsigned char*>(mapped) + oStrides) : nullptr;
-    rc0 = run_rank(h, cp, rc, static_cast<const fpe_pose*>(mapped), dStrides, L, cx.stream);
+    ArenaCursor A{cx.dev + szPose + sizes.outBytes, (zeroCopy ? mapped : cx.dev) + szPose, szPose};
+    rank_layout(L, A, nullptr, *out, true);
+    const fpe_stride* dStrides = strides ? reinterpret_cast<const fpe_stride*>(mapped + oStrides) : nullptr;
+    rc0 = run_rank(h, hc.cp, rc, reinterpret_cast<const fpe_pose*>(mapped), dStrides, L, cx.stream);
     if (rc0 != FPE_OK) return rc0;
-    void* dst[kPlanProducts + 4];
-    std::copy(slots(out->best_products), slots(out->best_products) + kPlanProducts, dst);
-    dst[kPlanProducts] = out->summary, dst[kPlanProducts + 1] = out->score, dst[kPlanProducts + 2] = out->best, dst[kPlanProducts + 3] = out->n_class0;
-    SegList segs;
-    for (int k = 0; k < kPlanProducts + 4; ++k) segs.add(szPose + L.outOff[k], L.outLen[k], dst[k]);
-    if (!zeroCopy) return copy_out(h, cx, segs, cx.dev, cx.pinned);
+    if (!zeroCopy) return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
     FPE_HIP(hipStreamSynchronize(cx.stream));
     cx.inFlight = false;
-    copy_from_pinned(segs, cx.pinned);
+    copy_from_pinned(A.outs, cx.pinned);
     return FPE_OK;
 }
 
@@ -2478,59 +2478,45 @@ int check_beam_args(const fpe_params* params, const fpe_beam_params* beam, int32
 }
 
 // Where everything a beam call touches on the device lives: the scratch (fpe::BeamScratch) and — the host form — the output block,
-// dense (outStride = n_{S-1} slots per root), in the order products, n_live, score, penalty, path, state.  outSlot[k]: bytes per
-// slot of output k (0: one element per root).  lay(base, outBase) fills the pointers; both bases null: sizes only.
+// dense (outStride = n_{S-1} slots per root), in the order products, n_live, score, penalty, path, state.  outSlot[q]: bytes per
+// slot of transfer q of the cursor's list (0: one element per root), for the underfilled repack.
 struct BeamLayout {
     fpe::BeamShape sh;
     fpe::BeamScratch sc;
     fpe_beam_out out;
-    size_t scratchBytes, outBytes;
-    size_t outOff[kPlanProducts + kBeamOwn], outLen[kPlanProducts + kBeamOwn], outSlot[kPlanProducts + kBeamOwn];
+    size_t outSlot[kPlanProducts + kBeamOwn];
 };
-void beam_layout(BeamLayout& L, const fpe_beam_out& want, bool hostForm, unsigned char* base, unsigned char* outBase) {
+void beam_layout(BeamLayout& L, ArenaCursor& A, const fpe_beam_out& want, bool hostForm) {
     const bool reads[kPlanProducts] = {true, false, true, true, false, false, false, false};  // beam_score_kernel's inputs
     const fpe::BeamShape& sh = L.sh;
     const size_t S = static_cast<size_t>(sh.S), k = static_cast<size_t>(sh.k), slots_ = static_cast<size_t>(sh.B) * sh.slotStride;
     const size_t chains = static_cast<size_t>(sh.B) * (sh.S > 1 ? fpe::beam_live(sh, sh.S - 2) : 1) * sh.M;
-    size_t off = 0, oo = 0;
-    const auto take = [&](size_t bytes) {
-        unsigned char* p = base + off;
-        off += align256(bytes);
-        return static_cast<void*>(p);
-    };
-    const auto takeOut = [&](int q, size_t bytesPerSlot, size_t n) {
-        L.outOff[q] = oo;
-        L.outLen[q] = bytesPerSlot * n;
-        oo += align256(L.outLen[q]);
-        return static_cast<void*>(outBase + L.outOff[q]);
-    };
-    for (int q = 0; q < kPlanProducts + kBeamOwn; ++q) L.outOff[q] = L.outLen[q] = L.outSlot[q] = 0;
-    L.sc.poses = static_cast<fpe_pose*>(take(chains * sizeof(fpe_pose)));
-    L.sc.strides = static_cast<fpe_stride*>(take(chains * sizeof(fpe_stride)));
-    L.sc.stateIn = static_cast<fpe_plan_state*>(take(chains * sizeof(fpe_plan_state)));
-    L.sc.stateOut = static_cast<fpe_plan_state*>(take(chains * sizeof(fpe_plan_state)));
-    L.sc.candPenalty = static_cast<double*>(take(chains * sizeof(double)));
-    L.sc.candScore = static_cast<double*>(take(chains * sizeof(double)));
-    L.sc.keys = take(chains * 16);
-    L.sc.surv = static_cast<fpe::BeamSurvivor*>(take(S * slots_ * sizeof(fpe::BeamSurvivor)));
-    L.sc.parents = static_cast<fpe_plan_state*>(take(slots_ * sizeof(fpe_plan_state)));
-    void* const* wanted = slots(want.products);
     const size_t outSlots = static_cast<size_t>(sh.B) * sh.outStride;
+    const auto out = [&](void* dst, size_t bytesPerSlot, bool perRoot = false) {
+        if (!dst || !hostForm) return dst;
+        L.outSlot[A.outs.n] = perRoot ? 0 : bytesPerSlot;
+        return A.out(dst, bytesPerSlot * (perRoot ? static_cast<size_t>(sh.B) : outSlots));
+    };
+    L.sc.poses = A.take_n<fpe_pose>(chains);
+    L.sc.strides = A.take_n<fpe_stride>(chains);
+    L.sc.stateIn = A.take_n<fpe_plan_state>(chains);
+    L.sc.stateOut = A.take_n<fpe_plan_state>(chains);
+    L.sc.candPenalty = A.take_n<double>(chains);
+    L.sc.candScore = A.take_n<double>(chains);
+    L.sc.keys = A.take(chains * 16);
+    L.sc.surv = A.take_n<fpe::BeamSurvivor>(S * slots_);
+    L.sc.parents = A.take_n<fpe_plan_state>(slots_);
+    void* const* wanted = slots(want.products);
     for (int q = 0; q < kPlanProducts; ++q) {
-        slots(L.sc.cand)[q] = (reads[q] || wanted[q]) ? take(product_bytes(q, chains, k)) : nullptr;
-        slots(L.sc.hist)[q] = wanted[q] ? take(product_bytes(q, S * slots_, k)) : nullptr;
-        L.outSlot[q] = product_bytes(q, 1, S * k);
-        slots(L.out.products)[q] = !wanted[q] ? nullptr : (hostForm ? takeOut(q, L.outSlot[q], outSlots) : wanted[q]);
+        slots(L.sc.cand)[q] = (reads[q] || wanted[q]) ? A.take(product_bytes(q, chains, k)) : nullptr;
+        slots(L.sc.hist)[q] = wanted[q] ? A.take(product_bytes(q, S * slots_, k)) : nullptr;
+        slots(L.out.products)[q] = out(wanted[q], product_bytes(q, 1, S * k));
     }
-    const int o = kPlanProducts;
-    L.outSlot[o + 1] = L.outSlot[o + 2] = sizeof(double), L.outSlot[o + 3] = S, L.outSlot[o + 4] = sizeof(fpe_plan_state);
-    L.out.n_live = !want.n_live ? nullptr : (hostForm ? static_cast<int32_t*>(takeOut(o, sizeof(int32_t), sh.B)) : want.n_live);
-    L.out.score = !want.score ? nullptr : (hostForm ? static_cast<double*>(takeOut(o + 1, L.outSlot[o + 1], outSlots)) : want.score);
-    L.out.penalty = !want.penalty ? nullptr : (hostForm ? static_cast<double*>(takeOut(o + 2, L.outSlot[o + 2], outSlots)) : want.penalty);
-    L.out.path = hostForm ? static_cast<uint8_t*>(takeOut(o + 3, L.outSlot[o + 3], outSlots)) : want.path;
-    L.out.state = !want.state ? nullptr : (hostForm ? static_cast<fpe_plan_state*>(takeOut(o + 4, L.outSlot[o + 4], outSlots)) : want.state);
-    L.scratchBytes = off;
-    L.outBytes = oo;
+    L.out.n_live = static_cast<int32_t*>(out(want.n_live, sizeof(int32_t), true));
+    L.out.score = static_cast<double*>(out(want.score, sizeof(double)));
+    L.out.penalty = static_cast<double*>(out(want.penalty, sizeof(double)));
+    L.out.path = static_cast<uint8_t*>(out(want.path, S));
+    L.out.state = static_cast<fpe_plan_state*>(out(want.state, sizeof(fpe_plan_state)));
 }
 
 // The launches of a prepared beam call on `stream`: S x (expand, the resume kernels through launch_plan, score / select / keep),
@@ -2567,16 +2553,14 @@ int fpe_plan_beam_device(fpe_handle h, const fpe_params* params, const fpe_beam_
     if (rc != FPE_OK) return rc;
     rc = check_packed_fits(cp, d_out->products.selected_packed != nullptr);
     if (rc != FPE_OK) return rc;
-    beam_layout(L, *d_out, false, nullptr, nullptr);
+    ArenaCursor sizes;
+    beam_layout(L, sizes, *d_out, false);
     mark_async_launch(cp);
-    void* scratch = nullptr;
-    FPE_HIP(hipMallocAsync(&scratch, L.scratchBytes, st));
-    beam_layout(L, *d_out, false, static_cast<unsigned char*>(scratch), nullptr);
-    rc = run_beam(h, cp, bc, d_poses, d_options, d_state_in, L, st);
-    const hipError_t f = hipFreeAsync(scratch, st);
-    if (rc != FPE_OK) return rc;
-    FPE_HIP(f);
-    return FPE_OK;
+    return with_stream_scratch(sizes.scratchBytes, st, [&](unsigned char* scratch) {
+        ArenaCursor A{scratch};
+        beam_layout(L, A, *d_out, false);
+        return run_beam(h, cp, bc, d_poses, d_options, d_state_in, L, st);
+    });
 }
 
 int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_pose* poses, const fpe_plan_state* state_in,
@@ -2595,55 +2579,40 @@ int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params*
     if (rc != FPE_OK) return rc;
     const fpe::BeamShape want = L.sh;  // (the caller's arrays: W slots per root)
     L.sh.outStride = L.sh.slotStride;  // the arena's output block is dense: only live slots exist there
-    beam_layout(L, *out, true, nullptr, nullptr);
+    ArenaCursor sizes;
+    beam_layout(L, sizes, *out, true);
     // both arenas: [poses | options | state_in | outputs | scratch (device arena only)]; the inputs are read from the pinned arena
     const size_t oOptions = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
     const size_t oStates = oOptions + align256(static_cast<size_t>(M) * sizeof(fpe_stride));
     const size_t szIn = oStates + (state_in ? align256(static_cast<size_t>(B) * sizeof(fpe_plan_state)) : 0);
     HostCall hc(h);
-    CallPlan& cp = hc.cp;
     CallCtx& cx = hc.cx;
-    FPE_HIP(hipSetDevice(h->device));
-    FPE_HIP(cx.reserve(szIn + L.outBytes + L.scratchBytes));
-    cx.inFlight = true;  // (prepare_call may already queue a bit-plane build)
-    rc = prepare_call(h, params, maxRadius, cp, cx.stream, true);
-    if (rc != FPE_OK) return rc;
-    rc = check_strides_launchable(cp, fpe::PlanForm::Resume);
-    if (rc != FPE_OK) return rc;
-    rc = check_packed_fits(cp, out->products.selected_packed != nullptr);
+    unsigned char* in = nullptr;
+    rc = open_batch_call(h, hc, params, maxRadius, szIn + sizes.outBytes + sizes.scratchBytes, out->products.selected_packed != nullptr,
+                         fpe::PlanForm::Resume, in);
     if (rc != FPE_OK) return rc;
     stage_batch_inputs(cx.pinned, 0, poses, nullptr, B, oStates, state_in);
     std::memcpy(cx.pinned + oOptions, options, static_cast<size_t>(M) * sizeof(fpe_stride));
-    void* mapped = nullptr;
-    FPE_HIP(hipHostGetDevicePointer(&mapped, cx.pinned, 0));
-    unsigned char* const in = static_cast<unsigned char*>(mapped);
-    beam_layout(L, *out, true, cx.dev + szIn + L.outBytes, cx.dev + szIn);
-    rc = run_beam(h, cp, bc, reinterpret_cast<const fpe_pose*>(in), reinterpret_cast<const fpe_stride*>(in + oOptions),
+    ArenaCursor A{cx.dev + szIn + sizes.outBytes, cx.dev + szIn, szIn};
+    beam_layout(L, A, *out, true);
+    rc = run_beam(h, hc.cp, bc, reinterpret_cast<const fpe_pose*>(in), reinterpret_cast<const fpe_stride*>(in + oOptions),
                   state_in ? reinterpret_cast<const fpe_plan_state*>(in + oStates) : nullptr, L, cx.stream);
     if (rc != FPE_OK) return rc;
-    void* dst[kPlanProducts + kBeamOwn];
-    std::copy(slots(out->products), slots(out->products) + kPlanProducts, dst);
-    const int o = kPlanProducts;
-    dst[o] = out->n_live, dst[o + 1] = out->score, dst[o + 2] = out->penalty, dst[o + 3] = out->path, dst[o + 4] = out->state;
-    if (L.sh.outStride == want.outStride) {  // a full beam: the arena's arrays are the caller's
-        SegList segs;
-        for (int q = 0; q < kPlanProducts + kBeamOwn; ++q) segs.add(szIn + L.outOff[q], L.outLen[q], dst[q]);
-        return copy_out(h, cx, segs, cx.dev, cx.pinned);
-    }
+    if (L.sh.outStride == want.outStride) return copy_out(h, cx, A.outs, cx.dev, cx.pinned);  // a full beam: the arena's arrays are the caller's
     // an underfilled beam (M^S < W: a few slots): one transfer, then every root's live slots to the head of its W slots — the dead
     // ones are not written
-    FPE_HIP(hipMemcpyAsync(cx.pinned + szIn, cx.dev + szIn, L.outBytes, hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipMemcpyAsync(cx.pinned + szIn, cx.dev + szIn, A.outBytes, hipMemcpyDeviceToHost, cx.stream));
     FPE_HIP(hipStreamSynchronize(cx.stream));
     cx.inFlight = false;
-    for (int q = 0; q < kPlanProducts + kBeamOwn; ++q) {
-        if (!dst[q] || !L.outLen[q]) continue;
-        const unsigned char* src = cx.pinned + szIn + L.outOff[q];
-        if (!L.outSlot[q] || q == o) {
-            std::memcpy(dst[q], src, L.outLen[q]);
+    for (int q = 0; q < A.outs.n; ++q) {
+        const Seg& seg = A.outs.s[q];
+        const unsigned char* src = cx.pinned + seg.off;
+        if (!L.outSlot[q]) {
+            std::memcpy(seg.dst, src, seg.len);
             continue;
         }
         const size_t live = L.outSlot[q] * L.sh.outStride, all = L.outSlot[q] * want.outStride;
-        for (int b = 0; b < B; ++b) std::memcpy(static_cast<unsigned char*>(dst[q]) + b * all, src + b * live, live);
+        for (int b = 0; b < B; ++b) std::memcpy(static_cast<unsigned char*>(seg.dst) + b * all, src + b * live, live);
     }
     return FPE_OK;
 }

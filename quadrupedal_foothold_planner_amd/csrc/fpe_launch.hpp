@@ -135,6 +135,47 @@ size_t centroid_map_scratch_bytes(const FootmapRoi& roi, const CmapConsts& cc);
 hipError_t launch_centroid_map(const DevMap& m, const PlanConsts& pc, const CmapConsts& cc, const FootmapRoi& roi, void* scratch,
                                uint8_t* d_code, int8_t* d_offset, float* d_z, hipStream_t stream);
 
+// ---- the products of a plan call --------------------------------------------------------------------------------
+// Described ONCE, for both sides: the eight of fpe_plan_out, then the four of fpe_opt_out, in field order — which is also the
+// order of the arenas that FootholdPlanner.plan_outputs(pinned=True) relies on (its one pinned block then leaves in one transfer,
+// copy_out).  The engine's sizes, offsets, device-side structs and copy segments (plan_host, the ranking's and the beam's layouts)
+// and the kernel side's copy table (plan_copies, fpe_rank.hpp) all follow this table: a new product is a line here beside its
+// field in include/fpe.h — and, where a ranking or a beam has to plan it for its own reading, a flag in that layout's reads[].
+enum ProductScale { kPerLeg, kPerCycle, kPerPose };  // elements: pose x cycle x leg, pose x cycle, pose
+struct Product {
+    size_t elemBytes;
+    ProductScale scale;
+};
+constexpr int kPlanProducts = 8, kOptProducts = 4, kProducts = kPlanProducts + kOptProducts;
+constexpr Product kProductTable[kProducts] = {
+    {sizeof(fpe_foothold), kPerLeg},            // fpe_plan_out: nominal
+    {sizeof(fpe_centroid_foothold), kPerLeg},   //   centroid
+    {3 * sizeof(double), kPerLeg},              //   default_next
+    {1, kPerCycle},                             //   cycle_ok
+    {12 * sizeof(double), kPerPose},            //   stance
+    {sizeof(fpe_selected_foothold), kPerLeg},   //   selected
+    {1, kPerPose},                              //   pose_status
+    {sizeof(fpe_selected_packed), kPerLeg},     //   selected_packed
+    {sizeof(fpe_opt_foothold), kPerLeg},        // fpe_opt_out: footholds
+    {sizeof(fpe_opt_cycle), kPerCycle},         //   cycles
+    {1, kPerPose},                              //   gate_fail_cycle
+    {2 * sizeof(double), kPerPose},             //   rows_after
+};
+constexpr int kCycleOk = 3;  // the one product the engine itself reads (the opt track's input, the speculative call's check)
+constexpr size_t product_bytes(int k, size_t B, size_t nCycles) {
+    return kProductTable[k].elemBytes * B *
+           (kProductTable[k].scale == kPerPose ? 1 : (kProductTable[k].scale == kPerCycle ? nCycles : nCycles * 4));
+}
+// The one place that views the two structs as arrays of pointers: slot k of fpe_plan_out = product k of the table, slot k of
+// fpe_opt_out = product kPlanProducts + k.
+static_assert(sizeof(fpe_plan_out) == kPlanProducts * sizeof(void*), "fpe_plan_out: one pointer per product of the table");
+static_assert(sizeof(fpe_opt_out) == kOptProducts * sizeof(void*), "fpe_opt_out: one pointer per product of the table");
+static_assert(offsetof(fpe_plan_out, cycle_ok) == kCycleOk * sizeof(void*), "kCycleOk names fpe_plan_out::cycle_ok");
+inline void** slots(fpe_plan_out& o) { return reinterpret_cast<void**>(&o); }
+inline void* const* slots(const fpe_plan_out& o) { return reinterpret_cast<void* const*>(&o); }
+inline void** slots(fpe_opt_out& o) { return reinterpret_cast<void**>(&o); }
+inline void* const* slots(const fpe_opt_out& o) { return reinterpret_cast<void* const*>(&o); }
+
 // ---- ranking of a planned batch (fpe_rank.hpp) ---------------------------------------------------------------
 struct RankConsts {
     double wFail, wSpiral, wNone, wDeviation, wSpeedSpread;

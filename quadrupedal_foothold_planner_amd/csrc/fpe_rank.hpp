@@ -1,7 +1,8 @@
 // fpe_rank.hpp — part seven of fpe_kernels.hip: rank a planned pose batch on the device (fpe_plan_rank*, include/fpe.h).
 // Three kernels behind the plan kernel, on what it wrote: a per-pose summary with its score and sort key, the K smallest keys
 // (sorted), and the copy of the chosen poses' products into K slots.  No atomics anywhere: every output is a function of the
-// inputs alone.
+// inputs alone.  The beam (fpe_beam.hpp) scores, sorts and copies with the same pieces, which live here once: PenaltyAcc, rank_key,
+// rank_sort_lds, plan_copies / rank_copy_blocks.
 #pragma once
 
 // Sort key of one pose, ascending = better: hi = class << 32 | image >> 32, lo = image << 32 | pose index, with `image` the
@@ -12,13 +13,14 @@ struct alignas(16) RankKey {
 
 constexpr int kRankTile = 8192;  // keys one workgroup sorts in LDS: 128 KiB of the CU's 160
 constexpr int kRankMaxK = 1024;
-constexpr int kRankProducts = 8;
+constexpr int kRankProducts = kPlanProducts;  // (the product table: fpe_launch.hpp)
 
-// One product of the gather: `unit`-byte words (16, 4 or 1: what both pointers and the per-pose size are multiples of)
+// One product of a block copy (a pose of the gather, a segment of a beam's keep / trace): `unit`-byte words (16, 4 or 1: what both
+// pointers and the block size are multiples of)
 struct RankCopy {
     const unsigned char* src;
     unsigned char* dst;
-    uint32_t words;  // per pose
+    uint32_t words;  // per block
     uint32_t unit;
 };
 struct RankCopies {
@@ -29,6 +31,84 @@ struct RankCopies {
 namespace {
 
 __device__ __forceinline__ bool rank_key_less(const RankKey& a, const RankKey& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+
+// The key of `score` (-0.0 already +0.0) and `index`: class `cls` and the order-preserving 64-bit image of the score, or — not
+// finite — class `clsNonFinite` and no image: those fall to the index alone.
+__device__ __forceinline__ RankKey rank_key(double score, uint32_t index, unsigned long long cls, unsigned long long clsNonFinite) {
+    const bool finite = __builtin_isfinite(score);
+    unsigned long long img = 0ull;
+    if (finite) {
+        const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(score));
+        img = (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
+    }
+    RankKey k;
+    k.hi = ((finite ? cls : clsNonFinite) << 32) | (img >> 32);
+    k.lo = (img << 32) | static_cast<unsigned long long>(index);
+    return k;
+}
+
+// The penalty chain of one candidate — a ranked pose or a beam's chain — on its group of four lanes, lane = leg.  Every lane of
+// the group runs the same f64 chain in the stated order (-ffp-contract=off): the scores are pinned byte for byte.
+struct PenaltyAcc {
+    uint32_t cnt01 = 0, cnt23 = 0;  // this leg's records by source, 16 bits each; behind finish(): the candidate's
+    int committed = 0;
+    double dev = 0.0;
+    // One gait cycle: this leg's record `f`, its default_next (x, y, ..) and whether the cycle is committed (uniform within the
+    // group: the shuffles run with every lane).
+    __device__ __forceinline__ void cycle(const fpe_foothold& f, const double* __restrict__ defaultNext, bool ok) {
+        enum { RF = 0, RH = 1, LH = 2, LF = 3 };
+        const uint32_t src = f.source & 3u;
+        const double dx = f.x - defaultNext[0], dy = f.y - defaultNext[1];
+        const double term = dx * dx + dy * dy;
+        if (src < 2) cnt01 += 1u << (16 * src);
+        else cnt23 += 1u << (16 * (src - 2));
+        double d[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) d[l] = __shfl(term, l, 4);
+        if (!ok) return;
+        ++committed;
+        dev = dev + d[RF];
+        dev = dev + d[RH];
+        dev = dev + d[LH];
+        dev = dev + d[LF];
+    }
+    __device__ __forceinline__ uint32_t n_source(int src) const { return ((src < 2 ? cnt01 : cnt23) >> (16 * (src & 1))) & 0xFFFFu; }
+    // Behind the last of nCycles cycles: the source counts over the four legs, and the weighted sum in its fixed order.
+    __device__ __forceinline__ double finish(double wFail, double wSpiral, double wNone, double wDeviation, int nCycles) {
+        cnt01 += __shfl_xor(cnt01, 1, 4);
+        cnt01 += __shfl_xor(cnt01, 2, 4);
+        cnt23 += __shfl_xor(cnt23, 1, 4);
+        cnt23 += __shfl_xor(cnt23, 2, 4);
+        const double t0 = wFail * static_cast<double>(nCycles - committed);
+        const double t1 = wSpiral * static_cast<double>(n_source(1));
+        const double t2 = wNone * static_cast<double>(n_source(2) + n_source(3));
+        const double t3 = wDeviation * dev;
+        double q = t0 + t1;
+        q = q + t2;
+        q = q + t3;
+        return q;
+    }
+};
+
+// The bitonic network over s[0, N) in LDS (N a power of two, the keys in place and a barrier behind them), ascending, by the
+// workgroup's kLanes lanes.  Declares no shared memory of its own: the kernels hand theirs.
+template <int kLanes>
+__device__ __forceinline__ void rank_sort_lds(RankKey* s, int N, int tid) {
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < (N >> 1); i += kLanes) {
+                const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1)), c = a | j;
+                const RankKey ka = s[a], kc = s[c];
+                const bool up = (a & k) == 0;
+                if (rank_key_less(kc, ka) == up) {
+                    s[a] = kc;
+                    s[c] = ka;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
 
 // One pose per group of four lanes, lane = leg: each lane loads its leg's records, the four values of a cycle meet by shuffle
 // and every lane of the group runs the same f64 chain on them in the stated order (lane 0 writes).
@@ -52,35 +132,23 @@ __device__ __forceinline__ void rank_summary_body(const fpe_pose* __restrict__ p
     double cur[4];
 #pragma unroll
     for (int l = 0; l < 4; ++l) cur[l] = __shfl(cx, l, 4);
-    uint32_t cnt01 = 0, cnt23 = 0;  // this leg's records by source, 16 bits each
-    int committed = 0, succeed = 0, firstFailed = 255, lastOk = 0, nKpi = 0;
-    double dev = 0.0, spSum = 0.0, spMin = 0.0, spMax = 0.0, fdMin = 0.0, fdMax = 0.0;
+    PenaltyAcc acc;
+    int succeed = 0, firstFailed = 255, lastOk = 0, nKpi = 0;
+    double spSum = 0.0, spMin = 0.0, spMax = 0.0, fdMin = 0.0, fdMax = 0.0;
     const size_t rec0 = static_cast<size_t>(bb) * nCycles * 4 + leg;
     for (int g = 0; g < nCycles; ++g) {
         const size_t q = rec0 + static_cast<size_t>(g) * 4;
         const fpe_foothold& f = nominal[q];
-        const double x = f.x, y = f.y;
-        const uint32_t src = f.source & 3u;
-        const double dx = x - defaultNext[q * 3], dy = y - defaultNext[q * 3 + 1];
-        const double term = dx * dx + dy * dy;
+        const double x = f.x;
         const int ok = cycleOk[static_cast<size_t>(bb) * nCycles + g] != 0;
-        if (src < 2) cnt01 += 1u << (16 * src);
-        else cnt23 += 1u << (16 * (src - 2));
-        double r[4], d[4];
+        double r[4];
 #pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            r[l] = __shfl(x, l, 4);
-            d[l] = __shfl(term, l, 4);
-        }
+        for (int l = 0; l < 4; ++l) r[l] = __shfl(x, l, 4);
+        acc.cycle(f, defaultNext + q * 3, ok);
         lastOk = ok;
         if (!ok && firstFailed == 255) firstFailed = g;
         if (!ok) continue;  // (uniform within the pose's four lanes; the shuffles above ran with every lane)
-        ++committed;
         succeed = g + 1;
-        dev = dev + d[RF];
-        dev = dev + d[RH];
-        dev = dev + d[LH];
-        dev = dev + d[LF];
         if (trot) {  // assemble_track_report (fpe_host.cpp), nominal track
             const double fd0 = r[RF] - r[LH], fd1 = r[LF] - r[RH];
             double c1, c2, c3;
@@ -113,52 +181,28 @@ __device__ __forceinline__ void rank_summary_body(const fpe_pose* __restrict__ p
             for (int l = 0; l < 4; ++l) cur[l] = r[l];
         }
     }
-    cnt01 += __shfl_xor(cnt01, 1, 4);
-    cnt01 += __shfl_xor(cnt01, 2, 4);
-    cnt23 += __shfl_xor(cnt23, 1, 4);
-    cnt23 += __shfl_xor(cnt23, 2, 4);
+    double sc = acc.finish(rc.wFail, rc.wSpiral, rc.wNone, rc.wDeviation, nCycles);
     if (leg != 0 || b >= B) return;
-    const uint32_t n0 = cnt01 & 0xFFFFu, n1 = cnt01 >> 16, n2 = cnt23 & 0xFFFFu, n3 = cnt23 >> 16;
     fpe_pose_summary s;
     s.success = static_cast<uint8_t>(lastOk);
     s.gait_cycles_succeed = static_cast<uint8_t>(succeed);
-    s.committed = static_cast<uint8_t>(committed);
+    s.committed = static_cast<uint8_t>(acc.committed);
     s.first_failed = static_cast<uint8_t>(firstFailed);
     s.pose_status = poseStatus[b];
     s.pad[0] = s.pad[1] = s.pad[2] = 0;
-    s.n_source[0] = static_cast<uint16_t>(n0);
-    s.n_source[1] = static_cast<uint16_t>(n1);
-    s.n_source[2] = static_cast<uint16_t>(n2);
-    s.n_source[3] = static_cast<uint16_t>(n3);
+    for (int q = 0; q < 4; ++q) s.n_source[q] = static_cast<uint16_t>(acc.n_source(q));
     s.cog_speed_sum = spSum;
     s.cog_speed_min = spMin;
     s.cog_speed_max = spMax;
     s.feet_distance_min = fdMin;
     s.feet_distance_max = fdMax;
-    s.deviation_sq_sum = dev;
+    s.deviation_sq_sum = acc.dev;
     summary[b] = s;
-    const double t0 = rc.wFail * static_cast<double>(nCycles - committed);
-    const double t1 = rc.wSpiral * static_cast<double>(n1);
-    const double t2 = rc.wNone * static_cast<double>(n2 + n3);
-    const double t3 = rc.wDeviation * dev;
     const double t4 = rc.wSpeedSpread * (spMax - spMin);
-    double sc = t0 + t1;
-    sc = sc + t2;
-    sc = sc + t3;
     sc = sc + t4;
     if (sc == 0.0) sc = 0.0;  // -0.0 -> +0.0
     score[b] = sc;
-    const bool finite = __builtin_isfinite(sc);
-    const unsigned long long cls = !finite ? 2ull : (succeed < rc.minCycles ? 1ull : 0ull);
-    unsigned long long img = 0ull;
-    if (finite) {
-        const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(sc));
-        img = (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
-    }
-    RankKey k;
-    k.hi = (cls << 32) | (img >> 32);
-    k.lo = (img << 32) | static_cast<unsigned long long>(static_cast<uint32_t>(b));
-    keys[b] = k;
+    keys[b] = rank_key(sc, static_cast<uint32_t>(b), succeed < rc.minCycles ? 1ull : 0ull, 2ull);
 }
 __global__ __launch_bounds__(256) void rank_summary_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, RankConsts rc,
                                                            const fpe_foothold* __restrict__ nominal, const double* __restrict__ defaultNext,
@@ -206,20 +250,7 @@ __global__ __launch_bounds__(1024) void rank_select_kernel(const RankKey* __rest
     for (int o = 32; o > 0; o >>= 1) c0 += __shfl_xor(c0, o, 64);
     if ((tid & 63) == 0) waveCount[tid >> 6] = c0;
     __syncthreads();
-    for (int k = 2; k <= N; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < (N >> 1); i += 1024) {
-                const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1)), c = a | j;
-                const RankKey ka = s[a], kc = s[c];
-                const bool up = (a & k) == 0;
-                if (rank_key_less(kc, ka) == up) {
-                    s[a] = kc;
-                    s[c] = ka;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    rank_sort_lds<1024>(s, N, tid);
     if (tileOut) {
         for (int i = tid; i < K; i += 1024) tileOut[static_cast<size_t>(blockIdx.x) * K + i] = i < N ? s[i] : none;
     } else {
@@ -239,22 +270,43 @@ __global__ __launch_bounds__(1024) void rank_select_kernel(const RankKey* __rest
     }
 }
 
-// Slot blockIdx.x takes pose best[blockIdx.x]: every requested product's block of that pose, word by word.
+// Block `from` of one product to block `to`, word by word, by the workgroup's 256 lanes
 template <class Word>
-__device__ __forceinline__ void rank_copy_words(const RankCopy& c, size_t pose, size_t slot) {
-    const Word* src = reinterpret_cast<const Word*>(c.src) + pose * c.words;
-    Word* dst = reinterpret_cast<Word*>(c.dst) + slot * c.words;
+__device__ __forceinline__ void rank_copy_words(const RankCopy& c, size_t from, size_t to) {
+    const Word* src = reinterpret_cast<const Word*>(c.src) + from * c.words;
+    Word* dst = reinterpret_cast<Word*>(c.dst) + to * c.words;
     for (uint32_t i = threadIdx.x; i < c.words; i += 256) dst[i] = src[i];
 }
-__global__ __launch_bounds__(256) void rank_gather_kernel(const int32_t* __restrict__ best, RankCopies cp) {
-    const size_t slot = blockIdx.x;
-    const size_t pose = static_cast<size_t>(best[slot]);
+// Block `from` of every product to block `to`
+__device__ __forceinline__ void rank_copy_blocks(const RankCopies& cp, size_t from, size_t to) {
     for (int p = 0; p < cp.n; ++p) {
         const RankCopy& c = cp.c[p];
-        if (c.unit == 16) rank_copy_words<uint4>(c, pose, slot);
-        else if (c.unit == 4) rank_copy_words<uint32_t>(c, pose, slot);
-        else rank_copy_words<unsigned char>(c, pose, slot);
+        if (c.unit == 16) rank_copy_words<uint4>(c, from, to);
+        else if (c.unit == 4) rank_copy_words<uint32_t>(c, from, to);
+        else rank_copy_words<unsigned char>(c, from, to);
     }
+}
+// Slot blockIdx.x takes pose best[blockIdx.x]: every requested product's block of that pose
+__global__ __launch_bounds__(256) void rank_gather_kernel(const int32_t* __restrict__ best, RankCopies cp) {
+    const size_t slot = blockIdx.x;
+    rank_copy_blocks(cp, static_cast<size_t>(best[slot]), slot);
+}
+
+// The copies of the plan products both structs hold, from the product table: blocks of `cycles` gait cycles (one pose of a
+// ranking, one segment of a beam), the destination's blocks counted from block dstBlockOffset.
+inline RankCopies plan_copies(const fpe_plan_out& from, const fpe_plan_out& to, int cycles, size_t dstBlockOffset) {
+    RankCopies cp;
+    cp.n = 0;
+    for (int k = 0; k < kPlanProducts; ++k) {
+        const unsigned char* src = static_cast<const unsigned char*>(slots(from)[k]);
+        unsigned char* dst = static_cast<unsigned char*>(slots(to)[k]);
+        if (!src || !dst) continue;
+        const size_t bytes = product_bytes(k, 1, static_cast<size_t>(cycles));
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | bytes;
+        const uint32_t unit = (bits & 15) == 0 ? 16u : ((bits & 3) == 0 ? 4u : 1u);
+        cp.c[cp.n++] = RankCopy{src, dst + dstBlockOffset * bytes, static_cast<uint32_t>(bytes / unit), unit};
+    }
+    return cp;
 }
 
 inline size_t rank_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
@@ -328,24 +380,7 @@ hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int
                        counts, nCounts);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    RankCopies cp;
-    cp.n = 0;
-    const auto add = [&](const void* src, void* dst, size_t bytesPerPose) {
-        if (!dst) return;
-        const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | bytesPerPose;
-        const uint32_t unit = (bits & 15) == 0 ? 16u : ((bits & 3) == 0 ? 4u : 1u);
-        cp.c[cp.n++] = RankCopy{static_cast<const unsigned char*>(src), static_cast<unsigned char*>(dst),
-                                static_cast<uint32_t>(bytesPerPose / unit), unit};
-    };
-    const size_t nRec = static_cast<size_t>(nCycles) * 4;
-    add(full.nominal, bestProducts.nominal, nRec * sizeof(fpe_foothold));
-    add(full.centroid, bestProducts.centroid, nRec * sizeof(fpe_centroid_foothold));
-    add(full.default_next, bestProducts.default_next, nRec * 3 * sizeof(double));
-    add(full.cycle_ok, bestProducts.cycle_ok, static_cast<size_t>(nCycles));
-    add(full.stance, bestProducts.stance, 12 * sizeof(double));
-    add(full.selected, bestProducts.selected, nRec * sizeof(fpe_selected_foothold));
-    add(full.pose_status, bestProducts.pose_status, 1);
-    add(full.selected_packed, bestProducts.selected_packed, nRec * sizeof(fpe_selected_packed));
+    const RankCopies cp = plan_copies(full, bestProducts, nCycles, 0);
     if (cp.n == 0) return hipSuccess;
     hipLaunchKernelGGL(rank_gather_kernel, dim3(K), dim3(256), 0, stream, d_best, cp);
     return hipGetLastError();

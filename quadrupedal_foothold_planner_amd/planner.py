@@ -104,6 +104,21 @@ def make_plan_states(params, poses=None, strides=None, feet=None, adjusted_y=0.0
 TUNING_DEFAULTS = {"service_opt_gate": 2, "service_overlap": 1, "service_poll": 1}
 
 
+def _fill_products(po, addresses):
+    """Set the fields of a PlanOut from {product name: address} — an array's ptr(), a device address, or 0 / None: not wanted."""
+    for k, p in addresses.items():
+        setattr(po, PRODUCT_FIELDS[k], p or None)
+    return po
+
+
+def _call_params(given, struct, defaults):
+    """The parameter block of a ranking / beam call: None (the engine's defaults), a `struct` instance, or a dict of its fields to
+    replace in `defaults()`."""
+    if given is None or isinstance(given, struct):
+        return given
+    return defaults(**dict(given))
+
+
 def _map_desc(rows, cols, resolution, position=(0.0, 0.0), start_index=(0, 0), storage_order="row"):
     return MapDesc(rows, cols, float(resolution), (C.c_double * 2)(*map(float, position)),
                    (C.c_int32 * 2)(*map(int, start_index)), 1 if storage_order == "row" else 0)
@@ -336,7 +351,6 @@ class FootholdPlanner(_Handle):
         poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
         B = poses.shape[0]
         shapes = product_shapes(B, n_cycles)
-        fields = PRODUCT_FIELDS
         if out is None:
             out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in products}
         else:  # the arrays of `out` are the products asked for (whatever `products` says)
@@ -349,10 +363,9 @@ class FootholdPlanner(_Handle):
         if cached is not None and cached[0] == key:
             po = cached[1]
         else:
-            po = PlanOut()
             for k in products:
                 assert out[k].shape == shapes[k][0] and out[k].dtype == shapes[k][1]
-                setattr(po, fields[k], ptr(out[k]))
+            po = _fill_products(PlanOut(), {k: ptr(out[k]) for k in products})
             self._plan_out_cache = (key, po, out)
         if strides is None:
             self._check(self._lib.fpe_plan(self._h, ptr(self.params), ptr(poses), B, int(n_cycles), C.byref(po)))
@@ -383,9 +396,7 @@ class FootholdPlanner(_Handle):
                 raise ValueError(f"states must hold one element per pose: shape {states.shape}, {B} poses")
         shapes = product_shapes(B, n_cycles)
         out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in PRODUCT_ORDER if k in products}
-        po = PlanOut()
-        for k in out:
-            setattr(po, PRODUCT_FIELDS[k], ptr(out[k]))
+        po = _fill_products(PlanOut(), {k: ptr(a) for k, a in out.items()})
         state_out = np.zeros(B, dtype=PLAN_STATE_DTYPE) if want_state else None
         self._check(self._lib.fpe_plan_resume(self._h, ptr(self.params), ptr(poses), ptr(_strides_for(strides, B)) if strides is not None else None,
                                               ptr(states), B, int(n_cycles), C.byref(po), ptr(state_out)))
@@ -394,22 +405,13 @@ class FootholdPlanner(_Handle):
     def plan_resume_device(self, d_poses_ptr, B, n_cycles, d_out, d_state_in_ptr=0, d_state_out_ptr=0, d_strides_ptr=0, stream=0):
         """fpe_plan_resume_device: `d_out` maps product names to device pointers; the state pointers are device arrays of B
         fpe_plan_state elements (0: none; the two may be the same array).  Asynchronous on `stream`."""
-        po = PlanOut()
-        for k, p in d_out.items():
-            setattr(po, PRODUCT_FIELDS[k], C.c_void_p(p) if p else None)
+        po = _fill_products(PlanOut(), d_out)
         self._check(self._lib.fpe_plan_resume_device(self._h, ptr(self.params), C.c_void_p(d_poses_ptr), C.c_void_p(d_strides_ptr or 0) if d_strides_ptr else None,
                                                      C.c_void_p(d_state_in_ptr) if d_state_in_ptr else None, int(B), int(n_cycles), C.byref(po),
                                                      C.c_void_p(d_state_out_ptr) if d_state_out_ptr else None, C.c_void_p(stream or 0)))
 
     # ---- beam search over stride options on resumable plans (build-defined: fpe_plan_beam*) ---------------------------------
     BEAM_PRODUCTS = ("nominal", "centroid", "default", "cycle_ok", "selected", "selected_packed")  # what a beam's plans can return
-
-    @staticmethod
-    def _beam_params(beam):
-        """None (the defaults), a _capi.BeamParams, or a dict of its fields to replace."""
-        if beam is None or isinstance(beam, _capi.BeamParams):
-            return beam
-        return _capi.beam_params_defaults(**dict(beam))
 
     def plan_beam(self, poses, options, beam=None, states=None, products=("nominal", "cycle_ok")):
         """fpe_plan_beam with host buffers: for every root pose a beam search over the stride `options` (an fpe_stride array,
@@ -428,7 +430,7 @@ class FootholdPlanner(_Handle):
             states = np.ascontiguousarray(states, dtype=PLAN_STATE_DTYPE)
             if states.shape != (B,):
                 raise ValueError(f"states must hold one element per pose: shape {states.shape}, {B} poses")
-        bp = self._beam_params(beam)
+        bp = _call_params(beam, _capi.BeamParams, _capi.beam_params_defaults)
         shape = bp if bp is not None else _capi.beam_params_defaults()
         S, k, W = max(int(shape.segments), 1), max(int(shape.cycles_per_segment), 1), max(int(shape.width), 1)
         shapes = product_shapes(B * W, S * k)
@@ -436,8 +438,7 @@ class FootholdPlanner(_Handle):
         out.update(path=np.zeros((B, W, S), np.uint8), score=np.zeros((B, W)), penalty=np.zeros((B, W)), n_live=np.zeros(B, np.int32),
                    state=np.zeros((B, W), PLAN_STATE_DTYPE))
         bo = _capi.BeamOut(ptr(out["n_live"]), ptr(out["score"]), ptr(out["penalty"]), ptr(out["path"]), ptr(out["state"]))
-        for q in products:
-            setattr(bo.products, PRODUCT_FIELDS[q], ptr(out[q]))
+        _fill_products(bo.products, {q: ptr(out[q]) for q in products})
         self._check(self._lib.fpe_plan_beam(self._h, ptr(self.params), C.byref(bp) if bp is not None else None, ptr(poses), ptr(states), B,
                                             ptr(options), M, C.byref(bo)))
         for q in products:
@@ -449,9 +450,8 @@ class FootholdPlanner(_Handle):
         """fpe_plan_beam_device: DEVICE pointers (0 / missing = not wanted), asynchronous on `stream`.  products: {product name:
         device pointer} with plan()'s shapes for B * W poses and S * k cycles."""
         bo = _capi.BeamOut(d_n_live_ptr or None, d_score_ptr or None, d_penalty_ptr or None, d_path_ptr or None, d_state_ptr or None)
-        for q, p in (products or {}).items():
-            setattr(bo.products, PRODUCT_FIELDS[q], p or None)
-        bp = self._beam_params(beam)
+        _fill_products(bo.products, products or {})
+        bp = _call_params(beam, _capi.BeamParams, _capi.beam_params_defaults)
         self._check(self._lib.fpe_plan_beam_device(self._h, ptr(self.params), C.byref(bp) if bp is not None else None, C.c_void_p(d_poses_ptr),
                                                    C.c_void_p(d_state_in_ptr) if d_state_in_ptr else None, int(B), C.c_void_p(d_options_ptr), int(M),
                                                    C.byref(bo), C.c_void_p(stream or 0)))
@@ -471,13 +471,6 @@ class FootholdPlanner(_Handle):
                                                           int(B), int(n_cycles), C.byref(po), C.c_void_p(stream or 0)))
 
     # ---- plan a batch and rank it on the device (build-defined: fpe_plan_rank*) ---------------------------------------------
-    @staticmethod
-    def _rank_params(rank):
-        """None (the defaults), a _capi.RankParams, or a dict of its fields to replace."""
-        if rank is None or isinstance(rank, _capi.RankParams):
-            return rank
-        return _capi.rank_params_defaults(**dict(rank))
-
     def plan_rank(self, poses, n_cycles, K, rank=None, products=("nominal", "cycle_ok", "stance"), summary=True, strides=None):
         """fpe_plan_rank with host buffers: plans the batch, scores every pose on the device and returns {"best": int32 [K] pose
         indices, best first, "n_class0": int, "summary": POSE_SUMMARY_DTYPE [B] and "score": float64 [B] (with summary=True),
@@ -497,9 +490,8 @@ class FootholdPlanner(_Handle):
             out["summary"] = np.zeros(B, _capi.POSE_SUMMARY_DTYPE)
             out["score"] = np.zeros(B, np.float64)
             ro.summary, ro.score = ptr(out["summary"]), ptr(out["score"])
-        for k in products:
-            setattr(ro.best_products, PRODUCT_FIELDS[k], ptr(out[k]))
-        rp = self._rank_params(rank)
+        _fill_products(ro.best_products, {k: ptr(out[k]) for k in products})
+        rp = _call_params(rank, _capi.RankParams, _capi.rank_params_defaults)
         if strides is None:
             self._check(self._lib.fpe_plan_rank(self._h, ptr(self.params), C.byref(rp) if rp is not None else None, ptr(poses), B,
                                                 int(n_cycles), K, C.byref(ro)))
@@ -514,14 +506,9 @@ class FootholdPlanner(_Handle):
         """Device form: DEVICE pointers (0 / missing = not wanted), asynchronous on `stream`.  best_products / full: dicts
         {product name: device pointer} of the K-slot compacted products and of the un-compacted products of all B poses."""
         ro = RankOut(d_summary_ptr or None, d_score_ptr or None, d_best_ptr or None, d_n_class0_ptr or None)
-        for k, p in (best_products or {}).items():
-            setattr(ro.best_products, PRODUCT_FIELDS[k], p or None)
-        fo = None
-        if full is not None:
-            fo = PlanOut()
-            for k, p in full.items():
-                setattr(fo, PRODUCT_FIELDS[k], p or None)
-        rp = self._rank_params(rank)
+        _fill_products(ro.best_products, best_products or {})
+        fo = _fill_products(PlanOut(), full) if full is not None else None
+        rp = _call_params(rank, _capi.RankParams, _capi.rank_params_defaults)
         self._check(self._lib.fpe_plan_rank_strides_device(self._h, ptr(self.params), C.byref(rp) if rp is not None else None,
                                                            C.c_void_p(d_poses_ptr), C.c_void_p(d_strides_ptr or 0), int(B), int(n_cycles),
                                                            int(K), C.byref(fo) if fo is not None else None, C.byref(ro),
