@@ -35,6 +35,8 @@ struct Unit {
     uint32_t pad[2];
 };
 static_assert(sizeof(Unit) == 144 && sizeof(Unit) % 16 == 0 && offsetof(Unit, visA) == 80 && offsetof(Unit, cx) == 112, "Unit layout");
+// three consecutive cells of a layer row / three consecutive floats of Unit::eA / eB, at a 4-byte boundary (leg_fast8m)
+typedef float UnitRow3 __attribute__((ext_vector_type(3), aligned(4)));
 
 // 3x3 form: lane s holds cell s + (s >= 4) of the box, every lane the middle cell (disc_issue); else the direct pass.
 template <bool kWant>
@@ -831,7 +833,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
         sm.baseX = subPosX + (subOrgX - 0.5 * m.g.res);
         sm.baseY = ye.sbaseY;
     }
-    // ---- same round trip: the elevation of both discs (lane = cell t of the 3x3 boxes) ----
+    // ---- same round trip: membership (lane = cell t of the 3x3 boxes) and elevation (lane = box row) of both discs ----
     const int t = g.sub + (g.sub >= 4 ? 1 : 0);
     const int a = t >= 6 ? 2 : (t >= 3 ? 1 : 0);
     const int bq = t - 3 * a;
@@ -840,17 +842,32 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
     const double dxB = cell_pos(m.g.baseX, m.g.res, i0f + a) - nx0;
     const bool visA = (dxA * dxA + dy2) <= hc.rf2;  // CircleIterator::isInside (cell_in_disc)
     const bool visB = kNoDefault ? false : (dxB * dxB + dy2) <= hc.rf2;
+    // The elevations for flush_unit, a box ROW per lane: lane L reads row min(L >> 1, 2) of the centre disc's box (even L) or of
+    // the default-track disc's (odd L; kNoDefault: every lane the centre disc's) with ONE 12-byte load — 4-byte aligned; inside
+    // the map: `boxes` above, and the rare path has left — and deposits it with one LDS store pair; lanes 6 and 7 repeat lanes 4
+    // and 5 (the same value to the same address: no predicate).  By cell — lane = cell t, the middle cell apart — it is four loads,
+    // four address sums and four LDS stores a cycle; the <4, true, *> instances, at the cap of 256 vector registers, keep that
+    // form (by row: five registers spilled, 24 bytes of scratch).
     // (32-bit cell offsets from the uniform layer base: bits_supported bounds the layer below 2 GiB)
+    constexpr bool kByRow = NRL < 4;
     const unsigned colsU = static_cast<unsigned>(m.g.cols);
-    const unsigned laneCell = __umul24(static_cast<unsigned>(a), colsU) + static_cast<unsigned>(bq);
-    const unsigned boxA = __umul24(static_cast<unsigned>(i0d), colsU) + static_cast<unsigned>(j0d);
-    const unsigned boxB = __umul24(static_cast<unsigned>(i0f), colsU) + static_cast<unsigned>(j0d);
-    const float eA = load_cell(m.elev, boxA + laneCell);
-    const float eMidA = load_cell(m.elev, boxA + colsU + 1u);
-    float eB = 0.0f, eMidB = 0.0f;
-    if constexpr (!kNoDefault) {
-        eB = load_cell(m.elev, boxB + laneCell);
-        eMidB = load_cell(m.elev, boxB + colsU + 1u);
+    const int rowL = min(g.sub >> 1, 2);
+    const bool laneB = !kNoDefault && (g.sub & 1) != 0;
+    UnitRow3 eRow = {};
+    float eA = 0.0f, eMidA = 0.0f, eB = 0.0f, eMidB = 0.0f;
+    if constexpr (kByRow) {
+        const unsigned boxRowCell = __umul24(static_cast<unsigned>((laneB ? i0f : i0d) + rowL), colsU) + static_cast<unsigned>(j0d);
+        eRow = *reinterpret_cast<const UnitRow3*>(reinterpret_cast<const char*>(m.elev) + static_cast<size_t>(boxRowCell << 2));
+    } else {
+        const unsigned laneCell = __umul24(static_cast<unsigned>(a), colsU) + static_cast<unsigned>(bq);
+        const unsigned boxA = __umul24(static_cast<unsigned>(i0d), colsU) + static_cast<unsigned>(j0d);
+        const unsigned boxB = __umul24(static_cast<unsigned>(i0f), colsU) + static_cast<unsigned>(j0d);
+        eA = load_cell(m.elev, boxA + laneCell);
+        eMidA = load_cell(m.elev, boxA + colsU + 1u);
+        if constexpr (!kNoDefault) {
+            eB = load_cell(m.elev, boxB + laneCell);
+            eMidB = load_cell(m.elev, boxB + colsU + 1u);
+        }
     }
     // In the shadow of that round trip: whether this lane's row of the five around the centre (FastRanks) lies in the search
     // rectangle, which only a spiral search uses — but most wavefronts have one leg in eight that needs it (88 % of the
@@ -887,11 +904,18 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
     }
     const bool defaultOk = !g.any(fail);  // the middle cell is always visited (cpp:2069-2081: at least one cell)
     // ---- deposits for flush_unit: elevations in CircleIterator order ----
-    unit->eA[t] = eA;
-    unit->eA[4] = eMidA;  // every lane stores the same value
-    if constexpr (!kNoDefault) {
-        unit->eB[t] = eB;
-        unit->eB[4] = eMidB;
+    if constexpr (kByRow) {
+        float* eDst = (laneB ? unit->eB : unit->eA) + 3 * rowL;
+        eDst[0] = eRow.x;
+        eDst[1] = eRow.y;
+        eDst[2] = eRow.z;
+    } else {
+        unit->eA[t] = eA;
+        unit->eA[4] = eMidA;  // every lane stores the same value
+        if constexpr (!kNoDefault) {
+            unit->eB[t] = eB;
+            unit->eB[4] = eMidB;
+        }
     }
     // ---- centroid method (cpp:1684-1952) as selects ----
     const int bottomRow = sm.ni - 1, rightCol = sm.nj - 1;
@@ -1235,80 +1259,128 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
         hwSlot &= 15u;
     }
     constexpr int kPrioSwapEighths = 3;
-    for (int cyc = 0; cyc < nCycles; ++cyc) {
-        if (kMid && cyc == (nCycles * kPrioSwapEighths) / 8 && (hwSlot & 1u)) __builtin_amdgcn_s_setprio(2);
-        if ((cyc & (kBatch - 1)) == 0) {
-            // y side of the next kBatch cycles: lane (leg, s) fills the entry of cycle cyc + s.  ajustedPose_[1] is the
-            // reference's running sum (cpp:1578): cycle cyc + s has seen s more additions of the drift
-            double a = adjY, mine = adjY;
+    if constexpr (kMid) {
+        // 3x3-only kernels: a loop nest by batch of eight cycles — the y fill, the batch's cycles, the flush.  What happens once per
+        // batch is placed by the outer loop, not tested in every cycle (in the flat form below: three scalar compares and branches a
+        // cycle, the fill's block inside the cycle loop, and the entry / unit / okBits positions re-formed from cyc & 7), and the
+        // inner loop walks the y entries and the units by pointer.  Every store, LDS write and bits_sync in the flat form's order.
+        const int prioCyc = (hwSlot & 1u) ? (nCycles * kPrioSwapEighths) / 8 : -1;  // the cycle of the hand-over (none: -1)
+        for (int c0 = 0; c0 < nCycles; c0 += kBatch) {
+            {
+                // y side of the batch's cycles: lane (leg, s) fills the entry of cycle c0 + s.  ajustedPose_[1] is the
+                // reference's running sum (cpp:1578): cycle c0 + s has seen s more additions of the drift
+                double a = adjY, mine = adjY;
 #pragma unroll
-            for (int k = 1; k < kBatch; ++k) {
-                a += hc.drift;
-                if (g.sub == k) mine = a;
-            }
-            if constexpr (kMid) {  // (its constants from the vector registers they are parked in)
-                const YFillConsts yc{hc.rf, hc.cornerEps, pc.winH};
+                for (int k = 1; k < kBatch; ++k) {
+                    a += hc.drift;
+                    if (g.sub == k) mine = a;
+                }
+                const YFillConsts yc{hc.rf, hc.cornerEps, pc.winH};  // (its constants from the vector registers they are parked in)
                 fill_yentry(m.g, yc, ls, (y0 + mine) + ls.biasY, ytab[g.sub]);  // cpp:2201, 2414
-            } else if (g.sub < kBatch) {
-                fill_yentry(m.g, pc, ls, (y0 + mine) + ls.biasY, ytab[g.sub]);
+                bits_sync<G>();
             }
-            bits_sync<G>();
+            const int nb = min(kBatch, nCycles - c0);  // (the last batch may be short)
+            const YEntry* yeP = ytab;
+            UnitT* unit = units;
+            for (int s = 0; s < nb; ++s, ++yeP, ++unit) {
+                const int cyc = c0 + s;
+                if (cyc == prioCyc) __builtin_amdgcn_s_setprio(2);
+                const YEntry& ye = *yeP;
+                bool cycleOk = true;
+                for (int ph = 0; ph < nPhases; ++ph) {  // (the phases: see the flat form below)
+                    const unsigned mask = (!kPlain && gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
+                    const bool active = kPlain || ((mask >> leg) & 1u) != 0u;  // (plain: every leg swings in the one phase)
+                    double myCtr = stanceCtr;
+                    if (!kStanceOnce || cyc != 0 || ph != 0) myCtr = polygon_center_x(sh.cur[myTrack]);  // (wave-uniform branch)
+                    LegCommit lc;
+                    lc.valid = 1;  // non-swing legs do not vote
+                    if (active)
+                        leg_fast8m<NRL, kNoDefault, kProd, kPlain>(m, bm, pc.winH, wantDefault, hc, role, fr, head, sh, lb, g, leg, ls, ye, myCtr, advance, cyc,
+                                                                   &lc, unit);
+                    const bool phaseOk = (__ballot(lc.valid == 0) & poseMask) == 0ull;
+                    if (phaseOk && active && g.sub == 0) {
+#pragma unroll
+                        for (int t = 0; t < 3; ++t) {
+                            sh.cur[t][leg][0] = lc.v[t][0];
+                            sh.cur[t][leg][1] = lc.v[t][1];
+                        }
+                    }
+                    bits_sync<G>();
+                    cycleOk = cycleOk && phaseOk;
+                }
+                adjY += hc.drift;  // cpp:1578
+                okBits |= (cycleOk ? 1u : 0u) << s;  // (bit cyc & 7, as flush_unit reads it)
+            }
+            {
+                // heights, output records and cycle validity of the batch's cycles: lane (leg, s) takes the unit of cycle c0 + s
+                // (once per eight cycles: h and the product pointers from the argument segment, see MidKernArgs)
+                const MidKernArgs* ka = mid_cold_args();
+                const double hF = ka->pc.h;
+                const fpe_plan_out outF = specialise_products<kProd>(ka->out);
+                if (live && g.sub < nb) flush_unit(m, hF, units[g.sub], ytab[g.sub], b, c0 + g.sub, leg, nCycles, okBits, outF);
+                okBits = 0u;
+                bits_sync<G>();  // the units and the y entries are rewritten next
+            }
         }
-        const YEntry& ye = ytab[cyc & (kBatch - 1)];
-        bool cycleOk = true;
-        for (int ph = 0; ph < nPhases; ++ph) {
-            const unsigned mask = (!kPlain && gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
-            const bool active = kPlain || ((mask >> leg) & 1u) != 0u;  // (plain: every leg swings in the one phase)
-            // feet-polygon centres (getPolygonCenter, cpp:2191, 2265): every lane computes ONE track's centre from the
-            // committed feet in LDS; the values reach the group's other lanes by swizzle (no LDS hand-off, no barrier)
-            double myCtr = stanceCtr;
-            if (!kStanceOnce || cyc != 0 || ph != 0) myCtr = polygon_center_x(sh.cur[myTrack]);  // (wave-uniform branch)
-            // footholdValidation_ (cpp:1323) is a ballot over the pose's lanes; the committed positions go from
-            // registers straight to PoseShared::cur (cpp:1332-1576)
-            LegCommit lc;
-            lc.valid = 1;  // non-swing legs do not vote
-            if (active) {
-                if constexpr (kMid) {
-                    leg_fast8m<NRL, kNoDefault, kProd, kPlain>(m, bm, pc.winH, wantDefault, hc, role, fr, head, sh, lb, g, leg, ls, ye, myCtr, advance, cyc, &lc,
-                                                       units + (cyc & (kBatch - 1)));
-                } else {
+    } else {
+        // generic kernels: the flat loop over the cycles (as a nest these kernels, at their cap of 168 vector registers, spill more:
+        // <3, false, 2> 12 -> 28 bytes of scratch, <4, false, 2> 48 -> 56, the stride form <3> 8 -> 28)
+        for (int cyc = 0; cyc < nCycles; ++cyc) {
+            if ((cyc & (kBatch - 1)) == 0) {
+                // y side of the next kBatch cycles: lane (leg, s) fills the entry of cycle cyc + s.  ajustedPose_[1] is the
+                // reference's running sum (cpp:1578): cycle cyc + s has seen s more additions of the drift
+                double a = adjY, mine = adjY;
+#pragma unroll
+                for (int k = 1; k < kBatch; ++k) {
+                    a += hc.drift;
+                    if (g.sub == k) mine = a;
+                }
+                if (g.sub < kBatch) fill_yentry(m.g, pc, ls, (y0 + mine) + ls.biasY, ytab[g.sub]);  // cpp:2201, 2414
+                bits_sync<G>();
+            }
+            const YEntry& ye = ytab[cyc & (kBatch - 1)];
+            bool cycleOk = true;
+            for (int ph = 0; ph < nPhases; ++ph) {
+                const unsigned mask = (!kPlain && gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
+                const bool active = kPlain || ((mask >> leg) & 1u) != 0u;  // (plain: every leg swings in the one phase)
+                // feet-polygon centres (getPolygonCenter, cpp:2191, 2265): every lane computes ONE track's centre from the
+                // committed feet in LDS; the values reach the group's other lanes by swizzle (no LDS hand-off, no barrier)
+                double myCtr = stanceCtr;
+                if (!kStanceOnce || cyc != 0 || ph != 0) myCtr = polygon_center_x(sh.cur[myTrack]);  // (wave-uniform branch)
+                // footholdValidation_ (cpp:1323) is a ballot over the pose's lanes; the committed positions go from
+                // registers straight to PoseShared::cur (cpp:1332-1576)
+                LegCommit lc;
+                lc.valid = 1;  // non-swing legs do not vote
+                if (active) {
                     constexpr int kKeep = (~(G - 1)) & 0x1F;
                     const double ctr0 = swizzle_f64<kKeep | (0 << 5)>(myCtr), ctr1 = swizzle_f64<kKeep | (1 << 5)>(myCtr),
                                  ctr2 = swizzle_f64<kKeep | (2 << 5)>(myCtr);
                     leg_phase_bits8<NRL, false>(m, bm, pc, lut, head, sh, lb, g, leg, ls, ye, ctr0, ctr1, ctr2, advance, cyc, out, &lc,
                                                 units + (cyc & (kBatch - 1)));
                 }
-            }
-            const bool phaseOk = (__ballot(lc.valid == 0) & poseMask) == 0ull;
-            if (phaseOk && active && g.sub == 0) {
+                const bool phaseOk = (__ballot(lc.valid == 0) & poseMask) == 0ull;
+                if (phaseOk && active && g.sub == 0) {
 #pragma unroll
-                for (int t = 0; t < 3; ++t) {  // x and y only: no later cycle reads a committed z (getPolygonCenter, cpp:2421-2463)
-                    sh.cur[t][leg][0] = lc.v[t][0];
-                    sh.cur[t][leg][1] = lc.v[t][1];
+                    for (int t = 0; t < 3; ++t) {  // x and y only: no later cycle reads a committed z (getPolygonCenter, cpp:2421-2463)
+                        sh.cur[t][leg][0] = lc.v[t][0];
+                        sh.cur[t][leg][1] = lc.v[t][1];
+                    }
                 }
+                bits_sync<G>();
+                cycleOk = cycleOk && phaseOk;
             }
-            bits_sync<G>();
-            cycleOk = cycleOk && phaseOk;
-        }
-        adjY += hc.drift;  // cpp:1578
-        okBits |= (cycleOk ? 1u : 0u) << (cyc & 7);
-        if ((cyc & (kBatch - 1)) == kBatch - 1 || cyc == nCycles - 1) {
-            // heights, output records and cycle validity of the last (up to) kBatch cycles: lane (leg, s) takes the
-            // unit of cycle base + s
-            const int c0 = cyc & ~(kBatch - 1);
-            if constexpr (kMid) {
-                // (once per eight cycles: h and the product pointers from the argument segment, see MidKernArgs)
-                const MidKernArgs* ka = mid_cold_args();
-                const double hF = ka->pc.h;
-                const fpe_plan_out outF = specialise_products<kProd>(ka->out);
-                if (live && c0 + g.sub <= cyc) flush_unit(m, hF, units[g.sub], ytab[g.sub], b, c0 + g.sub, leg, nCycles, okBits, outF);
-            } else {
-                const int us = g.sub >> 1;  // two lanes per unit (kBatch * 2 == G)
+            adjY += hc.drift;  // cpp:1578
+            okBits |= (cycleOk ? 1u : 0u) << (cyc & 7);
+            if ((cyc & (kBatch - 1)) == kBatch - 1 || cyc == nCycles - 1) {
+                // heights, output records and cycle validity of the last (up to) kBatch cycles: two lanes per unit (kBatch * 2 == G),
+                // lanes (leg, 2 s) and (leg, 2 s + 1) take the unit of cycle base + s
+                const int c0 = cyc & ~(kBatch - 1);
+                const int us = g.sub >> 1;
                 if (live && c0 + us <= cyc)
                     flush_unit_g(m, pc, sh.footDa, sh.footDb, units[us], ytab[us], b, c0 + us, leg, g.sub & 1, nCycles, okBits, out, cycBase);
+                okBits = 0u;
+                bits_sync<G>();  // the units and the y entries are rewritten next
             }
-            okBits = 0u;
-            bits_sync<G>();  // the units and the y entries are rewritten next
         }
     }
     if constexpr (kResume) {  // the state behind the last flush (the last phase's commit is behind its bits_sync)
