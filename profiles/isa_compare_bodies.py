@@ -1,10 +1,14 @@
-"""Compare the device code of two builds, symbol by symbol: isa_compare_bodies.py BASE.s HEAD.s [symbol expected to leave ...]
+"""Compare the device code of two builds, symbol by symbol: isa_compare_bodies.py BASE.s HEAD.s [symbol expected to leave | OLD=NEW ...]
 
 BASE.s / HEAD.s: csrc/fpe_kernels.hip compiled with build.py's FLAGS minus -shared, plus --offload-device-only -S.
 Every kernel (.amdhsa_kernel) and every device function (@function) is cut from `<symbol>:` to its `.Lfunc_end`, the
 function-numbered local labels (.LBB<n>_, .Ltmp<n>, .Lfunc_begin<n>) are renumbered away, and the texts are compared; the kernels'
 metadata lines (isa_kernel_metadata.py) are compared as well.  A host-side change leaves every common body identical and the
 symbol sets equal but for what it names as leaving (substrings of demangled names).  Exit status 1 otherwise.
+
+OLD=NEW pairs a kernel of BASE with the kernel of HEAD that replaces it under another name (both as isa_kernel_metadata.py prints
+them, without the namespace: "plan_sequential_stride_kernel=plan_sequential_kernel<fpe_stride const*>").  The pair is compared as one
+common symbol, body and metadata line, with HEAD's symbol name rewritten to BASE's.
 
 One difference follows from a kernel leaving or joining and is accepted only when proved harmless: a kernel that calls a device
 function which uses dynamic LDS passes its ordinal among such kernels in s15 (`s_mov_b32 s15, <id>`), the callee's index into
@@ -30,6 +34,7 @@ def bodies(path):
         body = re.sub(r"((?:\.L|\b)BB)\d+_", r"\1_", body)  # labels (.LBB<n>_<k>) and the loop comments that name them (BB<n>_<k>)
         body = re.sub(r"\.L(tmp|func_begin)\d+", r".L\1", body)
         body = re.sub(r"[ \t]+;", " ;", body)  # (comment columns move with the width of a label)
+        body = re.sub(r"^\t\.section\t\.text\.\S+$", "\t.text", body, flags=re.M)  # (a template's kernel descriptor sits in its own section)
         out[sym] = body
     assert kernels <= set(out), sorted(kernels - set(out))
     return kernels, out
@@ -53,10 +58,31 @@ def demangle(syms):
     return subprocess.run(["c++filt"] + syms, capture_output=True, text=True).stdout.splitlines() if syms else []
 
 
+def short(name):
+    """A demangled kernel name as isa_kernel_metadata.py prints it, without the namespace."""
+    name = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", "").replace("void fpe::", ""))
+    return name[5:] if name.startswith("fpe::") else name
+
+
+def renamed_line(line, names):
+    name = short(line[:80].strip())
+    return f"{names.get(name, name):80s}" + line[80:]
+
+
 def main():
-    base, head, leaving = sys.argv[1], sys.argv[2], sys.argv[3:]
+    base, head = sys.argv[1], sys.argv[2]
+    leaving = [a for a in sys.argv[3:] if "=" not in a]
+    pairs = dict(a.split("=", 1) for a in sys.argv[3:] if "=" in a)
     (kb, fb), (kh, fh) = bodies(base), bodies(head)
     print(f"base: {len(kb)} kernels, {len(fb) - len(kb)} device functions; head: {len(kh)} kernels, {len(fh) - len(kh)} device functions")
+    only_b, only_h = sorted(set(fb) - set(fh)), sorted(set(fh) - set(fb))
+    by_short_b, by_short_h = dict(zip(map(short, demangle(only_b)), only_b)), dict(zip(map(short, demangle(only_h)), only_h))
+    for old, new in pairs.items():
+        so, sn = by_short_b[old], by_short_h[new]  # (KeyError: no such kernel on that side)
+        fh[so] = fh.pop(sn).replace(sn, so)
+        if sn in kh:
+            kh = (kh - {sn}) | {so}
+        print("paired:", old, "=", new)
     gone, new = demangle(set(fb) - set(fh)), demangle(set(fh) - set(fb))
     for name in gone:
         print("only in base:", name)
@@ -68,6 +94,8 @@ def main():
     for name in differ:
         print("body differs:", name)
     print(f"{len(set(fb) & set(fh))} common symbols, {len(differ)} with a different body")
+    if not ids_only:
+        print("llvm.amdgcn.dynlds.offset.table:", "identical" if dynlds_table(base) == dynlds_table(head) else "DIFFERS", f"({len(dynlds_table(head))} entries)")
     renumber = sorted({(int(a), int(b)) for s in ids_only for a, b in zip(LDS_ID.findall(fb[s]), LDS_ID.findall(fh[s]))})
     tb, th = dynlds_table(base), dynlds_table(head)
     ids_ok = all(a1 < a2 and b1 < b2 for (a1, b1), (a2, b2) in zip(renumber, renumber[1:])) and all(tb[a] == th[b] for a, b in renumber)
@@ -75,7 +103,9 @@ def main():
         print(f"{len(ids_only)} kernels differ in their dynamic-LDS kernel id (s15) only; base id -> head id:", " ".join(f"{a}->{b}" for a, b in renumber))
         print(f"  llvm.amdgcn.dynlds.offset.table: {len(tb)} entries -> {len(th)};",
               "order kept, every kernel reads the entry it read before" if ids_ok else "NOT a harmless renumbering")
-    mb, mh = metadata(base), metadata(head)
+    back = {new[:80]: old for old, new in pairs.items()}
+    mb = collections.Counter(renamed_line(line, {}) for line in metadata(base).elements())
+    mh = collections.Counter(renamed_line(line, back) for line in metadata(head).elements())
     for line in sorted((mb - mh).elements()):
         print("metadata only in base:", line)
     for line in sorted((mh - mb).elements()):

@@ -1069,10 +1069,10 @@ constexpr int kBitsGenericWaves = 3;  // measured on cfg-4: 2 -> 1.36 ms, 3 -> 1
 // the gate of the first cycle, the cycle loop with its flushes.  kPlain (3x3-only kernels, decided per wavefront by the kernel):
 // both poses trot, no leg overrides the search radius, every search polygon is the rectangle — one phase a cycle with all four
 // legs swinging (no phase loop, no swing mask), advance = step, and the legs' search constants are the plan's own (uniform).
-// kPlain = false is the general code.  Always inlined into the kernel.  kStride (plan_bits_stride_kernel): step and drift are the
-// pose's own (sv, and hc.drift filled from it by the kernel) instead of the plan's.  kResume (plan_bits_resume_kernel, a stride form
-// too): with rs.in the prologue takes the pose's committed feet, running drift and cycle index from an earlier call's state instead
-// of the stance, and with rs.out the epilogue returns them behind the last flush (fpe_plan_resume*, include/fpe.h).
+// kPlain = false is the general code.  Always inlined into the kernel.  kStride (plan_bits_chain_kernel): step and drift are the
+// pose's own (sv, and hc.drift filled from it by the kernel) instead of the plan's.  kResume (its resume form, a stride form
+// too): with rs.in the prologue takes the pose's committed feet, running drift and cycle index from an earlier call's
+// state instead of the stance, and with rs.out the epilogue returns them behind the last flush (fpe_plan_resume*, include/fpe.h).
 // (The LDS views and the rank table's head are set up HERE, once per copy, not in the kernel ahead of the verdict: a value both
 // copies read has to be computed in front of the branch and stays in its register through either copy, where one copy's own
 // value is computed next to its use — with them in the kernel the <4, true, *> instances spilled four vector registers.)
@@ -1149,10 +1149,10 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
     bool started = true;
     if constexpr (kResume) {
         if (rs.in) {  // (uniform) the state of an earlier call instead of the stance; the padding slot of an odd batch reads pose B-1's
+            // chain_resume's text, kept here like the stance below
             started = false;
             const LegState st = load_leg_state(rs.in, b, leg);
-            const unsigned long long poseMaskR = ((1ull << kPoseThreads) - 1ull) << (slot * kPoseThreads);
-            const bool poseFinite = (__ballot(!st.finite) & poseMaskR) == 0ull;  // any non-finite value: the whole state is non-finite
+            const bool poseFinite = (__ballot(!st.finite) & pose_lane_mask<kPoseThreads>(slot)) == 0ull;  // any non-finite value: the whole state is
             adjY = st.adjY;
             cycBase = st.cycle;
             if (g.sub == 0) {
@@ -1164,7 +1164,8 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             }
         }
     }
-    // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699)
+    // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699): chain_stance's text, kept here (through the
+    // helpers the instantiations at their register cap were re-allocated: <4, true, *>, <4, false, 1>, the chain forms <3 | 4, 0>)
     if (started && g.sub == 0) {
         double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
         double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
@@ -1232,10 +1233,8 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
 
     const int nPhases = (!kPlain && gait == 1) ? 4 : 1;
     const double advance = (!kPlain && gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
-    // swing order LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
-    const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
-    constexpr int kPoseLanes = 4 * G;
-    const unsigned long long poseMask = ((1ull << kPoseLanes) - 1ull) << (slot * kPoseLanes);
+    const int walkOrder = walk_order(pc);
+    const unsigned long long poseMask = pose_lane_mask<kPoseThreads>(slot);  // the validation ballot's: the lanes of this lane's pose
     // the track whose feet-polygon centre this lane evaluates: 3x3-only kernels: the track of the lane's corner
     // (LaneRole); generic kernels: lane t evaluates track t
     const int myTrack = kMid ? lane_track(g.sub) : (g.sub < 2 ? g.sub : 2);
@@ -1388,62 +1387,74 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
     }
 }
 
+// The head of every 8-lane kernel: the lane's pose slot and leg, and the loads of its pose.  The pose first: its address needs
+// nothing but the preloaded arguments, and everything else waits for it.  The padding pose of the last block runs the chain on pose
+// B-1 (with ITS stride and state, in the chain forms) and stores nothing.
+struct PoseSlot8 {
+    int tid, slot, leg, b;
+    bool live;
+    const fpe_pose* pp;
+    double x0, y0, z0;
+    int gait;
+    float rOverride;
+    int polyKindIn;
+};
+__device__ __forceinline__ PoseSlot8 load_pose_slot8(const fpe_pose* __restrict__ poses, int B) {
+    constexpr int G = 8, kPoseThreads = 4 * G;
+    PoseSlot8 p;
+    p.tid = static_cast<int>(threadIdx.x);
+    p.slot = p.tid / kPoseThreads;
+    p.leg = (p.tid / G) & 3;
+    p.b = blockIdx.x * 2 + p.slot;
+    p.live = p.b < B;
+    if (!p.live) p.b = B - 1;
+    p.pp = poses + p.b;
+    p.x0 = p.pp->position[0], p.y0 = p.pp->position[1], p.z0 = p.pp->position[2];
+    p.gait = p.pp->gait;
+    p.rOverride = p.pp->leg_search_radius[p.leg];
+    p.polyKindIn = p.pp->leg_polygon_kind[p.leg];
+    return p;
+}
+// ... and the constants of the leg search parked in vector registers (HotConsts; the drift is the caller's: the plan's or the pose's)
+template <class PC>
+__device__ __forceinline__ HotConsts park_hot_consts(const PC& pc) {
+    HotConsts hc;
+    hc.rf = in_vgpr(pc.rf);
+    hc.rf2 = in_vgpr(pc.rf2);
+    hc.cornerEps = in_vgpr(pc.cornerEps);
+    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
+    return hc;
+}
+
 template <int NRL, bool kMid, int kProd>
 // (the pose pointer and the counts lead the argument list: scalar arguments at the head of the kernarg segment are
 // preloaded into SGPRs at wave launch, -amdgpu-kernarg-preload-count, so the pose loads can be issued at once)
 __global__ __launch_bounds__(64, kMid ? 2 : kBitsGenericWaves) void plan_bits_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles,
                                                           DevMap mArg, BitMap bm, typename std::conditional<kMid, PlanMidConsts, PlanConsts>::type pc,
                                                           SpiralLut lut, fpe_plan_out outArg) {
-    constexpr int G = 8;
     const fpe_plan_out out = specialise_products<kProd>(outArg);
-    constexpr int kPoseThreads = 4 * G;
-    const int tid = static_cast<int>(threadIdx.x);
-    const int slot = tid / kPoseThreads;
-    const int leg = (tid / G) & 3;
-    // the pose first: its address needs nothing but the preloaded arguments, and everything else waits for it
-    int b = blockIdx.x * 2 + slot;
-    const bool live = b < B;  // the padding pose of the last block runs the chain on pose B-1, stores nothing
-    if (!live) b = B - 1;
-    const fpe_pose* pp = poses + b;
-    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
-    const int gait = pp->gait;
-    const float rOverride = pp->leg_search_radius[leg];
-    const int polyKindIn = pp->leg_polygon_kind[leg];
+    const PoseSlot8 p = load_pose_slot8(poses, B);
     __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
-    // the map geometry doubles are operands of vector f64 arithmetic only: parked in VGPRs (see plan_chained_kernel) — in
-    // the 3x3-only variants; the generic ones run at their register cap (168 VGPRs at three wavefronts per SIMD), where the
-    // twenty registers cost more in spills than the scalar operands do in moves (measured: cfg-4 0.713 -> 0.664 ms without)
+    // the map geometry parked in VGPRs (park_geometry) — in the 3x3-only variants; the generic ones run at their register cap (168
+    // VGPRs at three wavefronts per SIMD), where the twenty registers cost more in spills than the scalar operands do in moves
+    // (measured: cfg-4 0.713 -> 0.664 ms without)
     DevMap m = mArg;
-    if constexpr (kMid) {
-        m.g.res = in_vgpr(m.g.res);
-        m.g.rinv = in_vgpr(m.g.rinv);
-        m.g.lenX = in_vgpr(m.g.lenX);
-        m.g.lenY = in_vgpr(m.g.lenY);
-        m.g.posX = in_vgpr(m.g.posX);
-        m.g.posY = in_vgpr(m.g.posY);
-        m.g.orgX = in_vgpr(m.g.orgX);
-        m.g.orgY = in_vgpr(m.g.orgY);
-        m.g.baseX = in_vgpr(m.g.baseX);
-        m.g.baseY = in_vgpr(m.g.baseY);
-    }
-    HotConsts hc;
-    hc.rf = in_vgpr(pc.rf);
-    hc.rf2 = in_vgpr(pc.rf2);
-    hc.cornerEps = in_vgpr(pc.cornerEps);
-    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
+    if constexpr (kMid) park_geometry(m);
+    HotConsts hc = park_hot_consts(pc);
     hc.drift = kMid ? in_vgpr(pc.drift) : pc.drift;  // (the generic variants run at their register cap: nothing extra parked)
     // 3x3-only kernels: one verdict per wavefront.  PLAIN = both pose slots trot, no leg overrides its search radius, every
     // search polygon is the rectangle: the reference planner's only case (one gait, one searchRadius_, getSearchPolygon).  The
     // padding slot of an odd batch runs pose B-1 again and votes as that pose does.  Each verdict has its own copy of the rest
     // of the kernel, inlined (as a callee the chain ran at 33.7 us instead of 24.7); the kernel's name and arguments stay.
     if constexpr (kMid) {
-        if (__ballot(gait == 1 || rOverride > 0.0f || polyKindIn != 0) == 0ull) {
-            plan_bits_body<NRL, kMid, kProd, true>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, m, mArg, bm, pc, lut, out, hc, tid, slot,
-                                                   leg);
+        if (__ballot(p.gait == 1 || p.rOverride > 0.0f || p.polyKindIn != 0) == 0ull) {
+            plan_bits_body<NRL, kMid, kProd, true>(p.pp, p.b, p.live, p.x0, p.y0, p.z0, p.gait, p.rOverride, p.polyKindIn, nCycles, m, mArg, bm, pc, lut, out, hc,
+                                                   p.tid, p.slot, p.leg);
             return;
         }
     }
-    plan_bits_body<NRL, kMid, kProd, false>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, m, mArg, bm, pc, lut, out, hc, tid, slot, leg);
+    plan_bits_body<NRL, kMid, kProd, false>(p.pp, p.b, p.live, p.x0, p.y0, p.z0, p.gait, p.rOverride, p.polyKindIn, nCycles, m, mArg, bm, pc, lut, out, hc, p.tid,
+                                            p.slot, p.leg);
 }
 
 static_assert(kernargs_mirror<decltype(plan_bits_kernel<2, true, 2>)>(
@@ -1452,71 +1463,27 @@ static_assert(kernargs_mirror<decltype(plan_bits_kernel<2, true, 2>)>(
                   offsetof(MidKernArgs, out) + sizeof(MidKernArgs::out)),
               "MidKernArgs must mirror the parameters of plan_bits_kernel<NRL, true, kProd>");
 
-// The stride form of the generic 8-lane kernel (fpe_plan_strides*): the same body, with the step and the drift of each pose slot read
-// from strides[b] — one 16-byte record per pose, loaded next to the pose — and `strides` as the one TRAILING argument behind
-// plan_bits_kernel's own list.  Generic variants only: a stride call on a 3x3-only configuration runs this kernel (the two are
-// pinned equivalent under no_mid_variant).
-template <int NRL, int kProd>
-__global__ __launch_bounds__(64, kBitsGenericWaves) void plan_bits_stride_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, DevMap mArg, BitMap bm,
-                                                                                PlanConsts pc, SpiralLut lut, fpe_plan_out outArg,
-                                                                                const fpe_stride* __restrict__ strides) {
-    constexpr int G = 8;
+// The chain forms of the generic 8-lane kernel: the same body behind plan_bits_kernel's own argument list and a TRAILING pack S, as
+// plan_chained_kernel's.  Generic variants only: a chain call on a 3x3-only configuration runs this kernel (the two are pinned
+// equivalent under no_mid_variant).
+// Stride form (fpe_plan_strides*): S = {const fpe_stride*} — the step and the drift of each pose slot read from strides[b], one
+// 16-byte record per pose, loaded next to the pose.
+// Resume form (fpe_plan_resume*): S = {const fpe_stride*, const fpe_plan_state*, fpe_plan_state*}, each of which may be null
+// (strides: the plan's own step and drift, one uniform branch; state_in: the stance prologue; state_out: nothing returned).  A pose's
+// 208-byte state is loaded beside its pose and its stride.
+template <int NRL, int kProd, class... S>
+__global__ __launch_bounds__(64, kBitsGenericWaves) void plan_bits_chain_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, DevMap mArg, BitMap bm,
+                                                                               PlanConsts pc, SpiralLut lut, fpe_plan_out outArg, S... chainArg) {
+    constexpr bool kResume = sizeof...(S) == 3;
+    static_assert(sizeof...(S) == 1 || kResume, "trailing arguments: the strides, or the strides and the two states");
     const fpe_plan_out out = specialise_products<kProd>(outArg);
-    constexpr int kPoseThreads = 4 * G;
-    const int tid = static_cast<int>(threadIdx.x);
-    const int slot = tid / kPoseThreads;
-    const int leg = (tid / G) & 3;
-    int b = blockIdx.x * 2 + slot;
-    const bool live = b < B;  // the padding pose of the last block runs the chain on pose B-1 (with ITS stride), stores nothing
-    if (!live) b = B - 1;
-    const fpe_pose* pp = poses + b;
-    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
-    const int gait = pp->gait;
-    const float rOverride = pp->leg_search_radius[leg];
-    const int polyKindIn = pp->leg_polygon_kind[leg];
-    const StrideVals sv = load_stride(strides, b);
+    const PoseSlot8 p = load_pose_slot8(poses, B);
+    StrideVals sv;
+    if constexpr (kResume) sv = load_stride_or_plan(stride_arg(chainArg...), p.b, pc);
+    else sv = load_stride(stride_arg(chainArg...), p.b);
     __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
-    HotConsts hc;
-    hc.rf = in_vgpr(pc.rf);
-    hc.rf2 = in_vgpr(pc.rf2);
-    hc.cornerEps = in_vgpr(pc.cornerEps);
-    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
+    HotConsts hc = park_hot_consts(pc);
     hc.drift = sv.drift;  // per pose slot: the y-table fill and the per-cycle sum add the pose's own drift
-    plan_bits_body<NRL, false, kProd, false, true>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, mArg, mArg, bm, pc, lut, out, hc, tid, slot, leg,
-                                                   sv);
-}
-
-// The resume form of the generic 8-lane kernel (fpe_plan_resume*): the stride form's body with the chain's state across the call
-// boundary — {strides, state_in, state_out} as the TRAILING arguments, each of which may be null (strides: the plan's own step and
-// drift, one uniform branch; state_in: today's prologue; state_out: nothing returned).  A pose's 208-byte state is loaded beside its
-// pose and its stride, the padding slot of an odd batch reading pose B-1's like its pose.
-template <int NRL, int kProd>
-__global__ __launch_bounds__(64, kBitsGenericWaves) void plan_bits_resume_kernel(const fpe_pose* __restrict__ poses, int B, int nCycles, DevMap mArg, BitMap bm,
-                                                                                PlanConsts pc, SpiralLut lut, fpe_plan_out outArg,
-                                                                                const fpe_stride* __restrict__ strides, const fpe_plan_state* stateIn,
-                                                                                fpe_plan_state* stateOut) {
-    constexpr int G = 8;
-    const fpe_plan_out out = specialise_products<kProd>(outArg);
-    constexpr int kPoseThreads = 4 * G;
-    const int tid = static_cast<int>(threadIdx.x);
-    const int slot = tid / kPoseThreads;
-    const int leg = (tid / G) & 3;
-    int b = blockIdx.x * 2 + slot;
-    const bool live = b < B;  // the padding pose of the last block runs the chain on pose B-1 (its stride, its state), stores nothing
-    if (!live) b = B - 1;
-    const fpe_pose* pp = poses + b;
-    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
-    const int gait = pp->gait;
-    const float rOverride = pp->leg_search_radius[leg];
-    const int polyKindIn = pp->leg_polygon_kind[leg];
-    const StrideVals sv = load_stride_or_plan(strides, b, pc);
-    __builtin_amdgcn_sched_barrier(0);  // (the loads above stay ahead of the kernel-argument fetches below)
-    HotConsts hc;
-    hc.rf = in_vgpr(pc.rf);
-    hc.rf2 = in_vgpr(pc.rf2);
-    hc.cornerEps = in_vgpr(pc.cornerEps);
-    hc.oneMinusEps = in_vgpr(1.0 - pc.cornerEps);
-    hc.drift = sv.drift;  // per pose slot: the y-table fill and the per-cycle sum add the pose's own drift
-    plan_bits_body<NRL, false, kProd, false, true, true>(pp, b, live, x0, y0, z0, gait, rOverride, polyKindIn, nCycles, mArg, mArg, bm, pc, lut, out, hc, tid, slot,
-                                                         leg, sv, ResumeArgs{stateIn, stateOut});
+    plan_bits_body<NRL, false, kProd, false, true, kResume>(p.pp, p.b, p.live, p.x0, p.y0, p.z0, p.gait, p.rOverride, p.polyKindIn, nCycles, mArg, mArg, bm, pc, lut,
+                                                            out, hc, p.tid, p.slot, p.leg, sv, resume_args(chainArg...));
 }

@@ -363,14 +363,16 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
     StrideVals sv{};
     if constexpr (kResume) sv = load_stride_or_plan(kaG->strides, b, pc);
     else if constexpr (kStride) sv = load_stride(kaG->strides, b);
+    // lane = leg: lanes 0-3 write, every lane loads the state of leg tid & 3 (the finite verdict is a ballot over the wavefront)
     double adjY = 0.0;  // ajustedPose_[1], cpp:759
     int cycBase = 0;    // gait_cycle_id of the call's first cycle
     bool started = true;
     if constexpr (kResume) {
         const fpe_plan_state* stateIn = kaG->stateIn;
-        if (stateIn) {  // (uniform) the committed feet, the running drift and the cycle index of an earlier call instead of the stance
+        if (stateIn) {  // (uniform) the state of an earlier call instead of the stance
             started = false;
-            const LegState st = load_leg_state(stateIn, b, tid & 3);  // lane = leg (every lane loads: the verdict is a ballot)
+            // chain_resume's text with lane = leg, kept here (through the helper the resume forms ran outside the parent's band)
+            const LegState st = load_leg_state(stateIn, b, tid & 3);  // (every lane loads: the verdict is a ballot)
             const bool poseFinite = __ballot(!st.finite) == 0ull;
             adjY = st.adjY;
             cycBase = __builtin_amdgcn_readfirstlane(st.cycle);
@@ -389,7 +391,8 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
         sh.footDb[k] = pc.footDb[k];
         sh.footOff[k] = 0;
     }
-    // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699): lane = leg
+    // initial stance and first-gait shift, lane = leg: chain_stance's text, kept here (through the helper the benchmarked plain
+    // instantiations compile to other instructions: the body reads its constants through the argument segment)
     if (started && tid < 4) {
         const int leg = tid;
         lsTab[leg] = make_leg_static(pc, pp, leg, m.g.res, lut);
@@ -416,7 +419,7 @@ __device__ __attribute__((noinline)) void seq_run_pose(const SeqKernArgs __attri
 
     const int nPhases = (gait == 1) ? 4 : 1;
     const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
-    const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
+    const int walkOrder = walk_order(pc);
 
     const int cycLag = (static_cast<int>(hwid & 3u) * nCycles) / 16;  // launch order of this wavefront on its SIMD (HW_ID.WAVE_ID: 0 oldest .. 3) x a sixteenth of the cycles
     for (int cyc = 0; cyc < nCycles; ++cyc) {

@@ -35,6 +35,31 @@ __device__ __forceinline__ double in_vgpr(double x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+// The map geometry is wave-uniform and would live in 20 scalar registers; the chained kernels need more uniform state than the 102
+// SGPRs hold, and every spilled SGPR costs a v_readlane (+ wait states) per use.  The doubles are only ever operands of vector f64
+// arithmetic, so the kernels that have the vector registers for it park them there.
+__device__ __forceinline__ void park_geometry(DevMap& m) {
+    m.g.res = in_vgpr(m.g.res);
+    m.g.rinv = in_vgpr(m.g.rinv);
+    m.g.lenX = in_vgpr(m.g.lenX);
+    m.g.lenY = in_vgpr(m.g.lenY);
+    m.g.posX = in_vgpr(m.g.posX);
+    m.g.posY = in_vgpr(m.g.posY);
+    m.g.orgX = in_vgpr(m.g.orgX);
+    m.g.orgY = in_vgpr(m.g.orgY);
+    m.g.baseX = in_vgpr(m.g.baseX);
+    m.g.baseY = in_vgpr(m.g.baseY);
+}
+// The lanes of pose `slot` in a wavefront that holds 64 / kPoseLanes poses: the mask of a ballot over one pose.
+template <int kPoseLanes>
+__device__ __forceinline__ unsigned long long pose_lane_mask(int slot) {
+    return (kPoseLanes == 64) ? ~0ull : (((1ull << (kPoseLanes & 63)) - 1ull) << (slot * kPoseLanes));
+}
+// swing order of the walk gait, two bits per phase: LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
+template <class PC>
+__device__ __forceinline__ int walk_order(const PC& pc) {
+    return pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
+}
 
 // A search centre must be finite and of sane magnitude.  The reference has no such test: a
 // non-finite centre (reachable once the centroid track has committed its "no case" (0,0,0)
@@ -1421,6 +1446,54 @@ __device__ __forceinline__ void store_leg_state(fpe_plan_state* __restrict__ st,
         s->reserved = 0;
     }
 }
+// ---- the start of a pose's chain, once for every plan kernel: what the first cycle finds in PoseShared::cur and in its running values --
+// Every kernel: `if constexpr (kResume) if (rs.in) { started = false; chain_resume ... }`, then `if (started && <writer>)` chain_stance, a
+// pose barrier, and the gate of the first cycle where `started`.
+// From the stance (every kernel that is no resume form, and a resume call without state_in): the initial stance (cpp:350-378) with the
+// first-gait shift (setFirstGait, cpp:2679-2699) on the three tracks, and out.stance.  Called by the one lane per leg that writes the
+// leg's feet; a padding pose (`live` false) stores no stance record.
+template <bool kStride, class PC>
+__device__ __forceinline__ void chain_stance(const PC& pc, const StrideVals& sv, double* stanceOut, bool live, int b, int leg, double x0, double y0, double z0,
+                                             double (*cur)[4][3]) {
+    double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
+    double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
+    double sz = 0;
+    sx += x0;
+    sy += y0;
+    sz += z0;
+    if (stanceOut && live) {
+        double* st = stanceOut + (static_cast<size_t>(b) * 4 + leg) * 3;
+        st[0] = sx;
+        st[1] = sy;
+        st[2] = sz;
+    }
+    for (int t = 0; t < 3; ++t) {
+        cur[t][leg][0] = sx - (kStride ? sv.stepHalf : pc.stepHalf);
+        cur[t][leg][1] = sy;
+        cur[t][leg][2] = sz;
+    }
+}
+// From the state of an earlier call (fpe_plan_state, include/fpe.h): the committed feet, the running drift and the cycle index; a pose
+// with any non-finite value starts with NaN x in every track.  Called by every lane (uniform branch; the padding slot of a short batch
+// reads pose B-1's): the lane loads leg `loadLeg`, the verdict is a ballot over the kPoseLanes lanes of pose `slot` of the wavefront,
+// and `writer` — one lane per leg, loadLeg == leg there — writes that leg's feet.  Returns what the chain's running values start from.
+struct ChainResume {
+    double adjY;  // ajustedPose_[1]
+    int cycBase;  // gait_cycle_id of the call's first cycle
+};
+template <int kPoseLanes>
+__device__ __forceinline__ ChainResume chain_resume(const fpe_plan_state* stateIn, int b, int slot, int loadLeg, int leg, bool writer, double (*cur)[4][3]) {
+    const LegState st = load_leg_state(stateIn, b, loadLeg);
+    const bool poseFinite = (__ballot(!st.finite) & pose_lane_mask<kPoseLanes>(slot)) == 0ull;
+    if (writer) {
+        for (int t = 0; t < 3; ++t) {
+            cur[t][leg][0] = poseFinite ? st.x[t] : __builtin_nan("");
+            cur[t][leg][1] = st.y[t];
+            cur[t][leg][2] = 0.0;
+        }
+    }
+    return ChainResume{st.adjY, st.cycle};
+}
 // kStride (the stride kernels): the step is the pose's own, sv.step.
 template <bool kStride = false>
 __device__ __forceinline__ uint8_t opt_gate_cycle0(const MapGeom& g, const PlanConsts& pc, double ctrX, double y0, const StrideVals& sv = StrideVals{}) {
@@ -1628,22 +1701,8 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
     constexpr bool kResume = sizeof...(S) == 3;
     static_assert((sizeof...(S) <= 1 || kResume) && !(kStride && kMid), "optional trailing arguments: the strides, or strides and the two states; generic variant only");
     static_assert(!kResume || G <= 16, "the resume form keeps a pose in one wavefront");
-    // The map geometry is wave-uniform and would live in 20 scalar registers; this kernel needs more uniform
-    // state than the 102 SGPRs hold, and every spilled SGPR costs a v_readlane (+ wait states) per use.  The
-    // doubles are only ever operands of vector f64 arithmetic, so they are parked in VGPRs instead.
     DevMap m = mArg;
-    if constexpr (G <= 16) {
-        m.g.res = in_vgpr(m.g.res);
-        m.g.rinv = in_vgpr(m.g.rinv);
-        m.g.lenX = in_vgpr(m.g.lenX);
-        m.g.lenY = in_vgpr(m.g.lenY);
-        m.g.posX = in_vgpr(m.g.posX);
-        m.g.posY = in_vgpr(m.g.posY);
-        m.g.orgX = in_vgpr(m.g.orgX);
-        m.g.orgY = in_vgpr(m.g.orgY);
-        m.g.baseX = in_vgpr(m.g.baseX);
-        m.g.baseY = in_vgpr(m.g.baseY);
-    }
+    if constexpr (G <= 16) park_geometry(m);
     constexpr int kPoseThreads = 4 * G;
     constexpr int kBlock = (G == 64) ? 256 : 64;
     constexpr int kPPB = kBlock / kPoseThreads;
@@ -1677,55 +1736,26 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
         sh.footDb[k] = pc.footDb[k];
         sh.footOff[k] = static_cast<int16_t>(pc.footDa[k] * pc.tileW + pc.footDb[k]);
     }
+    constexpr int kPoseLanes = G <= 16 ? 4 * G : 64;  // of a wavefront (G = 64: the pose's four wavefronts vote through the LDS)
     double adjY = 0.0;  // ajustedPose_[1], cpp:759
     int cycBase = 0;    // gait_cycle_id of the call's first cycle
     bool started = true;
     if constexpr (kResume) {
-        if (rs.in) {  // (uniform) the committed feet, the running drift and the cycle index of an earlier call instead of the stance
+        if (rs.in) {  // (uniform) the state of an earlier call instead of the stance
             started = false;
-            const LegState st = load_leg_state(rs.in, b, leg);
-            constexpr int kPoseLanesR = 4 * G;
-            const unsigned long long poseMaskR = (kPoseLanesR == 64) ? ~0ull : (((1ull << (kPoseLanesR & 63)) - 1ull) << (slot * kPoseLanesR));
-            const bool poseFinite = (__ballot(!st.finite) & poseMaskR) == 0ull;
-            adjY = st.adjY;
-            cycBase = st.cycle;
-            if (g.sub == 0) {
-                for (int t = 0; t < 3; ++t) {
-                    sh.cur[t][leg][0] = poseFinite ? st.x[t] : __builtin_nan("");
-                    sh.cur[t][leg][1] = st.y[t];
-                    sh.cur[t][leg][2] = 0.0;
-                }
-            }
+            const ChainResume cr = chain_resume<kPoseLanes>(rs.in, b, slot, leg, leg, g.sub == 0, sh.cur);
+            adjY = cr.adjY;
+            cycBase = cr.cycBase;
         }
     }
-    // initial stance (cpp:350-378) and first-gait shift (setFirstGait, cpp:2679-2699)
-    if (started && g.sub == 0) {
-        double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
-        double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
-        double sz = 0;
-        sx += x0;
-        sy += y0;
-        sz += z0;
-        if (out.stance && live) {
-            double* st = out.stance + (static_cast<size_t>(b) * 4 + leg) * 3;
-            st[0] = sx;
-            st[1] = sy;
-            st[2] = sz;
-        }
-        for (int t = 0; t < 3; ++t) {
-            sh.cur[t][leg][0] = sx - (kStride ? sv.stepHalf : pc.stepHalf);
-            sh.cur[t][leg][1] = sy;
-            sh.cur[t][leg][2] = sz;
-        }
-    }
+    if (started && g.sub == 0) chain_stance<kStride>(pc, sv, out.stance, live, b, leg, x0, y0, z0, sh.cur);
     pose_sync<G>();
     if (started && out.pose_status && live && leg == 0 && g.sub == 0)
         out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
 
     const int nPhases = (gait == 1) ? 4 : 1;
     const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
-    // swing order LF,RH,RF,LH (RF_FIRST=false) or RF,LH,LF,RH (build-defined walk)
-    const int walkOrder = pc.RF_FIRST ? ((0) | (2 << 2) | (3 << 4) | (1 << 6)) : ((3) | (1 << 2) | (0 << 4) | (2 << 6));
+    const int walkOrder = walk_order(pc);
 
     for (int cyc = 0; cyc < nCycles; ++cyc) {
         bool cycleOk = true;
@@ -1748,9 +1778,7 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
                 if (active) {
                     leg_phase<G, kMid, true>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out, &lc, cycBase);
                 }
-                constexpr int kPoseLanes = 4 * G;
-                const unsigned long long poseMask = (kPoseLanes == 64) ? ~0ull : (((1ull << (kPoseLanes & 63)) - 1ull) << (slot * kPoseLanes));
-                phaseOk = (__ballot(lc.valid == 0) & poseMask) == 0ull;
+                phaseOk = (__ballot(lc.valid == 0) & pose_lane_mask<kPoseLanes>(slot)) == 0ull;
                 if (phaseOk && active && g.sub == 0) {
 #pragma unroll
                     for (int t = 0; t < 3; ++t)
@@ -1790,15 +1818,113 @@ __global__ __launch_bounds__(G == 64 ? 256 : 64, G == 64 ? 4 : (G == 16 ? kMinWa
 // 64 lanes.  For large spiral windows (1 cm / 0.5 cm maps) a leg has enough cells and candidates to
 // fill a wavefront, the per-leg geometry becomes truly wave-uniform, there are no workgroup barriers
 // and — for the 4-phase walk gait, where only one leg swings per phase — no idle wavefronts.
-#define FPE_SEQUENTIAL_STRIDE 0
-#include "fpe_plan_sequential_body.hpp"  // plan_sequential_kernel
-#undef FPE_SEQUENTIAL_STRIDE
-#define FPE_SEQUENTIAL_STRIDE 1
-#include "fpe_plan_sequential_body.hpp"  // plan_sequential_stride_kernel: `strides` as the one trailing argument
-#undef FPE_SEQUENTIAL_STRIDE
-#define FPE_SEQUENTIAL_STRIDE 2
-#include "fpe_plan_sequential_body.hpp"  // plan_sequential_resume_kernel: strides, state_in and state_out behind the list
-#undef FPE_SEQUENTIAL_STRIDE
+// S: the optional trailing arguments, as plan_chained_kernel's — none, the strides (fpe_plan_strides*: step and drift of the pose
+// from strides[b]), or strides, state_in and state_out (fpe_plan_resume*, each of which may be null).
+template <class... S>
+__global__ __launch_bounds__(64, 4) void plan_sequential_kernel(DevMap m, PlanConsts pc, SpiralLut lut, const fpe_pose* __restrict__ poses, int B, int nCycles,
+                                                                fpe_plan_out out, S... chainArg) {
+    constexpr bool kStride = sizeof...(S) != 0;
+    constexpr bool kResume = sizeof...(S) == 3;
+    static_assert(sizeof...(S) <= 1 || kResume, "optional trailing arguments: the strides, or strides and the two states");
+    constexpr int G = 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = static_cast<int>(threadIdx.x);
+    const Grp<G> g(tid);
+    PoseShared& sh = *reinterpret_cast<PoseShared*>(smem);
+    uint8_t* tile = smem + sizeof(PoseShared);
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const bool live = true;
+
+    const fpe_pose* pp = poses + b;
+    const double x0 = pp->position[0], y0 = pp->position[1], z0 = pp->position[2];
+    const int gait = pp->gait;
+    StrideVals sv{};
+    if constexpr (kResume) sv = load_stride_or_plan(stride_arg(chainArg...), b, pc);
+    else if constexpr (kStride) sv = load_stride(stride_arg(chainArg...), b);
+    const ResumeArgs rs = resume_args(chainArg...);
+    const LutHead head = load_lut_head(lut, g);
+    for (int k = tid; k < pc.nFoot; k += G) {
+        sh.footDa[k] = pc.footDa[k];
+        sh.footDb[k] = pc.footDb[k];
+        sh.footOff[k] = static_cast<int16_t>(pc.footDa[k] * pc.tileW + pc.footDb[k]);
+    }
+    // lane = leg: lanes 0-3 write, every lane loads the state of leg tid & 3 (the finite verdict is a ballot over the wavefront)
+    double adjY = 0.0;  // ajustedPose_[1], cpp:759
+    int cycBase = 0;    // gait_cycle_id of the call's first cycle
+    bool started = true;
+    if constexpr (kResume) {
+        if (rs.in) {  // (uniform) the state of an earlier call instead of the stance
+            started = false;
+            const ChainResume cr = chain_resume<64>(rs.in, b, 0, tid & 3, tid, tid < 4, sh.cur);
+            adjY = cr.adjY;
+            cycBase = cr.cycBase;
+        }
+    }
+    // initial stance and first-gait shift, lane = leg: chain_stance's text, kept here (through the helper this kernel's plain form
+    // compiles to other instructions: the selects between the plan constants become branches)
+    if (started && tid < 4) {
+        const int leg = tid;
+        double sx = (leg == 0 || leg == 3) ? pc.LbHalf : -pc.LbHalf;
+        double sy = (leg <= 1) ? pc.WbHalfNeg : pc.WbHalfPos;
+        double sz = 0;
+        sx += x0;
+        sy += y0;
+        sz += z0;
+        if (out.stance) {
+            double* st = out.stance + (static_cast<size_t>(b) * 4 + leg) * 3;
+            st[0] = sx;
+            st[1] = sy;
+            st[2] = sz;
+        }
+        for (int t = 0; t < 3; ++t) {
+            sh.cur[t][leg][0] = sx - (kStride ? sv.stepHalf : pc.stepHalf);
+            sh.cur[t][leg][1] = sy;
+            sh.cur[t][leg][2] = sz;
+        }
+    }
+    pose_sync<16>();
+    if (started && out.pose_status && tid == 0) out.pose_status[b] = opt_gate_cycle0<kStride>(m.g, pc, polygon_center_x(sh.cur[0]), y0, sv);
+
+    const int nPhases = (gait == 1) ? 4 : 1;
+    const double advance = (gait == 1) ? (kStride ? sv.stepQuarter : pc.stepQuarter) : (kStride ? sv.step : pc.step);
+    const int walkOrder = walk_order(pc);
+
+    for (int cyc = 0; cyc < nCycles; ++cyc) {
+        bool cycleOk = true;
+        for (int ph = 0; ph < nPhases; ++ph) {
+            const unsigned mask = (gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
+            // feet-polygon centres: lane t computes track t (getPolygonCenter, cpp:2191, 2265)
+            if (tid < 3) {
+                sh.ctr[tid] = polygon_center_x(sh.cur[tid]);
+            }
+            if (tid < 4) sh.valid[tid] = 1;  // non-swing legs do not vote
+            pose_sync<16>();
+            for (int leg = 0; leg < 4; ++leg) {
+                if (!((mask >> leg) & 1u)) continue;
+                const LegStatic ls = make_leg_static(pc, pp, leg, m.g.res, lut);
+                leg_phase<G>(m, pc, lut, head, sh, tile, g, leg, ls, y0, adjY, advance, cyc, nCycles, b, live, out, nullptr, cycBase);
+            }
+            pose_sync<16>();
+            // footholdValidation_ = AND of the swing legs' flags (cpp:1323); commit or skip (cpp:1332-1576)
+            const bool phaseOk = (sh.valid[0] & sh.valid[1] & sh.valid[2] & sh.valid[3]) != 0;
+            if (phaseOk && tid < 36) {
+                const int leg = tid / 9, e = tid - leg * 9;
+                if ((mask >> leg) & 1u) {
+                    const int t = e / 3, k = e - t * 3;
+                    sh.cur[t][leg][k] = sh.nxt[t][leg][k];
+                }
+            }
+            pose_sync<16>();
+            cycleOk = cycleOk && phaseOk;
+        }
+        if (tid == 0 && out.cycle_ok) out.cycle_ok[static_cast<size_t>(b) * nCycles + cyc] = cycleOk ? 1 : 0;
+        adjY += kStride ? sv.drift : pc.drift;  // cpp:1578
+    }
+    if constexpr (kResume) {  // the state behind the last cycle (the last phase's commit is behind its pose_sync)
+        if (rs.out && tid < 4) store_leg_state(rs.out, b, tid, sh.cur, adjY, cycBase + nCycles);
+    }
+}
 
 // ---- open-loop per-leg search: one wavefront per checkFoothold call (hpp:94-100) ----------------------
 constexpr int kMaxQueriesPerBlock = 32;  // 256 threads / 8 lanes per query

@@ -83,13 +83,13 @@ static bool visit_direct(PlanUse& use) {
     if (k.form != PlanForm::Plain) {  // at the automatic group sizes only, and never a 3x3-only variant
         if (k.mid || (G != 8 && G != 65)) return false;
         if (k.form == PlanForm::Resume) {
-            if (G == 65) use(plan_sequential_resume_kernel);
+            if (G == 65) use(plan_sequential_kernel<const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>);
             else use(plan_chained_kernel<8, false, const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>);
         } else {
-            if (G == 65) use(plan_sequential_stride_kernel);
+            if (G == 65) use(plan_sequential_kernel<const fpe_stride*>);
             else use(plan_chained_kernel<8, false, const fpe_stride*>);
         }
-    } else if (G == 65 && !k.mid) use(plan_sequential_kernel);
+    } else if (G == 65 && !k.mid) use(plan_sequential_kernel<>);
     else if (G == 4 && !k.mid) use(plan_chained_kernel<4>);
     else if (G == 8 && k.mid) use(plan_chained_kernel<8, true>);
     else if (G == 8) use(plan_chained_kernel<8>);
@@ -99,20 +99,20 @@ static bool visit_direct(PlanUse& use) {
     return true;
 }
 
+// plan_bits_chain_kernel<NRL, 0, S...>: the stride and resume forms of the 8-lane family
+template <class... S>
+static void visit_lane8_chain(PlanUse& use) {
+    if (use.k.nrl == 2) use(plan_bits_chain_kernel<2, 0, S...>);
+    else if (use.k.nrl == 3) use(plan_bits_chain_kernel<3, 0, S...>);
+    else use(plan_bits_chain_kernel<4, 0, S...>);
+}
 static bool visit_lane8(PlanUse& use) {
     const PlanKernel& k = use.k;
     if (k.nrl < 2 || k.nrl > 4 || k.prod < 0 || k.prod > 2) return false;
     if (k.form != PlanForm::Plain) {  // generic variants, any-combination product mask
         if (k.mid || k.prod != 0) return false;
-        if (k.form == PlanForm::Resume) {
-            if (k.nrl == 2) use(plan_bits_resume_kernel<2, 0>);
-            else if (k.nrl == 3) use(plan_bits_resume_kernel<3, 0>);
-            else use(plan_bits_resume_kernel<4, 0>);
-        } else {
-            if (k.nrl == 2) use(plan_bits_stride_kernel<2, 0>);
-            else if (k.nrl == 3) use(plan_bits_stride_kernel<3, 0>);
-            else use(plan_bits_stride_kernel<4, 0>);
-        }
+        if (k.form == PlanForm::Resume) visit_lane8_chain<const fpe_stride*, const fpe_plan_state*, fpe_plan_state*>(use);
+        else visit_lane8_chain<const fpe_stride*>(use);
         return true;
     }
     switch (100 * k.nrl + 10 * k.mid + k.prod) {  // plan_bits_kernel<NRL, MID, PROD>
