@@ -130,12 +130,19 @@ static bool centreUsable(const Vec2& c) { return std::fabs(c.x) <= 1e6 && std::f
 
 // cpp:2520-2554.  f32 sequential sum in CircleIterator (row-major bbox) order; NaN -> 0.0 and
 // counted; values >= 10 skipped; empty count -> last iHeight; "+ h" in f64, returned as float.
-float getFootholdMeanHeight(const GridMap& map, const Vec2& center, float radius, double h) {
+static float meanHeightAround(const GridMap& map, const Vec2& center, float radius, double h, bool guarded) {
     byValueCopy(map);  // hpp:262 / cpp:2029, 2292-2301, 1687, 1820
     float iHeight = 0.0, meanHeight = 0.0;
     int i = 0;
-    if (!centreUsable(center)) return static_cast<float>(meanHeight + h);
+    if (guarded && !centreUsable(center)) return static_cast<float>(meanHeight + h);
     for (CircleIterator it(map, center, radius); !it.isPastEnd(); ++it) {
+        // Oracle-defined (NOT in the reference): a disc wholly past the map's far edge is bounded onto the edge, whose
+        // index can round to `size`; getPositionFromIndex fails there, the iterator's Position stays (0,0), and a centre
+        // within the radius of (0,0) — an untouched centroid result on a map that does not contain the origin,
+        // cpp:1290-1314 — passes isInside with that index.  Upstream then reads past the layer.  Defined here, as in the
+        // engine and in fpo_filters.cpp, as "the cell is not visited"; the reference built on the shims reads NaN there
+        // and counts a 0, which is the same value whenever that cell is the disc's only one.
+        if (!checkIfIndexInRange(*it, map.size)) continue;
         const float e = map.elevAt(*it);
         if (GridMap::isValid(e)) {
             iHeight = e;
@@ -153,6 +160,9 @@ float getFootholdMeanHeight(const GridMap& map, const Vec2& center, float radius
         meanHeight = iHeight;
     }
     return static_cast<float>(meanHeight + h);
+}
+float getFootholdMeanHeight(const GridMap& map, const Vec2& center, float radius, double h) {
+    return meanHeightAround(map, center, radius, h, true);
 }
 
 // cpp:2001-2036.  z is measured at the DEFAULT centre even when a candidate was chosen (cpp:2029).
@@ -245,7 +255,10 @@ void checkFootholdUseCentroidMethod(const GridMap& gridmap, const Vec2& p, float
         if (traversableEndRow) *traversableEndRow = i2.i;
     };
     auto finish = [&](const Vec2& q, uint8_t code) {
-        out.z = getFootholdMeanHeight(heightMap, q, prm.footRadius, prm.h);  // on gridmap_ (cpp:1687, 1820)
+        // on gridmap_ (cpp:1687, 1820).  q is the query centre, which passed centreUsable above, or the centre of a cell of the
+        // map: the oracle-defined guard is about search centres and does not apply to it — a map that reaches past 1e6 has
+        // heights there, and the reference reads them
+        out.z = meanHeightAround(heightMap, q, prm.footRadius, prm.h, false);
         out.x = q.x;
         out.y = q.y;
         out.code = code;

@@ -107,6 +107,27 @@ int main(int argc, char** argv) {
             for (const auto& rr : out.nominal) { valid += rr.valid; ++legs; }
         }
     }
+    // maps far from the origin, mean height asked for at (0, 0) — the untouched centroid result an opt foot can keep
+    // (fpo_opt.cpp STEP(6)): the disc is bounded onto the far corner, whose index rounds to `size` at these magnitudes
+    // (the bounding epsilon is absorbed); no cell may be read, the height is h.  The 13 x 8 map is the gait-cycle submap
+    // of tests/golden/ref/svc_far_2cm_1km, pose 8, cycle 4.
+    {
+        const Vec2 farPos[5] = {{1234.56, -987.25}, {1234.69, -987.33}, {123456.789, -98765.4321}, {-999000.37, 998000.11}, {968750.0, -937500.0}};
+        const int farSize[4][2] = {{13, 8}, {37, 18}, {140, 120}, {1, 1}};
+        for (const Vec2& fp : farPos)
+            for (const auto& sz : farSize)
+                for (const double r2 : resList) {
+                    GridMap g;
+                    g.size = {sz[0], sz[1]};
+                    g.res = r2;
+                    g.length = {sz[0] * r2, sz[1] * r2};
+                    g.position = fp;
+                    g.trav.assign((size_t)sz[0] * sz[1], 1.0f);
+                    g.elev.assign((size_t)sz[0] * sz[1], 0.25f);
+                    if (getFootholdMeanHeight(g, {0.0, 0.0}, 0.02f, 0.01) != static_cast<float>(0.0f + 0.01)) return 4;
+                    if (getFootholdMeanHeight(g, {fp.x, fp.y}, static_cast<float>(0.8 * r2), 0.01) != static_cast<float>(0.25f + 0.01)) return 5;
+                }
+    }
     std::printf("selftest ok: %ld valid of %ld legs\n", valid, legs);
     return 0;
 }

@@ -208,6 +208,40 @@ def cases():
         trav, elev = quantised_map(rows, cols, res, seed, pos, bad=0.12 if name != "legs_5mm_bigfoot" else 0.01)
         out.append(dict(name=name, mode="legs", trav=trav, elev=elev, res=res, position=pos, params=p,
                         queries=leg_queries(rows, cols, res, pos, p, np.random.default_rng(seed), 240, 200, 60)))
+    return out + far_cases()
+
+
+FAR_POSITIONS = ((1234.56, -987.25), (123456.789, -98765.4321), (-999000.37, 998000.11))
+
+
+def far_cases():
+    """Maps far from the origin — where a robot-centric map in an odom or UTM frame lies.  Every case draws from a
+    generator of its own (the shared one of cases() is consumed as before).  Every coordinate a chain can reach stays
+    below 1e6: the guard there (centreUsable) is the oracle's definition, not the reference's."""
+    near, mid, far = FAR_POSITIONS
+    out = []
+
+    def svc(name, rows, cols, res, pos, scale, n, B, variant, seed, map_seed, **over):
+        p = scaled_params(scale, **over)
+        trav, elev = quantised_map(rows, cols, res, map_seed, pos)
+        out.append(dict(name=name, mode="service", trav=trav, elev=elev, res=res, position=pos, params=p,
+                        poses=edge_poses(rows, cols, res, pos, p, np.random.default_rng(seed), B), n=n, variants=[variant]))
+
+    # 2 cm at 1.2 km.  Pose 8 derails its opt track in cycle 4: the optimiser keeps the index of an untouched centroid
+    # result, the point (0, 0), which this map does not contain, and the mean height is asked for at (0, 0)
+    # (oracle/fpo_planner.cpp, getFootholdMeanHeight)
+    svc("svc_far_2cm_1km", 128, 96, 0.02, near, 0.5, 5, 12, "yaml", 7, 900)
+    svc("svc_far_1cm_123km", 160, 128, 0.01, mid, 0.4, 4, 10, "yaml", 8, 900, footRadius=1.5 * 0.01)  # foot disc of 9 cells
+    svc("svc_far_237_999km", 150, 110, 0.0237, far, 0.6, 4, 10, "weights", 9, 900, RF_FIRST=1)
+    svc("svc_far_2cm_999km", 128, 96, 0.02, far, 0.5, 5, 12, "code", 10, 902)
+    # exact ties at a dyadic position 9.7e5 m out (2^-5 m cells: every cell centre and corner is exact in f64)
+    out.append(tie_case("svc_far_tie_r5_k4", 5, 160, 128, (31000000, -30000000), 4, 0.9375, 1, 404))
+    for name, rows, cols, res, pos, scale, seed in (("legs_far_2cm_123km", 96, 64, 0.02, mid, 1.0, 505),
+                                                    ("legs_far_5mm_999km", 128, 96, 0.005, far, 0.25, 506)):
+        p = scaled_params(scale)
+        trav, elev = quantised_map(rows, cols, res, seed, pos, bad=0.12)
+        out.append(dict(name=name, mode="legs", trav=trav, elev=elev, res=res, position=pos, params=p,
+                        queries=leg_queries(rows, cols, res, pos, p, np.random.default_rng(seed), 240, 200, 60)))
     return out
 
 
@@ -224,7 +258,14 @@ def screen_poses(c, asan_driver, workdir=None):
     (untouched (0,0,0) results of the centroid method, cpp:1777-1944, or the optimiser's start point kept after NLopt's
     precondition failed), getPolygonCenter divides 0 by 0 (cpp:2457) and the NaN centre reaches grid_map's (int) cast.
     The oracle and the engine DEFINE that case (centreUsable, fpo_planner.cpp); the reference does not, so it cannot
-    pin them there.  -> (kept mask over the poses, the reports' first lines)."""
+    pin them there.
+
+    NOT excluded, and not reported by the sanitizer build: an opt foot that keeps an untouched centroid result's index on
+    a map that does not contain the origin (svc_far_2cm_1km, pose 8, cycle 4).  getFootholdMeanHeight is then asked for
+    the height at (0, 0); grid_map's CircleIterator bounds the disc onto the far corner, whose index rounds to `size`, and
+    upstream would read one cell past the layer.  The shim returns NaN for that read and counts it (oobReads), so the
+    reference built on the shims is defined there: z = 0 + h.  The oracle visits no cell: the same value.
+    -> (kept mask over the poses, the reports' first lines)."""
     poses = np.asarray(c["poses"], np.float64).reshape(-1, 3)
     keep = np.ones(poses.shape[0], bool)
     reasons = []

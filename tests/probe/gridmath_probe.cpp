@@ -28,6 +28,16 @@ int probe_submap(int rows, int cols, double res, double px, double py, double x,
     base[0] = s.baseX; base[1] = s.baseY;
     return s.ok ? 1 : 0;
 }
+// submap_axis on both axes: out = ok_x, i0, ni, ok_y, j0, nj and the two bases
+void probe_submap_axes(int rows, int cols, double res, double px, double py, double x, double y, double lx, double ly, int* out,
+                       double* base) {
+    const MapGeom g = make_geom(rows, cols, res, px, py);
+    const SubmapAxis a = submap_axis(g.orgX, g.posX, g.lenX, g.baseX, g.res, g.rinv, g.rows, x, lx);
+    const SubmapAxis b = submap_axis(g.orgY, g.posY, g.lenY, g.baseY, g.res, g.rinv, g.cols, y, ly);
+    out[0] = a.ok; out[1] = a.i0; out[2] = a.ni;
+    out[3] = b.ok; out[4] = b.i0; out[5] = b.ni;
+    base[0] = a.base; base[1] = b.base;
+}
 double probe_cell_pos(int rows, int cols, double res, double px, double py, int axis, int idx) {
     const MapGeom g = make_geom(rows, cols, res, px, py);
     return axis == 0 ? cell_pos(g.baseX, g.res, idx) : cell_pos(g.baseY, g.res, idx);

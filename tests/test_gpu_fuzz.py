@@ -15,9 +15,15 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
+FAR_MAGNITUDES = (1e3, 1e4, 1e5, 9e5)
+
+
 def make_case(seed, focus=""):
     """focus "seq" (FPE_FUZZ_FOCUS): fine maps with wide search windows only — the one-wavefront-per-pose bit-window kernels
-    (plan_bits_seq_kernel<1, 2> / <2, 3>), which the unbiased generator reaches in 4 % / 0.3 % of its cases."""
+    (plan_bits_seq_kernel<1, 2> / <2, 3>), which the unbiased generator reaches in 4 % / 0.3 % of its cases.
+    focus "far": the case of the default stream, then the map's position and the poses moved by an offset per axis drawn
+    from a SECOND generator over FAR_MAGNITUDES x a random sign (the default stream is consumed as without it, so the
+    existing seeds and the committed summaries keep their meaning).  Every coordinate stays below the 1e6 guard."""
     rng = np.random.default_rng(seed)
     res = float(rng.choice([0.02, 0.02, 0.01, 0.005, 0.03, 0.025, 0.04, 0.0125]))
     rows, cols = int(rng.integers(150, 420)), int(rng.integers(150, 420))
@@ -68,14 +74,30 @@ def make_case(seed, focus=""):
     bits = rng.random() < 0.5 or focus == "seq"
     if bits:
         group = "0"
+    if focus == "far":
+        frng = np.random.default_rng([seed, 0xFA5])
+        off = frng.choice(FAR_MAGNITUDES, 2) * frng.choice([-1.0, 1.0], 2)
+        pos = (pos[0] + float(off[0]), pos[1] + float(off[1]))
+        poses["position"][:, 0] += off[0]
+        poses["position"][:, 1] += off[1]
     return dict(res=res, pos=pos, params=p, trav=trav, elev=elev, poses=poses, n=N, group=group, literal=literal, bits=bits)
 
 
 def test_random_differential_campaign():
+    run_campaign(int(os.environ.get("FPE_FUZZ_CASES", "3000")), int(os.environ.get("FPE_FUZZ_SEED", "20000")),
+                 os.environ.get("FPE_FUZZ_FOCUS", ""))
+
+
+def test_random_differential_campaign_far_from_the_origin():
+    """200 cases of focus "far" (about 1.5 s at the campaign's rate): the same generator with the map 1e3 .. 9e5 m out, where
+    the host's proofs give way to the literal walks and the direct kernels for some foot radii (tests/test_host_switches.py);
+    both families must have run."""
+    kernels = run_campaign(200, 20000, "far")
+    assert any(k.startswith("plan_bits") for k in kernels) and any(not k.startswith("plan_bits") for k in kernels), kernels
+
+
+def run_campaign(n_cases, seed0, focus):
     planner = FootholdPlanner(0)
-    n_cases = int(os.environ.get("FPE_FUZZ_CASES", "3000"))
-    seed0 = int(os.environ.get("FPE_FUZZ_SEED", "20000"))
-    focus = os.environ.get("FPE_FUZZ_FOCUS", "")
     src = np.zeros(4, np.int64)
     codes = np.zeros(7, np.int64)
     opt_status = np.zeros(4, np.int64)
@@ -150,3 +172,4 @@ def test_random_differential_campaign():
     if n_cases >= 100 and not focus:
         assert (opt_status[:3] > 0).all() and opt_gates > 0, (opt_status, opt_gates)
         assert any(k.startswith("plan_bits_kernel") for k in kernels) and any(k.startswith("plan_bits_seq_kernel") for k in kernels), kernels
+    return kernels

@@ -97,7 +97,7 @@ def base(rows, cols):
 class Case:
     """One update: the base, the shift, the patch values, the composed map, and the CPU-side conditions on them."""
 
-    def __init__(self, rows, cols, shift, rects, base_ref=None, sources=None, first_source=0):
+    def __init__(self, rows, cols, shift, rects, base_ref=None, sources=None, first_source=0, new_pos=NEW_POS):
         b, srcs = base(rows, cols)
         self.base = base_ref or b
         srcs = sources or srcs
@@ -134,7 +134,8 @@ class Case:
         assert np.array_equal(bits(trav), bits(cur_t)) and np.array_equal(bits(elev), bits(cur_e))
         self.n_patched = int(self.patched.sum())
         self.n_filled = int((~self.carried & ~self.patched).sum())
-        self.new = MapRef(trav, elev, NEW_POS, rows + cols + 1)
+        self.new_pos = new_pos
+        self.new = MapRef(trav, elev, new_pos, rows + cols + 1)
 
     def patches(self, form="packed"):
         return [(r[0], r[1], mu.patch_source(vt, form, self.rows, self.cols, r[0], r[1]), mu.patch_source(ve, form, self.rows, self.cols, r[0], r[1]))
@@ -173,14 +174,14 @@ def case(rows, cols, shift, set_name):
 
 def upload_base(planner, c, pairs=(YAML,)):
     """The base by fpe_upload_map, then observer 1 for each pair: the base snapshot holds their planes, so the update rebuilds them."""
-    planner.gridmapCallback(c.base.trav, c.base.elev, RES)
+    planner.gridmapCallback(c.base.trav, c.base.elev, RES, position=c.base.position)
     for pair in pairs:
         assert_cells_equal(observe_host(planner, pair, layers=False)["bits"], c.base.cells(pair), f"the base, pair {pair}")
 
 
 def check_updated(planner, c, pair, what, poses=True):
     info = planner.map_info()
-    assert (info["rows"], info["cols"], info["resolution"], info["position"]) == (c.rows, c.cols, RES, NEW_POS)
+    assert (info["rows"], info["cols"], info["resolution"], info["position"]) == (c.rows, c.cols, RES, c.new_pos)
     obs = observe_host(planner, pair, c.new.poses if poses else None)
     check_observers(obs, c.new, pair, what)
     assert_same_bytes(obs, c.new.fresh(pair), what)

@@ -33,16 +33,21 @@ def probe():
     L.probe_polygon.argtypes = [C.c_void_p, C.c_void_p, C.c_int, d, d, C.c_int]
     L.probe_bbox.argtypes = [C.c_int, C.c_int, d, d, d, d, d, d, C.c_void_p, C.c_void_p]
     L.probe_submap.argtypes = [C.c_int, C.c_int, d, d, d, d, d, d, d, C.c_void_p, C.c_void_p]
+    L.probe_submap_axes.argtypes = [C.c_int, C.c_int, d, d, d, d, d, d, d, C.c_void_p, C.c_void_p]
     L.probe_cell_pos.restype = d
     L.probe_cell_pos.argtypes = [C.c_int, C.c_int, d, d, d, C.c_int, C.c_int]
     return L
 
 
 RES = st.sampled_from([0.02, 0.01, 0.005, 0.03, 0.25, 0.1, 1.0 / 3.0])
+# Map positions: near the origin, and as far out as a robot-centric map in an odom or UTM frame gets (the engine's guard
+# is at 1e6).  FAR_POS: non-dyadic and dyadic ones, either sign.
+POS = st.floats(-50, 50) | st.floats(-1e6, 1e6)
+FAR_POS = [1234.56, -98765.4321, 123456.789, -999000.37, 998000.11, 968750.0, -937500.0]
 
 
 @settings(max_examples=400, deadline=None)
-@given(res=RES, n=st.integers(10, 4000), p=st.floats(-50, 50), frac=st.floats(-0.2, 1.2))
+@given(res=RES, n=st.integers(10, 4000), p=POS, frac=st.floats(-0.2, 1.2))
 def test_index_prediction_equals_literal_random(probe, res, n, p, frac):
     L_ = n * res
     org = 0.5 * L_
@@ -51,7 +56,7 @@ def test_index_prediction_equals_literal_random(probe, res, n, p, frac):
 
 
 @settings(max_examples=400, deadline=None)
-@given(res=RES, n=st.integers(10, 2000), p=st.sampled_from([0.0, 1.5, -3.25, 7.0]), k=st.integers(0, 2000),
+@given(res=RES, n=st.integers(10, 2000), p=st.sampled_from([0.0, 1.5, -3.25, 7.0] + FAR_POS), k=st.integers(0, 2000),
        half=st.sampled_from([0.0, 0.5, 1.0, 1.5, 2.0]), ulps=st.integers(-3, 3))
 def test_index_prediction_equals_literal_on_ties(probe, res, n, p, k, half, ulps):
     """positions on cell boundaries / centres +- a few ulps: where the prediction must defer"""
@@ -78,16 +83,20 @@ def test_fast_pnpoly_equals_literal(probe, data):
 
 
 @settings(max_examples=200, deadline=None)
-@given(res=st.sampled_from([0.02, 0.01, 0.25]), px=st.sampled_from([0.0, 3.7]), cx=st.floats(-3, 3), cy=st.floats(-3, 3),
-       r=st.sampled_from([0.02, 0.03, 0.25, 0.5]))
-def test_bbox_and_cells_match_oracle_circle_iterator(probe, res, px, cx, cy, r):
+@given(res=st.sampled_from([0.02, 0.01, 0.25]), px=st.sampled_from([0.0, 3.7] + FAR_POS), py=st.sampled_from([-1.0] + FAR_POS),
+       dx=st.floats(-3, 3), dy=st.floats(-3, 3), r=st.sampled_from([0.02, 0.03, 0.25, 0.5]), lattice=st.booleans())
+def test_bbox_and_cells_match_oracle_circle_iterator(probe, res, px, py, dx, dy, r, lattice):
+    """dx, dy: the circle's centre relative to the map's; lattice: on a multiple of the resolution (corners on cell edges)."""
     rows, cols = 240, 200
     rd = float(np.float32(r))
+    cx, cy = px + dx, py + 1.0 + dy
+    if lattice:
+        cx, cy = float(np.round(cx / res) * res), float(np.round(cy / res) * res)
     lit = np.zeros(4, np.int32)
     fast = np.zeros(4, np.int32)
-    probe.probe_bbox(rows, cols, res, px, -1.0, cx, cy, rd, lit.ctypes.data, fast.ctypes.data)
+    probe.probe_bbox(rows, cols, res, px, py, cx, cy, rd, lit.ctypes.data, fast.ctypes.data)
     assert lit.tolist() == fast.tolist()
-    m = fpo.OracleMap(np.ones((rows, cols), np.float32), np.zeros((rows, cols), np.float32), res, (px, -1.0))
+    m = fpo.OracleMap(np.ones((rows, cols), np.float32), np.zeros((rows, cols), np.float32), res, (px, py))
     cells = m.circle_cells(cx, cy, rd)
     # every visited cell lies in the engine's bounding box, in row-major order
     if len(cells):
@@ -95,26 +104,39 @@ def test_bbox_and_cells_match_oracle_circle_iterator(probe, res, px, cx, cy, r):
         assert cells[:, 1].min() >= lit[1] and cells[:, 1].max() < lit[1] + lit[3]
     for (i, j) in cells[:3].tolist():
         ok, x, y = m.get_position(i, j)
-        assert probe.probe_cell_pos(rows, cols, res, px, -1.0, 0, i) == x
-        assert probe.probe_cell_pos(rows, cols, res, px, -1.0, 1, j) == y
+        assert probe.probe_cell_pos(rows, cols, res, px, py, 0, i) == x
+        assert probe.probe_cell_pos(rows, cols, res, px, py, 1, j) == y
 
 
 @settings(max_examples=200, deadline=None)
-@given(res=st.sampled_from([0.02, 0.01, 0.005]), x=st.floats(-2.6, 2.6), y=st.floats(-2.2, 2.2), R=st.sampled_from([0.06, 0.1, 0.15]))
-def test_submap_geometry_matches_oracle_getSubmap(probe, res, x, y, R):
+@given(res=st.sampled_from([0.02, 0.01, 0.005]), x=st.floats(-2.6, 2.6), y=st.floats(-2.2, 2.2), R=st.sampled_from([0.06, 0.1, 0.15]),
+       px=st.sampled_from([0.0] + FAR_POS), py=st.sampled_from([0.0] + FAR_POS), lattice=st.booleans())
+def test_submap_geometry_matches_oracle_getSubmap(probe, res, x, y, R, px, py, lattice):
+    """x, y: the request relative to the map's centre, inside, on the border and past it; lattice: on a multiple of the
+    resolution, where with R a whole number of cells both corners lie on cell edges.  submap_axis, the per-axis
+    restatement the dense centroid map uses, must say what submap_info says."""
     rows, cols = int(round(4.8 / res)), int(round(4.0 / res))
     Rf = np.float32(R)
     lx, ly = float(Rf * 2), float(Rf)
+    x, y = px + x, py + y
+    if lattice:
+        x, y = float(np.round(x / res) * res), float(np.round(y / res) * res)
     out = np.zeros(4, np.int32)
     base = np.zeros(2, np.float64)
-    ok = probe.probe_submap(rows, cols, res, 0.0, 0.0, x, y, lx, ly, out.ctypes.data, base.ctypes.data)
-    m = fpo.OracleMap(np.ones((rows, cols), np.float32), np.zeros((rows, cols), np.float32), res)
+    ok = probe.probe_submap(rows, cols, res, px, py, x, y, lx, ly, out.ctypes.data, base.ctypes.data)
+    m = fpo.OracleMap(np.ones((rows, cols), np.float32), np.zeros((rows, cols), np.float32), res, (px, py))
     ok_o, o, pl = m.submap_info(x, y, lx, ly)
     assert bool(ok) == ok_o
     if ok_o:
         assert out.tolist() == o.tolist()
         # submap getPosition(0,0) = subPos + (subLen/2 - res/2)
         assert base[0] == pl[0] + (0.5 * pl[2] - 0.5 * res) and base[1] == pl[1] + (0.5 * pl[3] - 0.5 * res)
+    ax = np.zeros(6, np.int32)
+    abase = np.zeros(2, np.float64)
+    probe.probe_submap_axes(rows, cols, res, px, py, x, y, lx, ly, ax.ctypes.data, abase.ctypes.data)
+    assert bool(ax[0] and ax[3]) == bool(ok)
+    if ok:
+        assert [ax[1], ax[4], ax[2], ax[5]] == out.tolist() and abase.tolist() == base.tolist()
 
 
 def test_engine_geometry_reproduces_the_hand_traced_submaps(probe):

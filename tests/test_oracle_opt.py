@@ -190,6 +190,40 @@ def test_opt_gate_stops_the_chain_where_the_submap_leaves_the_map():
     assert prod["gate_fail_cycle"] == 3 and prod["path"].shape[0] == 3
 
 
+def test_kat_derailed_opt_foot_on_a_map_that_does_not_contain_the_origin():
+    """The flat case of the first KAT moved to the dyadic position (1024, -512): pose (1023, -512, 0), the same rows and
+    columns.  LF's rectangle is map rows 127..137; rows 127 and 137 are blocked, so its scan finds minRow = 0 and
+    maxRow = bottomRow: no case runs (code 5) and the centroid result stays untouched, the point (0, 0).  Its index on
+    gaitMap_ (top-left corner x = 1024 + 2 - 127 * 0.02 = 1023.46, y = -512 + 2 - 91 * 0.02 = -511.82) is
+    (int(1023.46 / 0.02), -int(511.82 / 0.02)) = (51173, -25591) give or take the rounding of the quotient: far outside
+    the 37 x 18 submap and outside the optimiser's box, so NLopt's precondition fails (status 1), x keeps the centroid
+    indices, getPosition fails for LF — the first conversion, so the one Position is still (0, 0) — and the mean height is
+    asked for at (0, 0), 1 km off the map: no cell, z = float(0 + h).  Every cell of the map is 0.25 high: any cell
+    read would show.  RH, converted next, is not derailed and has its own cell's height."""
+    t, e = flat(200, 200)
+    e[:] = 0.25
+    t[127, :] = 0.1
+    t[137, :] = 0.1
+    om = fpo.OracleMap(t, e, 0.02, (1024.0, -512.0))
+    p = yaml_params()
+    poses = oracle_poses([(1023.0, -512.0, 0.0)])
+    plan = om.plan(p, poses, 2)
+    o = om.plan_opt(p, fpo.opt_params_yaml(), poses, 2, plan["cycle_ok"])
+    c = o["cycles"][0, 0]
+    # the nominal track commits cycle 0, so the opt track commits LF = (0, 0): its feet centre is then about a quarter of
+    # the way to the origin, off the map, and the handler returns false in cycle 1
+    assert plan["cycle_ok"][0, 0] and o["gate_fail_cycle"][0] == 1
+    assert tuple(c["gait_top_left"]) == (127, 91) and tuple(c["gait_size"]) == (37, 18)
+    assert c["centroid_code"].tolist()[3] == 5  # RF, RH, LH, LF
+    assert abs(int(c["centroid_index"][0]) - 51173) <= 1 and abs(int(c["centroid_index"][1]) + 25591) <= 1
+    assert c["solver_status"] == 1 and c["x"].tolist() == [float(v) for v in c["centroid_index"]]
+    f = o["footholds"][0, 0]
+    assert (f[3]["x"], f[3]["y"]) == (0.0, 0.0)
+    assert np.float32(f[3]["z"]) == np.float32(np.float32(0.0) + 0.01)
+    ok, x, y = om.get_position(127 + int(c["x"][2]), 91 + int(c["x"][3]))  # RH
+    assert ok and abs(f[1]["x"] - x) < 1e-9 and abs(f[1]["y"] - y) < 1e-9 and np.float32(f[1]["z"]) == np.float32(np.float32(0.25) + 0.01)
+
+
 def test_cobyla_comparison_fixture_is_in_step_with_the_oracle():
     """tests/golden/cobyla_vs_lattice.json (make_cobyla_golden.py: scipy's COBYLA driving the literal chain, build container
     only) quotes solveLattice's x for its example cycles: re-derived here, so the statistics it carries belong to THIS
