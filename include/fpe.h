@@ -343,7 +343,8 @@ int fpe_map_info(fpe_handle h, fpe_map_desc* out); /* geometry of the current sn
  *    update, n_patches outside 0..FPE_UPDATE_MAX_PATCHES, reserved != 0, a non-finite position, an empty rectangle or one reaching
  *    outside the map, a null layer pointer in a used patch, a stride pair of neither form.  fpe_map_update_validate is that same
  *    routine without an engine: of `base` only rows and cols are read.
- * Out of scope: a change of size or resolution (a full upload), the producer's filters on the dirty region only. */
+ * Out of scope: a change of size or resolution (a full upload).  The producer's filters on the dirty region only are
+ * fpe_update_elevation* below. */
 #define FPE_UPDATE_MAX_PATCHES 8
 typedef struct fpe_map_patch {        /* 48 bytes */
     int32_t row0, col0, n_rows, n_cols;   /* rectangle in canonical indices of the NEW map; non-empty, inside it */
@@ -395,6 +396,62 @@ int fpe_traversability(fpe_handle h, const fpe_map_desc* desc, const fpe_filter_
  * stream waits GPU-side for the least recently used one.  `stream` must outlive the chains queued on it. */
 int fpe_traversability_device(fpe_handle h, const fpe_map_desc* desc, const fpe_filter_params* fp, const float* d_elevation,
                               float* d_traversability, float* d_layers, void* stream);
+
+/* ---- elevation-driven map updates: the producer's filters on the dirty region only ---------------------------------------------
+ * BUILD-DEFINED.  fpe_update_map's shift and patches, with patches that carry ELEVATION only: one call composes the new elevation
+ * layer (fpe_update_map's steps 1-3 applied to the elevation), runs the filter chain above over the tiles whose input changed,
+ * lets the shift carry every other cell's traversability, rebuilds the bit planes and installs the snapshot.
+ *  - `u`: shift, position, patch count, rectangles and stride forms mean what they mean for fpe_update_map.  patch[k].elevation is
+ *    required; patch[k].traversability must be NULL (FPE_E_INVALID_ARG).  Every other refusal of fpe_update_map applies unchanged;
+ *    a parameter set fpe_traversability* would refuse returns what it returns there (FPE_E_UNSUPPORTED for radii beyond the stencil
+ *    tables).  A refused call installs, queues and writes nothing.  fp == NULL: the defaults.  info may be NULL.
+ *  - Reach.  R = max(hN, hR, h1 + h2), h* = int(radius / resolution) + 1 of the normals, roughness, first and second step radius:
+ *    10 cells with the defaults at 2 cm.  fpe_filter_reach_cells returns it (FPE_E_INVALID_ARG < 0 for bad arguments).
+ *  - Dirty set D.  In the new map's canonical indices, with shift (sr, sc):
+ *      C holds the cells of every patch rectangle, and every cell without a source, meaning that (i + sr, j + sc) lies outside
+ *        the map.
+ *      B holds carried cells whose window is clipped differently by the map edge before and after the move.  If sr != 0, these are
+ *        the rows i with i < R, or i >= rows - R, or i + sr < R, or i + sr >= rows - R.  If sc != 0, the columns follow the same
+ *        rule.
+ *      D = {cells within Chebyshev distance R of a cell of C} united with B, clipped to the map.
+ *  - Content.  Let E* be the composed elevation and F what fpe_traversability_device writes for E* with the new map's geometry
+ *    {rows, cols, resolution, u->position, start (0,0), row-major} and d_layers == NULL — the traversability-only chain (it and the
+ *    all-layers chain are not bit-identical to each other; F is the former).  After the call the snapshot's elevation is E*, and its
+ *    traversability T* satisfies, bit for bit: every cell of D holds F; every other cell holds either F or the base snapshot's value
+ *    at (i + sr, j + sc), whatever produced that value; the set of cells the chain stored has recomputed_cells elements, contains D,
+ *    and is a function of the inputs alone (the chain stores whole tiles of its global tile grid, without a store mask).
+ *    NOT PROMISED: a carried value is the filter's answer at the OLD position and tile alignment — it is not re-derived at the new
+ *    position, and it is not byte-equal to a fresh run in the last place (the row-moment prefix differences depend on the tile
+ *    alignment, the lattice shapes on the map's distance from the origin).  A changed fpe_filter_params between updates is the
+ *    caller's business: carried cells keep what they hold.
+ *  - Routes.  route 0: region launches of the chain's two kernels over the dirty tiles.  route 1, NOT a partial update: where the
+ *    chain for these parameters and this geometry is not the two-launch traversability-only one (roughness radius != normal radius,
+ *    the published windows at 0.5 cm, a map too far from the origin for the lattice forms), or |shift| >= the map's size, the full
+ *    chain runs over the whole composed map; every cell then holds F and recomputed_cells = rows * cols.
+ *  - Everything else behaves byte for byte as if fpe_upload_map had been called with (T*, E*) and the new geometry: fpe_map_info,
+ *    the planes of every threshold pair the base held (rebuilt from T* behind the chain), lazily built planes for new pairs, and
+ *    fpe_update_map's snapshot semantics — a plan that entered before keeps the base, installation is atomic, updates (of either
+ *    kind) serialise among themselves, the device form never synchronises the host, the base counts as read by an asynchronous launch.
+ *  - fpe_elevation_update_plan: the validation and the dirty set without an engine; of `base` rows, cols, resolution are read (the
+ *    new position is u->position).  dirty: rows * cols bytes, 1 for the cells of D. */
+int fpe_filter_reach_cells(const fpe_filter_params* fp, double resolution);   /* host arithmetic; no engine */
+typedef struct fpe_elevation_update_info {
+    int32_t reach_cells;       /* R */
+    int32_t route;             /* 0 = region launches, 1 = the full chain over the whole map (fallback) */
+    int64_t dirty_cells;       /* |D| */
+    int64_t recomputed_cells;  /* cells whose traversability the chain stores: >= dirty_cells */
+} fpe_elevation_update_info;
+int fpe_elevation_update_plan(const fpe_map_desc* base, const fpe_filter_params* fp, const fpe_map_update* u,
+                              fpe_elevation_update_info* info /* may be NULL */, uint8_t* dirty /* [rows*cols] 0/1, may be NULL */);
+int fpe_update_elevation(fpe_handle h, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info);  /* patch pointers: HOST; synchronous */
+int fpe_update_elevation_device(fpe_handle h, const fpe_filter_params* fp, const fpe_map_update* u,
+                                fpe_elevation_update_info* info, void* stream);  /* `u` on the host, patch pointers: DEVICE; asynchronous */
+
+/* The canonical layers of the snapshot current at entry, bit for bit: row-major, start index (0, 0), rows * cols floats each.
+ * Either pointer may be NULL, not both.  Snapshot semantics of fpe_plan; the device form waits GPU-side for the snapshot's upload
+ * and never synchronises the host. */
+int fpe_read_map_layers(fpe_handle h, float* traversability, float* elevation);                       /* host; synchronous */
+int fpe_read_map_layers_device(fpe_handle h, float* d_traversability, float* d_elevation, void* stream);
 
 /* Name and shape of the kernel a chained plan with these parameters launches on the current map (evidence for
  * benchmarks and profiles; e.g. "plan_bits_kernel<2, true> (8 lanes per leg, 13 x 13 bit window, 3x3-only fast path)"). */

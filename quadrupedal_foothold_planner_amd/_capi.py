@@ -282,6 +282,11 @@ class MapUpdate(C.Structure):
                 ("patch", MapPatch * UPDATE_MAX_PATCHES)]
 
 
+class ElevationUpdateInfo(C.Structure):
+    """fpe_elevation_update_info: what an elevation-driven update recomputed (reach R, route, |D|, cells the chain stored)."""
+    _fields_ = [("reach_cells", C.c_int32), ("route", C.c_int32), ("dirty_cells", C.c_int64), ("recomputed_cells", C.c_int64)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -295,6 +300,7 @@ STRUCTS = {
     "fpe_pose_summary": PoseSummary, "fpe_rank_params": RankParams, "fpe_rank_out": RankOut, "fpe_layer_layout": LayerLayout,
     "fpe_layer_request": LayerRequest, "fpe_stride": STRIDE_DTYPE, "fpe_plan_state": PLAN_STATE_DTYPE,
     "fpe_beam_params": BeamParams, "fpe_beam_out": BeamOut, "fpe_map_patch": MapPatch, "fpe_map_update": MapUpdate,
+    "fpe_elevation_update_info": ElevationUpdateInfo,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -315,6 +321,12 @@ PROTOTYPES = {
     "fpe_update_map": (cint, [vp, P(MapUpdate)]),
     "fpe_update_map_device": (cint, [vp, P(MapUpdate), vp]),
     "fpe_map_update_validate": (cint, [P(MapDesc), P(MapUpdate)]),
+    "fpe_filter_reach_cells": (cint, [P(FilterParams), f64]),
+    "fpe_elevation_update_plan": (cint, [P(MapDesc), P(FilterParams), P(MapUpdate), P(ElevationUpdateInfo), vp]),
+    "fpe_update_elevation": (cint, [vp, P(FilterParams), P(MapUpdate), P(ElevationUpdateInfo)]),
+    "fpe_update_elevation_device": (cint, [vp, P(FilterParams), P(MapUpdate), P(ElevationUpdateInfo), vp]),
+    "fpe_read_map_layers": (cint, [vp, vp, vp]),
+    "fpe_read_map_layers_device": (cint, [vp, vp, vp, vp]),
     "fpe_filter_params_defaults": (cint, [P(FilterParams)]),
     "fpe_traversability": (cint, [vp, P(MapDesc), P(FilterParams), vp, vp, vp]),
     "fpe_traversability_device": (cint, [vp, P(MapDesc), P(FilterParams), vp, vp, vp, vp]),

@@ -1050,6 +1050,55 @@ int check_desc(const fpe_map_desc* d) {
     return FPE_OK;
 }
 
+// The step_height buffer of one traversability-only chain on `stream` (fpe_engine::filterSlots), with the GPU-side wait it may need
+// queued.  The caller holds h->filterMu from here until its chain is QUEUED and filter_slot_done has recorded the slot's event.
+int filter_slot_take(fpe_engine* h, size_t n, hipStream_t stream, fpe_engine::FilterSlot*& slot) {
+    slot = nullptr;
+    bool wait = false;
+    for (auto& fs : h->filterSlots)  // (1) this stream's own buffer
+        if (fs.buf && fs.cap >= n && fs.cap <= 4 * n + 4096 && fs.last == stream && (!slot || fs.use > slot->use)) slot = &fs;
+    // (the wait on the slot's event is queued in this case too: on the same in-order queue it is free, and a caller who destroyed
+    // the stream with work pending and got the same handle value back for a new one is ordered behind the old chain — ADVICE r5)
+    if (slot) wait = true;
+    if (!slot)
+        for (auto& fs : h->filterSlots)  // (2) an idle buffer
+            if (fs.buf && fs.cap >= n && fs.cap <= 4 * n + 4096 && hipEventQuery(fs.done) == hipSuccess) {
+                slot = &fs;
+                break;
+            }
+    (void)hipGetLastError();  // hipErrorNotReady of the queries above is not an error
+    if (!slot) {
+        for (auto& fs : h->filterSlots)  // (3) a free slot, else (4) the least recently used one
+            if (!fs.buf) {
+                slot = &fs;
+                break;
+            }
+        if (!slot) {
+            slot = &h->filterSlots[0];
+            for (auto& fs : h->filterSlots)
+                if (fs.use < slot->use) slot = &fs;
+            wait = true;
+        }
+        if (slot->buf && slot->cap < n) {  // too small (also reached by (4)): back to the pool, dirty — its last chain may still run
+            h->pool->give(slot->cap, slot->buf, true);
+            slot->buf = nullptr;
+            wait = false;
+        }
+        if (!slot->buf) FPE_HIP(alloc_units(*h->pool, n, &slot->buf, &slot->cap, true));  // cleanOnly: never a device synchronisation
+        if (!slot->done) FPE_HIP(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    }
+    if (wait) FPE_HIP(hipStreamWaitEvent(stream, slot->done, 0));
+    return FPE_OK;
+}
+// Behind the chain that used `slot` — or behind whatever part of it was queued when a later step failed: the event its next user
+// waits for is recorded on every way out (a slot left without one would let that user run beside this chain's kernels).
+hipError_t filter_slot_done(fpe_engine* h, fpe_engine::FilterSlot* slot, hipStream_t stream) {
+    const hipError_t e = hipEventRecord(slot->done, stream);
+    slot->last = stream;
+    slot->use = ++h->filterClock;
+    return e;
+}
+
 // ---- what a full upload (upload_common) and an incremental update (update_common) share ----------------------------------------
 // A snapshot of this geometry with both layers from the pool, not yet filled.
 int new_snapshot(fpe_engine* h, int rows, int cols, double res, double posX, double posY, std::shared_ptr<MapSnapshot>& out) {
@@ -1196,6 +1245,151 @@ int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, co
     return install_snapshot(h, snap, !srcOnDevice, stream);
 }
 
+}  // namespace
+
+// ---- fpe_update_elevation*: what the engine-free plan call and the engine's update share (host arithmetic only) ----------------
+namespace fpe {
+// What fpe_elevation_update_plan and the engine's fpe_update_elevation* share (host arithmetic only): the refusals, the new
+// geometry, the clamped shift, the dirty set D as rectangles, the route and — route 0 — the tile rectangles of the region launches.
+struct ElevationUpdatePlan {
+    fpe_elevation_update_info info;
+    FilterConsts fc;
+    MapGeom g;
+    int sr, sc;
+    std::vector<CellRect> dirty;
+    FilterRegion region;
+};
+
+// fpe_filter_params -> FilterConsts; FPE_E_INVALID_ARG for a radius or critical value that is not positive and finite.
+int filter_consts(const fpe_filter_params& fp, FilterConsts& fc) {
+    const double radii[4] = {fp.normal_radius, fp.step_first_radius, fp.step_second_radius, fp.roughness_radius};
+    for (double r : radii)
+        if (!(r > 0.0) || !std::isfinite(r)) return FPE_E_INVALID_ARG;
+    if (!(fp.slope_critical > 0.0) || !(fp.step_critical > 0.0) || !(fp.roughness_critical > 0.0) || fp.step_critical_cells <= 0) return FPE_E_INVALID_ARG;
+    fc = FilterConsts{fp.normal_radius, fp.slope_critical, fp.step_critical, fp.step_first_radius, fp.step_second_radius,
+                      fp.step_critical_cells, fp.roughness_critical, fp.roughness_radius};
+    return FPE_OK;
+}
+
+// The dirty set D of include/fpe.h as rectangles: the patch rectangles and the bands without a source grown by R, and the bands
+// whose window the map edge clips differently before and after the move — whole rows / columns, found as runs of per-line flags.
+void elevation_dirty_rects(int rows, int cols, int R, int sr, int sc, const fpe_map_update* u, std::vector<CellRect>& out) {
+    out.clear();
+    if (std::abs(sr) >= rows || std::abs(sc) >= cols) {  // nothing is carried: every cell is without a source
+        out.push_back(CellRect{0, 0, rows, cols});
+        return;
+    }
+    const auto line_runs = [&](int n, int s, bool rowAxis) {
+        std::vector<uint8_t> flag(static_cast<size_t>(n), 0);
+        for (int i = 0; i < n; ++i) {
+            // C grown by R: some line within R has no source
+            const int lo = std::max(i - R, 0), hi = std::min(i + R, n - 1);
+            const bool noSource = s > 0 ? hi + s >= n : (s < 0 ? lo + s < 0 : false);
+            const bool clipped = s != 0 && (i < R || i >= n - R || i + s < R || i + s >= n - R);  // B
+            flag[static_cast<size_t>(i)] = noSource || clipped;
+        }
+        for (int i = 0; i < n;) {
+            if (!flag[static_cast<size_t>(i)]) {
+                ++i;
+                continue;
+            }
+            int j = i;
+            while (j < n && flag[static_cast<size_t>(j)]) ++j;
+            out.push_back(rowAxis ? CellRect{i, 0, j, cols} : CellRect{0, i, rows, j});
+            i = j;
+        }
+    };
+    line_runs(rows, sr, true);
+    line_runs(cols, sc, false);
+    for (int k = 0; k < u->n_patches; ++k) {
+        const fpe_map_patch& p = u->patch[k];
+        const CellRect r{std::max(p.row0 - R, 0), std::max(p.col0 - R, 0), static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(p.row0) + p.n_rows + R, rows)),
+                         static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(p.col0) + p.n_cols + R, cols))};
+        bool inside = false;  // (a rectangle inside an earlier one adds nothing)
+        for (const CellRect& q : out) inside = inside || (q.r0 <= r.r0 && r.r1 <= q.r1 && q.c0 <= r.c0 && r.c1 <= q.c1);
+        if (!inside) out.push_back(r);
+    }
+}
+
+int plan_elevation_update(int rows, int cols, double res, const fpe_filter_params* fp, const fpe_map_update* u, ElevationUpdatePlan& plan, const char** why) {
+    auto bad = [&](int rc, const char* msg) {
+        *why = msg;
+        return rc;
+    };
+    int rc = check_map_update(rows, cols, u, true, why);
+    if (rc != FPE_OK) return rc;
+    if (rows > 32768 || cols > 32768) return bad(FPE_E_INVALID_ARG, "map size out of range");
+    if (!(res > 0.0) || !std::isfinite(res)) return bad(FPE_E_INVALID_ARG, "bad resolution");
+    fpe_filter_params def;
+    if (!fp) {
+        fpe_filter_params_defaults(&def);
+        fp = &def;
+    }
+    if (filter_consts(*fp, plan.fc) != FPE_OK) return bad(FPE_E_INVALID_ARG, "filter radii and critical values must be positive and finite");
+    plan.g = make_geom(rows, cols, res, u->position[0], u->position[1]);
+    if (!filters_supported(plan.fc, plan.g)) return bad(FPE_E_UNSUPPORTED, "filter radius spans more cells than the stencil tables hold");
+    plan.sr = std::max(-rows, std::min(rows, u->shift[0]));  // beyond +-rows nothing is carried either way
+    plan.sc = std::max(-cols, std::min(cols, u->shift[1]));
+    const int R = filter_reach_cells(plan.fc, res);
+    elevation_dirty_rects(rows, cols, R, plan.sr, plan.sc, u, plan.dirty);
+    plan.info.reach_cells = R;
+    plan.info.dirty_cells = cell_rects_union(plan.dirty.data(), static_cast<int>(plan.dirty.size()), rows, cols);
+    const bool carried = std::abs(plan.sr) < rows && std::abs(plan.sc) < cols;
+    const bool region = carried && static_cast<int>(plan.dirty.size()) <= kRegionMaxRects &&
+                        filters_region_plan(plan.g, plan.fc, plan.dirty.data(), static_cast<int>(plan.dirty.size()), &plan.region);
+    plan.info.route = region ? 0 : 1;
+    plan.info.recomputed_cells = region ? plan.region.recomputed : static_cast<int64_t>(rows) * cols;
+    return FPE_OK;
+}
+
+}  // namespace fpe
+
+namespace {
+
+// The patches of an update into its argument block.  Device form: the caller's arrays as they are.  Host form: packed row-major
+// into a call context's pinned arena (their strides resolved here), ONE host-to-device copy queued on the context's stream, which
+// becomes `stream`; the caller synchronises it and clears lease->ctx->inFlight.  elevationOnly: the patches of fpe_update_elevation*
+// (one layer; the kernel's traversability pointer stays null).
+int stage_update_patches(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, bool elevationOnly, fpe::MapUpdateArgs& a,
+                         std::unique_ptr<CtxLease>& lease, hipStream_t& stream) {
+    const int nl = elevationOnly ? 1 : 2;
+    if (srcOnDevice) {
+        for (int k = 0; k < u->n_patches; ++k) {
+            const fpe_map_patch& p = u->patch[k];
+            a.patch[k] = fpe::MapUpdatePatch{p.row0, p.col0, p.n_rows, p.n_cols, reinterpret_cast<const uint32_t*>(p.traversability),
+                                             reinterpret_cast<const uint32_t*>(p.elevation), p.row_stride, p.col_stride};
+        }
+        return FPE_OK;
+    }
+    lease.reset(new CtxLease(h->ctxPool));
+    CallCtx& cx = *lease->ctx;
+    size_t cells = 0;
+    for (int k = 0; k < u->n_patches; ++k) cells += static_cast<size_t>(u->patch[k].n_rows) * u->patch[k].n_cols;
+    const size_t bytes = nl * cells * sizeof(float);
+    FPE_HIP(cx.reserve(bytes));
+    stream = cx.stream;
+    float* hp = reinterpret_cast<float*>(cx.pinned);
+    size_t off = 0;
+    for (int k = 0; k < u->n_patches; ++k) {
+        const fpe_map_patch& p = u->patch[k];
+        const size_t pn = static_cast<size_t>(p.n_rows) * p.n_cols;
+        const float* src[2] = {elevationOnly ? p.elevation : p.traversability, p.elevation};
+        for (int l = 0; l < nl; ++l)
+            for (int r = 0; r < p.n_rows; ++r) {
+                float* row = hp + off + l * pn + static_cast<size_t>(r) * p.n_cols;
+                if (p.col_stride == 1) std::memcpy(row, src[l] + r * p.row_stride, static_cast<size_t>(p.n_cols) * sizeof(float));
+                else
+                    for (int c = 0; c < p.n_cols; ++c) row[c] = src[l][r * p.row_stride + c * p.col_stride];
+            }
+        const uint32_t* dp = reinterpret_cast<const uint32_t*>(cx.dev) + off;
+        a.patch[k] = fpe::MapUpdatePatch{p.row0, p.col0, p.n_rows, p.n_cols, elevationOnly ? nullptr : dp, elevationOnly ? dp : dp + pn, p.n_cols, 1};
+        off += nl * pn;
+    }
+    cx.inFlight = true;
+    if (bytes) FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, bytes, hipMemcpyHostToDevice, stream));
+    return FPE_OK;
+}
+
 // fpe_update_map*: the snapshot current at entry shifted by whole cells, cleared where nothing is carried, the patches written over
 // that (include/fpe.h) — one launch of map_update_kernel, which also writes the planes of every pair the base was planned with.
 // Host form: the patches packed row-major into the call context's pinned arena (their strides resolved here), ONE host-to-device
@@ -1214,7 +1408,7 @@ int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipS
     if (!base) return fail(FPE_E_NO_MAP, "no map uploaded");
     const int rows = base->g.rows, cols = base->g.cols;
     const char* why = "";
-    int rc = fpe::check_map_update(rows, cols, u, &why);
+    int rc = fpe::check_map_update(rows, cols, u, false, &why);
     if (rc != FPE_OK) return fail(rc, why);
     FPE_HIP(hipSetDevice(h->device));
     rc = new_snapshot(h, rows, cols, base->g.res, u->position[0], u->position[1], snap);
@@ -1232,40 +1426,8 @@ int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipS
     a.sc = std::max(-cols, std::min(cols, u->shift[1]));
     a.nPatches = u->n_patches;
     std::unique_ptr<CtxLease> lease;
-    if (srcOnDevice) {
-        for (int k = 0; k < u->n_patches; ++k) {
-            const fpe_map_patch& p = u->patch[k];
-            a.patch[k] = fpe::MapUpdatePatch{p.row0, p.col0, p.n_rows, p.n_cols, reinterpret_cast<const uint32_t*>(p.traversability),
-                                             reinterpret_cast<const uint32_t*>(p.elevation), p.row_stride, p.col_stride};
-        }
-    } else {
-        lease.reset(new CtxLease(h->ctxPool));
-        CallCtx& cx = *lease->ctx;
-        size_t cells = 0;
-        for (int k = 0; k < u->n_patches; ++k) cells += static_cast<size_t>(u->patch[k].n_rows) * u->patch[k].n_cols;
-        const size_t bytes = 2 * cells * sizeof(float);
-        FPE_HIP(cx.reserve(bytes));
-        stream = cx.stream;
-        float* hp = reinterpret_cast<float*>(cx.pinned);
-        size_t off = 0;
-        for (int k = 0; k < u->n_patches; ++k) {
-            const fpe_map_patch& p = u->patch[k];
-            const size_t pn = static_cast<size_t>(p.n_rows) * p.n_cols;
-            const float* src[2] = {p.traversability, p.elevation};
-            for (int l = 0; l < 2; ++l)
-                for (int r = 0; r < p.n_rows; ++r) {
-                    float* row = hp + off + l * pn + static_cast<size_t>(r) * p.n_cols;
-                    if (p.col_stride == 1) std::memcpy(row, src[l] + r * p.row_stride, static_cast<size_t>(p.n_cols) * sizeof(float));
-                    else
-                        for (int c = 0; c < p.n_cols; ++c) row[c] = src[l][r * p.row_stride + c * p.col_stride];
-                }
-            const uint32_t* dp = reinterpret_cast<const uint32_t*>(cx.dev) + off;
-            a.patch[k] = fpe::MapUpdatePatch{p.row0, p.col0, p.n_rows, p.n_cols, dp, dp + pn, p.n_cols, 1};
-            off += 2 * pn;
-        }
-        cx.inFlight = true;
-        if (bytes) FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, bytes, hipMemcpyHostToDevice, stream));
-    }
+    rc = stage_update_patches(h, u, srcOnDevice, false, a, lease, stream);
+    if (rc != FPE_OK) return rc;
     FPE_HIP(base->wait_ready(stream));  // the update's stream behind the base's upload
     // the device form reads the base asynchronously and keeps no reference past this call: the base counts as read by an
     // asynchronous launch, so its buffers (and, through ~MapSnapshot, its planes) are recycled only behind a device synchronisation
@@ -1291,6 +1453,135 @@ int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipS
         lease->ctx->inFlight = false;
     }
     return install_snapshot(h, snap, !srcOnDevice, stream);
+}
+
+// fpe_update_elevation*: fpe_update_map's composition with elevation-only patches (the traversability layer is carried or cleared),
+// then the producer's chain over the dirty tiles straight into the new snapshot's traversability layer — region launches (route 0)
+// or, where the chain is not the two-launch traversability-only one, the full chain over the whole composed map (route 1) — then the
+// planes of the base's threshold pairs from the finished layer (launch_build_bitmap: one pass over T* per pair; the planes cannot
+// ride in map_update_kernel here, the chain writes T* behind it).  One stream: compose -> step heights -> fused -> planes.
+int update_elevation_common(fpe_engine* h, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info, bool srcOnDevice,
+                            hipStream_t stream) {
+    if (!h || !u) return fail(FPE_E_INVALID_ARG, "null handle or update");
+    std::lock_guard<std::mutex> serial(h->updateMu);
+    CallPlan baseRef;  // (ahead of the lease, as in update_common)
+    std::shared_ptr<MapSnapshot>& base = baseRef.snap;
+    std::shared_ptr<MapSnapshot> snap;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        base = h->map;
+    }
+    if (!base) return fail(FPE_E_NO_MAP, "no map uploaded");
+    const int rows = base->g.rows, cols = base->g.cols;
+    fpe::ElevationUpdatePlan plan;
+    const char* why = "";
+    int rc = fpe::plan_elevation_update(rows, cols, base->g.res, fp, u, plan, &why);
+    if (rc != FPE_OK) return fail(rc, why);
+    FPE_HIP(hipSetDevice(h->device));
+    rc = new_snapshot(h, rows, cols, base->g.res, u->position[0], u->position[1], snap);
+    if (rc != FPE_OK) return rc;
+    const size_t n = snap->n;
+
+    fpe::MapUpdateArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.baseTrav = reinterpret_cast<const uint32_t*>(base->d_trav);
+    a.baseElev = reinterpret_cast<const uint32_t*>(base->d_elev);
+    a.dstTrav = reinterpret_cast<uint32_t*>(snap->d_trav);
+    a.dstElev = reinterpret_cast<uint32_t*>(snap->d_elev);
+    a.rows = rows;
+    a.cols = cols;
+    a.sr = plan.sr;
+    a.sc = plan.sc;
+    a.nPatches = u->n_patches;
+    a.nPairs = 0;  // the planes follow the chain
+    std::unique_ptr<CtxLease> lease;
+    rc = stage_update_patches(h, u, srcOnDevice, true, a, lease, stream);
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(base->wait_ready(stream));
+    if (srcOnDevice) mark_async_launch(baseRef);  // (as in update_common: the base is read asynchronously, no reference outlives the call)
+    // the new snapshot's own layers are written asynchronously from here on: should a later step fail, they go back dirty
+    struct DirtyOnExit {
+        MapSnapshot* s;
+        ~DirtyOnExit() {
+            if (s) s->note_async_use();
+        }
+    } dirtyOnExit{srcOnDevice ? snap.get() : nullptr};
+    FPE_HIP(fpe::launch_map_update(a, stream));
+
+    // pooled scratch of the full chain with intermediate layers (route 1 where the chain is not the traversability-only one)
+    struct Scratch {
+        std::shared_ptr<BufferPool> pool;
+        size_t cap = 0;
+        float* p = nullptr;
+        ~Scratch() {
+            if (p) pool->give(cap, p, true);
+        }
+    } scratch{h->pool};
+    const bool travOnly = plan.info.route == 0 || fpe::filters_trav_only_ok(plan.fc, plan.g);
+    if (travOnly) {
+        std::lock_guard<std::mutex> lk(h->filterMu);  // held until the chain is queued and the slot's event recorded
+        fpe_engine::FilterSlot* slot = nullptr;
+        rc = filter_slot_take(h, n, stream, slot);
+        if (rc != FPE_OK) return rc;
+        const fpe::FilterLayers L{nullptr, nullptr, nullptr, nullptr, slot->buf, nullptr, nullptr, snap->d_trav};
+        const hipError_t e = plan.info.route == 0 ? fpe::launch_filters_region(plan.g, plan.fc, snap->d_elev, L, plan.region, stream)
+                                                  : fpe::launch_filters(plan.g, plan.fc, snap->d_elev, L, true, stream);
+        const hipError_t f = filter_slot_done(h, slot, stream);  // also behind a chain that failed half-way
+        FPE_HIP(e);
+        FPE_HIP(f);
+    } else {
+        FPE_HIP(alloc_units(*h->pool, 8 * n, &scratch.p, &scratch.cap, srcOnDevice));  // (device form: never a device synchronisation)
+        float* d = scratch.p;
+        const fpe::FilterLayers L{d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, d + 6 * n, d + 7 * n};
+        FPE_HIP(fpe::launch_filters(plan.g, plan.fc, snap->d_elev, L, false, stream));
+        FPE_HIP(hipMemcpyAsync(snap->d_trav, L.trav, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    FPE_HIP(hipEventCreateWithFlags(&snap->ready, hipEventDisableTiming));
+    FPE_HIP(hipEventRecord(snap->ready, stream));
+    for (const auto& pair : carried_pairs(base)) {
+        std::shared_ptr<MaskSet> ms;
+        rc = build_mask(*snap, pair.first, pair.second, stream, srcOnDevice, ms);
+        if (rc != FPE_OK) return rc;
+        ms->lastUse.store(++snap->useClock);
+        snap->masks.push_back(std::move(ms));
+    }
+    if (!srcOnDevice) {  // host sources may be freed on return — and the arena goes back to the pool
+        FPE_HIP(hipStreamSynchronize(stream));
+        lease->ctx->inFlight = false;
+    }
+    dirtyOnExit.s = nullptr;
+    if (info) *info = plan.info;
+    return install_snapshot(h, snap, !srcOnDevice, stream);
+}
+
+// fpe_read_map_layers*: the canonical layers of the snapshot current at entry, copied out bit for bit.
+int read_layers_common(fpe_engine* h, float* trav, float* elev, bool onDevice, hipStream_t stream) {
+    if (!h || (!trav && !elev)) return fail(FPE_E_INVALID_ARG, "null handle, or no layer requested");
+    std::shared_ptr<MapSnapshot> snap;  // (ahead of the lease: on an early exit the lease waits for its stream first)
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        snap = h->map;
+    }
+    if (!snap) return fail(FPE_E_NO_MAP, "no map uploaded");
+    FPE_HIP(hipSetDevice(h->device));
+    const size_t bytes = snap->n * sizeof(float);
+    if (onDevice) {
+        FPE_HIP(snap->wait_ready(stream));
+        snap->note_async_use();  // read without the host waiting: the layers are recycled only behind a device synchronisation
+        if (trav) FPE_HIP(hipMemcpyAsync(trav, snap->d_trav, bytes, hipMemcpyDeviceToDevice, stream));
+        if (elev) FPE_HIP(hipMemcpyAsync(elev, snap->d_elev, bytes, hipMemcpyDeviceToDevice, stream));
+        return FPE_OK;
+    }
+    CtxLease lease(h->ctxPool);
+    CallCtx& cx = *lease.ctx;
+    FPE_HIP(cx.reserve(0));
+    FPE_HIP(snap->wait_ready(cx.stream));
+    cx.inFlight = true;
+    if (trav) FPE_HIP(hipMemcpyAsync(trav, snap->d_trav, bytes, hipMemcpyDeviceToHost, cx.stream));
+    if (elev) FPE_HIP(hipMemcpyAsync(elev, snap->d_elev, bytes, hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    return FPE_OK;
 }
 
 }  // namespace
@@ -1467,6 +1758,47 @@ int fpe_update_map_device(fpe_handle h, const fpe_map_update* u, void* stream) {
     return update_common(h, u, true, static_cast<hipStream_t>(stream));
 }
 
+int fpe_update_elevation(fpe_handle h, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info) {
+    return update_elevation_common(h, fp, u, info, false, nullptr);
+}
+
+int fpe_update_elevation_device(fpe_handle h, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info, void* stream) {
+    return update_elevation_common(h, fp, u, info, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_read_map_layers(fpe_handle h, float* traversability, float* elevation) { return read_layers_common(h, traversability, elevation, false, nullptr); }
+
+int fpe_read_map_layers_device(fpe_handle h, float* d_traversability, float* d_elevation, void* stream) {
+    return read_layers_common(h, d_traversability, d_elevation, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_filter_reach_cells(const fpe_filter_params* fp, double resolution) {
+    fpe_filter_params def;
+    if (!fp) {
+        fpe_filter_params_defaults(&def);
+        fp = &def;
+    }
+    fpe::FilterConsts fc;
+    if (!(resolution > 0.0) || !std::isfinite(resolution) || fpe::filter_consts(*fp, fc) != FPE_OK) return FPE_E_INVALID_ARG;
+    return fpe::filter_reach_cells(fc, resolution);
+}
+
+int fpe_elevation_update_plan(const fpe_map_desc* base, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info,
+                              uint8_t* dirty) {
+    if (!base) return FPE_E_INVALID_ARG;
+    fpe::ElevationUpdatePlan plan;
+    const char* why = nullptr;
+    const int rc = fpe::plan_elevation_update(base->rows, base->cols, base->resolution, fp, u, plan, &why);
+    if (rc != FPE_OK) return rc;
+    if (info) *info = plan.info;
+    if (dirty) {
+        std::memset(dirty, 0, static_cast<size_t>(base->rows) * base->cols);
+        for (const fpe::CellRect& r : plan.dirty)
+            for (int i = r.r0; i < r.r1; ++i) std::memset(dirty + static_cast<size_t>(i) * base->cols + r.c0, 1, static_cast<size_t>(r.c1 - r.c0));
+    }
+    return FPE_OK;
+}
+
 int fpe_filter_params_defaults(fpe_filter_params* out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null out");
     std::memset(out, 0, sizeof(*out));
@@ -1544,45 +1876,11 @@ int filters_common(fpe_engine* h, const fpe_map_desc* desc, const fpe_filter_par
             // the lock is held until the chain is QUEUED and its event recorded (see fpe_engine::filterSlots)
             std::lock_guard<std::mutex> lk(h->filterMu);
             fpe_engine::FilterSlot* slot = nullptr;
-            bool wait = false;
-            for (auto& fs : h->filterSlots)  // (1) this stream's own buffer
-                if (fs.buf && fs.cap >= n && fs.cap <= 4 * n + 4096 && fs.last == stream && (!slot || fs.use > slot->use)) slot = &fs;
-            // (the wait on the slot's event is queued in this case too: on the same in-order queue it is free, and a caller who destroyed
-            // the stream with work pending and got the same handle value back for a new one is ordered behind the old chain — ADVICE r5)
-            if (slot) wait = true;
-            if (!slot)
-                for (auto& fs : h->filterSlots)  // (2) an idle buffer
-                    if (fs.buf && fs.cap >= n && fs.cap <= 4 * n + 4096 && hipEventQuery(fs.done) == hipSuccess) {
-                        slot = &fs;
-                        break;
-                    }
-            (void)hipGetLastError();  // hipErrorNotReady of the queries above is not an error
-            if (!slot) {
-                for (auto& fs : h->filterSlots)  // (3) a free slot, else (4) the least recently used one
-                    if (!fs.buf) {
-                        slot = &fs;
-                        break;
-                    }
-                if (!slot) {
-                    slot = &h->filterSlots[0];
-                    for (auto& fs : h->filterSlots)
-                        if (fs.use < slot->use) slot = &fs;
-                    wait = true;
-                }
-                if (slot->buf && slot->cap < n) {  // too small (also reached by (4)): back to the pool, dirty — its last chain may still run
-                    h->pool->give(slot->cap, slot->buf, true);
-                    slot->buf = nullptr;
-                    wait = false;
-                }
-                if (!slot->buf) FPE_HIP(alloc_units(*h->pool, n, &slot->buf, &slot->cap, true));  // cleanOnly: never a device synchronisation
-                if (!slot->done) FPE_HIP(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
-            }
-            if (wait) FPE_HIP(hipStreamWaitEvent(stream, slot->done, 0));
+            rc = filter_slot_take(h, n, stream, slot);
+            if (rc != FPE_OK) return rc;
             const fpe::FilterLayers L{nullptr, nullptr, nullptr, nullptr, slot->buf, nullptr, nullptr, d_trav};
             FPE_HIP(fpe::launch_filters(g, fc, d_elev, L, true, stream));
-            FPE_HIP(hipEventRecord(slot->done, stream));
-            slot->last = stream;
-            slot->use = ++h->filterClock;
+            FPE_HIP(filter_slot_done(h, slot, stream));
         }
         if (!onDevice) {
             FPE_HIP(hipMemcpyAsync(trav, d_trav, n * sizeof(float), hipMemcpyDeviceToHost, stream));

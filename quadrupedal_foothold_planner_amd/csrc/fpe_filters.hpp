@@ -765,6 +765,39 @@ __global__ __launch_bounds__(TR * TC) void filter_step_runs_kernel(MapGeom g, co
     }
 }
 
+// The first window over the tiles of a rectangle list (region_tile, fpe_filters_fused.hpp): the same phase on the same global
+// tiles, so every step height it stores is the whole-map launch's, bit for bit.  The list is read through the argument segment.
+struct StepRegionKernArgs {
+    MapGeom g;
+    const float* src;
+    FilterLayers L;
+    double r;
+    int H;
+    StepShape sp;
+    TileRects rects;
+};
+template <int TR, int TC, int HS>
+__global__ __launch_bounds__(TR * TC) void filter_step_runs_region_kernel(MapGeom g, const float* __restrict__ src, FilterLayers L, double r, int H, StepShape sp,
+                                                                       TileRects rects) {
+    extern __shared__ __attribute__((aligned(16))) char ldsRaw[];
+    int ty, tx;
+    const auto ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    if (!region_tile((TileRectsPtr)(ka + offsetof(StepRegionKernArgs, rects)), ty, tx)) return;  // (workgroup-uniform: ahead of every barrier)
+    const int ti0 = ty * TR, tj0 = tx * TC;
+    const int i = ti0 + static_cast<int>(threadIdx.x) / TC, j = tj0 + static_cast<int>(threadIdx.x) % TC;
+    const bool live = i < g.rows && j < g.cols;
+    float hi, lo, centre;
+    int cnt;
+    step_runs_phase<false, TR, TC, HS>(ldsRaw, g, src, r, H, sp, 0.0f, ti0, tj0, live, hi, lo, cnt, centre);
+    if (!live) return;
+    L.stepHeight[static_cast<size_t>(i) * g.cols + j] = isfinite(centre) ? static_cast<float>(static_cast<double>(hi) - static_cast<double>(lo)) : __builtin_nanf("");
+}
+static_assert(kernargs_mirror<decltype(filter_step_runs_region_kernel<32, 32, 5>)>(
+                  {offsetof(StepRegionKernArgs, g), offsetof(StepRegionKernArgs, src), offsetof(StepRegionKernArgs, L), offsetof(StepRegionKernArgs, r),
+                   offsetof(StepRegionKernArgs, H), offsetof(StepRegionKernArgs, sp), offsetof(StepRegionKernArgs, rects)},
+                  offsetof(StepRegionKernArgs, rects) + sizeof(TileRects)),
+              "StepRegionKernArgs must mirror filter_step_runs_region_kernel's parameters");
+
 // ---- the chain's second launch (round 5): normals + slope + roughness by row moments and the StepFilter's second window over
 // the same 16 x 16 (32 x 32) cells, then the weighted sum.  kStep 0: the moment phase alone (the step window is a launch
 // of its own — its shape does not fit the row-run tables).  travOnly (run time, wave-uniform): store the traversability
@@ -772,7 +805,7 @@ __global__ __launch_bounds__(TR * TC) void filter_step_runs_kernel(MapGeom g, co
 // (512-thread workgroups: three of them per CU — six wavefronts per SIMD, 80 registers; without the hint the allocator takes 88
 // and a third of the CU's wavefronts with them: 0.283 -> 0.341 ms at 1 cm)
 // One tile of the fused launch: the second step window, the moment phase, the stores, the walking phase.
-template <int H, int TR, int TC, int HS>
+template <int H, int TR, int TC, int HS, bool kRegion = false>
 __device__ __forceinline__ void fused_tile(char* ldsRaw, const MapGeom& g, const float* __restrict__ elev, const FilterLayers& L, double rN, double slopeCritical, double roughCritical,
                                            double invSlopeCritical, double invRoughCritical, const StepShape& sN, double r2nd, int h2nd, const StepShape& s2, double stepCritical,
                                            float critDown, int nCritical, int kStepFlags, int travOnly, int ty, int tx) {
@@ -813,7 +846,7 @@ __device__ __forceinline__ void fused_tile(char* ldsRaw, const MapGeom& g, const
     }
     if (live && kStep && !travOnly) L.step[static_cast<size_t>(i) * g.cols + j] = stepOut;
     // the cells that take the literal walks (rank-deficient scatter, components at rounding level): a phase of their own
-    walk_phase<H, TR, TC>(ldsRaw, needWalk, stepOut);
+    walk_phase<H, TR, TC, kRegion>(ldsRaw, needWalk, stepOut);
 }
 
 constexpr int kFusedWaves = 6;
@@ -838,6 +871,29 @@ static_assert(kernargs_mirror<decltype(filter_fused_kernel<3, 32, 16, 5>)>(
                    offsetof(FusedKernArgs, kStepFlags), offsetof(FusedKernArgs, travOnly), offsetof(FusedKernArgs, tilesX), offsetof(FusedKernArgs, nTiles)},
                   offsetof(FusedKernArgs, nTiles) + sizeof(FusedKernArgs::nTiles)),
               "FusedKernArgs must mirror filter_fused_kernel's parameters");
+
+// The fused launch over the tiles of a rectangle list: FusedKernArgs as a prefix (walk_phase reads it), the list behind it.
+template <int H, int TR, int TC, int HS>
+__global__ __launch_bounds__(TR * TC) __attribute__((amdgpu_waves_per_eu(TR * TC == 512 ? ((H == 3 && HS == 5) ? kFusedWaves2cm : kFusedWaves) : 4))) void filter_fused_region_kernel(MapGeom g, const float* __restrict__ elev, FilterLayers L, double rN, double slopeCritical,
+                                                            double roughCritical, double invSlopeCritical, double invRoughCritical, StepShape sN, double r2nd, int h2nd, StepShape s2, double stepCritical,
+                                                            float critDown, int nCritical, int kStepFlags, int travOnly, int tilesX, int nTiles, TileRects rects) {
+    extern __shared__ __attribute__((aligned(16))) char ldsRaw[];
+    int ty, tx;
+    const auto ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    if (!fused_block_tile<true>(tilesX, nTiles, (TileRectsPtr)(ka + offsetof(FusedRegionKernArgs, rects)), ty, tx)) return;  // (workgroup-uniform)
+    fused_tile<H, TR, TC, HS, true>(ldsRaw, g, elev, L, rN, slopeCritical, roughCritical, invSlopeCritical, invRoughCritical, sN, r2nd, h2nd, s2, stepCritical, critDown, nCritical,
+                                    kStepFlags, travOnly, ty, tx);
+}
+#define FPE_FUSED_OFFSETS(S, P)                                                                                                                      \
+    offsetof(S, P g), offsetof(S, P elev), offsetof(S, P L), offsetof(S, P rN), offsetof(S, P slopeCritical), offsetof(S, P roughCritical),          \
+        offsetof(S, P invSlopeCritical), offsetof(S, P invRoughCritical), offsetof(S, P sN), offsetof(S, P r2nd), offsetof(S, P h2nd), offsetof(S, P s2), \
+        offsetof(S, P stepCritical), offsetof(S, P critDown), offsetof(S, P nCritical), offsetof(S, P kStepFlags), offsetof(S, P travOnly),         \
+        offsetof(S, P tilesX), offsetof(S, P nTiles)
+static_assert(offsetof(FusedRegionKernArgs, k) == 0, "FusedKernArgs is the prefix of the region kernel's arguments");
+static_assert(kernargs_mirror<decltype(filter_fused_region_kernel<3, 32, 16, 5>)>({FPE_FUSED_OFFSETS(FusedRegionKernArgs, k.), offsetof(FusedRegionKernArgs, rects)},
+                                                                                 offsetof(FusedRegionKernArgs, rects) + sizeof(TileRects)),
+              "FusedRegionKernArgs must mirror filter_fused_region_kernel's parameters");
+#undef FPE_FUSED_OFFSETS
 
 __host__ inline int filter_halo(double r, double res) { return static_cast<int>(r / res) + 1; }
 
@@ -920,6 +976,14 @@ FilterRoute filter_route(const FilterConsts& fc, const MapGeom& g) {
     }
     return rt;
 }
+// How far, in cells (Chebyshev), a changed elevation cell can reach into the traversability layer: the widest of the normals'
+// and the roughness disc and the two step windows one behind the other (a step value reads step heights within h2, each of which
+// reads elevations within h1).
+int filter_reach_cells(const FilterConsts& fc, double res) {
+    const int hN = filter_halo(fc.normalRadius, res), hR = filter_halo(fc.roughnessRadius, res);
+    const int h1 = filter_halo(fc.stepFirstRadius, res), h2 = filter_halo(fc.stepSecondRadius, res);
+    return std::max(std::max(hN, hR), h1 + h2);
+}
 // 1: the chain can run without the seven intermediate layers (launch_filters with travOnly).
 bool filters_trav_only_ok(const FilterConsts& fc, const MapGeom& g) {
     const FilterRoute rt = filter_route(fc, g);
@@ -1000,4 +1064,130 @@ hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float*
         hipLaunchKernelGGL(filter_step2_kernel, grid, block, disc_lds_bytes(rt.h2), stream, g, L, fc.stepSecondRadius, rt.h2, fc.stepCritical, critDown,
                            fc.stepCriticalCells);
     return hipGetLastError();
+}
+
+// ---- region launches of the traversability-only chain (fpe_update_elevation*) ---------------------------------------------------
+// Cells of the union of a few rectangles: coordinate compression (at most 2 n cuts per axis).
+int64_t cell_rects_union(const CellRect* r, int n, int rows, int cols) {
+    std::vector<int> ys(2 * static_cast<size_t>(n)), xs(2 * static_cast<size_t>(n));
+    int ny = 0, nx = 0;
+    const auto clip = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
+    for (int k = 0; k < n; ++k) {
+        ys[ny++] = clip(r[k].r0, rows);
+        ys[ny++] = clip(r[k].r1, rows);
+        xs[nx++] = clip(r[k].c0, cols);
+        xs[nx++] = clip(r[k].c1, cols);
+    }
+    std::sort(ys.begin(), ys.end());
+    std::sort(xs.begin(), xs.end());
+    int64_t cells = 0;
+    for (int a = 0; a + 1 < ny; ++a)
+        for (int b = 0; b + 1 < nx; ++b) {
+            if (ys[a] == ys[a + 1] || xs[b] == xs[b + 1]) continue;
+            for (int k = 0; k < n; ++k)
+                if (r[k].r0 <= ys[a] && ys[a + 1] <= r[k].r1 && r[k].c0 <= xs[b] && xs[b + 1] <= r[k].c1) {
+                    cells += static_cast<int64_t>(ys[a + 1] - ys[a]) * (xs[b + 1] - xs[b]);
+                    break;
+                }
+        }
+    return cells;
+}
+namespace {
+// tile code of the row-run launches -> tile rows, columns
+inline void runs_tile(int tcode, int& TR, int& TC) {
+    TR = tcode == 16 ? 16 : 32;
+    TC = tcode == 32 ? 32 : 16;
+}
+}  // namespace
+bool filters_region_plan(const MapGeom& g, const FilterConsts& fc, const CellRect* dirty, int nDirty, FilterRegion* out) {
+    if (nDirty < 0 || nDirty > kRegionMaxRects) return false;
+    const FilterRoute rt = filter_route(fc, g);
+    if (!(rt.tF && rt.stepFused)) return false;  // not the traversability-only route
+    int TR1, TC1;
+    runs_tile(rt.t1, TR1, TC1);
+    // the first window must be the row-run kernel, as in the full chain (launch_filters falls back to the walking kernel otherwise)
+    if (!rt.s1.ok || step_lds_bytes(rt.h1, rt.s1.nClasses, TR1, TC1) > 150 * 1024) return false;
+    const int TRf = kFusedRows, TCf = rt.tF;
+    FilterRegion rg{};
+    CellRect cover[kRegionMaxRects];
+    for (int k = 0; k < nDirty; ++k) {
+        const CellRect& d = dirty[k];
+        if (d.r0 < 0 || d.c0 < 0 || d.r1 > g.rows || d.c1 > g.cols || d.r0 >= d.r1 || d.c0 >= d.c1) return false;
+        const int ty0 = d.r0 / TRf, ty1 = (d.r1 - 1) / TRf + 1, tx0 = d.c0 / TCf, tx1 = (d.c1 - 1) / TCf + 1;
+        rg.fused.r[k] = TileRect{ty0, tx0, ty1 - ty0, tx1 - tx0};
+        rg.fused.nBlocks += (ty1 - ty0) * (tx1 - tx0);
+        cover[k] = CellRect{ty0 * TRf, tx0 * TCf, std::min(ty1 * TRf, g.rows), std::min(tx1 * TCf, g.cols)};
+        // the step heights those tiles read: their cells grown by the second window's halo, clipped to the map
+        const int r0 = std::max(cover[k].r0 - rt.h2, 0), r1 = std::min(cover[k].r1 + rt.h2, g.rows);
+        const int c0 = std::max(cover[k].c0 - rt.h2, 0), c1 = std::min(cover[k].c1 + rt.h2, g.cols);
+        const int sy0 = r0 / TR1, sy1 = (r1 - 1) / TR1 + 1, sx0 = c0 / TC1, sx1 = (c1 - 1) / TC1 + 1;
+        rg.step.r[k] = TileRect{sy0, sx0, sy1 - sy0, sx1 - sx0};
+        rg.step.nBlocks += (sy1 - sy0) * (sx1 - sx0);
+    }
+    rg.fused.n = rg.step.n = nDirty;
+    rg.recomputed = cell_rects_union(cover, nDirty, g.rows, g.cols);
+    *out = rg;
+    return true;
+}
+hipError_t launch_filters_region(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, const FilterRegion& rg, hipStream_t stream) {
+    const FilterRoute rt = filter_route(fc, g);
+    if (!(rt.tF && rt.stepFused && rt.s1.ok)) return hipErrorInvalidValue;
+    if (rg.fused.n == 0 || rg.fused.nBlocks == 0) return hipSuccess;  // nothing dirty
+    const auto fits = [](const void* fn, size_t bytes) -> hipError_t {
+        if (bytes <= 48 * 1024) return hipSuccess;
+        if (bytes > 150 * 1024) return hipErrorInvalidValue;
+        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    };
+    float critDown = static_cast<float>(fc.stepCritical);
+    if (static_cast<double>(critDown) > fc.stepCritical) critDown = std::nextafterf(critDown, -HUGE_VALF);
+    // 1. step heights (first window) over the grown tiles: the instantiation launch_filters picks for this tile code and halo
+    {
+        int TR, TC;
+        runs_tile(rt.t1, TR, TC);
+        const size_t bytes = step_lds_bytes(rt.h1, rt.s1.nClasses, TR, TC);
+        hipError_t e = hipErrorInvalidValue;
+#define FPE_RUNS_REGION(TRR, TCC, HS)                                                                                                              \
+    do {                                                                                                                                           \
+        e = fits(reinterpret_cast<const void*>(filter_step_runs_region_kernel<TRR, TCC, HS>), bytes);                                              \
+        if (e == hipSuccess)                                                                                                                       \
+            hipLaunchKernelGGL((filter_step_runs_region_kernel<TRR, TCC, HS>), dim3(rg.step.nBlocks), dim3(TRR * TCC), bytes, stream, g, d_elev, L, \
+                               fc.stepFirstRadius, rt.h1, rt.s1, rg.step);                                                                         \
+    } while (0)
+        if (rt.t1 == 32) {
+            if (rt.h1 == 5) FPE_RUNS_REGION(32, 32, 5);
+            else if (rt.h1 == 9) FPE_RUNS_REGION(32, 32, 9);
+            else FPE_RUNS_REGION(32, 32, 0);
+        } else if (rt.t1 == 24) {
+            if (rt.h1 == 17) FPE_RUNS_REGION(32, 16, 17);
+            else FPE_RUNS_REGION(32, 16, 0);
+        } else {
+            FPE_RUNS_REGION(16, 16, 0);
+        }
+#undef FPE_RUNS_REGION
+        if (e != hipSuccess) return e;
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    // 2. the fused launch over the dirty tiles
+    const auto fused = [&](auto kern) -> hipError_t {
+        const void* fn = reinterpret_cast<const void*>(kern);
+        const hipError_t e = fits(fn, rt.fusedBytes);
+        if (e != hipSuccess) return e;
+        const int tilesX = (g.cols + rt.tF - 1) / rt.tF, nTiles = tilesX * ((g.rows + kFusedRows - 1) / kFusedRows);
+        hipLaunchKernelGGL(kern, dim3(rg.fused.nBlocks), dim3(kFusedRows * rt.tF), rt.fusedBytes, stream, g, d_elev, L, fc.normalRadius, fc.slopeCritical, fc.roughnessCritical,
+                           1.0 / fc.slopeCritical, 1.0 / fc.roughnessCritical, rt.sN, fc.stepSecondRadius, rt.h2, rt.s2, fc.stepCritical, critDown, fc.stepCriticalCells,
+                           rt.stepFused | (fc.normalRadius <= fc.stepFirstRadius ? 2 : 0), 1, tilesX, nTiles, rg.fused);
+        return hipGetLastError();
+    };
+    if (rt.hN == 3 && rt.h2 == 5) return fused(filter_fused_region_kernel<3, kFusedRows, 16, 5>);
+    if (rt.hN == 6 && rt.h2 == 9) return fused(filter_fused_region_kernel<6, kFusedRows, 16, 9>);
+    switch (rt.hN) {
+#define FPE_FUSED_REGION_CASE(HH, TT) case HH: return fused(filter_fused_region_kernel<HH, kFusedRows, TT, 0>);
+        FPE_FUSED_REGION_CASE(1, 16) FPE_FUSED_REGION_CASE(2, 16) FPE_FUSED_REGION_CASE(3, 16) FPE_FUSED_REGION_CASE(4, 16) FPE_FUSED_REGION_CASE(5, 16)
+        FPE_FUSED_REGION_CASE(6, 16) FPE_FUSED_REGION_CASE(7, 16) FPE_FUSED_REGION_CASE(8, 16) FPE_FUSED_REGION_CASE(9, 32) FPE_FUSED_REGION_CASE(10, 32)
+        FPE_FUSED_REGION_CASE(11, 32) FPE_FUSED_REGION_CASE(12, 32)
+#undef FPE_FUSED_REGION_CASE
+        default: break;
+    }
+    return hipErrorInvalidValue;
 }

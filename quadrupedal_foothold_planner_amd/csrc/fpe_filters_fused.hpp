@@ -51,6 +51,42 @@ __device__ __forceinline__ void xcd_tile(int tilesX, int nTiles, int& ty, int& t
     tx = static_cast<int>(id - static_cast<unsigned>(ty) * static_cast<unsigned>(tilesX));
 }
 
+// Workgroup -> tile of a REGION launch (fpe_update_elevation*: the chain over the tiles whose input changed): the tiles stay on the
+// global grid, anchored at canonical (0, 0); the workgroups are numbered rectangle after rectangle of the short list behind the
+// kernel's other arguments, row-major inside a rectangle.  The rectangles may overlap: a tile belongs to the FIRST one that
+// contains it, and the workgroup a later rectangle puts on it is told to return at once (false) — no tile is computed twice in
+// one launch.  The list is read through the argument segment (scalar loads by a run-time index).
+typedef const TileRects __attribute__((address_space(4))) * TileRectsPtr;
+__device__ __forceinline__ bool region_tile(TileRectsPtr R, int& ty, int& tx) {
+    int b = static_cast<int>(blockIdx.x);
+    const int n = R->n;
+    ty = tx = 0;
+    int k = 0;
+    for (; k < n; ++k) {
+        const int cnt = R->r[k].ny * R->r[k].nx;
+        if (b < cnt) break;
+        b -= cnt;
+    }
+    if (k >= n) return false;
+    const int nx = R->r[k].nx, q = b / nx;
+    ty = R->r[k].ty0 + q;
+    tx = R->r[k].tx0 + (b - q * nx);
+    for (int m = 0; m < k; ++m)
+        if (ty >= R->r[m].ty0 && ty < R->r[m].ty0 + R->r[m].ny && tx >= R->r[m].tx0 && tx < R->r[m].tx0 + R->r[m].nx) return false;
+    return true;
+}
+// THE tile of a workgroup of the fused kernel, for its entry and for walk_phase alike (which does not receive its tile: it reads the
+// arguments again): the XCD-banded whole-map numbering, or — kRegion — the rectangle list.  false: the workgroup has no tile.
+template <bool kRegion>
+__device__ __forceinline__ bool fused_block_tile(int tilesX, int nTiles, TileRectsPtr rects, int& ty, int& tx) {
+    if constexpr (kRegion) {
+        return region_tile(rects, ty, tx);
+    } else {
+        xcd_tile(tilesX, nTiles, ty, tx);
+        return true;
+    }
+}
+
 // acos on [0, 1] (the float normal's z component, turned upwards) in f64: the rational approximation of fdlibm's e_acos.c
 // (Sun Microsystems; pS / qS are its published coefficients), the quotient by a refined reciprocal and the square root by a
 // refined reciprocal square root instead of IEEE division / sqrt sequences.  Within 1 ulp (f64) of the host's acos on 2 x 10^6
@@ -474,7 +510,13 @@ struct FusedKernArgs {
     float critDown;
     int nCritical, kStepFlags, travOnly, tilesX, nTiles;
 };
-template <int H, int TR, int TC>
+// filter_fused_region_kernel's: the same block with the rectangle list behind it, so that walk_phase reads every field it shares
+// with the whole-map kernel at the same place, and its tile from the list its entry took it from (fused_block_tile).
+struct FusedRegionKernArgs {
+    FusedKernArgs k;
+    TileRects rects;
+};
+template <int H, int TR, int TC, bool kRegion = false>
 __device__ __forceinline__ void walk_phase(char* ldsRaw, bool needWalk, float stepOut) {
     using Lay = FusedLayout<H, TR, TC>;
     if (!__syncthreads_or(needWalk ? 1 : 0)) return;  // (also: every thread is done with the prefix records)
@@ -488,7 +530,8 @@ __device__ __forceinline__ void walk_phase(char* ldsRaw, bool needWalk, float st
     const double r = ka->rN, slopeCritical = ka->slopeCritical, roughCritical = ka->roughCritical;
     const int kStep = ka->kStepFlags & 1, travOnly = ka->travOnly;
     int tyW, txW;
-    xcd_tile(ka->tilesX, ka->nTiles, tyW, txW);
+    // (a region workgroup that got here owns its tile: the others left at the kernel's entry)
+    fused_block_tile<kRegion>(ka->tilesX, ka->nTiles, (TileRectsPtr)((const char __attribute__((address_space(4)))*)ka4 + offsetof(FusedRegionKernArgs, rects)), tyW, txW);
     const int ti0 = tyW * TR, tj0 = txW * TC;
     const DiscLds d = disc_carve(ldsRaw, H, TR, TC);
     int* const count = reinterpret_cast<int*>(ldsRaw + Lay::discBytes);

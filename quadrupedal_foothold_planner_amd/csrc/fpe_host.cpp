@@ -631,14 +631,14 @@ int fpe_plan_state_from_feet(const double feet_xy[4][2], double adjusted_y, int3
 int fpe_map_update_validate(const fpe_map_desc* base, const fpe_map_update* u) {
     if (!base) return FPE_E_INVALID_ARG;
     const char* why = nullptr;
-    return fpe::check_map_update(base->rows, base->cols, u, &why);
+    return fpe::check_map_update(base->rows, base->cols, u, false, &why);
 }
 
 }  // extern "C"
 
 namespace fpe {
 
-int check_map_update(int rows, int cols, const fpe_map_update* u, const char** why) {
+int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevationOnly, const char** why) {
     auto bad = [&](const char* msg) {
         *why = msg;
         return static_cast<int>(FPE_E_INVALID_ARG);
@@ -653,7 +653,8 @@ int check_map_update(int rows, int cols, const fpe_map_update* u, const char** w
         if (p.n_rows <= 0 || p.n_cols <= 0) return bad("empty patch rectangle");
         if (p.row0 < 0 || p.col0 < 0 || static_cast<int64_t>(p.row0) + p.n_rows > rows || static_cast<int64_t>(p.col0) + p.n_cols > cols)
             return bad("patch rectangle outside the map");
-        if (!p.traversability || !p.elevation) return bad("null patch layer");
+        if (elevationOnly ? p.traversability != nullptr : !p.traversability) return bad(elevationOnly ? "an elevation update's patches carry no traversability" : "null patch layer");
+        if (!p.elevation) return bad("null patch layer");
         const bool rowMajor = p.col_stride == 1 && p.row_stride >= p.n_cols;
         const bool colMajor = p.row_stride == 1 && p.col_stride >= p.n_rows;
         if (!rowMajor && !colMajor) return bad("patch strides are neither row-major nor column-major with a pitch");

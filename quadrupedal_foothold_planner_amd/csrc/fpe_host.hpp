@@ -42,7 +42,9 @@ int spiral_rings(float searchRadius, double resolution);
 int validate_params(const fpe_params& p);
 
 // The refusals of fpe_update_map* for a map of rows x cols cells (include/fpe.h): FPE_OK, or FPE_E_INVALID_ARG with *why set.
-int check_map_update(int rows, int cols, const fpe_map_update* u, const char** why);
+// elevationOnly: the patches of fpe_update_elevation* (elevation required, traversability must be null).
+int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevationOnly, const char** why);
+
 
 // Opt track: the file-scope NLopt globals (cpp:28-51, 497-498, 514), the constraint thresholds
 // t1..t4 (cpp:1156-1159) and the column bounds of xBounds (cpp:1063-1066, 528-529), with the reference's typing.

@@ -20,8 +20,10 @@
 // -ffp-contract=off.  Reference citations: "cpp:" = foothold_planner/src/FootholdPlanner.cpp.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <type_traits>
+#include <vector>
 
 #include "fpe_device.hpp"
 #include "fpe_launch.hpp"

@@ -57,7 +57,7 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 constexpr int kUpdateMaxPairs = 4;  // the sets a snapshot keeps (acquire_mask)
 struct MapUpdatePatch {
     int32_t row0, col0, nr, nc;
-    const uint32_t* trav;
+    const uint32_t* trav;  // null: an elevation-only patch (fpe_update_elevation*): the traversability keeps the carried / cleared value
     const uint32_t* elev;
     int64_t rowStride, colStride;
 };
@@ -90,7 +90,34 @@ bool bits_supported(const PlanConsts& pc, const MapGeom& g);
 // ---- producer filters (fpe_filters.hpp) ----------------------------------------------------------------------
 bool filters_supported(const FilterConsts& fc, const MapGeom& g);
 bool filters_trav_only_ok(const FilterConsts& fc, const MapGeom& g);
+int filter_reach_cells(const FilterConsts& fc, double res);  // R of fpe_update_elevation* (include/fpe.h)
 hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, bool travOnly, hipStream_t stream);
+// Region launches of the traversability-only chain (fpe_update_elevation*): the same two kernels' bodies over the tiles of the
+// GLOBAL tile grid that a list of tile rectangles names, passed in the kernel arguments (no host-to-device copy).
+constexpr int kRegionMaxRects = 12;  // 8 patches + 4 bands
+struct TileRect {
+    int32_t ty0, tx0, ny, nx;  // tiles [ty0, ty0 + ny) x [tx0, tx0 + nx) of the launch's tile grid
+};
+struct TileRects {
+    int32_t n, nBlocks;  // rectangles used; workgroups of the launch = the sum of ny * nx
+    TileRect r[kRegionMaxRects];
+};
+struct CellRect {
+    int32_t r0, c0, r1, c1;  // cells [r0, r1) x [c0, c1)
+};
+struct FilterRegion {
+    TileRects fused;      // tiles of the fused launch: every tile that intersects a dirty rectangle
+    TileRects step;       // tiles of the step-height launch: those tiles' cells grown by the second step window's halo
+    int64_t recomputed;   // cells of the fused launch's tiles (the union, clipped to the map): what the chain stores
+};
+// Host arithmetic only.  false: no region launches for these parameters and this geometry (not the traversability-only route, a
+// step window the row-run kernel does not take, more than kRegionMaxRects rectangles) — the caller runs the full chain.
+bool filters_region_plan(const MapGeom& g, const FilterConsts& fc, const CellRect* dirty, int nDirty, FilterRegion* out);
+// Cells of the union of `n` rectangles (clipped to rows x cols)
+int64_t cell_rects_union(const CellRect* r, int n, int rows, int cols);
+// L.stepHeight and L.trav are the only valid pointers, as for launch_filters with travOnly.
+hipError_t launch_filters_region(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, const FilterRegion& rg,
+                                 hipStream_t stream);
 
 // ---- opt track (fpe_opt.hpp) ---------------------------------------------------------------------------------
 hipError_t launch_opt_track(const DevMap& m, const PlanConsts& pc, const OptConsts& oc, const fpe_pose* d_poses, int B, int nCycles,

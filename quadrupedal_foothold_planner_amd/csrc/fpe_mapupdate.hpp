@@ -20,6 +20,9 @@
 //                       per pair.  Rows -1 and `rows` of the planes fall into a group as rows of zeros; the padding word
 //                       groups are zeroed by launch_map_update, as launch_canonicalise does.
 // Values travel as 32-bit patterns.
+// fpe_update_elevation* (the producer's filters on the dirty region only) runs the same kernel with elevation-only patches — a patch
+// with a null traversability pointer leaves the carried or cleared value — and with no pairs: the chain writes the traversability
+// behind this pass, and the planes are built from the finished layer.
 #pragma once
 
 namespace {
@@ -61,7 +64,7 @@ __global__ __launch_bounds__(256) void map_update_kernel(MapUpdateArgs a) {
             const int pi = iFirst + r - q.row0;
             if (pi >= 0 && pi < q.nr) {
                 const int64_t k = pi * q.rowStride + pj * q.colStride;
-                t[r] = q.trav[k];
+                if (q.trav) t[r] = q.trav[k];  // (null: the elevation-only form of fpe_update_elevation* — the carried or cleared value stays)
                 e[r] = q.elev[k];
             }
         }

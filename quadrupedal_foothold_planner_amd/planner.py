@@ -159,6 +159,42 @@ def _host_patches(patches):
     return raw, keep
 
 
+def _host_elevation_patches(patches):
+    """[(row0, col0, elevation), ...] -> raw patches of an elevation-driven update (null traversability) and the arrays they point
+    into; strides as in _host_patches."""
+    raw, keep = _host_patches([(row0, col0, elev, elev) for row0, col0, elev in patches])
+    return [(r0, c0, nr, nc, None, e, rs, cs) for r0, c0, nr, nc, _, e, rs, cs in raw], keep
+
+
+def _info_dict(info):
+    return {"reach_cells": int(info.reach_cells), "route": int(info.route), "dirty_cells": int(info.dirty_cells),
+            "recomputed_cells": int(info.recomputed_cells)}
+
+
+def filter_reach_cells(resolution, params=None):
+    """fpe_filter_reach_cells: how many cells (Chebyshev) a changed elevation cell reaches into the traversability layer."""
+    r = _capi.lib().fpe_filter_reach_cells(C.byref(params) if params is not None else None, float(resolution))
+    if r < 0:
+        raise FpeError(r, "fpe_filter_reach_cells: bad filter parameters or resolution")
+    return r
+
+
+def elevation_update_plan(rows, cols, resolution, shift, position, rects, params=None, want_mask=True):
+    """fpe_elevation_update_plan (host arithmetic, no engine): the refusals and the dirty set of an elevation-driven update of a
+    rows x cols map.  rects: [(row0, col0, n_rows, n_cols), ...] (packed row-major sources are assumed) or raw patches as for
+    make_map_update.  Returns (info dict, dirty mask (rows, cols) uint8 or None); raises FpeError on a refusal."""
+    one = np.zeros(1, np.float32)  # the plan reads no patch value: any non-null elevation address will do
+    raw = [(p[0], p[1], p[2], p[3], None, one.ctypes.data, p[3], 1) if len(p) == 4 else p for p in rects]
+    u = make_map_update(shift, position, raw)
+    d = _map_desc(rows, cols, resolution)
+    info = _capi.ElevationUpdateInfo()
+    mask = np.zeros((rows, cols), np.uint8) if want_mask and rows > 0 and cols > 0 else None
+    rc = _capi.lib().fpe_elevation_update_plan(C.byref(d), C.byref(params) if params is not None else None, C.byref(u), C.byref(info), ptr(mask))
+    if rc != _capi.FPE_OK:
+        raise FpeError(rc, "fpe_elevation_update_plan refused the update")
+    return _info_dict(info), mask
+
+
 class _Handle:
     """What an engine and a group of engines share: the handle's creation, close / __del__, and the status check.  A subclass names
     its three entry points."""
@@ -246,6 +282,41 @@ class FootholdPlanner(_Handle):
         col_stride), ...] with DEVICE addresses and strides in floats; asynchronous on `stream`."""
         u = make_map_update(shift, position, list(patches))
         self._check(self._lib.fpe_update_map_device(self._h, C.byref(u), C.c_void_p(stream or 0)))
+
+    # ---- elevation-driven updates: the producer's filters on the dirty region only (fpe_update_elevation*) ----------
+    def update_elevation(self, shift, position, patches=(), params=None):
+        """fpe_update_elevation: update_map with patches = [(row0, col0, elevation), ...] that carry the elevation only; the
+        traversability of the cells whose input changed comes from the filter chain (`params`: a FilterParams, None = the
+        defaults), every other cell's is carried by the shift.  Returns the call's info dict (elevation_update_plan's).  Synchronous."""
+        raw, keep = _host_elevation_patches(patches)
+        u = make_map_update(shift, position, raw)
+        info = _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_update_elevation(self._h, C.byref(params) if params is not None else None, C.byref(u), C.byref(info)))
+        del keep
+        return _info_dict(info)
+
+    def update_elevation_device(self, shift, position, patches=(), params=None, stream=None):
+        """fpe_update_elevation_device: `patches` = [(row0, col0, n_rows, n_cols, d_elevation_ptr, row_stride, col_stride), ...] with
+        DEVICE addresses and strides in floats; asynchronous on `stream`, no host wait."""
+        raw = [(r0, c0, nr, nc, None, e, rs, cs) for r0, c0, nr, nc, e, rs, cs in patches]
+        u = make_map_update(shift, position, raw)
+        info = _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_update_elevation_device(self._h, C.byref(params) if params is not None else None, C.byref(u), C.byref(info),
+                                                          C.c_void_p(stream or 0)))
+        return _info_dict(info)
+
+    def read_map_layers(self, traversability=True, elevation=True):
+        """fpe_read_map_layers: the canonical layers of the current snapshot, bit for bit -> (traversability, elevation) as
+        (rows, cols) arrays (None for a layer not asked for)."""
+        g = self.map_info()
+        t = np.empty((g["rows"], g["cols"]), np.float32) if traversability else None
+        e = np.empty((g["rows"], g["cols"]), np.float32) if elevation else None
+        self._check(self._lib.fpe_read_map_layers(self._h, ptr(t), ptr(e)))
+        return t, e
+
+    def read_map_layers_device(self, d_trav_ptr=0, d_elev_ptr=0, stream=None):
+        """fpe_read_map_layers_device: the same copy into device buffers (0: not wanted), asynchronous on `stream`."""
+        self._check(self._lib.fpe_read_map_layers_device(self._h, C.c_void_p(d_trav_ptr or 0), C.c_void_p(d_elev_ptr or 0), C.c_void_p(stream or 0)))
 
     # ---- the producer of the map (SURVEY §8(f) N3; launch/mapping.launch:12-13) ----------------------
     def filter_params(self, **overrides):

@@ -1,0 +1,380 @@
+"""Elevation-driven map updates on the device (fpe_update_elevation*, fpe_read_map_layers*; include/fpe.h) against the numpy
+statement of the contract (tests/elevation_update_reference.py).  F — what every dirty cell must hold, bit for bit — is
+fpe_traversability_device's answer for the composed elevation E* at the new geometry, without a layer buffer.
+
+The bases carry a SENTINEL traversability S no filter can produce (finite, in [2, 3), different in every cell), so that every cell
+of the updated layer says where it came from: F (the chain stored it) or S shifted (the move carried it).
+
+Shapes (no map above 16 384 cells): 100 x 72 at 2 cm — several 32 x 16 and 32 x 32 tiles, ragged last tiles in both axes, the
+<3, 32, 16, 5> fused kernel; 48 x 40 at 2 cm — the 16 x 16 step tiles; 160 x 96 at 1 cm — <6, 32, 16, 9>; 100 x 72 at 2 cm with
+normal and roughness radius 0.07 — a generic fused instantiation.  The walk runs at 0.015625 m (dyadic: the oracle is then exact
+under translation, tests/test_cpu_elevation_update.py), which is another generic instantiation (halo 4)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import fpo
+from quadrupedal_foothold_planner_amd import _capi
+from quadrupedal_foothold_planner_amd.planner import FootholdPlanner, FpeError, make_map_update
+from tests import elevation_update_reference as er
+from tests import ingest_reference as ir
+from tests import map_update_reference as mu
+from tests import util
+from tests.test_gpu_filters import assert_layers_equal, assert_traversability_only
+from tests.test_gpu_ingest import N_CYCLES, DeviceSide, assert_same_bytes, edge_poses, observe_host
+
+pytestmark = pytest.mark.gpu
+
+POS0 = (0.0, 0.0)
+GENERIC = dict(normal_radius=0.07, roughness_radius=0.07)
+SHAPES = {"100x72@2cm": (100, 72, 0.02, {}), "48x40@2cm": (48, 40, 0.02, {}), "160x96@1cm": (160, 96, 0.01, {}),
+          "100x72@2cm,r0.07": (100, 72, 0.02, GENERIC)}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def planner():
+    p = FootholdPlanner(0)
+    yield p
+    p.close()
+
+
+def sentinel(rows, cols):
+    """Finite values in [2, 3), different per cell: nothing a filter produces (the layers lie in [0, 1] or are NaN)."""
+    s = (2.0 + (np.arange(rows * cols, dtype=np.float64) + 0.5) / (rows * cols)).astype(np.float32).reshape(rows, cols)
+    assert np.unique(s).size == rows * cols and s.min() >= 2.0 and s.max() < 3.0
+    return s
+
+
+def chain(planner, elev, res, pos, fp):
+    """F: fpe_traversability_device on a device copy of `elev`, no layer buffer."""
+    import torch
+
+    rows, cols = elev.shape
+    d_e = torch.from_numpy(np.ascontiguousarray(elev)).cuda()
+    d_t = torch.full((rows * cols,), 9.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    planner.traversability_device(d_e.data_ptr(), d_t.data_ptr(), rows, cols, res, position=pos, params=fp)
+    torch.cuda.synchronize()
+    return d_t.cpu().numpy().reshape(rows, cols)
+
+
+def check_update(t_new, e_new, info, f, e_star, s_shift, carried, d, rows, cols, shift, rects, R, what, route=None):
+    """The content contract of include/fpe.h on the layers read back."""
+    assert np.array_equal(bits(e_new), bits(e_star)), f"{what}: elevation is not E*"
+    assert np.array_equal(bits(t_new)[d], bits(f)[d]), f"{what}: {int((bits(t_new)[d] != bits(f)[d]).sum())} cells of D do not hold F"
+    is_f, is_s = bits(t_new) == bits(f), carried & (bits(t_new) == bits(s_shift))
+    assert (is_f | is_s).all(), f"{what}: {int((~(is_f | is_s)).sum())} cells hold neither F nor the shifted base"
+    stored = ~is_s  # (F != S wherever both are defined: a cell that does not hold the carried value was stored by the chain)
+    assert int(stored.sum()) == info["recomputed_cells"], f"{what}: {int(stored.sum())} cells stored, info says {info['recomputed_cells']}"
+    assert info["dirty_cells"] == int(d.sum()) and info["reach_cells"] == R, what
+    if route is not None:
+        assert info["route"] == route, what
+    if info["route"] == 0:
+        assert info["recomputed_cells"] <= er.grown_rect_cells(rows, cols, er.dirty_rects(rows, cols, shift, rects, R), 31), what
+    else:
+        assert info["recomputed_cells"] == rows * cols and is_f.all(), what
+
+
+# ---- 3. every valid case of the CPU test -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shift_k", range(6))
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_update_holds_f_on_d_and_f_or_the_carried_value_elsewhere(planner, shape, shift_k):
+    rows, cols, res, radii = SHAPES[shape]
+    shift = er.shifts(rows, cols)[shift_k]
+    fp = planner.filter_params(**radii)
+    R = er.reach(res, **dict(er.DEFAULT_RADII, **radii))
+    e0, s = er.terrain(rows, cols, 40 + shift_k), sentinel(rows, cols)
+    pos1 = er.moved_position(POS0, shift, res)
+    carried = mu.carried_mask(rows, cols, shift)
+    s_shift = er.shifted(s, shift)
+    showing = 0
+    for k, name in enumerate(er.PATCH_SETS):
+        rects = er.patch_rects(name, rows, cols, shift)
+        pv = er.patch_values(rects, 100 * shift_k + k)
+        e_star = er.compose_elevation(e0, shift, pv)
+        d = er.dirty_set(rows, cols, shift, rects, R)
+        f = chain(planner, e_star, res, pos1, fp)
+        assert (f[np.isfinite(f)] <= 1.0).all() and np.isfinite(f).any() == np.isfinite(e_star).any()  # F != S wherever F is finite
+        showing += bool(carried.any() and d.any() and (~d).any())
+        planner.gridmapCallback(s, e0, res, position=POS0)
+        info = planner.update_elevation(shift, pos1, pv, params=fp)
+        t_new, e_new = planner.read_map_layers()
+        mi = planner.map_info()
+        assert (mi["rows"], mi["cols"], mi["resolution"], mi["position"]) == (rows, cols, res, pos1)
+        check_update(t_new, e_new, info, f, e_star, s_shift, carried, d, rows, cols, shift, rects, R, f"{shape}, shift {shift}, patches {name}",
+                     route=0 if carried.any() else 1)
+    # the cases show something: cells carried, cells in D and cells outside D together (never for a shift that carries nothing;
+    # on 48 x 40 the grown patches leave cells outside D for the small sets only)
+    assert showing >= (3 if carried.any() else 0), showing
+
+
+def test_patch_source_forms_and_a_null_info(planner):
+    """Pitched and column-major host sources go as they are; info may be NULL."""
+    rows, cols, res = 100, 72, 0.02
+    shift, pos1 = (5, 3), er.moved_position(POS0, (5, 3), res)
+    e0, s = er.terrain(rows, cols, 7), sentinel(rows, cols)
+    rects = er.patch_rects("bands", rows, cols, shift) + [(30, 14, 4, 4)]
+    pv = er.patch_values(rects, 8)
+    e_star = er.compose_elevation(e0, shift, pv)
+    f = chain(planner, e_star, res, pos1, None)
+    d = er.dirty_set(rows, cols, shift, rects, 10)
+    for form in mu.FORMS:
+        planner.gridmapCallback(s, e0, res, position=POS0)
+        src = [(r0, c0, mu.patch_source(v, form, rows, cols, r0, c0)) for r0, c0, v in pv]
+        info = planner.update_elevation(shift, pos1, src)
+        t_new, e_new = planner.read_map_layers()
+        check_update(t_new, e_new, info, f, e_star, er.shifted(s, shift), mu.carried_mask(rows, cols, shift), d, rows, cols, shift, rects, 10, form, route=0)
+    planner.gridmapCallback(s, e0, res, position=POS0)
+    raw = [(r0, c0, v.shape[0], v.shape[1], None, v.ctypes.data, v.shape[1], 1) for r0, c0, v in pv]
+    u = make_map_update(shift, pos1, raw)
+    assert planner._lib.fpe_update_elevation(planner._h, None, C.byref(u), None) == _capi.FPE_OK
+    assert np.array_equal(bits(planner.read_map_layers()[0]), bits(t_new))  # a function of the inputs alone
+
+
+# ---- 4. the fallback ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows,cols,res,radii", [(100, 72, 0.02, dict(roughness_radius=0.07)), (128, 96, 0.005, {})], ids=["roughness 0.07", "0.5 cm"])
+def test_fallback_runs_the_full_chain(planner, rows, cols, res, radii):
+    shift, fp = (5, 3), planner.filter_params(**radii)
+    R = er.reach(res, **dict(er.DEFAULT_RADII, **radii))
+    pos1 = er.moved_position(POS0, shift, res)
+    e0, s = er.terrain(rows, cols, 61), sentinel(rows, cols)
+    rects = er.patch_rects("bands", rows, cols, shift)
+    pv = er.patch_values(rects, 62)
+    e_star = er.compose_elevation(e0, shift, pv)
+    f = chain(planner, e_star, res, pos1, fp)
+    planner.gridmapCallback(s, e0, res, position=POS0)
+    info = planner.update_elevation(shift, pos1, pv, params=fp)
+    t_new, e_new = planner.read_map_layers()
+    assert info["route"] == 1 and info["recomputed_cells"] == rows * cols
+    assert np.array_equal(bits(t_new), bits(f)) and np.array_equal(bits(e_new), bits(e_star))
+    assert info["dirty_cells"] == int(er.dirty_set(rows, cols, shift, rects, R).sum())
+
+
+# ---- 5. equivalence with an upload -------------------------------------------------------------------------------------------------
+def observe_all(planner, pairs, poses):
+    return [observe_host(planner, pair, poses) for pair in pairs]
+
+
+def test_updated_engine_equals_a_fresh_upload_of_the_layers(planner):
+    rows, cols, res = 100, 72, ir.RES
+    assert res == 0.02
+    shift, pos1 = (5, 3), er.moved_position(POS0, (5, 3), res)
+    e0 = er.terrain(rows, cols, 71, holes=0.01)
+    t0 = chain(planner, e0, res, POS0, None)
+    rects = er.patch_rects("bands", rows, cols, shift)  # (with the bands alone the tiles of rows 32 .. 63, columns 16 .. 47 are carried)
+    pv = er.patch_values(rects, 72)
+    held, fresh_pair = [ir.YAML_PAIR, ir.HISTORY_PAIRS[1]], (0.9, 0.85)
+    assert fresh_pair not in held and ir.HISTORY_PAIRS[1] != ir.YAML_PAIR
+    poses = edge_poses(rows, cols, 73)
+    a = FootholdPlanner(0)
+    b = FootholdPlanner(0)
+    try:
+        a.gridmapCallback(t0, e0, res, position=POS0)
+        base_obs = observe_all(a, held, None)  # the base now holds the planes of both pairs
+        info = a.update_elevation(shift, pos1, pv)
+        assert info["route"] == 0 and 0 < info["recomputed_cells"] < rows * cols
+        t_new, e_new = a.read_map_layers()
+        got = observe_all(a, held + [fresh_pair], poses)
+        b.gridmapCallback(t_new, e_new, res, position=pos1)
+        want = observe_all(b, held + [fresh_pair], poses)
+        assert a.map_info() == b.map_info()
+        for pair, g, w, in zip(held + [fresh_pair], got, want):
+            assert_same_bytes(g, w, f"updated against uploaded, pair {pair}")
+            assert "plan_bits_" in g["kernel"] and g["kernel"] == w["kernel"]
+            for k in g["plan"]:
+                assert g["plan"][k].tobytes() == w["plan"][k].tobytes(), (pair, k)
+        # stale planes would show: the held pairs' planes changed with the update
+        for g, o in zip(got, base_obs):
+            assert not np.array_equal(g["bits"]["flags"], o["bits"]["flags"])
+    finally:
+        a.close()
+        b.close()
+
+
+# ---- 6. a walk -----------------------------------------------------------------------------------------------------------------------
+def test_a_walk_of_five_updates_stays_within_the_frozen_bar(planner):
+    rows, cols, res, step = 100, 72, 0.015625, (3, -2)
+    R = er.reach(res)
+    e = er.terrain(rows, cols, 81, holes=0.01)
+    pos = (0.25, -0.5)
+    prm = fpo.filter_defaults()
+    ora_t = fpo.traversability_filters(e, res, position=pos, params=prm)["traversability"]  # the reference's own walk, on the CPU
+    planner.gridmapCallback(chain(planner, e, res, pos, None), e, res, position=pos)
+    for k in range(5):
+        rects = er.patch_rects("bands", rows, cols, step)
+        pv = er.patch_values(rects, 82 + k)
+        e = er.compose_elevation(e, step, pv)
+        pos = er.moved_position(pos, step, res)
+        info = planner.update_elevation(step, pos, pv)
+        assert info["route"] == 0 and info["recomputed_cells"] < rows * cols
+        d = er.dirty_set(rows, cols, step, rects, R)
+        ora_t = np.where(d, fpo.traversability_filters(e, res, position=pos, params=prm)["traversability"], er.shifted(ora_t, step))
+    ora = fpo.traversability_filters(e, res, position=pos, params=prm)
+    # the condition on the seed: the reference alone, walked the same way, ends where a fresh run on the final map does
+    assert np.array_equal(bits(ora_t), bits(ora["traversability"]))
+    t_new, e_new = planner.read_map_layers()
+    assert np.array_equal(bits(e_new), bits(e))
+    trav, layers = planner.traversability_from_elevation(e, res, position=pos, want_layers=True)
+    same_normal = assert_layers_equal(layers, ora)
+    assert_traversability_only(t_new, layers, ora, same_normal)
+
+
+# ---- 7. device form, refusals, read-back -----------------------------------------------------------------------------------------------
+def test_device_form_with_no_host_wait_and_plans_on_either_side():
+    rows, cols, res = 100, 72, ir.RES
+    shift, pos1 = (5, 3), er.moved_position(POS0, (5, 3), res)
+    e0 = er.terrain(rows, cols, 91, holes=0.01)
+    rects = er.patch_rects("bands", rows, cols, shift)
+    pv = er.patch_values(rects, 92)
+    e_star = er.compose_elevation(e0, shift, pv)
+    poses = edge_poses(rows, cols, 93)
+    planner = FootholdPlanner(0)
+    try:
+        t0 = chain(planner, e0, res, POS0, None)
+        f = chain(planner, e_star, res, pos1, None)
+        d = er.dirty_set(rows, cols, shift, rects, 10)
+        t_carried = er.shifted(t0, shift)  # (outside D either F or this is allowed)
+        pair = ir.YAML_PAIR
+        prm, opo = util.to_oracle_params(planner.params), util.to_oracle_poses(poses)
+        want_base = fpo.OracleMap(t0, e0, res).plan(prm, opo, N_CYCLES, threads=8)
+        dev = DeviceSide()
+        torch = dev.torch
+        d_poses = dev.poses(poses)
+        d_t0, d_e0 = torch.from_numpy(t0.reshape(-1)).cuda(), torch.from_numpy(e0.reshape(-1)).cuda()
+        d_patch = [torch.from_numpy(np.ascontiguousarray(v).reshape(-1)).cuda() for _, _, v in pv]
+        d_tout = torch.zeros(rows * cols, dtype=torch.float32, device="cuda")
+        d_eout = torch.zeros(rows * cols, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # the sources are in HBM; from here on the host waits for nothing
+        planner.upload_map_device(d_t0.data_ptr(), d_e0.data_ptr(), rows, cols, res, position=POS0, stream=dev.up.cuda_stream)
+        before = dev.queue_plan(planner, pair, d_poses, poses.shape[0], N_CYCLES)
+        raw = [(r0, c0, v.shape[0], v.shape[1], dp.data_ptr(), v.shape[1], 1) for (r0, c0, v), dp in zip(pv, d_patch)]
+        info = planner.update_elevation_device(shift, pos1, raw, stream=dev.up.cuda_stream)
+        after = dev.queue_plan(planner, pair, d_poses, poses.shape[0], N_CYCLES)
+        planner.read_map_layers_device(d_tout.data_ptr(), d_eout.data_ptr(), stream=dev.side.cuda_stream)
+        dev.side.synchronize()
+        dev.up.synchronize()
+        assert info["route"] == 0
+        t_new, e_new = d_tout.cpu().numpy().reshape(rows, cols), d_eout.cpu().numpy().reshape(rows, cols)
+        assert np.array_equal(bits(e_new), bits(e_star)) and np.array_equal(bits(t_new)[d], bits(f)[d])
+        assert ((bits(t_new) == bits(f)) | (bits(t_new) == bits(t_carried))).all()
+        util.assert_plan_equal(dev.fetch_plan(before, poses.shape[0], N_CYCLES), want_base)
+        got_after = dev.fetch_plan(after, poses.shape[0], N_CYCLES)
+        # the plan queued behind the update sees T*: a fresh engine given the layers read back plans the same, byte for byte
+        other = FootholdPlanner(0)
+        try:
+            other.gridmapCallback(t_new, e_new, res, position=pos1)
+            other.params = planner.params
+            fresh = other.plan(poses, N_CYCLES)
+        finally:
+            other.close()
+        for k in ("nominal", "cycle_ok"):
+            assert got_after[k].tobytes() == fresh[k].tobytes(), k
+        assert got_after["nominal"].tobytes() != dev.fetch_plan(before, poses.shape[0], N_CYCLES)["nominal"].tobytes(), "the two maps must plan differently"
+    finally:
+        planner.close()
+
+
+def test_refusals_leave_the_snapshot_as_it_was():
+    rows, cols, res = 48, 40, 0.02
+    e0, s = er.terrain(rows, cols, 95), sentinel(rows, cols)
+    v = np.zeros((4, 5), np.float32)
+    planner = FootholdPlanner(0)
+    try:
+        for call in (lambda: planner.update_elevation((1, 0), POS0, []), lambda: planner.update_elevation_device((1, 0), POS0, []),
+                     lambda: planner.read_map_layers()):
+            with pytest.raises(FpeError) as x:
+                call()
+            assert x.value.code == _capi.FPE_E_NO_MAP
+        planner.gridmapCallback(s, e0, res, position=POS0)
+        info = planner.map_info()
+        refused = [
+            make_map_update((1, 0), POS0, [(0, 0, 4, 5, v.ctypes.data, v.ctypes.data, 5, 1)]),  # a traversability pointer
+            make_map_update((1, 0), (float("nan"), 0.0), []),
+            make_map_update((1, 0), POS0, [(rows - 3, 0, 4, 5, None, v.ctypes.data, 5, 1)]),
+            make_map_update((1, 0), POS0, [(0, 0, 4, 5, None, None, 5, 1)]),
+            make_map_update((1, 0), POS0, [(0, 0, 4, 5, None, v.ctypes.data, 5, 2)]),
+            make_map_update((1, 0), POS0, [(0, 0, 0, 5, None, v.ctypes.data, 5, 1)]),
+        ]
+        refused.append(make_map_update((1, 0), POS0, []))
+        refused[-1].reserved = 1
+        refused.append(make_map_update((1, 0), POS0, []))
+        refused[-1].n_patches = 9
+        out = _capi.ElevationUpdateInfo(-5, -5, -5, -5)
+        for k, u in enumerate(refused):
+            assert planner._lib.fpe_update_elevation(planner._h, None, C.byref(u), C.byref(out)) == _capi.FPE_E_INVALID_ARG, k
+            assert planner._lib.fpe_update_elevation_device(planner._h, None, C.byref(u), C.byref(out), None) == _capi.FPE_E_INVALID_ARG, k
+        good = make_map_update((1, 0), POS0, [])
+        assert planner._lib.fpe_update_elevation(planner._h, C.byref(planner.filter_params(normal_radius=0.6)), C.byref(good), C.byref(out)) == _capi.FPE_E_UNSUPPORTED
+        assert planner._lib.fpe_update_elevation(planner._h, C.byref(planner.filter_params(normal_radius=0.0)), C.byref(good), C.byref(out)) == _capi.FPE_E_INVALID_ARG
+        assert planner._lib.fpe_update_elevation(planner._h, None, None, None) == _capi.FPE_E_INVALID_ARG
+        assert planner._lib.fpe_read_map_layers(planner._h, None, None) == _capi.FPE_E_INVALID_ARG
+        assert (out.reach_cells, out.route, out.dirty_cells, out.recomputed_cells) == (-5, -5, -5, -5)
+        assert planner.map_info() == info
+        t, e = planner.read_map_layers()
+        assert np.array_equal(bits(t), bits(s)) and np.array_equal(bits(e), bits(e0))
+        assert planner.update_elevation((1, 0), er.moved_position(POS0, (1, 0), res), [])["route"] == 0  # and the engine still takes a good one
+        only_t, none = planner.read_map_layers(elevation=False)
+        assert none is None and only_t.shape == (rows, cols)
+        none, only_e = planner.read_map_layers(traversability=False)
+        assert none is None and np.array_equal(bits(only_e), bits(er.shifted(e0, (1, 0))))
+    finally:
+        planner.close()
+
+
+@pytest.mark.parametrize("order", ["col", "row"])
+def test_read_back_of_an_uploaded_map_is_the_canonical_upload(planner, order):
+    rows, cols = 65, 63
+    rng = np.random.default_rng(5)
+    t = rng.random((rows, cols), dtype=np.float32)
+    e = rng.standard_normal((rows, cols)).astype(np.float32)
+    t[3, 4], e[7, 8], e[0, 0] = np.nan, np.nan, -np.inf
+    start = (17, 40)
+    bufs = [ir.message_buffer(a, start[0], start[1], order) for a in (t, e)]
+    bufs = [b if order == "row" else b.reshape(cols, rows) for b in bufs]
+    planner.gridmapCallback(bufs[0], bufs[1], 0.02, start_index=start, storage_order=order)
+    gt, ge = planner.read_map_layers()
+    assert np.array_equal(bits(gt), bits(t)) and np.array_equal(bits(ge), bits(e))
+    only_e = planner.read_map_layers(traversability=False)
+    assert only_e[0] is None and np.array_equal(bits(only_e[1]), bits(e))
+
+
+# ---- 8. cells that walk, in a dirty tile that is not tile (0, 0) -----------------------------------------------------------------------
+def test_walking_cells_in_a_dirty_tile_away_from_the_first(planner):
+    """The fused kernel's walking phase reads its tile again from the kernel arguments: a region launch that took the whole-map
+    numbering there would walk the wrong tile.  A single line of finite cells with varying elevations inside a band of holes (its
+    discs are collinear: rank-deficient, and not a plateau) and the edge of a constant plateau, both inside dirty tiles of tile
+    rows 1 and 2, tile columns 1 .. 3."""
+    rows, cols, res = 100, 72, 0.02
+    shift, pos1 = (0, 0), POS0
+    e0 = er.terrain(rows, cols, 97, holes=0.0)
+    e0[44:57, 18:60] = np.nan
+    e0[50, 20:58] = (0.1 + 0.03 * np.sin(np.arange(38) / 3.0)).astype(np.float32)  # one line of finite cells
+    e0[70:90, 20:50] = np.float32(0.25)                                             # a plateau: its edge cells see two elevations
+    rects = [(48, 30, 5, 12), (68, 24, 8, 8)]
+    pv = []
+    for r0, c0, nr, nc in rects:
+        v = e0[r0:r0 + nr, c0:c0 + nc].copy()
+        v[np.isfinite(v)] += np.float32(0.004)  # the same shapes, other elevations
+        pv.append((r0, c0, v))
+    e_star = er.compose_elevation(e0, shift, pv)
+    d = er.dirty_set(rows, cols, shift, rects, 10)
+    # on the CPU, through the oracle: rank-deficient cells that are no plateau interior (the z axis by the rank test, with a step
+    # height above 0 or a lone member) lie in D, outside tile (0, 0)
+    ora = fpo.traversability_filters(e_star, res, position=pos1)
+    with np.errstate(invalid="ignore"):
+        deficient = (ora["normal_z"] == 1.0) & ~(ora["step_height"] == 0)
+    ii, jj = np.nonzero(deficient & d)
+    assert ((ii >= 32) & (jj >= 16)).sum() >= 20 and ((ii == 50) & (jj >= 16)).sum() >= 10
+    s = sentinel(rows, cols)
+    f = chain(planner, e_star, res, pos1, None)
+    planner.gridmapCallback(s, e0, res, position=POS0)
+    info = planner.update_elevation(shift, pos1, pv)
+    t_new, e_new = planner.read_map_layers()
+    check_update(t_new, e_new, info, f, e_star, s, np.ones((rows, cols), bool), d, rows, cols, shift, rects, 10, "walking cells", route=0)
+    assert not d[:32, :16].any() and np.array_equal(bits(t_new)[:32, :16], bits(s)[:32, :16])  # tile (0, 0) is not dirty: nothing was stored there
+    assert np.isfinite(f[50, 30:42]).all() and np.array_equal(bits(t_new)[50, 20:58], bits(f)[50, 20:58])
