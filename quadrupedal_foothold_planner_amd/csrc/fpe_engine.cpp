@@ -416,6 +416,19 @@ hipError_t alloc_units(BufferPool& pool, size_t n, float** out, size_t* cap, boo
     *cap = n;
     return hipMalloc(reinterpret_cast<void**>(out), n * sizeof(float) + kLayerPadBytes);
 }
+// One pooled buffer of a call, returned to the pool on every exit path: recycled like the snapshot layers (a 10-20 Hz map stream
+// must not hipMalloc / hipFree per message).  dirty: work queued on it may still run when the call returns — its next taker
+// synchronises the device before reuse (BufferPool).
+struct PooledBuf {
+    std::shared_ptr<BufferPool> pool;
+    bool dirty;
+    size_t cap = 0;
+    float* p = nullptr;
+    hipError_t take(size_t n, bool cleanOnly = false) { return alloc_units(*pool, n, &p, &cap, cleanOnly); }
+    ~PooledBuf() {
+        if (p) pool->give(cap, p, dirty);
+    }
+};
 
 // What one launch needs besides the constants: the snapshot, and (bit-window path) its bit planes.
 struct CallPlan {
@@ -463,6 +476,17 @@ int build_mask(MapSnapshot& snap, float thrD, float thrC, hipStream_t stream, bo
         return fail_hip(e, "bit-plane build");
     }
     out = std::move(ms);
+    return FPE_OK;
+}
+// The planes of the carried pairs from `first` on, from the new snapshot's finished traversability layer, behind `stream`.
+int build_carried_planes(MapSnapshot& snap, const std::vector<std::pair<float, float>>& pairs, size_t first, hipStream_t stream, bool cleanOnly) {
+    for (size_t k = first; k < pairs.size(); ++k) {
+        std::shared_ptr<MaskSet> ms;
+        const int rc = build_mask(snap, pairs[k].first, pairs[k].second, stream, cleanOnly, ms);
+        if (rc != FPE_OK) return rc;
+        ms->lastUse.store(++snap.useClock);
+        snap.masks.push_back(std::move(ms));
+    }
     return FPE_OK;
 }
 
@@ -1040,9 +1064,9 @@ int copy_out(fpe_engine* h, CallCtx& cx, SegList list, const unsigned char* dev,
 
 int check_desc(const fpe_map_desc* d) {
     if (!d) return fail(FPE_E_INVALID_ARG, "null map descriptor");
-    if (d->rows <= 0 || d->cols <= 0 || d->rows > 32768 || d->cols > 32768)
-        return fail(FPE_E_INVALID_ARG, "map size out of range");
-    if (!(d->resolution > 0.0) || !std::isfinite(d->resolution)) return fail(FPE_E_INVALID_ARG, "bad resolution");
+    const char* why = "";
+    const int rc = fpe::check_map_geometry(d->rows, d->cols, d->resolution, &why);
+    if (rc != FPE_OK) return fail(rc, why);
     if (!std::isfinite(d->position[0]) || !std::isfinite(d->position[1])) return fail(FPE_E_INVALID_ARG, "bad position");
     if (d->start_index[0] < 0 || d->start_index[0] >= d->rows || d->start_index[1] < 0 || d->start_index[1] >= d->cols)
         return fail(FPE_E_INVALID_ARG, "start index out of range");
@@ -1175,20 +1199,10 @@ int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, co
     const bool canonical = desc->storage_order == 1 && desc->start_index[0] == 0 && desc->start_index[1] == 0;
     const float* src[2] = {trav, elev};
     float* dst[2] = {snap->d_trav, snap->d_elev};
-    // staging layer of a host upload in message layout: recycled like the snapshot layers (a 10-20 Hz map stream
-    // must not hipMalloc/hipFree per message), and returned to the pool on every exit path
-    struct Staging {
-        std::shared_ptr<BufferPool> pool;
-        size_t cap = 0;
-        float* p = nullptr;
-        ~Staging() {
-            if (p) pool->give(cap, p);
-        }
-    } stagingGuard{h->pool};
+    // staging layer of a host upload in message layout (handed back clean: a host upload waits for its stream layer by layer)
+    PooledBuf stagingGuard{h->pool, false};
     float*& staging = stagingGuard.p;
-    if (!srcOnDevice && !canonical) {
-        FPE_HIP(alloc_units(*h->pool, n, &staging, &stagingGuard.cap));
-    }
+    if (!srcOnDevice && !canonical) FPE_HIP(stagingGuard.take(n));
     // Threshold pairs the CURRENT snapshot was planned with: their bit planes are built here, on the upload's stream — the
     // upload is the 10-20 Hz path that may take a recycled ("dirty") buffer behind a device synchronisation; the first plan on
     // the new map then finds its planes and pays nothing (include/fpe.h: "plans never pay for it").  The FIRST pair's planes
@@ -1235,116 +1249,10 @@ int upload_common(fpe_engine* h, const fpe_map_desc* desc, const float* trav, co
         rc = folded_ready(*snap, folded, stream);
         if (rc != FPE_OK) return rc;
     }
-    for (size_t k = folded ? 1 : 0; k < pairs.size(); ++k) {
-        std::shared_ptr<MaskSet> ms;
-        rc = build_mask(*snap, pairs[k].first, pairs[k].second, stream, false, ms);
-        if (rc != FPE_OK) return rc;
-        ms->lastUse.store(++snap->useClock);
-        snap->masks.push_back(std::move(ms));
-    }
+    rc = build_carried_planes(*snap, pairs, folded ? 1 : 0, stream, false);
+    if (rc != FPE_OK) return rc;
     return install_snapshot(h, snap, !srcOnDevice, stream);
 }
-
-}  // namespace
-
-// ---- fpe_update_elevation*: what the engine-free plan call and the engine's update share (host arithmetic only) ----------------
-namespace fpe {
-// What fpe_elevation_update_plan and the engine's fpe_update_elevation* share (host arithmetic only): the refusals, the new
-// geometry, the clamped shift, the dirty set D as rectangles, the route and — route 0 — the tile rectangles of the region launches.
-struct ElevationUpdatePlan {
-    fpe_elevation_update_info info;
-    FilterConsts fc;
-    MapGeom g;
-    int sr, sc;
-    std::vector<CellRect> dirty;
-    FilterRegion region;
-};
-
-// fpe_filter_params -> FilterConsts; FPE_E_INVALID_ARG for a radius or critical value that is not positive and finite.
-int filter_consts(const fpe_filter_params& fp, FilterConsts& fc) {
-    const double radii[4] = {fp.normal_radius, fp.step_first_radius, fp.step_second_radius, fp.roughness_radius};
-    for (double r : radii)
-        if (!(r > 0.0) || !std::isfinite(r)) return FPE_E_INVALID_ARG;
-    if (!(fp.slope_critical > 0.0) || !(fp.step_critical > 0.0) || !(fp.roughness_critical > 0.0) || fp.step_critical_cells <= 0) return FPE_E_INVALID_ARG;
-    fc = FilterConsts{fp.normal_radius, fp.slope_critical, fp.step_critical, fp.step_first_radius, fp.step_second_radius,
-                      fp.step_critical_cells, fp.roughness_critical, fp.roughness_radius};
-    return FPE_OK;
-}
-
-// The dirty set D of include/fpe.h as rectangles: the patch rectangles and the bands without a source grown by R, and the bands
-// whose window the map edge clips differently before and after the move — whole rows / columns, found as runs of per-line flags.
-void elevation_dirty_rects(int rows, int cols, int R, int sr, int sc, const fpe_map_update* u, std::vector<CellRect>& out) {
-    out.clear();
-    if (std::abs(sr) >= rows || std::abs(sc) >= cols) {  // nothing is carried: every cell is without a source
-        out.push_back(CellRect{0, 0, rows, cols});
-        return;
-    }
-    const auto line_runs = [&](int n, int s, bool rowAxis) {
-        std::vector<uint8_t> flag(static_cast<size_t>(n), 0);
-        for (int i = 0; i < n; ++i) {
-            // C grown by R: some line within R has no source
-            const int lo = std::max(i - R, 0), hi = std::min(i + R, n - 1);
-            const bool noSource = s > 0 ? hi + s >= n : (s < 0 ? lo + s < 0 : false);
-            const bool clipped = s != 0 && (i < R || i >= n - R || i + s < R || i + s >= n - R);  // B
-            flag[static_cast<size_t>(i)] = noSource || clipped;
-        }
-        for (int i = 0; i < n;) {
-            if (!flag[static_cast<size_t>(i)]) {
-                ++i;
-                continue;
-            }
-            int j = i;
-            while (j < n && flag[static_cast<size_t>(j)]) ++j;
-            out.push_back(rowAxis ? CellRect{i, 0, j, cols} : CellRect{0, i, rows, j});
-            i = j;
-        }
-    };
-    line_runs(rows, sr, true);
-    line_runs(cols, sc, false);
-    for (int k = 0; k < u->n_patches; ++k) {
-        const fpe_map_patch& p = u->patch[k];
-        const CellRect r{std::max(p.row0 - R, 0), std::max(p.col0 - R, 0), static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(p.row0) + p.n_rows + R, rows)),
-                         static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(p.col0) + p.n_cols + R, cols))};
-        bool inside = false;  // (a rectangle inside an earlier one adds nothing)
-        for (const CellRect& q : out) inside = inside || (q.r0 <= r.r0 && r.r1 <= q.r1 && q.c0 <= r.c0 && r.c1 <= q.c1);
-        if (!inside) out.push_back(r);
-    }
-}
-
-int plan_elevation_update(int rows, int cols, double res, const fpe_filter_params* fp, const fpe_map_update* u, ElevationUpdatePlan& plan, const char** why) {
-    auto bad = [&](int rc, const char* msg) {
-        *why = msg;
-        return rc;
-    };
-    int rc = check_map_update(rows, cols, u, true, why);
-    if (rc != FPE_OK) return rc;
-    if (rows > 32768 || cols > 32768) return bad(FPE_E_INVALID_ARG, "map size out of range");
-    if (!(res > 0.0) || !std::isfinite(res)) return bad(FPE_E_INVALID_ARG, "bad resolution");
-    fpe_filter_params def;
-    if (!fp) {
-        fpe_filter_params_defaults(&def);
-        fp = &def;
-    }
-    if (filter_consts(*fp, plan.fc) != FPE_OK) return bad(FPE_E_INVALID_ARG, "filter radii and critical values must be positive and finite");
-    plan.g = make_geom(rows, cols, res, u->position[0], u->position[1]);
-    if (!filters_supported(plan.fc, plan.g)) return bad(FPE_E_UNSUPPORTED, "filter radius spans more cells than the stencil tables hold");
-    plan.sr = std::max(-rows, std::min(rows, u->shift[0]));  // beyond +-rows nothing is carried either way
-    plan.sc = std::max(-cols, std::min(cols, u->shift[1]));
-    const int R = filter_reach_cells(plan.fc, res);
-    elevation_dirty_rects(rows, cols, R, plan.sr, plan.sc, u, plan.dirty);
-    plan.info.reach_cells = R;
-    plan.info.dirty_cells = cell_rects_union(plan.dirty.data(), static_cast<int>(plan.dirty.size()), rows, cols);
-    const bool carried = std::abs(plan.sr) < rows && std::abs(plan.sc) < cols;
-    const bool region = carried && static_cast<int>(plan.dirty.size()) <= kRegionMaxRects &&
-                        filters_region_plan(plan.g, plan.fc, plan.dirty.data(), static_cast<int>(plan.dirty.size()), &plan.region);
-    plan.info.route = region ? 0 : 1;
-    plan.info.recomputed_cells = region ? plan.region.recomputed : static_cast<int64_t>(rows) * cols;
-    return FPE_OK;
-}
-
-}  // namespace fpe
-
-namespace {
 
 // The patches of an update into its argument block.  Device form: the caller's arrays as they are.  Host form: packed row-major
 // into a call context's pinned arena (their strides resolved here), ONE host-to-device copy queued on the context's stream, which
@@ -1390,17 +1298,26 @@ int stage_update_patches(fpe_engine* h, const fpe_map_update* u, bool srcOnDevic
     return FPE_OK;
 }
 
-// fpe_update_map*: the snapshot current at entry shifted by whole cells, cleared where nothing is carried, the patches written over
-// that (include/fpe.h) — one launch of map_update_kernel, which also writes the planes of every pair the base was planned with.
-// Host form: the patches packed row-major into the call context's pinned arena (their strides resolved here), ONE host-to-device
-// copy, the kernel on the context's stream, one synchronisation.  Device form: the caller's patch arrays as they are, on `stream`.
-int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipStream_t stream) {
-    if (!h || !u) return fail(FPE_E_INVALID_ARG, "null handle or update");
-    std::lock_guard<std::mutex> serial(h->updateMu);
+// ---- what fpe_update_map* and fpe_update_elevation* share: an incremental update from its entry to its composing kernel's
+// arguments (update_open) and from the finished layers to the installed snapshot (update_close) -------------------------------------
+struct UpdateCall {
+    std::unique_lock<std::mutex> serial;  // h->updateMu, for the whole call
     // (declared ahead of the lease: on an early exit the lease waits for its stream BEFORE the snapshots are released, as in HostCall)
     CallPlan baseRef;
-    std::shared_ptr<MapSnapshot>& base = baseRef.snap;
     std::shared_ptr<MapSnapshot> snap;
+    std::unique_ptr<CtxLease> lease;
+    fpe::MapUpdateArgs a;
+    hipStream_t stream = nullptr;
+    bool srcOnDevice = false;
+};
+// The snapshot current at entry as the base, check(base geometry, &why) — the call's refusals —, the new snapshot, map_update_kernel's
+// arguments but for the pairs, the patches staged (host form: ONE host-to-device copy on the call context's stream, which becomes
+// uc.stream), and that stream behind the base's upload.
+template <class Check>
+int update_open(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, bool elevationOnly, hipStream_t stream, UpdateCall& uc, Check check) {
+    if (!h || !u) return fail(FPE_E_INVALID_ARG, "null handle or update");
+    uc.serial = std::unique_lock<std::mutex>(h->updateMu);
+    std::shared_ptr<MapSnapshot>& base = uc.baseRef.snap;
     {
         std::lock_guard<std::mutex> lk(h->mu);
         base = h->map;
@@ -1408,51 +1325,107 @@ int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipS
     if (!base) return fail(FPE_E_NO_MAP, "no map uploaded");
     const int rows = base->g.rows, cols = base->g.cols;
     const char* why = "";
-    int rc = fpe::check_map_update(rows, cols, u, false, &why);
+    int rc = check(base->g, &why);
     if (rc != FPE_OK) return fail(rc, why);
     FPE_HIP(hipSetDevice(h->device));
-    rc = new_snapshot(h, rows, cols, base->g.res, u->position[0], u->position[1], snap);
+    rc = new_snapshot(h, rows, cols, base->g.res, u->position[0], u->position[1], uc.snap);
     if (rc != FPE_OK) return rc;
 
-    fpe::MapUpdateArgs a;
+    fpe::MapUpdateArgs& a = uc.a;
     std::memset(&a, 0, sizeof(a));
     a.baseTrav = reinterpret_cast<const uint32_t*>(base->d_trav);
     a.baseElev = reinterpret_cast<const uint32_t*>(base->d_elev);
-    a.dstTrav = reinterpret_cast<uint32_t*>(snap->d_trav);
-    a.dstElev = reinterpret_cast<uint32_t*>(snap->d_elev);
+    a.dstTrav = reinterpret_cast<uint32_t*>(uc.snap->d_trav);
+    a.dstElev = reinterpret_cast<uint32_t*>(uc.snap->d_elev);
     a.rows = rows;
     a.cols = cols;
     a.sr = std::max(-rows, std::min(rows, u->shift[0]));  // beyond +-rows nothing is carried either way
     a.sc = std::max(-cols, std::min(cols, u->shift[1]));
     a.nPatches = u->n_patches;
-    std::unique_ptr<CtxLease> lease;
-    rc = stage_update_patches(h, u, srcOnDevice, false, a, lease, stream);
+    uc.stream = stream;
+    uc.srcOnDevice = srcOnDevice;
+    rc = stage_update_patches(h, u, srcOnDevice, elevationOnly, a, uc.lease, uc.stream);
     if (rc != FPE_OK) return rc;
-    FPE_HIP(base->wait_ready(stream));  // the update's stream behind the base's upload
+    FPE_HIP(base->wait_ready(uc.stream));  // the update's stream behind the base's upload
     // the device form reads the base asynchronously and keeps no reference past this call: the base counts as read by an
     // asynchronous launch, so its buffers (and, through ~MapSnapshot, its planes) are recycled only behind a device synchronisation
-    if (srcOnDevice) mark_async_launch(baseRef);
-    const std::vector<std::pair<float, float>> pairs = carried_pairs(base);
+    if (srcOnDevice) mark_async_launch(uc.baseRef);
+    return FPE_OK;
+}
+// Behind the kernels that wrote the new snapshot's layers: its ready event, planes() — the carried pairs' planes into the snapshot's
+// sets —, the host form's synchronisation, and the snapshot becomes the engine's current one.
+template <class Planes>
+int update_close(fpe_engine* h, UpdateCall& uc, Planes planes) {
+    FPE_HIP(hipEventCreateWithFlags(&uc.snap->ready, hipEventDisableTiming));
+    FPE_HIP(hipEventRecord(uc.snap->ready, uc.stream));
+    const int rc = planes();
+    if (rc != FPE_OK) return rc;
+    if (!uc.srcOnDevice) {  // host sources may be freed on return — and the arena goes back to the pool
+        FPE_HIP(hipStreamSynchronize(uc.stream));
+        uc.lease->ctx->inFlight = false;
+    }
+    return install_snapshot(h, uc.snap, !uc.srcOnDevice, uc.stream);
+}
+
+// fpe_update_map*: the snapshot current at entry shifted by whole cells, cleared where nothing is carried, the patches written over
+// that (include/fpe.h) — one launch of map_update_kernel, which also writes the planes of every pair the base was planned with.
+// Host form: the patches packed row-major into the call context's pinned arena (their strides resolved here), ONE host-to-device
+// copy, the kernel on the context's stream, one synchronisation.  Device form: the caller's patch arrays as they are, on `stream`.
+int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipStream_t stream) {
+    UpdateCall uc;
+    int rc = update_open(h, u, srcOnDevice, false, stream, uc,
+                         [&](const fpe::MapGeom& g, const char** why) { return fpe::check_map_update(g.rows, g.cols, u, false, why); });
+    if (rc != FPE_OK) return rc;
+    fpe::MapUpdateArgs& a = uc.a;
+    const std::vector<std::pair<float, float>> pairs = carried_pairs(uc.baseRef.snap);
     std::vector<std::shared_ptr<MaskSet>> folded(pairs.size());
     a.nPairs = static_cast<int32_t>(std::min<size_t>(pairs.size(), fpe::kUpdateMaxPairs));
     for (int k = 0; k < a.nPairs; ++k) {
-        rc = alloc_folded(*snap, pairs[static_cast<size_t>(k)], folded[static_cast<size_t>(k)]);
+        rc = alloc_folded(*uc.snap, pairs[static_cast<size_t>(k)], folded[static_cast<size_t>(k)]);
         if (rc != FPE_OK) return rc;
         a.pair[k] = fpe::MapUpdatePair{reinterpret_cast<uint4*>(folded[static_cast<size_t>(k)]->d_words), pairs[static_cast<size_t>(k)].first,
                                        pairs[static_cast<size_t>(k)].second};
     }
-    FPE_HIP(fpe::launch_map_update(a, stream));
-    FPE_HIP(hipEventCreateWithFlags(&snap->ready, hipEventDisableTiming));
-    FPE_HIP(hipEventRecord(snap->ready, stream));
-    for (int k = 0; k < a.nPairs; ++k) {
-        rc = folded_ready(*snap, folded[static_cast<size_t>(k)], stream);
+    FPE_HIP(fpe::launch_map_update(a, uc.stream));
+    return update_close(h, uc, [&]() {
+        for (int k = 0; k < a.nPairs; ++k) {
+            const int rk = folded_ready(*uc.snap, folded[static_cast<size_t>(k)], uc.stream);
+            if (rk != FPE_OK) return rk;
+        }
+        return static_cast<int>(FPE_OK);
+    });
+}
+
+// The producer's chain on `stream` for the map of geometry g, as `rt` decided it (ONE filter_route per API call).
+//   travOnly (rt.travOnly): the two-launch chain that stores step_height — into a slot of fpe_engine::filterSlots, under filterMu —
+//     and traversability, straight into d_trav: over the whole map or, with `region`, over its tiles;
+//   else: the full chain through eight layers — the caller's (d_layers) or pooled ones (taken into `pooled` here; cleanOnly as in
+//     alloc_units) — and, where d_trav is given and is not the layers' own traversability, the device-to-device copy into it.
+int run_filter_chain(fpe_engine* h, const fpe::MapGeom& g, const fpe::FilterConsts& fc, const fpe::FilterRoute& rt, const fpe::FilterRegion* region, bool travOnly,
+                     const float* d_elev, float* d_trav, float* d_layers, PooledBuf& pooled, bool cleanOnly, hipStream_t stream) {
+    const size_t n = static_cast<size_t>(g.rows) * g.cols;
+    if (travOnly) {
+        // the lock is held until the chain is QUEUED and its event recorded (see fpe_engine::filterSlots)
+        std::lock_guard<std::mutex> lk(h->filterMu);
+        fpe_engine::FilterSlot* slot = nullptr;
+        const int rc = filter_slot_take(h, n, stream, slot);
         if (rc != FPE_OK) return rc;
+        const fpe::FilterLayers L{nullptr, nullptr, nullptr, nullptr, slot->buf, nullptr, nullptr, d_trav};
+        const hipError_t e = fpe::launch_filters(g, fc, rt, d_elev, L, true, region, stream);
+        const hipError_t f = filter_slot_done(h, slot, stream);  // also behind a chain that failed half-way
+        FPE_HIP(e);
+        FPE_HIP(f);
+        return FPE_OK;
     }
-    if (!srcOnDevice) {  // host sources may be freed on return — and the arena goes back to the pool
-        FPE_HIP(hipStreamSynchronize(stream));
-        lease->ctx->inFlight = false;
+    if (!d_layers) {
+        FPE_HIP(pooled.take(8 * n, cleanOnly));
+        d_layers = pooled.p;
     }
-    return install_snapshot(h, snap, !srcOnDevice, stream);
+    const fpe::FilterLayers L{d_layers, d_layers + n, d_layers + 2 * n, d_layers + 3 * n, d_layers + 4 * n, d_layers + 5 * n,
+                              d_layers + 6 * n, d_layers + 7 * n};
+    FPE_HIP(fpe::launch_filters(g, fc, rt, d_elev, L, false, nullptr, stream));
+    if (d_trav && d_trav != L.trav) FPE_HIP(hipMemcpyAsync(d_trav, L.trav, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    return FPE_OK;
 }
 
 // fpe_update_elevation*: fpe_update_map's composition with elevation-only patches (the traversability layer is carried or cleared),
@@ -1462,96 +1435,34 @@ int update_common(fpe_engine* h, const fpe_map_update* u, bool srcOnDevice, hipS
 // ride in map_update_kernel here, the chain writes T* behind it).  One stream: compose -> step heights -> fused -> planes.
 int update_elevation_common(fpe_engine* h, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info, bool srcOnDevice,
                             hipStream_t stream) {
-    if (!h || !u) return fail(FPE_E_INVALID_ARG, "null handle or update");
-    std::lock_guard<std::mutex> serial(h->updateMu);
-    CallPlan baseRef;  // (ahead of the lease, as in update_common)
-    std::shared_ptr<MapSnapshot>& base = baseRef.snap;
-    std::shared_ptr<MapSnapshot> snap;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        base = h->map;
-    }
-    if (!base) return fail(FPE_E_NO_MAP, "no map uploaded");
-    const int rows = base->g.rows, cols = base->g.cols;
+    UpdateCall uc;
     fpe::ElevationUpdatePlan plan;
-    const char* why = "";
-    int rc = fpe::plan_elevation_update(rows, cols, base->g.res, fp, u, plan, &why);
-    if (rc != FPE_OK) return fail(rc, why);
-    FPE_HIP(hipSetDevice(h->device));
-    rc = new_snapshot(h, rows, cols, base->g.res, u->position[0], u->position[1], snap);
+    int rc = update_open(h, u, srcOnDevice, true, stream, uc, [&](const fpe::MapGeom& g, const char** why) {
+        return fpe::plan_elevation_update(g.rows, g.cols, g.res, fp, u, plan, why);
+    });
     if (rc != FPE_OK) return rc;
-    const size_t n = snap->n;
-
-    fpe::MapUpdateArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.baseTrav = reinterpret_cast<const uint32_t*>(base->d_trav);
-    a.baseElev = reinterpret_cast<const uint32_t*>(base->d_elev);
-    a.dstTrav = reinterpret_cast<uint32_t*>(snap->d_trav);
-    a.dstElev = reinterpret_cast<uint32_t*>(snap->d_elev);
-    a.rows = rows;
-    a.cols = cols;
-    a.sr = plan.sr;
-    a.sc = plan.sc;
-    a.nPatches = u->n_patches;
-    a.nPairs = 0;  // the planes follow the chain
-    std::unique_ptr<CtxLease> lease;
-    rc = stage_update_patches(h, u, srcOnDevice, true, a, lease, stream);
-    if (rc != FPE_OK) return rc;
-    FPE_HIP(base->wait_ready(stream));
-    if (srcOnDevice) mark_async_launch(baseRef);  // (as in update_common: the base is read asynchronously, no reference outlives the call)
+    MapSnapshot& snap = *uc.snap;
     // the new snapshot's own layers are written asynchronously from here on: should a later step fail, they go back dirty
     struct DirtyOnExit {
         MapSnapshot* s;
         ~DirtyOnExit() {
             if (s) s->note_async_use();
         }
-    } dirtyOnExit{srcOnDevice ? snap.get() : nullptr};
-    FPE_HIP(fpe::launch_map_update(a, stream));
+    } dirtyOnExit{srcOnDevice ? &snap : nullptr};
+    FPE_HIP(fpe::launch_map_update(uc.a, uc.stream));  // (nPairs 0: the planes follow the chain)
 
-    // pooled scratch of the full chain with intermediate layers (route 1 where the chain is not the traversability-only one)
-    struct Scratch {
-        std::shared_ptr<BufferPool> pool;
-        size_t cap = 0;
-        float* p = nullptr;
-        ~Scratch() {
-            if (p) pool->give(cap, p, true);
-        }
-    } scratch{h->pool};
-    const bool travOnly = plan.info.route == 0 || fpe::filters_trav_only_ok(plan.fc, plan.g);
-    if (travOnly) {
-        std::lock_guard<std::mutex> lk(h->filterMu);  // held until the chain is queued and the slot's event recorded
-        fpe_engine::FilterSlot* slot = nullptr;
-        rc = filter_slot_take(h, n, stream, slot);
-        if (rc != FPE_OK) return rc;
-        const fpe::FilterLayers L{nullptr, nullptr, nullptr, nullptr, slot->buf, nullptr, nullptr, snap->d_trav};
-        const hipError_t e = plan.info.route == 0 ? fpe::launch_filters_region(plan.g, plan.fc, snap->d_elev, L, plan.region, stream)
-                                                  : fpe::launch_filters(plan.g, plan.fc, snap->d_elev, L, true, stream);
-        const hipError_t f = filter_slot_done(h, slot, stream);  // also behind a chain that failed half-way
-        FPE_HIP(e);
-        FPE_HIP(f);
-    } else {
-        FPE_HIP(alloc_units(*h->pool, 8 * n, &scratch.p, &scratch.cap, srcOnDevice));  // (device form: never a device synchronisation)
-        float* d = scratch.p;
-        const fpe::FilterLayers L{d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, d + 6 * n, d + 7 * n};
-        FPE_HIP(fpe::launch_filters(plan.g, plan.fc, snap->d_elev, L, false, stream));
-        FPE_HIP(hipMemcpyAsync(snap->d_trav, L.trav, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    }
-    FPE_HIP(hipEventCreateWithFlags(&snap->ready, hipEventDisableTiming));
-    FPE_HIP(hipEventRecord(snap->ready, stream));
-    for (const auto& pair : carried_pairs(base)) {
-        std::shared_ptr<MaskSet> ms;
-        rc = build_mask(*snap, pair.first, pair.second, stream, srcOnDevice, ms);
-        if (rc != FPE_OK) return rc;
-        ms->lastUse.store(++snap->useClock);
-        snap->masks.push_back(std::move(ms));
-    }
-    if (!srcOnDevice) {  // host sources may be freed on return — and the arena goes back to the pool
-        FPE_HIP(hipStreamSynchronize(stream));
-        lease->ctx->inFlight = false;
-    }
+    // pooled scratch of the full chain with intermediate layers (route 1 where the chain is not the traversability-only one);
+    // device form: never a device synchronisation
+    PooledBuf scratch{h->pool, true};
+    const bool region = plan.info.route == 0;
+    rc = run_filter_chain(h, plan.g, plan.fc, plan.rt, region ? &plan.region : nullptr, region || plan.rt.travOnly, snap.d_elev, snap.d_trav, nullptr, scratch,
+                          srcOnDevice, uc.stream);
+    if (rc != FPE_OK) return rc;
+    rc = update_close(h, uc, [&]() { return build_carried_planes(snap, carried_pairs(uc.baseRef.snap), 0, uc.stream, srcOnDevice); });
+    if (rc != FPE_OK) return rc;
     dirtyOnExit.s = nullptr;
     if (info) *info = plan.info;
-    return install_snapshot(h, snap, !srcOnDevice, stream);
+    return FPE_OK;
 }
 
 // fpe_read_map_layers*: the canonical layers of the snapshot current at entry, copied out bit for bit.
@@ -1772,44 +1683,9 @@ int fpe_read_map_layers_device(fpe_handle h, float* d_traversability, float* d_e
     return read_layers_common(h, d_traversability, d_elevation, true, static_cast<hipStream_t>(stream));
 }
 
-int fpe_filter_reach_cells(const fpe_filter_params* fp, double resolution) {
-    fpe_filter_params def;
-    if (!fp) {
-        fpe_filter_params_defaults(&def);
-        fp = &def;
-    }
-    fpe::FilterConsts fc;
-    if (!(resolution > 0.0) || !std::isfinite(resolution) || fpe::filter_consts(*fp, fc) != FPE_OK) return FPE_E_INVALID_ARG;
-    return fpe::filter_reach_cells(fc, resolution);
-}
-
-int fpe_elevation_update_plan(const fpe_map_desc* base, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info,
-                              uint8_t* dirty) {
-    if (!base) return FPE_E_INVALID_ARG;
-    fpe::ElevationUpdatePlan plan;
-    const char* why = nullptr;
-    const int rc = fpe::plan_elevation_update(base->rows, base->cols, base->resolution, fp, u, plan, &why);
-    if (rc != FPE_OK) return rc;
-    if (info) *info = plan.info;
-    if (dirty) {
-        std::memset(dirty, 0, static_cast<size_t>(base->rows) * base->cols);
-        for (const fpe::CellRect& r : plan.dirty)
-            for (int i = r.r0; i < r.r1; ++i) std::memset(dirty + static_cast<size_t>(i) * base->cols + r.c0, 1, static_cast<size_t>(r.c1 - r.c0));
-    }
-    return FPE_OK;
-}
-
 int fpe_filter_params_defaults(fpe_filter_params* out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null out");
-    std::memset(out, 0, sizeof(*out));
-    out->normal_radius = 0.05;
-    out->slope_critical = 1.0;
-    out->step_critical = 0.12;
-    out->step_first_radius = 0.08;
-    out->step_second_radius = 0.08;
-    out->step_critical_cells = 4;
-    out->roughness_critical = 0.05;
-    out->roughness_radius = 0.05;
+    fpe::filter_params_defaults(*out);
     return FPE_OK;
 }
 
@@ -1819,85 +1695,53 @@ int filters_common(fpe_engine* h, const fpe_map_desc* desc, const fpe_filter_par
     if (!h || !fp || !elev || !trav) return fail(FPE_E_INVALID_ARG, "null argument");
     int rc = check_desc(desc);
     if (rc != FPE_OK) return rc;
-    const double radii[4] = {fp->normal_radius, fp->step_first_radius, fp->step_second_radius, fp->roughness_radius};
-    for (double r : radii)
-        if (!(r > 0.0) || !std::isfinite(r)) return fail(FPE_E_INVALID_ARG, "filter radius must be positive and finite");
-    if (!(fp->slope_critical > 0.0) || !(fp->step_critical > 0.0) || !(fp->roughness_critical > 0.0) || fp->step_critical_cells <= 0)
-        return fail(FPE_E_INVALID_ARG, "filter critical values must be positive");
+    fpe::FilterConsts fc;
+    if (fpe::filter_consts(*fp, fc) != FPE_OK) return fail(FPE_E_INVALID_ARG, fpe::kBadFilterParams);
     const fpe::MapGeom g = fpe::make_geom(desc->rows, desc->cols, desc->resolution, desc->position[0], desc->position[1]);
-    const fpe::FilterConsts fc{fp->normal_radius, fp->slope_critical, fp->step_critical, fp->step_first_radius, fp->step_second_radius,
-                               fp->step_critical_cells, fp->roughness_critical, fp->roughness_radius};
     if (!fpe::filters_supported(fc, g)) return fail(FPE_E_UNSUPPORTED, "filter radius spans more cells than the stencil tables hold");
+    const fpe::FilterRoute rt = fpe::filter_route(fc, g);
     FPE_HIP(hipSetDevice(h->device));
     const size_t n = static_cast<size_t>(desc->rows) * desc->cols;
     const bool canonical = desc->storage_order == 1 && desc->start_index[0] == 0 && desc->start_index[1] == 0;
-    // pooled scratch: the canonical elevation (when the source is a host buffer or in message layout) and the eight layers
-    struct Scratch {
-        std::shared_ptr<BufferPool> pool;
-        std::vector<std::pair<size_t, float*>> bufs;
-        ~Scratch() {
-            for (auto& b : bufs) pool->give(b.first, b.second, true);
-        }
-    } scratch{h->pool, {}};
-    auto take = [&](size_t units, float** out) -> hipError_t {
-        size_t cap = 0;
-        hipError_t e = alloc_units(*h->pool, units, out, &cap);
-        if (e == hipSuccess) scratch.bufs.emplace_back(cap, *out);
-        return e;
-    };
+    // pooled scratch: the canonical elevation (when the source is a host buffer or in message layout), its staging copy, a host
+    // caller's traversability and the eight layers
+    // (handed back marked dirty: the next taker synchronises the device before reuse, BufferPool)
+    PooledBuf canon{h->pool, true}, staging{h->pool, true}, travBuf{h->pool, true}, layerBuf{h->pool, true};
     const float* d_elev = elev;
     if (!onDevice || !canonical) {
-        float* canon = nullptr;
-        FPE_HIP(take(n, &canon));
+        FPE_HIP(canon.take(n));
         const float* dsrc = elev;
         if (!onDevice) {
-            float* staging = canon;
-            if (!canonical) FPE_HIP(take(n, &staging));
-            FPE_HIP(hipMemcpyAsync(staging, elev, n * sizeof(float), hipMemcpyHostToDevice, stream));
-            dsrc = staging;
+            float* stage = canon.p;
+            if (!canonical) {
+                FPE_HIP(staging.take(n));
+                stage = staging.p;
+            }
+            FPE_HIP(hipMemcpyAsync(stage, elev, n * sizeof(float), hipMemcpyHostToDevice, stream));
+            dsrc = stage;
         }
         if (!canonical)
-            FPE_HIP(fpe::launch_canonicalise(dsrc, canon, desc->rows, desc->cols, desc->start_index[0], desc->start_index[1],
+            FPE_HIP(fpe::launch_canonicalise(dsrc, canon.p, desc->rows, desc->cols, desc->start_index[0], desc->start_index[1],
                                              desc->storage_order, stream));
-        d_elev = canon;
+        d_elev = canon.p;
     }
-    float* d_layers = onDevice ? layers : nullptr;
     // Nobody asked for the intermediate layers (device caller without a layer buffer, host caller without `layers`): the
     // two-launch chain that stores step_height and traversability only, traversability straight into the caller's buffer
     // when it is a device buffer.
     // (not when the caller's traversability buffer IS — or overlaps — the elevation buffer: the fused launch writes traversability
     // tile by tile while its neighbours still read their halos; the layer-buffer path below writes scratch and copies afterwards)
     const bool inPlace = onDevice && trav < elev + n && elev < trav + n;
-    const bool travOnly = !layers && !inPlace && fpe::filters_trav_only_ok(fc, g);
-    if (travOnly) {
-        float* d_trav = trav;
-        if (!onDevice) FPE_HIP(take(n, &d_trav));
-        {
-            // the lock is held until the chain is QUEUED and its event recorded (see fpe_engine::filterSlots)
-            std::lock_guard<std::mutex> lk(h->filterMu);
-            fpe_engine::FilterSlot* slot = nullptr;
-            rc = filter_slot_take(h, n, stream, slot);
-            if (rc != FPE_OK) return rc;
-            const fpe::FilterLayers L{nullptr, nullptr, nullptr, nullptr, slot->buf, nullptr, nullptr, d_trav};
-            FPE_HIP(fpe::launch_filters(g, fc, d_elev, L, true, stream));
-            FPE_HIP(filter_slot_done(h, slot, stream));
-        }
-        if (!onDevice) {
-            FPE_HIP(hipMemcpyAsync(trav, d_trav, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-            FPE_HIP(hipStreamSynchronize(stream));
-        }
-        return FPE_OK;
+    const bool travOnly = !layers && !inPlace && rt.travOnly;
+    float* d_trav = onDevice ? trav : nullptr;
+    if (travOnly && !onDevice) {
+        FPE_HIP(travBuf.take(n));
+        d_trav = travBuf.p;
     }
-    if (!d_layers) FPE_HIP(take(8 * n, &d_layers));
-    const fpe::FilterLayers L{d_layers, d_layers + n, d_layers + 2 * n, d_layers + 3 * n, d_layers + 4 * n, d_layers + 5 * n,
-                              d_layers + 6 * n, d_layers + 7 * n};
-    FPE_HIP(fpe::launch_filters(g, fc, d_elev, L, false, stream));
-    if (onDevice) {
-        if (trav != L.trav) FPE_HIP(hipMemcpyAsync(trav, L.trav, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        // pooled scratch is handed back marked dirty: the next taker synchronises the device before reuse (BufferPool)
-    } else {
-        FPE_HIP(hipMemcpyAsync(trav, L.trav, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (layers) FPE_HIP(hipMemcpyAsync(layers, d_layers, 8 * n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    rc = run_filter_chain(h, g, fc, rt, nullptr, travOnly, d_elev, d_trav, onDevice ? layers : nullptr, layerBuf, false, stream);
+    if (rc != FPE_OK) return rc;
+    if (!onDevice) {
+        FPE_HIP(hipMemcpyAsync(trav, travOnly ? d_trav : layerBuf.p + 7 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (layers) FPE_HIP(hipMemcpyAsync(layers, layerBuf.p, 8 * n * sizeof(float), hipMemcpyDeviceToHost, stream));
         FPE_HIP(hipStreamSynchronize(stream));
     }
     return FPE_OK;

@@ -21,9 +21,8 @@
 
 namespace {
 
-constexpr int kFT = 16;        // tile edge of the disc stencils
-constexpr int kFilterMaxH = 24;  // largest halo the tables are sized for (e.g. r 0.115 m at 0.5 cm)
-
+// (kFT, the table limits, StepShape and the LDS-size formulas — disc_lds_bytes, step_lds_bytes, fused_moment_bytes: fpe_launch.hpp,
+// where the host's description of the chain sees them too)
 struct DiscLds {
     float* tile;        // (TR + 2H) x (TC + 2H) source cells, row-major, NaN outside the map
     double *xP, *yP;    // positions of the tile's rows / columns (halo included)
@@ -31,12 +30,6 @@ struct DiscLds {
     int *bi0, *bi1, *bj0, *bj1;  // [TR] / [TC] bounding rows / columns of the cell's iterator
     int H, WR, WC;      // halo, tile rows and columns with the halo
 };
-// (TR x TC: the workgroup's cells — kFT x kFT for the walking kernels; 16 x 16, 32 x 16 (rows x columns) or 32 x 32 for the
-// row-moment and row-run kernels)
-__host__ __device__ inline size_t disc_lds_bytes(int H, int TR = kFT, int TC = kFT) {
-    const int WR = TR + 2 * H, WC = TC + 2 * H;
-    return static_cast<size_t>(WR) * WC * 4 + static_cast<size_t>(WR + WC) * 8 + static_cast<size_t>(TR + TC) * (2 * H + 1) * 8 + 2 * (TR + TC) * 4 + 16;
-}
 __device__ __forceinline__ DiscLds disc_carve(char* base, int H, int TR = kFT, int TC = kFT) {
     DiscLds d;
     d.H = H;
@@ -404,66 +397,6 @@ __global__ __launch_bounds__(256) void filter_normals_kernel(MapGeom g, const fl
     if (fuseRough) L.rough[cell] = orough;
 }
 
-// ---- the disc as a lattice SHAPE -------------------------------------------------------------------------------------------
-// On the uniform lattice the members of a cell's disc are the same offsets for every cell — row offset o holds the columns
-// |dc| <= w(o) — except for the few offsets that lie ON the circle ((0, R), (R, 0), (3, 4) R / 5 ...), where
-// CircleIterator::isInside's rounding decides cell by cell.  step_shape sorts the offsets on the host: squared distance
-// against r^2 with a relative margin of 1e-7 (position differences are good to 1e-12).
-constexpr int kStepMaxClasses = 14;
-constexpr int kStepMaxEdge = 24;
-struct StepShape {
-    int8_t rowW[2 * kFilterMaxH + 1 + 3];  // per row offset o + H: its robust half-width, -1: no robust member
-    int8_t edgeR[kStepMaxEdge], edgeC[kStepMaxEdge];  // offsets on the circle
-    uint32_t storeMask;                // bit w: some row has half-width w — the run is stored at that width; its class = the number of set bits below w
-    int32_t nEdge, nClasses, wMax;
-    int32_t ok;                        // 0: the shape does not fit the step kernels' tables (the walking kernels run)
-    int32_t rowsOk;                    // 0: not even the rows' half-widths are to be trusted (map too far from the origin)
-    uint64_t edgeRows;                 // bit o + H: row offset o holds an offset on the circle (complete also when the edge list overflowed)
-};
-// reach: the largest |coordinate| of a cell of the map — a position difference carries ~2 ulp of that, which decides how wide
-// the band of offsets is that the per-cell arithmetic must settle.
-__host__ inline StepShape step_shape(double r, double res, int H, double reach) {
-    StepShape sp{};
-    for (auto& c : sp.rowW) c = -1;
-    sp.ok = 1;
-    sp.rowsOk = 1;
-    const double r2 = r * r, res2 = res * res;
-    // relative margin on squared distances: 1e-7 near the origin; far from it the rounding of the positions themselves
-    // (4 ulp of `reach` on a difference of one resolution, twice that on its square), with a factor of 16 to spare.
-    // Beyond 1e-3 two neighbouring offsets of a row could both be in doubt: the walking kernels take over.
-    const double rel = fmax(1e-7, 16.0 * 8.0 * 2.220446049250313e-16 * reach / res);
-    if (rel > 1e-3) {
-        sp.ok = sp.rowsOk = 0;
-        return sp;
-    }
-    const double margin = rel * r2;
-    for (int o = -H; o <= H; ++o) {
-        int w = -1;
-        for (int k = 0; k <= H; ++k) {
-            const double d2 = (static_cast<double>(o) * o + static_cast<double>(k) * k) * res2;
-            if (d2 < r2 - margin) {
-                w = k;
-            } else if (d2 <= r2 + margin) {  // on the circle: decided per cell
-                sp.edgeRows |= 1ull << (o + H);
-                for (int sgn = (k == 0 ? 1 : -1); sgn <= 1; sgn += 2) {
-                    if (sp.nEdge >= kStepMaxEdge) {
-                        sp.ok = 0;  // (the rows' half-widths below stay valid: the normals kernel tests the next column itself)
-                    } else {
-                        sp.edgeR[sp.nEdge] = static_cast<int8_t>(o);
-                        sp.edgeC[sp.nEdge] = static_cast<int8_t>(sgn * k);
-                        ++sp.nEdge;
-                    }
-                }
-            }
-        }
-        sp.rowW[o + H] = static_cast<int8_t>(w);
-        if (w >= 0) sp.storeMask |= 1u << w;
-        if (w > sp.wMax) sp.wMax = w;
-    }
-    sp.nClasses = __builtin_popcount(sp.storeMask);
-    if (sp.nClasses > kStepMaxClasses) sp.ok = 0;
-    return sp;
-}
 // ---- the same three filters by ROW MOMENTS (round 4; the kernel is round 5's filter_fused_kernel, fpe_filters_fused.hpp) -------
 // A cell's disc is at most 2H + 1 row intervals (disc_walk: the members of a row are one interval).  Everything the three
 // filters need of the members — count, mean, the 3 x 3 scatter matrix about the mean, and the sum of squared plane
@@ -477,8 +410,6 @@ __host__ inline StepShape step_shape(double r, double res, int H, double reach) 
 // rank-deficient matrix, smallest eigenvalue below 1e-10 of the scale: exact planes, flat synthetic ground, fewer than three
 // members, where the rank test and the last bits of a tiny component depend on the summation order — the cell takes the
 // literal walks above instead (wave-divergent; no natural terrain gets there).
-constexpr int kMomentMaxH = 12;
-
 // RoughnessFilter: needs the finished normal layers.
 __global__ __launch_bounds__(256) void filter_roughness_kernel(MapGeom g, const float* __restrict__ elev, FilterLayers L, double r, int H, double critical) {
     extern __shared__ __attribute__((aligned(16))) char ldsRaw[];
@@ -583,11 +514,6 @@ __global__ __launch_bounds__(256) void filter_step2_kernel(MapGeom g, FilterLaye
 //      the bounding box of the cell) and folds the members among them one by one.
 // Invalid cells are quiet NaNs in the tile: v_max / v_min skip them, `>` is false on them — what the iterator's isValid
 // test does.  Same members as disc_walk by construction: bit-identical layers (tests/test_gpu_filters.py).
-__host__ __device__ inline size_t step_lds_bytes(int H, int nClasses, int TR = kFT, int TC = kFT) {
-    const int WR = TR + 2 * H;
-    return ((disc_lds_bytes(H, TR, TC) + 15) & ~static_cast<size_t>(15)) + static_cast<size_t>(nClasses) * WR * TC * 8 + 128;
-}
-
 // kSecond false: step_height = max - min of the elevation over the first window.  true: the second window over the step
 // heights (their maximum and the number above the critical value).  One tile's worth as a device function — every thread of
 // the workgroup takes part in the barriers; `live`: the thread's cell lies inside the map.  Returns the fold of the window
@@ -895,163 +821,97 @@ static_assert(kernargs_mirror<decltype(filter_fused_region_kernel<3, 32, 16, 5>)
               "FusedRegionKernArgs must mirror filter_fused_region_kernel's parameters");
 #undef FPE_FUSED_OFFSETS
 
-__host__ inline int filter_halo(double r, double res) { return static_cast<int>(r / res) + 1; }
-
-}  // namespace
-
-bool filters_supported(const FilterConsts& fc, const MapGeom& g) {
-    const double rmax = std::fmax(std::fmax(fc.normalRadius, fc.roughnessRadius), std::fmax(fc.stepFirstRadius, fc.stepSecondRadius));
-    return filter_halo(rmax, g.res) <= kFilterMaxH;
+// ---- launches: THE list of instantiations, for the whole-map kernels and their region twins alike ---------------------------------
+// A form of the route (fpe_host.cpp: filter_route) -> its template arguments as constants: f(TR, TC, HS) / f(H, TC, HS).  Each
+// launch below names the whole-map kernel and the region kernel of a form in ONE generic lambda, so a form listed here exists
+// for both, and one that is not listed exists for neither.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <class F>
+hipError_t with_runs_form(const WindowForm& w, F&& f) {
+#define FPE_RUNS(TRR, TCC, HSS) \
+    if (w.TR == TRR && w.TC == TCC && w.HS == HSS) return f(Int<TRR>{}, Int<TCC>{}, Int<HSS>{})
+    FPE_RUNS(32, 32, 5);
+    FPE_RUNS(32, 32, 9);
+    FPE_RUNS(32, 32, 0);
+    FPE_RUNS(32, 16, 17);  // the published windows (0.08 m) at 0.5 cm
+    FPE_RUNS(32, 16, 0);
+    FPE_RUNS(16, 16, 0);
+#undef FPE_RUNS
+    return hipErrorInvalidValue;
 }
-// What a chain with these parameters can do without the caller's layer buffer: 1 = the two-launch chain that stores
-// step_height and traversability only (the fused kernel covers normals, slope, roughness and the second step window),
-// 0 = the intermediate layers have to exist (some filter runs as a launch of its own).
-struct FilterRoute {
-    StepShape sN, s1, s2;
-    int hN, hR, h1, h2;
-    int tF;          // tile COLUMNS of the fused kernel (its rows: 32), 0: the moment form does not apply (walking kernels)
-    int stepFused;   // the second step window rides in the fused kernel
-    int t1, t2;      // tiles of the row-run launches: 32 = 32 x 32, 24 = 32 rows x 16 columns, 16 = 16 x 16
-    size_t fusedBytes;
-};
-namespace {
-template <int H, int TR, int TC, int HS = 0>
-hipError_t launch_fused_one(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, const FilterRoute& rt, float critDown, int travOnly,
-                            hipStream_t stream) {
-    const void* fn = reinterpret_cast<const void*>(filter_fused_kernel<H, TR, TC, HS>);
-    if (rt.fusedBytes > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(rt.fusedBytes));
-        if (e != hipSuccess) return e;
-    }
-    const int tilesX = (g.cols + TC - 1) / TC, nTiles = tilesX * ((g.rows + TR - 1) / TR);
-    hipLaunchKernelGGL((filter_fused_kernel<H, TR, TC, HS>), dim3(nTiles), dim3(TR * TC), rt.fusedBytes, stream, g, d_elev, L, fc.normalRadius, fc.slopeCritical,
-                       fc.roughnessCritical, 1.0 / fc.slopeCritical, 1.0 / fc.roughnessCritical, rt.sN, fc.stepSecondRadius, rt.h2, rt.s2, fc.stepCritical, critDown, fc.stepCriticalCells,
-                       rt.stepFused | (fc.normalRadius <= fc.stepFirstRadius ? 2 : 0), travOnly, tilesX, nTiles);
+template <class F>
+hipError_t with_fused_form(const FusedForm& u, F&& f) {
+#define FPE_FUSED_CASE(HH, TT, HSS) \
+    if (u.H == HH && u.TC == TT && u.HS == HSS) return f(Int<HH>{}, Int<TT>{}, Int<HSS>{})
+    // the published default chain at 2 cm and 1 cm (normals 0.05 m, second step window 0.08 m): the step window's halo is a
+    // compile-time constant too
+    FPE_FUSED_CASE(3, 16, 5);
+    FPE_FUSED_CASE(6, 16, 9);
+    FPE_FUSED_CASE(1, 16, 0); FPE_FUSED_CASE(2, 16, 0); FPE_FUSED_CASE(3, 16, 0); FPE_FUSED_CASE(4, 16, 0); FPE_FUSED_CASE(5, 16, 0); FPE_FUSED_CASE(6, 16, 0);
+    FPE_FUSED_CASE(7, 16, 0); FPE_FUSED_CASE(8, 16, 0); FPE_FUSED_CASE(9, 32, 0); FPE_FUSED_CASE(10, 32, 0); FPE_FUSED_CASE(11, 32, 0); FPE_FUSED_CASE(12, 32, 0);
+#undef FPE_FUSED_CASE
+    return hipErrorInvalidValue;
+}
+// beyond 48 KB of dynamic LDS a kernel has to be told
+hipError_t fits(const void* fn, size_t bytes) {
+    if (bytes <= 48 * 1024) return hipSuccess;
+    if (bytes > kFilterMaxLds) return hipErrorInvalidValue;
+    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+}
+// One launch of a tiled kernel: one workgroup per tile, its dynamic LDS allowed first
+template <class K, class... Args>
+hipError_t launch_tiles(K kern, unsigned blocks, unsigned threads, size_t bytes, hipStream_t stream, Args... args) {
+    const hipError_t e = fits(reinterpret_cast<const void*>(kern), bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), bytes, stream, args...);
     return hipGetLastError();
 }
-// The fused kernel's tile: 32 rows x 16 columns (512 threads) for halos up to eight cells, 32 x 32 beyond.  Rows amortise: the
-// row runs of the step window are one per (tile row with halo, interior column), the prefix scans one lane per tile row.
-constexpr int kFusedRows = 32;
-constexpr int kFusedSmallMaxH = 8;
-int fused_tile(int H) { return H <= kFusedSmallMaxH ? 16 : 32; }
+
 }  // namespace
-FilterRoute filter_route(const FilterConsts& fc, const MapGeom& g) {
-    FilterRoute rt{};
-    rt.hN = filter_halo(fc.normalRadius, g.res);
-    rt.hR = filter_halo(fc.roughnessRadius, g.res);
-    rt.h1 = filter_halo(fc.stepFirstRadius, g.res);
-    rt.h2 = filter_halo(fc.stepSecondRadius, g.res);
-    const double reach = std::fmax(std::fabs(g.posX) + g.orgX, std::fabs(g.posY) + g.orgY) + g.res;
-    rt.sN = step_shape(fc.normalRadius, g.res, rt.hN, reach);
-    rt.s1 = step_shape(fc.stepFirstRadius, g.res, rt.h1, reach);
-    rt.s2 = step_shape(fc.stepSecondRadius, g.res, rt.h2, reach);
-    // The moment form takes the lattice as EXACT integers; the published filters (and the oracle) sum the cells' rounded f64
-    // positions.  Near the origin the two agree far inside a float ulp; at a coordinate of `reach` a position carries an error of
-    // ulp(reach) ~ 2e-16 reach against a spacing of res, and the normal follows it: beyond reach / res = 2e5 (2 km at 1 cm, 4e-11
-    // relative) the literal walks run instead (at 3 000 km a handful of cells differed by up to 8 float ulps; tests).
-    const bool latticeExact = reach / g.res < 2.0e5;
-    const bool sameDisc = fc.roughnessRadius == fc.normalRadius;  // the published default chain: both 0.05 m
-    if (sameDisc && rt.hN >= 1 && rt.hN <= kMomentMaxH && rt.sN.rowsOk && latticeExact) rt.tF = fused_tile(rt.hN);
-    // Tile edge of the row-run launches: 32 (1024 threads) when a tile row with its halo is still one wavefront load and the
-    // arrays fit the LDS, else 16.
-    // (32 x 16 where a 32-column tile row with its halo is more than one wavefront load or the runs outgrow the LDS: windows of
-    // 15-24 cells — 0.08 m at 0.5 cm: against 16 x 16 the runs per cell drop from 3.1 to 2.1 and the CU holds eight wavefronts
-    // instead of four)
-    const auto tile_of = [&](int H, int nClasses) {
-        if (g.rows < 64 || g.cols < 64) return 16;
-        if (32 + 2 * H <= 64 && step_lds_bytes(H, nClasses, 32, 32) <= 150 * 1024) return 32;
-        if (16 + 2 * H <= 64 && step_lds_bytes(H, nClasses, 32, 16) <= 150 * 1024) return 24;
-        return 16;
-    };
-    rt.t1 = tile_of(rt.h1, rt.s1.nClasses);
-    rt.t2 = tile_of(rt.h2, rt.s2.nClasses);
-    if (rt.tF) {
-        rt.fusedBytes = fused_moment_bytes(rt.hN, kFusedRows, rt.tF);
-        const size_t stepBytes = step_lds_bytes(rt.h2, rt.s2.nClasses, kFusedRows, rt.tF);
-        if (rt.s2.ok && rt.tF + 2 * rt.h2 <= 64 && stepBytes <= 150 * 1024) {
-            rt.stepFused = 1;
-            if (stepBytes > rt.fusedBytes) rt.fusedBytes = stepBytes;
-        }
-        if (rt.fusedBytes > 150 * 1024) rt.tF = rt.stepFused = 0;
-    }
-    return rt;
-}
-// How far, in cells (Chebyshev), a changed elevation cell can reach into the traversability layer: the widest of the normals'
-// and the roughness disc and the two step windows one behind the other (a step value reads step heights within h2, each of which
-// reads elevations within h1).
-int filter_reach_cells(const FilterConsts& fc, double res) {
-    const int hN = filter_halo(fc.normalRadius, res), hR = filter_halo(fc.roughnessRadius, res);
-    const int h1 = filter_halo(fc.stepFirstRadius, res), h2 = filter_halo(fc.stepSecondRadius, res);
-    return std::max(std::max(hN, hR), h1 + h2);
-}
-// 1: the chain can run without the seven intermediate layers (launch_filters with travOnly).
-bool filters_trav_only_ok(const FilterConsts& fc, const MapGeom& g) {
-    const FilterRoute rt = filter_route(fc, g);
-    return rt.tF != 0 && rt.stepFused != 0;
-}
-// The chain on `stream`: step heights, then normals + slope + roughness + second step window + weighted sum in one launch
-// (filter_fused_kernel); launches of their own for whatever the lattice forms do not cover.  travOnly: only L.stepHeight and
-// L.trav are valid pointers (filters_trav_only_ok must have said yes).
-hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, bool travOnly, hipStream_t stream) {
+
+hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const FilterRoute& rt, const float* d_elev, const FilterLayers& L, bool travOnly,
+                          const FilterRegion* region, hipStream_t stream) {
+    if ((travOnly && !rt.travOnly) || (region && !(rt.regionOk && travOnly))) return hipErrorInvalidValue;
+    if (region && (region->fused.n == 0 || region->fused.nBlocks == 0)) return hipSuccess;  // nothing dirty
     const dim3 grid((g.cols + kFT - 1) / kFT, (g.rows + kFT - 1) / kFT), block(256);
-    const FilterRoute rt = filter_route(fc, g);
-    if (travOnly && !(rt.tF && rt.stepFused)) return hipErrorInvalidValue;
-    const auto fits = [](const void* fn, size_t bytes) -> bool {  // beyond 48 KB of dynamic LDS a kernel has to be told
-        if (bytes <= 48 * 1024) return true;
-        if (bytes > 150 * 1024) return false;
-        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) == hipSuccess;
-    };
     float critDown = static_cast<float>(fc.stepCritical);
     if (static_cast<double>(critDown) > fc.stepCritical) critDown = std::nextafterf(critDown, -HUGE_VALF);
-    // one row-run launch (kSecond false: step heights from the elevation; true: step + weighted sum from the step heights)
-    const auto launch_runs = [&](auto second, int tcode, int H, const StepShape& sp, const float* src, double radius) -> bool {
+    // one row-run launch (kSecond false: step heights from the elevation; true: step + weighted sum from the step heights); over
+    // `region`'s grown tiles the first window's region kernel of the same form: the same phase on the same global tiles
+    const auto launch_runs = [&](auto second, const WindowForm& w, int H, const StepShape& sp, const float* src, double radius) {
         constexpr bool kSecond = decltype(second)::value;
-        const int TR = tcode == 16 ? 16 : 32, TC = tcode == 32 ? 32 : 16;
-        const size_t bytes = step_lds_bytes(H, sp.nClasses, TR, TC);
-        const int tilesX = (g.cols + TC - 1) / TC, nTiles = tilesX * ((g.rows + TR - 1) / TR);
-        const double crit = kSecond ? fc.stepCritical : 0.0;
-        const float cd = kSecond ? critDown : 0.0f;
-        const int nCrit = kSecond ? fc.stepCriticalCells : 1;
-#define FPE_RUNS(TRR, TCC, HS)                                                                                                                          \
-    do {                                                                                                                                                \
-        if (!fits(reinterpret_cast<const void*>(filter_step_runs_kernel<kSecond, TRR, TCC, HS>), bytes)) return false;                                  \
-        hipLaunchKernelGGL((filter_step_runs_kernel<kSecond, TRR, TCC, HS>), dim3(nTiles), dim3(TRR * TCC), bytes, stream, g, src, L, radius, H, sp, crit, cd, \
-                           nCrit, tilesX, nTiles);                                                                                                      \
-        return true;                                                                                                                                    \
-    } while (0)
-        if (!sp.ok) return false;
-        if (tcode == 32) {
-            if (!kSecond && H == 5) FPE_RUNS(32, 32, 5);
-            if (!kSecond && H == 9) FPE_RUNS(32, 32, 9);
-            FPE_RUNS(32, 32, 0);
-        }
-        if (tcode == 24) {
-            if (H == 17) FPE_RUNS(32, 16, 17);  // the published windows (0.08 m) at 0.5 cm
-            FPE_RUNS(32, 16, 0);
-        }
-        FPE_RUNS(16, 16, 0);
-#undef FPE_RUNS
+        return with_runs_form(w, [&](auto TR, auto TC, auto HS) {
+            const int tilesX = (g.cols + TC - 1) / TC, nTiles = tilesX * ((g.rows + TR - 1) / TR);
+            if constexpr (!kSecond)
+                if (region)
+                    return launch_tiles(filter_step_runs_region_kernel<TR, TC, HS>, region->step.nBlocks, TR * TC, w.ldsBytes, stream, g, src, L, radius, H, sp,
+                                        region->step);
+            return launch_tiles(filter_step_runs_kernel<kSecond, TR, TC, HS>, nTiles, TR * TC, w.ldsBytes, stream, g, src, L, radius, H, sp,
+                                kSecond ? fc.stepCritical : 0.0, kSecond ? critDown : 0.0f, kSecond ? fc.stepCriticalCells : 1, tilesX, nTiles);
+        });
     };
     // 1. step heights (first window)
-    if (!launch_runs(std::false_type{}, rt.t1, rt.h1, rt.s1, d_elev, fc.stepFirstRadius))  // (the walking kernel writes L.stepHeight only: fine for travOnly too)
-        hipLaunchKernelGGL(filter_step1_kernel, grid, block, disc_lds_bytes(rt.h1), stream, g, d_elev, L, fc.stepFirstRadius, rt.h1);
-    // 2. normals + slope + roughness [+ second step window + weighted sum]
-    bool stepDone = false;
-    if (rt.tF) {
-        hipError_t e = hipErrorInvalidValue;
-        // the published default chain at 2 cm and 1 cm (normals 0.05 m, second step window 0.08 m): the step window's halo is a
-        // compile-time constant too
-        if (rt.stepFused && rt.hN == 3 && rt.h2 == 5) e = launch_fused_one<3, kFusedRows, 16, 5>(g, fc, d_elev, L, rt, critDown, travOnly ? 1 : 0, stream);
-        else if (rt.stepFused && rt.hN == 6 && rt.h2 == 9) e = launch_fused_one<6, kFusedRows, 16, 9>(g, fc, d_elev, L, rt, critDown, travOnly ? 1 : 0, stream);
-        else switch (rt.hN) {
-#define FPE_FUSED_CASE(HH, TT) case HH: e = launch_fused_one<HH, kFusedRows, TT>(g, fc, d_elev, L, rt, critDown, travOnly ? 1 : 0, stream); break;
-            FPE_FUSED_CASE(1, 16) FPE_FUSED_CASE(2, 16) FPE_FUSED_CASE(3, 16) FPE_FUSED_CASE(4, 16) FPE_FUSED_CASE(5, 16) FPE_FUSED_CASE(6, 16)
-            FPE_FUSED_CASE(7, 16) FPE_FUSED_CASE(8, 16) FPE_FUSED_CASE(9, 32) FPE_FUSED_CASE(10, 32) FPE_FUSED_CASE(11, 32) FPE_FUSED_CASE(12, 32)
-#undef FPE_FUSED_CASE
-            default: break;
-        }
+    if (rt.first.kind == WindowForm::kRuns) {
+        const hipError_t e = launch_runs(std::false_type{}, rt.first, rt.h1, rt.s1, d_elev, fc.stepFirstRadius);
         if (e != hipSuccess) return e;
-        stepDone = rt.stepFused != 0;
+    } else {  // (the walking kernel writes L.stepHeight only: fine for travOnly too)
+        hipLaunchKernelGGL(filter_step1_kernel, grid, block, rt.first.ldsBytes, stream, g, d_elev, L, fc.stepFirstRadius, rt.h1);
+    }
+    // 2. normals + slope + roughness [+ second step window + weighted sum]
+    if (rt.fused.H) {
+        const hipError_t e = with_fused_form(rt.fused, [&](auto H, auto TC, auto HS) {
+            const int tilesX = (g.cols + TC - 1) / TC, nTiles = tilesX * ((g.rows + kFusedRows - 1) / kFusedRows);
+            // THE argument list of the fused kernels (FusedKernArgs); the region kernel takes its rectangle list behind it
+            const auto fused = [&](auto kern, unsigned blocks, auto... rects) {
+                return launch_tiles(kern, blocks, kFusedRows * TC, rt.fusedBytes, stream, g, d_elev, L, fc.normalRadius, fc.slopeCritical, fc.roughnessCritical,
+                                    1.0 / fc.slopeCritical, 1.0 / fc.roughnessCritical, rt.sN, fc.stepSecondRadius, rt.h2, rt.s2, fc.stepCritical, critDown,
+                                    fc.stepCriticalCells, rt.stepFused | (fc.normalRadius <= fc.stepFirstRadius ? 2 : 0), travOnly ? 1 : 0, tilesX, nTiles, rects...);
+            };
+            if (region) return fused(filter_fused_region_kernel<H, kFusedRows, TC, HS>, region->fused.nBlocks, region->fused);
+            return fused(filter_fused_kernel<H, kFusedRows, TC, HS>, nTiles);
+        });
+        if (e != hipSuccess) return e;
     } else {
         const int fuse = fc.roughnessRadius == fc.normalRadius ? 1 : 0;
         hipLaunchKernelGGL(filter_normals_kernel, grid, block, disc_lds_bytes(rt.hN), stream, g, d_elev, L, fc.normalRadius, rt.hN, fc.slopeCritical, fuse,
@@ -1060,134 +920,12 @@ hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float*
             hipLaunchKernelGGL(filter_roughness_kernel, grid, block, disc_lds_bytes(rt.hR), stream, g, d_elev, L, fc.roughnessRadius, rt.hR, fc.roughnessCritical);
     }
     // 3. second step window + weighted sum, when it did not ride in the fused launch
-    if (!stepDone && !launch_runs(std::true_type{}, rt.t2, rt.h2, rt.s2, static_cast<const float*>(L.stepHeight), fc.stepSecondRadius))
-        hipLaunchKernelGGL(filter_step2_kernel, grid, block, disc_lds_bytes(rt.h2), stream, g, L, fc.stepSecondRadius, rt.h2, fc.stepCritical, critDown,
+    if (rt.second.kind == WindowForm::kRuns) {
+        const hipError_t e = launch_runs(std::true_type{}, rt.second, rt.h2, rt.s2, static_cast<const float*>(L.stepHeight), fc.stepSecondRadius);
+        if (e != hipSuccess) return e;
+    } else if (rt.second.kind == WindowForm::kWalk) {
+        hipLaunchKernelGGL(filter_step2_kernel, grid, block, rt.second.ldsBytes, stream, g, L, fc.stepSecondRadius, rt.h2, fc.stepCritical, critDown,
                            fc.stepCriticalCells);
+    }
     return hipGetLastError();
-}
-
-// ---- region launches of the traversability-only chain (fpe_update_elevation*) ---------------------------------------------------
-// Cells of the union of a few rectangles: coordinate compression (at most 2 n cuts per axis).
-int64_t cell_rects_union(const CellRect* r, int n, int rows, int cols) {
-    std::vector<int> ys(2 * static_cast<size_t>(n)), xs(2 * static_cast<size_t>(n));
-    int ny = 0, nx = 0;
-    const auto clip = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
-    for (int k = 0; k < n; ++k) {
-        ys[ny++] = clip(r[k].r0, rows);
-        ys[ny++] = clip(r[k].r1, rows);
-        xs[nx++] = clip(r[k].c0, cols);
-        xs[nx++] = clip(r[k].c1, cols);
-    }
-    std::sort(ys.begin(), ys.end());
-    std::sort(xs.begin(), xs.end());
-    int64_t cells = 0;
-    for (int a = 0; a + 1 < ny; ++a)
-        for (int b = 0; b + 1 < nx; ++b) {
-            if (ys[a] == ys[a + 1] || xs[b] == xs[b + 1]) continue;
-            for (int k = 0; k < n; ++k)
-                if (r[k].r0 <= ys[a] && ys[a + 1] <= r[k].r1 && r[k].c0 <= xs[b] && xs[b + 1] <= r[k].c1) {
-                    cells += static_cast<int64_t>(ys[a + 1] - ys[a]) * (xs[b + 1] - xs[b]);
-                    break;
-                }
-        }
-    return cells;
-}
-namespace {
-// tile code of the row-run launches -> tile rows, columns
-inline void runs_tile(int tcode, int& TR, int& TC) {
-    TR = tcode == 16 ? 16 : 32;
-    TC = tcode == 32 ? 32 : 16;
-}
-}  // namespace
-bool filters_region_plan(const MapGeom& g, const FilterConsts& fc, const CellRect* dirty, int nDirty, FilterRegion* out) {
-    if (nDirty < 0 || nDirty > kRegionMaxRects) return false;
-    const FilterRoute rt = filter_route(fc, g);
-    if (!(rt.tF && rt.stepFused)) return false;  // not the traversability-only route
-    int TR1, TC1;
-    runs_tile(rt.t1, TR1, TC1);
-    // the first window must be the row-run kernel, as in the full chain (launch_filters falls back to the walking kernel otherwise)
-    if (!rt.s1.ok || step_lds_bytes(rt.h1, rt.s1.nClasses, TR1, TC1) > 150 * 1024) return false;
-    const int TRf = kFusedRows, TCf = rt.tF;
-    FilterRegion rg{};
-    CellRect cover[kRegionMaxRects];
-    for (int k = 0; k < nDirty; ++k) {
-        const CellRect& d = dirty[k];
-        if (d.r0 < 0 || d.c0 < 0 || d.r1 > g.rows || d.c1 > g.cols || d.r0 >= d.r1 || d.c0 >= d.c1) return false;
-        const int ty0 = d.r0 / TRf, ty1 = (d.r1 - 1) / TRf + 1, tx0 = d.c0 / TCf, tx1 = (d.c1 - 1) / TCf + 1;
-        rg.fused.r[k] = TileRect{ty0, tx0, ty1 - ty0, tx1 - tx0};
-        rg.fused.nBlocks += (ty1 - ty0) * (tx1 - tx0);
-        cover[k] = CellRect{ty0 * TRf, tx0 * TCf, std::min(ty1 * TRf, g.rows), std::min(tx1 * TCf, g.cols)};
-        // the step heights those tiles read: their cells grown by the second window's halo, clipped to the map
-        const int r0 = std::max(cover[k].r0 - rt.h2, 0), r1 = std::min(cover[k].r1 + rt.h2, g.rows);
-        const int c0 = std::max(cover[k].c0 - rt.h2, 0), c1 = std::min(cover[k].c1 + rt.h2, g.cols);
-        const int sy0 = r0 / TR1, sy1 = (r1 - 1) / TR1 + 1, sx0 = c0 / TC1, sx1 = (c1 - 1) / TC1 + 1;
-        rg.step.r[k] = TileRect{sy0, sx0, sy1 - sy0, sx1 - sx0};
-        rg.step.nBlocks += (sy1 - sy0) * (sx1 - sx0);
-    }
-    rg.fused.n = rg.step.n = nDirty;
-    rg.recomputed = cell_rects_union(cover, nDirty, g.rows, g.cols);
-    *out = rg;
-    return true;
-}
-hipError_t launch_filters_region(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, const FilterRegion& rg, hipStream_t stream) {
-    const FilterRoute rt = filter_route(fc, g);
-    if (!(rt.tF && rt.stepFused && rt.s1.ok)) return hipErrorInvalidValue;
-    if (rg.fused.n == 0 || rg.fused.nBlocks == 0) return hipSuccess;  // nothing dirty
-    const auto fits = [](const void* fn, size_t bytes) -> hipError_t {
-        if (bytes <= 48 * 1024) return hipSuccess;
-        if (bytes > 150 * 1024) return hipErrorInvalidValue;
-        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    };
-    float critDown = static_cast<float>(fc.stepCritical);
-    if (static_cast<double>(critDown) > fc.stepCritical) critDown = std::nextafterf(critDown, -HUGE_VALF);
-    // 1. step heights (first window) over the grown tiles: the instantiation launch_filters picks for this tile code and halo
-    {
-        int TR, TC;
-        runs_tile(rt.t1, TR, TC);
-        const size_t bytes = step_lds_bytes(rt.h1, rt.s1.nClasses, TR, TC);
-        hipError_t e = hipErrorInvalidValue;
-#define FPE_RUNS_REGION(TRR, TCC, HS)                                                                                                              \
-    do {                                                                                                                                           \
-        e = fits(reinterpret_cast<const void*>(filter_step_runs_region_kernel<TRR, TCC, HS>), bytes);                                              \
-        if (e == hipSuccess)                                                                                                                       \
-            hipLaunchKernelGGL((filter_step_runs_region_kernel<TRR, TCC, HS>), dim3(rg.step.nBlocks), dim3(TRR * TCC), bytes, stream, g, d_elev, L, \
-                               fc.stepFirstRadius, rt.h1, rt.s1, rg.step);                                                                         \
-    } while (0)
-        if (rt.t1 == 32) {
-            if (rt.h1 == 5) FPE_RUNS_REGION(32, 32, 5);
-            else if (rt.h1 == 9) FPE_RUNS_REGION(32, 32, 9);
-            else FPE_RUNS_REGION(32, 32, 0);
-        } else if (rt.t1 == 24) {
-            if (rt.h1 == 17) FPE_RUNS_REGION(32, 16, 17);
-            else FPE_RUNS_REGION(32, 16, 0);
-        } else {
-            FPE_RUNS_REGION(16, 16, 0);
-        }
-#undef FPE_RUNS_REGION
-        if (e != hipSuccess) return e;
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    // 2. the fused launch over the dirty tiles
-    const auto fused = [&](auto kern) -> hipError_t {
-        const void* fn = reinterpret_cast<const void*>(kern);
-        const hipError_t e = fits(fn, rt.fusedBytes);
-        if (e != hipSuccess) return e;
-        const int tilesX = (g.cols + rt.tF - 1) / rt.tF, nTiles = tilesX * ((g.rows + kFusedRows - 1) / kFusedRows);
-        hipLaunchKernelGGL(kern, dim3(rg.fused.nBlocks), dim3(kFusedRows * rt.tF), rt.fusedBytes, stream, g, d_elev, L, fc.normalRadius, fc.slopeCritical, fc.roughnessCritical,
-                           1.0 / fc.slopeCritical, 1.0 / fc.roughnessCritical, rt.sN, fc.stepSecondRadius, rt.h2, rt.s2, fc.stepCritical, critDown, fc.stepCriticalCells,
-                           rt.stepFused | (fc.normalRadius <= fc.stepFirstRadius ? 2 : 0), 1, tilesX, nTiles, rg.fused);
-        return hipGetLastError();
-    };
-    if (rt.hN == 3 && rt.h2 == 5) return fused(filter_fused_region_kernel<3, kFusedRows, 16, 5>);
-    if (rt.hN == 6 && rt.h2 == 9) return fused(filter_fused_region_kernel<6, kFusedRows, 16, 9>);
-    switch (rt.hN) {
-#define FPE_FUSED_REGION_CASE(HH, TT) case HH: return fused(filter_fused_region_kernel<HH, kFusedRows, TT, 0>);
-        FPE_FUSED_REGION_CASE(1, 16) FPE_FUSED_REGION_CASE(2, 16) FPE_FUSED_REGION_CASE(3, 16) FPE_FUSED_REGION_CASE(4, 16) FPE_FUSED_REGION_CASE(5, 16)
-        FPE_FUSED_REGION_CASE(6, 16) FPE_FUSED_REGION_CASE(7, 16) FPE_FUSED_REGION_CASE(8, 16) FPE_FUSED_REGION_CASE(9, 32) FPE_FUSED_REGION_CASE(10, 32)
-        FPE_FUSED_REGION_CASE(11, 32) FPE_FUSED_REGION_CASE(12, 32)
-#undef FPE_FUSED_REGION_CASE
-        default: break;
-    }
-    return hipErrorInvalidValue;
 }

@@ -37,11 +37,6 @@ struct FusedLayout {
                                          2 * (TR + TC) * 4 + 16 + 15) & ~static_cast<size_t>(15);
     static constexpr size_t recBytes = static_cast<size_t>(WR) * W1 * 16;  // one record array: a record per (tile row, column prefix)
 };
-__host__ inline size_t fused_moment_bytes(int H, int TR, int TC) {
-    const int WR = TR + 2 * H, W1 = TC + 2 * H + 1;
-    return ((disc_lds_bytes(H, TR, TC) + 15) & ~static_cast<size_t>(15)) + 2 * static_cast<size_t>(WR) * W1 * 16;
-}
-
 // Workgroup -> tile, XCD-aware and bijective (the dispatcher is observed to place block b on XCD b % 8; a wrong guess costs
 // speed only): XCD x takes a contiguous band of the row-major tile order.
 __device__ __forceinline__ void xcd_tile(int tilesX, int nTiles, int& ty, int& tx) {

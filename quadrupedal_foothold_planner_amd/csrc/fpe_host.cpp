@@ -634,6 +634,33 @@ int fpe_map_update_validate(const fpe_map_desc* base, const fpe_map_update* u) {
     return fpe::check_map_update(base->rows, base->cols, u, false, &why);
 }
 
+int fpe_filter_reach_cells(const fpe_filter_params* fp, double resolution) {
+    fpe_filter_params def;
+    if (!fp) {
+        fpe::filter_params_defaults(def);
+        fp = &def;
+    }
+    fpe::FilterConsts fc;
+    if (!(resolution > 0.0) || !std::isfinite(resolution) || fpe::filter_consts(*fp, fc) != FPE_OK) return FPE_E_INVALID_ARG;
+    return fpe::filter_reach_cells(fc, resolution);
+}
+
+int fpe_elevation_update_plan(const fpe_map_desc* base, const fpe_filter_params* fp, const fpe_map_update* u, fpe_elevation_update_info* info,
+                              uint8_t* dirty) {
+    if (!base) return FPE_E_INVALID_ARG;
+    fpe::ElevationUpdatePlan plan;
+    const char* why = nullptr;
+    const int rc = fpe::plan_elevation_update(base->rows, base->cols, base->resolution, fp, u, plan, &why);
+    if (rc != FPE_OK) return rc;
+    if (info) *info = plan.info;
+    if (dirty) {
+        std::memset(dirty, 0, static_cast<size_t>(base->rows) * base->cols);
+        for (const fpe::CellRect& r : plan.dirty)
+            for (int i = r.r0; i < r.r1; ++i) std::memset(dirty + static_cast<size_t>(i) * base->cols + r.c0, 1, static_cast<size_t>(r.c1 - r.c0));
+    }
+    return FPE_OK;
+}
+
 }  // extern "C"
 
 namespace fpe {
@@ -659,6 +686,289 @@ int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevation
         const bool colMajor = p.row_stride == 1 && p.col_stride >= p.n_rows;
         if (!rowMajor && !colMajor) return bad("patch strides are neither row-major nor column-major with a pitch");
     }
+    return FPE_OK;
+}
+
+int check_map_geometry(int rows, int cols, double res, const char** why) {
+    auto bad = [&](const char* msg) {
+        *why = msg;
+        return static_cast<int>(FPE_E_INVALID_ARG);
+    };
+    if (rows <= 0 || cols <= 0 || rows > 32768 || cols > 32768) return bad("map size out of range");
+    if (!(res > 0.0) || !std::isfinite(res)) return bad("bad resolution");
+    return FPE_OK;
+}
+
+// ---- the producer's filter chain: what runs, decided on the host (the kernels: fpe_filters.hpp) ---------------------------------
+void filter_params_defaults(fpe_filter_params& out) {
+    std::memset(&out, 0, sizeof(out));
+    out.normal_radius = 0.05;
+    out.slope_critical = 1.0;
+    out.step_critical = 0.12;
+    out.step_first_radius = 0.08;
+    out.step_second_radius = 0.08;
+    out.step_critical_cells = 4;
+    out.roughness_critical = 0.05;
+    out.roughness_radius = 0.05;
+}
+
+const char* const kBadFilterParams = "filter radii and critical values must be positive and finite";
+int filter_consts(const fpe_filter_params& fp, FilterConsts& fc) {
+    const double radii[4] = {fp.normal_radius, fp.step_first_radius, fp.step_second_radius, fp.roughness_radius};
+    for (double r : radii)
+        if (!(r > 0.0) || !std::isfinite(r)) return FPE_E_INVALID_ARG;
+    if (!(fp.slope_critical > 0.0) || !(fp.step_critical > 0.0) || !(fp.roughness_critical > 0.0) || fp.step_critical_cells <= 0) return FPE_E_INVALID_ARG;
+    fc = FilterConsts{fp.normal_radius, fp.slope_critical, fp.step_critical, fp.step_first_radius, fp.step_second_radius,
+                      fp.step_critical_cells, fp.roughness_critical, fp.roughness_radius};
+    return FPE_OK;
+}
+
+StepShape step_shape(double r, double res, int H, double reach) {
+    StepShape sp{};
+    for (auto& c : sp.rowW) c = -1;
+    sp.ok = 1;
+    sp.rowsOk = 1;
+    const double r2 = r * r, res2 = res * res;
+    // relative margin on squared distances: 1e-7 near the origin; far from it the rounding of the positions themselves
+    // (4 ulp of `reach` on a difference of one resolution, twice that on its square), with a factor of 16 to spare.
+    // Beyond 1e-3 two neighbouring offsets of a row could both be in doubt: the walking kernels take over.
+    const double rel = fmax(1e-7, 16.0 * 8.0 * 2.220446049250313e-16 * reach / res);
+    if (rel > 1e-3) {
+        sp.ok = sp.rowsOk = 0;
+        return sp;
+    }
+    const double margin = rel * r2;
+    for (int o = -H; o <= H; ++o) {
+        int w = -1;
+        for (int k = 0; k <= H; ++k) {
+            const double d2 = (static_cast<double>(o) * o + static_cast<double>(k) * k) * res2;
+            if (d2 < r2 - margin) {
+                w = k;
+            } else if (d2 <= r2 + margin) {  // on the circle: decided per cell
+                sp.edgeRows |= 1ull << (o + H);
+                for (int sgn = (k == 0 ? 1 : -1); sgn <= 1; sgn += 2) {
+                    if (sp.nEdge >= kStepMaxEdge) {
+                        sp.ok = 0;  // (the rows' half-widths below stay valid: the normals kernel tests the next column itself)
+                    } else {
+                        sp.edgeR[sp.nEdge] = static_cast<int8_t>(o);
+                        sp.edgeC[sp.nEdge] = static_cast<int8_t>(sgn * k);
+                        ++sp.nEdge;
+                    }
+                }
+            }
+        }
+        sp.rowW[o + H] = static_cast<int8_t>(w);
+        if (w >= 0) sp.storeMask |= 1u << w;
+        if (w > sp.wMax) sp.wMax = w;
+    }
+    sp.nClasses = __builtin_popcount(sp.storeMask);
+    if (sp.nClasses > kStepMaxClasses) sp.ok = 0;
+    return sp;
+}
+
+int filter_halo(double r, double res) { return static_cast<int>(r / res) + 1; }
+
+bool filters_supported(const FilterConsts& fc, const MapGeom& g) {
+    const double rmax = std::fmax(std::fmax(fc.normalRadius, fc.roughnessRadius), std::fmax(fc.stepFirstRadius, fc.stepSecondRadius));
+    return filter_halo(rmax, g.res) <= kFilterMaxH;
+}
+
+FilterRoute filter_route(const FilterConsts& fc, const MapGeom& g) {
+    FilterRoute rt{};
+    rt.hN = filter_halo(fc.normalRadius, g.res);
+    rt.hR = filter_halo(fc.roughnessRadius, g.res);
+    rt.h1 = filter_halo(fc.stepFirstRadius, g.res);
+    rt.h2 = filter_halo(fc.stepSecondRadius, g.res);
+    const double reach = std::fmax(std::fabs(g.posX) + g.orgX, std::fabs(g.posY) + g.orgY) + g.res;
+    rt.sN = step_shape(fc.normalRadius, g.res, rt.hN, reach);
+    rt.s1 = step_shape(fc.stepFirstRadius, g.res, rt.h1, reach);
+    rt.s2 = step_shape(fc.stepSecondRadius, g.res, rt.h2, reach);
+    // The moment form takes the lattice as EXACT integers; the published filters (and the oracle) sum the cells' rounded f64
+    // positions.  Near the origin the two agree far inside a float ulp; at a coordinate of `reach` a position carries an error of
+    // ulp(reach) ~ 2e-16 reach against a spacing of res, and the normal follows it: beyond reach / res = 2e5 (2 km at 1 cm, 4e-11
+    // relative) the literal walks run instead (at 3 000 km a handful of cells differed by up to 8 float ulps; tests).
+    const bool latticeExact = reach / g.res < 2.0e5;
+    const bool sameDisc = fc.roughnessRadius == fc.normalRadius;  // the published default chain: both 0.05 m
+    if (sameDisc && rt.hN >= 1 && rt.hN <= kMomentMaxH && rt.sN.rowsOk && latticeExact) rt.tF = rt.hN <= kFusedSmallMaxH ? 16 : 32;
+    // Tile edge of the row-run launches: 32 (1024 threads) when a tile row with its halo is still one wavefront load and the
+    // arrays fit the LDS, else 16.
+    // (32 x 16 where a 32-column tile row with its halo is more than one wavefront load or the runs outgrow the LDS: windows of
+    // 15-24 cells — 0.08 m at 0.5 cm: against 16 x 16 the runs per cell drop from 3.1 to 2.1 and the CU holds eight wavefronts
+    // instead of four)
+    // (tile code: 32 = 32 x 32, 24 = 32 rows x 16 columns, 16 = 16 x 16)
+    const auto tile_of = [&](int H, int nClasses) {
+        if (g.rows < 64 || g.cols < 64) return 16;
+        if (32 + 2 * H <= 64 && step_lds_bytes(H, nClasses, 32, 32) <= kFilterMaxLds) return 32;
+        if (16 + 2 * H <= 64 && step_lds_bytes(H, nClasses, 32, 16) <= kFilterMaxLds) return 24;
+        return 16;
+    };
+    if (rt.tF) {
+        rt.fusedBytes = fused_moment_bytes(rt.hN, kFusedRows, rt.tF);
+        const size_t stepBytes = step_lds_bytes(rt.h2, rt.s2.nClasses, kFusedRows, rt.tF);
+        if (rt.s2.ok && rt.tF + 2 * rt.h2 <= 64 && stepBytes <= kFilterMaxLds) {
+            rt.stepFused = 1;
+            if (stepBytes > rt.fusedBytes) rt.fusedBytes = stepBytes;
+        }
+        if (rt.fusedBytes > kFilterMaxLds) rt.tF = rt.stepFused = 0;
+    }
+    // The instantiation of each launch.  A row-run window: its tile, and its halo as a compile-time constant (HS) for the windows
+    // of the published default chain — 0.08 m at 2 cm and 1 cm (5 and 9 cells; the first window's 32 x 32 form only: the second
+    // rides in the fused launch there) and at 0.5 cm (17 cells on 32 x 16); the walking kernel where the shape does not fit the
+    // row-run tables or the runs outgrow the LDS.
+    const auto window = [&](bool second, int H, const StepShape& sp) {
+        const int tcode = tile_of(H, sp.nClasses);
+        WindowForm w{};
+        w.TR = tcode == 16 ? 16 : 32;
+        w.TC = tcode == 32 ? 32 : 16;
+        w.ldsBytes = step_lds_bytes(H, sp.nClasses, w.TR, w.TC);
+        if (tcode == 32 && !second && (H == 5 || H == 9)) w.HS = H;
+        if (tcode == 24 && H == 17) w.HS = H;  // the published windows (0.08 m) at 0.5 cm
+        w.kind = sp.ok && w.ldsBytes <= kFilterMaxLds ? WindowForm::kRuns : WindowForm::kWalk;
+        if (w.kind == WindowForm::kWalk) w = WindowForm{WindowForm::kWalk, 0, 0, 0, disc_lds_bytes(H)};
+        return w;
+    };
+    rt.first = window(false, rt.h1, rt.s1);
+    rt.second = rt.stepFused ? WindowForm{WindowForm::kInFused, 0, 0, 0, 0} : window(true, rt.h2, rt.s2);
+    if (rt.tF) {
+        // the published default chain at 2 cm and 1 cm (normals 0.05 m, second step window 0.08 m): the step window's halo is a
+        // compile-time constant too
+        const bool published = rt.stepFused && ((rt.hN == 3 && rt.h2 == 5) || (rt.hN == 6 && rt.h2 == 9));
+        rt.fused = FusedForm{rt.hN, rt.tF, published ? rt.h2 : 0};
+    }
+    rt.travOnly = rt.tF != 0 && rt.stepFused != 0;
+    rt.regionOk = rt.travOnly && rt.first.kind == WindowForm::kRuns;
+    return rt;
+}
+
+// How far, in cells (Chebyshev), a changed elevation cell can reach into the traversability layer: the widest of the normals'
+// and the roughness disc and the two step windows one behind the other (a step value reads step heights within h2, each of which
+// reads elevations within h1).
+int filter_reach_cells(const FilterConsts& fc, double res) {
+    const int hN = filter_halo(fc.normalRadius, res), hR = filter_halo(fc.roughnessRadius, res);
+    const int h1 = filter_halo(fc.stepFirstRadius, res), h2 = filter_halo(fc.stepSecondRadius, res);
+    return std::max(std::max(hN, hR), h1 + h2);
+}
+
+// ---- region launches of the traversability-only chain (fpe_update_elevation*) ---------------------------------------------------
+// Cells of the union of a few rectangles: coordinate compression (at most 2 n cuts per axis).
+int64_t cell_rects_union(const CellRect* r, int n, int rows, int cols) {
+    std::vector<int> ys(2 * static_cast<size_t>(n)), xs(2 * static_cast<size_t>(n));
+    int ny = 0, nx = 0;
+    const auto clip = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
+    for (int k = 0; k < n; ++k) {
+        ys[ny++] = clip(r[k].r0, rows);
+        ys[ny++] = clip(r[k].r1, rows);
+        xs[nx++] = clip(r[k].c0, cols);
+        xs[nx++] = clip(r[k].c1, cols);
+    }
+    std::sort(ys.begin(), ys.end());
+    std::sort(xs.begin(), xs.end());
+    int64_t cells = 0;
+    for (int a = 0; a + 1 < ny; ++a)
+        for (int b = 0; b + 1 < nx; ++b) {
+            if (ys[a] == ys[a + 1] || xs[b] == xs[b + 1]) continue;
+            for (int k = 0; k < n; ++k)
+                if (r[k].r0 <= ys[a] && ys[a + 1] <= r[k].r1 && r[k].c0 <= xs[b] && xs[b + 1] <= r[k].c1) {
+                    cells += static_cast<int64_t>(ys[a + 1] - ys[a]) * (xs[b + 1] - xs[b]);
+                    break;
+                }
+        }
+    return cells;
+}
+bool filters_region_plan(const MapGeom& g, const FilterRoute& rt, const CellRect* dirty, int nDirty, FilterRegion* out) {
+    if (nDirty < 0 || nDirty > kRegionMaxRects || !rt.regionOk) return false;
+    const int TR1 = rt.first.TR, TC1 = rt.first.TC, TRf = kFusedRows, TCf = rt.fused.TC;
+    FilterRegion rg{};
+    CellRect cover[kRegionMaxRects];
+    for (int k = 0; k < nDirty; ++k) {
+        const CellRect& d = dirty[k];
+        if (d.r0 < 0 || d.c0 < 0 || d.r1 > g.rows || d.c1 > g.cols || d.r0 >= d.r1 || d.c0 >= d.c1) return false;
+        const int ty0 = d.r0 / TRf, ty1 = (d.r1 - 1) / TRf + 1, tx0 = d.c0 / TCf, tx1 = (d.c1 - 1) / TCf + 1;
+        rg.fused.r[k] = TileRect{ty0, tx0, ty1 - ty0, tx1 - tx0};
+        rg.fused.nBlocks += (ty1 - ty0) * (tx1 - tx0);
+        cover[k] = CellRect{ty0 * TRf, tx0 * TCf, std::min(ty1 * TRf, g.rows), std::min(tx1 * TCf, g.cols)};
+        // the step heights those tiles read: their cells grown by the second window's halo, clipped to the map
+        const int r0 = std::max(cover[k].r0 - rt.h2, 0), r1 = std::min(cover[k].r1 + rt.h2, g.rows);
+        const int c0 = std::max(cover[k].c0 - rt.h2, 0), c1 = std::min(cover[k].c1 + rt.h2, g.cols);
+        const int sy0 = r0 / TR1, sy1 = (r1 - 1) / TR1 + 1, sx0 = c0 / TC1, sx1 = (c1 - 1) / TC1 + 1;
+        rg.step.r[k] = TileRect{sy0, sx0, sy1 - sy0, sx1 - sx0};
+        rg.step.nBlocks += (sy1 - sy0) * (sx1 - sx0);
+    }
+    rg.fused.n = rg.step.n = nDirty;
+    rg.recomputed = cell_rects_union(cover, nDirty, g.rows, g.cols);
+    *out = rg;
+    return true;
+}
+
+// The dirty set D of include/fpe.h as rectangles: the patch rectangles and the bands without a source grown by R, and the bands
+// whose window the map edge clips differently before and after the move — whole rows / columns, found as runs of per-line flags.
+void elevation_dirty_rects(int rows, int cols, int R, int sr, int sc, const fpe_map_update* u, std::vector<CellRect>& out) {
+    out.clear();
+    if (std::abs(sr) >= rows || std::abs(sc) >= cols) {  // nothing is carried: every cell is without a source
+        out.push_back(CellRect{0, 0, rows, cols});
+        return;
+    }
+    const auto line_runs = [&](int n, int s, bool rowAxis) {
+        std::vector<uint8_t> flag(static_cast<size_t>(n), 0);
+        for (int i = 0; i < n; ++i) {
+            // C grown by R: some line within R has no source
+            const int lo = std::max(i - R, 0), hi = std::min(i + R, n - 1);
+            const bool noSource = s > 0 ? hi + s >= n : (s < 0 ? lo + s < 0 : false);
+            const bool clipped = s != 0 && (i < R || i >= n - R || i + s < R || i + s >= n - R);  // B
+            flag[static_cast<size_t>(i)] = noSource || clipped;
+        }
+        for (int i = 0; i < n;) {
+            if (!flag[static_cast<size_t>(i)]) {
+                ++i;
+                continue;
+            }
+            int j = i;
+            while (j < n && flag[static_cast<size_t>(j)]) ++j;
+            out.push_back(rowAxis ? CellRect{i, 0, j, cols} : CellRect{0, i, rows, j});
+            i = j;
+        }
+    };
+    line_runs(rows, sr, true);
+    line_runs(cols, sc, false);
+    for (int k = 0; k < u->n_patches; ++k) {
+        const fpe_map_patch& p = u->patch[k];
+        const CellRect r{std::max(p.row0 - R, 0), std::max(p.col0 - R, 0), static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(p.row0) + p.n_rows + R, rows)),
+                         static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(p.col0) + p.n_cols + R, cols))};
+        bool inside = false;  // (a rectangle inside an earlier one adds nothing)
+        for (const CellRect& q : out) inside = inside || (q.r0 <= r.r0 && r.r1 <= q.r1 && q.c0 <= r.c0 && r.c1 <= q.c1);
+        if (!inside) out.push_back(r);
+    }
+}
+
+int plan_elevation_update(int rows, int cols, double res, const fpe_filter_params* fp, const fpe_map_update* u, ElevationUpdatePlan& plan, const char** why) {
+    auto bad = [&](int rc, const char* msg) {
+        *why = msg;
+        return rc;
+    };
+    int rc = check_map_update(rows, cols, u, true, why);
+    if (rc != FPE_OK) return rc;
+    rc = check_map_geometry(rows, cols, res, why);
+    if (rc != FPE_OK) return rc;
+    fpe_filter_params def;
+    if (!fp) {
+        filter_params_defaults(def);
+        fp = &def;
+    }
+    if (filter_consts(*fp, plan.fc) != FPE_OK) return bad(FPE_E_INVALID_ARG, kBadFilterParams);
+    plan.g = make_geom(rows, cols, res, u->position[0], u->position[1]);
+    if (!filters_supported(plan.fc, plan.g)) return bad(FPE_E_UNSUPPORTED, "filter radius spans more cells than the stencil tables hold");
+    plan.rt = filter_route(plan.fc, plan.g);
+    plan.sr = std::max(-rows, std::min(rows, u->shift[0]));  // beyond +-rows nothing is carried either way
+    plan.sc = std::max(-cols, std::min(cols, u->shift[1]));
+    const int R = filter_reach_cells(plan.fc, res);
+    elevation_dirty_rects(rows, cols, R, plan.sr, plan.sc, u, plan.dirty);
+    plan.info.reach_cells = R;
+    plan.info.dirty_cells = cell_rects_union(plan.dirty.data(), static_cast<int>(plan.dirty.size()), rows, cols);
+    const bool carried = std::abs(plan.sr) < rows && std::abs(plan.sc) < cols;
+    const bool region = carried && static_cast<int>(plan.dirty.size()) <= kRegionMaxRects &&
+                        filters_region_plan(plan.g, plan.rt, plan.dirty.data(), static_cast<int>(plan.dirty.size()), &plan.region);
+    plan.info.route = region ? 0 : 1;
+    plan.info.recomputed_cells = region ? plan.region.recomputed : static_cast<int64_t>(rows) * cols;
     return FPE_OK;
 }
 

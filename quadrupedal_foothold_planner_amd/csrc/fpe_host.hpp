@@ -1,10 +1,11 @@
 // fpe_host.hpp — host-side logic of the engine that needs no GPU: parameter typing, derived
-// constants, the spiral rank table, tile sizing and GlobalFootholds message assembly.
+// constants, the spiral rank table, tile sizing, GlobalFootholds message assembly, and what the filter chain and an
+// elevation-driven map update launch (filter_route, plan_elevation_update).
 #pragma once
 #include <cstdint>
 #include <vector>
 
-#include "fpe_device.hpp"
+#include "fpe_launch.hpp"
 
 namespace fpe {
 
@@ -44,6 +45,28 @@ int validate_params(const fpe_params& p);
 // The refusals of fpe_update_map* for a map of rows x cols cells (include/fpe.h): FPE_OK, or FPE_E_INVALID_ARG with *why set.
 // elevationOnly: the patches of fpe_update_elevation* (elevation required, traversability must be null).
 int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevationOnly, const char** why);
+// Size and resolution of a map the engine takes (fpe_upload_map*, fpe_traversability*, fpe_update_elevation*): FPE_OK, or
+// FPE_E_INVALID_ARG with *why set.
+int check_map_geometry(int rows, int cols, double res, const char** why);
+
+// ---- the producer's filter chain (fpe_filters.hpp): its host arithmetic — filter_route and friends are declared in fpe_launch.hpp ----
+void filter_params_defaults(fpe_filter_params& out);
+// fpe_filter_params -> FilterConsts; FPE_E_INVALID_ARG for a radius or critical value that is not positive and finite.
+int filter_consts(const fpe_filter_params& fp, FilterConsts& fc);
+extern const char* const kBadFilterParams;  // the fpe_last_error text of that refusal
+// What fpe_elevation_update_plan and the engine's fpe_update_elevation* share (host arithmetic only): the refusals, the new
+// geometry, the clamped shift, the dirty set D as rectangles, the route and — route 0 — the tile rectangles of the region launches.
+struct ElevationUpdatePlan {
+    fpe_elevation_update_info info;
+    FilterConsts fc;
+    MapGeom g;
+    FilterRoute rt;
+    int sr, sc;
+    std::vector<CellRect> dirty;
+    FilterRegion region;
+};
+void elevation_dirty_rects(int rows, int cols, int R, int sr, int sc, const fpe_map_update* u, std::vector<CellRect>& out);
+int plan_elevation_update(int rows, int cols, double res, const fpe_filter_params* fp, const fpe_map_update* u, ElevationUpdatePlan& plan, const char** why);
 
 
 // Opt track: the file-scope NLopt globals (cpp:28-51, 497-498, 514), the constraint thresholds

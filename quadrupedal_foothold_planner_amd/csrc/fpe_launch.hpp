@@ -88,10 +88,82 @@ hipError_t launch_build_bitmap(const float* d_trav, int rows, int cols, float th
 bool bits_supported(const PlanConsts& pc, const MapGeom& g);
 
 // ---- producer filters (fpe_filters.hpp) ----------------------------------------------------------------------
+// What the host's description of the chain (fpe_host.cpp: filter_route and what follows from it — no GPU call, compiled for the
+// host by the CPU tests) and the kernels share: the table limits, the shape a disc takes on the lattice, the LDS-size formulas the
+// kernels carve their arrays with, and the rectangle lists of the region launches.
+constexpr int kFT = 16;        // tile edge of the disc stencils
+constexpr int kFilterMaxH = 24;  // largest halo the tables are sized for (e.g. r 0.115 m at 0.5 cm)
+constexpr int kStepMaxClasses = 14;
+constexpr int kStepMaxEdge = 24;
+constexpr int kMomentMaxH = 12;
+// The fused kernel's tile: 32 rows x 16 columns (512 threads) for halos up to eight cells, 32 x 32 beyond.  Rows amortise: the
+// row runs of the step window are one per (tile row with halo, interior column), the prefix scans one lane per tile row.
+constexpr int kFusedRows = 32;
+constexpr int kFusedSmallMaxH = 8;
+constexpr size_t kFilterMaxLds = 150 * 1024;  // dynamic LDS a filter kernel is given at most
+// (TR x TC: the workgroup's cells — kFT x kFT for the walking kernels; 16 x 16, 32 x 16 (rows x columns) or 32 x 32 for the
+// row-moment and row-run kernels)
+__host__ __device__ inline size_t disc_lds_bytes(int H, int TR = kFT, int TC = kFT) {
+    const int WR = TR + 2 * H, WC = TC + 2 * H;
+    return static_cast<size_t>(WR) * WC * 4 + static_cast<size_t>(WR + WC) * 8 + static_cast<size_t>(TR + TC) * (2 * H + 1) * 8 + 2 * (TR + TC) * 4 + 16;
+}
+__host__ __device__ inline size_t step_lds_bytes(int H, int nClasses, int TR = kFT, int TC = kFT) {
+    const int WR = TR + 2 * H;
+    return ((disc_lds_bytes(H, TR, TC) + 15) & ~static_cast<size_t>(15)) + static_cast<size_t>(nClasses) * WR * TC * 8 + 128;
+}
+__host__ __device__ inline size_t fused_moment_bytes(int H, int TR, int TC) {
+    const int WR = TR + 2 * H, W1 = TC + 2 * H + 1;
+    return ((disc_lds_bytes(H, TR, TC) + 15) & ~static_cast<size_t>(15)) + 2 * static_cast<size_t>(WR) * W1 * 16;
+}
+// ---- the disc as a lattice SHAPE -------------------------------------------------------------------------------------------
+// On the uniform lattice the members of a cell's disc are the same offsets for every cell — row offset o holds the columns
+// |dc| <= w(o) — except for the few offsets that lie ON the circle ((0, R), (R, 0), (3, 4) R / 5 ...), where
+// CircleIterator::isInside's rounding decides cell by cell.  step_shape sorts the offsets on the host: squared distance
+// against r^2 with a relative margin of 1e-7 (position differences are good to 1e-12).
+struct StepShape {
+    int8_t rowW[2 * kFilterMaxH + 1 + 3];  // per row offset o + H: its robust half-width, -1: no robust member
+    int8_t edgeR[kStepMaxEdge], edgeC[kStepMaxEdge];  // offsets on the circle
+    uint32_t storeMask;                // bit w: some row has half-width w — the run is stored at that width; its class = the number of set bits below w
+    int32_t nEdge, nClasses, wMax;
+    int32_t ok;                        // 0: the shape does not fit the step kernels' tables (the walking kernels run)
+    int32_t rowsOk;                    // 0: not even the rows' half-widths are to be trusted (map too far from the origin)
+    uint64_t edgeRows;                 // bit o + H: row offset o holds an offset on the circle (complete also when the edge list overflowed)
+};
+// reach: the largest |coordinate| of a cell of the map — a position difference carries ~2 ulp of that, which decides how wide
+// the band of offsets is that the per-cell arithmetic must settle.
+StepShape step_shape(double r, double res, int H, double reach);
+int filter_halo(double r, double res);
 bool filters_supported(const FilterConsts& fc, const MapGeom& g);
-bool filters_trav_only_ok(const FilterConsts& fc, const MapGeom& g);
 int filter_reach_cells(const FilterConsts& fc, double res);  // R of fpe_update_elevation* (include/fpe.h)
-hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, bool travOnly, hipStream_t stream);
+
+// THE decision of a chain with these parameters on this geometry, made once per call (filter_route) and handed to everything that
+// plans or launches: the halos and shapes, and the instantiation of each of the chain's launches.
+struct WindowForm {  // a step window's launch
+    enum Kind : int32_t { kWalk = 0, kRuns = 1, kInFused = 2 };  // the walking kernel | filter_step_runs*_kernel<TR, TC, HS> | rides in the fused launch
+    int32_t kind, TR, TC, HS;
+    size_t ldsBytes;
+};
+struct FusedForm {  // filter_fused*_kernel<H, kFusedRows, TC, HS>; H == 0: the separate normals / roughness kernels
+    int32_t H, TC, HS;
+};
+struct FilterRoute {
+    StepShape sN, s1, s2;
+    int hN, hR, h1, h2;
+    int tF;          // tile COLUMNS of the fused kernel (its rows: 32), 0: the moment form does not apply (walking kernels)
+    int stepFused;   // the second step window rides in the fused kernel
+    size_t fusedBytes;
+    WindowForm first, second;
+    FusedForm fused;
+    // What a chain with these parameters can do without the caller's layer buffer: 1 = the two-launch chain that stores
+    // step_height and traversability only (the fused kernel covers normals, slope, roughness and the second step window),
+    // 0 = the intermediate layers have to exist (some filter runs as a launch of its own).
+    int travOnly;
+    // 1: region launches exist for this chain — it is the traversability-only one and its first window is the row-run kernel, as
+    // in the full chain (which falls back to the walking kernel otherwise)
+    int regionOk;
+};
+FilterRoute filter_route(const FilterConsts& fc, const MapGeom& g);
+
 // Region launches of the traversability-only chain (fpe_update_elevation*): the same two kernels' bodies over the tiles of the
 // GLOBAL tile grid that a list of tile rectangles names, passed in the kernel arguments (no host-to-device copy).
 constexpr int kRegionMaxRects = 12;  // 8 patches + 4 bands
@@ -110,14 +182,17 @@ struct FilterRegion {
     TileRects step;       // tiles of the step-height launch: those tiles' cells grown by the second step window's halo
     int64_t recomputed;   // cells of the fused launch's tiles (the union, clipped to the map): what the chain stores
 };
-// Host arithmetic only.  false: no region launches for these parameters and this geometry (not the traversability-only route, a
-// step window the row-run kernel does not take, more than kRegionMaxRects rectangles) — the caller runs the full chain.
-bool filters_region_plan(const MapGeom& g, const FilterConsts& fc, const CellRect* dirty, int nDirty, FilterRegion* out);
+// Host arithmetic only.  false: no region launches for this route (FilterRoute::regionOk) or more than kRegionMaxRects
+// rectangles — the caller runs the full chain.
+bool filters_region_plan(const MapGeom& g, const FilterRoute& rt, const CellRect* dirty, int nDirty, FilterRegion* out);
 // Cells of the union of `n` rectangles (clipped to rows x cols)
 int64_t cell_rects_union(const CellRect* r, int n, int rows, int cols);
-// L.stepHeight and L.trav are the only valid pointers, as for launch_filters with travOnly.
-hipError_t launch_filters_region(const MapGeom& g, const FilterConsts& fc, const float* d_elev, const FilterLayers& L, const FilterRegion& rg,
-                                 hipStream_t stream);
+// The chain on `stream`: step heights, then normals + slope + roughness + second step window + weighted sum in one launch
+// (filter_fused_kernel); launches of their own for whatever the lattice forms do not cover.  travOnly: only L.stepHeight and
+// L.trav are valid pointers (rt.travOnly must say yes).  region: null, or the tiles to run (rt.regionOk; travOnly) — the
+// region kernels of the same forms.
+hipError_t launch_filters(const MapGeom& g, const FilterConsts& fc, const FilterRoute& rt, const float* d_elev, const FilterLayers& L, bool travOnly,
+                          const FilterRegion* region, hipStream_t stream);
 
 // ---- opt track (fpe_opt.hpp) ---------------------------------------------------------------------------------
 hipError_t launch_opt_track(const DevMap& m, const PlanConsts& pc, const OptConsts& oc, const fpe_pose* d_poses, int B, int nCycles,

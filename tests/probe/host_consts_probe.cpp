@@ -21,4 +21,25 @@ void probe_plan_consts(const fpe_params* p, int rows, int cols, double res, doub
     out[5] = c.tileW;
     *cornerEps = c.cornerEps;
 }
+
+// What the filter chain launches for (geometry, filter parameters): filter_route's decision.
+// out[0..3]  halos hN, hR, h1, h2
+// out[4..7]  first window: kind (0 walking kernel, 1 row runs, 2 rides in the fused launch), TR, TC, HS
+// out[8..10] fused: H (0: the separate normals / roughness kernels), TC, HS
+// out[11..14] second window, as the first
+// out[15] trav_only, out[16] region_ok, out[17] stepFused, out[18] nClasses of the first window's shape, out[19] of the second's
+// returns FPE_OK, FPE_E_INVALID_ARG (parameters) or FPE_E_UNSUPPORTED (a radius beyond the tables)
+int probe_filter_route(const fpe_filter_params* fp, int rows, int cols, double res, double px, double py, int* out) {
+    FilterConsts fc;
+    if (filter_consts(*fp, fc) != FPE_OK) return FPE_E_INVALID_ARG;
+    const MapGeom g = make_geom(rows, cols, res, px, py);
+    if (!filters_supported(fc, g)) return FPE_E_UNSUPPORTED;
+    const FilterRoute rt = filter_route(fc, g);
+    const int v[20] = {rt.hN, rt.hR, rt.h1, rt.h2, rt.first.kind, rt.first.TR, rt.first.TC, rt.first.HS, rt.fused.H, rt.fused.TC, rt.fused.HS,
+                       rt.second.kind, rt.second.TR, rt.second.TC, rt.second.HS, rt.travOnly, rt.regionOk, rt.stepFused, rt.s1.nClasses, rt.s2.nClasses};
+    for (int k = 0; k < 20; ++k) out[k] = v[k];
+    return FPE_OK;
+}
+// step_lds_bytes as the kernels carve it
+long probe_step_lds_bytes(int H, int nClasses, int TR, int TC) { return static_cast<long>(step_lds_bytes(H, nClasses, TR, TC)); }
 }

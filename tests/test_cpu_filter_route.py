@@ -1,0 +1,319 @@
+"""CPU tests of the filter chain's kernel selection: csrc/fpe_host.cpp::filter_route compiled for the host through
+tests/probe/host_consts_probe.cpp (g++, no GPU).  The rules are restated here from their statement, independently of the code
+under test — halos, the lattice shape of a disc (its classes of row half-widths and its offsets on the circle), the LDS-size
+formula, the tile code of a window, its compile-time halo, the fused form — and asserted on the cases the GPU tests run
+(tests/test_gpu_elevation_update.py) and on both sides of every threshold.  The forms are also checked against the kernels the
+parent of the selection refactoring launched for the same cases (profiles/filter_chain_kernels.txt, a kernel trace).
+
+That the region kernels exist for every form the route can name is a compile-time fact of csrc/fpe_filters.hpp: the whole-map
+and the region kernel of a form are named in one generic lambda under one list of forms (with_runs_form, with_fused_form).  What
+remains to assert here: every form the route names, on every case, is in that list."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+from quadrupedal_foothold_planner_amd import _capi
+from quadrupedal_foothold_planner_amd.planner import elevation_update_plan
+from tests.test_host_switches import probe  # noqa: F401  (the fixture that builds the probe)
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIMIT = 150 * 1024
+WALK, RUNS, IN_FUSED = 0, 1, 2
+RUNS_FORMS = {(32, 32, 5), (32, 32, 9), (32, 32, 0), (32, 16, 17), (32, 16, 0), (16, 16, 0)}
+FUSED_FORMS = {(3, 16, 5), (6, 16, 9)} | {(h, 16, 0) for h in range(1, 9)} | {(h, 32, 0) for h in range(9, 13)}
+DEFAULTS = dict(normal_radius=0.05, roughness_radius=0.05, step_first_radius=0.08, step_second_radius=0.08)
+
+
+def filter_params(**overrides):
+    fp = _capi.FilterParams(normal_radius=0.05, slope_critical=1.0, step_critical=0.12, step_first_radius=0.08, step_second_radius=0.08,
+                            step_critical_cells=4, roughness_critical=0.05, roughness_radius=0.05)
+    for k, v in overrides.items():
+        setattr(fp, k, v)
+    return fp
+
+
+def route(probe, rows, cols, res, pos=(0.0, 0.0), **radii):  # noqa: F811
+    out = (C.c_int * 20)()
+    probe.probe_filter_route.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    fp = filter_params(**radii)
+    assert probe.probe_filter_route(C.byref(fp), rows, cols, res, float(pos[0]), float(pos[1]), out) == _capi.FPE_OK
+    v = list(out)
+    return dict(halos=tuple(v[0:4]), first=tuple(v[4:8]), fused=tuple(v[8:11]), second=tuple(v[11:15]), trav_only=v[15], region_ok=v[16])
+
+
+# ---- the rules, restated -------------------------------------------------------------------------------------------------------
+def halo(r, res):
+    return int(r / res) + 1
+
+
+def disc_lds_bytes(H, TR=16, TC=16):
+    WR, WC = TR + 2 * H, TC + 2 * H
+    return WR * WC * 4 + (WR + WC) * 8 + (TR + TC) * (2 * H + 1) * 8 + 2 * (TR + TC) * 4 + 16
+
+
+def step_lds_bytes(H, n_classes, TR, TC):
+    return ((disc_lds_bytes(H, TR, TC) + 15) & ~15) + n_classes * (TR + 2 * H) * TC * 8 + 128
+
+
+def fused_moment_bytes(H, TR, TC):
+    return ((disc_lds_bytes(H, TR, TC) + 15) & ~15) + 2 * (TR + 2 * H) * (TC + 2 * H + 1) * 16
+
+
+def reach_of(rows, cols, res, pos):
+    return max(abs(pos[0]) + 0.5 * rows * res, abs(pos[1]) + 0.5 * cols * res) + res
+
+
+def shape(r, res, H, reach):
+    """The disc on the lattice: (classes of robust row half-widths, offsets on the circle, rows trusted, fits the row-run tables)."""
+    rel = max(1e-7, 16.0 * 8.0 * 2.220446049250313e-16 * reach / res)
+    if rel > 1e-3:
+        return 0, 0, False, False
+    r2, margin = r * r, rel * r * r
+    widths, n_edge = set(), 0
+    for o in range(-H, H + 1):
+        w = -1
+        for k in range(H + 1):
+            d2 = (float(o) * o + float(k) * k) * (res * res)
+            if d2 < r2 - margin:
+                w = k
+            elif d2 <= r2 + margin:
+                n_edge += 1 if k == 0 else 2
+        if w >= 0:
+            widths.add(w)
+    return len(widths), n_edge, True, n_edge <= 24 and len(widths) <= 14
+
+
+def tile_code(rows, cols, H, n_classes):
+    if rows < 64 or cols < 64:
+        return (16, 16)
+    if 32 + 2 * H <= 64 and step_lds_bytes(H, n_classes, 32, 32) <= LIMIT:
+        return (32, 32)
+    if 16 + 2 * H <= 64 and step_lds_bytes(H, n_classes, 32, 16) <= LIMIT:
+        return (32, 16)
+    return (16, 16)
+
+
+def window(rows, cols, H, shp, second):
+    n_classes, _, _, ok = shp
+    TR, TC = tile_code(rows, cols, H, n_classes)
+    if not ok or step_lds_bytes(H, n_classes, TR, TC) > LIMIT:
+        return (WALK, 0, 0, 0)
+    hs = 0
+    if (TR, TC) == (32, 32) and not second and H in (5, 9):
+        hs = H
+    if (TR, TC) == (32, 16) and H == 17:
+        hs = 17
+    return (RUNS, TR, TC, hs)
+
+
+def expected(rows, cols, res, pos=(0.0, 0.0), **radii):
+    p = dict(DEFAULTS, **radii)
+    hN, hR, h1, h2 = (halo(p[k], res) for k in ("normal_radius", "roughness_radius", "step_first_radius", "step_second_radius"))
+    reach = reach_of(rows, cols, res, pos)
+    sN, s1, s2 = shape(p["normal_radius"], res, hN, reach), shape(p["step_first_radius"], res, h1, reach), shape(p["step_second_radius"], res, h2, reach)
+    tF = step_fused = 0
+    if p["roughness_radius"] == p["normal_radius"] and 1 <= hN <= 12 and sN[2] and reach / res < 2.0e5:
+        tF = 16 if hN <= 8 else 32
+        fused_bytes = fused_moment_bytes(hN, 32, tF)
+        step_bytes = step_lds_bytes(h2, s2[0], 32, tF)
+        if s2[3] and tF + 2 * h2 <= 64 and step_bytes <= LIMIT:
+            step_fused, fused_bytes = 1, max(fused_bytes, step_bytes)
+        if fused_bytes > LIMIT:
+            tF = step_fused = 0
+    fused = (0, 0, 0)
+    if tF:
+        if step_fused and (hN, h2) in ((3, 5), (6, 9)):
+            fused = (hN, 16, h2)
+        else:
+            fused = (hN, 16 if hN <= 8 else 32, 0)
+    first = window(rows, cols, h1, s1, False)
+    second = (IN_FUSED, 0, 0, 0) if step_fused else window(rows, cols, h2, s2, True)
+    trav_only = int(bool(tF and step_fused))
+    return dict(halos=(hN, hR, h1, h2), first=first, fused=fused, second=second, trav_only=trav_only, region_ok=int(trav_only and first[0] == RUNS))
+
+
+def both(r):
+    return dict(normal_radius=r, roughness_radius=r)
+
+
+# ---- the cases ------------------------------------------------------------------------------------------------------------------
+# label (as in profiles/filter_chain_kernels.txt) -> rows, cols, res, radii, shift, first form, fused form: the GPU test's table,
+# then its SHAPES, then the two fallbacks
+TABLE = {
+    "100x72@0.02 first=0.10": (100, 72, 0.02, dict(step_first_radius=0.10), (5, 3), (32, 32, 0), (3, 16, 5)),
+    "100x72@0.02 second=0.10": (100, 72, 0.02, dict(step_second_radius=0.10), (5, 3), (32, 32, 5), (3, 16, 0)),
+    "100x72@0.02 r=0.01": (100, 72, 0.02, both(0.01), (5, 3), (32, 32, 5), (1, 16, 0)),
+    "160x96@0.01 r=0.075": (160, 96, 0.01, both(0.075), (5, 3), (32, 32, 9), (8, 16, 0)),
+    "160x96@0.01 r=0.085": (160, 96, 0.01, both(0.085), (5, 3), (32, 32, 9), (9, 32, 0)),
+    "160x96@0.01 r=0.115": (160, 96, 0.01, both(0.115), (5, 3), (32, 32, 9), (12, 32, 0)),
+    "128x96@0.005 r=0.03": (128, 96, 0.005, both(0.03), (0, 0), (32, 16, 17), (7, 16, 0)),
+    "128x96@0.005 r=0.03 first=0.10": (128, 96, 0.005, dict(both(0.03), step_first_radius=0.10), (0, 0), (32, 16, 0), (7, 16, 0)),
+    "100x72@0.02": (100, 72, 0.02, {}, (5, 3), (32, 32, 5), (3, 16, 5)),
+    "48x40@0.02": (48, 40, 0.02, {}, (5, 3), (16, 16, 0), (3, 16, 5)),
+    "160x96@0.01": (160, 96, 0.01, {}, (5, 3), (32, 32, 9), (6, 16, 9)),
+    "100x72@0.02 r=0.07": (100, 72, 0.02, both(0.07), (5, 3), (32, 32, 5), (4, 16, 0)),
+}
+FALLBACKS = {
+    "100x72@0.02 roughness=0.07": (100, 72, 0.02, dict(roughness_radius=0.07), (5, 3)),
+    "128x96@0.005": (128, 96, 0.005, {}, (5, 3)),
+}
+
+
+def test_hand_computed_lds_sizes_of_the_issue(probe):  # noqa: F811
+    """0.10 m and 0.08 m at 0.5 cm (halos 21 and 17) on 32 x 16 tiles, and that both outgrow 150 KiB on 32 x 32."""
+    probe.probe_step_lds_bytes.restype = C.c_long
+    for r, H, want in ((0.10, 21, 139456), (0.08, 17, 104128)):
+        n_classes = shape(r, 0.005, H, reach_of(128, 96, 0.005, (0.0, 0.0)))[0]
+        assert step_lds_bytes(H, n_classes, 32, 16) == want == probe.probe_step_lds_bytes(H, n_classes, 32, 16)
+        assert step_lds_bytes(H, n_classes, 32, 32) > LIMIT and probe.probe_step_lds_bytes(H, n_classes, 32, 32) == step_lds_bytes(H, n_classes, 32, 32)
+
+
+@pytest.mark.parametrize("label", list(TABLE))
+def test_table_cases_select_the_stated_forms(probe, label):  # noqa: F811
+    rows, cols, res, radii, shift, first, fused = TABLE[label]
+    got = route(probe, rows, cols, res, **radii)
+    assert got == expected(rows, cols, res, **radii), label
+    assert got["first"] == (RUNS,) + first and got["fused"] == fused and got["second"] == (IN_FUSED, 0, 0, 0), (label, got)
+    assert got["trav_only"] == 1 and got["region_ok"] == 1
+
+
+def threshold_cases():
+    yield "side 63", (63, 100, 0.02, {})
+    yield "side 64", (64, 100, 0.02, {})
+    yield "cols 63", (100, 63, 0.02, {})
+    yield "cols 64", (100, 64, 0.02, {})
+    # H 16 / 17 (32 + 2 H <= 64) and 24 / 25 (16 + 2 H <= 64; 25 is beyond the tables: refused, below) for the tile code
+    yield "h1 16", (128, 96, 0.005, dict(step_first_radius=0.0775))
+    yield "h1 17", (128, 96, 0.005, dict(step_first_radius=0.0825))
+    yield "h1 24", (128, 96, 0.005, dict(step_first_radius=0.1175))
+    yield "h2 16 unfused", (128, 96, 0.005, dict(step_second_radius=0.0775))
+    yield "h2 24 unfused", (128, 96, 0.005, dict(step_second_radius=0.1175))
+    for r in (0.075, 0.085, 0.115, 0.125):  # hN 8 / 9 and 12 / 13 at 1 cm
+        yield f"hN of {r}", (160, 96, 0.01, both(r))
+    # tF + 2 h2 at 64 / 66: tF 32 with h2 16 / 17; with tF 16 the sum reaches 64 at h2 24 and a halo of 25 is refused.  On both
+    # tile widths the LDS limit decides first: tF 16 between h2 20 and 21 (144 016 / 158 400 bytes), tF 32 between 13 and 14
+    # (147 648 / 153 744 bytes) — so the second window does not ride at 64 or at 66
+    yield "tF 32 at 1 cm, h2 13", (160, 96, 0.01, dict(both(0.085), step_second_radius=0.125))
+    yield "tF 32 at 1 cm, h2 14", (160, 96, 0.01, dict(both(0.085), step_second_radius=0.135))
+    yield "tF 16, h2 20", (128, 96, 0.005, dict(both(0.03), step_second_radius=0.0975))
+    yield "tF 16, h2 21", (128, 96, 0.005, dict(both(0.03), step_second_radius=0.1025))
+    yield "tF 16, h2 24", (128, 96, 0.005, dict(both(0.03), step_second_radius=0.1175))
+    yield "tF 32, h2 16", (128, 96, 0.005, dict(step_second_radius=0.0775))
+    yield "tF 32, h2 17", (128, 96, 0.005, {})
+    yield "tF 32 at 1 cm, h2 16", (160, 96, 0.01, dict(both(0.085), step_second_radius=0.155))
+    yield "tF 32 at 1 cm, h2 17", (160, 96, 0.01, dict(both(0.085), step_second_radius=0.165))
+    yield "roughness != normal", (100, 72, 0.02, dict(roughness_radius=0.07))
+    yield "roughness != normal, 1 cm", (160, 96, 0.01, dict(normal_radius=0.05, roughness_radius=0.06))
+
+
+@pytest.mark.parametrize("name,case", list(threshold_cases()), ids=[n for n, _ in threshold_cases()])
+def test_both_sides_of_every_threshold(probe, name, case):  # noqa: F811
+    rows, cols, res, radii = case
+    got, want = route(probe, rows, cols, res, **radii), expected(rows, cols, res, **radii)
+    assert got == want, (name, got, want)
+
+
+def test_the_thresholds_fall_where_the_cases_say(probe):  # noqa: F811
+    """The cases above straddle what they claim to (on the restated rules, which the previous test ties to the code)."""
+    e = expected
+    assert e(63, 100, 0.02)["first"][1:3] == (16, 16) == e(100, 63, 0.02)["first"][1:3] and e(64, 100, 0.02)["first"][1:3] == (32, 32) == e(100, 64, 0.02)["first"][1:3]
+    h16, h17, h24 = (e(128, 96, 0.005, step_first_radius=r) for r in (0.0775, 0.0825, 0.1175))
+    assert (h16["halos"][2], h17["halos"][2], h24["halos"][2]) == (16, 17, 24)
+    assert h16["first"][1:3] in ((32, 32), (32, 16)) and h17["first"] == (RUNS, 32, 16, 17) and h24["first"][1:3] in ((32, 16), (16, 16))
+    assert 32 + 2 * 16 <= 64 < 32 + 2 * 17 and 16 + 2 * 24 <= 64 < 16 + 2 * 25
+    fused = [e(160, 96, 0.01, **both(r))["fused"] for r in (0.075, 0.085, 0.115, 0.125)]
+    assert fused == [(8, 16, 0), (9, 32, 0), (12, 32, 0), (0, 0, 0)]
+    lds = [e(128, 96, 0.005, **dict(both(0.03), step_second_radius=r))["second"] for r in (0.0975, 0.1025, 0.1175)]
+    assert lds == [(IN_FUSED, 0, 0, 0), (RUNS, 16, 16, 0), (RUNS, 16, 16, 0)]  # (the 16 x 16 runs: 32 x 16 outgrows the LDS as well)
+    assert step_lds_bytes(20, 12, 32, 16) == 144016 <= LIMIT < step_lds_bytes(21, 13, 32, 16) == 158400
+    a, b = e(160, 96, 0.01, **dict(both(0.085), step_second_radius=0.155)), e(160, 96, 0.01, **dict(both(0.085), step_second_radius=0.165))
+    assert (a["halos"][3], b["halos"][3]) == (16, 17) and a["fused"][1] == b["fused"][1] == 32  # 32 + 32 = 64, 32 + 34 = 66
+    assert a["second"] == (RUNS, 32, 16, 0) and b["second"] == (RUNS, 32, 16, 17) and a["trav_only"] == b["trav_only"] == 0
+    lds = [e(160, 96, 0.01, **dict(both(0.085), step_second_radius=r))["second"][0] for r in (0.125, 0.135)]
+    assert lds == [IN_FUSED, RUNS] and step_lds_bytes(13, 8, 32, 32) == 147648 <= LIMIT < step_lds_bytes(14, 8, 32, 32) == 153744
+    assert e(100, 72, 0.02, roughness_radius=0.07)["fused"] == (0, 0, 0)
+    # a halo of 25 cells is refused before any route is made
+    out = (C.c_int * 20)()
+    fp = filter_params(step_first_radius=0.1225)
+    assert halo(0.1225, 0.005) == 25 and probe.probe_filter_route(C.byref(fp), 128, 96, C.c_double(0.005), C.c_double(0.0), C.c_double(0.0), out) == _capi.FPE_E_UNSUPPORTED
+
+
+def test_far_from_the_origin_the_moment_form_leaves_at_2e5_cells(probe):  # noqa: F811
+    rows, cols, res = 100, 72, 0.02
+    flip = 2.0e5 * res - 0.5 * rows * res - res  # reach / res = 2e5
+    for px, fused in ((flip * (1 - 1e-6), (3, 16, 5)), (flip * (1 + 1e-6), (0, 0, 0)), (-flip * (1 + 1e-6), (0, 0, 0)), (0.5 * flip, (3, 16, 5))):
+        got = route(probe, rows, cols, res, pos=(px, 0.0))
+        assert got == expected(rows, cols, res, pos=(px, 0.0)) and got["fused"] == fused, (px, got)
+        assert got["trav_only"] == got["region_ok"] == int(fused != (0, 0, 0))
+    got = route(probe, rows, cols, res, pos=(0.0, flip * 1.5))
+    assert got["fused"] == (0, 0, 0) and got["first"] == (RUNS, 32, 32, 5) and got["second"] == (RUNS, 32, 32, 0)
+
+
+def all_cases():
+    for label, c in TABLE.items():
+        yield label, c[:5]
+    for label, c in FALLBACKS.items():
+        yield label, c
+    for name, (rows, cols, res, radii) in threshold_cases():
+        yield name, (rows, cols, res, radii, (5, 3))
+
+
+def test_every_named_form_is_in_the_launch_list_and_the_plan_reports_the_route(probe):  # noqa: F811
+    """Every form a route names is one of the listed instantiations (which exist as whole-map and as region kernels alike), and
+    fpe_elevation_update_plan's route is 0 exactly when region launches exist and the shift carries something."""
+    seen = set()
+    for label, (rows, cols, res, radii, shift) in all_cases():
+        got = route(probe, rows, cols, res, **radii)
+        for w in (got["first"], got["second"]):
+            assert (w[0] == RUNS and w[1:] in RUNS_FORMS) or (w[0] in (WALK, IN_FUSED) and w[1:] == (0, 0, 0)), (label, w)
+        assert got["fused"] == (0, 0, 0) or got["fused"] in FUSED_FORMS, (label, got)
+        assert got["region_ok"] == int(got["trav_only"] and got["first"][0] == RUNS)
+        fp = filter_params(**radii)
+        for sh in (shift, (0, 0), (rows, 0), (-3, cols + 1)):
+            pos = (-sh[0] * res, -sh[1] * res)
+            info, _ = elevation_update_plan(rows, cols, res, sh, pos, [(30, 14, 4, 4)], params=fp, want_mask=False)
+            carried = abs(sh[0]) < rows and abs(sh[1]) < cols
+            assert info["route"] == (0 if got["region_ok"] and carried else 1), (label, sh, info, got)
+            seen.add((got["region_ok"], carried))
+    assert seen == {(0, True), (0, False), (1, True), (1, False)}
+
+
+def kernel_names(got, region):
+    """The filter kernels a chain of these forms launches, in order, as a kernel trace names them."""
+    out = []
+    f = got["first"]
+    out.append(("filter_step_runs_region_kernel<%d,%d,%d>" % f[1:] if region else "filter_step_runs_kernel<false,%d,%d,%d>" % f[1:]) if f[0] == RUNS else "filter_step1_kernel")
+    if got["fused"] != (0, 0, 0):
+        out.append(("filter_fused_region_kernel" if region else "filter_fused_kernel") + "<%d,32,%d,%d>" % got["fused"])
+    else:
+        out.append("filter_normals_kernel")
+        if got["roughness_differs"]:
+            out.append("filter_roughness_kernel")
+    s = got["second"]
+    if s[0] == RUNS:
+        out.append("filter_step_runs_kernel<true,%d,%d,%d>" % s[1:])
+    elif s[0] == WALK:
+        out.append("filter_step2_kernel")
+    return out
+
+
+def test_the_forms_are_the_kernels_the_parent_launched(probe):  # noqa: F811
+    """profiles/filter_chain_kernels.txt: per case the whole-map chain and the update, traced on an MI355X before the selection was
+    unified.  The probe's forms name the same kernels in the same order."""
+    lines = [ln for ln in open(os.path.join(HERE, "..", "profiles", "filter_chain_kernels.txt")).read().splitlines() if ln and not ln.startswith("#")]
+    traced = {}
+    for ln in lines:
+        m = re.fullmatch(r"(.+) \| (chain|update route ([01])): (.*)", ln)
+        traced[(m.group(1), "chain" if m.group(2) == "chain" else "update")] = (m.group(3), m.group(4).split())
+    cases = dict((label, c[:5]) for label, c in TABLE.items())
+    cases.update(FALLBACKS)
+    assert {k[0] for k in traced} == set(cases) and len(traced) == 2 * len(cases)
+    for label, (rows, cols, res, radii, shift) in cases.items():
+        got = route(probe, rows, cols, res, **radii)
+        got["roughness_differs"] = dict(DEFAULTS, **radii)["roughness_radius"] != dict(DEFAULTS, **radii)["normal_radius"]
+        assert traced[(label, "chain")][1] == kernel_names(got, False), label
+        route_id, names = traced[(label, "update")]
+        assert int(route_id) == (0 if got["region_ok"] else 1), label
+        assert names == kernel_names(got, bool(got["region_ok"])), label

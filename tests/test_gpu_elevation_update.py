@@ -378,3 +378,46 @@ def test_walking_cells_in_a_dirty_tile_away_from_the_first(planner):
     check_update(t_new, e_new, info, f, e_star, s, np.ones((rows, cols), bool), d, rows, cols, shift, rects, 10, "walking cells", route=0)
     assert not d[:32, :16].any() and np.array_equal(bits(t_new)[:32, :16], bits(s)[:32, :16])  # tile (0, 0) is not dirty: nothing was stored there
     assert np.isfinite(f[50, 30:42]).all() and np.array_equal(bits(t_new)[50, 20:58], bits(f)[50, 20:58])
+
+
+# ---- 9. every form the chain can select, region launches against the whole-map chain ---------------------------------------------------
+# The smallest maps on which each first-window form (tile, compile-time halo HS) and each fused form <H, 32, TC, HS> is still
+# selected (tests/test_cpu_filter_route.py pins the selection itself); SHAPES above cover <3, 32, 16, 5>, the 16 x 16 tiles,
+# <6, 32, 16, 9> and <4, 32, 16, 0>.  Every case takes route 0 and leaves cells outside the stored set, so a carried cell can show.
+def _both(r):
+    return dict(normal_radius=r, roughness_radius=r)
+
+
+FORM_CASES = {
+    "2cm,first 0.10: 32x32 HS0, <3,32,16,5>": (100, 72, 0.02, dict(step_first_radius=0.10), (5, 3)),
+    "2cm,second 0.10: 32x32 HS5, <3,32,16,0>": (100, 72, 0.02, dict(step_second_radius=0.10), (5, 3)),
+    "2cm,r0.01: 32x32 HS5, <1,32,16,0>": (100, 72, 0.02, _both(0.01), (5, 3)),
+    "1cm,r0.075: 32x32 HS9, <8,32,16,0>": (160, 96, 0.01, _both(0.075), (5, 3)),
+    "1cm,r0.085: 32x32 HS9, <9,32,32,0>": (160, 96, 0.01, _both(0.085), (5, 3)),
+    "1cm,r0.115: 32x32 HS9, <12,32,32,0>": (160, 96, 0.01, _both(0.115), (5, 3)),
+    "0.5cm,r0.03: 32x16 HS17, <7,32,16,0>": (128, 96, 0.005, _both(0.03), (0, 0)),
+    "0.5cm,r0.03,first 0.10: 32x16 HS0, <7,32,16,0>": (128, 96, 0.005, dict(_both(0.03), step_first_radius=0.10), (0, 0)),
+}
+
+
+@pytest.mark.parametrize("case", list(FORM_CASES))
+def test_region_launches_of_every_selected_form_hold_the_whole_map_chain(planner, case):
+    rows, cols, res, radii, shift = FORM_CASES[case]
+    fp = planner.filter_params(**radii)
+    R = er.reach(res, **dict(er.DEFAULT_RADII, **radii))
+    e0, s = er.terrain(rows, cols, 110 + list(FORM_CASES).index(case)), sentinel(rows, cols)
+    pos1 = er.moved_position(POS0, shift, res)
+    carried, s_shift = mu.carried_mask(rows, cols, shift), er.shifted(s, shift)
+    for k, name in enumerate(("tilecorner", "bands") if shift != (0, 0) else ("tilecorner",)):
+        rects = er.patch_rects(name, rows, cols, shift)
+        assert name != "tilecorner" or rects == [(30, 14, 4, 4)]
+        pv = er.patch_values(rects, 130 + k)
+        e_star = er.compose_elevation(e0, shift, pv)
+        d = er.dirty_set(rows, cols, shift, rects, R)
+        f = chain(planner, e_star, res, pos1, fp)
+        planner.gridmapCallback(s, e0, res, position=POS0)
+        info = planner.update_elevation(shift, pos1, pv, params=fp)
+        t_new, e_new = planner.read_map_layers()
+        print(case, name, info)
+        assert 0 < info["recomputed_cells"] < rows * cols, (case, name, info)
+        check_update(t_new, e_new, info, f, e_star, s_shift, carried, d, rows, cols, shift, rects, R, f"{case}, patches {name}", route=0)

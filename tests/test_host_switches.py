@@ -23,7 +23,7 @@ CSRC = os.path.join(HERE, "..", "quadrupedal_foothold_planner_amd", "csrc")
 @pytest.fixture(scope="module")
 def probe():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("fpe_host.cpp", "fpe_host.hpp", "fpe_device.hpp", "fpe_gridmath.hpp")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("fpe_host.cpp", "fpe_host.hpp", "fpe_launch.hpp", "fpe_device.hpp", "fpe_gridmath.hpp")]
     if not os.path.exists(OUT) or max(os.path.getmtime(f) for f in deps) > os.path.getmtime(OUT):
         hip_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(fbuild.HIPCC))), "include")
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
