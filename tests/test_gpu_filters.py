@@ -443,10 +443,12 @@ def test_random_filter_campaign(planner):
 def test_step_windows_with_members_on_the_circle(planner, res, r1, r2, pos):
     """The step filter's windows by row runs (filter_step_runs_kernel): radii that are whole numbers of cells put lattice
     offsets ON the circle — (0, R), (3, 4) R / 5, (5, 12) R / 13, (6, 8) R / 10 — where CircleIterator::isInside's rounding
-    decides cell by cell (more so far from the origin); a window of 23 cells has more distinct half-widths than the stored
-    runs hold and takes the walking kernels.  Thousands of kilometres from the origin the band of offsets in doubt widens
-    with the rounding of the positions (step_shape's `reach`); at 2e9 m nothing is trusted and every kernel walks.  The step
-    heights are a max minus a min: bit-identical or wrong."""
+    decides cell by cell (more so far from the origin); the window of 23 cells (0.23 m at 1 cm, halo 24) has 13 distinct
+    half-widths, which the stored runs hold (14): it takes the 16 x 16 row runs like the others, by the host probe — only
+    radii of 23.0 .. 23.35 cells have 15 and take the walking kernels on a trusted lattice (tests/test_cpu_filter_route.py;
+    run against the oracle by tests/test_gpu_filter_forms.py).  Thousands of kilometres from the origin the band of offsets in
+    doubt widens with the rounding of the positions (step_shape's `reach`); at 2e9 m nothing is trusted and every kernel walks.
+    The step heights are a max minus a min: bit-identical or wrong."""
     rng = np.random.default_rng(int(r1 * 1000) * 7 + int(r2 * 1000))
     rows, cols = 96, 110
     ii, jj = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
