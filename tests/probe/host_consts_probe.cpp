@@ -22,6 +22,20 @@ void probe_plan_consts(const fpe_params* p, int rows, int cols, double res, doub
     *cornerEps = c.cornerEps;
 }
 
+// The constants the open-loop queries and the dense maps select their kernels by (tests/test_cpu_dense_forms.py), with the
+// literal_discs switch of fpe_set_tuning as an argument.
+// out: winH, footRobust, footReach, midCellInside, nFoot, tileW, nHW, spiral_rings(maxSearchRadius)
+void probe_dense_consts(const fpe_params* p, int rows, int cols, double res, double px, double py, float maxSearchRadius, int literalDiscs,
+                        int* out) {
+    const MapGeom g = make_geom(rows, cols, res, px, py);
+    Tuning tuning;
+    tuning.literalDiscs = literalDiscs ? 1 : 0;
+    PlanConsts c;
+    derive_constants(*p, g, maxSearchRadius, tuning, c);
+    const int v[8] = {c.winH, c.footRobust, c.footReach, c.midCellInside, c.nFoot, c.tileW, c.nHW, spiral_rings(maxSearchRadius, res)};
+    for (int k = 0; k < 8; ++k) out[k] = v[k];
+}
+
 // What the filter chain launches for (geometry, filter parameters): filter_route's decision.
 // out[0..3]  halos hN, hR, h1, h2
 // out[4..7]  first window: kind (0 walking kernel, 1 row runs, 2 rides in the fused launch), TR, TC, HS

@@ -125,7 +125,9 @@ def test_large_maps_border_and_random_interior(planner, case):
 
 
 def test_tie_radius_takes_the_literal_walk(planner):
-    """A lattice point on the circle: footRobust = 0, the per-cell literal walk; literal_discs = 1 changes nothing."""
+    """A lattice point on the circle, and the same under literal_discs = 1: both against the oracle and equal.  That this radius has
+    footRobust = 0 and runs footmap_direct_kernel<false> is not asserted here: tests/dense_form_cases.py ("foothold_map rf=0.05
+    res=rf/3 lattice tie") with tests/test_cpu_dense_forms.py pins it."""
     rf = np.float32(0.05)
     res = float(np.float64(rf)) / 3.0  # offset (3, 0) lies on the circle
     params = with_params(planner, footRadius=rf)
@@ -140,8 +142,10 @@ def test_tie_radius_takes_the_literal_walk(planner):
 
 @pytest.mark.parametrize("rf,res", [(0.0, 0.02), (0.045, 0.01), (0.055, 0.01), (0.062, 0.01), (0.07, 0.02), (0.065, 0.01), (0.02, 0.005)])
 def test_foot_radii_and_the_forced_literal_walk(planner, rf, res):
-    """footRadius 0, discs of several cells (proved tables with and without a row-interval form, and a disc too large for
-    the table), each also under literal_discs = 1."""
+    """footRadius 0 and discs of several cells, each also under literal_discs = 1.  Which kernels these radii run (bit planes, the
+    proved table with and without a row-interval form, the literal walk of a disc too large for the table) is not asserted here:
+    the table of tests/dense_form_cases.py has one case per form, pinned by tests/test_cpu_dense_forms.py and compared cell for
+    cell in tests/test_gpu_dense_forms.py."""
     params = with_params(planner, footRadius=np.float32(rf))
     trav, elev = hard_map(120, 101, res, seed=31)
     planner.gridmapCallback(trav, elev, res)
