@@ -1003,6 +1003,108 @@ int fpe_export_layers(fpe_handle h, const fpe_params* params, const int32_t roi[
 int fpe_export_layers_device(fpe_handle h, const fpe_params* params, const int32_t roi[4], const fpe_layer_layout* layout,
                              const fpe_layer_request* d_request /* dst = DEVICE pointers */, void* stream);
 
+/* ---- swing checks: each planned step against the elevation layer ------------------------------------------------------------------
+ * BUILD-DEFINED (the reference reads the elevation layer for getFootholdMeanHeight alone and never looks at the ground between two
+ * successive footholds of a leg).  A SEGMENT runs from A = (ax, ay, az) to B = (bx, by, bz), all doubles, with a radius
+ * r = double(float radius).  On the snapshot current at entry, with MapGeom g (csrc/fpe_gridmath.hpp), a cell (i, j), 0 <= i < rows,
+ * 0 <= j < cols, belongs to the segment's CAPSULE iff, in f64, in exactly this order, without contraction:
+ *     px = cell_pos(g.baseX, g.res, i);  py = cell_pos(g.baseY, g.res, j)
+ *     dx = bx - ax;  dy = by - ay;  L2 = dx*dx + dy*dy
+ *     t  = L2 > 0 ? ((px-ax)*dx + (py-ay)*dy) / L2 : 0;   t = t < 0 ? 0 : (t > 1 ? 1 : t)
+ *     ex = px - (ax + t*dx);  ey = py - (ay + t*dy)
+ *     member  <=>  ex*ex + ey*ey <= r*r
+ * A member with elevation e (f32) is KNOWN iff isfinite(e) && e < 10.0f — the cut of getFootholdMeanHeight (cpp:2533), so the check and
+ * the plan's z agree on which cells count.  A known member has lift_c = double(e) - (az + t*(bz - az)): its height above the straight
+ * line between the two foot heights.  Every quantity of a record is order-free — a count, a maximum, or an argmax with a stated tie
+ * rule — so its value does not depend on how the device splits the cells:
+ *   lift           the maximum lift_c over the known members: what a swing must clear above the chord.  +0.0 when there is none.
+ *                  Maxima are taken in IEEE-754 totalOrder (+0.0 ranks above -0.0; no value is NaN), so the bits are defined too;
+ *   row, col       the known member attaining `lift`; among several the lowest row, then the lowest column.  (-1, -1) when none;
+ *   max_elevation  the maximum e over the known members (totalOrder); 0 when there is none;
+ *   n_cells        members (inside the map);  n_unknown: members that are not known;
+ *   rise           bz - az;
+ *   length_sq      L2 — the square, so that nothing rests on a device square root;
+ *   flags          FPE_SWING_* bits, below.
+ * Radius: query.radius <= 0 means limits.radius, and that, if <= 0, params.footRadius.
+ * Limits: a NULL `limits` is fpe_swing_limits_defaults — the three limits +infinity (no OVER bit is ever set), radius 0.
+ * Refusals.  Every form returns FPE_E_INVALID_ARG for a null argument, n or B < 1, n_cycles outside 1..255, limits.reserved != 0, a NaN
+ * limit, or a default radius (limits.radius, else params.footRadius) that is not finite or above FPE_SWING_MAX_RADIUS.  The host forms
+ * also refuse — nothing is queued or written — a query with reserved != 0, a non-finite coordinate or radius, |coordinate| > 1e6, or a
+ * radius above FPE_SWING_MAX_RADIUS, and fpe_swing_plan what fpe_plan refuses.  The device forms cannot look at the values: such a
+ * segment (reserved is not read) gives a record with flags = FPE_SWING_REFUSED and every other field zero.  FPE_E_UNSUPPORTED on a
+ * map with a resolution below 1e-4 m or a cell farther than 2e6 m from the origin on either axis: the kernels' cell enumeration is
+ * proven a superset of the members for the rest (csrc/fpe_swing.hpp).
+ * The plan-bound segments are what a consumer of the GlobalFootholds message executes.  With the products nominal [B, n, 4], cycle_ok
+ * [B, n] and the start feet [B, 4, 3] (x, y, z of RF, RH, LH, LF), record (b, g, leg) at ((b * n_cycles) + g) * 4 + leg:
+ *   - describes a segment iff cycle_ok[b, g] != 0;  B = nominal[b, g, leg] as (x, y, double(z));
+ *   - A = the same leg's nominal record of the latest g' < g with cycle_ok[b, g'] != 0, or start_feet[b, leg] when there is none;
+ *   - equals, bit for bit, the record the open-loop form returns for the query {A, B, radius 0}, with foot_id = leg and
+ *     gait_cycle_id = g filled in (the open-loop form leaves both 0);
+ *   - of a cycle that did not commit: all zero but foot_id and gait_cycle_id.
+ * The start feet default to the plan's `stance` product.  stance carries the POSE's z, not a terrain height (RF/RH/LH/LF_initialPosition_,
+ * cpp:350-378): the first swing's rise and lift are then relative to the body height given in the pose.  A caller that knows where the feet
+ * stand — a resumed plan, heights read from the map — hands in feet of its own.
+ * The per-pose summary covers the records of the pose that describe a segment, whatever else their flags say: max_lift (totalOrder),
+ * max_abs_rise = max fabs(rise), max_length_sq, each 0 when the pose has no segment; n_segments; n_over: segments with any OVER bit;
+ * n_unknown: segments with UNKNOWN, EMPTY or OFF_MAP; first_over_cycle: the lowest g of a segment with an OVER bit, 255 when none.
+ * No atomics anywhere: every byte is a function of the inputs alone.  Out of scope: a swing term in fpe_plan_rank* / fpe_plan_beam*,
+ * fpe_multi_*, the service calls, the opt and centroid tracks' footholds, any trajectory shape beyond the lift above the chord. */
+#define FPE_SWING_SEGMENT     1u   /* the record describes a segment */
+#define FPE_SWING_OFF_MAP     2u   /* A or B fails checkIfPositionWithinMap (within_axis on either axis) */
+#define FPE_SWING_EMPTY       4u   /* n_cells == 0 */
+#define FPE_SWING_UNKNOWN     8u   /* n_unknown > 0 */
+#define FPE_SWING_OVER_LIFT   16u  /* lift > limits.max_lift */
+#define FPE_SWING_OVER_RISE   32u  /* fabs(rise) > limits.max_rise */
+#define FPE_SWING_OVER_LENGTH 64u  /* length_sq > limits.max_length * limits.max_length */
+#define FPE_SWING_REFUSED     128u /* device forms: a segment the host forms refuse; every other field zero, SEGMENT not set */
+#define FPE_SWING_MAX_RADIUS  0.5f
+typedef struct fpe_swing_query {      /* 56 bytes */
+    double  a[3], b[3];    /* A and B: x, y, z */
+    float   radius;        /* <= 0: limits.radius, else params.footRadius */
+    int32_t reserved;      /* 0 */
+} fpe_swing_query;
+typedef struct fpe_swing_limits {     /* 32 bytes */
+    double  max_lift, max_rise, max_length;   /* not NaN; +infinity: no limit */
+    float   radius;        /* the capsule radius of queries that give none; <= 0: params.footRadius */
+    int32_t reserved;      /* 0 */
+} fpe_swing_limits;
+typedef struct fpe_swing_record {     /* 48 bytes */
+    double  lift, rise, length_sq;
+    float   max_elevation;
+    int32_t n_cells, n_unknown;
+    int32_t row, col;
+    uint8_t flags;         /* FPE_SWING_* */
+    uint8_t foot_id;       /* plan-bound: 0 RF, 1 RH, 2 LH, 3 LF; open-loop: 0 */
+    uint8_t gait_cycle_id; /* plan-bound: g; open-loop: 0 */
+    uint8_t pad;
+} fpe_swing_record;
+typedef struct fpe_swing_summary {    /* 40 bytes; element b belongs to pose b */
+    double  max_lift, max_abs_rise, max_length_sq;
+    int32_t n_segments, n_over, n_unknown;
+    uint8_t first_over_cycle;  /* 255: none */
+    uint8_t pad[3];
+} fpe_swing_summary;
+typedef struct fpe_swing_out {        /* 16 bytes; either pointer may be NULL */
+    fpe_swing_record*  records;  /* [B * n_cycles * 4] */
+    fpe_swing_summary* summary;  /* [B] */
+} fpe_swing_out;
+int fpe_swing_limits_defaults(fpe_swing_limits* out);
+/* Open-loop: n arbitrary segments.  Host arrays, synchronous / device arrays, asynchronous on `stream`. */
+int fpe_swing_segments(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_swing_query* queries, int32_t n,
+                       fpe_swing_record* out);
+int fpe_swing_segments_device(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_swing_query* d_queries,
+                              int32_t n, fpe_swing_record* d_out, void* stream);
+/* Plan-bound, device arrays: reads d_products->nominal and ->cycle_ok (both required) as a plan call on `stream` left them, and
+ * ->stance when d_start_feet (B * 4 * 3 doubles) is NULL; `d_products` and `d_out` themselves are host structs of device pointers.
+ * Asynchronous on `stream`, behind whatever filled the products there. */
+int fpe_swing_plan_device(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_plan_out* d_products,
+                          const double* d_start_feet, int32_t B, int32_t n_cycles, const fpe_swing_out* d_out, void* stream);
+/* Plan and check in one call, host arrays, synchronous: plans exactly as fpe_plan (strides NULL) or fpe_plan_strides would, checks the
+ * plan on the same stream with no host synchronisation in between, on ONE snapshot, and returns the requested products (NULL: none)
+ * and the swing outputs.  The start feet are the plan's stance. */
+int fpe_swing_plan(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_pose* poses,
+                   const fpe_stride* strides, int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_swing_out* out);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

@@ -287,6 +287,37 @@ class ElevationUpdateInfo(C.Structure):
     _fields_ = [("reach_cells", C.c_int32), ("route", C.c_int32), ("dirty_cells", C.c_int64), ("recomputed_cells", C.c_int64)]
 
 
+# FPE_SWING_* flag bits of fpe_swing_record.flags and the radius bound of a swing segment
+SWING_SEGMENT, SWING_OFF_MAP, SWING_EMPTY, SWING_UNKNOWN, SWING_OVER_LIFT, SWING_OVER_RISE, SWING_OVER_LENGTH, SWING_REFUSED = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+SWING_MAX_RADIUS = np.float32(0.5)
+# fpe_swing_query: one segment A -> B with its capsule radius (<= 0: the limits' radius, else params.footRadius)
+SWING_QUERY_DTYPE = np.dtype([("a", "<f8", (3,)), ("b", "<f8", (3,)), ("radius", "<f4"), ("reserved", "<i4")], align=True)
+# fpe_swing_record: what a segment's capsule holds of the elevation layer; fpe_swing_summary: one pose's records reduced
+SWING_RECORD_DTYPE = np.dtype(
+    [("lift", "<f8"), ("rise", "<f8"), ("length_sq", "<f8"), ("max_elevation", "<f4"), ("n_cells", "<i4"), ("n_unknown", "<i4"),
+     ("row", "<i4"), ("col", "<i4"), ("flags", "u1"), ("foot_id", "u1"), ("gait_cycle_id", "u1"), ("pad", "u1")],
+    align=True,
+)
+SWING_SUMMARY_DTYPE = np.dtype(
+    [("max_lift", "<f8"), ("max_abs_rise", "<f8"), ("max_length_sq", "<f8"), ("n_segments", "<i4"), ("n_over", "<i4"),
+     ("n_unknown", "<i4"), ("first_over_cycle", "u1"), ("pad", "u1", (3,))],
+    align=True,
+)
+assert (SWING_QUERY_DTYPE.itemsize, SWING_RECORD_DTYPE.itemsize, SWING_SUMMARY_DTYPE.itemsize) == (56, 48, 40)
+
+
+class SwingLimits(C.Structure):
+    """fpe_swing_limits: the three limits behind the OVER bits (+infinity: none) and the default capsule radius."""
+    _fields_ = [("max_lift", C.c_double), ("max_rise", C.c_double), ("max_length", C.c_double), ("radius", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class SwingOut(C.Structure):
+    """fpe_swing_out: outputs of a plan-bound swing check (either pointer may be NULL)."""
+    _fields_ = [("records", C.c_void_p), ("summary", C.c_void_p)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -300,7 +331,8 @@ STRUCTS = {
     "fpe_pose_summary": PoseSummary, "fpe_rank_params": RankParams, "fpe_rank_out": RankOut, "fpe_layer_layout": LayerLayout,
     "fpe_layer_request": LayerRequest, "fpe_stride": STRIDE_DTYPE, "fpe_plan_state": PLAN_STATE_DTYPE,
     "fpe_beam_params": BeamParams, "fpe_beam_out": BeamOut, "fpe_map_patch": MapPatch, "fpe_map_update": MapUpdate,
-    "fpe_elevation_update_info": ElevationUpdateInfo,
+    "fpe_elevation_update_info": ElevationUpdateInfo, "fpe_swing_query": SWING_QUERY_DTYPE, "fpe_swing_limits": SwingLimits,
+    "fpe_swing_record": SWING_RECORD_DTYPE, "fpe_swing_summary": SWING_SUMMARY_DTYPE, "fpe_swing_out": SwingOut,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -387,6 +419,11 @@ PROTOTYPES = {
     "fpe_beam_params_defaults": (cint, [P(BeamParams)]),
     "fpe_plan_beam": (cint, [vp, vp, P(BeamParams), vp, vp, i32, vp, i32, P(BeamOut)]),
     "fpe_plan_beam_device": (cint, [vp, vp, P(BeamParams), vp, vp, i32, vp, i32, P(BeamOut), vp]),
+    "fpe_swing_limits_defaults": (cint, [P(SwingLimits)]),
+    "fpe_swing_segments": (cint, [vp, vp, P(SwingLimits), vp, i32, vp]),
+    "fpe_swing_segments_device": (cint, [vp, vp, P(SwingLimits), vp, i32, vp, vp]),
+    "fpe_swing_plan_device": (cint, [vp, vp, P(SwingLimits), P(PlanOut), vp, i32, i32, P(SwingOut), vp]),
+    "fpe_swing_plan": (cint, [vp, vp, P(SwingLimits), vp, vp, i32, i32, P(PlanOut), P(SwingOut)]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),
@@ -477,6 +514,17 @@ def beam_params_defaults(**overrides):
             raise ValueError(f"unknown beam parameter {k!r}")
         setattr(bp, k, v)
     return bp
+
+
+def swing_limits_defaults(**overrides):
+    """fpe_swing_limits_defaults, with any field replaced by a keyword."""
+    sl = SwingLimits()
+    assert lib().fpe_swing_limits_defaults(C.byref(sl)) == FPE_OK
+    for k, v in overrides.items():
+        if k not in dict(SwingLimits._fields_):
+            raise ValueError(f"unknown swing limit {k!r}")
+        setattr(sl, k, v)
+    return sl
 
 
 def spiral_offsets(n_rings):

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <deque>
+#include <limits>
 #include <thread>
 #include <cstdio>
 #include <cstdlib>
@@ -880,9 +881,10 @@ hipError_t run_export_layers(fpe_engine* h, const ExportPlan& xp, const fpe_laye
 }
 
 // The host form of an open-loop query call behind its per-query checks: n queries up, `launch(cp, d_queries, d_out, stream)`,
-// n records back, both through the context's arenas.
+// n records back, both through the context's arenas.  check (may be null): a refusal that needs the call's snapshot, ahead of any copy.
 template <class Query, class Record, class Launch>
-int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, const Query* queries, int32_t n, Record* out, Launch launch) {
+int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, const Query* queries, int32_t n, Record* out, Launch launch,
+                     int (*check)(const CallPlan&) = nullptr) {
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
     const size_t nQ = static_cast<size_t>(n) * sizeof(Query), nO = static_cast<size_t>(n) * sizeof(Record);
     const size_t szQ = align256(nQ);
@@ -892,6 +894,7 @@ int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, c
     FPE_HIP(cx.reserve(szQ + align256(nO)));
     cx.inFlight = true;
     int rc = prepare_call(h, params, maxRadius, hc.cp, cx.stream, false);
+    if (rc == FPE_OK && check) rc = check(hc.cp);
     if (rc != FPE_OK) return rc;
     std::memcpy(cx.pinned, queries, nQ);
     FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, nQ, hipMemcpyHostToDevice, cx.stream));
@@ -2757,6 +2760,176 @@ int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params*
         for (int b = 0; b < B; ++b) std::memcpy(static_cast<unsigned char*>(seg.dst) + b * all, src + b * live, live);
     }
     return FPE_OK;
+}
+
+// ---- swing checks (fpe_swing_*; kernels: fpe_swing.hpp) ------------------------------------------------------------------------
+int fpe_swing_limits_defaults(fpe_swing_limits* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->max_lift = out->max_rise = out->max_length = std::numeric_limits<double>::infinity();
+    return FPE_OK;
+}
+
+namespace {
+// The limits of a swing call as the kernels take them (limits NULL: the defaults), checked; the default radius resolved.
+int swing_consts(const fpe_params* params, const fpe_swing_limits* limits, fpe::SwingConsts& sc) {
+    if (!params) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    fpe_swing_limits def;
+    if (!limits) {
+        fpe_swing_limits_defaults(&def);
+        limits = &def;
+    }
+    if (limits->reserved != 0) return fail(FPE_E_INVALID_ARG, "fpe_swing_limits.reserved must be 0");
+    if (std::isnan(limits->max_lift) || std::isnan(limits->max_rise) || std::isnan(limits->max_length))
+        return fail(FPE_E_INVALID_ARG, "swing limits must not be NaN");
+    const float r = limits->radius > 0.0f ? limits->radius : params->footRadius;
+    if (!std::isfinite(limits->radius) || !std::isfinite(r) || r > FPE_SWING_MAX_RADIUS)
+        return fail(FPE_E_INVALID_ARG, "swing radius must be finite and at most FPE_SWING_MAX_RADIUS");
+    sc = fpe::SwingConsts{limits->max_lift, limits->max_rise, limits->max_length * limits->max_length, r, 0};
+    return FPE_OK;
+}
+int check_swing_map(const CallPlan& cp) {
+    if (!fpe::swing_map_supported(cp.snap->g))
+        return fail(FPE_E_UNSUPPORTED, "swing checks need a resolution of at least 1e-4 m and a map within 2e6 m of the origin");
+    return FPE_OK;
+}
+// One segment end or start foot of a host-form call
+bool swing_point_ok(const double* p) {
+    for (int k = 0; k < 3; ++k)
+        if (!(std::fabs(p[k]) <= 1e6)) return false;  // (NaN and infinities fail the comparison)
+    return true;
+}
+int check_swing_shape(int32_t B, int32_t n_cycles) {
+    if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
+    if (static_cast<int64_t>(B) * n_cycles * 4 > (1 << 30)) return fail(FPE_E_INVALID_ARG, "B * n_cycles * 4 must not exceed 2^30");
+    return FPE_OK;
+}
+}  // namespace
+
+int fpe_swing_segments_device(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_swing_query* d_queries,
+                              int32_t n, fpe_swing_record* d_out, void* stream) {
+    if (!d_queries || !d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    fpe::SwingConsts sc;
+    int rc = swing_consts(params, limits, sc);
+    if (rc != FPE_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    rc = prepare_call(h, params, 0.0f, cp, st, false);
+    if (rc == FPE_OK) rc = check_swing_map(cp);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    FPE_HIP(fpe::launch_swing_segments(dev_map(*cp.snap), sc, d_queries, n, d_out, st));
+    return FPE_OK;
+}
+
+int fpe_swing_segments(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_swing_query* queries, int32_t n,
+                       fpe_swing_record* out) {
+    if (!queries || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    fpe::SwingConsts sc;
+    const int rc = swing_consts(params, limits, sc);
+    if (rc != FPE_OK) return rc;
+    for (int k = 0; k < n; ++k) {
+        if (queries[k].reserved != 0) return fail(FPE_E_INVALID_ARG, "fpe_swing_query.reserved must be 0");
+        if (!swing_point_ok(queries[k].a) || !swing_point_ok(queries[k].b)) return fail(FPE_E_INVALID_ARG, "non-finite or over-bound segment");
+        if (!std::isfinite(queries[k].radius) || queries[k].radius > FPE_SWING_MAX_RADIUS) return fail(FPE_E_INVALID_ARG, "bad segment radius");
+    }
+    return query_round_trip(h, params, 0.0f, queries, n, out,
+                            [&](const CallPlan& cp, const fpe_swing_query* d_q, fpe_swing_record* d_out, hipStream_t s) {
+                                return fpe::launch_swing_segments(dev_map(*cp.snap), sc, d_q, n, d_out, s);
+                            },
+                            check_swing_map);
+}
+
+int fpe_swing_plan_device(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_plan_out* d_products,
+                          const double* d_start_feet, int32_t B, int32_t n_cycles, const fpe_swing_out* d_out, void* stream) {
+    if (!d_products || !d_out || !d_products->nominal || !d_products->cycle_ok) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!d_start_feet && !d_products->stance) return fail(FPE_E_INVALID_ARG, "neither start feet nor the stance product given");
+    if (!d_out->records && !d_out->summary) return fail(FPE_E_INVALID_ARG, "no swing output requested");
+    fpe::SwingConsts sc;
+    int rc = check_swing_shape(B, n_cycles);
+    if (rc == FPE_OK) rc = swing_consts(params, limits, sc);
+    if (rc != FPE_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    rc = prepare_call(h, params, 0.0f, cp, st, false);
+    if (rc == FPE_OK) rc = check_swing_map(cp);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    const double* feet = d_start_feet ? d_start_feet : d_products->stance;
+    if (d_out->records) {
+        FPE_HIP(fpe::launch_swing_plan(dev_map(*cp.snap), sc, d_products->nominal, d_products->cycle_ok, feet, B, n_cycles, d_out->records,
+                                       d_out->summary, st));
+        return FPE_OK;
+    }
+    // the summary alone: its records live in stream-ordered scratch
+    return with_stream_scratch(static_cast<size_t>(B) * n_cycles * 4 * sizeof(fpe_swing_record), st, [&](unsigned char* scratch) {
+        FPE_HIP(fpe::launch_swing_plan(dev_map(*cp.snap), sc, d_products->nominal, d_products->cycle_ok, feet, B, n_cycles,
+                                       reinterpret_cast<fpe_swing_record*>(scratch), d_out->summary, st));
+        return static_cast<int>(FPE_OK);
+    });
+}
+
+namespace {
+// Where everything a plan-and-check call touches on the device lives: the plan's products — the requested ones in the output block,
+// what the check reads besides (nominal, cycle_ok, stance) in scratch, null for the rest — then the records (scratch when only the
+// summary is wanted) and the summary.
+struct SwingLayout {
+    int32_t B, n;
+    fpe_plan_out plan;
+    fpe_swing_record* records;
+    fpe_swing_summary* summary;
+};
+static_assert(kPlanProducts + 2 <= kProducts + 1, "SegList holds a plan-and-check call's outputs");
+void swing_layout(SwingLayout& L, ArenaCursor& A, const fpe_plan_out* want, const fpe_swing_out& so) {
+    const bool reads[kPlanProducts] = {true, false, false, true, true, false, false, false};  // swing_segments_kernel<true>'s inputs
+    const size_t B = static_cast<size_t>(L.B), n = static_cast<size_t>(L.n);
+    void* const* wanted = want ? slots(*want) : nullptr;
+    for (int k = 0; k < kPlanProducts; ++k)
+        slots(L.plan)[k] = (wanted && wanted[k]) ? A.out(wanted[k], product_bytes(k, B, n)) : (reads[k] ? A.take(product_bytes(k, B, n)) : nullptr);
+    const size_t szRec = B * n * 4 * sizeof(fpe_swing_record);
+    L.records = static_cast<fpe_swing_record*>(so.records ? A.out(so.records, szRec) : A.take(szRec));
+    L.summary = static_cast<fpe_swing_summary*>(so.summary ? A.out(so.summary, B * sizeof(fpe_swing_summary)) : nullptr);
+}
+}  // namespace
+
+int fpe_swing_plan(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_pose* poses, const fpe_stride* strides,
+                   int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_swing_out* out) {
+    if (!h || !poses || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!out->records && !out->summary) return fail(FPE_E_INVALID_ARG, "no swing output requested");
+    fpe::SwingConsts sc;
+    int rc = check_swing_shape(B, n_cycles);
+    if (rc == FPE_OK) rc = swing_consts(params, limits, sc);
+    if (rc != FPE_OK) return rc;
+    float maxRadius = 0.0f;
+    rc = check_host_poses(poses, B, maxRadius);
+    if (rc == FPE_OK) rc = check_host_strides(strides, B);
+    if (rc != FPE_OK) return rc;
+    SwingLayout L{};
+    L.B = B, L.n = n_cycles;
+    ArenaCursor sizes;
+    swing_layout(L, sizes, products, *out);
+    // both arenas: [poses (| strides) | outputs | scratch (device arena only)]; the inputs are read from the pinned arena, as in fpe_plan
+    const size_t oStrides = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    const size_t szIn = oStrides + (strides ? align256(static_cast<size_t>(B) * sizeof(fpe_stride)) : 0);
+    HostCall hc(h);
+    CallCtx& cx = hc.cx;
+    unsigned char* in = nullptr;
+    rc = open_batch_call(h, hc, params, maxRadius, szIn + sizes.outBytes + sizes.scratchBytes, products && products->selected_packed,
+                         strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain, in);
+    if (rc == FPE_OK) rc = check_swing_map(hc.cp);
+    if (rc != FPE_OK) return rc;
+    stage_batch_inputs(cx.pinned, oStrides, poses, strides, B);
+    ArenaCursor A{cx.dev + szIn + sizes.outBytes, cx.dev + szIn, szIn};
+    swing_layout(L, A, products, *out);
+    // the plan through the plan runner, then the check behind it on the same stream and the same snapshot
+    rc = launch_plan(h, hc.cp, reinterpret_cast<const fpe_pose*>(in), B, n_cycles, L.plan, cx.stream,
+                     {strides ? reinterpret_cast<const fpe_stride*>(in + oStrides) : nullptr});
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(fpe::launch_swing_plan(dev_map(*hc.cp.snap), sc, L.plan.nominal, L.plan.cycle_ok, L.plan.stance, B, n_cycles, L.records, L.summary,
+                                   cx.stream));
+    return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
 }
 
 int fpe_last_service_gate(fpe_handle h, fpe_service_gate* out) {

@@ -2272,6 +2272,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_beam.hpp"
 // ---- part ten: incremental map updates (fpe_update_map*) ----------------------------------------------------------
 #include "fpe_mapupdate.hpp"
+// ---- part eleven: swing checks (fpe_swing_*) ------------------------------------------------------------------------
+#include "fpe_swing.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)

@@ -355,4 +355,20 @@ hipError_t launch_beam_prune(const BeamConsts& bc, const BeamShape& sh, int s, c
 // Behind the last segment: every live slot's path, products, state, score and penalty, and n_live
 hipError_t launch_beam_trace(const BeamShape& sh, const BeamScratch& sc, const fpe_beam_out& d_out, hipStream_t stream);
 
+// ---- swing checks (fpe_swing.hpp) ----------------------------------------------------------------------------
+// The limits of a call as the kernels take them, by value, checked by the host (no NaN): max_length already squared, and the radius
+// of a segment that names none already resolved (limits.radius, else params.footRadius; finite, <= FPE_SWING_MAX_RADIUS).
+struct SwingConsts {
+    double maxLift, maxRise, maxLengthSq;
+    float defaultRadius;
+    int32_t pad;
+};
+bool swing_map_supported(const MapGeom& g);  // the maps the kernels' cell enumeration is proven on (fpe_swing.hpp)
+hipError_t launch_swing_segments(const DevMap& m, const SwingConsts& sc, const fpe_swing_query* d_q, int n, fpe_swing_record* d_out,
+                                 hipStream_t stream);
+// The segments a plan's products imply: B * nCycles * 4 records (required) and, where d_summary is given, one summary per pose
+hipError_t launch_swing_plan(const DevMap& m, const SwingConsts& sc, const fpe_foothold* d_nominal, const uint8_t* d_cycleOk,
+                             const double* d_startFeet, int B, int nCycles, fpe_swing_record* d_records, fpe_swing_summary* d_summary,
+                             hipStream_t stream);
+
 }  // namespace fpe

@@ -100,6 +100,28 @@ def make_plan_states(params, poses=None, strides=None, feet=None, adjusted_y=0.0
     return states
 
 
+def make_swing_queries(a, b, radius=0.0):
+    """Build an fpe_swing_query array (swing_segments) from [n, 3] start points A and end points B (x, y, z) and per-segment capsule
+    radii (float32; <= 0: the limits' radius, else params.footRadius); a scalar radius broadcasts."""
+    a, b = np.asarray(a, dtype=np.float64).reshape(-1, 3), np.asarray(b, dtype=np.float64).reshape(-1, 3)
+    q = np.zeros(a.shape[0], dtype=_capi.SWING_QUERY_DTYPE)
+    q["a"], q["b"], q["radius"] = a, b, radius
+    return q
+
+
+def make_swing_limits(max_lift=np.inf, max_rise=np.inf, max_length=np.inf, radius=0.0):
+    """An fpe_swing_limits block: the limits behind the OVER bits (+infinity: no limit) and the capsule radius of segments that give
+    none (<= 0: params.footRadius).  Pure host arithmetic: no engine, no GPU."""
+    return _capi.SwingLimits(float(max_lift), float(max_rise), float(max_length), float(radius), 0)
+
+
+def _swing_limits(limits):
+    """None (the engine's defaults), a SwingLimits block, or a dict of make_swing_limits' keywords."""
+    if limits is None or isinstance(limits, _capi.SwingLimits):
+        return limits
+    return make_swing_limits(**dict(limits))
+
+
 # fpe_set_tuning's knobs whose engine default is not 0 (tuning() restores these after a with-block)
 TUNING_DEFAULTS = {"service_opt_gate": 2, "service_overlap": 1, "service_poll": 1}
 
@@ -718,6 +740,59 @@ class FootholdPlanner(_Handle):
         co = self._dense_out("centroid-map", code=d_code_ptr, offset=d_offset_ptr, z=d_z_ptr)
         self._check(self._lib.fpe_centroid_map_device(self._h, ptr(self.params), ptr(r), float(search_radius or 0.0), C.byref(co),
                                                       C.c_void_p(stream or 0)))
+
+    # ---- swing checks: each planned step against the elevation layer (build-defined: fpe_swing_*) ---------------------------
+    def swing_segments(self, queries, limits=None):
+        """fpe_swing_segments: one SWING_RECORD_DTYPE record per SWING_QUERY_DTYPE query (make_swing_queries) on the current map.
+        `limits`: None (no limit, radius params.footRadius), make_swing_limits(...) or a dict of its keywords."""
+        queries = np.ascontiguousarray(queries, dtype=_capi.SWING_QUERY_DTYPE).reshape(-1)
+        out = np.zeros(queries.shape[0], dtype=_capi.SWING_RECORD_DTYPE)
+        sl = _swing_limits(limits)
+        self._check(self._lib.fpe_swing_segments(self._h, ptr(self.params), C.byref(sl) if sl is not None else None, ptr(queries),
+                                                 queries.shape[0], ptr(out)))
+        return out
+
+    def swing_segments_device(self, d_queries_ptr, n, d_out_ptr, limits=None, stream=0):
+        """Device form: DEVICE pointers to n queries and n records, asynchronous on `stream`."""
+        sl = _swing_limits(limits)
+        self._check(self._lib.fpe_swing_segments_device(self._h, ptr(self.params), C.byref(sl) if sl is not None else None,
+                                                        C.c_void_p(d_queries_ptr), int(n), C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)))
+
+    def plan_swing(self, poses, n_cycles, limits=None, strides=None, products=("nominal", "cycle_ok", "stance"), summary=True):
+        """fpe_swing_plan with host buffers: plans the batch as plan() does (strides: as there) and checks every planned step against
+        the elevation layer in the same call.  Returns the requested plan products plus "swing": SWING_RECORD_DTYPE [B, n_cycles, 4],
+        "swing_length": float64 sqrt of its length_sq, and (summary=True) "swing_summary": SWING_SUMMARY_DTYPE [B].  The start feet
+        are the plan's stance, which carries the pose's z."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        B = poses.shape[0]
+        unknown = set(products) - set(PRODUCT_ORDER)
+        if unknown:
+            raise ValueError(f"unknown plan products {sorted(unknown)}")
+        shapes = product_shapes(B, n_cycles)
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in PRODUCT_ORDER if k in products}
+        po = _fill_products(PlanOut(), {k: ptr(out[k]) for k in out})
+        out["swing"] = np.zeros((B, n_cycles, 4), _capi.SWING_RECORD_DTYPE)
+        so = _capi.SwingOut(ptr(out["swing"]), None)
+        if summary:
+            out["swing_summary"] = np.zeros(B, _capi.SWING_SUMMARY_DTYPE)
+            so.summary = ptr(out["swing_summary"])
+        sl = _swing_limits(limits)
+        self._check(self._lib.fpe_swing_plan(self._h, ptr(self.params), C.byref(sl) if sl is not None else None, ptr(poses),
+                                             ptr(_strides_for(strides, B)) if strides is not None else None, B, int(n_cycles),
+                                             C.byref(po), C.byref(so)))
+        out["swing_length"] = np.sqrt(out["swing"]["length_sq"])
+        return out
+
+    def swing_plan_device(self, d_nominal_ptr, d_cycle_ok_ptr, B, n_cycles, d_records_ptr=0, d_summary_ptr=0, d_stance_ptr=0,
+                          d_start_feet_ptr=0, limits=None, stream=0):
+        """fpe_swing_plan_device: DEVICE pointers to a plan's nominal and cycle_ok products as a plan call on `stream` left them, the
+        start feet ([B, 4, 3] doubles; 0: the plan's stance product, d_stance_ptr) and the outputs (0 = not wanted)."""
+        po = _fill_products(PlanOut(), {"nominal": d_nominal_ptr, "cycle_ok": d_cycle_ok_ptr, "stance": d_stance_ptr})
+        so = _capi.SwingOut(d_records_ptr or None, d_summary_ptr or None)
+        sl = _swing_limits(limits)
+        self._check(self._lib.fpe_swing_plan_device(self._h, ptr(self.params), C.byref(sl) if sl is not None else None, C.byref(po),
+                                                    C.c_void_p(d_start_feet_ptr or 0), int(B), int(n_cycles), C.byref(so),
+                                                    C.c_void_p(stream or 0)))
 
     # ---- the dense maps as grid_map message layers (fpe_export_layers*) ----------------------------------------------------
     def _layer_request(self, names, dsts, snap_search_radius, snap_polygon, centroid_search_radius):
