@@ -304,7 +304,7 @@ __device__ __forceinline__ void fill_yentry(const MapGeom& mg, const PC& pc, con
         idx[k] = -static_cast<int>(kk);
     }
     bool cornersWithin = true;  // checkIfPositionWithinMap of the centroid rectangle's bounded corners (y axis)
-    if (__ballot(!safe) != 0ull) {
+    if (FPE_RARE_IF((std::is_same<PC, YFillConsts>::value), __ballot(!safe) != 0ull)) {  // (weighted in the 3x3-only kernels)
         const double tly = bound_axis(xs0[0], mg.orgY, mg.posY, mg.lenY);
         const double bry = bound_axis(xs0[1], mg.orgY, mg.posY, mg.lenY);
         const double tlr = bound_axis(xs0[3], mg.orgY, mg.posY, mg.lenY);
@@ -808,7 +808,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
     const bool dfltLane = (g.sub == 5) | (g.sub == 6);
     const bool laneOk = kNoDefault ? (dfltLane | (safe & (fabs(nxq) <= 1e6))) : (safe & (fabs(nxq) <= 1e6));
     const bool rare = (!kPlain & !ls.radiusOk) | ((ye.flags & (2 | kYCentreMid)) != (2 | kYCentreMid)) | !laneOk | (!kNoDefault & !wantDefault) | !boxes;
-    if (__ballot(rare) != 0ull) {  // wave-uniform
+    if (FPE_RARE(__ballot(rare) != 0ull)) {  // wave-uniform
         const double ctr0 = swizzle_f64<kKeep | (5 << 5)>(myCtr), ctr1 = swizzle_f64<kKeep | (0 << 5)>(myCtr),
                      ctr2 = swizzle_f64<kKeep | (7 << 5)>(myCtr);
         // (rare: the plan constants, the rank tables and the product pointers from the argument segment, here)
@@ -992,7 +992,7 @@ __device__ __forceinline__ void leg_fast8m(const DevMap& m, const BitMap& bm, in
             wj = icj + static_cast<int>((fk.dj >> rank4) & 7ull) - 2;
             searched = lk.nCand <= 16;  // nothing beyond the sixteen
         }
-        if (!found && !searched) {  // other polygons, larger foot discs, small search radii, or no hit in the first two rounds
+        if (FPE_RARE(!found && !searched)) {  // other polygons, larger foot discs, small search radii, or no hit in the first two rounds
             LegCtx c;
             c.cyc = cyc;
             c.cx = cx;
@@ -1104,7 +1104,7 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
     const LutHead head = load_lut_head(lut, g);
     LegStatic ls;
     {
-        if (!kPlain && __ballot(rOverride > 0.0f) != 0ull) {  // some leg of the wavefront overrides the search radius (build-defined)
+        if (!kPlain && FPE_RARE_IF(kMid, __ballot(rOverride > 0.0f) != 0ull)) {  // some leg of the wavefront overrides the search radius (build-defined)
             ls = make_leg_static(pc, pp, leg, m.g.res, lut);
         } else {  // the reference's single searchRadius_: constants precomputed on the host
             ls.Rf = pc.searchRadius;
@@ -1194,10 +1194,10 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
     // (<4, false, 2 / 0>: 48 -> 64 / 72 bytes of scratch with it) — those compute the centre at both places, as before.
     constexpr bool kStanceOnce = kMid && NRL < 4;
     double stanceCtr = 0.0;
-    if constexpr (kStanceOnce) stanceCtr = polygon_center_x(sh.cur[0]);
+    if constexpr (kStanceOnce) stanceCtr = polygon_center_x<kMid>(sh.cur[0]);
     if (started && out.pose_status) {
         // getGaitCycleSearchGridMap's getSubmap in the first cycle (opt_gate_cycle0), its four corners on four lanes
-        const double gx = (kStanceOnce ? stanceCtr : polygon_center_x(sh.cur[0])) + (kStride ? sv.step : pc.step), gy = y0 + 0.0;  // cpp:2327-2329
+        const double gx = (kStanceOnce ? stanceCtr : polygon_center_x<kMid>(sh.cur[0])) + (kStride ? sv.step : pc.step), gy = y0 + 0.0;  // cpp:2327-2329
         Submap gs;
         {
             // lane q & 3: 0 top-left x, 1 top-left y, 2 bottom-right x, 3 bottom-right y — predicted as in the x pass
@@ -1211,7 +1211,7 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             const double kq = trunc(qf);
             const double fr = fabs(qf - kq);
             const bool safe = (fr > pc.cornerEps) & (fr < 1.0 - pc.cornerEps) & (qf < -pc.cornerEps) & (qf > pc.cornerEps - cells);
-            if (__ballot(!safe) == 0ull) {
+            if (!FPE_RARE_IF(kMid, __ballot(!safe) != 0ull)) {
                 const int idxq = -static_cast<int>(kq);
                 constexpr int kKeep = (~(G - 1)) & 0x1F;
                 BBox gbb;
@@ -1283,14 +1283,14 @@ __device__ __forceinline__ void plan_bits_body(const fpe_pose* pp, int b, bool l
             UnitT* unit = units;
             for (int s = 0; s < nb; ++s, ++yeP, ++unit) {
                 const int cyc = c0 + s;
-                if (cyc == prioCyc) __builtin_amdgcn_s_setprio(2);
+                if (FPE_RARE(cyc == prioCyc)) __builtin_amdgcn_s_setprio(2);
                 const YEntry& ye = *yeP;
                 bool cycleOk = true;
                 for (int ph = 0; ph < nPhases; ++ph) {  // (the phases: see the flat form below)
                     const unsigned mask = (!kPlain && gait == 1) ? (1u << ((walkOrder >> (2 * ph)) & 3)) : 0xFu;
                     const bool active = kPlain || ((mask >> leg) & 1u) != 0u;  // (plain: every leg swings in the one phase)
                     double myCtr = stanceCtr;
-                    if (!kStanceOnce || cyc != 0 || ph != 0) myCtr = polygon_center_x(sh.cur[myTrack]);  // (wave-uniform branch)
+                    if (!FPE_RARE(kStanceOnce && cyc == 0 && ph == 0)) myCtr = polygon_center_x<true>(sh.cur[myTrack]);  // (wave-uniform branch)
                     LegCommit lc;
                     lc.valid = 1;  // non-swing legs do not vote
                     if (active)

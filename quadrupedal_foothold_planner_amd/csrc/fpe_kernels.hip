@@ -37,6 +37,16 @@ __device__ __forceinline__ double in_vgpr(double x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+// Branch weights, the engine's one spelling: FPE_RARE(c) is c, and tells the compiler that c is false on all but unusual input.
+// For WAVE-UNIFORM tests whose true side is rare whatever the terrain — the map's border, a coordinate within rounding distance of a
+// cell boundary, non-finite or >= 1e6 coordinates, the ends of the exponent range, the one cycle of the priority hand-over — and
+// guards a large body: without a weight every such test counts as even odds in block placement, spill weights and live-range
+// splitting, and the hot path is threaded between the cold bodies.  Not for anything the terrain decides (defaultOk, found, the
+// centroid cases).  A macro, not an inline function: the hint is lowered to a branch weight before inlining, inside a helper it
+// would find no branch.  FPE_RARE_IF(k, c): the hint only where the compile-time flag k holds — helpers that the generic, stride,
+// resume, one-wavefront-per-pose and direct kernels share keep those kernels' code as it is.
+#define FPE_RARE(c) __builtin_expect(static_cast<bool>(c), 0)
+#define FPE_RARE_IF(k, c) ((k) ? FPE_RARE(c) : static_cast<bool>(c))
 // The map geometry is wave-uniform and would live in 20 scalar registers; the chained kernels need more uniform state than the 102
 // SGPRs hold, and every spilled SGPR costs a v_readlane (+ wait states) per use.  The doubles are only ever operands of vector f64
 // arithmetic, so the kernels that have the vector registers for it park them there.
@@ -1340,16 +1350,19 @@ __device__ __forceinline__ void store_selected(const fpe_plan_out& out, size_t o
 // r = x - 3 q is exact in an FMA (a small multiple of ulp(q)), and q + r * c = x/3 + (x/3 - q) * eps with |eps| <= 2^-53:
 // the perturbation is < 2^-52 ulp while x / 3 is never closer than ulp / 6 to a rounding boundary (3 * midpoint is an
 // odd multiple of half an ulp of the quotient's grid, x an even one), so the final FMA rounds to RN(x / 3).  Zero, NaN
-// and values near the ends of the exponent range take the division itself (wave-uniform branch).
+// and values near the ends of the exponent range take the division itself (wave-uniform branch; kRareGuard: weighted as rare, for
+// the 3x3-only 8-lane kernels — see FPE_RARE_IF).
+template <bool kRareGuard = false>
 __device__ __forceinline__ double div3(double x) {
     const double ax = fabs(x);
-    if (__ballot(!(ax > 1e-280 && ax < 1e300)) != 0ull) return x / 3.0;
+    if (FPE_RARE_IF(kRareGuard, __ballot(!(ax > 1e-280 && ax < 1e300)) != 0ull)) return x / 3.0;
     const double c = 0x1.5555555555555p-2;
     const double q = x * c;
     const double r = __builtin_fma(-3.0, q, x);
     return __builtin_fma(r, c, q);
 }
 
+template <bool kRareGuard = false>
 __device__ __forceinline__ double polygon_center_x(const double (*feet)[3]) {
     const double x1 = feet[0][0], y1 = feet[0][1];
     double x2 = feet[1][0], y2 = feet[1][1];
@@ -1363,7 +1376,7 @@ __device__ __forceinline__ double polygon_center_x(const double (*feet)[3]) {
         x2 = x3;
         y2 = y3;
     }
-    return div3(sum_x / sum_s);
+    return div3<kRareGuard>(sum_x / sum_s);
 }
 
 // getGaitCycleSearchGridMap (cpp:2307-2349) in the FIRST gait cycle: the opt track's current feet are the shifted
