@@ -1105,6 +1105,121 @@ int fpe_swing_plan_device(fpe_handle h, const fpe_params* params, const fpe_swin
 int fpe_swing_plan(fpe_handle h, const fpe_params* params, const fpe_swing_limits* limits, const fpe_pose* poses,
                    const fpe_stride* strides, int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_swing_out* out);
 
+/* ---- trunk checks: each planned stance's body box against the elevation layer ------------------------------------------------------
+ * BUILD-DEFINED (the reference never looks at the ground under the body: a plan whose footholds and swings all pass can still put the
+ * belly on a kerb, a stair nose or a block the feet straddle).  A STANCE is four feet f[leg] = (x, y, z), all doubles, in the order
+ * RF, RH, LH, LF — in the reference's stance (cpp:350-378) the front feet are RF and LF, and the left feet LH and LF have the larger
+ * y — and a box of half extents hx, hy, each double(float).  All arithmetic is f64, in exactly this order, without contraction:
+ *     cx  = ((x0 + x1) + (x2 + x3)) * 0.25;   cy, zm likewise from y and z
+ *     dxf = ((x0 + x3) - (x1 + x2)) * 0.5;    dzf = ((z0 + z3) - (z1 + z2)) * 0.5      front minus hind
+ *     dyl = ((y2 + y3) - (y0 + y1)) * 0.5;    dzl = ((z2 + z3) - (z0 + z1)) * 0.5      left minus right
+ *     slope_x = dxf > 0 ? dzf / dxf : 0;      slope_y = dyl > 0 ? dzl / dyl : 0
+ *     base_z  = zm + limits.ride_height
+ * On the snapshot current at entry, with MapGeom g (csrc/fpe_gridmath.hpp), cell (i, j), 0 <= i < rows, 0 <= j < cols, is a MEMBER iff
+ *     px = cell_pos(g.baseX, g.res, i);  py = cell_pos(g.baseY, g.res, j);      fabs(px - cx) <= hx  &&  fabs(py - cy) <= hy
+ * so the members are an index rectangle, decided per row and per column.  A member with elevation e (f32) is KNOWN iff isfinite(e) &&
+ * e < 10.0f — the cut of getFootholdMeanHeight (cpp:2533) and of the swing check — and a known member has
+ *     gap_c = (base_z + (slope_x * (px - cx) + slope_y * (py - cy))) - double(e)
+ * the height of the body plane through the feet, lifted by ride_height, above the ground of that cell.  Every quantity of a record is
+ * order-free — a count, an extremum, or an argmin with a stated tie rule:
+ *   clearance      the minimum gap_c over the known members, taken in IEEE-754 totalOrder (-0.0 ranks below +0.0; nothing is NaN: see
+ *                  the slope bound below), so the bits are defined and clearance is the gap_c of the cell the record names.  +infinity
+ *                  when there is no known member;
+ *   row, col       the known member attaining it; among several the lowest row, then the lowest column.  (-1, -1) when there is none;
+ *   slope_x, slope_y, base_z   as derived above: what a controller sets body pitch, roll and height from;
+ *   max_elevation  the totalOrder maximum of e over the known members; 0 when there is none;
+ *   n_cells        members (inside the map);  n_unknown: members that are not known;
+ *   flags          FPE_TRUNK_* bits, below.
+ * Half extents: query.half_length / half_width <= 0 means the limits' value, and that, if <= 0, 0.5 * double(params.length) /
+ * 0.5 * double(params.width).  Limits: a NULL `limits` is fpe_trunk_limits_defaults — min_clearance -infinity, both slope limits
+ * +infinity (no UNDER / OVER bit is ever set), ride_height 0, both half extents 0.
+ * Refusals.  Every form returns FPE_E_INVALID_ARG for a null argument, n or B < 1, n_cycles outside 1..255, a limits.reserved word
+ * that is not 0, a NaN limit, a ride_height that is not finite or beyond +-1e6, or a default half extent (the limits', else half the
+ * params') that is not finite, <= 0 or above FPE_TRUNK_MAX_HALF_EXTENT; FPE_E_UNSUPPORTED on the maps the swing check refuses (a
+ * resolution below 1e-4 m, a cell farther than 2e6 m from the origin: the kernels' cell enumeration is proven a superset of the
+ * members for the rest, csrc/fpe_trunk.hpp) and when the default box exceeds FPE_TRUNK_MAX_CELLS by the f64 expression
+ *     (2.0 * hx / g.res + 3.0) * (2.0 * hy / g.res + 3.0) > FPE_TRUNK_MAX_CELLS
+ * The host forms also refuse (FPE_E_INVALID_ARG; nothing is queued or written) a stance with a query.reserved word that is not 0, a
+ * non-finite coordinate, |coordinate| > 1e6, a half extent that is not finite or above FPE_TRUNK_MAX_HALF_EXTENT, a box over the cell
+ * cap by the same expression, or a slope beyond +-FPE_TRUNK_MAX_SLOPE; fpe_trunk_plan refuses what fpe_plan refuses.  The slope
+ * bound is what makes "nothing is NaN" true: feet a hair apart give an infinite slope, and infinity times a zero offset is a NaN whose
+ * bits differ between machines; within the bound every gap_c is finite.  The device forms cannot look at the values: such a stance
+ * (reserved is not read) gives a record with flags = FPE_TRUNK_REFUSED and every other field zero, decided per record in the kernel by
+ * the same expressions.
+ * The plan-bound stances are the four feet on the ground when cycle g of a plan has landed.  With the products nominal [B, n, 4] and
+ * cycle_ok [B, n], record (b, g) at b * n_cycles + g:
+ *   - describes a stance iff cycle_ok[b, g] != 0;  its feet are nominal[b, g, leg] as (x, y, double(z)), its half extents the defaults;
+ *   - equals, bit for bit, the record the open-loop form returns for that query, with gait_cycle_id = g filled in;
+ *   - of a cycle that did not commit: all zero but gait_cycle_id.
+ * Successive boxes of one pose overlap by construction — a cycle moves the feet by the step length (0.18 m in the yaml), far below
+ * the body length (0.4387 m) — so the ground under the moving trunk is covered from cycle to cycle by the union of the records.  The
+ * half-cycle stances of the trot's two diagonal pairs (two feet down, two in the air) are not checked.
+ * The per-pose summary runs over the pose's records that describe a stance, whatever else their flags say: min_clearance (totalOrder;
+ * +infinity when there is none), max_abs_slope_x / _y = max fabs(slope) (0 when none), n_stances, n_bad: stances with UNDER_CLEARANCE
+ * or OVER_SLOPE, n_unknown: stances with UNKNOWN, EMPTY or OFF_MAP, first_bad_cycle: the lowest g of a bad stance, 255 when none.
+ * No atomics anywhere: every byte is a function of the inputs alone.  Out of scope: a trunk term in fpe_plan_rank* / fpe_plan_beam*,
+ * fpe_multi_*, the service calls, the opt and centroid tracks' footholds, yaw (the box is axis-aligned in the map frame, as the
+ * reference's stance is), the trot's half-cycle stances, any body shape other than the axis-aligned box. */
+#define FPE_TRUNK_STANCE          1u   /* the record describes a stance */
+#define FPE_TRUNK_OFF_MAP         2u   /* any of the four corners (cx +- hx, cy +- hy) fails checkIfPositionWithinMap (within_axis) */
+#define FPE_TRUNK_EMPTY           4u   /* n_cells == 0 */
+#define FPE_TRUNK_UNKNOWN         8u   /* n_unknown > 0 */
+#define FPE_TRUNK_UNDER_CLEARANCE 16u  /* clearance < limits.min_clearance */
+#define FPE_TRUNK_OVER_SLOPE      32u  /* fabs(slope_x) > limits.max_slope_x || fabs(slope_y) > limits.max_slope_y */
+#define FPE_TRUNK_DEGENERATE      64u  /* !(dxf > 0) || !(dyl > 0): the slope of that axis is 0 */
+#define FPE_TRUNK_REFUSED         128u /* device forms: a stance the host forms refuse; every other field zero, STANCE not set */
+#define FPE_TRUNK_MAX_HALF_EXTENT 1.0f
+#define FPE_TRUNK_MAX_CELLS       65536
+#define FPE_TRUNK_MAX_SLOPE       1e6
+typedef struct fpe_trunk_query {      /* 112 bytes */
+    double  feet[4][3];    /* RF, RH, LH, LF: x, y, z */
+    float   half_length;   /* hx; <= 0: limits.half_length, else 0.5 * params.length */
+    float   half_width;    /* hy; <= 0: limits.half_width, else 0.5 * params.width */
+    int32_t reserved[2];   /* 0 */
+} fpe_trunk_query;
+typedef struct fpe_trunk_limits {     /* 48 bytes */
+    double  min_clearance;            /* not NaN; -infinity: no limit */
+    double  max_slope_x, max_slope_y; /* not NaN; +infinity: no limit */
+    double  ride_height;              /* finite, |ride_height| <= 1e6: the body plane's height above the plane through the feet */
+    float   half_length, half_width;  /* the box of stances that give none; <= 0: half of params.length / params.width */
+    int32_t reserved[2];              /* 0 */
+} fpe_trunk_limits;
+typedef struct fpe_trunk_record {     /* 56 bytes */
+    double  clearance, slope_x, slope_y, base_z;
+    float   max_elevation;
+    int32_t n_cells, n_unknown;
+    int32_t row, col;
+    uint8_t flags;         /* FPE_TRUNK_* */
+    uint8_t gait_cycle_id; /* plan-bound: g; open-loop: 0 */
+    uint8_t pad[2];
+} fpe_trunk_record;
+typedef struct fpe_trunk_summary {    /* 40 bytes; element b belongs to pose b */
+    double  min_clearance, max_abs_slope_x, max_abs_slope_y;
+    int32_t n_stances, n_bad, n_unknown;
+    uint8_t first_bad_cycle;  /* 255: none */
+    uint8_t pad[3];
+} fpe_trunk_summary;
+typedef struct fpe_trunk_out {        /* 16 bytes; either pointer may be NULL */
+    fpe_trunk_record*  records;  /* [B * n_cycles] */
+    fpe_trunk_summary* summary;  /* [B] */
+} fpe_trunk_out;
+int fpe_trunk_limits_defaults(fpe_trunk_limits* out);
+/* Open-loop: n arbitrary stances.  Host arrays, synchronous / device arrays, asynchronous on `stream`. */
+int fpe_trunk_stances(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_trunk_query* queries, int32_t n,
+                      fpe_trunk_record* out);
+int fpe_trunk_stances_device(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_trunk_query* d_queries,
+                             int32_t n, fpe_trunk_record* d_out, void* stream);
+/* Plan-bound, device arrays: reads d_products->nominal and ->cycle_ok (both required) as a plan call on `stream` left them;
+ * `d_products` and `d_out` themselves are host structs of device pointers.  Asynchronous on `stream`, behind whatever filled the
+ * products there. */
+int fpe_trunk_plan_device(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_plan_out* d_products,
+                          int32_t B, int32_t n_cycles, const fpe_trunk_out* d_out, void* stream);
+/* Plan and check in one call, host arrays, synchronous: plans exactly as fpe_plan (strides NULL) or fpe_plan_strides would, checks the
+ * plan on the same stream with no host synchronisation in between, on ONE snapshot, and returns the requested products (NULL: none)
+ * and the trunk outputs. */
+int fpe_trunk_plan(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_pose* poses,
+                   const fpe_stride* strides, int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_trunk_out* out);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

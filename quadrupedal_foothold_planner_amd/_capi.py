@@ -318,6 +318,39 @@ class SwingOut(C.Structure):
     _fields_ = [("records", C.c_void_p), ("summary", C.c_void_p)]
 
 
+# FPE_TRUNK_* flag bits of fpe_trunk_record.flags and the bounds of a trunk stance
+TRUNK_STANCE, TRUNK_OFF_MAP, TRUNK_EMPTY, TRUNK_UNKNOWN, TRUNK_UNDER_CLEARANCE, TRUNK_OVER_SLOPE, TRUNK_DEGENERATE, TRUNK_REFUSED = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+TRUNK_MAX_HALF_EXTENT = np.float32(1.0)
+TRUNK_MAX_CELLS = 65536
+TRUNK_MAX_SLOPE = 1e6
+# fpe_trunk_query: one stance, the feet RF, RH, LH, LF (x, y, z) and the box's half extents (<= 0: the limits', else half the params')
+TRUNK_QUERY_DTYPE = np.dtype([("feet", "<f8", (4, 3)), ("half_length", "<f4"), ("half_width", "<f4"), ("reserved", "<i4", (2,))], align=True)
+# fpe_trunk_record: what a stance's body box holds of the elevation layer; fpe_trunk_summary: one pose's records reduced
+TRUNK_RECORD_DTYPE = np.dtype(
+    [("clearance", "<f8"), ("slope_x", "<f8"), ("slope_y", "<f8"), ("base_z", "<f8"), ("max_elevation", "<f4"), ("n_cells", "<i4"),
+     ("n_unknown", "<i4"), ("row", "<i4"), ("col", "<i4"), ("flags", "u1"), ("gait_cycle_id", "u1"), ("pad", "u1", (2,))],
+    align=True,
+)
+TRUNK_SUMMARY_DTYPE = np.dtype(
+    [("min_clearance", "<f8"), ("max_abs_slope_x", "<f8"), ("max_abs_slope_y", "<f8"), ("n_stances", "<i4"), ("n_bad", "<i4"),
+     ("n_unknown", "<i4"), ("first_bad_cycle", "u1"), ("pad", "u1", (3,))],
+    align=True,
+)
+assert (TRUNK_QUERY_DTYPE.itemsize, TRUNK_RECORD_DTYPE.itemsize, TRUNK_SUMMARY_DTYPE.itemsize) == (112, 56, 40)
+
+
+class TrunkLimits(C.Structure):
+    """fpe_trunk_limits: the limits behind UNDER_CLEARANCE / OVER_SLOPE (-/+infinity: none), the ride height and the default box."""
+    _fields_ = [("min_clearance", C.c_double), ("max_slope_x", C.c_double), ("max_slope_y", C.c_double), ("ride_height", C.c_double),
+                ("half_length", C.c_float), ("half_width", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class TrunkOut(C.Structure):
+    """fpe_trunk_out: outputs of a plan-bound trunk check (either pointer may be NULL)."""
+    _fields_ = [("records", C.c_void_p), ("summary", C.c_void_p)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -333,6 +366,8 @@ STRUCTS = {
     "fpe_beam_params": BeamParams, "fpe_beam_out": BeamOut, "fpe_map_patch": MapPatch, "fpe_map_update": MapUpdate,
     "fpe_elevation_update_info": ElevationUpdateInfo, "fpe_swing_query": SWING_QUERY_DTYPE, "fpe_swing_limits": SwingLimits,
     "fpe_swing_record": SWING_RECORD_DTYPE, "fpe_swing_summary": SWING_SUMMARY_DTYPE, "fpe_swing_out": SwingOut,
+    "fpe_trunk_query": TRUNK_QUERY_DTYPE, "fpe_trunk_limits": TrunkLimits, "fpe_trunk_record": TRUNK_RECORD_DTYPE,
+    "fpe_trunk_summary": TRUNK_SUMMARY_DTYPE, "fpe_trunk_out": TrunkOut,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -424,6 +459,11 @@ PROTOTYPES = {
     "fpe_swing_segments_device": (cint, [vp, vp, P(SwingLimits), vp, i32, vp, vp]),
     "fpe_swing_plan_device": (cint, [vp, vp, P(SwingLimits), P(PlanOut), vp, i32, i32, P(SwingOut), vp]),
     "fpe_swing_plan": (cint, [vp, vp, P(SwingLimits), vp, vp, i32, i32, P(PlanOut), P(SwingOut)]),
+    "fpe_trunk_limits_defaults": (cint, [P(TrunkLimits)]),
+    "fpe_trunk_stances": (cint, [vp, vp, P(TrunkLimits), vp, i32, vp]),
+    "fpe_trunk_stances_device": (cint, [vp, vp, P(TrunkLimits), vp, i32, vp, vp]),
+    "fpe_trunk_plan_device": (cint, [vp, vp, P(TrunkLimits), P(PlanOut), i32, i32, P(TrunkOut), vp]),
+    "fpe_trunk_plan": (cint, [vp, vp, P(TrunkLimits), vp, vp, i32, i32, P(PlanOut), P(TrunkOut)]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),
@@ -525,6 +565,17 @@ def swing_limits_defaults(**overrides):
             raise ValueError(f"unknown swing limit {k!r}")
         setattr(sl, k, v)
     return sl
+
+
+def trunk_limits_defaults(**overrides):
+    """fpe_trunk_limits_defaults, with any field replaced by a keyword."""
+    tl = TrunkLimits()
+    assert lib().fpe_trunk_limits_defaults(C.byref(tl)) == FPE_OK
+    for k, v in overrides.items():
+        if k not in dict(TrunkLimits._fields_) or k == "reserved":
+            raise ValueError(f"unknown trunk limit {k!r}")
+        setattr(tl, k, v)
+    return tl
 
 
 def spiral_offsets(n_rings):

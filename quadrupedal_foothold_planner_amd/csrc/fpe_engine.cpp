@@ -13,6 +13,7 @@
 #include <deque>
 #include <limits>
 #include <thread>
+#include <type_traits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -881,10 +882,11 @@ hipError_t run_export_layers(fpe_engine* h, const ExportPlan& xp, const fpe_laye
 }
 
 // The host form of an open-loop query call behind its per-query checks: n queries up, `launch(cp, d_queries, d_out, stream)`,
-// n records back, both through the context's arenas.  check (may be null): a refusal that needs the call's snapshot, ahead of any copy.
-template <class Query, class Record, class Launch>
+// n records back, both through the context's arenas.  check (a function pointer, which may be null, or any callable): a refusal that
+// needs the call's snapshot, ahead of any copy.
+template <class Query, class Record, class Launch, class Check = int (*)(const CallPlan&)>
 int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, const Query* queries, int32_t n, Record* out, Launch launch,
-                     int (*check)(const CallPlan&) = nullptr) {
+                     Check check = nullptr) {
     if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
     const size_t nQ = static_cast<size_t>(n) * sizeof(Query), nO = static_cast<size_t>(n) * sizeof(Record);
     const size_t szQ = align256(nQ);
@@ -894,7 +896,11 @@ int query_round_trip(fpe_engine* h, const fpe_params* params, float maxRadius, c
     FPE_HIP(cx.reserve(szQ + align256(nO)));
     cx.inFlight = true;
     int rc = prepare_call(h, params, maxRadius, hc.cp, cx.stream, false);
-    if (rc == FPE_OK && check) rc = check(hc.cp);
+    if constexpr (std::is_pointer_v<Check>) {
+        if (rc == FPE_OK && check) rc = check(hc.cp);
+    } else {
+        if (rc == FPE_OK) rc = check(hc.cp);
+    }
     if (rc != FPE_OK) return rc;
     std::memcpy(cx.pinned, queries, nQ);
     FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, nQ, hipMemcpyHostToDevice, cx.stream));
@@ -2929,6 +2935,178 @@ int fpe_swing_plan(fpe_handle h, const fpe_params* params, const fpe_swing_limit
     if (rc != FPE_OK) return rc;
     FPE_HIP(fpe::launch_swing_plan(dev_map(*hc.cp.snap), sc, L.plan.nominal, L.plan.cycle_ok, L.plan.stance, B, n_cycles, L.records, L.summary,
                                    cx.stream));
+    return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
+}
+
+// ---- trunk checks (fpe_trunk_*; kernels: fpe_trunk.hpp) ------------------------------------------------------------------------
+int fpe_trunk_limits_defaults(fpe_trunk_limits* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->min_clearance = -std::numeric_limits<double>::infinity();
+    out->max_slope_x = out->max_slope_y = std::numeric_limits<double>::infinity();
+    return FPE_OK;
+}
+
+namespace {
+// The limits of a trunk call as the kernels take them (limits NULL: the defaults), checked; the default box resolved.
+int trunk_consts(const fpe_params* params, const fpe_trunk_limits* limits, fpe::TrunkConsts& tc) {
+    if (!params) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    fpe_trunk_limits def;
+    if (!limits) {
+        fpe_trunk_limits_defaults(&def);
+        limits = &def;
+    }
+    if (limits->reserved[0] != 0 || limits->reserved[1] != 0) return fail(FPE_E_INVALID_ARG, "fpe_trunk_limits.reserved must be 0");
+    if (std::isnan(limits->min_clearance) || std::isnan(limits->max_slope_x) || std::isnan(limits->max_slope_y) ||
+        std::isnan(limits->half_length) || std::isnan(limits->half_width))
+        return fail(FPE_E_INVALID_ARG, "trunk limits must not be NaN");
+    if (!(std::fabs(limits->ride_height) <= 1e6)) return fail(FPE_E_INVALID_ARG, "ride_height must be finite and within +-1e6");
+    const double hx = limits->half_length > 0.0f ? static_cast<double>(limits->half_length) : 0.5 * static_cast<double>(params->length);
+    const double hy = limits->half_width > 0.0f ? static_cast<double>(limits->half_width) : 0.5 * static_cast<double>(params->width);
+    for (double v : {hx, hy})
+        if (!std::isfinite(v) || !(v > 0.0) || v > static_cast<double>(FPE_TRUNK_MAX_HALF_EXTENT))
+            return fail(FPE_E_INVALID_ARG, "the default trunk half extents must be finite, positive and at most FPE_TRUNK_MAX_HALF_EXTENT");
+    tc = fpe::TrunkConsts{limits->min_clearance, limits->max_slope_x, limits->max_slope_y, limits->ride_height, hx, hy};
+    return FPE_OK;
+}
+// What needs the call's snapshot: the maps the enumeration is proven on, and the default box against the cell cap
+int check_trunk_map(const CallPlan& cp, const fpe::TrunkConsts& tc) {
+    if (!fpe::swing_map_supported(cp.snap->g))
+        return fail(FPE_E_UNSUPPORTED, "trunk checks need a resolution of at least 1e-4 m and a map within 2e6 m of the origin");
+    if (!fpe::trunk_box_supported(tc.defaultHx, tc.defaultHy, cp.snap->g.res))
+        return fail(FPE_E_UNSUPPORTED, "the default trunk box exceeds FPE_TRUNK_MAX_CELLS cells at this resolution");
+    return FPE_OK;
+}
+int check_trunk_shape(int32_t B, int32_t n_cycles) {
+    if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
+    if (static_cast<int64_t>(B) * n_cycles > (1 << 30)) return fail(FPE_E_INVALID_ARG, "B * n_cycles must not exceed 2^30");
+    return FPE_OK;
+}
+}  // namespace
+
+int fpe_trunk_stances_device(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_trunk_query* d_queries,
+                             int32_t n, fpe_trunk_record* d_out, void* stream) {
+    if (!d_queries || !d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    fpe::TrunkConsts tc;
+    int rc = trunk_consts(params, limits, tc);
+    if (rc != FPE_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    rc = prepare_call(h, params, 0.0f, cp, st, false);
+    if (rc == FPE_OK) rc = check_trunk_map(cp, tc);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    FPE_HIP(fpe::launch_trunk_stances(dev_map(*cp.snap), tc, d_queries, n, d_out, st));
+    return FPE_OK;
+}
+
+int fpe_trunk_stances(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_trunk_query* queries, int32_t n,
+                      fpe_trunk_record* out) {
+    if (!queries || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    fpe::TrunkConsts tc;
+    const int rc = trunk_consts(params, limits, tc);
+    if (rc != FPE_OK) return rc;
+    for (int k = 0; k < n; ++k)
+        if (queries[k].reserved[0] != 0 || queries[k].reserved[1] != 0) return fail(FPE_E_INVALID_ARG, "fpe_trunk_query.reserved must be 0");
+    return query_round_trip(h, params, 0.0f, queries, n, out,
+                            [&](const CallPlan& cp, const fpe_trunk_query* d_q, fpe_trunk_record* d_out, hipStream_t s) {
+                                return fpe::launch_trunk_stances(dev_map(*cp.snap), tc, d_q, n, d_out, s);
+                            },
+                            [&](const CallPlan& cp) {
+                                const int rm = check_trunk_map(cp, tc);
+                                if (rm != FPE_OK) return rm;
+                                for (int k = 0; k < n; ++k)  // (the cell cap is in cells: it needs the snapshot's resolution)
+                                    if (fpe::trunk_stance_refused(tc, queries[k], cp.snap->g.res))
+                                        return fail(FPE_E_INVALID_ARG, "non-finite or over-bound stance, half extent, box or slope");
+                                return static_cast<int>(FPE_OK);
+                            });
+}
+
+int fpe_trunk_plan_device(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_plan_out* d_products,
+                          int32_t B, int32_t n_cycles, const fpe_trunk_out* d_out, void* stream) {
+    if (!d_products || !d_out || !d_products->nominal || !d_products->cycle_ok) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!d_out->records && !d_out->summary) return fail(FPE_E_INVALID_ARG, "no trunk output requested");
+    fpe::TrunkConsts tc;
+    int rc = check_trunk_shape(B, n_cycles);
+    if (rc == FPE_OK) rc = trunk_consts(params, limits, tc);
+    if (rc != FPE_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    rc = prepare_call(h, params, 0.0f, cp, st, false);
+    if (rc == FPE_OK) rc = check_trunk_map(cp, tc);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    if (d_out->records) {
+        FPE_HIP(fpe::launch_trunk_plan(dev_map(*cp.snap), tc, d_products->nominal, d_products->cycle_ok, B, n_cycles, d_out->records,
+                                       d_out->summary, st));
+        return FPE_OK;
+    }
+    // the summary alone: its records live in stream-ordered scratch
+    return with_stream_scratch(static_cast<size_t>(B) * n_cycles * sizeof(fpe_trunk_record), st, [&](unsigned char* scratch) {
+        FPE_HIP(fpe::launch_trunk_plan(dev_map(*cp.snap), tc, d_products->nominal, d_products->cycle_ok, B, n_cycles,
+                                       reinterpret_cast<fpe_trunk_record*>(scratch), d_out->summary, st));
+        return static_cast<int>(FPE_OK);
+    });
+}
+
+namespace {
+// Where everything a plan-and-check call touches on the device lives: the plan's products — the requested ones in the output block,
+// what the check reads besides (nominal, cycle_ok) in scratch, null for the rest — then the records (scratch when only the summary is
+// wanted) and the summary.
+struct TrunkLayout {
+    int32_t B, n;
+    fpe_plan_out plan;
+    fpe_trunk_record* records;
+    fpe_trunk_summary* summary;
+};
+void trunk_layout(TrunkLayout& L, ArenaCursor& A, const fpe_plan_out* want, const fpe_trunk_out& to) {
+    const bool reads[kPlanProducts] = {true, false, false, true, false, false, false, false};  // trunk_stances_kernel<true>'s inputs
+    const size_t B = static_cast<size_t>(L.B), n = static_cast<size_t>(L.n);
+    void* const* wanted = want ? slots(*want) : nullptr;
+    for (int k = 0; k < kPlanProducts; ++k)
+        slots(L.plan)[k] = (wanted && wanted[k]) ? A.out(wanted[k], product_bytes(k, B, n)) : (reads[k] ? A.take(product_bytes(k, B, n)) : nullptr);
+    const size_t szRec = B * n * sizeof(fpe_trunk_record);
+    L.records = static_cast<fpe_trunk_record*>(to.records ? A.out(to.records, szRec) : A.take(szRec));
+    L.summary = static_cast<fpe_trunk_summary*>(to.summary ? A.out(to.summary, B * sizeof(fpe_trunk_summary)) : nullptr);
+}
+}  // namespace
+
+int fpe_trunk_plan(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_pose* poses, const fpe_stride* strides,
+                   int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_trunk_out* out) {
+    if (!h || !poses || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!out->records && !out->summary) return fail(FPE_E_INVALID_ARG, "no trunk output requested");
+    fpe::TrunkConsts tc;
+    int rc = check_trunk_shape(B, n_cycles);
+    if (rc == FPE_OK) rc = trunk_consts(params, limits, tc);
+    if (rc != FPE_OK) return rc;
+    float maxRadius = 0.0f;
+    rc = check_host_poses(poses, B, maxRadius);
+    if (rc == FPE_OK) rc = check_host_strides(strides, B);
+    if (rc != FPE_OK) return rc;
+    TrunkLayout L{};
+    L.B = B, L.n = n_cycles;
+    ArenaCursor sizes;
+    trunk_layout(L, sizes, products, *out);
+    // both arenas: [poses (| strides) | outputs | scratch (device arena only)]; the inputs are read from the pinned arena, as in fpe_plan
+    const size_t oStrides = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    const size_t szIn = oStrides + (strides ? align256(static_cast<size_t>(B) * sizeof(fpe_stride)) : 0);
+    HostCall hc(h);
+    CallCtx& cx = hc.cx;
+    unsigned char* in = nullptr;
+    rc = open_batch_call(h, hc, params, maxRadius, szIn + sizes.outBytes + sizes.scratchBytes, products && products->selected_packed,
+                         strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain, in);
+    if (rc == FPE_OK) rc = check_trunk_map(hc.cp, tc);
+    if (rc != FPE_OK) return rc;
+    stage_batch_inputs(cx.pinned, oStrides, poses, strides, B);
+    ArenaCursor A{cx.dev + szIn + sizes.outBytes, cx.dev + szIn, szIn};
+    trunk_layout(L, A, products, *out);
+    // the plan through the plan runner, then the check behind it on the same stream and the same snapshot
+    rc = launch_plan(h, hc.cp, reinterpret_cast<const fpe_pose*>(in), B, n_cycles, L.plan, cx.stream,
+                     {strides ? reinterpret_cast<const fpe_stride*>(in + oStrides) : nullptr});
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(fpe::launch_trunk_plan(dev_map(*hc.cp.snap), tc, L.plan.nominal, L.plan.cycle_ok, B, n_cycles, L.records, L.summary, cx.stream));
     return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
 }
 

@@ -371,4 +371,21 @@ hipError_t launch_swing_plan(const DevMap& m, const SwingConsts& sc, const fpe_f
                              const double* d_startFeet, int B, int nCycles, fpe_swing_record* d_records, fpe_swing_summary* d_summary,
                              hipStream_t stream);
 
+// ---- trunk checks (fpe_trunk.hpp) ----------------------------------------------------------------------------
+// The limits of a call as the kernels take them, by value, checked by the host (no NaN; rideHeight finite), and the box of a stance
+// that names none already resolved (the limits' half extents, else half of params.length / params.width; finite, in
+// (0, FPE_TRUNK_MAX_HALF_EXTENT]).
+struct TrunkConsts {
+    double minClearance, maxSlopeX, maxSlopeY, rideHeight;
+    double defaultHx, defaultHy;
+};
+bool trunk_box_supported(double hx, double hy, double res);  // the cell cap of include/fpe.h (FPE_TRUNK_MAX_CELLS)
+// Whether a host form refuses the stance: the expressions the kernel answers FPE_TRUNK_REFUSED by
+bool trunk_stance_refused(const TrunkConsts& tc, const fpe_trunk_query& q, double res);
+hipError_t launch_trunk_stances(const DevMap& m, const TrunkConsts& tc, const fpe_trunk_query* d_q, int n, fpe_trunk_record* d_out,
+                                hipStream_t stream);
+// The stances a plan's products imply: B * nCycles records (required) and, where d_summary is given, one summary per pose
+hipError_t launch_trunk_plan(const DevMap& m, const TrunkConsts& tc, const fpe_foothold* d_nominal, const uint8_t* d_cycleOk, int B,
+                             int nCycles, fpe_trunk_record* d_records, fpe_trunk_summary* d_summary, hipStream_t stream);
+
 }  // namespace fpe

@@ -122,6 +122,30 @@ def _swing_limits(limits):
     return make_swing_limits(**dict(limits))
 
 
+def make_trunk_queries(feet, half_length=0.0, half_width=0.0):
+    """Build an fpe_trunk_query array (trunk_stances) from [n, 4, 3] feet (RF, RH, LH, LF; x, y, z) and per-stance half extents of the
+    body box (float32; <= 0: the limits' value, else half of params.length / params.width); scalars broadcast."""
+    feet = np.asarray(feet, dtype=np.float64).reshape(-1, 4, 3)
+    q = np.zeros(feet.shape[0], dtype=_capi.TRUNK_QUERY_DTYPE)
+    q["feet"], q["half_length"], q["half_width"] = feet, half_length, half_width
+    return q
+
+
+def make_trunk_limits(min_clearance=-np.inf, max_slope_x=np.inf, max_slope_y=np.inf, ride_height=0.0, half_length=0.0, half_width=0.0):
+    """An fpe_trunk_limits block: the limits behind UNDER_CLEARANCE / OVER_SLOPE (-/+infinity: no limit), the height of the body plane
+    above the plane through the feet, and the box of stances that give none (<= 0: half of params.length / params.width).  Pure host
+    arithmetic: no engine, no GPU."""
+    return _capi.TrunkLimits(float(min_clearance), float(max_slope_x), float(max_slope_y), float(ride_height), float(half_length),
+                             float(half_width), (C.c_int32 * 2)(0, 0))
+
+
+def _trunk_limits(limits):
+    """None (the engine's defaults), a TrunkLimits block, or a dict of make_trunk_limits' keywords."""
+    if limits is None or isinstance(limits, _capi.TrunkLimits):
+        return limits
+    return make_trunk_limits(**dict(limits))
+
+
 # fpe_set_tuning's knobs whose engine default is not 0 (tuning() restores these after a with-block)
 TUNING_DEFAULTS = {"service_opt_gate": 2, "service_overlap": 1, "service_poll": 1}
 
@@ -793,6 +817,56 @@ class FootholdPlanner(_Handle):
         self._check(self._lib.fpe_swing_plan_device(self._h, ptr(self.params), C.byref(sl) if sl is not None else None, C.byref(po),
                                                     C.c_void_p(d_start_feet_ptr or 0), int(B), int(n_cycles), C.byref(so),
                                                     C.c_void_p(stream or 0)))
+
+    # ---- trunk checks: each planned stance's body box against the elevation layer (build-defined: fpe_trunk_*) -------------
+    def trunk_stances(self, queries, limits=None):
+        """fpe_trunk_stances: one TRUNK_RECORD_DTYPE record per TRUNK_QUERY_DTYPE query (make_trunk_queries) on the current map.
+        `limits`: None (no limit, ride height 0, the box of params.length x params.width), make_trunk_limits(...) or a dict of its
+        keywords."""
+        queries = np.ascontiguousarray(queries, dtype=_capi.TRUNK_QUERY_DTYPE).reshape(-1)
+        out = np.zeros(queries.shape[0], dtype=_capi.TRUNK_RECORD_DTYPE)
+        tl = _trunk_limits(limits)
+        self._check(self._lib.fpe_trunk_stances(self._h, ptr(self.params), C.byref(tl) if tl is not None else None, ptr(queries),
+                                                queries.shape[0], ptr(out)))
+        return out
+
+    def trunk_stances_device(self, d_queries_ptr, n, d_out_ptr, limits=None, stream=0):
+        """Device form: DEVICE pointers to n queries and n records, asynchronous on `stream`."""
+        tl = _trunk_limits(limits)
+        self._check(self._lib.fpe_trunk_stances_device(self._h, ptr(self.params), C.byref(tl) if tl is not None else None,
+                                                       C.c_void_p(d_queries_ptr), int(n), C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)))
+
+    def plan_trunk(self, poses, n_cycles, limits=None, strides=None, products=("nominal", "cycle_ok"), summary=True):
+        """fpe_trunk_plan with host buffers: plans the batch as plan() does (strides: as there) and checks the body box of every
+        planned stance against the elevation layer in the same call.  Returns the requested plan products plus "trunk":
+        TRUNK_RECORD_DTYPE [B, n_cycles] and (summary=True) "trunk_summary": TRUNK_SUMMARY_DTYPE [B]."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        B = poses.shape[0]
+        unknown = set(products) - set(PRODUCT_ORDER)
+        if unknown:
+            raise ValueError(f"unknown plan products {sorted(unknown)}")
+        shapes = product_shapes(B, n_cycles)
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in PRODUCT_ORDER if k in products}
+        po = _fill_products(PlanOut(), {k: ptr(out[k]) for k in out})
+        out["trunk"] = np.zeros((B, n_cycles), _capi.TRUNK_RECORD_DTYPE)
+        to = _capi.TrunkOut(ptr(out["trunk"]), None)
+        if summary:
+            out["trunk_summary"] = np.zeros(B, _capi.TRUNK_SUMMARY_DTYPE)
+            to.summary = ptr(out["trunk_summary"])
+        tl = _trunk_limits(limits)
+        self._check(self._lib.fpe_trunk_plan(self._h, ptr(self.params), C.byref(tl) if tl is not None else None, ptr(poses),
+                                             ptr(_strides_for(strides, B)) if strides is not None else None, B, int(n_cycles),
+                                             C.byref(po), C.byref(to)))
+        return out
+
+    def trunk_plan_device(self, d_nominal_ptr, d_cycle_ok_ptr, B, n_cycles, d_records_ptr=0, d_summary_ptr=0, limits=None, stream=0):
+        """fpe_trunk_plan_device: DEVICE pointers to a plan's nominal and cycle_ok products as a plan call on `stream` left them and
+        the outputs (0 = not wanted)."""
+        po = _fill_products(PlanOut(), {"nominal": d_nominal_ptr, "cycle_ok": d_cycle_ok_ptr})
+        to = _capi.TrunkOut(d_records_ptr or None, d_summary_ptr or None)
+        tl = _trunk_limits(limits)
+        self._check(self._lib.fpe_trunk_plan_device(self._h, ptr(self.params), C.byref(tl) if tl is not None else None, C.byref(po),
+                                                    int(B), int(n_cycles), C.byref(to), C.c_void_p(stream or 0)))
 
     # ---- the dense maps as grid_map message layers (fpe_export_layers*) ----------------------------------------------------
     def _layer_request(self, names, dsts, snap_search_radius, snap_polygon, centroid_search_radius):
