@@ -1220,6 +1220,113 @@ int fpe_trunk_plan_device(fpe_handle h, const fpe_params* params, const fpe_trun
 int fpe_trunk_plan(fpe_handle h, const fpe_params* params, const fpe_trunk_limits* limits, const fpe_pose* poses,
                    const fpe_stride* strides, int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_trunk_out* out);
 
+/* ---- edge margin: the distance from cells and planned footholds to bad ground ---------------------------------------------------------
+ * BUILD-DEFINED (the reference answers yes or no against the foot disc: a foothold whose disc just passes on a stair nose and one in the
+ * middle of a tread look alike).  Everything is an integer, computed on the snapshot current at entry from its bit planes; all indices
+ * are canonical (i, j).  For the threshold pair (thrDefault, thrCandidate) = (params->defaultFootholdThreshold,
+ * params->candidateFootholdThreshold) and the f32 traversability t of a cell, the classes are
+ *   FPE_MARGIN_LOW_CANDIDATE  the cell is in the map and  isfinite(t) && t < thrCandidate   (plane C: build_bitmap_kernel's compare)
+ *   FPE_MARGIN_LOW_DEFAULT    the cell is in the map and  isfinite(t) && t < thrDefault     (plane Df)
+ *   FPE_MARGIN_UNKNOWN        the cell is in the map and  !isfinite(t)                      (plane F clear: NaN, +infinity, -infinity)
+ *   FPE_MARGIN_OFF_MAP        i < 0, i >= rows, j < 0 or j >= cols
+ * so a -infinity cell is UNKNOWN and belongs to no LOW class (the plane D, which holds the raw compare, is not read).  `classes` is a
+ * non-empty subset of the four bits; a cell is BAD iff it belongs to a selected class.
+ * Margin of a cell.  reach = mp.reach_cells, 1 <= reach <= FPE_MARGIN_MAX_CELLS.  For ANY integer cell (i, j), in the map or not:
+ *   dist_sq   min { di^2 + dj^2 : di^2 + dj^2 <= reach^2 and cell (i + di, j + dj) is BAD };  FPE_MARGIN_NONE when the set is empty;
+ *   (di, dj)  the offset attaining it; among several the lowest di, then the lowest dj;  (0, 0) when dist_sq is NONE.
+ * No square root, no float: there is no tolerance anywhere.  The metric margin is res * sqrt(dist_sq); only a caller computes it.
+ * Limit.  min_margin is a double in metres, finite and >= 0.  With MapGeom g (csrc/fpe_gridmath.hpp) and res2 = g.res * g.res formed
+ * once, in f64, a record is UNDER iff
+ *     dist_sq != FPE_MARGIN_NONE  &&  double(dist_sq) * res2 < min_margin * min_margin
+ * so min_margin = 0 sets no bit.  A limit the reach cannot decide is refused with FPE_E_UNSUPPORTED:
+ *     min_margin * min_margin > double(reach * reach) * res2
+ * Records.  A record of cell (row, col): dist_sq, di, dj as above and flags FOOTHOLD | CENTRE_OFF_MAP (the cell itself is not in the
+ * map) | NO_BAD (dist_sq is NONE) | UNDER.  A cell with row < -FPE_PACKED_BIAS, row >= rows + FPE_PACKED_BIAS, or the same for col (a
+ * default hit carries getIndex(centre), up to a foot radius outside the map; nothing the planner produces lies farther out) is refused:
+ * the host forms return FPE_E_INVALID_ARG and write nothing; the device forms cannot look at the values and give a record with
+ * flags = FPE_MARGIN_REFUSED and every other field zero (the plan-bound form: but the two ids), decided by the same expression.
+ * Forms.  Dense (fpe_margin_map*): dist_sq and / or nearest = (di, dj) for every cell of a region, roi as fpe_foothold_map.  Open-loop
+ * (fpe_margin_cells*): n arbitrary cells; foot_id and gait_cycle_id are 0.  Plan-bound (fpe_margin_plan_device): reads
+ * d_products->nominal [B, n_cycles, 4] (required) only; record (b, g, leg) at (b * n_cycles + g) * 4 + leg describes a foothold iff
+ * nominal[b, g, leg].valid != 0, its cell is that record's (row, col), and it equals, bit for bit, the open-loop record of that cell
+ * with foot_id = leg and gait_cycle_id = g filled in; the record of an invalid foothold is all zero but those two ids.  Note that the
+ * margin is that of the record's CELL: up to half a cell off the continuous centre of a default hit.
+ * The per-pose summary runs over the pose's records with FOOTHOLD set (a REFUSED record has none): min_dist_sq, NONE taking part as
+ * 65535 (65535 when there is no foothold), min_cycle / min_leg the lowest (g, leg) attaining it (255, 255 without a foothold),
+ * n_footholds, n_under (UNDER), n_off_map (CENTRE_OFF_MAP), first_under_cycle the lowest g of an UNDER record (255: none).
+ * Conventions as fpe_trunk_*: host forms are synchronous; device forms are asynchronous on `stream` and see the snapshot current at
+ * entry (the pair's bit planes are built on first use, on that stream).  A NULL `mp` is fpe_margin_params_defaults: classes
+ * LOW_CANDIDATE | UNKNOWN | OFF_MAP, reach 8, min_margin 0.
+ * Refusals (a refused call writes nothing).  FPE_E_INVALID_ARG: a null argument, n or B < 1, n_cycles outside 1..255 (or
+ * B * n_cycles * 4 > 2^30), classes outside 1..15, reach_cells outside 1..FPE_MARGIN_MAX_CELLS, a reserved word that is not 0, a
+ * min_margin that is NaN, infinite or negative, a bad roi, both dense outputs NULL, both plan-bound outputs NULL.  FPE_E_NO_MAP.
+ * FPE_E_UNSUPPORTED: the undecidable limit above.  fpe_margin_plan also refuses what fpe_plan refuses.
+ * No atomics anywhere: every byte is a function of the inputs alone.  Out of scope: a margin term in fpe_plan_rank* / fpe_plan_beam*;
+ * a margin layer in fpe_export_layers (its request struct has fixed arrays: a new layer would change the ABI); fpe_multi_*, the service
+ * calls, the opt and centroid tracks; sub-cell positions (see the note above); reaches beyond FPE_MARGIN_MAX_CELLS cells. */
+#define FPE_MARGIN_LOW_CANDIDATE 1u
+#define FPE_MARGIN_LOW_DEFAULT   2u
+#define FPE_MARGIN_UNKNOWN       4u
+#define FPE_MARGIN_OFF_MAP       8u
+#define FPE_MARGIN_MAX_CELLS     31
+#define FPE_MARGIN_NONE          65535u
+#define FPE_MARGIN_FOOTHOLD       1u   /* the record describes a foothold; open-loop records always set it */
+#define FPE_MARGIN_CENTRE_OFF_MAP 2u   /* the queried cell is not in the map */
+#define FPE_MARGIN_NO_BAD         4u   /* dist_sq is FPE_MARGIN_NONE */
+#define FPE_MARGIN_UNDER          8u   /* below mp.min_margin, by the expression above */
+#define FPE_MARGIN_REFUSED        128u /* device forms: a cell the host forms refuse; every other field zero, FOOTHOLD not set */
+typedef struct fpe_margin_params {    /* 24 bytes */
+    int32_t classes;       /* FPE_MARGIN_* class bits, 1..15 */
+    int32_t reach_cells;   /* 1..FPE_MARGIN_MAX_CELLS */
+    double  min_margin;    /* metres; finite, >= 0; 0: no limit */
+    int32_t reserved[2];   /* 0 */
+} fpe_margin_params;
+typedef struct fpe_margin_map_out {   /* 16 bytes; either may be NULL, not both */
+    uint16_t* dist_sq;     /* [n_rows * n_cols] */
+    int8_t*   nearest;     /* [n_rows * n_cols * 2] di, dj */
+} fpe_margin_map_out;
+typedef struct fpe_margin_query {     /* 8 bytes */
+    int32_t row, col;
+} fpe_margin_query;
+typedef struct fpe_margin_record {    /* 8 bytes */
+    uint16_t dist_sq;
+    int8_t   di, dj;
+    uint8_t  flags;         /* FPE_MARGIN_FOOTHOLD .. FPE_MARGIN_REFUSED */
+    uint8_t  foot_id;       /* plan-bound: leg; open-loop: 0 */
+    uint8_t  gait_cycle_id; /* plan-bound: g; open-loop: 0 */
+    uint8_t  pad;
+} fpe_margin_record;
+typedef struct fpe_margin_summary {   /* 16 bytes; element b belongs to pose b */
+    uint16_t min_dist_sq;
+    uint8_t  min_cycle, min_leg;
+    uint16_t n_footholds, n_under, n_off_map;
+    uint8_t  first_under_cycle;  /* 255: none */
+    uint8_t  pad[5];
+} fpe_margin_summary;
+typedef struct fpe_margin_out {       /* 16 bytes; either pointer may be NULL, not both */
+    fpe_margin_record*  records;  /* [B * n_cycles * 4] */
+    fpe_margin_summary* summary;  /* [B] */
+} fpe_margin_out;
+int fpe_margin_params_defaults(fpe_margin_params* out);
+/* Dense: every cell of the region (roi NULL: the whole map).  Host arrays, synchronous / device arrays, asynchronous on `stream`. */
+int fpe_margin_map(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const int32_t roi[4], const fpe_margin_map_out* out);
+int fpe_margin_map_device(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const int32_t roi[4],
+                          const fpe_margin_map_out* d_out, void* stream);
+/* Open-loop: n arbitrary cells. */
+int fpe_margin_cells(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_margin_query* queries, int32_t n,
+                     fpe_margin_record* out);
+int fpe_margin_cells_device(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_margin_query* d_queries,
+                            int32_t n, fpe_margin_record* d_out, void* stream);
+/* Plan-bound, device arrays: reads d_products->nominal (required) as a plan call on `stream` left it; `d_products` and `d_out`
+ * themselves are host structs of device pointers.  Asynchronous on `stream`, behind whatever filled the product there. */
+int fpe_margin_plan_device(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_plan_out* d_products, int32_t B,
+                           int32_t n_cycles, const fpe_margin_out* d_out, void* stream);
+/* Plan and check in one call, host arrays, synchronous: plans exactly as fpe_plan (strides NULL) or fpe_plan_strides would, checks the
+ * plan on the same stream with no host synchronisation in between, on ONE snapshot, and returns the requested products (NULL: none)
+ * and the margin outputs. */
+int fpe_margin_plan(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_pose* poses, const fpe_stride* strides,
+                    int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_margin_out* out);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

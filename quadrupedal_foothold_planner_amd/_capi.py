@@ -351,6 +351,38 @@ class TrunkOut(C.Structure):
     _fields_ = [("records", C.c_void_p), ("summary", C.c_void_p)]
 
 
+# FPE_MARGIN_* class bits of fpe_margin_params.classes, flag bits of fpe_margin_record.flags, and the bounds of a margin call
+MARGIN_LOW_CANDIDATE, MARGIN_LOW_DEFAULT, MARGIN_UNKNOWN, MARGIN_OFF_MAP = 1, 2, 4, 8
+MARGIN_FOOTHOLD, MARGIN_CENTRE_OFF_MAP, MARGIN_NO_BAD, MARGIN_UNDER, MARGIN_REFUSED = 1, 2, 4, 8, 128
+MARGIN_MAX_CELLS = 31
+MARGIN_NONE = 65535
+# fpe_margin_query: one cell; fpe_margin_record: its margin; fpe_margin_summary: one pose's records reduced
+MARGIN_QUERY_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4")], align=True)
+MARGIN_RECORD_DTYPE = np.dtype(
+    [("dist_sq", "<u2"), ("di", "i1"), ("dj", "i1"), ("flags", "u1"), ("foot_id", "u1"), ("gait_cycle_id", "u1"), ("pad", "u1")], align=True)
+MARGIN_SUMMARY_DTYPE = np.dtype(
+    [("min_dist_sq", "<u2"), ("min_cycle", "u1"), ("min_leg", "u1"), ("n_footholds", "<u2"), ("n_under", "<u2"), ("n_off_map", "<u2"),
+     ("first_under_cycle", "u1"), ("pad", "u1", (5,))],
+    align=True,
+)
+assert (MARGIN_QUERY_DTYPE.itemsize, MARGIN_RECORD_DTYPE.itemsize, MARGIN_SUMMARY_DTYPE.itemsize) == (8, 8, 16)
+
+
+class MarginParams(C.Structure):
+    """fpe_margin_params: the class bits that make a cell BAD, the reach in cells and the limit behind UNDER (0: none)."""
+    _fields_ = [("classes", C.c_int32), ("reach_cells", C.c_int32), ("min_margin", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class MarginMapOut(C.Structure):
+    """fpe_margin_map_out: products of a dense margin call (either pointer may be NULL, not both)."""
+    _fields_ = [("dist_sq", C.c_void_p), ("nearest", C.c_void_p)]
+
+
+class MarginOut(C.Structure):
+    """fpe_margin_out: outputs of a plan-bound margin call (either pointer may be NULL, not both)."""
+    _fields_ = [("records", C.c_void_p), ("summary", C.c_void_p)]
+
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -368,6 +400,8 @@ STRUCTS = {
     "fpe_swing_record": SWING_RECORD_DTYPE, "fpe_swing_summary": SWING_SUMMARY_DTYPE, "fpe_swing_out": SwingOut,
     "fpe_trunk_query": TRUNK_QUERY_DTYPE, "fpe_trunk_limits": TrunkLimits, "fpe_trunk_record": TRUNK_RECORD_DTYPE,
     "fpe_trunk_summary": TRUNK_SUMMARY_DTYPE, "fpe_trunk_out": TrunkOut,
+    "fpe_margin_params": MarginParams, "fpe_margin_map_out": MarginMapOut, "fpe_margin_query": MARGIN_QUERY_DTYPE,
+    "fpe_margin_record": MARGIN_RECORD_DTYPE, "fpe_margin_summary": MARGIN_SUMMARY_DTYPE, "fpe_margin_out": MarginOut,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -464,6 +498,13 @@ PROTOTYPES = {
     "fpe_trunk_stances_device": (cint, [vp, vp, P(TrunkLimits), vp, i32, vp, vp]),
     "fpe_trunk_plan_device": (cint, [vp, vp, P(TrunkLimits), P(PlanOut), i32, i32, P(TrunkOut), vp]),
     "fpe_trunk_plan": (cint, [vp, vp, P(TrunkLimits), vp, vp, i32, i32, P(PlanOut), P(TrunkOut)]),
+    "fpe_margin_params_defaults": (cint, [P(MarginParams)]),
+    "fpe_margin_map": (cint, [vp, vp, P(MarginParams), vp, P(MarginMapOut)]),
+    "fpe_margin_map_device": (cint, [vp, vp, P(MarginParams), vp, P(MarginMapOut), vp]),
+    "fpe_margin_cells": (cint, [vp, vp, P(MarginParams), vp, i32, vp]),
+    "fpe_margin_cells_device": (cint, [vp, vp, P(MarginParams), vp, i32, vp, vp]),
+    "fpe_margin_plan_device": (cint, [vp, vp, P(MarginParams), P(PlanOut), i32, i32, P(MarginOut), vp]),
+    "fpe_margin_plan": (cint, [vp, vp, P(MarginParams), vp, vp, i32, i32, P(PlanOut), P(MarginOut)]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

@@ -3110,6 +3110,244 @@ int fpe_trunk_plan(fpe_handle h, const fpe_params* params, const fpe_trunk_limit
     return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
 }
 
+// ---- edge margin (fpe_margin_*; kernels: fpe_margin.hpp) -----------------------------------------------------------------------
+int fpe_margin_params_defaults(fpe_margin_params* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->classes = FPE_MARGIN_LOW_CANDIDATE | FPE_MARGIN_UNKNOWN | FPE_MARGIN_OFF_MAP;
+    out->reach_cells = 8;
+    return FPE_OK;
+}
+
+namespace {
+// The parameters of a margin call (mp NULL: the defaults), checked; what needs no map.
+int margin_params(const fpe_margin_params* mp, fpe_margin_params& r) {
+    if (!mp) {
+        fpe_margin_params_defaults(&r);
+        return FPE_OK;
+    }
+    r = *mp;
+    if (r.classes < 1 || r.classes > 15) return fail(FPE_E_INVALID_ARG, "fpe_margin_params.classes must be in 1..15");
+    if (r.reach_cells < 1 || r.reach_cells > FPE_MARGIN_MAX_CELLS)
+        return fail(FPE_E_INVALID_ARG, "fpe_margin_params.reach_cells must be in 1..FPE_MARGIN_MAX_CELLS");
+    if (r.reserved[0] != 0 || r.reserved[1] != 0) return fail(FPE_E_INVALID_ARG, "fpe_margin_params.reserved must be 0");
+    if (!std::isfinite(r.min_margin) || r.min_margin < 0.0) return fail(FPE_E_INVALID_ARG, "min_margin must be finite and >= 0");
+    return FPE_OK;
+}
+// What needs the call's snapshot: the limit against the reach, and the kernels' constants
+int margin_consts(const fpe_margin_params& r, const fpe::MapGeom& g, fpe::MarginConsts& mc) {
+    const double res2 = g.res * g.res, mm2 = r.min_margin * r.min_margin;
+    if (mm2 > static_cast<double>(r.reach_cells * r.reach_cells) * res2)
+        return fail(FPE_E_UNSUPPORTED, "min_margin lies beyond reach_cells at this resolution: the reach cannot decide the limit");
+    mc = fpe::MarginConsts{r.classes, r.reach_cells, res2, mm2};
+    return FPE_OK;
+}
+int check_margin_shape(int32_t B, int32_t n_cycles) {
+    if (B <= 0 || n_cycles <= 0 || n_cycles > 255) return fail(FPE_E_INVALID_ARG, "B and n_cycles must be in [1, ..] / [1, 255]");
+    if (static_cast<int64_t>(B) * n_cycles * 4 > (1 << 30)) return fail(FPE_E_INVALID_ARG, "B * n_cycles * 4 must not exceed 2^30");
+    return FPE_OK;
+}
+// The planes of the call's threshold pair on cp.snap, built on `stream` on first use (the lookup of prepare_call)
+int margin_planes(const fpe_params& params, CallPlan& cp, hipStream_t stream) {
+    return acquire_mask(*cp.snap, params.defaultFootholdThreshold, params.candidateFootholdThreshold, stream, cp);
+}
+// Every form but fpe_margin_plan: the checks, the snapshot current at entry, (dense: the region,) the constants, the planes; `stream`
+// ordered after the snapshot's upload and the planes' build.  queries (host; may be null): the n cells of a host form, each checked
+// against the snapshot's size.  Nothing is queued ahead of a refusal.
+int prepare_margin(fpe_engine* h, const fpe_params* params, const fpe_margin_params* mp, const int32_t roi[4], fpe::FootmapRoi* r,
+                   CallPlan& cp, fpe::MarginConsts& mc, hipStream_t stream, const fpe_margin_query* queries = nullptr, int32_t n = 0) {
+    if (!h || !params) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    fpe_margin_params q;
+    int rc = margin_params(mp, q);
+    if (rc != FPE_OK) return rc;
+    rc = fpe::validate_params(*params);
+    if (rc != FPE_OK) return fail(rc, "non-finite or negative parameter");
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        cp.snap = h->map;
+    }
+    if (!cp.snap) return fail(FPE_E_NO_MAP, "no map uploaded");
+    if (r) {
+        rc = resolve_roi(roi, cp.snap->g, *r);
+        if (rc != FPE_OK) return rc;
+    }
+    rc = margin_consts(q, cp.snap->g, mc);
+    if (rc != FPE_OK) return rc;
+    for (int32_t k = 0; queries && k < n; ++k)
+        if (fpe::margin_query_refused(cp.snap->g.rows, cp.snap->g.cols, queries[k]))
+            return fail(FPE_E_INVALID_ARG, "a query cell lies FPE_PACKED_BIAS cells or more outside the map");
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cp.snap->wait_ready(stream));
+    return margin_planes(*params, cp, stream);
+}
+}  // namespace
+
+int fpe_margin_map_device(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const int32_t roi[4],
+                          const fpe_margin_map_out* d_out, void* stream) {
+    if (!d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!d_out->dist_sq && !d_out->nearest) return fail(FPE_E_INVALID_ARG, "no output requested");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    fpe::FootmapRoi r{};
+    fpe::MarginConsts mc;
+    const int rc = prepare_margin(h, params, mp, roi, &r, cp, mc, st);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    FPE_HIP(fpe::launch_margin_map(cp.bits, cp.snap->g, mc, r, d_out->dist_sq, d_out->nearest, st));
+    return FPE_OK;
+}
+
+int fpe_margin_map(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const int32_t roi[4], const fpe_margin_map_out* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!out->dist_sq && !out->nearest) return fail(FPE_E_INVALID_ARG, "no output requested");
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(0));  // the stream
+    fpe::FootmapRoi r{};
+    fpe::MarginConsts mc;
+    const int rc = prepare_margin(h, params, mp, roi, &r, cp, mc, cx.stream);
+    if (rc != FPE_OK) return rc;
+    const size_t n = static_cast<size_t>(r.nr) * r.nc;
+    const HostProduct prod[2] = {{out->dist_sq, n * sizeof(uint16_t)}, {out->nearest, n * 2}};
+    return stage_products(cx, prod, [&](unsigned char* const* d, hipStream_t s) {
+        return fpe::launch_margin_map(cp.bits, cp.snap->g, mc, r, reinterpret_cast<uint16_t*>(d[0]), reinterpret_cast<int8_t*>(d[1]), s);
+    });
+}
+
+int fpe_margin_cells_device(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_margin_query* d_queries,
+                            int32_t n, fpe_margin_record* d_out, void* stream) {
+    if (!d_queries || !d_out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    fpe::MarginConsts mc;
+    const int rc = prepare_margin(h, params, mp, nullptr, nullptr, cp, mc, st);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    FPE_HIP(fpe::launch_margin_cells(cp.bits, cp.snap->g, mc, d_queries, n, d_out, st));
+    return FPE_OK;
+}
+
+int fpe_margin_cells(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_margin_query* queries, int32_t n,
+                     fpe_margin_record* out) {
+    if (!queries || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (n <= 0) return fail(FPE_E_INVALID_ARG, "n must be positive");
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    // n queries up, n records back, both through the context's arenas (as query_round_trip, behind this family's prepare)
+    const size_t nQ = static_cast<size_t>(n) * sizeof(fpe_margin_query), nO = static_cast<size_t>(n) * sizeof(fpe_margin_record);
+    const size_t szQ = align256(nQ);
+    HostCall hc(h);
+    CallPlan& cp = hc.cp;
+    CallCtx& cx = hc.cx;
+    FPE_HIP(hipSetDevice(h->device));
+    FPE_HIP(cx.reserve(szQ + align256(nO)));
+    fpe::MarginConsts mc;
+    cx.inFlight = true;
+    const int rc = prepare_margin(h, params, mp, nullptr, nullptr, cp, mc, cx.stream, queries, n);
+    if (rc != FPE_OK) return rc;
+    std::memcpy(cx.pinned, queries, nQ);
+    FPE_HIP(hipMemcpyAsync(cx.dev, cx.pinned, nQ, hipMemcpyHostToDevice, cx.stream));
+    FPE_HIP(fpe::launch_margin_cells(cp.bits, cp.snap->g, mc, reinterpret_cast<const fpe_margin_query*>(cx.dev), n,
+                                     reinterpret_cast<fpe_margin_record*>(cx.dev + szQ), cx.stream));
+    FPE_HIP(hipMemcpyAsync(cx.pinned + szQ, cx.dev + szQ, nO, hipMemcpyDeviceToHost, cx.stream));
+    FPE_HIP(hipStreamSynchronize(cx.stream));
+    cx.inFlight = false;
+    std::memcpy(out, cx.pinned + szQ, nO);
+    return FPE_OK;
+}
+
+int fpe_margin_plan_device(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_plan_out* d_products, int32_t B,
+                           int32_t n_cycles, const fpe_margin_out* d_out, void* stream) {
+    if (!d_products || !d_out || !d_products->nominal) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!d_out->records && !d_out->summary) return fail(FPE_E_INVALID_ARG, "no margin output requested");
+    int rc = check_margin_shape(B, n_cycles);
+    if (rc != FPE_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    fpe::MarginConsts mc;
+    rc = prepare_margin(h, params, mp, nullptr, nullptr, cp, mc, st);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    if (d_out->records) {
+        FPE_HIP(fpe::launch_margin_plan(cp.bits, cp.snap->g, mc, d_products->nominal, B, n_cycles, d_out->records, d_out->summary, st));
+        return FPE_OK;
+    }
+    // the summary alone: its records live in stream-ordered scratch
+    return with_stream_scratch(static_cast<size_t>(B) * n_cycles * 4 * sizeof(fpe_margin_record), st, [&](unsigned char* scratch) {
+        FPE_HIP(fpe::launch_margin_plan(cp.bits, cp.snap->g, mc, d_products->nominal, B, n_cycles,
+                                        reinterpret_cast<fpe_margin_record*>(scratch), d_out->summary, st));
+        return static_cast<int>(FPE_OK);
+    });
+}
+
+namespace {
+// Where everything a plan-and-margin call touches on the device lives, as TrunkLayout: the plan's products — the requested ones in
+// the output block, what the check reads besides (nominal) in scratch, null for the rest — then the records (scratch when only the
+// summary is wanted) and the summary.
+struct MarginLayout {
+    int32_t B, n;
+    fpe_plan_out plan;
+    fpe_margin_record* records;
+    fpe_margin_summary* summary;
+};
+void margin_layout(MarginLayout& L, ArenaCursor& A, const fpe_plan_out* want, const fpe_margin_out& mo) {
+    const bool reads[kPlanProducts] = {true, false, false, false, false, false, false, false};  // margin_cells_kernel<true>'s input
+    const size_t B = static_cast<size_t>(L.B), n = static_cast<size_t>(L.n);
+    void* const* wanted = want ? slots(*want) : nullptr;
+    for (int k = 0; k < kPlanProducts; ++k)
+        slots(L.plan)[k] = (wanted && wanted[k]) ? A.out(wanted[k], product_bytes(k, B, n)) : (reads[k] ? A.take(product_bytes(k, B, n)) : nullptr);
+    const size_t szRec = B * n * 4 * sizeof(fpe_margin_record);
+    L.records = static_cast<fpe_margin_record*>(mo.records ? A.out(mo.records, szRec) : A.take(szRec));
+    L.summary = static_cast<fpe_margin_summary*>(mo.summary ? A.out(mo.summary, B * sizeof(fpe_margin_summary)) : nullptr);
+}
+}  // namespace
+
+int fpe_margin_plan(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_pose* poses, const fpe_stride* strides,
+                    int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_margin_out* out) {
+    if (!h || !params || !poses || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!out->records && !out->summary) return fail(FPE_E_INVALID_ARG, "no margin output requested");
+    fpe_margin_params q;
+    int rc = check_margin_shape(B, n_cycles);
+    if (rc == FPE_OK) rc = margin_params(mp, q);
+    if (rc != FPE_OK) return rc;
+    float maxRadius = 0.0f;
+    rc = check_host_poses(poses, B, maxRadius);
+    if (rc == FPE_OK) rc = check_host_strides(strides, B);
+    if (rc != FPE_OK) return rc;
+    MarginLayout L{};
+    L.B = B, L.n = n_cycles;
+    ArenaCursor sizes;
+    margin_layout(L, sizes, products, *out);
+    // both arenas: [poses (| strides) | outputs | scratch (device arena only)]; the inputs are read from the pinned arena, as in fpe_plan
+    const size_t oStrides = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
+    const size_t szIn = oStrides + (strides ? align256(static_cast<size_t>(B) * sizeof(fpe_stride)) : 0);
+    CallPlan planes;  // the margin's planes: declared ahead of the lease, so released behind it (HostCall)
+    HostCall hc(h);
+    CallCtx& cx = hc.cx;
+    unsigned char* in = nullptr;
+    rc = open_batch_call(h, hc, params, maxRadius, szIn + sizes.outBytes + sizes.scratchBytes, products && products->selected_packed,
+                         strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain, in);
+    fpe::MarginConsts mc;
+    if (rc == FPE_OK) rc = margin_consts(q, hc.cp.snap->g, mc);
+    if (rc != FPE_OK) return rc;
+    // the pair's planes by the same lookup the plan made (it finds the plan's set where the plan launches with one): one snapshot
+    planes.snap = hc.cp.snap;
+    rc = margin_planes(*params, planes, cx.stream);
+    if (rc != FPE_OK) return rc;
+    stage_batch_inputs(cx.pinned, oStrides, poses, strides, B);
+    ArenaCursor A{cx.dev + szIn + sizes.outBytes, cx.dev + szIn, szIn};
+    margin_layout(L, A, products, *out);
+    // the plan through the plan runner, then the check behind it on the same stream and the same snapshot
+    rc = launch_plan(h, hc.cp, reinterpret_cast<const fpe_pose*>(in), B, n_cycles, L.plan, cx.stream,
+                     {strides ? reinterpret_cast<const fpe_stride*>(in + oStrides) : nullptr});
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(fpe::launch_margin_plan(planes.bits, planes.snap->g, mc, L.plan.nominal, B, n_cycles, L.records, L.summary, cx.stream));
+    return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
+}
+
 int fpe_last_service_gate(fpe_handle h, fpe_service_gate* out) {
     if (!h || !out) return fail(FPE_E_INVALID_ARG, "null argument");
     if (g_gateEngine != h) return fail(FPE_E_INVALID_ARG, "no fpe_plan_service* call was made with this engine on this thread");

@@ -388,4 +388,23 @@ hipError_t launch_trunk_stances(const DevMap& m, const TrunkConsts& tc, const fp
 hipError_t launch_trunk_plan(const DevMap& m, const TrunkConsts& tc, const fpe_foothold* d_nominal, const uint8_t* d_cycleOk, int B,
                              int nCycles, fpe_trunk_record* d_records, fpe_trunk_summary* d_summary, hipStream_t stream);
 
+// ---- edge margin (fpe_margin.hpp) ----------------------------------------------------------------------------
+// The parameters of a call as the kernels take them, by value, checked by the host: the class bits (1..15), the reach in cells
+// (1..FPE_MARGIN_MAX_CELLS), and the two sides of the limit's comparison, each formed once in f64 (res2 = g.res * g.res,
+// minMargin2 = min_margin * min_margin).
+struct MarginConsts {
+    int32_t classes, reach;
+    double res2, minMargin2;
+};
+// Whether a host form refuses the cell: the expression the kernel answers FPE_MARGIN_REFUSED by
+bool margin_query_refused(int rows, int cols, const fpe_margin_query& q);
+int margin_lanes_log2(int reach);  // lanes per query of margin_cells_kernel, as a power of two
+hipError_t launch_margin_map(const BitMap& bm, const MapGeom& g, const MarginConsts& mc, const FootmapRoi& roi, uint16_t* d_distSq,
+                             int8_t* d_nearest, hipStream_t stream);
+hipError_t launch_margin_cells(const BitMap& bm, const MapGeom& g, const MarginConsts& mc, const fpe_margin_query* d_q, int n,
+                               fpe_margin_record* d_out, hipStream_t stream);
+// The footholds a plan's nominal product holds: B * nCycles * 4 records (required) and, where d_summary is given, one summary per pose
+hipError_t launch_margin_plan(const BitMap& bm, const MapGeom& g, const MarginConsts& mc, const fpe_foothold* d_nominal, int B, int nCycles,
+                              fpe_margin_record* d_records, fpe_margin_summary* d_summary, hipStream_t stream);
+
 }  // namespace fpe

@@ -146,6 +146,25 @@ def _trunk_limits(limits):
     return make_trunk_limits(**dict(limits))
 
 
+def make_margin_params(classes=_capi.MARGIN_LOW_CANDIDATE | _capi.MARGIN_UNKNOWN | _capi.MARGIN_OFF_MAP, reach_cells=8, min_margin=0.0):
+    """An fpe_margin_params block: the FPE_MARGIN_* class bits that make a cell BAD, the reach in cells (1..31) and the limit in metres
+    behind UNDER (0: no limit).  Pure host arithmetic: no engine, no GPU."""
+    return _capi.MarginParams(int(classes), int(reach_cells), float(min_margin), (C.c_int32 * 2)(0, 0))
+
+
+def _margin_params(mp):
+    """None (the engine's defaults), a MarginParams block, or a dict of make_margin_params' keywords."""
+    if mp is None or isinstance(mp, _capi.MarginParams):
+        return mp
+    return make_margin_params(**dict(mp))
+
+
+def margin_metres(dist_sq, resolution):
+    """The metric margin res * sqrt(dist_sq) of dist_sq values (any shape) as float64; +infinity where dist_sq is FPE_MARGIN_NONE."""
+    d = np.asarray(dist_sq)
+    return np.where(d == _capi.MARGIN_NONE, np.inf, float(resolution) * np.sqrt(d.astype(np.float64)))
+
+
 # fpe_set_tuning's knobs whose engine default is not 0 (tuning() restores these after a with-block)
 TUNING_DEFAULTS = {"service_opt_gate": 2, "service_overlap": 1, "service_poll": 1}
 
@@ -670,7 +689,8 @@ class FootholdPlanner(_Handle):
     # behind [n_rows, n_cols]
     _DENSE = {"foothold-map": (FootholdMapOut, {"flags": (np.uint8, ()), "height": (np.float32, ())}),
               "foothold-snap": (FootholdSnapOut, {"offset": (np.int8, (2,)), "source": (np.uint8, ()), "z": (np.float32, ())}),
-              "centroid-map": (CentroidMapOut, {"code": (np.uint8, ()), "offset": (np.int8, (2,)), "z": (np.float32, ())})}
+              "centroid-map": (CentroidMapOut, {"code": (np.uint8, ()), "offset": (np.int8, (2,)), "z": (np.float32, ())}),
+              "margin-map": (_capi.MarginMapOut, {"dist_sq": (np.uint16, ()), "nearest": (np.int8, (2,))})}
 
     @classmethod
     def _dense_out(cls, what, **addresses):
@@ -867,6 +887,76 @@ class FootholdPlanner(_Handle):
         tl = _trunk_limits(limits)
         self._check(self._lib.fpe_trunk_plan_device(self._h, ptr(self.params), C.byref(tl) if tl is not None else None, C.byref(po),
                                                     int(B), int(n_cycles), C.byref(to), C.c_void_p(stream or 0)))
+
+    # ---- edge margin: distance from cells and planned footholds to bad ground (build-defined: fpe_margin_*) ---------------
+    def margin_map(self, mp=None, roi=None, products=("dist_sq", "nearest")):
+        """fpe_margin_map on the current map: {"dist_sq": uint16 [n_rows, n_cols] (MARGIN_NONE: no bad cell within reach), "nearest":
+        int8 [n_rows, n_cols, 2] (di, dj)} for the requested products.  `mp`: None (classes candidate | unknown | off-map, reach 8, no
+        limit), make_margin_params(...) or a dict of its keywords; roi as in foothold_map."""
+        r, out, mo = self._dense_outputs("margin-map", roi, products)
+        m = _margin_params(mp)
+        self._check(self._lib.fpe_margin_map(self._h, ptr(self.params), C.byref(m) if m is not None else None, ptr(r), C.byref(mo)))
+        return out
+
+    def margin_map_device(self, d_dist_sq_ptr, d_nearest_ptr, mp=None, roi=None, stream=0):
+        """Device form: DEVICE pointers (0 = product not wanted), asynchronous on `stream`."""
+        r = self._roi(roi)
+        mo = self._dense_out("margin-map", dist_sq=d_dist_sq_ptr, nearest=d_nearest_ptr)
+        m = _margin_params(mp)
+        self._check(self._lib.fpe_margin_map_device(self._h, ptr(self.params), C.byref(m) if m is not None else None, ptr(r), C.byref(mo),
+                                                    C.c_void_p(stream or 0)))
+
+    def margin_cells(self, cells, mp=None):
+        """fpe_margin_cells: one MARGIN_RECORD_DTYPE record per cell of `cells` ([n, 2] canonical (row, col), in the map or not, or a
+        MARGIN_QUERY_DTYPE array) on the current map."""
+        if not (isinstance(cells, np.ndarray) and cells.dtype == _capi.MARGIN_QUERY_DTYPE):
+            rc = np.asarray(cells, dtype=np.int32).reshape(-1, 2)
+            cells = np.zeros(rc.shape[0], dtype=_capi.MARGIN_QUERY_DTYPE)
+            cells["row"], cells["col"] = rc[:, 0], rc[:, 1]
+        queries = np.ascontiguousarray(cells).reshape(-1)
+        out = np.zeros(queries.shape[0], dtype=_capi.MARGIN_RECORD_DTYPE)
+        m = _margin_params(mp)
+        self._check(self._lib.fpe_margin_cells(self._h, ptr(self.params), C.byref(m) if m is not None else None, ptr(queries),
+                                               queries.shape[0], ptr(out)))
+        return out
+
+    def margin_cells_device(self, d_queries_ptr, n, d_out_ptr, mp=None, stream=0):
+        """Device form: DEVICE pointers to n queries and n records, asynchronous on `stream`."""
+        m = _margin_params(mp)
+        self._check(self._lib.fpe_margin_cells_device(self._h, ptr(self.params), C.byref(m) if m is not None else None,
+                                                      C.c_void_p(d_queries_ptr), int(n), C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)))
+
+    def margin_plan(self, poses, n_cycles, mp=None, strides=None, products=("nominal",), summary=True):
+        """fpe_margin_plan with host buffers: plans the batch as plan() does (strides: as there) and measures the margin of every
+        planned foothold's cell in the same call.  Returns the requested plan products plus "margin": MARGIN_RECORD_DTYPE
+        [B, n_cycles, 4] and (summary=True) "margin_summary": MARGIN_SUMMARY_DTYPE [B]."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        B = poses.shape[0]
+        unknown = set(products) - set(PRODUCT_ORDER)
+        if unknown:
+            raise ValueError(f"unknown plan products {sorted(unknown)}")
+        shapes = product_shapes(B, n_cycles)
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in PRODUCT_ORDER if k in products}
+        po = _fill_products(PlanOut(), {k: ptr(out[k]) for k in out})
+        out["margin"] = np.zeros((B, n_cycles, 4), _capi.MARGIN_RECORD_DTYPE)
+        mo = _capi.MarginOut(ptr(out["margin"]), None)
+        if summary:
+            out["margin_summary"] = np.zeros(B, _capi.MARGIN_SUMMARY_DTYPE)
+            mo.summary = ptr(out["margin_summary"])
+        m = _margin_params(mp)
+        self._check(self._lib.fpe_margin_plan(self._h, ptr(self.params), C.byref(m) if m is not None else None, ptr(poses),
+                                              ptr(_strides_for(strides, B)) if strides is not None else None, B, int(n_cycles),
+                                              C.byref(po), C.byref(mo)))
+        return out
+
+    def margin_plan_device(self, d_nominal_ptr, B, n_cycles, d_records_ptr=0, d_summary_ptr=0, mp=None, stream=0):
+        """fpe_margin_plan_device: a DEVICE pointer to a plan's nominal product as a plan call on `stream` left it, and the outputs
+        (0 = not wanted)."""
+        po = _fill_products(PlanOut(), {"nominal": d_nominal_ptr})
+        mo = _capi.MarginOut(d_records_ptr or None, d_summary_ptr or None)
+        m = _margin_params(mp)
+        self._check(self._lib.fpe_margin_plan_device(self._h, ptr(self.params), C.byref(m) if m is not None else None, C.byref(po),
+                                                     int(B), int(n_cycles), C.byref(mo), C.c_void_p(stream or 0)))
 
     # ---- the dense maps as grid_map message layers (fpe_export_layers*) ----------------------------------------------------
     def _layer_request(self, names, dsts, snap_search_radius, snap_polygon, centroid_search_radius):
