@@ -1047,8 +1047,9 @@ int fpe_export_layers_device(fpe_handle h, const fpe_params* params, const int32
  * The per-pose summary covers the records of the pose that describe a segment, whatever else their flags say: max_lift (totalOrder),
  * max_abs_rise = max fabs(rise), max_length_sq, each 0 when the pose has no segment; n_segments; n_over: segments with any OVER bit;
  * n_unknown: segments with UNKNOWN, EMPTY or OFF_MAP; first_over_cycle: the lowest g of a segment with an OVER bit, 255 when none.
- * No atomics anywhere: every byte is a function of the inputs alone.  Out of scope: a swing term in fpe_plan_rank* / fpe_plan_beam*,
- * fpe_multi_*, the service calls, the opt and centroid tracks' footholds, any trajectory shape beyond the lift above the chord. */
+ * No atomics anywhere: every byte is a function of the inputs alone.  A swing term in the ranking: the checked ranking below
+ * (fpe_plan_rank_checked*).  Out of scope: fpe_plan_beam*, fpe_multi_*, the service calls, the opt and centroid tracks' footholds,
+ * any trajectory shape beyond the lift above the chord. */
 #define FPE_SWING_SEGMENT     1u   /* the record describes a segment */
 #define FPE_SWING_OFF_MAP     2u   /* A or B fails checkIfPositionWithinMap (within_axis on either axis) */
 #define FPE_SWING_EMPTY       4u   /* n_cells == 0 */
@@ -1157,9 +1158,10 @@ int fpe_swing_plan(fpe_handle h, const fpe_params* params, const fpe_swing_limit
  * The per-pose summary runs over the pose's records that describe a stance, whatever else their flags say: min_clearance (totalOrder;
  * +infinity when there is none), max_abs_slope_x / _y = max fabs(slope) (0 when none), n_stances, n_bad: stances with UNDER_CLEARANCE
  * or OVER_SLOPE, n_unknown: stances with UNKNOWN, EMPTY or OFF_MAP, first_bad_cycle: the lowest g of a bad stance, 255 when none.
- * No atomics anywhere: every byte is a function of the inputs alone.  Out of scope: a trunk term in fpe_plan_rank* / fpe_plan_beam*,
- * fpe_multi_*, the service calls, the opt and centroid tracks' footholds, yaw (the box is axis-aligned in the map frame, as the
- * reference's stance is), the trot's half-cycle stances, any body shape other than the axis-aligned box. */
+ * No atomics anywhere: every byte is a function of the inputs alone.  A trunk term in the ranking: the checked ranking below
+ * (fpe_plan_rank_checked*).  Out of scope: fpe_plan_beam*, fpe_multi_*, the service calls, the opt and centroid tracks' footholds,
+ * yaw (the box is axis-aligned in the map frame, as the reference's stance is), the trot's half-cycle stances, any body shape other
+ * than the axis-aligned box. */
 #define FPE_TRUNK_STANCE          1u   /* the record describes a stance */
 #define FPE_TRUNK_OFF_MAP         2u   /* any of the four corners (cx +- hx, cy +- hy) fails checkIfPositionWithinMap (within_axis) */
 #define FPE_TRUNK_EMPTY           4u   /* n_cells == 0 */
@@ -1261,7 +1263,8 @@ int fpe_trunk_plan(fpe_handle h, const fpe_params* params, const fpe_trunk_limit
  * B * n_cycles * 4 > 2^30), classes outside 1..15, reach_cells outside 1..FPE_MARGIN_MAX_CELLS, a reserved word that is not 0, a
  * min_margin that is NaN, infinite or negative, a bad roi, both dense outputs NULL, both plan-bound outputs NULL.  FPE_E_NO_MAP.
  * FPE_E_UNSUPPORTED: the undecidable limit above.  fpe_margin_plan also refuses what fpe_plan refuses.
- * No atomics anywhere: every byte is a function of the inputs alone.  Out of scope: a margin term in fpe_plan_rank* / fpe_plan_beam*;
+ * No atomics anywhere: every byte is a function of the inputs alone.  A margin term in the ranking: the checked ranking below
+ * (fpe_plan_rank_checked*).  Out of scope: fpe_plan_beam*;
  * a margin layer in fpe_export_layers (its request struct has fixed arrays: a new layer would change the ABI); fpe_multi_*, the service
  * calls, the opt and centroid tracks; sub-cell positions (see the note above); reaches beyond FPE_MARGIN_MAX_CELLS cells. */
 #define FPE_MARGIN_LOW_CANDIDATE 1u
@@ -1326,6 +1329,87 @@ int fpe_margin_plan_device(fpe_handle h, const fpe_params* params, const fpe_mar
  * and the margin outputs. */
 int fpe_margin_plan(fpe_handle h, const fpe_params* params, const fpe_margin_params* mp, const fpe_pose* poses, const fpe_stride* strides,
                     int32_t B, int32_t n_cycles, const fpe_plan_out* products, const fpe_margin_out* out);
+
+/* ---- checked ranking: the swing, trunk and margin checks folded into the pick --------------------------------------------------------
+ * BUILD-DEFINED.  fpe_plan_rank* scores a pose on commit counts, source counts, deviation and speed spread alone; a pose whose plan puts
+ * the belly on a kerb ranks as well as a clean one.  One call plans the batch as fpe_plan_rank_strides does, reduces every pose's plan
+ * to the three check summaries on the device — no check record is written or allocated anywhere on this path — folds them into the
+ * ranking's class and score and returns the best K exactly as fpe_plan_rank does.
+ * Parameters.  `checks` is a subset of FPE_CHECK_SWING | FPE_CHECK_TRUNK | FPE_CHECK_MARGIN (0 is allowed: no check runs); `reject` a
+ * subset of checks | (checks ? FPE_CHECK_UNKNOWN : 0); the five weights are finite; `reserved` is +0.0 by its bits.  The blocks
+ * `swing`, `trunk` and `margin` are the limits of fpe_swing_* / fpe_trunk_* / fpe_margin_*; the block of a disabled check is not read:
+ * garbage there is not an error.  fpe_check_params_defaults: checks = all three, reject = 0, w_swing_over 10, w_lift 0, w_trunk_bad 10,
+ * w_margin_under 1, w_unknown 1, the three blocks their own *_defaults — with which no OVER / UNDER / bad bit is ever set, so only the
+ * unknown term acts until the caller sets limits.
+ * Summaries.  With the products of the plan, S[b], T[b] and M[b] are, bit for bit, what fpe_swing_plan_device (start feet from
+ * d_start_feet, else the `stance` product), fpe_trunk_plan_device and fpe_margin_plan_device write into summary[b] for the same
+ * products, the same limit blocks and the snapshot current at entry.  REFUSED records are covered by this: those forms' rules hold.
+ * Per pose:   unknown = (SWING ? S.n_unknown : 0) + (TRUNK ? T.n_unknown : 0) + (MARGIN ? M.n_off_map : 0), an int;
+ *             hit = SWING iff enabled and S.n_over > 0 | TRUNK iff enabled and T.n_bad > 0 | MARGIN iff enabled and M.n_under > 0 |
+ *                   UNKNOWN iff unknown > 0.
+ * Score.  `base` is the f64 fpe_plan_rank / fpe_plan_rank_strides stores in score[b] for this pose (-0.0 already +0.0).  In f64, each
+ * product first, added left to right, without contraction:
+ *     v = base
+ *     if SWING:   v = v + w_swing_over   * double(S.n_over);   v = v + w_lift * S.max_lift
+ *     if TRUNK:   v = v + w_trunk_bad    * double(T.n_bad)
+ *     if MARGIN:  v = v + w_margin_under * double(M.n_under)
+ *     if checks:  v = v + w_unknown      * double(unknown)
+ *     score = (v == 0.0) ? +0.0 : v
+ * S.max_lift is always finite (0 without a segment).  T.min_clearance can be +infinity, and the pose-level M.min_dist_sq takes two or
+ * three values on rough ground: there is no clearance and no distance term.
+ * Class and order.  Class 2: the score is not finite.  Class 1: otherwise, gait_cycles_succeed < min_cycles or (hit & reject) != 0.
+ * Class 0: the rest.  The order (class, score, pose index), the tie rule, the K bound, n_class0 and the gather are fpe_plan_rank's.
+ * With checks == 0 every output of fpe_rank_out is byte-identical to fpe_plan_rank_strides with the same arguments.
+ * Outputs.  fpe_rank_out as it is: `score` holds the checked score, `summary` the unchanged fpe_pose_summary.  Beside it fpe_check_out
+ * (any pointer may be NULL): the three summaries (the array of a disabled check is left untouched), base_score and hit.
+ * Records of the winners need no new call: best_products holds nominal, cycle_ok and stance of the K winners in K slots, and
+ * fpe_swing_plan_device / fpe_trunk_plan_device / fpe_margin_plan_device take them with B = K.
+ * Refusals (a refused call writes and queues nothing).  Everything fpe_plan_rank_strides[_device] refuses; for each ENABLED check
+ * everything its *_plan_device form refuses at call level (a NaN limit, a bad radius, half extent or ride height, the box over the cell
+ * cap, the unsupported map, the undecidable min_margin -> FPE_E_UNSUPPORTED, classes or reach out of range, reserved words), decided by
+ * the same host functions; and, FPE_E_INVALID_ARG: bits outside the sets above, a non-finite weight, `reserved` not +0.0.
+ * fpe_check_plan_device is the check stage alone, on products a plan call left on `stream`: nominal is required, cycle_ok with SWING or
+ * TRUNK, and with SWING d_start_feet or the stance product.  It computes no score: it refuses (FPE_E_INVALID_ARG) a non-NULL
+ * base_score, checks == 0, and a d_out without `hit` and without the summary array of any enabled check.
+ * Conventions as fpe_plan_rank*: `rank` NULL and `checks` NULL mean the respective defaults; the host form is synchronous; the device
+ * forms are asynchronous on `stream` and see the snapshot current at entry (the margin's bit planes are built on first use, on that
+ * stream).  No atomics anywhere: every byte is a function of the inputs alone.
+ * Out of scope: a check term in fpe_plan_beam* (its per-segment scoring needs partial-plan check state), fpe_multi_*, the service calls,
+ * the opt and centroid tracks. */
+#define FPE_CHECK_SWING   1u
+#define FPE_CHECK_TRUNK   2u
+#define FPE_CHECK_MARGIN  4u
+#define FPE_CHECK_UNKNOWN 8u
+typedef struct fpe_check_params {     /* 160 bytes */
+    uint32_t checks;       /* subset of SWING | TRUNK | MARGIN; 0 is allowed */
+    uint32_t reject;       /* subset of checks | (checks ? FPE_CHECK_UNKNOWN : 0) */
+    double   w_swing_over, w_lift, w_trunk_bad, w_margin_under, w_unknown;   /* all finite */
+    double   reserved;     /* +0.0 (bits) */
+    fpe_swing_limits  swing;    /* read only when SWING is enabled */
+    fpe_trunk_limits  trunk;    /* read only when TRUNK is enabled */
+    fpe_margin_params margin;   /* read only when MARGIN is enabled */
+} fpe_check_params;
+typedef struct fpe_check_out {        /* 40 bytes; any pointer may be NULL */
+    fpe_swing_summary*  swing;       /* [B]; untouched when SWING is disabled */
+    fpe_trunk_summary*  trunk;       /* [B]; untouched when TRUNK is disabled */
+    fpe_margin_summary* margin;      /* [B]; untouched when MARGIN is disabled */
+    double*             base_score;  /* [B]: the score before the check terms */
+    uint8_t*            hit;         /* [B]: FPE_CHECK_* bits */
+} fpe_check_out;
+int fpe_check_params_defaults(fpe_check_params* out);
+/* The check stage alone, device arrays: the three summaries and `hit`, no record array anywhere.  `d_products` and `d_out` themselves
+ * are host structs of device pointers.  Asynchronous on `stream`, behind whatever filled the products there. */
+int fpe_check_plan_device(fpe_handle h, const fpe_params* params, const fpe_check_params* checks, const fpe_plan_out* d_products,
+                          const double* d_start_feet, int32_t B, int32_t n_cycles, const fpe_check_out* d_out, void* stream);
+/* Plan, check and rank, device arrays; arguments as fpe_plan_rank_strides_device (d_strides and d_full may be NULL), d_check_out may be
+ * NULL.  The start feet are the plan's stance. */
+int fpe_plan_rank_checked_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_check_params* checks,
+                                 const fpe_pose* d_poses, const fpe_stride* d_strides, int32_t B, int32_t n_cycles, int32_t K,
+                                 const fpe_plan_out* d_full, const fpe_rank_out* d_out, const fpe_check_out* d_check_out, void* stream);
+/* The same with host arrays, synchronous; arguments as fpe_plan_rank_strides (strides may be NULL), check_out may be NULL. */
+int fpe_plan_rank_checked(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_check_params* checks,
+                          const fpe_pose* poses, const fpe_stride* strides, int32_t B, int32_t n_cycles, int32_t K,
+                          const fpe_rank_out* out, const fpe_check_out* check_out);
 
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,

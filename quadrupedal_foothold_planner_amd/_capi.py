@@ -383,6 +383,24 @@ class MarginOut(C.Structure):
     _fields_ = [("records", C.c_void_p), ("summary", C.c_void_p)]
 
 
+CHECK_SWING, CHECK_TRUNK, CHECK_MARGIN, CHECK_UNKNOWN = 1, 2, 4, 8  # FPE_CHECK_* bits of fpe_check_params and of fpe_check_out.hit
+
+
+class CheckParams(C.Structure):
+    """fpe_check_params: the checks a checked ranking folds into its score (FPE_CHECK_* bits), the hit bits that move a pose to class
+    1, the weights of the score's check terms and the three checks' own limit blocks (read only when their check is enabled)."""
+    _fields_ = [("checks", C.c_uint32), ("reject", C.c_uint32), ("w_swing_over", C.c_double), ("w_lift", C.c_double),
+                ("w_trunk_bad", C.c_double), ("w_margin_under", C.c_double), ("w_unknown", C.c_double), ("reserved", C.c_double),
+                ("swing", SwingLimits), ("trunk", TrunkLimits), ("margin", MarginParams)]
+
+
+class CheckOut(C.Structure):
+    """fpe_check_out: the check outputs of a checked ranking, one element per pose (any pointer may be NULL)."""
+    _fields_ = [("swing", C.c_void_p), ("trunk", C.c_void_p), ("margin", C.c_void_p), ("base_score", C.c_void_p), ("hit", C.c_void_p)]
+
+
+assert (C.sizeof(CheckParams), C.sizeof(CheckOut)) == (160, 40)
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -402,6 +420,7 @@ STRUCTS = {
     "fpe_trunk_summary": TRUNK_SUMMARY_DTYPE, "fpe_trunk_out": TrunkOut,
     "fpe_margin_params": MarginParams, "fpe_margin_map_out": MarginMapOut, "fpe_margin_query": MARGIN_QUERY_DTYPE,
     "fpe_margin_record": MARGIN_RECORD_DTYPE, "fpe_margin_summary": MARGIN_SUMMARY_DTYPE, "fpe_margin_out": MarginOut,
+    "fpe_check_params": CheckParams, "fpe_check_out": CheckOut,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -505,6 +524,11 @@ PROTOTYPES = {
     "fpe_margin_cells_device": (cint, [vp, vp, P(MarginParams), vp, i32, vp, vp]),
     "fpe_margin_plan_device": (cint, [vp, vp, P(MarginParams), P(PlanOut), i32, i32, P(MarginOut), vp]),
     "fpe_margin_plan": (cint, [vp, vp, P(MarginParams), vp, vp, i32, i32, P(PlanOut), P(MarginOut)]),
+    "fpe_check_params_defaults": (cint, [P(CheckParams)]),
+    "fpe_check_plan_device": (cint, [vp, vp, P(CheckParams), P(PlanOut), vp, i32, i32, P(CheckOut), vp]),
+    "fpe_plan_rank_checked_device": (cint, [vp, vp, P(RankParams), P(CheckParams), vp, vp, i32, i32, i32, P(PlanOut), P(RankOut),
+                                            P(CheckOut), vp]),
+    "fpe_plan_rank_checked": (cint, [vp, vp, P(RankParams), P(CheckParams), vp, vp, i32, i32, i32, P(RankOut), P(CheckOut)]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),
@@ -617,6 +641,13 @@ def trunk_limits_defaults(**overrides):
             raise ValueError(f"unknown trunk limit {k!r}")
         setattr(tl, k, v)
     return tl
+
+
+def check_params_defaults():
+    """fpe_check_params_defaults: all three checks, no reject bit, the documented weights, each check's own default limits."""
+    cp = CheckParams()
+    assert lib().fpe_check_params_defaults(C.byref(cp)) == FPE_OK
+    return cp
 
 
 def spiral_offsets(n_rings):

@@ -933,8 +933,10 @@ struct Seg {
     size_t off, len;
     void* dst;
 };
+constexpr int kMaxSegs = kPlanProducts + 4 + 5;  // the longest list: a checked ranking's products, rank outputs and check outputs
+static_assert(kProducts + 1 <= kMaxSegs, "SegList holds a resume call's products and its state");
 struct SegList {
-    Seg s[kProducts + 1];  // (a ranking call: its eight products and four outputs of its own; a resume call: the state as well)
+    Seg s[kMaxSegs];  // (a ranking call: its eight products and four outputs of its own, checked: five more; a resume call: the state as well)
     int n = 0;
     void add(size_t off, size_t len, void* dst) {
         if (dst && len) s[n++] = Seg{off, len, dst};
@@ -996,7 +998,7 @@ int copy_out(fpe_engine* h, CallCtx& cx, SegList list, const unsigned char* dev,
     Seg* const segs = list.s;
     const int nSeg = list.n;
     size_t staged = 0;
-    bool pinnedSeg[kProducts + 1];
+    bool pinnedSeg[kMaxSegs];
     for (int k = 0; k < nSeg; ++k) pinnedSeg[k] = is_pinned_host(segs[k].dst);
     for (int k = 0; k < nSeg; ++k) {
         if (!pinnedSeg[k]) {
@@ -2479,7 +2481,7 @@ struct RankLayout {
     int32_t* nClass0;
     void* keys;
 };
-static_assert(kPlanProducts + 4 <= kProducts, "SegList holds a ranking call's outputs");
+static_assert(kPlanProducts + 4 + 5 <= kMaxSegs, "SegList holds a (checked) ranking call's outputs");
 void rank_layout(RankLayout& L, ArenaCursor& A, const fpe_plan_out* dFull, const fpe_rank_out& want, bool hostForm) {
     const bool reads[kPlanProducts] = {true, false, true, true, true, false, true, false};  // rank_summary_kernel's inputs
     const size_t B = static_cast<size_t>(L.B), K = static_cast<size_t>(L.K), n = static_cast<size_t>(L.n);
@@ -2498,14 +2500,33 @@ void rank_layout(RankLayout& L, ArenaCursor& A, const fpe_plan_out* dFull, const
     L.keys = A.take(fpe::rank_scratch_bytes(L.B, L.K));
 }
 
-// The launches of a prepared ranking call on `stream`: the plan through launch_plan, then summary, select, gather.
+// The launches of a prepared ranking call on `stream`: the plan through launch_plan, then summary, (check: the check stage of a
+// checked ranking,) select, gather.
 int run_rank(fpe_engine* h, const CallPlan& cp, const fpe::RankConsts& rc, const fpe_pose* d_poses, const fpe_stride* d_strides, const RankLayout& L,
-             hipStream_t stream) {
+             hipStream_t stream, const fpe::CheckStage* check) {
     int rc0 = launch_plan(h, cp, d_poses, L.B, L.n, L.full, stream, {d_strides});
     if (rc0 != FPE_OK) return rc0;
-    FPE_HIP(fpe::launch_rank(rc, d_poses, L.B, L.n, L.K, L.full, L.summary, L.score, L.keys, L.bestIdx, L.nClass0, L.best, stream, d_strides));
+    FPE_HIP(fpe::launch_rank(rc, d_poses, L.B, L.n, L.K, L.full, L.summary, L.score, L.keys, L.bestIdx, L.nClass0, L.best, stream, d_strides,
+                             check));
     return FPE_OK;
 }
+
+// The check stage of a checked ranking (fpe_plan_rank_checked*; defined with them, behind the three checks' host functions).  Both
+// ranking forms take one — null: a plain ranking, every step below skipped — and call, in this order:
+struct CheckCall;
+int check_call_map(CheckCall& cc, const CallPlan& cp);  // the refusals that need the snapshot; the margin's constants
+// the check outputs behind the ranking's in the layout (the host form: in the output block)
+void check_call_layout(CheckCall& cc, ArenaCursor& A, int32_t B, bool hostForm);
+int check_call_planes(CheckCall& cc, const fpe_params& params, const CallPlan& cp, hipStream_t stream);  // the margin's bit planes
+void check_call_mark_async(const CheckCall& cc);
+// what launch_rank takes: the stage on the layout's products; null when there is nothing to launch
+const fpe::CheckStage* check_call_stage(CheckCall& cc, const CallPlan& cp, const RankLayout& L);
+
+int rank_device_call(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, CheckCall* check, const fpe_pose* d_poses,
+                     const fpe_stride* d_strides, int32_t B, int32_t n_cycles, int32_t K, const fpe_plan_out* d_full, const fpe_rank_out* d_out,
+                     void* stream);
+int rank_host_call(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, CheckCall* check, const fpe_pose* poses,
+                   const fpe_stride* strides, int32_t B, int32_t n_cycles, int32_t K, const fpe_rank_out* out);
 }  // namespace
 
 int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses, int32_t B,
@@ -2516,6 +2537,15 @@ int fpe_plan_rank_device(fpe_handle h, const fpe_params* params, const fpe_rank_
 int fpe_plan_rank_strides_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* d_poses,
                                  const fpe_stride* d_strides, int32_t B, int32_t n_cycles, int32_t K, const fpe_plan_out* d_full,
                                  const fpe_rank_out* d_out, void* stream) {
+    return rank_device_call(h, params, rank, nullptr, d_poses, d_strides, B, n_cycles, K, d_full, d_out, stream);
+}
+
+namespace {
+// The device form of every ranking call; rank's and check's arguments that need no map are checked by the caller's entry point
+// (check) and here (rank).
+int rank_device_call(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, CheckCall* check, const fpe_pose* d_poses,
+                     const fpe_stride* d_strides, int32_t B, int32_t n_cycles, int32_t K, const fpe_plan_out* d_full, const fpe_rank_out* d_out,
+                     void* stream) {
     fpe::RankConsts rc;
     int rc0 = check_rank_args(params, rank, B, n_cycles, K, d_out, rc);
     if (rc0 != FPE_OK) return rc0;
@@ -2532,13 +2562,21 @@ int fpe_plan_rank_strides_device(fpe_handle h, const fpe_params* params, const f
     if (rc0 != FPE_OK) return rc0;
     rc0 = check_strides_launchable(cp, d_strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain);
     if (rc0 != FPE_OK) return rc0;
+    if (check) {
+        rc0 = check_call_map(*check, cp);
+        if (rc0 == FPE_OK) rc0 = check_call_planes(*check, *params, cp, st);
+        if (rc0 != FPE_OK) return rc0;
+        check_call_mark_async(*check);
+    }
     mark_async_launch(cp);
     return with_stream_scratch(sizes.scratchBytes, st, [&](unsigned char* scratch) {
         ArenaCursor A{scratch};
         rank_layout(L, A, d_full, *d_out, false);
-        return run_rank(h, cp, rc, d_poses, d_strides, L, st);
+        if (check) check_call_layout(*check, A, B, false);
+        return run_rank(h, cp, rc, d_poses, d_strides, L, st, check ? check_call_stage(*check, cp, L) : nullptr);
     });
 }
+}  // namespace
 
 int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses, int32_t B, int32_t n_cycles,
                   int32_t K, const fpe_rank_out* out) {
@@ -2547,6 +2585,13 @@ int fpe_plan_rank(fpe_handle h, const fpe_params* params, const fpe_rank_params*
 
 int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_pose* poses, const fpe_stride* strides,
                           int32_t B, int32_t n_cycles, int32_t K, const fpe_rank_out* out) {
+    return rank_host_call(h, params, rank, nullptr, poses, strides, B, n_cycles, K, out);
+}
+
+namespace {
+// The host form of every ranking call (as rank_device_call)
+int rank_host_call(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, CheckCall* check, const fpe_pose* poses,
+                   const fpe_stride* strides, int32_t B, int32_t n_cycles, int32_t K, const fpe_rank_out* out) {
     fpe::RankConsts rc;
     int rc0 = check_rank_args(params, rank, B, n_cycles, K, out, rc);
     if (rc0 != FPE_OK) return rc0;
@@ -2560,6 +2605,7 @@ int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank
     L.B = B, L.n = n_cycles, L.K = K;
     ArenaCursor sizes;
     rank_layout(L, sizes, nullptr, *out, true);
+    if (check) check_call_layout(*check, sizes, B, true);
     // both arenas: [poses (| strides) | outputs | scratch].  The poses are read from the pinned arena (device-mapped), as in fpe_plan; outputs of up
     // to kZeroCopyBytes are WRITTEN there by the kernels too (no transfer at all: a DMA costs some ten microseconds, whatever its size)
     const size_t oStrides = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
@@ -2571,11 +2617,18 @@ int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank
     rc0 = open_batch_call(h, hc, params, maxRadius, szPose + sizes.outBytes + sizes.scratchBytes, out->best_products.selected_packed != nullptr,
                           strides ? fpe::PlanForm::Stride : fpe::PlanForm::Plain, mapped);
     if (rc0 != FPE_OK) return rc0;
+    if (check) {
+        rc0 = check_call_map(*check, hc.cp);
+        if (rc0 == FPE_OK) rc0 = check_call_planes(*check, *params, hc.cp, cx.stream);
+        if (rc0 != FPE_OK) return rc0;
+    }
     stage_batch_inputs(cx.pinned, oStrides, poses, strides, B);
     ArenaCursor A{cx.dev + szPose + sizes.outBytes, (zeroCopy ? mapped : cx.dev) + szPose, szPose};
     rank_layout(L, A, nullptr, *out, true);
+    if (check) check_call_layout(*check, A, B, true);
     const fpe_stride* dStrides = strides ? reinterpret_cast<const fpe_stride*>(mapped + oStrides) : nullptr;
-    rc0 = run_rank(h, hc.cp, rc, reinterpret_cast<const fpe_pose*>(mapped), dStrides, L, cx.stream);
+    rc0 = run_rank(h, hc.cp, rc, reinterpret_cast<const fpe_pose*>(mapped), dStrides, L, cx.stream,
+                   check ? check_call_stage(*check, hc.cp, L) : nullptr);
     if (rc0 != FPE_OK) return rc0;
     if (!zeroCopy) return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
     FPE_HIP(hipStreamSynchronize(cx.stream));
@@ -2583,6 +2636,7 @@ int fpe_plan_rank_strides(fpe_handle h, const fpe_params* params, const fpe_rank
     copy_from_pinned(A.outs, cx.pinned);
     return FPE_OK;
 }
+}  // namespace
 
 int fpe_beam_params_defaults(fpe_beam_params* out) {
     if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
@@ -2600,7 +2654,7 @@ int fpe_beam_params_defaults(fpe_beam_params* out) {
 
 namespace {
 constexpr int kBeamOwn = 5;  // a beam call's outputs of its own, behind the products: n_live, score, penalty, path, state
-static_assert(kPlanProducts + kBeamOwn <= kProducts + 1, "SegList holds a beam call's outputs");
+static_assert(kPlanProducts + kBeamOwn <= kMaxSegs, "SegList holds a beam call's outputs");
 
 // Arguments of fpe_plan_beam* that need no map; bc / sh: the beam's constants and shape (beam NULL: the defaults).
 int check_beam_args(const fpe_params* params, const fpe_beam_params* beam, int32_t B, int32_t M, const fpe_beam_out* out, fpe::BeamConsts& bc,
@@ -2887,7 +2941,7 @@ struct SwingLayout {
     fpe_swing_record* records;
     fpe_swing_summary* summary;
 };
-static_assert(kPlanProducts + 2 <= kProducts + 1, "SegList holds a plan-and-check call's outputs");
+static_assert(kPlanProducts + 2 <= kMaxSegs, "SegList holds a plan-and-check call's outputs");
 void swing_layout(SwingLayout& L, ArenaCursor& A, const fpe_plan_out* want, const fpe_swing_out& so) {
     const bool reads[kPlanProducts] = {true, false, false, true, true, false, false, false};  // swing_segments_kernel<true>'s inputs
     const size_t B = static_cast<size_t>(L.B), n = static_cast<size_t>(L.n);
@@ -3346,6 +3400,167 @@ int fpe_margin_plan(fpe_handle h, const fpe_params* params, const fpe_margin_par
     if (rc != FPE_OK) return rc;
     FPE_HIP(fpe::launch_margin_plan(planes.bits, planes.snap->g, mc, L.plan.nominal, B, n_cycles, L.records, L.summary, cx.stream));
     return copy_out(h, cx, A.outs, cx.dev, cx.pinned);
+}
+
+// ---- checked ranking (fpe_plan_rank_checked*, fpe_check_plan_device; kernel: fpe_check.hpp) -------------------------------------
+int fpe_check_params_defaults(fpe_check_params* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->checks = FPE_CHECK_SWING | FPE_CHECK_TRUNK | FPE_CHECK_MARGIN;
+    out->reject = 0;
+    out->w_swing_over = 10.0;
+    out->w_lift = 0.0;
+    out->w_trunk_bad = 10.0;
+    out->w_margin_under = 1.0;
+    out->w_unknown = 1.0;
+    fpe_swing_limits_defaults(&out->swing);
+    fpe_trunk_limits_defaults(&out->trunk);
+    fpe_margin_params_defaults(&out->margin);
+    return FPE_OK;
+}
+
+namespace {
+// The check stage of one call: what the caller asked for, the kernel's argument block as the checks below fill it in, and the
+// margin's planes (a CallPlan of their own on the call's snapshot, as in fpe_margin_plan; the object outlives the call's lease).
+struct CheckCall {
+    fpe_check_out want{};       // the caller's arrays (null: not wanted; those of a disabled check: cleared)
+    fpe_check_out out{};        // where the kernel writes them (check_call_layout)
+    fpe_margin_params margin{};  // the checked margin block
+    CallPlan planes;
+    fpe::CheckStage stage{};
+};
+
+// Arguments of a check stage that need no map (checks NULL: the defaults): the bits, the weights, and each ENABLED check's block
+// through the host function of its own family; a disabled check's block is not read.
+int check_check_args(const fpe_params* params, const fpe_check_params* checks, const fpe_check_out* out, CheckCall& cc) {
+    if (!params) return fail(FPE_E_INVALID_ARG, "null handle or params");
+    fpe_check_params def;
+    if (!checks) {
+        fpe_check_params_defaults(&def);
+        checks = &def;
+    }
+    constexpr uint32_t kAll = FPE_CHECK_SWING | FPE_CHECK_TRUNK | FPE_CHECK_MARGIN;
+    const uint32_t on = checks->checks;
+    if (on & ~kAll) return fail(FPE_E_INVALID_ARG, "fpe_check_params.checks holds bits outside SWING | TRUNK | MARGIN");
+    if (checks->reject & ~(on | (on ? FPE_CHECK_UNKNOWN : 0u)))
+        return fail(FPE_E_INVALID_ARG, "fpe_check_params.reject must be a subset of checks | (checks ? UNKNOWN : 0)");
+    const double w[5] = {checks->w_swing_over, checks->w_lift, checks->w_trunk_bad, checks->w_margin_under, checks->w_unknown};
+    for (double v : w)
+        if (!std::isfinite(v)) return fail(FPE_E_INVALID_ARG, "check weights must be finite");
+    uint64_t reservedBits;
+    std::memcpy(&reservedBits, &checks->reserved, sizeof(reservedBits));
+    if (reservedBits != 0) return fail(FPE_E_INVALID_ARG, "fpe_check_params.reserved must be +0.0");
+    fpe::CheckArgs& a = cc.stage.a;
+    a.checks = on, a.reject = checks->reject;
+    a.wSwingOver = w[0], a.wLift = w[1], a.wTrunkBad = w[2], a.wMarginUnder = w[3], a.wUnknown = w[4];
+    int rc = FPE_OK;
+    if (on & FPE_CHECK_SWING) rc = swing_consts(params, &checks->swing, a.sc);
+    if (rc == FPE_OK && (on & FPE_CHECK_TRUNK)) rc = trunk_consts(params, &checks->trunk, a.tc);
+    if (rc == FPE_OK && (on & FPE_CHECK_MARGIN)) rc = margin_params(&checks->margin, cc.margin);
+    if (rc != FPE_OK) return rc;
+    if (out) cc.want = *out;
+    if (!(on & FPE_CHECK_SWING)) cc.want.swing = nullptr;
+    if (!(on & FPE_CHECK_TRUNK)) cc.want.trunk = nullptr;
+    if (!(on & FPE_CHECK_MARGIN)) cc.want.margin = nullptr;
+    return FPE_OK;
+}
+
+int check_call_map(CheckCall& cc, const CallPlan& cp) {
+    fpe::CheckArgs& a = cc.stage.a;
+    int rc = FPE_OK;
+    if (a.checks & FPE_CHECK_SWING) rc = check_swing_map(cp);
+    if (rc == FPE_OK && (a.checks & FPE_CHECK_TRUNK)) rc = check_trunk_map(cp, a.tc);
+    if (rc == FPE_OK && (a.checks & FPE_CHECK_MARGIN)) {
+        rc = margin_consts(cc.margin, cp.snap->g, a.mc);
+        a.marginLanesLog2 = fpe::margin_lanes_log2(cc.margin.reach_cells);
+    }
+    return rc;
+}
+
+// The pair's planes on the call's snapshot by the lookup the plan made, built on `stream` on first use (as fpe_margin_plan)
+int check_call_planes(CheckCall& cc, const fpe_params& params, const CallPlan& cp, hipStream_t stream) {
+    if (!(cc.stage.a.checks & FPE_CHECK_MARGIN)) return FPE_OK;
+    cc.planes.snap = cp.snap;
+    return margin_planes(params, cc.planes, stream);
+}
+
+void check_call_mark_async(const CheckCall& cc) {
+    if (cc.planes.snap) mark_async_launch(cc.planes);
+}
+
+void check_call_layout(CheckCall& cc, ArenaCursor& A, int32_t B, bool hostForm) {
+    const size_t n = static_cast<size_t>(B);
+    const auto out = [&](void* dst, size_t bytes) { return (dst && hostForm) ? A.out(dst, bytes) : dst; };
+    cc.out.swing = static_cast<fpe_swing_summary*>(out(cc.want.swing, n * sizeof(fpe_swing_summary)));
+    cc.out.trunk = static_cast<fpe_trunk_summary*>(out(cc.want.trunk, n * sizeof(fpe_trunk_summary)));
+    cc.out.margin = static_cast<fpe_margin_summary*>(out(cc.want.margin, n * sizeof(fpe_margin_summary)));
+    cc.out.base_score = static_cast<double*>(out(cc.want.base_score, n * sizeof(double)));
+    cc.out.hit = static_cast<uint8_t*>(out(cc.want.hit, n));
+}
+
+// The stage on a snapshot, products and start feet, with the outputs check_call_layout placed
+void check_stage_fill(CheckCall& cc, const CallPlan& cp, const fpe_foothold* nominal, const uint8_t* cycleOk, const double* startFeet) {
+    cc.stage.m = dev_map(*cp.snap);
+    cc.stage.bm = cc.planes.bits;
+    fpe::CheckArgs& a = cc.stage.a;
+    a.nominal = nominal, a.cycleOk = cycleOk, a.startFeet = startFeet;
+    a.swing = cc.out.swing, a.trunk = cc.out.trunk, a.margin = cc.out.margin, a.baseScore = cc.out.base_score, a.hit = cc.out.hit;
+}
+
+const fpe::CheckStage* check_call_stage(CheckCall& cc, const CallPlan& cp, const RankLayout& L) {
+    // no check enabled: the score, the classes and the keys are the summary's; only base_score and hit would be left to write
+    if (cc.stage.a.checks == 0 && !cc.out.base_score && !cc.out.hit) return nullptr;
+    check_stage_fill(cc, cp, L.full.nominal, L.full.cycle_ok, L.full.stance);
+    return &cc.stage;
+}
+}  // namespace
+
+int fpe_check_plan_device(fpe_handle h, const fpe_params* params, const fpe_check_params* checks, const fpe_plan_out* d_products,
+                          const double* d_start_feet, int32_t B, int32_t n_cycles, const fpe_check_out* d_out, void* stream) {
+    if (!d_products || !d_out || !d_products->nominal) return fail(FPE_E_INVALID_ARG, "null argument");
+    CheckCall cc;
+    int rc = check_swing_shape(B, n_cycles);
+    if (rc == FPE_OK) rc = check_check_args(params, checks, d_out, cc);
+    if (rc != FPE_OK) return rc;
+    const uint32_t on = cc.stage.a.checks;
+    if (on == 0) return fail(FPE_E_INVALID_ARG, "no check enabled");
+    if (d_out->base_score) return fail(FPE_E_INVALID_ARG, "the check stage alone computes no score: base_score must be NULL");
+    if (!cc.want.swing && !cc.want.trunk && !cc.want.margin && !cc.want.hit)
+        return fail(FPE_E_INVALID_ARG, "no output of an enabled check requested");
+    if ((on & (FPE_CHECK_SWING | FPE_CHECK_TRUNK)) && !d_products->cycle_ok) return fail(FPE_E_INVALID_ARG, "null argument (cycle_ok)");
+    if ((on & FPE_CHECK_SWING) && !d_start_feet && !d_products->stance)
+        return fail(FPE_E_INVALID_ARG, "neither start feet nor the stance product given");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallPlan cp;
+    rc = prepare_call(h, params, 0.0f, cp, st, false);
+    if (rc == FPE_OK) rc = check_call_map(cc, cp);
+    if (rc == FPE_OK) rc = check_call_planes(cc, *params, cp, st);
+    if (rc != FPE_OK) return rc;
+    mark_async_launch(cp);
+    check_call_mark_async(cc);
+    ArenaCursor none;
+    check_call_layout(cc, none, B, false);
+    check_stage_fill(cc, cp, d_products->nominal, d_products->cycle_ok, d_start_feet ? d_start_feet : d_products->stance);
+    FPE_HIP(fpe::launch_plan_check(cc.stage, B, n_cycles, false, st));
+    return FPE_OK;
+}
+
+int fpe_plan_rank_checked_device(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_check_params* checks,
+                                 const fpe_pose* d_poses, const fpe_stride* d_strides, int32_t B, int32_t n_cycles, int32_t K,
+                                 const fpe_plan_out* d_full, const fpe_rank_out* d_out, const fpe_check_out* d_check_out, void* stream) {
+    CheckCall cc;
+    const int rc = check_check_args(params, checks, d_check_out, cc);
+    if (rc != FPE_OK) return rc;
+    return rank_device_call(h, params, rank, &cc, d_poses, d_strides, B, n_cycles, K, d_full, d_out, stream);
+}
+
+int fpe_plan_rank_checked(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_check_params* checks,
+                          const fpe_pose* poses, const fpe_stride* strides, int32_t B, int32_t n_cycles, int32_t K,
+                          const fpe_rank_out* out, const fpe_check_out* check_out) {
+    CheckCall cc;
+    const int rc = check_check_args(params, checks, check_out, cc);
+    if (rc != FPE_OK) return rc;
+    return rank_host_call(h, params, rank, &cc, poses, strides, B, n_cycles, K, out);
 }
 
 int fpe_last_service_gate(fpe_handle h, fpe_service_gate* out) {

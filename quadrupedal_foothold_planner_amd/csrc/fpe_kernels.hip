@@ -2291,6 +2291,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_trunk.hpp"
 // ---- part thirteen: the edge margin (fpe_margin_*; uses part four's column mask and part eleven's reductions) ------
 #include "fpe_margin.hpp"
+// ---- part fourteen: the checked ranking (fpe_plan_rank_checked*; folds parts eleven to thirteen into part seven's keys) ----
+#include "fpe_check.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)

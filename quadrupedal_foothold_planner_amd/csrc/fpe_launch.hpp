@@ -286,10 +286,14 @@ struct RankConsts {
     int32_t rfFirst;
 };
 size_t rank_scratch_bytes(int B, int K);
-// d_strides: one fpe_stride per pose, the stride form of the call (fpe_plan_rank_strides*); null: the kernels as they were
+struct CheckStage;  // (the checked ranking, below)
+// d_strides: one fpe_stride per pose, the stride form of the call (fpe_plan_rank_strides*); null: the kernels as they were.
+// check: the check stage of fpe_plan_rank_checked*, launched between the summary and the select on the summary's score, pose
+// summary and keys; null: none.
 hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
                        fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
-                       const fpe_plan_out& bestProducts, hipStream_t stream, const fpe_stride* d_strides = nullptr);
+                       const fpe_plan_out& bestProducts, hipStream_t stream, const fpe_stride* d_strides = nullptr,
+                       const CheckStage* check = nullptr);
 hipError_t set_max_lds_rank();
 
 // ---- the dense maps as message layers (fpe_layers.hpp) -------------------------------------------------------
@@ -406,5 +410,38 @@ hipError_t launch_margin_cells(const BitMap& bm, const MapGeom& g, const MarginC
 // The footholds a plan's nominal product holds: B * nCycles * 4 records (required) and, where d_summary is given, one summary per pose
 hipError_t launch_margin_plan(const BitMap& bm, const MapGeom& g, const MarginConsts& mc, const fpe_foothold* d_nominal, int B, int nCycles,
                               fpe_margin_record* d_records, fpe_margin_summary* d_summary, hipStream_t stream);
+
+// ---- checked ranking (fpe_check.hpp) -------------------------------------------------------------------------
+// The argument block of plan_check_kernel: the enabled checks with their constants (those of a disabled check are not read), the
+// weights, the products read and the outputs (null: not wanted).  The last four are the ranking's: launch_rank fills them in from
+// its own arguments; launch_plan_check alone (fpe_check_plan_device) leaves them null.
+struct CheckArgs {
+    uint32_t checks, reject;  // FPE_CHECK_* bits
+    double wSwingOver, wLift, wTrunkBad, wMarginUnder, wUnknown;
+    SwingConsts sc;
+    TrunkConsts tc;
+    MarginConsts mc;
+    int32_t marginLanesLog2;  // margin_lanes_log2(mc.reach)
+    int32_t minCycles;        // the ranking's class-1 threshold
+    const fpe_foothold* nominal;
+    const uint8_t* cycleOk;
+    const double* startFeet;  // B * 4 * 3: the caller's, else the stance product
+    fpe_swing_summary* swing;
+    fpe_trunk_summary* trunk;
+    fpe_margin_summary* margin;
+    double* baseScore;
+    uint8_t* hit;
+    const fpe_pose_summary* poseSummary;
+    double* score;
+    void* keys;  // RankKey[B] (fpe_rank.hpp)
+};
+// What a check stage launches with: the snapshot's layers, the margin's planes (not read without FPE_CHECK_MARGIN) and the block
+struct CheckStage {
+    DevMap m;
+    BitMap bm;
+    CheckArgs a;
+};
+// rank: the form behind rank_summary_kernel (reads score and poseSummary, writes score and keys), else the summaries and hit alone
+hipError_t launch_plan_check(const CheckStage& st, int B, int nCycles, bool rank, hipStream_t stream);
 
 }  // namespace fpe

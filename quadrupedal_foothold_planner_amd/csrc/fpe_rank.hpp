@@ -333,7 +333,7 @@ size_t rank_scratch_bytes(int B, int K) {
 // required here (the engine hands scratch for what the caller did not ask for).
 hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int nCycles, int K, const fpe_plan_out& full,
                        fpe_pose_summary* d_summary, double* d_score, void* scratch, int32_t* d_best, int32_t* d_nClass0,
-                       const fpe_plan_out& bestProducts, hipStream_t stream, const fpe_stride* d_strides) {
+                       const fpe_plan_out& bestProducts, hipStream_t stream, const fpe_stride* d_strides, const CheckStage* check) {
     unsigned char* sp = static_cast<unsigned char*>(scratch);
     RankKey* keys = reinterpret_cast<RankKey*>(sp);
     sp += rank_align256(static_cast<size_t>(B) * sizeof(RankKey));
@@ -347,6 +347,15 @@ hipError_t launch_rank(const RankConsts& rc, const fpe_pose* d_poses, int B, int
                        d_score, keys);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (check) {  // fpe_plan_rank_checked*: the check terms onto the summary's score, the keys rewritten (fpe_check.hpp)
+        CheckStage st = *check;
+        st.a.poseSummary = d_summary;
+        st.a.score = d_score;
+        st.a.keys = keys;
+        st.a.minCycles = rc.minCycles;
+        e = launch_plan_check(st, B, nCycles, true, stream);
+        if (e != hipSuccess) return e;
+    }
     const RankKey* cur = keys;
     int n = B;
     const int32_t* counts = nullptr;

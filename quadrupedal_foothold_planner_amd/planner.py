@@ -159,6 +159,38 @@ def _margin_params(mp):
     return make_margin_params(**dict(mp))
 
 
+CHECK_NAMES = {"swing": _capi.CHECK_SWING, "trunk": _capi.CHECK_TRUNK, "margin": _capi.CHECK_MARGIN, "unknown": _capi.CHECK_UNKNOWN}
+
+
+def _check_bits(bits):
+    """FPE_CHECK_* bits from an int or from names ("swing", "trunk", "margin", "unknown")."""
+    if isinstance(bits, (int, np.integer)):
+        return int(bits)
+    return int(sum({CHECK_NAMES[k] for k in bits}))
+
+
+def make_check_params(checks=("swing", "trunk", "margin"), reject=0, w_swing_over=10.0, w_lift=0.0, w_trunk_bad=10.0, w_margin_under=1.0,
+                      w_unknown=1.0, swing=None, trunk=None, margin=None):
+    """An fpe_check_params block (plan_rank_checked, check_plan_device): the enabled checks and the reject bits (ints of FPE_CHECK_*
+    bits or names), the weights of the score's check terms, and each check's limits — None (that family's defaults: no limit), its
+    make_*_limits / make_margin_params block, or a dict of those keywords.  Pure host arithmetic: no engine, no GPU."""
+    cp = _capi.CheckParams()
+    cp.checks, cp.reject = _check_bits(checks), _check_bits(reject)
+    cp.w_swing_over, cp.w_lift, cp.w_trunk_bad = float(w_swing_over), float(w_lift), float(w_trunk_bad)
+    cp.w_margin_under, cp.w_unknown, cp.reserved = float(w_margin_under), float(w_unknown), 0.0
+    cp.swing = _swing_limits(swing) or make_swing_limits()
+    cp.trunk = _trunk_limits(trunk) or make_trunk_limits()
+    cp.margin = _margin_params(margin) or make_margin_params()
+    return cp
+
+
+def _check_params(cp):
+    """None (the engine's defaults), a CheckParams block, or a dict of make_check_params' keywords."""
+    if cp is None or isinstance(cp, _capi.CheckParams):
+        return cp
+    return make_check_params(**dict(cp))
+
+
 def margin_metres(dist_sq, resolution):
     """The metric margin res * sqrt(dist_sq) of dist_sq values (any shape) as float64; +infinity where dist_sq is FPE_MARGIN_NONE."""
     d = np.asarray(dist_sq)
@@ -649,6 +681,74 @@ class FootholdPlanner(_Handle):
                                                            C.c_void_p(d_poses_ptr), C.c_void_p(d_strides_ptr or 0), int(B), int(n_cycles),
                                                            int(K), C.byref(fo) if fo is not None else None, C.byref(ro),
                                                            C.c_void_p(stream or 0)))
+
+    # ---- checked ranking: the swing, trunk and margin checks folded into the pick (build-defined: fpe_plan_rank_checked*) ----
+    def plan_rank_checked(self, poses, n_cycles, K, rank=None, checks=None, products=("nominal", "cycle_ok", "stance"), summary=True,
+                          strides=None):
+        """fpe_plan_rank_checked with host buffers: plan_rank with every pose's plan also reduced on the device to the enabled
+        checks' summaries, which enter the score and the class.  `checks`: None (all three checks with their default limits, no
+        reject bit), make_check_params(...) or a dict of its keywords.  Returns plan_rank's dict — "score" is the checked score —
+        plus (summary=True) "base_score": float64 [B], "hit": uint8 [B] of FPE_CHECK_* bits, and "swing_summary" / "trunk_summary" /
+        "margin_summary" [B] for the enabled checks."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        B, K = poses.shape[0], int(K)
+        unknown = set(products) - set(PRODUCT_ORDER)
+        if unknown:
+            raise ValueError(f"unknown plan products {sorted(unknown)}")
+        shapes = product_shapes(max(K, 0), n_cycles)
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in PRODUCT_ORDER if k in products}
+        best = np.zeros(max(K, 0), np.int32)
+        n0 = np.zeros(1, np.int32)
+        ro = RankOut(None, None, ptr(best), ptr(n0))
+        _fill_products(ro.best_products, {k: ptr(out[k]) for k in products})
+        cp = _check_params(checks)
+        on = cp.checks if cp is not None else _capi.CHECK_SWING | _capi.CHECK_TRUNK | _capi.CHECK_MARGIN
+        co = _capi.CheckOut()
+        if summary:
+            out["summary"] = np.zeros(B, _capi.POSE_SUMMARY_DTYPE)
+            out["score"], out["base_score"], out["hit"] = np.zeros(B, np.float64), np.zeros(B, np.float64), np.zeros(B, np.uint8)
+            ro.summary, ro.score = ptr(out["summary"]), ptr(out["score"])
+            co.base_score, co.hit = ptr(out["base_score"]), ptr(out["hit"])
+            for name, bit, dt in (("swing", _capi.CHECK_SWING, _capi.SWING_SUMMARY_DTYPE), ("trunk", _capi.CHECK_TRUNK, _capi.TRUNK_SUMMARY_DTYPE),
+                                  ("margin", _capi.CHECK_MARGIN, _capi.MARGIN_SUMMARY_DTYPE)):
+                if on & bit:
+                    out[name + "_summary"] = np.zeros(B, dt)
+                    setattr(co, name, ptr(out[name + "_summary"]))
+        rp = _call_params(rank, _capi.RankParams, _capi.rank_params_defaults)
+        self._check(self._lib.fpe_plan_rank_checked(self._h, ptr(self.params), C.byref(rp) if rp is not None else None,
+                                                    C.byref(cp) if cp is not None else None, ptr(poses),
+                                                    ptr(_strides_for(strides, B)) if strides is not None else None, B, int(n_cycles), K,
+                                                    C.byref(ro), C.byref(co)))
+        out["best"], out["n_class0"] = best, int(n0[0])
+        return out
+
+    def plan_rank_checked_device(self, d_poses_ptr, B, n_cycles, K, d_best_ptr, rank=None, checks=None, d_summary_ptr=0, d_score_ptr=0,
+                                 d_n_class0_ptr=0, best_products=None, full=None, check_out=None, stream=0, d_strides_ptr=0):
+        """Device form: plan_rank_device's arguments plus `checks` (as plan_rank_checked) and check_out: a dict {"swing" | "trunk" |
+        "margin" | "base_score" | "hit": device pointer} of the per-pose check outputs wanted (None: none)."""
+        ro = RankOut(d_summary_ptr or None, d_score_ptr or None, d_best_ptr or None, d_n_class0_ptr or None)
+        _fill_products(ro.best_products, best_products or {})
+        fo = _fill_products(PlanOut(), full) if full is not None else None
+        rp = _call_params(rank, _capi.RankParams, _capi.rank_params_defaults)
+        cp = _check_params(checks)
+        co = _capi.CheckOut(**{k: (v or None) for k, v in check_out.items()}) if check_out is not None else None
+        self._check(self._lib.fpe_plan_rank_checked_device(self._h, ptr(self.params), C.byref(rp) if rp is not None else None,
+                                                           C.byref(cp) if cp is not None else None, C.c_void_p(d_poses_ptr),
+                                                           C.c_void_p(d_strides_ptr or 0), int(B), int(n_cycles), int(K),
+                                                           C.byref(fo) if fo is not None else None, C.byref(ro),
+                                                           C.byref(co) if co is not None else None, C.c_void_p(stream or 0)))
+
+    def check_plan_device(self, d_nominal_ptr, d_cycle_ok_ptr, B, n_cycles, check_out, checks=None, d_stance_ptr=0, d_start_feet_ptr=0,
+                          stream=0):
+        """fpe_check_plan_device: the check stage alone on DEVICE pointers to a plan's products as a plan call on `stream` left them
+        (the start feet: [B, 4, 3] doubles; 0: the stance product, d_stance_ptr).  check_out: as in plan_rank_checked_device, without
+        "base_score" — the stage computes no score."""
+        po = _fill_products(PlanOut(), {"nominal": d_nominal_ptr, "cycle_ok": d_cycle_ok_ptr, "stance": d_stance_ptr})
+        cp = _check_params(checks)
+        co = _capi.CheckOut(**{k: (v or None) for k, v in check_out.items()})
+        self._check(self._lib.fpe_check_plan_device(self._h, ptr(self.params), C.byref(cp) if cp is not None else None, C.byref(po),
+                                                    C.c_void_p(d_start_feet_ptr or 0), int(B), int(n_cycles), C.byref(co),
+                                                    C.c_void_p(stream or 0)))
 
     # ---- the opt track of a batch (cpp:913-1319, 1485-1568; build-defined optimiser) ---------------------------
     def plan_opt(self, poses, n_cycles, cycle_ok=None):
