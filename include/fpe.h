@@ -271,6 +271,8 @@ int fpe_destroy(fpe_handle h);
  * opt points of the centroid path) come back EMPTY — never the truncated track of an aborted chain — and
  * fpe_last_service_gate names kind FPE_GATE_BUILD_DEFINED and the cycle: a caller that wants the handler's behaviour checks
  * fail_kind, not only the return value.  "service_cycle0_gate_only" (older name): 1 = service_opt_gate 0, 0 = 2.
+ * "beam_check_waves": the wavefronts per candidate of the checked beam's check kernel (fpe_plan_beam_checked*): 0 (DEFAULT) by the
+ * map's resolution, 1 or 4 forced; the outputs do not depend on it.
  * "service_overlap" (default 1): a call that runs the plan AND the opt track for at most four poses launches the opt
  * track's chain on a second stream beside the plan kernel, on nominal cycle flags of 1 (the flags only decide which cycles the
  * chain commits, cpp:1323-1332, and are 1 unless a nominal search fails), and runs it again on the real flags in the call where
@@ -925,6 +927,7 @@ int fpe_describe_plan_resume(fpe_handle h, const fpe_params* params, char* buf, 
  *    step / 2) — has NaN x in every track, which gives a NaN cx: the candidate is class 1, and so is every descendant.  A non-finite
  *    step length on a finite parent state fails every cycle and commits nothing: the candidate keeps its parent's feet, so it is
  *    class 0 with k failed cycles in its penalty.
+ * The swing, trunk and margin checks in the pruning: the checked beam (fpe_plan_beam_checked*, behind the checked ranking).
  * Out of scope: a global beam across roots, deduplication of equal states, the opt track, the service calls, fpe_multi_* / dist.py. */
 #define FPE_BEAM_MAX_OPTIONS 16
 #define FPE_BEAM_MAX_WIDTH   64
@@ -1048,8 +1051,8 @@ int fpe_export_layers_device(fpe_handle h, const fpe_params* params, const int32
  * max_abs_rise = max fabs(rise), max_length_sq, each 0 when the pose has no segment; n_segments; n_over: segments with any OVER bit;
  * n_unknown: segments with UNKNOWN, EMPTY or OFF_MAP; first_over_cycle: the lowest g of a segment with an OVER bit, 255 when none.
  * No atomics anywhere: every byte is a function of the inputs alone.  A swing term in the ranking: the checked ranking below
- * (fpe_plan_rank_checked*).  Out of scope: fpe_plan_beam*, fpe_multi_*, the service calls, the opt and centroid tracks' footholds,
- * any trajectory shape beyond the lift above the chord. */
+ * (fpe_plan_rank_checked*); in the beam's pruning: the checked beam (fpe_plan_beam_checked*).  Out of scope: fpe_multi_*, the
+ * service calls, the opt and centroid tracks' footholds, any trajectory shape beyond the lift above the chord. */
 #define FPE_SWING_SEGMENT     1u   /* the record describes a segment */
 #define FPE_SWING_OFF_MAP     2u   /* A or B fails checkIfPositionWithinMap (within_axis on either axis) */
 #define FPE_SWING_EMPTY       4u   /* n_cells == 0 */
@@ -1159,8 +1162,8 @@ int fpe_swing_plan(fpe_handle h, const fpe_params* params, const fpe_swing_limit
  * +infinity when there is none), max_abs_slope_x / _y = max fabs(slope) (0 when none), n_stances, n_bad: stances with UNDER_CLEARANCE
  * or OVER_SLOPE, n_unknown: stances with UNKNOWN, EMPTY or OFF_MAP, first_bad_cycle: the lowest g of a bad stance, 255 when none.
  * No atomics anywhere: every byte is a function of the inputs alone.  A trunk term in the ranking: the checked ranking below
- * (fpe_plan_rank_checked*).  Out of scope: fpe_plan_beam*, fpe_multi_*, the service calls, the opt and centroid tracks' footholds,
- * yaw (the box is axis-aligned in the map frame, as the reference's stance is), the trot's half-cycle stances, any body shape other
+ * (fpe_plan_rank_checked*); in the beam's pruning: the checked beam (fpe_plan_beam_checked*).  Out of scope: fpe_multi_*, the
+ * service calls, the opt and centroid tracks' footholds, yaw (the box is axis-aligned in the map frame, as the reference's stance is), the trot's half-cycle stances, any body shape other
  * than the axis-aligned box. */
 #define FPE_TRUNK_STANCE          1u   /* the record describes a stance */
 #define FPE_TRUNK_OFF_MAP         2u   /* any of the four corners (cx +- hx, cy +- hy) fails checkIfPositionWithinMap (within_axis) */
@@ -1264,7 +1267,7 @@ int fpe_trunk_plan(fpe_handle h, const fpe_params* params, const fpe_trunk_limit
  * min_margin that is NaN, infinite or negative, a bad roi, both dense outputs NULL, both plan-bound outputs NULL.  FPE_E_NO_MAP.
  * FPE_E_UNSUPPORTED: the undecidable limit above.  fpe_margin_plan also refuses what fpe_plan refuses.
  * No atomics anywhere: every byte is a function of the inputs alone.  A margin term in the ranking: the checked ranking below
- * (fpe_plan_rank_checked*).  Out of scope: fpe_plan_beam*;
+ * (fpe_plan_rank_checked*); in the beam's pruning: the checked beam (fpe_plan_beam_checked*).  Out of scope:
  * a margin layer in fpe_export_layers (its request struct has fixed arrays: a new layer would change the ABI); fpe_multi_*, the service
  * calls, the opt and centroid tracks; sub-cell positions (see the note above); reaches beyond FPE_MARGIN_MAX_CELLS cells. */
 #define FPE_MARGIN_LOW_CANDIDATE 1u
@@ -1374,8 +1377,8 @@ int fpe_margin_plan(fpe_handle h, const fpe_params* params, const fpe_margin_par
  * Conventions as fpe_plan_rank*: `rank` NULL and `checks` NULL mean the respective defaults; the host form is synchronous; the device
  * forms are asynchronous on `stream` and see the snapshot current at entry (the margin's bit planes are built on first use, on that
  * stream).  No atomics anywhere: every byte is a function of the inputs alone.
- * Out of scope: a check term in fpe_plan_beam* (its per-segment scoring needs partial-plan check state), fpe_multi_*, the service calls,
- * the opt and centroid tracks. */
+ * The checks in fpe_plan_beam*'s pruning: the checked beam below (fpe_plan_beam_checked*), which carries the partial-plan check state
+ * from segment to segment.  Out of scope: fpe_multi_*, the service calls, the opt and centroid tracks. */
 #define FPE_CHECK_SWING   1u
 #define FPE_CHECK_TRUNK   2u
 #define FPE_CHECK_MARGIN  4u
@@ -1410,6 +1413,70 @@ int fpe_plan_rank_checked_device(fpe_handle h, const fpe_params* params, const f
 int fpe_plan_rank_checked(fpe_handle h, const fpe_params* params, const fpe_rank_params* rank, const fpe_check_params* checks,
                           const fpe_pose* poses, const fpe_stride* strides, int32_t B, int32_t n_cycles, int32_t K,
                           const fpe_rank_out* out, const fpe_check_out* check_out);
+
+/* ---- checked beam: the swing, trunk and margin checks folded into the beam's pruning ------------------------------------------------
+ * BUILD-DEFINED.  fpe_plan_beam* prunes on commit counts, sources, deviation and progress alone: it can drop the only stride sequence
+ * that keeps the belly off a kerb.  Here every candidate carries the check state of its whole path — the three summaries over all
+ * cycles of its ancestry — and that state enters the candidate's score and class in every segment.  No check record is written or
+ * allocated anywhere, and nothing synchronises the host between segments.
+ * Everything fpe_plan_beam defines stays: candidates, c = p * M + m, the segment penalty q, progress, n_s, the outputs, replay, dead
+ * slots not written, no atomics.  `checks` is a fpe_check_params block with the checked ranking's rules.  On top of the beam:
+ *  - Start feet of a root.  start_feet[b] (x, y, z of RF, RH, LH, LF) when given.  Otherwise, with state_in == NULL, the `stance`
+ *    product of the root's plan (the same for every option; what fpe_plan_rank_checked uses).  With state_in != NULL and start_feet ==
+ *    NULL the state carries no z: with SWING enabled the call is refused (FPE_E_INVALID_ARG); without SWING the start feet are +0.0
+ *    (they only show in `feet`, for a leg whose path commits nothing).
+ *  - Carried feet of a candidate.  Per leg, (x, y, double(z)) of the leg's `nominal` record of the latest cycle along the candidate's
+ *    ancestry, this segment included, with cycle_ok != 0; when there is none, the root's start feet.  This is the plan-bound swing's
+ *    rule for A applied across segment boundaries: a candidate whose segment commits nothing inherits its parent's feet.
+ *    check_out.feet is this block of the final slots; a following call takes it as start_feet, together with out.state as state_in.
+ *  - Path summaries of a candidate.  S_c, T_c, M_c: the three summaries over all (s + 1) * k cycles of the ancestry so far, the swing
+ *    from the root's start feet.  Cycle indices g count from the BEAM's first cycle — first_over_cycle, first_bad_cycle,
+ *    first_under_cycle and min_cycle; they are not state.cycle + g.
+ *    THE CONTRACT.  For every live final slot, the summaries and `hit` in check_out are byte for byte what fpe_check_plan_device writes
+ *    for the slot's products: nominal and cycle_ok of out.products, S * k cycles, the root's start feet, the same fpe_check_params,
+ *    the same snapshot.  Everything that form inherits is covered by this: REFUSED records count as there; the margin reads
+ *    nominal.valid and not cycle_ok, so valid feet of a failed cycle count; the "0 / +infinity / 65535 / 255 when there is none"
+ *    rules apply.
+ *  - unknown and hit: as in the checked ranking, from the path summaries.
+ *  - Score.  P_c = P_parent + q stays the unchecked accumulation, output in base_penalty; it is the only thing a child inherits as
+ *    P_parent: the check terms are never accumulated twice.  Then, in f64, each product first, added left to right, no contraction:
+ *        v = P_c
+ *        if SWING:   v = v + w_swing_over   * double(S_c.n_over);   v = v + w_lift * S_c.max_lift
+ *        if TRUNK:   v = v + w_trunk_bad    * double(T_c.n_bad)
+ *        if MARGIN:  v = v + w_margin_under * double(M_c.n_under)
+ *        if checks:  v = v + w_unknown      * double(unknown)
+ *        t = w_progress * cx;   score = v - t;   -0.0 is stored as +0.0
+ *    out.penalty holds v.
+ *  - Class and order.  Class 2: the score is not finite, ordered by c alone.  Class 1: otherwise, (hit & reject) != 0.  Class 0: the
+ *    rest.  The order is (class, score, c) ascending.  n_s is unchanged, so a root whose candidates are all class 1 still fills its
+ *    slots, by score.  Counts only grow along a path: a rejected candidate's descendants are rejected.
+ *  - No checks.  With checks->checks == 0 every byte of fpe_beam_out equals fpe_plan_beam's, and check_out is not touched.
+ *  - Refusals (nothing written or queued): everything fpe_plan_beam[_device] refuses; for each ENABLED check everything
+ *    fpe_check_plan_device refuses at call level, decided by the same host functions (the unsupported map and the undecidable
+ *    min_margin -> FPE_E_UNSUPPORTED included); the fpe_check_params bit, weight and `reserved` rules of the checked ranking; the
+ *    missing start feet, above; and, the host form only, with SWING enabled: a start foot coordinate that is not finite or beyond
+ *    +-1e6.  The device form cannot look at values: a bad start foot takes the swing record's own REFUSED path.
+ * Conventions, snapshot semantics and asynchrony are those of fpe_plan_beam*: `beam` NULL and `checks` NULL mean the respective
+ * defaults, check_out may be NULL; the margin's bit planes are acquired once, on the call's snapshot (built on first use, on the
+ * call's stream).
+ * Out of scope: a concatenation contract for checked beams, a global beam, fpe_multi_*, the service calls, the opt and centroid tracks. */
+typedef struct fpe_beam_check_out {   /* 48 bytes; every pointer may be NULL; element b * W + w belongs to slot (b, w); dead slots are not written */
+    fpe_swing_summary*  swing;        /* [B * W]; untouched when SWING is disabled */
+    fpe_trunk_summary*  trunk;        /* [B * W]; untouched when TRUNK is disabled */
+    fpe_margin_summary* margin;       /* [B * W]; untouched when MARGIN is disabled */
+    double*             base_penalty; /* [B * W]: the accumulated penalty without the check terms */
+    uint8_t*            hit;          /* [B * W]: FPE_CHECK_* bits */
+    double*             feet;         /* [B * W * 4 * 3]: where the feet stand behind the last cycle, x, y, z of RF, RH, LH, LF */
+} fpe_beam_check_out;
+/* Host arrays; synchronous.  Arguments as fpe_plan_beam; start_feet: [B * 4 * 3] or NULL. */
+int fpe_plan_beam_checked(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_check_params* checks,
+                          const fpe_pose* poses, const fpe_plan_state* state_in, const double* start_feet, int32_t B,
+                          const fpe_stride* options, int32_t M, const fpe_beam_out* out, const fpe_beam_check_out* check_out);
+/* Device arrays (every non-NULL pointer of d_out and d_check_out too); asynchronous on `stream`, as fpe_plan_beam_device. */
+int fpe_plan_beam_checked_device(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_check_params* checks,
+                                 const fpe_pose* d_poses, const fpe_plan_state* d_state_in, const double* d_start_feet, int32_t B,
+                                 const fpe_stride* d_options, int32_t M, const fpe_beam_out* d_out,
+                                 const fpe_beam_check_out* d_check_out, void* stream);
 
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,

@@ -399,7 +399,13 @@ class CheckOut(C.Structure):
     _fields_ = [("swing", C.c_void_p), ("trunk", C.c_void_p), ("margin", C.c_void_p), ("base_score", C.c_void_p), ("hit", C.c_void_p)]
 
 
-assert (C.sizeof(CheckParams), C.sizeof(CheckOut)) == (160, 40)
+class BeamCheckOut(C.Structure):
+    """fpe_beam_check_out: the check outputs of a checked beam, one element per slot (b, w) (any pointer may be NULL)."""
+    _fields_ = [("swing", C.c_void_p), ("trunk", C.c_void_p), ("margin", C.c_void_p), ("base_penalty", C.c_void_p), ("hit", C.c_void_p),
+                ("feet", C.c_void_p)]
+
+
+assert (C.sizeof(CheckParams), C.sizeof(CheckOut), C.sizeof(BeamCheckOut)) == (160, 40, 48)
 
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
@@ -420,7 +426,7 @@ STRUCTS = {
     "fpe_trunk_summary": TRUNK_SUMMARY_DTYPE, "fpe_trunk_out": TrunkOut,
     "fpe_margin_params": MarginParams, "fpe_margin_map_out": MarginMapOut, "fpe_margin_query": MARGIN_QUERY_DTYPE,
     "fpe_margin_record": MARGIN_RECORD_DTYPE, "fpe_margin_summary": MARGIN_SUMMARY_DTYPE, "fpe_margin_out": MarginOut,
-    "fpe_check_params": CheckParams, "fpe_check_out": CheckOut,
+    "fpe_check_params": CheckParams, "fpe_check_out": CheckOut, "fpe_beam_check_out": BeamCheckOut,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -529,6 +535,9 @@ PROTOTYPES = {
     "fpe_plan_rank_checked_device": (cint, [vp, vp, P(RankParams), P(CheckParams), vp, vp, i32, i32, i32, P(PlanOut), P(RankOut),
                                             P(CheckOut), vp]),
     "fpe_plan_rank_checked": (cint, [vp, vp, P(RankParams), P(CheckParams), vp, vp, i32, i32, i32, P(RankOut), P(CheckOut)]),
+    "fpe_plan_beam_checked": (cint, [vp, vp, P(BeamParams), P(CheckParams), vp, vp, vp, i32, vp, i32, P(BeamOut), P(BeamCheckOut)]),
+    "fpe_plan_beam_checked_device": (cint, [vp, vp, P(BeamParams), P(CheckParams), vp, vp, vp, i32, vp, i32, P(BeamOut), P(BeamCheckOut),
+                                            vp]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

@@ -70,6 +70,8 @@ __device__ __forceinline__ int check_min32(int v, int from = kSwingLanes) {
 }
 
 // Wavefront `wave` of the swing: the partial sums of fpe_swing_summary (as swing_summary_kernel forms it) over its segments
+// (kWaves, here and below: the wavefronts that share a plan — four in plan_check_kernel; the checked beam also builds one)
+template <int kWaves = 4>
 __device__ __forceinline__ void check_swing_part(const DevMap& m, const CheckArgs& a, const fpe_foothold* __restrict__ nominal,
                                                  const uint8_t* __restrict__ ok, const double* __restrict__ feet, int nCycles, int wave,
                                                  int lane, CheckPart& out) {
@@ -87,7 +89,7 @@ __device__ __forceinline__ void check_swing_part(const DevMap& m, const CheckArg
         const fpe_foothold& to = nominal[g * 4 + leg];
         s.ax = s.bx, s.ay = s.by, s.az = s.bz;
         s.bx = to.x, s.by = to.y, s.bz = static_cast<double>(to.z);
-        if ((ordinal++ & 3) != wave) continue;  // another wavefront's segment
+        if ((ordinal++ & (kWaves - 1)) != wave) continue;  // another wavefront's segment
         const fpe_swing_record rec = swing_segment_record(m, a.sc, s, l16);
         const uint32_t fl = rec.flags;
         if (!(fl & FPE_SWING_SEGMENT)) continue;
@@ -114,6 +116,7 @@ __device__ __forceinline__ void check_swing_part(const DevMap& m, const CheckArg
 }
 
 // Wavefront `wave` of the trunk: the partial sums of fpe_trunk_summary (as trunk_summary_kernel forms it) over its stances
+template <int kWaves = 4>
 __device__ __forceinline__ void check_trunk_part(const DevMap& m, const CheckArgs& a, const fpe_foothold* __restrict__ nominal,
                                                  const uint8_t* __restrict__ ok, int nCycles, int wave, int lane, CheckPart& out) {
     constexpr uint32_t kBad = FPE_TRUNK_UNDER_CLEARANCE | FPE_TRUNK_OVER_SLOPE;
@@ -121,7 +124,7 @@ __device__ __forceinline__ void check_trunk_part(const DevMap& m, const CheckArg
     const int grp = lane >> 4, l16 = lane & (kSwingLanes - 1);
     long long clearKey = kSwingNoKey64, sxKey = 0, syKey = 0;
     int nStances = 0, nBad = 0, nUnknown = 0, firstBad = 255;
-    for (int g = wave * 4 + grp; g < nCycles; g += 16) {
+    for (int g = wave * 4 + grp; g < nCycles; g += 4 * kWaves) {
         if (ok[g] == 0) continue;  // (a whole group: trunk_stance_record's shuffles stay inside it)
         TrunkStance s;
 #pragma unroll
@@ -156,6 +159,7 @@ __device__ __forceinline__ void check_trunk_part(const DevMap& m, const CheckArg
 }
 
 // Wavefront `wave` of the margin: the partial sums of fpe_margin_summary (as margin_summary_kernel forms it) over its cells
+template <int kWaves = 4>
 __device__ __forceinline__ void check_margin_part(const BitMap& bm, int rows, int cols, const CheckArgs& a,
                                                   const fpe_foothold* __restrict__ nominal, int nCycles, int wave, int lane,
                                                   CheckMarginPart& out) {
@@ -164,7 +168,7 @@ __device__ __forceinline__ void check_margin_part(const BitMap& bm, int rows, in
     const int nRec = nCycles * 4, per = 64 >> k;  // cells of a chunk
     long long best = 0x7FFFFFFFFFFFFFFFll;  // dist_sq << 16 | g * 4 + leg (below 2^32): the lowest (dist_sq, g, leg)
     int nFoot = 0, nUnder = 0, nOff = 0, firstUnder = 255;
-    for (int s0 = (3 - wave) * per; s0 < nRec; s0 += 4 * per) {
+    for (int s0 = (kWaves - 1 - wave) * per; s0 < nRec; s0 += kWaves * per) {
         const int s = s0 + (lane >> k);
         if (s >= nRec) continue;  // (a whole sub-group: the key's shuffles stay inside it — here and below)
         const fpe_foothold& f = nominal[s];

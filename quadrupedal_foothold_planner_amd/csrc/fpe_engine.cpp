@@ -933,10 +933,10 @@ struct Seg {
     size_t off, len;
     void* dst;
 };
-constexpr int kMaxSegs = kPlanProducts + 4 + 5;  // the longest list: a checked ranking's products, rank outputs and check outputs
+constexpr int kMaxSegs = kPlanProducts + 5 + 6;  // the longest list: a checked beam's products, beam outputs and check outputs
 static_assert(kProducts + 1 <= kMaxSegs, "SegList holds a resume call's products and its state");
 struct SegList {
-    Seg s[kMaxSegs];  // (a ranking call: its eight products and four outputs of its own, checked: five more; a resume call: the state as well)
+    Seg s[kMaxSegs];  // (a ranking call: its eight products and four outputs of its own, checked: five more; a beam call: five, checked: six more; a resume call: the state as well)
     int n = 0;
     void add(size_t off, size_t len, void* dst) {
         if (dst && len) s[n++] = Seg{off, len, dst};
@@ -1629,6 +1629,9 @@ int fpe_set_tuning(fpe_handle h, const char* key, int32_t value) {
     else if (k == "service_opt_gate") {
         if (value < 0 || value > 2) return fail(FPE_E_INVALID_ARG, "service_opt_gate is 0 (exact gates only), 1 (advisory) or 2 (enforce)");
         h->tuning.serviceOptGate = value;
+    } else if (k == "beam_check_waves") {
+        if (value != 0 && value != 1 && value != 4) return fail(FPE_E_INVALID_ARG, "beam_check_waves is 0 (automatic), 1 or 4");
+        h->tuning.beamCheckWaves = value;
     } else if (k == "service_overlap") h->tuning.serviceOverlap = value ? 1 : 0;
     else if (k == "service_poll") h->tuning.servicePoll = value ? 1 : 0;
     else if (k == "service_cycle0_gate_only") h->tuning.serviceOptGate = value ? 0 : 2;  // (older name)
@@ -2654,7 +2657,8 @@ int fpe_beam_params_defaults(fpe_beam_params* out) {
 
 namespace {
 constexpr int kBeamOwn = 5;  // a beam call's outputs of its own, behind the products: n_live, score, penalty, path, state
-static_assert(kPlanProducts + kBeamOwn <= kMaxSegs, "SegList holds a beam call's outputs");
+constexpr int kBeamCheckOwn = 6;  // a checked beam's, behind those: the three summaries, base_penalty, hit, feet
+static_assert(kPlanProducts + kBeamOwn + kBeamCheckOwn <= kMaxSegs, "SegList holds a (checked) beam call's outputs");
 
 // Arguments of fpe_plan_beam* that need no map; bc / sh: the beam's constants and shape (beam NULL: the defaults).
 int check_beam_args(const fpe_params* params, const fpe_beam_params* beam, int32_t B, int32_t M, const fpe_beam_out* out, fpe::BeamConsts& bc,
@@ -2689,10 +2693,25 @@ struct BeamLayout {
     fpe::BeamShape sh;
     fpe::BeamScratch sc;
     fpe_beam_out out;
-    size_t outSlot[kPlanProducts + kBeamOwn];
+    size_t outSlot[kPlanProducts + kBeamOwn + kBeamCheckOwn];
 };
-void beam_layout(BeamLayout& L, ArenaCursor& A, const fpe_beam_out& want, bool hostForm) {
-    const bool reads[kPlanProducts] = {true, false, true, true, false, false, false, false};  // beam_score_kernel's inputs
+// The check stage of a checked beam (fpe_plan_beam_checked*; defined with them, behind the checked ranking).  Both beam forms take
+// one — null: a plain beam, every step below skipped, the launches those of fpe_plan_beam* — and call, in this order:
+struct BeamCheckCall;
+// the refusals that need the snapshot; the margin's constants; the lane mapping of the check kernel
+int beam_check_map(fpe_engine* h, BeamCheckCall& bc, const fpe_params& params, const CallPlan& cp);
+// the candidates' and parents' check states in the scratch, the check outputs behind the beam's in the layout
+void beam_check_layout(BeamCheckCall& bc, BeamLayout& L, ArenaCursor& A, bool hostForm);
+int beam_check_planes(BeamCheckCall& bc, const fpe_params& params, const CallPlan& cp, hipStream_t stream);  // the margin's bit planes
+void beam_check_mark_async(const BeamCheckCall& bc);
+bool beam_check_wants_stance(const BeamCheckCall& bc, bool haveStateIn);  // segment 0's plan writes the roots' start feet
+// score / select / keep of segment s and the trace with the checks folded in (launch_beam_prune's and launch_beam_trace's places)
+int beam_check_prune(BeamCheckCall& bc, const CallPlan& cp, const fpe::BeamConsts& consts, const BeamLayout& L, int s, hipStream_t stream);
+int beam_check_trace(BeamCheckCall& bc, const BeamLayout& L, hipStream_t stream);
+
+void beam_layout(BeamLayout& L, ArenaCursor& A, const fpe_beam_out& want, bool hostForm, bool wantStance = false) {
+    // beam_score_kernel's inputs (wantStance: a checked beam from the poses, whose roots start from the stance)
+    const bool reads[kPlanProducts] = {true, false, true, true, wantStance, false, false, false};
     const fpe::BeamShape& sh = L.sh;
     const size_t S = static_cast<size_t>(sh.S), k = static_cast<size_t>(sh.k), slots_ = static_cast<size_t>(sh.B) * sh.slotStride;
     const size_t chains = static_cast<size_t>(sh.B) * (sh.S > 1 ? fpe::beam_live(sh, sh.S - 2) : 1) * sh.M;
@@ -2727,24 +2746,47 @@ void beam_layout(BeamLayout& L, ArenaCursor& A, const fpe_beam_out& want, bool h
 // The launches of a prepared beam call on `stream`: S x (expand, the resume kernels through launch_plan, score / select / keep),
 // then the trace.  Nothing synchronises the host.
 int run_beam(fpe_engine* h, const CallPlan& cp, const fpe::BeamConsts& bc, const fpe_pose* d_poses, const fpe_stride* d_options,
-             const fpe_plan_state* d_stateIn, const BeamLayout& L, hipStream_t stream) {
+             const fpe_plan_state* d_stateIn, const BeamLayout& L, hipStream_t stream, BeamCheckCall* check) {
     const fpe::BeamShape& sh = L.sh;
     for (int s = 0; s < sh.S; ++s) {
         FPE_HIP(fpe::launch_beam_expand(sh, s, d_poses, d_options, d_stateIn, L.sc, stream));
         const int chains = sh.B * (s == 0 ? 1 : fpe::beam_live(sh, s - 1)) * sh.M;
         const fpe::PlanChain chain{L.sc.strides, (s == 0 && !d_stateIn) ? nullptr : L.sc.stateIn, L.sc.stateOut};
-        const int rc = launch_plan(h, cp, L.sc.poses, chains, sh.k, L.sc.cand, stream, chain);
+        fpe_plan_out cand = L.sc.cand;
+        if (s > 0) cand.stance = nullptr;  // (a checked beam's start feet: segment 0's alone)
+        int rc = launch_plan(h, cp, L.sc.poses, chains, sh.k, cand, stream, chain);
         if (rc != FPE_OK) return rc;
-        FPE_HIP(fpe::launch_beam_prune(bc, sh, s, L.sc, stream));
+        if (check) {
+            rc = beam_check_prune(*check, cp, bc, L, s, stream);
+            if (rc != FPE_OK) return rc;
+        } else {
+            FPE_HIP(fpe::launch_beam_prune(bc, sh, s, L.sc, stream));
+        }
     }
+    if (check) return beam_check_trace(*check, L, stream);
     FPE_HIP(fpe::launch_beam_trace(sh, L.sc, L.out, stream));
     return FPE_OK;
 }
+
+int beam_device_call(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, BeamCheckCall* check, const fpe_pose* d_poses,
+                     const fpe_plan_state* d_state_in, int32_t B, const fpe_stride* d_options, int32_t M, const fpe_beam_out* d_out,
+                     void* stream);
+int beam_host_call(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, BeamCheckCall* check, const fpe_pose* poses,
+                   const fpe_plan_state* state_in, const double* start_feet, int32_t B, const fpe_stride* options, int32_t M,
+                   const fpe_beam_out* out);
 }  // namespace
 
 int fpe_plan_beam_device(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_pose* d_poses,
                          const fpe_plan_state* d_state_in, int32_t B, const fpe_stride* d_options, int32_t M, const fpe_beam_out* d_out,
                          void* stream) {
+    return beam_device_call(h, params, beam, nullptr, d_poses, d_state_in, B, d_options, M, d_out, stream);
+}
+
+namespace {
+// The device form of every beam call; check's arguments that need no map are checked by the caller's entry point.
+int beam_device_call(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, BeamCheckCall* check, const fpe_pose* d_poses,
+                     const fpe_plan_state* d_state_in, int32_t B, const fpe_stride* d_options, int32_t M, const fpe_beam_out* d_out,
+                     void* stream) {
     BeamLayout L{};
     fpe::BeamConsts bc;
     int rc = check_beam_args(params, beam, B, M, d_out, bc, L.sh);
@@ -2758,18 +2800,41 @@ int fpe_plan_beam_device(fpe_handle h, const fpe_params* params, const fpe_beam_
     if (rc != FPE_OK) return rc;
     rc = check_packed_fits(cp, d_out->products.selected_packed != nullptr);
     if (rc != FPE_OK) return rc;
+    const bool wantStance = check && beam_check_wants_stance(*check, d_state_in != nullptr);
+    if (check) {
+        rc = beam_check_map(h, *check, *params, cp);
+        if (rc == FPE_OK) rc = beam_check_planes(*check, *params, cp, st);
+        if (rc != FPE_OK) return rc;
+        beam_check_mark_async(*check);
+    }
     ArenaCursor sizes;
-    beam_layout(L, sizes, *d_out, false);
+    beam_layout(L, sizes, *d_out, false, wantStance);
+    if (check) beam_check_layout(*check, L, sizes, false);
     mark_async_launch(cp);
     return with_stream_scratch(sizes.scratchBytes, st, [&](unsigned char* scratch) {
         ArenaCursor A{scratch};
-        beam_layout(L, A, *d_out, false);
-        return run_beam(h, cp, bc, d_poses, d_options, d_state_in, L, st);
+        beam_layout(L, A, *d_out, false, wantStance);
+        if (check) beam_check_layout(*check, L, A, false);
+        return run_beam(h, cp, bc, d_poses, d_options, d_state_in, L, st, check);
     });
 }
+}  // namespace
 
 int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_pose* poses, const fpe_plan_state* state_in,
                   int32_t B, const fpe_stride* options, int32_t M, const fpe_beam_out* out) {
+    return beam_host_call(h, params, beam, nullptr, poses, state_in, nullptr, B, options, M, out);
+}
+
+namespace {
+// Where a checked beam's host form finds the start feet it staged (device pointer; beam_check_prune reads it), and its look at
+// their values (the swing's segment ends: finite, within 1e6 m)
+void beam_check_set_start_feet(BeamCheckCall& bc, const double* d_startFeet);
+int beam_check_host_feet(const BeamCheckCall& bc, const double* startFeet, int32_t B);
+
+// The host form of every beam call (as beam_device_call); start_feet: a checked beam's, staged behind the states
+int beam_host_call(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, BeamCheckCall* check, const fpe_pose* poses,
+                   const fpe_plan_state* state_in, const double* start_feet, int32_t B, const fpe_stride* options, int32_t M,
+                   const fpe_beam_out* out) {
     BeamLayout L{};
     fpe::BeamConsts bc;
     int rc = check_beam_args(params, beam, B, M, out, bc, L.sh);
@@ -2781,27 +2846,41 @@ int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params*
     rc = check_host_strides(options, M);
     if (rc != FPE_OK) return rc;
     rc = check_host_states(state_in, B, L.sh.S * L.sh.k);
+    if (rc == FPE_OK && check) rc = beam_check_host_feet(*check, start_feet, B);
     if (rc != FPE_OK) return rc;
     const fpe::BeamShape want = L.sh;  // (the caller's arrays: W slots per root)
     L.sh.outStride = L.sh.slotStride;  // the arena's output block is dense: only live slots exist there
+    const bool wantStance = check && beam_check_wants_stance(*check, state_in != nullptr);
     ArenaCursor sizes;
-    beam_layout(L, sizes, *out, true);
-    // both arenas: [poses | options | state_in | outputs | scratch (device arena only)]; the inputs are read from the pinned arena
+    beam_layout(L, sizes, *out, true, wantStance);
+    if (check) beam_check_layout(*check, L, sizes, true);
+    // both arenas: [poses | options | state_in | start_feet | outputs | scratch (device arena only)]; the inputs are read from the pinned arena
     const size_t oOptions = align256(static_cast<size_t>(B) * sizeof(fpe_pose));
     const size_t oStates = oOptions + align256(static_cast<size_t>(M) * sizeof(fpe_stride));
-    const size_t szIn = oStates + (state_in ? align256(static_cast<size_t>(B) * sizeof(fpe_plan_state)) : 0);
+    const size_t oFeet = oStates + (state_in ? align256(static_cast<size_t>(B) * sizeof(fpe_plan_state)) : 0);
+    const size_t szIn = oFeet + (start_feet ? align256(static_cast<size_t>(B) * 12 * sizeof(double)) : 0);
     HostCall hc(h);
     CallCtx& cx = hc.cx;
     unsigned char* in = nullptr;
     rc = open_batch_call(h, hc, params, maxRadius, szIn + sizes.outBytes + sizes.scratchBytes, out->products.selected_packed != nullptr,
                          fpe::PlanForm::Resume, in);
     if (rc != FPE_OK) return rc;
+    if (check) {
+        rc = beam_check_map(h, *check, *params, hc.cp);
+        if (rc == FPE_OK) rc = beam_check_planes(*check, *params, hc.cp, cx.stream);
+        if (rc != FPE_OK) return rc;
+    }
     stage_batch_inputs(cx.pinned, 0, poses, nullptr, B, oStates, state_in);
     std::memcpy(cx.pinned + oOptions, options, static_cast<size_t>(M) * sizeof(fpe_stride));
+    if (start_feet) {
+        std::memcpy(cx.pinned + oFeet, start_feet, static_cast<size_t>(B) * 12 * sizeof(double));
+        beam_check_set_start_feet(*check, reinterpret_cast<const double*>(in + oFeet));
+    }
     ArenaCursor A{cx.dev + szIn + sizes.outBytes, cx.dev + szIn, szIn};
-    beam_layout(L, A, *out, true);
+    beam_layout(L, A, *out, true, wantStance);
+    if (check) beam_check_layout(*check, L, A, true);
     rc = run_beam(h, hc.cp, bc, reinterpret_cast<const fpe_pose*>(in), reinterpret_cast<const fpe_stride*>(in + oOptions),
-                  state_in ? reinterpret_cast<const fpe_plan_state*>(in + oStates) : nullptr, L, cx.stream);
+                  state_in ? reinterpret_cast<const fpe_plan_state*>(in + oStates) : nullptr, L, cx.stream, check);
     if (rc != FPE_OK) return rc;
     if (L.sh.outStride == want.outStride) return copy_out(h, cx, A.outs, cx.dev, cx.pinned);  // a full beam: the arena's arrays are the caller's
     // an underfilled beam (M^S < W: a few slots): one transfer, then every root's live slots to the head of its W slots — the dead
@@ -2821,6 +2900,7 @@ int fpe_plan_beam(fpe_handle h, const fpe_params* params, const fpe_beam_params*
     }
     return FPE_OK;
 }
+}  // namespace
 
 // ---- swing checks (fpe_swing_*; kernels: fpe_swing.hpp) ------------------------------------------------------------------------
 int fpe_swing_limits_defaults(fpe_swing_limits* out) {
@@ -3561,6 +3641,120 @@ int fpe_plan_rank_checked(fpe_handle h, const fpe_params* params, const fpe_rank
     const int rc = check_check_args(params, checks, check_out, cc);
     if (rc != FPE_OK) return rc;
     return rank_host_call(h, params, rank, &cc, poses, strides, B, n_cycles, K, out);
+}
+
+// ---- checked beam (fpe_plan_beam_checked*; kernels: fpe_beam_check.hpp) ---------------------------------------------------------
+namespace {
+// The check stage of one beam call: the checked ranking's (its fpe_check_out is not used: a beam's check outputs are per slot),
+// what the caller asked for, where the kernels write it, and the roots' start feet as the device sees them (null: the stance).
+struct BeamCheckCall {
+    CheckCall cc;
+    fpe_beam_check_out want{};  // the caller's arrays (null: not wanted; those of a disabled check: cleared)
+    fpe_beam_check_out out{};
+    const double* dStartFeet = nullptr;
+    bool haveStateIn = false;
+    int waves = 1;  // wavefronts per candidate of beam_check_kernel (beam_check_map)
+};
+
+// Arguments of a checked beam's check stage that need no map: check_check_args' rules, and the start feet a swing needs
+int check_beam_check_args(const fpe_params* params, const fpe_check_params* checks, const fpe_beam_check_out* out, bool haveStateIn,
+                          const double* startFeet, BeamCheckCall& bc) {
+    const int rc = check_check_args(params, checks, nullptr, bc.cc);
+    if (rc != FPE_OK) return rc;
+    const uint32_t on = bc.cc.stage.a.checks;
+    if ((on & FPE_CHECK_SWING) && haveStateIn && !startFeet)
+        return fail(FPE_E_INVALID_ARG, "a swing check of a beam from state_in needs start_feet: the state carries no z");
+    if (out) bc.want = *out;
+    if (!(on & FPE_CHECK_SWING)) bc.want.swing = nullptr;
+    if (!(on & FPE_CHECK_TRUNK)) bc.want.trunk = nullptr;
+    if (!(on & FPE_CHECK_MARGIN)) bc.want.margin = nullptr;
+    bc.dStartFeet = startFeet;
+    bc.haveStateIn = haveStateIn;
+    return FPE_OK;
+}
+
+// One wavefront per candidate keeps every SIMD busy where a record covers few cells; where it covers thousands, the three checks one
+// behind the other in one wavefront are the long pole and plan_check_kernel's four wavefronts per candidate win (measured at 198
+// and at 3 080 cells under the body box: DESIGN.md 4.21).  The cells under the body box stand for the size of every record.
+int beam_check_map(fpe_engine* h, BeamCheckCall& bc, const fpe_params& params, const CallPlan& cp) {
+    int32_t knob;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        knob = h->tuning.beamCheckWaves;
+    }
+    const double res = cp.snap->g.res;
+    const double boxCells = (static_cast<double>(params.length) / res) * (static_cast<double>(params.width) / res);
+    bc.waves = knob ? knob : (boxCells > 1024.0 ? 4 : 1);
+    return check_call_map(bc.cc, cp);
+}
+int beam_check_planes(BeamCheckCall& bc, const fpe_params& params, const CallPlan& cp, hipStream_t stream) {
+    return check_call_planes(bc.cc, params, cp, stream);
+}
+void beam_check_mark_async(const BeamCheckCall& bc) { check_call_mark_async(bc.cc); }
+bool beam_check_wants_stance(const BeamCheckCall& bc, bool haveStateIn) { return !bc.dStartFeet && !haveStateIn; }
+void beam_check_set_start_feet(BeamCheckCall& bc, const double* d_startFeet) { bc.dStartFeet = d_startFeet; }
+int beam_check_host_feet(const BeamCheckCall& bc, const double* startFeet, int32_t B) {
+    if (!(bc.cc.stage.a.checks & FPE_CHECK_SWING) || !startFeet) return FPE_OK;  // (without the swing they only pass through to `feet`)
+    for (int64_t q = 0; q < static_cast<int64_t>(B) * 4; ++q)
+        if (!swing_point_ok(startFeet + q * 3)) return fail(FPE_E_INVALID_ARG, "start feet must be finite and within 1e6 m");
+    return FPE_OK;
+}
+
+void beam_check_layout(BeamCheckCall& bc, BeamLayout& L, ArenaCursor& A, bool hostForm) {
+    const fpe::BeamShape& sh = L.sh;
+    const size_t slots_ = static_cast<size_t>(sh.B) * sh.slotStride, outSlots = static_cast<size_t>(sh.B) * sh.outStride;
+    const size_t chains = static_cast<size_t>(sh.B) * (sh.S > 1 ? fpe::beam_live(sh, sh.S - 2) : 1) * sh.M;
+    L.sc.candCheck = A.take(chains * fpe::kBeamCheckStateBytes);
+    L.sc.parentsCheck = A.take(slots_ * fpe::kBeamCheckStateBytes);
+    const auto out = [&](void* dst, size_t bytesPerSlot) {
+        if (!dst || !hostForm) return dst;
+        L.outSlot[A.outs.n] = bytesPerSlot;
+        return A.out(dst, bytesPerSlot * outSlots);
+    };
+    bc.out.swing = static_cast<fpe_swing_summary*>(out(bc.want.swing, sizeof(fpe_swing_summary)));
+    bc.out.trunk = static_cast<fpe_trunk_summary*>(out(bc.want.trunk, sizeof(fpe_trunk_summary)));
+    bc.out.margin = static_cast<fpe_margin_summary*>(out(bc.want.margin, sizeof(fpe_margin_summary)));
+    bc.out.base_penalty = static_cast<double*>(out(bc.want.base_penalty, sizeof(double)));
+    bc.out.hit = static_cast<uint8_t*>(out(bc.want.hit, 1));
+    bc.out.feet = static_cast<double*>(out(bc.want.feet, 12 * sizeof(double)));
+}
+
+int beam_check_prune(BeamCheckCall& bc, const CallPlan& cp, const fpe::BeamConsts& consts, const BeamLayout& L, int s, hipStream_t stream) {
+    bc.cc.stage.m = dev_map(*cp.snap);
+    bc.cc.stage.bm = bc.cc.planes.bits;
+    fpe::BeamCheckArgs args{};
+    args.bc = consts;
+    if (bc.dStartFeet) args.rootFeet = bc.dStartFeet, args.rootFeetStride = 12;
+    else if (!bc.haveStateIn) args.rootFeet = L.sc.cand.stance, args.rootFeetStride = 12 * L.sh.M;  // chain b * M: option 0's, as every option's
+    FPE_HIP(fpe::launch_beam_prune_checked(L.sh, s, L.sc, bc.cc.stage, args, bc.waves, stream));
+    return FPE_OK;
+}
+
+int beam_check_trace(BeamCheckCall& bc, const BeamLayout& L, hipStream_t stream) {
+    FPE_HIP(fpe::launch_beam_trace_checked(L.sh, L.sc, L.out, bc.cc.stage.a.checks, bc.out, stream));
+    return FPE_OK;
+}
+}  // namespace
+
+int fpe_plan_beam_checked_device(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_check_params* checks,
+                                 const fpe_pose* d_poses, const fpe_plan_state* d_state_in, const double* d_start_feet, int32_t B,
+                                 const fpe_stride* d_options, int32_t M, const fpe_beam_out* d_out,
+                                 const fpe_beam_check_out* d_check_out, void* stream) {
+    BeamCheckCall bc;
+    const int rc = check_beam_check_args(params, checks, d_check_out, d_state_in != nullptr, d_start_feet, bc);
+    if (rc != FPE_OK) return rc;
+    // no check enabled: the unchecked beam's launches, check_out not touched
+    return beam_device_call(h, params, beam, bc.cc.stage.a.checks ? &bc : nullptr, d_poses, d_state_in, B, d_options, M, d_out, stream);
+}
+
+int fpe_plan_beam_checked(fpe_handle h, const fpe_params* params, const fpe_beam_params* beam, const fpe_check_params* checks,
+                          const fpe_pose* poses, const fpe_plan_state* state_in, const double* start_feet, int32_t B,
+                          const fpe_stride* options, int32_t M, const fpe_beam_out* out, const fpe_beam_check_out* check_out) {
+    BeamCheckCall bc;
+    const int rc = check_beam_check_args(params, checks, check_out, state_in != nullptr, start_feet, bc);
+    if (rc != FPE_OK) return rc;
+    const uint32_t on = bc.cc.stage.a.checks;
+    return beam_host_call(h, params, beam, on ? &bc : nullptr, poses, state_in, on ? start_feet : nullptr, B, options, M, out);
 }
 
 int fpe_last_service_gate(fpe_handle h, fpe_service_gate* out) {

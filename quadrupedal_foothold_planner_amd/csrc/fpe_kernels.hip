@@ -2293,6 +2293,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_margin.hpp"
 // ---- part fourteen: the checked ranking (fpe_plan_rank_checked*; folds parts eleven to thirteen into part seven's keys) ----
 #include "fpe_check.hpp"
+// ---- part fifteen: the checked beam (fpe_plan_beam_checked*; folds part fourteen's parts into part nine's pruning) ----------
+#include "fpe_beam_check.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)

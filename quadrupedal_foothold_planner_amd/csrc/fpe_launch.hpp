@@ -348,6 +348,8 @@ struct BeamScratch {
     BeamSurvivor* surv;         // [S][B][slotStride]
     fpe_plan_state* parents;    // [B][slotStride] the states behind the last segment's survivors
     fpe_plan_out hist;          // [S][B][slotStride] blocks of k cycles: the requested products only
+    void* candCheck;            // [chains] the candidates' check states, kBeamCheckStateBytes each (a checked beam only: fpe_beam_check.hpp)
+    void* parentsCheck;         // [B][slotStride] those behind the last segment's survivors
 };
 int beam_live(const BeamShape& sh, int s);  // n_s = min(W, M^(s+1)): entries every root keeps behind segment s
 // Segment s: the candidates' inputs from the survivors of segment s - 1 (s = 0: from d_stateIn, or — null — none: the chains start
@@ -443,5 +445,31 @@ struct CheckStage {
 };
 // rank: the form behind rank_summary_kernel (reads score and poseSummary, writes score and keys), else the summaries and hit alone
 hipError_t launch_plan_check(const CheckStage& st, int B, int nCycles, bool rank, hipStream_t stream);
+
+
+// ---- checked beam (fpe_beam_check.hpp) -----------------------------------------------------------------------
+constexpr size_t kBeamCheckStateBytes = 208;  // one candidate's or parent's check state (BeamCheckState)
+// What beam_check_kernel takes beside the check stage's block.  The engine fills in bc, rootFeet and rootFeetStride;
+// launch_beam_prune_checked the rest, from the shape, the segment and the scratch.
+struct BeamCheckArgs {
+    int32_t nPrev, M, k, slotStride, seg;
+    int32_t rootFeetStride;      // doubles from one root's start feet to the next root's
+    BeamConsts bc;
+    const double* defaultNext;
+    const fpe_plan_state* stateOut;
+    const void* parents;         // the parents' check states; null in segment 0, which starts from
+    const double* rootFeet;      // the roots' start feet: the caller's, else the stance the segment's plan wrote (null: none, +0.0)
+    void* cand;
+    double* candPenalty;
+    double* candScore;
+    void* keys;
+};
+// Segment s behind its plan call: check and score (waves: 1 or 4 wavefronts per candidate), select, keep — launch_beam_prune's
+// three launches with the checks folded in
+hipError_t launch_beam_prune_checked(const BeamShape& sh, int s, const BeamScratch& sc, const CheckStage& st, const BeamCheckArgs& args,
+                                     int waves, hipStream_t stream);
+// launch_beam_trace with the check outputs (d_checkOut: device pointers, null: not wanted) of the enabled `checks`
+hipError_t launch_beam_trace_checked(const BeamShape& sh, const BeamScratch& sc, const fpe_beam_out& d_out, uint32_t checks,
+                                     const fpe_beam_check_out& d_checkOut, hipStream_t stream);
 
 }  // namespace fpe

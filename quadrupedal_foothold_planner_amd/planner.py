@@ -465,7 +465,7 @@ class FootholdPlanner(_Handle):
         return buf.value.decode()
 
     def set_tuning(self, **kw):
-        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
+        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, beam_check_waves, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
         for k, v in kw.items():
             self._check(self._lib.fpe_set_tuning(self._h, k.encode(), int(v)))
             self._tuning[k] = int(v)
@@ -623,6 +623,74 @@ class FootholdPlanner(_Handle):
         self._check(self._lib.fpe_plan_beam_device(self._h, ptr(self.params), C.byref(bp) if bp is not None else None, C.c_void_p(d_poses_ptr),
                                                    C.c_void_p(d_state_in_ptr) if d_state_in_ptr else None, int(B), C.c_void_p(d_options_ptr), int(M),
                                                    C.byref(bo), C.c_void_p(stream or 0)))
+
+    # ---- checked beam: the swing, trunk and margin checks folded into the beam's pruning (build-defined: fpe_plan_beam_checked*) ----
+    def plan_beam_checked(self, poses, options, beam=None, checks=None, states=None, start_feet=None, products=("nominal", "cycle_ok")):
+        """fpe_plan_beam_checked with host buffers: plan_beam with every candidate's path also reduced on the device to the enabled
+        checks' summaries, which enter the score and the class in every segment.  `checks`: as in plan_rank_checked; start_feet:
+        float64 [B, 4, 3] (x, y, z of RF, RH, LH, LF) where the roots' feet stand, or None (the plan's stance; with `states` a swing
+        check needs them).  Returns plan_beam's dict — "penalty" and "score" hold the checked values — plus, with any check enabled,
+        "base_penalty": float64 [B, W], "hit": uint8 [B, W] of FPE_CHECK_* bits, "feet": float64 [B, W, 4, 3] (the start_feet of a
+        following call, with "state" as its states) and "swing_summary" / "trunk_summary" / "margin_summary" [B, W] for the enabled
+        checks; slots w >= n_live[b] are left as allocated (zeros)."""
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE)
+        options = np.ascontiguousarray(options, dtype=STRIDE_DTYPE).reshape(-1)
+        B, M = poses.shape[0], options.shape[0]
+        unknown = set(products) - set(self.BEAM_PRODUCTS)
+        if unknown:
+            raise ValueError(f"a beam call has no products {sorted(unknown)}")
+        if states is not None:
+            states = np.ascontiguousarray(states, dtype=PLAN_STATE_DTYPE)
+            if states.shape != (B,):
+                raise ValueError(f"states must hold one element per pose: shape {states.shape}, {B} poses")
+        if start_feet is not None:
+            start_feet = np.ascontiguousarray(start_feet, dtype=np.float64)
+            if start_feet.shape != (B, 4, 3):
+                raise ValueError(f"start_feet must be [B, 4, 3]: shape {start_feet.shape}, {B} poses")
+        bp = _call_params(beam, _capi.BeamParams, _capi.beam_params_defaults)
+        shape = bp if bp is not None else _capi.beam_params_defaults()
+        S, k, W = max(int(shape.segments), 1), max(int(shape.cycles_per_segment), 1), max(int(shape.width), 1)
+        shapes = product_shapes(B * W, S * k)
+        out = {q: np.zeros(shapes[q][0], dtype=shapes[q][1]) for q in PRODUCT_ORDER if q in products}
+        out.update(path=np.zeros((B, W, S), np.uint8), score=np.zeros((B, W)), penalty=np.zeros((B, W)), n_live=np.zeros(B, np.int32),
+                   state=np.zeros((B, W), PLAN_STATE_DTYPE))
+        bo = _capi.BeamOut(ptr(out["n_live"]), ptr(out["score"]), ptr(out["penalty"]), ptr(out["path"]), ptr(out["state"]))
+        _fill_products(bo.products, {q: ptr(out[q]) for q in products})
+        cp = _check_params(checks)
+        on = cp.checks if cp is not None else _capi.CHECK_SWING | _capi.CHECK_TRUNK | _capi.CHECK_MARGIN
+        co = _capi.BeamCheckOut()
+        if on:
+            out.update(base_penalty=np.zeros((B, W)), hit=np.zeros((B, W), np.uint8), feet=np.zeros((B, W, 4, 3)))
+            co.base_penalty, co.hit, co.feet = ptr(out["base_penalty"]), ptr(out["hit"]), ptr(out["feet"])
+            for name, bit, dt in (("swing", _capi.CHECK_SWING, _capi.SWING_SUMMARY_DTYPE), ("trunk", _capi.CHECK_TRUNK, _capi.TRUNK_SUMMARY_DTYPE),
+                                  ("margin", _capi.CHECK_MARGIN, _capi.MARGIN_SUMMARY_DTYPE)):
+                if on & bit:
+                    out[name + "_summary"] = np.zeros((B, W), dt)
+                    setattr(co, name, ptr(out[name + "_summary"]))
+        self._check(self._lib.fpe_plan_beam_checked(self._h, ptr(self.params), C.byref(bp) if bp is not None else None,
+                                                    C.byref(cp) if cp is not None else None, ptr(poses), ptr(states), ptr(start_feet), B,
+                                                    ptr(options), M, C.byref(bo), C.byref(co)))
+        for q in products:
+            out[q] = out[q].reshape((B, W) + out[q].shape[1:])
+        return out
+
+    def plan_beam_checked_device(self, d_poses_ptr, B, d_options_ptr, M, d_path_ptr, beam=None, checks=None, d_state_in_ptr=0,
+                                 d_start_feet_ptr=0, d_n_live_ptr=0, d_score_ptr=0, d_penalty_ptr=0, d_state_ptr=0, products=None,
+                                 check_out=None, stream=0):
+        """fpe_plan_beam_checked_device: plan_beam_device's arguments plus `checks` (as plan_rank_checked), the roots' start feet
+        ([B, 4, 3] doubles; 0: the stance) and check_out: a dict {"swing" | "trunk" | "margin" | "base_penalty" | "hit" | "feet":
+        device pointer} of the per-slot check outputs wanted (None: none)."""
+        bo = _capi.BeamOut(d_n_live_ptr or None, d_score_ptr or None, d_penalty_ptr or None, d_path_ptr or None, d_state_ptr or None)
+        _fill_products(bo.products, products or {})
+        bp = _call_params(beam, _capi.BeamParams, _capi.beam_params_defaults)
+        cp = _check_params(checks)
+        co = _capi.BeamCheckOut(**{k: (v or None) for k, v in check_out.items()}) if check_out is not None else None
+        self._check(self._lib.fpe_plan_beam_checked_device(self._h, ptr(self.params), C.byref(bp) if bp is not None else None,
+                                                           C.byref(cp) if cp is not None else None, C.c_void_p(d_poses_ptr),
+                                                           C.c_void_p(d_state_in_ptr) if d_state_in_ptr else None,
+                                                           C.c_void_p(d_start_feet_ptr) if d_start_feet_ptr else None, int(B),
+                                                           C.c_void_p(d_options_ptr), int(M), C.byref(bo),
+                                                           C.byref(co) if co is not None else None, C.c_void_p(stream or 0)))
 
     # ---- chained plan, device-resident (torch tensors / raw pointers) ----------------------------------
     def plan_device(self, d_poses_ptr, B, n_cycles, d_nominal_ptr=0, d_centroid_ptr=0, d_default_ptr=0,
