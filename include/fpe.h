@@ -273,6 +273,8 @@ int fpe_destroy(fpe_handle h);
  * fail_kind, not only the return value.  "service_cycle0_gate_only" (older name): 1 = service_opt_gate 0, 0 = 2.
  * "beam_check_waves": the wavefronts per candidate of the checked beam's check kernel (fpe_plan_beam_checked*): 0 (DEFAULT) by the
  * map's resolution, 1 or 4 forced; the outputs do not depend on it.
+ * "scan_merge": the form of the two point passes of fpe_scan_fuse*: 0 (DEFAULT) the engine's choice, 1 plain, 2 merged (see there);
+ * the outputs do not depend on it.
  * "service_overlap" (default 1): a call that runs the plan AND the opt track for at most four poses launches the opt
  * track's chain on a second stream beside the plan kernel, on nominal cycle flags of 1 (the flags only decide which cycles the
  * chain commits, cpp:1323-1332, and are 1 unless a nominal search fails), and runs it again on the real flags in the call where
@@ -1477,6 +1479,128 @@ int fpe_plan_beam_checked_device(fpe_handle h, const fpe_params* params, const f
                                  const fpe_pose* d_poses, const fpe_plan_state* d_state_in, const double* d_start_feet, int32_t B,
                                  const fpe_stride* d_options, int32_t M, const fpe_beam_out* d_out,
                                  const fpe_beam_check_out* d_check_out, void* stream);
+
+/* ---- scan fusion: point clouds into the elevation layer on the device ---------------------------------------------------------------
+ * BUILD-DEFINED (the reference's bring-up starts elevation_mapping ahead of the producer above, launch/mapping.launch:9-13; that
+ * package is not part of the reference and no version is pinned: parity is against the build's own numpy statement,
+ * tests/scan_reference.py).  One depth or lidar scan is fused into a robot-centric height map that lives in HBM, and the rectangle it
+ * touched goes into the planner's snapshot through fpe_update_elevation_device without crossing the host link.  Every per-cell
+ * reduction is an INTEGER reduction, so the result does not depend on the order in which the points arrive.
+ *
+ * 1. The scan state (fpe_scan_handle; owned by the engine it was created on; destroy it before that engine).  Two canonical device
+ *    layers of one geometry {rows, cols, resolution, position}: `elevation` and `variance`, row-major, start index (0, 0).
+ *    INVARIANT: in both layers a cell is unknown iff it holds the quiet NaN 0x7FC00000 (both layers hold it then).
+ *     - create: every cell unknown.  Of `geom`, start_index must be (0, 0) and storage_order 1 (FPE_E_INVALID_ARG otherwise).
+ *       Scratch of 16 bytes per state cell and a second pair of layer buffers are allocated here.
+ *     - set_layers: rows * cols floats each, canonical; a cell that is NaN in either source becomes unknown in both layers.
+ *     - read_layers: either pointer may be NULL, not both.
+ *     - move: new cell (i, j) takes old cell (i + sr, j + sc) of both layers bit for bit, or becomes unknown where that lies outside
+ *       (fpe_update_map's steps 1-2); |shift| >= size is valid; the geometry's position becomes `position` (finite).  The state
+ *       holds a second buffer pair and swaps: nothing is shifted in place.
+ *    Ordering: a state keeps an event behind its last operation and every operation waits GPU-side for it before its first kernel
+ *    or copy, on whatever stream it runs (the filter scratch's pattern); the device forms never synchronise the host.  The host
+ *    forms run on a stream of the state's and return complete.  Operations of one state serialise on the host.
+ *
+ * 2. Fusing one scan (fpe_scan_fuse[_device]).  THE CONTRACT.  Every product and every sum is rounded on its own (no contraction), in
+ *    the order written; f32 divisions are IEEE.  T = scan->sensor_to_map, (xs, ys, zs) the point's three floats as doubles.
+ *    Per point, in f64; the FIRST failing test decides the drop counter:
+ *      1. dropped_nonfinite  if any of the three floats is not finite;
+ *      2. dropped_range      unless  double(min_range) * double(min_range) <= (xs*xs + ys*ys) + zs*zs <= double(max_range) * double(max_range);
+ *      3. xm = ((T0*xs + T1*ys) + T2*zs) + T3;  ym = ((T4*xs + T5*ys) + T6*zs) + T7;  zm = ((T8*xs + T9*ys) + T10*zs) + T11;
+ *      4. dropped_height     unless  double(min_z) <= zm <= double(max_z);
+ *      5. dropped_off_roi    unless  checkIfPositionWithinMap holds on both axes (t = -((x - position) - 0.5 * length); 0 <= t < length)
+ *                            and the cell (getIndexFromPosition, -(int)(((x - 0.5 * length) - position) / resolution), the true
+ *                            division) lies inside scan->roi;
+ *      6. otherwise ACCEPTED, with q = (int32) rint(zm * 65536.0)   (|zm| <= 16384, so |q| <= 2^30).
+ *    Per roi cell with accepted points:
+ *      top = max q;  band_q = rint(double(band) * 65536.0), taken as 2^31 when it is larger (a band beyond 32768 m keeps every point);
+ *      KEPT are the points with q >= top - band_q (in 64 bits): n their count, S the 64-bit sum of their q; the others count into
+ *      below_band;  z_m = (float)((double(S) / double(n)) * (1.0 / 65536.0));
+ *      dx = cx - T3, dy = cy - T7 with (cx, cy) the cell's centre (getPositionFromIndex: (position + (0.5 * length - 0.5 * resolution))
+ *      + resolution * double(-index));  d2 = (float)(dx*dx + dy*dy), the sum in f64;
+ *      v_m = max((var_base + var_range * d2) / (float)n, var_min)   in f32.
+ *    Fusing with the prior (h, v) of the cell, in f32:
+ *      prior unknown                       -> NEW:      h' = z_m;  v' = min(v_m, var_max)
+ *      else d = z_m - h;  s = v + v_m;
+ *        d*d > (gate*gate) * s             -> OUTLIER:  replace_count > 0 && n >= replace_count -> REPLACED: NEW's values;
+ *                                                       otherwise h' = h;  v' = min(v + var_outlier, var_max)
+ *        otherwise                         -> FUSED:    k = v / s;  h' = h + k*d;  v' = min(max(v - k*v, var_min), var_max)
+ *    (min / max are fminf / fmaxf.  Should h' or v' come out NaN — a prior of infinities —, the cell becomes unknown in both layers:
+ *    the invariant holds whatever the layers were set to.)  A cell with no accepted point is NOT WRITTEN: its bytes stay.
+ *    info counts what the names say: n_points = scan->n_points = the five point classes' sum; cells_touched = cells_new + cells_fused +
+ *    cells_outlier; cells_outlier INCLUDES cells_replaced; bbox in the state's indices.
+ *    Refusals (nothing written, nothing queued; FPE_E_INVALID_ARG): null arguments (the device form's d_info may be NULL), n_points
+ *    outside 0..FPE_SCAN_MAX_POINTS, point_stride < 3, a reserved field that is not 0, a roi that is empty or reaches outside the
+ *    state, a non-finite transform or parameter, min_range > max_range, min_z > max_z, |min_z| or |max_z| > 16384, a negative
+ *    variance parameter (var_base, var_range, var_min, var_max, var_outlier), var_min > var_max, gate <= 0, band < 0.
+ *    fpe_scan_validate is that same routine without an engine (of `geom`: rows, cols, resolution).
+ *    Forms.  Host: host points, host info (may be NULL), synchronous.  Device: device points, device info (16 int32; may be NULL),
+ *    asynchronous on `stream`, never synchronises the host — except that the 8-byte point records of the passes grow on demand: the
+ *    FIRST call of a state with a larger n_points than any before allocates (hipMalloc / hipFree, which synchronise the device).
+ *    Three launches: scan_top_kernel (classify, integer max per cell, one 8-byte record per point), scan_sum_kernel (count and 64-bit
+ *    sum of the kept points, integer atomics only), scan_fuse_kernel (one lane per roi cell: the rule above, both layers, info, and
+ *    the cell's scratch words reset, so no call starts with a memset).  No float atomics anywhere.  fpe_set_tuning "scan_merge":
+ *    0 (DEFAULT) the engine's choice, 1 the plain form (one atomic per point), 2 the merged form (runs of equal cells across
+ *    adjacent lanes of a wavefront are reduced in registers first: one atomic per run); the outputs do not depend on it.
+ *
+ * 3. Into the planner's snapshot.
+ *     - fpe_scan_install: the state's content becomes the engine's current snapshot: fpe_traversability_device on the state's
+ *       elevation with the state's geometry and d_layers == NULL, then fpe_upload_map_device of that traversability and the elevation.
+ *       fp == NULL: the defaults.  Returns what those two return.
+ *     - fpe_scan_ingest_device, in this order: fpe_scan_move when `shift` is not (0, 0) or `position` differs from the state's; the
+ *       fuse; fpe_update_elevation_device with that shift and position and ONE patch: scan->roi, pointing into the state's elevation
+ *       layer (row-major with a pitch: row_stride = cols).  The snapshot is byte for byte what those three public calls leave.
+ *       Refused as a whole (nothing moved, written, queued or installed): everything the fuse refuses; a non-finite position;
+ *       FPE_E_NO_MAP before any map exists; FPE_E_INVALID_ARG when the snapshot's rows, cols or resolution differ from the state's;
+ *       what fpe_update_elevation_device refuses for these filter parameters (fp == NULL: the defaults).  update_info may be NULL.
+ *     - fpe_scan_ingest: the same with host points and a host scan info; synchronous.
+ *    PROMISED: after an install and any sequence of ingests, fpe_read_map_layers' elevation equals the state's elevation bit for bit. */
+#define FPE_SCAN_MAX_POINTS (1 << 22)
+typedef struct fpe_scan_state* fpe_scan_handle;
+typedef struct fpe_scan_params {   /* 48 bytes */
+    float min_range, max_range;    /* on |p|^2 in the sensor frame */
+    float min_z, max_z;            /* map-frame height window; |.| <= 16384 */
+    float band;                    /* m below a cell's top that still counts as the surface */
+    float var_base, var_range;     /* one point's variance at a cell: var_base + var_range * d2 */
+    float var_min, var_max;
+    float gate;                    /* sigmas */
+    float var_outlier;             /* added to a cell's variance by a gated-out scan */
+    int32_t replace_count;         /* a gated-out cell with >= this many kept points is replaced; 0 = never */
+} fpe_scan_params;
+typedef struct fpe_scan {          /* 128 bytes */
+    double sensor_to_map[12];      /* row-major 3 x 4: m = R p + t */
+    int32_t n_points;              /* 0 .. FPE_SCAN_MAX_POINTS */
+    int32_t point_stride;          /* floats per point, >= 3; x, y, z first */
+    int32_t roi[4];                /* row0, col0, n_rows, n_cols in the state's indices; non-empty, inside */
+    int32_t reserved[2];           /* 0 */
+} fpe_scan;
+typedef struct fpe_scan_info {     /* 64 bytes, sixteen int32 */
+    int32_t n_points, dropped_nonfinite, dropped_range, dropped_height, dropped_off_roi, accepted, below_band,
+            cells_touched, cells_new, cells_fused, cells_outlier, cells_replaced;
+    int32_t bbox[4];               /* row_min, col_min, row_max, col_max of touched cells; {0,0,-1,-1} when none */
+} fpe_scan_info;
+/* min_range 0.1, max_range 10, min_z -100, max_z 100, band 0.05, var_base 1e-4, var_range 1e-4, var_min 1e-6, var_max 1.0, gate 3,
+ * var_outlier 1e-3, replace_count 0 */
+int fpe_scan_params_defaults(fpe_scan_params* out);
+int fpe_scan_validate(const fpe_map_desc* geom, const fpe_scan_params* sp, const fpe_scan* scan);   /* host arithmetic only; no engine */
+int fpe_scan_create(fpe_handle h, const fpe_map_desc* geom, fpe_scan_handle* out);
+int fpe_scan_destroy(fpe_scan_handle s);
+int fpe_scan_geometry(fpe_scan_handle s, fpe_map_desc* out);
+int fpe_scan_set_layers(fpe_scan_handle s, const float* elevation, const float* variance);                           /* host; synchronous */
+int fpe_scan_set_layers_device(fpe_scan_handle s, const float* d_elevation, const float* d_variance, void* stream);
+int fpe_scan_read_layers(fpe_scan_handle s, float* elevation, float* variance);                                      /* host; synchronous */
+int fpe_scan_read_layers_device(fpe_scan_handle s, float* d_elevation, float* d_variance, void* stream);
+int fpe_scan_move(fpe_scan_handle s, const int32_t shift[2], const double position[2], void* stream);                /* asynchronous */
+int fpe_scan_fuse(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const float* points, fpe_scan_info* info);
+int fpe_scan_fuse_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const float* d_points,
+                         fpe_scan_info* d_info, void* stream);
+int fpe_scan_install(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, void* stream);
+int fpe_scan_ingest(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan,
+                    const float* points, const int32_t shift[2], const double position[2], fpe_scan_info* scan_info,
+                    fpe_elevation_update_info* update_info);
+int fpe_scan_ingest_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan,
+                           const float* d_points, const int32_t shift[2], const double position[2], fpe_scan_info* d_scan_info,
+                           fpe_elevation_update_info* update_info, void* stream);
 
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,

@@ -407,6 +407,31 @@ class BeamCheckOut(C.Structure):
 
 assert (C.sizeof(CheckParams), C.sizeof(CheckOut), C.sizeof(BeamCheckOut)) == (160, 40, 48)
 
+SCAN_MAX_POINTS = 1 << 22  # FPE_SCAN_MAX_POINTS
+
+
+class ScanParams(C.Structure):
+    """fpe_scan_params: the point tests (range, height window), the surface band, the variance model and the gate of a scan fusion."""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("min_z", C.c_float), ("max_z", C.c_float), ("band", C.c_float),
+                ("var_base", C.c_float), ("var_range", C.c_float), ("var_min", C.c_float), ("var_max", C.c_float), ("gate", C.c_float),
+                ("var_outlier", C.c_float), ("replace_count", C.c_int32)]
+
+
+class Scan(C.Structure):
+    """fpe_scan: one scan's sensor-to-map transform (row-major 3 x 4), point count and stride, and the roi it may write."""
+    _fields_ = [("sensor_to_map", C.c_double * 12), ("n_points", C.c_int32), ("point_stride", C.c_int32), ("roi", C.c_int32 * 4),
+                ("reserved", C.c_int32 * 2)]
+
+
+# fpe_scan_info: sixteen int32 (the array form is what a device info is read back as)
+SCAN_INFO_DTYPE = np.dtype(
+    [("n_points", "<i4"), ("dropped_nonfinite", "<i4"), ("dropped_range", "<i4"), ("dropped_height", "<i4"), ("dropped_off_roi", "<i4"),
+     ("accepted", "<i4"), ("below_band", "<i4"), ("cells_touched", "<i4"), ("cells_new", "<i4"), ("cells_fused", "<i4"),
+     ("cells_outlier", "<i4"), ("cells_replaced", "<i4"), ("bbox", "<i4", (4,))],
+    align=True,
+)
+assert (C.sizeof(ScanParams), C.sizeof(Scan), SCAN_INFO_DTYPE.itemsize) == (48, 128, 64)
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -427,6 +452,7 @@ STRUCTS = {
     "fpe_margin_params": MarginParams, "fpe_margin_map_out": MarginMapOut, "fpe_margin_query": MARGIN_QUERY_DTYPE,
     "fpe_margin_record": MARGIN_RECORD_DTYPE, "fpe_margin_summary": MARGIN_SUMMARY_DTYPE, "fpe_margin_out": MarginOut,
     "fpe_check_params": CheckParams, "fpe_check_out": CheckOut, "fpe_beam_check_out": BeamCheckOut,
+    "fpe_scan_params": ScanParams, "fpe_scan": Scan, "fpe_scan_info": SCAN_INFO_DTYPE,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -538,6 +564,21 @@ PROTOTYPES = {
     "fpe_plan_beam_checked": (cint, [vp, vp, P(BeamParams), P(CheckParams), vp, vp, vp, i32, vp, i32, P(BeamOut), P(BeamCheckOut)]),
     "fpe_plan_beam_checked_device": (cint, [vp, vp, P(BeamParams), P(CheckParams), vp, vp, vp, i32, vp, i32, P(BeamOut), P(BeamCheckOut),
                                             vp]),
+    "fpe_scan_params_defaults": (cint, [P(ScanParams)]),
+    "fpe_scan_validate": (cint, [P(MapDesc), P(ScanParams), P(Scan)]),
+    "fpe_scan_create": (cint, [vp, P(MapDesc), P(vp)]),
+    "fpe_scan_destroy": (cint, [vp]),
+    "fpe_scan_geometry": (cint, [vp, P(MapDesc)]),
+    "fpe_scan_set_layers": (cint, [vp, vp, vp]),
+    "fpe_scan_set_layers_device": (cint, [vp, vp, vp, vp]),
+    "fpe_scan_read_layers": (cint, [vp, vp, vp]),
+    "fpe_scan_read_layers_device": (cint, [vp, vp, vp, vp]),
+    "fpe_scan_move": (cint, [vp, P(i32), P(f64), vp]),
+    "fpe_scan_fuse": (cint, [vp, P(ScanParams), P(Scan), vp, vp]),
+    "fpe_scan_fuse_device": (cint, [vp, P(ScanParams), P(Scan), vp, vp, vp]),
+    "fpe_scan_install": (cint, [vp, vp, P(FilterParams), vp]),
+    "fpe_scan_ingest": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(Scan), vp, P(i32), P(f64), vp, P(ElevationUpdateInfo)]),
+    "fpe_scan_ingest_device": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(Scan), vp, P(i32), P(f64), vp, P(ElevationUpdateInfo), vp]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

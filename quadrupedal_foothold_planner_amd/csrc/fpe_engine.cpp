@@ -1632,6 +1632,9 @@ int fpe_set_tuning(fpe_handle h, const char* key, int32_t value) {
     } else if (k == "beam_check_waves") {
         if (value != 0 && value != 1 && value != 4) return fail(FPE_E_INVALID_ARG, "beam_check_waves is 0 (automatic), 1 or 4");
         h->tuning.beamCheckWaves = value;
+    } else if (k == "scan_merge") {
+        if (value < 0 || value > 2) return fail(FPE_E_INVALID_ARG, "scan_merge is 0 (the engine's choice), 1 (plain) or 2 (merged)");
+        h->tuning.scanMerge = value;
     } else if (k == "service_overlap") h->tuning.serviceOverlap = value ? 1 : 0;
     else if (k == "service_poll") h->tuning.servicePoll = value ? 1 : 0;
     else if (k == "service_cycle0_gate_only") h->tuning.serviceOptGate = value ? 0 : 2;  // (older name)
@@ -3955,6 +3958,370 @@ int fpe_plan_service_opt(fpe_handle h, const fpe_params* params, const fpe_opt_p
         *n_default_rows = rows;
     }
     return FPE_OK;
+}
+
+}  // extern "C"
+
+// ---- scan fusion (fpe_scan_*; include/fpe.h): the scan state, the fuse, and the way into the planner's snapshot ------------------
+// A state owns two pairs of canonical layers (the current one and the one a move writes), the fuse's scratch (16 bytes per cell, at
+// rest between calls), the accumulators of a call's info, the point records (grown on demand) and — for the host forms — a stream,
+// a points staging buffer and a device info.  Ordering: `last` is recorded behind every operation on whatever stream it ran, and
+// every operation waits for it GPU-side first (the filter scratch's pattern, filter_slot_take); `mu` makes the order in which the
+// operations are queued the order of those events.
+struct fpe_scan_state {
+    fpe_engine* h = nullptr;
+    std::mutex mu;
+    fpe::MapGeom g;
+    size_t n = 0;
+    float* elev[2] = {nullptr, nullptr};  // [cur]: the layer; [cur ^ 1]: the second buffer (a move's destination, a host set's staging)
+    float* var[2] = {nullptr, nullptr};
+    int cur = 0;
+    fpe::ScanCell* cells = nullptr;
+    int32_t* acc = nullptr;  // kScanAccWords accumulators, then sixteen words: the host forms' device info
+    uint2* rec = nullptr;
+    size_t recCap = 0;       // records
+    float* pts = nullptr;
+    size_t ptsCap = 0;       // floats
+    float* trav = nullptr;   // fpe_scan_install's traversability layer (allocated by the first install)
+    hipEvent_t last = nullptr;
+    hipStream_t own = nullptr;
+};
+
+namespace {
+
+constexpr int kScanMergeDefault = 2;  // "scan_merge" 0: the form measured faster on both workloads of profiles/scan_summary.txt
+
+// An operation of a state on `stream`: behind the state's last one, and its own event recorded on every way out (an operation that
+// failed half-way may have queued work the next one must not overtake).  The caller holds s->mu.
+struct ScanOp {
+    fpe_scan_state* s;
+    hipStream_t stream;
+    bool entered = false;
+    int enter() {
+        FPE_HIP(hipSetDevice(s->h->device));
+        FPE_HIP(hipStreamWaitEvent(stream, s->last, 0));
+        entered = true;
+        return FPE_OK;
+    }
+    ~ScanOp() {
+        if (entered) (void)hipEventRecord(s->last, stream);
+    }
+};
+
+fpe_map_desc scan_desc(const fpe_scan_state* s) {
+    fpe_map_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.rows = s->g.rows;
+    d.cols = s->g.cols;
+    d.resolution = s->g.res;
+    d.position[0] = s->g.posX;
+    d.position[1] = s->g.posY;
+    d.storage_order = 1;
+    return d;
+}
+
+template <class T>
+int scan_grow(T*& buf, size_t& cap, size_t want) {
+    if (want <= cap) return FPE_OK;
+    T* p = nullptr;
+    FPE_HIP(hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T)));
+    if (buf) (void)hipFree(buf);  // (synchronises the device: nothing still reads the old buffer)
+    buf = p;
+    cap = want;
+    return FPE_OK;
+}
+
+int scan_set_layers(fpe_scan_state* s, const float* elev, const float* var, bool onDevice, hipStream_t stream) {
+    if (!s || !elev || !var) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    ScanOp op{s, onDevice ? stream : s->own};
+    int rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    const int c = s->cur;
+    if (!onDevice) {  // staged in the second buffer pair
+        FPE_HIP(hipMemcpyAsync(s->elev[c ^ 1], elev, s->n * sizeof(float), hipMemcpyHostToDevice, op.stream));
+        FPE_HIP(hipMemcpyAsync(s->var[c ^ 1], var, s->n * sizeof(float), hipMemcpyHostToDevice, op.stream));
+        elev = s->elev[c ^ 1];
+        var = s->var[c ^ 1];
+    }
+    FPE_HIP(fpe::launch_scan_set(reinterpret_cast<const uint32_t*>(elev), reinterpret_cast<const uint32_t*>(var), reinterpret_cast<uint32_t*>(s->elev[c]),
+                                 reinterpret_cast<uint32_t*>(s->var[c]), s->n, op.stream));
+    if (!onDevice) FPE_HIP(hipStreamSynchronize(op.stream));
+    return FPE_OK;
+}
+
+int scan_read_layers(fpe_scan_state* s, float* elev, float* var, bool onDevice, hipStream_t stream) {
+    if (!s || (!elev && !var)) return fail(FPE_E_INVALID_ARG, "null state, or no layer requested");
+    std::lock_guard<std::mutex> lk(s->mu);
+    ScanOp op{s, onDevice ? stream : s->own};
+    int rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    const hipMemcpyKind kind = onDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (elev) FPE_HIP(hipMemcpyAsync(elev, s->elev[s->cur], s->n * sizeof(float), kind, op.stream));
+    if (var) FPE_HIP(hipMemcpyAsync(var, s->var[s->cur], s->n * sizeof(float), kind, op.stream));
+    if (!onDevice) FPE_HIP(hipStreamSynchronize(op.stream));
+    return FPE_OK;
+}
+
+// (the caller holds s->mu and has entered `stream`)
+int scan_move_locked(fpe_scan_state* s, const int32_t shift[2], const double position[2], hipStream_t stream) {
+    const int rows = s->g.rows, cols = s->g.cols, c = s->cur;
+    const int sr = std::max(-rows, std::min(rows, shift[0])), sc = std::max(-cols, std::min(cols, shift[1]));  // beyond: nothing is carried either way
+    FPE_HIP(fpe::launch_scan_move(reinterpret_cast<const uint32_t*>(s->elev[c]), reinterpret_cast<const uint32_t*>(s->var[c]),
+                                  reinterpret_cast<uint32_t*>(s->elev[c ^ 1]), reinterpret_cast<uint32_t*>(s->var[c ^ 1]), rows, cols, sr, sc, stream));
+    s->cur = c ^ 1;
+    s->g = fpe::make_geom(rows, cols, s->g.res, position[0], position[1]);
+    return FPE_OK;
+}
+
+// The three passes on `stream` (the caller holds s->mu, has validated the call and has entered `stream`).
+int scan_fuse_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan, const float* d_points, fpe_scan_info* d_info, hipStream_t stream) {
+    int rc = scan_grow(s->rec, s->recCap, static_cast<size_t>(scan->n_points));
+    if (rc != FPE_OK) return rc;
+    int merge;
+    {
+        std::lock_guard<std::mutex> lk(s->h->mu);
+        merge = s->h->tuning.scanMerge;
+    }
+    if (merge == 0) merge = kScanMergeDefault;
+    fpe::ScanArgs a;
+    fpe::scan_consts(*sp, *scan, s->g, a);
+    a.points = d_points;
+    a.rec = s->rec;
+    a.cells = s->cells;
+    a.acc = s->acc;
+    a.elev = reinterpret_cast<uint32_t*>(s->elev[s->cur]);
+    a.var = reinterpret_cast<uint32_t*>(s->var[s->cur]);
+    a.info = reinterpret_cast<int32_t*>(d_info);
+    FPE_HIP(fpe::launch_scan_fuse(a, merge == 2, stream));
+    return FPE_OK;
+}
+
+int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan) {
+    const char* why = "";
+    const int rc = fpe::check_scan(s->g.rows, s->g.cols, sp, scan, &why);
+    return rc == FPE_OK ? rc : fail(rc, why);
+}
+
+// Host points into the state's staging buffer on its own stream (entered)
+int scan_stage_points(fpe_scan_state* s, const fpe_scan* scan, const float* points) {
+    const size_t nf = static_cast<size_t>(scan->n_points) * static_cast<size_t>(scan->point_stride);
+    const int rc = scan_grow(s->pts, s->ptsCap, std::max<size_t>(nf, 3));
+    if (rc != FPE_OK) return rc;
+    if (nf) FPE_HIP(hipMemcpyAsync(s->pts, points, nf * sizeof(float), hipMemcpyHostToDevice, s->own));
+    return FPE_OK;
+}
+
+int scan_fuse_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan, const float* points, fpe_scan_info* info, bool onDevice,
+                     hipStream_t stream) {
+    if (!s || !points) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    int rc = scan_check(s, sp, scan);
+    if (rc != FPE_OK) return rc;
+    ScanOp op{s, onDevice ? stream : s->own};
+    rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    if (onDevice) return scan_fuse_locked(s, sp, scan, points, info, stream);
+    rc = scan_stage_points(s, scan, points);
+    if (rc != FPE_OK) return rc;
+    fpe_scan_info* dInfo = reinterpret_cast<fpe_scan_info*>(s->acc + fpe::kScanAccWords);
+    rc = scan_fuse_locked(s, sp, scan, s->pts, dInfo, s->own);
+    if (rc != FPE_OK) return rc;
+    fpe_scan_info got;
+    FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, s->own));
+    FPE_HIP(hipStreamSynchronize(s->own));
+    if (info) *info = got;
+    return FPE_OK;
+}
+
+int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan, const float* points,
+                       const int32_t shift[2], const double position[2], fpe_scan_info* scanInfo, fpe_elevation_update_info* updateInfo, bool onDevice,
+                       hipStream_t stream) {
+    if (!h || !s || !points || !shift || !position) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (s->h != h) return fail(FPE_E_INVALID_ARG, "the scan state belongs to another engine");
+    std::lock_guard<std::mutex> lk(s->mu);
+    // every refusal ahead of the first queued operation
+    int rc = scan_check(s, sp, scan);
+    if (rc != FPE_OK) return rc;
+    fpe_map_update u;
+    std::memset(&u, 0, sizeof(u));
+    u.shift[0] = shift[0];
+    u.shift[1] = shift[1];
+    u.position[0] = position[0];
+    u.position[1] = position[1];
+    u.n_patches = 1;
+    auto patch = [&]() {  // scan->roi of the state's CURRENT elevation layer, row-major with the layer's pitch
+        const float* e = s->elev[s->cur] + static_cast<size_t>(scan->roi[0]) * s->g.cols + scan->roi[1];
+        u.patch[0] = fpe_map_patch{scan->roi[0], scan->roi[1], scan->roi[2], scan->roi[3], nullptr, e, s->g.cols, 1};
+    };
+    patch();
+    {
+        std::shared_ptr<MapSnapshot> snap;
+        {
+            std::lock_guard<std::mutex> lkE(h->mu);
+            snap = h->map;
+        }
+        if (!snap) return fail(FPE_E_NO_MAP, "no map uploaded");
+        if (snap->g.rows != s->g.rows || snap->g.cols != s->g.cols || snap->g.res != s->g.res)
+            return fail(FPE_E_INVALID_ARG, "the snapshot's size or resolution differs from the scan state's");
+        fpe::ElevationUpdatePlan plan;
+        const char* why = "";
+        rc = fpe::plan_elevation_update(s->g.rows, s->g.cols, s->g.res, fp, &u, plan, &why);
+        if (rc != FPE_OK) return fail(rc, why);
+    }
+    ScanOp op{s, onDevice ? stream : s->own};
+    rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    fpe_scan_info* dInfo = scanInfo;
+    if (!onDevice) {
+        rc = scan_stage_points(s, scan, points);
+        if (rc != FPE_OK) return rc;
+        points = s->pts;
+        dInfo = reinterpret_cast<fpe_scan_info*>(s->acc + fpe::kScanAccWords);
+    }
+    if (shift[0] != 0 || shift[1] != 0 || position[0] != s->g.posX || position[1] != s->g.posY) {
+        rc = scan_move_locked(s, shift, position, op.stream);
+        if (rc != FPE_OK) return rc;
+        patch();  // (the move swapped the buffers)
+    }
+    rc = scan_fuse_locked(s, sp, scan, points, dInfo, op.stream);
+    if (rc != FPE_OK) return rc;
+    rc = update_elevation_common(h, fp, &u, updateInfo, true, op.stream);
+    if (rc != FPE_OK) return rc;
+    if (!onDevice) {
+        fpe_scan_info got;
+        FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, op.stream));
+        FPE_HIP(hipStreamSynchronize(op.stream));
+        if (scanInfo) *scanInfo = got;
+    }
+    return FPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fpe_scan_create(fpe_handle h, const fpe_map_desc* geom, fpe_scan_handle* out) {
+    if (!out) return fail(FPE_E_INVALID_ARG, "null out handle");
+    *out = nullptr;
+    if (!h) return fail(FPE_E_INVALID_ARG, "null handle");
+    int rc = check_desc(geom);
+    if (rc != FPE_OK) return rc;
+    if (geom->start_index[0] != 0 || geom->start_index[1] != 0 || geom->storage_order != 1)
+        return fail(FPE_E_INVALID_ARG, "a scan state is canonical: start index (0, 0), row-major");
+    FPE_HIP(hipSetDevice(h->device));
+    fpe_scan_state* s = new (std::nothrow) fpe_scan_state();
+    if (!s) return fail(FPE_E_NOMEM, "out of host memory");
+    s->h = h;
+    s->g = fpe::make_geom(geom->rows, geom->cols, geom->resolution, geom->position[0], geom->position[1]);
+    s->n = static_cast<size_t>(geom->rows) * geom->cols;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = hipMalloc(reinterpret_cast<void**>(&s->elev[k]), s->n * sizeof(float) + kLayerPadBytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->var[k]), s->n * sizeof(float) + kLayerPadBytes);
+    }
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->cells), s->n * sizeof(fpe::ScanCell));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->acc), (fpe::kScanAccWords + 16) * sizeof(int32_t));
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->last, hipEventDisableTiming);
+    if (e == hipSuccess) e = fpe::launch_scan_set(nullptr, nullptr, reinterpret_cast<uint32_t*>(s->elev[0]), reinterpret_cast<uint32_t*>(s->var[0]), s->n, s->own);
+    if (e == hipSuccess) e = fpe::launch_scan_reset(s->cells, s->n, s->acc, s->own);
+    if (e == hipSuccess) e = hipEventRecord(s->last, s->own);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->own);
+    if (e != hipSuccess) {
+        fpe_scan_destroy(s);
+        return fail_hip(e, "fpe_scan_create");
+    }
+    *out = s;
+    return FPE_OK;
+}
+
+int fpe_scan_destroy(fpe_scan_handle s) {
+    if (!s) return FPE_OK;
+    (void)hipSetDevice(s->h->device);
+    if (s->last) (void)hipEventSynchronize(s->last);  // the last operation, on whatever stream it ran
+    if (s->own) (void)hipStreamSynchronize(s->own);
+    for (int k = 0; k < 2; ++k) {
+        if (s->elev[k]) (void)hipFree(s->elev[k]);  // (hipFree synchronises the device: a snapshot update still reading a layer has finished)
+        if (s->var[k]) (void)hipFree(s->var[k]);
+    }
+    if (s->cells) (void)hipFree(s->cells);
+    if (s->acc) (void)hipFree(s->acc);
+    if (s->rec) (void)hipFree(s->rec);
+    if (s->pts) (void)hipFree(s->pts);
+    if (s->trav) (void)hipFree(s->trav);
+    if (s->last) (void)hipEventDestroy(s->last);
+    if (s->own) (void)hipStreamDestroy(s->own);
+    delete s;
+    return FPE_OK;
+}
+
+int fpe_scan_geometry(fpe_scan_handle s, fpe_map_desc* out) {
+    if (!s || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    *out = scan_desc(s);
+    return FPE_OK;
+}
+
+int fpe_scan_set_layers(fpe_scan_handle s, const float* elevation, const float* variance) { return scan_set_layers(s, elevation, variance, false, nullptr); }
+
+int fpe_scan_set_layers_device(fpe_scan_handle s, const float* d_elevation, const float* d_variance, void* stream) {
+    return scan_set_layers(s, d_elevation, d_variance, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_read_layers(fpe_scan_handle s, float* elevation, float* variance) { return scan_read_layers(s, elevation, variance, false, nullptr); }
+
+int fpe_scan_read_layers_device(fpe_scan_handle s, float* d_elevation, float* d_variance, void* stream) {
+    return scan_read_layers(s, d_elevation, d_variance, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_move(fpe_scan_handle s, const int32_t shift[2], const double position[2], void* stream) {
+    if (!s || !shift || !position) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!std::isfinite(position[0]) || !std::isfinite(position[1])) return fail(FPE_E_INVALID_ARG, "bad position");
+    std::lock_guard<std::mutex> lk(s->mu);
+    ScanOp op{s, static_cast<hipStream_t>(stream)};
+    const int rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    return scan_move_locked(s, shift, position, op.stream);
+}
+
+int fpe_scan_fuse(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const float* points, fpe_scan_info* info) {
+    return scan_fuse_common(s, sp, scan, points, info, false, nullptr);
+}
+
+int fpe_scan_fuse_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const float* d_points, fpe_scan_info* d_info, void* stream) {
+    return scan_fuse_common(s, sp, scan, d_points, d_info, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_install(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, void* stream) {
+    if (!h || !s) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (s->h != h) return fail(FPE_E_INVALID_ARG, "the scan state belongs to another engine");
+    fpe_filter_params def;
+    if (!fp) {
+        fpe::filter_params_defaults(def);
+        fp = &def;
+    }
+    std::lock_guard<std::mutex> lk(s->mu);
+    FPE_HIP(hipSetDevice(h->device));
+    if (!s->trav) FPE_HIP(hipMalloc(reinterpret_cast<void**>(&s->trav), s->n * sizeof(float) + kLayerPadBytes));
+    ScanOp op{s, static_cast<hipStream_t>(stream)};
+    int rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    const fpe_map_desc d = scan_desc(s);
+    rc = filters_common(h, &d, fp, s->elev[s->cur], true, s->trav, nullptr, op.stream);
+    if (rc != FPE_OK) return rc;
+    return upload_common(h, &d, s->trav, s->elev[s->cur], true, op.stream);
+}
+
+int fpe_scan_ingest(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan, const float* points,
+                    const int32_t shift[2], const double position[2], fpe_scan_info* scan_info, fpe_elevation_update_info* update_info) {
+    return scan_ingest_common(h, s, fp, sp, scan, points, shift, position, scan_info, update_info, false, nullptr);
+}
+
+int fpe_scan_ingest_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan,
+                           const float* d_points, const int32_t shift[2], const double position[2], fpe_scan_info* d_scan_info,
+                           fpe_elevation_update_info* update_info, void* stream) {
+    return scan_ingest_common(h, s, fp, sp, scan, d_points, shift, position, d_scan_info, update_info, true, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

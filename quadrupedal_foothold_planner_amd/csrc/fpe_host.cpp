@@ -661,9 +661,93 @@ int fpe_elevation_update_plan(const fpe_map_desc* base, const fpe_filter_params*
     return FPE_OK;
 }
 
+int fpe_scan_params_defaults(fpe_scan_params* out) {
+    if (!out) return FPE_E_INVALID_ARG;
+    fpe::scan_params_defaults(*out);
+    return FPE_OK;
+}
+
+int fpe_scan_validate(const fpe_map_desc* geom, const fpe_scan_params* sp, const fpe_scan* scan) {
+    if (!geom) return FPE_E_INVALID_ARG;
+    const char* why = nullptr;
+    const int rc = fpe::check_map_geometry(geom->rows, geom->cols, geom->resolution, &why);
+    if (rc != FPE_OK) return rc;
+    return fpe::check_scan(geom->rows, geom->cols, sp, scan, &why);
+}
+
 }  // extern "C"
 
 namespace fpe {
+
+void scan_params_defaults(fpe_scan_params& out) {
+    out.min_range = 0.1f;
+    out.max_range = 10.0f;
+    out.min_z = -100.0f;
+    out.max_z = 100.0f;
+    out.band = 0.05f;
+    out.var_base = 1e-4f;
+    out.var_range = 1e-4f;
+    out.var_min = 1e-6f;
+    out.var_max = 1.0f;
+    out.gate = 3.0f;
+    out.var_outlier = 1e-3f;
+    out.replace_count = 0;
+}
+
+int check_scan(int rows, int cols, const fpe_scan_params* sp, const fpe_scan* scan, const char** why) {
+    auto bad = [&](const char* msg) {
+        *why = msg;
+        return static_cast<int>(FPE_E_INVALID_ARG);
+    };
+    if (!sp || !scan) return bad("null scan or scan parameters");
+    if (scan->n_points < 0 || scan->n_points > FPE_SCAN_MAX_POINTS) return bad("n_points out of range");
+    if (scan->point_stride < 3) return bad("point_stride below 3");
+    if (scan->reserved[0] != 0 || scan->reserved[1] != 0) return bad("reserved must be 0");
+    const int32_t* roi = scan->roi;
+    if (roi[2] <= 0 || roi[3] <= 0) return bad("empty roi");
+    if (roi[0] < 0 || roi[1] < 0 || static_cast<int64_t>(roi[0]) + roi[2] > rows || static_cast<int64_t>(roi[1]) + roi[3] > cols)
+        return bad("roi outside the state");
+    for (double t : scan->sensor_to_map)
+        if (!std::isfinite(t)) return bad("non-finite transform");
+    const float all[11] = {sp->min_range, sp->max_range, sp->min_z, sp->max_z, sp->band, sp->var_base, sp->var_range, sp->var_min, sp->var_max,
+                           sp->gate, sp->var_outlier};
+    for (float v : all)
+        if (!std::isfinite(v)) return bad("non-finite scan parameter");
+    if (sp->min_range > sp->max_range) return bad("min_range above max_range");
+    if (sp->min_z > sp->max_z) return bad("min_z above max_z");
+    if (std::fabs(sp->min_z) > 16384.0f || std::fabs(sp->max_z) > 16384.0f) return bad("height limits beyond +-16384");
+    if (sp->var_base < 0.0f || sp->var_range < 0.0f || sp->var_min < 0.0f || sp->var_max < 0.0f || sp->var_outlier < 0.0f)
+        return bad("negative variance parameter");
+    if (sp->var_min > sp->var_max) return bad("var_min above var_max");
+    if (!(sp->gate > 0.0f)) return bad("gate must be positive");
+    if (sp->band < 0.0f) return bad("negative band");
+    return FPE_OK;
+}
+
+// The constants of a fuse as the kernels take them: every widening and square of the contract formed once, here.
+void scan_consts(const fpe_scan_params& sp, const fpe_scan& scan, const MapGeom& g, ScanArgs& a) {
+    for (int k = 0; k < 12; ++k) a.T[k] = scan.sensor_to_map[k];
+    a.minR2 = static_cast<double>(sp.min_range) * static_cast<double>(sp.min_range);
+    a.maxR2 = static_cast<double>(sp.max_range) * static_cast<double>(sp.max_range);
+    a.minZ = sp.min_z;
+    a.maxZ = sp.max_z;
+    a.g = g;
+    const double bq = std::rint(static_cast<double>(sp.band) * 65536.0);
+    a.bandQ = bq >= 2147483648.0 ? (int64_t{1} << 31) : static_cast<int64_t>(bq);
+    a.varBase = sp.var_base;
+    a.varRange = sp.var_range;
+    a.varMin = sp.var_min;
+    a.varMax = sp.var_max;
+    a.gate2 = sp.gate * sp.gate;
+    a.varOutlier = sp.var_outlier;
+    a.replaceCount = sp.replace_count;
+    a.n = scan.n_points;
+    a.stride = scan.point_stride;
+    a.row0 = scan.roi[0];
+    a.col0 = scan.roi[1];
+    a.nr = scan.roi[2];
+    a.nc = scan.roi[3];
+}
 
 int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevationOnly, const char** why) {
     auto bad = [&](const char* msg) {

@@ -48,6 +48,9 @@ int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevation
 // Size and resolution of a map the engine takes (fpe_upload_map*, fpe_traversability*, fpe_update_elevation*): FPE_OK, or
 // FPE_E_INVALID_ARG with *why set.
 int check_map_geometry(int rows, int cols, double res, const char** why);
+// The refusals of fpe_scan_fuse* for a state of rows x cols cells (include/fpe.h): FPE_OK, or FPE_E_INVALID_ARG with *why set.
+int check_scan(int rows, int cols, const fpe_scan_params* sp, const fpe_scan* scan, const char** why);
+void scan_params_defaults(fpe_scan_params& out);
 
 // ---- the producer's filter chain (fpe_filters.hpp): its host arithmetic — filter_route and friends are declared in fpe_launch.hpp ----
 void filter_params_defaults(fpe_filter_params& out);

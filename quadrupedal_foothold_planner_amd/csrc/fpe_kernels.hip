@@ -2295,6 +2295,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_check.hpp"
 // ---- part fifteen: the checked beam (fpe_plan_beam_checked*; folds part fourteen's parts into part nine's pruning) ----------
 #include "fpe_beam_check.hpp"
+// ---- part sixteen: scan fusion (fpe_scan_*): a point cloud into the elevation and variance layers of a scan state ----------
+#include "fpe_scan.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)

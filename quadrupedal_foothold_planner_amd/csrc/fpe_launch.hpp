@@ -472,4 +472,54 @@ hipError_t launch_beam_prune_checked(const BeamShape& sh, int s, const BeamScrat
 hipError_t launch_beam_trace_checked(const BeamShape& sh, const BeamScratch& sc, const fpe_beam_out& d_out, uint32_t checks,
                                      const fpe_beam_check_out& d_checkOut, hipStream_t stream);
 
+// ---- scan fusion (fpe_scan.hpp) ------------------------------------------------------------------------------
+// The scratch of one state cell between the passes of a fuse, indexed by the cell's LOCAL index in the call's roi (r * nc + c, which
+// is below rows * cols): 16 bytes, at rest {kScanTopNone, 0, 0} — written so at create, and again by scan_fuse_kernel for every cell
+// a call touched.
+struct alignas(16) ScanCell {
+    int32_t top;    // max q of the accepted points (atomicMax)
+    uint32_t count;  // kept points
+    int64_t sum;     // their q, summed
+};
+static_assert(sizeof(ScanCell) == 16, "16 bytes of scratch per state cell (include/fpe.h)");
+constexpr int32_t kScanTopNone = INT32_MIN;
+constexpr uint32_t kScanNoCell = 0xFFFFFFFFu;  // the record of a dropped point
+// The accumulators of a call's info between its passes (device, 32 words, owned by the state): words 0-15 are fpe_scan_info's, at
+// rest 0 but for the bbox minima (INT32_MAX) and maxima (-1); word 16 is scan_fuse_kernel's ticket (at rest 0).  The last workgroup of
+// scan_fuse_kernel takes the totals out with atomic exchanges that put the rest values back, and writes the caller's info.
+constexpr int kScanAccWords = 32;
+constexpr int kScanTicket = 16;
+// The argument block of the three passes, by value: the contract's constants formed once on the host (the squares and widenings of
+// include/fpe.h), the state's geometry, the roi and the buffers.
+struct ScanArgs {
+    double T[12];
+    double minR2, maxR2, minZ, maxZ;
+    MapGeom g;
+    int64_t bandQ;  // min(rint(double(band) * 65536), 2^31)
+    float varBase, varRange, varMin, varMax, gate2, varOutlier;  // gate2 = gate * gate (f32)
+    int32_t replaceCount;
+    int32_t n, stride;
+    int32_t row0, col0, nr, nc;
+    const float* points;
+    uint2* rec;       // [n]: (local cell or kScanNoCell, q)
+    ScanCell* cells;  // [rows * cols]
+    int32_t* acc;     // [kScanAccWords]
+    uint32_t* elev;   // the state's layers, as 32-bit patterns
+    uint32_t* var;
+    int32_t* info;    // the caller's fpe_scan_info (device), or null
+};
+void scan_consts(const fpe_scan_params& sp, const fpe_scan& scan, const MapGeom& g, ScanArgs& a);  // fpe_host.cpp
+// The three passes of a fuse on `stream`, and each alone.  merge: the merged form of the two point passes.
+hipError_t launch_scan_fuse(const ScanArgs& a, bool merge, hipStream_t stream);
+hipError_t launch_scan_top(const ScanArgs& a, bool merge, hipStream_t stream);
+hipError_t launch_scan_sum(const ScanArgs& a, bool merge, hipStream_t stream);
+hipError_t launch_scan_cells(const ScanArgs& a, hipStream_t stream);
+// every cell's scratch and the accumulators to their rest values (create)
+hipError_t launch_scan_reset(ScanCell* cells, size_t n, int32_t* acc, hipStream_t stream);
+// new (i, j) = old (i + sr, j + sc) of both layers, or the cleared value (|sr| <= rows, |sc| <= cols: clamped by the caller)
+hipError_t launch_scan_move(const uint32_t* srcElev, const uint32_t* srcVar, uint32_t* dstElev, uint32_t* dstVar, int rows, int cols, int sr, int sc,
+                            hipStream_t stream);
+// both layers from two sources: a cell that is NaN in either becomes the cleared value in both (srcElev null: every cell cleared)
+hipError_t launch_scan_set(const uint32_t* srcElev, const uint32_t* srcVar, uint32_t* dstElev, uint32_t* dstVar, size_t n, hipStream_t stream);
+
 }  // namespace fpe

@@ -292,6 +292,39 @@ def elevation_update_plan(rows, cols, resolution, shift, position, rects, params
     return _info_dict(info), mask
 
 
+def scan_params(**overrides):
+    """fpe_scan_params_defaults, with any field replaced by a keyword."""
+    sp = _capi.ScanParams()
+    assert _capi.lib().fpe_scan_params_defaults(C.byref(sp)) == _capi.FPE_OK
+    for k, v in overrides.items():
+        if k not in dict(_capi.ScanParams._fields_):
+            raise ValueError(f"unknown scan parameter {k!r}")
+        setattr(sp, k, v)
+    return sp
+
+
+def make_scan(sensor_to_map, n_points, roi, point_stride=3):
+    """An fpe_scan: the sensor-to-map transform (3 x 4, or 4 x 4 whose last row is dropped; row-major), the number of points, their
+    stride in floats and the roi (row0, col0, n_rows, n_cols) of the state the scan may write."""
+    t = np.asarray(sensor_to_map, dtype=np.float64)
+    if t.shape == (4, 4):
+        t = t[:3]
+    if t.size != 12:
+        raise ValueError("sensor_to_map is a 3 x 4 (or 4 x 4) matrix")
+    s = _capi.Scan()
+    s.sensor_to_map[:] = [float(x) for x in t.reshape(12)]
+    s.n_points, s.point_stride = int(n_points), int(point_stride)
+    s.roi[:] = [int(x) for x in roi]
+    return s
+
+
+def scan_validate(rows, cols, resolution, params, scan):
+    """fpe_scan_validate (host arithmetic, no engine): the status a fuse of `scan` into a rows x cols state would be refused with,
+    or FPE_OK.  `params` / `scan` may be None (a null argument)."""
+    d = _map_desc(rows, cols, resolution)
+    return _capi.lib().fpe_scan_validate(C.byref(d), C.byref(params) if params is not None else None, C.byref(scan) if scan is not None else None)
+
+
 class _Handle:
     """What an engine and a group of engines share: the handle's creation, close / __del__, and the status check.  A subclass names
     its three entry points."""
@@ -447,6 +480,11 @@ class FootholdPlanner(_Handle):
         self._check(self._lib.fpe_traversability_device(self._h, C.byref(d), C.byref(fp), C.c_void_p(d_elev_ptr),
                                                         C.c_void_p(d_trav_ptr), C.c_void_p(d_layers_ptr or 0), C.c_void_p(stream or 0)))
 
+    # ---- scan fusion: point clouds into an elevation layer that never leaves HBM (fpe_scan_*) ------------------------
+    def scan_state(self, rows, cols, resolution, position=(0.0, 0.0)):
+        """fpe_scan_create: a ScanState of this engine, every cell unknown."""
+        return ScanState(self, rows, cols, resolution, position)
+
     def map_info(self):
         d = MapDesc()
         self._check(self._lib.fpe_map_info(self._h, C.byref(d)))
@@ -465,7 +503,7 @@ class FootholdPlanner(_Handle):
         return buf.value.decode()
 
     def set_tuning(self, **kw):
-        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, beam_check_waves, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
+        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, beam_check_waves, scan_merge, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
         for k, v in kw.items():
             self._check(self._lib.fpe_set_tuning(self._h, k.encode(), int(v)))
             self._tuning[k] = int(v)
@@ -1257,6 +1295,114 @@ class FootholdPlanner(_Handle):
         out["opt"]["report"] = self._report(rep[2])
         out["opt"]["cycles"] = cyc[: int(gait_cycles)].copy()
         return out
+
+
+class ScanState:
+    """A scan state of one engine (fpe_scan_*; include/fpe.h): a robot-centric elevation layer and its variance layer in HBM, into
+    which point clouds are fused.  Made by FootholdPlanner.scan_state(); close it before its planner.  The device forms take device
+    addresses and a stream handle and never synchronise the host."""
+
+    def __init__(self, planner, rows, cols, resolution, position=(0.0, 0.0)):
+        self._planner, self._lib = planner, planner._lib
+        self._s = C.c_void_p()
+        d = _map_desc(rows, cols, resolution, position)
+        planner._check(self._lib.fpe_scan_create(planner._h, C.byref(d), C.byref(self._s)))
+        self.rows, self.cols, self.resolution = int(rows), int(cols), float(resolution)
+
+    def close(self):
+        if getattr(self, "_s", None) and getattr(self._planner, "_h", None):
+            self._lib.fpe_scan_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        self._planner._check(rc)
+
+    def geometry(self):
+        d = MapDesc()
+        self._check(self._lib.fpe_scan_geometry(self._s, C.byref(d)))
+        return {"rows": d.rows, "cols": d.cols, "resolution": d.resolution, "position": tuple(d.position)}
+
+    def set_layers(self, elevation, variance):
+        """Both layers from (rows, cols) host arrays; a cell that is NaN in either becomes unknown in both.  Synchronous."""
+        e, v = (np.ascontiguousarray(a, dtype=np.float32) for a in (elevation, variance))
+        if e.shape != (self.rows, self.cols) or v.shape != e.shape:
+            raise ValueError("set_layers takes two (rows, cols) arrays")
+        self._check(self._lib.fpe_scan_set_layers(self._s, ptr(e), ptr(v)))
+
+    def set_layers_device(self, d_elev_ptr, d_var_ptr, stream=None):
+        self._check(self._lib.fpe_scan_set_layers_device(self._s, C.c_void_p(d_elev_ptr), C.c_void_p(d_var_ptr), C.c_void_p(stream or 0)))
+
+    def read_layers(self, elevation=True, variance=True):
+        """-> (elevation, variance) as (rows, cols) arrays, bit for bit (None for a layer not asked for).  Synchronous."""
+        e = np.empty((self.rows, self.cols), np.float32) if elevation else None
+        v = np.empty((self.rows, self.cols), np.float32) if variance else None
+        self._check(self._lib.fpe_scan_read_layers(self._s, ptr(e), ptr(v)))
+        return e, v
+
+    def read_layers_device(self, d_elev_ptr=0, d_var_ptr=0, stream=None):
+        self._check(self._lib.fpe_scan_read_layers_device(self._s, C.c_void_p(d_elev_ptr or 0), C.c_void_p(d_var_ptr or 0), C.c_void_p(stream or 0)))
+
+    def move(self, shift, position, stream=None):
+        """fpe_scan_move: new cell (i, j) takes old cell (i + sr, j + sc) of both layers, or becomes unknown; asynchronous."""
+        sh, pos = (C.c_int32 * 2)(int(shift[0]), int(shift[1])), (C.c_double * 2)(float(position[0]), float(position[1]))
+        self._check(self._lib.fpe_scan_move(self._s, sh, pos, C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def _points(points, scan):
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.size < scan.n_points * scan.point_stride:
+            raise ValueError("fewer floats than n_points * point_stride")
+        return p if p.size else np.zeros(3, np.float32)  # (n_points == 0: any non-null address)
+
+    def fuse(self, scan, points, params=None):
+        """fpe_scan_fuse: host points ((n, point_stride) floats) -> the call's info as a SCAN_INFO_DTYPE record.  Synchronous."""
+        p = self._points(points, scan)
+        info = np.zeros(1, _capi.SCAN_INFO_DTYPE)
+        self._check(self._lib.fpe_scan_fuse(self._s, C.byref(params if params is not None else scan_params()), C.byref(scan), ptr(p), ptr(info)))
+        return info[0]
+
+    def fuse_device(self, scan, d_points_ptr, params=None, d_info_ptr=0, stream=None):
+        """fpe_scan_fuse_device: device points, a device info of sixteen int32 (0: not wanted); asynchronous on `stream`."""
+        self._check(self._lib.fpe_scan_fuse_device(self._s, C.byref(params if params is not None else scan_params()), C.byref(scan),
+                                                   C.c_void_p(d_points_ptr), C.c_void_p(d_info_ptr or 0), C.c_void_p(stream or 0)))
+
+    def install(self, filter_params=None, stream=None):
+        """fpe_scan_install: the state's content becomes the planner's current snapshot (filters, then an upload); asynchronous."""
+        pl = self._planner
+        self._check(self._lib.fpe_scan_install(pl._h, self._s, C.byref(filter_params) if filter_params is not None else None, C.c_void_p(stream or 0)))
+        pl.rows, pl.cols, pl.resolution = self.rows, self.cols, self.resolution
+
+    @staticmethod
+    def _move_args(shift, position):
+        return (C.c_int32 * 2)(int(shift[0]), int(shift[1])), (C.c_double * 2)(float(position[0]), float(position[1]))
+
+    def ingest(self, scan, points, shift, position, params=None, filter_params=None):
+        """fpe_scan_ingest: move (when the shift or the position says so), fuse, and the roi into the snapshot through an
+        elevation-driven update -> (scan info record, update info dict).  Synchronous."""
+        p = self._points(points, scan)
+        sh, pos = self._move_args(shift, position)
+        info, ui = np.zeros(1, _capi.SCAN_INFO_DTYPE), _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_scan_ingest(self._planner._h, self._s, C.byref(filter_params) if filter_params is not None else None,
+                                              C.byref(params if params is not None else scan_params()), C.byref(scan), ptr(p), sh, pos, ptr(info),
+                                              C.byref(ui)))
+        return info[0], _info_dict(ui)
+
+    def ingest_device(self, scan, d_points_ptr, shift, position, params=None, filter_params=None, d_info_ptr=0, stream=None):
+        """fpe_scan_ingest_device: the same with device points and a device scan info (0: not wanted), asynchronous on `stream` ->
+        the update info dict."""
+        sh, pos = self._move_args(shift, position)
+        ui = _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_scan_ingest_device(self._planner._h, self._s, C.byref(filter_params) if filter_params is not None else None,
+                                                     C.byref(params if params is not None else scan_params()), C.byref(scan),
+                                                     C.c_void_p(d_points_ptr), sh, pos, C.c_void_p(d_info_ptr or 0), C.byref(ui),
+                                                     C.c_void_p(stream or 0)))
+        return _info_dict(ui)
 
 
 class MultiFootholdPlanner(_Handle):
