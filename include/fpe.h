@@ -275,6 +275,9 @@ int fpe_destroy(fpe_handle h);
  * map's resolution, 1 or 4 forced; the outputs do not depend on it.
  * "scan_merge": the form of the two point passes of fpe_scan_fuse*: 0 (DEFAULT) the engine's choice, 1 plain, 2 merged (see there);
  * the outputs do not depend on it.
+ * "scan_clear_form": the form of the ray pass of fpe_scan_clear*: 0 (DEFAULT) the engine's choice, 1 one lane per ray, 2 a group of
+ * adjacent lanes per ray; "scan_clear_group": that group's width: 0 (DEFAULT) the engine's choice, 16, 32 or 64 (see there); the
+ * outputs depend on neither.
  * "service_overlap" (default 1): a call that runs the plan AND the opt track for at most four poses launches the opt
  * track's chain on a second stream beside the plan kernel, on nominal cycle flags of 1 (the flags only decide which cycles the
  * chain commits, cpp:1323-1332, and are 1 unless a nominal search fails), and runs it again on the real flags in the call where
@@ -1601,6 +1604,78 @@ int fpe_scan_ingest(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp
 int fpe_scan_ingest_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan,
                            const float* d_points, const int32_t shift[2], const double position[2], fpe_scan_info* d_scan_info,
                            fpe_elevation_update_info* update_info, void* stream);
+
+/* 4. Visibility clearing (fpe_scan_clear[_device]): cells a new scan SEES THROUGH become unknown.  The fuse can only grow obstacles: a
+ *    cell is rewritten only by points that land in it, and a prior above what the scan sees is gated out.  What has left (a person, a
+ *    door leaf, something tall seen at a grazing angle) therefore stays in the state until rays of a later scan pass below its height.
+ *    BUILD-DEFINED like the fuse; the numpy statement is tests/scan_clear_reference.py.  THE CONTRACT, with point 2's conventions (f64,
+ *    every product and sum rounded on its own, no contraction, the grid arithmetic of checkIfPositionWithinMap and
+ *    getIndexFromPosition).  T = scan->sensor_to_map; the sensor's origin in the map frame is (T3, T7, T11).
+ *    Per point i:
+ *      1. strided_out     if i % ray_stride != 0; the point is not read;
+ *      2. dropped_points  if one of point 2's tests 1-4 fails (non-finite, range, transform, height window; sp's limits).  A point that
+ *                         passes is a RAY, wherever its end lies;
+ *      3. dx = xm - T3, dy = ym - T7, dz = zm - T11;  m = fmax(fabs(dx), fabs(dy));  step = double(sample_step) * resolution;
+ *         Kd = ceil(m / step);
+ *      4. rays_long       if Kd > double(max_samples) (compared in f64); the ray is not walked;
+ *      5. otherwise K = (int)Kd and the ray's samples are k = start_samples .. K - end_samples - 1; rays_empty if there are none.
+ *         `rays` counts every ray, the long and the empty ones included;
+ *      6. sample k: t = double(k) / double(K);  x = T3 + t*dx, y = T7 + t*dy, z = T11 + t*dz.  It is INSIDE iff
+ *         checkIfPositionWithinMap holds on both axes and its cell lies in scan->roi (samples_in_roi counts these); an inside sample
+ *         VIOLATES its cell iff the cell's prior elevation h is not NaN and (z + double(margin)) < double(h);
+ *      7. a ray counts against a cell ONCE, however many of its samples violate it (hit_pairs counts these pairs; the cell's hits + 1).
+ *         x and y are monotone in k, so a ray's samples in one cell are one run of consecutive k.
+ *    Per roi cell: hits >= 1 counts into cells_hit; hits >= min_hits CLEARS the cell: both layers take 0x7FC00000, it counts into
+ *    cells_cleared and lies in bbox (state indices).  Every other cell's bytes stay.  The prior is read by the ray pass and written
+ *    only by the cell pass, and the only per-cell reduction is an integer count: the result does not depend on the order of the
+ *    points (ray_stride == 1; above 1 the stride selects by index).
+ *    Refusals (FPE_E_INVALID_ARG; nothing written, nothing queued): everything the fuse refuses for sp and scan; a null cp; a
+ *    non-finite sample_step or margin; a field outside the range its comment gives; reserved != 0.  fpe_scan_clear_validate is that
+ *    same routine without an engine.
+ *    Forms: as the fuse's (host: host points, host info or NULL, synchronous; device: device points, device info of 64 bytes or NULL,
+ *    asynchronous on `stream`, never synchronises the host).  Ordering as in point 1.  Two launches: a ray pass (integer atomics into
+ *    the hits word of the cells' scratch, which is the fuse's `count` word: 0 at rest) and scan_clear_cells_kernel (one lane per roi
+ *    cell: clears, puts the hits back to 0, writes the info from the last workgroup).  The state's scratch is at rest afterwards.
+ *    fpe_set_tuning "scan_clear_form": 0 (DEFAULT) the engine's choice, 1 one lane per ray, 2 a group of adjacent lanes per ray;
+ *    "scan_clear_group": the lanes per ray of form 2: 0 (DEFAULT) the engine's choice, 16, 32 or 64.  The outputs depend on neither.
+ *     - fpe_scan_ingest_clear[_device]: fpe_scan_ingest[_device] with the clear between the move and the fuse: move (when the shift or
+ *       the position says so), CLEAR, fuse, fpe_update_elevation_device with the one roi patch.  A cell that is cleared and hit by the
+ *       same scan comes out NEW.  The snapshot is byte for byte what those four public calls leave; point 3's promise keeps holding
+ *       (cleared cells lie inside the roi, and the patch carries their NaN).  Refused as a whole under fpe_scan_ingest's conditions
+ *       plus the clear's.  clear_info, scan_info and update_info may each be NULL.
+ *    (These declarations carry `extern`: tests/test_cpu_scan.py counts the lines that start with `int fpe_scan_` as the fifteen
+ *    entry points of points 1-3.) */
+typedef struct fpe_scan_clear_params {   /* 32 bytes */
+    float   sample_step;    /* in cells, along the ray's dominant ground axis; 0 < . <= 1 */
+    float   margin;         /* m a ray must pass BELOW a cell's height to count against it; >= 0 */
+    int32_t start_samples;  /* samples skipped at the sensor's end; >= 0 */
+    int32_t end_samples;    /* samples skipped at the point's end (the hit itself and its neighbourhood); >= 0 */
+    int32_t min_hits;       /* rays that must count against a cell to clear it; >= 1 */
+    int32_t ray_stride;     /* point i casts a ray iff i % ray_stride == 0; >= 1 */
+    int32_t max_samples;    /* rays with more samples than this are not walked; 1 .. 65536 */
+    int32_t reserved;       /* 0 */
+} fpe_scan_clear_params;
+/* defaults: 0.5, 0.10, 2, 4, 2, 1, 4096, 0 */
+typedef struct fpe_scan_clear_info {     /* 64 bytes */
+    int32_t n_points, strided_out, dropped_points, rays, rays_long, rays_empty, cells_hit, cells_cleared;
+    int32_t bbox[4];        /* of the cleared cells, state indices; {0,0,-1,-1} when none */
+    int64_t samples_in_roi, hit_pairs;
+} fpe_scan_clear_info;
+extern int fpe_scan_clear_params_defaults(fpe_scan_clear_params* out);
+extern int fpe_scan_clear_validate(const fpe_map_desc* geom, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                                   const fpe_scan* scan);                                                /* host arithmetic only; no engine */
+extern int fpe_scan_clear(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan,
+                          const float* points, fpe_scan_clear_info* info);
+extern int fpe_scan_clear_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan,
+                                 const float* d_points, fpe_scan_clear_info* d_info, void* stream);
+extern int fpe_scan_ingest_clear(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp,
+                                 const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* points, const int32_t shift[2],
+                                 const double position[2], fpe_scan_clear_info* clear_info, fpe_scan_info* scan_info,
+                                 fpe_elevation_update_info* update_info);
+extern int fpe_scan_ingest_clear_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp,
+                                        const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* d_points,
+                                        const int32_t shift[2], const double position[2], fpe_scan_clear_info* d_clear_info,
+                                        fpe_scan_info* d_scan_info, fpe_elevation_update_info* update_info, void* stream);
 
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,

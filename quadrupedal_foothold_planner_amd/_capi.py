@@ -432,6 +432,21 @@ SCAN_INFO_DTYPE = np.dtype(
 )
 assert (C.sizeof(ScanParams), C.sizeof(Scan), SCAN_INFO_DTYPE.itemsize) == (48, 128, 64)
 
+
+class ScanClearParams(C.Structure):
+    """fpe_scan_clear_params: how the rays of a visibility clearing are sampled and when a cell they pass below becomes unknown."""
+    _fields_ = [("sample_step", C.c_float), ("margin", C.c_float), ("start_samples", C.c_int32), ("end_samples", C.c_int32),
+                ("min_hits", C.c_int32), ("ray_stride", C.c_int32), ("max_samples", C.c_int32), ("reserved", C.c_int32)]
+
+
+# fpe_scan_clear_info: twelve int32 and two int64 (sixteen int32 words when a device info is read back)
+SCAN_CLEAR_INFO_DTYPE = np.dtype(
+    [("n_points", "<i4"), ("strided_out", "<i4"), ("dropped_points", "<i4"), ("rays", "<i4"), ("rays_long", "<i4"), ("rays_empty", "<i4"),
+     ("cells_hit", "<i4"), ("cells_cleared", "<i4"), ("bbox", "<i4", (4,)), ("samples_in_roi", "<i8"), ("hit_pairs", "<i8")],
+    align=True,
+)
+assert (C.sizeof(ScanClearParams), SCAN_CLEAR_INFO_DTYPE.itemsize) == (32, 64)
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -453,6 +468,7 @@ STRUCTS = {
     "fpe_margin_record": MARGIN_RECORD_DTYPE, "fpe_margin_summary": MARGIN_SUMMARY_DTYPE, "fpe_margin_out": MarginOut,
     "fpe_check_params": CheckParams, "fpe_check_out": CheckOut, "fpe_beam_check_out": BeamCheckOut,
     "fpe_scan_params": ScanParams, "fpe_scan": Scan, "fpe_scan_info": SCAN_INFO_DTYPE,
+    "fpe_scan_clear_params": ScanClearParams, "fpe_scan_clear_info": SCAN_CLEAR_INFO_DTYPE,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -579,6 +595,14 @@ PROTOTYPES = {
     "fpe_scan_install": (cint, [vp, vp, P(FilterParams), vp]),
     "fpe_scan_ingest": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(Scan), vp, P(i32), P(f64), vp, P(ElevationUpdateInfo)]),
     "fpe_scan_ingest_device": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(Scan), vp, P(i32), P(f64), vp, P(ElevationUpdateInfo), vp]),
+    "fpe_scan_clear_params_defaults": (cint, [P(ScanClearParams)]),
+    "fpe_scan_clear_validate": (cint, [P(MapDesc), P(ScanParams), P(ScanClearParams), P(Scan)]),
+    "fpe_scan_clear": (cint, [vp, P(ScanParams), P(ScanClearParams), P(Scan), vp, vp]),
+    "fpe_scan_clear_device": (cint, [vp, P(ScanParams), P(ScanClearParams), P(Scan), vp, vp, vp]),
+    "fpe_scan_ingest_clear": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(Scan), vp, P(i32), P(f64), vp, vp,
+                                     P(ElevationUpdateInfo)]),
+    "fpe_scan_ingest_clear_device": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(Scan), vp, P(i32), P(f64), vp, vp,
+                                            P(ElevationUpdateInfo), vp]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

@@ -1635,6 +1635,12 @@ int fpe_set_tuning(fpe_handle h, const char* key, int32_t value) {
     } else if (k == "scan_merge") {
         if (value < 0 || value > 2) return fail(FPE_E_INVALID_ARG, "scan_merge is 0 (the engine's choice), 1 (plain) or 2 (merged)");
         h->tuning.scanMerge = value;
+    } else if (k == "scan_clear_form") {
+        if (value < 0 || value > 2) return fail(FPE_E_INVALID_ARG, "scan_clear_form is 0 (the engine's choice), 1 (a lane per ray) or 2 (a group per ray)");
+        h->tuning.scanClearForm = value;
+    } else if (k == "scan_clear_group") {
+        if (value != 0 && value != 16 && value != 32 && value != 64) return fail(FPE_E_INVALID_ARG, "scan_clear_group is 0 (the engine's choice), 16, 32 or 64");
+        h->tuning.scanClearGroup = value;
     } else if (k == "service_overlap") h->tuning.serviceOverlap = value ? 1 : 0;
     else if (k == "service_poll") h->tuning.servicePoll = value ? 1 : 0;
     else if (k == "service_cycle0_gate_only") h->tuning.serviceOptGate = value ? 0 : 2;  // (older name)
@@ -3977,7 +3983,7 @@ struct fpe_scan_state {
     float* var[2] = {nullptr, nullptr};
     int cur = 0;
     fpe::ScanCell* cells = nullptr;
-    int32_t* acc = nullptr;  // kScanAccWords accumulators, then sixteen words: the host forms' device info
+    int32_t* acc = nullptr;  // kScanAccWords accumulators, then twice sixteen words: the host forms' device infos (the fuse's, the clear's)
     uint2* rec = nullptr;
     size_t recCap = 0;       // records
     float* pts = nullptr;
@@ -3990,6 +3996,9 @@ struct fpe_scan_state {
 namespace {
 
 constexpr int kScanMergeDefault = 2;  // "scan_merge" 0: the form measured faster on both workloads of profiles/scan_summary.txt
+// "scan_clear_form" / "scan_clear_group" 0: the form measured faster on the depth image of profiles/scan_clear_summary.txt
+constexpr int kScanClearFormDefault = 1;
+constexpr int kScanClearGroupDefault = 16;
 
 // An operation of a state on `stream`: behind the state's last one, and its own event recorded on every way out (an operation that
 // failed half-way may have queued work the next one must not overtake).  The caller holds s->mu.
@@ -4097,11 +4106,36 @@ int scan_fuse_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sca
     return FPE_OK;
 }
 
-int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan) {
+// The two passes of a clear on `stream` (the caller holds s->mu, has validated the call and has entered `stream`).
+int scan_clear_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* d_points,
+                      fpe_scan_clear_info* d_info, hipStream_t stream) {
+    int form, group;
+    {
+        std::lock_guard<std::mutex> lk(s->h->mu);
+        form = s->h->tuning.scanClearForm;
+        group = s->h->tuning.scanClearGroup;
+    }
+    if (form == 0) form = kScanClearFormDefault;
+    if (group == 0) group = kScanClearGroupDefault;
+    fpe::ScanClearArgs a;
+    fpe::scan_clear_consts(*sp, *cp, *scan, s->g, a);
+    a.points = d_points;
+    a.cells = s->cells;
+    a.acc = s->acc;
+    a.elev = reinterpret_cast<uint32_t*>(s->elev[s->cur]);
+    a.var = reinterpret_cast<uint32_t*>(s->var[s->cur]);
+    a.info = reinterpret_cast<int32_t*>(d_info);
+    FPE_HIP(fpe::launch_scan_clear(a, form, group, stream));
+    return FPE_OK;
+}
+
+// (cp == nullptr with withClear == false: the fuse's refusals alone)
+int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, bool withClear, const fpe_scan* scan) {
     const char* why = "";
-    const int rc = fpe::check_scan(s->g.rows, s->g.cols, sp, scan, &why);
+    const int rc = withClear ? fpe::check_scan_clear(s->g.rows, s->g.cols, sp, cp, scan, &why) : fpe::check_scan(s->g.rows, s->g.cols, sp, scan, &why);
     return rc == FPE_OK ? rc : fail(rc, why);
 }
+int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan) { return scan_check(s, sp, nullptr, false, scan); }
 
 // Host points into the state's staging buffer on its own stream (entered)
 int scan_stage_points(fpe_scan_state* s, const fpe_scan* scan, const float* points) {
@@ -4134,14 +4168,37 @@ int scan_fuse_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sca
     return FPE_OK;
 }
 
-int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan, const float* points,
-                       const int32_t shift[2], const double position[2], fpe_scan_info* scanInfo, fpe_elevation_update_info* updateInfo, bool onDevice,
-                       hipStream_t stream) {
+int scan_clear_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* points,
+                      fpe_scan_clear_info* info, bool onDevice, hipStream_t stream) {
+    if (!s || !points) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    int rc = scan_check(s, sp, cp, true, scan);
+    if (rc != FPE_OK) return rc;
+    ScanOp op{s, onDevice ? stream : s->own};
+    rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    if (onDevice) return scan_clear_locked(s, sp, cp, scan, points, info, stream);
+    rc = scan_stage_points(s, scan, points);
+    if (rc != FPE_OK) return rc;
+    fpe_scan_clear_info* dInfo = reinterpret_cast<fpe_scan_clear_info*>(s->acc + fpe::kScanAccWords + 16);
+    rc = scan_clear_locked(s, sp, cp, scan, s->pts, dInfo, s->own);
+    if (rc != FPE_OK) return rc;
+    fpe_scan_clear_info got;
+    FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, s->own));
+    FPE_HIP(hipStreamSynchronize(s->own));
+    if (info) *info = got;
+    return FPE_OK;
+}
+
+// fpe_scan_ingest* (withClear false: cp and clearInfo unused) and fpe_scan_ingest_clear* (the clear between the move and the fuse)
+int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                       bool withClear, const fpe_scan* scan, const float* points, const int32_t shift[2], const double position[2],
+                       fpe_scan_clear_info* clearInfo, fpe_scan_info* scanInfo, fpe_elevation_update_info* updateInfo, bool onDevice, hipStream_t stream) {
     if (!h || !s || !points || !shift || !position) return fail(FPE_E_INVALID_ARG, "null argument");
     if (s->h != h) return fail(FPE_E_INVALID_ARG, "the scan state belongs to another engine");
     std::lock_guard<std::mutex> lk(s->mu);
     // every refusal ahead of the first queued operation
-    int rc = scan_check(s, sp, scan);
+    int rc = scan_check(s, sp, cp, withClear, scan);
     if (rc != FPE_OK) return rc;
     fpe_map_update u;
     std::memset(&u, 0, sizeof(u));
@@ -4173,16 +4230,22 @@ int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params
     rc = op.enter();
     if (rc != FPE_OK) return rc;
     fpe_scan_info* dInfo = scanInfo;
+    fpe_scan_clear_info* dClearInfo = clearInfo;
     if (!onDevice) {
         rc = scan_stage_points(s, scan, points);
         if (rc != FPE_OK) return rc;
         points = s->pts;
         dInfo = reinterpret_cast<fpe_scan_info*>(s->acc + fpe::kScanAccWords);
+        dClearInfo = reinterpret_cast<fpe_scan_clear_info*>(s->acc + fpe::kScanAccWords + 16);
     }
     if (shift[0] != 0 || shift[1] != 0 || position[0] != s->g.posX || position[1] != s->g.posY) {
         rc = scan_move_locked(s, shift, position, op.stream);
         if (rc != FPE_OK) return rc;
         patch();  // (the move swapped the buffers)
+    }
+    if (withClear) {
+        rc = scan_clear_locked(s, sp, cp, scan, points, dClearInfo, op.stream);
+        if (rc != FPE_OK) return rc;
     }
     rc = scan_fuse_locked(s, sp, scan, points, dInfo, op.stream);
     if (rc != FPE_OK) return rc;
@@ -4190,9 +4253,12 @@ int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params
     if (rc != FPE_OK) return rc;
     if (!onDevice) {
         fpe_scan_info got;
+        fpe_scan_clear_info gotClear;
         FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, op.stream));
+        if (withClear) FPE_HIP(hipMemcpyAsync(&gotClear, dClearInfo, sizeof(gotClear), hipMemcpyDeviceToHost, op.stream));
         FPE_HIP(hipStreamSynchronize(op.stream));
         if (scanInfo) *scanInfo = got;
+        if (withClear && clearInfo) *clearInfo = gotClear;
     }
     return FPE_OK;
 }
@@ -4221,7 +4287,7 @@ int fpe_scan_create(fpe_handle h, const fpe_map_desc* geom, fpe_scan_handle* out
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->var[k]), s->n * sizeof(float) + kLayerPadBytes);
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->cells), s->n * sizeof(fpe::ScanCell));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->acc), (fpe::kScanAccWords + 16) * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->acc), (fpe::kScanAccWords + 32) * sizeof(int32_t));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->last, hipEventDisableTiming);
     if (e == hipSuccess) e = fpe::launch_scan_set(nullptr, nullptr, reinterpret_cast<uint32_t*>(s->elev[0]), reinterpret_cast<uint32_t*>(s->var[0]), s->n, s->own);
@@ -4315,13 +4381,37 @@ int fpe_scan_install(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* f
 
 int fpe_scan_ingest(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan, const float* points,
                     const int32_t shift[2], const double position[2], fpe_scan_info* scan_info, fpe_elevation_update_info* update_info) {
-    return scan_ingest_common(h, s, fp, sp, scan, points, shift, position, scan_info, update_info, false, nullptr);
+    return scan_ingest_common(h, s, fp, sp, nullptr, false, scan, points, shift, position, nullptr, scan_info, update_info, false, nullptr);
 }
 
 int fpe_scan_ingest_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan,
                            const float* d_points, const int32_t shift[2], const double position[2], fpe_scan_info* d_scan_info,
                            fpe_elevation_update_info* update_info, void* stream) {
-    return scan_ingest_common(h, s, fp, sp, scan, d_points, shift, position, d_scan_info, update_info, true, static_cast<hipStream_t>(stream));
+    return scan_ingest_common(h, s, fp, sp, nullptr, false, scan, d_points, shift, position, nullptr, d_scan_info, update_info, true,
+                              static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_clear(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* points,
+                   fpe_scan_clear_info* info) {
+    return scan_clear_common(s, sp, cp, scan, points, info, false, nullptr);
+}
+
+int fpe_scan_clear_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* d_points,
+                          fpe_scan_clear_info* d_info, void* stream) {
+    return scan_clear_common(s, sp, cp, scan, d_points, d_info, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_ingest_clear(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                          const fpe_scan* scan, const float* points, const int32_t shift[2], const double position[2], fpe_scan_clear_info* clear_info,
+                          fpe_scan_info* scan_info, fpe_elevation_update_info* update_info) {
+    return scan_ingest_common(h, s, fp, sp, cp, true, scan, points, shift, position, clear_info, scan_info, update_info, false, nullptr);
+}
+
+int fpe_scan_ingest_clear_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                                 const fpe_scan* scan, const float* d_points, const int32_t shift[2], const double position[2],
+                                 fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info, fpe_elevation_update_info* update_info, void* stream) {
+    return scan_ingest_common(h, s, fp, sp, cp, true, scan, d_points, shift, position, d_clear_info, d_scan_info, update_info, true,
+                              static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -675,6 +675,20 @@ int fpe_scan_validate(const fpe_map_desc* geom, const fpe_scan_params* sp, const
     return fpe::check_scan(geom->rows, geom->cols, sp, scan, &why);
 }
 
+int fpe_scan_clear_params_defaults(fpe_scan_clear_params* out) {
+    if (!out) return FPE_E_INVALID_ARG;
+    fpe::scan_clear_params_defaults(*out);
+    return FPE_OK;
+}
+
+int fpe_scan_clear_validate(const fpe_map_desc* geom, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan) {
+    if (!geom) return FPE_E_INVALID_ARG;
+    const char* why = nullptr;
+    const int rc = fpe::check_map_geometry(geom->rows, geom->cols, geom->resolution, &why);
+    if (rc != FPE_OK) return rc;
+    return fpe::check_scan_clear(geom->rows, geom->cols, sp, cp, scan, &why);
+}
+
 }  // extern "C"
 
 namespace fpe {
@@ -747,6 +761,62 @@ void scan_consts(const fpe_scan_params& sp, const fpe_scan& scan, const MapGeom&
     a.col0 = scan.roi[1];
     a.nr = scan.roi[2];
     a.nc = scan.roi[3];
+}
+
+void scan_clear_params_defaults(fpe_scan_clear_params& out) {
+    out.sample_step = 0.5f;
+    out.margin = 0.10f;
+    out.start_samples = 2;
+    out.end_samples = 4;
+    out.min_hits = 2;
+    out.ray_stride = 1;
+    out.max_samples = 4096;
+    out.reserved = 0;
+}
+
+int check_scan_clear(int rows, int cols, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const char** why) {
+    const int rc = check_scan(rows, cols, sp, scan, why);
+    if (rc != FPE_OK) return rc;
+    auto bad = [&](const char* msg) {
+        *why = msg;
+        return static_cast<int>(FPE_E_INVALID_ARG);
+    };
+    if (!cp) return bad("null clear parameters");
+    if (!std::isfinite(cp->sample_step) || !std::isfinite(cp->margin)) return bad("non-finite clear parameter");
+    if (!(cp->sample_step > 0.0f && cp->sample_step <= 1.0f)) return bad("sample_step outside (0, 1]");
+    if (cp->margin < 0.0f) return bad("negative margin");
+    if (cp->start_samples < 0 || cp->end_samples < 0) return bad("negative start_samples or end_samples");
+    if (cp->min_hits < 1) return bad("min_hits below 1");
+    if (cp->ray_stride < 1) return bad("ray_stride below 1");
+    if (cp->max_samples < 1 || cp->max_samples > 65536) return bad("max_samples outside 1 .. 65536");
+    if (cp->reserved != 0) return bad("reserved must be 0");
+    return FPE_OK;
+}
+
+// The constants of a clear as its kernels take them: the fuse's point tests (scan_consts) and the clear's widenings.
+void scan_clear_consts(const fpe_scan_params& sp, const fpe_scan_clear_params& cp, const fpe_scan& scan, const MapGeom& g, ScanClearArgs& a) {
+    ScanArgs f;
+    scan_consts(sp, scan, g, f);
+    for (int k = 0; k < 12; ++k) a.T[k] = f.T[k];
+    a.minR2 = f.minR2;
+    a.maxR2 = f.maxR2;
+    a.minZ = f.minZ;
+    a.maxZ = f.maxZ;
+    a.g = g;
+    a.step = static_cast<double>(cp.sample_step) * g.res;
+    a.margin = cp.margin;
+    a.maxSamples = cp.max_samples;
+    a.startSamples = cp.start_samples;
+    a.endSamples = cp.end_samples;
+    a.minHits = cp.min_hits;
+    a.rayStride = cp.ray_stride;
+    a.n = f.n;
+    a.stride = f.stride;
+    a.nCast = static_cast<int32_t>((static_cast<int64_t>(f.n) + cp.ray_stride - 1) / cp.ray_stride);
+    a.row0 = f.row0;
+    a.col0 = f.col0;
+    a.nr = f.nr;
+    a.nc = f.nc;
 }
 
 int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevationOnly, const char** why) {

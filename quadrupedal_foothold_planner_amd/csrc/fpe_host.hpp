@@ -51,6 +51,9 @@ int check_map_geometry(int rows, int cols, double res, const char** why);
 // The refusals of fpe_scan_fuse* for a state of rows x cols cells (include/fpe.h): FPE_OK, or FPE_E_INVALID_ARG with *why set.
 int check_scan(int rows, int cols, const fpe_scan_params* sp, const fpe_scan* scan, const char** why);
 void scan_params_defaults(fpe_scan_params& out);
+// The refusals of fpe_scan_clear*: check_scan's, then the clear parameters'.
+int check_scan_clear(int rows, int cols, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const char** why);
+void scan_clear_params_defaults(fpe_scan_clear_params& out);
 
 // ---- the producer's filter chain (fpe_filters.hpp): its host arithmetic — filter_route and friends are declared in fpe_launch.hpp ----
 void filter_params_defaults(fpe_filter_params& out);

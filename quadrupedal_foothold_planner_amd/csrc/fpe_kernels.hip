@@ -2297,6 +2297,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_beam_check.hpp"
 // ---- part sixteen: scan fusion (fpe_scan_*): a point cloud into the elevation and variance layers of a scan state ----------
 #include "fpe_scan.hpp"
+// ---- part seventeen: scan visibility clearing (fpe_scan_clear*; uses part sixteen's constants, counters and ticket) ---------
+#include "fpe_scan_clear.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)

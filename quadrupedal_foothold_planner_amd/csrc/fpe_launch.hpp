@@ -522,4 +522,35 @@ hipError_t launch_scan_move(const uint32_t* srcElev, const uint32_t* srcVar, uin
 // both layers from two sources: a cell that is NaN in either becomes the cleared value in both (srcElev null: every cell cleared)
 hipError_t launch_scan_set(const uint32_t* srcElev, const uint32_t* srcVar, uint32_t* dstElev, uint32_t* dstVar, size_t n, hipStream_t stream);
 
+// ---- scan visibility clearing (fpe_scan_clear.hpp) -------------------------------------------------------------
+// The clear shares the state's scratch with the fuse (the two never overlap on one state): a cell's hits are counted in ScanCell's
+// `count` word (0 at rest), the bounding box and the ticket are the fuse's accumulator words 12-15 and 16 (same rest values), and
+// its own totals live in words the fuse leaves at 0:
+constexpr int kClearAccDropped = 17;  // then rays, rays_long, rays_empty, cells_hit, cells_cleared: fpe_scan_clear_info's words 2-7
+constexpr int kClearAccWide = 24;     // samples_in_roi and hit_pairs, 64 bits each (words 24-27; 8-byte aligned): the info's words 12-15
+// The argument block of both passes, by value.
+struct ScanClearArgs {
+    double T[12];
+    double minR2, maxR2, minZ, maxZ;
+    MapGeom g;
+    double step;        // double(sample_step) * resolution
+    double margin;      // double(margin)
+    double maxSamples;  // double(max_samples)
+    int32_t startSamples, endSamples, minHits, rayStride;
+    int32_t n, stride;  // points, floats per point
+    int32_t nCast;      // points that cast a ray or are dropped: ceil(n / rayStride)
+    int32_t row0, col0, nr, nc;
+    const float* points;
+    ScanCell* cells;
+    int32_t* acc;
+    uint32_t* elev;
+    uint32_t* var;
+    int32_t* info;  // the caller's fpe_scan_clear_info (device) as sixteen words, or null
+};
+void scan_clear_consts(const fpe_scan_params& sp, const fpe_scan_clear_params& cp, const fpe_scan& scan, const MapGeom& g, ScanClearArgs& a);  // fpe_host.cpp
+// The ray pass (form 1: one lane per ray; 2: `group` = 16, 32 or 64 adjacent lanes per ray) and the cell pass on `stream`.
+hipError_t launch_scan_clear(const ScanClearArgs& a, int form, int group, hipStream_t stream);
+hipError_t launch_scan_clear_rays(const ScanClearArgs& a, int form, int group, hipStream_t stream);
+hipError_t launch_scan_clear_cells(const ScanClearArgs& a, hipStream_t stream);
+
 }  // namespace fpe

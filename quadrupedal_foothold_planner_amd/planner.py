@@ -325,6 +325,25 @@ def scan_validate(rows, cols, resolution, params, scan):
     return _capi.lib().fpe_scan_validate(C.byref(d), C.byref(params) if params is not None else None, C.byref(scan) if scan is not None else None)
 
 
+def scan_clear_params(**overrides):
+    """fpe_scan_clear_params_defaults, with any field replaced by a keyword."""
+    cp = _capi.ScanClearParams()
+    assert _capi.lib().fpe_scan_clear_params_defaults(C.byref(cp)) == _capi.FPE_OK
+    for k, v in overrides.items():
+        if k not in dict(_capi.ScanClearParams._fields_):
+            raise ValueError(f"unknown scan clear parameter {k!r}")
+        setattr(cp, k, v)
+    return cp
+
+
+def scan_clear_validate(rows, cols, resolution, params, clear_params, scan):
+    """fpe_scan_clear_validate (host arithmetic, no engine): the status a clear of `scan` in a rows x cols state would be refused
+    with, or FPE_OK.  `params` / `clear_params` / `scan` may be None (a null argument)."""
+    d = _map_desc(rows, cols, resolution)
+    ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+    return _capi.lib().fpe_scan_clear_validate(C.byref(d), ref(params), ref(clear_params), ref(scan))
+
+
 class _Handle:
     """What an engine and a group of engines share: the handle's creation, close / __del__, and the status check.  A subclass names
     its three entry points."""
@@ -503,7 +522,7 @@ class FootholdPlanner(_Handle):
         return buf.value.decode()
 
     def set_tuning(self, **kw):
-        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, beam_check_waves, scan_merge, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
+        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, beam_check_waves, scan_merge, scan_clear_form, scan_clear_group, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
         for k, v in kw.items():
             self._check(self._lib.fpe_set_tuning(self._h, k.encode(), int(v)))
             self._tuning[k] = int(v)
@@ -1402,6 +1421,46 @@ class ScanState:
                                                      C.byref(params if params is not None else scan_params()), C.byref(scan),
                                                      C.c_void_p(d_points_ptr), sh, pos, C.c_void_p(d_info_ptr or 0), C.byref(ui),
                                                      C.c_void_p(stream or 0)))
+        return _info_dict(ui)
+
+    # ---- visibility clearing: cells a scan sees through become unknown (fpe_scan_clear*) -------------------------------
+    def clear(self, scan, points, params=None, clear_params=None):
+        """fpe_scan_clear: host points -> the call's info as a SCAN_CLEAR_INFO_DTYPE record.  Synchronous."""
+        p = self._points(points, scan)
+        info = np.zeros(1, _capi.SCAN_CLEAR_INFO_DTYPE)
+        self._check(self._lib.fpe_scan_clear(self._s, C.byref(params if params is not None else scan_params()),
+                                             C.byref(clear_params if clear_params is not None else scan_clear_params()), C.byref(scan), ptr(p), ptr(info)))
+        return info[0]
+
+    def clear_device(self, scan, d_points_ptr, params=None, clear_params=None, d_info_ptr=0, stream=None):
+        """fpe_scan_clear_device: device points, a device info of 64 bytes (0: not wanted); asynchronous on `stream`."""
+        self._check(self._lib.fpe_scan_clear_device(self._s, C.byref(params if params is not None else scan_params()),
+                                                    C.byref(clear_params if clear_params is not None else scan_clear_params()), C.byref(scan),
+                                                    C.c_void_p(d_points_ptr), C.c_void_p(d_info_ptr or 0), C.c_void_p(stream or 0)))
+
+    def ingest_clear(self, scan, points, shift, position, params=None, clear_params=None, filter_params=None):
+        """fpe_scan_ingest_clear: move (when the shift or the position says so), clear, fuse, and the roi into the snapshot ->
+        (clear info record, scan info record, update info dict).  Synchronous."""
+        p = self._points(points, scan)
+        sh, pos = self._move_args(shift, position)
+        cinfo, info, ui = np.zeros(1, _capi.SCAN_CLEAR_INFO_DTYPE), np.zeros(1, _capi.SCAN_INFO_DTYPE), _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_scan_ingest_clear(self._planner._h, self._s, C.byref(filter_params) if filter_params is not None else None,
+                                                    C.byref(params if params is not None else scan_params()),
+                                                    C.byref(clear_params if clear_params is not None else scan_clear_params()), C.byref(scan), ptr(p),
+                                                    sh, pos, ptr(cinfo), ptr(info), C.byref(ui)))
+        return cinfo[0], info[0], _info_dict(ui)
+
+    def ingest_clear_device(self, scan, d_points_ptr, shift, position, params=None, clear_params=None, filter_params=None, d_clear_info_ptr=0,
+                            d_info_ptr=0, stream=None):
+        """fpe_scan_ingest_clear_device: the same with device points and device infos (0: not wanted), asynchronous on `stream` ->
+        the update info dict."""
+        sh, pos = self._move_args(shift, position)
+        ui = _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_scan_ingest_clear_device(self._planner._h, self._s, C.byref(filter_params) if filter_params is not None else None,
+                                                           C.byref(params if params is not None else scan_params()),
+                                                           C.byref(clear_params if clear_params is not None else scan_clear_params()), C.byref(scan),
+                                                           C.c_void_p(d_points_ptr), sh, pos, C.c_void_p(d_clear_info_ptr or 0),
+                                                           C.c_void_p(d_info_ptr or 0), C.byref(ui), C.c_void_p(stream or 0)))
         return _info_dict(ui)
 
 
