@@ -278,6 +278,8 @@ int fpe_destroy(fpe_handle h);
  * "scan_clear_form": the form of the ray pass of fpe_scan_clear*: 0 (DEFAULT) the engine's choice, 1 one lane per ray, 2 a group of
  * adjacent lanes per ray; "scan_clear_group": that group's width: 0 (DEFAULT) the engine's choice, 16, 32 or 64 (see there); the
  * outputs depend on neither.
+ * "scan_close_form": the form of fpe_scan_close*'s kernel: 0 (DEFAULT) the engine's choice, 1 direct, 2 tiled in LDS (see there); the
+ * outputs do not depend on it.
  * "service_overlap" (default 1): a call that runs the plan AND the opt track for at most four poses launches the opt
  * track's chain on a second stream beside the plan kernel, on nominal cycle flags of 1 (the flags only decide which cycles the
  * chain commits, cpp:1323-1332, and are 1 unless a nominal search fails), and runs it again on the real flags in the call where
@@ -1676,6 +1678,81 @@ extern int fpe_scan_ingest_clear_device(fpe_handle h, fpe_scan_handle s, const f
                                         const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* d_points,
                                         const int32_t shift[2], const double position[2], fpe_scan_clear_info* d_clear_info,
                                         fpe_scan_info* d_scan_info, fpe_elevation_update_info* update_info, void* stream);
+
+/* 5. Gap closing (fpe_scan_close[_device]): small holes of the state's elevation bridged FOR THE PLANNER.  A fused scan is full of
+ *    them (cells between two lidar rings, between the pixels of a depth image at range, cells the clear has just removed), and the
+ *    filter chain and every check read an unknown cell as "no data".  The close is a PURE FUNCTION of the state's elevation layer: it
+ *    never writes the state (an invented height never becomes the prior of a later fuse), reads no variance and produces none.
+ *    BUILD-DEFINED like the fuse; the numpy statement is tests/scan_close_reference.py.  THE CONTRACT: all arithmetic is f32, every
+ *    operation rounded on its own, no contraction, IEEE division.  A cell is KNOWN iff it lies inside the map and its elevation is not
+ *    NaN (infinities are known); off the map counts as unknown.  The axes are a0 = (0, +1), a1 = (+1, 0), a2 = (+1, +1),
+ *    a3 = (+1, -1), as (row, column) steps.  For every cell c of the requested rectangle:
+ *      1. c known: the output takes the cell's bits;
+ *      2. otherwise, per axis a: s+ is the least s in 1..reach for which c + s a is known, s- the same for c - s a (each search ends
+ *         at the first known cell or at the map's edge); the axis SPANS iff both exist and s+ + s- - 1 <= max_gap; h+ and h- are its
+ *         two end heights;
+ *      3. n = the number of spanning axes; lo and hi = the least and the greatest end height over the spanning axes only;
+ *      4. n == 0: no_support;  0 < n < min_axes: rejected_axes;  not ((hi - lo) <= max_spread): rejected_spread (a NaN difference
+ *         is rejected here);
+ *      5. otherwise the spanning axis with the least s+ + s-, the lowest axis number among equals, gives
+ *         v = h- + (h+ - h-) * (float(s-) / float(s+ + s-));  a NaN v is rejected_spread, any other v FILLS the cell;
+ *      6. every cell that is neither known nor filled takes the quiet NaN 0x7FC00000.
+ *    fpe_scan_close[_device] writes the closed elevation of `rect` = {row0, col0, n_rows, n_cols} rectangle-local: element (r, c) at
+ *    out[r * out_row_stride + c], out_row_stride >= n_cols.  cls may be NULL; given, it takes one byte per cell with the same pitch:
+ *    0 known, 1 filled, 2 no_support, 3 rejected_axes, 4 rejected_spread.  Nothing outside the rectangle's elements is written, and
+ *    neither the state's layers nor its scratch.  info may be NULL; cells = known + unknown, unknown = filled + no_support +
+ *    rejected_axes + rejected_spread.  A closed value depends on the state only within `reach` cells.
+ *    Refusals (FPE_E_INVALID_ARG; nothing written, nothing queued): a null state, kp, rect or out; a field outside the range its
+ *    comment gives; a NaN or negative max_spread; a reserved word that is not 0; out_row_stride < n_cols; a rectangle that is empty
+ *    or reaches outside the state.  fpe_scan_close_validate is that routine without an engine (of `geom` rows, cols, resolution).
+ *    Forms: host (host out / cls / info, synchronous) and device (device buffers, a device info of 64 bytes, asynchronous on
+ *    `stream`, never synchronises the host).  Ordering as in point 1: an operation of the state.  One launch per rectangle, in one of
+ *    two forms of identical output, fpe_set_tuning "scan_close_form": 0 (DEFAULT) the engine's choice, 1 direct (one lane per cell,
+ *    the searches through global memory), 2 tiled (a workgroup stages a 16 x 64 tile and a halo of `reach` in LDS).
+ *     - fpe_scan_install_closed: fpe_scan_install with the closed whole-map layer in place of the state's elevation: the snapshot's
+ *       elevation is close(state), its traversability the filter chain's answer for that.
+ *     - fpe_scan_ingest_closed[_device]: move (when the shift or the position says so), the clear when cp != NULL, the fuse, the close
+ *       of up to three rectangles, then ONE fpe_update_elevation_device whose patches carry the closed rectangles: (1) scan->roi
+ *       grown by `reach` on every side, clipped to the map; (2) if sr > 0 the rows [0, reach), if sr < 0 the last `reach` rows, all
+ *       columns; (3) the same for sc on the columns.  Later patches may overlap earlier ones; their values agree.  close_info
+ *       describes rectangle (1).  Refused as a whole under fpe_scan_ingest_clear's conditions (without the clear's when cp == NULL)
+ *       plus the close's, before anything is queued.  Every info may be NULL.
+ *       PROMISED: after fpe_scan_install_closed and any sequence of fpe_scan_ingest_closed* calls with the same kp, the elevation
+ *       fpe_read_map_layers returns equals close(whole state) bit for bit (off the map and unknown are the same thing to the close,
+ *       so entering cells change nothing, and only the side whose neighbours left the map loses support).  Mixing these with
+ *       fpe_scan_install / fpe_scan_ingest / fpe_scan_ingest_clear or with another kp VOIDS that promise: those write the state's own
+ *       elevation into the snapshot, and the carried cells keep what the last call put there. */
+typedef struct fpe_scan_close_params {   /* 32 bytes */
+    int32_t reach;          /* cells searched along each direction; 1 .. 8 */
+    int32_t max_gap;        /* unknown cells an axis may bridge (s+ + s- - 1); 1 .. 2 * reach - 1 */
+    int32_t min_axes;       /* spanning axes a filled cell needs; 1 .. 4 */
+    float   max_spread;     /* m between the least and the greatest end height; >= 0, may be +infinity, not NaN */
+    int32_t reserved[4];    /* 0 */
+} fpe_scan_close_params;
+/* defaults: 4, 5, 2, 0.08 */
+typedef struct fpe_scan_close_info {     /* 64 bytes */
+    int32_t cells, known, unknown, filled, no_support, rejected_axes, rejected_spread, reserved;
+    int32_t bbox[4];        /* of the filled cells, state indices; {0,0,-1,-1} when none */
+    int32_t reserved2[4];
+} fpe_scan_close_info;
+extern int fpe_scan_close_params_defaults(fpe_scan_close_params* out);
+extern int fpe_scan_close_validate(const fpe_map_desc* geom, const fpe_scan_close_params* kp, const int32_t rect[4]);  /* host arithmetic only; no engine */
+extern int fpe_scan_close(fpe_scan_handle s, const fpe_scan_close_params* kp, const int32_t rect[4], float* out, int64_t out_row_stride,
+                          uint8_t* cls, fpe_scan_close_info* info);
+extern int fpe_scan_close_device(fpe_scan_handle s, const fpe_scan_close_params* kp, const int32_t rect[4], float* d_out,
+                                 int64_t out_row_stride, uint8_t* d_cls, fpe_scan_close_info* d_info, void* stream);
+extern int fpe_scan_install_closed(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_close_params* kp,
+                                   void* stream);
+extern int fpe_scan_ingest_closed(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp,
+                                  const fpe_scan_clear_params* cp, const fpe_scan_close_params* kp, const fpe_scan* scan,
+                                  const float* points, const int32_t shift[2], const double position[2],
+                                  fpe_scan_clear_info* clear_info, fpe_scan_info* scan_info, fpe_scan_close_info* close_info,
+                                  fpe_elevation_update_info* update_info);
+extern int fpe_scan_ingest_closed_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp,
+                                         const fpe_scan_clear_params* cp, const fpe_scan_close_params* kp, const fpe_scan* scan,
+                                         const float* d_points, const int32_t shift[2], const double position[2],
+                                         fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info,
+                                         fpe_scan_close_info* d_close_info, fpe_elevation_update_info* update_info, void* stream);
 
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,

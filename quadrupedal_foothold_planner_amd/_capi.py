@@ -447,6 +447,21 @@ SCAN_CLEAR_INFO_DTYPE = np.dtype(
 )
 assert (C.sizeof(ScanClearParams), SCAN_CLEAR_INFO_DTYPE.itemsize) == (32, 64)
 
+
+class ScanCloseParams(C.Structure):
+    """fpe_scan_close_params: how far a gap closing searches, how wide a gap it bridges, how many axes must span a cell and how far
+    their end heights may lie apart."""
+    _fields_ = [("reach", C.c_int32), ("max_gap", C.c_int32), ("min_axes", C.c_int32), ("max_spread", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+# fpe_scan_close_info: sixteen int32
+SCAN_CLOSE_INFO_DTYPE = np.dtype(
+    [("cells", "<i4"), ("known", "<i4"), ("unknown", "<i4"), ("filled", "<i4"), ("no_support", "<i4"), ("rejected_axes", "<i4"),
+     ("rejected_spread", "<i4"), ("reserved", "<i4"), ("bbox", "<i4", (4,)), ("reserved2", "<i4", (4,))],
+    align=True,
+)
+assert (C.sizeof(ScanCloseParams), SCAN_CLOSE_INFO_DTYPE.itemsize) == (32, 64)
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -469,6 +484,7 @@ STRUCTS = {
     "fpe_check_params": CheckParams, "fpe_check_out": CheckOut, "fpe_beam_check_out": BeamCheckOut,
     "fpe_scan_params": ScanParams, "fpe_scan": Scan, "fpe_scan_info": SCAN_INFO_DTYPE,
     "fpe_scan_clear_params": ScanClearParams, "fpe_scan_clear_info": SCAN_CLEAR_INFO_DTYPE,
+    "fpe_scan_close_params": ScanCloseParams, "fpe_scan_close_info": SCAN_CLOSE_INFO_DTYPE,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -603,6 +619,15 @@ PROTOTYPES = {
                                      P(ElevationUpdateInfo)]),
     "fpe_scan_ingest_clear_device": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(Scan), vp, P(i32), P(f64), vp, vp,
                                             P(ElevationUpdateInfo), vp]),
+    "fpe_scan_close_params_defaults": (cint, [P(ScanCloseParams)]),
+    "fpe_scan_close_validate": (cint, [P(MapDesc), P(ScanCloseParams), P(i32)]),
+    "fpe_scan_close": (cint, [vp, P(ScanCloseParams), P(i32), vp, C.c_int64, vp, vp]),
+    "fpe_scan_close_device": (cint, [vp, P(ScanCloseParams), P(i32), vp, C.c_int64, vp, vp, vp]),
+    "fpe_scan_install_closed": (cint, [vp, vp, P(FilterParams), P(ScanCloseParams), vp]),
+    "fpe_scan_ingest_closed": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(ScanCloseParams), P(Scan), vp, P(i32), P(f64),
+                                      vp, vp, vp, P(ElevationUpdateInfo)]),
+    "fpe_scan_ingest_closed_device": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(ScanCloseParams), P(Scan), vp, P(i32),
+                                             P(f64), vp, vp, vp, P(ElevationUpdateInfo), vp]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

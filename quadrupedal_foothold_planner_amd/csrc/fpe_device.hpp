@@ -53,6 +53,7 @@ struct Tuning {
     int32_t beamCheckWaves = 0;  // fpe_plan_beam_checked*: wavefronts per candidate of beam_check_kernel, 1 or 4; 0: by the map's resolution (fpe_engine.cpp, beam_check_map)
     int32_t scanClearForm = 0;   // fpe_scan_clear*: 0 the engine's choice, 1 one lane per ray, 2 a group of adjacent lanes per ray (fpe_scan_clear.hpp)
     int32_t scanClearGroup = 0;  // that group's width: 0 the engine's choice, 16, 32, 64
+    int32_t scanCloseForm = 0;   // fpe_scan_close*: 0 the engine's choice, 1 direct (one lane per cell), 2 tiled in LDS (fpe_scan_close.hpp)
     int32_t scanMerge = 0;      // fpe_scan_fuse*: 0 the engine's choice, 1 the plain form, 2 runs of equal cells merged across adjacent lanes (fpe_scan.hpp)
     int32_t serviceOptGate = 2;  // fpe_plan_service*: 2 enforce (default: the handler's behaviour), 1 advisory (chain runs, reported), 0 exact gates only (no opt chain) (include/fpe.h)
 };

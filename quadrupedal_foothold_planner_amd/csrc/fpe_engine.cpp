@@ -1641,6 +1641,9 @@ int fpe_set_tuning(fpe_handle h, const char* key, int32_t value) {
     } else if (k == "scan_clear_group") {
         if (value != 0 && value != 16 && value != 32 && value != 64) return fail(FPE_E_INVALID_ARG, "scan_clear_group is 0 (the engine's choice), 16, 32 or 64");
         h->tuning.scanClearGroup = value;
+    } else if (k == "scan_close_form") {
+        if (value < 0 || value > 2) return fail(FPE_E_INVALID_ARG, "scan_close_form is 0 (the engine's choice), 1 (direct) or 2 (tiled)");
+        h->tuning.scanCloseForm = value;
     } else if (k == "service_overlap") h->tuning.serviceOverlap = value ? 1 : 0;
     else if (k == "service_poll") h->tuning.servicePoll = value ? 1 : 0;
     else if (k == "service_cycle0_gate_only") h->tuning.serviceOptGate = value ? 0 : 2;  // (older name)
@@ -3989,6 +3992,10 @@ struct fpe_scan_state {
     float* pts = nullptr;
     size_t ptsCap = 0;       // floats
     float* trav = nullptr;   // fpe_scan_install's traversability layer (allocated by the first install)
+    float* closed = nullptr;     // the closed elevation the planner gets (fpe_scan_install_closed, fpe_scan_ingest_closed) and the host close's
+                                 // staging; allocated by the first close, with:
+    int32_t* closeAcc = nullptr; // the close's own accumulators and the host forms' device info (kCloseAccWords)
+    bool closeFresh = false;     // closeAcc still has to be reset, on the stream of the first close
     hipEvent_t last = nullptr;
     hipStream_t own = nullptr;
 };
@@ -3999,6 +4006,7 @@ constexpr int kScanMergeDefault = 2;  // "scan_merge" 0: the form measured faste
 // "scan_clear_form" / "scan_clear_group" 0: the form measured faster on the depth image of profiles/scan_clear_summary.txt
 constexpr int kScanClearFormDefault = 1;
 constexpr int kScanClearGroupDefault = 16;
+constexpr int kScanCloseFormDefault = 2;  // "scan_close_form" 0: see profiles/scan_close_summary.txt
 
 // An operation of a state on `stream`: behind the state's last one, and its own event recorded on every way out (an operation that
 // failed half-way may have queued work the next one must not overtake).  The caller holds s->mu.
@@ -4129,6 +4137,97 @@ int scan_clear_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sc
     return FPE_OK;
 }
 
+// The close's buffers, allocated by a state's first close (the caller holds s->mu and has set the device); the accumulators are
+// reset by scan_close_locked on the stream of that close, which every later operation of the state is ordered behind.
+int scan_close_alloc(fpe_scan_state* s) {
+    if (!s->closed) FPE_HIP(hipMalloc(reinterpret_cast<void**>(&s->closed), s->n * sizeof(float) + kLayerPadBytes));
+    if (!s->closeAcc) {
+        FPE_HIP(hipMalloc(reinterpret_cast<void**>(&s->closeAcc), fpe::kCloseAccWords * sizeof(int32_t)));
+        s->closeFresh = true;
+    }
+    return FPE_OK;
+}
+
+// The one launch of a close on `stream` (the caller holds s->mu, has validated the call, has called scan_close_alloc and has entered
+// `stream`).  The state's layers and scratch are only read.
+int scan_close_locked(fpe_scan_state* s, const fpe_scan_close_params* kp, const int32_t rect[4], float* d_out, int64_t outStride, uint8_t* d_cls,
+                      fpe_scan_close_info* d_info, hipStream_t stream) {
+    int form;
+    {
+        std::lock_guard<std::mutex> lk(s->h->mu);
+        form = s->h->tuning.scanCloseForm;
+    }
+    if (form == 0) form = kScanCloseFormDefault;
+    if (s->closeFresh) {
+        FPE_HIP(fpe::launch_scan_close_reset(s->closeAcc, stream));
+        s->closeFresh = false;
+    }
+    fpe::ScanCloseArgs a;
+    fpe::scan_close_consts(*kp, rect, s->g.rows, s->g.cols, a);
+    a.outStride = outStride;
+    a.elev = reinterpret_cast<const uint32_t*>(s->elev[s->cur]);
+    a.out = reinterpret_cast<uint32_t*>(d_out);
+    a.cls = d_cls;
+    a.acc = s->closeAcc;
+    a.info = reinterpret_cast<int32_t*>(d_info);
+    FPE_HIP(fpe::launch_scan_close(a, form, stream));
+    return FPE_OK;
+}
+
+int scan_close_check(const fpe_scan_state* s, const fpe_scan_close_params* kp, const int32_t rect[4]) {
+    const char* why = "";
+    const int rc = fpe::check_scan_close(s->g.rows, s->g.cols, kp, rect, &why);
+    return rc == FPE_OK ? rc : fail(rc, why);
+}
+
+// The rectangles an ingest closes (include/fpe.h): the roi grown by the reach, then the strips whose neighbours a move took off the map.
+int scan_close_rects(const fpe_scan_state* s, const fpe_scan_close_params* kp, const fpe_scan* scan, const int32_t shift[2], int32_t rects[3][4]) {
+    const int rows = s->g.rows, cols = s->g.cols, R = kp->reach;
+    const int r0 = std::max(0, scan->roi[0] - R), c0 = std::max(0, scan->roi[1] - R);
+    const int r1 = std::min<int64_t>(rows, static_cast<int64_t>(scan->roi[0]) + scan->roi[2] + R);
+    const int c1 = std::min<int64_t>(cols, static_cast<int64_t>(scan->roi[1]) + scan->roi[3] + R);
+    int n = 0;
+    const auto put = [&](int a, int b, int c, int d) {
+        rects[n][0] = a, rects[n][1] = b, rects[n][2] = c, rects[n][3] = d;
+        ++n;
+    };
+    put(r0, c0, r1 - r0, c1 - c0);
+    if (shift[0] != 0) put(shift[0] > 0 ? 0 : rows - R, 0, R, cols);
+    if (shift[1] != 0) put(0, shift[1] > 0 ? 0 : cols - R, rows, R);
+    return n;
+}
+
+int scan_close_common(fpe_scan_state* s, const fpe_scan_close_params* kp, const int32_t rect[4], float* out, int64_t outStride, uint8_t* cls,
+                      fpe_scan_close_info* info, bool onDevice, hipStream_t stream) {
+    if (!s || !out) return fail(FPE_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    int rc = scan_close_check(s, kp, rect);
+    if (rc != FPE_OK) return rc;
+    if (outStride < rect[3]) return fail(FPE_E_INVALID_ARG, "out_row_stride below the rectangle's columns");
+    FPE_HIP(hipSetDevice(s->h->device));
+    rc = scan_close_alloc(s);
+    if (rc != FPE_OK) return rc;
+    ScanOp op{s, onDevice ? stream : s->own};
+    rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    if (onDevice) return scan_close_locked(s, kp, rect, out, outStride, cls, info, stream);
+    // host form: the rectangle is closed into `closed` (dense), the classes into the second elevation buffer (a staging area, as for
+    // a host set), and both come back with their pitch
+    const size_t nr = static_cast<size_t>(rect[2]), nc = static_cast<size_t>(rect[3]);
+    uint8_t* dCls = cls ? reinterpret_cast<uint8_t*>(s->elev[s->cur ^ 1]) : nullptr;
+    fpe_scan_close_info* dInfo = reinterpret_cast<fpe_scan_close_info*>(s->closeAcc + fpe::kCloseAccInfo);
+    rc = scan_close_locked(s, kp, rect, s->closed, rect[3], dCls, dInfo, s->own);
+    if (rc != FPE_OK) return rc;
+    fpe_scan_close_info got;
+    FPE_HIP(hipMemcpy2DAsync(out, static_cast<size_t>(outStride) * sizeof(float), s->closed, nc * sizeof(float), nc * sizeof(float), nr, hipMemcpyDeviceToHost,
+                             s->own));
+    if (cls) FPE_HIP(hipMemcpy2DAsync(cls, static_cast<size_t>(outStride), dCls, nc, nc, nr, hipMemcpyDeviceToHost, s->own));
+    FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, s->own));
+    FPE_HIP(hipStreamSynchronize(s->own));
+    if (info) *info = got;
+    return FPE_OK;
+}
+
 // (cp == nullptr with withClear == false: the fuse's refusals alone)
 int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, bool withClear, const fpe_scan* scan) {
     const char* why = "";
@@ -4190,16 +4289,31 @@ int scan_clear_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sc
     return FPE_OK;
 }
 
-// fpe_scan_ingest* (withClear false: cp and clearInfo unused) and fpe_scan_ingest_clear* (the clear between the move and the fuse)
+// fpe_scan_ingest* (withClear false: cp and clearInfo unused), fpe_scan_ingest_clear* (the clear between the move and the fuse) and
+// fpe_scan_ingest_closed* (withClose: behind the fuse the close of up to three rectangles into `closed`, which the patches then carry
+// in place of the state's own elevation; withClose false: kp and closeInfo unused)
 int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
-                       bool withClear, const fpe_scan* scan, const float* points, const int32_t shift[2], const double position[2],
-                       fpe_scan_clear_info* clearInfo, fpe_scan_info* scanInfo, fpe_elevation_update_info* updateInfo, bool onDevice, hipStream_t stream) {
+                       bool withClear, const fpe_scan_close_params* kp, bool withClose, const fpe_scan* scan, const float* points, const int32_t shift[2],
+                       const double position[2], fpe_scan_clear_info* clearInfo, fpe_scan_info* scanInfo, fpe_scan_close_info* closeInfo,
+                       fpe_elevation_update_info* updateInfo, bool onDevice, hipStream_t stream) {
     if (!h || !s || !points || !shift || !position) return fail(FPE_E_INVALID_ARG, "null argument");
     if (s->h != h) return fail(FPE_E_INVALID_ARG, "the scan state belongs to another engine");
     std::lock_guard<std::mutex> lk(s->mu);
     // every refusal ahead of the first queued operation
     int rc = scan_check(s, sp, cp, withClear, scan);
     if (rc != FPE_OK) return rc;
+    int32_t rects[3][4];
+    int nRects = 0;
+    if (withClose) {
+        if (!kp) return fail(FPE_E_INVALID_ARG, "null close parameters");
+        const int32_t whole[4] = {0, 0, s->g.rows, s->g.cols};
+        rc = scan_close_check(s, kp, whole);  // (the parameters; the rectangles below lie inside by construction)
+        if (rc != FPE_OK) return rc;
+        nRects = scan_close_rects(s, kp, scan, shift, rects);
+        FPE_HIP(hipSetDevice(h->device));
+        rc = scan_close_alloc(s);  // (the patches below point into `closed`)
+        if (rc != FPE_OK) return rc;
+    }
     fpe_map_update u;
     std::memset(&u, 0, sizeof(u));
     u.shift[0] = shift[0];
@@ -4207,9 +4321,14 @@ int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params
     u.position[0] = position[0];
     u.position[1] = position[1];
     u.n_patches = 1;
-    auto patch = [&]() {  // scan->roi of the state's CURRENT elevation layer, row-major with the layer's pitch
+    auto patch = [&]() {  // scan->roi of the state's CURRENT elevation layer, row-major with the layer's pitch; or the closed rectangles
         const float* e = s->elev[s->cur] + static_cast<size_t>(scan->roi[0]) * s->g.cols + scan->roi[1];
         u.patch[0] = fpe_map_patch{scan->roi[0], scan->roi[1], scan->roi[2], scan->roi[3], nullptr, e, s->g.cols, 1};
+        for (int k = 0; k < nRects; ++k) {
+            const int32_t* r = rects[k];
+            u.patch[k] = fpe_map_patch{r[0], r[1], r[2], r[3], nullptr, s->closed + static_cast<size_t>(r[0]) * s->g.cols + r[1], s->g.cols, 1};
+        }
+        if (nRects) u.n_patches = nRects;
     };
     patch();
     {
@@ -4231,12 +4350,14 @@ int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params
     if (rc != FPE_OK) return rc;
     fpe_scan_info* dInfo = scanInfo;
     fpe_scan_clear_info* dClearInfo = clearInfo;
+    fpe_scan_close_info* dCloseInfo = closeInfo;
     if (!onDevice) {
         rc = scan_stage_points(s, scan, points);
         if (rc != FPE_OK) return rc;
         points = s->pts;
         dInfo = reinterpret_cast<fpe_scan_info*>(s->acc + fpe::kScanAccWords);
         dClearInfo = reinterpret_cast<fpe_scan_clear_info*>(s->acc + fpe::kScanAccWords + 16);
+        if (withClose) dCloseInfo = reinterpret_cast<fpe_scan_close_info*>(s->closeAcc + fpe::kCloseAccInfo);
     }
     if (shift[0] != 0 || shift[1] != 0 || position[0] != s->g.posX || position[1] != s->g.posY) {
         rc = scan_move_locked(s, shift, position, op.stream);
@@ -4249,16 +4370,24 @@ int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params
     }
     rc = scan_fuse_locked(s, sp, scan, points, dInfo, op.stream);
     if (rc != FPE_OK) return rc;
+    for (int k = 0; k < nRects; ++k) {  // (close_info describes the first rectangle; the strips write none)
+        const int32_t* r = rects[k];
+        rc = scan_close_locked(s, kp, r, s->closed + static_cast<size_t>(r[0]) * s->g.cols + r[1], s->g.cols, nullptr, k == 0 ? dCloseInfo : nullptr, op.stream);
+        if (rc != FPE_OK) return rc;
+    }
     rc = update_elevation_common(h, fp, &u, updateInfo, true, op.stream);
     if (rc != FPE_OK) return rc;
     if (!onDevice) {
         fpe_scan_info got;
         fpe_scan_clear_info gotClear;
+        fpe_scan_close_info gotClose;
         FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, op.stream));
+        if (withClose) FPE_HIP(hipMemcpyAsync(&gotClose, dCloseInfo, sizeof(gotClose), hipMemcpyDeviceToHost, op.stream));
         if (withClear) FPE_HIP(hipMemcpyAsync(&gotClear, dClearInfo, sizeof(gotClear), hipMemcpyDeviceToHost, op.stream));
         FPE_HIP(hipStreamSynchronize(op.stream));
         if (scanInfo) *scanInfo = got;
         if (withClear && clearInfo) *clearInfo = gotClear;
+        if (withClose && closeInfo) *closeInfo = gotClose;
     }
     return FPE_OK;
 }
@@ -4316,6 +4445,8 @@ int fpe_scan_destroy(fpe_scan_handle s) {
     if (s->rec) (void)hipFree(s->rec);
     if (s->pts) (void)hipFree(s->pts);
     if (s->trav) (void)hipFree(s->trav);
+    if (s->closed) (void)hipFree(s->closed);
+    if (s->closeAcc) (void)hipFree(s->closeAcc);
     if (s->last) (void)hipEventDestroy(s->last);
     if (s->own) (void)hipStreamDestroy(s->own);
     delete s;
@@ -4381,13 +4512,13 @@ int fpe_scan_install(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* f
 
 int fpe_scan_ingest(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan, const float* points,
                     const int32_t shift[2], const double position[2], fpe_scan_info* scan_info, fpe_elevation_update_info* update_info) {
-    return scan_ingest_common(h, s, fp, sp, nullptr, false, scan, points, shift, position, nullptr, scan_info, update_info, false, nullptr);
+    return scan_ingest_common(h, s, fp, sp, nullptr, false, nullptr, false, scan, points, shift, position, nullptr, scan_info, nullptr, update_info, false, nullptr);
 }
 
 int fpe_scan_ingest_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan,
                            const float* d_points, const int32_t shift[2], const double position[2], fpe_scan_info* d_scan_info,
                            fpe_elevation_update_info* update_info, void* stream) {
-    return scan_ingest_common(h, s, fp, sp, nullptr, false, scan, d_points, shift, position, nullptr, d_scan_info, update_info, true,
+    return scan_ingest_common(h, s, fp, sp, nullptr, false, nullptr, false, scan, d_points, shift, position, nullptr, d_scan_info, nullptr, update_info, true,
                               static_cast<hipStream_t>(stream));
 }
 
@@ -4404,14 +4535,67 @@ int fpe_scan_clear_device(fpe_scan_handle s, const fpe_scan_params* sp, const fp
 int fpe_scan_ingest_clear(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
                           const fpe_scan* scan, const float* points, const int32_t shift[2], const double position[2], fpe_scan_clear_info* clear_info,
                           fpe_scan_info* scan_info, fpe_elevation_update_info* update_info) {
-    return scan_ingest_common(h, s, fp, sp, cp, true, scan, points, shift, position, clear_info, scan_info, update_info, false, nullptr);
+    return scan_ingest_common(h, s, fp, sp, cp, true, nullptr, false, scan, points, shift, position, clear_info, scan_info, nullptr, update_info, false, nullptr);
 }
 
 int fpe_scan_ingest_clear_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
                                  const fpe_scan* scan, const float* d_points, const int32_t shift[2], const double position[2],
                                  fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info, fpe_elevation_update_info* update_info, void* stream) {
-    return scan_ingest_common(h, s, fp, sp, cp, true, scan, d_points, shift, position, d_clear_info, d_scan_info, update_info, true,
+    return scan_ingest_common(h, s, fp, sp, cp, true, nullptr, false, scan, d_points, shift, position, d_clear_info, d_scan_info, nullptr, update_info, true,
                               static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_close(fpe_scan_handle s, const fpe_scan_close_params* kp, const int32_t rect[4], float* out, int64_t out_row_stride, uint8_t* cls,
+                   fpe_scan_close_info* info) {
+    return scan_close_common(s, kp, rect, out, out_row_stride, cls, info, false, nullptr);
+}
+
+int fpe_scan_close_device(fpe_scan_handle s, const fpe_scan_close_params* kp, const int32_t rect[4], float* d_out, int64_t out_row_stride, uint8_t* d_cls,
+                          fpe_scan_close_info* d_info, void* stream) {
+    return scan_close_common(s, kp, rect, d_out, out_row_stride, d_cls, d_info, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_install_closed(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_close_params* kp, void* stream) {
+    if (!h || !s) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (s->h != h) return fail(FPE_E_INVALID_ARG, "the scan state belongs to another engine");
+    fpe_filter_params def;
+    if (!fp) {
+        fpe::filter_params_defaults(def);
+        fp = &def;
+    }
+    std::lock_guard<std::mutex> lk(s->mu);
+    const int32_t whole[4] = {0, 0, s->g.rows, s->g.cols};
+    int rc = scan_close_check(s, kp, whole);
+    if (rc != FPE_OK) return rc;
+    FPE_HIP(hipSetDevice(h->device));
+    if (!s->trav) FPE_HIP(hipMalloc(reinterpret_cast<void**>(&s->trav), s->n * sizeof(float) + kLayerPadBytes));
+    rc = scan_close_alloc(s);
+    if (rc != FPE_OK) return rc;
+    ScanOp op{s, static_cast<hipStream_t>(stream)};
+    rc = op.enter();
+    if (rc != FPE_OK) return rc;
+    rc = scan_close_locked(s, kp, whole, s->closed, s->g.cols, nullptr, nullptr, op.stream);
+    if (rc != FPE_OK) return rc;
+    const fpe_map_desc d = scan_desc(s);
+    rc = filters_common(h, &d, fp, s->closed, true, s->trav, nullptr, op.stream);
+    if (rc != FPE_OK) return rc;
+    return upload_common(h, &d, s->trav, s->closed, true, op.stream);
+}
+
+int fpe_scan_ingest_closed(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                           const fpe_scan_close_params* kp, const fpe_scan* scan, const float* points, const int32_t shift[2], const double position[2],
+                           fpe_scan_clear_info* clear_info, fpe_scan_info* scan_info, fpe_scan_close_info* close_info,
+                           fpe_elevation_update_info* update_info) {
+    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, true, scan, points, shift, position, clear_info, scan_info, close_info, update_info, false,
+                              nullptr);
+}
+
+int fpe_scan_ingest_closed_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                                  const fpe_scan_close_params* kp, const fpe_scan* scan, const float* d_points, const int32_t shift[2],
+                                  const double position[2], fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info,
+                                  fpe_scan_close_info* d_close_info, fpe_elevation_update_info* update_info, void* stream) {
+    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, true, scan, d_points, shift, position, d_clear_info, d_scan_info, d_close_info,
+                              update_info, true, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

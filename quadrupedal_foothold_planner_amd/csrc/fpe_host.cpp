@@ -689,6 +689,20 @@ int fpe_scan_clear_validate(const fpe_map_desc* geom, const fpe_scan_params* sp,
     return fpe::check_scan_clear(geom->rows, geom->cols, sp, cp, scan, &why);
 }
 
+int fpe_scan_close_params_defaults(fpe_scan_close_params* out) {
+    if (!out) return FPE_E_INVALID_ARG;
+    fpe::scan_close_params_defaults(*out);
+    return FPE_OK;
+}
+
+int fpe_scan_close_validate(const fpe_map_desc* geom, const fpe_scan_close_params* kp, const int32_t rect[4]) {
+    if (!geom) return FPE_E_INVALID_ARG;
+    const char* why = nullptr;
+    const int rc = fpe::check_map_geometry(geom->rows, geom->cols, geom->resolution, &why);
+    if (rc != FPE_OK) return rc;
+    return fpe::check_scan_close(geom->rows, geom->cols, kp, rect, &why);
+}
+
 }  // extern "C"
 
 namespace fpe {
@@ -817,6 +831,50 @@ void scan_clear_consts(const fpe_scan_params& sp, const fpe_scan_clear_params& c
     a.col0 = f.col0;
     a.nr = f.nr;
     a.nc = f.nc;
+}
+
+void scan_close_params_defaults(fpe_scan_close_params& out) {
+    std::memset(&out, 0, sizeof(out));
+    out.reach = 4;
+    out.max_gap = 5;
+    out.min_axes = 2;
+    out.max_spread = 0.08f;
+}
+
+int check_scan_close(int rows, int cols, const fpe_scan_close_params* kp, const int32_t rect[4], const char** why) {
+    auto bad = [&](const char* msg) {
+        *why = msg;
+        return static_cast<int>(FPE_E_INVALID_ARG);
+    };
+    if (!kp || !rect) return bad("null close parameters or rectangle");
+    if (kp->reach < 1 || kp->reach > kCloseMaxReach) return bad("reach outside 1 .. 8");
+    if (kp->max_gap < 1 || kp->max_gap > 2 * kp->reach - 1) return bad("max_gap outside 1 .. 2 * reach - 1");
+    if (kp->min_axes < 1 || kp->min_axes > 4) return bad("min_axes outside 1 .. 4");
+    if (!(kp->max_spread >= 0.0f)) return bad("max_spread negative or NaN");
+    for (int k = 0; k < 4; ++k)
+        if (kp->reserved[k] != 0) return bad("reserved must be 0");
+    if (rect[2] < 1 || rect[3] < 1) return bad("empty rectangle");
+    if (rect[0] < 0 || rect[1] < 0 || rect[0] > rows - rect[2] || rect[1] > cols - rect[3]) return bad("the rectangle reaches outside the state");
+    return FPE_OK;
+}
+
+void scan_close_consts(const fpe_scan_close_params& kp, const int32_t rect[4], int rows, int cols, ScanCloseArgs& a) {
+    a.rows = rows;
+    a.cols = cols;
+    a.row0 = rect[0];
+    a.col0 = rect[1];
+    a.nr = rect[2];
+    a.nc = rect[3];
+    a.reach = kp.reach;
+    a.maxGap = kp.max_gap;
+    a.minAxes = kp.min_axes;
+    a.maxSpread = kp.max_spread;
+    a.outStride = rect[3];
+    a.elev = nullptr;
+    a.out = nullptr;
+    a.cls = nullptr;
+    a.acc = nullptr;
+    a.info = nullptr;
 }
 
 int check_map_update(int rows, int cols, const fpe_map_update* u, bool elevationOnly, const char** why) {

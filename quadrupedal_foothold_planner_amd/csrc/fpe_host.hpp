@@ -54,6 +54,9 @@ void scan_params_defaults(fpe_scan_params& out);
 // The refusals of fpe_scan_clear*: check_scan's, then the clear parameters'.
 int check_scan_clear(int rows, int cols, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const char** why);
 void scan_clear_params_defaults(fpe_scan_clear_params& out);
+// The refusals of fpe_scan_close* for a state of rows x cols cells: the parameters' ranges, then the rectangle.
+int check_scan_close(int rows, int cols, const fpe_scan_close_params* kp, const int32_t rect[4], const char** why);
+void scan_close_params_defaults(fpe_scan_close_params& out);
 
 // ---- the producer's filter chain (fpe_filters.hpp): its host arithmetic — filter_route and friends are declared in fpe_launch.hpp ----
 void filter_params_defaults(fpe_filter_params& out);

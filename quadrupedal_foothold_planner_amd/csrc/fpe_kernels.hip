@@ -2299,6 +2299,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_scan.hpp"
 // ---- part seventeen: scan visibility clearing (fpe_scan_clear*; uses part sixteen's constants, counters and ticket) ---------
 #include "fpe_scan_clear.hpp"
+// ---- part eighteen: scan gap closing (fpe_scan_close*; a pure function of a state's elevation layer) --------------------------
+#include "fpe_scan_close.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)

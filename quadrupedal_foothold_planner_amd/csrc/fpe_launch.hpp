@@ -553,4 +553,32 @@ hipError_t launch_scan_clear(const ScanClearArgs& a, int form, int group, hipStr
 hipError_t launch_scan_clear_rays(const ScanClearArgs& a, int form, int group, hipStream_t stream);
 hipError_t launch_scan_clear_cells(const ScanClearArgs& a, hipStream_t stream);
 
+// ---- scan gap closing (fpe_scan_close.hpp) ---------------------------------------------------------------------
+// The close has an accumulator block of its own (allocated with the state's `closed` layer, reset there): words 0-4 count the known,
+// filled, no_support, rejected_axes and rejected_spread cells (at rest 0), words 8-11 are the filled cells' bounding box (at rest
+// INT32_MAX, INT32_MAX, -1, -1), word 16 is the ticket (at rest 0); words 32-47 are the host forms' device info.
+constexpr int kCloseAccWords = 48;
+constexpr int kCloseAccBox = 8;
+constexpr int kCloseTicket = 16;
+constexpr int kCloseAccInfo = 32;
+constexpr int kCloseMaxReach = 8;
+// The argument block of the one launch, by value.
+struct ScanCloseArgs {
+    int32_t rows, cols;          // the state's size
+    int32_t row0, col0, nr, nc;  // the rectangle
+    int32_t reach, maxGap, minAxes;
+    float maxSpread;
+    int64_t outStride;     // floats (and bytes of cls) per output row
+    const uint32_t* elev;  // the state's elevation, as 32-bit patterns: read only
+    uint32_t* out;         // rectangle-local
+    uint8_t* cls;          // rectangle-local, or null
+    int32_t* acc;          // [kCloseAccWords]
+    int32_t* info;         // the caller's fpe_scan_close_info (device) as sixteen words, or null
+};
+void scan_close_consts(const fpe_scan_close_params& kp, const int32_t rect[4], int rows, int cols, ScanCloseArgs& a);  // fpe_host.cpp
+// One launch on `stream`.  form 1: direct, one lane per cell; 2: tiled, a 16 x 64 tile and its halo in LDS per workgroup.
+hipError_t launch_scan_close(const ScanCloseArgs& a, int form, hipStream_t stream);
+// the accumulator block to its rest values (when it is allocated)
+hipError_t launch_scan_close_reset(int32_t* acc, hipStream_t stream);
+
 }  // namespace fpe

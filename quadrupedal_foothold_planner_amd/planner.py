@@ -344,6 +344,31 @@ def scan_clear_validate(rows, cols, resolution, params, clear_params, scan):
     return _capi.lib().fpe_scan_clear_validate(C.byref(d), ref(params), ref(clear_params), ref(scan))
 
 
+def scan_close_params(**overrides):
+    """fpe_scan_close_params_defaults, with any field replaced by a keyword (reserved: a sequence of four)."""
+    kp = _capi.ScanCloseParams()
+    assert _capi.lib().fpe_scan_close_params_defaults(C.byref(kp)) == _capi.FPE_OK
+    for k, v in overrides.items():
+        if k not in dict(_capi.ScanCloseParams._fields_):
+            raise ValueError(f"unknown scan close parameter {k!r}")
+        if k == "reserved":
+            kp.reserved[:] = [int(x) for x in v]
+        else:
+            setattr(kp, k, v)
+    return kp
+
+
+def _rect(rect):
+    return None if rect is None else (C.c_int32 * 4)(*(int(x) for x in rect))
+
+
+def scan_close_validate(rows, cols, resolution, close_params, rect):
+    """fpe_scan_close_validate (host arithmetic, no engine): the status a close of `rect` = (row0, col0, n_rows, n_cols) of a
+    rows x cols state would be refused with, or FPE_OK.  `close_params` / `rect` may be None (a null argument)."""
+    d = _map_desc(rows, cols, resolution)
+    return _capi.lib().fpe_scan_close_validate(C.byref(d), C.byref(close_params) if close_params is not None else None, _rect(rect))
+
+
 class _Handle:
     """What an engine and a group of engines share: the handle's creation, close / __del__, and the status check.  A subclass names
     its three entry points."""
@@ -522,7 +547,7 @@ class FootholdPlanner(_Handle):
         return buf.value.decode()
 
     def set_tuning(self, **kw):
-        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, beam_check_waves, scan_merge, scan_clear_form, scan_clear_group, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
+        """fpe_set_tuning: plan_group, literal_discs, no_mid_variant, no_bits, beam_check_waves, scan_merge, scan_clear_form, scan_clear_group, scan_close_form, service_opt_gate, service_overlap, service_poll (build-defined test / tuning knobs)."""
         for k, v in kw.items():
             self._check(self._lib.fpe_set_tuning(self._h, k.encode(), int(v)))
             self._tuning[k] = int(v)
@@ -1461,6 +1486,64 @@ class ScanState:
                                                            C.byref(clear_params if clear_params is not None else scan_clear_params()), C.byref(scan),
                                                            C.c_void_p(d_points_ptr), sh, pos, C.c_void_p(d_clear_info_ptr or 0),
                                                            C.c_void_p(d_info_ptr or 0), C.byref(ui), C.c_void_p(stream or 0)))
+        return _info_dict(ui)
+
+    # ---- gap closing: small holes of the elevation bridged for the planner (fpe_scan_close*) ---------------------------
+    # (`close()` is the state's destructor, so the binding of fpe_scan_close is called close_gaps)
+    def close_gaps(self, rect=None, close_params=None, classes=True, row_stride=None):
+        """fpe_scan_close: the closed elevation of `rect` = (row0, col0, n_rows, n_cols) (None: the whole state) -> ((n_rows,
+        n_cols) float32 array, uint8 class array or None, SCAN_CLOSE_INFO_DTYPE record).  The state is not written.  Synchronous.
+        row_stride: the pitch of the buffers the call writes (the arrays returned are views of their first n_cols columns)."""
+        r = (0, 0, self.rows, self.cols) if rect is None else tuple(int(x) for x in rect)
+        pitch = int(row_stride) if row_stride is not None else max(r[3], 1)
+        out = np.zeros((max(r[2], 1), max(pitch, 1)), np.float32)
+        cls = np.zeros(out.shape, np.uint8) if classes else None
+        info = np.zeros(1, _capi.SCAN_CLOSE_INFO_DTYPE)
+        self._check(self._lib.fpe_scan_close(self._s, C.byref(close_params if close_params is not None else scan_close_params()), _rect(r), ptr(out),
+                                             pitch, ptr(cls), ptr(info)))
+        return out[:r[2], :r[3]], (cls[:r[2], :r[3]] if classes else None), info[0]
+
+    def close_gaps_device(self, rect, d_out_ptr, row_stride, close_params=None, d_cls_ptr=0, d_info_ptr=0, stream=None):
+        """fpe_scan_close_device: device buffers with a pitch of `row_stride` elements, a device info of 64 bytes (0: not wanted);
+        asynchronous on `stream`."""
+        self._check(self._lib.fpe_scan_close_device(self._s, C.byref(close_params if close_params is not None else scan_close_params()), _rect(rect),
+                                                    C.c_void_p(d_out_ptr), int(row_stride), C.c_void_p(d_cls_ptr or 0), C.c_void_p(d_info_ptr or 0),
+                                                    C.c_void_p(stream or 0)))
+
+    def install_closed(self, close_params=None, filter_params=None, stream=None):
+        """fpe_scan_install_closed: install with the closed whole-map layer in place of the state's elevation; asynchronous."""
+        pl = self._planner
+        self._check(self._lib.fpe_scan_install_closed(pl._h, self._s, C.byref(filter_params) if filter_params is not None else None,
+                                                      C.byref(close_params if close_params is not None else scan_close_params()), C.c_void_p(stream or 0)))
+        pl.rows, pl.cols, pl.resolution = self.rows, self.cols, self.resolution
+
+    def ingest_closed(self, scan, points, shift, position, params=None, clear_params=None, close_params=None, filter_params=None):
+        """fpe_scan_ingest_closed: move, the clear (when clear_params is given), fuse, the close of the touched rectangles, and those
+        into the snapshot -> (clear info record or None, scan info record, close info record, update info dict).  Synchronous."""
+        p = self._points(points, scan)
+        sh, pos = self._move_args(shift, position)
+        cinfo, info, kinfo = np.zeros(1, _capi.SCAN_CLEAR_INFO_DTYPE), np.zeros(1, _capi.SCAN_INFO_DTYPE), np.zeros(1, _capi.SCAN_CLOSE_INFO_DTYPE)
+        ui = _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_scan_ingest_closed(self._planner._h, self._s, C.byref(filter_params) if filter_params is not None else None,
+                                                     C.byref(params if params is not None else scan_params()),
+                                                     C.byref(clear_params) if clear_params is not None else None,
+                                                     C.byref(close_params if close_params is not None else scan_close_params()), C.byref(scan), ptr(p),
+                                                     sh, pos, ptr(cinfo), ptr(info), ptr(kinfo), C.byref(ui)))
+        return (cinfo[0] if clear_params is not None else None), info[0], kinfo[0], _info_dict(ui)
+
+    def ingest_closed_device(self, scan, d_points_ptr, shift, position, params=None, clear_params=None, close_params=None, filter_params=None,
+                             d_clear_info_ptr=0, d_info_ptr=0, d_close_info_ptr=0, stream=None):
+        """fpe_scan_ingest_closed_device: the same with device points and device infos (0: not wanted), asynchronous on `stream` ->
+        the update info dict."""
+        sh, pos = self._move_args(shift, position)
+        ui = _capi.ElevationUpdateInfo()
+        self._check(self._lib.fpe_scan_ingest_closed_device(self._planner._h, self._s, C.byref(filter_params) if filter_params is not None else None,
+                                                            C.byref(params if params is not None else scan_params()),
+                                                            C.byref(clear_params) if clear_params is not None else None,
+                                                            C.byref(close_params if close_params is not None else scan_close_params()), C.byref(scan),
+                                                            C.c_void_p(d_points_ptr), sh, pos, C.c_void_p(d_clear_info_ptr or 0),
+                                                            C.c_void_p(d_info_ptr or 0), C.c_void_p(d_close_info_ptr or 0), C.byref(ui),
+                                                            C.c_void_p(stream or 0)))
         return _info_dict(ui)
 
 
