@@ -1754,6 +1754,77 @@ extern int fpe_scan_ingest_closed_device(fpe_handle h, fpe_scan_handle s, const 
                                          fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info,
                                          fpe_scan_close_info* d_close_info, fpe_elevation_update_info* update_info, void* stream);
 
+/* 6. Scan images (the *_image entry points): a depth camera's or a spinning lidar's image fused and cleared WITHOUT a point cloud.
+ *    BUILD-DEFINED like points 2 - 5; the numpy statement is tests/scan_image_reference.py.  THE EQUIVALENCE: every image form writes,
+ *    byte for byte, what its point form writes when given the points P of the image — a tight array of n_sel points, scan->n_points
+ *    = n_sel, a stride of 3: both layers of the state, every word of every info record, the planner's snapshot.  The points are never
+ *    materialised: no kernel of the image forms writes an x, y, z triple to memory, and a state allocates nothing per point beyond
+ *    the 8-byte records it already has.
+ *    SELECTED PIXELS: rows v = ri * row_step for ri = 0 .. nr - 1, nr = ceil(height / row_step); columns u = ci * col_step for
+ *    ci = 0 .. nc - 1, nc = ceil(width / col_step); n_sel = nr * nc; the point ordinal is i = ri * nc + ci (the clear's ray_stride
+ *    selects on i, as in point 4).
+ *    THE POINT OF A PIXEL: all arithmetic is f32, every operation rounded on its own, no contraction, IEEE division (no reciprocal is
+ *    multiplied in).  raw is the element at v * row_pitch + u.  U16: invalid iff raw == 0, d = float(raw) * depth_scale.  F32: invalid
+ *    unless raw is finite and > 0, d = raw * depth_scale.  An invalid pixel is the point (NaN, NaN, NaN), which the fuse's test 1
+ *    counts under dropped_nonfinite (fpe_scan_info keeps its sixteen words); a d that overflows meets the same test.
+ *      pinhole:    x = ((float(u) - cx) * d) / fx;   y = ((float(v) - cy) * d) / fy;   z = d
+ *      spherical:  (ce, se) = row_dir[2v], row_dir[2v + 1];  (ca, sa) = col_dir[2u], col_dir[2u + 1];
+ *                  w = d * ce;   x = w * ca;   y = w * sa;   z = d * se
+ *    The tables are data: the caller takes the cosines, the contract has no trigonometry.  scan->sensor_to_map maps that frame to the
+ *    map.  Non-finite table entries are not refused (a device form cannot see them): their points are dropped_nonfinite.
+ *    REFUSALS (FPE_E_INVALID_ARG; nothing written, nothing queued, nothing installed): everything the point form refuses for sp, cp,
+ *    kp, scan, shift and position; a null im or image; a model or a format outside its two values; a width or height outside
+ *    1 .. 4096; row_pitch < width; a step below 1; a depth_scale that is not finite or not > 0; pinhole: fx or fy not finite or 0, cx
+ *    or cy not finite; spherical: a null table; a reserved word that is not 0; n_sel > FPE_SCAN_MAX_POINTS; scan->n_points != n_sel.
+ *    scan->point_stride must pass the old check (>= 3) and is otherwise not read.  fpe_scan_image_validate is that routine without
+ *    an engine (cp may be NULL: the fuse's refusals alone).
+ *    FORMS, ordering, asynchrony and grow-on-demand allocation are the point forms'.  Host forms take a host image and host tables
+ *    and stage them at their own size (2 or 4 bytes per pixel, plus the two tables); device forms take a device image, and row_dir /
+ *    col_dir are device addresses.  fpe_scan_image_points (host only) writes the n_sel x 3 floats of the rule: the CPU-checkable
+ *    statement of it.
+ *     - fpe_scan_ingest_image[_device] is ONE routine for the three ingests: cp == NULL and kp == NULL: fpe_scan_ingest; cp given,
+ *       kp == NULL: fpe_scan_ingest_clear; kp given (cp given or NULL): fpe_scan_ingest_closed, with its PROMISED statement and its
+ *       voiding rule.  The order of operations and the patches are the existing ones.
+ *    Kernels (csrc/fpe_scan_image.hpp): the top pass has one form, the merged one, and sums its five class counts per workgroup in
+ *    LDS; the ray pass keeps both forms and "scan_clear_form" / "scan_clear_group" their meaning; "scan_merge" does not apply. */
+#define FPE_SCAN_IMAGE_PINHOLE   0   /* optical frame: x right, y down, z forward */
+#define FPE_SCAN_IMAGE_SPHERICAL 1   /* separable direction tables: a spinning lidar's range image */
+#define FPE_SCAN_DEPTH_U16 0         /* uint16; 0 = no return */
+#define FPE_SCAN_DEPTH_F32 1         /* float; valid iff finite and > 0 */
+typedef struct fpe_scan_image {       /* 72 bytes */
+    int32_t model, format;
+    int32_t width, height;        /* pixels; 1 .. 4096 each */
+    int32_t row_pitch;            /* ELEMENTS between rows; >= width (a crop is a pointer offset plus this) */
+    int32_t row_step, col_step;   /* every row_step-th row and col_step-th column is a point; >= 1 */
+    float   depth_scale;          /* metres per unit; finite, > 0 */
+    float   fx, fy, cx, cy;       /* pinhole; fx, fy finite and not 0; cx, cy finite */
+    int32_t reserved[2];          /* 0 */
+    const float* row_dir;         /* spherical: height x {cos e, sin e}; host pointer in host forms, device pointer in device forms */
+    const float* col_dir;         /* spherical: width  x {cos a, sin a} */
+} fpe_scan_image;
+extern int fpe_scan_image_validate(const fpe_map_desc* geom, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                                   const fpe_scan* scan, const fpe_scan_image* im);                 /* host arithmetic only; no engine */
+extern int fpe_scan_image_points(const fpe_scan_image* im, const void* image, float* out_xyz);     /* host only */
+extern int fpe_scan_fuse_image(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const fpe_scan_image* im,
+                               const void* image, fpe_scan_info* info);
+extern int fpe_scan_fuse_image_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const fpe_scan_image* im,
+                                      const void* d_image, fpe_scan_info* d_info, void* stream);
+extern int fpe_scan_clear_image(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan,
+                                const fpe_scan_image* im, const void* image, fpe_scan_clear_info* info);
+extern int fpe_scan_clear_image_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                                       const fpe_scan* scan, const fpe_scan_image* im, const void* d_image,
+                                       fpe_scan_clear_info* d_info, void* stream);
+extern int fpe_scan_ingest_image(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp,
+                                 const fpe_scan_clear_params* cp, const fpe_scan_close_params* kp, const fpe_scan* scan,
+                                 const fpe_scan_image* im, const void* image, const int32_t shift[2], const double position[2],
+                                 fpe_scan_clear_info* clear_info, fpe_scan_info* scan_info, fpe_scan_close_info* close_info,
+                                 fpe_elevation_update_info* update_info);
+extern int fpe_scan_ingest_image_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp,
+                                        const fpe_scan_clear_params* cp, const fpe_scan_close_params* kp, const fpe_scan* scan,
+                                        const fpe_scan_image* im, const void* d_image, const int32_t shift[2],
+                                        const double position[2], fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info,
+                                        fpe_scan_close_info* d_close_info, fpe_elevation_update_info* update_info, void* stream);
+
 /* ---- host-side helpers (no GPU needed) -------------------------------------------------------- */
 /* SpiralIterator visiting order as index offsets (di,dj) for rings 0..n_rings (generateRing walk,
  * consumed from the back).  Writes min(count, max_cells) entries of (di, dj, ring); returns count. */

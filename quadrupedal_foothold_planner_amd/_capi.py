@@ -462,6 +462,20 @@ SCAN_CLOSE_INFO_DTYPE = np.dtype(
 )
 assert (C.sizeof(ScanCloseParams), SCAN_CLOSE_INFO_DTYPE.itemsize) == (32, 64)
 
+SCAN_IMAGE_PINHOLE, SCAN_IMAGE_SPHERICAL = 0, 1  # FPE_SCAN_IMAGE_*
+SCAN_DEPTH_U16, SCAN_DEPTH_F32 = 0, 1            # FPE_SCAN_DEPTH_*
+
+
+class ScanImage(C.Structure):
+    """fpe_scan_image: how the pixels of a depth or range image become points (model, format, size, pitch, steps, scale, the pinhole
+    intrinsics or the two direction tables)."""
+    _fields_ = [("model", C.c_int32), ("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("row_pitch", C.c_int32),
+                ("row_step", C.c_int32), ("col_step", C.c_int32), ("depth_scale", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("reserved", C.c_int32 * 2), ("row_dir", C.c_void_p), ("col_dir", C.c_void_p)]
+
+
+assert C.sizeof(ScanImage) == 72
+
 ABI_VERSION = 5  # FPE_ABI_VERSION of include/fpe.h: the layout the mirrors above have
 # every struct of include/fpe.h -> its mirror (tests/test_cpu_abi.py checks each against the C compiler, and the key set against the header)
 STRUCTS = {
@@ -484,7 +498,7 @@ STRUCTS = {
     "fpe_check_params": CheckParams, "fpe_check_out": CheckOut, "fpe_beam_check_out": BeamCheckOut,
     "fpe_scan_params": ScanParams, "fpe_scan": Scan, "fpe_scan_info": SCAN_INFO_DTYPE,
     "fpe_scan_clear_params": ScanClearParams, "fpe_scan_clear_info": SCAN_CLEAR_INFO_DTYPE,
-    "fpe_scan_close_params": ScanCloseParams, "fpe_scan_close_info": SCAN_CLOSE_INFO_DTYPE,
+    "fpe_scan_close_params": ScanCloseParams, "fpe_scan_close_info": SCAN_CLOSE_INFO_DTYPE, "fpe_scan_image": ScanImage,
 }
 FILTER_LAYERS = ("normal_x", "normal_y", "normal_z", "slope", "step_height", "step", "roughness", "traversability")
 
@@ -628,6 +642,16 @@ PROTOTYPES = {
                                       vp, vp, vp, P(ElevationUpdateInfo)]),
     "fpe_scan_ingest_closed_device": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(ScanCloseParams), P(Scan), vp, P(i32),
                                              P(f64), vp, vp, vp, P(ElevationUpdateInfo), vp]),
+    "fpe_scan_image_validate": (cint, [P(MapDesc), P(ScanParams), P(ScanClearParams), P(Scan), P(ScanImage)]),
+    "fpe_scan_image_points": (cint, [P(ScanImage), vp, vp]),
+    "fpe_scan_fuse_image": (cint, [vp, P(ScanParams), P(Scan), P(ScanImage), vp, vp]),
+    "fpe_scan_fuse_image_device": (cint, [vp, P(ScanParams), P(Scan), P(ScanImage), vp, vp, vp]),
+    "fpe_scan_clear_image": (cint, [vp, P(ScanParams), P(ScanClearParams), P(Scan), P(ScanImage), vp, vp]),
+    "fpe_scan_clear_image_device": (cint, [vp, P(ScanParams), P(ScanClearParams), P(Scan), P(ScanImage), vp, vp, vp]),
+    "fpe_scan_ingest_image": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(ScanCloseParams), P(Scan), P(ScanImage), vp,
+                                     P(i32), P(f64), vp, vp, vp, P(ElevationUpdateInfo)]),
+    "fpe_scan_ingest_image_device": (cint, [vp, vp, P(FilterParams), P(ScanParams), P(ScanClearParams), P(ScanCloseParams), P(Scan), P(ScanImage),
+                                            vp, P(i32), P(f64), vp, vp, vp, P(ElevationUpdateInfo), vp]),
     "fpe_spiral_offsets": (cint, [i32, vp, i32]),
     "fpe_tile_halfwidth": (cint, [f32, f32, f64]),
     "fpe_algorithmic_bytes_per_foothold": (f64, [f32, f32, f64]),

@@ -19,7 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libfpe.so")
 LOCK_PATH = os.path.join(_HERE, ".libfpe.lock")
 SOURCES = ["fpe_kernels.hip", "fpe_engine.cpp", "fpe_host.cpp", "fpe_multi.cpp"]
-HEADERS = ["fpe_gridmath.hpp", "fpe_device.hpp", "fpe_launch.hpp", "fpe_host.hpp", "fpe_bits.hpp", "fpe_bits_window.hpp", "fpe_bits_lane8.hpp", "fpe_bits_seq.hpp", "fpe_plan_launch.hpp", "fpe_filters.hpp", "fpe_filters_fused.hpp", "fpe_opt.hpp", "fpe_footmap.hpp", "fpe_footsnap.hpp", "fpe_centroidmap.hpp", "fpe_rank.hpp", "fpe_layers.hpp", "fpe_beam.hpp", "fpe_mapupdate.hpp", "fpe_swing.hpp", "fpe_trunk.hpp", "fpe_margin.hpp", "fpe_check.hpp", "fpe_beam_check.hpp", "fpe_scan.hpp", "fpe_scan_clear.hpp", "fpe_scan_close.hpp", os.path.join("..", "..", "include", "fpe.h")]
+HEADERS = ["fpe_gridmath.hpp", "fpe_device.hpp", "fpe_launch.hpp", "fpe_host.hpp", "fpe_bits.hpp", "fpe_bits_window.hpp", "fpe_bits_lane8.hpp", "fpe_bits_seq.hpp", "fpe_plan_launch.hpp", "fpe_filters.hpp", "fpe_filters_fused.hpp", "fpe_opt.hpp", "fpe_footmap.hpp", "fpe_footsnap.hpp", "fpe_centroidmap.hpp", "fpe_rank.hpp", "fpe_layers.hpp", "fpe_beam.hpp", "fpe_mapupdate.hpp", "fpe_swing.hpp", "fpe_trunk.hpp", "fpe_margin.hpp", "fpe_check.hpp", "fpe_beam_check.hpp", "fpe_scan.hpp", "fpe_scan_clear.hpp", "fpe_scan_close.hpp", "fpe_scan_image.hpp", os.path.join("..", "..", "include", "fpe.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "--offload-arch=gfx950",

@@ -3989,7 +3989,7 @@ struct fpe_scan_state {
     int32_t* acc = nullptr;  // kScanAccWords accumulators, then twice sixteen words: the host forms' device infos (the fuse's, the clear's)
     uint2* rec = nullptr;
     size_t recCap = 0;       // records
-    float* pts = nullptr;
+    float* pts = nullptr;    // the host forms' staging: points, or an image at its own size and its two tables (scan_stage)
     size_t ptsCap = 0;       // floats
     float* trav = nullptr;   // fpe_scan_install's traversability layer (allocated by the first install)
     float* closed = nullptr;     // the closed elevation the planner gets (fpe_scan_install_closed, fpe_scan_ingest_closed) and the host close's
@@ -4091,8 +4091,37 @@ int scan_move_locked(fpe_scan_state* s, const int32_t shift[2], const double pos
     return FPE_OK;
 }
 
+// The point source of a fuse, a clear or an ingest: points with the scan's stride, or an image (its descriptor and its elements;
+// point 6 of the scan block).  As the entry points take it the addresses are the caller's (host or device); scan_stage gives the
+// device form of a host source; the *_locked routines take device addresses only.
+struct ScanSource {
+    bool isImage = false;
+    const float* points = nullptr;
+    const fpe_scan_image* im = nullptr;
+    const void* image = nullptr;
+    const float* rowDir = nullptr;  // the tables' addresses as the kernels read them (device forms: the descriptor's)
+    const float* colDir = nullptr;
+    static ScanSource of_points(const float* points) {
+        ScanSource r;
+        r.points = points;
+        return r;
+    }
+    static ScanSource of_image(const fpe_scan_image* im, const void* image) {
+        ScanSource r;
+        r.isImage = true;
+        r.im = im;
+        r.image = image;
+        if (im) {
+            r.rowDir = im->row_dir;
+            r.colDir = im->col_dir;
+        }
+        return r;
+    }
+    bool given() const { return isImage ? (im != nullptr && image != nullptr) : points != nullptr; }
+};
+
 // The three passes on `stream` (the caller holds s->mu, has validated the call and has entered `stream`).
-int scan_fuse_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan, const float* d_points, fpe_scan_info* d_info, hipStream_t stream) {
+int scan_fuse_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan, const ScanSource& src, fpe_scan_info* d_info, hipStream_t stream) {
     int rc = scan_grow(s->rec, s->recCap, static_cast<size_t>(scan->n_points));
     if (rc != FPE_OK) return rc;
     int merge;
@@ -4103,19 +4132,24 @@ int scan_fuse_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sca
     if (merge == 0) merge = kScanMergeDefault;
     fpe::ScanArgs a;
     fpe::scan_consts(*sp, *scan, s->g, a);
-    a.points = d_points;
+    a.points = src.points;
     a.rec = s->rec;
     a.cells = s->cells;
     a.acc = s->acc;
     a.elev = reinterpret_cast<uint32_t*>(s->elev[s->cur]);
     a.var = reinterpret_cast<uint32_t*>(s->var[s->cur]);
     a.info = reinterpret_cast<int32_t*>(d_info);
-    FPE_HIP(fpe::launch_scan_fuse(a, merge == 2, stream));
+    if (src.isImage) {  // (one form of the top pass: "scan_merge" does not apply)
+        fpe::scan_image_consts(*src.im, src.image, src.rowDir, src.colDir, a.im);
+        FPE_HIP(fpe::launch_scan_fuse_image(a, stream));
+    } else {
+        FPE_HIP(fpe::launch_scan_fuse(a, merge == 2, stream));
+    }
     return FPE_OK;
 }
 
 // The two passes of a clear on `stream` (the caller holds s->mu, has validated the call and has entered `stream`).
-int scan_clear_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* d_points,
+int scan_clear_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const ScanSource& src,
                       fpe_scan_clear_info* d_info, hipStream_t stream) {
     int form, group;
     {
@@ -4127,13 +4161,18 @@ int scan_clear_locked(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sc
     if (group == 0) group = kScanClearGroupDefault;
     fpe::ScanClearArgs a;
     fpe::scan_clear_consts(*sp, *cp, *scan, s->g, a);
-    a.points = d_points;
+    a.points = src.points;
     a.cells = s->cells;
     a.acc = s->acc;
     a.elev = reinterpret_cast<uint32_t*>(s->elev[s->cur]);
     a.var = reinterpret_cast<uint32_t*>(s->var[s->cur]);
     a.info = reinterpret_cast<int32_t*>(d_info);
-    FPE_HIP(fpe::launch_scan_clear(a, form, group, stream));
+    if (src.isImage) {
+        fpe::scan_image_consts(*src.im, src.image, src.rowDir, src.colDir, a.im);
+        FPE_HIP(fpe::launch_scan_clear_image(a, form, group, stream));
+    } else {
+        FPE_HIP(fpe::launch_scan_clear(a, form, group, stream));
+    }
     return FPE_OK;
 }
 
@@ -4228,37 +4267,62 @@ int scan_close_common(fpe_scan_state* s, const fpe_scan_close_params* kp, const 
     return FPE_OK;
 }
 
-// (cp == nullptr with withClear == false: the fuse's refusals alone)
-int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, bool withClear, const fpe_scan* scan) {
+// (cp == nullptr with withClear == false: the fuse's refusals alone; an image source: then the descriptor's and n_points against it)
+int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, bool withClear, const fpe_scan* scan,
+               const ScanSource& src) {
     const char* why = "";
-    const int rc = withClear ? fpe::check_scan_clear(s->g.rows, s->g.cols, sp, cp, scan, &why) : fpe::check_scan(s->g.rows, s->g.cols, sp, scan, &why);
+    int rc = withClear ? fpe::check_scan_clear(s->g.rows, s->g.cols, sp, cp, scan, &why) : fpe::check_scan(s->g.rows, s->g.cols, sp, scan, &why);
+    if (rc == FPE_OK && src.isImage) rc = fpe::check_scan_image(s->g.rows, s->g.cols, sp, nullptr, scan, src.im, &why);
     return rc == FPE_OK ? rc : fail(rc, why);
 }
-int scan_check(const fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan) { return scan_check(s, sp, nullptr, false, scan); }
 
-// Host points into the state's staging buffer on its own stream (entered)
-int scan_stage_points(fpe_scan_state* s, const fpe_scan* scan, const float* points) {
-    const size_t nf = static_cast<size_t>(scan->n_points) * static_cast<size_t>(scan->point_stride);
-    const int rc = scan_grow(s->pts, s->ptsCap, std::max<size_t>(nf, 3));
+// A host source into the state's staging buffer on its own stream (entered); `dev` is its device form.  Points: n_points *
+// point_stride floats.  An image at its own size: the elements up to the last pixel of the last row, then (spherical) the two tables.
+int scan_stage(fpe_scan_state* s, const fpe_scan* scan, const ScanSource& src, ScanSource& dev) {
+    dev = src;
+    if (!src.isImage) {
+        const size_t nf = static_cast<size_t>(scan->n_points) * static_cast<size_t>(scan->point_stride);
+        const int rc = scan_grow(s->pts, s->ptsCap, std::max<size_t>(nf, 3));
+        if (rc != FPE_OK) return rc;
+        if (nf) FPE_HIP(hipMemcpyAsync(s->pts, src.points, nf * sizeof(float), hipMemcpyHostToDevice, s->own));
+        dev.points = s->pts;
+        return FPE_OK;
+    }
+    const fpe_scan_image& im = *src.im;
+    const size_t elems = static_cast<size_t>(im.height - 1) * static_cast<size_t>(im.row_pitch) + static_cast<size_t>(im.width);
+    const size_t bytes = elems * (im.format == FPE_SCAN_DEPTH_U16 ? 2 : 4);
+    const size_t imageFloats = (bytes + 3) / 4;
+    const bool tables = im.model == FPE_SCAN_IMAGE_SPHERICAL;
+    const size_t rowFloats = tables ? 2 * static_cast<size_t>(im.height) : 0, colFloats = tables ? 2 * static_cast<size_t>(im.width) : 0;
+    const int rc = scan_grow(s->pts, s->ptsCap, imageFloats + rowFloats + colFloats);
     if (rc != FPE_OK) return rc;
-    if (nf) FPE_HIP(hipMemcpyAsync(s->pts, points, nf * sizeof(float), hipMemcpyHostToDevice, s->own));
+    FPE_HIP(hipMemcpyAsync(s->pts, src.image, bytes, hipMemcpyHostToDevice, s->own));
+    dev.image = s->pts;
+    dev.rowDir = dev.colDir = nullptr;
+    if (tables) {
+        FPE_HIP(hipMemcpyAsync(s->pts + imageFloats, im.row_dir, rowFloats * sizeof(float), hipMemcpyHostToDevice, s->own));
+        FPE_HIP(hipMemcpyAsync(s->pts + imageFloats + rowFloats, im.col_dir, colFloats * sizeof(float), hipMemcpyHostToDevice, s->own));
+        dev.rowDir = s->pts + imageFloats;
+        dev.colDir = s->pts + imageFloats + rowFloats;
+    }
     return FPE_OK;
 }
 
-int scan_fuse_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan, const float* points, fpe_scan_info* info, bool onDevice,
+int scan_fuse_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan* scan, const ScanSource& src, fpe_scan_info* info, bool onDevice,
                      hipStream_t stream) {
-    if (!s || !points) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!s || !src.given()) return fail(FPE_E_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(s->mu);
-    int rc = scan_check(s, sp, scan);
+    int rc = scan_check(s, sp, nullptr, false, scan, src);
     if (rc != FPE_OK) return rc;
     ScanOp op{s, onDevice ? stream : s->own};
     rc = op.enter();
     if (rc != FPE_OK) return rc;
-    if (onDevice) return scan_fuse_locked(s, sp, scan, points, info, stream);
-    rc = scan_stage_points(s, scan, points);
+    if (onDevice) return scan_fuse_locked(s, sp, scan, src, info, stream);
+    ScanSource dev;
+    rc = scan_stage(s, scan, src, dev);
     if (rc != FPE_OK) return rc;
     fpe_scan_info* dInfo = reinterpret_cast<fpe_scan_info*>(s->acc + fpe::kScanAccWords);
-    rc = scan_fuse_locked(s, sp, scan, s->pts, dInfo, s->own);
+    rc = scan_fuse_locked(s, sp, scan, dev, dInfo, s->own);
     if (rc != FPE_OK) return rc;
     fpe_scan_info got;
     FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, s->own));
@@ -4267,20 +4331,21 @@ int scan_fuse_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sca
     return FPE_OK;
 }
 
-int scan_clear_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* points,
+int scan_clear_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const ScanSource& src,
                       fpe_scan_clear_info* info, bool onDevice, hipStream_t stream) {
-    if (!s || !points) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!s || !src.given()) return fail(FPE_E_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(s->mu);
-    int rc = scan_check(s, sp, cp, true, scan);
+    int rc = scan_check(s, sp, cp, true, scan, src);
     if (rc != FPE_OK) return rc;
     ScanOp op{s, onDevice ? stream : s->own};
     rc = op.enter();
     if (rc != FPE_OK) return rc;
-    if (onDevice) return scan_clear_locked(s, sp, cp, scan, points, info, stream);
-    rc = scan_stage_points(s, scan, points);
+    if (onDevice) return scan_clear_locked(s, sp, cp, scan, src, info, stream);
+    ScanSource dev;
+    rc = scan_stage(s, scan, src, dev);
     if (rc != FPE_OK) return rc;
     fpe_scan_clear_info* dInfo = reinterpret_cast<fpe_scan_clear_info*>(s->acc + fpe::kScanAccWords + 16);
-    rc = scan_clear_locked(s, sp, cp, scan, s->pts, dInfo, s->own);
+    rc = scan_clear_locked(s, sp, cp, scan, dev, dInfo, s->own);
     if (rc != FPE_OK) return rc;
     fpe_scan_clear_info got;
     FPE_HIP(hipMemcpyAsync(&got, dInfo, sizeof(got), hipMemcpyDeviceToHost, s->own));
@@ -4291,16 +4356,16 @@ int scan_clear_common(fpe_scan_state* s, const fpe_scan_params* sp, const fpe_sc
 
 // fpe_scan_ingest* (withClear false: cp and clearInfo unused), fpe_scan_ingest_clear* (the clear between the move and the fuse) and
 // fpe_scan_ingest_closed* (withClose: behind the fuse the close of up to three rectangles into `closed`, which the patches then carry
-// in place of the state's own elevation; withClose false: kp and closeInfo unused)
+// in place of the state's own elevation; withClose false: kp and closeInfo unused); fpe_scan_ingest_image* is all three, by its cp and kp
 int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
-                       bool withClear, const fpe_scan_close_params* kp, bool withClose, const fpe_scan* scan, const float* points, const int32_t shift[2],
+                       bool withClear, const fpe_scan_close_params* kp, bool withClose, const fpe_scan* scan, const ScanSource& given, const int32_t shift[2],
                        const double position[2], fpe_scan_clear_info* clearInfo, fpe_scan_info* scanInfo, fpe_scan_close_info* closeInfo,
                        fpe_elevation_update_info* updateInfo, bool onDevice, hipStream_t stream) {
-    if (!h || !s || !points || !shift || !position) return fail(FPE_E_INVALID_ARG, "null argument");
+    if (!h || !s || !given.given() || !shift || !position) return fail(FPE_E_INVALID_ARG, "null argument");
     if (s->h != h) return fail(FPE_E_INVALID_ARG, "the scan state belongs to another engine");
     std::lock_guard<std::mutex> lk(s->mu);
     // every refusal ahead of the first queued operation
-    int rc = scan_check(s, sp, cp, withClear, scan);
+    int rc = scan_check(s, sp, cp, withClear, scan, given);
     if (rc != FPE_OK) return rc;
     int32_t rects[3][4];
     int nRects = 0;
@@ -4351,10 +4416,10 @@ int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params
     fpe_scan_info* dInfo = scanInfo;
     fpe_scan_clear_info* dClearInfo = clearInfo;
     fpe_scan_close_info* dCloseInfo = closeInfo;
+    ScanSource src = given;
     if (!onDevice) {
-        rc = scan_stage_points(s, scan, points);
+        rc = scan_stage(s, scan, given, src);
         if (rc != FPE_OK) return rc;
-        points = s->pts;
         dInfo = reinterpret_cast<fpe_scan_info*>(s->acc + fpe::kScanAccWords);
         dClearInfo = reinterpret_cast<fpe_scan_clear_info*>(s->acc + fpe::kScanAccWords + 16);
         if (withClose) dCloseInfo = reinterpret_cast<fpe_scan_close_info*>(s->closeAcc + fpe::kCloseAccInfo);
@@ -4365,10 +4430,10 @@ int scan_ingest_common(fpe_engine* h, fpe_scan_state* s, const fpe_filter_params
         patch();  // (the move swapped the buffers)
     }
     if (withClear) {
-        rc = scan_clear_locked(s, sp, cp, scan, points, dClearInfo, op.stream);
+        rc = scan_clear_locked(s, sp, cp, scan, src, dClearInfo, op.stream);
         if (rc != FPE_OK) return rc;
     }
-    rc = scan_fuse_locked(s, sp, scan, points, dInfo, op.stream);
+    rc = scan_fuse_locked(s, sp, scan, src, dInfo, op.stream);
     if (rc != FPE_OK) return rc;
     for (int k = 0; k < nRects; ++k) {  // (close_info describes the first rectangle; the strips write none)
         const int32_t* r = rects[k];
@@ -4483,11 +4548,11 @@ int fpe_scan_move(fpe_scan_handle s, const int32_t shift[2], const double positi
 }
 
 int fpe_scan_fuse(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const float* points, fpe_scan_info* info) {
-    return scan_fuse_common(s, sp, scan, points, info, false, nullptr);
+    return scan_fuse_common(s, sp, scan, ScanSource::of_points(points), info, false, nullptr);
 }
 
 int fpe_scan_fuse_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const float* d_points, fpe_scan_info* d_info, void* stream) {
-    return scan_fuse_common(s, sp, scan, d_points, d_info, true, static_cast<hipStream_t>(stream));
+    return scan_fuse_common(s, sp, scan, ScanSource::of_points(d_points), d_info, true, static_cast<hipStream_t>(stream));
 }
 
 int fpe_scan_install(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, void* stream) {
@@ -4512,36 +4577,36 @@ int fpe_scan_install(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* f
 
 int fpe_scan_ingest(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan, const float* points,
                     const int32_t shift[2], const double position[2], fpe_scan_info* scan_info, fpe_elevation_update_info* update_info) {
-    return scan_ingest_common(h, s, fp, sp, nullptr, false, nullptr, false, scan, points, shift, position, nullptr, scan_info, nullptr, update_info, false, nullptr);
+    return scan_ingest_common(h, s, fp, sp, nullptr, false, nullptr, false, scan, ScanSource::of_points(points), shift, position, nullptr, scan_info, nullptr, update_info, false, nullptr);
 }
 
 int fpe_scan_ingest_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan* scan,
                            const float* d_points, const int32_t shift[2], const double position[2], fpe_scan_info* d_scan_info,
                            fpe_elevation_update_info* update_info, void* stream) {
-    return scan_ingest_common(h, s, fp, sp, nullptr, false, nullptr, false, scan, d_points, shift, position, nullptr, d_scan_info, nullptr, update_info, true,
+    return scan_ingest_common(h, s, fp, sp, nullptr, false, nullptr, false, scan, ScanSource::of_points(d_points), shift, position, nullptr, d_scan_info, nullptr, update_info, true,
                               static_cast<hipStream_t>(stream));
 }
 
 int fpe_scan_clear(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* points,
                    fpe_scan_clear_info* info) {
-    return scan_clear_common(s, sp, cp, scan, points, info, false, nullptr);
+    return scan_clear_common(s, sp, cp, scan, ScanSource::of_points(points), info, false, nullptr);
 }
 
 int fpe_scan_clear_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const float* d_points,
                           fpe_scan_clear_info* d_info, void* stream) {
-    return scan_clear_common(s, sp, cp, scan, d_points, d_info, true, static_cast<hipStream_t>(stream));
+    return scan_clear_common(s, sp, cp, scan, ScanSource::of_points(d_points), d_info, true, static_cast<hipStream_t>(stream));
 }
 
 int fpe_scan_ingest_clear(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
                           const fpe_scan* scan, const float* points, const int32_t shift[2], const double position[2], fpe_scan_clear_info* clear_info,
                           fpe_scan_info* scan_info, fpe_elevation_update_info* update_info) {
-    return scan_ingest_common(h, s, fp, sp, cp, true, nullptr, false, scan, points, shift, position, clear_info, scan_info, nullptr, update_info, false, nullptr);
+    return scan_ingest_common(h, s, fp, sp, cp, true, nullptr, false, scan, ScanSource::of_points(points), shift, position, clear_info, scan_info, nullptr, update_info, false, nullptr);
 }
 
 int fpe_scan_ingest_clear_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
                                  const fpe_scan* scan, const float* d_points, const int32_t shift[2], const double position[2],
                                  fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info, fpe_elevation_update_info* update_info, void* stream) {
-    return scan_ingest_common(h, s, fp, sp, cp, true, nullptr, false, scan, d_points, shift, position, d_clear_info, d_scan_info, nullptr, update_info, true,
+    return scan_ingest_common(h, s, fp, sp, cp, true, nullptr, false, scan, ScanSource::of_points(d_points), shift, position, d_clear_info, d_scan_info, nullptr, update_info, true,
                               static_cast<hipStream_t>(stream));
 }
 
@@ -4586,7 +4651,7 @@ int fpe_scan_ingest_closed(fpe_handle h, fpe_scan_handle s, const fpe_filter_par
                            const fpe_scan_close_params* kp, const fpe_scan* scan, const float* points, const int32_t shift[2], const double position[2],
                            fpe_scan_clear_info* clear_info, fpe_scan_info* scan_info, fpe_scan_close_info* close_info,
                            fpe_elevation_update_info* update_info) {
-    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, true, scan, points, shift, position, clear_info, scan_info, close_info, update_info, false,
+    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, true, scan, ScanSource::of_points(points), shift, position, clear_info, scan_info, close_info, update_info, false,
                               nullptr);
 }
 
@@ -4594,8 +4659,45 @@ int fpe_scan_ingest_closed_device(fpe_handle h, fpe_scan_handle s, const fpe_fil
                                   const fpe_scan_close_params* kp, const fpe_scan* scan, const float* d_points, const int32_t shift[2],
                                   const double position[2], fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info,
                                   fpe_scan_close_info* d_close_info, fpe_elevation_update_info* update_info, void* stream) {
-    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, true, scan, d_points, shift, position, d_clear_info, d_scan_info, d_close_info,
+    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, true, scan, ScanSource::of_points(d_points), shift, position, d_clear_info, d_scan_info, d_close_info,
                               update_info, true, static_cast<hipStream_t>(stream));
+}
+
+// ---- the image forms (point 6 of the scan block): the same routines with an image as the point source ---------------------------
+int fpe_scan_fuse_image(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const fpe_scan_image* im, const void* image,
+                        fpe_scan_info* info) {
+    return scan_fuse_common(s, sp, scan, ScanSource::of_image(im, image), info, false, nullptr);
+}
+
+int fpe_scan_fuse_image_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan* scan, const fpe_scan_image* im, const void* d_image,
+                               fpe_scan_info* d_info, void* stream) {
+    return scan_fuse_common(s, sp, scan, ScanSource::of_image(im, d_image), d_info, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_clear_image(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const fpe_scan_image* im,
+                         const void* image, fpe_scan_clear_info* info) {
+    return scan_clear_common(s, sp, cp, scan, ScanSource::of_image(im, image), info, false, nullptr);
+}
+
+int fpe_scan_clear_image_device(fpe_scan_handle s, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan,
+                                const fpe_scan_image* im, const void* d_image, fpe_scan_clear_info* d_info, void* stream) {
+    return scan_clear_common(s, sp, cp, scan, ScanSource::of_image(im, d_image), d_info, true, static_cast<hipStream_t>(stream));
+}
+
+int fpe_scan_ingest_image(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                          const fpe_scan_close_params* kp, const fpe_scan* scan, const fpe_scan_image* im, const void* image, const int32_t shift[2],
+                          const double position[2], fpe_scan_clear_info* clear_info, fpe_scan_info* scan_info, fpe_scan_close_info* close_info,
+                          fpe_elevation_update_info* update_info) {
+    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, kp != nullptr, scan, ScanSource::of_image(im, image), shift, position, clear_info, scan_info,
+                              close_info, update_info, false, nullptr);
+}
+
+int fpe_scan_ingest_image_device(fpe_handle h, fpe_scan_handle s, const fpe_filter_params* fp, const fpe_scan_params* sp, const fpe_scan_clear_params* cp,
+                                 const fpe_scan_close_params* kp, const fpe_scan* scan, const fpe_scan_image* im, const void* d_image,
+                                 const int32_t shift[2], const double position[2], fpe_scan_clear_info* d_clear_info, fpe_scan_info* d_scan_info,
+                                 fpe_scan_close_info* d_close_info, fpe_elevation_update_info* update_info, void* stream) {
+    return scan_ingest_common(h, s, fp, sp, cp, cp != nullptr, kp, kp != nullptr, scan, ScanSource::of_image(im, d_image), shift, position, d_clear_info,
+                              d_scan_info, d_close_info, update_info, true, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 
 namespace fpe {
 
@@ -703,6 +704,58 @@ int fpe_scan_close_validate(const fpe_map_desc* geom, const fpe_scan_close_param
     return fpe::check_scan_close(geom->rows, geom->cols, kp, rect, &why);
 }
 
+int fpe_scan_image_validate(const fpe_map_desc* geom, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan,
+                            const fpe_scan_image* im) {
+    if (!geom) return FPE_E_INVALID_ARG;
+    const char* why = nullptr;
+    const int rc = fpe::check_map_geometry(geom->rows, geom->cols, geom->resolution, &why);
+    if (rc != FPE_OK) return rc;
+    return fpe::check_scan_image(geom->rows, geom->cols, sp, cp, scan, im, &why);
+}
+
+// The rule of point 6 of the scan block in plain C++: every operation is one f32 operation (this file is built without contraction).
+int fpe_scan_image_points(const fpe_scan_image* im, const void* image, float* out_xyz) {
+    const char* why = nullptr;
+    if (!image || !out_xyz || fpe::check_scan_image_desc(im, &why) != FPE_OK) return FPE_E_INVALID_ARG;
+    const int nr = fpe::scan_image_sel_rows(*im), nc = fpe::scan_image_sel_cols(*im);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (int ri = 0; ri < nr; ++ri) {
+        for (int ci = 0; ci < nc; ++ci) {
+            const int v = ri * im->row_step, u = ci * im->col_step;
+            const size_t k = static_cast<size_t>(v) * static_cast<size_t>(im->row_pitch) + static_cast<size_t>(u);
+            float* o = out_xyz + 3 * (static_cast<size_t>(ri) * nc + ci);
+            float d;
+            bool valid;
+            if (im->format == FPE_SCAN_DEPTH_U16) {
+                const uint16_t raw = static_cast<const uint16_t*>(image)[k];
+                valid = raw != 0;
+                d = static_cast<float>(raw) * im->depth_scale;
+            } else {
+                const float raw = static_cast<const float*>(image)[k];
+                valid = std::isfinite(raw) && raw > 0.0f;
+                d = raw * im->depth_scale;
+            }
+            if (!valid) {
+                o[0] = o[1] = o[2] = nan;
+            } else if (im->model == FPE_SCAN_IMAGE_PINHOLE) {
+                const float xn = (static_cast<float>(u) - im->cx) * d;
+                const float yn = (static_cast<float>(v) - im->cy) * d;
+                o[0] = xn / im->fx;
+                o[1] = yn / im->fy;
+                o[2] = d;
+            } else {
+                const float ce = im->row_dir[2 * v], se = im->row_dir[2 * v + 1];
+                const float ca = im->col_dir[2 * u], sa = im->col_dir[2 * u + 1];
+                const float w = d * ce;
+                o[0] = w * ca;
+                o[1] = w * sa;
+                o[2] = d * se;
+            }
+        }
+    }
+    return FPE_OK;
+}
+
 }  // extern "C"
 
 namespace fpe {
@@ -775,6 +828,7 @@ void scan_consts(const fpe_scan_params& sp, const fpe_scan& scan, const MapGeom&
     a.col0 = scan.roi[1];
     a.nr = scan.roi[2];
     a.nc = scan.roi[3];
+    a.im = ScanImage{};  // (the image forms set it)
 }
 
 void scan_clear_params_defaults(fpe_scan_clear_params& out) {
@@ -831,6 +885,59 @@ void scan_clear_consts(const fpe_scan_params& sp, const fpe_scan_clear_params& c
     a.col0 = f.col0;
     a.nr = f.nr;
     a.nc = f.nc;
+    a.im = f.im;
+}
+
+int check_scan_image_desc(const fpe_scan_image* im, const char** why) {
+    auto bad = [&](const char* msg) {
+        *why = msg;
+        return static_cast<int>(FPE_E_INVALID_ARG);
+    };
+    if (!im) return bad("null image descriptor");
+    if (im->model != FPE_SCAN_IMAGE_PINHOLE && im->model != FPE_SCAN_IMAGE_SPHERICAL) return bad("unknown image model");
+    if (im->format != FPE_SCAN_DEPTH_U16 && im->format != FPE_SCAN_DEPTH_F32) return bad("unknown depth format");
+    if (im->width < 1 || im->width > 4096 || im->height < 1 || im->height > 4096) return bad("image width or height outside 1 .. 4096");
+    if (im->row_pitch < im->width) return bad("row_pitch below width");
+    if (im->row_step < 1 || im->col_step < 1) return bad("row_step or col_step below 1");
+    if (!std::isfinite(im->depth_scale) || !(im->depth_scale > 0.0f)) return bad("depth_scale must be finite and positive");
+    if (im->model == FPE_SCAN_IMAGE_PINHOLE) {
+        if (!std::isfinite(im->fx) || !std::isfinite(im->fy) || im->fx == 0.0f || im->fy == 0.0f) return bad("fx and fy must be finite and not 0");
+        if (!std::isfinite(im->cx) || !std::isfinite(im->cy)) return bad("cx and cy must be finite");
+    } else if (!im->row_dir || !im->col_dir) {
+        return bad("a spherical image needs both direction tables");
+    }
+    if (im->reserved[0] != 0 || im->reserved[1] != 0) return bad("reserved must be 0");
+    if (static_cast<int64_t>(scan_image_sel_rows(*im)) * scan_image_sel_cols(*im) > FPE_SCAN_MAX_POINTS) return bad("more selected pixels than FPE_SCAN_MAX_POINTS");
+    return FPE_OK;
+}
+
+int check_scan_image(int rows, int cols, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const fpe_scan_image* im,
+                     const char** why) {
+    int rc = cp ? check_scan_clear(rows, cols, sp, cp, scan, why) : check_scan(rows, cols, sp, scan, why);
+    if (rc == FPE_OK) rc = check_scan_image_desc(im, why);
+    if (rc != FPE_OK) return rc;
+    if (scan->n_points != scan_image_sel_rows(*im) * scan_image_sel_cols(*im)) {
+        *why = "n_points is not the number of selected pixels";
+        return FPE_E_INVALID_ARG;
+    }
+    return FPE_OK;
+}
+
+void scan_image_consts(const fpe_scan_image& im, const void* d_image, const float* d_rowDir, const float* d_colDir, ScanImage& out) {
+    out.data = d_image;
+    out.rowDir = d_rowDir;
+    out.colDir = d_colDir;
+    out.model = im.model;
+    out.format = im.format;
+    out.pitch = im.row_pitch;
+    out.rowStep = im.row_step;
+    out.colStep = im.col_step;
+    out.selCols = scan_image_sel_cols(im);
+    out.scale = im.depth_scale;
+    out.fx = im.fx;
+    out.fy = im.fy;
+    out.cx = im.cx;
+    out.cy = im.cy;
 }
 
 void scan_close_params_defaults(fpe_scan_close_params& out) {

@@ -57,6 +57,15 @@ void scan_clear_params_defaults(fpe_scan_clear_params& out);
 // The refusals of fpe_scan_close* for a state of rows x cols cells: the parameters' ranges, then the rectangle.
 int check_scan_close(int rows, int cols, const fpe_scan_close_params* kp, const int32_t rect[4], const char** why);
 void scan_close_params_defaults(fpe_scan_close_params& out);
+// The refusals of the image forms (point 6 of the scan block): check_scan's (check_scan_clear's when cp is given), then the
+// descriptor's, then scan->n_points against the selected pixels.
+int check_scan_image(int rows, int cols, const fpe_scan_params* sp, const fpe_scan_clear_params* cp, const fpe_scan* scan, const fpe_scan_image* im,
+                     const char** why);
+// The descriptor's own refusals (everything of the list that needs neither the state nor the scan)
+int check_scan_image_desc(const fpe_scan_image* im, const char** why);
+// The selected rows and columns of a valid descriptor.
+inline int scan_image_sel_rows(const fpe_scan_image& im) { return (im.height - 1) / im.row_step + 1; }
+inline int scan_image_sel_cols(const fpe_scan_image& im) { return (im.width - 1) / im.col_step + 1; }
 
 // ---- the producer's filter chain (fpe_filters.hpp): its host arithmetic — filter_route and friends are declared in fpe_launch.hpp ----
 void filter_params_defaults(fpe_filter_params& out);

@@ -2301,6 +2301,8 @@ hipError_t launch_canonicalise(const float* d_src, float* d_dst, int rows, int c
 #include "fpe_scan_clear.hpp"
 // ---- part eighteen: scan gap closing (fpe_scan_close*; a pure function of a state's elevation layer) --------------------------
 #include "fpe_scan_close.hpp"
+// ---- part nineteen: the image forms of the scan entry points (fpe_scan_*_image*; a pixel is a point in registers) ------------
+#include "fpe_scan_image.hpp"
 
 hipError_t set_max_lds(size_t planBytes, size_t searchBytes) {
     const hipError_t ep = set_max_lds_plan(planBytes);  // every direct plan instantiation, from their own list (fpe_plan_launch.hpp)

@@ -489,6 +489,18 @@ constexpr uint32_t kScanNoCell = 0xFFFFFFFFu;  // the record of a dropped point
 // scan_fuse_kernel takes the totals out with atomic exchanges that put the rest values back, and writes the caller's info.
 constexpr int kScanAccWords = 32;
 constexpr int kScanTicket = 16;
+// The point source of the image forms (fpe_scan_*_image*; fpe_scan_image.hpp), by value at the END of both argument blocks: the
+// descriptor's fields with device addresses.  data == null: the call's points are `points` with `stride`.
+struct ScanImage {
+    const void* data;      // uint16 or float elements
+    const float* rowDir;   // spherical: height x {cos e, sin e}
+    const float* colDir;   // spherical: width x {cos a, sin a}
+    int32_t model, format;
+    int32_t pitch;         // elements between rows
+    int32_t rowStep, colStep;
+    int32_t selCols;       // selected columns: ceil(width / colStep); the point ordinal is ri * selCols + ci
+    float scale, fx, fy, cx, cy;
+};
 // The argument block of the three passes, by value: the contract's constants formed once on the host (the squares and widenings of
 // include/fpe.h), the state's geometry, the roi and the buffers.
 struct ScanArgs {
@@ -507,13 +519,19 @@ struct ScanArgs {
     uint32_t* elev;   // the state's layers, as 32-bit patterns
     uint32_t* var;
     int32_t* info;    // the caller's fpe_scan_info (device), or null
+    ScanImage im;     // the image forms' point source (data null: `points`)
 };
 void scan_consts(const fpe_scan_params& sp, const fpe_scan& scan, const MapGeom& g, ScanArgs& a);  // fpe_host.cpp
+// The descriptor as the kernels take it, with the three device addresses (fpe_host.cpp)
+void scan_image_consts(const fpe_scan_image& im, const void* d_image, const float* d_rowDir, const float* d_colDir, ScanImage& out);
 // The three passes of a fuse on `stream`, and each alone.  merge: the merged form of the two point passes.
 hipError_t launch_scan_fuse(const ScanArgs& a, bool merge, hipStream_t stream);
 hipError_t launch_scan_top(const ScanArgs& a, bool merge, hipStream_t stream);
 hipError_t launch_scan_sum(const ScanArgs& a, bool merge, hipStream_t stream);
 hipError_t launch_scan_cells(const ScanArgs& a, hipStream_t stream);
+// The image forms' fuse (a.im.data set; fpe_scan_image.hpp): scan_top_image_kernel, then the merged sum pass and the cell pass.
+hipError_t launch_scan_fuse_image(const ScanArgs& a, hipStream_t stream);
+hipError_t launch_scan_top_image(const ScanArgs& a, hipStream_t stream);
 // every cell's scratch and the accumulators to their rest values (create)
 hipError_t launch_scan_reset(ScanCell* cells, size_t n, int32_t* acc, hipStream_t stream);
 // new (i, j) = old (i + sr, j + sc) of both layers, or the cleared value (|sr| <= rows, |sc| <= cols: clamped by the caller)
@@ -546,12 +564,15 @@ struct ScanClearArgs {
     uint32_t* elev;
     uint32_t* var;
     int32_t* info;  // the caller's fpe_scan_clear_info (device) as sixteen words, or null
+    ScanImage im;   // the image forms' point source (data null: `points`)
 };
 void scan_clear_consts(const fpe_scan_params& sp, const fpe_scan_clear_params& cp, const fpe_scan& scan, const MapGeom& g, ScanClearArgs& a);  // fpe_host.cpp
 // The ray pass (form 1: one lane per ray; 2: `group` = 16, 32 or 64 adjacent lanes per ray) and the cell pass on `stream`.
 hipError_t launch_scan_clear(const ScanClearArgs& a, int form, int group, hipStream_t stream);
 hipError_t launch_scan_clear_rays(const ScanClearArgs& a, int form, int group, hipStream_t stream);
 hipError_t launch_scan_clear_cells(const ScanClearArgs& a, hipStream_t stream);
+// The image forms' clear (a.im.data set; fpe_scan_image.hpp): the same ray kernels with the pixel source, then the cell pass.
+hipError_t launch_scan_clear_image(const ScanClearArgs& a, int form, int group, hipStream_t stream);
 
 // ---- scan gap closing (fpe_scan_close.hpp) ---------------------------------------------------------------------
 // The close has an accumulator block of its own (allocated with the state's `closed` layer, reset there): words 0-4 count the known,

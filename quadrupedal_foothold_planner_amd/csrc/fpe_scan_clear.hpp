@@ -8,7 +8,9 @@
 //   ray pass     every point that casts a ray (i % ray_stride == 0) is classified by the fuse's tests 1-4; a ray's samples
 //                k = start .. K - end - 1 are placed by the contract's rule in f64 (t = k / K by a true division, each product and sum
 //                rounded on its own).  x and y are monotone in k, so the samples of a ray that fall into one cell are consecutive: a
-//                RUN.  A run with at least one violating sample issues ONE atomicAdd on the cell's hits.  Two forms, same results:
+//                RUN.  A run with at least one violating sample issues ONE atomicAdd on the cell's hits.  Two forms, same results, each
+//                with the point source as a template parameter (ClearPointSource here: the call's points; fpe_scan_image.hpp's
+//                ClearImageSource: a pixel); clear_ray_of is everything from the point where a ray has its x, y, z:
 //       scan_clear_rays_lane_kernel      one lane per ray, looping over its samples; the current cell and a violated flag in
 //                                        registers, the atomic when the cell changes.
 //       scan_clear_rays_group_kernel<G>  G = 16, 32 or 64 adjacent lanes per ray, a chunk of G samples per step.  Runs are found as
@@ -33,12 +35,9 @@ struct ClearRay {
     double dx, dy, dz;
 };
 
-__device__ __forceinline__ ClearRay clear_ray(const ScanClearArgs& a, int c) {
-    ClearRay r{0, 0, 0, 0, 0.0, 0.0, 0.0};
-    if (c >= a.nCast) return r;
-    const float* s = a.points + static_cast<size_t>(c) * static_cast<size_t>(a.rayStride) * static_cast<size_t>(a.stride);
-    const float x = s[0], y = s[1], z = s[2];
-    r.cls = 1;
+// The ray of a point that is cast, from the point where it has x, y, z (sensor frame): the fuse's tests 1-4, then the sample range.
+__device__ __forceinline__ ClearRay clear_ray_of(const ScanClearArgs& a, float x, float y, float z) {
+    ClearRay r{1, 0, 0, 0, 0.0, 0.0, 0.0};
     if (!(__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z))) return r;
     const double xs = x, ys = y, zs = z;
     const double r2 = (xs * xs + ys * ys) + zs * zs;
@@ -58,6 +57,26 @@ __device__ __forceinline__ ClearRay clear_ray(const ScanClearArgs& a, int c) {
     r.k1 = r.K - a.endSamples;
     r.cls = r.k0 < r.k1 ? 4 : 3;
     return r;
+}
+
+// The point source of the ray kernels (their template parameter): the x, y, z of point ordinal i.  This one reads the call's points;
+// the image forms' source is fpe_scan_image.hpp's.
+struct ClearPointSource {
+    static __device__ __forceinline__ void xyz(const ScanClearArgs& a, int i, float& x, float& y, float& z) {
+        const float* s = a.points + static_cast<size_t>(i) * static_cast<size_t>(a.stride);
+        x = s[0];
+        y = s[1];
+        z = s[2];
+    }
+};
+
+// Cast point c (ordinal c * ray_stride) as a ray.
+template <class Source>
+__device__ __forceinline__ ClearRay clear_ray(const ScanClearArgs& a, int c) {
+    if (c >= a.nCast) return ClearRay{0, 0, 0, 0, 0.0, 0.0, 0.0};
+    float x, y, z;
+    Source::xyz(a, c * a.rayStride, x, y, z);  // (below n <= FPE_SCAN_MAX_POINTS)
+    return clear_ray_of(a, x, y, z);
 }
 
 // Sample k of a walked ray: its local cell in the roi (kScanNoCell: not inside) and whether it violates that cell.
@@ -115,11 +134,12 @@ __device__ __forceinline__ void clear_block_counts(const ScanClearArgs& a, int32
     }
 }
 
+template <class Source>
 __global__ __launch_bounds__(kScanBlock) void scan_clear_rays_lane_kernel(ScanClearArgs a) {
     __shared__ int32_t sCnt[6];
     if (threadIdx.x < 6) sCnt[threadIdx.x] = 0;
     __syncthreads();
-    const ClearRay r = clear_ray(a, static_cast<int>(blockIdx.x) * kScanBlock + static_cast<int>(threadIdx.x));
+    const ClearRay r = clear_ray<Source>(a, static_cast<int>(blockIdx.x) * kScanBlock + static_cast<int>(threadIdx.x));
     int32_t nIn = 0, nPairs = 0;
     if (r.cls == 4) {
         uint32_t cur = kScanNoCell;
@@ -147,7 +167,7 @@ __global__ __launch_bounds__(kScanBlock) void scan_clear_rays_lane_kernel(ScanCl
     clear_block_counts(a, sCnt, true, r.cls, nIn, nPairs);
 }
 
-template <int G>
+template <int G, class Source>
 __global__ __launch_bounds__(kScanBlock) void scan_clear_rays_group_kernel(ScanClearArgs a) {
     static_assert(G == 16 || G == 32 || G == 64, "a group is a power-of-two part of a wavefront");
     __shared__ int32_t sCnt[6];
@@ -159,7 +179,7 @@ __global__ __launch_bounds__(kScanBlock) void scan_clear_rays_group_kernel(ScanC
     const int end = first + G;
     const unsigned long long below = (1ull << lane) - 1ull;  // the lanes below this one
     const unsigned long long group = (G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull) << first;
-    const ClearRay r = clear_ray(a, static_cast<int>(blockIdx.x) * (kScanBlock / G) + static_cast<int>(threadIdx.x) / G);
+    const ClearRay r = clear_ray<Source>(a, static_cast<int>(blockIdx.x) * (kScanBlock / G) + static_cast<int>(threadIdx.x) / G);
     const int k1 = r.cls == 4 ? r.k1 : 0;
     uint32_t carryCell = kScanNoCell;  // the run that reached the last chunk's end (the same in every lane of the group)
     bool carryFlag = false;            // (set only while carryCell is a cell)
@@ -274,21 +294,27 @@ __global__ __launch_bounds__(kScanBlock) void scan_clear_cells_kernel(ScanClearA
     }
 }
 
-}  // namespace
-
-hipError_t launch_scan_clear_rays(const ScanClearArgs& a, int form, int group, hipStream_t stream) {
+// The ray pass of either point source.
+template <class Source>
+hipError_t clear_rays_launch(const ScanClearArgs& a, int form, int group, hipStream_t stream) {
     if (a.nCast <= 0) return hipSuccess;
     const size_t n = static_cast<size_t>(a.nCast);
     if (form == 1) {
-        hipLaunchKernelGGL(scan_clear_rays_lane_kernel, dim3(scan_blocks(n)), dim3(kScanBlock), 0, stream, a);
+        hipLaunchKernelGGL(scan_clear_rays_lane_kernel<Source>, dim3(scan_blocks(n)), dim3(kScanBlock), 0, stream, a);
     } else if (group == 16) {
-        hipLaunchKernelGGL(scan_clear_rays_group_kernel<16>, dim3(scan_blocks(n * 16)), dim3(kScanBlock), 0, stream, a);
+        hipLaunchKernelGGL((scan_clear_rays_group_kernel<16, Source>), dim3(scan_blocks(n * 16)), dim3(kScanBlock), 0, stream, a);
     } else if (group == 32) {
-        hipLaunchKernelGGL(scan_clear_rays_group_kernel<32>, dim3(scan_blocks(n * 32)), dim3(kScanBlock), 0, stream, a);
+        hipLaunchKernelGGL((scan_clear_rays_group_kernel<32, Source>), dim3(scan_blocks(n * 32)), dim3(kScanBlock), 0, stream, a);
     } else {
-        hipLaunchKernelGGL(scan_clear_rays_group_kernel<64>, dim3(scan_blocks(n * 64)), dim3(kScanBlock), 0, stream, a);
+        hipLaunchKernelGGL((scan_clear_rays_group_kernel<64, Source>), dim3(scan_blocks(n * 64)), dim3(kScanBlock), 0, stream, a);
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_scan_clear_rays(const ScanClearArgs& a, int form, int group, hipStream_t stream) {
+    return clear_rays_launch<ClearPointSource>(a, form, group, stream);
 }
 
 // (runs for n == 0 too: it writes the caller's info)

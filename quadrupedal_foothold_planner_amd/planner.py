@@ -358,6 +358,61 @@ def scan_close_params(**overrides):
     return kp
 
 
+def make_scan_image(model, format, width, height, row_pitch=None, row_step=1, col_step=1, depth_scale=1.0, fx=1.0, fy=1.0, cx=0.0, cy=0.0,
+                    row_dir=None, col_dir=None):
+    """An fpe_scan_image.  model: "pinhole" / "spherical" (or the constant); format: "u16" / "f32".  row_dir / col_dir (spherical): a
+    float32 array of (height, 2) / (width, 2) {cos, sin} for the host forms (kept alive by the descriptor), or a device address."""
+    im = _capi.ScanImage()
+    im.model = {"pinhole": _capi.SCAN_IMAGE_PINHOLE, "spherical": _capi.SCAN_IMAGE_SPHERICAL}.get(model, model)
+    im.format = {"u16": _capi.SCAN_DEPTH_U16, "f32": _capi.SCAN_DEPTH_F32}.get(format, format)
+    im.width, im.height = int(width), int(height)
+    im.row_pitch = int(width if row_pitch is None else row_pitch)
+    im.row_step, im.col_step = int(row_step), int(col_step)
+    im.depth_scale, im.fx, im.fy, im.cx, im.cy = (float(x) for x in (depth_scale, fx, fy, cx, cy))
+    keep = []
+    for name, table in (("row_dir", row_dir), ("col_dir", col_dir)):
+        if table is None or isinstance(table, int):
+            setattr(im, name, table or None)
+        else:
+            t = np.ascontiguousarray(table, dtype=np.float32)
+            keep.append(t)
+            setattr(im, name, t.ctypes.data)
+    im._keep = keep
+    return im
+
+
+def scan_image_selected(im):
+    """(selected rows, selected columns) of a descriptor: n_sel is their product."""
+    return -(-im.height // im.row_step), -(-im.width // im.col_step)
+
+
+def scan_image_validate(rows, cols, resolution, params, clear_params, scan, im):
+    """fpe_scan_image_validate (host arithmetic, no engine): the status an image form would be refused with, or FPE_OK.  Any of the
+    four may be None (clear_params None: the fuse's refusals alone)."""
+    d = _map_desc(rows, cols, resolution)
+    ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+    return _capi.lib().fpe_scan_image_validate(C.byref(d), ref(params), ref(clear_params), ref(scan), ref(im))
+
+
+def _image(image, im):
+    """The host image as the library reads it: uint16 or float32 elements, at least (height - 1) * row_pitch + width of them."""
+    a = np.ascontiguousarray(image, dtype=np.uint16 if im.format == _capi.SCAN_DEPTH_U16 else np.float32)
+    if a.size < (im.height - 1) * im.row_pitch + im.width:
+        raise ValueError("fewer elements than (height - 1) * row_pitch + width")
+    return a
+
+
+def scan_image_points(im, image):
+    """fpe_scan_image_points (host only): the (n_sel, 3) float32 points of the image by the contract's rule."""
+    a = _image(image, im)
+    nr, nc = scan_image_selected(im)
+    out = np.empty((nr * nc, 3), np.float32)
+    rc = _capi.lib().fpe_scan_image_points(C.byref(im), ptr(a), ptr(out))
+    if rc != _capi.FPE_OK:
+        raise FpeError(rc, "fpe_scan_image_points refused the descriptor")
+    return out
+
+
 def _rect(rect):
     return None if rect is None else (C.c_int32 * 4)(*(int(x) for x in rect))
 
@@ -1544,6 +1599,67 @@ class ScanState:
                                                             C.c_void_p(d_points_ptr), sh, pos, C.c_void_p(d_clear_info_ptr or 0),
                                                             C.c_void_p(d_info_ptr or 0), C.c_void_p(d_close_info_ptr or 0), C.byref(ui),
                                                             C.c_void_p(stream or 0)))
+        return _info_dict(ui)
+
+    # ---- scan images: a depth or range image as the point source, without a point cloud (fpe_scan_*_image*) --------------
+    # `scan.n_points` is the number of selected pixels (scan_image_selected); `im` comes from make_scan_image.
+    image_points = staticmethod(scan_image_points)
+
+    def fuse_image(self, scan, im, image, params=None):
+        """fpe_scan_fuse_image: a host image (and host tables) -> the call's info as a SCAN_INFO_DTYPE record.  Synchronous."""
+        a = _image(image, im)
+        info = np.zeros(1, _capi.SCAN_INFO_DTYPE)
+        self._check(self._lib.fpe_scan_fuse_image(self._s, C.byref(params if params is not None else scan_params()), C.byref(scan), C.byref(im), ptr(a),
+                                                  ptr(info)))
+        return info[0]
+
+    def fuse_image_device(self, scan, im, d_image_ptr, params=None, d_info_ptr=0, stream=None):
+        """fpe_scan_fuse_image_device: a device image (the descriptor's tables are device addresses), a device info of sixteen int32
+        (0: not wanted); asynchronous on `stream`."""
+        self._check(self._lib.fpe_scan_fuse_image_device(self._s, C.byref(params if params is not None else scan_params()), C.byref(scan), C.byref(im),
+                                                         C.c_void_p(d_image_ptr), C.c_void_p(d_info_ptr or 0), C.c_void_p(stream or 0)))
+
+    def clear_image(self, scan, im, image, params=None, clear_params=None):
+        """fpe_scan_clear_image: a host image -> the call's info as a SCAN_CLEAR_INFO_DTYPE record.  Synchronous."""
+        a = _image(image, im)
+        info = np.zeros(1, _capi.SCAN_CLEAR_INFO_DTYPE)
+        self._check(self._lib.fpe_scan_clear_image(self._s, C.byref(params if params is not None else scan_params()),
+                                                   C.byref(clear_params if clear_params is not None else scan_clear_params()), C.byref(scan),
+                                                   C.byref(im), ptr(a), ptr(info)))
+        return info[0]
+
+    def clear_image_device(self, scan, im, d_image_ptr, params=None, clear_params=None, d_info_ptr=0, stream=None):
+        """fpe_scan_clear_image_device: a device image, a device info of 64 bytes (0: not wanted); asynchronous on `stream`."""
+        self._check(self._lib.fpe_scan_clear_image_device(self._s, C.byref(params if params is not None else scan_params()),
+                                                          C.byref(clear_params if clear_params is not None else scan_clear_params()), C.byref(scan),
+                                                          C.byref(im), C.c_void_p(d_image_ptr), C.c_void_p(d_info_ptr or 0), C.c_void_p(stream or 0)))
+
+    def ingest_image(self, scan, im, image, shift, position, params=None, clear_params=None, close_params=None, filter_params=None):
+        """fpe_scan_ingest_image: ingest (neither clear_params nor close_params), ingest_clear (clear_params) or ingest_closed
+        (close_params, with or without clear_params) of a host image -> (clear info record or None, scan info record, close info
+        record or None, update info dict).  Synchronous."""
+        a = _image(image, im)
+        sh, pos = self._move_args(shift, position)
+        cinfo, info, kinfo = np.zeros(1, _capi.SCAN_CLEAR_INFO_DTYPE), np.zeros(1, _capi.SCAN_INFO_DTYPE), np.zeros(1, _capi.SCAN_CLOSE_INFO_DTYPE)
+        ui = _capi.ElevationUpdateInfo()
+        ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+        self._check(self._lib.fpe_scan_ingest_image(self._planner._h, self._s, ref(filter_params), C.byref(params if params is not None else scan_params()),
+                                                    ref(clear_params), ref(close_params), C.byref(scan), C.byref(im), ptr(a), sh, pos, ptr(cinfo),
+                                                    ptr(info), ptr(kinfo), C.byref(ui)))
+        return (cinfo[0] if clear_params is not None else None), info[0], (kinfo[0] if close_params is not None else None), _info_dict(ui)
+
+    def ingest_image_device(self, scan, im, d_image_ptr, shift, position, params=None, clear_params=None, close_params=None, filter_params=None,
+                            d_clear_info_ptr=0, d_info_ptr=0, d_close_info_ptr=0, stream=None):
+        """fpe_scan_ingest_image_device: the same with a device image and device infos (0: not wanted), asynchronous on `stream` ->
+        the update info dict."""
+        sh, pos = self._move_args(shift, position)
+        ui = _capi.ElevationUpdateInfo()
+        ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+        self._check(self._lib.fpe_scan_ingest_image_device(self._planner._h, self._s, ref(filter_params),
+                                                           C.byref(params if params is not None else scan_params()), ref(clear_params),
+                                                           ref(close_params), C.byref(scan), C.byref(im), C.c_void_p(d_image_ptr), sh, pos,
+                                                           C.c_void_p(d_clear_info_ptr or 0), C.c_void_p(d_info_ptr or 0),
+                                                           C.c_void_p(d_close_info_ptr or 0), C.byref(ui), C.c_void_p(stream or 0)))
         return _info_dict(ui)
 
 
